@@ -14,7 +14,11 @@ shard and its own sampler stream (seed + rank, train.py:36); per step the gradie
 (SUM, utils.py:47) between backward and Adam, per cycle the normalizer statistics are all-reduced
 (mean, normalizer.py:60-64).  Weak scaling: global batch = N x 256.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else the line
+has carried: the CPU baseline, the per-kernel profile and roofline, the calibration probes, the cycle-inclusive estimate
+of a short timed region and, at N > 1, the replica fingerprints, device ids and the timed pass over the other exchanges.
 """
 from __future__ import annotations
 
@@ -55,10 +59,17 @@ def parse():
                          "processes (rl_arm_under_sparse_reward_amd/feeder.py) on the snapshot policy while the cycles run; "
                          "every finished wave is stored into the shard by DMA out of the shared ring (not the default line)")
     ap.add_argument("--feeder-workers", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement and check the line has carried (see the module doc)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: leave out the per-kernel profile and roofline")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step left to its caller as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 class Runner:
@@ -198,6 +209,31 @@ def barrier(world):
         import torch.distributed as dist
 
         dist.barrier()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, r: Runner):
+    """--dump-outputs: what the timed path hands its caller after its last step -- that step's (actor, critic) losses, the
+    four networks and the two normalizers' statistics -- one DIR/<name>.npy each.  The inputs (episodes, initial networks,
+    sampler stream) are seeded, so two builds run with the same arguments can be compared file for file."""
+    from rl_arm_under_sparse_reward_amd.ddpg_agent import NET_ACTOR, NET_ACTOR_TARGET, NET_CRITIC, NET_CRITIC_TARGET
+
+    ag = r.agent
+    arrays = {"losses_last_step": ag.last_losses(1)[0],
+              "actor_params": ag._get_flat(NET_ACTOR), "critic_params": ag._get_flat(NET_CRITIC),
+              "actor_target_params": ag._get_flat(NET_ACTOR_TARGET), "critic_target_params": ag._get_flat(NET_CRITIC_TARGET),
+              "o_norm_mean": ag.o_norm.mean, "o_norm_std": ag.o_norm.std,
+              "g_norm_mean": ag.g_norm.mean, "g_norm_std": ag.g_norm.std}
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    assert all(v.dtype in (np.float32, np.float64) for v in arrays.values()), {k: v.dtype for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"bench: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def profile_kernels(r: Runner, cycles=3):
@@ -617,6 +653,8 @@ def main():
                         "store": "hp_buffer_store_pinned: DMA out of the device-registered shared-memory ring",
                         "env": "synthetic.PointMassGoalEnv (PyBullet is absent from the box)"}
         r.env_feeder.close()
+    if a.dump_outputs and rank == 0:      # data-parallel replicas hold the same networks: rank 0 writes for all of them
+        dump_outputs(a.dump_outputs, r)
     # cycle-boundary work inside the timed region: [store 2 episodes + normalizer refresh, polyak]; a steady state has
     # one of each per 40 steps
     boundaries = {"store_and_normalizer": r.opens - opens0, "polyak": r.closes - closes0,
@@ -630,9 +668,9 @@ def main():
         dt = float(t.item())
     # A timed region shorter than one training cycle (the driver's --steps 20) crosses no cycle boundary: measure the
     # boundary-inclusive rate as well, over whole cycles (store 2 episodes, normalizer refresh, 40 updates, polyak each),
-    # after the timed region so that the contract's K steps stay exactly K
+    # after the timed region so that the contract's K steps stay exactly K (--full)
     cycle_inclusive = None
-    if boundaries["polyak"] < max(1, a.steps // N_BATCHES) or a.steps < N_BATCHES:
+    if a.full and (boundaries["polyak"] < max(1, a.steps // N_BATCHES) or a.steps < N_BATCHES):
         n_cyc = 25
         r.run_steps((-r.in_cycle) % N_BATCHES)
         r.run_steps(2 * N_BATCHES)
@@ -658,7 +696,7 @@ def main():
     # fingerprints its online + target parameters and rank 0 reports whether all fingerprints agree
     replicas_same = None
     devices = None
-    if world > 1:
+    if world > 1 and a.full:
         replicas_same = replicas_identical(r, world, shared)
         # "N ranks on N devices" belongs in the record: every rank's PCI bus id, and how many ranks the exchange itself counts
         import ctypes as _C0
@@ -677,7 +715,7 @@ def main():
     # What ran, asked WHILE the transport that carried the timed region is still attached (VERDICT r05 Weak 3: asked after
     # close_comm() the agent is single-rank again and names kernels a data-parallel rank never launches): the engine, the
     # kernels of one update read off the library's own launch logic (hp_agent_update_kernels), the exchange.
-    eng = r.agent.engine()
+    eng = r.agent.engine() if a.full else None
     ran = exchange_name(r.agent) if dp else None
     dp_native = r.agent._native_comm is not None
     dp_peer = r.agent._peer is not None
@@ -689,7 +727,7 @@ def main():
     # live per-launch durations (HIP event pairs on the launch stream).  At N > 1 every rank runs the pass -- its launches
     # exchange with the peers' -- and rank 0 reports its own figures.
     prof = None
-    if not a.no_profile:
+    if a.full and not a.no_profile:
         try:
             prof = profile_kernels(r)
             r.agent.check_exchange()
@@ -704,16 +742,23 @@ def main():
     if rank == 0:
         import ctypes as C
         from rl_arm_under_sparse_reward_amd import _lib as _l
-        mhz = C.c_double()
-        _l.check(r.ctx.lib.hp_ctx_clock_mhz(r.ctx.h, C.byref(mhz)))      # shader clock right after the timed region
-        cal = (C.c_double * 4)()
-        try:
-            _l.check(r.ctx.lib.hp_ctx_calibrate(r.ctx.h, cal))
-            calibration = {"launch_floor_us": round(cal[0], 3), "lds_dma_GBps_per_cu": round(cal[1], 1),
-                           "mfma4x4_dependent_cycles": round(cal[2], 2), "shader_clock_mhz": round(cal[3]),
-                           "typical": CALIBRATION_TYPICAL}
-        except Exception as e:        # noqa: BLE001 -- a diagnostic must not cost the run its line
-            calibration = {"error": str(e)}
+        diagnostics, full_config = {}, {}
+        if a.full:
+            mhz = C.c_double()
+            _l.check(r.ctx.lib.hp_ctx_clock_mhz(r.ctx.h, C.byref(mhz)))      # shader clock right after the timed region
+            cal = (C.c_double * 4)()
+            try:
+                _l.check(r.ctx.lib.hp_ctx_calibrate(r.ctx.h, cal))
+                calibration = {"launch_floor_us": round(cal[0], 3), "lds_dma_GBps_per_cu": round(cal[1], 1),
+                               "mfma4x4_dependent_cycles": round(cal[2], 2), "shader_clock_mhz": round(cal[3]),
+                               "typical": CALIBRATION_TYPICAL}
+            except Exception as e:        # noqa: BLE001 -- a diagnostic must not cost the run its line
+                calibration = {"error": str(e)}
+            full_config = {"engine": eng, "shader_clock_mhz_after_run": round(mhz.value)}
+            # ~200 us of probes that characterise THIS box (rlarm_hip_debug.h: hp_ctx_calibrate), taken right after the timed
+            # region: about one box in seven of the pool ran every kernel of this path ~1.4 x slower at the same shader clock --
+            # with these three rates in the line a slow box can be told from a regression
+            diagnostics = {"calibration": calibration}
         out = {
             "metric": baseline_metric_name(a),
             "value": round(value, 1), "unit": "transitions/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -740,21 +785,16 @@ def main():
                                               2: "two-phase (reduce-scatter + all-gather over peer memory)"}.get(peer_phases),
                        "cycle_mode": cycle_mode,
                        "peer_gate_kernels": bool(r.agent.comm.shared_device) if dp_peer else None,
-                       "replicas_bit_identical": replicas_same,
-                       "devices": devices,
+                       **({"replicas_bit_identical": replicas_same, "devices": devices} if world > 1 and a.full else {}),
                        "devices_shared_by_ranks": bool(shared) if world > 1 else None,
-                       "engine": eng,
                        "sampler_rng": "MT19937 numpy-legacy stream on device (bit-exact indices)",
                        "final_losses": [float(losses[0]), float(losses[1])],
-                       "shader_clock_mhz_after_run": round(mhz.value)},
-            # ~200 us of probes that characterise THIS box (rlarm_hip_debug.h: hp_ctx_calibrate), taken right after the timed region:
-            # about one box in seven of the pool ran every kernel of this path ~1.4 x slower at the same shader clock -- with these
-            # three rates in the line a slow box can be told from a regression
-            "calibration": calibration,
+                       **full_config},
+            **diagnostics,
         }
         if prof:
             out.update(roofline_fields(a, r, eng, prof, ms_per_step, world, dp, ran))
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(a, a.cpu_seconds)
             out["speedup_vs_cpu_baseline"] = round(value / out["cpu_baseline"]["value"], 1)
             # the port timed next to the imported reference where both can run (the build container,
@@ -781,7 +821,7 @@ def main():
 
     if dp:
         r.agent.close_comm()
-    if world > 1 and os.environ.get("RLARM_BENCH_ALTERNATIVES", "1") != "0":
+    if world > 1 and a.full and os.environ.get("RLARM_BENCH_ALTERNATIVES", "1") != "0":
         # The headline record is COMPLETE at this point.  The extra passes run against a time box, under a watchdog: if one of
         # them hangs (a rank died inside a collective) the watchdog prints the line with the passes that finished and
         # ends the process with status 0 -- on every rank, rank 0 first -- instead of losing what may be the only multi-GPU run.

@@ -3,6 +3,11 @@
 import glob
 import importlib.util
 import os
+import sys
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 spec = importlib.util.spec_from_file_location("bench_module", os.path.join(REPO, "bench.py"))
@@ -39,3 +44,37 @@ def test_committed_summaries_parse_and_carry_a_fingerprint():
 
 def test_missing_summary_is_empty_not_an_error():
     assert bench.committed_kernel_averages(os.path.join(REPO, "profiles", "no_such_file.txt")) == ({}, None)
+
+
+def test_plain_run_is_the_default_and_steps_are_checked(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "5", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def _fake_runner(n_params):
+    norm = SimpleNamespace(mean=np.zeros(3, np.float32), std=np.ones(3, np.float64))
+    agent = SimpleNamespace(last_losses=lambda n: np.arange(2 * n, dtype=np.float32).reshape(n, 2),
+                            _get_flat=lambda slot: np.full(n_params, slot, np.float32), o_norm=norm, g_norm=norm)
+    return SimpleNamespace(agent=agent)
+
+
+def test_dump_outputs_writes_one_float_npy_per_array(tmp_path):
+    bench.dump_outputs(str(tmp_path / "out"), _fake_runner(5))
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert set(got) == {"losses_last_step", "actor_params", "critic_params", "actor_target_params", "critic_target_params",
+                        "o_norm_mean", "o_norm_std", "g_norm_mean", "g_norm_std"}
+    assert got["losses_last_step"].tolist() == [0.0, 1.0] and got["critic_target_params"].tolist() == [3.0] * 5
+    assert got["o_norm_std"].dtype == np.float64 and got["actor_params"].dtype == np.float32
+
+
+def test_dump_outputs_refuses_more_than_64_mb(tmp_path):
+    with pytest.raises(RuntimeError, match="more than"):
+        bench.dump_outputs(str(tmp_path / "out"), _fake_runner(5 << 20))
+    assert not (tmp_path / "out").exists()

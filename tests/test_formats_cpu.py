@@ -3,13 +3,11 @@
   tests/golden/ref_checkpoint_probe.npz     what the reference's reader (demo_push.py:15-22 + models.actor) computes from it
   tests/golden/ref_written_6_push_demo.npz  get_push_demo (get_demo_data_push.py:24-94) driving a stand-in GoalEnv
   tests/golden/reward_dense_success.npz     compute_reward 'dense' / _is_success (bmirobot_env_push_F.py:84-90, 243-245)
-CPU half: the oracle reads these files like the reference does; our writers produce the same schema; and (build
-container only) a checkpoint in our payload layout loads into the reference's own models.actor."""
+CPU half: the oracle reads these files like the reference does; our writers produce the same schema; and a checkpoint in
+our payload layout loads into the reference's own models.actor (tests/golden/our_checkpoint_reference_actor.npz)."""
 import os
-import sys
 
 import numpy as np
-import pytest
 import torch
 
 from conftest import GOLDEN, bits, load_golden
@@ -17,7 +15,6 @@ from oracle import ddpg_update as oupd
 from oracle.her_replay import compute_reward, is_success
 from oracle.running_norm import RunningNorm
 
-REF = "/root/reference"
 KEYS = ["fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "fc3.weight", "fc3.bias", "action_out.weight",
         "action_out.bias"]
 ENV_PARAMS = {"obs": 27, "goal": 3, "action": 4, "action_max": 0.5, "max_timesteps": 100}
@@ -54,13 +51,17 @@ def test_oracle_reads_reference_checkpoint_like_demo_push():
     assert np.allclose(got, pr["actions"], rtol=1e-6, atol=1e-7)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference checkout (build container only)")
 def test_our_checkpoint_layout_loads_into_the_reference_actor(tmp_path):
     """A checkpoint in the layout ddpg_agent.checkpoint_payload() produces -- [mean, std, mean, std, state_dict of our
     models.actor container] -- goes through the reference's reader: torch.load + models.actor.load_state_dict (strict)
-    + process_inputs (demo_push.py:15-22,28,41)."""
+    + process_inputs (demo_push.py:15-22,28,41).  tests/golden/our_checkpoint_reference_actor.npz holds what the
+    reference's actor module did with this same seeded payload (tools/gen_golden.py): its state_dict layout, which a
+    strict load must match key for key and shape for shape, a fingerprint of the weights it loaded, and its action."""
+    import hashlib
+
     from rl_arm_under_sparse_reward_amd.models import actor as our_actor
 
+    ref = load_golden("our_checkpoint_reference_actor.npz")
     torch.manual_seed(3)
     ours = our_actor(dict(ENV_PARAMS))               # unattached container: state_dict() is the host tensors
     rs = np.random.RandomState(0)
@@ -68,23 +69,18 @@ def test_our_checkpoint_layout_loads_into_the_reference_actor(tmp_path):
                rs.normal(size=3).astype(np.float32), np.abs(rs.normal(size=3)) + 0.1, ours.state_dict()]
     path = str(tmp_path / "125_False1_model.pt")
     torch.save(payload, path)
-    sys.path.insert(0, REF)
-    try:
-        import models as ref_models
-    finally:
-        sys.path.remove(REF)
     o_mean, o_std, g_mean, g_std, model = torch.load(path, map_location=lambda storage, loc: storage, weights_only=False)
-    net = ref_models.actor(dict(ENV_PARAMS))
-    net.load_state_dict(model)                        # strict: key names and shapes must match the reference module
-    net.eval()
+    assert list(model.keys()) == list(ref["keys"])
+    for (k, v), shape, dtype in zip(model.items(), ref["shapes"], ref["dtypes"]):
+        assert list(v.shape) + [0] * (2 - v.dim()) == shape.tolist() and str(v.dtype) == dtype, k
+    assert hashlib.sha256(b"".join(v.numpy().tobytes() for v in model.values())).hexdigest() == str(ref["weights_sha256"])
     o, g = rs.uniform(-1, 1, 27), rs.uniform(0, 0.5, 3)
     x = np.concatenate([np.clip((np.clip(o, -200, 200) - o_mean) / o_std, -5, 5),
                         np.clip((np.clip(g, -200, 200) - g_mean) / g_std, -5, 5)])
+    assert np.array_equal(x, ref["x"])
     xt = torch.tensor(x, dtype=torch.float32)
-    with torch.no_grad():
-        a_ref = net(xt).numpy()
     a_orc = oupd.actor_forward(ours.state_dict(), xt[None], 0.5).numpy()[0]
-    assert np.allclose(a_ref, a_orc, rtol=1e-6, atol=1e-7)
+    assert np.allclose(ref["actions"], a_orc, rtol=1e-6, atol=1e-7)
 
 
 def test_reference_written_demo_schema_and_our_writer(tmp_path):

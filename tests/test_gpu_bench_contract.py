@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -34,7 +35,7 @@ def _run(*flags, timeout=600, **extra_env):
 def test_driver_invocation_prints_the_contract_line():
     with open(os.path.join(REPO, "BASELINE.json")) as fh:
         base = json.load(fh)
-    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "3")
+    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "3")
     assert d["metric"] == base["metric"] and d["unit"] == "transitions/s"
     assert (d["n_gpus"], d["steps"], d["warmup"]) == (1, 20, 5)
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None
@@ -65,6 +66,35 @@ def test_driver_invocation_prints_the_contract_line():
     assert f["achieved"] == pytest.approx(528 * f["batch"] / (f["avg_launch_us"] * 1e-6) / 1e9, rel=1e-3)
 
 
+DUMPED = {"losses_last_step", "actor_params", "critic_params", "actor_target_params", "critic_target_params", "o_norm_mean",
+          "o_norm_std", "g_norm_mean", "g_norm_std"}
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """Without --full the line is the headline measurement and nothing else, over exactly --steps timed steps; --dump-outputs
+    writes what the last timed step left to its caller as float .npy files, bit for bit the same on a second run."""
+    with open(os.path.join(REPO, "BASELINE.json")) as fh:
+        base = json.load(fh)
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        d = _run("--gpus", "1", "--steps", "60", "--warmup", "10", "--dump-outputs", str(out))
+        assert d["metric"] == base["metric"] and d["unit"] == "transitions/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f32" and (d["n_gpus"], d["steps"], d["warmup"]) == (1, 60, 10)
+        assert abs(d["value"] - 256 * 60 / (d["ms_per_step"] * 60e-3)) <= 1e-3 * d["value"]
+        assert 2e6 < d["value"] < 2e7
+        assert not {"roofline", "cpu_baseline", "calibration", "cycle_inclusive_estimate"} & set(d), sorted(d)
+        assert "engine" not in d["config"]
+        got = {p.stem: np.load(p) for p in out.iterdir()}
+        assert set(got) == DUMPED and {p.suffix for p in out.iterdir()} == {".npy"}
+        assert all(v.dtype in (np.float32, np.float64) and v.size for v in got.values())
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+        assert got["losses_last_step"].tolist() == np.float32(d["config"]["final_losses"]).tolist()
+        dumps.append(got)
+    for k in DUMPED:
+        assert np.array_equal(dumps[0][k].view(np.uint8), dumps[1][k].view(np.uint8)), k
+
+
 @pytest.mark.parametrize("batch", [256, 3072])     # 3072: the 32-row engine + split weight-gradient tiles under the exchange
 def test_plain_shell_multi_rank_launch(batch):
     d = _run("--gpus", "2", "--batch", str(batch), "--steps", "80", "--warmup", "40", "--no-cpu-baseline", "--no-profile")
@@ -87,7 +117,7 @@ def test_plain_shell_launch_rehearses_4_and_8_ranks(world):
     (IPC-mapped peer memory exactly as between GPUs; the fabric itself is what cannot be rehearsed).  Nothing is forced, so the
     transport and form are the DEFAULT ones: peer memory, two-phase (reduce-scatter + all-gather) from 4 ranks.  Then the
     one-shot form and the torch.distributed fallback: same replicas, and one-shot == two-phase bit for bit."""
-    common = ("--gpus", str(world), "--episodes", "64", "--steps", "80", "--warmup", "40", "--no-cpu-baseline", "--no-profile")
+    common = ("--gpus", str(world), "--episodes", "64", "--steps", "80", "--warmup", "40", "--full", "--no-cpu-baseline", "--no-profile")
     d = _run(*common, timeout=900)
     assert d["n_gpus"] == world and d["config"]["global_batch"] == 256 * world
     assert d["config"]["exchange"] == "peer-memory", d["config"]
@@ -114,7 +144,7 @@ def test_baseline_configs_4_and_5_rehearsed_at_their_real_per_rank_workloads(nam
     256 on 64-episode shards.  Here: the exact `bench.py --gpus 8` code path at those per-rank workloads with NOTHING forced, all
     ranks on the one device of the test box (default transport = peer memory with gate kernels, default form at 8 ranks =
     two-phase, cycle = hipGraph), replicas bit-identical, no fallback; then the one-shot form: the same losses bit for bit."""
-    common = ("--gpus", "8", *flags, "--steps", "40", "--warmup", "40", "--no-cpu-baseline", "--no-profile")
+    common = ("--gpus", "8", *flags, "--steps", "40", "--warmup", "40", "--full", "--no-cpu-baseline", "--no-profile")
     d = _run(*common, timeout=1500)
     c = d["config"]
     assert d["n_gpus"] == 8 and c["global_batch"] == 8 * per_rank_batch
@@ -142,7 +172,7 @@ def test_eight_rank_rehearsal_times_the_exchange_alternatives():
     torch.distributed) and records us/update + replica identity for each; the per-rank PCI bus ids and the rank counts say
     whether it was N ranks on N devices.  Rehearsed with eight ranks on the one device: RCCL cannot run there (it refuses two
     ranks per device; the record must say what the pass ran as), every peer form and the torch fallback must."""
-    d = _run("--gpus", "8", "--episodes", "64", "--steps", "80", "--warmup", "40", "--no-cpu-baseline", "--no-profile", timeout=1500,
+    d = _run("--gpus", "8", "--episodes", "64", "--steps", "80", "--warmup", "40", "--full", "--no-cpu-baseline", "--no-profile", timeout=1500,
              RLARM_BENCH_ALTERNATIVES="1")
     c = d["config"]
     assert d["n_gpus"] == 8 and c["replicas_bit_identical"] is True
@@ -160,7 +190,7 @@ def test_eight_rank_rehearsal_times_the_exchange_alternatives():
 
 def test_alternatives_pass_survives_a_failing_transport():
     """... and a transport that fails in the extra passes costs its own entry, not the line."""
-    d = _run("--gpus", "2", "--episodes", "64", "--steps", "80", "--warmup", "40", "--no-cpu-baseline", "--no-profile", timeout=900,
+    d = _run("--gpus", "2", "--episodes", "64", "--steps", "80", "--warmup", "40", "--full", "--no-cpu-baseline", "--no-profile", timeout=900,
              RLARM_BENCH_ALTERNATIVES="1", RLARM_BENCH_FAIL_ALT="peer memory, two-phase", RLARM_PEER_TIMEOUT_S="3")
     alts = d["exchange_alternatives"]
     bad = [x for x in alts if x["exchange"].startswith("peer memory, two-phase")]
@@ -198,7 +228,7 @@ def test_forced_data_parallel_line_names_the_kernels_it_ran(transport, chain, ti
     library's launch logic enqueues WHILE the transport is attached (round 5 asked after close_comm() and named the single-rank
     k_fb_split8 for a rank that ran k_fb_slab8): `config.engine.kernels_per_update` = hp_agent_update_kernels, the roofline's
     kernel is one of them, and a rocprofv3 --kernel-trace of the same command lists every one of them."""
-    flags = ("--steps", "400", "--warmup", "80", "--no-cpu-baseline")
+    flags = ("--steps", "400", "--warmup", "80", "--full", "--no-cpu-baseline")
     d, traced = _trace_kernel_names(flags, {"RLARM_BENCH_FORCE_DP": "1", "RLARM_COMM": transport}, tmp_path)
     c, r = d["config"], d["roofline"]
     assert c["exchange"] == {"peer": "peer-memory", "rccl": "rccl"}[transport]
@@ -221,7 +251,7 @@ def test_first_contact_failures_of_the_peer_exchange_still_yield_a_line(inject):
     Every rank must drop the peer exchange together, the run must degrade to the next transport (RCCL on a device each; two
     ranks on ONE device cannot use RCCL, so torch.distributed here), print the headline with the failure recorded and the
     alternatives pass inside its time box, and exit 0."""
-    d = _run("--gpus", "2", "--episodes", "64", "--steps", "80", "--warmup", "40", "--no-cpu-baseline", "--no-profile", timeout=600,
+    d = _run("--gpus", "2", "--episodes", "64", "--steps", "80", "--warmup", "40", "--full", "--no-cpu-baseline", "--no-profile", timeout=600,
              RLARM_BENCH_ALTERNATIVES="1", RLARM_BENCH_ALT_BUDGET_S="45", RLARM_PEER_INJECT=inject + "@1")
     c = d["config"]
     assert d["n_gpus"] == 2 and c["exchange"] in ("rccl", "torch.distributed") and c["replicas_bit_identical"] is True
@@ -236,7 +266,7 @@ def test_first_contact_failures_of_the_peer_exchange_still_yield_a_line(inject):
 def test_alternatives_pass_is_time_boxed():
     """... and the extra passes fit their time box: with 12 s for five transports every pass that starts gets a cut number of
     cycles or is recorded as skipped, and the line is printed."""
-    d = _run("--gpus", "2", "--episodes", "64", "--steps", "80", "--warmup", "40", "--no-cpu-baseline", "--no-profile", timeout=600,
+    d = _run("--gpus", "2", "--episodes", "64", "--steps", "80", "--warmup", "40", "--full", "--no-cpu-baseline", "--no-profile", timeout=600,
              RLARM_BENCH_ALTERNATIVES="1", RLARM_BENCH_ALT_BUDGET_S="12")
     alts = d["exchange_alternatives"]
     assert len(alts) == 5 and any("skipped" in x for x in alts), alts

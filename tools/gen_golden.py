@@ -628,6 +628,43 @@ def gen_checkpoint(ref, out):
     print("ref_checkpoint_model.pt:", len(blob), "bytes; keys", list(model.keys()))
 
 
+def gen_our_checkpoint(ref, out):
+    """A checkpoint in OUR payload layout (ddpg_agent.checkpoint_payload: [mean, std, mean, std, state_dict of our models.actor
+    container], seeded as tests/test_formats_cpu.py builds it) through the reference's reader: torch.load +
+    models.actor.load_state_dict (strict) + one forward on a probe input.  Recorded: the reference actor's state_dict layout,
+    a fingerprint of the weights it loaded, the probe input and the reference's action."""
+    import hashlib
+
+    import torch
+
+    from rl_arm_under_sparse_reward_amd.models import actor as our_actor
+
+    torch.manual_seed(3)
+    ours = our_actor(dict(ENV_PARAMS))
+    rs = np.random.RandomState(0)
+    payload = [rs.normal(size=27).astype(np.float32), np.abs(rs.normal(size=27)) + 0.1,
+               rs.normal(size=3).astype(np.float32), np.abs(rs.normal(size=3)) + 0.1, ours.state_dict()]
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "125_False1_model.pt")
+        torch.save(payload, path)
+        o_mean, o_std, g_mean, g_std, model = torch.load(path, map_location=lambda storage, loc: storage, weights_only=False)
+    net = ref.models.actor(dict(ENV_PARAMS))
+    net.load_state_dict(model)                        # strict
+    net.eval()
+    o, g = rs.uniform(-1, 1, 27), rs.uniform(0, 0.5, 3)
+    x = np.concatenate([np.clip((np.clip(o, -200, 200) - o_mean) / o_std, -5, 5),
+                        np.clip((np.clip(g, -200, 200) - g_mean) / g_std, -5, 5)])
+    with torch.no_grad():
+        a_ref = net(torch.tensor(x, dtype=torch.float32)).numpy()
+    layout = net.state_dict()
+    sha = hashlib.sha256(b"".join(v.numpy().tobytes() for v in model.values())).hexdigest()
+    np.savez_compressed(os.path.join(out, "our_checkpoint_reference_actor.npz"), keys=np.array(list(layout.keys())),
+                        shapes=np.array([list(v.shape) + [0] * (2 - v.dim()) for v in layout.values()], np.int64),
+                        dtypes=np.array([str(v.dtype) for v in layout.values()]), weights_sha256=np.array(sha),
+                        x=x, actions=a_ref, torch_version=np.array(torch.__version__))
+    print("our_checkpoint_reference_actor.npz: keys", list(layout.keys()), "action", a_ref.tolist())
+
+
 def gen_reference_demo(out, demo_num=6):
     """A12 / N2: a demo file written by the reference's own generator: get_push_demo (get_demo_data_push.py:24-94,
     executed unmodified; its module cannot be imported because it pulls in gym + pybullet at the top) driving a
@@ -791,8 +828,8 @@ def main():
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     ref = load_reference()
-    todo = a.only.split(",") if a.only else ["rng", "her", "reward", "storage", "norm", "ddpg", "demo", "ckpt", "refdemo",
-                                             "dense", "rollout"]
+    todo = a.only.split(",") if a.only else ["rng", "her", "reward", "storage", "norm", "ddpg", "demo", "ckpt", "ourckpt",
+                                             "refdemo", "dense", "rollout"]
     if "rng" in todo:
         gen_rng_kat(ref, a.out)
     if "her" in todo:
@@ -809,6 +846,8 @@ def main():
         gen_demo(a.out)
     if "ckpt" in todo:
         gen_checkpoint(ref, a.out)
+    if "ourckpt" in todo:
+        gen_our_checkpoint(ref, a.out)
     if "refdemo" in todo:
         gen_reference_demo(a.out)
     if "dense" in todo:

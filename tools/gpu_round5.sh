@@ -28,17 +28,17 @@ for B in 256 1024; do BATCH=$B tools/ubench/pmc_tcc.sh > $O/pmc_tcc_b$B.txt 2>&1
 # and checked against the kernel sources' fingerprint (traffic_stale, duration_stale)
 for B in 256 512 1024 4096; do cp $O/pmc_traffic_b$B.json profiles/r05_pmc_traffic_b$B.json; done
 for cfg in "256 4" "512 8" "1024 4" "4096 4"; do set -- $cfg; cp $O/kernel_trace_b$1_k$2.txt profiles/r05_kernel_trace_b$1_k$2.txt; done
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.log 2>&1; tail -1 $O/bench_driver_style.log > $O/bench_n1_b256_driver_style.json
-python bench.py --steps 4000 --warmup 400 > $O/bench_b256.log 2>&1; tail -1 $O/bench_b256.log > $O/bench_n1_b256.json
-RLARM_SPLIT=0 python bench.py --steps 4000 --warmup 400 --no-cpu-baseline > $O/bench_b256_two_launch.log 2>&1; tail -1 $O/bench_b256_two_launch.log > $O/bench_n1_b256_two_launch_form.json
-RLARM_BENCH_FORCE_DP=1 python bench.py --steps 4000 --warmup 400 --no-cpu-baseline --no-profile > $O/bench_b256_dp.log 2>&1; tail -1 $O/bench_b256_dp.log > $O/bench_n1_b256_forced_dp_world1.json
-RLARM_BENCH_FORCE_DP=1 RLARM_PEER_TILES=0 python bench.py --steps 4000 --warmup 400 --no-cpu-baseline --no-profile > $O/bench_b256_dp0.log 2>&1; tail -1 $O/bench_b256_dp0.log > $O/bench_n1_b256_forced_dp_world1_separate_exchange_launch.json
-RLARM_BENCH_FORCE_DP=1 RLARM_COMM=rccl python bench.py --steps 4000 --warmup 400 --no-cpu-baseline --no-profile > $O/bench_b256_dp_rccl.log 2>&1; tail -1 $O/bench_b256_dp_rccl.log > $O/bench_n1_b256_forced_dp_world1_rccl.json
-python bench.py --batch 1024 --steps 2000 --warmup 200 --cpu-seconds 10 > $O/bench_b1024.log 2>&1; tail -1 $O/bench_b1024.log > $O/bench_n1_b1024.json
-python bench.py --batch 512 --replay-k 8 --steps 2000 --warmup 200 --cpu-seconds 10 > $O/bench_b512k8.log 2>&1; tail -1 $O/bench_b512k8.log > $O/bench_n1_b512_k8.json
-python bench.py --batch 4096 --steps 800 --warmup 80 --no-cpu-baseline > $O/bench_b4096.log 2>&1; tail -1 $O/bench_b4096.log > $O/bench_n1_b4096.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.log 2>&1; tail -1 $O/bench_driver_style.log > $O/bench_n1_b256_driver_style.json
+python bench.py --full --steps 4000 --warmup 400 > $O/bench_b256.log 2>&1; tail -1 $O/bench_b256.log > $O/bench_n1_b256.json
+RLARM_SPLIT=0 python bench.py --full --steps 4000 --warmup 400 --no-cpu-baseline > $O/bench_b256_two_launch.log 2>&1; tail -1 $O/bench_b256_two_launch.log > $O/bench_n1_b256_two_launch_form.json
+RLARM_BENCH_FORCE_DP=1 python bench.py --full --steps 4000 --warmup 400 --no-cpu-baseline --no-profile > $O/bench_b256_dp.log 2>&1; tail -1 $O/bench_b256_dp.log > $O/bench_n1_b256_forced_dp_world1.json
+RLARM_BENCH_FORCE_DP=1 RLARM_PEER_TILES=0 python bench.py --full --steps 4000 --warmup 400 --no-cpu-baseline --no-profile > $O/bench_b256_dp0.log 2>&1; tail -1 $O/bench_b256_dp0.log > $O/bench_n1_b256_forced_dp_world1_separate_exchange_launch.json
+RLARM_BENCH_FORCE_DP=1 RLARM_COMM=rccl python bench.py --full --steps 4000 --warmup 400 --no-cpu-baseline --no-profile > $O/bench_b256_dp_rccl.log 2>&1; tail -1 $O/bench_b256_dp_rccl.log > $O/bench_n1_b256_forced_dp_world1_rccl.json
+python bench.py --full --batch 1024 --steps 2000 --warmup 200 --cpu-seconds 10 > $O/bench_b1024.log 2>&1; tail -1 $O/bench_b1024.log > $O/bench_n1_b1024.json
+python bench.py --full --batch 512 --replay-k 8 --steps 2000 --warmup 200 --cpu-seconds 10 > $O/bench_b512k8.log 2>&1; tail -1 $O/bench_b512k8.log > $O/bench_n1_b512_k8.json
+python bench.py --full --batch 4096 --steps 800 --warmup 80 --no-cpu-baseline > $O/bench_b4096.log 2>&1; tail -1 $O/bench_b4096.log > $O/bench_n1_b4096.json
 # 8 ranks on the one device: the line a multi-GPU run prints, exchange_alternatives and device identity included (rehearsal, never a number to quote)
-timeout 900 python bench.py --gpus 8 --episodes 64 --steps 80 --warmup 40 --no-cpu-baseline --no-profile > $O/bench_rehearsal_8ranks.log 2>&1; grep '^{"metric"' $O/bench_rehearsal_8ranks.log > $O/bench_rehearsal_8_ranks_one_device.json
+timeout 900 python bench.py --full --gpus 8 --episodes 64 --steps 80 --warmup 40 --no-cpu-baseline --no-profile > $O/bench_rehearsal_8ranks.log 2>&1; grep '^{"metric"' $O/bench_rehearsal_8ranks.log > $O/bench_rehearsal_8_ranks_one_device.json
 i=0; rm -f $O/pmc_sq_b256.txt
 for set in "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES" "SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_MFMA SQ_INSTS_VALU" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS" "SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_WAIT_ANY"; do
   i=$((i+1)); d=$O/pmcs_$i; rm -rf $d; mkdir -p $d
