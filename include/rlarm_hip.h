@@ -169,8 +169,9 @@ typedef struct {
 int hp_buffer_sample_dev(hp_buffer *buf, hp_rng *rng, hp_norm *o_norm, hp_norm *g_norm, int64_t batch, double future_p,
                          double sq_threshold, double clip_obs, const hp_sample_dev_out *dev_out);
 /* Throughput mode of the sampler (SURVEY 8b's `storage_dtype` = fp32; opt-in, NOT bit-identical to the reference's float64 rows):
- * hp_buffer_enable_f32_rows builds -- from what the buffer holds now, and behind every later store -- a float32 mirror of the
- * observations and actions laid out for the gather (one (episode, timestep) per 128-byte line: obs_t | action_t), the goals
+ * hp_buffer_enable_f32_rows builds -- from what the buffer holds now, and behind every later store, those of cycles whose graph was
+ * captured before included (they are captured again) -- a float32 mirror of the observations and actions laid out for the gather
+ * (one (episode, timestep) per 128-byte line: obs_t | action_t), the goals
  * staying float64.  hp_buffer_sample_dev_f32 = hp_buffer_sample_dev reading that mirror: same stream, same draws, indices,
  * relabelled goals (her.py:35-36), rewards (:38) and goal columns of x / x_next BIT-identical; actions identical (the learner takes
  * float32(actions) either way); the observation columns are those of float32-rounded observations (replay_buffer.py:23-27 stores

@@ -16,6 +16,7 @@
 #pragma once
 #include "internal.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -150,6 +151,47 @@ __device__ __forceinline__ bool handoff_wait(const unsigned *ctr, unsigned need,
 #include "slab_common.h"
 #include "peer.h"
 
+// What a captured update sequence bakes in beyond the agent's own state: the handles, the arguments, and the buffer's generation.
+struct SeqKey {
+    enum Kind { CYCLE, UPDATES } kind;
+    hp_buffer *b;
+    hp_norm *on, *gn;
+    hp_rng *rng;
+    int n;              // n_batches / n_updates
+    int64_t n_new;      // 0 for UPDATES
+    double future_p, sq_threshold;
+    bool open;          // the cycle opens with k_cycle_open
+    uint64_t gen;       // hp_buffer::gen
+    bool operator==(const SeqKey &o) const {
+        return kind == o.kind && b == o.b && on == o.on && gn == o.gn && rng == o.rng && n == o.n && n_new == o.n_new &&
+               future_p == o.future_p && sq_threshold == o.sq_threshold && open == o.open && gen == o.gen;
+    }
+};
+// One cycle graph and up to eight update graphs (a loop uses one or two chunk lengths), oldest evicted first.
+struct GraphCache {
+    struct Entry {
+        SeqKey key;
+        GraphExec exec;
+    };
+    std::vector<Entry> entries;
+    hipGraphExec_t find(const SeqKey &k) const {
+        for (const Entry &e : entries)
+            if (e.key == k) return e.exec.h;
+        return nullptr;
+    }
+    bool has(SeqKey::Kind kind) const {
+        return std::any_of(entries.begin(), entries.end(), [&](const Entry &e) { return e.key.kind == kind; });
+    }
+    hipGraphExec_t put(const SeqKey &k, GraphExec &&x) {
+        const auto same_kind = [&](const Entry &e) { return e.key.kind == k.kind; };
+        if (std::count_if(entries.begin(), entries.end(), same_kind) >= (k.kind == SeqKey::CYCLE ? 1 : 8))
+            entries.erase(std::find_if(entries.begin(), entries.end(), same_kind));
+        entries.push_back({k, std::move(x)});
+        return entries.back().exec.h;
+    }
+    void clear() { entries.clear(); }
+};
+
 enum { PROF_SAMPLE = 0, PROF_GEMM_FWD = 1, PROF_GEMM_BWD = 2, PROF_LOSS = 3, PROF_ADAM = 4, PROF_PLAN = 5, PROF_DW = 6, PROF_N = 7 };
 
 struct hp_agent {
@@ -210,20 +252,11 @@ struct hp_agent {
     hp_peer *peer = nullptr;      // one-shot exchange over peer memory (hp_agent_set_peer); takes precedence over comm
     bool grad_mean = false;       // divide the all-reduced gradients by the world size (default: SUM, like the reference)
     bool comm_warm = false;       // the collectives of a cycle have each run once outside a capture
-    bool graph_refused = false;   // capturing the cycle with collectives failed once: stay on eager launches
-    // graphs of hp_agent_sample_and_update(n_updates), one per distinct argument set (a training loop that does not use
-    // hp_agent_train_cycle replays its inner loop instead of issuing 2 launches per update)
-    struct UpdGraph {
-        hipGraphExec_t exec;
-        int n_updates;
-        hp_buffer *b;
-        hp_norm *on, *gn;
-        hp_rng *rng;
-        double future_p, sq;
-    };
-    std::vector<UpdGraph> upd_graphs;
-    // cycle graph cache
-    hipGraphExec_t graph = nullptr;
+    bool graph_refused = false;   // a capture with collectives was refused once: stay on eager launches
+    // captured sequences: the device part of hp_agent_train_cycle, and hp_agent_sample_and_update(n) (a training loop that does not
+    // use train_cycle replays its inner loop instead of issuing 2 launches per update).  Cleared when what the agent bakes into
+    // them changes: the plans' addresses (ensure_plan), the communicator, the peer exchange, the gradient reduction.
+    GraphCache graphs;
     unsigned *open_sync = nullptr;       // k_cycle_open's flags (cycle_open.hip)
     int loss_wg = 1;                     // the loss log is written by a workgroup of its own behind the weight-gradient tiles (gemm_lds.h gemm_loss_wg)
     int dw_ksplit = 0;                   // reduction slices of the narrow weight-gradient problems (RLARM_DW_KSPLIT; 0/1: none)
@@ -238,15 +271,6 @@ struct hp_agent {
     unsigned *fault_host = nullptr;      // pinned + mapped mirror of the fault word (agent_check_fault), and its device address
     unsigned *fault_host_dev = nullptr;
     bool cycle_open = true;              // RLARM_CYCLE_OPEN=0: slots / scatter / plans / normalizer as separate launches
-    bool g_open = false;
-    void *g_slots = nullptr;
-    hp_buffer *g_buf = nullptr;
-    hp_norm *g_on = nullptr, *g_gn = nullptr;
-    hp_rng *g_rng = nullptr;
-    int64_t g_n_new = -1;
-    int g_n_batches = -1;
-    double g_future_p = -1, g_sq = -1;
-    void *g_stage = nullptr;
     // profiling
     bool prof = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;

@@ -6,7 +6,7 @@
 
 #include <functional>
 
-static void drop_graph(hp_agent *a);
+static int run_seq(hp_agent *a, const SeqKey &k);
 
 // A bounded in-launch hand-off gave up in an earlier launch (k_cycle_open's flags, k_fb_split8's counters): work was skipped, so
 // buffer / normalizer / parameters are no longer what the reference would hold.  The word is sticky and mirrored into pinned
@@ -21,13 +21,18 @@ int agent_check_fault(const hp_agent *a, const char *who) {
     return HP_ERR_STATE;
 }
 
-static int ensure_plan(hp_agent *a, int n_batches) {
+// norm_rows: transitions of the normalizer's index plan (a cycle's), 0 = not needed
+static int ensure_plan(hp_agent *a, int n_batches, int norm_rows = 0) {
+    // the cached graphs have the plans' addresses baked into their draw / gather / ride-along kernels: growing a plan frees
+    // that memory, so the graphs go with it (captured again on their next call)
     if (n_batches > a->plan_batches) {
-        // the cached cycle graph has the plan's address baked into its draw / gather / ride-along kernels: growing the
-        // plan frees that memory, so the graph goes with it (rebuilt by the next hp_agent_train_cycle)
-        drop_graph(a);
+        a->graphs.clear();
         HP_TRY(a->plan.ensure((size_t)n_batches * a->B * sizeof(PlanRec)));
         a->plan_batches = n_batches;
+    }
+    if ((size_t)norm_rows * sizeof(PlanRec) > a->norm_plan.bytes) {
+        a->graphs.clear();
+        HP_TRY(a->norm_plan.ensure((size_t)norm_rows * sizeof(PlanRec)));
     }
     return HP_OK;
 }
@@ -227,13 +232,6 @@ template <class T> static int dev_alloc(hp_agent *a, T **p, size_t count) {
     a->owned.push_back(q);
     *p = static_cast<T *>(q);
     return HP_OK;
-}
-
-static void drop_graph(hp_agent *a) {   // every cached graph: they all bake in the plan address, the communicator, the switches
-    if (a->graph) (void)hipGraphExecDestroy(a->graph);
-    a->graph = nullptr;
-    for (auto &u : a->upd_graphs) (void)hipGraphExecDestroy(u.exec);
-    a->upd_graphs.clear();
 }
 
 // --------------------------------------------------------------------------------- C ABI
@@ -498,53 +496,7 @@ int hp_agent_sample_and_update(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *
     HP_TRY(peer_check_alive(a->peer, "hp_agent_sample_and_update"));
     HP_TRY(agent_check_fault(a, "hp_agent_sample_and_update"));
     HP_REQUIRE(b->current_size > 0, HP_ERR_EMPTY, "high <= 0");
-    HP_TRY(ensure_plan(a, n_updates));
-    hipStream_t s = a->ctx->stream;
-    // The n_updates x 2 launches have constant arguments (all state is device resident), so the call is replayed as a
-    // cached hipGraph: same kernels, same order, same bits as the eager launches, ~1.5 us less boundary per launch.
-    // Not under profiling (per-launch events), not on the legacy stream (cannot be captured), not after a refusal.
-    const bool graphable = !a->prof && s != hipStreamLegacy && !a->graph_refused && a->upd_graph_ok;
-    if (graphable) {
-        for (auto &u : a->upd_graphs)
-            if (u.n_updates == n_updates && u.b == b && u.on == on && u.gn == gn && u.rng == rng &&
-                u.future_p == future_p && u.sq == sq_threshold) {
-                HP_CHECK_HIP(hipGraphLaunch(u.exec, s));
-                a->host_steps += n_updates;
-                return HP_OK;
-            }
-        if (a->comm && !a->comm_warm) {   // RCCL sets its channels up lazily: first collective outside a capture
-            a->comm_warm = true;
-            HP_TRY(comm_allreduce_sum_f32(a->comm, a->grads, (size_t)a->n_arena));
-            HP_TRY(comm_allreduce_sum_f32(a->comm, on->d->sync, (size_t)(2 * on->size + 1)));
-            HP_TRY(comm_allreduce_sum_f32(a->comm, gn->d->sync, (size_t)(2 * gn->size + 1)));
-        }
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        HP_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        int st = enqueue_updates(a, b, on, gn, rng, future_p, sq_threshold, n_updates, true);
-        hipError_t e = hipStreamEndCapture(s, &graph);
-        if (st == HP_OK && e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (st == HP_OK && e == hipSuccess) {
-            if (a->upd_graphs.size() >= 8) {   // a loop uses one or two chunk lengths; keep the cache small
-                (void)hipGraphExecDestroy(a->upd_graphs.front().exec);
-                a->upd_graphs.erase(a->upd_graphs.begin());
-            }
-            a->upd_graphs.push_back({exec, n_updates, b, on, gn, rng, future_p, sq_threshold});
-            HP_CHECK_HIP(hipGraphLaunch(exec, s));
-            a->host_steps += n_updates;
-            return HP_OK;
-        }
-        if (!a->comm) {
-            if (st != HP_OK) return st;
-            HP_CHECK_HIP(e);
-        }
-        (void)hipGetLastError();       // a capture with collectives was refused: nothing ran, fall through to eager launches
-        a->graph_refused = true;
-    }
-    HP_TRY(enqueue_updates(a, b, on, gn, rng, future_p, sq_threshold, n_updates, true));
-    a->host_steps += n_updates;
-    return HP_OK;
+    return run_seq(a, {SeqKey::UPDATES, b, on, gn, rng, n_updates, 0, future_p, sq_threshold, false, b->gen});
 }
 
 int hp_agent_forward_backward(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, double future_p,
@@ -654,12 +606,56 @@ static int enqueue_cycle_tail(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *g
     return HP_OK;
 }
 
+// RCCL sets its channels up lazily, on the first collective of a kind: do that outside a capture, once per attach, before the first
+// capture of every rank (stays symmetric across ranks).  The gradients are recomputed before they are read; the zeroed sync vectors
+// are idle between cycles (overwritten by k_norm_begin).
+static int comm_warm_up(hp_agent *a, hp_norm *on, hp_norm *gn) {
+    if (!a->comm || a->comm_warm) return HP_OK;
+    a->comm_warm = true;
+    HP_TRY(comm_allreduce_sum_f32(a->comm, a->grads, (size_t)a->n_arena));
+    HP_TRY(comm_allreduce_sum_f32(a->comm, on->d->sync, (size_t)(2 * on->size + 1)));
+    return comm_allreduce_sum_f32(a->comm, gn->d->sync, (size_t)(2 * gn->size + 1));
+}
+
+static int enqueue_seq(hp_agent *a, const SeqKey &k) {
+    if (k.kind == SeqKey::UPDATES) return enqueue_updates(a, k.b, k.on, k.gn, k.rng, k.future_p, k.sq_threshold, k.n, true);
+    return enqueue_cycle_tail(a, k.b, k.on, k.gn, k.rng, k.future_p, k.sq_threshold, k.n, a->norm_plan.as<PlanRec>(), k.open);
+}
+
+// One update sequence.  Its launches have constant arguments (all state is device resident), so it replays the cached hipGraph of
+// its key, captured on the first call: same kernels, same order, same bits as eager launches, ~1.5 us less boundary per launch.
+// Eager launches instead under profiling (per-launch events), on the legacy default stream (cannot be captured; for this call only),
+// after a refused capture with collectives (sticky), and for update calls under RLARM_UPDATE_GRAPH=0.
+static int run_seq(hp_agent *a, const SeqKey &k) {
+    hipStream_t s = a->ctx->stream;
+    const bool eager = a->prof || s == hipStreamLegacy || a->graph_refused || (k.kind == SeqKey::UPDATES && !a->upd_graph_ok);
+    hipGraphExec_t exec = eager ? nullptr : a->graphs.find(k);
+    if (!exec) {
+        HP_TRY(ensure_plan(a, k.n, k.kind == SeqKey::CYCLE ? k.b->T : 0));
+        if (!eager) {
+            HP_TRY(comm_warm_up(a, k.on, k.gn));
+            HP_CHECK_HIP(hipStreamSynchronize(s));
+            Captured c = capture_graph(s, [&] { return enqueue_seq(a, k); });
+            if (c.exec.h) exec = a->graphs.put(k, std::move(c.exec));
+            else if (!a->comm) return c.status();
+            // A capture that contains collectives was refused (RCCL build without graph support, or a lazy allocation inside
+            // the capture).  Nothing was executed -- a capture only records -- so the same work is issued as ordinary launches
+            // from now on; the other ranks see the same sequence of collectives either way.
+            else a->graph_refused = true;
+        }
+    }
+    if (exec) HP_CHECK_HIP(hipGraphLaunch(exec, s));
+    else HP_TRY(enqueue_seq(a, k));
+    a->host_steps += k.n;
+    return HP_OK;
+}
+
 extern "C" {
 
 int hp_agent_set_grad_reduce(hp_agent *a, int32_t mean) {
     HP_REQUIRE(a, HP_ERR_INVALID, "hp_agent_set_grad_reduce: null handle");
     HP_SERIALISE(a);
-    if (a->grad_mean != (mean != 0)) drop_graph(a);
+    if (a->grad_mean != (mean != 0)) a->graphs.clear();
     a->grad_mean = mean != 0;
     return HP_OK;
 }
@@ -669,7 +665,7 @@ int hp_agent_set_grad_reduce(hp_agent *a, int32_t mean) {
 int hp_agent_cycle_mode(hp_agent *a, int32_t *mode) {
     HP_REQUIRE(a && mode, HP_ERR_INVALID, "hp_agent_cycle_mode: null argument");
     HP_SERIALISE(a);
-    *mode = a->graph_refused ? 2 : (a->graph ? 1 : 0);
+    *mode = a->graph_refused ? 2 : (a->graphs.has(SeqKey::CYCLE) ? 1 : 0);
     return HP_OK;
 }
 
@@ -680,7 +676,7 @@ int hp_agent_set_peer(hp_agent *a, hp_peer *peer) {
     HP_REQUIRE(!peer || (peer->connected && peer->n_grad == (size_t)a->n_arena), HP_ERR_INVALID,
                "hp_agent_set_peer: exchange not connected, or its gradient length differs from the agent's (%d floats)", a->n_arena);
     HP_REQUIRE(!peer || a->slab, HP_ERR_INVALID, "hp_agent_set_peer: needs a slab engine (the optimizer kernel with fragment copies)");
-    drop_graph(a);
+    a->graphs.clear();
     a->peer = peer;
     return HP_OK;
 }
@@ -689,16 +685,12 @@ int hp_agent_set_comm(hp_agent *a, hp_comm *comm) {
     HP_REQUIRE(a, HP_ERR_INVALID, "hp_agent_set_comm: null handle");
     HP_SERIALISE(a);
     HP_REQUIRE(!comm || comm->ctx == a->ctx, HP_ERR_INVALID, "hp_agent_set_comm: communicator belongs to another context");
-    drop_graph(a);
+    a->graphs.clear();
     a->graph_refused = false;
     a->comm_warm = false;
     a->comm = comm;
     return HP_OK;
 }
-
-// everything of a cycle behind the staging of its episodes: one cached graph
-static int train_cycle_staged(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, int64_t n_new, double future_p,
-                              double sq_threshold, int32_t n_batches, bool open);
 
 static int train_cycle_checks(hp_agent *a, hp_buffer *b, int64_t n_new, int32_t n_batches, const char *who) {
     HP_REQUIRE(n_new > 0 && n_batches > 0, HP_ERR_INVALID, "%s: n_new and n_batches must be positive", who);
@@ -720,7 +712,7 @@ int hp_agent_train_cycle(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp
     const bool open = a->cycle_open && cycle_open_fits(a, n_new);
     if (open) HP_TRY(buffer_stage_for_cycle(b, obs, ag_host, g, actions, n_new));
     else HP_TRY(buffer_stage_and_store(b, rng, obs, ag_host, g, actions, n_new));
-    return train_cycle_staged(a, b, on, gn, rng, n_new, future_p, sq_threshold, n_batches, open);
+    return run_seq(a, {SeqKey::CYCLE, b, on, gn, rng, n_batches, n_new, future_p, sq_threshold, open, b->gen});
 }
 
 // The same cycle on episodes that lie in a host block registered with the device (hp_host_register: the feeder's shared-memory
@@ -733,70 +725,7 @@ int hp_agent_train_cycle_pinned(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm 
     HP_TRY(train_cycle_checks(a, b, n_new, n_batches, "hp_agent_train_cycle_pinned"));
     const bool open = a->cycle_open && cycle_open_fits(a, n_new);
     HP_TRY(buffer_stage_pinned(b, rng, block, n_new, ticket, !open));
-    return train_cycle_staged(a, b, on, gn, rng, n_new, future_p, sq_threshold, n_batches, open);
-}
-
-static int train_cycle_staged(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, int64_t n_new, double future_p,
-                              double sq_threshold, int32_t n_batches, bool open) {
-    hipStream_t s = a->ctx->stream;
-    // 2. everything else is one graph; rebuild when a baked-in argument changes
-    const bool same = a->graph && a->g_buf == b && a->g_on == on && a->g_gn == gn && a->g_rng == rng &&
-                      a->g_n_new == n_new && a->g_n_batches == n_batches && a->g_future_p == future_p &&
-                      a->g_sq == sq_threshold && a->g_stage == b->st_obs.p && a->g_slots == b->st_slots.p && a->g_open == open;
-    // the legacy default stream cannot be captured: eager launches for THIS call only (the context may be back on a capturable
-    // stream at the next one; only a refused capture with collectives, below, is sticky)
-    if (a->graph_refused || s == hipStreamLegacy) {
-        HP_TRY(ensure_plan(a, n_batches));
-        HP_TRY(a->norm_plan.ensure((size_t)b->T * sizeof(PlanRec)));
-        HP_TRY(enqueue_cycle_tail(a, b, on, gn, rng, future_p, sq_threshold, n_batches, a->norm_plan.as<PlanRec>(), open));
-        a->host_steps += n_batches;
-        return HP_OK;
-    }
-    if (!same) {
-        drop_graph(a);
-        HP_TRY(ensure_plan(a, n_batches));
-        HP_TRY(a->norm_plan.ensure((size_t)b->T * sizeof(PlanRec)));
-        if (a->comm && !a->comm_warm) {
-            a->comm_warm = true;   // once per attach, on the first cycle of every rank: stays symmetric across ranks
-            // RCCL sets up its channels lazily on the first collective of a given kind: do that outside the capture
-            // (the gradients are recomputed before they are read, the zeroed sync vectors are idle between cycles)
-            HP_TRY(comm_allreduce_sum_f32(a->comm, a->grads, (size_t)a->n_arena));
-            HP_TRY(comm_allreduce_sum_f32(a->comm, on->d->sync, (size_t)(2 * on->size + 1)));   // overwritten by
-            HP_TRY(comm_allreduce_sum_f32(a->comm, gn->d->sync, (size_t)(2 * gn->size + 1)));   // k_norm_begin
-        }
-        HP_CHECK_HIP(hipStreamSynchronize(s));
-        hipGraph_t graph = nullptr;
-        HP_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        int st = enqueue_cycle_tail(a, b, on, gn, rng, future_p, sq_threshold, n_batches, a->norm_plan.as<PlanRec>(), open);
-        hipError_t e = hipStreamEndCapture(s, &graph);
-        if (st == HP_OK && e == hipSuccess) {
-            e = hipGraphInstantiate(&a->graph, graph, nullptr, nullptr, 0);
-            if (e != hipSuccess) a->graph = nullptr;
-        }
-        if (graph) (void)hipGraphDestroy(graph);
-        if (st != HP_OK || e != hipSuccess) {
-            if (!a->comm) {
-                if (st != HP_OK) return st;
-                HP_CHECK_HIP(e);
-            }
-            // A capture that contains collectives was refused (RCCL build without graph support, or a lazy allocation
-            // inside the capture).  Nothing was executed -- a capture only records -- so the same work is issued as
-            // ordinary launches from now on; the other ranks see the same sequence of collectives either way.
-            (void)hipGetLastError();
-            a->graph_refused = true;
-            HP_TRY(enqueue_cycle_tail(a, b, on, gn, rng, future_p, sq_threshold, n_batches, a->norm_plan.as<PlanRec>(), open));
-            a->host_steps += n_batches;
-            return HP_OK;
-        }
-        a->g_buf = b; a->g_on = on; a->g_gn = gn; a->g_rng = rng;
-        a->g_n_new = n_new; a->g_n_batches = n_batches; a->g_future_p = future_p; a->g_sq = sq_threshold;
-        a->g_stage = b->st_obs.p;
-        a->g_slots = b->st_slots.p;
-        a->g_open = open;
-    }
-    HP_CHECK_HIP(hipGraphLaunch(a->graph, s));
-    a->host_steps += n_batches;
-    return HP_OK;
+    return run_seq(a, {SeqKey::CYCLE, b, on, gn, rng, n_batches, n_new, future_p, sq_threshold, open, b->gen});
 }
 
 // which launch structure a sequence of n_updates sampled updates WITH optimizer steps takes on this agent: 0 = chain launch +
@@ -830,24 +759,17 @@ int hp_agent_update_kernels(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn,
     } rebind{a->ctx, bound};
     a->ctx->stream = s;
     std::vector<std::string> log;
-    hipGraph_t graph = nullptr;
     unsigned *pending = a->split_reset_pending;
-    HP_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    hp_klog = &log;
-    int st;
-    if (caller_exchanges) {
-        st = enqueue_updates(a, b, on, gn, rng, future_p, sq_threshold, 1, false);
+    hp_klog = &log;   // (the collectives are named, not issued: comm.hip)
+    const Captured c = capture_graph(s, [&] {
+        if (!caller_exchanges) return enqueue_updates(a, b, on, gn, rng, future_p, sq_threshold, n_updates, true);
+        HP_TRY(enqueue_updates(a, b, on, gn, rng, future_p, sq_threshold, 1, false));
         HP_KLOG("host:all_reduce");
-        if (st == HP_OK) st = enqueue_adam(a);
-    } else {
-        st = enqueue_updates(a, b, on, gn, rng, future_p, sq_threshold, n_updates, true);
-    }
+        return enqueue_adam(a);
+    }, false);
     hp_klog = nullptr;
-    const hipError_t e = hipStreamEndCapture(s, &graph);
-    if (graph) (void)hipGraphDestroy(graph);
     a->split_reset_pending = pending;
-    if (e != hipSuccess) (void)hipGetLastError();   // (a capture with collectives may be refused: the log is complete all the same)
-    if (st != HP_OK) return st;
+    HP_TRY(c.status());
     std::string j;
     for (size_t i = 0; i < log.size(); ++i) j += (i ? "," : "") + log[i];
     HP_REQUIRE((int)j.size() + 1 <= out_len, HP_ERR_INVALID, "hp_agent_update_kernels: %zu bytes needed", j.size() + 1);
@@ -888,7 +810,7 @@ int hp_agent_profile_read(hp_agent *a, double *ms_out, int32_t n) {
 
 void hp_agent_destroy(hp_agent *a) {
     if (!a) return;
-    drop_graph(a);
+    a->graphs.clear();
     (void)hipStreamSynchronize(a->ctx->stream);
     for (void *p : a->owned) (void)hipFree(p);
     if (a->act_stream) {

@@ -1329,25 +1329,19 @@ int hp_agent_debug_chain(hp_agent *a, int32_t kind, int32_t n, double *us_per_la
         }
     };
     HP_CHECK_HIP(hipStreamSynchronize(s));
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    HP_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    int st = HP_OK;
-    for (int i = 0; i < n && st == HP_OK; ++i) st = one();
-    hipError_t e = hipStreamEndCapture(s, &g);
-    if (st != HP_OK) return st;
-    HP_CHECK_HIP(e);
-    HP_CHECK_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    HP_CHECK_HIP(hipGraphLaunch(ge, s));
+    const Captured c = capture_graph(s, [&] {
+        for (int i = 0; i < n; ++i) HP_TRY(one());
+        return (int)HP_OK;
+    });
+    HP_TRY(c.status());
+    HP_CHECK_HIP(hipGraphLaunch(c.exec.h, s));
     HP_CHECK_HIP(hipEventRecord(a->ev0, s));
-    HP_CHECK_HIP(hipGraphLaunch(ge, s));
+    HP_CHECK_HIP(hipGraphLaunch(c.exec.h, s));
     HP_CHECK_HIP(hipEventRecord(a->ev1, s));
     HP_CHECK_HIP(hipEventSynchronize(a->ev1));
     float ms = 0.f;
     HP_CHECK_HIP(hipEventElapsedTime(&ms, a->ev0, a->ev1));
     *us_per_launch = 1e3 * ms / n;
-    (void)hipGraphExecDestroy(ge);
-    (void)hipGraphDestroy(g);
     return HP_OK;
 }
 

@@ -571,6 +571,12 @@ static int launch_pack(hp_buffer *b, const long long *slots, int64_t first, int6
 }
 int buffer_launch_pack(hp_buffer *b, int64_t n_new) { return launch_pack(b, b->st_slots.as<long long>(), 0, n_new); }
 
+// grow a staging allocation; moving it invalidates the captured cycles that read it (hp_buffer::gen)
+static int stage_ensure(hp_buffer *b, DevBuf &d, size_t need) {
+    if (need > d.bytes) ++b->gen;
+    return d.ensure(need);
+}
+
 // stage host episodes on the device (st_*): one pinned copy, one H2D.  copy-in semantics (replay_buffer.py:39-42): the
 // caller's arrays are read by the CPU memcpy below and never again; the DMA reads our pinned staging.
 static int buffer_stage(hp_buffer *b, const double *obs, const double *ag, const double *g, const double *actions,
@@ -578,7 +584,7 @@ static int buffer_stage(hp_buffer *b, const double *obs, const double *ag, const
     hipStream_t s = b->ctx->stream;
     const size_t n0 = n_new * b->ep_obs() * 8, n1 = n_new * b->ep_ag() * 8, n2 = n_new * b->ep_g() * 8,
                  n3 = n_new * b->ep_act() * 8;
-    HP_TRY(b->st_obs.ensure(n0 + n1 + n2 + n3));
+    HP_TRY(stage_ensure(b, b->st_obs, n0 + n1 + n2 + n3));
     char *dst = b->st_obs.as<char>();
     b->st_ag = reinterpret_cast<double *>(dst + n0);
     b->st_g = reinterpret_cast<double *>(dst + n0 + n1);
@@ -599,7 +605,7 @@ static int buffer_stage(hp_buffer *b, const double *obs, const double *ag, const
 int buffer_stage_and_store(hp_buffer *b, hp_rng *rng, const double *obs, const double *ag, const double *g,
                            const double *actions, int64_t n_new) {
     hipStream_t s = b->ctx->stream;
-    HP_TRY(b->st_slots.ensure(n_new * 8));
+    HP_TRY(stage_ensure(b, b->st_slots, n_new * 8));
     HP_TRY(buffer_stage(b, obs, ag, g, actions, n_new));
     HP_TRY(rng_launch_slots(rng, b, n_new, b->st_slots.as<int64_t>()));
     hipLaunchKernelGGL(k_store_scatter, dim3((unsigned)(n_new * STORE_PARTS)), dim3(256), 0, s, b->st_slots.as<long long>(),
@@ -621,8 +627,8 @@ int buffer_stage_pinned(hp_buffer *b, hp_rng *rng, const double *block, int64_t 
     hipStream_t s = b->ctx->stream;
     const size_t n0 = n_new * b->ep_obs() * 8, n1 = n_new * b->ep_ag() * 8, n2 = n_new * b->ep_g() * 8,
                  n3 = n_new * b->ep_act() * 8;
-    HP_TRY(b->st_slots.ensure(n_new * 8));
-    HP_TRY(b->st_obs.ensure(n0 + n1 + n2 + n3));
+    HP_TRY(stage_ensure(b, b->st_slots, n_new * 8));
+    HP_TRY(stage_ensure(b, b->st_obs, n0 + n1 + n2 + n3));
     char *dst = b->st_obs.as<char>();
     b->st_ag = reinterpret_cast<double *>(dst + n0);
     b->st_g = reinterpret_cast<double *>(dst + n0 + n1);
@@ -652,7 +658,7 @@ int buffer_stage_pinned(hp_buffer *b, hp_rng *rng, const double *block, int64_t 
 
 int buffer_stage_for_cycle(hp_buffer *b, const double *obs, const double *ag, const double *g, const double *actions,
                            int64_t n_new) {
-    HP_TRY(b->st_slots.ensure(n_new * 8));
+    HP_TRY(stage_ensure(b, b->st_slots, n_new * 8));
     HP_TRY(buffer_stage(b, obs, ag, g, actions, n_new));
     b->current_size = (b->current_size + n_new < b->size) ? b->current_size + n_new : b->size;
     b->n_transitions_stored += (int64_t)b->T * n_new;
@@ -1022,6 +1028,7 @@ extern "C" int hp_buffer_enable_f32_rows(hp_buffer *b) {
     }
     b->row_w = row_w;
     b->goal_w = goal_w;
+    ++b->gen;   // a cycle captured before now does not refresh the rows
     return launch_pack(b, nullptr, 0, b->size);      // (rows of unfilled slots hold whatever the allocation held: never sampled)
 }
 

@@ -74,10 +74,12 @@ __global__ void k_scale_div(float *v, int n, float denom) {
 }  // namespace
 
 // ---- internal entry points used by agent.hip (enqueue on the context's stream) ---------------------------
+// While the launch log is on (hp_agent_update_kernels' dry run) the collectives are named, not issued.
 int comm_allreduce_sum_f32(hp_comm *c, float *dev, size_t n) {
     RcclApi *api = rccl();
     if (!api) return HP_ERR_STATE;
     HP_KLOG("rccl:ncclAllReduce");
+    if (hp_klog) return HP_OK;
     HP_CHECK_NCCL(api, api->AllReduce(dev, dev, n, ncclFloat32, ncclSum, (ncclComm_t)c->nccl, c->ctx->stream));
     return HP_OK;
 }
@@ -85,6 +87,7 @@ int comm_allreduce_sum_f32(hp_comm *c, float *dev, size_t n) {
 int comm_allreduce_mean_f32(hp_comm *c, float *dev, size_t n) {
     HP_TRY(comm_allreduce_sum_f32(c, dev, n));
     HP_KLOG("k_scale_div");
+    if (hp_klog) return HP_OK;
     hipLaunchKernelGGL(k_scale_div, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->ctx->stream, dev, (int)n,
                        (float)c->world);
     HP_CHECK_HIP(hipGetLastError());

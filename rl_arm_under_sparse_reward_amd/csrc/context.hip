@@ -243,20 +243,17 @@ int hp_ctx_launch_floor(hp_ctx *ctx, int n, int graph, double *us_per_kernel) {
     HP_CHECK_HIP(hipEventCreate(&e1));
     float ms = 0.f;
     if (graph) {
-        hipGraph_t g;
-        hipGraphExec_t ge;
         HP_CHECK_HIP(hipStreamSynchronize(s));
-        HP_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        for (int i = 0; i < n; ++i) hipLaunchKernelGGL(k_floor_probe, dim3(1), dim3(64), 0, s, d);
-        HP_CHECK_HIP(hipStreamEndCapture(s, &g));
-        HP_CHECK_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-        HP_CHECK_HIP(hipGraphLaunch(ge, s));
+        const Captured c = capture_graph(s, [&] {
+            for (int i = 0; i < n; ++i) hipLaunchKernelGGL(k_floor_probe, dim3(1), dim3(64), 0, s, d);
+            return (int)HP_OK;
+        });
+        HP_TRY(c.status());
+        HP_CHECK_HIP(hipGraphLaunch(c.exec.h, s));
         HP_CHECK_HIP(hipEventRecord(e0, s));
-        HP_CHECK_HIP(hipGraphLaunch(ge, s));
+        HP_CHECK_HIP(hipGraphLaunch(c.exec.h, s));
         HP_CHECK_HIP(hipEventRecord(e1, s));
         HP_CHECK_HIP(hipEventSynchronize(e1));
-        (void)hipGraphExecDestroy(ge);
-        (void)hipGraphDestroy(g);
     } else {
         for (int i = 0; i < 64; ++i) hipLaunchKernelGGL(k_floor_probe, dim3(1), dim3(64), 0, s, d);
         HP_CHECK_HIP(hipEventRecord(e0, s));

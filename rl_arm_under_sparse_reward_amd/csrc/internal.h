@@ -65,6 +65,43 @@ struct DevBuf {
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// ------------------------------------------------------------------ stream capture
+struct GraphExec {   // an instantiated hipGraph, destroyed with its owner
+    hipGraphExec_t h = nullptr;
+    GraphExec() = default;
+    GraphExec(GraphExec &&o) noexcept : h(o.h) { o.h = nullptr; }
+    GraphExec &operator=(GraphExec &&o) noexcept { std::swap(h, o.h); return *this; }
+    ~GraphExec() { if (h) (void)hipGraphExecDestroy(h); }
+};
+struct Captured {
+    int st = HP_OK;              // what the enqueueing callable returned: the launch logic failed
+    hipError_t e = hipSuccess;   // the runtime refused the capture or its instantiation
+    GraphExec exec;              // set when both succeeded and the capture was not a dry run
+    int status() const {         // HP_OK or the first failure, with the error message set
+        if (st != HP_OK) return st;
+        HP_REQUIRE(e == hipSuccess, HP_ERR_HIP, "stream capture failed: %s", hipGetErrorString(e));
+        return HP_OK;
+    }
+};
+// Records what enqueue() puts on s under a thread-local capture and instantiates it -- or discards it (instantiate = false: a dry
+// run).  Nothing enqueued runs here.  The hipGraph_t is destroyed on every path; a runtime error is cleared from HIP's last error.
+template <class F> Captured capture_graph(hipStream_t s, F &&enqueue, bool instantiate = true) {
+    Captured c;
+    c.e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
+    if (c.e == hipSuccess) {
+        c.st = enqueue();
+        hipGraph_t g = nullptr;
+        c.e = hipStreamEndCapture(s, &g);
+        if (c.st == HP_OK && c.e == hipSuccess && instantiate) c.e = hipGraphInstantiate(&c.exec.h, g, nullptr, nullptr, 0);
+        if (g) (void)hipGraphDestroy(g);
+    }
+    if (c.e != hipSuccess) {
+        c.exec.h = nullptr;
+        (void)hipGetLastError();
+    }
+    return c;
+}
+
 // ------------------------------------------------------------------ context
 struct hp_ctx {
     int device = 0;
@@ -189,6 +226,7 @@ struct hp_buffer {
     int32_t row_w = 0, goal_w = 0;
     // sampling scratch
     DevBuf plan, out;
+    uint64_t gen = 0;   // bumped whenever what a captured cycle reads moves or appears (staging reallocated, throughput rows enabled)
     size_t ep_obs() const { return (size_t)(T + 1) * obs_dim; }
     size_t ep_ag() const { return (size_t)(T + 1) * goal_dim; }
     size_t ep_g() const { return (size_t)T * goal_dim; }

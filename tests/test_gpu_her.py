@@ -453,10 +453,12 @@ def test_sample_device_f32_rows_throughput_mode(n, B, k, mode, clip_obs):
     assert state_equal(dev, *rs.get_state()[1:3])
 
 
-def test_f32_rows_follow_the_cycle_graph_and_keep_losses_within_the_bar():
+@pytest.mark.parametrize("enable_after", [0, 1], ids=["enabled_before_cycles", "enabled_after_graph_captured"])
+def test_f32_rows_follow_the_cycle_graph_and_keep_losses_within_the_bar(enable_after):
     """The mirror behind hp_agent_train_cycle's in-launch scatter (k_cycle_open -> k_pack_rows inside the cycle graph), and the
     north-star bar on what the mode changes: an update on a throughput-mode minibatch has both losses within 1e-5 (relative) of the
-    same update on the float64-row minibatch."""
+    same update on the float64-row minibatch.  Enabled after a cycle has captured its graph, the mirror must be followed by
+    the cycles after it all the same (the cycle graph is captured again)."""
     import torch
     from oracle import ddpg_update as oupd
     from rl_arm_under_sparse_reward_amd.arguments import Args
@@ -467,8 +469,9 @@ def test_f32_rows_follow_the_cycle_graph_and_keep_losses_within_the_bar():
     rng = fresh_rng(11)
     agent = ddpg_agent(Args(batch_size=256, buffer_size=40 * 100), None, dict(ENV_PARAMS), ctx=ctx(), rng=rng)
     agent.buffer.store_episode(make_episodes(40, seed=5, mode="walk"))      # full: the cycles below overwrite random slots
-    agent.buffer.enable_f32_rows()
     for c in range(3):
+        if c == enable_after:
+            agent.buffer.enable_f32_rows()
         agent.train_cycle(make_episodes(2, seed=60 + c, mode="walk"), 4)
     state = rng.get_state()
     a = agent.buffer.sample_device(512, agent.o_norm, agent.g_norm, clip_obs=200)
