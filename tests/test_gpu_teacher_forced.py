@@ -35,15 +35,16 @@ Batch sizes of BASELINE configs 2 / 5 / 3-4 / 4096 with their default engines, a
 in a 1-rank group."""
 import os
 import socket
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from gpu_common import ENV_PARAMS, DeviceEpisodeBuffer, fresh_rng, state_equal
+from gpu_common import ENV_PARAMS, DeviceEpisodeBuffer, fresh_rng, make_shape_episodes, state_equal
 from oracle import ddpg_update as oupd
 from oracle.her_replay import EpisodeStore, future_probability
-from oracle.running_norm import RunningNorm, update_normalizers
+from oracle.running_norm import RunningNorm, preproc_og, update_normalizers
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd.arguments import Args
 from rl_arm_under_sparse_reward_amd.ddpg_agent import (NET_ACTOR, NET_ACTOR_TARGET, NET_CRITIC, NET_CRITIC_TARGET,
@@ -142,40 +143,64 @@ def _teach(agent, learner):
     return sa
 
 
-def _run(batch, k, comm=None, n_steps=N_STEPS, n_eps=64):
+def _run(batch, k, comm=None, n_steps=N_STEPS, n_eps=64, env_params=None, hp=None, before_step=None, on_minibatch=None,
+         polyak_every=10, spare_eps=0):
+    """`n_steps` teacher-forced updates.  env_params: the GoalEnv shape and action_max (bmirobot's 27/3/4 and 0.5 when None;
+    other shapes get gpu_common.make_shape_episodes); hp: Args overrides of the learner's hyperparameters, given to the
+    device agent, the oracle learner, the normalizers, the Adam twins and the float64 yardstick alike.  before_step(i, side)
+    may change the oracle's state before it is taught to the device; on_minibatch(i, side, mb) sees each step's minibatch
+    before the oracle's update; spare_eps: room in the replay buffer for that many more episodes.  Returns the worst
+    numbers, the agent and `side`: the oracle's learner, store, normalizers and RNG, the episodes and the settings."""
     torch.set_num_threads(4)
-    eps = make_episodes(n_eps, seed=3, mode="walk")
+    ep = dict(env_params or ENV_PARAMS)
+    hp = dict(hp or {})
+    args = Args(batch_size=batch, buffer_size=(n_eps + spare_eps) * ep["max_timesteps"], replay_k=k, **hp)
+    od, gd, ad, T = ep["obs"], ep["goal"], ep["action"], ep["max_timesteps"]
+    if env_params is None:
+        eps = make_episodes(n_eps, seed=3, mode="walk")
+    else:
+        eps = make_shape_episodes(n_eps, od, gd, ad, T, seed=3)
     torch.manual_seed(0)
     rng = fresh_rng(7)
-    agent = ddpg_agent(Args(batch_size=batch, buffer_size=n_eps * 100, replay_k=k), None, dict(ENV_PARAMS), comm=comm, rng=rng)
+    agent = ddpg_agent(args, None, ep, comm=comm, rng=rng)
     a0 = {kk: v.detach().clone() for kk, v in agent.actor_network.state_dict().items()}
     c0 = {kk: v.detach().clone() for kk, v in agent.critic_network.state_dict().items()}
-    learner = oupd.DDPGLearner(a0, c0)
+    amax = float(ep["action_max"])
+    learner = oupd.DDPGLearner(a0, c0, max_action=amax, gamma=args.gamma, action_l2=args.action_l2,
+                               lr_actor=args.lr_actor, lr_critic=args.lr_critic, polyak=args.polyak)
+    lrs = {"actor": args.lr_actor, "critic": args.lr_critic}
     rs = np.random.RandomState(7)
-    st = EpisodeStore(100, 27, 3, 4, n_eps * 100)
+    st = EpisodeStore(T, od, gd, ad, (n_eps + spare_eps) * T)
     fp = future_probability("future", k)
-    on, gn = RunningNorm(27, default_clip_range=5), RunningNorm(3, default_clip_range=5)
+    on, gn = RunningNorm(od, default_clip_range=args.clip_range), RunningNorm(gd, default_clip_range=args.clip_range)
     st.store_episode(eps, rs)
     agent.buffer.store_episode(eps)
     two = [a[-2:] for a in eps]
-    scratch = DeviceEpisodeBuffer(2, 100, 27, 3, 4)
+    scratch = DeviceEpisodeBuffer(2, T, od, gd, ad)
     scratch.store(rng, two)
-    _lib.check(agent.lib.hp_norm_update_from_staged(scratch.h, rng.h, agent.o_norm.h, agent.g_norm.h, fp, 200.0))
+    _lib.check(agent.lib.hp_norm_update_from_staged(scratch.h, rng.h, agent.o_norm.h, agent.g_norm.h, fp, float(args.clip_obs)))
     agent.o_norm.recompute_stats(); agent.g_norm.recompute_stats()
-    update_normalizers(on, gn, two, fp, rs)
+    update_normalizers(on, gn, two, fp, rs, clip_obs=args.clip_obs)
+    side = SimpleNamespace(learner=learner, st=st, rs=rs, on=on, gn=gn, fp=fp, rng=rng, args=args, env_params=ep, lrs=lrs,
+                           eps=eps, batch=batch)
     worst_loss, worst_param, worst_grad, worst_adam, worst_vs64, n_ambiguous = 0.0, 0.0, 0.0, 0.0, 0.0, 0
     for i in range(n_steps):
+        if before_step is not None:
+            before_step(i, side)
         step = _teach(agent, learner)
         assert step == i
         m_dev, v_dev, s_dev = agent.get_adam_state(NET_CRITIC)       # the hook round-trips (pack/unpack is lossless)
         assert s_dev == i and np.array_equal(m_dev, _adam_flat(learner.critic_optim, learner.critic)[0])
-        twins = {"actor": _AdamTwin(learner.actor, learner.actor_optim, 1e-3),
-                 "critic": _AdamTwin(learner.critic, learner.critic_optim, 1e-3)}     # oracle state BEFORE the step
+        twins = {"actor": _AdamTwin(learner.actor, learner.actor_optim, lrs["actor"]),
+                 "critic": _AdamTwin(learner.critic, learner.critic_optim, lrs["critic"])}     # oracle state BEFORE the step
         agent._update_network(1)
         got = agent.last_losses(1)[0]
         tr, _ = st.sample(batch, fp, rs)
-        mb = oupd.minibatch_tensors(tr, on, gn)
-        g64 = _f64_gradients(learner.actor, learner.critic, learner.actor_target, learner.critic_target, *mb)
+        mb = oupd.minibatch_tensors(tr, on, gn, clip_obs=args.clip_obs)
+        if on_minibatch is not None:
+            on_minibatch(i, side, mb)
+        g64 = _f64_gradients(learner.actor, learner.critic, learner.actor_target, learner.critic_target, *mb,
+                             max_action=amax, gamma=args.gamma, action_l2=args.action_l2)
         res = learner.update(*mb)
         for j, name in enumerate(("actor_loss", "critic_loss")):
             rel = abs(float(got[j]) - res[name]) / max(abs(res[name]), 1e-3)
@@ -206,7 +231,7 @@ def _run(batch, k, comm=None, n_steps=N_STEPS, n_eps=64):
             p_dev = p_dev32.astype(np.float64)
             # allowed: one ulp of the parameter (final rounding of p + step) + 5e-7 of the step size lr (the step itself is
             # ~6 float32 operations, and torch's CPU kernels fuse some multiply-adds the device keeps apart): 5e-10
-            allowed = np.spacing(np.abs(p_twin32)).astype(np.float64) + 5e-7 * 1e-3
+            allowed = np.spacing(np.abs(p_twin32)).astype(np.float64) + 5e-7 * lrs[name]
             ulps = np.abs(p_dev - p_twin32.astype(np.float64)) / allowed
             aerr = float(ulps.max())
             worst_adam = max(worst_adam, aerr)
@@ -219,7 +244,7 @@ def _run(batch, k, comm=None, n_steps=N_STEPS, n_eps=64):
                 assert err <= PARAM_ATOL, (i, name, "param", err, int(well.sum()))
             assert float(np.median(np.abs(p_dev - p_ref))) <= 1e-7, (i, name)
         assert agent.get_adam_state(NET_ACTOR)[2] == i + 1
-        if i % 10 == 9:            # ddpg_agent.py:149-150 every so often, so that targets != online nets in later steps
+        if i % polyak_every == polyak_every - 1:   # ddpg_agent.py:149-150 every so often: targets != online nets later on
             agent._soft_update_target_network(); learner.soft_update()
             tgt = agent._get_flat(NET_CRITIC_TARGET).astype(np.float64)
             assert float(np.max(np.abs(tgt - learner.flat("critic_target")))) <= PARAM_ATOL
@@ -227,14 +252,14 @@ def _run(batch, k, comm=None, n_steps=N_STEPS, n_eps=64):
     # of 2 x 40 (step, network) pairs: ties that flip a mask are rare events, not an excuse -- their number grows with the
     # number of pre-activations per update, i.e. with the batch (observed: 1 at batch 256, 9 at 4096)
     assert n_ambiguous <= 3 * max(1, batch // 1024), n_ambiguous
-    return (worst_loss, worst_grad, worst_adam, worst_param, worst_vs64, n_ambiguous), agent
+    return (worst_loss, worst_grad, worst_adam, worst_param, worst_vs64, n_ambiguous), agent, side
 
 
 @pytest.mark.parametrize("batch,k", [(256, 4), (512, 8), (1024, 4), (4096, 4)],
                          ids=["config2_b256", "config5_b512_k8", "config3_4_b1024", "b4096"])
 def test_every_update_meets_the_north_star_bar_single_rank(batch, k, monkeypatch):
     monkeypatch.setenv("RLARM_KEEP_GRADS", "1")      # the optimizer epilogues also write the gradient out (read by hp_agent_create)
-    worst, agent = _run(batch, k)
+    worst, agent, _ = _run(batch, k)
     print(f"teacher-forced batch {batch} k {k} engine {agent.engine()}: worst over 40 steps: loss rel {worst[0]:.2e}, "
           f"grad / max|g| {worst[1]:.2e} (error vs float64 = {worst[4]:.2f} x torch float32's), optimizer vs torch.optim.Adam {worst[2]:.2f} x (1 ulp + 5e-10), well-conditioned param {worst[3]:.2e}, ReLU ties {worst[5]}")
 
@@ -247,7 +272,7 @@ def test_every_update_meets_the_bar_through_the_split_launch(batch, k, n_eps, mo
     two in-launch counters, the actor's tiles behind it -- on the 64-episode buffer and on the full 5000-episode shard."""
     monkeypatch.setenv("RLARM_KEEP_GRADS", "1")
     monkeypatch.setenv("RLARM_SPLIT", "1")
-    worst, agent = _run(batch, k, n_eps=n_eps, n_steps=N_STEPS if n_eps <= 64 else 20)
+    worst, agent, _ = _run(batch, k, n_eps=n_eps, n_steps=N_STEPS if n_eps <= 64 else 20)
     print(f"teacher-forced (split launch) batch {batch} k {k} episodes {n_eps}: worst: loss rel {worst[0]:.2e}, grad / max|g| {worst[1]:.2e} "
           f"(vs float64 = {worst[4]:.2f} x torch float32's), optimizer {worst[2]:.2f} x (1 ulp + 5e-10), param {worst[3]:.2e}, ReLU ties {worst[5]}")
 
@@ -256,7 +281,7 @@ def test_every_update_meets_the_bar_through_the_split_launch(batch, k, n_eps, mo
 def test_every_update_meets_the_bar_on_the_full_shard(batch, k, monkeypatch):
     """the teacher-forced bars on the BASELINE shard (5000 episodes, 149 MB of float64 rows), default engines."""
     monkeypatch.setenv("RLARM_KEEP_GRADS", "1")
-    worst, agent = _run(batch, k, n_eps=5000, n_steps=20)
+    worst, agent, _ = _run(batch, k, n_eps=5000, n_steps=20)
     print(f"teacher-forced full shard batch {batch} k {k} engine {agent.engine()}: worst over 20 steps: loss rel {worst[0]:.2e}, "
           f"grad / max|g| {worst[1]:.2e}, optimizer {worst[2]:.2f} x (1 ulp + 5e-10), param {worst[3]:.2e}, ReLU ties {worst[5]}")
 
@@ -291,7 +316,7 @@ def test_every_update_meets_the_bar_through_the_data_parallel_optimizer(transpor
     comm = None
     try:
         comm = Communicator(0, force=True)
-        worst, agent = _run(256, 4, comm=comm)
+        worst, agent, _ = _run(256, 4, comm=comm)
         assert (agent._peer is not None) == (transport == "peer")
         assert (agent._native_comm is not None) == (transport == "native")
         kernels = agent.update_kernels(1)["updates"][0]
@@ -310,3 +335,196 @@ def test_every_update_meets_the_bar_through_the_data_parallel_optimizer(transpor
             comm.close()
         _lib.Context.default().set_stream(None)
         dist.destroy_process_group()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# The same bars away from the reference's defaults.  Every hyperparameter the learner reads, as in
+# tests/golden/ddpg_update_hparams.npz (tools/gen_golden.py DDPG_HPARAMS): gamma 0.9 (clip_return 10), action_l2 0.5,
+# unequal learning rates (a swapped per-element rate selection in an optimizer kernel is invisible at 1e-3 / 1e-3),
+# polyak 0.9, and clips that bite -- clip_obs 0.8 clips ~16% of the raw values, clip_range 1.5 ~17% of the normalised ones;
+# action_max 0.7 is not a power of two, so a dropped or reordered division by it is not exact.
+HP = dict(gamma=0.9, action_l2=0.5, lr_actor=3e-4, lr_critic=2e-3, polyak=0.9, clip_range=1.5, clip_obs=0.8)
+HP_ENV = dict(ENV_PARAMS, action_max=0.7)
+CASE_STEPS = 12              # polyak every 4 steps: later steps see targets that differ from the online nets
+
+# launch structures of one update: switch name -> environment read by hp_agent_create
+LAUNCH = {"default": {}, "split": {"RLARM_SPLIT": "1"}, "slab8_rows8": {"RLARM_SLAB_ROWS": "8"},
+          "slab8_rows16": {"RLARM_SLAB_ROWS": "16"}, "slab32": {"RLARM_ENGINE": "slab32"}, "dw64": {"RLARM_DW64": "s3"},
+          "adam_unfused": {"RLARM_FUSE_ADAM": "0"}, "layers": {"RLARM_ENGINE": "layers"},
+          "slab32_dw64": {"RLARM_ENGINE": "slab32", "RLARM_DW64": "s3"}}
+
+
+def _launch(name, monkeypatch):
+    monkeypatch.setenv("RLARM_KEEP_GRADS", "1")
+    for kk, v in LAUNCH[name].items():
+        monkeypatch.setenv(kk, v)
+
+
+def _expect_engine(agent, launch, engine):
+    """The engine a case is about, asserted, so that a change of the default table cannot move the case elsewhere silently."""
+    e = agent.engine()
+    assert e["engine"] == engine, (launch, e)
+    first = agent.update_kernels(1)["updates"][0][0]
+    if launch == "split":
+        assert first.startswith("k_fb_split8"), (launch, first)
+    elif engine == "slab8":
+        assert first == "k_fb_slab8", (launch, first)
+    return e
+
+
+def _report(tag, worst, agent, n_steps, extra=""):
+    e = agent.engine()
+    print(f"teacher-forced {tag} engine {e['engine']} rows {e['slab_rows']} {e['weight_grad']}: worst over {n_steps} steps: "
+          f"loss rel {worst[0]:.2e}, grad / max|g| {worst[1]:.2e} (error vs float64 = {worst[4]:.2f} x torch float32's), "
+          f"optimizer vs torch.optim.Adam {worst[2]:.2f} x (1 ulp + 5e-7 lr), well-conditioned param {worst[3]:.2e}, "
+          f"ReLU ties {worst[5]}{extra}")
+
+
+@pytest.mark.parametrize("launch", ["default", "split", "slab8_rows8", "slab8_rows16", "slab32", "dw64", "adam_unfused",
+                                    "layers"])
+def test_every_update_meets_the_bar_at_other_hyperparameters(launch, monkeypatch):
+    """Case A: HP at 27/3/4, batch 256, through every launch structure of the update."""
+    _launch(launch, monkeypatch)
+    worst, agent, _ = _run(256, 4, n_steps=CASE_STEPS, hp=HP, env_params=HP_ENV, polyak_every=4)
+    _expect_engine(agent, launch, {"slab32": "slab32", "layers": "layers"}.get(launch, "slab8"))
+    _report(f"hparams {launch} batch 256", worst, agent, CASE_STEPS)
+
+
+@pytest.mark.parametrize("batch,k,want", [(7, 4, ("slab8", 4, "gemm_lds 32x32")), (449, 4, ("slab8", 4, "gemm_lds 32x32")),
+                                          (513, 8, ("slab8", 8, "gemm_lds 32x32")), (1281, 4, ("slab8", 16, "gemm_lds 32x32")),
+                                          (2080, 4, ("slab32", 32, "dw64 split 3"))])
+def test_every_update_meets_the_bar_at_other_hyperparameters_ragged(batch, k, want, monkeypatch):
+    """Case A, ragged batches on the default table: padding rows, 1/B, the dw64 slices of a batch that is no multiple of 64."""
+    _launch("default", monkeypatch)
+    worst, agent, _ = _run(batch, k, n_steps=CASE_STEPS, hp=HP, env_params=HP_ENV, polyak_every=4)
+    e = agent.engine()
+    assert (e["engine"], e["slab_rows"], e["weight_grad"]) == want, e
+    _report(f"hparams default batch {batch} k {k}", worst, agent, CASE_STEPS)
+
+
+def _target_q_probe(side):
+    """The next states of every stored transition, clipped and normalised like a minibatch (float32)."""
+    if not hasattr(side, "x_next_probe"):
+        obs, _, g, _ = side.eps
+        o, gg = preproc_og(obs[:, 1:, :].reshape(-1, obs.shape[-1]), g.reshape(-1, g.shape[-1]), side.args.clip_obs)
+        side.x_next_probe = torch.tensor(np.concatenate([side.on.normalize(o), side.gn.normalize(gg)], axis=1), dtype=torch.float32)
+    return side.x_next_probe
+
+
+def _spread_target_q(i, side, lo=-4.5, hi=4.5):
+    """Before every step: rescale and shift the oracle critic target's head (q_out) so that Q' of the stored next states
+    runs from `lo` at its 10th to `hi` at its 90th percentile.  With gamma = 0.5 (clip_return 2) and r in {-1, 0},
+    r + gamma Q' then falls below -2 on some rows and above 0 on others: both sides of the clamp of ddpg_agent.py:259-260."""
+    L, amax = side.learner, side.env_params["action_max"]
+    x = _target_q_probe(side)
+    with torch.no_grad():
+        q = oupd.critic_forward(L.critic_target, x, oupd.actor_forward(L.actor_target, x, amax), amax).double().numpy()
+        q10, q90 = np.percentile(q, [10, 90])
+        scale = (hi - lo) / (q90 - q10)
+        L.critic_target["q_out.weight"].mul_(float(scale))
+        L.critic_target["q_out.bias"].mul_(float(scale)).add_(float(lo - scale * q10))
+
+
+def _clamp_branches(i, side, mb):
+    """float64 target of the taught state on this minibatch: the fraction of rows clamped at -clip_return and at 0."""
+    L, amax, gamma = side.learner, side.env_params["action_max"], side.args.gamma
+    AT = {kk: v.detach().double() for kk, v in L.actor_target.items()}
+    CT = {kk: v.detach().double() for kk, v in L.critic_target.items()}
+    _, xn, _, r = (t.double() for t in mb)
+    with torch.no_grad():
+        y = (r + gamma * oupd.critic_forward(CT, xn, oupd.actor_forward(AT, xn, amax), amax)).numpy()
+    lo, hi = float(np.mean(y < -1 / (1 - gamma))), float(np.mean(y > 0))
+    assert lo >= 0.05 and hi >= 0.05, (i, lo, hi)
+    side.branch_min = min(getattr(side, "branch_min", (1.0, 1.0))[0], lo), min(getattr(side, "branch_min", (1.0, 1.0))[1], hi)
+
+
+@pytest.mark.parametrize("launch", ["default", "split", "slab32", "layers"])
+def test_every_update_meets_the_bar_on_both_clamp_branches(launch, monkeypatch):
+    """Case B: gamma 0.5 puts clip_return at 2; the target critic's head is spread so that every minibatch has rows clamped
+    at -2 AND rows clamped at 0 (>= 5% each, asserted in float64 on the taught state, so the case cannot pass vacuously)."""
+    _launch(launch, monkeypatch)
+    hp = dict(HP, gamma=0.5)
+    worst, agent, side = _run(256, 4, n_steps=CASE_STEPS, hp=hp, env_params=HP_ENV, polyak_every=4,
+                              before_step=_spread_target_q, on_minibatch=_clamp_branches)
+    _expect_engine(agent, launch, {"slab32": "slab32", "layers": "layers"}.get(launch, "slab8"))
+    _report(f"clamp branches {launch}", worst, agent, CASE_STEPS,
+            f", rows clamped at -clip_return >= {side.branch_min[0]:.2f}, at 0 >= {side.branch_min[1]:.2f}")
+
+
+# (obs, goal, action, action_max, default engine): the slab engines' eligibility edges and the first shapes beyond them
+SHAPES = [(13, 3, 4, 0.7, "slab8"),      # xdim 16: the action at column 16, ldx 32
+          (29, 3, 4, 0.5, "slab8"),      # xdim 32: K1 of the actor full, the action right after x, no zero gap
+          (29, 3, 1, 2.0, "slab8"),      # one action
+          (20, 1, 3, 0.7, "slab8"),      # one-wide goal, three actions
+          (30, 3, 4, 0.7, "layers"),     # xdim 33: the first shape of the layer engine
+          (25, 2, 5, 1.3, "layers"),     # five actions
+          (60, 3, 7, 0.5, "layers")]
+SHAPE_CASES = [(s, "default") for s in SHAPES] + [(s, launch) for s in SHAPES if s[4] == "slab8" for launch in ("split", "slab32")]
+
+
+@pytest.mark.parametrize("shape,launch", SHAPE_CASES, ids=[f"{o}_{g}_{a}_{launch}" for (o, g, a, _, _), launch in SHAPE_CASES])
+def test_every_update_meets_the_bar_at_other_env_shapes(shape, launch, monkeypatch):
+    """Case C: GoalEnv shapes other than 27/3/4, default hyperparameters, 24 episodes of 50 steps."""
+    o, g, a, amax, engine = shape
+    _launch(launch, monkeypatch)
+    env = {"obs": o, "goal": g, "action": a, "action_max": amax, "max_timesteps": 50}
+    worst, agent, _ = _run(256, 4, n_steps=CASE_STEPS, n_eps=24, env_params=env, polyak_every=4)
+    _expect_engine(agent, launch, "slab32" if launch == "slab32" else engine)
+    _report(f"shape {o}/{g}/{a} action_max {amax} {launch}", worst, agent, CASE_STEPS)
+
+
+def _load_learner(learner, agent):
+    """oracle state := device state (parameters, targets, Adam moments and step count), the inverse of _teach."""
+    for slot, which in ((NET_ACTOR, "actor"), (NET_CRITIC, "critic"), (NET_ACTOR_TARGET, "actor_target"),
+                        (NET_CRITIC_TARGET, "critic_target")):
+        flat, off = agent._get_flat(slot), 0
+        for t in getattr(learner, which).values():
+            with torch.no_grad():
+                t.copy_(torch.from_numpy(flat[off:off + t.numel()].reshape(t.shape)))
+            off += t.numel()
+    for slot, params, optim in ((NET_ACTOR, learner.actor, learner.actor_optim), (NET_CRITIC, learner.critic, learner.critic_optim)):
+        m, v, step = agent.get_adam_state(slot)
+        off = 0
+        for p in params.values():
+            n = p.numel()
+            st = optim.state[p]
+            st["exp_avg"].copy_(torch.from_numpy(m[off:off + n].reshape(p.shape)))
+            st["exp_avg_sq"].copy_(torch.from_numpy(v[off:off + n].reshape(p.shape)))
+            st["step"].fill_(step)
+            off += n
+
+
+@pytest.mark.parametrize("launch", ["default", "split", "slab32_dw64", "layers"])
+def test_polyak_folded_into_the_last_update_at_other_polyak(launch, monkeypatch):
+    """Case D: polyak 0.9 folded into the optimizer epilogue of a cycle's last update (slab engines; k_polyak on layers).
+    The targets must equal (1-p) p_new + p t_old in float32 BIT FOR BIT (numpy float32: correctly rounded, unfused -- the
+    expression of k_polyak_frag), p_new being the device's own post-step parameters; then, with the targets left as the
+    cycle wrote them, one more update against the oracle loaded from the device's state meets the loss bar, which it
+    cannot if the folded write reached the arena but not the forward-fragment copy the next update's target chains read."""
+    _launch(launch, monkeypatch)
+    worst, agent, side = _run(256, 4, n_steps=4, hp=HP, env_params=HP_ENV, polyak_every=4, spare_eps=4)
+    _expect_engine(agent, launch, "slab32" if launch == "slab32_dw64" else "layers" if launch == "layers" else "slab8")
+    learner, p = side.learner, np.float32(side.args.polyak)
+    _teach(agent, learner)
+    t_old = {s: agent._get_flat(s) for s in (NET_ACTOR_TARGET, NET_CRITIC_TARGET)}
+    assert not np.array_equal(t_old[NET_ACTOR_TARGET], agent._get_flat(NET_ACTOR))
+    new = make_episodes(4, seed=11, mode="walk")
+    side.st.store_episode(new, side.rs)
+    agent.train_cycle(new, n_batches=1)                     # store + normalizer + 1 update + polyak, one graph
+    update_normalizers(side.on, side.gn, new, side.fp, side.rs, clip_obs=side.args.clip_obs)
+    side.st.sample(256, side.fp, side.rs)
+    for src, tgt in ((NET_ACTOR, NET_ACTOR_TARGET), (NET_CRITIC, NET_CRITIC_TARGET)):
+        want = np.float32(1 - side.args.polyak) * agent._get_flat(src) + p * t_old[tgt]
+        got = agent._get_flat(tgt)
+        assert want.dtype == np.float32 and np.array_equal(got.view(np.uint32), want.view(np.uint32)), \
+            (launch, tgt, int(np.sum(got != want)), float(np.max(np.abs(got - want))))
+    assert np.array_equal(agent.o_norm.mean, side.on.mean) and np.array_equal(agent.g_norm.std, side.gn.std)
+    _load_learner(learner, agent)
+    agent._update_network(1)
+    got = agent.last_losses(1)[0]
+    tr, _ = side.st.sample(256, side.fp, side.rs)
+    res = learner.update(*oupd.minibatch_tensors(tr, side.on, side.gn, clip_obs=side.args.clip_obs))
+    rel = [abs(float(got[j]) - res[nm]) / max(abs(res[nm]), 1e-3) for j, nm in enumerate(("actor_loss", "critic_loss"))]
+    assert max(rel) <= LOSS_RTOL, (launch, got, res["actor_loss"], res["critic_loss"])
+    assert state_equal(side.rng, *side.rs.get_state()[1:3])
+    _report(f"folded polyak 0.9 {launch}", worst, agent, 4, f"; targets bit-exact, next update loss rel {max(rel):.2e}")

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from conftest import bits, load_golden
-from gpu_common import ENV_PARAMS, fresh_rng, state_equal
+from gpu_common import ENV_PARAMS, fresh_rng, make_shape_episodes, state_equal
 from oracle import ddpg_update as oupd
 from oracle.her_replay import EpisodeStore, future_probability
 from oracle.running_norm import RunningNorm, update_normalizers
@@ -21,10 +21,10 @@ pytestmark = pytest.mark.gpu
 LOSS_RTOL = 1e-5
 
 
-def make_agent(batch=256, n_eps=64, seed=125, replay_k=4, **kw):
+def make_agent(batch=256, n_eps=64, seed=125, replay_k=4, env_params=None, **kw):
     args = Args(batch_size=batch, buffer_size=n_eps * 100, replay_k=replay_k, **kw)
     rng = fresh_rng(seed)
-    return ddpg_agent(args, None, dict(ENV_PARAMS), rng=rng), rng
+    return ddpg_agent(args, None, dict(env_params or ENV_PARAMS), rng=rng), rng
 
 
 def close(a, b, atol):
@@ -124,6 +124,85 @@ def test_three_sampled_updates_from_seed_golden(engine, monkeypatch):
     update_agrees(agent._get_flat(NET_ACTOR_TARGET), g["actor_target_after_polyak"], g["init_actor"], 2e-2, 2e-8)
     update_agrees(agent._get_flat(NET_CRITIC_TARGET), g["critic_target_after_polyak"], g["init_critic"], 2e-2, 2e-8)
     assert state_equal(rng, g["key"], g["pos"])            # sampler consumed exactly the reference's words
+
+
+# tests/golden/ddpg_update_hparams.npz: the same pipeline as ddpg_update.npz with every learner hyperparameter off its default
+# (gamma 0.9, action_l2 0.5, lr 3e-4 / 2e-3, polyak 0.9, clip_range 1.5, clip_obs 0.8, action_max 0.7); its arrays hold the
+# fixture's probe elements of each parameter vector, its initial weights regenerate from torch.manual_seed(0)
+def _hparams_agent(g):
+    import hashlib
+    hp = dict(zip((str(n) for n in g["hparam_names"]), (float(v) for v in g["hparams"])))
+    amax = hp.pop("action_max")
+    n_eps, _, np_seed, B, k = (int(x) for x in g["meta"])
+    torch.manual_seed(0)                 # the actor / critic containers draw their init like models.py (ddpg_agent.py:24-25)
+    agent, rng = make_agent(batch=B, n_eps=n_eps, seed=np_seed, replay_k=k, env_params=dict(ENV_PARAMS, action_max=amax), **hp)
+    for slot, nm in ((NET_ACTOR, "actor"), (NET_CRITIC, "critic")):
+        assert hashlib.sha256(agent._get_flat(slot).tobytes()).hexdigest() == str(g[f"init_{nm}_sha256"]), nm
+    return agent, rng, hp
+
+
+@pytest.mark.parametrize("engine", ENGINES)
+def test_one_update_on_identical_minibatch_hparams_golden(engine, monkeypatch):
+    """test_one_update_on_identical_minibatch_golden at the fixture's hyperparameters: the losses carry gamma, clip_return,
+    action_l2 and action_max, the post-step parameters each network's own learning rate, the soft update polyak 0.9."""
+    _select_engine(engine, monkeypatch)
+    g = load_golden("ddpg_update_hparams.npz")
+    agent, _, hp = _hparams_agent(g)
+    pa, pc = g["probe_actor"], g["probe_critic"]
+    init_a, init_c = agent._get_flat(NET_ACTOR), agent._get_flat(NET_CRITIC)
+    la, lc = agent.update_on_minibatch(g["x_step1"], g["x_next_step1"], g["a_step1"], g["r_step1"])
+    assert abs(la - g["actor_loss"][0]) <= LOSS_RTOL * abs(g["actor_loss"][0]), (la, g["actor_loss"][0])
+    assert abs(lc - g["critic_loss"][0]) <= LOSS_RTOL * abs(g["critic_loss"][0]), (lc, g["critic_loss"][0])
+    ga, gc = agent.get_flat_grads(NET_ACTOR), agent.get_flat_grads(NET_CRITIC)
+    assert close(ga[pa], g["actor_grads_step1"], 2e-5 * float(g["actor_grads_step1_absmax"]))
+    assert close(gc[pc], g["critic_grads_step1"], 2e-5 * float(g["critic_grads_step1_absmax"]))
+    big = np.abs(g["critic_grads_step1"]) > 1e-3 * float(g["critic_grads_step1_absmax"])
+    assert np.allclose(gc[pc][big], g["critic_grads_step1"][big], rtol=2e-3, atol=0)
+    assert close(agent._get_flat(NET_ACTOR)[pa], g["actor_after_step1"], 5e-6)
+    assert close(agent._get_flat(NET_CRITIC)[pc], g["critic_after_step1"], 5e-6)
+    m, v, step = agent.get_adam_state(NET_CRITIC)
+    assert step == 1
+    assert np.allclose(m[pc], 0.1 * g["critic_grads_step1"], rtol=1e-3, atol=1e-9)
+    assert np.array_equal(agent._get_flat(NET_ACTOR_TARGET), init_a)
+    agent._soft_update_target_network()
+    for src, tgt, init in ((NET_ACTOR, NET_ACTOR_TARGET, init_a), (NET_CRITIC, NET_CRITIC_TARGET, init_c)):
+        want = np.float32(1 - hp["polyak"]) * agent._get_flat(src) + np.float32(hp["polyak"]) * init
+        assert np.array_equal(bits(agent._get_flat(tgt)), bits(want.astype(np.float32))), tgt
+
+
+@pytest.mark.parametrize("engine", ENGINES)
+def test_three_sampled_updates_from_seed_hparams_golden(engine, monkeypatch):
+    """test_three_sampled_updates_from_seed_golden at the fixture's hyperparameters: clip_obs in the normalizer update and in
+    the update path's gather, clip_range in its normalisation, then three sampled updates and a polyak-0.9 soft update."""
+    _select_engine(engine, monkeypatch)
+    g = load_golden("ddpg_update_hparams.npz")
+    agent, rng, hp = _hparams_agent(g)
+    pa, pc = g["probe_actor"], g["probe_critic"]
+    init_a, init_c = agent._get_flat(NET_ACTOR)[pa], agent._get_flat(NET_CRITIC)[pc]
+    n_eps, dseed = (int(x) for x in g["meta"][:2])
+    eps = make_episodes(n_eps, seed=dseed, mode="walk")
+    assert episode_checksum(eps) == float(g["checksum"])
+    agent.buffer.store_episode(eps)
+    from gpu_common import DeviceEpisodeBuffer
+    scratch = DeviceEpisodeBuffer(2, 100, 27, 3, 4)
+    scratch.store(rng, [a[:2] for a in eps])
+    _lib.check(agent.lib.hp_norm_update_from_staged(scratch.h, rng.h, agent.o_norm.h, agent.g_norm.h,
+                                                    agent.her_module.future_p, hp["clip_obs"]))
+    agent.o_norm.recompute_stats(); agent.g_norm.recompute_stats()
+    for nm, a in (("o_mean", agent.o_norm.mean), ("o_std", agent.o_norm.std), ("g_mean", agent.g_norm.mean),
+                  ("g_std", agent.g_norm.std)):
+        assert np.array_equal(bits(a), bits(g[nm])), nm
+    agent._update_network(3)
+    losses = agent.last_losses(3)
+    for i in range(3):
+        assert abs(losses[i, 0] - g["actor_loss"][i]) <= 3 * LOSS_RTOL * abs(g["actor_loss"][i]), (i, losses[i])
+        assert abs(losses[i, 1] - g["critic_loss"][i]) <= 3 * LOSS_RTOL * abs(g["critic_loss"][i]), (i, losses[i])
+    update_agrees(agent._get_flat(NET_ACTOR)[pa], g["actor_after_step3"], init_a, 2e-2, 2e-7)
+    update_agrees(agent._get_flat(NET_CRITIC)[pc], g["critic_after_step3"], init_c, 2e-2, 2e-7)
+    agent._soft_update_target_network()
+    update_agrees(agent._get_flat(NET_ACTOR_TARGET)[pa], g["actor_target_after_polyak"], init_a, 2e-2, 2e-8)
+    update_agrees(agent._get_flat(NET_CRITIC_TARGET)[pc], g["critic_target_after_polyak"], init_c, 2e-2, 2e-8)
+    assert state_equal(rng, g["key"], g["pos"])
 
 
 @pytest.mark.parametrize("batch,k", [(256, 4), (100, 8), (512, 8), (1024, 4), (7, 4), (449, 4), (1281, 4),
@@ -361,6 +440,43 @@ def test_critic_forward_matches_oracle():
     assert np.allclose(agent.critic_target_network(x[:1].numpy(), a[:1].numpy()), want[:1], rtol=1e-5, atol=1e-6)
     with pytest.raises(ValueError):
         agent.critic_network(x, a[:-1])
+
+
+@pytest.mark.parametrize("obs_dim,goal_dim,act_dim,amax", [(29, 3, 1, 0.7), (29, 3, 1, 2.0), (20, 1, 3, 0.7), (20, 1, 3, 2.0),
+                                                       (27, 3, 4, 0.7)])
+def test_forward_entry_points_match_oracle_at_other_action_scales(obs_dim, goal_dim, act_dim, amax):
+    """actor_network(x), critic_network(x, a) and act(obs, g, clip_obs=...) at action_max != 0.5 (the scale multiplies the
+    tanh and divides the critic's action columns: not exact unless a power of two) and one or three actions, with clip_obs
+    0.8 / clip_range 1.5 clipping a good part of the raw and of the normalised inputs of act."""
+    T, n_eps = 20, 8
+    env = {"obs": obs_dim, "goal": goal_dim, "action": act_dim, "action_max": amax, "max_timesteps": T}
+    torch.manual_seed(0)
+    rng = fresh_rng(5)
+    agent = ddpg_agent(Args(batch_size=64, buffer_size=n_eps * T, clip_obs=0.8, clip_range=1.5), None, env, rng=rng)
+    eps = make_shape_episodes(n_eps, obs_dim, goal_dim, act_dim, T, seed=6)
+    agent._update_normalizer(eps)
+    on, gn = RunningNorm(obs_dim, default_clip_range=1.5), RunningNorm(goal_dim, default_clip_range=1.5)
+    update_normalizers(on, gn, eps, future_probability("future", 4), np.random.RandomState(5), clip_obs=0.8)
+    assert np.array_equal(bits(agent.o_norm.mean), bits(on.mean)) and np.array_equal(bits(agent.g_norm.std), bits(gn.std))
+    rs = np.random.RandomState(3)
+    xdim = obs_dim + goal_dim
+    x = rs.normal(size=(37, xdim)).astype(np.float32)
+    pa = {k: v.detach().clone() for k, v in agent.actor_network.state_dict().items()}
+    want = oupd.actor_forward(pa, torch.from_numpy(x), amax).numpy()
+    got = agent.actor_network(torch.from_numpy(x)).numpy()
+    assert got.shape == (37, act_dim) and np.allclose(got, want, rtol=1e-5, atol=1e-6 * amax)
+    a = rs.uniform(-amax, amax, size=(37, act_dim)).astype(np.float32)
+    pc = {k: v.detach() for k, v in agent.critic_network.state_dict().items()}
+    want_q = oupd.critic_forward(pc, torch.from_numpy(x), torch.from_numpy(a), amax).numpy()
+    got_q = agent.critic_network(torch.from_numpy(x), torch.from_numpy(a)).numpy()
+    assert got_q.shape == (37, 1) and np.allclose(got_q, want_q, rtol=1e-5, atol=1e-6)
+    obs, g = rs.uniform(-1.6, 1.6, size=(41, obs_dim)), rs.uniform(-1.6, 1.6, size=(41, goal_dim))
+    o_c, g_c = np.clip(obs, -0.8, 0.8), np.clip(g, -0.8, 0.8)
+    xin = np.concatenate([on.normalize(o_c), gn.normalize(g_c)], axis=1)
+    assert np.mean(np.abs(obs) > 0.8) > 0.2 and np.mean(np.abs(xin) == 1.5) > 0.05      # both clips bite
+    want_act = oupd.actor_forward(pa, torch.tensor(xin, dtype=torch.float32), amax).numpy()
+    got_act = agent.act(obs, g, clip_obs=0.8)
+    assert got_act.shape == (41, act_dim) and np.allclose(got_act, want_act, rtol=1e-5, atol=1e-6 * amax)
 
 
 def test_checkpoint_format_roundtrip(tmp_path):
@@ -652,11 +768,7 @@ def test_other_env_shapes_track_oracle(obs_dim, goal_dim, act_dim, T):
     torch.set_num_threads(4)
     env_params = {"obs": obs_dim, "goal": goal_dim, "action": act_dim, "action_max": 0.5, "max_timesteps": T}
     n_eps, batch = 24, 256
-    rs0 = np.random.RandomState(4)
-    obs = rs0.uniform(-1, 1, (n_eps, T + 1, obs_dim))
-    obs[:, :, :goal_dim] = rs0.uniform(0, 0.5, (n_eps, 1, goal_dim)) + np.cumsum(rs0.normal(0, 0.012, (n_eps, T + 1, goal_dim)), 1)
-    eps = [obs, obs[:, :, :goal_dim].copy(), np.repeat(rs0.uniform(0, 0.5, (n_eps, 1, goal_dim)), T, 1),
-           rs0.uniform(-0.5, 0.5, (n_eps, T, act_dim))]
+    eps = make_shape_episodes(n_eps, obs_dim, goal_dim, act_dim, T, seed=4)
     torch.manual_seed(0)
     rng = fresh_rng(7)
     agent = ddpg_agent(Args(batch_size=batch, buffer_size=n_eps * T), None, env_params, rng=rng)

@@ -116,3 +116,74 @@ def test_ddpg_update_golden():
     assert np.allclose(learner.flat("actor_target"), g["actor_target_after_polyak"], rtol=0, atol=1e-6)
     assert np.allclose(learner.flat("critic_target"), g["critic_target_after_polyak"], rtol=0, atol=1e-6)
     assert rs.get_state()[2] == int(g["pos"]) and np.array_equal(rs.get_state()[1], g["key"])
+
+
+
+def hparams_initial_weights():
+    """The initial weights of ddpg_update_hparams.npz: torch.manual_seed(0), then models.py's four nn.Linear of the actor
+    and of the critic, in that order (ddpg_agent.py:24-25); state-dict-like {name: tensor} per net."""
+    torch.manual_seed(0)
+    nets = []
+    for d_in, keys, d_out in ((30, oupd.ACTOR_KEYS, 4), (34, oupd.CRITIC_KEYS, 1)):
+        lins = [torch.nn.Linear(d_in, 256), torch.nn.Linear(256, 256), torch.nn.Linear(256, 256), torch.nn.Linear(256, d_out)]
+        nets.append({f"{k}.{p}": getattr(lin, p).detach().clone() for k, lin in zip(keys, lins) for p in ("weight", "bias")})
+    return nets
+
+
+def hparams_golden_setup(g):
+    """Hyperparameters, episodes and initial weights of ddpg_update_hparams.npz, each checked against what it records."""
+    import hashlib
+    hp = dict(zip((str(n) for n in g["hparam_names"]), (float(v) for v in g["hparams"])))
+    n_eps, dseed, np_seed, B, k = (int(x) for x in g["meta"])
+    eps = make_episodes(n_eps, seed=dseed, mode="walk")
+    assert episode_checksum(eps) == float(g["checksum"])
+    a0, c0 = hparams_initial_weights()
+    for net, nm in ((a0, "actor"), (c0, "critic")):
+        assert hashlib.sha256(oupd.flatten(list(net.values())).tobytes()).hexdigest() == str(g[f"init_{nm}_sha256"]), nm
+    return hp, eps, (n_eps, np_seed, B, k), a0, c0
+
+
+def test_ddpg_update_hparams_golden():
+    """The oracle's handling of every learner hyperparameter (gamma and its clip_return, action_l2, the two learning rates,
+    polyak, action_max, clip_obs, clip_range) against the reference run at non-default values (tools/gen_golden.py
+    gen_ddpg_update_hparams); the fixture keeps the probe_indices elements of every parameter vector."""
+    g = load_golden("ddpg_update_hparams.npz")
+    hp, eps, (n_eps, np_seed, B, k), a0, c0 = hparams_golden_setup(g)
+    assert hp == dict(gamma=0.9, action_l2=0.5, lr_actor=3e-4, lr_critic=2e-3, polyak=0.9, clip_range=1.5, clip_obs=0.8,
+                      action_max=0.7)
+    assert float(g["clip_fraction"].min()) >= 0.01          # both clips act on the recorded minibatches
+    torch.set_num_threads(1)
+    rs = np.random.RandomState(np_seed)
+    st = EpisodeStore(100, 27, 3, 4, n_eps * 100)
+    st.store_episode(eps, rs)
+    fp = future_probability("future", k)
+    on, gn = RunningNorm(27, default_clip_range=hp["clip_range"]), RunningNorm(3, default_clip_range=hp["clip_range"])
+    update_normalizers(on, gn, [a[:2] for a in eps], fp, rs, clip_obs=hp["clip_obs"])
+    for a, nm in ((on.mean, "o_mean"), (on.std, "o_std"), (gn.mean, "g_mean"), (gn.std, "g_std")):
+        assert np.array_equal(bits(a), bits(g[nm])), nm
+    learner = oupd.DDPGLearner(a0, c0, max_action=hp["action_max"], gamma=hp["gamma"], action_l2=hp["action_l2"],
+                               lr_actor=hp["lr_actor"], lr_critic=hp["lr_critic"], polyak=hp["polyak"])
+    pa, pc = g["probe_actor"], g["probe_critic"]
+    for i in range(3):
+        tr, _ = st.sample(B, fp, rs)
+        x, xn, a, r = oupd.minibatch_tensors(tr, on, gn, clip_obs=hp["clip_obs"])
+        if i == 0:
+            assert np.array_equal(x.numpy(), g["x_step1"]) and np.array_equal(xn.numpy(), g["x_next_step1"])
+            assert np.array_equal(a.numpy(), g["a_step1"]) and np.array_equal(bits(r.numpy()), bits(g["r_step1"]))
+        res = learner.update(x, xn, a, r)
+        assert abs(res["actor_loss"] - g["actor_loss"][i]) <= 1e-5 * abs(g["actor_loss"][i])
+        assert abs(res["critic_loss"] - g["critic_loss"][i]) <= 1e-5 * abs(g["critic_loss"][i])
+        if i == 0:
+            for nm in ("actor", "critic"):
+                ref = float(g[f"{nm}_grads_step1_absmax"])
+                assert abs(float(np.abs(res[f"{nm}_grads"]).max()) - ref) <= 1e-4 * ref, nm
+            assert np.allclose(res["actor_grads"][pa], g["actor_grads_step1"], rtol=1e-4, atol=1e-9)
+            assert np.allclose(res["critic_grads"][pc], g["critic_grads_step1"], rtol=1e-4, atol=1e-9)
+            assert np.allclose(learner.flat("actor")[pa], g["actor_after_step1"], rtol=0, atol=1e-6)
+            assert np.allclose(learner.flat("critic")[pc], g["critic_after_step1"], rtol=0, atol=1e-6)
+    assert np.allclose(learner.flat("actor")[pa], g["actor_after_step3"], rtol=0, atol=3e-6)
+    assert np.allclose(learner.flat("critic")[pc], g["critic_after_step3"], rtol=0, atol=3e-6)
+    learner.soft_update()
+    assert np.allclose(learner.flat("actor_target")[pa], g["actor_target_after_polyak"], rtol=0, atol=1e-6)
+    assert np.allclose(learner.flat("critic_target")[pc], g["critic_target_after_polyak"], rtol=0, atol=1e-6)
+    assert rs.get_state()[2] == int(g["pos"]) and np.array_equal(rs.get_state()[1], g["key"])
