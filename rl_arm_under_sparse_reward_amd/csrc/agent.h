@@ -266,7 +266,6 @@ struct hp_agent {
     // chain launch.  RLARM_SPLIT: unset = where it fits and the sequence has at least SPLIT_MIN_UPDATES updates, 0 = never,
     // 1 = wherever it fits (single updates too: parity tests)
     int split_mode = -1;                 // RLARM_SPLIT=0|1: never / also for short sequences (default: from SPLIT_MIN_UPDATES updates)
-    unsigned *split_reset_pending = nullptr;   // a split launch whose tiles wrote gradients only went out: the next optimizer launch clears its counter set
     unsigned *k1_sync = nullptr;         // device: hand-off counters of the split launch, then the sticky fault word (SPLIT_FAULT)
     unsigned *fault_host = nullptr;      // pinned + mapped mirror of the fault word (agent_check_fault), and its device address
     unsigned *fault_host_dev = nullptr;
@@ -417,42 +416,62 @@ static inline void add_dw(Launch &L, const float *dY, int ldy, int Nout, const f
     p.epi = EPI_NONE;
 }
 
-struct GatherCtx {   // where the minibatch comes from (nullptr plan = inputs already staged in XA/XP/XT/R)
-    hp_buffer *b;
-    hp_norm *on, *gn;
-    const PlanRec *plan;
-    double sq;
-    // slab engine: draw a LATER update's index plan in a spare workgroup of this update's kernel
-    hp_rng *rng = nullptr;
-    PlanRec *next_plan = nullptr;
-    double future_p = 0.0;
-    // merged slab8 kernel: input sets ping-pong between updates.  xset = the set this update reads (and, when it
-    // gathers in-kernel, writes); pregathered = a previous launch already filled it; ahead_plan = plan of the NEXT
-    // update, gathered by spare workgroups of this launch into the other set.
-    int xset = 0;
-    bool pregathered = false;
-    const PlanRec *ahead_plan = nullptr;
-    // full chain launch: the plan draw (next_plan) and the look-ahead gather (ahead_plan) ride in the weight-gradient
-    // launch instead of the chain kernel
-    bool ride_in_dw = false;
-    // data-parallel ranks exchanging through peer memory: this update's gradients go straight into the exchange buffer
-    float *grads_out = nullptr;
-    // last update of a training cycle: the optimizer launch also applies the soft update of both target networks
-    // (ddpg_agent.py:149-150) to the parameters it has just stepped -- no separate polyak launch
-    bool polyak_after = false;
-    // split launch (slab8_split.h): this update's Q' was computed one launch ahead (set qset of QT / QT2); t_plan = plan of the
-    // NEXT update, whose Q' the target chains of this launch compute into the other set (nullptr: last update of the sequence)
-    bool split = false;
-    int qset = 0;
-    // data-parallel ranks, tile-wise exchange: index of this update in its sequence (the exchange epoch), -1: not this form
-    int peer_u = -1;
-    const PlanRec *t_plan = nullptr;
-};
 // what the in-launch weight-gradient tiles of k_fb_split8 do behind their products (slab8_split.h: one instantiation per form)
 enum { SPLIT_TILES_ADAM = 0,   // single rank: optimizer step of the critic inside the launch (behind the actor-side chains' gates)
        SPLIT_TILES_PEER = 1,   // data-parallel ranks, one device each: rank exchange tile by tile, then the same step (utils.py:43-48 + Adam)
        SPLIT_TILES_GRADS = 2 };// gradients only: exchange (RCCL, two-phase / gated peer memory) + optimizer follow as launches of their own
 #define SPLIT_MIN_UPDATES 12  // shorter sequences keep the two-launch form: the prologue launch costs ~17 us per sequence, an update gains ~1.4
+
+// How a sequence of sampled updates is launched, decided once per sequence (seq_plan, agent.hip): every launch of the sequence, and
+// what hp_agent_update_form reports, follows from these fields.
+struct SeqPlan {
+    // where the index plan of update u + lead is drawn, and the look-ahead gather of update u + 1's inputs runs
+    enum { RIDE_NONE,     // every plan drawn up front (layer engine, gradient-only sequences)
+           RIDE_CHAIN,    // spare workgroups of the chain kernel
+           RIDE_DW,       // behind the weight-gradient tiles: the chain launch has no CU to spare
+           RIDE_FRONT     // a draw launch of its own in front of the update (slab32 under profiling whose chains fill the CUs)
+    } ride = RIDE_NONE;
+    int lead = 1;               // plans drawn this many updates ahead: 2 with the look-ahead gather
+    bool ahead = false;         // input sets ping-pong: update u + 1's inputs are gathered during update u
+    bool s32_serial = false;    // slab32 without riders: every update's gather is a launch in front of it
+    bool split = false;         // split launch (slab8_split.h)
+    int tiles_mode = SPLIT_TILES_GRADS;   // ... what its in-launch tiles do (SPLIT_TILES_*)
+    enum { OPT_NONE,            // gradients only
+           OPT_TILES,           // optimizer in the weight-gradient tiles' epilogue
+           OPT_PEER_TILES,      // ... behind a tile-wise rank exchange (gemm_lds.h PEER)
+           OPT_KERNEL,          // a stand-alone optimizer kernel behind the tiles
+           OPT_PEER_KERNEL,     // peer exchange + optimizer kernel(s) on the gradients written to the exchange buffer (peer.hip)
+           OPT_ALLREDUCE        // RCCL all-reduce, then the stand-alone optimizer kernel
+    } opt = OPT_NONE;
+    bool fold = false;          // the last update's optimizer launch also applies the soft target update (cycles only)
+};
+
+struct GatherCtx {   // one update of a sequence: where its minibatch comes from (nullptr plan = inputs already staged in XA/XP/XT/R)
+    hp_buffer *b;
+    hp_norm *on, *gn;
+    const PlanRec *plan;
+    double sq;
+    const SeqPlan *seq = nullptr;
+    int u = 0;            // index of this update in its sequence (the tile-wise exchange's epoch)
+    // the draw of a LATER update's index plan (seq->ride)
+    hp_rng *rng = nullptr;
+    PlanRec *next_plan = nullptr;
+    double future_p = 0.0;
+    // input sets ping-pong between updates.  xset = the set this update reads (and, when it gathers in-kernel, writes);
+    // pregathered = a previous launch already filled it; ahead_plan = plan of the NEXT update, gathered into the other set.
+    int xset = 0;
+    bool pregathered = false;
+    const PlanRec *ahead_plan = nullptr;
+    // data-parallel ranks exchanging through peer memory: this update's gradients go straight into the exchange buffer
+    float *grads_out = nullptr;
+    // last update of a training cycle: the optimizer launch also applies the soft update of both target networks
+    // (ddpg_agent.py:149-150) to the parameters it has just stepped -- no separate polyak launch
+    bool polyak_after = false;
+    // split launch: this update's Q' was computed one launch ahead (set qset of QT / QT2); t_plan = plan of the NEXT update, whose
+    // Q' the target chains of this launch compute into the other set (nullptr: last update of the sequence)
+    int qset = 0;
+    const PlanRec *t_plan = nullptr;
+};
 
 // workgroups of the chain kernel that carry chains (the spare ones -- index plan, look-ahead gather, L2 warmers -- follow)
 static inline int chain_wgs(const hp_agent *a) { return 2 * (a->Mp / a->s8_rows); }
@@ -466,6 +485,7 @@ Launch build_dw_group(const hp_agent *a, const float *sXA, const float *sXP, flo
 // forwards + losses + backwards of one update.  Inputs: gc == nullptr -> already in XA/XP/XT/R (minibatch API), else sampled
 // (HER gather fused into the chain kernel / k_gather_fused).  fuse_adam: the caller wants the optimizer step applied too;
 // the slab engines then do it in the weight-gradient launch's epilogue and the caller must NOT enqueue Adam again (*fused).
+// A sampled update of a sequence takes the optimizer placement of gc->seq (fuse_adam: OPT_TILES / OPT_PEER_TILES).
 int enqueue_forward_backward(hp_agent *a, const GatherCtx *gc = nullptr, bool fuse_adam = false, bool *fused = nullptr);
 // only = 1 / 2: just the chain kernel / just the weight-gradient launch (timing diagnostics, hp_agent_debug_chain)
 int enqueue_forward_backward_slab(hp_agent *a, const GatherCtx *gc, bool fuse_adam, int only = 0);
@@ -473,25 +493,20 @@ int enqueue_forward_backward_slab(hp_agent *a, const GatherCtx *gc, bool fuse_ad
 bool split_fits(const hp_agent *a);
 bool split_fits_rows(const hp_agent *a, int rows);
 // ... and its prologue: the target chains of a sequence's FIRST update (plan = that update's index plan) into Q' set 0
-int enqueue_split_prologue(hp_agent *a, const GatherCtx *gc, int tiles_mode);   // tiles_mode: SPLIT_TILES_* of the sequence's updates
+int enqueue_split_prologue(hp_agent *a, const GatherCtx *gc);   // (the k_fb_split8 instantiation of gc->seq->tiles_mode)
 // a bounded in-launch hand-off gave up earlier (k_cycle_open, k_fb_split8): HP_ERR_STATE + message; free for the host
 int agent_check_fault(const hp_agent *a, const char *who);
-int enqueue_adam(hp_agent *a, bool polyak_after = false);   // polyak_after: see GatherCtx (slab engines; returns whether via *folded)
+// the counter set the split launch of update u counts in (slab8_split.h; the optimizer launch behind a SPLIT_TILES_GRADS launch clears it)
+static inline unsigned *split_set(const hp_agent *a, int u) { return a->k1_sync + (u & 1) * SPLIT_SET_WORDS; }
+// stand-alone optimizer kernel; gc: the sampled update it steps (polyak_after), reset_sync: a split launch's counter set to clear
+int enqueue_adam(hp_agent *a, const GatherCtx *gc = nullptr, unsigned *reset_sync = nullptr);
 int enqueue_polyak(hp_agent *a);
 // cycle_open.hip: slots + scatter + normalizer update + first minibatch plans of a cycle as one launch
 bool cycle_open_fits(const hp_agent *a, int64_t n_new);
 int cycle_open_launch(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, PlanRec *norm_plan, int n_first,
                       double future_p, bool recompute);
-// utils.sync_grads (utils.py:43-48) + both Adam steps of update u as the peer exchange's optimizer kernel(s) (peer.hip)
-int enqueue_peer_adam(hp_agent *a, int u, bool polyak_after = false);
-// data-parallel ranks: do the weight-gradient tiles exchange by themselves (one launch: gradients + rank exchange + optimizer)?
-// (a launch with more tiles than flag rows takes the separate exchange + optimizer kernel instead of failing)
-static inline bool peer_tiles_ok(const hp_agent *a) {
-    return a->peer && a->peer->tiles && a->peer->phases == 1 && !a->peer->gate && a->slab && !a->dw64 && a->fuse_adam_ok &&
-           build_dw_group(a, a->XA, a->XP).tiles <= HP_PEER_TILES;
-}
-// can the optimizer launches of this agent apply the soft target update themselves?  (slab engines: yes)
-static inline bool polyak_foldable(const hp_agent *a) { return a->slab; }
+// utils.sync_grads (utils.py:43-48) + both Adam steps of update gc->u as the peer exchange's optimizer kernel(s) (peer.hip)
+int enqueue_peer_adam(hp_agent *a, const GatherCtx *gc, unsigned *reset_sync);
 // ---- defined in agent_layers.hip
 int enqueue_forward_backward_layers(hp_agent *a);
 int layers_enqueue_adam(hp_agent *a);

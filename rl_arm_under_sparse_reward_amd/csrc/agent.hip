@@ -58,111 +58,119 @@ struct CycleOpts {
     std::function<int()> between;    // what follows the draws and precedes the first update
     bool polyak_folded = false;
 };
-// Does a sequence of n_updates sampled updates WITH optimizer steps on this agent take the split form (slab8_split.h)?  ONE
-// predicate for the launch logic (enqueue_updates: `ride` = with_adam on a slab engine is the only further condition, the others
-// follow from the terms below) and for what hp_agent_update_form reports.
-static bool update_takes_split_form(const hp_agent *a, int n_updates) {
-    const bool full = a->slab8 && chain_wgs(a) + 1 + S8_AHEAD_WGS > a->ctx->cu_count;   // no CU left for the chain kernel's spare workgroups
-    return a->slab8 && a->gather_ahead && !full && split_fits(a) &&
-           (a->split_mode >= 0 ? a->split_mode == 1 : n_updates >= SPLIT_MIN_UPDATES);
+// data-parallel ranks: do the weight-gradient tiles exchange by themselves (one launch: gradients + rank exchange + optimizer)?
+// (a launch with more tiles than flag rows takes the separate exchange + optimizer kernel instead of failing)
+static bool peer_tiles_ok(const hp_agent *a) {
+    return a->peer && a->peer->tiles && a->peer->phases == 1 && !a->peer->gate && a->slab && !a->dw64 && a->fuse_adam_ok &&
+           build_dw_group(a, a->XA, a->XP).tiles <= HP_PEER_TILES;
+}
+
+// The launch form of a sequence of n_updates sampled updates on this agent as it is now: what enqueue_updates launches and what
+// hp_agent_update_form reports, decided in this one place.
+static SeqPlan seq_plan(const hp_agent *a, int n_updates, bool with_adam) {
+    SeqPlan p;
+    // slab engines: update u draws the plan of a later update in a spare workgroup (same stream order of draws, so the same
+    // indices).  Layer engine and gradient-only calls: one kernel draws all of them up front.
+    const bool ride = a->slab && with_adam;
+    // slab8 launch with no CU left for the chain kernel's spare workgroups: both jobs ride in the weight-gradient launch
+    // (k_gemm_lds_adam_ride).  (A second stream beside the chain kernel was the alternative until round 4: its cross-queue graph
+    // edges cost ~4 us each, 65.5 vs 71.4 us at batch 1024, and at batch 4096 k_draw_plan took 83 us instead of 3.4 next to the
+    // chain kernel; removed in round 5.)  slab32: its chain kernel never gathers and its launches fill the CUs from batch 4096, so
+    // both jobs ride in the weight-gradient launch as well.  Profiling brackets every launch with events: the gather then runs in
+    // front of every launch.
+    const bool full = a->slab8 && chain_wgs(a) + 1 + S8_AHEAD_WGS > a->ctx->cu_count;
+    const bool s32_ride = ride && a->slab32 && !a->prof;
+    const bool dw_ride = s32_ride || (ride && a->slab8 && full);
+    p.s32_serial = a->slab32 && !s32_ride;
+    // plans are drawn TWO updates ahead so that update u can gather the inputs of update u+1 from a plan that an earlier launch
+    // finished (the order of draws in the stream is unchanged)
+    p.ahead = ride && ((a->slab8 && (a->gather_ahead || dw_ride)) || s32_ride);
+    p.lead = p.ahead ? 2 : 1;
+    // serial slab32 launch that fills the CUs: a spare workgroup would only start when the first chain ends (137 instead of 87 us
+    // per launch at batch 4096) -- draw in front of the launch
+    p.ride = !ride ? SeqPlan::RIDE_NONE : dw_ride ? SeqPlan::RIDE_DW
+           : (p.s32_serial && 2 * (a->Mp / S32_ROWS) >= a->ctx->cu_count) ? SeqPlan::RIDE_FRONT : SeqPlan::RIDE_CHAIN;
+    const bool peer_tiles = with_adam && peer_tiles_ok(a);
+    const bool fuse = with_adam && !a->comm && (!a->peer || peer_tiles) && a->slab && a->fuse_adam_ok;
+    p.opt = !with_adam ? SeqPlan::OPT_NONE : peer_tiles ? SeqPlan::OPT_PEER_TILES : a->peer ? SeqPlan::OPT_PEER_KERNEL
+          : fuse ? SeqPlan::OPT_TILES : a->comm ? SeqPlan::OPT_ALLREDUCE : SeqPlan::OPT_KERNEL;
+    // split form (slab8_split.h): target chains one update ahead, the critic's weight gradients + optimizer step inside the chain
+    // launch.  Needs the chain kernel's own look-ahead (plans two updates ahead, gather workgroups) and the fused optimizer.
+    p.split = p.ahead && p.ride == SeqPlan::RIDE_CHAIN && a->slab8 && split_fits(a) &&
+              (a->split_mode >= 0 ? a->split_mode == 1 : n_updates >= SPLIT_MIN_UPDATES);
+    p.tiles_mode = p.opt == SeqPlan::OPT_PEER_TILES ? SPLIT_TILES_PEER : p.opt == SeqPlan::OPT_TILES ? SPLIT_TILES_ADAM : SPLIT_TILES_GRADS;
+    return p;
 }
 
 static int enqueue_updates(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, double future_p, double sq,
                            int n_updates, bool with_adam, CycleOpts *cyc = nullptr) {
-    // slab engine: only the first minibatch's indices are drawn up front; update u draws the plan of update u+1 in
-    // a spare workgroup of its backward kernel (same stream order of draws, so the same indices).  Layer engine:
-    // one kernel draws all of them (nothing else consumes the stream in between, like the reference's inner loop).
-    const bool ride = a->slab && with_adam;
-    // merged slab8 kernel: plans are drawn TWO updates ahead so that spare workgroups of update u can gather the inputs
-    // of update u+1 from a plan that an earlier launch finished (the order of draws in the stream is unchanged)
-    const int chains = chain_wgs(a);
-    // ... and when the launch is full (no CU for spare workgroups) both jobs move out of the chain kernel
-    const bool full = a->slab8 && chains + 1 + S8_AHEAD_WGS > a->ctx->cu_count;
-    // slab8 engine, full launch: both jobs ride in the weight-gradient launch (k_gemm_lds_adam_ride).  (A second stream beside
-    // the chain kernel was the alternative until round 4: its cross-queue graph edges cost ~4 us each, 65.5 vs 71.4 us at batch
-    // 1024, and at batch 4096 k_draw_plan took 83 us instead of 3.4 next to the chain kernel; removed in round 5.)
-    // slab32 engine: its chain kernel never gathers and its launches fill the CUs from batch 4096, so both jobs ride in the
-    // weight-gradient launch as well.  Profiling brackets every launch with events: the gather then runs in front of every launch.
-    const bool s32_ride = ride && a->slab32 && !a->prof;
-    const bool s32_serial = a->slab32 && !s32_ride;
-    const bool dw_ride = s32_ride || (ride && a->slab8 && full);
-    const bool ahead = ride && ((a->slab8 && (a->gather_ahead || dw_ride)) || s32_ride);
-    const int lead = ahead ? 2 : 1;
-    // split form (slab8_split.h): target chains one update ahead, the critic's weight gradients + optimizer step inside the chain
-    // launch.  Needs the chain kernel's own look-ahead (plans two updates ahead, gather workgroups) and the fused optimizer.
-    const bool split = ride && ahead && !dw_ride && update_takes_split_form(a, n_updates);
+    SeqPlan P = seq_plan(a, n_updates, with_adam);
+    P.fold = cyc && with_adam && a->slab;   // (the slab engines' optimizer launches can step the targets too)
+    HP_REQUIRE(P.opt != SeqPlan::OPT_PEER_TILES || !a->comm, HP_ERR_STATE,
+               "tile-wise exchange: the engine did not take the fused optimizer path (a communicator is attached too)");
+    PlanRec *plans = a->plan.as<PlanRec>();
     HP_KLOG("#open");
     {
         ProfScope ps(a, PROF_PLAN);
-        const int first = ride ? (n_updates < lead ? n_updates : lead) : n_updates;
+        const int first = P.ride != SeqPlan::RIDE_NONE ? std::min(n_updates, P.lead) : n_updates;
         if (cyc && cyc->open)
             HP_TRY(cycle_open_launch(a, b, on, gn, rng, cyc->norm_plan, first, future_p, cyc->recompute));
         else if (cyc)   // ddpg_agent._update_normalizer's plan (T transitions of the staged episodes), then the first minibatch plans
-            HP_TRY(rng_launch_plan2(rng, b->staged_n, b->T, b->T, cyc->norm_plan, b->d_meta, a->B, first, future_p,
-                                    a->plan.as<PlanRec>()));
+            HP_TRY(rng_launch_plan2(rng, b->staged_n, b->T, b->T, cyc->norm_plan, b->d_meta, a->B, first, future_p, plans));
         else
-            HP_TRY(rng_launch_plan(rng, b->d_meta, 0, b->T, a->B, first, future_p, a->plan.as<PlanRec>()));
+            HP_TRY(rng_launch_plan(rng, b->d_meta, 0, b->T, a->B, first, future_p, plans));
     }
     if (cyc && cyc->between) HP_TRY(cyc->between());
-    const bool fold = cyc && with_adam && polyak_foldable(a);
-    if (cyc) cyc->polyak_folded = fold;
+    if (cyc) cyc->polyak_folded = P.fold;
     // split form: Q' of the FIRST update's minibatch comes from a prologue launch of target chains (every later one from the
     // launch before).  Round 4 also built the alternative -- the first update's critic chains run k_fb_slab8's whole critic side
     // and hand off to the tiles at their end, no prologue: 37.90 vs 37.92 us/update over cycles, 40.97 vs 41.14 in the driver's
     // 20-step form, and an intermittent optimizer mismatch in the teacher-forced test that the prologue form never showed;
     // removed.
-    if (split) {
+    if (P.split) {
         HP_KLOG("#prologue");
-        GatherCtx g0{b, on, gn, a->plan.as<PlanRec>(), sq};
-        const bool fuse = with_adam && !a->comm && (!a->peer || peer_tiles_ok(a));   // (as for the updates below)
-        HP_TRY(enqueue_split_prologue(a, &g0, !fuse ? SPLIT_TILES_GRADS : (a->peer ? SPLIT_TILES_PEER : SPLIT_TILES_ADAM)));
+        GatherCtx g0{b, on, gn, plans, sq, &P};
+        HP_TRY(enqueue_split_prologue(a, &g0));
     }
     for (int u = 0; u < n_updates; ++u) {
         HP_KLOG("#update");
-        GatherCtx gc{b, on, gn, a->plan.as<PlanRec>() + (size_t)u * a->B, sq};
-        gc.split = split;
+        GatherCtx gc{b, on, gn, plans + (size_t)u * a->B, sq, &P, u};
         gc.qset = u & 1;
-        gc.t_plan = (split && u + 1 < n_updates) ? a->plan.as<PlanRec>() + (size_t)(u + 1) * a->B : nullptr;
-        if (ride && u + lead < n_updates) {
-            PlanRec *next = a->plan.as<PlanRec>() + (size_t)(u + lead) * a->B;
-            if (a->slab32 && s32_serial && 2 * (a->Mp / S32_ROWS) >= a->ctx->cu_count) {
-                // serial mode (profiling) of a launch that fills the CUs: a spare workgroup would only start
-                // when the first chain ends (137 instead of 87 us per launch at batch 4096) -- draw in front of the launch
-                HP_TRY(rng_launch_plan(rng, b->d_meta, 0, b->T, a->B, 1, future_p, next));
-            } else {
+        gc.t_plan = (P.split && u + 1 < n_updates) ? plans + (size_t)(u + 1) * a->B : nullptr;
+        if (P.ride != SeqPlan::RIDE_NONE && u + P.lead < n_updates) {
+            PlanRec *next = plans + (size_t)(u + P.lead) * a->B;
+            if (P.ride == SeqPlan::RIDE_FRONT) HP_TRY(rng_launch_plan(rng, b->d_meta, 0, b->T, a->B, 1, future_p, next));
+            else {
                 gc.rng = rng;
                 gc.next_plan = next;
                 gc.future_p = future_p;
             }
         }
-        if (a->slab32 && (s32_serial || u == 0))   // nobody gathered this update's inputs beside the previous one
-            HP_TRY(enqueue_gather(a, b, on, gn, gc.plan, sq, ahead ? (u & 1) : 0));
-        if (ahead) {
+        if (a->slab32 && (P.s32_serial || u == 0))   // nobody gathered this update's inputs beside the previous one
+            HP_TRY(enqueue_gather(a, b, on, gn, gc.plan, sq, P.ahead ? (u & 1) : 0));
+        if (P.ahead) {
             gc.xset = u & 1;
             gc.pregathered = u > 0;
-            if (u + 1 < n_updates) gc.ahead_plan = a->plan.as<PlanRec>() + (size_t)(u + 1) * a->B;
+            if (u + 1 < n_updates) gc.ahead_plan = plans + (size_t)(u + 1) * a->B;
         }
-        gc.ride_in_dw = dw_ride;
-        const bool last_fold = fold && u == n_updates - 1;
-        gc.polyak_after = last_fold;
-        const bool peer_tiles = with_adam && peer_tiles_ok(a);
-        const bool via_peer = with_adam && a->peer != nullptr && !peer_tiles;
-        if (via_peer) gc.grads_out = peer_grad_buffer(a->peer, u + 1);   // epoch base is even: parity of epoch base + u + 1
-        if (peer_tiles) gc.peer_u = u;   // the weight-gradient tiles exchange and step by themselves (gemm_lds.h PEER)
-        bool fused = false;
-        HP_TRY(enqueue_forward_backward(a, &gc, with_adam && !a->comm && (!a->peer || peer_tiles), &fused));
-        HP_REQUIRE(!peer_tiles || fused, HP_ERR_STATE, "tile-wise exchange: the engine did not take the fused optimizer path");
-        if (via_peer) {
+        gc.polyak_after = P.fold && u == n_updates - 1;
+        // epoch base is even: parity of epoch base + u + 1
+        if (P.opt == SeqPlan::OPT_PEER_KERNEL) gc.grads_out = peer_grad_buffer(a->peer, u + 1);
+        HP_TRY(enqueue_forward_backward(a, &gc, P.opt == SeqPlan::OPT_TILES || P.opt == SeqPlan::OPT_PEER_TILES));
+        // a split launch whose tiles wrote gradients only: the optimizer launch behind the exchange clears its counter set
+        unsigned *reset = P.split && P.tiles_mode == SPLIT_TILES_GRADS ? split_set(a, u) : nullptr;
+        if (P.opt == SeqPlan::OPT_PEER_KERNEL) {
             // utils.sync_grads (utils.py:43-48) + both Adam steps in ONE kernel: every rank reads the peers' gradient
             // vectors over xGMI, sums them in rank order and steps (peer.hip)
-            HP_TRY(enqueue_peer_adam(a, u, last_fold));
-        } else if (with_adam) {
+            HP_TRY(enqueue_peer_adam(a, &gc, reset));
+        } else if (P.opt == SeqPlan::OPT_ALLREDUCE) {
             // utils.sync_grads (utils.py:43-48): SUM over ranks between backward and the optimizer step; one
             // all-reduce covers both networks (the reference sends the actor's and the critic's separately)
-            if (a->comm)
-                HP_TRY(a->grad_mean ? comm_allreduce_mean_f32(a->comm, a->grads, (size_t)a->n_arena)
-                                    : comm_allreduce_sum_f32(a->comm, a->grads, (size_t)a->n_arena));
-            if (!fused) HP_TRY(enqueue_adam(a, last_fold));
+            HP_TRY(a->grad_mean ? comm_allreduce_mean_f32(a->comm, a->grads, (size_t)a->n_arena)
+                                : comm_allreduce_sum_f32(a->comm, a->grads, (size_t)a->n_arena));
+            HP_TRY(enqueue_adam(a, &gc, reset));
+        } else if (P.opt == SeqPlan::OPT_KERNEL) {
+            HP_TRY(enqueue_adam(a, &gc, reset));
         }
     }
     HP_KLOG("#close");
@@ -733,7 +741,7 @@ int hp_agent_train_cycle_pinned(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm 
 // Gradient-only sequences (with_adam false) never split; hp_agent_update_kernels names the kernels of either.
 int hp_agent_update_form(hp_agent *a, int32_t n_updates, int32_t *form) {
     HP_REQUIRE(a && form, HP_ERR_INVALID, "hp_agent_update_form: null argument");
-    *form = update_takes_split_form(a, n_updates) ? 1 : 0;
+    *form = seq_plan(a, n_updates, true).split ? 1 : 0;
     return HP_OK;
 }
 
@@ -759,7 +767,6 @@ int hp_agent_update_kernels(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn,
     } rebind{a->ctx, bound};
     a->ctx->stream = s;
     std::vector<std::string> log;
-    unsigned *pending = a->split_reset_pending;
     hp_klog = &log;   // (the collectives are named, not issued: comm.hip)
     const Captured c = capture_graph(s, [&] {
         if (!caller_exchanges) return enqueue_updates(a, b, on, gn, rng, future_p, sq_threshold, n_updates, true);
@@ -768,7 +775,6 @@ int hp_agent_update_kernels(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn,
         return enqueue_adam(a);
     }, false);
     hp_klog = nullptr;
-    a->split_reset_pending = pending;
     HP_TRY(c.status());
     std::string j;
     for (size_t i = 0; i < log.size(); ++i) j += (i ? "," : "") + log[i];

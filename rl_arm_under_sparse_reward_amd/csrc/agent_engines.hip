@@ -393,12 +393,6 @@ int enqueue_gather(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, const Pl
     return HP_OK;
 }
 
-static AdamFuse adam_fuse(hp_agent *a);
-static void fold_polyak(hp_agent *a, AdamFuse &F) {   // the optimizer launch also steps the targets (GatherCtx::polyak_after)
-    F.tgt = a->targets; F.fragFT = a->fragFT;
-    F.polyak = (float)a->cfg.polyak; F.one_minus = (float)(1.0 - a->cfg.polyak);
-}
-
 static ArenaMap arena_map(const hp_agent *a) {
     ArenaMap am;
     am.la = a->la;
@@ -406,6 +400,57 @@ static ArenaMap arena_map(const hp_agent *a) {
     am.H = a->H;
     am.mode = a->slab32 ? 2 : 1;
     return am;
+}
+
+static AdamFuse adam_fuse(hp_agent *a) {
+    AdamFuse F;
+    F.p = a->params; F.p_out = a->params; F.m = a->adam_m; F.v = a->adam_v; F.fragF = a->fragF; F.fragD = a->fragD;
+    F.grads_base = a->grads; F.st = a->d_state; F.scal = &a->d_state->neg_step_actor; F.am = arena_map(a); F.n_actor = a->la.total;
+    F.keep_grads = 1;
+    F.tgt = nullptr; F.fragFT = nullptr; F.polyak = 0.f; F.one_minus = 0.f;
+    F.gate = nullptr; F.gate_need = 0u; F.gate_sel = 0u; F.fault = nullptr; F.fault_host = nullptr; F.gate_ticks = 0ull; F.reset_sync = nullptr; F.tl_mark = 0;
+    F.w = (float)(1.0 - a->cfg.adam_beta1); F.b2 = (float)a->cfg.adam_beta2;
+    F.omb2 = (float)(1.0 - a->cfg.adam_beta2); F.eps = (float)a->cfg.adam_eps;
+    F.part = a->part; F.nslab = a->Mp / (a->slab8 ? a->s8_rows : S32_ROWS); F.B = a->B;
+    F.act_dim = a->cfg.act_dim;
+    F.action_l2 = (float)a->cfg.action_l2; F.loss_log = a->loss_log;
+    F.wt = a->Mp <= 768 ? 1 : 0;   // us/update without / with: 40.9 / 40.3 at 256, 44.9 / 44.4 at 384, 46.9 / 46.1 at 512 k8, 53.1 / 52.9 at 768, 55.6 / 55.8 at 1024
+    return F;
+}
+
+#define SPLIT_WAIT_TICKS 50000000ull   // bounded in-launch waits: 0.5 s of the 100 MHz wall clock, three orders of magnitude beyond a launch
+
+// What an optimizer block needs to know about its launch beyond the update it steps (adam_block)
+struct OptGates {
+    enum { IN_TILES, ADAM_KERNEL, PEER_KERNEL } where = IN_TILES;   // the weight-gradient tiles' epilogue, k_adam_frag*, k_peer_adam*
+    const unsigned *gate = nullptr;   // k_fb_split8's tiles: the counter set their steps wait on (gate_need chains, gate_sel per problem)
+    unsigned need = 0, sel = 0;
+    int tl_mark = 0;                  // time-line builds: this launch records its gate stamps
+    unsigned *reset_sync = nullptr;   // the launch behind a split launch: clears the counter set that launch counted in
+};
+
+// The optimizer argument block of one launch.  gc: the sampled update it steps (nullptr: staged minibatch, lone step, prologue).
+static AdamFuse adam_block(hp_agent *a, const GatherCtx *gc, const OptGates &g = {}) {
+    AdamFuse F = adam_fuse(a);
+    // inside a sampled update loop nobody reads the gradient vector (hp_agent_get_grads documents this): the launches that compute or
+    // exchange it leave it out of memory (1.17 MB of the ~6.7 MB the tile launch leaves dirty in L2) unless RLARM_KEEP_GRADS=1, when
+    // hp_agent_get_grads returns the exchanged sum.  k_adam_frag* reads it from memory.
+    F.keep_grads = (!gc || a->keep_grads_dbg || g.where == OptGates::ADAM_KERNEL) ? 1 : 0;
+    if (gc && gc->polyak_after) {   // the optimizer launch also steps the targets
+        F.tgt = a->targets; F.fragFT = a->fragFT;
+        F.polyak = (float)a->cfg.polyak; F.one_minus = (float)(1.0 - a->cfg.polyak);
+    }
+    if (g.gate) {
+        F.gate = g.gate; F.gate_need = g.need; F.gate_sel = g.sel;
+        F.fault = a->k1_sync + SPLIT_FAULT; F.fault_host = a->fault_host_dev; F.gate_ticks = SPLIT_WAIT_TICKS;
+        F.tl_mark = g.tl_mark;
+    }
+    F.reset_sync = g.reset_sync;
+    // plain stores in the stand-alone optimizer kernels: write-through (adam_fuse: small minibatches) pays inside a tile launch,
+    // where other workgroups still multiply while the stepped state drains; a kernel that does nothing else only waits for its
+    // own acknowledgements (forced data-parallel world 1, us/update: RCCL form 44.7 -> 43.5, separate peer exchange 45.3 -> 44.9)
+    if (g.where != OptGates::IN_TILES) F.wt = 0;
+    return F;
 }
 
 int enqueue_relayout(hp_agent *a, bool targets) {
@@ -596,9 +641,19 @@ static Launch build_dw_half(const hp_agent *a, bool critic, const float *sX, flo
     return L;
 }
 
-// slab engines: forwards + losses + backwards of one update (inputs in XA/XP/XT/R): chain kernel + weight-gradient launch
-// only = 1 / 2: just the chain kernel / just the weight-gradient launch (timing diagnostics, hp_agent_debug_chain)
-// argument blocks of the chain kernels for one update (gc as in enqueue_forward_backward_slab)
+// the look-ahead gather: update u + 1's inputs (plan gc->ahead_plan) into the input set this update does not read (chain kernel,
+// split launch, riders of the weight-gradient launch)
+template <class T> static void aim_ahead(const hp_agent *a, const GatherCtx *gc, const GatherSrc &gs, T &X) {
+    const bool xs = gc->xset != 0;
+    X.ahead = gs;
+    X.ahead.plan = gc->ahead_plan;
+    X.ahead.plan_any = gc->ahead_plan;
+    X.ahead.R = xs ? a->R : a->R2;
+    X.aXT = xs ? a->XT : a->XT2; X.aXA = xs ? a->XA : a->XA2; X.aXP = xs ? a->XP : a->XP2;
+}
+
+// argument blocks of the chain kernels for one update (gc as in enqueue_forward_backward_slab), with the plan draw and the
+// look-ahead gather in spare workgroups unless they ride in the weight-gradient launch
 struct FbBuilt {
     FbSlabArgs P;
     int nslab, xs;
@@ -638,7 +693,7 @@ static void build_fb_args(hp_agent *a, const GatherCtx *gc, FbBuilt &O) {
         A.CPh1 = a->CP.h1; A.CPh2 = a->CP.h2; A.CPh3 = a->CP.h3;
         A.QT = a->QT; A.QA = a->QA; A.QP = a->QP;
     }
-    const bool ride_dw = gc && gc->ride_in_dw;
+    const bool ride_dw = gc && gc->seq && gc->seq->ride == SeqPlan::RIDE_DW;
     const bool ride = gc && gc->next_plan && gc->rng && !ride_dw;
     {
         BwdSlabArgs &A = P.b;
@@ -663,6 +718,15 @@ static void build_fb_args(hp_agent *a, const GatherCtx *gc, FbBuilt &O) {
         A.T = ride ? gc->b->T : 0;
         A.plan_batch = a->B;
     }
+    P.n_plan = ride ? 1 : 0;
+    P.n_ahead = 0;
+    P.ahead = P.f.gs;
+    P.aXT = P.aXA = P.aXP = nullptr;
+    if (gc && gc->ahead_plan && !ride_dw) {   // next update's inputs into the other set
+        P.n_ahead = S8_AHEAD_WGS;
+        aim_ahead(a, gc, P.f.gs, P);
+    }
+    P.xcd_split = P.n_pref = 0;
     O.nslab = nslab; O.xs = xs; O.sXA = sXA; O.sXP = sXP; O.sXT = sXT; O.sR = sR; O.ride_dw = ride_dw; O.ride = ride;
 }
 
@@ -670,45 +734,75 @@ static void build_fb_args(hp_agent *a, const GatherCtx *gc, FbBuilt &O) {
 // summation order only; inside the tn == 0 tiles otherwise, and in the launches that exchange tile-wise between ranks: same bits)
 static bool sep_bias_on(const hp_agent *a) { return a->Mp >= GL_RING_MIN_K && !a->dw64; }
 
-static int enqueue_split_update(hp_agent *a, const GatherCtx *gc, FbBuilt &built, bool fuse_adam, int only);
+// One weight-gradient launch: 32 x 32 tiles (gemm_lds.h) or 64 x 64 tiles with split batch rows (dw64.h), the optimizer step in
+// their epilogue (F) or not, the plan draw / look-ahead gather (R) behind the tiles; peer_u >= 0: the tiles exchange between ranks
+// by themselves (gemm_lds.h PEER) from flag row row0 on
+static int launch_dw(hp_agent *a, Launch &L, const AdamFuse *F, const RideArgs &R, int peer_u = -1, int row0 = 0) {
+    const int riders = R.n_plan + R.n_ahead;
+    if (!a->dw64 && !F && !riders) return launch_group(a, L, PROF_DW);
+    ProfScope ps(a, PROF_DW);
+    hipStream_t s = a->ctx->stream;
+    const bool uni = L.g.uni != 0;
+    if (a->dw64) {
+        // large minibatch: 64 x 64 tiles, batch rows split over workgroups (dw64.h); the riders follow the tiles
+        Dw64Args X;
+        HP_TRY(dw64_args(a, L, X));
+        const unsigned grid = X.n_wg + riders;
+        HP_KLOG(F ? "k_dw64_adam" : "k_dw64");
+        if (F) hipLaunchKernelGGL(k_dw64_adam, dim3(grid), dim3(DW_THREADS), 0, s, L.g, *F, R, X);
+        else hipLaunchKernelGGL(k_dw64, dim3(grid), dim3(DW_THREADS), 0, s, L.g, R, X);
+    } else if (peer_u >= 0) {
+        // data-parallel ranks: the tiles exchange by themselves; riders, if any, behind them
+        HP_REQUIRE(F && a->peer && row0 + L.tiles <= HP_PEER_TILES, HP_ERR_STATE, "tile-wise exchange: %d tiles exceed the flag rows",
+                   row0 + L.tiles);
+        HP_KLOG(uni ? "k_gemm_lds_adam_peer_u" : "k_gemm_lds_adam_peer");
+        hipLaunchKernelGGL(uni ? k_gemm_lds_adam_peer_u : k_gemm_lds_adam_peer, dim3(L.tiles + riders), dim3(GL_THREADS), 0, s, L.head(0),
+                           L.head(1), L.g, *F, R, L.tiles, a->peer->dev, peer_u, a->grad_mean ? 1 : 0, row0);
+    } else {
+        // tiles, then the bias panels, then the riders; with the optimizer, the loss log's own workgroup last
+        const int front = L.tiles + (sep_bias_on(a) ? L.separate_bias() : 0);
+        if (F) L.g.loss_wg = a->loss_wg;
+        const unsigned grid = front + riders + L.g.loss_wg;
+        if (F && riders) {
+            HP_KLOG(uni ? "k_gemm_lds_adam_ride_u" : "k_gemm_lds_adam_ride");
+            hipLaunchKernelGGL(uni ? k_gemm_lds_adam_ride_u : k_gemm_lds_adam_ride, dim3(grid), dim3(GL_THREADS), 0, s, L.head(0), L.head(1),
+                               front, L.g, *F, R);
+        } else if (riders) {
+            HP_KLOG(uni ? "k_gemm_lds_ride_u" : "k_gemm_lds_ride");
+            hipLaunchKernelGGL(uni ? k_gemm_lds_ride_u : k_gemm_lds_ride, dim3(grid), dim3(GL_THREADS), 0, s, L.g, R, front);
+        } else {
+            HP_KLOG(uni ? "k_gemm_lds_adam_u" : "k_gemm_lds_adam");
+            hipLaunchKernelGGL(uni ? k_gemm_lds_adam_u : k_gemm_lds_adam, dim3(grid), dim3(GL_THREADS), 0, s, L.head(0), L.head(1), L.g, *F);
+        }
+    }
+    HP_CHECK_HIP(hipGetLastError());
+    return HP_OK;
+}
+
+// slab engines: forwards + losses + backwards of one update (inputs in XA/XP/XT/R): chain kernel + weight-gradient launch
+// only = 1 / 2: just the chain kernel / just the weight-gradient launch (timing diagnostics, hp_agent_debug_chain)
+static int enqueue_split_update(hp_agent *a, const GatherCtx *gc, FbBuilt &built, int only);
 int enqueue_forward_backward_slab(hp_agent *a, const GatherCtx *gc, bool fuse_adam, int only) {
-    const int ldx = a->ldx;
     hipStream_t s = a->ctx->stream;
     FbBuilt built;
     build_fb_args(a, gc, built);
     FbSlabArgs &P = built.P;
-    const int nslab = built.nslab, xs = built.xs;
-    float *sXA = built.sXA, *sXP = built.sXP;
-    const bool ride_dw = built.ride_dw, ride = built.ride;
-    if (gc && gc->split) return enqueue_split_update(a, gc, built, fuse_adam, only);
+    const int nslab = built.nslab;
+    if (gc && gc->seq && gc->seq->split) return enqueue_split_update(a, gc, built, only);
     if (only == 2) {
     } else if (a->slab8) {
         // one launch: each workgroup carries its rows through forward AND backward (k_fb_slab8)
         ProfScope ps(a, PROF_GEMM_FWD);
-        P.n_plan = ride ? 1 : 0;
-        P.n_ahead = 0;
         // chains split across XCD halves: measured (us/update, split vs not) 42.0 vs 43.5 at batch 128, 44.0 vs 45.2 at 256,
         // 46.6 vs 46.6 at 384, 48.0 vs 47.8 at 448, 77.3 vs 74.6 at 1024 -- it pays while the chains leave half of the CUs free
         const int n_chain = chain_wgs(a);
         P.xcd_split = (nslab % 4 == 0) && 4 * nslab <= a->ctx->cu_count;
-        P.ahead = P.f.gs;
-        P.aXT = P.aXA = P.aXP = nullptr;
-        if (gc && gc->ahead_plan && !ride_dw) {   // next update's inputs into the other set
-            P.n_ahead = S8_AHEAD_WGS;
-            P.ahead.plan = gc->ahead_plan;
-            P.ahead.plan_any = gc->ahead_plan;
-            P.ahead.R = xs ? a->R : a->R2;
-            P.aXT = xs ? a->XT : a->XT2; P.aXA = xs ? a->XA : a->XA2; P.aXP = xs ? a->XP : a->XP2;
-        }
         // L2 warmers: spare workgroups (the same number on every XCD) while the launch still fits the CUs.  Measured (us/update, with
         // 8 vs without): 39.9 vs 42.4 at batch 128, 42.1 vs 44.4 at 256, 46.4 vs 46.6 at 384, 52.8 vs 54.2 at 512, 56.6 vs 57.1 at 768.
         // Two per XCD instead of one (round 3, after the entry reordering): 39.65 vs 39.82 at batch 256, 41.3 vs 43.0 at 384; 24 / 32: no
         // further gain (40.0 / 40.0 vs 39.95 with 16).
-        {
-            const int fit = a->ctx->cu_count - (n_chain + P.n_plan + P.n_ahead);
-            const int want = fit >= 16 ? 16 : (fit >= 8 ? 8 : 0);
-            P.n_pref = want;
-        }
+        const int fit = a->ctx->cu_count - (n_chain + P.n_plan + P.n_ahead);
+        P.n_pref = fit >= 16 ? 16 : (fit >= 8 ? 8 : 0);
         const unsigned grid = n_chain + P.n_plan + P.n_ahead + P.n_pref;
         HP_KLOG("k_fb_slab8");
         if (a->s8_rows == 4)
@@ -721,102 +815,36 @@ int enqueue_forward_backward_slab(hp_agent *a, const GatherCtx *gc, bool fuse_ad
     } else {
         // 32-row slabs, forward + backward of a chain in one workgroup; inputs come gathered (enqueue_updates)
         ProfScope ps(a, PROF_GEMM_FWD);
-        P.n_plan = ride ? 1 : 0;
-        P.n_ahead = P.n_pref = P.xcd_split = 0;
         HP_KLOG("k_fb_slab32");
         hipLaunchKernelGGL(s32::k_fb_slab32, dim3(2 * nslab + P.n_plan), dim3(S32_THREADS), 0, s, P);
         HP_CHECK_HIP(hipGetLastError());
     }
-    if (only != 1) {   // all weight gradients (+ the optimizer when no gradient exchange follows) as their own launch
-        Launch L = build_dw_group(a, sXA, sXP, gc ? gc->grads_out : nullptr);
-        const bool riders = ride_dw && ((gc->next_plan && gc->rng) || gc->ahead_plan);
-        RideArgs R;
-        memset(&R, 0, sizeof(R));
-        if (riders) {
-            if (gc->next_plan && gc->rng) {
-                R.n_plan = 1;
-                R.rng = gc->rng->d_state; R.meta = gc->b->d_meta; R.next_plan = gc->next_plan; R.future_p = gc->future_p;
-                R.T = gc->b->T; R.plan_batch = a->B;
-            }
-            if (gc->ahead_plan) {
-                // one pass of 32 rows (8 waves x 4 rows in flight) per gather workgroup: each pass is two dependent HBM
-                // latencies, so fewer, longer workgroups made this launch 3 us longer than its tiles (61.0 vs 58.6 us/update at
-                // batch 1024 with 8 vs 32 of them)
-                R.n_ahead = (a->B + 31) / 32 < 64 ? (a->B + 31) / 32 : 64;
-                R.ahead = P.f.gs;
-                R.ahead.plan = gc->ahead_plan; R.ahead.plan_any = gc->ahead_plan;
-                R.ahead.R = xs ? a->R : a->R2;
-                R.aXT = xs ? a->XT : a->XT2; R.aXA = xs ? a->XA : a->XA2; R.aXP = xs ? a->XP : a->XP2;
-                R.ldx = ldx; R.act_off = a->act_off; R.act_dim = a->cfg.act_dim; R.max_action = (float)a->cfg.max_action;
-            }
+    if (only == 1) return HP_OK;
+    // all weight gradients (+ the optimizer when no gradient exchange follows) as their own launch
+    Launch L = build_dw_group(a, built.sXA, built.sXP, gc ? gc->grads_out : nullptr);
+    RideArgs R;
+    memset(&R, 0, sizeof(R));
+    if (built.ride_dw) {
+        if (gc->next_plan && gc->rng) {
+            R.n_plan = 1;
+            R.rng = gc->rng->d_state; R.meta = gc->b->d_meta; R.next_plan = gc->next_plan; R.future_p = gc->future_p;
+            R.T = gc->b->T; R.plan_batch = a->B;
         }
-        if (a->dw64) {
-            // large minibatch: 64 x 64 tiles, batch rows split over workgroups (dw64.h); the riders follow the tiles
-            ProfScope ps(a, PROF_DW);
-            Dw64Args X;
-            HP_TRY(dw64_args(a, L, X));
-            const unsigned grid = X.n_wg + R.n_plan + R.n_ahead;
-            if (fuse_adam) {
-                AdamFuse F = adam_fuse(a);
-                F.keep_grads = (gc == nullptr || a->keep_grads_dbg) ? 1 : 0;
-                if (gc && gc->polyak_after) fold_polyak(a, F);
-                HP_KLOG("k_dw64_adam");
-                hipLaunchKernelGGL(k_dw64_adam, dim3(grid), dim3(DW_THREADS), 0, s, L.g, F, R, X);
-            } else {
-                HP_KLOG("k_dw64");
-                hipLaunchKernelGGL(k_dw64, dim3(grid), dim3(DW_THREADS), 0, s, L.g, R, X);
-            }
-            HP_CHECK_HIP(hipGetLastError());
-        } else if (fuse_adam && gc && gc->peer_u >= 0) {
-            // data-parallel ranks: the tiles exchange by themselves (gemm_lds.h PEER); riders, if any, behind them
-            ProfScope ps(a, PROF_DW);
-            HP_REQUIRE(a->peer && L.tiles <= HP_PEER_TILES, HP_ERR_STATE, "tile-wise exchange: %d tiles exceed the flag rows", L.tiles);
-            const unsigned grid = L.tiles + R.n_plan + R.n_ahead;
-            AdamFuse F = adam_fuse(a);
-            F.keep_grads = a->keep_grads_dbg ? 1 : 0;
-            if (gc->polyak_after) fold_polyak(a, F);
-            HP_KLOG(L.g.uni ? "k_gemm_lds_adam_peer_u" : "k_gemm_lds_adam_peer");
-            hipLaunchKernelGGL(L.g.uni ? k_gemm_lds_adam_peer_u : k_gemm_lds_adam_peer, dim3(grid), dim3(GL_THREADS), 0, s, L.head(0), L.head(1), L.g, F, R,
-                               L.tiles, a->peer->dev, gc->peer_u, a->grad_mean ? 1 : 0, 0);
-            HP_CHECK_HIP(hipGetLastError());
-        } else if (riders) {
-            ProfScope ps(a, PROF_DW);
-            const int front = L.tiles + (sep_bias_on(a) ? L.separate_bias() : 0);   // tiles, then the bias panels, then the riders
-            const unsigned grid = front + R.n_plan + R.n_ahead;
-            if (fuse_adam) {
-                AdamFuse F = adam_fuse(a);
-                F.keep_grads = a->keep_grads_dbg ? 1 : 0;
-                if (gc->polyak_after) fold_polyak(a, F);
-                L.g.loss_wg = a->loss_wg;
-                HP_KLOG(L.g.uni ? "k_gemm_lds_adam_ride_u" : "k_gemm_lds_adam_ride");
-                hipLaunchKernelGGL(L.g.uni ? k_gemm_lds_adam_ride_u : k_gemm_lds_adam_ride, dim3(grid + L.g.loss_wg), dim3(GL_THREADS), 0, s, L.head(0), L.head(1),
-                                   front, L.g, F, R);
-            } else {
-                HP_KLOG(L.g.uni ? "k_gemm_lds_ride_u" : "k_gemm_lds_ride");
-                hipLaunchKernelGGL(L.g.uni ? k_gemm_lds_ride_u : k_gemm_lds_ride, dim3(grid), dim3(GL_THREADS), 0, s, L.g, R, front);
-            }
-            HP_CHECK_HIP(hipGetLastError());
-        } else if (fuse_adam) {
-            ProfScope ps(a, PROF_DW);
-            // inside a sampled update loop nobody reads the gradient vector (hp_agent_get_grads documents this): 1.17 MB of
-            // the ~6.7 MB this kernel leaves dirty in L2 for the end-of-kernel write-back
-            AdamFuse F = adam_fuse(a);
-            F.keep_grads = (gc == nullptr || a->keep_grads_dbg) ? 1 : 0;
-            if (gc && gc->polyak_after) fold_polyak(a, F);
-            const int front = L.tiles + (sep_bias_on(a) ? L.separate_bias() : 0);
-            L.g.loss_wg = a->loss_wg;
-            HP_KLOG(L.g.uni ? "k_gemm_lds_adam_u" : "k_gemm_lds_adam");
-            hipLaunchKernelGGL(L.g.uni ? k_gemm_lds_adam_u : k_gemm_lds_adam, dim3(front + L.g.loss_wg), dim3(GL_THREADS), 0, s, L.head(0), L.head(1), L.g, F);
-            HP_CHECK_HIP(hipGetLastError());
-        } else {
-            HP_TRY(launch_group(a, L, PROF_DW));
+        if (gc->ahead_plan) {
+            // one pass of 32 rows (8 waves x 4 rows in flight) per gather workgroup: each pass is two dependent HBM
+            // latencies, so fewer, longer workgroups made this launch 3 us longer than its tiles (61.0 vs 58.6 us/update at
+            // batch 1024 with 8 vs 32 of them)
+            R.n_ahead = (a->B + 31) / 32 < 64 ? (a->B + 31) / 32 : 64;
+            aim_ahead(a, gc, P.f.gs, R);
+            R.ldx = a->ldx; R.act_off = a->act_off; R.act_dim = a->cfg.act_dim; R.max_action = (float)a->cfg.max_action;
         }
     }
-    return HP_OK;
+    const AdamFuse F = adam_block(a, gc);
+    const bool peer = fuse_adam && gc && gc->seq && gc->seq->opt == SeqPlan::OPT_PEER_TILES;
+    return launch_dw(a, L, fuse_adam ? &F : nullptr, R, peer ? gc->u : -1);
 }
 
-// ---- one update in the split form: k_fb_split8 (chains + the critic's tiles and optimizer step [+ the actor's]), then -- in
-// the two-launch form -- the actor's tiles
+// ---- one update in the split form: k_fb_split8 (chains + the critic's tiles and optimizer step), then the actor's tiles
 // k_fb_split8 with its role table as leading scalar arguments: word r = role r, byte x = its workgroups on XCD x
 static void launch_split(unsigned grid, hipStream_t s, const FbSplitArgs &Q, int tiles_mode = SPLIT_TILES_ADAM) {
     unsigned long long w[SR_N];
@@ -837,33 +865,20 @@ static void split_common(hp_agent *a, FbSplitArgs &Q, int set) {
     Q.sync_other = a->k1_sync + ((set + 1) & 1) * SPLIT_SET_WORDS;
     Q.fault = a->k1_sync + SPLIT_FAULT;
     Q.fault_host = a->fault_host_dev;
-    Q.wait_ticks = 50000000ull;   // 0.5 s of the 100 MHz wall clock: three orders of magnitude beyond a launch
+    Q.wait_ticks = SPLIT_WAIT_TICKS;
 }
 
-static int enqueue_split_update(hp_agent *a, const GatherCtx *gc, FbBuilt &built, bool fuse_adam, int only) {
+static int enqueue_split_update(hp_agent *a, const GatherCtx *gc, FbBuilt &built, int only) {
     HP_REQUIRE(only == 0 && split_fits(a), HP_ERR_STATE, "split launch: not available for this engine / call");
     // what the in-launch tiles do behind their products (slab8_split_args.h): the optimizer step (single rank), the tile-wise rank
     // exchange + the step (data-parallel ranks on a device each, gemm_lds.h PEER), or nothing -- the caller exchanges the gradient
-    // vector and steps in launches of its own (RCCL; two-phase / gated peer memory; utils.sync_grads from a host loop)
-    const int mode = !fuse_adam ? SPLIT_TILES_GRADS : (gc->peer_u >= 0 ? SPLIT_TILES_PEER : SPLIT_TILES_ADAM);
+    // vector and steps in launches of its own (RCCL; two-phase / gated peer memory)
+    const int mode = gc->seq->tiles_mode;
     hipStream_t s = a->ctx->stream;
     FbSlabArgs &P = built.P;
-    const int xs = built.xs, nslab = built.nslab;
+    const int nslab = built.nslab;
     static FbSplitArgs Qz;   // zero template (the struct has padding the kernel never reads)
     FbSplitArgs Q = Qz;
-    P.n_plan = built.ride ? 1 : 0;
-    P.n_ahead = 0;
-    P.xcd_split = 0;
-    P.n_pref = 0;
-    P.ahead = P.f.gs;
-    P.aXT = P.aXA = P.aXP = nullptr;
-    if (gc->ahead_plan) {   // next update's inputs into the other set (the target side gathers its own rows)
-        P.n_ahead = S8_AHEAD_WGS;
-        P.ahead.plan = gc->ahead_plan;
-        P.ahead.plan_any = gc->ahead_plan;
-        P.ahead.R = xs ? a->R : a->R2;
-        P.aXT = xs ? a->XT : a->XT2; P.aXA = xs ? a->XA : a->XA2; P.aXP = xs ? a->XP : a->XP2;
-    }
     Q.tgs = P.f.gs;
     if (gc->t_plan) {
         Q.tgs.plan = gc->t_plan;
@@ -880,28 +895,17 @@ static int enqueue_split_update(hp_agent *a, const GatherCtx *gc, FbBuilt &built
     Launch L = build_dw_half(a, true, built.sXA, mode == SPLIT_TILES_GRADS ? gc->grads_out : nullptr);
     Launch La = build_dw_half(a, false, built.sXP, mode == SPLIT_TILES_GRADS ? gc->grads_out : nullptr);
     Q.tile_stage = 0u | (0u << 4) | (1u << 8) | (2u << 12);
-    const unsigned gate_sel = 4u | (3u << 4) | (5u << 8) | (3u << 12);
     Q.tiles = L.g;
     Q.need_c = (unsigned)nslab;
     // time-line builds: the last launch with target chains AND a plan workgroup stamps
     Q.tl_mark = (gc->t_plan != nullptr && P.n_plan > 0) ? 1 : 0;
-    AdamFuse F = adam_fuse(a);
-    F.keep_grads = a->keep_grads_dbg ? 1 : 0;
-    if (gc->polyak_after) fold_polyak(a, F);
-    F.gate = Q.sync;
-    F.gate_need = (unsigned)nslab;
-    F.gate_sel = gate_sel;
-    F.fault = Q.fault;
-    F.fault_host = a->fault_host_dev;
-    F.gate_ticks = Q.wait_ticks;
-    F.tl_mark = Q.tl_mark;
-    Q.adam = F;
+    Q.adam = adam_block(a, gc, {OptGates::IN_TILES, Q.sync, (unsigned)nslab, 4u | (3u << 4) | (5u << 8) | (3u << 12), Q.tl_mark});
     Q.s = P;
     if (mode == SPLIT_TILES_PEER) {
         HP_REQUIRE(a->peer && a->peer->d_dev && L.tiles + La.tiles <= HP_PEER_TILES, HP_ERR_STATE,
                    "tile-wise exchange in the split launch: %d + %d tiles exceed the flag rows", L.tiles, La.tiles);
         Q.peer = a->peer->d_dev;
-        Q.peer_u = gc->peer_u;
+        Q.peer_u = gc->u;
         Q.peer_mean = a->grad_mean ? 1 : 0;
     }
     const unsigned grid = build_split_roles(a, Q, true, gc->t_plan != nullptr, P.n_plan, P.n_ahead, L.tiles);
@@ -910,55 +914,27 @@ static int enqueue_split_update(hp_agent *a, const GatherCtx *gc, FbBuilt &built
         launch_split(grid, s, Q, mode);
         HP_CHECK_HIP(hipGetLastError());
     }
-    {   // the actor's weight gradients (+ optimizer step): 144 tiles at the reference shapes, one per CU
-        ProfScope ps(a, PROF_DW);
-        if (mode == SPLIT_TILES_GRADS) {
-            // gradients only (k_gemm_lds); the optimizer launch behind the exchange clears this launch's counter set (enqueue_adam /
-            // enqueue_peer_adam take it from split_reset_pending)
-            HP_KLOG(La.g.uni ? "k_gemm_lds_u" : "k_gemm_lds");
-            hipLaunchKernelGGL(La.g.uni ? k_gemm_lds_u : k_gemm_lds, dim3(La.tiles), dim3(GL_THREADS), 0, s, La.g);
-            HP_CHECK_HIP(hipGetLastError());
-            a->split_reset_pending = Q.sync;
-            return HP_OK;
-        }
-        AdamFuse Fa = adam_fuse(a);
-        Fa.keep_grads = a->keep_grads_dbg ? 1 : 0;
-        if (gc->polyak_after) fold_polyak(a, Fa);
-        Fa.reset_sync = Q.sync;   // every split launch then starts from a clean set whatever the parity of the sequence before it
-        if (mode == SPLIT_TILES_PEER) {
-            // the same tiles exchanging by themselves (gemm_lds.h PEER), flag rows behind the critic's; tile 0 writes the loss log
-            // and clears the counter set (the bias gradients stay inside the tn == 0 tiles, as in every tile-wise launch)
-            RideArgs R;
-            memset(&R, 0, sizeof(R));
-            HP_KLOG(La.g.uni ? "k_gemm_lds_adam_peer_u" : "k_gemm_lds_adam_peer");
-            hipLaunchKernelGGL(La.g.uni ? k_gemm_lds_adam_peer_u : k_gemm_lds_adam_peer, dim3(La.tiles), dim3(GL_THREADS), 0, s, La.head(0), La.head(1), La.g, Fa, R,
-                               La.tiles, a->peer->dev, gc->peer_u, a->grad_mean ? 1 : 0, L.tiles);
-        } else {
-            const int front = La.tiles + (sep_bias_on(a) ? La.separate_bias() : 0);
-            La.g.loss_wg = a->loss_wg;
-            HP_KLOG(La.g.uni ? "k_gemm_lds_adam_u" : "k_gemm_lds_adam");
-            hipLaunchKernelGGL(La.g.uni ? k_gemm_lds_adam_u : k_gemm_lds_adam, dim3(front + La.g.loss_wg), dim3(GL_THREADS), 0, s, La.head(0), La.head(1), La.g, Fa);
-        }
-        HP_CHECK_HIP(hipGetLastError());
-    }
-    return HP_OK;
+    // the actor's weight gradients (+ optimizer step): 144 tiles at the reference shapes, one per CU.  The launch clears this
+    // launch's counter set, so that every split launch starts from a clean set whatever the parity of the sequence before it
+    // (gradients only: the optimizer launch behind the exchange does, enqueue_updates).  Tile-wise exchange: flag rows behind the
+    // critic's; tile 0 writes the loss log and clears the set (the bias gradients stay inside the tn == 0 tiles, as in every
+    // tile-wise launch).
+    OptGates g;
+    g.reset_sync = Q.sync;
+    const AdamFuse Fa = adam_block(a, gc, g);
+    RideArgs R;
+    memset(&R, 0, sizeof(R));
+    return launch_dw(a, La, mode == SPLIT_TILES_GRADS ? nullptr : &Fa, R, mode == SPLIT_TILES_PEER ? gc->u : -1, L.tiles);
 }
 
 // target chains of the sequence's first update (its plan: gc->plan) -> Q' set 0; also clears the first update's counter set
-int enqueue_split_prologue(hp_agent *a, const GatherCtx *gc, int tiles_mode) {
+int enqueue_split_prologue(hp_agent *a, const GatherCtx *gc) {
     HP_REQUIRE(gc && split_fits(a), HP_ERR_STATE, "split launch: not available for this engine");
     FbBuilt built;
-    GatherCtx g0 = *gc;
-    g0.pregathered = false;
-    g0.next_plan = nullptr;
-    g0.rng = nullptr;
-    build_fb_args(a, &g0, built);
+    build_fb_args(a, gc, built);   // (the sequence's first gc: its own inputs, no riders)
     FbSlabArgs &P = built.P;
     static FbSplitArgs Qz;
     FbSplitArgs Q = Qz;
-    P.n_plan = P.n_ahead = P.xcd_split = P.n_pref = 0;
-    P.ahead = P.f.gs;
-    P.aXT = P.aXA = P.aXP = nullptr;
     Q.tgs = P.f.gs;
     Q.tgs.plan = gc->plan;
     Q.tgs.plan_any = gc->plan;
@@ -968,53 +944,32 @@ int enqueue_split_prologue(hp_agent *a, const GatherCtx *gc, int tiles_mode) {
     split_common(a, Q, 1);        // sync_other = set 0, the first update's
     Q.need_c = 0u;
     Q.reset_sync = 1;
-    Q.adam = adam_fuse(a);
+    Q.adam = adam_block(a, nullptr);
     Q.s = P;
     const unsigned grid = build_split_roles(a, Q, false, true, 0, 0, 0);
     ProfScope ps(a, PROF_PLAN);   // (once per sequence, with the index draws: not an update's launch)
-    launch_split(grid, a->ctx->stream, Q, tiles_mode);   // (no tiles here: the instantiation the sequence's updates run, so that a rank executes ONE k_fb_split8)
+    // (no tiles here: the instantiation the sequence's updates run, so that a rank executes ONE k_fb_split8)
+    launch_split(grid, a->ctx->stream, Q, gc->seq->tiles_mode);
     HP_CHECK_HIP(hipGetLastError());
     return HP_OK;
 }
 
-static AdamFuse adam_fuse(hp_agent *a) {
-    AdamFuse F;
-    F.p = a->params; F.p_out = a->params; F.m = a->adam_m; F.v = a->adam_v; F.fragF = a->fragF; F.fragD = a->fragD;
-    F.grads_base = a->grads; F.st = a->d_state; F.scal = &a->d_state->neg_step_actor; F.am = arena_map(a); F.n_actor = a->la.total;
-    F.keep_grads = 1;
-    F.tgt = nullptr; F.fragFT = nullptr; F.polyak = 0.f; F.one_minus = 0.f;
-    F.gate = nullptr; F.gate_need = 0u; F.gate_sel = 0u; F.fault = nullptr; F.fault_host = nullptr; F.gate_ticks = 0ull; F.reset_sync = nullptr; F.tl_mark = 0;
-    F.w = (float)(1.0 - a->cfg.adam_beta1); F.b2 = (float)a->cfg.adam_beta2;
-    F.omb2 = (float)(1.0 - a->cfg.adam_beta2); F.eps = (float)a->cfg.adam_eps;
-    F.part = a->part; F.nslab = a->Mp / (a->slab8 ? a->s8_rows : S32_ROWS); F.B = a->B;
-    F.act_dim = a->cfg.act_dim;
-    F.action_l2 = (float)a->cfg.action_l2; F.loss_log = a->loss_log;
-    F.wt = a->Mp <= 768 ? 1 : 0;   // us/update without / with: 40.9 / 40.3 at 256, 44.9 / 44.4 at 384, 46.9 / 46.1 at 512 k8, 53.1 / 52.9 at 768, 55.6 / 55.8 at 1024
-    return F;
-}
-
-int enqueue_adam(hp_agent *a, bool polyak_after) {
+int enqueue_adam(hp_agent *a, const GatherCtx *gc, unsigned *reset_sync) {
     ProfScope ps(a, PROF_ADAM);
+    if (!a->slab) return layers_enqueue_adam(a);
+    OptGates g;
+    g.where = OptGates::ADAM_KERNEL;
+    g.reset_sync = reset_sync;
+    const AdamFuse F = adam_block(a, gc, g);
     const int n = a->n_arena;
-    if (a->slab) {
-        AdamFuse F = adam_fuse(a);
-        if (polyak_after) fold_polyak(a, F);
-        F.reset_sync = a->split_reset_pending;   // behind a split launch whose tiles wrote gradients only (enqueue_split_update)
-        a->split_reset_pending = nullptr;
-        // plain stores in the stand-alone optimizer kernels: write-through (adam_fuse: small minibatches) pays inside a tile launch,
-        // where other workgroups still multiply while the stepped state drains; a kernel that does nothing else only waits for its
-        // own acknowledgements (forced data-parallel world 1, us/update: RCCL form 44.7 -> 43.5, separate peer exchange 45.3 -> 44.9)
-        F.wt = 0;
-        const bool by4 = n % 4 == 0 && a->la.total % 4 == 0;
-        HP_KLOG(by4 ? "k_adam_frag4" : "k_adam_frag");
-        if (by4)
-            hipLaunchKernelGGL(k_adam_frag4, dim3((n / 4 + 255) / 256), dim3(256), 0, a->ctx->stream, F, a->grads, n / 4);
-        else
-            hipLaunchKernelGGL(k_adam_frag, dim3((n + 255) / 256), dim3(256), 0, a->ctx->stream, F, a->grads, n);
-        HP_CHECK_HIP(hipGetLastError());
-        return HP_OK;
-    }
-    return layers_enqueue_adam(a);
+    const bool by4 = n % 4 == 0 && a->la.total % 4 == 0;
+    HP_KLOG(by4 ? "k_adam_frag4" : "k_adam_frag");
+    if (by4)
+        hipLaunchKernelGGL(k_adam_frag4, dim3((n / 4 + 255) / 256), dim3(256), 0, a->ctx->stream, F, a->grads, n / 4);
+    else
+        hipLaunchKernelGGL(k_adam_frag, dim3((n + 255) / 256), dim3(256), 0, a->ctx->stream, F, a->grads, n);
+    HP_CHECK_HIP(hipGetLastError());
+    return HP_OK;
 }
 
 int enqueue_polyak(hp_agent *a) {
@@ -1046,16 +1001,13 @@ int enqueue_forward_backward(hp_agent *a, const GatherCtx *gc, bool fuse_adam, b
     return enqueue_forward_backward_layers(a);
 }
 
-int enqueue_peer_adam(hp_agent *a, int u, bool polyak_after) {
-    AdamFuse F = adam_fuse(a);
-    if (polyak_after) fold_polyak(a, F);
-    F.grads_base = a->grads;
-    F.keep_grads = a->keep_grads_dbg ? 1 : 0;   // RLARM_KEEP_GRADS=1: hp_agent_get_grads then returns the exchanged sum
-    F.reset_sync = a->split_reset_pending;
-    a->split_reset_pending = nullptr;
-    F.wt = 0;   // (plain stores in the stand-alone optimizer kernels: enqueue_adam)
+int enqueue_peer_adam(hp_agent *a, const GatherCtx *gc, unsigned *reset_sync) {
+    OptGates g;
+    g.where = OptGates::PEER_KERNEL;
+    g.reset_sync = reset_sync;
+    const AdamFuse F = adam_block(a, gc, g);
     ProfScope ps(a, PROF_ADAM);
-    return peer_enqueue_adam(a->peer, F, a->n_arena, u, a->grad_mean);
+    return peer_enqueue_adam(a->peer, F, a->n_arena, gc->u, a->grad_mean);
 }
 
 // actor rows on the device.  Scratch layout: [head_bytes of caller data] | X rows | h1 | h2 | h3 | tanh | actions; `fill`

@@ -526,6 +526,44 @@ def _run_cycles(agent, n_cycles=3, n_batches=4, graph=False):
             agent.last_losses(n_cycles * n_batches), agent.o_norm.mean, agent.g_norm.std)
 
 
+def klog(open_, updates, close=(), prologue=()):
+    """The dict update_kernels returns, from runs of identical updates: updates = [(kernels, count), ...]."""
+    return {"open": list(open_), "prologue": list(prologue), "updates": [list(k) for k, c in updates for _ in range(c)],
+            "close": list(close)}
+
+
+# update_kernels(4) per transport and reduction, the whole log
+PEER_END = ["k_peer_seq_end"]
+WORLD1_KLOG = {
+    ("torch", "sum"): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds"], 1)], close=["host:all_reduce", "k_adam_frag4"]),
+    ("torch", "mean"): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds"], 1)], close=["host:all_reduce", "k_adam_frag4"]),
+    ("native", "sum"): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds", "rccl:ncclAllReduce", "k_adam_frag4"], 4)]),
+    ("native", "mean"): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds", "rccl:ncclAllReduce", "k_scale_div", "k_adam_frag4"], 4)]),
+    ("peer", "sum"): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds_adam_peer"], 4)], close=PEER_END),
+    ("peer", "mean"): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds_adam_peer"], 4)], close=PEER_END),
+    ("native+dw64", "sum"): klog(["k_draw_plan"], [(["k_fb_slab8", "k_dw64", "rccl:ncclAllReduce", "k_adam_frag4"], 4)]),
+    ("peer+dw64", "sum"): klog(["k_draw_plan"], [(["k_fb_slab8", "k_dw64", "k_peer_adam"], 4)], close=PEER_END),
+    ("peer+2phase", "sum"): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds", "k_peer_reduce_slice", "k_peer_adam2"], 4)],
+                                 close=PEER_END),
+    ("peer+2phase", "mean"): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds", "k_peer_reduce_slice", "k_peer_adam2"], 4)],
+                                  close=PEER_END),
+    ("peer+notiles", "sum"): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds", "k_peer_adam"], 4)], close=PEER_END),
+    ("peer+notiles", "mean"): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds", "k_peer_adam"], 4)], close=PEER_END),
+    ("peer+split", "sum"): klog(["k_draw_plan"], [(["k_fb_split8<1>", "k_gemm_lds_adam_peer"], 4)], close=PEER_END,
+                                prologue=["k_fb_split8<1>"]),
+    ("peer+split", "mean"): klog(["k_draw_plan"], [(["k_fb_split8<1>", "k_gemm_lds_adam_peer"], 4)], close=PEER_END,
+                                 prologue=["k_fb_split8<1>"]),
+    ("native+split", "sum"): klog(["k_draw_plan"], [(["k_fb_split8<2>", "k_gemm_lds", "rccl:ncclAllReduce", "k_adam_frag4"], 4)],
+                                  prologue=["k_fb_split8<2>"]),
+    ("native+split", "mean"): klog(["k_draw_plan"], [(["k_fb_split8<2>", "k_gemm_lds", "rccl:ncclAllReduce", "k_scale_div",
+                                                       "k_adam_frag4"], 4)], prologue=["k_fb_split8<2>"]),
+    ("peer+notiles+split", "sum"): klog(["k_draw_plan"], [(["k_fb_split8<2>", "k_gemm_lds", "k_peer_adam"], 4)], close=PEER_END,
+                                        prologue=["k_fb_split8<2>"]),
+    ("peer+2phase+split", "sum"): klog(["k_draw_plan"], [(["k_fb_split8<2>", "k_gemm_lds", "k_peer_reduce_slice", "k_peer_adam2"], 4)],
+                                       close=PEER_END, prologue=["k_fb_split8<2>"]),
+}
+
+
 @pytest.mark.parametrize("transport,graph,reduce", [("torch", False, "sum"), ("native", False, "sum"), ("native", True, "sum"),
                                                     ("torch", False, "mean"), ("native", True, "mean"),
                                                     ("peer", False, "sum"), ("peer", True, "sum"), ("peer", True, "mean"),
@@ -550,8 +588,8 @@ def test_rccl_path_world1_equals_single_rank_bitwise(transport, graph, reduce, m
     import socket
     import torch.distributed as dist
     from rl_arm_under_sparse_reward_amd.utils import Communicator
-    split = transport.endswith("+split")
-    if split:                           # the 4-update sequences of _run_cycles take the split form only when forced
+    full = transport
+    if transport.endswith("+split"):    # the 4-update sequences of _run_cycles take the split form only when forced
         transport = transport[:-6]
         monkeypatch.setenv("RLARM_SPLIT", "1")
     if transport.endswith("+2phase"):   # reduce-scatter + all-gather form of the peer exchange (one rank: one slice)
@@ -584,8 +622,8 @@ def test_rccl_path_world1_equals_single_rank_bitwise(transport, graph, reduce, m
         assert (comm.native is not None) == (transport == "native")
         assert (comm.peer is not None) == (transport == "peer")      # one-shot exchange over peer memory (csrc/peer.hip)
         got = _run_cycles(agent, graph=graph)
-        first = agent.update_kernels(4)["updates"][-1][0]        # (a host-driven exchange reports ONE update)
-        assert first.startswith("k_fb_split8<") == split and (not split or first != "k_fb_split8<0>"), first
+        k = agent.update_kernels(4)                              # (a host-driven exchange reports ONE update)
+        assert k == WORLD1_KLOG[full, reduce], k
         _lib.Context.default().synchronize()
         torch.cuda.synchronize()
         agent.close_comm()
@@ -909,17 +947,40 @@ def test_a_failing_deferred_update_names_itself_and_stays_owed():
     assert np.isfinite(empty.last_losses(2)).all()
 
 
-@pytest.mark.parametrize("batch,n_updates,want", [
-    (256, 40, ["k_fb_split8<0>", "k_gemm_lds_adam"]),            # the headline: split launch + the actor's tiles
-    (256, 4, ["k_fb_slab8", "k_gemm_lds_adam"]),                 # short sequences keep the two-launch form
-    (512, 40, ["k_fb_slab8", "k_gemm_lds_adam_ride_u"]),         # 256 chains fill the CUs: plan + gather ride in the tile launch
-    (1024, 40, ["k_fb_slab8", "k_gemm_lds_adam_ride"]),
-    (4096, 40, ["k_fb_slab32", "k_dw64_adam"])])
-def test_update_kernels_names_what_the_launch_logic_enqueues(batch, n_updates, want):
+# The whole launch log of a sequence, per engine shape and switch.
+UPDATE_KLOG = {
+    ("", 256, 40): klog(["k_draw_plan"], [(["k_fb_split8<0>", "k_gemm_lds_adam"], 40)], prologue=["k_fb_split8<0>"]),
+    ("", 256, 4): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds_adam"], 4)]),
+    ("", 256, 1): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds_adam"], 1)]),
+    ("RLARM_SPLIT=0", 256, 40): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds_adam"], 40)]),
+    ("RLARM_SPLIT=1", 256, 4): klog(["k_draw_plan"], [(["k_fb_split8<0>", "k_gemm_lds_adam"], 4)], prologue=["k_fb_split8<0>"]),
+    ("RLARM_SPLIT=1", 256, 1): klog(["k_draw_plan"], [(["k_fb_split8<0>", "k_gemm_lds_adam"], 1)], prologue=["k_fb_split8<0>"]),
+    # the last update has nothing left to draw or gather: no riders
+    ("", 512, 40): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds_adam_ride_u"], 39), (["k_fb_slab8", "k_gemm_lds_adam_u"], 1)]),
+    ("", 1024, 40): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds_adam_ride"], 39), (["k_fb_slab8", "k_gemm_lds_adam"], 1)]),
+    ("", 2048, 40): klog(["k_draw_plan"], [(["k_fb_slab8", "k_dw64_adam"], 40)]),
+    ("", 4096, 40): klog(["k_draw_plan"], [(["k_gather_fused", "k_fb_slab32", "k_dw64_adam"], 1), (["k_fb_slab32", "k_dw64_adam"], 39)]),
+    ("RLARM_ENGINE=layers", 256, 4): klog(["k_draw_plan"], [(["k_gather_fused"] + ["k_gemm_lds"] * 16, 4)]),
+    ("RLARM_FUSE_ADAM=0", 256, 4): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds", "k_adam_frag4"], 4)]),
+    ("RLARM_FUSE_ADAM=0", 1024, 4): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds_ride", "k_adam_frag4"], 3),
+                                                           (["k_fb_slab8", "k_gemm_lds", "k_adam_frag4"], 1)]),
+    ("RLARM_FUSE_ADAM=0", 4096, 4): klog(["k_draw_plan"], [(["k_gather_fused", "k_fb_slab32", "k_dw64", "k_adam_frag4"], 1),
+                                                           (["k_fb_slab32", "k_dw64", "k_adam_frag4"], 3)]),
+}
+
+
+@pytest.mark.parametrize("switch,batch,n_updates", [
+    ("", 256, 40), ("", 256, 4), ("", 256, 1),          # the headline: split launch + the actor's tiles; short sequences: two launches
+    ("RLARM_SPLIT=0", 256, 40), ("RLARM_SPLIT=1", 256, 4), ("RLARM_SPLIT=1", 256, 1),
+    ("", 512, 40),                                        # 256 chains fill the CUs: plan + gather ride in the tile launch
+    ("", 1024, 40), ("", 2048, 40),                       # 8- and 16-row slabs; dw64 from 1536
+    ("", 4096, 40),                                       # slab32
+    ("RLARM_ENGINE=layers", 256, 4),
+    ("RLARM_FUSE_ADAM=0", 256, 4), ("RLARM_FUSE_ADAM=0", 1024, 4), ("RLARM_FUSE_ADAM=0", 4096, 4)])
+def test_update_kernels_names_what_the_launch_logic_enqueues(switch, batch, n_updates, monkeypatch):
     """hp_agent_update_kernels (round 6): the kernels of a sequence read off the library's own launch logic, run under a stream
-    capture that is thrown away.  Per engine shape: the names of a steady-state update, the sequence's opening and closing
-    launches, and -- the capture being discarded -- no effect on the learner: the same updates afterwards give the same bits
-    as on an agent that was never asked."""
+    capture that is thrown away.  Per engine shape and switch: the whole launch log of the sequence, and -- the capture being
+    discarded -- no effect on the learner: the same updates afterwards give the same bits as on an agent that was never asked."""
     def run(ask):
         torch.manual_seed(0)
         agent, rng = make_agent(batch=batch, n_eps=32, seed=21)
@@ -928,11 +989,9 @@ def test_update_kernels_names_what_the_launch_logic_enqueues(batch, n_updates, w
         k = agent.update_kernels(n_updates) if ask else None
         agent._update_network(6)
         return agent, k, (agent._get_flat(NET_ACTOR), agent._get_flat(NET_CRITIC), agent.last_losses(6), rng.get_state()[1], np.asarray([rng.get_state()[2]]))
+    _select_engine(switch, monkeypatch)
     agent, k, asked = run(True)
-    assert len(k["updates"]) == n_updates
-    assert k["updates"][min(2, n_updates - 1)] == want, k["updates"][:3]
-    assert k["open"] and k["open"][0].startswith("k_draw_plan")
-    assert ("k_fb_split8<0>" in k["prologue"]) == want[0].startswith("k_fb_split8")
+    assert k == UPDATE_KLOG[switch, batch, n_updates], k
     assert agent.engine()["kernels_per_update"] == agent.update_kernels()["updates"][2]
     _, _, plain = run(False)
     for a, b in zip(asked, plain):
