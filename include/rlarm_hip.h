@@ -40,7 +40,9 @@ extern "C" {
  * hp_peer_set_gate, hp_ctx_pci_bus_id, hp_agent_status were added.  3 (round 5): hp_buffer_sample_dev (device-output fused
  * sampler) was added.  4 (round 6): hp_ctx_get_stream and hp_ctx_borrow_stream / hp_ctx_return_stream were added (a host that hands
  * device outputs to a framework has them written on the framework's stream for that call instead of rebinding the context), and the sampler's throughput modes
- * (hp_buffer_enable_f32_rows, hp_buffer_sample_dev_f32, hp_buffer_sample_dev_fast).  hp_abi_version() returns the
+ * (hp_buffer_enable_f32_rows, hp_buffer_sample_dev_f32, hp_buffer_sample_dev_fast).  Still 4 (round 7): the training-state entry
+ * points (hp_state_*) were added -- purely additive: no existing declaration, structure or behaviour changed, so a host built against
+ * the round-6 header runs unchanged on this library.  hp_abi_version() returns the
  * library's value; a host must refuse a library whose version differs from the header it was built against. */
 #define HP_ABI_VERSION 4
 
@@ -390,6 +392,62 @@ int hp_agent_train_cycle(hp_agent *ag, hp_buffer *buf, hp_norm *o_norm, hp_norm 
 int hp_agent_train_cycle_pinned(hp_agent *ag, hp_buffer *buf, hp_norm *o_norm, hp_norm *g_norm, hp_rng *rng,
                                 const double *block, int64_t n_new, double future_p, double sq_threshold,
                                 int32_t n_batches, uint64_t *ticket);
+
+/* ---- training state: stop a run and continue it bit for bit ---------------------------------------------
+ * What the reference wished for and never finished (ddpg_agent.py:54-62, "load the data to continue the training", commented
+ * out; its save_checkpoint :158-161 keeps the normalizer statistics and the actor only).  A training state is everything the
+ * learner's future depends on, in `n` named sections of one byte blob (hp_state_layout):
+ *   actor, critic, actor_target, critic_target, adam_{actor,critic}_{m,v}   float32, the reference's flat named_parameters()
+ *       order (utils.py:18-27) -- converted from / to the padded arena on the device, so a blob does not depend on engine, slab
+ *       width or RLARM_* switches;           adam_step  int64 [1] (both optimizers step together)
+ *   {o,g}_norm_{local_sum,local_sumsq,local_count,total_sum,total_sumsq,total_count,mean,std}   normalizer.py:12-20, all of it
+ *   rng_key uint32 [624], rng_pos int32 [1]   the MT19937 stream (np.random.get_state()[1:3])
+ *   buffer_{obs,ag,g,actions}   float64 rows of episodes [0, current_size), slot order;   buffer_counters  int64 [2] =
+ *       current_size, n_transitions_stored (replay_buffer.py:18-19)
+ * NOT part of a state: staged episodes (hp_buffer_stage), sampling plans, gradients, the loss log -- after a restore
+ * hp_agent_get_losses reports only updates made since --, policy snapshots (hp_agent_policy_snapshot must be called again before
+ * hp_agent_act_snapshot) and the profiling state.
+ * Checksum of a section: its bytes as little-endian 64-bit words w_0 .. w_{n-1} (the last zero-padded to 8 bytes),
+ * A = sum w_i mod 2^64, B = sum (i + 1) w_i mod 2^64.  sums[2 i], sums[2 i + 1] = (A, B) of section i. */
+typedef struct {
+    char name[32];
+    int32_t dtype;        /* 0 float32, 1 float64, 2 int64, 3 uint32, 4 int32 */
+    int32_t elem_bytes;
+    int64_t count;        /* elements */
+    int64_t offset;       /* bytes from the start of the blob (a multiple of 256) */
+} hp_state_section;
+typedef struct {          /* shapes a state was captured with: hp_state_restore compares them with the receiving objects */
+    int32_t obs_dim, goal_dim, act_dim, hidden, T, reserved;
+    int64_t capacity;     /* hp_buffer_create's size_episodes: overflow slot draws depend on it (replay_buffer.py:57-71) */
+    int64_t current_size; /* episodes the blob holds */
+} hp_state_dims;
+#define HP_STATE_SECTIONS 32
+/* Sections of a state of `current_size` episodes (< 0: what the buffer holds now) for these objects.  out may be NULL; *n: in, room
+ * in out; out, HP_STATE_SECTIONS.  *total_bytes: size of the blob. */
+int hp_state_layout(hp_agent *ag, hp_buffer *buf, hp_norm *o_norm, hp_norm *g_norm, int64_t current_size, hp_state_section *out,
+                    int32_t *n, size_t *total_bytes);
+/* Snapshot, stream-ordered, without a host wait: the context's stream gets device-to-device copies of every section into an arena
+ * the agent owns (grown when needed) and an event; a second stream waits for the event, sums every section and drains arena and sums
+ * to pinned host memory in chunks.  The learner's next call (hp_agent_train_cycle, ...) may follow at once: it neither waits for the
+ * drain nor can it alter what the drain reads.  One capture at a time: while a ticket has not been fetched, a second capture FAILS
+ * with HP_ERR_STATE (nothing enqueued).  *bytes (may be NULL): size of the blob hp_state_fetch will deliver. */
+int hp_state_capture(hp_agent *ag, hp_buffer *buf, hp_norm *o_norm, hp_norm *g_norm, hp_rng *rng, uint64_t *ticket, size_t *bytes);
+/* Collect a capture: wait != 0 blocks until the drain is over (outside the context's lock: another thread keeps training), else
+ * *done = 0 is returned while it runs.  Then the blob is copied to host_out (`bytes` must be the capture's size), sums[2 *
+ * HP_STATE_SECTIONS] receives the device-side checksums, the ticket is retired and *done = 1.  host_out == NULL abandons the
+ * ticket (waits for its drain).  One thread per ticket. */
+int hp_state_fetch(hp_agent *ag, uint64_t ticket, int32_t wait, void *host_out, size_t bytes, uint64_t *sums, int32_t *done);
+/* Put a state back -- into fresh objects or into ones that have run since (roll-back; cached update and cycle graphs stay
+ * valid).  dims that differ from the receivers are refused with HP_ERR_INVALID and a message naming the field.  The blob is uploaded
+ * into the snapshot arena and summed THERE; sums that differ from `sums` are refused with HP_ERR_INVALID naming the section BEFORE
+ * any live state is touched.  Then: parameters, targets, Adam m / v / step, both normalizers, the random stream, buffer rows into
+ * the same slots, the counters on the device and in the host mirror; the kernels' weight copies are rebuilt as hp_agent_set_params
+ * does, the float32 throughput rows when the buffer has them.  Synchronises. */
+int hp_state_restore(hp_agent *ag, hp_buffer *buf, hp_norm *o_norm, hp_norm *g_norm, hp_rng *rng, const hp_state_dims *dims,
+                     const void *host_in, size_t bytes, const uint64_t *sums);
+/* The checksum kernel on any device memory (8-byte aligned): out2 = (A, B).  blocks = 0: the library's grid, else that many
+ * workgroups (the result does not depend on it).  Synchronises. */
+int hp_state_checksum_dev(hp_ctx *ctx, const void *dev, size_t bytes, int32_t blocks, uint64_t *out2);
 
 /* timing hook for bench.py: average device time (ms) of the kernels tagged `which` over the
  * last recorded region; see DESIGN.md "Measurement". */

@@ -45,6 +45,17 @@ class AgentCfg(C.Structure):
                 ("adam_beta1", C.c_double), ("adam_beta2", C.c_double), ("adam_eps", C.c_double)]
 
 
+class StateSection(C.Structure):
+    _fields_ = [("name", C.c_char * 32), ("dtype", C.c_int32), ("elem_bytes", C.c_int32), ("count", C.c_int64),
+                ("offset", C.c_int64)]
+
+
+class StateDims(C.Structure):
+    _fields_ = [("obs_dim", C.c_int32), ("goal_dim", C.c_int32), ("act_dim", C.c_int32), ("hidden", C.c_int32),
+                ("T", C.c_int32), ("reserved", C.c_int32), ("capacity", C.c_int64), ("current_size", C.c_int64)]
+
+
+STATE_SECTIONS = 32  # HP_STATE_SECTIONS
 ABI_VERSION = 4     # HP_ABI_VERSION of include/rlarm_hip.h this table binds
 
 # entry points declared in include/rlarm_hip_debug.h: diagnostics and test hooks, outside the stable surface
@@ -172,6 +183,15 @@ PROTOTYPES = {
     "hp_agent_profile": (C.c_int, [C.c_void_p, C.c_int32]),
     "hp_agent_profile_read": (C.c_int, [C.c_void_p, f64p, C.c_int32]),
     "hp_agent_destroy": (None, [C.c_void_p]),
+    "hp_state_layout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(StateSection),
+                                  C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    "hp_state_capture": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_size_t)]),
+    "hp_state_fetch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64),
+                                 C.POINTER(C.c_int32)]),
+    "hp_state_restore": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StateDims), C.c_void_p,
+                                   C.c_size_t, C.POINTER(C.c_uint64)]),
+    "hp_state_checksum_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

@@ -239,6 +239,8 @@ struct hp_agent {
         hipEvent_t ready = nullptr;
     } snap[2];
     int snap_cur = -1, snap_pending = -1;
+    // training state (state.hip): snapshot arena, drain stream and pinned copy of hp_state_capture / hp_state_restore, made on first use
+    struct StateArena *state = nullptr;
     // index plans of later updates drawn on a second stream, concurrently with the chain kernel, when the launch has no
     // spare CU for a ride-along plan workgroup (enqueue_updates)
     hipStream_t act_stream = nullptr;
@@ -507,6 +509,8 @@ int cycle_open_launch(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rn
                       double future_p, bool recompute);
 // utils.sync_grads (utils.py:43-48) + both Adam steps of update gc->u as the peer exchange's optimizer kernel(s) (peer.hip)
 int enqueue_peer_adam(hp_agent *a, const GatherCtx *gc, unsigned *reset_sync);
+// ---- defined in state.hip
+void state_arena_destroy(hp_agent *a);
 // ---- defined in agent_layers.hip
 int enqueue_forward_backward_layers(hp_agent *a);
 int layers_enqueue_adam(hp_agent *a);

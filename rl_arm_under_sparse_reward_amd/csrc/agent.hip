@@ -818,6 +818,7 @@ void hp_agent_destroy(hp_agent *a) {
     if (!a) return;
     a->graphs.clear();
     (void)hipStreamSynchronize(a->ctx->stream);
+    state_arena_destroy(a);
     for (void *p : a->owned) (void)hipFree(p);
     if (a->act_stream) {
         (void)hipStreamSynchronize(a->act_stream);

@@ -570,6 +570,7 @@ static int launch_pack(hp_buffer *b, const long long *slots, int64_t first, int6
     return HP_OK;
 }
 int buffer_launch_pack(hp_buffer *b, int64_t n_new) { return launch_pack(b, b->st_slots.as<long long>(), 0, n_new); }
+int buffer_launch_pack_range(hp_buffer *b, int64_t first, int64_t n) { return launch_pack(b, nullptr, first, n); }
 
 // grow a staging allocation; moving it invalidates the captured cycles that read it (hp_buffer::gen)
 static int stage_ensure(hp_buffer *b, DevBuf &d, size_t need) {

@@ -233,6 +233,7 @@ struct hp_buffer {
     size_t ep_act() const { return (size_t)T * act_dim; }
 };
 int buffer_launch_pack(hp_buffer *b, int64_t n_new);   // refresh the throughput rows of the episodes just scattered (no-op when off)
+int buffer_launch_pack_range(hp_buffer *b, int64_t first, int64_t n);   // ... of episodes [first, first + n) (hp_state_restore)
 
 // ------------------------------------------------------------------ normalizer
 #define NORM_MAX 256   // columns a normalizer can hold (bmirobot: 27 observations, 3 goals); hp_norm_create rejects more

@@ -1,0 +1,497 @@
+// state.hip -- the training state: everything a continued run needs (both networks and their targets, Adam m / v / step, both
+// normalizers, the MT19937 stream, the replay buffer's episodes and counters) captured into a snapshot arena in stream order,
+// drained to pinned host memory on a second stream, and restored -- after a device-side checksum of what was uploaded -- into live
+// objects.  The reference has the wish only (ddpg_agent.py:54-62, "load the data to continue the training", commented out).
+//   capture   ctx stream: k_state_flat (arena -> flat order, 8 vectors) | k_state_small | 4 device-to-device row copies | event
+//             drain stream: wait(event) | k_checksum per section | chunked copies to pinned memory | event
+//   restore   upload into the SAME arena | k_checksum per section, compared with the caller's sums | only then: k_state_flat /
+//             k_state_small / row copies the other way, relayout of both parameter sets, throughput rows, host mirrors
+#include "state.h"
+
+typedef unsigned long long u64;
+typedef u64 u64x2 __attribute__((ext_vector_type(2)));
+
+#define ST_ALIGN 256                    // section offsets in the blob
+#define ST_DRAIN_CHUNK (16u << 20)      // bytes per copy of the drain
+
+struct StateArena {
+    char *dev = nullptr;          // the snapshot (capture) / the uploaded state (restore)
+    size_t dev_bytes = 0;
+    u64 *d_sums = nullptr;        // 2 * ST_SECTIONS: (A, B) per section
+    char *pin = nullptr;          // pinned host copy of the snapshot, filled by the drain
+    size_t pin_bytes = 0;
+    u64 *pin_sums = nullptr;
+    hipStream_t drain = nullptr;
+    hipEvent_t captured = nullptr, drained = nullptr;
+    uint64_t ticket = 0;          // of the most recent capture
+    bool pending = false;         // ... which has not been fetched (or abandoned) yet
+    size_t bytes = 0;             // ... and its blob size
+};
+
+// ------------------------------------------------------------------------------- kernels
+// Position-weighted checksum of a section read as little-endian 64-bit words w_0 .. w_{n-1} (the last one zero-padded):
+// A = sum w_i, B = sum (i + 1) w_i, both mod 2^64.  Both sums are associative and commutative, so the grid shape does not
+// matter: grid-stride over 16-byte loads (four in flight per lane), wave reduction, one pair of 64-bit atomic adds per
+// workgroup.  The words that do not fit the 16-byte body (a leading one when the section starts 8 mod 16, a trailing odd one,
+// the padded tail) are added by one thread.
+__device__ __forceinline__ void sum_pair(const u64x2 x, u64 i0, u64 &a, u64 &b) {
+    a += x.x + x.y;
+    b += (i0 + 1ull) * x.x + (i0 + 2ull) * x.y;
+}
+
+__global__ __launch_bounds__(256) void k_checksum(const u64 *__restrict__ w, u64 nwords, unsigned tail_bytes, u64 *out) {
+    const u64 head = (nwords > 0 && ((uintptr_t)w & 8u)) ? 1ull : 0ull;
+    const u64x2 *v = reinterpret_cast<const u64x2 *>(w + head);
+    const u64 npairs = (nwords - head) / 2;
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    u64 a = 0, b = 0;
+    for (; p + 3 * stride < npairs; p += 4 * stride) {
+        const u64x2 x0 = __builtin_nontemporal_load(v + p), x1 = __builtin_nontemporal_load(v + p + stride),
+                    x2 = __builtin_nontemporal_load(v + p + 2 * stride), x3 = __builtin_nontemporal_load(v + p + 3 * stride);
+        sum_pair(x0, head + 2 * p, a, b);
+        sum_pair(x1, head + 2 * (p + stride), a, b);
+        sum_pair(x2, head + 2 * (p + 2 * stride), a, b);
+        sum_pair(x3, head + 2 * (p + 3 * stride), a, b);
+    }
+    for (; p < npairs; p += stride) sum_pair(__builtin_nontemporal_load(v + p), head + 2 * p, a, b);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (head) { a += w[0]; b += w[0]; }
+        if ((nwords - head) & 1ull) { a += w[nwords - 1]; b += nwords * w[nwords - 1]; }
+        if (tail_bytes) {
+            const unsigned char *t = reinterpret_cast<const unsigned char *>(w + nwords);
+            u64 x = 0;
+            for (unsigned k = 0; k < tail_bytes; ++k) x |= (u64)t[k] << (8 * k);
+            a += x;
+            b += (nwords + 1ull) * x;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        a += __shfl_down(a, off);
+        b += __shfl_down(b, off);
+    }
+    __shared__ u64 red[2][4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[0][wave] = a; red[1][wave] = b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        b = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        if (a) atomicAdd(out, a);
+        if (b) atomicAdd(out + 1, b);
+    }
+}
+
+// eight parameter-shaped vectors between the padded arena and the reference's flat order: blockIdx.y = vector
+struct FlatArgs {
+    float *arena[8];   // live arenas: params, params, targets, targets, adam_m, adam_v, adam_m, adam_v
+    float *flat[8];    // sections ST_ACTOR .. ST_ADAM_CRITIC_V of the snapshot
+    FlatMap m[2];      // actor, critic
+};
+
+template <bool RESTORE> __global__ __launch_bounds__(256) void k_state_flat(const FlatArgs A) {
+    const int vec = blockIdx.y;
+    const FlatMap &m = A.m[(vec == 1 || vec == 3 || vec >= 6) ? 1 : 0];   // actor | critic
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m.n) return;
+    const int i = flat_to_arena(m, j);
+    if (RESTORE) A.arena[vec][i] = A.flat[vec][j];   // the arena's padding is zero and stays zero (agent.h)
+    else A.flat[vec][j] = A.arena[vec][i];
+}
+
+// the small state: both normalizers (every field of NormDev but the `sync` scratch), the MT19937 key and position, the Adam
+// step, the buffer's counters.  One workgroup.
+struct SmallArgs {
+    NormDev *nz[2];
+    int size[2];
+    MtState *rng;
+    AgentDevState *st;
+    BufMeta *meta;
+    char *base;
+    long long off[ST_SECTIONS];
+};
+
+template <bool RESTORE, class T> __device__ __forceinline__ void small_copy(T *live, T *snap, int n) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        if (RESTORE) live[i] = snap[i];
+        else snap[i] = live[i];
+    }
+}
+
+template <bool RESTORE> __global__ __launch_bounds__(256) void k_state_small(const SmallArgs A) {
+    for (int k = 0; k < 2; ++k) {
+        NormDev *nz = A.nz[k];
+        const int s0 = k ? ST_GNORM : ST_ONORM, n = A.size[k];
+        auto f32 = [&](int f) { return reinterpret_cast<float *>(A.base + A.off[s0 + f]); };
+        small_copy<RESTORE>(nz->local_sum, f32(NF_LOCAL_SUM), n);
+        small_copy<RESTORE>(nz->local_sumsq, f32(NF_LOCAL_SUMSQ), n);
+        small_copy<RESTORE>(nz->local_count, f32(NF_LOCAL_COUNT), 1);
+        small_copy<RESTORE>(nz->total_sum, f32(NF_TOTAL_SUM), n);
+        small_copy<RESTORE>(nz->total_sumsq, f32(NF_TOTAL_SUMSQ), n);
+        small_copy<RESTORE>(nz->total_count, f32(NF_TOTAL_COUNT), 1);
+        small_copy<RESTORE>(nz->mean, f32(NF_MEAN), n);
+        small_copy<RESTORE>(nz->std, reinterpret_cast<double *>(A.base + A.off[s0 + NF_STD]), n);
+    }
+    small_copy<RESTORE>(A.rng->key, reinterpret_cast<uint32_t *>(A.base + A.off[ST_RNG_KEY]), MT_N);
+    small_copy<RESTORE>(&A.rng->pos, reinterpret_cast<int32_t *>(A.base + A.off[ST_RNG_POS]), 1);
+    small_copy<RESTORE>(&A.st->step, reinterpret_cast<long long *>(A.base + A.off[ST_ADAM_STEP]), 1);
+    long long *cnt = reinterpret_cast<long long *>(A.base + A.off[ST_BUF_COUNTERS]);
+    if (threadIdx.x == 0) {
+        if (RESTORE) {
+            A.meta->current_size = cnt[0];
+            A.meta->n_transitions_stored = cnt[1];
+            A.st->n_logged = 0;   // the loss log is not part of a state: hp_agent_get_losses reports updates made since
+        } else {
+            cnt[0] = A.meta->current_size;
+            cnt[1] = A.meta->n_transitions_stored;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------- host side
+static FlatMap flat_map(const hp_agent *a, bool critic) {
+    const NetLayout &l = critic ? a->lc : a->la;
+    FlatMap m;
+    m.w1 = l.w1; m.b1 = l.b1; m.w2 = l.w2; m.b2 = l.b2; m.w3 = l.w3; m.b3 = l.b3; m.w4 = l.w4; m.b4 = l.b4;
+    m.K1 = l.K1; m.H = a->H; m.xdim = a->xdim; m.act_off = a->act_off;
+    m.in1 = critic ? a->xdim + a->cfg.act_dim : a->xdim;
+    m.out4 = critic ? 1 : a->cfg.act_dim;
+    m.base = critic ? a->la.total : 0;
+    m.n = m.H * m.in1 + m.H + 2 * (m.H * m.H + m.H) + m.out4 * m.H + m.out4;
+    return m;
+}
+
+static const char *const k_norm_field[NORM_FIELDS] = {"local_sum", "local_sumsq", "local_count", "total_sum",
+                                                      "total_sumsq", "total_count", "mean", "std"};
+static const int k_elem_bytes[5] = {4, 8, 8, 4, 4};
+
+static size_t state_layout(const hp_agent *a, const hp_buffer *b, const hp_norm *on, const hp_norm *gn, int64_t cs,
+                           hp_state_section *S) {
+    memset(S, 0, sizeof(hp_state_section) * ST_SECTIONS);
+    auto set = [&](int i, const char *name, int dtype, int64_t count) {
+        snprintf(S[i].name, sizeof(S[i].name), "%s", name);
+        S[i].dtype = dtype;
+        S[i].elem_bytes = k_elem_bytes[dtype];
+        S[i].count = count;
+    };
+    const int64_t na = flat_map(a, false).n, nc = flat_map(a, true).n;
+    set(ST_ACTOR, "actor", SD_F32, na);
+    set(ST_CRITIC, "critic", SD_F32, nc);
+    set(ST_ACTOR_TARGET, "actor_target", SD_F32, na);
+    set(ST_CRITIC_TARGET, "critic_target", SD_F32, nc);
+    set(ST_ADAM_ACTOR_M, "adam_actor_m", SD_F32, na);
+    set(ST_ADAM_ACTOR_V, "adam_actor_v", SD_F32, na);
+    set(ST_ADAM_CRITIC_M, "adam_critic_m", SD_F32, nc);
+    set(ST_ADAM_CRITIC_V, "adam_critic_v", SD_F32, nc);
+    set(ST_ADAM_STEP, "adam_step", SD_I64, 1);
+    for (int k = 0; k < 2; ++k)
+        for (int f = 0; f < NORM_FIELDS; ++f) {
+            char name[32];
+            snprintf(name, sizeof(name), "%s_%s", k ? "g_norm" : "o_norm", k_norm_field[f]);
+            const bool one = f == NF_LOCAL_COUNT || f == NF_TOTAL_COUNT;
+            set((k ? ST_GNORM : ST_ONORM) + f, name, f == NF_STD ? SD_F64 : SD_F32, one ? 1 : (k ? gn->size : on->size));
+        }
+    set(ST_RNG_KEY, "rng_key", SD_U32, MT_N);
+    set(ST_RNG_POS, "rng_pos", SD_I32, 1);
+    set(ST_BUF_OBS, "buffer_obs", SD_F64, cs * (int64_t)b->ep_obs());
+    set(ST_BUF_AG, "buffer_ag", SD_F64, cs * (int64_t)b->ep_ag());
+    set(ST_BUF_G, "buffer_g", SD_F64, cs * (int64_t)b->ep_g());
+    set(ST_BUF_ACT, "buffer_actions", SD_F64, cs * (int64_t)b->ep_act());
+    set(ST_BUF_COUNTERS, "buffer_counters", SD_I64, 2);
+    size_t off = 0;
+    for (int i = 0; i < ST_SECTIONS; ++i) {
+        S[i].offset = (int64_t)off;
+        off += ((size_t)S[i].count * S[i].elem_bytes + ST_ALIGN - 1) / ST_ALIGN * ST_ALIGN;
+    }
+    return off;
+}
+
+static int state_handles(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, const char *who) {
+    HP_REQUIRE(a && b && on && gn && rng, HP_ERR_INVALID, "%s: null handle", who);
+    HP_REQUIRE(b->ctx == a->ctx && on->ctx == a->ctx && gn->ctx == a->ctx && rng->ctx == a->ctx, HP_ERR_INVALID,
+               "%s: the handles belong to different contexts", who);
+    HP_REQUIRE(b->obs_dim == a->cfg.obs_dim && b->goal_dim == a->cfg.goal_dim && b->act_dim == a->cfg.act_dim, HP_ERR_INVALID,
+               "%s: buffer dimensions do not match the agent", who);
+    HP_REQUIRE(on->size == a->cfg.obs_dim && gn->size == a->cfg.goal_dim, HP_ERR_INVALID,
+               "%s: normalizer sizes do not match the agent", who);
+    return HP_OK;
+}
+
+static int arena_get(hp_agent *a, StateArena **out) {
+    if (!a->state) {
+        StateArena *A = new StateArena();
+        a->state = A;
+        HP_CHECK_HIP(hipStreamCreateWithFlags(&A->drain, hipStreamNonBlocking));
+        HP_CHECK_HIP(hipEventCreateWithFlags(&A->captured, hipEventDisableTiming));
+        HP_CHECK_HIP(hipEventCreateWithFlags(&A->drained, hipEventDisableTiming));
+        HP_CHECK_HIP(hipMalloc((void **)&A->d_sums, sizeof(u64) * 2 * ST_SECTIONS));
+        HP_CHECK_HIP(hipHostMalloc((void **)&A->pin_sums, sizeof(u64) * 2 * ST_SECTIONS, hipHostMallocDefault));
+    }
+    *out = a->state;
+    return HP_OK;
+}
+
+// grow the snapshot arena (nobody reads it: the caller has made sure no drain is in flight)
+static int arena_ensure(StateArena *A, size_t need) {
+    if (need <= A->dev_bytes) return HP_OK;
+    if (A->dev) (void)hipFree(A->dev);
+    A->dev = nullptr;
+    A->dev_bytes = 0;
+    HP_CHECK_HIP(hipMalloc((void **)&A->dev, need));
+    A->dev_bytes = need;
+    return HP_OK;
+}
+
+static int launch_checksum(const void *dev, size_t bytes, u64 *d_out, hipStream_t s, int blocks = 0) {
+    const u64 nwords = bytes / 8;
+    if (blocks <= 0) {
+        const u64 want = (nwords / 2 + 256 * 4 - 1) / (256 * 4);   // four 16-byte loads per lane and trip
+        blocks = (int)std::min<u64>(std::max<u64>(want, 1), 2048);
+    }
+    HP_KLOG("k_checksum");
+    hipLaunchKernelGGL(k_checksum, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const u64 *>(dev), nwords,
+                       (unsigned)(bytes % 8), d_out);
+    HP_CHECK_HIP(hipGetLastError());
+    return HP_OK;
+}
+
+static int checksum_sections(StateArena *A, const hp_state_section *S, hipStream_t s) {
+    HP_CHECK_HIP(hipMemsetAsync(A->d_sums, 0, sizeof(u64) * 2 * ST_SECTIONS, s));
+    for (int i = 0; i < ST_SECTIONS; ++i)
+        HP_TRY(launch_checksum(A->dev + S[i].offset, (size_t)S[i].count * S[i].elem_bytes, A->d_sums + 2 * i, s));
+    return HP_OK;
+}
+
+static FlatArgs flat_args(hp_agent *a, char *base, const hp_state_section *S) {
+    FlatArgs F;
+    float *arena[8] = {a->params, a->params, a->targets, a->targets, a->adam_m, a->adam_v, a->adam_m, a->adam_v};
+    for (int v = 0; v < 8; ++v) {
+        F.arena[v] = arena[v];
+        F.flat[v] = reinterpret_cast<float *>(base + S[ST_ACTOR + v].offset);
+    }
+    F.m[0] = flat_map(a, false);
+    F.m[1] = flat_map(a, true);
+    return F;
+}
+
+static SmallArgs small_args(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, char *base,
+                            const hp_state_section *S) {
+    SmallArgs M;
+    M.nz[0] = on->d; M.nz[1] = gn->d;
+    M.size[0] = on->size; M.size[1] = gn->size;
+    M.rng = rng->d_state; M.st = a->d_state; M.meta = b->d_meta; M.base = base;
+    for (int i = 0; i < ST_SECTIONS; ++i) M.off[i] = S[i].offset;
+    return M;
+}
+
+void state_arena_destroy(hp_agent *a) {
+    StateArena *A = a->state;
+    if (!A) return;
+    if (A->drain) (void)hipStreamSynchronize(A->drain);
+    if (A->dev) (void)hipFree(A->dev);
+    if (A->d_sums) (void)hipFree(A->d_sums);
+    if (A->pin) (void)hipHostFree(A->pin);
+    if (A->pin_sums) (void)hipHostFree(A->pin_sums);
+    if (A->captured) (void)hipEventDestroy(A->captured);
+    if (A->drained) (void)hipEventDestroy(A->drained);
+    if (A->drain) (void)hipStreamDestroy(A->drain);
+    delete A;
+    a->state = nullptr;
+}
+
+// --------------------------------------------------------------------------------- C ABI
+extern "C" {
+
+int hp_state_layout(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, int64_t current_size, hp_state_section *out,
+                    int32_t *n, size_t *total_bytes) {
+    HP_REQUIRE(a && b && on && gn && n, HP_ERR_INVALID, "hp_state_layout: null argument");
+    HP_SERIALISE(a);
+    if (current_size < 0) current_size = b->current_size;
+    HP_REQUIRE(current_size <= b->size, HP_ERR_INVALID, "hp_state_layout: current_size %lld exceeds the buffer's capacity %lld",
+               (long long)current_size, (long long)b->size);
+    hp_state_section S[ST_SECTIONS];
+    const size_t total = state_layout(a, b, on, gn, current_size, S);
+    if (out) {
+        HP_REQUIRE(*n >= ST_SECTIONS, HP_ERR_INVALID, "hp_state_layout: room for %d sections, %d needed", *n, ST_SECTIONS);
+        memcpy(out, S, sizeof(S));
+    }
+    *n = ST_SECTIONS;
+    if (total_bytes) *total_bytes = total;
+    return HP_OK;
+}
+
+int hp_state_capture(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, uint64_t *ticket, size_t *bytes) {
+    HP_TRY(state_handles(a, b, on, gn, rng, "hp_state_capture"));
+    HP_REQUIRE(ticket, HP_ERR_INVALID, "hp_state_capture: null ticket");
+    HP_SERIALISE(a);
+    HP_TRY(agent_check_fault(a, "hp_state_capture"));
+    StateArena *A = nullptr;
+    HP_TRY(arena_get(a, &A));
+    HP_REQUIRE(!A->pending, HP_ERR_STATE, "hp_state_capture: the capture with ticket %llu has not been fetched yet "
+               "(hp_state_fetch; a null host_out abandons it)", (unsigned long long)A->ticket);
+    hipStream_t s = a->ctx->stream;
+    const int64_t cs = b->current_size;
+    hp_state_section S[ST_SECTIONS];
+    const size_t total = state_layout(a, b, on, gn, cs, S);
+    // the previous ticket was fetched, so its drain is over: arena and pinned copy are free
+    HP_TRY(arena_ensure(A, total));
+    if (total > A->pin_bytes) {
+        if (A->pin) (void)hipHostFree(A->pin);
+        A->pin = nullptr;
+        A->pin_bytes = 0;
+        HP_CHECK_HIP(hipHostMalloc((void **)&A->pin, total, hipHostMallocDefault));
+        A->pin_bytes = total;
+    }
+    // learner's stream: the snapshot itself, nothing else
+    const FlatArgs F = flat_args(a, A->dev, S);
+    const int nmax = std::max(F.m[0].n, F.m[1].n);
+    HP_KLOG("k_state_flat");
+    hipLaunchKernelGGL(k_state_flat<false>, dim3((unsigned)((nmax + 255) / 256), 8), dim3(256), 0, s, F);
+    HP_CHECK_HIP(hipGetLastError());
+    HP_KLOG("k_state_small");
+    hipLaunchKernelGGL(k_state_small<false>, dim3(1), dim3(256), 0, s, small_args(a, b, on, gn, rng, A->dev, S));
+    HP_CHECK_HIP(hipGetLastError());
+    const double *rows[4] = {b->d_obs, b->d_ag, b->d_g, b->d_act};
+    for (int k = 0; k < 4 && cs > 0; ++k)
+        HP_CHECK_HIP(hipMemcpyAsync(A->dev + S[ST_BUF_OBS + k].offset, rows[k], (size_t)S[ST_BUF_OBS + k].count * 8,
+                                    hipMemcpyDeviceToDevice, s));
+    HP_CHECK_HIP(hipEventRecord(A->captured, s));
+    // drain stream: checksums of the snapshot, then the snapshot and the sums to pinned memory
+    HP_CHECK_HIP(hipStreamWaitEvent(A->drain, A->captured, 0));
+    HP_TRY(checksum_sections(A, S, A->drain));
+    for (size_t off = 0; off < total; off += ST_DRAIN_CHUNK)
+        HP_CHECK_HIP(hipMemcpyAsync(A->pin + off, A->dev + off, std::min<size_t>(ST_DRAIN_CHUNK, total - off),
+                                    hipMemcpyDeviceToHost, A->drain));
+    HP_CHECK_HIP(hipMemcpyAsync(A->pin_sums, A->d_sums, sizeof(u64) * 2 * ST_SECTIONS, hipMemcpyDeviceToHost, A->drain));
+    HP_CHECK_HIP(hipEventRecord(A->drained, A->drain));
+    A->pending = true;
+    A->bytes = total;
+    *ticket = ++A->ticket;
+    if (bytes) *bytes = total;
+    return HP_OK;
+}
+
+int hp_state_fetch(hp_agent *a, uint64_t ticket, int32_t wait, void *host_out, size_t bytes, uint64_t *sums, int32_t *done) {
+    HP_REQUIRE(a, HP_ERR_INVALID, "hp_state_fetch: null handle");
+    StateArena *A = nullptr;
+    {
+        HP_SERIALISE(a);
+        A = a->state;
+        HP_REQUIRE(A && A->pending && ticket == A->ticket, HP_ERR_STATE, "hp_state_fetch: ticket %llu is not the pending capture",
+                   (unsigned long long)ticket);
+        HP_REQUIRE(!host_out || bytes == A->bytes, HP_ERR_INVALID, "hp_state_fetch: the capture holds %zu bytes, the caller gave %zu",
+                   A->bytes, bytes);
+    }
+    // outside the context lock: the trainer keeps enqueueing meanwhile
+    if (wait || !host_out) HP_CHECK_HIP(hipEventSynchronize(A->drained));
+    else {
+        const hipError_t q = hipEventQuery(A->drained);
+        if (q == hipErrorNotReady) {
+            (void)hipGetLastError();
+            if (done) *done = 0;
+            return HP_OK;
+        }
+        HP_CHECK_HIP(q);
+    }
+    // (the pinned copy cannot change under this: a new capture is refused while this ticket is pending)
+    if (host_out) memcpy(host_out, A->pin, A->bytes);
+    if (sums) memcpy(sums, A->pin_sums, sizeof(u64) * 2 * ST_SECTIONS);
+    {
+        HP_SERIALISE(a);
+        A->pending = false;
+    }
+    if (done) *done = 1;
+    return HP_OK;
+}
+
+int hp_state_restore(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, const hp_state_dims *dims,
+                     const void *host_in, size_t bytes, const uint64_t *sums) {
+    HP_TRY(state_handles(a, b, on, gn, rng, "hp_state_restore"));
+    HP_REQUIRE(dims && host_in && sums, HP_ERR_INVALID, "hp_state_restore: null argument");
+    HP_SERIALISE(a);
+    HP_TRY(agent_check_fault(a, "hp_state_restore"));
+#define ST_FIELD(name, got, want)                                                                                   \
+    HP_REQUIRE((long long)(got) == (long long)(want), HP_ERR_INVALID, "hp_state_restore: %s of the state is %lld, the receiver has %lld", \
+               name, (long long)(got), (long long)(want))
+    ST_FIELD("obs", dims->obs_dim, a->cfg.obs_dim);
+    ST_FIELD("goal", dims->goal_dim, a->cfg.goal_dim);
+    ST_FIELD("action", dims->act_dim, a->cfg.act_dim);
+    ST_FIELD("hidden", dims->hidden, a->H);
+    ST_FIELD("T", dims->T, b->T);
+    ST_FIELD("capacity", dims->capacity, b->size);   // the overflow slot draws depend on it (replay_buffer.py:57-71)
+#undef ST_FIELD
+    const int64_t cs = dims->current_size;
+    HP_REQUIRE(cs >= 0 && cs <= b->size, HP_ERR_INVALID, "hp_state_restore: current_size %lld outside [0, %lld]", (long long)cs,
+               (long long)b->size);
+    hp_state_section S[ST_SECTIONS];
+    const size_t total = state_layout(a, b, on, gn, cs, S);
+    HP_REQUIRE(bytes == total, HP_ERR_INVALID, "hp_state_restore: a state of %lld episodes is %zu bytes, the caller gave %zu",
+               (long long)cs, total, bytes);
+    const char *in = static_cast<const char *>(host_in);
+    long long cnt[2];
+    int32_t pos;
+    memcpy(cnt, in + S[ST_BUF_COUNTERS].offset, sizeof(cnt));
+    memcpy(&pos, in + S[ST_RNG_POS].offset, sizeof(pos));
+    HP_REQUIRE(cnt[0] == cs, HP_ERR_INVALID, "hp_state_restore: buffer_counters says current_size %lld, the header %lld", cnt[0],
+               (long long)cs);
+    HP_REQUIRE(pos >= 0 && pos <= MT_N, HP_ERR_INVALID, "hp_state_restore: rng_pos %d outside [0, 624]", pos);
+    StateArena *A = nullptr;
+    HP_TRY(arena_get(a, &A));
+    // a capture still draining reads the arena: let it finish (its pinned copy stays fetchable)
+    if (A->pending) HP_CHECK_HIP(hipEventSynchronize(A->drained));
+    hipStream_t s = a->ctx->stream;
+    HP_TRY(arena_ensure(A, total));
+    // 1. upload into the arena and sum it THERE: nothing live is touched before the sums agree with the caller's
+    HP_CHECK_HIP(hipMemcpyAsync(A->dev, host_in, total, hipMemcpyHostToDevice, s));
+    HP_TRY(checksum_sections(A, S, s));
+    u64 got[2 * ST_SECTIONS];
+    HP_CHECK_HIP(hipMemcpyAsync(got, A->d_sums, sizeof(got), hipMemcpyDeviceToHost, s));
+    HP_CHECK_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < ST_SECTIONS; ++i)
+        HP_REQUIRE(got[2 * i] == sums[2 * i] && got[2 * i + 1] == sums[2 * i + 1], HP_ERR_INVALID,
+                   "hp_state_restore: checksum of '%s' on the device is (%016llx, %016llx), the state says (%016llx, %016llx): nothing "
+                   "was restored", S[i].name, got[2 * i], got[2 * i + 1], (u64)sums[2 * i], (u64)sums[2 * i + 1]);
+    // 2. commit.  Parameters, targets and optimizer state into the arenas, then every derived copy as hp_agent_set_params /
+    // hp_agent_sync_targets rebuild them
+    const FlatArgs F = flat_args(a, A->dev, S);
+    const int nmax = std::max(F.m[0].n, F.m[1].n);
+    hipLaunchKernelGGL(k_state_flat<true>, dim3((unsigned)((nmax + 255) / 256), 8), dim3(256), 0, s, F);
+    HP_CHECK_HIP(hipGetLastError());
+    HP_TRY(enqueue_relayout(a, false));
+    HP_TRY(enqueue_relayout(a, true));
+    hipLaunchKernelGGL(k_state_small<true>, dim3(1), dim3(256), 0, s, small_args(a, b, on, gn, rng, A->dev, S));
+    HP_CHECK_HIP(hipGetLastError());
+    double *rows[4] = {b->d_obs, b->d_ag, b->d_g, b->d_act};
+    for (int k = 0; k < 4 && cs > 0; ++k)
+        HP_CHECK_HIP(hipMemcpyAsync(rows[k], A->dev + S[ST_BUF_OBS + k].offset, (size_t)S[ST_BUF_OBS + k].count * 8,
+                                    hipMemcpyDeviceToDevice, s));
+    HP_TRY(buffer_launch_pack_range(b, 0, cs));   // throughput rows, when the receiver has them
+    b->current_size = cs;
+    b->n_transitions_stored = cnt[1];
+    b->staged_n = 0;                 // staged episodes are not part of a state
+    // a policy snapshot taken before now is a copy of parameters that no longer exist: hp_agent_act_snapshot must not serve it
+    a->snap_cur = -1;
+    a->snap_pending = -1;
+    // The cached update and cycle graphs stay valid: they bake in addresses (unchanged) and read every counter from device
+    // memory (BufMeta, AgentDevState, MtState) at run time.
+    HP_CHECK_HIP(hipStreamSynchronize(s));
+    return HP_OK;
+}
+
+int hp_state_checksum_dev(hp_ctx *ctx, const void *dev, size_t bytes, int32_t blocks, uint64_t *out2) {
+    HP_REQUIRE(ctx && out2 && (dev || bytes == 0), HP_ERR_INVALID, "hp_state_checksum_dev: null argument");
+    HP_REQUIRE(((uintptr_t)dev & 7u) == 0, HP_ERR_INVALID, "hp_state_checksum_dev: the data must start on an 8-byte boundary");
+    HP_REQUIRE(blocks >= 0 && blocks <= 65536, HP_ERR_INVALID, "hp_state_checksum_dev: blocks must be in [0, 65536]");
+    CtxGuard guard(ctx);
+    out2[0] = out2[1] = 0;
+    if (bytes == 0) return HP_OK;
+    HP_TRY(ctx->reward_ws.ensure(256));
+    u64 *d = ctx->reward_ws.as<u64>();
+    HP_CHECK_HIP(hipMemsetAsync(d, 0, 16, ctx->stream));
+    HP_TRY(launch_checksum(dev, bytes, d, ctx->stream, blocks));
+    HP_CHECK_HIP(hipMemcpyAsync(out2, d, 16, hipMemcpyDeviceToHost, ctx->stream));
+    HP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    return HP_OK;
+}
+
+}  // extern "C"

@@ -513,6 +513,27 @@ class ddpg_agent:
         self.o_norm.set_stats(o_mean, o_std)
         self.g_norm.set_stats(g_mean, g_std)
 
+    # ------------------------------------------------------------------ training state (train_state.py, csrc/state.hip)
+    def save_training_state(self, path, wait=True, extra=None, epoch=0, cycle=0):
+        """Everything a continued run needs -- what ddpg_agent.py:54-62 wished for ("load the data to continue the training") --
+        in one .npz of named arrays: both networks and targets, Adam m / v / step, both normalizers, the device random stream,
+        the replay buffer, and the host side (numpy's global stream, success_rates, savetime, `epoch` / `cycle` reached, the
+        caller's opaque `extra` bytes, e.g. a pickled simulator).  Pending deferred updates are issued first.  The device part
+        is snapshotted in stream order without a host wait; wait=False returns a handle whose `.result()` finishes the file
+        while training goes on (one capture at a time: a second one before `.result()` raises)."""
+        from . import train_state
+        return train_state.save(self, path, wait=wait, extra=extra, epoch=epoch, cycle=cycle)
+
+    def load_training_state(self, path):
+        """Continue from `save_training_state`'s file, in a fresh agent or in this one after more cycles (roll-back): the run
+        that follows is bit-identical to the one that never stopped.  Refused, with nothing changed, when dims, capacity, T, rank
+        or world size differ or the uploaded bytes do not sum on the device to what the file records.  Returns `extra`; the
+        epoch / cycle the state was saved at are in `self.resumed_at`."""
+        from . import train_state
+        extra, manifest = train_state.load(self, path)
+        self.resumed_at = (int(manifest["epoch"]), int(manifest["cycle"]))
+        return extra
+
     # ------------------------------------------------------------------ rollout side (host glue, SURVEY 8f N1)
     def _preproc_inputs(self, obs, g):
         inputs = np.concatenate([self.o_norm.normalize(obs), self.g_norm.normalize(g)])
@@ -587,8 +608,15 @@ class ddpg_agent:
         environment; a list of environments is stepped in lockstep, which reorders the exploration draws).  The
         hand-back synchronises, which the next rollout needs anyway: it evaluates the updated actor."""
         share = bool(getattr(self.args, "share_numpy_stream", True))
+        # optional: args.resume = a training state to continue from (ddpg_agent.py:54-62), args.state_path = where to save one
+        # after every epoch's evaluation; each rank has its own file (its buffer is its shard of the episodes)
+        state_path, resume, first_epoch = getattr(self.args, "state_path", None), getattr(self.args, "resume", None), 0
+        if resume:
+            from .train_state import rank_path
+            self.load_training_state(rank_path(resume, self.comm.rank))
+            first_epoch = self.resumed_at[0]
         print("initial buffer size:", self.buffer.current_size)                  # :97
-        for epoch in range(self.args.n_epochs):
+        for epoch in range(first_epoch, self.args.n_epochs):
             start = time.time()
             for _ in range(self.args.n_cycles):
                 episodes = self.collect_episodes(self.args.num_rollouts_per_mpi, epoch)
@@ -605,6 +633,9 @@ class ddpg_agent:
             if self.comm.rank == 0:
                 print('[{}] epoch is: {}, eval success rate is: {:.3f}'.format(datetime.now(), epoch, rate))
                 self.save_checkpoint()
+            if state_path:
+                from .train_state import rank_path
+                self.save_training_state(rank_path(state_path, self.comm.rank), epoch=epoch + 1)
 
     def _eval_agent(self):
         """ddpg_agent.py:280-304: success at the last step of n_test_rollouts noise-free episodes, averaged over ranks;

@@ -1,0 +1,148 @@
+"""Training-state file format without a device: the numpy twin of the checksum kernel, the writer / reader round trip, `verify`,
+and the atomic write (rl_arm_under_sparse_reward_amd/train_state.py)."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+from rl_arm_under_sparse_reward_amd import train_state as ts
+
+
+def big_int_sums(raw: bytes):
+    """The definition, in Python integers: little-endian 64-bit words, zero-padded; A = sum w_i, B = sum (i + 1) w_i mod 2^64."""
+    raw = raw + b"\0" * ((-len(raw)) % 8)
+    words = [int.from_bytes(raw[i:i + 8], "little") for i in range(0, len(raw), 8)]
+    return sum(words) % 2 ** 64, sum((i + 1) * w for i, w in enumerate(words)) % 2 ** 64
+
+
+@pytest.mark.parametrize("n", [0, 1, 7, 8, 9, 4096 + 3])
+def test_numpy_checksum_equals_the_big_integer_definition(n):
+    raw = np.random.RandomState(n).randint(0, 256, n).astype(np.uint8).tobytes()
+    assert ts.checksum(raw) == big_int_sums(raw)
+    assert ts.checksum(np.frombuffer(raw, np.uint8)) == big_int_sums(raw)
+
+
+def test_numpy_checksum_crosses_its_chunk_boundary():
+    raw = np.random.RandomState(1).randint(0, 256, 8 * (1 << 20) + 24).astype(np.uint8)
+    raw[:64] = 255                      # large words early: B wraps 2^64 many times over
+    assert ts.checksum(raw) == big_int_sums(raw.tobytes())
+
+
+def test_checksum_notices_bit_flips_swaps_and_truncation():
+    raw = bytearray(np.random.RandomState(3).randint(0, 256, 4096 + 3).astype(np.uint8).tobytes())
+    ref = ts.checksum(bytes(raw))
+    flipped = bytearray(raw); flipped[1234] ^= 0x10
+    assert ts.checksum(bytes(flipped)) != ref
+    swapped = bytearray(raw)
+    assert swapped[80:88] != swapped[160:168]
+    swapped[80:88], swapped[160:168] = raw[160:168], raw[80:88]           # two unequal words change places
+    s = ts.checksum(bytes(swapped))
+    assert s[0] == ref[0] and s[1] != ref[1]                               # the plain sum cannot see it, the weighted one does
+    assert ts.checksum(bytes(raw[:4096 - 8])) != ref                       # a shorter word count
+    zeros = bytes(64)
+    assert ts.checksum(zeros) == ts.checksum(zeros[:32]) == (0, 0)         # (all-zero data has no length: the shapes in the manifest do)
+
+
+DIMS = {"obs": 5, "goal": 2, "action": 3, "hidden": 32, "T": 4, "capacity": 7, "current_size": 3}
+
+
+def synthetic_state(seed=0):
+    rs = np.random.RandomState(seed)
+    arrays, listed = {}, {}
+    for name, (dt, shape) in ts.expected_shapes(DIMS).items():
+        if name == "buffer_counters":
+            a = np.array([DIMS["current_size"], DIMS["current_size"] * DIMS["T"]], dt)
+        elif np.dtype(dt).kind == "f":
+            a = rs.normal(size=shape).astype(dt)
+        else:
+            a = rs.randint(0, 2 ** 31 - 1, size=shape).astype(dt)
+        arrays[name] = a
+        listed[name] = {"dtype": dt, "shape": list(shape), "sum": list(ts.checksum(a))}
+    st = np.random.RandomState(9).get_state()
+    arrays.update({"np_random_key": st[1].astype(np.uint32), "success_rates": np.array([0.25, 0.5]),
+                   "extra": np.frombuffer(b"opaque", np.uint8).copy()})
+    manifest = {"format": ts.FORMAT_VERSION, "dims": dict(DIMS), "rank": 0, "world_size": 1, "abi": 4, "arrays": listed,
+                "np_random": {"pos": int(st[2]), "has_gauss": 0, "cached_gaussian": 0.0}, "rng_gauss": [0, 0.0], "savetime": 2,
+                "epoch": 2, "cycle": 0}
+    return arrays, manifest
+
+
+def test_round_trip_and_verify(tmp_path, capsys):
+    arrays, manifest = synthetic_state()
+    path = ts.write_state(tmp_path / "state.npz", arrays, manifest)
+    got, m = ts.read_state(path)
+    assert m == json.loads(json.dumps(manifest)) and sorted(got) == sorted(arrays)
+    for k, a in arrays.items():
+        assert got[k].dtype == a.dtype and got[k].shape == a.shape and got[k].tobytes() == a.tobytes(), k
+    assert ts.verify(path)["dims"] == DIMS
+    assert ts.main(["verify", path]) == 0 and "ok:" in capsys.readouterr().out
+    with np.load(path) as z:                                  # a person can open it: plain named arrays, nothing pickled
+        assert z["actor"].dtype == np.float32 and z["buffer_obs"].shape == (3, 5, 5)
+    assert os.listdir(tmp_path) == ["state.npz"]              # no temporary file left behind
+
+
+def rewrite(tmp_path, arrays, manifest, name="bad.npz"):
+    return ts.write_state(tmp_path / name, arrays, manifest)
+
+
+def test_verify_rejects_a_changed_byte_naming_the_array(tmp_path, capsys):
+    arrays, manifest = synthetic_state()
+    raw = arrays["buffer_ag"].view(np.uint8).reshape(-1).copy()
+    raw[17] ^= 1
+    arrays["buffer_ag"] = raw.view(arrays["buffer_ag"].dtype).reshape(arrays["buffer_ag"].shape)
+    path = rewrite(tmp_path, arrays, manifest)
+    with pytest.raises(ts.StateError, match="'buffer_ag'"):
+        ts.verify(path)
+    assert ts.main(["verify", path]) == 1 and "buffer_ag" in capsys.readouterr().err
+
+
+def test_verify_rejects_a_missing_array_naming_it(tmp_path):
+    arrays, manifest = synthetic_state()
+    del arrays["adam_critic_v"]
+    with pytest.raises(ts.StateError, match="'adam_critic_v' is missing"):
+        ts.verify(rewrite(tmp_path, arrays, manifest))
+
+
+@pytest.mark.parametrize("field, array", [("obs", "actor"), ("T", "buffer_obs"), ("current_size", "buffer_obs"), ("goal", "actor")])
+def test_verify_rejects_an_altered_manifest_dimension_naming_the_array(tmp_path, field, array):
+    arrays, manifest = synthetic_state()
+    manifest["dims"][field] += 1
+    with pytest.raises(ts.StateError, match=f"'{array}'"):
+        ts.verify(rewrite(tmp_path, arrays, manifest))
+
+
+def test_a_file_cut_short_does_not_load(tmp_path):
+    arrays, manifest = synthetic_state()
+    path = ts.write_state(tmp_path / "state.npz", arrays, manifest)
+    raw = open(path, "rb").read()
+    for keep in (len(raw) // 2, len(raw) - 7, 10):
+        cut = tmp_path / f"cut{keep}.npz"
+        cut.write_bytes(raw[:keep])
+        with pytest.raises(ts.StateError):
+            ts.read_state(cut)
+
+
+def test_an_interrupted_write_never_shows_under_the_final_name(tmp_path, monkeypatch):
+    arrays, manifest = synthetic_state()
+    final = tmp_path / "state.npz"
+    ts.write_state(final, arrays, manifest)
+    before = final.read_bytes()
+
+    def killed(f, payload):
+        np.save(f, payload["actor"])          # some bytes are out, then the process dies
+        raise KeyboardInterrupt
+
+    monkeypatch.setattr(ts, "_write_npz", killed)
+    arrays2, manifest2 = synthetic_state(seed=1)
+    with pytest.raises(KeyboardInterrupt):
+        ts.write_state(final, arrays2, manifest2)
+    assert final.read_bytes() == before and os.listdir(tmp_path) == ["state.npz"]   # the old state stands, nothing half-written
+    with pytest.raises(KeyboardInterrupt):
+        ts.write_state(tmp_path / "fresh.npz", arrays2, manifest2)
+    assert not (tmp_path / "fresh.npz").exists()
+
+
+def test_rank_paths():
+    assert ts.rank_path("runs/state.npz", 3) == "runs/state_rank3.npz"
+    assert ts.rank_path("state", 0) == "state_rank0"
