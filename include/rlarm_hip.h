@@ -98,6 +98,22 @@ int hp_rng_get_state(hp_rng *rng, uint32_t *key624, int32_t *pos);        /* syn
 /* test hooks: the primitive draws, results copied to host (synchronises) */
 int hp_rng_randint(hp_rng *rng, int64_t low, int64_t high, int64_t count, int64_t *host_out);
 int hp_rng_uniform(hp_rng *rng, int64_t count, double *host_out);
+/* Skip n_words 32-bit words of the stream as if they had been drawn and thrown away (RandomState.bytes(4 * n_words)), without
+ * walking to them: MT19937 is linear over GF(2), the key block at any offset is an XOR of windows of the next 19937 + 623 words
+ * selected by x^J mod the generator's characteristic polynomial (jump-ahead; Haramoto et al. 2008).  hp_rng_get_state afterwards
+ * equals numpy's (key, pos) bit for bit, word 0 and the pos = 624 boundary rule included.  n_words < 2^62.  Synchronises. */
+int hp_rng_advance(hp_rng *rng, uint64_t n_words);
+/* Parallel form of the sampler's index draw (her.py:24-33) -- the REFERENCE's stream, the same words in the same order, only not
+ * walked by one workgroup: the stream is entered at every 16th block at once (jump-ahead), written out raw, and the four draws
+ * of a batch (randint(N), randint(T), two uniforms) run over it as device-wide passes.  min_batch <= 0: off (the default; nothing
+ * changes for anyone).  min_batch > 0: every index draw of hp_buffer_sample, hp_buffer_sample_dev and hp_buffer_sample_dev_f32 with
+ * batch >= min_batch takes it; indices, outputs and the stream state afterwards are bit-identical to the sequential draw, which
+ * stays enqueued behind it and does the work in the (probability < 2^-64) case that a batch consumes more words than were laid out.
+ * HP_PARALLEL_DRAW_MIN_BATCH is the measured crossover.  Asynchronous and capturable like the calls it serves, except
+ * that the first draw of a larger batch than any before allocates scratch: inside a stream capture such a draw stays sequential.
+ * The fused learner's own plan draws (hp_agent_sample_and_update, hp_agent_train_cycle) never take this path. */
+#define HP_PARALLEL_DRAW_MIN_BATCH 65536
+int hp_rng_set_parallel(hp_rng *rng, int64_t min_batch);
 void hp_rng_destroy(hp_rng *rng);
 
 /* ---- episodic replay buffer ------------------------------------------------------------

@@ -38,6 +38,20 @@ int hp_buffer_sample_dev_us(hp_buffer *buf, hp_rng *rng, hp_norm *o_norm, hp_nor
 int hp_buffer_sample_dev_fast_us(hp_buffer *buf, hp_norm *o_norm, hp_norm *g_norm, int64_t batch, double future_p, double sq_threshold,
                                  double clip_obs, int32_t reps, int32_t f32_rows, double *us);
 
+/* host only, no device needed: limbs312[0 .. 312) = the coefficients of x^n_words mod phi, phi = the characteristic polynomial
+ * of MT19937's one-word transition (degree 19937; bit i of limb i / 64 = coefficient of x^i).  For the generated raw
+ * (untempered) words z_n of any stream:  z_{n + n_words} = XOR over the set coefficients c_i of z_{n + i}.  phi is recovered by
+ * Berlekamp-Massey from the generator's own output on first use and checked against a second seed; HP_ERR_STATE if that fails. */
+int hp_mt_jump_poly(uint64_t n_words, uint64_t *limbs312);
+/* which path the sampler's index draws took (hp_rng_set_parallel): the threshold in force (0 = off) and the device counters of
+ * draws committed by the parallel kernels / done by the sequential kernel behind them.  Synchronises. */
+int hp_rng_parallel_info(hp_rng *rng, int64_t *min_batch, int64_t *n_parallel, int64_t *n_fallback);
+/* test hook: the NEXT parallel draw may use only the first `words` words of the stream it lays out (0 = all), so that a batch
+ * that does not fit takes the ordinary overflow path: nothing committed, the sequential kernel behind does the draw */
+int hp_rng_debug_set_window(hp_rng *rng, int64_t words);
+/* diagnostic: host milliseconds spent so far building this stream's table of jump polynomials */
+int hp_rng_debug_table_ms(hp_rng *rng, double *ms);
+
 /* test hook: load torch.optim.Adam state (exp_avg, exp_avg_sq in the flat order of utils.py:18-27; either may be NULL) and the
  * number of optimizer steps already taken (shared by both optimizers, ddpg_agent.py:272,277 step together) */
 int hp_agent_set_adam(hp_agent *ag, int32_t net, const float *m_host, const float *v_host, int64_t n, int64_t step);

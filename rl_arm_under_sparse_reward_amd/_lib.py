@@ -57,10 +57,12 @@ class StateDims(C.Structure):
 
 STATE_SECTIONS = 32  # HP_STATE_SECTIONS
 ABI_VERSION = 4     # HP_ABI_VERSION of include/rlarm_hip.h this table binds
+PARALLEL_DRAW_MIN_BATCH = 65536   # HP_PARALLEL_DRAW_MIN_BATCH: the measured crossover of the parallel index draw
 
 # entry points declared in include/rlarm_hip_debug.h: diagnostics and test hooks, outside the stable surface
 DEBUG_SYMBOLS = {"hp_ctx_launch_floor", "hp_ctx_event_pair_us", "hp_ctx_clock_mhz", "hp_ctx_calibrate", "hp_buffer_sample_device_us",
                  "hp_buffer_sample_dev_us", "hp_buffer_sample_dev_fast_us",
+                 "hp_mt_jump_poly", "hp_rng_parallel_info", "hp_rng_debug_set_window", "hp_rng_debug_table_ms",
                  "hp_agent_set_adam", "hp_agent_debug_chain", "hp_agent_debug_timeline", "hp_agent_update_kernels"}
 
 # name -> (restype, argtypes); every symbol declared in include/rlarm_hip.h and include/rlarm_hip_debug.h
@@ -86,6 +88,12 @@ PROTOTYPES = {
     "hp_rng_get_state": (C.c_int, [C.c_void_p, u32p, C.POINTER(C.c_int32)]),
     "hp_rng_randint": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, i64p]),
     "hp_rng_uniform": (C.c_int, [C.c_void_p, C.c_int64, f64p]),
+    "hp_rng_advance": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "hp_rng_set_parallel": (C.c_int, [C.c_void_p, C.c_int64]),
+    "hp_rng_parallel_info": (C.c_int, [C.c_void_p, i64p, i64p, i64p]),
+    "hp_rng_debug_set_window": (C.c_int, [C.c_void_p, C.c_int64]),
+    "hp_rng_debug_table_ms": (C.c_int, [C.c_void_p, f64p]),
+    "hp_mt_jump_poly": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64)]),
     "hp_rng_destroy": (None, [C.c_void_p]),
     "hp_buffer_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_void_pp]),
     "hp_buffer_store": (C.c_int, [C.c_void_p, C.c_void_p, f64p, f64p, f64p, f64p, C.c_int64]),

@@ -861,7 +861,7 @@ int hp_buffer_sample(hp_buffer *b, hp_rng *rng, int64_t batch, double future_p, 
     double *d_out = b->out.as<double>();
     double *d_r64 = d_out + batch * row;
     float *d_r = reinterpret_cast<float *>(d_r64 + batch);
-    HP_TRY(rng_launch_plan(rng, b->d_meta, 0, b->T, batch, 1, future_p, d_plan));
+    HP_TRY(rng_launch_plan_sample(rng, b->d_meta, b->T, batch, future_p, d_plan));
     HP_TRY(buffer_launch_gather_dict(b, d_plan, batch, sq_threshold, d_out, d_r, o->r64 ? d_r64 : nullptr));
     double *p = d_out;
     auto pull = [&](double *dst, size_t n) -> hipError_t {
@@ -1003,7 +1003,7 @@ extern "C" int hp_buffer_sample_dev(hp_buffer *b, hp_rng *rng, hp_norm *on, hp_n
     if ((size_t)batch * sizeof(PlanRec) > b->plan.bytes) HP_CHECK_HIP(hipStreamSynchronize(b->ctx->stream));   // an earlier asynchronous call may still read the plan that is about to be freed
     HP_TRY(b->plan.ensure(batch * sizeof(PlanRec)));
     PlanRec *d_plan = b->plan.as<PlanRec>();
-    HP_TRY(rng_launch_plan(rng, b->d_meta, 0, b->T, batch, 1, future_p, d_plan));
+    HP_TRY(rng_launch_plan_sample(rng, b->d_meta, b->T, batch, future_p, d_plan));
     return buffer_launch_gather_fused(b, d_plan, on, gn, batch, sq_threshold, clip_obs, o);
 }
 
@@ -1042,7 +1042,7 @@ extern "C" int hp_buffer_sample_dev_f32(hp_buffer *b, hp_rng *rng, hp_norm *on, 
     if ((size_t)batch * sizeof(PlanRec) > b->plan.bytes) HP_CHECK_HIP(hipStreamSynchronize(b->ctx->stream));
     HP_TRY(b->plan.ensure(batch * sizeof(PlanRec)));
     PlanRec *d_plan = b->plan.as<PlanRec>();
-    HP_TRY(rng_launch_plan(rng, b->d_meta, 0, b->T, batch, 1, future_p, d_plan));
+    HP_TRY(rng_launch_plan_sample(rng, b->d_meta, b->T, batch, future_p, d_plan));
     return buffer_launch_gather_packed(b, d_plan, on, gn, batch, sq_threshold, clip_obs, o);
 }
 
@@ -1130,10 +1130,10 @@ extern "C" int hp_buffer_sample_dev_us(hp_buffer *b, hp_rng *rng, hp_norm *on, h
         ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
     } ev;
     for (int i = 0; i < 3; ++i) HP_CHECK_HIP(hipEventCreate(&ev.e[i]));
-    HP_TRY(rng_launch_plan(rng, b->d_meta, 0, b->T, batch, 1, future_p, d_plan));
+    HP_TRY(rng_launch_plan_sample(rng, b->d_meta, b->T, batch, future_p, d_plan));
     HP_TRY(gather(d_plan, &o));   // warm
     HP_CHECK_HIP(hipEventRecord(ev.e[0], s));
-    for (int i = 0; i < reps; ++i) HP_TRY(rng_launch_plan(rng, b->d_meta, 0, b->T, batch, 1, future_p, d_plan));
+    for (int i = 0; i < reps; ++i) HP_TRY(rng_launch_plan_sample(rng, b->d_meta, b->T, batch, future_p, d_plan));
     HP_CHECK_HIP(hipEventRecord(ev.e[1], s));
     for (int i = 0; i < reps; ++i) HP_TRY(gather(d_plan, &o));
     HP_CHECK_HIP(hipEventRecord(ev.e[2], s));

@@ -184,7 +184,15 @@ struct hp_rng {
     hp_ctx *ctx = nullptr;
     MtState *d_state = nullptr;
     DevBuf scratch;  // test-hook outputs
+    // parallel form of the sampler's index draw + hp_rng_advance (rng_parallel.hip)
+    int64_t par_min_batch = 0;       // hp_rng_set_parallel: draws of at least this many transitions take it; 0 = off
+    int64_t par_debug_window = 0;    // hp_rng_debug_set_window: stream words the NEXT parallel draw may use (0 = all it sized)
+    struct ParCtl *d_par = nullptr;  // device: cursors between the passes, commit / fall-back flags, counters
+    DevBuf par_raw, par_win, par_counts, par_table, par_poly;   // raw stream, 33-block window, chunk counts, jump polynomials
+    std::vector<uint64_t> par_polys; // host copy of the segment table: g_{p S}, p = 1 .. size / 312
+    double par_table_ms = 0;         // host time spent building it (reported once in DESIGN 3.6)
 };
+void rng_parallel_release(hp_rng *rng);
 
 // one drawn transition index record (her.py:24-33)
 struct __attribute__((aligned(16))) PlanRec {
@@ -286,6 +294,9 @@ int comm_allreduce_mean_f32(hp_comm *c, float *dev, size_t n);   // normalizer.p
 int rng_launch_plan(hp_rng *rng, const BufMeta *d_meta, int64_t n_eps_fixed, int32_t T, int64_t batch,
                     int32_t n_batches, double future_p, PlanRec *d_plan, hipStream_t stream = nullptr);
 int rng_launch_slots(hp_rng *rng, hp_buffer *buf, int64_t n_new, int64_t *d_slots);
+// rng_parallel.hip: the index draw of the three sampler entry points -- rng_launch_plan, or its parallel form behind
+// hp_rng_set_parallel (same words, same plan, same final state)
+int rng_launch_plan_sample(hp_rng *rng, const BufMeta *d_meta, int32_t T, int64_t batch, double future_p, PlanRec *d_plan);
 // normalizer plan (batch_first transitions out of n_first staged episodes) + the first n_batches minibatch plans, one launch
 int rng_launch_plan2(hp_rng *rng, int64_t n_first, int32_t T, int64_t batch_first, PlanRec *d_plan_first,
                      const BufMeta *d_meta, int64_t batch, int32_t n_batches, double future_p, PlanRec *d_plan);

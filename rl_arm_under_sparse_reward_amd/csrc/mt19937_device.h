@@ -95,11 +95,9 @@ __device__ __forceinline__ void mt_load(MtWg &g, const MtState *st, uint32_t (*r
     __syncthreads();
 }
 
-__device__ __forceinline__ void mt_store(const MtWg &g, MtState *st) {
-    // numpy keeps (block, pos) with pos in [0,624]; a cursor on a block boundary belongs to the
-    // block just finished (pos == 624 -> "twist before the next word").
-    long long c = g.cursor;
-    int b, pos;
+// numpy keeps (block, pos) with pos in [0,624]; a cursor on a block boundary belongs to the
+// block just finished (pos == 624 -> "twist before the next word").
+__device__ __forceinline__ void mt_final_block(long long c, int &b, int &pos) {
     if (c > 0 && c % MT_N == 0) {
         b = (int)(c / MT_N) - 1;
         pos = MT_N;
@@ -107,6 +105,11 @@ __device__ __forceinline__ void mt_store(const MtWg &g, MtState *st) {
         b = (int)(c / MT_N);
         pos = (int)(c % MT_N);
     }
+}
+
+__device__ __forceinline__ void mt_store(const MtWg &g, MtState *st) {
+    int b, pos;
+    mt_final_block(g.cursor, b, pos);
     __syncthreads();
     for (int k = threadIdx.x; k < MT_N; k += MT_THREADS) st->key[k] = g.blk[b & 3][k];
     if (threadIdx.x == 0) st->pos = pos;
@@ -135,6 +138,28 @@ __device__ __forceinline__ int mt_prefix(MtWg &g, bool acc, int &total) {
     return off + within;
 }
 
+// The per-element arithmetic of the draws, shared with the device-wide form of the same draws (rng_parallel.hip):
+// the rejection mask of randint (smallest 2^k - 1 >= rng), the double of two tempered words, her.py:29 and her.py:31-33.
+__device__ __forceinline__ uint32_t mt_bound_mask(uint32_t rng) {
+    uint32_t mask = rng;
+    mask |= mask >> 1;
+    mask |= mask >> 2;
+    mask |= mask >> 4;
+    mask |= mask >> 8;
+    mask |= mask >> 16;
+    return mask;
+}
+__device__ __forceinline__ double mt_to_double(uint32_t w0, uint32_t w1) {
+    uint32_t a = w0 >> 5;
+    uint32_t b = w1 >> 6;
+    return ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
+}
+__device__ __forceinline__ int mt_her_flag(double u, double future_p) { return (u < future_p) ? 1 : 0; }
+__device__ __forceinline__ int mt_her_future(int t, int T, double u) {
+    double off = u * (double)(T - t);  // her.py:31 (float64 * int64)
+    return t + 1 + (int)off;           // her.py:32-33 (astype(int) truncates)
+}
+
 // legacy randint: `count` values uniform in [0, rng] by masked rejection; emit(i, value).
 template <class Emit>
 __device__ __forceinline__ void mt_draw_bounded(MtWg &g, uint32_t rng, long long count, Emit emit) {
@@ -142,12 +167,7 @@ __device__ __forceinline__ void mt_draw_bounded(MtWg &g, uint32_t rng, long long
         for (long long i = threadIdx.x; i < count; i += MT_THREADS) emit(i, 0u);
         return;
     }
-    uint32_t mask = rng;
-    mask |= mask >> 1;
-    mask |= mask >> 2;
-    mask |= mask >> 4;
-    mask |= mask >> 8;
-    mask |= mask >> 16;
+    const uint32_t mask = mt_bound_mask(rng);
     long long produced = 0;
     while (produced < count) {
         mt_ensure(g, g.cursor + MT_THREADS);
@@ -179,9 +199,7 @@ __device__ __forceinline__ void mt_draw_double(MtWg &g, long long count, Emit em
         if (n > MT_THREADS) n = MT_THREADS;
         mt_ensure(g, g.cursor + 2 * n);
         if ((long long)threadIdx.x < n) {
-            uint32_t a = mt_word(g, g.cursor + 2 * threadIdx.x) >> 5;
-            uint32_t b = mt_word(g, g.cursor + 2 * threadIdx.x + 1) >> 6;
-            double u = ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
+            double u = mt_to_double(mt_word(g, g.cursor + 2 * threadIdx.x), mt_word(g, g.cursor + 2 * threadIdx.x + 1));
             emit(produced + threadIdx.x, u);
         }
         g.cursor += 2 * n;
@@ -227,12 +245,10 @@ __device__ __forceinline__ void mt_her_draw(MtWg &g, long long n_eps, int T, lon
         PlanRec *p = plan + (long long)b * batch;
         mt_draw_bounded(g, (uint32_t)(n_eps - 1), batch, [&](long long i, uint32_t v) { mt_put<WT>(&p[i].e, (int)v); });
         mt_draw_bounded(g, (uint32_t)(T - 1), batch, [&](long long i, uint32_t v) { mt_put<WT>(&p[i].t, (int)v); });
-        mt_draw_double(g, batch, [&](long long i, double u) { mt_put<WT>(&p[i].her, (u < future_p) ? 1 : 0); });
+        mt_draw_double(g, batch, [&](long long i, double u) { mt_put<WT>(&p[i].her, mt_her_flag(u, future_p)); });
         __syncthreads();  // p[i].t may have been written by another thread
         mt_draw_double(g, batch, [&](long long i, double u) {
-            int t = p[i].t;
-            double off = u * (double)(T - t);  // her.py:31 (float64 * int64)
-            mt_put<WT>(&p[i].fut, t + 1 + (int)off);   // her.py:32-33 (astype(int) truncates)
+            mt_put<WT>(&p[i].fut, mt_her_future(p[i].t, T, u));
         });
         __syncthreads();
     }

@@ -188,6 +188,7 @@ void hp_rng_destroy(hp_rng *rng) {
     if (!rng) return;
     if (rng->d_state) (void)hipFree(rng->d_state);
     rng->scratch.release();
+    rng_parallel_release(rng);
     delete rng;
 }
 

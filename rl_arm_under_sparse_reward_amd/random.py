@@ -6,6 +6,7 @@ the stream lives in HBM next to the kernels that consume it; this module mirrors
 numpy calls a reference-style script uses to control it:
 
     seed(s)          <-> np.random.seed(s)
+    advance(n)       <-> np.random.bytes(4 * n), thrown away (jump-ahead: no walk to the new position)
     get_state()      <-> np.random.get_state()      (same 5-tuple)
     set_state(st)    <-> np.random.set_state(st)
 
@@ -64,6 +65,28 @@ class DeviceRandomState:
         _lib.check(self.lib.hp_rng_set_state(self.h, _lib.ptr(key, C.c_uint32), C.c_int32(int(pos))))
         self.seeded = True
         self._gauss = gauss
+
+    def advance(self, n_words):
+        """Skip `n_words` 32-bit words as if they had been drawn and thrown away (hp_rng_advance): the state afterwards is
+        numpy's after `bytes(4 * n_words)`, reached by jump-ahead instead of by generating the words."""
+        n_words = int(n_words)
+        if n_words < 0:
+            raise ValueError("advance: n_words must be non-negative")
+        _lib.check(self.lib.hp_rng_advance(self.h, C.c_uint64(n_words)))
+
+    def set_parallel(self, min_batch=None):
+        """hp_rng_set_parallel: sampler index draws of at least `min_batch` transitions take the parallel form of the reference's
+        draw (None: the library's measured crossover; 0: off).  Same stream, same indices, same state afterwards."""
+        if min_batch is None:
+            min_batch = _lib.PARALLEL_DRAW_MIN_BATCH
+        _lib.check(self.lib.hp_rng_set_parallel(self.h, C.c_int64(int(min_batch))))
+
+    def parallel_info(self):
+        """(min_batch, n_parallel, n_fallback): the threshold in force (0 = off) and how many sampler draws the parallel kernels
+        committed / the sequential kernel behind them did (hp_rng_parallel_info; synchronises)."""
+        m, p, f = C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(self.lib.hp_rng_parallel_info(self.h, C.byref(m), C.byref(p), C.byref(f)))
+        return m.value, p.value, f.value
 
     # test hooks: the two primitive draws of the hot path, executed on the device
     def randint(self, low, high=None, size=1):

@@ -229,6 +229,15 @@ class replay_buffer:
         so a minibatch is one kernel launch whatever its size (the MT19937 draw of 2^18 transitions is a 2 ms sequential kernel)."""
         self._fast_seed, self._fast_calls = int(seed), 0
 
+    def enable_parallel_draw(self, min_batch=None):
+        """Opt into the parallel form of the index draw (hp_rng_set_parallel) for `sample()` and `sample_device()` calls of at
+        least `min_batch` transitions (None: the library's measured crossover; 0 switches it off again).  Unlike
+        enable_fast_draw this IS the reference's random stream: her.py:24-33's four draws take the same MT19937 words in the
+        same order, indices and outputs are bit-identical and `get_state()` afterwards is the same -- the stream is only entered
+        at many offsets at once (jump-ahead) instead of being walked by one workgroup.  The mode belongs to the stream
+        (`self.rng`): buffers that share it share the setting."""
+        self.rng.set_parallel(min_batch)
+
     def sample_device(self, batch_size, o_norm, g_norm, clip_obs=200, f32_rows=False, fast_draw=False):
         """`sample(batch_size)` followed by the learner's preprocessing (ddpg_agent.py:227-243: _preproc_og, both
         normalizers, concatenate, float32 tensors) in one gather kernel with device outputs: a dict of torch CUDA tensors

@@ -1,0 +1,274 @@
+"""hp_rng_advance and the parallel form of the sampler's index draw (csrc/rng_parallel.hip, hp_rng_set_parallel).  Everything is
+compared with numpy's legacy RandomState, the reference-generated goldens and the unchanged sequential draw -- never with the
+parallel code itself -- and every comparison is exact.  hp_rng_parallel_info's device counters prove which path ran."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from conftest import bits, load_golden
+from gpu_common import ENV_PARAMS, DeviceEpisodeBuffer, ctx, fresh_rng, make_shape_episodes, state_equal
+from rl_arm_under_sparse_reward_amd import _lib
+from rl_arm_under_sparse_reward_amd.her import her_sampler, squared_threshold
+from rl_arm_under_sparse_reward_amd.replay_buffer import replay_buffer
+from rl_arm_under_sparse_reward_amd.synthetic import episode_checksum, make_episodes
+
+pytestmark = pytest.mark.gpu
+
+JUMPS = (1, 623, 624, 625, 19937, 624 * 1000, 10 ** 7 + 3)
+OD, GD, AD = 4, 2, 2          # small rows: the draw is what is under test; these shapes take the 16-byte gather kernels
+KEYS = ("obs", "ag", "g", "actions", "obs_next", "ag_next", "r")
+SQ = squared_threshold(0.05)
+
+
+# ---- check 4: hp_rng_advance ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", JUMPS)
+def test_advance_equals_numpy_drawing_and_discarding(n):
+    for seed in (0, 125, 2 ** 32 - 1):
+        for generated_key in (False, True):
+            rs = np.random.RandomState(seed)
+            if generated_key:                     # a key block the generator produced, not init_genrand's
+                rs.bytes(4 * 1000)
+            key = rs.get_state()[1]
+            for pos in (0, 1, 623, 624):
+                rs.set_state(("MT19937", key, pos))
+                dev = fresh_rng()
+                dev.set_state(rs.get_state())
+                rs.bytes(4 * n)
+                dev.advance(n)
+                st = dev.get_state()
+                assert st[2] == rs.get_state()[2], (n, seed, pos)
+                assert np.array_equal(st[1], rs.get_state()[1]), (n, seed, pos)     # all 624 words, word 0 included
+                assert np.array_equal(dev.randint(0, 5000, 700), rs.randint(0, 5000, 700))
+
+
+def test_advance_lands_on_the_boundary_rule_and_rejects_nonsense():
+    rs, dev = np.random.RandomState(5), fresh_rng(5)
+    for n in (624, 624 * 40, 1, 623, 624 * 33, 624 * 34 - 1, 1):     # cursors on block boundaries: pos = 624 of the block just finished
+        rs.bytes(4 * n)
+        dev.advance(n)
+        assert state_equal(dev, *rs.get_state()[1:3]), n
+    dev.advance(0)
+    assert state_equal(dev, *rs.get_state()[1:3])
+    with pytest.raises(ValueError):
+        dev.advance(-1)
+    with pytest.raises(ValueError):
+        dev.advance(2 ** 62)
+
+
+# ---- helpers ----------------------------------------------------------------------------------------------------------------
+def _norms(seed=3):
+    from rl_arm_under_sparse_reward_amd.normalizer import normalizer
+    rs = np.random.RandomState(seed)
+    o, g = normalizer(OD, default_clip_range=5, ctx=ctx()), normalizer(GD, default_clip_range=5, ctx=ctx())
+    o.update(rs.uniform(-1, 1, (64, OD))); g.update(rs.uniform(0, 0.5, (64, GD)))
+    o.recompute_stats(); g.recompute_stats()
+    return o, g
+
+
+def _twin_buffers(n_eps, T):
+    """two buffers holding the same episodes (filling below capacity draws nothing from a stream)"""
+    eps = make_shape_episodes(n_eps, OD, GD, AD, T, seed=n_eps + T)
+    out = []
+    for _ in range(2):
+        b = DeviceEpisodeBuffer(n_eps, T, OD, GD, AD)
+        b.store(fresh_rng(0), eps)
+        b.enable_f32_rows()
+        out.append(b)
+    return out
+
+
+def _call(buf, rng, o, g, B, api):
+    if api == "host":
+        tr, idx = buf.sample(rng, B, 0.8, SQ, with_indices=True)
+        return {**tr, **idx}
+    got, idx = buf.sample_device(rng, o, g, B, 0.8, SQ, 200, with_indices=True, f32_rows=(api == "f32"))
+    return {k: v.cpu().numpy() for k, v in {**got, **idx}.items()}
+
+
+def _same(a, b, what):
+    assert set(a) == set(b)
+    for k in a:
+        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape, (what, k)
+        assert np.array_equal(bits(a[k]), bits(b[k])), (what, k)
+
+
+# ---- check 5: bit identity with the sequential draw --------------------------------------------------------------------------
+@pytest.mark.parametrize("T", [1, 50, 100])
+@pytest.mark.parametrize("n_eps", [1, 2, 100, 5000, 8192, 8193])
+def test_parallel_draw_is_bit_identical_to_the_sequential_draw(n_eps, T):
+    """N = 1: numpy consumes nothing; powers of two: no rejection; 2^k + 1: acceptance just above 1/2, the worst case.  Three
+    consecutive calls per entry point, so a call starts where the previous one ended mid-block."""
+    b_par, b_seq = _twin_buffers(n_eps, T)
+    o, g = _norms()
+    par, seq = fresh_rng(1234 + n_eps), fresh_rng(1234 + n_eps)
+    par.set_parallel(1)
+    assert par.parallel_info() == (1, 0, 0) and seq.parallel_info() == (0, 0, 0)
+    calls = 0
+    for B in (1, 255, 256, 4096, 65537, 2 ** 18):
+        for api in ("host", "dev", "f32"):
+            for rep in range(3):
+                got, ref = _call(b_par, par, o, g, B, api), _call(b_seq, seq, o, g, B, api)
+                _same(got, ref, (n_eps, T, B, api, rep))
+                assert got["e"].max() < n_eps and got["t"].max() < T
+                calls += 1
+                st = seq.get_state()
+                assert state_equal(par, st[1], st[2]), (n_eps, T, B, api, rep)
+                assert par.parallel_info() == (1, calls, 0), (n_eps, T, B, api, rep)    # the parallel kernels did it, every time
+    assert seq.parallel_info() == (0, 0, 0)
+
+
+def test_parallel_draw_matches_numpy_itself():
+    """not only the sequential twin: her.py:24-33 replayed with numpy on the same seed"""
+    n_eps, T, B = 8193, 100, 65537
+    b_par, _ = _twin_buffers(n_eps, T)
+    par, rs = fresh_rng(77), np.random.RandomState(77)
+    par.set_parallel(1)
+    for _ in range(2):
+        _, idx = b_par.sample(par, B, 0.8, SQ, with_indices=True)
+        e, t = rs.randint(0, n_eps, B), rs.randint(T, size=B)
+        her = rs.uniform(size=B) < 0.8
+        fut = (t + 1 + (rs.uniform(size=B) * (T - t)).astype(int))
+        assert np.array_equal(idx["e"], e) and np.array_equal(idx["t"], t)
+        assert np.array_equal(idx["her"], her) and np.array_equal(idx["future_t"], fut)
+        assert state_equal(par, *rs.get_state()[1:3])
+    assert par.parallel_info() == (1, 2, 0)
+
+
+# ---- check 6: the reference KATs through the parallel path --------------------------------------------------------------------
+def test_rng_kat_golden_through_the_parallel_draw():
+    g = load_golden("rng_kat.npz")
+    bufs = {}
+    assert len(g["cases"]) == 38
+    for tag in g["cases"]:
+        tag = str(tag)
+        seed, n, B, k = (int(x[1:]) for x in tag.split("_"))
+        if n not in bufs:
+            b = DeviceEpisodeBuffer(n, 100, 1, 1, 1)
+            z = np.zeros
+            b.store(fresh_rng(0), [z((n, 101, 1)), z((n, 101, 1)), z((n, 100, 1)), z((n, 100, 1))])
+            bufs[n] = b
+        dev = fresh_rng(seed)
+        dev.set_parallel(1)
+        _, idx = bufs[n].sample(dev, B, 1 - 1.0 / (1 + k), 0.0025, with_indices=True)
+        her = g[tag + "_her"]
+        assert np.array_equal(idx["e"], g[tag + "_e"]), tag
+        assert np.array_equal(idx["t"], g[tag + "_t"]), tag
+        assert np.array_equal(idx["her"], her), tag
+        assert np.array_equal(idx["future_t"][her], g[tag + "_future_t"][her]), tag
+        assert state_equal(dev, g[tag + "_key"], g[tag + "_pos"]), tag
+        assert dev.parallel_info() == (1, 1, 0), tag
+
+
+def test_her_sample_golden_through_the_parallel_draw():
+    g = load_golden("her_sample.npz")
+    for tag in g["cases"]:
+        tag = str(tag)
+        n, B, k, seed, dseed = (int(x) for x in g[tag + "_meta"])
+        eps = make_episodes(n, seed=dseed, mode=str(g[tag + "_mode"]))
+        assert episode_checksum(eps) == float(g[tag + "_checksum"])
+        dev = fresh_rng(seed)
+        sampler = her_sampler("future", k, rng=dev)
+        buf = replay_buffer(ENV_PARAMS, n * 100, sampler.sample_her_transitions, rng=dev)
+        buf.store_episode(eps)
+        buf.enable_parallel_draw(min_batch=1)
+        tr = buf.sample(B)
+        for key in KEYS:
+            assert np.array_equal(bits(tr[key]), bits(g[f"{tag}_{key}"])), (tag, key)
+        assert state_equal(dev, g[tag + "_key"], g[tag + "_pos"]), tag
+        assert dev.parallel_info() == (1, 1, 0), tag
+
+
+# ---- check 7: overflow falls back, without a host round trip ------------------------------------------------------------------
+@pytest.mark.parametrize("words", [1, 700, 3000, 9000, 20000])
+def test_a_draw_that_does_not_fit_falls_back_to_the_sequential_kernel(words):
+    """The debug hook shrinks the laid-out stream for ONE call: the first rejection draw (700: inside the loaded key's block),
+    the second, or the uniforms no longer fit.  Nothing is committed, the sequential kernel behind does the draw."""
+    b_par, b_seq = _twin_buffers(8193, 100)
+    o, g = _norms()
+    par, seq = fresh_rng(9), fresh_rng(9)
+    par.set_parallel(1)
+    lib = _lib.load()
+    B = 4096
+    _same(_call(b_par, par, o, g, B, "dev"), _call(b_seq, seq, o, g, B, "dev"), "before")
+    assert par.parallel_info() == (1, 1, 0)
+    _lib.check(lib.hp_rng_debug_set_window(par.h, C.c_int64(words)))
+    _same(_call(b_par, par, o, g, B, "dev"), _call(b_seq, seq, o, g, B, "dev"), "shrunk")
+    assert state_equal(par, *seq.get_state()[1:3])
+    assert par.parallel_info() == (1, 1, 1)
+    _same(_call(b_par, par, o, g, B, "host"), _call(b_seq, seq, o, g, B, "host"), "after")      # the hook was for one call
+    assert state_equal(par, *seq.get_state()[1:3])
+    assert par.parallel_info() == (1, 2, 1)
+
+
+# ---- check 8: off by default, off below the threshold, never in the learner ---------------------------------------------------
+def test_default_and_below_threshold_take_the_sequential_draw():
+    b_par, b_seq = _twin_buffers(100, 50)
+    o, g = _norms()
+    par, seq = fresh_rng(4), fresh_rng(4)
+    for B in (256, 4096):
+        _same(_call(b_par, par, o, g, B, "dev"), _call(b_seq, seq, o, g, B, "dev"), B)
+    assert par.parallel_info() == (0, 0, 0)                      # never enabled
+    par.set_parallel(4096)
+    for B, api in ((256, "dev"), (4095, "host"), (4095, "f32")):
+        _same(_call(b_par, par, o, g, B, api), _call(b_seq, seq, o, g, B, api), B)
+    assert par.parallel_info() == (4096, 0, 0)                   # enabled, below the threshold
+    _same(_call(b_par, par, o, g, 4096, "dev"), _call(b_seq, seq, o, g, 4096, "dev"), 4096)
+    assert par.parallel_info() == (4096, 1, 0)
+    par.set_parallel()                                           # None: the library's measured crossover
+    assert par.parallel_info()[0] == _lib.PARALLEL_DRAW_MIN_BATCH
+    par.set_parallel(0)
+    _same(_call(b_par, par, o, g, 4096, "dev"), _call(b_seq, seq, o, g, 4096, "dev"), "off again")
+    assert par.parallel_info() == (0, 1, 0)
+    assert state_equal(par, *seq.get_state()[1:3])
+
+
+def test_the_fused_learner_never_takes_the_parallel_draw():
+    """hp_agent_update_kernels names exactly the kernels the launch-log test pins for the parent (UPDATE_KLOG), whatever the mode;
+    updates draw their plans with the learner's own kernels and count nothing."""
+    import torch
+    from test_gpu_update import UPDATE_KLOG, make_agent
+
+    def run(mode):
+        torch.manual_seed(0)
+        agent, rng = make_agent(batch=256, n_eps=32, seed=21)
+        agent.buffer.store_episode(make_episodes(15, seed=9, mode="walk"))
+        if mode:
+            agent.buffer.enable_parallel_draw(min_batch=1)
+        agent._update_normalizer()
+        names = agent.update_kernels(40)
+        agent._update_network(6)
+        st = rng.get_state()
+        return names, st, rng.parallel_info()
+
+    (n_on, st_on, info_on), (n_off, st_off, info_off) = run(True), run(False)
+    assert n_on == n_off == UPDATE_KLOG["", 256, 40]
+    assert not [k for k in str(n_on).replace("'", " ").replace(",", " ").split() if k.startswith(("k_par", "k_mt_"))]
+    assert info_on == (1, 0, 0) and info_off == (0, 0, 0)
+    assert np.array_equal(st_on[1], st_off[1]) and st_on[2] == st_off[2]
+
+
+# ---- check 9: capturable ------------------------------------------------------------------------------------------------------
+def test_parallel_draw_replays_from_a_captured_graph():
+    import torch
+    b_par, b_seq = _twin_buffers(5000, 100)
+    o, g = _norms()
+    par, seq = fresh_rng(31), fresh_rng(31)
+    par.set_parallel(1)
+    B = 20000
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):        # warm-up on the capture stream: scratch is allocated here, not under the capture
+        warm = b_par.sample_device(par, o, g, B, 0.8, SQ, 200, with_indices=True)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        out, idx = b_par.sample_device(par, o, g, B, 0.8, SQ, 200, with_indices=True)
+    got = []
+    for _ in range(3):
+        graph.replay()
+        torch.cuda.synchronize()
+        got.append({k: v.cpu().numpy().copy() for k, v in {**out, **idx}.items()})
+    assert par.parallel_info() == (1, 4, 0)                      # the warm-up and three replays; the capture itself ran nothing
+    _same({k: v.cpu().numpy() for k, v in {**warm[0], **warm[1]}.items()}, _call(b_seq, seq, o, g, B, "dev"), "warm-up")
+    for i in range(3):
+        _same(got[i], _call(b_seq, seq, o, g, B, "dev"), i)
+    assert state_equal(par, *seq.get_state()[1:3])
