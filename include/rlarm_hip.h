@@ -62,6 +62,7 @@ typedef struct hp_norm hp_norm;
 typedef struct hp_agent hp_agent;
 typedef struct hp_comm hp_comm;
 typedef struct hp_peer hp_peer;
+typedef struct hp_rollout hp_rollout;
 
 int hp_abi_version(void);
 const char *hp_last_error(void);
@@ -98,6 +99,17 @@ int hp_rng_get_state(hp_rng *rng, uint32_t *key624, int32_t *pos);        /* syn
 /* test hooks: the primitive draws, results copied to host (synchronises) */
 int hp_rng_randint(hp_rng *rng, int64_t low, int64_t high, int64_t count, int64_t *host_out);
 int hp_rng_uniform(hp_rng *rng, int64_t count, double *host_out);
+/* ... and the two other primitive draws of the exploration noise (ddpg_agent.py:174-184), in numpy's legacy form: randn(count)
+ * (polar method with its cached second normal) and binomial(1, p, count) (inversion; qn = exp(log(1 - p')) with p' = p for
+ * p <= 0.5, 1 - p otherwise, computed by the caller's libm once).  Same words consumed as numpy; the normals may differ from
+ * numpy's in the last places (the device's log), the binomials are equal. */
+int hp_rng_standard_normal(hp_rng *rng, int64_t count, double *host_out);
+int hp_rng_binomial1(hp_rng *rng, double p, double qn, int64_t count, int64_t *host_out);
+/* numpy's cached second normal (fields 3 and 4 of the legacy state tuple) lives next to (key, pos) on the device.  hp_rng_seed and
+ * hp_rng_set_state clear it (np.random.seed does; a caller restoring a 5-tuple calls hp_rng_set_gauss after hp_rng_set_state).
+ * Both synchronise. */
+int hp_rng_get_gauss(hp_rng *rng, int32_t *has_gauss, double *gauss);
+int hp_rng_set_gauss(hp_rng *rng, int32_t has_gauss, double gauss);
 /* Skip n_words 32-bit words of the stream as if they had been drawn and thrown away (RandomState.bytes(4 * n_words)), without
  * walking to them: MT19937 is linear over GF(2), the key block at any offset is an XOR of windows of the next 19937 + 623 words
  * selected by x^J mod the generator's characteristic polynomial (jump-ahead; Haramoto et al. 2008).  hp_rng_get_state afterwards
@@ -141,6 +153,9 @@ int hp_host_register(hp_ctx *ctx, void *host, size_t bytes);
 int hp_host_unregister(hp_ctx *ctx, void *host);
 int hp_buffer_store_pinned(hp_buffer *buf, hp_rng *rng, const double *block, int64_t n_new, uint64_t *ticket);
 int hp_buffer_store_done(hp_buffer *buf, uint64_t ticket, int32_t wait, int32_t *done);
+/* store_episode on a block of the same layout that lies in DEVICE memory (a wave collected by hp_rollout_step): a device-to-device
+ * copy in stream order, same slot draw and scatter; no ticket -- the block may be rewritten by later work on the stream. */
+int hp_buffer_store_dev(hp_buffer *buf, hp_rng *rng, const double *block_dev, int64_t n_new);
 int hp_buffer_info(hp_buffer *buf, int64_t *size, int64_t *current_size, int64_t *n_transitions_stored,
                    int32_t *T);
 /* slots chosen by the most recent hp_buffer_store (parity tests); synchronises */
@@ -311,6 +326,32 @@ int hp_agent_critic_forward(hp_agent *ag, int32_t net, const float *x_host, cons
  * rollouts do not, so the drop-in passes 0.  rows = the environments of a vectorised feeder stepped in lockstep. */
 int hp_agent_act(hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, int32_t net, const double *obs_host,
                  const double *g_host, int64_t rows, double clip_obs, float *actions_host);
+/* The same call on rows that lie in device memory (a vectorised simulator's tensors): same kernels, same bits, actions written to
+ * device memory; asynchronous on the context's stream, nothing is copied and nothing waits. */
+int hp_agent_act_dev(hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, int32_t net, const double *obs_dev,
+                     const double *g_dev, int64_t rows, double clip_obs, float *actions_dev);
+
+/* ---- rollouts collected on the device (ddpg_agent.py:101-137 for a vectorised simulator in device memory) -----------------
+ * A wave block holds n_envs episodes in the layout of hp_buffer_store_pinned (dims and T from `buf`).  Per timestep
+ * hp_rollout_step records the current rows (obs[i,t], ag[i,t], g[i,t]), evaluates the online actor as hp_agent_act_dev does
+ * (clip_obs = 0) into actions_f32_dev, and -- explore != 0 -- applies ddpg_agent._select_actions (:174-184) to every row in
+ * the host's order (env i = 0 .. n-1: randn(act), uniform(act), binomial(1, random_eps)) out of `rng`'s stream; qn as
+ * hp_rng_binomial1.  clip_abs > 0 clips the action to +-clip_abs (:118-119).  actions[i,t] is recorded as float64, the float32
+ * actions stay in actions_f32_dev for the simulator.  ag == NULL: actions_f32_dev already holds the policy outputs (action_max
+ * from hp_rollout_set_action_max).  Two launches per timestep, asynchronous, no host copy.  hp_rollout_finish records row T.
+ * hp_rollout_begin selects the episodes [first, first + n_rows) of the block as the wave the following calls step (default: all
+ * n_envs), so more episodes than simulator instances are collected wave after wave into one block.  hp_rollout_read copies one
+ * array (0 obs, 1 ag, 2 g, 3 actions) to the host and synchronises. */
+int hp_rollout_create(hp_ctx *ctx, hp_buffer *buf, int64_t n_envs, hp_rollout **out);
+int hp_rollout_begin(hp_rollout *ro, int64_t first_episode, int64_t n_rows);
+int hp_rollout_set_action_max(hp_rollout *ro, double action_max);
+int hp_rollout_step(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, hp_rng *rng, int32_t t,
+                    const double *obs_dev, const double *ag_dev, const double *g_dev, int32_t explore, double noise_eps,
+                    double random_eps, double qn, double clip_abs, float *actions_f32_dev);
+int hp_rollout_finish(hp_rollout *ro, const double *obs_dev, const double *ag_dev);
+int hp_rollout_block(hp_rollout *ro, void **block_dev, int64_t *n_episodes, int64_t *offsets4, int64_t *elems);
+int hp_rollout_read(hp_rollout *ro, int32_t which, double *host_out);
+void hp_rollout_destroy(hp_rollout *ro);
 
 /* Policy calls that do not queue behind training: hp_agent_policy_snapshot copies the online actor and both normalizers'
  * statistics (stream-ordered with the updates, no host wait); hp_agent_act_snapshot evaluates the most recent COMPLETE
@@ -408,6 +449,10 @@ int hp_agent_train_cycle(hp_agent *ag, hp_buffer *buf, hp_norm *o_norm, hp_norm 
 int hp_agent_train_cycle_pinned(hp_agent *ag, hp_buffer *buf, hp_norm *o_norm, hp_norm *g_norm, hp_rng *rng,
                                 const double *block, int64_t n_new, double future_p, double sq_threshold,
                                 int32_t n_batches, uint64_t *ticket);
+/* ... and on a block in device memory (hp_rollout_block): no DMA from the host, no ticket; same launches otherwise. */
+int hp_agent_train_cycle_dev(hp_agent *ag, hp_buffer *buf, hp_norm *o_norm, hp_norm *g_norm, hp_rng *rng,
+                             const double *block_dev, int64_t n_new, double future_p, double sq_threshold,
+                             int32_t n_batches);
 
 /* ---- training state: stop a run and continue it bit for bit ---------------------------------------------
  * What the reference wished for and never finished (ddpg_agent.py:54-62, "load the data to continue the training", commented

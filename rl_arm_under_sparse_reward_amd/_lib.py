@@ -88,6 +88,10 @@ PROTOTYPES = {
     "hp_rng_get_state": (C.c_int, [C.c_void_p, u32p, C.POINTER(C.c_int32)]),
     "hp_rng_randint": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, i64p]),
     "hp_rng_uniform": (C.c_int, [C.c_void_p, C.c_int64, f64p]),
+    "hp_rng_standard_normal": (C.c_int, [C.c_void_p, C.c_int64, f64p]),
+    "hp_rng_binomial1": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int64, i64p]),
+    "hp_rng_get_gauss": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), f64p]),
+    "hp_rng_set_gauss": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
     "hp_rng_advance": (C.c_int, [C.c_void_p, C.c_uint64]),
     "hp_rng_set_parallel": (C.c_int, [C.c_void_p, C.c_int64]),
     "hp_rng_parallel_info": (C.c_int, [C.c_void_p, i64p, i64p, i64p]),
@@ -101,6 +105,7 @@ PROTOTYPES = {
     "hp_host_register": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "hp_host_unregister": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hp_buffer_store_pinned": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_uint64)]),
+    "hp_buffer_store_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "hp_buffer_store_done": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_int32)]),
     "hp_buffer_info": (C.c_int, [C.c_void_p, i64p, i64p, i64p, C.POINTER(C.c_int32)]),
     "hp_buffer_last_slots": (C.c_int, [C.c_void_p, i64p, C.c_int64]),
@@ -150,6 +155,17 @@ PROTOTYPES = {
     "hp_agent_actor_forward": (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_int64, f32p]),
     "hp_agent_critic_forward": (C.c_int, [C.c_void_p, C.c_int32, f32p, f32p, C.c_int64, f32p]),
     "hp_agent_act": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, f64p, f64p, C.c_int64, C.c_double, f32p]),
+    "hp_agent_act_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_double,
+                                   C.c_void_p]),
+    "hp_rollout_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, c_void_pp]),
+    "hp_rollout_begin": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
+    "hp_rollout_set_action_max": (C.c_int, [C.c_void_p, C.c_double]),
+    "hp_rollout_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    "hp_rollout_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hp_rollout_block": (C.c_int, [C.c_void_p, c_void_pp, i64p, i64p, i64p]),
+    "hp_rollout_read": (C.c_int, [C.c_void_p, C.c_int32, f64p]),
+    "hp_rollout_destroy": (None, [C.c_void_p]),
     "hp_agent_policy_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hp_agent_act_snapshot": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int64, C.c_double, f32p]),
     "hp_agent_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
@@ -181,6 +197,8 @@ PROTOTYPES = {
                                        f64p, C.c_int64, C.c_double, C.c_double, C.c_int32]),
     "hp_agent_train_cycle_pinned": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                               C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_uint64)]),
+    "hp_agent_train_cycle_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_double, C.c_double, C.c_int32]),
     "hp_agent_debug_chain": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, f64p]),
     "hp_agent_debug_timeline": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "hp_agent_update_kernels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,

@@ -736,6 +736,19 @@ int hp_agent_train_cycle_pinned(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm 
     return run_seq(a, {SeqKey::CYCLE, b, on, gn, rng, n_batches, n_new, future_p, sq_threshold, open, b->gen});
 }
 
+// The same cycle on episodes that lie in DEVICE memory in that layout (a wave collected by hp_rollout_step): the staging is a
+// device-to-device copy in stream order, so there is no ticket; slot draw, scatter, normalizer update and cached graph are the same.
+int hp_agent_train_cycle_dev(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, const double *block_dev,
+                             int64_t n_new, double future_p, double sq_threshold, int32_t n_batches) {
+    HP_TRY(check_handles(a, b, on, gn, rng, "hp_agent_train_cycle_dev"));
+    HP_SERIALISE(a);
+    HP_REQUIRE(block_dev, HP_ERR_INVALID, "hp_agent_train_cycle_dev: null block");
+    HP_TRY(train_cycle_checks(a, b, n_new, n_batches, "hp_agent_train_cycle_dev"));
+    const bool open = a->cycle_open && cycle_open_fits(a, n_new);
+    HP_TRY(buffer_stage_dev(b, rng, block_dev, n_new, !open));
+    return run_seq(a, {SeqKey::CYCLE, b, on, gn, rng, n_batches, n_new, future_p, sq_threshold, open, b->gen});
+}
+
 // which launch structure a sequence of n_updates sampled updates WITH optimizer steps takes on this agent: 0 = chain launch +
 // weight-gradient launch, 1 = split launch (slab8_split.h) + the actor's tile launch (data-parallel ranks included, round 6).
 // Gradient-only sequences (with_adam false) never split; hp_agent_update_kernels names the kernels of either.

@@ -1013,7 +1013,8 @@ int enqueue_peer_adam(hp_agent *a, const GatherCtx *gc, unsigned *reset_sync) {
 // actor rows on the device.  Scratch layout: [head_bytes of caller data] | X rows | h1 | h2 | h3 | tanh | actions; `fill`
 // enqueues whatever turns the caller data into X (zeroed beforehand).
 template <typename Fill>
-static int actor_rows(hp_agent *a, int32_t net, int64_t rows, size_t head_bytes, float *actions_host, Fill fill) {
+static int actor_rows(hp_agent *a, int32_t net, int64_t rows, size_t head_bytes, float *actions_host, Fill fill,
+                      float *actions_dev = nullptr) {
     const int H = a->H, ldx = a->ldx, ad = a->cfg.act_dim;
     const int Mp = roundup((int)rows, 32);
     hipStream_t s = a->ctx->stream;
@@ -1040,6 +1041,10 @@ static int actor_rows(hp_agent *a, int32_t net, int64_t rows, size_t head_bytes,
     hipLaunchKernelGGL(k_unpack_actions, dim3((unsigned)((rows * ad + 255) / 256)), dim3(256), 0, s, tp, (int)rows, 16, 0, ad,
                        (float)a->cfg.max_action, outp);
     HP_CHECK_HIP(hipGetLastError());
+    if (actions_dev) {   // device caller (agent_act_dev): the actions stay on the device, in stream order, no host wait
+        HP_CHECK_HIP(hipMemcpyAsync(actions_dev, outp, (size_t)rows * ad * 4, hipMemcpyDeviceToDevice, s));
+        return HP_OK;
+    }
     HP_CHECK_HIP(hipMemcpyAsync(actions_host, outp, (size_t)rows * ad * 4, hipMemcpyDeviceToHost, s));
     HP_CHECK_HIP(hipStreamSynchronize(s));
     return HP_OK;
@@ -1119,7 +1124,50 @@ static int policy_rows_slab(hp_agent *a, hp_norm *on, hp_norm *gn, int32_t net, 
     return HP_OK;
 }
 
+// hp_agent_act for rows that already lie in device memory (a vectorised simulator's tensors, rollout.hip): the same kernels on the
+// caller's pointers -- k_policy_slab8 reads obs / g and writes the actions in place, nothing is copied and nothing waits.
+int agent_act_dev(hp_agent *a, hp_norm *on, hp_norm *gn, int32_t net, const double *obs_dev, const double *g_dev, int64_t rows,
+                  double clip_obs, float *actions_dev) {
+    HP_REQUIRE(net == HP_NET_ACTOR || net == HP_NET_ACTOR_TARGET, HP_ERR_INVALID, "hp_agent_act_dev: net must be an actor");
+    HP_REQUIRE(rows > 0 && rows < (1 << 24), HP_ERR_INVALID, "hp_agent_act_dev: rows out of range");
+    const int od = on->size, gd = gn->size;
+    HP_REQUIRE(od + gd == a->xdim, HP_ERR_INVALID, "hp_agent_act_dev: normalizer sizes %d+%d do not match the actor input %d", od,
+               gd, a->xdim);
+    const double co = clip_obs > 0 ? clip_obs : INFINITY;
+    hipStream_t s = a->ctx->stream;
+    if (a->slab8) {
+        PolicyArgs P;
+        memset(&P, 0, sizeof(P));
+        P.obs = obs_dev; P.g = g_dev;
+        P.od = od; P.gd = gd;
+        P.onz = on->d; P.gnz = gn->d;
+        P.clip_obs = co; P.clip_o = on->clip; P.clip_g = gn->clip;
+        P.rows = (int)rows;
+        P.net = (net == HP_NET_ACTOR) ? SlabNetPtrs{a->fragF, a->fragD, a->params} : SlabNetPtrs{a->fragFT, nullptr, a->targets};
+        P.la = a->la; P.H = a->H; P.act_dim = a->cfg.act_dim; P.max_action = (float)a->cfg.max_action;
+        P.actions = actions_dev;
+        hipLaunchKernelGGL(s8r4::k_policy_slab8, dim3((unsigned)((rows + 3) / 4)), dim3(S8_THREADS), 0, s, P);
+        HP_CHECK_HIP(hipGetLastError());
+        return HP_OK;
+    }
+    return actor_rows(a, net, rows, 0, nullptr, [&](char *, float *X, hipStream_t st) -> int {
+        const long long n = (long long)rows * (od + gd);
+        hipLaunchKernelGGL(k_policy_inputs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, obs_dev, g_dev, (int)rows, od, gd,
+                           on->d, gn->d, co, on->clip, gn->clip, X, a->ldx);
+        HP_CHECK_HIP(hipGetLastError());
+        return (int)HP_OK;
+    }, actions_dev);
+}
+
 extern "C" {
+
+int hp_agent_act_dev(hp_agent *a, hp_norm *on, hp_norm *gn, int32_t net, const double *obs_dev, const double *g_dev,
+                     int64_t rows, double clip_obs, float *actions_dev) {
+    HP_REQUIRE(a && on && gn && obs_dev && g_dev && actions_dev, HP_ERR_INVALID, "hp_agent_act_dev: null argument");
+    HP_SERIALISE(a);
+    HP_REQUIRE(on->ctx == a->ctx && gn->ctx == a->ctx, HP_ERR_INVALID, "hp_agent_act_dev: handles belong to different contexts");
+    return agent_act_dev(a, on, gn, net, obs_dev, g_dev, rows, clip_obs, actions_dev);
+}
 
 int hp_agent_actor_forward(hp_agent *a, int32_t net, const float *x_host, int64_t rows, float *actions_host) {
     HP_REQUIRE(a && x_host && actions_host, HP_ERR_INVALID, "hp_agent_actor_forward: null argument");

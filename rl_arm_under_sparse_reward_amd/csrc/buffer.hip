@@ -657,6 +657,33 @@ int buffer_stage_pinned(hp_buffer *b, hp_rng *rng, const double *block, int64_t 
     return HP_OK;
 }
 
+// Episodes in a device block of the same layout (hp_rollout's wave block): the copy is device to device, in stream order behind
+// the kernels that wrote the block -- no DMA from the host, no ticket.  Slots, scatter, throughput rows as above.
+int buffer_stage_dev(hp_buffer *b, hp_rng *rng, const double *block_dev, int64_t n_new, bool store_now) {
+    hipStream_t s = b->ctx->stream;
+    const size_t n0 = n_new * b->ep_obs() * 8, n1 = n_new * b->ep_ag() * 8, n2 = n_new * b->ep_g() * 8,
+                 n3 = n_new * b->ep_act() * 8;
+    HP_TRY(stage_ensure(b, b->st_slots, n_new * 8));
+    HP_TRY(stage_ensure(b, b->st_obs, n0 + n1 + n2 + n3));
+    char *dst = b->st_obs.as<char>();
+    b->st_ag = reinterpret_cast<double *>(dst + n0);
+    b->st_g = reinterpret_cast<double *>(dst + n0 + n1);
+    b->st_act = reinterpret_cast<double *>(dst + n0 + n1 + n2);
+    HP_CHECK_HIP(hipMemcpyAsync(dst, block_dev, n0 + n1 + n2 + n3, hipMemcpyDeviceToDevice, s));
+    b->staged_n = n_new;
+    if (store_now) {
+        HP_TRY(rng_launch_slots(rng, b, n_new, b->st_slots.as<int64_t>()));
+        hipLaunchKernelGGL(k_store_scatter, dim3((unsigned)(n_new * STORE_PARTS)), dim3(256), 0, s, b->st_slots.as<long long>(),
+                           (long long)n_new, b->st_obs.as<double>(), b->st_ag, b->st_g, b->st_act, b->d_obs, b->d_ag, b->d_g,
+                           b->d_act, (long long)b->ep_obs(), (long long)b->ep_ag(), (long long)b->ep_g(), (long long)b->ep_act());
+        HP_CHECK_HIP(hipGetLastError());
+        HP_TRY(buffer_launch_pack(b, n_new));
+    }
+    b->current_size = (b->current_size + n_new < b->size) ? b->current_size + n_new : b->size;
+    b->n_transitions_stored += (int64_t)b->T * n_new;
+    return HP_OK;
+}
+
 int buffer_stage_for_cycle(hp_buffer *b, const double *obs, const double *ag, const double *g, const double *actions,
                            int64_t n_new) {
     HP_TRY(stage_ensure(b, b->st_slots, n_new * 8));
@@ -732,6 +759,14 @@ int hp_buffer_store_pinned(hp_buffer *b, hp_rng *rng, const double *block, int64
     HP_REQUIRE(n_new > 0, HP_ERR_INVALID, "hp_buffer_store_pinned: n_new must be positive");
     HP_REQUIRE(!(b->current_size == 0 && n_new > b->size), HP_ERR_INVALID, "high <= 0");
     return buffer_stage_pinned(b, rng, block, n_new, ticket, true);
+}
+
+int hp_buffer_store_dev(hp_buffer *b, hp_rng *rng, const double *block_dev, int64_t n_new) {
+    HP_REQUIRE(b && rng && block_dev, HP_ERR_INVALID, "hp_buffer_store_dev: null argument");
+    HP_SERIALISE(b);
+    HP_REQUIRE(n_new > 0, HP_ERR_INVALID, "hp_buffer_store_dev: n_new must be positive");
+    HP_REQUIRE(!(b->current_size == 0 && n_new > b->size), HP_ERR_INVALID, "high <= 0");
+    return buffer_stage_dev(b, rng, block_dev, n_new, true);
 }
 
 int hp_buffer_store_done(hp_buffer *b, uint64_t ticket, int32_t wait, int32_t *done) {

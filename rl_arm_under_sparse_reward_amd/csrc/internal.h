@@ -177,8 +177,10 @@ struct PinnedBuf {
 struct MtState {  // device-resident, same fields as numpy's legacy state tuple
     uint32_t key[MT_N];
     int32_t pos;
-    int32_t pad[3];
+    int32_t has_gauss;   // legacy_gauss's cached second normal (numpy's has_gauss / gauss): written by the normal draws only
+    double gauss;
 };
+static_assert(sizeof(MtState) == MT_N * 4 + 16, "MtState: key | pos | has_gauss | gauss");
 
 struct hp_rng {
     hp_ctx *ctx = nullptr;
@@ -311,6 +313,12 @@ int buffer_stage_for_cycle(hp_buffer *b, const double *obs, const double *ag, co
                            int64_t n_new);
 // the same out of a device-registered host block (feeder ring); store_now: slots + scatter follow at once
 int buffer_stage_pinned(hp_buffer *b, hp_rng *rng, const double *block, int64_t n_new, uint64_t *ticket, bool store_now);
+// the same out of a DEVICE block (a rollout wave collected on the device, rollout.hip): a device-to-device copy, no ticket
+int buffer_stage_dev(hp_buffer *b, hp_rng *rng, const double *block_dev, int64_t n_new, bool store_now);
+
+// agent_engines.hip: hp_agent_act on device rows, actions left on the device, nothing copied, no host wait
+int agent_act_dev(hp_agent *a, hp_norm *on, hp_norm *gn, int32_t net, const double *obs_dev, const double *g_dev, int64_t rows,
+                  double clip_obs, float *actions_dev);
 
 // norm.hip
 int norm_launch_update_from_plan(hp_norm *o, hp_norm *g, hp_buffer *b, const PlanRec *d_plan, int64_t rows,

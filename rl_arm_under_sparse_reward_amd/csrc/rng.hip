@@ -1,5 +1,5 @@
 // rng.hip -- device random stream object + the index-draw kernels of the HER sampler.
-#include "mt19937_device.h"
+#include "mt19937_wave.h"
 
 // ------------------------------------------------------------------------------- kernels
 // her.py:24-33 for `n_batches` consecutive minibatches: plan[b*batch + i] = (e, t, future_t, her).
@@ -68,6 +68,26 @@ __global__ __launch_bounds__(MT_THREADS) void k_test_uniform(MtState *st, long l
     mt_load(g, st, ring, ibuf);
     mt_draw_double(g, count, [&](long long i, double u) { out[i] = u; });
     mt_store(g, st);
+}
+
+// test hooks of the wave-walked draws (mt19937_wave.h): np.random.randn(count) and np.random.binomial(1, eps, count)
+__global__ __launch_bounds__(MW_THREADS) void k_test_normal(MtState *st, long long count, double *out) {
+    __shared__ uint32_t ring[4][MT_N];
+    MwState w;
+    mw_load(w, st, ring);
+    mw_draw_normal(w, count, [&](long long i, double z) { out[i] = z; });
+    mw_store(w, st);
+}
+
+__global__ __launch_bounds__(MW_THREADS) void k_test_binomial1(MtState *st, double eps, double qn, long long count, long long *out) {
+    __shared__ uint32_t ring[4][MT_N];
+    MwState w;
+    mw_load(w, st, ring);
+    for (long long i = 0; i < count; ++i) {
+        const int x = mw_draw_binomial1(w, eps, qn);
+        if (threadIdx.x == 0) out[i] = x;
+    }
+    mw_store(w, st);
 }
 
 // ------------------------------------------------------------------------------ launchers
@@ -180,6 +200,59 @@ int hp_rng_uniform(hp_rng *rng, int64_t count, double *host_out) {
                        (long long)count, rng->scratch.as<double>());
     HP_CHECK_HIP(hipGetLastError());
     HP_CHECK_HIP(hipMemcpyAsync(host_out, rng->scratch.p, (size_t)count * 8, hipMemcpyDeviceToHost, rng->ctx->stream));
+    HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
+    return HP_OK;
+}
+
+int hp_rng_standard_normal(hp_rng *rng, int64_t count, double *host_out) {
+    HP_REQUIRE(rng && host_out, HP_ERR_INVALID, "hp_rng_standard_normal: null argument");
+    HP_SERIALISE(rng);
+    HP_REQUIRE(count >= 0, HP_ERR_INVALID, "hp_rng_standard_normal: negative count");
+    if (count == 0) return HP_OK;
+    HP_TRY(rng->scratch.ensure((size_t)count * 8));
+    hipLaunchKernelGGL(k_test_normal, dim3(1), dim3(MW_THREADS), 0, rng->ctx->stream, rng->d_state, (long long)count,
+                       rng->scratch.as<double>());
+    HP_CHECK_HIP(hipGetLastError());
+    HP_CHECK_HIP(hipMemcpyAsync(host_out, rng->scratch.p, (size_t)count * 8, hipMemcpyDeviceToHost, rng->ctx->stream));
+    HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
+    return HP_OK;
+}
+
+int hp_rng_binomial1(hp_rng *rng, double p, double qn, int64_t count, int64_t *host_out) {
+    HP_REQUIRE(rng && host_out, HP_ERR_INVALID, "hp_rng_binomial1: null argument");
+    HP_SERIALISE(rng);
+    HP_REQUIRE(p >= 0.0 && p <= 1.0, HP_ERR_INVALID, "p < 0, p > 1 or p is NaN");   // numpy's message
+    HP_REQUIRE(count >= 0, HP_ERR_INVALID, "hp_rng_binomial1: negative count");
+    if (count == 0) return HP_OK;
+    HP_TRY(rng->scratch.ensure((size_t)count * 8));
+    hipLaunchKernelGGL(k_test_binomial1, dim3(1), dim3(MW_THREADS), 0, rng->ctx->stream, rng->d_state, p, qn, (long long)count,
+                       rng->scratch.as<long long>());
+    HP_CHECK_HIP(hipGetLastError());
+    HP_CHECK_HIP(hipMemcpyAsync(host_out, rng->scratch.p, (size_t)count * 8, hipMemcpyDeviceToHost, rng->ctx->stream));
+    HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
+    return HP_OK;
+}
+
+// numpy's cached second normal (state tuple fields 3 and 4); hp_rng_seed and hp_rng_set_state clear it, as numpy's seed() does and
+// as a 3-tuple set_state does -- a caller that carries one sets it after the key
+int hp_rng_get_gauss(hp_rng *rng, int32_t *has_gauss, double *gauss) {
+    HP_REQUIRE(rng && has_gauss && gauss, HP_ERR_INVALID, "hp_rng_get_gauss: null argument");
+    HP_SERIALISE(rng);
+    struct { int32_t has; int32_t pad; double v; } h;
+    HP_CHECK_HIP(hipMemcpyAsync(&h.has, &rng->d_state->has_gauss, 4, hipMemcpyDeviceToHost, rng->ctx->stream));
+    HP_CHECK_HIP(hipMemcpyAsync(&h.v, &rng->d_state->gauss, 8, hipMemcpyDeviceToHost, rng->ctx->stream));
+    HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
+    *has_gauss = h.has;
+    *gauss = h.v;
+    return HP_OK;
+}
+
+int hp_rng_set_gauss(hp_rng *rng, int32_t has_gauss, double gauss) {
+    HP_REQUIRE(rng, HP_ERR_INVALID, "hp_rng_set_gauss: null handle");
+    HP_SERIALISE(rng);
+    const int32_t has = has_gauss ? 1 : 0;
+    HP_CHECK_HIP(hipMemcpyAsync(&rng->d_state->has_gauss, &has, 4, hipMemcpyHostToDevice, rng->ctx->stream));
+    HP_CHECK_HIP(hipMemcpyAsync(&rng->d_state->gauss, &gauss, 8, hipMemcpyHostToDevice, rng->ctx->stream));
     HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
     return HP_OK;
 }

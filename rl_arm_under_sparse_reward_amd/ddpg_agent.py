@@ -47,6 +47,9 @@ class ddpg_agent:
         # policy call per timestep (the host feeder of SURVEY 8f N1)
         self.envs = list(env) if isinstance(env, (list, tuple)) else [env]
         self.env = self.envs[0]
+        # a vectorised simulator in device memory (device_env.py): rollouts, evaluation and learn() take the device path
+        self.vec_env = env if getattr(env, "is_device_vec_env", False) else None
+        self._rollouts = {}              # DeviceEpisodes blocks by episode count
         self.env_params = env_params
         self.ctx = ctx or _lib.Context.default()
         self.lib = self.ctx.lib
@@ -392,11 +395,23 @@ class ddpg_agent:
         contains the RCCL all-reduces (gradients every update, normalizer sums once) when the library owns the
         communicator; otherwise the loop is driven from the host."""
         n_batches = int(n_batches or self.args.n_batches)
+        device_block = hasattr(episode_batch, "block") and hasattr(episode_batch, "numpy")    # device_env.DeviceEpisodes
         if self.comm.active and self._native_comm is None and self._peer is None:   # collectives on torch.distributed: host-driven loop
-            self.buffer.store_episode(episode_batch)
-            self._update_normalizer(episode_batch)
+            if device_block:
+                with self._stage_lock:       # store + normalizer update on the episodes the store just staged, as one unit
+                    self.buffer.store_episode(episode_batch)
+                    self._update_normalizer()
+            else:
+                self.buffer.store_episode(episode_batch)
+                self._update_normalizer(episode_batch)
             self._update_network(n_batches)
             self._soft_update_target_network()
+            return
+        if device_block:
+            # the same cycle out of the device block (hp_agent_train_cycle_dev): a device-to-device copy instead of the upload
+            _lib.check(self.lib.hp_agent_train_cycle_dev(
+                *self._handles(), C.c_void_p(episode_batch.block), len(episode_batch),
+                float(self.her_module.future_p), float(self.her_module.sq_threshold), n_batches))
             return
         # same shape validation as store_episode (a wrong T or dimension raises ValueError like numpy's broadcast at
         # replay_buffer.py:39-42 instead of letting the library read past the arrays)
@@ -554,6 +569,62 @@ class ddpg_agent:
                                          _lib.ptr(out, C.c_float)))
         return out.reshape(obs.shape[:-1] + (out.shape[-1],))
 
+    def act_device(self, obs_t, g_t, target=False, clip_obs=0.0):
+        """`act` for float64 device tensors [n, obs] / [n, goal] (or single rows): the same kernels on the tensors' memory, a
+        float32 device tensor back.  Runs in torch's current stream order; no copy, no synchronisation."""
+        if obs_t.dtype != torch.float64 or g_t.dtype != torch.float64 or not obs_t.is_cuda or not g_t.is_cuda:
+            raise ValueError("act_device: float64 tensors on the context's device expected")
+        o2 = obs_t.reshape(-1, obs_t.shape[-1]).contiguous()
+        g2 = g_t.reshape(-1, g_t.shape[-1]).contiguous()
+        if o2.shape[0] != g2.shape[0]:
+            raise ValueError("act: observation and goal stacks differ in length")
+        out = torch.empty((o2.shape[0], self.env_params['action']), dtype=torch.float32, device=o2.device)
+        self._flush_updates()
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_agent_act_dev(self.h, self.o_norm.h, self.g_norm.h, NET_ACTOR_TARGET if target else NET_ACTOR,
+                                                 C.c_void_p(o2.data_ptr()), C.c_void_p(g2.data_ptr()), o2.shape[0],
+                                                 float(clip_obs), C.c_void_p(out.data_ptr())))
+        return out.reshape(tuple(obs_t.shape[:-1]) + (out.shape[-1],))
+
+    def collect_episodes_device(self, vec_env=None, n_rollouts=None, epoch=0, explore=True, success_out=None):
+        """`collect_episodes` for a vectorised device environment (device_env.py): `n_rollouts` episodes (default: one wave of
+        vec_env.n_envs) in waves of n_envs, T timesteps of two launches each (csrc/rollout.hip) on torch's current stream, no
+        host copy and no host wait per timestep.  Exploration (:174-184, the +-0.15 clip from epoch 100) is drawn on the device
+        from `self.rng`, for env 0 .. n-1 in turn like the host lockstep path.  Returns a `DeviceEpisodes` handle for
+        `train_cycle` / `buffer.store_episode`; `.numpy()` gives the four arrays `collect_episodes` returns."""
+        from .device_env import DeviceEpisodes, binomial1_qn
+        vec_env = vec_env or self.vec_env
+        n_total = int(n_rollouts or vec_env.n_envs)
+        T, ad = int(self.env_params['max_timesteps']), int(self.env_params['action'])
+        eps = self._rollouts.get(n_total)
+        if eps is None:
+            eps = self._rollouts[n_total] = DeviceEpisodes(self.ctx, self.buffer._dev, n_total)
+        qn = binomial1_qn(self.args.random_eps)[0] if explore else 1.0
+        clip_abs = 0.15 if epoch >= 100 else 0.0                                  # ddpg_agent.py:118-119
+        self._flush_updates()
+        done = 0
+        p = lambda t: C.c_void_p(t.data_ptr())
+        while done < n_total:
+            k = min(vec_env.n_envs, n_total - done)
+            o = vec_env.reset() if k == vec_env.n_envs else vec_env.reset(k)
+            actions = torch.empty((k, ad), dtype=torch.float32, device=o['observation'].device)
+            with self.ctx.torch_bridge():       # the whole wave in torch's stream order, between the environment's own kernels
+                _lib.check(self.lib.hp_rollout_begin(eps.h, done, k))
+                for t in range(T):
+                    obs, ag, g = (o[key].contiguous() for key in ('observation', 'achieved_goal', 'desired_goal'))
+                    _lib.check(self.lib.hp_rollout_step(eps.h, self.h, self.o_norm.h, self.g_norm.h, self.rng.h, t, p(obs), p(ag),
+                                                        p(g), 1 if explore else 0, float(self.args.noise_eps),
+                                                        float(self.args.random_eps), qn, clip_abs, p(actions)))
+                    o, _, _, info = vec_env.step(actions)
+                obs, ag = o['observation'].contiguous(), o['achieved_goal'].contiguous()
+                _lib.check(self.lib.hp_rollout_finish(eps.h, p(obs), p(ag)))
+            if success_out is not None:
+                success_out.append(info['is_success'])
+            done += k
+        if explore:
+            self.rng.mark_normals_drawn()
+        return eps
+
     def _select_actions(self, pi):
         """ddpg_agent.py:174-184: Gaussian noise, clip, epsilon-random (numpy global RNG, like the reference).  `action`
         stays the float32 array the policy returned and is updated in place, so every step rounds to float32 exactly
@@ -616,6 +687,8 @@ class ddpg_agent:
             self.load_training_state(rank_path(resume, self.comm.rank))
             first_epoch = self.resumed_at[0]
         print("initial buffer size:", self.buffer.current_size)                  # :97
+        if self.vec_env is not None:
+            return self._learn_device(share, state_path, first_epoch)
         for epoch in range(first_epoch, self.args.n_epochs):
             start = time.time()
             for _ in range(self.args.n_cycles):
@@ -637,9 +710,53 @@ class ddpg_agent:
                 from .train_state import rank_path
                 self.save_training_state(rank_path(state_path, self.comm.rank), epoch=epoch + 1)
 
+    def _learn_device(self, share, state_path, first_epoch):
+        """learn() with a vectorised device environment: every draw of a cycle -- exploration, overflow slots, HER indices --
+        comes from the device stream, so the single stream stays on the device for the whole run: numpy's state is handed over
+        once here and handed back at the end and wherever a training state is saved (not twice per cycle), and nothing
+        synchronises between the rollout and the learner phase of a cycle."""
+        if share:
+            self.rng.set_state(np.random.get_state())
+        for epoch in range(first_epoch, self.args.n_epochs):
+            start = time.time()
+            for _ in range(self.args.n_cycles):
+                self.train_cycle(self.collect_episodes_device(n_rollouts=self.args.num_rollouts_per_mpi, epoch=epoch))
+            self.ctx.synchronize()
+            self.check_exchange()
+            print(str(time.time() - start))
+            rate = self._eval_agent()
+            self.success_rates.append(rate)
+            if self.comm.rank == 0:
+                print('[{}] epoch is: {}, eval success rate is: {:.3f}'.format(datetime.now(), epoch, rate))
+                self.save_checkpoint()
+            if state_path:
+                from .train_state import rank_path
+                if share:
+                    np.random.set_state(self.rng.get_state())
+                self.save_training_state(rank_path(state_path, self.comm.rank), epoch=epoch + 1)
+        if share:
+            np.random.set_state(self.rng.get_state())
+
+    def _eval_agent_device(self):
+        """_eval_agent on the device path: noise-free lockstep rollouts, the success flags of each wave's last step gathered on
+        the device and copied to the host once at the end."""
+        flags, remaining = [], int(self.args.n_test_rollouts)
+        while remaining > 0:
+            k = min(self.vec_env.n_envs, remaining)
+            self.collect_episodes_device(n_rollouts=k, explore=False, success_out=flags)
+            remaining -= k
+        wins = torch.cat([f.reshape(-1).to(torch.float64) for f in flags]).cpu().numpy()
+        local = torch.tensor([float(np.mean(wins))], dtype=torch.float64)
+        if self.comm.world_size > 1:
+            local = local.to(f"cuda:{self.ctx.device_id}")
+        self.comm.allreduce_mean_(local)
+        return float(local.item())
+
     def _eval_agent(self):
         """ddpg_agent.py:280-304: success at the last step of n_test_rollouts noise-free episodes, averaged over ranks;
         the environments in self.envs run in lockstep with one batched policy call per timestep."""
+        if self.vec_env is not None:
+            return self._eval_agent_device()
         wins = []
         remaining = int(self.args.n_test_rollouts)
         while remaining > 0:

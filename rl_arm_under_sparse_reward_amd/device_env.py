@@ -1,0 +1,161 @@
+"""Rollouts collected on the device, for simulators whose state already lives there.
+
+**Vectorised device GoalEnv protocol.**  `ddpg_agent` takes, in place of a gym-GoalEnv-like object, one object `env` with
+
+    env.is_device_vec_env == True
+    env.n_envs, env.env_params, env.distance_threshold, env.reward_type
+    env.reset()              -> {'observation': [n, obs], 'achieved_goal': [n, goal], 'desired_goal': [n, goal]}
+    env.step(actions_f32)    -> (obs_dict, reward, done, {'is_success': tensor[n]})
+
+where every array is a contiguous float64 torch tensor on the context's device and `actions_f32` is the float32 tensor
+[n, action] the library wrote.  The environment runs on torch's current stream; the library enqueues its own kernels of a rollout
+wave on that same stream (`Context.torch_bridge`, hp_ctx_borrow_stream) and orders its own stream behind it when the learner next
+runs -- events on the device, never a host wait.  The tensors an environment returns must stay valid until the next `step` /
+`reset` call (the library reads them in stream order and keeps no reference).
+
+With such an environment `ddpg_agent.collect_episodes_device` runs T timesteps of two launches each (csrc/rollout.hip) with no
+host copy in between, the exploration noise of ddpg_agent.py:174-184 drawn on the device from the reference's MT19937 stream, and
+returns a `DeviceEpisodes` handle that `train_cycle` / `buffer.store_episode` consume without the episodes ever visiting the host.
+
+Draw order with n environments: per timestep, for env i = 0 .. n-1: randn(action), uniform(action), binomial(1) -- the order of
+the host lockstep path (`collect_episodes` on a list of environments); with one environment it is the reference's own order.
+
+`PointMassVecEnv` is the tensor twin of `synthetic.PointMassGoalEnv`.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def wave_layout(n_envs, T, obs, goal, act):
+    """Offsets (float64 elements) of obs | ag | g | actions inside a wave block and its length: the staging layout of the host
+    feeder (feeder._Layout), which is what hp_rollout_create allocates."""
+    o_ag = n_envs * (T + 1) * obs
+    o_g = o_ag + n_envs * (T + 1) * goal
+    o_act = o_g + n_envs * T * goal
+    return {"obs": 0, "ag": o_ag, "g": o_g, "actions": o_act, "elems": o_act + n_envs * T * act}
+
+
+def binomial1_qn(p):
+    """(qn, reflected) of numpy's legacy binomial(1, p): the inversion runs on p' = p for p <= 0.5 and on p' = 1 - p otherwise
+    (the result is then 1 - X); qn = exp(1 * log(1 - p')) is computed here once, by the host's libm like numpy's own."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("p < 0, p > 1 or p is NaN")
+    reflected = not (p <= 0.5)
+    pe = 1.0 - p if reflected else p
+    return math.exp(math.log(1.0 - pe)), reflected
+
+
+class DeviceEpisodes:
+    """Episodes collected by `collect_episodes_device`: a device block [obs | ag | g | actions] of `n` episodes (hp_rollout).
+    `.numpy()` copies the four arrays `collect_episodes` returns to the host (synchronises).  The block belongs to the agent and
+    is rewritten by its next `collect_episodes_device` call for the same number of episodes."""
+
+    def __init__(self, ctx, buffer_dev, n):
+        self.ctx, self.lib, self.n = ctx, ctx.lib, int(n)
+        self.T, self.dims = buffer_dev.T, dict(buffer_dev.dims)
+        self.h = C.c_void_p()
+        _lib.check(self.lib.hp_rollout_create(ctx.h, buffer_dev.h, self.n, C.byref(self.h)))
+        p = C.c_void_p()
+        _lib.check(self.lib.hp_rollout_block(self.h, C.byref(p), None, None, None))
+        self.block = p.value
+
+    def __len__(self):
+        return self.n
+
+    def numpy(self):
+        n, T, d = self.n, self.T, self.dims
+        out = [np.empty((n, T + 1, d["obs"])), np.empty((n, T + 1, d["ag"])), np.empty((n, T, d["g"])),
+               np.empty((n, T, d["actions"]))]
+        for which, a in enumerate(out):
+            _lib.check(self.lib.hp_rollout_read(self.h, which, _lib.ptr(a, C.c_double)))
+        return out
+
+    def __del__(self):
+        try:
+            self.lib.hp_rollout_destroy(self.h)
+        except Exception:
+            pass
+
+
+class PointMassVecEnv:
+    """n `synthetic.PointMassGoalEnv`s as tensors: env i resets from RandomState(seed + i) on the host (one upload per episode),
+    `step` is elementwise float64 torch -- multiply and add as separate ops, so the bits are the host environment's.  Works with
+    device="cpu" too."""
+
+    is_device_vec_env = True
+
+    def __init__(self, n_envs, seed=0, device="cuda", max_timesteps=100, distance_threshold=0.05, reward_type='sparse',
+                 step_scale=0.1):
+        self.n_envs = int(n_envs)
+        self.device = torch.device(device)
+        self.rs = [np.random.RandomState(seed + i) for i in range(self.n_envs)]
+        self.max_timesteps = int(max_timesteps)
+        self.distance_threshold = float(distance_threshold)
+        self.reward_type = reward_type
+        self.step_scale = float(step_scale)
+        self.active = self.n_envs
+        z = torch.zeros((self.n_envs, 3), dtype=torch.float64, device=self.device)
+        self.pos, self.vel, self.goal = z, z.clone(), z.clone()
+
+    @property
+    def env_params(self):
+        return {'obs': 27, 'goal': 3, 'action': 4, 'action_max': 0.5, 'max_timesteps': self.max_timesteps}
+
+    def _observation(self):
+        n = self.pos.shape[0]
+        obs = torch.zeros((n, 27), dtype=torch.float64, device=self.device)
+        obs[:, 0:3] = self.pos
+        obs[:, 3:6] = self.vel
+        obs[:, 12:15] = self.pos
+        return {'observation': obs, 'achieved_goal': self.pos.clone(), 'desired_goal': self.goal.clone()}
+
+    def reset(self, n_active=None):
+        """Reset the first `n_active` environments (default: all) -- only those draw from their streams, like the host lockstep
+        path, which resets only the environments of the wave -- and step those from now on."""
+        k = self.n_envs if n_active is None else int(n_active)
+        if not 0 < k <= self.n_envs:
+            raise ValueError("n_active outside [1, n_envs]")
+        both = np.empty((2, k, 3))
+        for i in range(k):
+            both[0, i] = self.rs[i].uniform(0.0, 0.5, 3)
+            both[1, i] = self.rs[i].uniform(0.0, 0.5, 3)
+        dev = torch.from_numpy(both).to(self.device)
+        self.pos, self.goal = dev[0].contiguous(), dev[1].contiguous()
+        self.vel = torch.zeros_like(self.pos)
+        self.active = k
+        return self._observation()
+
+    def _distance(self, a, b):
+        d = a - b
+        # numpy's norm over three components: a left-to-right sum of squares, then the square root
+        return torch.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2])
+
+    def compute_reward(self, achieved_goal, goal, info):
+        """Tensors in, tensors out; numpy arrays (what her_sampler probes a reward function with) take the host environment's
+        own arithmetic."""
+        if not torch.is_tensor(achieved_goal):
+            d = np.linalg.norm(np.asarray(achieved_goal) - np.asarray(goal), axis=-1)
+            return -(d > self.distance_threshold).astype(np.float32) if self.reward_type == 'sparse' else -d
+        d = self._distance(achieved_goal, goal)
+        if self.reward_type == 'sparse':
+            return -(d > self.distance_threshold).to(torch.float32)
+        return -d
+
+    def step(self, actions):
+        a = torch.clamp(actions.to(torch.float64), -0.5, 0.5)
+        scaled = self.step_scale * a[:, :3]                 # multiply, then add: two roundings, like numpy
+        new = torch.clamp(self.pos + scaled, 0.0, 0.5)
+        self.vel = new - self.pos
+        self.pos = new
+        observation = self._observation()
+        success = (self._distance(observation['achieved_goal'], self.goal) < self.distance_threshold).to(torch.float32)
+        info = {'is_success': success}
+        return observation, self.compute_reward(observation['achieved_goal'], self.goal, info), False, info

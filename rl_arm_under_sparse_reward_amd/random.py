@@ -29,10 +29,11 @@ class DeviceRandomState:
         self.h = C.c_void_p()
         _lib.check(self.lib.hp_rng_create(self.ctx.h, C.byref(self.h)))
         self.seeded = False       # seed() / set_state() called (a fresh stream carries numpy's default key, seed 5489)
-        # numpy's legacy state also carries a cached Gaussian (has_gauss, cached_gaussian).  Nothing on the device draws
-        # normals, and randint / random_sample never touch that cache in numpy either, so it is carried through unchanged:
-        # np.random.set_state(dev.get_state()) after dev.set_state(np.random.get_state()) keeps a pending second normal
-        self._gauss = (0, 0.0)
+        # numpy's legacy state also carries a cached Gaussian (has_gauss, cached_gaussian).  It lives on the device next to
+        # (key, pos), where the normal draws of the exploration noise (csrc/mt19937_wave.h) read and write it; randint /
+        # random_sample never touch it, in numpy either.  `_gauss` is a view of it; the host copy below is reused until a
+        # device draw of normals may have changed it (`_gauss_stale`), so reading it costs no device round trip otherwise
+        self._gauss_host, self._gauss_stale = (0, 0.0), False
         if seed is not None:
             self.seed(seed)
 
@@ -42,13 +43,33 @@ class DeviceRandomState:
             raise ValueError("Seed must be between 0 and 2**32 - 1")     # numpy's message
         _lib.check(self.lib.hp_rng_seed(self.h, C.c_uint32(seed)))
         self.seeded = True
-        self._gauss = (0, 0.0)                                           # numpy's seed() drops the cached normal
+        self._gauss_host, self._gauss_stale = (0, 0.0), False            # numpy's seed() drops the cached normal (hp_rng_seed too)
+
+    @property
+    def _gauss(self):
+        """(has_gauss, cached_gaussian) of the device stream (hp_rng_get_gauss; synchronises only after a device draw of normals)."""
+        if self._gauss_stale:
+            has, val = C.c_int32(), C.c_double()
+            _lib.check(self.lib.hp_rng_get_gauss(self.h, C.byref(has), C.byref(val)))
+            self._gauss_host, self._gauss_stale = (int(has.value), float(val.value)), False
+        return self._gauss_host
+
+    @_gauss.setter
+    def _gauss(self, gauss):
+        gauss = (int(gauss[0]), float(gauss[1]))
+        _lib.check(self.lib.hp_rng_set_gauss(self.h, C.c_int32(gauss[0]), C.c_double(gauss[1])))
+        self._gauss_host, self._gauss_stale = (1 if gauss[0] else 0, gauss[1]), False
+
+    def mark_normals_drawn(self):
+        """A device kernel drew normals from this stream (rollout steps with exploration): the cached Gaussian must be read back."""
+        self._gauss_stale = True
 
     def get_state(self):
         key = np.empty(624, np.uint32)
         pos = C.c_int32()
         _lib.check(self.lib.hp_rng_get_state(self.h, _lib.ptr(key, C.c_uint32), C.byref(pos)))
-        return ("MT19937", key, int(pos.value), int(self._gauss[0]), float(self._gauss[1]))
+        gauss = self._gauss
+        return ("MT19937", key, int(pos.value), int(gauss[0]), float(gauss[1]))
 
     def set_state(self, state):
         if isinstance(state, dict):
@@ -99,6 +120,20 @@ class DeviceRandomState:
     def uniform(self, size=1):
         out = np.empty(int(size), np.float64)
         _lib.check(self.lib.hp_rng_uniform(self.h, int(size), _lib.ptr(out, C.c_double)))
+        return out
+
+    def standard_normal(self, size=1):
+        """np.random.randn(size) on the device (legacy polar method, cached second normal included)."""
+        out = np.empty(int(size), np.float64)
+        _lib.check(self.lib.hp_rng_standard_normal(self.h, int(size), _lib.ptr(out, C.c_double)))
+        self._gauss_stale = True
+        return out
+
+    def binomial1(self, p, size=1):
+        """np.random.binomial(1, p, size) on the device (legacy inversion)."""
+        from .device_env import binomial1_qn
+        out = np.empty(int(size), np.int64)
+        _lib.check(self.lib.hp_rng_binomial1(self.h, float(p), binomial1_qn(p)[0], int(size), _lib.ptr(out, C.c_int64)))
         return out
 
     def __del__(self):

@@ -207,7 +207,12 @@ class replay_buffer:
         return self._dev.info()[2]
 
     def store_episode(self, episode_batch):
-        """replay_buffer.py:32-43 (+ _get_storage_idx :57-71 on the device)."""
+        """replay_buffer.py:32-43 (+ _get_storage_idx :57-71 on the device).  A `device_env.DeviceEpisodes` handle is stored out
+        of its device block (hp_buffer_store_dev): no host copy."""
+        if hasattr(episode_batch, "block") and hasattr(episode_batch, "numpy"):
+            _lib.check(self._dev.lib.hp_buffer_store_dev(self._dev.h, self.rng.h, C.c_void_p(episode_batch.block),
+                                                         len(episode_batch)))
+            return
         self._dev.store(self.rng, episode_batch)
 
     def sample(self, batch_size):
