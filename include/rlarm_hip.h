@@ -63,6 +63,7 @@ typedef struct hp_agent hp_agent;
 typedef struct hp_comm hp_comm;
 typedef struct hp_peer hp_peer;
 typedef struct hp_rollout hp_rollout;
+typedef struct hp_rng_streams hp_rng_streams;
 
 int hp_abi_version(void);
 const char *hp_last_error(void);
@@ -352,6 +353,31 @@ int hp_rollout_finish(hp_rollout *ro, const double *obs_dev, const double *ag_de
 int hp_rollout_block(hp_rollout *ro, void **block_dev, int64_t *n_episodes, int64_t *offsets4, int64_t *elems);
 int hp_rollout_read(hp_rollout *ro, int32_t which, double *host_out);
 void hp_rollout_destroy(hp_rollout *ro);
+
+/* ---- one exploration stream per environment ---------------------------------------------------------------------------------
+ * The reference gives every MPI rank one environment and one numpy stream seeded `seed + rank` (train.py:34-39) and lets the rank
+ * drive _select_actions (ddpg_agent.py:174-184) alone.  An hp_rng_streams is n such streams side by side in device memory: stream i
+ * is a whole legacy state (key[624], pos, has_gauss, cached normal) interoperable with np.random.RandomState(seed_i).get_state().
+ * hp_streams_create seeds every stream with numpy's default key (5489); hp_streams_seed seeds stream i with seeds_host[i]
+ * (n_seeds must be the stream count) or, seeds_host == NULL, with base_seed + i -- n init_genrand recurrences run on the device,
+ * one per stream -- and clears the cached normals.  get / set of one state and of all states (keys [n][624], pos / has_gauss /
+ * gauss [n]) synchronise.
+ * hp_rollout_step_streams is hp_rollout_step with the stream array in place of the single stream: row i of the wave draws
+ * randn(act), uniform(act), binomial(1, random_eps) out of stream i alone, so what an environment draws depends neither on the
+ * number of environments nor on the wave it is part of, and a wave of k rows (hp_rollout_begin) advances streams 0 .. k-1 only.
+ * Rounding points, qn, clip_abs and the teacher-forced form (ag == NULL) are hp_rollout_step's; the draw launch has one wave per
+ * row instead of one wave for all rows.  explore == 0 touches no stream (streams may be NULL).  A wave wider than the array is
+ * refused. */
+int hp_streams_create(hp_ctx *ctx, int64_t n, hp_rng_streams **out);
+int hp_streams_seed(hp_rng_streams *s, const uint32_t *seeds_host, int64_t n_seeds, uint32_t base_seed);
+int hp_streams_get_state(hp_rng_streams *s, int64_t i, uint32_t *key624, int32_t *pos, int32_t *has_gauss, double *gauss);
+int hp_streams_set_state(hp_rng_streams *s, int64_t i, const uint32_t *key624, int32_t pos, int32_t has_gauss, double gauss);
+int hp_streams_get_all(hp_rng_streams *s, uint32_t *keys, int32_t *pos, int32_t *has_gauss, double *gauss);
+int hp_streams_set_all(hp_rng_streams *s, const uint32_t *keys, const int32_t *pos, const int32_t *has_gauss, const double *gauss);
+void hp_streams_destroy(hp_rng_streams *s);
+int hp_rollout_step_streams(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, hp_rng_streams *streams, int32_t t,
+                            const double *obs_dev, const double *ag_dev, const double *g_dev, int32_t explore, double noise_eps,
+                            double random_eps, double qn, double clip_abs, float *actions_f32_dev);
 
 /* Policy calls that do not queue behind training: hp_agent_policy_snapshot copies the online actor and both normalizers'
  * statistics (stream-ordered with the updates, no host wait); hp_agent_act_snapshot evaluates the most recent COMPLETE

@@ -166,6 +166,16 @@ PROTOTYPES = {
     "hp_rollout_block": (C.c_int, [C.c_void_p, c_void_pp, i64p, i64p, i64p]),
     "hp_rollout_read": (C.c_int, [C.c_void_p, C.c_int32, f64p]),
     "hp_rollout_destroy": (None, [C.c_void_p]),
+    "hp_streams_create": (C.c_int, [C.c_void_p, C.c_int64, c_void_pp]),
+    "hp_streams_seed": (C.c_int, [C.c_void_p, u32p, C.c_int64, C.c_uint32]),
+    "hp_streams_get_state": (C.c_int, [C.c_void_p, C.c_int64, u32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), f64p]),
+    "hp_streams_set_state": (C.c_int, [C.c_void_p, C.c_int64, u32p, C.c_int32, C.c_int32, C.c_double]),
+    "hp_streams_get_all": (C.c_int, [C.c_void_p, u32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), f64p]),
+    "hp_streams_set_all": (C.c_int, [C.c_void_p, u32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), f64p]),
+    "hp_streams_destroy": (None, [C.c_void_p]),
+    "hp_rollout_step_streams": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                          C.c_void_p]),
     "hp_agent_policy_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hp_agent_act_snapshot": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int64, C.c_double, f32p]),
     "hp_agent_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,

@@ -196,6 +196,14 @@ struct hp_rng {
 };
 void rng_parallel_release(hp_rng *rng);
 
+// one exploration stream per environment of a vectorised simulator (rng_streams.hip, k_rollout_step_streams in rollout.hip):
+// n whole legacy states side by side, stream i belonging to row i of a rollout wave
+struct hp_rng_streams {
+    hp_ctx *ctx = nullptr;
+    int64_t n = 0;
+    MtState *d_state = nullptr;   // [n]
+};
+
 // one drawn transition index record (her.py:24-33)
 struct __attribute__((aligned(16))) PlanRec {
     int32_t e;    // episode index

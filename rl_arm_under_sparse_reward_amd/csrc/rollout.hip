@@ -58,6 +58,33 @@ __device__ __forceinline__ void ro_record(const RolloutStepArgs &A, long long e0
     }
 }
 
+// ddpg_agent._select_actions (:174-184) for row i of the wave, out of the stream loaded into w: randn(act), uniform(act),
+// binomial(1).  Shared by the single-stream walk and the per-environment form, so one stream gives the same bits in both.
+__device__ __forceinline__ void ro_explore_row(const RolloutStepArgs &A, MwState &w, double *zs, int i) {
+    const int lane = threadIdx.x, ad = A.ad;
+    const float amax = (float)A.amax, clipf = (float)A.clip_abs;
+    // :177 action += noise_eps * max_action * randn(act): float32 array += float64 array, rounded once
+    mw_draw_normal(w, ad, [&](long long k, double z) { zs[k] = z; });
+    __syncthreads();
+    float a = 0.f;
+    if (lane < ad) {
+        a = A.pi[(long long)i * ad + lane];
+        a = (float)__dadd_rn((double)a, __dmul_rn(A.noise_scale, zs[lane]));
+        a = fminf(fmaxf(a, -amax), amax);                                          // :178 np.clip in float32
+    }
+    __syncthreads();   // zs is rewritten by the next environment's normals
+    double ra = 0.0;
+    mw_draw_uniform(w, -A.amax, __dsub_rn(A.amax, -A.amax), ad, [&](int, double u) { ra = u; });   // :179-180
+    const int b = mw_draw_binomial1(w, A.random_eps, A.qn);                        // :182
+    if (lane < ad) {
+        // :182 action += binomial * (random_actions - action), float64 arithmetic rounded to float32 once
+        a = (float)__dadd_rn((double)a, __dmul_rn((double)b, __dsub_rn(ra, (double)a)));
+        if (A.clip_abs > 0) a = fminf(fmaxf(a, -clipf), clipf);                    // :118-119, float32
+        A.pi[(long long)i * ad + lane] = a;
+        A.b_act[((long long)i * A.T + A.t) * ad + lane] = (double)a;
+    }
+}
+
 __global__ __launch_bounds__(MW_THREADS) void k_rollout_step(const RolloutStepArgs A) {
     __shared__ uint32_t ring[4][MT_N];
     __shared__ double zs[RO_MAX_ACT];
@@ -68,7 +95,6 @@ __global__ __launch_bounds__(MW_THREADS) void k_rollout_step(const RolloutStepAr
     }
     if (!A.pi) return;   // closing record only
     const int ad = A.ad;
-    const float amax = (float)A.amax, clipf = (float)A.clip_abs;
     if (!A.explore) {
         // ddpg_agent.collect_episodes with explore=False: action = pi.astype(float64), clipped in float64 from epoch 100 on
         for (long long e = lane; e < (long long)A.rows * ad; e += MW_THREADS) {
@@ -82,32 +108,42 @@ __global__ __launch_bounds__(MW_THREADS) void k_rollout_step(const RolloutStepAr
     }
     MwState w;
     mw_load(w, A.st, ring);
-    for (int i = 0; i < A.rows; ++i) {
-        // :177 action += noise_eps * max_action * randn(act): float32 array += float64 array, rounded once
-        mw_draw_normal(w, ad, [&](long long k, double z) { zs[k] = z; });
-        __syncthreads();
-        float a = 0.f;
-        if (lane < ad) {
-            a = A.pi[(long long)i * ad + lane];
-            a = (float)__dadd_rn((double)a, __dmul_rn(A.noise_scale, zs[lane]));
-            a = fminf(fmaxf(a, -amax), amax);                                          // :178 np.clip in float32
-        }
-        __syncthreads();   // zs is rewritten by the next environment's normals
-        double ra = 0.0;
-        mw_draw_uniform(w, -A.amax, __dsub_rn(A.amax, -A.amax), ad, [&](int, double u) { ra = u; });   // :179-180
-        const int b = mw_draw_binomial1(w, A.random_eps, A.qn);                        // :182
-        if (lane < ad) {
-            // :182 action += binomial * (random_actions - action), float64 arithmetic rounded to float32 once
-            a = (float)__dadd_rn((double)a, __dmul_rn((double)b, __dsub_rn(ra, (double)a)));
-            if (A.clip_abs > 0) a = fminf(fmaxf(a, -clipf), clipf);                    // :118-119, float32
-            A.pi[(long long)i * ad + lane] = a;
-            A.b_act[((long long)i * A.T + A.t) * ad + lane] = (double)a;
-        }
-    }
+    for (int i = 0; i < A.rows; ++i) ro_explore_row(A, w, zs, i);
     mw_store(w, A.st);
 }
 
-static int rollout_launch(hp_rollout *ro, RolloutStepArgs &A, int t) {
+// The same step with one stream per environment (hp_rollout_step_streams): workgroup i < rows is the one wave that draws row i's
+// exploration out of stream i -- the draws of ro_explore_row, the code of the single-stream walk, on an LDS ring of its own --
+// and the workgroups behind them record the rows.  No wave loops over environments: the grid grows with the active rows, and
+// a partial wave leaves the streams behind it alone.  State traffic per environment and step: the key is read (2.5 KB); what is
+// written back is pos and the cached normal (16 bytes) unless the walk ended in a block generated here, which for 4 action
+// components (about 20 words a step) is one step in thirty -- only then is the key rewritten.
+__global__ __launch_bounds__(MW_THREADS) void k_rollout_step_streams(const RolloutStepArgs A) {
+    __shared__ uint32_t ring[4][MT_N];
+    __shared__ double zs[RO_MAX_ACT];
+    const int lane = threadIdx.x;
+    if ((int)blockIdx.x >= A.rows) {
+        ro_record(A, (long long)((int)blockIdx.x - A.rows) * MW_THREADS + lane, (long long)A.record_blocks * MW_THREADS);
+        return;
+    }
+    const int i = blockIdx.x;
+    MtState *st = A.st + i;
+    MwState w;
+    mw_load(w, st, ring);
+    ro_explore_row(A, w, zs, i);
+    int b, pos;
+    mt_final_block(w.g.cursor, b, pos);
+    __syncthreads();
+    if (b > 0)
+        for (int k = lane; k < MT_N; k += MW_THREADS) st->key[k] = ring[b & 3][k];
+    if (lane == 0) {
+        st->pos = pos;
+        st->has_gauss = w.has_gauss;
+        st->gauss = w.gauss;
+    }
+}
+
+static int rollout_launch(hp_rollout *ro, RolloutStepArgs &A, int t, bool per_env_streams = false) {
     A.b_obs = ro->block + ro->first * (ro->T + 1) * ro->od;
     A.b_ag = ro->block + ro->o_ag + ro->first * (ro->T + 1) * ro->gd;
     A.b_g = ro->block + ro->o_g + ro->first * ro->T * ro->gd;
@@ -116,9 +152,38 @@ static int rollout_launch(hp_rollout *ro, RolloutStepArgs &A, int t) {
     const long long elems = ro->rows * (ro->od + 2 * ro->gd);
     long long nb = (elems + 4 * MW_THREADS - 1) / (4 * MW_THREADS);   // four elements per thread
     A.record_blocks = (int)(nb < 1 ? 1 : (nb > 2048 ? 2048 : nb));
-    hipLaunchKernelGGL(k_rollout_step, dim3(1 + A.record_blocks), dim3(MW_THREADS), 0, ro->ctx->stream, A);
+    if (per_env_streams)
+        hipLaunchKernelGGL(k_rollout_step_streams, dim3(A.rows + A.record_blocks), dim3(MW_THREADS), 0, ro->ctx->stream, A);
+    else
+        hipLaunchKernelGGL(k_rollout_step, dim3(1 + A.record_blocks), dim3(MW_THREADS), 0, ro->ctx->stream, A);
     HP_CHECK_HIP(hipGetLastError());
     return HP_OK;
+}
+
+// the part of a step both stream forms share: the policy launch, then the draw + record launch.  `st` is the single stream's state
+// or -- per_env_streams -- the first of one state per row
+static int rollout_step(const char *entry, hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, MtState *st, bool per_env_streams, int32_t t,
+                        const double *obs_dev, const double *ag_dev, const double *g_dev, int32_t explore, double noise_eps,
+                        double random_eps, double qn, double clip_abs, float *actions_f32_dev) {
+    double amax = ro->action_max;
+    if (a) {   // a == NULL: actions_f32_dev already holds the policy outputs (teacher-forced tests)
+        HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx, HP_ERR_INVALID,
+                   "%s: handles belong to different contexts", entry);
+        HP_REQUIRE(a->cfg.act_dim == ro->ad && on->size == ro->od && gn->size == ro->gd, HP_ERR_INVALID,
+                   "%s: agent / normalizer dimensions differ from the block's", entry);
+        HP_TRY(agent_act_dev(a, on, gn, HP_NET_ACTOR, obs_dev, g_dev, ro->rows, 0.0, actions_f32_dev));
+        amax = a->cfg.max_action;
+    }
+    RolloutStepArgs A;
+    memset(&A, 0, sizeof(A));
+    A.obs = obs_dev; A.ag = ag_dev; A.g = g_dev;
+    A.pi = actions_f32_dev;
+    A.st = st;
+    A.explore = explore ? 1 : 0;
+    A.amax = amax;
+    A.noise_scale = noise_eps * amax;
+    A.random_eps = random_eps; A.qn = qn; A.clip_abs = clip_abs;
+    return rollout_launch(ro, A, t, per_env_streams && explore);   // explore == 0 touches no stream: the single-stream kernel's path
 }
 
 extern "C" {
@@ -178,25 +243,26 @@ int hp_rollout_step(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, hp_rn
     HP_REQUIRE(t >= 0 && t < ro->T, HP_ERR_INVALID, "hp_rollout_step: t=%d outside [0, %d)", t, ro->T);
     HP_REQUIRE(!rng || rng->ctx == ro->ctx, HP_ERR_INVALID, "hp_rollout_step: random stream belongs to another context");
     HP_REQUIRE(!explore || (random_eps >= 0.0 && random_eps <= 1.0), HP_ERR_INVALID, "p < 0, p > 1 or p is NaN");
-    double amax = ro->action_max;
-    if (a) {   // a == NULL: actions_f32_dev already holds the policy outputs (teacher-forced tests)
-        HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx, HP_ERR_INVALID,
-                   "hp_rollout_step: handles belong to different contexts");
-        HP_REQUIRE(a->cfg.act_dim == ro->ad && on->size == ro->od && gn->size == ro->gd, HP_ERR_INVALID,
-                   "hp_rollout_step: agent / normalizer dimensions differ from the block's");
-        HP_TRY(agent_act_dev(a, on, gn, HP_NET_ACTOR, obs_dev, g_dev, ro->rows, 0.0, actions_f32_dev));
-        amax = a->cfg.max_action;
-    }
-    RolloutStepArgs A;
-    memset(&A, 0, sizeof(A));
-    A.obs = obs_dev; A.ag = ag_dev; A.g = g_dev;
-    A.pi = actions_f32_dev;
-    A.st = rng ? rng->d_state : nullptr;
-    A.explore = explore ? 1 : 0;
-    A.amax = amax;
-    A.noise_scale = noise_eps * amax;
-    A.random_eps = random_eps; A.qn = qn; A.clip_abs = clip_abs;
-    return rollout_launch(ro, A, t);
+    return rollout_step("hp_rollout_step", ro, a, on, gn, rng ? rng->d_state : nullptr, false, t, obs_dev, ag_dev, g_dev, explore, noise_eps, random_eps, qn,
+                        clip_abs, actions_f32_dev);
+}
+
+int hp_rollout_step_streams(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, hp_rng_streams *streams, int32_t t,
+                            const double *obs_dev, const double *ag_dev, const double *g_dev, int32_t explore, double noise_eps,
+                            double random_eps, double qn, double clip_abs, float *actions_f32_dev) {
+    HP_REQUIRE(ro && obs_dev && ag_dev && g_dev && actions_f32_dev, HP_ERR_INVALID, "hp_rollout_step_streams: null argument");
+    HP_REQUIRE(!explore || streams, HP_ERR_INVALID, "hp_rollout_step_streams: exploration needs the stream array");
+    HP_REQUIRE(!a || (on && gn), HP_ERR_INVALID, "hp_rollout_step_streams: the policy needs both normalizers");
+    HP_SERIALISE(ro);
+    HP_REQUIRE(t >= 0 && t < ro->T, HP_ERR_INVALID, "hp_rollout_step_streams: t=%d outside [0, %d)", t, ro->T);
+    HP_REQUIRE(!streams || streams->ctx == ro->ctx, HP_ERR_INVALID, "hp_rollout_step_streams: stream array belongs to another context");
+    HP_REQUIRE(!explore || ro->rows <= streams->n, HP_ERR_INVALID,
+               "hp_rollout_step_streams: a wave of %lld environments is wider than the array of %lld streams", (long long)ro->rows,
+               (long long)streams->n);
+    HP_REQUIRE(ro->ad <= RO_MAX_ACT, HP_ERR_INVALID, "hp_rollout_step_streams: at most %d action components", RO_MAX_ACT);
+    HP_REQUIRE(!explore || (random_eps >= 0.0 && random_eps <= 1.0), HP_ERR_INVALID, "p < 0, p > 1 or p is NaN");
+    return rollout_step("hp_rollout_step_streams", ro, a, on, gn, streams ? streams->d_state : nullptr, true, t, obs_dev, ag_dev, g_dev, explore, noise_eps,
+                        random_eps, qn, clip_abs, actions_f32_dev);
 }
 
 int hp_rollout_set_action_max(hp_rollout *ro, double action_max) {

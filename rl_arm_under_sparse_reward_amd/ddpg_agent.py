@@ -50,6 +50,7 @@ class ddpg_agent:
         # a vectorised simulator in device memory (device_env.py): rollouts, evaluation and learn() take the device path
         self.vec_env = env if getattr(env, "is_device_vec_env", False) else None
         self._rollouts = {}              # DeviceEpisodes blocks by episode count
+        self.explore_streams = None      # random.DeviceRandomStreams: one exploration stream per environment (enable_explore_streams)
         self.env_params = env_params
         self.ctx = ctx or _lib.Context.default()
         self.lib = self.ctx.lib
@@ -586,11 +587,27 @@ class ddpg_agent:
                                                  float(clip_obs), C.c_void_p(out.data_ptr())))
         return out.reshape(tuple(obs_t.shape[:-1]) + (out.shape[-1],))
 
+    def enable_explore_streams(self, base_seed=None, seeds=None):
+        """Give every environment of the vectorised simulator its own exploration stream (random.DeviceRandomStreams,
+        hp_rollout_step_streams): env i draws `_select_actions` out of `RandomState(seeds[i])` alone -- n reference workers
+        (one environment and one stream seeded `seed + rank` each, train.py:34-39) side by side -- so its trajectory depends
+        neither on n_envs nor on the wave it is part of, and the draw of a timestep is one wave per environment instead of one
+        wave for all.  Default seeds: base_seed + i with base_seed = args.seed + rank * n_envs, distinct over all environments
+        of all ranks.  `self.rng` then serves the learner alone (overflow slots, HER indices)."""
+        if self.vec_env is None:
+            raise ValueError("enable_explore_streams: the agent has no vectorised device environment")
+        n = int(self.vec_env.n_envs)
+        if seeds is None and base_seed is None:
+            base_seed = int(self.args.seed) + self.comm.rank * n
+        self.explore_streams = _random.DeviceRandomStreams(n, seeds=seeds, base_seed=base_seed, ctx=self.ctx)
+        return self.explore_streams
+
     def collect_episodes_device(self, vec_env=None, n_rollouts=None, epoch=0, explore=True, success_out=None):
         """`collect_episodes` for a vectorised device environment (device_env.py): `n_rollouts` episodes (default: one wave of
         vec_env.n_envs) in waves of n_envs, T timesteps of two launches each (csrc/rollout.hip) on torch's current stream, no
         host copy and no host wait per timestep.  Exploration (:174-184, the +-0.15 clip from epoch 100) is drawn on the device
-        from `self.rng`, for env 0 .. n-1 in turn like the host lockstep path.  Returns a `DeviceEpisodes` handle for
+        from `self.rng`, for env 0 .. n-1 in turn like the host lockstep path -- or, after `enable_explore_streams`, for every
+        environment from its own stream (a wave of k < n_envs rows advances the streams of those k only).  Returns a `DeviceEpisodes` handle for
         `train_cycle` / `buffer.store_episode`; `.numpy()` gives the four arrays `collect_episodes` returns."""
         from .device_env import DeviceEpisodes, binomial1_qn
         vec_env = vec_env or self.vec_env
@@ -604,6 +621,11 @@ class ddpg_agent:
         self._flush_updates()
         done = 0
         p = lambda t: C.c_void_p(t.data_ptr())
+        streams = self.explore_streams
+        if streams is not None and len(streams) != vec_env.n_envs:
+            raise ValueError(f"collect_episodes_device: {len(streams)} exploration streams for {vec_env.n_envs} environments")
+        step, stream_h = ((self.lib.hp_rollout_step_streams, streams.h) if streams is not None
+                          else (self.lib.hp_rollout_step, self.rng.h))
         while done < n_total:
             k = min(vec_env.n_envs, n_total - done)
             o = vec_env.reset() if k == vec_env.n_envs else vec_env.reset(k)
@@ -612,16 +634,16 @@ class ddpg_agent:
                 _lib.check(self.lib.hp_rollout_begin(eps.h, done, k))
                 for t in range(T):
                     obs, ag, g = (o[key].contiguous() for key in ('observation', 'achieved_goal', 'desired_goal'))
-                    _lib.check(self.lib.hp_rollout_step(eps.h, self.h, self.o_norm.h, self.g_norm.h, self.rng.h, t, p(obs), p(ag),
-                                                        p(g), 1 if explore else 0, float(self.args.noise_eps),
-                                                        float(self.args.random_eps), qn, clip_abs, p(actions)))
+                    _lib.check(step(eps.h, self.h, self.o_norm.h, self.g_norm.h, stream_h, t, p(obs), p(ag), p(g),
+                                    1 if explore else 0, float(self.args.noise_eps), float(self.args.random_eps), qn, clip_abs,
+                                    p(actions)))
                     o, _, _, info = vec_env.step(actions)
                 obs, ag = o['observation'].contiguous(), o['achieved_goal'].contiguous()
                 _lib.check(self.lib.hp_rollout_finish(eps.h, p(obs), p(ag)))
             if success_out is not None:
                 success_out.append(info['is_success'])
             done += k
-        if explore:
+        if explore and streams is None:     # (the streams keep no host copy of their cached normals: nothing to invalidate)
             self.rng.mark_normals_drawn()
         return eps
 
@@ -682,6 +704,8 @@ class ddpg_agent:
         # optional: args.resume = a training state to continue from (ddpg_agent.py:54-62), args.state_path = where to save one
         # after every epoch's evaluation; each rank has its own file (its buffer is its shard of the episodes)
         state_path, resume, first_epoch = getattr(self.args, "state_path", None), getattr(self.args, "resume", None), 0
+        if self.vec_env is not None and getattr(self.args, "explore_streams", False) and self.explore_streams is None:
+            self.enable_explore_streams()    # args.explore_streams: before a resume, whose state carries the streams' states
         if resume:
             from .train_state import rank_path
             self.load_training_state(rank_path(resume, self.comm.rank))

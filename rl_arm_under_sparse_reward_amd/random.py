@@ -143,6 +143,94 @@ class DeviceRandomState:
             pass
 
 
+class DeviceRandomStreams:
+    """n device random streams, one per environment of a vectorised simulator (csrc/rng_streams.hip): stream i is
+    `np.random.RandomState(seeds[i])`, by default `RandomState(base_seed + i)` -- the reference's `seed + rank` (train.py:34-39)
+    with an environment where the reference has a rank.  States are numpy's `get_state()` 5-tuples, cached normal included.
+    `ddpg_agent.enable_explore_streams` hands one of these to the rollout steps (hp_rollout_step_streams)."""
+
+    def __init__(self, n, seeds=None, base_seed=None, ctx=None):
+        self.ctx = ctx or _lib.Context.default()
+        self.lib = self.ctx.lib
+        self.n = int(n)
+        self.h = C.c_void_p()
+        _lib.check(self.lib.hp_streams_create(self.ctx.h, C.c_int64(self.n), C.byref(self.h)))
+        if seeds is not None or base_seed is not None:
+            self.seed(seeds=seeds, base_seed=base_seed)
+
+    def __len__(self):
+        return self.n
+
+    def seed(self, seeds=None, base_seed=None):
+        """Stream i := RandomState(seeds[i]), or RandomState(base_seed + i); cached normals are dropped, as numpy's seed() does."""
+        if (seeds is None) == (base_seed is None):
+            raise ValueError("seed: give either a list of seeds or a base seed")
+        if seeds is None:
+            base = int(base_seed)
+            if not (0 <= base and base + self.n - 1 <= 2**32 - 1):
+                raise ValueError("Seed must be between 0 and 2**32 - 1")     # numpy's message
+            _lib.check(self.lib.hp_streams_seed(self.h, None, C.c_int64(self.n), C.c_uint32(base)))
+            return
+        wide = np.asarray(seeds, dtype=np.int64).reshape(-1)
+        if wide.size and (wide.min() < 0 or wide.max() > 2**32 - 1):
+            raise ValueError("Seed must be between 0 and 2**32 - 1")
+        arr = np.ascontiguousarray(wide, dtype=np.uint32)
+        # (a list of the wrong length is the library's error to name)
+        _lib.check(self.lib.hp_streams_seed(self.h, _lib.ptr(arr, C.c_uint32), C.c_int64(arr.size), C.c_uint32(0)))
+
+    def get_state(self, i):
+        key = np.empty(624, np.uint32)
+        pos, has, val = C.c_int32(), C.c_int32(), C.c_double()
+        _lib.check(self.lib.hp_streams_get_state(self.h, C.c_int64(int(i)), _lib.ptr(key, C.c_uint32), C.byref(pos), C.byref(has),
+                                                 C.byref(val)))
+        return ("MT19937", key, int(pos.value), int(has.value), float(val.value))
+
+    def set_state(self, i, state):
+        if state[0] != "MT19937":
+            raise ValueError("set_state can only be used with legacy MT19937 state instances.")
+        key = np.ascontiguousarray(state[1], dtype=np.uint32)
+        if key.shape != (624,):
+            raise ValueError("state must be 624 longs")
+        has, val = (int(state[3]), float(state[4])) if len(state) >= 5 else (0, 0.0)
+        _lib.check(self.lib.hp_streams_set_state(self.h, C.c_int64(int(i)), _lib.ptr(key, C.c_uint32), C.c_int32(int(state[2])),
+                                                 C.c_int32(has), C.c_double(val)))
+
+    def get_arrays(self):
+        """All states as four arrays: keys uint32 [n, 624], pos int32 [n], has_gauss int32 [n], gauss float64 [n] (what a
+        training state stores)."""
+        keys, pos = np.empty((self.n, 624), np.uint32), np.empty(self.n, np.int32)
+        has, val = np.empty(self.n, np.int32), np.empty(self.n, np.float64)
+        _lib.check(self.lib.hp_streams_get_all(self.h, _lib.ptr(keys, C.c_uint32), _lib.ptr(pos, C.c_int32), _lib.ptr(has, C.c_int32),
+                                               _lib.ptr(val, C.c_double)))
+        return keys, pos, has, val
+
+    def set_arrays(self, keys, pos, has_gauss, gauss):
+        keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        pos, has = np.ascontiguousarray(pos, dtype=np.int32).reshape(-1), np.ascontiguousarray(has_gauss, dtype=np.int32).reshape(-1)
+        val = np.ascontiguousarray(gauss, dtype=np.float64).reshape(-1)
+        if keys.shape != (self.n, 624) or not (pos.size == has.size == val.size == self.n):
+            raise ValueError(f"set_arrays: {self.n} streams need keys [{self.n}, 624] and {self.n} positions / cached normals")
+        _lib.check(self.lib.hp_streams_set_all(self.h, _lib.ptr(keys, C.c_uint32), _lib.ptr(pos, C.c_int32), _lib.ptr(has, C.c_int32),
+                                               _lib.ptr(val, C.c_double)))
+
+    def get_states(self):
+        keys, pos, has, val = self.get_arrays()
+        return [("MT19937", keys[i].copy(), int(pos[i]), int(has[i]), float(val[i])) for i in range(self.n)]
+
+    def set_states(self, states):
+        states = list(states)
+        if len(states) != self.n:
+            raise ValueError(f"set_states: {len(states)} states for {self.n} streams")
+        self.set_arrays(np.stack([np.asarray(s[1], dtype=np.uint32) for s in states]), [s[2] for s in states],
+                        [s[3] if len(s) >= 5 else 0 for s in states], [s[4] if len(s) >= 5 else 0.0 for s in states])
+
+    def __del__(self):
+        try:
+            self.lib.hp_streams_destroy(self.h)
+        except Exception:
+            pass
+
+
 _global = None
 
 

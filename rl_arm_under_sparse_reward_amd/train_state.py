@@ -11,6 +11,8 @@ File: ONE uncompressed .npz of named arrays a person can open with numpy --
     actor critic actor_target critic_target adam_{actor,critic}_{m,v}      float32, named_parameters() order (utils.py:18-27)
     adam_step  o_norm_* g_norm_*  rng_key rng_pos  buffer_{obs,ag,g,actions}  buffer_counters
     np_random_key  success_rates  extra  manifest
+    explore_stream_{keys,pos,has_gauss,gauss}      only when the agent explores with one stream per environment
+                                                   (ddpg_agent.enable_explore_streams): uint32 [n, 624], int32 [n], int32 [n], float64 [n]
 
 `manifest` is JSON text: format version, dims, capacity, T, rank, world size, library ABI, dtype / shape / checksum (A, B) of every
 device array, and the host scalars.  It is written to a temporary name and renamed, so a killed process never leaves a half-written
@@ -81,6 +83,16 @@ def expected_shapes(dims: dict) -> dict:
     return out
 
 
+def stream_shapes(n: int) -> dict:
+    """name -> (dtype, shape) of the arrays that carry n per-environment exploration streams (random.DeviceRandomStreams): numpy's
+    legacy state of every stream -- key, position, has_gauss, cached normal.  A state saved without such streams has none of
+    them and no 'explore_streams' field in its manifest."""
+    n = int(n)
+    return {"explore_stream_keys": ("<u4", (n, 624)), "explore_stream_pos": ("<i4", (n,)),
+            "explore_stream_has_gauss": ("<i4", (n,)), "explore_stream_gauss": ("<f8", (n,))}
+
+
+STREAM_ARRAYS = tuple(stream_shapes(0))
 DEVICE_ARRAYS = tuple(expected_shapes({"obs": 1, "goal": 1, "action": 1, "hidden": 1, "T": 1, "current_size": 0}))
 
 
@@ -156,6 +168,46 @@ def check_arrays(arrays, manifest, sums=True, where="state"):
     for name in ("np_random_key", "success_rates", "extra"):
         if name not in arrays:
             raise StateError(f"{where}: array '{name}' is missing")
+    check_stream_arrays(arrays, manifest, where=where)
+
+
+def check_stream_arrays(arrays, manifest, where="state"):
+    """The per-environment exploration streams of a state: all four arrays or none, as the manifest's 'explore_streams' field
+    says, shaped for its stream count, positions inside [0, 624], and summing to what it records (they are a few KB per stream and
+    reach the device by a plain copy, so their sums are always checked here, on the host)."""
+    rec = manifest.get("explore_streams")
+    if rec is None:
+        extra = [n for n in STREAM_ARRAYS if n in arrays]
+        if extra:
+            raise StateError(f"{where}: array '{extra[0]}' is present but the manifest has no 'explore_streams' field")
+        return
+    want = stream_shapes(rec["n"])
+    for name in STREAM_ARRAYS:
+        if name not in arrays:
+            raise StateError(f"{where}: array '{name}' is missing")
+        if name not in rec["arrays"]:
+            raise StateError(f"{where}: manifest has no entry for array '{name}'")
+        a, (dt, shape) = arrays[name], want[name]
+        if a.dtype.newbyteorder("<") != np.dtype(dt) or tuple(a.shape) != tuple(shape):
+            raise StateError(f"{where}: array '{name}' is {a.dtype} {tuple(a.shape)}, {rec['n']} streams imply {np.dtype(dt)} {tuple(shape)}")
+        got, listed = checksum(a), [int(x) for x in rec["arrays"][name]["sum"]]
+        if list(got) != listed:
+            raise StateError(f"{where}: array '{name}' sums to ({got[0]:016x}, {got[1]:016x}), the manifest says "
+                             f"({listed[0]:016x}, {listed[1]:016x})")
+    pos = arrays["explore_stream_pos"]
+    if pos.size and (int(pos.min()) < 0 or int(pos.max()) > 624):
+        raise StateError(f"{where}: array 'explore_stream_pos' holds a position outside [0, 624]")
+
+
+def stream_record(keys, pos, has_gauss, gauss):
+    """(arrays, manifest field) of n exploration streams, as a state file stores them."""
+    n = int(np.asarray(pos).size)
+    arrays = {}
+    for (name, (dt, shape)), a in zip(stream_shapes(n).items(), (keys, pos, has_gauss, gauss)):
+        arrays[name] = np.ascontiguousarray(a, dtype=dt).reshape(shape)
+    rec = {"n": n, "arrays": {k: {"dtype": stream_shapes(n)[k][0], "shape": list(a.shape), "sum": list(checksum(a))}
+                              for k, a in arrays.items()}}
+    return arrays, rec
 
 
 def verify(path):
@@ -211,6 +263,11 @@ class PendingSave:
         self.host_arrays = {"np_random_key": np.array(st[1], dtype=np.uint32),
                             "success_rates": np.array(agent.success_rates, dtype=np.float64),
                             "extra": np.frombuffer(bytes(extra or b""), dtype=np.uint8).copy()}
+        streams = getattr(agent, "explore_streams", None)
+        if streams is not None:
+            # copied now (a few KB per stream; synchronises), so rollouts that follow a wait=False capture do not move them
+            stream_arrays, self.host["explore_streams"] = stream_record(*streams.get_arrays())
+            self.host_arrays.update(stream_arrays)
 
     def done(self):
         return self._done is not None
@@ -266,6 +323,16 @@ def load(agent, path, verify_host=False):
     for key in ("obs", "goal", "action", "hidden", "T", "capacity"):
         if int(manifest["dims"][key]) != mine[key]:
             raise StateError(f"{where}: {key} of the state is {manifest['dims'][key]}, the receiver has {mine[key]}")
+    streams, rec = getattr(agent, "explore_streams", None), manifest.get("explore_streams")
+    names = ", ".join(f"'{n}'" for n in STREAM_ARRAYS)
+    if streams is not None and rec is None:
+        raise StateError(f"{where}: the agent explores with one stream per environment, but the state was saved without: arrays "
+                         f"{names} are missing")
+    if streams is None and rec is not None:
+        raise StateError(f"{where}: the state carries {rec['n']} per-environment exploration streams (arrays {names}), but the "
+                         "agent has none: call enable_explore_streams() (args.explore_streams) before loading")
+    if streams is not None and int(rec["n"]) != len(streams):
+        raise StateError(f"{where}: array 'explore_stream_keys' holds {rec['n']} streams, the agent has {len(streams)} environments")
     check_arrays(arrays, manifest, sums=verify_host, where=where)
     agent._flush_updates()
     sections, total = _layout(agent, mine["current_size"])
@@ -289,6 +356,8 @@ def load(agent, path, verify_host=False):
     np.random.set_state(("MT19937", arrays["np_random_key"], int(r["pos"]), int(r["has_gauss"]), float(r["cached_gaussian"])))
     agent.rng.seeded = True
     agent.rng._gauss = (int(manifest["rng_gauss"][0]), float(manifest["rng_gauss"][1]))
+    if streams is not None:
+        streams.set_arrays(*(arrays[n] for n in STREAM_ARRAYS))
     agent.success_rates = [float(x) for x in arrays["success_rates"]]
     agent.savetime = int(manifest["savetime"])
     return arrays["extra"].tobytes(), manifest
