@@ -182,9 +182,29 @@ struct MtState {  // device-resident, same fields as numpy's legacy state tuple
 };
 static_assert(sizeof(MtState) == MT_N * 4 + 16, "MtState: key | pos | has_gauss | gauss");
 
-struct hp_rng {
+// numpy _legacy_seeding(int) -> mt19937_seed() -> init_genrand: the key of RandomState(seed) (its pos is 624, no cached normal)
+__host__ __device__ inline void mt_init_genrand(uint32_t seed, uint32_t *key) {
+    for (uint32_t i = 0; i < MT_N; ++i) {
+        key[i] = seed;
+        seed = 1812433253u * (seed ^ (seed >> 30)) + i + 1u;
+    }
+}
+
+// n whole legacy states side by side in one allocation.  As hp_rng_streams: one exploration stream per environment of a
+// vectorised simulator (rng_streams.hip, k_rollout_step_streams in rollout.hip), stream i belonging to row i of a rollout wave.
+struct hp_rng_streams {
     hp_ctx *ctx = nullptr;
-    MtState *d_state = nullptr;
+    int64_t n = 1;
+    MtState *d_state = nullptr;   // [n]
+};
+// The host round trip of MtStates (rng_streams.hip): `count` states between `host` and d_state + first, on the context's stream,
+// waited for (the host side is pageable).  mt_state_fill makes one state from the fields of numpy's state tuple: the one place
+// that checks pos and drops a cached normal that is not given (`stream` < 0: the message does not name a stream).
+int mt_states_get(hp_rng_streams *s, MtState *host, int64_t first, int64_t count);
+int mt_states_put(hp_rng_streams *s, const MtState *host, int64_t first, int64_t count);
+int mt_state_fill(MtState &h, const char *entry, int64_t stream, const uint32_t *key624, int32_t pos, int32_t has_gauss, double gauss);
+
+struct hp_rng : hp_rng_streams {   // the one stream of the sampler: n = 1
     DevBuf scratch;  // test-hook outputs
     // parallel form of the sampler's index draw + hp_rng_advance (rng_parallel.hip)
     int64_t par_min_batch = 0;       // hp_rng_set_parallel: draws of at least this many transitions take it; 0 = off
@@ -195,14 +215,6 @@ struct hp_rng {
     double par_table_ms = 0;         // host time spent building it (reported once in DESIGN 3.6)
 };
 void rng_parallel_release(hp_rng *rng);
-
-// one exploration stream per environment of a vectorised simulator (rng_streams.hip, k_rollout_step_streams in rollout.hip):
-// n whole legacy states side by side, stream i belonging to row i of a rollout wave
-struct hp_rng_streams {
-    hp_ctx *ctx = nullptr;
-    int64_t n = 0;
-    MtState *d_state = nullptr;   // [n]
-};
 
 // one drawn transition index record (her.py:24-33)
 struct __attribute__((aligned(16))) PlanRec {

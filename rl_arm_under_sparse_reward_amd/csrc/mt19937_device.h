@@ -61,22 +61,37 @@ __device__ __forceinline__ uint32_t mt_twist_one(const uint32_t *src, const uint
     return far ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
 }
 
+// Every cooperative step of the walk takes the workgroup's width as a compile-time thread count: MT_THREADS for the index draws,
+// one wave for the exploration draws (mt19937_wave.h), MTP_JUMP_THREADS for the segment fill (rng_parallel.hip).
+// One phase of the twist, words [lo, hi) of the new block: a width that covers a phase writes it in one pass, without a loop,
+// behind the LDS-only barrier; a narrower one (the one-wave walk) loops and keeps the full barrier it has always had.
+template <int NT>
+__device__ __forceinline__ void mt_twist_phase(const uint32_t *src, uint32_t *dst, int lo, int hi) {
+    const int tid = threadIdx.x;
+    if constexpr (NT >= MT_N - MT_M) {
+        if (tid < hi - lo) dst[lo + tid] = mt_twist_one(src, dst, lo + tid);
+        mt_sync();
+    } else {
+        for (int k = lo + tid; k < hi; k += NT) dst[k] = mt_twist_one(src, dst, k);
+        __syncthreads();
+    }
+}
+
 // produce block nblk from block nblk-1 (workgroup-wide)
+template <int NT = MT_THREADS>
 __device__ __forceinline__ void mt_generate_block(MtWg &g) {
     const uint32_t *src = g.blk[(g.nblk - 1) & 3];
     uint32_t *dst = g.blk[g.nblk & 3];
-    const int tid = threadIdx.x;
-    if (tid < MT_N - MT_M) dst[tid] = mt_twist_one(src, dst, tid);  // k in [0,227)
-    mt_sync();
-    if (tid < MT_N - MT_M) dst[227 + tid] = mt_twist_one(src, dst, 227 + tid);  // k in [227,454)
-    mt_sync();
-    if (tid < MT_N - 454) dst[454 + tid] = mt_twist_one(src, dst, 454 + tid);  // k in [454,624)
-    mt_sync();
+    mt_twist_phase<NT>(src, dst, 0, 227);
+    mt_twist_phase<NT>(src, dst, 227, 454);
+    mt_twist_phase<NT>(src, dst, 454, MT_N);
     g.nblk += 1;
 }
 
+// words [cursor, abs_end) readable; abs_end - cursor stays far below the three blocks the ring keeps behind the newest
+template <int NT = MT_THREADS>
 __device__ __forceinline__ void mt_ensure(MtWg &g, long long abs_end) {
-    while ((long long)g.nblk * MT_N < abs_end) mt_generate_block(g);
+    while ((long long)g.nblk * MT_N < abs_end) mt_generate_block<NT>(g);
 }
 
 __device__ __forceinline__ uint32_t mt_word(const MtWg &g, long long abs) {
@@ -85,10 +100,11 @@ __device__ __forceinline__ uint32_t mt_word(const MtWg &g, long long abs) {
     return mt_temper(g.blk[b & 3][o]);
 }
 
+template <int NT = MT_THREADS>
 __device__ __forceinline__ void mt_load(MtWg &g, const MtState *st, uint32_t (*ring)[MT_N], int *ibuf) {
     g.blk = ring;
     g.ibuf = ibuf;
-    for (int k = threadIdx.x; k < MT_N; k += MT_THREADS) ring[0][k] = st->key[k];
+    for (int k = threadIdx.x; k < MT_N; k += NT) ring[0][k] = st->key[k];
     g.cursor = st->pos;
     g.nblk = 1;
     g.flip = 0;
@@ -97,22 +113,41 @@ __device__ __forceinline__ void mt_load(MtWg &g, const MtState *st, uint32_t (*r
 
 // numpy keeps (block, pos) with pos in [0,624]; a cursor on a block boundary belongs to the
 // block just finished (pos == 624 -> "twist before the next word").
-__device__ __forceinline__ void mt_final_block(long long c, int &b, int &pos) {
+__host__ __device__ __forceinline__ void mt_final_block(long long c, long long &b, int &pos) {
     if (c > 0 && c % MT_N == 0) {
-        b = (int)(c / MT_N) - 1;
+        b = c / MT_N - 1;
         pos = MT_N;
     } else {
-        b = (int)(c / MT_N);
+        b = c / MT_N;
         pos = (int)(c % MT_N);
     }
 }
 
-__device__ __forceinline__ void mt_store(const MtWg &g, MtState *st) {
-    int b, pos;
-    mt_final_block(g.cursor, b, pos);
+// The one commit of a walk back into numpy's (key, pos).  `block_at(b)` = raw block b of the walk: the LDS ring, or the raw
+// scratch stream of the parallel draw.  Block 0 is the loaded key, which is still what *st holds: the key is rewritten only when
+// the walk left it.  `gauss` != nullptr: the cached normal of the caller's walk goes with it.
+template <int NT = MT_THREADS, class Blocks>
+__device__ __forceinline__ void mt_commit(MtState *st, long long cursor, Blocks block_at, int has_gauss = 0, const double *gauss = nullptr) {
+    long long b;
+    int pos;
+    mt_final_block(cursor, b, pos);
+    if (b > 0) {
+        const uint32_t *src = block_at(b);
+        for (int k = threadIdx.x; k < MT_N; k += NT) st->key[k] = src[k];
+    }
+    if (threadIdx.x == 0) {
+        st->pos = pos;
+        if (gauss) {
+            st->has_gauss = has_gauss;
+            st->gauss = *gauss;
+        }
+    }
+}
+
+template <int NT = MT_THREADS>
+__device__ __forceinline__ void mt_store(const MtWg &g, MtState *st, int has_gauss = 0, const double *gauss = nullptr) {
     __syncthreads();
-    for (int k = threadIdx.x; k < MT_N; k += MT_THREADS) st->key[k] = g.blk[b & 3][k];
-    if (threadIdx.x == 0) st->pos = pos;
+    mt_commit<NT>(st, g.cursor, [&](long long b) { return g.blk[b & 3]; }, has_gauss, gauss);
 }
 
 // exclusive prefix of a predicate over the MT_THREADS-thread workgroup; returns this thread's rank among the

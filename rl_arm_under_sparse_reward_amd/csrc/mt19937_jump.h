@@ -1,4 +1,4 @@
-// mt19937_jump.h -- jump polynomials of MT19937 on the host (plain C++, no device needed).
+// mt19937_jump.h -- jump polynomials of MT19937 on the host (host code only, no device needed).
 //
 // MT19937 is linear over GF(2): with phi the characteristic polynomial of its one-word transition (degree 19937), every bit
 // of the sequence of GENERATED raw (untempered) words z_n obeys  XOR_{i : phi_i} z_{n+i} = 0, and for g_J(x) = x^J mod phi(x)
@@ -16,6 +16,8 @@
 #include <cstring>
 #include <vector>
 
+#include "internal.h"   // mt_init_genrand
+
 #define MTJ_DEG 19937
 #define MTJ_LIMBS 312                       // 312 * 64 = 19968 > 19937: holds phi itself too
 #define MTJ_TOP (MTJ_DEG & 63)              // bit of limb 311 that is x^19937
@@ -27,10 +29,7 @@ namespace mtj {
 // raw (untempered) generated words of numpy's init_genrand(seed): z_0 .. z_{n-1}, z_0 = first word after the seed block
 inline std::vector<uint32_t> raw_words(uint32_t seed, size_t n) {
     std::vector<uint32_t> s(624 + n);
-    for (uint32_t i = 0; i < 624; ++i) {
-        s[i] = seed;
-        seed = 1812433253u * (seed ^ (seed >> 30)) + i + 1u;
-    }
+    mt_init_genrand(seed, s.data());
     for (size_t k = 624; k < s.size(); ++k) {
         const uint32_t y = (s[k - 624] & 0x80000000u) | (s[k - 623] & 0x7fffffffu);
         s[k] = s[k - 624 + 397] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);

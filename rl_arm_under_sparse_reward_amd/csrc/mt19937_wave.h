@@ -18,53 +18,17 @@
 
 #define MW_THREADS 64
 
+// The one-wave walk: an MtWg of MW_THREADS threads + numpy's cached second normal.  Constructing one is mt_load and store() is
+// mt_store: both are cooperative and hold a workgroup barrier, so both run under workgroup-uniform control flow only.
 struct MwState {
     MtWg g;
     int has_gauss;
     double gauss;
-};
-
-__device__ __forceinline__ void mw_generate_block(MtWg &g) {
-    const uint32_t *src = g.blk[(g.nblk - 1) & 3];
-    uint32_t *dst = g.blk[g.nblk & 3];
-    const int tid = threadIdx.x;
-    for (int k = tid; k < 227; k += MW_THREADS) dst[k] = mt_twist_one(src, dst, k);   // the three phases of mt_generate_block
-    __syncthreads();
-    for (int k = 227 + tid; k < 454; k += MW_THREADS) dst[k] = mt_twist_one(src, dst, k);
-    __syncthreads();
-    for (int k = 454 + tid; k < MT_N; k += MW_THREADS) dst[k] = mt_twist_one(src, dst, k);
-    __syncthreads();
-    g.nblk += 1;
-}
-
-// words [cursor, abs_end) readable; abs_end - cursor stays far below the three blocks the ring keeps behind the newest
-__device__ __forceinline__ void mw_ensure(MtWg &g, long long abs_end) {
-    while ((long long)g.nblk * MT_N < abs_end) mw_generate_block(g);
-}
-
-__device__ __forceinline__ void mw_load(MwState &w, const MtState *st, uint32_t (*ring)[MT_N]) {
-    w.g.blk = ring;
-    w.g.ibuf = nullptr;
-    w.g.flip = 0;
-    for (int k = threadIdx.x; k < MT_N; k += MW_THREADS) ring[0][k] = st->key[k];
-    w.g.cursor = st->pos;
-    w.g.nblk = 1;
-    w.has_gauss = st->has_gauss;
-    w.gauss = st->gauss;
-    __syncthreads();
-}
-
-__device__ __forceinline__ void mw_store(const MwState &w, MtState *st) {
-    int b, pos;
-    mt_final_block(w.g.cursor, b, pos);
-    __syncthreads();
-    for (int k = threadIdx.x; k < MT_N; k += MW_THREADS) st->key[k] = w.g.blk[b & 3][k];
-    if (threadIdx.x == 0) {
-        st->pos = pos;
-        st->has_gauss = w.has_gauss;
-        st->gauss = w.gauss;
+    __device__ __forceinline__ MwState(const MtState *st, uint32_t (*ring)[MT_N]) : has_gauss(st->has_gauss), gauss(st->gauss) {
+        mt_load<MW_THREADS>(g, st, ring, nullptr);
     }
-}
+    __device__ __forceinline__ void store(MtState *st) const { mt_store<MW_THREADS>(g, st, has_gauss, &gauss); }
+};
 
 __device__ __forceinline__ double mw_double_at(const MtWg &g, long long abs) {
     return mt_to_double(mt_word(g, abs), mt_word(g, abs + 1));
@@ -84,7 +48,7 @@ __device__ __forceinline__ void mw_draw_normal(MwState &w, long long count, Emit
     }
     while (done < count) {
         const long long need = (count - done + 1) / 2;   // accepted attempts still to take
-        mw_ensure(w.g, w.g.cursor + 4 * MW_THREADS);
+        mt_ensure<MW_THREADS>(w.g, w.g.cursor + 4 * MW_THREADS);
         const long long at = w.g.cursor + 4 * lane;
         const double x1 = __dsub_rn(__dmul_rn(2.0, mw_double_at(w.g, at)), 1.0);
         const double x2 = __dsub_rn(__dmul_rn(2.0, mw_double_at(w.g, at + 2)), 1.0);
@@ -120,7 +84,7 @@ __device__ __forceinline__ void mw_draw_normal(MwState &w, long long count, Emit
 // random_uniform(low, range) = low + range * next_double, `count` times (count <= MW_THREADS per call: one value per lane)
 template <class Emit>
 __device__ __forceinline__ void mw_draw_uniform(MwState &w, double low, double range, int count, Emit emit) {
-    mw_ensure(w.g, w.g.cursor + 2 * count);
+    mt_ensure<MW_THREADS>(w.g, w.g.cursor + 2 * count);
     if ((int)threadIdx.x < count) emit((int)threadIdx.x, __dadd_rn(low, __dmul_rn(range, mw_double_at(w.g, w.g.cursor + 2 * threadIdx.x))));
     w.g.cursor += 2 * count;
 }
@@ -135,7 +99,7 @@ __device__ __forceinline__ int mw_draw_binomial1(MwState &w, double eps, double 
     const long long bound = 1;
     long long X = 0;
     double px = qn;
-    mw_ensure(w.g, w.g.cursor + 2);
+    mt_ensure<MW_THREADS>(w.g, w.g.cursor + 2);
     double U = mw_double_at(w.g, w.g.cursor);
     w.g.cursor += 2;
     while (U > px) {
@@ -143,7 +107,7 @@ __device__ __forceinline__ int mw_draw_binomial1(MwState &w, double eps, double 
         if (X > bound) {
             X = 0;
             px = qn;
-            mw_ensure(w.g, w.g.cursor + 2);
+            mt_ensure<MW_THREADS>(w.g, w.g.cursor + 2);
             U = mw_double_at(w.g, w.g.cursor);
             w.g.cursor += 2;
         } else {

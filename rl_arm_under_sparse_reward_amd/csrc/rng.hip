@@ -51,8 +51,9 @@ __global__ __launch_bounds__(MT_THREADS) void k_draw_slots(MtState *st, BufMeta 
     }
 }
 
-__global__ __launch_bounds__(MT_THREADS) void k_test_randint(MtState *st, long long low, uint32_t rng,
-                                                            long long count, long long *out) {
+// (the hooks' kernels take (state, out, count, further arguments): rng_hook launches them)
+__global__ __launch_bounds__(MT_THREADS) void k_test_randint(MtState *st, long long *out, long long count, long long low,
+                                                            uint32_t rng) {
     __shared__ uint32_t ring[4][MT_N];
     __shared__ int ibuf[MT_IBUF];
     MtWg g;
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(MT_THREADS) void k_test_randint(MtState *st, long l
     mt_store(g, st);
 }
 
-__global__ __launch_bounds__(MT_THREADS) void k_test_uniform(MtState *st, long long count, double *out) {
+__global__ __launch_bounds__(MT_THREADS) void k_test_uniform(MtState *st, double *out, long long count) {
     __shared__ uint32_t ring[4][MT_N];
     __shared__ int ibuf[MT_IBUF];
     MtWg g;
@@ -71,23 +72,21 @@ __global__ __launch_bounds__(MT_THREADS) void k_test_uniform(MtState *st, long l
 }
 
 // test hooks of the wave-walked draws (mt19937_wave.h): np.random.randn(count) and np.random.binomial(1, eps, count)
-__global__ __launch_bounds__(MW_THREADS) void k_test_normal(MtState *st, long long count, double *out) {
+__global__ __launch_bounds__(MW_THREADS) void k_test_normal(MtState *st, double *out, long long count) {
     __shared__ uint32_t ring[4][MT_N];
-    MwState w;
-    mw_load(w, st, ring);
+    MwState w(st, ring);
     mw_draw_normal(w, count, [&](long long i, double z) { out[i] = z; });
-    mw_store(w, st);
+    w.store(st);
 }
 
-__global__ __launch_bounds__(MW_THREADS) void k_test_binomial1(MtState *st, double eps, double qn, long long count, long long *out) {
+__global__ __launch_bounds__(MW_THREADS) void k_test_binomial1(MtState *st, long long *out, long long count, double eps, double qn) {
     __shared__ uint32_t ring[4][MT_N];
-    MwState w;
-    mw_load(w, st, ring);
+    MwState w(st, ring);
     for (long long i = 0; i < count; ++i) {
         const int x = mw_draw_binomial1(w, eps, qn);
         if (threadIdx.x == 0) out[i] = x;
     }
-    mw_store(w, st);
+    w.store(st);
 }
 
 // ------------------------------------------------------------------------------ launchers
@@ -116,6 +115,20 @@ int rng_launch_slots(hp_rng *rng, hp_buffer *buf, int64_t n_new, int64_t *d_slot
     return HP_OK;
 }
 
+// The part the four draw hooks share: device scratch for `count` results, one single-workgroup launch of
+// kernel(state, out, count, extra...), the results copied to the host, and the wait (host_out is pageable).
+template <class Out, class... Extra>
+static int rng_hook(hp_rng *rng, void (*kernel)(MtState *, Out *, long long, Extra...), int threads, int64_t count, void *host_out,
+                    Extra... extra) {
+    if (count == 0) return HP_OK;
+    HP_TRY(rng->scratch.ensure((size_t)count * sizeof(Out)));
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(threads), 0, rng->ctx->stream, rng->d_state, rng->scratch.as<Out>(), (long long)count, extra...);
+    HP_CHECK_HIP(hipGetLastError());
+    HP_CHECK_HIP(hipMemcpyAsync(host_out, rng->scratch.p, (size_t)count * sizeof(Out), hipMemcpyDeviceToHost, rng->ctx->stream));
+    HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
+    return HP_OK;
+}
+
 // --------------------------------------------------------------------------------- C ABI
 extern "C" {
 
@@ -139,36 +152,25 @@ int hp_rng_seed(hp_rng *rng, uint32_t seed) {
     HP_SERIALISE(rng);
     MtState h;
     memset(&h, 0, sizeof(h));
-    for (int i = 0; i < MT_N; ++i) {
-        h.key[i] = seed;
-        seed = 1812433253u * (seed ^ (seed >> 30)) + (uint32_t)i + 1u;
-    }
+    mt_init_genrand(seed, h.key);
     h.pos = MT_N;
-    // stream-ordered with the kernels that use the state; the pageable source is copied before return
-    HP_CHECK_HIP(hipMemcpyAsync(rng->d_state, &h, sizeof(h), hipMemcpyHostToDevice, rng->ctx->stream));
-    HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
-    return HP_OK;
+    return mt_states_put(rng, &h, 0, 1);
 }
 
 int hp_rng_set_state(hp_rng *rng, const uint32_t *key624, int32_t pos) {
     HP_REQUIRE(rng && key624, HP_ERR_INVALID, "hp_rng_set_state: null argument");
     HP_SERIALISE(rng);
-    HP_REQUIRE(pos >= 0 && pos <= MT_N, HP_ERR_INVALID, "hp_rng_set_state: pos %d outside [0, 624]", pos);
     MtState h;
     memset(&h, 0, sizeof(h));
-    memcpy(h.key, key624, sizeof(h.key));
-    h.pos = pos;
-    HP_CHECK_HIP(hipMemcpyAsync(rng->d_state, &h, sizeof(h), hipMemcpyHostToDevice, rng->ctx->stream));
-    HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
-    return HP_OK;
+    HP_TRY(mt_state_fill(h, "hp_rng_set_state", -1, key624, pos, 0, 0.0));
+    return mt_states_put(rng, &h, 0, 1);
 }
 
 int hp_rng_get_state(hp_rng *rng, uint32_t *key624, int32_t *pos) {
     HP_REQUIRE(rng && key624 && pos, HP_ERR_INVALID, "hp_rng_get_state: null argument");
     HP_SERIALISE(rng);
     MtState h;
-    HP_CHECK_HIP(hipMemcpyAsync(&h, rng->d_state, sizeof(h), hipMemcpyDeviceToHost, rng->ctx->stream));
-    HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
+    HP_TRY(mt_states_get(rng, &h, 0, 1));
     memcpy(key624, h.key, sizeof(h.key));
     *pos = h.pos;
     return HP_OK;
@@ -180,42 +182,21 @@ int hp_rng_randint(hp_rng *rng, int64_t low, int64_t high, int64_t count, int64_
     HP_REQUIRE(high > low, HP_ERR_INVALID, "high <= 0");  // numpy's message for randint(0, 0)
     HP_REQUIRE(high - low - 1 < 0xFFFFFFFFll, HP_ERR_INVALID, "hp_rng_randint: range needs more than 32 bits");
     HP_REQUIRE(count >= 0, HP_ERR_INVALID, "hp_rng_randint: negative count");
-    if (count == 0) return HP_OK;
-    HP_TRY(rng->scratch.ensure((size_t)count * 8));
-    hipLaunchKernelGGL(k_test_randint, dim3(1), dim3(MT_THREADS), 0, rng->ctx->stream, rng->d_state,
-                       (long long)low, (uint32_t)(high - low - 1), (long long)count, rng->scratch.as<long long>());
-    HP_CHECK_HIP(hipGetLastError());
-    HP_CHECK_HIP(hipMemcpyAsync(host_out, rng->scratch.p, (size_t)count * 8, hipMemcpyDeviceToHost, rng->ctx->stream));
-    HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
-    return HP_OK;
+    return rng_hook(rng, k_test_randint, MT_THREADS, count, host_out, (long long)low, (uint32_t)(high - low - 1));
 }
 
 int hp_rng_uniform(hp_rng *rng, int64_t count, double *host_out) {
     HP_REQUIRE(rng && host_out, HP_ERR_INVALID, "hp_rng_uniform: null argument");
     HP_SERIALISE(rng);
     HP_REQUIRE(count >= 0, HP_ERR_INVALID, "hp_rng_uniform: negative count");
-    if (count == 0) return HP_OK;
-    HP_TRY(rng->scratch.ensure((size_t)count * 8));
-    hipLaunchKernelGGL(k_test_uniform, dim3(1), dim3(MT_THREADS), 0, rng->ctx->stream, rng->d_state,
-                       (long long)count, rng->scratch.as<double>());
-    HP_CHECK_HIP(hipGetLastError());
-    HP_CHECK_HIP(hipMemcpyAsync(host_out, rng->scratch.p, (size_t)count * 8, hipMemcpyDeviceToHost, rng->ctx->stream));
-    HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
-    return HP_OK;
+    return rng_hook(rng, k_test_uniform, MT_THREADS, count, host_out);
 }
 
 int hp_rng_standard_normal(hp_rng *rng, int64_t count, double *host_out) {
     HP_REQUIRE(rng && host_out, HP_ERR_INVALID, "hp_rng_standard_normal: null argument");
     HP_SERIALISE(rng);
     HP_REQUIRE(count >= 0, HP_ERR_INVALID, "hp_rng_standard_normal: negative count");
-    if (count == 0) return HP_OK;
-    HP_TRY(rng->scratch.ensure((size_t)count * 8));
-    hipLaunchKernelGGL(k_test_normal, dim3(1), dim3(MW_THREADS), 0, rng->ctx->stream, rng->d_state, (long long)count,
-                       rng->scratch.as<double>());
-    HP_CHECK_HIP(hipGetLastError());
-    HP_CHECK_HIP(hipMemcpyAsync(host_out, rng->scratch.p, (size_t)count * 8, hipMemcpyDeviceToHost, rng->ctx->stream));
-    HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
-    return HP_OK;
+    return rng_hook(rng, k_test_normal, MW_THREADS, count, host_out);
 }
 
 int hp_rng_binomial1(hp_rng *rng, double p, double qn, int64_t count, int64_t *host_out) {
@@ -223,14 +204,7 @@ int hp_rng_binomial1(hp_rng *rng, double p, double qn, int64_t count, int64_t *h
     HP_SERIALISE(rng);
     HP_REQUIRE(p >= 0.0 && p <= 1.0, HP_ERR_INVALID, "p < 0, p > 1 or p is NaN");   // numpy's message
     HP_REQUIRE(count >= 0, HP_ERR_INVALID, "hp_rng_binomial1: negative count");
-    if (count == 0) return HP_OK;
-    HP_TRY(rng->scratch.ensure((size_t)count * 8));
-    hipLaunchKernelGGL(k_test_binomial1, dim3(1), dim3(MW_THREADS), 0, rng->ctx->stream, rng->d_state, p, qn, (long long)count,
-                       rng->scratch.as<long long>());
-    HP_CHECK_HIP(hipGetLastError());
-    HP_CHECK_HIP(hipMemcpyAsync(host_out, rng->scratch.p, (size_t)count * 8, hipMemcpyDeviceToHost, rng->ctx->stream));
-    HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
-    return HP_OK;
+    return rng_hook(rng, k_test_binomial1, MW_THREADS, count, host_out, p, qn);
 }
 
 // numpy's cached second normal (state tuple fields 3 and 4); hp_rng_seed and hp_rng_set_state clear it, as numpy's seed() does and
@@ -238,23 +212,21 @@ int hp_rng_binomial1(hp_rng *rng, double p, double qn, int64_t count, int64_t *h
 int hp_rng_get_gauss(hp_rng *rng, int32_t *has_gauss, double *gauss) {
     HP_REQUIRE(rng && has_gauss && gauss, HP_ERR_INVALID, "hp_rng_get_gauss: null argument");
     HP_SERIALISE(rng);
-    struct { int32_t has; int32_t pad; double v; } h;
-    HP_CHECK_HIP(hipMemcpyAsync(&h.has, &rng->d_state->has_gauss, 4, hipMemcpyDeviceToHost, rng->ctx->stream));
-    HP_CHECK_HIP(hipMemcpyAsync(&h.v, &rng->d_state->gauss, 8, hipMemcpyDeviceToHost, rng->ctx->stream));
-    HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
-    *has_gauss = h.has;
-    *gauss = h.v;
+    MtState h;
+    HP_TRY(mt_states_get(rng, &h, 0, 1));
+    *has_gauss = h.has_gauss;
+    *gauss = h.gauss;
     return HP_OK;
 }
 
 int hp_rng_set_gauss(hp_rng *rng, int32_t has_gauss, double gauss) {
     HP_REQUIRE(rng, HP_ERR_INVALID, "hp_rng_set_gauss: null handle");
     HP_SERIALISE(rng);
-    const int32_t has = has_gauss ? 1 : 0;
-    HP_CHECK_HIP(hipMemcpyAsync(&rng->d_state->has_gauss, &has, 4, hipMemcpyHostToDevice, rng->ctx->stream));
-    HP_CHECK_HIP(hipMemcpyAsync(&rng->d_state->gauss, &gauss, 8, hipMemcpyHostToDevice, rng->ctx->stream));
-    HP_CHECK_HIP(hipStreamSynchronize(rng->ctx->stream));
-    return HP_OK;
+    MtState h;
+    HP_TRY(mt_states_get(rng, &h, 0, 1));
+    h.has_gauss = has_gauss ? 1 : 0;
+    h.gauss = gauss;
+    return mt_states_put(rng, &h, 0, 1);
 }
 
 void hp_rng_destroy(hp_rng *rng) {

@@ -49,11 +49,7 @@ struct ParCtl {
 __global__ __launch_bounds__(MT_THREADS) void k_mt_window(const MtState *st, uint32_t *win) {
     __shared__ uint32_t ring[4][MT_N];
     MtWg g;
-    g.blk = ring;
-    g.ibuf = nullptr;
-    g.nblk = 1;
-    for (int k = threadIdx.x; k < MT_N; k += MT_THREADS) ring[0][k] = st->key[k];
-    __syncthreads();
+    mt_load(g, st, ring, nullptr);
     for (int j = 0; j < MTP_WIN_BLOCKS; ++j) {
         mt_generate_block(g);
         const uint32_t *blk = ring[(g.nblk - 1) & 3];
@@ -96,16 +92,16 @@ __global__ __launch_bounds__(MTP_JUMP_THREADS) void k_mt_jumpfill(const MtState 
     uint32_t(*ring)[MT_N] = reinterpret_cast<uint32_t(*)[MT_N]>(smem);
     uint32_t *w = smem + 4 * MT_N;
     const int p = blockIdx.x, tid = threadIdx.x;
-    MtWg g;
+    MtWg g;   // p > 0: ring block 0 is the block the segment's jump lands on
     g.blk = ring;
-    g.ibuf = nullptr;
     g.nblk = 1;
     int next, end = (p + 1) * MTP_SEG_BLOCKS;
     if (end > n_gen) end = n_gen;
     if (p == 0) {
-        if (tid < MT_N) raw[tid] = ring[0][tid] = st->key[tid];
+        mt_load<MTP_JUMP_THREADS>(g, st, ring, nullptr);
+        if (tid < MT_N) raw[tid] = ring[0][tid];
         if (tid == 0) {
-            ctl->c[0] = st->pos;
+            ctl->c[0] = g.cursor;
             ctl->fail[0] = ctl->fail[1] = 0;
             ctl->done = 0;
         }
@@ -118,7 +114,7 @@ __global__ __launch_bounds__(MTP_JUMP_THREADS) void k_mt_jumpfill(const MtState 
     }
     __syncthreads();
     for (int j = next; j < end; ++j) {
-        mt_generate_block(g);
+        mt_generate_block<MTP_JUMP_THREADS>(g);
         if (tid < MT_N) raw[(size_t)(1 + j) * MT_N + tid] = ring[(g.nblk - 1) & 3][tid];
     }
 }
@@ -250,11 +246,8 @@ __global__ __launch_bounds__(MTP_THREADS) void k_par_uniform(ParCtl *ctl, const 
         plan[i] = r;
     }
     if (blockIdx.x == 0) {         // commit: the final state in numpy's representation
-        int b, pos;
-        mt_final_block(end, b, pos);
-        for (int k = threadIdx.x; k < MT_N; k += MTP_THREADS) st->key[k] = raw[(size_t)b * MT_N + k];
+        mt_commit<MTP_THREADS>(st, end, [&](long long b) { return raw + (size_t)b * MT_N; });
         if (threadIdx.x == 0) {
-            st->pos = pos;
             ctl->done = 1;
             ctl->n_parallel += 1;
         }
@@ -411,20 +404,16 @@ int hp_rng_advance(hp_rng *rng, uint64_t n_words) {
     int32_t pos = 0;
     HP_CHECK_HIP(hipMemcpyAsync(&pos, &rng->d_state->pos, 4, hipMemcpyDeviceToHost, s));
     HP_CHECK_HIP(hipStreamSynchronize(s));
-    const uint64_t c = (uint64_t)pos + n_words;          // cursor in words, block 0 = the loaded key
-    uint64_t b = c / MT_N;
-    int32_t new_pos = (int32_t)(c % MT_N);
-    if (new_pos == 0) {   // mt_final_block's rule (c > 0 here)
-        b -= 1;
-        new_pos = MT_N;
-    }
+    long long b;          // cursor in words, block 0 = the loaded key
+    int new_pos;
+    mt_final_block((long long)pos + (long long)n_words, b, new_pos);
     if (b == 0) {
         HP_CHECK_HIP(hipMemcpyAsync(&rng->d_state->pos, &new_pos, 4, hipMemcpyHostToDevice, s));
         HP_CHECK_HIP(hipStreamSynchronize(s));
         return HP_OK;
     }
     MtPoly g;     // generated block b - 1 starts (b - 1) * 624 words behind z_0
-    HP_REQUIRE(mtj::jump_poly((b - 1) * MT_N, g), HP_ERR_STATE,
+    HP_REQUIRE(mtj::jump_poly((uint64_t)(b - 1) * MT_N, g), HP_ERR_STATE,
                "MT19937's characteristic polynomial could not be derived (Berlekamp-Massey self-check failed)");
     HP_TRY(rng->par_win.ensure((size_t)MTP_WIN_WORDS * 4));
     HP_TRY(rng->par_poly.ensure(sizeof(g.w)));

@@ -15,24 +15,36 @@
 __global__ __launch_bounds__(RS_SEED_THREADS) void k_streams_seed(MtState *st, const uint32_t *seeds, uint32_t base, long long n) {
     const long long i = (long long)blockIdx.x * RS_SEED_THREADS + threadIdx.x;
     if (i >= n) return;
-    uint32_t s = seeds ? seeds[i] : base + (uint32_t)i;
     MtState *m = st + i;
-    for (int k = 0; k < MT_N; ++k) {
-        m->key[k] = s;
-        s = 1812433253u * (s ^ (s >> 30)) + (uint32_t)k + 1u;
-    }
+    mt_init_genrand(seeds ? seeds[i] : base + (uint32_t)i, m->key);
     m->pos = MT_N;
     m->has_gauss = 0;
     m->gauss = 0.0;
 }
 
-static int streams_copy(hp_rng_streams *s, void *host, int64_t first, int64_t count, bool to_host) {
-    MtState *dev = s->d_state + first;
-    const size_t bytes = (size_t)count * sizeof(MtState);
-    if (to_host) HP_CHECK_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s->ctx->stream));
-    else HP_CHECK_HIP(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, s->ctx->stream));
-    // stream-ordered with the kernels that use the states; the pageable side is done with before return
+// stream-ordered with the kernels that use the states; the pageable side is done with before return
+int mt_states_get(hp_rng_streams *s, MtState *host, int64_t first, int64_t count) {
+    HP_CHECK_HIP(hipMemcpyAsync(host, s->d_state + first, (size_t)count * sizeof(MtState), hipMemcpyDeviceToHost, s->ctx->stream));
     HP_CHECK_HIP(hipStreamSynchronize(s->ctx->stream));
+    return HP_OK;
+}
+
+int mt_states_put(hp_rng_streams *s, const MtState *host, int64_t first, int64_t count) {
+    HP_CHECK_HIP(hipMemcpyAsync(s->d_state + first, host, (size_t)count * sizeof(MtState), hipMemcpyHostToDevice, s->ctx->stream));
+    HP_CHECK_HIP(hipStreamSynchronize(s->ctx->stream));
+    return HP_OK;
+}
+
+int mt_state_fill(MtState &h, const char *entry, int64_t stream, const uint32_t *key624, int32_t pos, int32_t has_gauss, double gauss) {
+    if (pos < 0 || pos > MT_N) {
+        if (stream < 0) hp_set_error("%s: pos %d outside [0, 624]", entry, pos);
+        else hp_set_error("%s: pos %d of stream %lld outside [0, 624]", entry, pos, (long long)stream);
+        return HP_ERR_INVALID;
+    }
+    memcpy(h.key, key624, sizeof(h.key));
+    h.pos = pos;
+    h.has_gauss = has_gauss ? 1 : 0;
+    h.gauss = has_gauss ? gauss : 0.0;
     return HP_OK;
 }
 
@@ -96,7 +108,7 @@ int hp_streams_get_state(hp_rng_streams *s, int64_t i, uint32_t *key624, int32_t
     HP_SERIALISE(s);
     HP_REQUIRE(i >= 0 && i < s->n, HP_ERR_INVALID, "hp_streams_get_state: stream %lld outside [0, %lld)", (long long)i, (long long)s->n);
     MtState h;
-    HP_TRY(streams_copy(s, &h, i, 1, true));
+    HP_TRY(mt_states_get(s, &h, i, 1));
     memcpy(key624, h.key, sizeof(h.key));
     *pos = h.pos;
     *has_gauss = h.has_gauss;
@@ -108,20 +120,16 @@ int hp_streams_set_state(hp_rng_streams *s, int64_t i, const uint32_t *key624, i
     HP_REQUIRE(s && key624, HP_ERR_INVALID, "hp_streams_set_state: null argument");
     HP_SERIALISE(s);
     HP_REQUIRE(i >= 0 && i < s->n, HP_ERR_INVALID, "hp_streams_set_state: stream %lld outside [0, %lld)", (long long)i, (long long)s->n);
-    HP_REQUIRE(pos >= 0 && pos <= MT_N, HP_ERR_INVALID, "hp_streams_set_state: pos %d outside [0, 624]", pos);
     MtState h;
-    memcpy(h.key, key624, sizeof(h.key));
-    h.pos = pos;
-    h.has_gauss = has_gauss ? 1 : 0;
-    h.gauss = has_gauss ? gauss : 0.0;
-    return streams_copy(s, &h, i, 1, false);
+    HP_TRY(mt_state_fill(h, "hp_streams_set_state", -1, key624, pos, has_gauss, gauss));
+    return mt_states_put(s, &h, i, 1);
 }
 
 int hp_streams_get_all(hp_rng_streams *s, uint32_t *keys, int32_t *pos, int32_t *has_gauss, double *gauss) {
     HP_REQUIRE(s && keys && pos && has_gauss && gauss, HP_ERR_INVALID, "hp_streams_get_all: null argument");
     HP_SERIALISE(s);
     std::vector<MtState> h((size_t)s->n);
-    HP_TRY(streams_copy(s, h.data(), 0, s->n, true));
+    HP_TRY(mt_states_get(s, h.data(), 0, s->n));
     for (int64_t i = 0; i < s->n; ++i) {
         memcpy(keys + i * MT_N, h[i].key, sizeof(h[i].key));
         pos[i] = h[i].pos;
@@ -134,17 +142,9 @@ int hp_streams_get_all(hp_rng_streams *s, uint32_t *keys, int32_t *pos, int32_t 
 int hp_streams_set_all(hp_rng_streams *s, const uint32_t *keys, const int32_t *pos, const int32_t *has_gauss, const double *gauss) {
     HP_REQUIRE(s && keys && pos && has_gauss && gauss, HP_ERR_INVALID, "hp_streams_set_all: null argument");
     HP_SERIALISE(s);
-    for (int64_t i = 0; i < s->n; ++i)
-        HP_REQUIRE(pos[i] >= 0 && pos[i] <= MT_N, HP_ERR_INVALID, "hp_streams_set_all: pos %d of stream %lld outside [0, 624]", pos[i],
-                   (long long)i);
     std::vector<MtState> h((size_t)s->n);
-    for (int64_t i = 0; i < s->n; ++i) {
-        memcpy(h[i].key, keys + i * MT_N, sizeof(h[i].key));
-        h[i].pos = pos[i];
-        h[i].has_gauss = has_gauss[i] ? 1 : 0;
-        h[i].gauss = has_gauss[i] ? gauss[i] : 0.0;
-    }
-    return streams_copy(s, h.data(), 0, s->n, false);
+    for (int64_t i = 0; i < s->n; ++i) HP_TRY(mt_state_fill(h[i], "hp_streams_set_all", i, keys + i * MT_N, pos[i], has_gauss[i], gauss[i]));
+    return mt_states_put(s, h.data(), 0, s->n);
 }
 
 void hp_streams_destroy(hp_rng_streams *s) {

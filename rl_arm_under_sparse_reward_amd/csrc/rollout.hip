@@ -106,18 +106,17 @@ __global__ __launch_bounds__(MW_THREADS) void k_rollout_step(const RolloutStepAr
         }
         return;
     }
-    MwState w;
-    mw_load(w, A.st, ring);
+    MwState w(A.st, ring);
     for (int i = 0; i < A.rows; ++i) ro_explore_row(A, w, zs, i);
-    mw_store(w, A.st);
+    w.store(A.st);
 }
 
 // The same step with one stream per environment (hp_rollout_step_streams): workgroup i < rows is the one wave that draws row i's
 // exploration out of stream i -- the draws of ro_explore_row, the code of the single-stream walk, on an LDS ring of its own --
 // and the workgroups behind them record the rows.  No wave loops over environments: the grid grows with the active rows, and
 // a partial wave leaves the streams behind it alone.  State traffic per environment and step: the key is read (2.5 KB); what is
-// written back is pos and the cached normal (16 bytes) unless the walk ended in a block generated here, which for 4 action
-// components (about 20 words a step) is one step in thirty -- only then is the key rewritten.
+// written back is pos and the cached normal (16 bytes) unless the walk ended in a block generated here (mt_commit's rule), which
+// for 4 action components (about 20 words a step) is one step in thirty -- only then is the key rewritten.
 __global__ __launch_bounds__(MW_THREADS) void k_rollout_step_streams(const RolloutStepArgs A) {
     __shared__ uint32_t ring[4][MT_N];
     __shared__ double zs[RO_MAX_ACT];
@@ -128,19 +127,9 @@ __global__ __launch_bounds__(MW_THREADS) void k_rollout_step_streams(const Rollo
     }
     const int i = blockIdx.x;
     MtState *st = A.st + i;
-    MwState w;
-    mw_load(w, st, ring);
+    MwState w(st, ring);
     ro_explore_row(A, w, zs, i);
-    int b, pos;
-    mt_final_block(w.g.cursor, b, pos);
-    __syncthreads();
-    if (b > 0)
-        for (int k = lane; k < MT_N; k += MW_THREADS) st->key[k] = ring[b & 3][k];
-    if (lane == 0) {
-        st->pos = pos;
-        st->has_gauss = w.has_gauss;
-        st->gauss = w.gauss;
-    }
+    w.store(st);
 }
 
 static int rollout_launch(hp_rollout *ro, RolloutStepArgs &A, int t, bool per_env_streams = false) {

@@ -22,6 +22,18 @@ import numpy as np
 from . import _lib
 
 
+def legacy_state(state):
+    """numpy's legacy state tuple (3 or 5 fields; numpy accepts the 3-tuple too) -> (key uint32 [624], pos, has_gauss, gauss);
+    the two refusals carry numpy's messages."""
+    if state[0] != "MT19937":
+        raise ValueError("set_state can only be used with legacy MT19937 state instances.")
+    key = np.ascontiguousarray(state[1], dtype=np.uint32)
+    if key.shape != (624,):
+        raise ValueError("state must be 624 longs")
+    has, val = (int(state[3]), float(state[4])) if len(state) >= 5 else (0, 0.0)
+    return key, int(state[2]), has, val
+
+
 class DeviceRandomState:
     def __init__(self, seed=None, ctx=None):
         self.ctx = ctx or _lib.Context.default()
@@ -72,20 +84,12 @@ class DeviceRandomState:
         return ("MT19937", key, int(pos.value), int(gauss[0]), float(gauss[1]))
 
     def set_state(self, state):
-        if isinstance(state, dict):
-            key, pos = state["state"]["key"], state["state"]["pos"]
-            gauss = (int(state.get("has_gauss", 0)), float(state.get("gauss", 0.0)))
-        else:
-            if state[0] != "MT19937":
-                raise ValueError("set_state can only be used with legacy MT19937 state instances.")
-            key, pos = state[1], state[2]
-            gauss = (int(state[3]), float(state[4])) if len(state) >= 5 else (0, 0.0)   # numpy accepts the 3-tuple too
-        key = np.ascontiguousarray(key, dtype=np.uint32)
-        if key.shape != (624,):
-            raise ValueError("state must be 624 longs")
-        _lib.check(self.lib.hp_rng_set_state(self.h, _lib.ptr(key, C.c_uint32), C.c_int32(int(pos))))
+        if isinstance(state, dict):     # numpy's dict form: its bit generator is not named by field 0 of a tuple
+            state = ("MT19937", state["state"]["key"], state["state"]["pos"], state.get("has_gauss", 0), state.get("gauss", 0.0))
+        key, pos, has, val = legacy_state(state)
+        _lib.check(self.lib.hp_rng_set_state(self.h, _lib.ptr(key, C.c_uint32), C.c_int32(pos)))
         self.seeded = True
-        self._gauss = gauss
+        self._gauss = (has, val)
 
     def advance(self, n_words):
         """Skip `n_words` 32-bit words as if they had been drawn and thrown away (hp_rng_advance): the state afterwards is
@@ -186,14 +190,9 @@ class DeviceRandomStreams:
         return ("MT19937", key, int(pos.value), int(has.value), float(val.value))
 
     def set_state(self, i, state):
-        if state[0] != "MT19937":
-            raise ValueError("set_state can only be used with legacy MT19937 state instances.")
-        key = np.ascontiguousarray(state[1], dtype=np.uint32)
-        if key.shape != (624,):
-            raise ValueError("state must be 624 longs")
-        has, val = (int(state[3]), float(state[4])) if len(state) >= 5 else (0, 0.0)
-        _lib.check(self.lib.hp_streams_set_state(self.h, C.c_int64(int(i)), _lib.ptr(key, C.c_uint32), C.c_int32(int(state[2])),
-                                                 C.c_int32(has), C.c_double(val)))
+        key, pos, has, val = legacy_state(state)
+        _lib.check(self.lib.hp_streams_set_state(self.h, C.c_int64(int(i)), _lib.ptr(key, C.c_uint32), C.c_int32(pos), C.c_int32(has),
+                                                 C.c_double(val)))
 
     def get_arrays(self):
         """All states as four arrays: keys uint32 [n, 624], pos int32 [n], has_gauss int32 [n], gauss float64 [n] (what a

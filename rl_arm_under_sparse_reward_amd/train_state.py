@@ -140,28 +140,33 @@ def read_state(path):
     return arrays, manifest
 
 
+def _check_array(where, name, arrays, listed, want, implied_by, sums, entry=True):
+    """One array of a state: present, listed in the manifest, of the dtype and shape `implied_by` implies (`want`) and
+    (entry=True) its manifest entry records, and (sums=True) summing to the (A, B) recorded there."""
+    if name not in arrays:
+        raise StateError(f"{where}: array '{name}' is missing")
+    if name not in listed:
+        raise StateError(f"{where}: manifest has no entry for array '{name}'")
+    a, (dt, shape) = arrays[name], want
+    if a.dtype.newbyteorder("<") != np.dtype(dt) or tuple(a.shape) != tuple(shape):
+        raise StateError(f"{where}: array '{name}' is {a.dtype} {tuple(a.shape)}, {implied_by} imply {np.dtype(dt)} {tuple(shape)}")
+    if entry and (listed[name]["dtype"] != dt or tuple(listed[name]["shape"]) != tuple(shape)):
+        raise StateError(f"{where}: manifest entry of array '{name}' ({listed[name]['dtype']} {tuple(listed[name]['shape'])}) "
+                         f"contradicts its dims ({dt} {tuple(shape)})")
+    if sums:
+        got, said = checksum(a), [int(x) for x in listed[name]["sum"]]
+        if list(got) != said:
+            raise StateError(f"{where}: array '{name}' sums to ({got[0]:016x}, {got[1]:016x}), the manifest says "
+                             f"({said[0]:016x}, {said[1]:016x})")
+
+
 def check_arrays(arrays, manifest, sums=True, where="state"):
     """Every device array present, shaped as the manifest's dims imply and as the manifest records, and (sums=True) its bytes
     summing to the manifest's (A, B).  Raises StateError naming the array."""
     want = expected_shapes(manifest["dims"])
     listed = manifest["arrays"]
     for name in DEVICE_ARRAYS:
-        if name not in arrays:
-            raise StateError(f"{where}: array '{name}' is missing")
-        if name not in listed:
-            raise StateError(f"{where}: manifest has no entry for array '{name}'")
-        a = arrays[name]
-        dt, shape = want[name]
-        if a.dtype.newbyteorder("<") != np.dtype(dt) or tuple(a.shape) != tuple(shape):
-            raise StateError(f"{where}: array '{name}' is {a.dtype} {tuple(a.shape)}, the manifest's dims imply {np.dtype(dt)} {tuple(shape)}")
-        if listed[name]["dtype"] != dt or tuple(listed[name]["shape"]) != tuple(shape):
-            raise StateError(f"{where}: manifest entry of array '{name}' ({listed[name]['dtype']} {tuple(listed[name]['shape'])}) "
-                             f"contradicts its dims ({dt} {tuple(shape)})")
-        if sums:
-            got = checksum(a)
-            if list(got) != [int(x) for x in listed[name]["sum"]]:
-                raise StateError(f"{where}: array '{name}' sums to ({got[0]:016x}, {got[1]:016x}), the manifest says "
-                                 f"({int(listed[name]['sum'][0]):016x}, {int(listed[name]['sum'][1]):016x})")
+        _check_array(where, name, arrays, listed, want[name], "the manifest's dims", sums)
     if int(arrays["buffer_counters"][0]) != int(manifest["dims"]["current_size"]):
         raise StateError(f"{where}: array 'buffer_counters' says current_size {int(arrays['buffer_counters'][0])}, "
                          f"the manifest {manifest['dims']['current_size']}")
@@ -183,17 +188,7 @@ def check_stream_arrays(arrays, manifest, where="state"):
         return
     want = stream_shapes(rec["n"])
     for name in STREAM_ARRAYS:
-        if name not in arrays:
-            raise StateError(f"{where}: array '{name}' is missing")
-        if name not in rec["arrays"]:
-            raise StateError(f"{where}: manifest has no entry for array '{name}'")
-        a, (dt, shape) = arrays[name], want[name]
-        if a.dtype.newbyteorder("<") != np.dtype(dt) or tuple(a.shape) != tuple(shape):
-            raise StateError(f"{where}: array '{name}' is {a.dtype} {tuple(a.shape)}, {rec['n']} streams imply {np.dtype(dt)} {tuple(shape)}")
-        got, listed = checksum(a), [int(x) for x in rec["arrays"][name]["sum"]]
-        if list(got) != listed:
-            raise StateError(f"{where}: array '{name}' sums to ({got[0]:016x}, {got[1]:016x}), the manifest says "
-                             f"({listed[0]:016x}, {listed[1]:016x})")
+        _check_array(where, name, arrays, rec["arrays"], want[name], f"{rec['n']} streams", True, entry=False)
     pos = arrays["explore_stream_pos"]
     if pos.size and (int(pos.min()) < 0 or int(pos.max()) > 624):
         raise StateError(f"{where}: array 'explore_stream_pos' holds a position outside [0, 624]")

@@ -29,3 +29,22 @@ def make_shape_episodes(n_eps, obs_dim, goal_dim, act_dim, T, seed=4):
     obs[:, :, :goal_dim] = rs.uniform(0, 0.5, (n_eps, 1, goal_dim)) + np.cumsum(rs.normal(0, 0.012, (n_eps, T + 1, goal_dim)), 1)
     return [obs, obs[:, :, :goal_dim].copy(), np.repeat(rs.uniform(0, 0.5, (n_eps, 1, goal_dim)), T, 1),
             rs.uniform(-0.5, 0.5, (n_eps, T, act_dim))]
+
+
+def ulp_distance(a, b):
+    ia, ib = a.view(np.int64).copy(), b.view(np.int64).copy()
+    ia[ia < 0] = np.int64(-2**63) - ia[ia < 0]
+    ib[ib < 0] = np.int64(-2**63) - ib[ib < 0]
+    return np.abs(ia - ib)
+
+
+def host_select_actions(rs, pi, noise_eps, random_eps, amax, clip):
+    """ddpg_agent._select_actions (:174-184) for one environment, drawing from the RandomState `rs`."""
+    action = pi.copy()
+    action += noise_eps * amax * rs.randn(*action.shape)
+    action = np.clip(action, -amax, amax)
+    ra = rs.uniform(low=-amax, high=amax, size=action.shape[0])
+    action += rs.binomial(1, random_eps, 1)[0] * (ra - action)
+    if clip:
+        action = np.clip(action, -0.15, 0.15)
+    return action

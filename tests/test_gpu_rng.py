@@ -1,10 +1,17 @@
 """Device MT19937 + numpy-legacy draws (csrc/mt19937_device.h) vs numpy RandomState and the
 golden index vectors the reference's her.py produced."""
+import ctypes as C
+import functools
+
 import numpy as np
 import pytest
+import torch
 
 from conftest import load_golden
-from gpu_common import DeviceEpisodeBuffer, fresh_rng, state_equal
+from gpu_common import DeviceEpisodeBuffer, ctx, fresh_rng, host_select_actions, state_equal, ulp_distance
+from rl_arm_under_sparse_reward_amd import _lib
+from rl_arm_under_sparse_reward_amd.device_env import DeviceEpisodes, binomial1_qn
+from rl_arm_under_sparse_reward_amd.random import DeviceRandomStreams
 
 pytestmark = pytest.mark.gpu
 
@@ -105,3 +112,80 @@ def test_rng_kat_golden_through_sampler():
         assert np.array_equal(idx["future_t"][her], g[tag + "_future_t"][her]), tag
         assert np.all((idx["future_t"] >= idx["t"] + 1) & (idx["future_t"] <= 100)), tag
         assert state_equal(dev, g[tag + "_key"], g[tag + "_pos"]), tag
+
+
+# ---- the commit of a walk: every draw from every kind of starting position -------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _generated_key():
+    """The key of RandomState(11) after 700 words: a generated block, not a seed key."""
+    rs = np.random.RandomState(11)
+    rs.bytes(4 * 700)
+    return rs.get_state()[1]
+
+
+def _forced(p):
+    return ("MT19937", _generated_key(), p, 0, 0.0)
+
+
+def _assert_committed_like_numpy(dev_state, rs, key_before, where):
+    """Key, pos and has_gauss are numpy's, the cached normal within 4 ulp; after a draw numpy finishes inside the loaded block (no
+    twist) the key still holds the loaded words (their content: a rewrite with the same words cannot be told from no write)."""
+    sn = rs.get_state()
+    assert np.array_equal(dev_state[1], sn[1]) and dev_state[2] == sn[2] and dev_state[3] == sn[3], where
+    assert int(ulp_distance(np.float64([dev_state[4]]), np.float64([sn[4]])).max()) <= 4, where
+    if np.array_equal(sn[1], key_before):
+        assert sn[2] <= 624 and np.array_equal(dev_state[1], key_before), where
+
+
+@pytest.mark.parametrize("p", [0, 1, 311, 620, 621, 622, 623, 624])
+def test_every_draw_commits_numpys_state_from_every_start(p):
+    """Each draw hook and advance(), each from a stream forced to position p of a generated key: words that end inside the loaded
+    block, exactly on its boundary (pos == 624), one word behind it and two blocks on.  Values: integers, uniforms and binomials
+    equal numpy's, normals within 4 ulp (the bar of test_draw_hooks_follow_numpy)."""
+    draws = [("randint", n) for n in (1, 624 - p, 625 - p, 1248 - p)] + [("uniform", n) for n in (1, 312)]
+    draws += [("standard_normal", n) for n in (1, 2, 3, 400)] + [("binomial1", n) for n in (1, 400)]
+    draws += [("advance", n) for n in (1, 624 - p, 625 - p)]
+    dev, rs = fresh_rng(0), np.random.RandomState(0)
+    for name, n in draws:
+        if n <= 0:
+            continue
+        dev.set_state(_forced(p)); rs.set_state(_forced(p))
+        if name == "randint":
+            assert np.array_equal(dev.randint(0, 2**16, n), rs.randint(0, 2**16, n)), (p, name, n)
+        elif name == "uniform":
+            assert np.array_equal(dev.uniform(n), rs.random_sample(n)), (p, name, n)
+        elif name == "standard_normal":
+            assert int(ulp_distance(dev.standard_normal(n), rs.randn(n)).max()) <= 4, (p, name, n)
+        elif name == "binomial1":
+            assert np.array_equal(dev.binomial1(0.3, n), rs.binomial(1, 0.3, n)), (p, name, n)
+        else:
+            dev.advance(n); rs.bytes(4 * n)
+        _assert_committed_like_numpy(dev.get_state(), rs, _generated_key(), (p, name, n))
+
+
+def test_per_environment_streams_commit_numpys_state():
+    """One teacher-forced exploring step of two per-environment streams, stream 0 started at position 0 (the walk ends inside
+    the loaded key) and stream 1 at 623 (it leaves it): states as above, actions within one float32 spacing of
+    `_select_actions` driven by each stream's own RandomState."""
+    od, gd, ad, T, noise_eps, random_eps, amax = 10, 2, 4, 2, 0.2, 0.3, 0.5
+    c = ctx()
+    buf = DeviceEpisodeBuffer(4, T, od, gd, ad, ctx=c)
+    eps = DeviceEpisodes(c, buf, 2)
+    _lib.check(c.lib.hp_rollout_set_action_max(eps.h, amax))
+    streams, host = DeviceRandomStreams(2, base_seed=1, ctx=c), [np.random.RandomState(0), np.random.RandomState(0)]
+    for i, start in enumerate((0, 623)):
+        streams.set_state(i, _forced(start)); host[i].set_state(_forced(start))
+    prs = np.random.RandomState(1)
+    pi = prs.uniform(-0.6, 0.6, (2, ad)).astype(np.float32)
+    o, a, g = (torch.from_numpy(prs.uniform(-1, 1, (2, d))).to("cuda:0") for d in (od, gd, gd))
+    act = torch.from_numpy(pi).to("cuda:0")
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    with c.torch_bridge():
+        _lib.check(c.lib.hp_rollout_step_streams(eps.h, None, None, None, streams.h, 0, ptr(o), ptr(a), ptr(g), 1, noise_eps, random_eps,
+                                                 binomial1_qn(random_eps)[0], 0.0, ptr(act)))
+    want = np.stack([host_select_actions(host[i], pi[i], noise_eps, random_eps, amax, False) for i in range(2)])
+    got = act.cpu().numpy()
+    assert want.dtype == np.float32 and np.all(np.abs(got.astype(np.float64) - want) <= np.spacing(np.abs(want)))
+    for i in range(2):
+        _assert_committed_like_numpy(streams.get_state(i), host[i], _generated_key(), i)
+    assert np.array_equal(host[0].get_state()[1], _generated_key()) and not np.array_equal(host[1].get_state()[1], _generated_key())
