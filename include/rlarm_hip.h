@@ -532,6 +532,34 @@ int hp_state_fetch(hp_agent *ag, uint64_t ticket, int32_t wait, void *host_out, 
  * does, the float32 throughput rows when the buffer has them.  Synchronises. */
 int hp_state_restore(hp_agent *ag, hp_buffer *buf, hp_norm *o_norm, hp_norm *g_norm, hp_rng *rng, const hp_state_dims *dims,
                      const void *host_in, size_t bytes, const uint64_t *sums);
+/* ---- delta states: the buffer as the episodes written since a base capture -----------------------------------
+ * The buffer keeps a uint32 stamp per slot and one device word, the capture epoch (1 at creation).  Every scatter of an episode
+ * (hp_buffer_store*, hp_agent_train_cycle*, eager or inside a cached graph) stamps its slot with the epoch it READS from device
+ * memory; every capture, full or delta, records `capture_epoch = epoch` in stream order and then advances the epoch.  Stamps are
+ * absolute: a slot is dirty with respect to a capture c iff its stamp is > c, so a capture that is never fetched loses nothing.
+ * hp_state_restore zeroes the stamps, makes `min_since` a value larger than any epoch handed out before and leaves the epoch at
+ * min_since + 1: the restored state itself stands for a capture with epoch min_since.
+ * A delta blob has HP_STATE_DELTA_SECTIONS sections: the 27 small ones of a full state (actor .. rng_pos) under the same names, then
+ *   buffer_delta_header  int64 [4] = n_dirty, overflow, capture_epoch, since_epoch
+ *   buffer_delta_slots   int64 [max_dirty]: the slots in [0, current_size) with stamp > since_epoch, ascending; n_dirty are used
+ *   buffer_delta_{obs,ag,g,actions}   float64 [max_dirty][...]: the rows of those slots, in that order; n_dirty episodes are used
+ *   buffer_counters      int64 [2]
+ * The slot and row sections are summed over their used prefix. */
+#define HP_STATE_DELTA_SECTIONS 34
+/* Sections of a delta sized for `max_dirty` episodes.  out may be NULL; *n: in, room in out; out, HP_STATE_DELTA_SECTIONS. */
+int hp_state_layout_delta(hp_agent *ag, hp_buffer *buf, hp_norm *o_norm, hp_norm *g_norm, int64_t max_dirty, hp_state_section *out,
+                          int32_t *n, size_t *total_bytes);
+/* As hp_state_capture, with the buffer captured as the slots written since the capture `since_epoch` (dirty scan + row pack on the
+ * context's stream).  max_dirty in [0, current_size] bounds the episodes the blob has room for: the caller passes min(episodes
+ * stored since that capture, current_size).  since_epoch below the buffer's min_since, or not below its epoch, is refused with
+ * HP_ERR_STATE before anything is enqueued.  Shares the one-capture-at-a-time rule and hp_state_fetch with hp_state_capture; the
+ * `sums` given to hp_state_fetch must then hold 2 * HP_STATE_DELTA_SECTIONS words.  A delta that found more than max_dirty dirty
+ * slots makes hp_state_fetch fail with HP_ERR_STATE (the ticket is retired, nothing is delivered). */
+int hp_state_capture_delta(hp_agent *ag, hp_buffer *buf, hp_norm *o_norm, hp_norm *g_norm, hp_rng *rng, uint32_t since_epoch,
+                           int64_t max_dirty, uint64_t *ticket, size_t *bytes);
+/* The epochs, from the host mirror (no wait): *capture_epoch = what this agent's most recent capture recorded (0: none yet),
+ * *epoch = the buffer's current epoch, *min_since = the smallest since_epoch a delta capture accepts.  Any pointer may be NULL. */
+int hp_state_epochs(hp_agent *ag, hp_buffer *buf, uint32_t *capture_epoch, uint32_t *epoch, uint32_t *min_since);
 /* The checksum kernel on any device memory (8-byte aligned): out2 = (A, B).  blocks = 0: the library's grid, else that many
  * workgroups (the result does not depend on it).  Synchronises. */
 int hp_state_checksum_dev(hp_ctx *ctx, const void *dev, size_t bytes, int32_t blocks, uint64_t *out2);

@@ -72,6 +72,13 @@ int hp_agent_update_kernels(hp_agent *ag, hp_buffer *buf, hp_norm *o_norm, hp_no
  * -DSLAB_TIMELINE writes them (tools/ubench/), a production build returns zeros */
 int hp_agent_debug_timeline(hp_agent *ag, uint64_t *out192);
 
+/* test hook: the dirty scan of a delta capture alone.  REPLACES the buffer's per-slot stamps with stamps_host[0 .. capacity), then
+ * finds the slots in [0, current_size) whose stamp is > since, ascending: slots_out[0 .. min(*n_dirty, max_dirty)), *n_dirty = how
+ * many there are, *overflow = (*n_dirty > max_dirty).  Count, scan, emit over chunks of HP_STATE_DIRTY_CHUNK slots.  Synchronises. */
+#define HP_STATE_DIRTY_CHUNK 2048
+int hp_state_debug_dirty_scan(hp_buffer *buf, const uint32_t *stamps_host, int64_t current_size, uint32_t since, int64_t max_dirty,
+                              int64_t *slots_out, int64_t *n_dirty, int32_t *overflow);
+
 /* diagnostic: a ~200 us calibration of the box this process landed on, so that a slow box can be told from a regression in a
  * bench line (about one box in seven of the pool ran every kernel of this path ~1.4 x slower at the same shader clock):
  *   out[0] launch floor, us per dependent trivial kernel in a captured hipGraph

@@ -56,6 +56,8 @@ class StateDims(C.Structure):
 
 
 STATE_SECTIONS = 32  # HP_STATE_SECTIONS
+STATE_DELTA_SECTIONS = 34   # HP_STATE_DELTA_SECTIONS
+STATE_DIRTY_CHUNK = 2048    # HP_STATE_DIRTY_CHUNK (rlarm_hip_debug.h): slots per workgroup of a delta capture's dirty scan
 ABI_VERSION = 4     # HP_ABI_VERSION of include/rlarm_hip.h this table binds
 PARALLEL_DRAW_MIN_BATCH = 65536   # HP_PARALLEL_DRAW_MIN_BATCH: the measured crossover of the parallel index draw
 
@@ -63,6 +65,7 @@ PARALLEL_DRAW_MIN_BATCH = 65536   # HP_PARALLEL_DRAW_MIN_BATCH: the measured cro
 DEBUG_SYMBOLS = {"hp_ctx_launch_floor", "hp_ctx_event_pair_us", "hp_ctx_clock_mhz", "hp_ctx_calibrate", "hp_buffer_sample_device_us",
                  "hp_buffer_sample_dev_us", "hp_buffer_sample_dev_fast_us",
                  "hp_mt_jump_poly", "hp_rng_parallel_info", "hp_rng_debug_set_window", "hp_rng_debug_table_ms",
+                 "hp_state_debug_dirty_scan",
                  "hp_agent_set_adam", "hp_agent_debug_chain", "hp_agent_debug_timeline", "hp_agent_update_kernels"}
 
 # name -> (restype, argtypes); every symbol declared in include/rlarm_hip.h and include/rlarm_hip_debug.h
@@ -227,6 +230,13 @@ PROTOTYPES = {
                                  C.POINTER(C.c_int32)]),
     "hp_state_restore": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StateDims), C.c_void_p,
                                    C.c_size_t, C.POINTER(C.c_uint64)]),
+    "hp_state_layout_delta": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(StateSection),
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    "hp_state_capture_delta": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64,
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)]),
+    "hp_state_epochs": (C.c_int, [C.c_void_p, C.c_void_p, u32p, u32p, u32p]),
+    "hp_state_debug_dirty_scan": (C.c_int, [C.c_void_p, u32p, C.c_int64, C.c_uint32, C.c_int64, i64p, i64p,
+                                            C.POINTER(C.c_int32)]),
     "hp_state_checksum_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_uint64)]),
 }
 

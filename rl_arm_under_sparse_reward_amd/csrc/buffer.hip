@@ -532,11 +532,12 @@ __global__ __launch_bounds__(256) void k_store_scatter(const long long *__restri
                                                        const double *s_obs, const double *s_ag, const double *s_g,
                                                        const double *s_act, double *obs, double *ag, double *g,
                                                        double *act, long long ep_obs, long long ep_ag,
-                                                       long long ep_g, long long ep_act) {
+                                                       long long ep_g, long long ep_act, uint32_t *slot_epoch,
+                                                       const uint32_t *epoch) {
     // STORE_PARTS workgroups per episode, each a strided share of its values: one or two copies per thread instead of a
     // loop of fifteen dependent-latency iterations (the copy of 2 episodes was 9.6 us of every cycle)
     store_scatter_share([&](long long j) { return slots[j]; }, blockIdx.x / STORE_PARTS, blockIdx.x % STORE_PARTS, STORE_PARTS,
-                        n_new, s_obs, s_ag, s_g, s_act, obs, ag, g, act, ep_obs, ep_ag, ep_g, ep_act);
+                        n_new, s_obs, s_ag, s_g, s_act, obs, ag, g, act, ep_obs, ep_ag, ep_g, ep_act, slot_epoch, epoch);
 }
 
 // ------------------------------------------------------------------------------ launchers
@@ -612,7 +613,7 @@ int buffer_stage_and_store(hp_buffer *b, hp_rng *rng, const double *obs, const d
     hipLaunchKernelGGL(k_store_scatter, dim3((unsigned)(n_new * STORE_PARTS)), dim3(256), 0, s, b->st_slots.as<long long>(),
                        (long long)n_new, b->st_obs.as<double>(), b->st_ag, b->st_g,
                        b->st_act, b->d_obs, b->d_ag, b->d_g, b->d_act, (long long)b->ep_obs(),
-                       (long long)b->ep_ag(), (long long)b->ep_g(), (long long)b->ep_act());
+                       (long long)b->ep_ag(), (long long)b->ep_g(), (long long)b->ep_act(), b->d_slot_epoch, b->d_epoch);
     HP_CHECK_HIP(hipGetLastError());
     HP_TRY(buffer_launch_pack(b, n_new));
     // host mirror of replay_buffer.py:68 and :43
@@ -648,7 +649,7 @@ int buffer_stage_pinned(hp_buffer *b, hp_rng *rng, const double *block, int64_t 
         HP_TRY(rng_launch_slots(rng, b, n_new, b->st_slots.as<int64_t>()));
         hipLaunchKernelGGL(k_store_scatter, dim3((unsigned)(n_new * STORE_PARTS)), dim3(256), 0, s, b->st_slots.as<long long>(),
                            (long long)n_new, b->st_obs.as<double>(), b->st_ag, b->st_g, b->st_act, b->d_obs, b->d_ag, b->d_g,
-                           b->d_act, (long long)b->ep_obs(), (long long)b->ep_ag(), (long long)b->ep_g(), (long long)b->ep_act());
+                           b->d_act, (long long)b->ep_obs(), (long long)b->ep_ag(), (long long)b->ep_g(), (long long)b->ep_act(), b->d_slot_epoch, b->d_epoch);
         HP_CHECK_HIP(hipGetLastError());
         HP_TRY(buffer_launch_pack(b, n_new));
     }
@@ -675,7 +676,7 @@ int buffer_stage_dev(hp_buffer *b, hp_rng *rng, const double *block_dev, int64_t
         HP_TRY(rng_launch_slots(rng, b, n_new, b->st_slots.as<int64_t>()));
         hipLaunchKernelGGL(k_store_scatter, dim3((unsigned)(n_new * STORE_PARTS)), dim3(256), 0, s, b->st_slots.as<long long>(),
                            (long long)n_new, b->st_obs.as<double>(), b->st_ag, b->st_g, b->st_act, b->d_obs, b->d_ag, b->d_g,
-                           b->d_act, (long long)b->ep_obs(), (long long)b->ep_ag(), (long long)b->ep_g(), (long long)b->ep_act());
+                           b->d_act, (long long)b->ep_obs(), (long long)b->ep_ag(), (long long)b->ep_g(), (long long)b->ep_act(), b->d_slot_epoch, b->d_epoch);
         HP_CHECK_HIP(hipGetLastError());
         HP_TRY(buffer_launch_pack(b, n_new));
     }
@@ -717,6 +718,11 @@ int hp_buffer_create(hp_ctx *ctx, int64_t size_episodes, int32_t T, int32_t obs_
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_act, size_episodes * b->ep_act() * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_meta, sizeof(BufMeta));
     if (e == hipSuccess) e = hipMemsetAsync(b->d_meta, 0, sizeof(BufMeta), ctx->stream);
+    // who wrote which slot, and when (state.hip: delta states): a stamp per slot, the capture epoch in an allocation of its own
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_slot_epoch, size_episodes * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_slot_epoch, 0, size_episodes * sizeof(uint32_t), ctx->stream);
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_epoch, sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)b->d_epoch, (int)b->epoch, 1, ctx->stream);
     if (e != hipSuccess) {
         hp_set_error("hp_buffer_create: device allocation failed: %s", hipGetErrorString(e));
         hp_buffer_destroy(b);
@@ -1268,6 +1274,9 @@ void hp_buffer_destroy(hp_buffer *b) {
     if (b->d_g) (void)hipFree(b->d_g);
     if (b->d_act) (void)hipFree(b->d_act);
     if (b->d_meta) (void)hipFree(b->d_meta);
+    if (b->d_slot_epoch) (void)hipFree(b->d_slot_epoch);
+    if (b->d_epoch) (void)hipFree(b->d_epoch);
+    b->dirty_counts.release();
     if (b->p_row) (void)hipFree(b->p_row);
     if (b->p_goal) (void)hipFree(b->p_goal);
     for (hipEvent_t ev : b->pin_events)

@@ -41,6 +41,8 @@ struct OpenArgs {
     const double *s_obs, *s_ag, *s_g, *s_act;
     double *obs, *ag, *g, *act;
     long long ep_obs, ep_ag, ep_g, ep_act;
+    uint32_t *slot_epoch;         // per-slot stamp and the capture epoch it takes (addresses fixed at hp_buffer_create)
+    const uint32_t *epoch;
     // normalizer
     NormDev *onz, *gnz;
     int obs_dim, goal_dim;
@@ -121,7 +123,7 @@ __global__ __launch_bounds__(OPEN_THREADS) void k_cycle_open(const OpenArgs A) {
         if (open_wait(A.sync + 0, A))
         store_scatter_share([&](long long j) { return __hip_atomic_load(A.slots + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
                             w / OPEN_PARTS, w % OPEN_PARTS, OPEN_PARTS, A.inc, A.s_obs, A.s_ag, A.s_g, A.s_act, A.obs, A.ag, A.g,
-                            A.act, A.ep_obs, A.ep_ag, A.ep_g, A.ep_act);
+                            A.act, A.ep_obs, A.ep_ag, A.ep_g, A.ep_act, A.slot_epoch, A.epoch);
         if (threadIdx.x == 0) open_leave(A.sync);
     }
 }
@@ -158,6 +160,8 @@ int cycle_open_launch(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rn
     A.ep_ag = b->ep_ag();
     A.ep_g = b->ep_g();
     A.ep_act = b->ep_act();
+    A.slot_epoch = b->d_slot_epoch;
+    A.epoch = b->d_epoch;
     A.onz = on->d;
     A.gnz = gn->d;
     A.obs_dim = b->obs_dim;

@@ -236,6 +236,13 @@ struct hp_buffer {
     int32_t T = 0, obs_dim = 0, goal_dim = 0, act_dim = 0;
     double *d_obs = nullptr, *d_ag = nullptr, *d_g = nullptr, *d_act = nullptr;
     BufMeta *d_meta = nullptr;
+    // Delta states (state.hip).  slot_epoch[slot] = the value of *d_epoch when the slot was last scattered into (0: never, or not
+    // since the last restore); every capture records *d_epoch and then advances it, so a slot is dirty with respect to a capture c
+    // iff its stamp is > c.  The scatter kernels read *d_epoch at run time (store_device.h).  epoch mirrors *d_epoch (only captures
+    // and restores move it, all enqueued by the host); stamps older than min_since were zeroed by a restore.
+    uint32_t *d_slot_epoch = nullptr, *d_epoch = nullptr;
+    uint32_t epoch = 1, min_since = 0;
+    DevBuf dirty_counts;   // per-chunk counts of the dirty scan
     // host mirror (slot policy is deterministic given n_new, so the host can track it)
     int64_t current_size = 0, n_transitions_stored = 0;
     // staging of the most recent store_episode batch (also the source of _update_normalizer)

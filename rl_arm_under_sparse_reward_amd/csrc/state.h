@@ -16,6 +16,20 @@ enum {
     ST_BUF_COUNTERS,                                                     // int64 [2]: current_size, n_transitions_stored
     ST_SECTIONS = 32
 };
+// Sections of a DELTA state (hp_state_layout_delta): the small sections ST_ACTOR .. ST_RNG_POS at the same indices, then the buffer
+// as the episodes written since a base capture.
+enum {
+    DS_HEADER = ST_RNG_POS + 1,                                          // int64 [4]: n_dirty, overflow, capture_epoch, since_epoch
+    DS_SLOTS,                                                            // int64 [max_dirty]: the dirty slots, ascending
+    DS_OBS, DS_AG, DS_G, DS_ACT,                                         // float64 rows of those slots, packed [max_dirty][...]
+    DS_COUNTERS,                                                         // int64 [2], as ST_BUF_COUNTERS
+    DS_SECTIONS = 34
+};
+static_assert(DS_COUNTERS + 1 == DS_SECTIONS && DS_SECTIONS == HP_STATE_DELTA_SECTIONS, "delta section count");
+#define DS_CHUNK_THREADS 256
+#define DS_CHUNK_ITEMS 8
+#define DS_CHUNK (DS_CHUNK_THREADS * DS_CHUNK_ITEMS)                     // slots per workgroup of the dirty scan
+static_assert(DS_CHUNK == HP_STATE_DIRTY_CHUNK, "rlarm_hip_debug.h names the chunk for the scan's test");
 enum { NF_LOCAL_SUM = 0, NF_LOCAL_SUMSQ, NF_LOCAL_COUNT, NF_TOTAL_SUM, NF_TOTAL_SUMSQ, NF_TOTAL_COUNT, NF_MEAN, NF_STD, NORM_FIELDS };
 enum { SD_F32 = 0, SD_F64 = 1, SD_I64 = 2, SD_U32 = 3, SD_I32 = 4 };   // hp_state_section::dtype
 

@@ -6,10 +6,13 @@
 //             drain stream: wait(event) | k_checksum per section | chunked copies to pinned memory | event
 //   restore   upload into the SAME arena | k_checksum per section, compared with the caller's sums | only then: k_state_flat /
 //             k_state_small / row copies the other way, relayout of both parameter sets, throughput rows, host mirrors
+//   delta     as capture, with the buffer captured as the slots stamped since a base capture: k_dirty_count | k_dirty_scan |
+//             k_dirty_emit (ascending slot list) | k_delta_pack (their rows) instead of the four whole-array copies
 #include "state.h"
 
 typedef unsigned long long u64;
 typedef u64 u64x2 __attribute__((ext_vector_type(2)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 #define ST_ALIGN 256                    // section offsets in the blob
 #define ST_DRAIN_CHUNK (16u << 20)      // bytes per copy of the drain
@@ -17,7 +20,7 @@ typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 struct StateArena {
     char *dev = nullptr;          // the snapshot (capture) / the uploaded state (restore)
     size_t dev_bytes = 0;
-    u64 *d_sums = nullptr;        // 2 * ST_SECTIONS: (A, B) per section
+    u64 *d_sums = nullptr;        // 2 * DS_SECTIONS: (A, B) per section (a full state uses the first 2 * ST_SECTIONS)
     char *pin = nullptr;          // pinned host copy of the snapshot, filled by the drain
     size_t pin_bytes = 0;
     u64 *pin_sums = nullptr;
@@ -26,6 +29,9 @@ struct StateArena {
     uint64_t ticket = 0;          // of the most recent capture
     bool pending = false;         // ... which has not been fetched (or abandoned) yet
     size_t bytes = 0;             // ... and its blob size
+    int n_sections = ST_SECTIONS; // ... and its section count: ST_SECTIONS (full) or DS_SECTIONS (delta)
+    size_t hdr_off = 0;           // ... a delta's header section in the blob
+    uint32_t capture_epoch = 0;   // the buffer epoch the most recent capture recorded (host mirror)
 };
 
 // ------------------------------------------------------------------------------- kernels
@@ -39,7 +45,7 @@ __device__ __forceinline__ void sum_pair(const u64x2 x, u64 i0, u64 &a, u64 &b) 
     b += (i0 + 1ull) * x.x + (i0 + 2ull) * x.y;
 }
 
-__global__ __launch_bounds__(256) void k_checksum(const u64 *__restrict__ w, u64 nwords, unsigned tail_bytes, u64 *out) {
+__device__ __forceinline__ void checksum_body(const u64 *__restrict__ w, u64 nwords, unsigned tail_bytes, u64 *out) {
     const u64 head = (nwords > 0 && ((uintptr_t)w & 8u)) ? 1ull : 0ull;
     const u64x2 *v = reinterpret_cast<const u64x2 *>(w + head);
     const u64 npairs = (nwords - head) / 2;
@@ -80,6 +86,17 @@ __global__ __launch_bounds__(256) void k_checksum(const u64 *__restrict__ w, u64
         if (a) atomicAdd(out, a);
         if (b) atomicAdd(out + 1, b);
     }
+}
+
+__global__ __launch_bounds__(256) void k_checksum(const u64 *__restrict__ w, u64 nwords, unsigned tail_bytes, u64 *out) {
+    checksum_body(w, nwords, tail_bytes, out);
+}
+
+// the used prefix of a delta's slot list or packed rows: hdr[0] episodes (never more than the section has room for)
+__global__ __launch_bounds__(256) void k_checksum_prefix(const u64 *__restrict__ w, const long long *__restrict__ hdr,
+                                                         u64 words_per_ep, long long max_dirty, u64 *out) {
+    const long long n = hdr[0] < max_dirty ? hdr[0] : max_dirty;
+    checksum_body(w, (u64)n * words_per_ep, 0u, out);
 }
 
 // eight parameter-shaped vectors between the padded arena and the reference's flat order: blockIdx.y = vector
@@ -148,6 +165,138 @@ template <bool RESTORE> __global__ __launch_bounds__(256) void k_state_small(con
     }
 }
 
+// ---- delta: which slots were written since a capture, and their rows
+// Dirty scan: the slots in [0, cs) whose stamp is > since, ascending.  Count per chunk of DS_CHUNK slots, exclusive scan of the
+// counts by one workgroup (capacities go to 2^31 slots = 2^20 chunks; 5 000 slots are 3), emit.  Within a chunk a thread looks at
+// slot chunk * DS_CHUNK + it * 256 + tid, so (it, wave, lane) order is slot order.
+struct DirtyArgs {
+    const uint32_t *stamp;
+    long long cs;          // slots scanned (the buffer's current_size)
+    uint32_t since;
+    long long max_dirty;   // room in `slots`
+    long long *counts;     // [n_chunks]: counts, then (k_dirty_scan) the number of dirty slots in front of each chunk
+    long long n_chunks;
+    long long *hdr;        // [0] n_dirty, [1] overflow
+    long long *slots;
+};
+
+__device__ __forceinline__ bool dirty_at(const DirtyArgs &A, long long slot) { return slot < A.cs && A.stamp[slot] > A.since; }
+
+__global__ __launch_bounds__(DS_CHUNK_THREADS) void k_dirty_count(const DirtyArgs A) {
+    __shared__ int wave_n[DS_CHUNK_THREADS / 64];
+    const long long first = (long long)blockIdx.x * DS_CHUNK;
+    int n = 0;
+#pragma unroll
+    for (int it = 0; it < DS_CHUNK_ITEMS; ++it)
+        n += __popcll(__ballot(dirty_at(A, first + it * DS_CHUNK_THREADS + threadIdx.x)));
+    if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) A.counts[blockIdx.x] = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+}
+
+__global__ __launch_bounds__(256) void k_dirty_scan(const DirtyArgs A) {
+    __shared__ long long wave_tot[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    long long carry = 0;
+    for (long long base = 0; base < A.n_chunks; base += 256) {
+        const long long j = base + tid;
+        const long long v = j < A.n_chunks ? A.counts[j] : 0;
+        long long x = v;
+        for (int o = 1; o < 64; o <<= 1) {
+            const long long y = __shfl_up(x, o);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) wave_tot[wave] = x;
+        __syncthreads();
+        long long pre = 0;
+        for (int k = 0; k < wave; ++k) pre += wave_tot[k];
+        if (j < A.n_chunks) A.counts[j] = carry + pre + x - v;
+        carry += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        A.hdr[0] = carry;
+        A.hdr[1] = carry > A.max_dirty ? 1 : 0;   // the caller's bound was wrong: nothing past it is emitted, fetch refuses
+    }
+}
+
+__global__ __launch_bounds__(DS_CHUNK_THREADS) void k_dirty_emit(const DirtyArgs A) {
+    __shared__ int wave_n[DS_CHUNK_ITEMS][DS_CHUNK_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long first = (long long)blockIdx.x * DS_CHUNK;
+    u64 bal[DS_CHUNK_ITEMS];
+#pragma unroll
+    for (int it = 0; it < DS_CHUNK_ITEMS; ++it) {
+        bal[it] = __ballot(dirty_at(A, first + it * DS_CHUNK_THREADS + tid));
+        if (lane == 0) wave_n[it][wave] = __popcll(bal[it]);
+    }
+    __syncthreads();
+    long long pos = A.counts[blockIdx.x];
+#pragma unroll
+    for (int it = 0; it < DS_CHUNK_ITEMS; ++it) {
+        int before = 0, all = 0;
+        for (int w = 0; w < DS_CHUNK_THREADS / 64; ++w) {
+            if (w < wave) before += wave_n[it][w];
+            all += wave_n[it][w];
+        }
+        if ((bal[it] >> lane) & 1ull) {
+            const long long at = pos + before + __popcll(bal[it] & ((1ull << lane) - 1ull));
+            if (at < A.max_dirty) A.slots[at] = first + it * DS_CHUNK_THREADS + tid;
+        }
+        pos += all;
+    }
+}
+
+// Row pack: episode e of the delta = the rows of slot slots[e], for the four arrays.  DS_PACK_PARTS workgroups share an episode;
+// the grid strides over the n_dirty episodes the scan found (read from the header: the host does not know the count).  Rows start
+// on 8-byte boundaries, (T + 1) * dim doubles long: where source and destination agree on their offset mod 16 the body is 16-byte
+// loads and stores (behind a leading word when both sit at 8 mod 16), otherwise word by word.
+#define DS_PACK_PARTS 4
+struct PackArgs {
+    const long long *hdr, *slots;
+    long long max_dirty;
+    const double *src[4];
+    double *dst[4];
+    long long ep[4];
+};
+
+__device__ __forceinline__ void copy_row(double *__restrict__ d, const double *__restrict__ s, long long n, long long t0, long long step) {
+    const unsigned ms = (unsigned)(((uintptr_t)s >> 3) & 1u), md = (unsigned)(((uintptr_t)d >> 3) & 1u);
+    if (ms != md) {
+        for (long long k = t0; k < n; k += step) d[k] = s[k];
+        return;
+    }
+    const long long head = (ms && n > 0) ? 1 : 0, npairs = (n - head) / 2;
+    const f64x2 *sv = reinterpret_cast<const f64x2 *>(s + head);
+    f64x2 *dv = reinterpret_cast<f64x2 *>(d + head);
+    for (long long p = t0; p < npairs; p += step) dv[p] = sv[p];
+    if (t0 == 0) {
+        if (head) d[0] = s[0];
+        if ((n - head) & 1) d[n - 1] = s[n - 1];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_delta_pack(const PackArgs A) {
+    const long long n = A.hdr[0] < A.max_dirty ? A.hdr[0] : A.max_dirty;
+    const int part = blockIdx.x % DS_PACK_PARTS;
+    const long long t0 = (long long)part * blockDim.x + threadIdx.x, step = (long long)DS_PACK_PARTS * blockDim.x;
+    for (long long e = blockIdx.x / DS_PACK_PARTS; e < n; e += gridDim.x / DS_PACK_PARTS) {
+        const long long slot = A.slots[e];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) copy_row(A.dst[k] + e * A.ep[k], A.src[k] + slot * A.ep[k], A.ep[k], t0, step);
+    }
+}
+
+// a capture records the buffer's epoch and advances it, in stream order: what is scattered behind it is stamped with the new value
+__global__ void k_epoch_advance(uint32_t *epoch, long long *hdr, long long since) {
+    const uint32_t e = *epoch;
+    if (hdr) {
+        hdr[2] = (long long)e;
+        hdr[3] = since;
+    }
+    *epoch = e + 1u;
+}
+
 // ------------------------------------------------------------------------------- host side
 static FlatMap flat_map(const hp_agent *a, bool critic) {
     const NetLayout &l = critic ? a->lc : a->la;
@@ -206,6 +355,34 @@ static size_t state_layout(const hp_agent *a, const hp_buffer *b, const hp_norm 
     return off;
 }
 
+// a delta with room for max_dirty episodes: the small sections of a full state at their indices, then DS_HEADER .. DS_COUNTERS
+static size_t delta_layout(const hp_agent *a, const hp_buffer *b, const hp_norm *on, const hp_norm *gn, int64_t max_dirty,
+                           hp_state_section *S) {
+    hp_state_section F[ST_SECTIONS];
+    (void)state_layout(a, b, on, gn, 0, F);
+    memset(S, 0, sizeof(hp_state_section) * DS_SECTIONS);
+    memcpy(S, F, sizeof(hp_state_section) * (ST_RNG_POS + 1));
+    auto set = [&](int i, const char *name, int dtype, int64_t count) {
+        snprintf(S[i].name, sizeof(S[i].name), "%s", name);
+        S[i].dtype = dtype;
+        S[i].elem_bytes = k_elem_bytes[dtype];
+        S[i].count = count;
+    };
+    set(DS_HEADER, "buffer_delta_header", SD_I64, 4);
+    set(DS_SLOTS, "buffer_delta_slots", SD_I64, max_dirty);
+    set(DS_OBS, "buffer_delta_obs", SD_F64, max_dirty * (int64_t)b->ep_obs());
+    set(DS_AG, "buffer_delta_ag", SD_F64, max_dirty * (int64_t)b->ep_ag());
+    set(DS_G, "buffer_delta_g", SD_F64, max_dirty * (int64_t)b->ep_g());
+    set(DS_ACT, "buffer_delta_actions", SD_F64, max_dirty * (int64_t)b->ep_act());
+    set(DS_COUNTERS, "buffer_counters", SD_I64, 2);
+    size_t off = 0;
+    for (int i = 0; i < DS_SECTIONS; ++i) {
+        S[i].offset = (int64_t)off;
+        off += ((size_t)S[i].count * S[i].elem_bytes + ST_ALIGN - 1) / ST_ALIGN * ST_ALIGN;
+    }
+    return off;
+}
+
 static int state_handles(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, const char *who) {
     HP_REQUIRE(a && b && on && gn && rng, HP_ERR_INVALID, "%s: null handle", who);
     HP_REQUIRE(b->ctx == a->ctx && on->ctx == a->ctx && gn->ctx == a->ctx && rng->ctx == a->ctx, HP_ERR_INVALID,
@@ -224,8 +401,8 @@ static int arena_get(hp_agent *a, StateArena **out) {
         HP_CHECK_HIP(hipStreamCreateWithFlags(&A->drain, hipStreamNonBlocking));
         HP_CHECK_HIP(hipEventCreateWithFlags(&A->captured, hipEventDisableTiming));
         HP_CHECK_HIP(hipEventCreateWithFlags(&A->drained, hipEventDisableTiming));
-        HP_CHECK_HIP(hipMalloc((void **)&A->d_sums, sizeof(u64) * 2 * ST_SECTIONS));
-        HP_CHECK_HIP(hipHostMalloc((void **)&A->pin_sums, sizeof(u64) * 2 * ST_SECTIONS, hipHostMallocDefault));
+        HP_CHECK_HIP(hipMalloc((void **)&A->d_sums, sizeof(u64) * 2 * DS_SECTIONS));
+        HP_CHECK_HIP(hipHostMalloc((void **)&A->pin_sums, sizeof(u64) * 2 * DS_SECTIONS, hipHostMallocDefault));
     }
     *out = a->state;
     return HP_OK;
@@ -284,6 +461,35 @@ static SmallArgs small_args(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn,
     return M;
 }
 
+// The dirty scan of `cs` slots of b on stream s: hdr[0] = n_dirty, hdr[1] = overflow, slots[0 .. min(n_dirty, max_dirty)).
+static int launch_dirty_scan(hp_buffer *b, int64_t cs, uint32_t since, int64_t max_dirty, long long *hdr, long long *slots,
+                             hipStream_t s) {
+    DirtyArgs D;
+    D.stamp = b->d_slot_epoch;
+    D.cs = cs;
+    D.since = since;
+    D.max_dirty = max_dirty;
+    D.n_chunks = (cs + DS_CHUNK - 1) / DS_CHUNK;
+    HP_TRY(b->dirty_counts.ensure(std::max<size_t>((size_t)D.n_chunks, 1) * sizeof(long long)));
+    D.counts = b->dirty_counts.as<long long>();
+    D.hdr = hdr;
+    D.slots = slots;
+    if (D.n_chunks > 0) {
+        HP_KLOG("k_dirty_count");
+        hipLaunchKernelGGL(k_dirty_count, dim3((unsigned)D.n_chunks), dim3(DS_CHUNK_THREADS), 0, s, D);
+        HP_CHECK_HIP(hipGetLastError());
+    }
+    HP_KLOG("k_dirty_scan");
+    hipLaunchKernelGGL(k_dirty_scan, dim3(1), dim3(256), 0, s, D);
+    HP_CHECK_HIP(hipGetLastError());
+    if (D.n_chunks > 0 && max_dirty > 0) {
+        HP_KLOG("k_dirty_emit");
+        hipLaunchKernelGGL(k_dirty_emit, dim3((unsigned)D.n_chunks), dim3(DS_CHUNK_THREADS), 0, s, D);
+        HP_CHECK_HIP(hipGetLastError());
+    }
+    return HP_OK;
+}
+
 void state_arena_destroy(hp_agent *a) {
     StateArena *A = a->state;
     if (!A) return;
@@ -320,19 +526,32 @@ int hp_state_layout(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, int64_t
     return HP_OK;
 }
 
-int hp_state_capture(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, uint64_t *ticket, size_t *bytes) {
-    HP_TRY(state_handles(a, b, on, gn, rng, "hp_state_capture"));
-    HP_REQUIRE(ticket, HP_ERR_INVALID, "hp_state_capture: null ticket");
+// Both kinds of capture.  delta: the buffer as the slots stamped since the capture `since` (room for max_dirty episodes).
+static int state_capture(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, bool delta, uint32_t since,
+                         int64_t max_dirty, uint64_t *ticket, size_t *bytes) {
+    const char *who = delta ? "hp_state_capture_delta" : "hp_state_capture";
+    HP_TRY(state_handles(a, b, on, gn, rng, who));
+    HP_REQUIRE(ticket, HP_ERR_INVALID, "%s: null ticket", who);
     HP_SERIALISE(a);
-    HP_TRY(agent_check_fault(a, "hp_state_capture"));
+    HP_TRY(agent_check_fault(a, who));
     StateArena *A = nullptr;
     HP_TRY(arena_get(a, &A));
-    HP_REQUIRE(!A->pending, HP_ERR_STATE, "hp_state_capture: the capture with ticket %llu has not been fetched yet "
-               "(hp_state_fetch; a null host_out abandons it)", (unsigned long long)A->ticket);
+    HP_REQUIRE(!A->pending, HP_ERR_STATE, "%s: the capture with ticket %llu has not been fetched yet "
+               "(hp_state_fetch; a null host_out abandons it)", who, (unsigned long long)A->ticket);
+    HP_REQUIRE(b->epoch < 0xFFFFFFFFu, HP_ERR_STATE, "%s: the buffer's capture epoch has reached 2^32 - 1", who);
     hipStream_t s = a->ctx->stream;
     const int64_t cs = b->current_size;
-    hp_state_section S[ST_SECTIONS];
-    const size_t total = state_layout(a, b, on, gn, cs, S);
+    if (delta) {
+        HP_REQUIRE(since >= b->min_since, HP_ERR_STATE, "hp_state_capture_delta: since_epoch %u is older than the last restore "
+                   "(min_since %u): the rows that changed before it are not known any more", since, b->min_since);
+        HP_REQUIRE(since < b->epoch, HP_ERR_STATE, "hp_state_capture_delta: since_epoch %u is not a capture of this buffer "
+                   "(its epoch is %u)", since, b->epoch);
+        HP_REQUIRE(max_dirty >= 0 && max_dirty <= cs, HP_ERR_INVALID, "hp_state_capture_delta: max_dirty %lld outside [0, %lld]",
+                   (long long)max_dirty, (long long)cs);
+    }
+    hp_state_section S[DS_SECTIONS];
+    const int nsec = delta ? DS_SECTIONS : ST_SECTIONS;
+    const size_t total = delta ? delta_layout(a, b, on, gn, max_dirty, S) : state_layout(a, b, on, gn, cs, S);
     // the previous ticket was fetched, so its drain is over: arena and pinned copy are free
     HP_TRY(arena_ensure(A, total));
     if (total > A->pin_bytes) {
@@ -348,26 +567,107 @@ int hp_state_capture(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng
     HP_KLOG("k_state_flat");
     hipLaunchKernelGGL(k_state_flat<false>, dim3((unsigned)((nmax + 255) / 256), 8), dim3(256), 0, s, F);
     HP_CHECK_HIP(hipGetLastError());
+    SmallArgs M = small_args(a, b, on, gn, rng, A->dev, S);
+    if (delta) M.off[ST_BUF_COUNTERS] = S[DS_COUNTERS].offset;   // (the small sections sit at a full state's indices)
     HP_KLOG("k_state_small");
-    hipLaunchKernelGGL(k_state_small<false>, dim3(1), dim3(256), 0, s, small_args(a, b, on, gn, rng, A->dev, S));
+    hipLaunchKernelGGL(k_state_small<false>, dim3(1), dim3(256), 0, s, M);
     HP_CHECK_HIP(hipGetLastError());
     const double *rows[4] = {b->d_obs, b->d_ag, b->d_g, b->d_act};
-    for (int k = 0; k < 4 && cs > 0; ++k)
-        HP_CHECK_HIP(hipMemcpyAsync(A->dev + S[ST_BUF_OBS + k].offset, rows[k], (size_t)S[ST_BUF_OBS + k].count * 8,
-                                    hipMemcpyDeviceToDevice, s));
+    long long *hdr = nullptr;
+    if (delta) {
+        hdr = reinterpret_cast<long long *>(A->dev + S[DS_HEADER].offset);
+        long long *slots = reinterpret_cast<long long *>(A->dev + S[DS_SLOTS].offset);
+        HP_TRY(launch_dirty_scan(b, cs, since, max_dirty, hdr, slots, s));
+        if (max_dirty > 0) {
+            PackArgs P;
+            P.hdr = hdr;
+            P.slots = slots;
+            P.max_dirty = max_dirty;
+            const long long ep[4] = {(long long)b->ep_obs(), (long long)b->ep_ag(), (long long)b->ep_g(), (long long)b->ep_act()};
+            for (int k = 0; k < 4; ++k) {
+                P.src[k] = rows[k];
+                P.dst[k] = reinterpret_cast<double *>(A->dev + S[DS_OBS + k].offset);
+                P.ep[k] = ep[k];
+            }
+            HP_KLOG("k_delta_pack");
+            hipLaunchKernelGGL(k_delta_pack, dim3((unsigned)(std::min<int64_t>(max_dirty, 4096) * DS_PACK_PARTS)), dim3(256), 0, s, P);
+            HP_CHECK_HIP(hipGetLastError());
+        }
+    } else {
+        for (int k = 0; k < 4 && cs > 0; ++k)
+            HP_CHECK_HIP(hipMemcpyAsync(A->dev + S[ST_BUF_OBS + k].offset, rows[k], (size_t)S[ST_BUF_OBS + k].count * 8,
+                                        hipMemcpyDeviceToDevice, s));
+    }
+    HP_KLOG("k_epoch_advance");
+    hipLaunchKernelGGL(k_epoch_advance, dim3(1), dim3(1), 0, s, b->d_epoch, hdr, (long long)since);
+    HP_CHECK_HIP(hipGetLastError());
+    A->capture_epoch = b->epoch++;
     HP_CHECK_HIP(hipEventRecord(A->captured, s));
     // drain stream: checksums of the snapshot, then the snapshot and the sums to pinned memory
     HP_CHECK_HIP(hipStreamWaitEvent(A->drain, A->captured, 0));
-    HP_TRY(checksum_sections(A, S, A->drain));
+    if (delta) {
+        HP_CHECK_HIP(hipMemsetAsync(A->d_sums, 0, sizeof(u64) * 2 * DS_SECTIONS, A->drain));
+        for (int i = 0; i < DS_SECTIONS; ++i) {
+            if (i < DS_SLOTS || i > DS_ACT) {
+                HP_TRY(launch_checksum(A->dev + S[i].offset, (size_t)S[i].count * S[i].elem_bytes, A->d_sums + 2 * i, A->drain));
+                continue;
+            }
+            if (max_dirty == 0) continue;
+            const u64 per_ep = (u64)(S[i].count / max_dirty);   // 8-byte words per episode
+            const u64 want = ((u64)S[i].count / 2 + 256 * 4 - 1) / (256 * 4);
+            HP_KLOG("k_checksum_prefix");
+            hipLaunchKernelGGL(k_checksum_prefix, dim3((unsigned)std::min<u64>(std::max<u64>(want, 1), 2048)), dim3(256), 0, A->drain,
+                               reinterpret_cast<const u64 *>(A->dev + S[i].offset), hdr, per_ep, (long long)max_dirty,
+                               A->d_sums + 2 * i);
+            HP_CHECK_HIP(hipGetLastError());
+        }
+    } else HP_TRY(checksum_sections(A, S, A->drain));
     for (size_t off = 0; off < total; off += ST_DRAIN_CHUNK)
         HP_CHECK_HIP(hipMemcpyAsync(A->pin + off, A->dev + off, std::min<size_t>(ST_DRAIN_CHUNK, total - off),
                                     hipMemcpyDeviceToHost, A->drain));
-    HP_CHECK_HIP(hipMemcpyAsync(A->pin_sums, A->d_sums, sizeof(u64) * 2 * ST_SECTIONS, hipMemcpyDeviceToHost, A->drain));
+    HP_CHECK_HIP(hipMemcpyAsync(A->pin_sums, A->d_sums, sizeof(u64) * 2 * nsec, hipMemcpyDeviceToHost, A->drain));
     HP_CHECK_HIP(hipEventRecord(A->drained, A->drain));
     A->pending = true;
     A->bytes = total;
+    A->n_sections = nsec;
+    A->hdr_off = delta ? (size_t)S[DS_HEADER].offset : 0;
     *ticket = ++A->ticket;
     if (bytes) *bytes = total;
+    return HP_OK;
+}
+
+int hp_state_capture(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, uint64_t *ticket, size_t *bytes) {
+    return state_capture(a, b, on, gn, rng, false, 0, 0, ticket, bytes);
+}
+
+int hp_state_capture_delta(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, uint32_t since_epoch, int64_t max_dirty,
+                           uint64_t *ticket, size_t *bytes) {
+    return state_capture(a, b, on, gn, rng, true, since_epoch, max_dirty, ticket, bytes);
+}
+
+int hp_state_layout_delta(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, int64_t max_dirty, hp_state_section *out, int32_t *n,
+                          size_t *total_bytes) {
+    HP_REQUIRE(a && b && on && gn && n, HP_ERR_INVALID, "hp_state_layout_delta: null argument");
+    HP_SERIALISE(a);
+    HP_REQUIRE(max_dirty >= 0 && max_dirty <= b->size, HP_ERR_INVALID, "hp_state_layout_delta: max_dirty %lld outside [0, %lld]",
+               (long long)max_dirty, (long long)b->size);
+    hp_state_section S[DS_SECTIONS];
+    const size_t total = delta_layout(a, b, on, gn, max_dirty, S);
+    if (out) {
+        HP_REQUIRE(*n >= DS_SECTIONS, HP_ERR_INVALID, "hp_state_layout_delta: room for %d sections, %d needed", *n, DS_SECTIONS);
+        memcpy(out, S, sizeof(S));
+    }
+    *n = DS_SECTIONS;
+    if (total_bytes) *total_bytes = total;
+    return HP_OK;
+}
+
+int hp_state_epochs(hp_agent *a, hp_buffer *b, uint32_t *capture_epoch, uint32_t *epoch, uint32_t *min_since) {
+    HP_REQUIRE(a && b && b->ctx == a->ctx, HP_ERR_INVALID, "hp_state_epochs: null handle, or handles of different contexts");
+    HP_SERIALISE(a);
+    if (capture_epoch) *capture_epoch = a->state ? a->state->capture_epoch : 0u;
+    if (epoch) *epoch = b->epoch;
+    if (min_since) *min_since = b->min_since;
     return HP_OK;
 }
 
@@ -394,12 +694,18 @@ int hp_state_fetch(hp_agent *a, uint64_t ticket, int32_t wait, void *host_out, s
         HP_CHECK_HIP(q);
     }
     // (the pinned copy cannot change under this: a new capture is refused while this ticket is pending)
-    if (host_out) memcpy(host_out, A->pin, A->bytes);
-    if (sums) memcpy(sums, A->pin_sums, sizeof(u64) * 2 * ST_SECTIONS);
+    long long hdr[2] = {0, 0};
+    if (A->n_sections == DS_SECTIONS) memcpy(hdr, A->pin + A->hdr_off, sizeof(hdr));
+    if (host_out && !hdr[1]) {
+        memcpy(host_out, A->pin, A->bytes);
+        if (sums) memcpy(sums, A->pin_sums, sizeof(u64) * 2 * A->n_sections);
+    }
     {
         HP_SERIALISE(a);
         A->pending = false;
     }
+    HP_REQUIRE(!host_out || !hdr[1], HP_ERR_STATE, "hp_state_fetch: the delta found %lld dirty slots, more than the max_dirty it was "
+               "sized for: nothing is delivered, the ticket is retired", hdr[0]);
     if (done) *done = 1;
     return HP_OK;
 }
@@ -435,6 +741,7 @@ int hp_state_restore(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng
     HP_REQUIRE(cnt[0] == cs, HP_ERR_INVALID, "hp_state_restore: buffer_counters says current_size %lld, the header %lld", cnt[0],
                (long long)cs);
     HP_REQUIRE(pos >= 0 && pos <= MT_N, HP_ERR_INVALID, "hp_state_restore: rng_pos %d outside [0, 624]", pos);
+    HP_REQUIRE(b->epoch < 0xFFFFFFFDu, HP_ERR_STATE, "hp_state_restore: the buffer's capture epoch has reached 2^32 - 1");
     StateArena *A = nullptr;
     HP_TRY(arena_get(a, &A));
     // a capture still draining reads the arena: let it finish (its pinned copy stays fetchable)
@@ -469,12 +776,44 @@ int hp_state_restore(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng
     b->current_size = cs;
     b->n_transitions_stored = cnt[1];
     b->staged_n = 0;                 // staged episodes are not part of a state
+    // Delta states: which slots changed before now is not known any more.  The stamps start over; the restored state stands for a
+    // capture with an epoch larger than any handed out before (min_since), and what is stored from here on is stamped above it.
+    HP_CHECK_HIP(hipMemsetAsync(b->d_slot_epoch, 0, (size_t)b->size * sizeof(uint32_t), s));
+    b->min_since = b->epoch + 1u;
+    b->epoch = b->min_since + 1u;
+    HP_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)b->d_epoch, (int)b->epoch, 1, s));
     // a policy snapshot taken before now is a copy of parameters that no longer exist: hp_agent_act_snapshot must not serve it
     a->snap_cur = -1;
     a->snap_pending = -1;
     // The cached update and cycle graphs stay valid: they bake in addresses (unchanged) and read every counter from device
     // memory (BufMeta, AgentDevState, MtState) at run time.
     HP_CHECK_HIP(hipStreamSynchronize(s));
+    return HP_OK;
+}
+
+int hp_state_debug_dirty_scan(hp_buffer *b, const uint32_t *stamps_host, int64_t current_size, uint32_t since, int64_t max_dirty,
+                              int64_t *slots_out, int64_t *n_dirty, int32_t *overflow) {
+    HP_REQUIRE(b && stamps_host && n_dirty && (slots_out || max_dirty == 0), HP_ERR_INVALID, "hp_state_debug_dirty_scan: null argument");
+    HP_REQUIRE(current_size >= 0 && current_size <= b->size && max_dirty >= 0 && max_dirty <= b->size, HP_ERR_INVALID,
+               "hp_state_debug_dirty_scan: current_size / max_dirty outside [0, %lld]", (long long)b->size);
+    HP_SERIALISE(b);
+    hipStream_t s = b->ctx->stream;
+    DevBuf out;   // header (2 words, padded to 4) | slots
+    HP_TRY(out.ensure((4 + std::max<size_t>((size_t)max_dirty, 1)) * sizeof(long long)));
+    long long *hdr = out.as<long long>(), *slots = hdr + 4;
+    long long h[2] = {0, 0};
+    int st = HP_OK;
+    hipError_t e = hipMemcpyAsync(b->d_slot_epoch, stamps_host, (size_t)b->size * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) st = launch_dirty_scan(b, current_size, since, max_dirty, hdr, slots, s);
+    if (e == hipSuccess && st == HP_OK) e = hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    const long long used = h[0] < max_dirty ? h[0] : max_dirty;
+    if (e == hipSuccess && st == HP_OK && used > 0) e = hipMemcpy(slots_out, slots, (size_t)used * sizeof(long long), hipMemcpyDeviceToHost);
+    out.release();
+    HP_TRY(st);
+    HP_CHECK_HIP(e);
+    *n_dirty = h[0];
+    if (overflow) *overflow = (int32_t)h[1];
     return HP_OK;
 }
 

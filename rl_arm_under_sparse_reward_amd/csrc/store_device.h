@@ -6,12 +6,17 @@
 // Episode i of the staged batch goes to slot slots[i] unless a LATER staged episode has the same slot (numpy's
 // `buffers[idxs] = mb` lets the last occurrence win).  One of `parts` workgroups per episode copies a strided share of its
 // values.  Workgroup-uniform control flow; `slot_of(j)` reads slots[j] (plain or agent-scope load, the caller knows).
+// Every (episode, part) also stamps its slot with the buffer's capture epoch, READ FROM DEVICE MEMORY so that a cached graph keeps
+// stamping right after a capture advanced it (state.hip: delta states).  A dropped episode stamps too: its slot was written, by
+// the winner, with the same value.
 template <class SlotOf>
 __device__ __forceinline__ void store_scatter_share(SlotOf slot_of, long long i, int part, int parts, long long n_new,
                                                     const double *s_obs, const double *s_ag, const double *s_g,
                                                     const double *s_act, double *obs, double *ag, double *g, double *act,
-                                                    long long ep_obs, long long ep_ag, long long ep_g, long long ep_act) {
+                                                    long long ep_obs, long long ep_ag, long long ep_g, long long ep_act,
+                                                    uint32_t *slot_epoch, const uint32_t *epoch) {
     const long long slot = slot_of(i);
+    if (threadIdx.x == 0) slot_epoch[slot] = *epoch;
     int dup = 0;
     for (long long j = i + 1 + threadIdx.x; j < n_new; j += blockDim.x) dup |= (slot_of(j) == slot);
     if (__syncthreads_or(dup)) return;

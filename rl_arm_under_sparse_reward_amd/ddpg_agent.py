@@ -530,25 +530,72 @@ class ddpg_agent:
         self.g_norm.set_stats(g_mean, g_std)
 
     # ------------------------------------------------------------------ training state (train_state.py, csrc/state.hip)
-    def save_training_state(self, path, wait=True, extra=None, epoch=0, cycle=0):
+    def save_training_state(self, path, wait=True, extra=None, epoch=0, cycle=0, base=None):
         """Everything a continued run needs -- what ddpg_agent.py:54-62 wished for ("load the data to continue the training") --
         in one .npz of named arrays: both networks and targets, Adam m / v / step, both normalizers, the device random stream,
         the replay buffer, and the host side (numpy's global stream, success_rates, savetime, `epoch` / `cycle` reached, the
         caller's opaque `extra` bytes, e.g. a pickled simulator).  Pending deferred updates are issued first.  The device part
         is snapshotted in stream order without a host wait; wait=False returns a handle whose `.result()` finishes the file
-        while training goes on (one capture at a time: a second one before `.result()` raises)."""
+        while training goes on (one capture at a time: a second one before `.result()` raises).
+        base=PATH of a full state this agent saved or loaded in this process: write a *delta* -- the small arrays, and the buffer
+        as the episodes stored since that state (a few MB instead of the whole buffer; the device knows which slots were
+        written).  Base + delta restore exactly what a full state taken now restores.  A base this agent does not know, or one
+        older than a load_training_state done since, is refused before anything is captured."""
         from . import train_state
-        return train_state.save(self, path, wait=wait, extra=extra, epoch=epoch, cycle=cycle)
+        return train_state.save(self, path, wait=wait, extra=extra, epoch=epoch, cycle=cycle, base=base)
 
-    def load_training_state(self, path):
+    def load_training_state(self, path, base=None):
         """Continue from `save_training_state`'s file, in a fresh agent or in this one after more cycles (roll-back): the run
         that follows is bit-identical to the one that never stopped.  Refused, with nothing changed, when dims, capacity, T, rank
         or world size differ or the uploaded bytes do not sum on the device to what the file records.  Returns `extra`; the
-        epoch / cycle the state was saved at are in `self.resumed_at`."""
+        epoch / cycle the state was saved at are in `self.resumed_at`.  A delta is composed with its base on the host first
+        (`base`, default: the file name the delta records, beside it)."""
         from . import train_state
-        extra, manifest = train_state.load(self, path)
+        extra, manifest = train_state.load(self, path, base=base)
         self.resumed_at = (int(manifest["epoch"]), int(manifest["cycle"]))
         return extra
+
+    def _resume_state(self, resume):
+        """args.resume: the cumulative delta beside the base when it cites that base, otherwise the base alone."""
+        from . import train_state as ts
+        base = ts.rank_path(resume, self.comm.rank)
+        delta = ts.rank_path(ts.delta_path(resume), self.comm.rank)
+        take = base
+        if os.path.exists(delta):
+            try:
+                cited, key = ts.read_manifest(delta)["base"], ts.base_key(ts.read_manifest(base), where=base)
+                if all(cited[f] == key[f] for f in ("lineage", "capture_epoch", "current_size", "sums")):
+                    take = delta
+            except (ts.StateError, KeyError):
+                pass
+        print("resuming from", take, "(delta over %s)" % base if take is delta else "(full state)")
+        self.load_training_state(take, base=base if take is delta else None)
+
+    def _save_epoch_state(self, state_path, epoch):
+        """learn()'s save after an epoch.  args.state_full_every = k >= 1: every k-th save rewrites the base `state_path`, the
+        saves between rewrite ONE cumulative delta beside it against that base; 0: every save is full."""
+        from . import train_state as ts
+        base = ts.rank_path(state_path, self.comm.rank)
+        every = int(getattr(self.args, "state_full_every", 0) or 0)
+        if every <= 0:
+            return self.save_training_state(base, epoch=epoch)
+        delta = ts.rank_path(ts.delta_path(state_path), self.comm.rank)
+        n = getattr(self, "_state_saves", 0)
+        self._state_saves = n + 1
+        if n % every != 0:
+            try:
+                ts.known_base(self, base)
+            except ts.StateError:
+                pass          # e.g. the first save after a resume from a delta: its base is older than the restore
+            else:
+                return self.save_training_state(delta, epoch=epoch, base=base)
+        # re-base: the new base first, the stale delta after -- a crash between the two leaves a valid, newer, full state (and
+        # a delta that cites another base, which a resume does not take)
+        out = self.save_training_state(base, epoch=epoch)
+        self._state_saves = 1
+        if os.path.exists(delta):
+            os.unlink(delta)
+        return out
 
     # ------------------------------------------------------------------ rollout side (host glue, SURVEY 8f N1)
     def _preproc_inputs(self, obs, g):
@@ -707,8 +754,7 @@ class ddpg_agent:
         if self.vec_env is not None and getattr(self.args, "explore_streams", False) and self.explore_streams is None:
             self.enable_explore_streams()    # args.explore_streams: before a resume, whose state carries the streams' states
         if resume:
-            from .train_state import rank_path
-            self.load_training_state(rank_path(resume, self.comm.rank))
+            self._resume_state(resume)
             first_epoch = self.resumed_at[0]
         print("initial buffer size:", self.buffer.current_size)                  # :97
         if self.vec_env is not None:
@@ -731,8 +777,7 @@ class ddpg_agent:
                 print('[{}] epoch is: {}, eval success rate is: {:.3f}'.format(datetime.now(), epoch, rate))
                 self.save_checkpoint()
             if state_path:
-                from .train_state import rank_path
-                self.save_training_state(rank_path(state_path, self.comm.rank), epoch=epoch + 1)
+                self._save_epoch_state(state_path, epoch + 1)
 
     def _learn_device(self, share, state_path, first_epoch):
         """learn() with a vectorised device environment: every draw of a cycle -- exploration, overflow slots, HER indices --
@@ -754,10 +799,9 @@ class ddpg_agent:
                 print('[{}] epoch is: {}, eval success rate is: {:.3f}'.format(datetime.now(), epoch, rate))
                 self.save_checkpoint()
             if state_path:
-                from .train_state import rank_path
                 if share:
                     np.random.set_state(self.rng.get_state())
-                self.save_training_state(rank_path(state_path, self.comm.rank), epoch=epoch + 1)
+                self._save_epoch_state(state_path, epoch + 1)
         if share:
             np.random.set_state(self.rng.get_state())
 

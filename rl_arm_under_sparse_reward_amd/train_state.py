@@ -25,10 +25,29 @@ B = sum (i + 1) w_i mod 2^64.  The device computes it on the snapshot at capture
     python -m rl_arm_under_sparse_reward_amd.train_state verify FILE
 
 checks a state file on a machine without a GPU.
+
+Delta states.  A full save writes the whole replay buffer again (149 MB of rows per rank at the reference's size, against 3 MB
+stored between two epochs).  `save(agent, path, base=FULL)` writes a *delta* instead: every small array under the names above, and
+the buffer as the episodes written since the full state FULL was captured --
+
+    buffer_delta_slots                      int64 [n_dirty], ascending
+    buffer_delta_{obs,ag,g,actions}         float64 [n_dirty, ...]: the rows of those slots
+    buffer_counters, host arrays, exploration-stream arrays as in a full state
+
+with manifest format 2, "kind": "delta", its own "capture_epoch", "dims" with the NEW current_size and
+"base": {name, lineage, capture_epoch, current_size, sums of the base's four buffer arrays}.  A full state's manifest carries
+"lineage" (a 64-bit id made at an agent's first save -- a hash of that state's checksums -- and kept across resumes) and "capture_epoch" (the buffer epoch the
+capture recorded, csrc/state.hip); one without them -- written before deltas existed -- cannot serve as a base.  The base of a
+delta is always a full state.  `compose(base, delta)` (pure numpy) rebuilds what a full state taken at the delta's instant
+holds; `load()` of a delta composes and then restores as ever.
+
+    python -m rl_arm_under_sparse_reward_amd.train_state verify DELTA [--base BASE]
+    python -m rl_arm_under_sparse_reward_amd.train_state flatten BASE DELTA OUT
 """
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 import json
 import os
 import sys
@@ -37,6 +56,9 @@ import zipfile
 import numpy as np
 
 FORMAT_VERSION = 1
+DELTA_FORMAT_VERSION = 2            # a delta: refused by a reader that knows format 1 only
+BUFFER_ARRAYS = ("buffer_obs", "buffer_ag", "buffer_g", "buffer_actions")
+DELTA_ROW_ARRAYS = ("buffer_delta_obs", "buffer_delta_ag", "buffer_delta_g", "buffer_delta_actions")
 _DTYPES = {0: "<f4", 1: "<f8", 2: "<i8", 3: "<u4", 4: "<i4"}        # hp_state_section.dtype
 _NORM_FIELDS = ("local_sum", "local_sumsq", "local_count", "total_sum", "total_sumsq", "total_count", "mean", "std")
 _MASK = (1 << 64) - 1
@@ -135,9 +157,53 @@ def read_state(path):
         manifest = json.loads(str(arrays.pop("manifest")[()]))
     except ValueError as e:
         raise StateError(f"{path}: 'manifest' is not JSON ({e})") from e
-    if manifest.get("format") != FORMAT_VERSION:
-        raise StateError(f"{path}: manifest 'format' is {manifest.get('format')!r}, this build reads {FORMAT_VERSION}")
+    fmt, kind = manifest.get("format"), manifest.get("kind", "full")
+    if (fmt, kind) not in ((FORMAT_VERSION, "full"), (DELTA_FORMAT_VERSION, "delta")):
+        raise StateError(f"{path}: manifest 'format' is {fmt!r} ('kind' {kind!r}), this build reads {FORMAT_VERSION} (full states) "
+                         f"and {DELTA_FORMAT_VERSION} (deltas)")
     return arrays, manifest
+
+
+def read_manifest(path):
+    """The manifest alone (the arrays of an .npz are read on access: a 150 MB base costs nothing here)."""
+    try:
+        with np.load(os.fspath(path), allow_pickle=False) as z:
+            return json.loads(str(z["manifest"][()]))
+    except (zipfile.BadZipFile, EOFError, OSError, ValueError, KeyError) as e:
+        raise StateError(f"{path}: not a readable training state ({type(e).__name__}: {e})") from e
+
+
+def is_delta(manifest) -> bool:
+    return manifest.get("kind", "full") == "delta"
+
+
+def delta_path(path):
+    """`state.npz` -> `state.delta.npz`: the cumulative delta learn() keeps beside its base (args.state_full_every)."""
+    root, ext = os.path.splitext(os.fspath(path))
+    return f"{root}.delta{ext}"
+
+
+def delta_shapes(dims: dict, n_dirty: int) -> dict:
+    """name -> (dtype, shape) of the arrays that stand for the buffer in a delta of n_dirty episodes."""
+    o, g, a, T, n = int(dims["obs"]), int(dims["goal"]), int(dims["action"]), int(dims["T"]), int(n_dirty)
+    return {"buffer_delta_slots": ("<i8", (n,)), "buffer_delta_obs": ("<f8", (n, T + 1, o)), "buffer_delta_ag": ("<f8", (n, T + 1, g)),
+            "buffer_delta_g": ("<f8", (n, T, g)), "buffer_delta_actions": ("<f8", (n, T, a))}
+
+
+def base_key(manifest, where="state"):
+    """What names a full state as a base: (lineage, capture_epoch, current_size, sums of its four buffer arrays)."""
+    if is_delta(manifest):
+        raise StateError(f"{where}: manifest 'kind' is 'delta': the base of a delta must be a full state (no delta on a delta)")
+    if "lineage" not in manifest or "capture_epoch" not in manifest:
+        raise StateError(f"{where}: manifest has no 'lineage' / 'capture_epoch': this full state was written before delta states "
+                         "existed and cannot serve as a base (load it and save a new full state)")
+    return {"lineage": str(manifest["lineage"]), "capture_epoch": int(manifest["capture_epoch"]),
+            "current_size": int(manifest["dims"]["current_size"]),
+            "sums": {n: [int(x) for x in manifest["arrays"][n]["sum"]] for n in BUFFER_ARRAYS}}
+
+
+def _key_tuple(key):
+    return (key["lineage"], key["capture_epoch"], key["current_size"], tuple(tuple(key["sums"][n]) for n in BUFFER_ARRAYS))
 
 
 def _check_array(where, name, arrays, listed, want, implied_by, sums, entry=True):
@@ -205,9 +271,99 @@ def stream_record(keys, pos, has_gauss, gauss):
     return arrays, rec
 
 
-def verify(path):
-    """Check a state file without a GPU; returns its manifest."""
+def check_delta_arrays(arrays, manifest, sums=True, where="delta"):
+    """A delta by itself: every small device array as the dims imply, the slot list and the four row arrays shaped for
+    manifest['n_dirty'] and (sums=True) summing to what the manifest records, the slot list strictly ascending inside
+    [0, current_size) and holding every slot of the grown region [base current_size, current_size)."""
+    dims, listed = manifest["dims"], manifest["arrays"]
+    want = expected_shapes(dims)
+    for name in DEVICE_ARRAYS:
+        if name not in BUFFER_ARRAYS:
+            _check_array(where, name, arrays, listed, want[name], "the manifest's dims", sums)
+    n = int(manifest["n_dirty"])
+    for name, w in delta_shapes(dims, n).items():
+        _check_array(where, name, arrays, listed, w, f"the manifest's dims and n_dirty {n}", sums)
+    cs, cs0 = int(dims["current_size"]), int(manifest["base"]["current_size"])
+    if int(arrays["buffer_counters"][0]) != cs:
+        raise StateError(f"{where}: array 'buffer_counters' says current_size {int(arrays['buffer_counters'][0])}, the manifest {cs}")
+    if not 0 <= cs0 <= cs:
+        raise StateError(f"{where}: manifest 'base' has current_size {cs0}, the delta {cs}: a buffer does not shrink")
+    slots = arrays["buffer_delta_slots"]
+    if n and (int(slots[0]) < 0 or int(slots[-1]) >= cs or int(slots.min()) < 0 or int(slots.max()) >= cs):
+        raise StateError(f"{where}: array 'buffer_delta_slots' holds a slot outside [0, {cs})")
+    if n > 1 and not bool(np.all(np.diff(slots) > 0)):
+        raise StateError(f"{where}: array 'buffer_delta_slots' is not strictly ascending")
+    grown = np.arange(cs0, cs, dtype=np.int64)
+    if grown.size and not np.array_equal(slots[slots >= cs0], grown):
+        raise StateError(f"{where}: array 'buffer_delta_slots' does not list every slot of the grown region [{cs0}, {cs})")
+    for name in ("np_random_key", "success_rates", "extra"):
+        if name not in arrays:
+            raise StateError(f"{where}: array '{name}' is missing")
+    check_stream_arrays(arrays, manifest, where=where)
+
+
+def compose(base_path, delta_path_, sums=True):
+    """Base + delta -> (arrays, manifest) of the full state taken at the delta's instant, as `read_state` returns one.  Pure
+    numpy.  Refused, naming the array or field: a base that is a delta or has no lineage, a lineage / capture_epoch / current_size /
+    buffer sum of the base that is not what the delta cites, any delta array that does not sum to its manifest entry, a slot list
+    that is not strictly ascending inside [0, current_size) or misses part of the grown region."""
+    base_where, where = os.fspath(base_path), os.fspath(delta_path_)
+    arrays, manifest = read_state(where)
+    if not is_delta(manifest):
+        raise StateError(f"{where}: manifest 'kind' is not 'delta'")
+    b_arrays, b_manifest = read_state(base_where)
+    key, cited = base_key(b_manifest, where=base_where), manifest["base"]
+    for field in ("lineage", "capture_epoch", "current_size"):
+        if key[field] != type(key[field])(cited[field]):
+            raise StateError(f"{base_where}: '{field}' of the base is {key[field]!r}, the delta {where} cites {cited[field]!r}")
+    for name in BUFFER_ARRAYS:
+        if key["sums"][name] != [int(x) for x in cited["sums"][name]]:
+            raise StateError(f"{base_where}: array '{name}' of the base sums to {tuple(key['sums'][name])}, the delta {where} cites "
+                             f"{tuple(cited['sums'][name])}: not the state this delta was taken against")
+    for f in ("obs", "goal", "action", "hidden", "T", "capacity"):
+        if int(b_manifest["dims"][f]) != int(manifest["dims"][f]):
+            raise StateError(f"{base_where}: {f} of the base is {b_manifest['dims'][f]}, of the delta {manifest['dims'][f]}")
+    want0 = expected_shapes(b_manifest["dims"])
+    for name in BUFFER_ARRAYS:       # the base's rows are what its manifest (and so the delta) says
+        _check_array(base_where, name, b_arrays, b_manifest["arrays"], want0[name], "the manifest's dims", sums)
+    check_delta_arrays(arrays, manifest, sums=sums, where=where)
+    dims, cs0 = manifest["dims"], key["current_size"]
+    want, slots = expected_shapes(dims), arrays["buffer_delta_slots"]
+    out = {k: v for k, v in arrays.items() if not k.startswith("buffer_delta_")}
+    listed = {k: v for k, v in manifest["arrays"].items() if not k.startswith("buffer_delta_")}
+    for name, rows in zip(BUFFER_ARRAYS, DELTA_ROW_ARRAYS):
+        dt, shape = want[name]
+        full = np.empty(shape, dt)
+        full[:cs0] = b_arrays[name]
+        full[slots] = arrays[rows]
+        out[name] = full
+        listed[name] = {"dtype": dt, "shape": list(shape), "sum": list(checksum(full))}
+    composed = {k: v for k, v in manifest.items() if k not in ("kind", "base", "n_dirty", "arrays", "format")}
+    composed.update({"format": FORMAT_VERSION, "arrays": listed})
+    ordered = {name: out[name] for name in DEVICE_ARRAYS}
+    ordered.update({k: v for k, v in out.items() if k not in ordered})
+    return ordered, composed
+
+
+def flatten(base_path, delta_path_, out_path):
+    """Write compose(base, delta) as a full state: what save_training_state(out_path) would have written at the delta's instant
+    (it keeps the delta's lineage and capture_epoch, so it can serve as a base where the delta was loaded)."""
+    arrays, manifest = compose(base_path, delta_path_)
+    return write_state(out_path, arrays, manifest)
+
+
+def default_base(path, manifest):
+    """The base a delta names, taken beside the delta."""
+    return os.path.join(os.path.dirname(os.fspath(path)), manifest["base"]["name"])
+
+
+def verify(path, base=None):
+    """Check a state file without a GPU; returns its manifest.  A delta is checked together with its base (default: the name its
+    manifest records, beside it)."""
     arrays, manifest = read_state(path)
+    if is_delta(manifest):
+        compose(base or default_base(path, manifest), path)
+        return manifest
     check_arrays(arrays, manifest, sums=True, where=os.fspath(path))
     return manifest
 
@@ -234,22 +390,91 @@ def _layout(agent, current_size=-1):
     return [(s.name.decode(), _DTYPES[s.dtype], int(s.count), int(s.offset)) for s in secs[:n.value]], int(total.value)
 
 
+def _layout_delta(agent, max_dirty):
+    from . import _lib
+    secs = (_lib.StateSection * _lib.STATE_DELTA_SECTIONS)()
+    n, total = C.c_int32(_lib.STATE_DELTA_SECTIONS), C.c_size_t()
+    _lib.check(agent.lib.hp_state_layout_delta(agent.h, agent.buffer._dev.h, agent.o_norm.h, agent.g_norm.h, int(max_dirty), secs,
+                                               C.byref(n), C.byref(total)))
+    return [(s.name.decode(), _DTYPES[s.dtype], int(s.count), int(s.offset)) for s in secs[:n.value]], int(total.value)
+
+
+def _buffer_counts(agent):
+    """(current_size, episodes stored so far) from the buffer's host mirror: no wait."""
+    cs, nts, T = C.c_int64(), C.c_int64(), C.c_int32()
+    from . import _lib
+    _lib.check(agent.lib.hp_buffer_info(agent.buffer._dev.h, None, C.byref(cs), C.byref(nts), C.byref(T)))
+    return int(cs.value), int(nts.value) // int(T.value)
+
+
+def _epochs(agent):
+    """(capture_epoch of the agent's latest capture, the buffer's epoch, min_since)."""
+    from . import _lib
+    c, e, m = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _lib.check(agent.lib.hp_state_epochs(agent.h, agent.buffer._dev.h, C.byref(c), C.byref(e), C.byref(m)))
+    return int(c.value), int(e.value), int(m.value)
+
+
+def _known(agent):
+    """Full states this process saved from or loaded into `agent`, as delta bases: key -> (since_epoch of the buffer in THIS
+    process, episodes stored when it was captured)."""
+    if not hasattr(agent, "_state_known"):
+        agent._state_known, agent._state_lineage = {}, None
+    return agent._state_known
+
+
+def _lineage(agent, listed):
+    """The run's 64-bit id: made at an agent's first save, kept from then on and across resumes (load() takes the file's).  It is
+    a hash of that first state's checksums -- as good as random between runs, while two runs that are bit-identical agree, so
+    their files still compare equal."""
+    _known(agent)
+    if agent._state_lineage is None:
+        text = json.dumps([int(agent.comm.rank), sorted((k, v["sum"]) for k, v in listed.items())])
+        agent._state_lineage = hashlib.sha256(text.encode()).hexdigest()[:16]
+    return agent._state_lineage
+
+
+def known_base(agent, base_path):
+    """(key, since_epoch, episodes) of the full state at base_path if a delta can be taken against it now; StateError otherwise:
+    not a full state with a lineage, not saved or loaded by this agent in this process, or older than the last restore."""
+    where = os.fspath(base_path)
+    key = base_key(read_manifest(where), where=where)
+    rec = _known(agent).get(_key_tuple(key))
+    if rec is None:
+        raise StateError(f"{where}: 'lineage' {key['lineage']} / 'capture_epoch' {key['capture_epoch']} is not a state this agent "
+                         "saved or loaded in this process: which rows changed since it is not known (save a full state first)")
+    if rec[0] < _epochs(agent)[2]:
+        raise StateError(f"{where}: 'capture_epoch' {key['capture_epoch']} is older than the load_training_state done since: which "
+                         "rows changed since it is not known any more (save a full state first)")
+    return key, rec[0], rec[1]
+
+
 class PendingSave:
     """A capture in flight (`save_training_state(wait=False)`): the device part was snapshotted in stream order when this object
     was made, the host part (numpy's stream, success_rates, savetime) copied at the same moment; training may go on.
     `.result()` waits for the drain, writes the file and returns its path.  While it is outstanding a second capture on the same
-    agent raises (HP_ERR_STATE)."""
+    agent raises (HP_ERR_STATE).  base = the path of a full state this agent saved or loaded: a delta against it."""
 
-    def __init__(self, agent, path, extra=None, epoch=0, cycle=0):
+    def __init__(self, agent, path, extra=None, epoch=0, cycle=0, base=None):
         from . import _lib
-        self.agent, self.path, self._done = agent, os.fspath(path), None
+        self.agent, self.path, self._done, self.base = agent, os.fspath(path), None, None
+        if base is not None:       # refused before anything is captured
+            key, since, episodes0 = known_base(agent, base)
+            self.base = dict(key, name=os.path.basename(os.fspath(base)))
         agent._flush_updates()
         ticket, nbytes = C.c_uint64(), C.c_size_t()
-        _lib.check(agent.lib.hp_state_capture(*agent._handles(), C.byref(ticket), C.byref(nbytes)))
+        cs, self.episodes = _buffer_counts(agent)
+        if base is None:
+            _lib.check(agent.lib.hp_state_capture(*agent._handles(), C.byref(ticket), C.byref(nbytes)))
+            # (no library call that stores between the capture and this: the buffer's size is the captured one)
+            self.sections, total = _layout(agent, -1)
+        else:
+            self.max_dirty = min(self.episodes - episodes0, cs)
+            _lib.check(agent.lib.hp_state_capture_delta(*agent._handles(), since, self.max_dirty, C.byref(ticket), C.byref(nbytes)))
+            self.sections, total = _layout_delta(agent, self.max_dirty)
         self.ticket, self.nbytes = ticket.value, nbytes.value
-        # (no library call between the capture and this: the buffer's size is the captured one)
-        self.sections, total = _layout(agent, -1)
         assert total == self.nbytes, (total, self.nbytes)
+        self.capture_epoch = _epochs(agent)[0]
         st = np.random.get_state()
         gauss = agent.rng._gauss
         self.host = {"np_random": {"pos": int(st[2]), "has_gauss": int(st[3]), "cached_gaussian": float(st[4])},
@@ -271,43 +496,70 @@ class PendingSave:
         if self._done is not None:
             return self._done
         from . import _lib
-        agent = self.agent
+        agent, delta = self.agent, self.base is not None
         blob = np.empty(self.nbytes, np.uint8)
-        sums = (C.c_uint64 * (2 * _lib.STATE_SECTIONS))()
+        sums = (C.c_uint64 * (2 * len(self.sections)))()
         done = C.c_int32()
         fetch = object.__getattribute__(agent.lib, "_cdll").hp_state_fetch      # no flush of deferred updates in front of a wait
-        _lib.check(fetch(agent.h, self.ticket, 1, blob.ctypes.data_as(C.c_void_p), blob.size, sums, C.byref(done)))
-        off_counters = next(o for n, _, _, o in self.sections if n == "buffer_counters")
-        cs = int(blob[off_counters:off_counters + 8].view("<i8")[0])
+        try:
+            _lib.check(fetch(agent.h, self.ticket, 1, blob.ctypes.data_as(C.c_void_p), blob.size, sums, C.byref(done)))
+        except ValueError as e:
+            raise StateError(f"save: {e}") from e
+        offs = {n: o for n, _, _, o in self.sections}
+        cs = int(blob[offs["buffer_counters"]:offs["buffer_counters"] + 8].view("<i8")[0])
         dims = _dims_of(agent, cs)
         want = expected_shapes(dims)
+        n_dirty = 0
+        if delta:
+            n_dirty, overflow, cap, _ = (int(x) for x in blob[offs["buffer_delta_header"]:offs["buffer_delta_header"] + 32].view("<i8"))
+            if overflow or n_dirty > self.max_dirty or cap != self.capture_epoch:
+                raise StateError(f"save: array 'buffer_delta_header' says n_dirty {n_dirty}, overflow {overflow}, capture_epoch {cap}; "
+                                 f"the host sized the delta for {self.max_dirty} episodes at capture_epoch {self.capture_epoch}")
+            want.update(delta_shapes(dims, n_dirty))
         arrays, listed = {}, {}
         for i, (name, dt, count, off) in enumerate(self.sections):
-            a = blob[off:off + count * np.dtype(dt).itemsize].view(dt).reshape(want[name][1])
             dev = (int(sums[2 * i]), int(sums[2 * i + 1]))
+            used = int(np.prod(want[name][1])) if name in want else count     # a delta's slot / row sections: the used prefix
+            a = blob[off:off + used * np.dtype(dt).itemsize].view(dt)
             if checksum(a) != dev:      # what left the device is what the device summed
                 raise StateError(f"save: array '{name}' arrived with sums {checksum(a)}, the device computed {dev}")
-            arrays[name] = a
-            listed[name] = {"dtype": dt, "shape": list(a.shape), "sum": [dev[0], dev[1]]}
+            if name == "buffer_delta_header":
+                continue                # its fields go into the manifest
+            arrays[name] = a.reshape(want[name][1])
+            listed[name] = {"dtype": dt, "shape": list(arrays[name].shape), "sum": [dev[0], dev[1]]}
         manifest = {"format": FORMAT_VERSION, "dims": dims, "rank": int(agent.comm.rank), "world_size": int(agent.comm.world_size),
-                    "abi": int(_lib.ABI_VERSION), "arrays": listed, **self.host}
+                    "abi": int(_lib.ABI_VERSION), "arrays": listed, "lineage": _lineage(agent, listed), "capture_epoch": self.capture_epoch,
+                    **self.host}
+        if delta:
+            manifest.update({"format": DELTA_FORMAT_VERSION, "kind": "delta", "n_dirty": n_dirty, "base": self.base})
+            rows = sum(arrays[n].nbytes for n in DELTA_ROW_ARRAYS)
+            per_ep = 8 * ((dims["T"] + 1) * (dims["obs"] + dims["goal"]) + dims["T"] * (dims["goal"] + dims["action"]))
+            assert rows == n_dirty * per_ep, (rows, n_dirty, per_ep)
         arrays.update(self.host_arrays)
         self._done = write_state(self.path, arrays, manifest)
+        if not delta:                   # from now on a delta can be taken against this file
+            _known(agent)[_key_tuple(base_key(manifest))] = (self.capture_epoch, self.episodes)
         return self._done
 
 
-def save(agent, path, wait=True, extra=None, epoch=0, cycle=0):
-    h = PendingSave(agent, path, extra=extra, epoch=epoch, cycle=cycle)
+def save(agent, path, wait=True, extra=None, epoch=0, cycle=0, base=None):
+    h = PendingSave(agent, path, extra=extra, epoch=epoch, cycle=cycle, base=base)
     return h.result() if wait else h
 
 
-def load(agent, path, verify_host=False):
+def load(agent, path, verify_host=False, base=None):
     """Restore `agent` (its networks, optimizers, normalizers, random stream and replay buffer) and the host side of the run
     from a state file; returns (extra bytes, manifest).  A file that does not fit the agent -- dims, capacity, T, rank, world size
-    -- or whose bytes do not sum on the DEVICE to what the manifest records is refused before anything is changed."""
+    -- or whose bytes do not sum on the DEVICE to what the manifest records is refused before anything is changed.  A delta is
+    composed with its base first (`base`, default: the name the delta records, beside it), on the host, and then restored like
+    the full state it stands for."""
     from . import _lib
-    arrays, manifest = read_state(path)
     where = os.fspath(path)
+    manifest = read_manifest(where)
+    if is_delta(manifest):
+        arrays, manifest = compose(base or default_base(where, manifest), where, sums=True)
+    else:
+        arrays, manifest = read_state(path)
     if int(manifest.get("abi", -1)) != _lib.ABI_VERSION:
         raise StateError(f"{where}: written with library ABI {manifest.get('abi')}, this build has {_lib.ABI_VERSION}")
     for key, have in (("rank", agent.comm.rank), ("world_size", agent.comm.world_size)):
@@ -346,6 +598,13 @@ def load(agent, path, verify_host=False):
         _lib.check(agent.lib.hp_state_restore(*agent._handles(), C.byref(dims), blob.ctypes.data_as(C.c_void_p), blob.size, sums))
     except ValueError as e:
         raise StateError(f"{where}: {e}") from e
+    # Delta bases: the stamps started over, so every state this agent knew is now older than the restore (known_base says so);
+    # the state just loaded (a full file, or the full state a delta stands for -- `flatten` writes that one out) is known from here
+    # on, and the run keeps its lineage
+    known = _known(agent)
+    if "lineage" in manifest and "capture_epoch" in manifest:
+        agent._state_lineage = str(manifest["lineage"])
+        known[_key_tuple(base_key(manifest))] = (_epochs(agent)[2], _buffer_counts(agent)[1])
     # host side of the run
     r = manifest["np_random"]
     np.random.set_state(("MT19937", arrays["np_random_key"], int(r["pos"]), int(r["has_gauss"]), float(r["cached_gaussian"])))
@@ -358,18 +617,30 @@ def load(agent, path, verify_host=False):
     return arrays["extra"].tobytes(), manifest
 
 
+_USAGE = ("usage: python -m rl_arm_under_sparse_reward_amd.train_state verify FILE [--base BASE]\n"
+          "       python -m rl_arm_under_sparse_reward_amd.train_state flatten BASE DELTA OUT")
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    if len(argv) != 2 or argv[0] != "verify":
-        print("usage: python -m rl_arm_under_sparse_reward_amd.train_state verify FILE", file=sys.stderr)
+    base = None
+    if len(argv) == 4 and argv[0] == "verify" and argv[2] == "--base":
+        base, argv = argv[3], argv[:2]
+    if not ((len(argv) == 2 and argv[0] == "verify") or (len(argv) == 4 and argv[0] == "flatten")):
+        print(_USAGE, file=sys.stderr)
         return 2
     try:
-        m = verify(argv[1])
+        if argv[0] == "flatten":
+            flatten(argv[1], argv[2], argv[3])
+            m, what = verify(argv[3]), f"{argv[3]} = {argv[1]} + {argv[2]}"
+        else:
+            m, what = verify(argv[1], base=base), argv[1]
     except StateError as e:
         print(f"FAILED: {e}", file=sys.stderr)
         return 1
     d = m["dims"]
-    print(f"ok: {argv[1]}: format {m['format']}, rank {m['rank']}/{m['world_size']}, epoch {m['epoch']}, "
+    kind = f"delta of {m['n_dirty']} episodes over {base or m['base']['name']}, " if is_delta(m) else ""
+    print(f"ok: {what}: format {m['format']}, {kind}rank {m['rank']}/{m['world_size']}, epoch {m['epoch']}, "
           f"{d['current_size']}/{d['capacity']} episodes of T={d['T']}, obs/goal/action {d['obs']}/{d['goal']}/{d['action']}, "
           f"{len(m['arrays'])} arrays verified")
     return 0

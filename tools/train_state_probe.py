@@ -8,6 +8,12 @@
     python tools/train_state_probe.py state                       checksum kernel GB/s on the buffer section, wall time of a full
                                                                   save and a full load at that size
 
+    python tools/train_state_probe.py delta [--root TREE]         full against delta saves at that size (profiles/
+                                                                  train_state_delta.json): the learner-stream part of a capture
+                                                                  (enqueue until the learner's stream is idle again) and
+                                                                  capture-to-file, for a full state and -- where the tree has
+                                                                  them -- for a delta with --dirty episodes stored since the base
+
 --root TREE imports the package from another checkout (e.g. the parent commit, built), so that (a) parent, (b) this commit without a
 capture and (c) with captures are measured by the same script; each prints one JSON line.  Every figure is the median over
 --repeats timed blocks, with the min..max spread next to it.
@@ -118,17 +124,64 @@ def run_state(a):
                       "save_ms": spread(saves), "load_ms": spread(loads), "verify_cpu_ms": round(verify_ms, 1)}))
 
 
+def run_delta(a):
+    agent, eps = make_agent(a.episodes)
+    lib, ticket, nbytes = agent.lib, C.c_uint64(), C.c_size_t()
+    has_delta = hasattr(object.__getattribute__(lib, "_cdll"), "hp_state_capture_delta")
+
+    def learner_part(capture):
+        """ms from the capture call until the learner's stream is idle again; the ticket is abandoned outside the clock"""
+        out = []
+        for _ in range(a.repeats + 1):
+            agent.ctx.synchronize()
+            t0 = time.perf_counter()
+            assert capture() == 0
+            agent.ctx.synchronize()
+            out.append((time.perf_counter() - t0) * 1e3)
+            assert lib.hp_state_fetch(agent.h, ticket.value, 1, None, 0, None, None) == 0
+        return spread(out[1:])
+
+    def to_file(path, **kw):
+        out = []
+        for _ in range(a.repeats + 1):
+            agent.ctx.synchronize()
+            t0 = time.perf_counter(); agent.save_training_state(path, **kw); out.append((time.perf_counter() - t0) * 1e3)
+        return spread(out[1:])
+
+    res = {"probe": "delta", "root": a.root or ".", "source": fingerprint(a.root or REPO), "episodes": a.episodes, "T": 100}
+    with tempfile.TemporaryDirectory() as d:
+        base = os.path.join(d, "state.npz")
+        res["full"] = {"learner_stream_ms": learner_part(lambda: lib.hp_state_capture(*agent._handles(), C.byref(ticket), C.byref(nbytes))),
+                       "captured_bytes": int(nbytes.value), "capture_to_file_ms": to_file(base), "file_bytes": os.path.getsize(base)}
+        if has_delta:
+            from rl_arm_under_sparse_reward_amd import train_state as ts
+            for _ in range(a.dirty // 2):
+                agent.train_cycle(eps)
+            since = ts.known_base(agent, base)[1]
+            res["delta"] = {"episodes_stored_since_base": a.dirty // 2 * 2,
+                            "learner_stream_ms": learner_part(lambda: lib.hp_state_capture_delta(
+                                *agent._handles(), since, a.dirty // 2 * 2, C.byref(ticket), C.byref(nbytes))),
+                            "captured_bytes": int(nbytes.value)}
+            path = os.path.join(d, "state.delta.npz")
+            res["delta"]["capture_to_file_ms"] = to_file(path, base=base)
+            res["delta"]["file_bytes"] = os.path.getsize(path)
+            res["delta"]["n_dirty"] = int(ts.read_manifest(path)["n_dirty"])
+            t0 = time.perf_counter(); ts.compose(base, path); res["delta"]["compose_cpu_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+    print(json.dumps(res))
+
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
-    p.add_argument("probe", choices=["cycles", "state"])
+    p.add_argument("probe", choices=["cycles", "state", "delta"])
     p.add_argument("--root", default=None)
     p.add_argument("--capture", type=int, default=0, help="capture behind every N-th cycle (0: never)")
     p.add_argument("--episodes", type=int, default=5000)
     p.add_argument("--cycles", type=int, default=50)
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--repeats", type=int, default=7)
+    p.add_argument("--dirty", type=int, default=100, help="delta: episodes stored since the base (two per cycle)")
     a = p.parse_args()
     sys.path.insert(0, os.path.abspath(a.root) if a.root else REPO)
-    (run_cycles if a.probe == "cycles" else run_state)(a)
+    {"cycles": run_cycles, "state": run_state, "delta": run_delta}[a.probe](a)
