@@ -379,6 +379,31 @@ int hp_rollout_step_streams(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_no
                             const double *obs_dev, const double *ag_dev, const double *g_dev, int32_t explore, double noise_eps,
                             double random_eps, double qn, double clip_abs, float *actions_f32_dev);
 
+/* ---- whole episodes in one launch, for environments the library steps itself -------------------------------------------------
+ * For an environment whose dynamics the library can evaluate (an analytic, vectorised simulator) the T timesteps of a wave need
+ * no launch boundary: hp_rollout_episodes collects the wave selected by hp_rollout_begin -- `rows` episodes, row i on stream i --
+ * in ONE launch.  Workgroup b owns rows 4b .. 4b+3 and loops over t: observe, record obs / ag / g [i,t], the policy of
+ * hp_agent_act_dev (clip_obs = 0), exploration as hp_rollout_step_streams (explore != 0) or the noise-free branch of
+ * hp_rollout_step (explore == 0: streams may be NULL, no stream is touched), record actions[i,t], step.  Then row T is recorded,
+ * success_dev[i] (float32 [rows]) receives is_success of the last step and the environment's final state is written back.  Block,
+ * stream states and environment state are bit for bit what T per-step launches around the same arithmetic in torch leave.
+ * Asynchronous on the context's stream, capturable.  Needs the agent the fused policy kernel serves (hidden 256, padded input
+ * width <= 48, at most 4 action components: hp_agent_engine reports 8); any other agent is refused and keeps the per-step calls.
+ * HP_ERR_INVALID names the field for: an unknown kind, dimensions of block / agent / normalizers / environment that differ, a
+ * wave wider than the stream array, explore != 0 without streams, an agent of another shape.
+ * Adding an environment kind is a build-time change in two places: one struct in csrc/env_device.h (load, observe, step,
+ * is_success, store over the arrays of hp_env_desc, with its dimensions as constants) and one case in the dispatch of
+ * hp_rollout_episodes (csrc/rollout.hip) next to HP_ENV_POINT_MASS; the kernel is a template over that struct. */
+enum { HP_ENV_POINT_MASS = 1 };
+typedef struct {
+    int32_t kind, reserved;
+    double params[8];         /* point mass: [0] step_scale, [1] distance_threshold */
+    double *state_dev[4];     /* point mass: [0] pos [n][3], [1] vel [n][3], [2] goal [n][3]; read at entry, pos / vel written at exit */
+} hp_env_desc;
+int hp_rollout_episodes(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, hp_rng_streams *streams,
+                        const hp_env_desc *env, int32_t explore, double noise_eps, double random_eps, double qn,
+                        double clip_abs, float *success_dev);
+
 /* Policy calls that do not queue behind training: hp_agent_policy_snapshot copies the online actor and both normalizers'
  * statistics (stream-ordered with the updates, no host wait); hp_agent_act_snapshot evaluates the most recent COMPLETE
  * snapshot on a second stream, so a feeder can step its environments while a training cycle runs (its policy lags the

@@ -50,6 +50,14 @@ class StateSection(C.Structure):
                 ("offset", C.c_int64)]
 
 
+class EnvDesc(C.Structure):
+    """hp_env_desc: an environment the library steps itself (hp_rollout_episodes)"""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("params", C.c_double * 8), ("state_dev", C.c_void_p * 4)]
+
+
+ENV_POINT_MASS = 1
+
+
 class StateDims(C.Structure):
     _fields_ = [("obs_dim", C.c_int32), ("goal_dim", C.c_int32), ("act_dim", C.c_int32), ("hidden", C.c_int32),
                 ("T", C.c_int32), ("reserved", C.c_int32), ("capacity", C.c_int64), ("current_size", C.c_int64)]
@@ -179,6 +187,8 @@ PROTOTYPES = {
     "hp_rollout_step_streams": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
                                           C.c_void_p]),
+    "hp_rollout_episodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EnvDesc), C.c_int32,
+                                      C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "hp_agent_policy_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hp_agent_act_snapshot": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int64, C.c_double, f32p]),
     "hp_agent_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,

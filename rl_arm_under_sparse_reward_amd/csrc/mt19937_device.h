@@ -63,17 +63,31 @@ __device__ __forceinline__ uint32_t mt_twist_one(const uint32_t *src, const uint
 
 // Every cooperative step of the walk takes the workgroup's width as a compile-time thread count: MT_THREADS for the index draws,
 // one wave for the exploration draws (mt19937_wave.h), MTP_JUMP_THREADS for the segment fill (rng_parallel.hip).
+// NT == 64 is the one-wave walk.  Its thread index is the lane inside the wavefront and its barrier is wave-local, so that several
+// walks -- one ring each -- can run side by side on the waves of a wider workgroup (k_rollout_episodes) with trip counts that
+// differ from wave to wave: no wave ever waits for another.  A wave's LDS operations execute in order, so a value one lane wrote
+// is there for another lane's later read; the fences keep the compiler from moving LDS accesses across the point.
+template <int NT> __device__ __forceinline__ int mt_tid() { return NT == 64 ? (int)(threadIdx.x & 63) : (int)threadIdx.x; }
+template <int NT> __device__ __forceinline__ void mt_barrier() {
+    if constexpr (NT == 64) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+        __syncthreads();
+    }
+}
 // One phase of the twist, words [lo, hi) of the new block: a width that covers a phase writes it in one pass, without a loop,
-// behind the LDS-only barrier; a narrower one (the one-wave walk) loops and keeps the full barrier it has always had.
+// behind the LDS-only barrier; a narrower one (the one-wave walk) loops and ends the phase with mt_barrier.
 template <int NT>
 __device__ __forceinline__ void mt_twist_phase(const uint32_t *src, uint32_t *dst, int lo, int hi) {
-    const int tid = threadIdx.x;
+    const int tid = mt_tid<NT>();
     if constexpr (NT >= MT_N - MT_M) {
         if (tid < hi - lo) dst[lo + tid] = mt_twist_one(src, dst, lo + tid);
         mt_sync();
     } else {
         for (int k = lo + tid; k < hi; k += NT) dst[k] = mt_twist_one(src, dst, k);
-        __syncthreads();
+        mt_barrier<NT>();
     }
 }
 
@@ -104,11 +118,11 @@ template <int NT = MT_THREADS>
 __device__ __forceinline__ void mt_load(MtWg &g, const MtState *st, uint32_t (*ring)[MT_N], int *ibuf) {
     g.blk = ring;
     g.ibuf = ibuf;
-    for (int k = threadIdx.x; k < MT_N; k += NT) ring[0][k] = st->key[k];
+    for (int k = mt_tid<NT>(); k < MT_N; k += NT) ring[0][k] = st->key[k];
     g.cursor = st->pos;
     g.nblk = 1;
     g.flip = 0;
-    __syncthreads();
+    mt_barrier<NT>();
 }
 
 // numpy keeps (block, pos) with pos in [0,624]; a cursor on a block boundary belongs to the
@@ -133,9 +147,9 @@ __device__ __forceinline__ void mt_commit(MtState *st, long long cursor, Blocks 
     mt_final_block(cursor, b, pos);
     if (b > 0) {
         const uint32_t *src = block_at(b);
-        for (int k = threadIdx.x; k < MT_N; k += NT) st->key[k] = src[k];
+        for (int k = mt_tid<NT>(); k < MT_N; k += NT) st->key[k] = src[k];
     }
-    if (threadIdx.x == 0) {
+    if (mt_tid<NT>() == 0) {
         st->pos = pos;
         if (gauss) {
             st->has_gauss = has_gauss;
@@ -146,7 +160,7 @@ __device__ __forceinline__ void mt_commit(MtState *st, long long cursor, Blocks 
 
 template <int NT = MT_THREADS>
 __device__ __forceinline__ void mt_store(const MtWg &g, MtState *st, int has_gauss = 0, const double *gauss = nullptr) {
-    __syncthreads();
+    mt_barrier<NT>();
     mt_commit<NT>(st, g.cursor, [&](long long b) { return g.blk[b & 3]; }, has_gauss, gauss);
 }
 

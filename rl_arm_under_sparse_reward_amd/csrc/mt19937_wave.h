@@ -2,8 +2,9 @@
 //
 // These are the three draws of ddpg_agent._select_actions (:174-184).  Their word consumption is data dependent twice over --
 // the polar method rejects pairs, and a cached second normal carries from one randn call into the next -- and the draws of one
-// environment are only a few dozen words, so the walk is made by ONE wave (a 64-thread workgroup: every barrier below is a
-// single-wave barrier) on the LDS ring of mt19937_device.h:
+// environment are only a few dozen words, so the walk is made by ONE wave on the LDS ring of mt19937_device.h.  The wave is a
+// 64-thread workgroup of its own or one wave of a wider workgroup that runs one walk per wave, each on its own ring: the lane is
+// the lane inside the wavefront and every barrier below is wave-local (mt_tid<64>, mt_barrier<64>):
 //   * all lanes hold the same cursor / cached normal: control flow is wave-uniform, nothing is exchanged between lanes but
 //     ballots and one shuffle;
 //   * randn: lane k evaluates the polar attempt at cursor + 4 k (an attempt always consumes two doubles, accepted or not); a
@@ -18,13 +19,20 @@
 
 #define MW_THREADS 64
 
-// The one-wave walk: an MtWg of MW_THREADS threads + numpy's cached second normal.  Constructing one is mt_load and store() is
-// mt_store: both are cooperative and hold a workgroup barrier, so both run under workgroup-uniform control flow only.
+__device__ __forceinline__ int mw_lane() { return mt_tid<MW_THREADS>(); }
+__device__ __forceinline__ void mw_sync() { mt_barrier<MW_THREADS>(); }
+
+// The one-wave walk: an MtWg of MW_THREADS threads + numpy's cached second normal.  Constructing one (or load()) is mt_load and
+// store() is mt_store: both are cooperative across the wave, so both run under wave-uniform control flow only.
 struct MwState {
     MtWg g;
     int has_gauss;
     double gauss;
-    __device__ __forceinline__ MwState(const MtState *st, uint32_t (*ring)[MT_N]) : has_gauss(st->has_gauss), gauss(st->gauss) {
+    __device__ __forceinline__ MwState() : has_gauss(0), gauss(0.0) {}
+    __device__ __forceinline__ MwState(const MtState *st, uint32_t (*ring)[MT_N]) { load(st, ring); }
+    __device__ __forceinline__ void load(const MtState *st, uint32_t (*ring)[MT_N]) {
+        has_gauss = st->has_gauss;
+        gauss = st->gauss;
         mt_load<MW_THREADS>(g, st, ring, nullptr);
     }
     __device__ __forceinline__ void store(MtState *st) const { mt_store<MW_THREADS>(g, st, has_gauss, &gauss); }
@@ -38,7 +46,7 @@ __device__ __forceinline__ double mw_double_at(const MtWg &g, long long abs) {
 // lane computed it.  A pending cached normal is value 0; an odd remainder leaves its second normal cached.
 template <class Emit>
 __device__ __forceinline__ void mw_draw_normal(MwState &w, long long count, Emit emit) {
-    const int lane = threadIdx.x;
+    const int lane = mw_lane();
     long long done = 0;
     if (count > 0 && w.has_gauss) {
         if (lane == 0) emit(0, w.gauss);
@@ -85,7 +93,8 @@ __device__ __forceinline__ void mw_draw_normal(MwState &w, long long count, Emit
 template <class Emit>
 __device__ __forceinline__ void mw_draw_uniform(MwState &w, double low, double range, int count, Emit emit) {
     mt_ensure<MW_THREADS>(w.g, w.g.cursor + 2 * count);
-    if ((int)threadIdx.x < count) emit((int)threadIdx.x, __dadd_rn(low, __dmul_rn(range, mw_double_at(w.g, w.g.cursor + 2 * threadIdx.x))));
+    const int lane = mw_lane();
+    if (lane < count) emit(lane, __dadd_rn(low, __dmul_rn(range, mw_double_at(w.g, w.g.cursor + 2 * lane))));
     w.g.cursor += 2 * count;
 }
 

@@ -14,8 +14,27 @@
 // They stay two because they have opposite shapes: the policy is wide (every row independent) and the draw is one sequential
 // walk whose word count is data dependent; folded into one launch the walk would either wait behind a grid-wide hand-off inside
 // the kernel or run once per workgroup.  Recording rides along with the walk for free.
-#include "agent.h"
+//
+// A whole wave is ONE launch (k_rollout_episodes, hp_rollout_episodes) when nothing is left that needs a launch boundary per
+// timestep: the environment's dynamics are device functions of the library (env_device.h) and every row draws from its own stream
+// (or nothing is drawn).  Workgroup b owns rows 4b .. 4b+3 and loops over t by itself -- no cross-workgroup hand-off, no grid-wide
+// wait, no host in the loop -- through the SAME device functions: the policy slab of k_policy_slab8 (s8_policy_slab), ro_explore_row
+// and the noise-free branch of k_rollout_step (ro_plain_row).
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wundefined-inline"   // agent_device.h declares the 32-row engine's fragment map, which no code here calls
+#include "agent_device.h"
+#pragma clang diagnostic pop
+#include "env_device.h"
 #include "mt19937_wave.h"
+
+// the 4-row policy slab's device functions (no kernel of slab8.h is compiled here)
+#define S8_DEVICE_ONLY
+#define S8_NRG 1
+#define S8_NS s8ro
+#include "slab8.h"
+#undef S8_NRG
+#undef S8_NS
+#undef S8_DEVICE_ONLY
 
 #define RO_MAX_ACT 16
 
@@ -29,6 +48,13 @@ struct hp_rollout {
     int64_t o_ag = 0, o_g = 0, o_act = 0, elems = 0;   // offsets in float64 elements (feeder._Layout)
 };
 
+// what turns a policy output into an action: the constants of ddpg_agent._select_actions (:174-184) and of the +-0.15 clip (:118-119)
+struct ExploreArgs {
+    int ad;
+    double noise_scale;            // noise_eps * action_max (the reference's float64 product)
+    double amax, random_eps, qn, clip_abs;
+};
+
 struct RolloutStepArgs {
     const double *obs, *ag, *g;    // this timestep's rows [rows][dim] (g == nullptr: the closing record of row T)
     double *b_obs, *b_ag, *b_g, *b_act;   // block arrays, already offset to episode `first`
@@ -36,8 +62,7 @@ struct RolloutStepArgs {
     MtState *st;
     int rows, T, t, od, gd, ad;
     int explore, record_blocks;
-    double noise_scale;            // noise_eps * action_max (the reference's float64 product)
-    double amax, random_eps, qn, clip_abs;
+    ExploreArgs x;
 };
 
 // element e of this timestep's rows -> its place in the block
@@ -58,21 +83,23 @@ __device__ __forceinline__ void ro_record(const RolloutStepArgs &A, long long e0
     }
 }
 
-// ddpg_agent._select_actions (:174-184) for row i of the wave, out of the stream loaded into w: randn(act), uniform(act),
-// binomial(1).  Shared by the single-stream walk and the per-environment form, so one stream gives the same bits in both.
-__device__ __forceinline__ void ro_explore_row(const RolloutStepArgs &A, MwState &w, double *zs, int i) {
-    const int lane = threadIdx.x, ad = A.ad;
+// ddpg_agent._select_actions (:174-184) for one row, out of the stream loaded into w: randn(act), uniform(act), binomial(1).
+// pi: the row's policy outputs in, its actions out (float32 [ad]); act: its place in the block (float64 [ad]); zs: ad doubles of
+// LDS of this wave's own.  One wave, wave-local barriers (mt19937_wave.h).  Shared by the single-stream walk, the per-environment
+// form and the whole-episode kernel, so one stream gives the same bits in all three.
+__device__ __forceinline__ void ro_explore_row(const ExploreArgs &A, MwState &w, double *zs, float *pi, double *act) {
+    const int lane = mw_lane(), ad = A.ad;
     const float amax = (float)A.amax, clipf = (float)A.clip_abs;
     // :177 action += noise_eps * max_action * randn(act): float32 array += float64 array, rounded once
     mw_draw_normal(w, ad, [&](long long k, double z) { zs[k] = z; });
-    __syncthreads();
+    mw_sync();
     float a = 0.f;
     if (lane < ad) {
-        a = A.pi[(long long)i * ad + lane];
+        a = pi[lane];
         a = (float)__dadd_rn((double)a, __dmul_rn(A.noise_scale, zs[lane]));
         a = fminf(fmaxf(a, -amax), amax);                                          // :178 np.clip in float32
     }
-    __syncthreads();   // zs is rewritten by the next environment's normals
+    mw_sync();   // zs is rewritten by the next normals
     double ra = 0.0;
     mw_draw_uniform(w, -A.amax, __dsub_rn(A.amax, -A.amax), ad, [&](int, double u) { ra = u; });   // :179-180
     const int b = mw_draw_binomial1(w, A.random_eps, A.qn);                        // :182
@@ -80,9 +107,17 @@ __device__ __forceinline__ void ro_explore_row(const RolloutStepArgs &A, MwState
         // :182 action += binomial * (random_actions - action), float64 arithmetic rounded to float32 once
         a = (float)__dadd_rn((double)a, __dmul_rn((double)b, __dsub_rn(ra, (double)a)));
         if (A.clip_abs > 0) a = fminf(fmaxf(a, -clipf), clipf);                    // :118-119, float32
-        A.pi[(long long)i * ad + lane] = a;
-        A.b_act[((long long)i * A.T + A.t) * ad + lane] = (double)a;
+        pi[lane] = a;
+        act[lane] = (double)a;
     }
+}
+
+// ddpg_agent.collect_episodes with explore=False for one element: action = pi.astype(float64), clipped in float64 from epoch 100 on
+__device__ __forceinline__ void ro_plain_element(const ExploreArgs &A, float *pi, double *act) {
+    double a = (double)*pi;
+    if (A.clip_abs > 0) a = fmin(fmax(a, -A.clip_abs), A.clip_abs);
+    *act = a;
+    *pi = (float)a;
 }
 
 __global__ __launch_bounds__(MW_THREADS) void k_rollout_step(const RolloutStepArgs A) {
@@ -96,18 +131,14 @@ __global__ __launch_bounds__(MW_THREADS) void k_rollout_step(const RolloutStepAr
     if (!A.pi) return;   // closing record only
     const int ad = A.ad;
     if (!A.explore) {
-        // ddpg_agent.collect_episodes with explore=False: action = pi.astype(float64), clipped in float64 from epoch 100 on
         for (long long e = lane; e < (long long)A.rows * ad; e += MW_THREADS) {
-            double a = (double)A.pi[e];
-            if (A.clip_abs > 0) a = fmin(fmax(a, -A.clip_abs), A.clip_abs);
             const long long i = e / ad, j = e - i * ad;
-            A.b_act[(i * A.T + A.t) * ad + j] = a;
-            A.pi[e] = (float)a;
+            ro_plain_element(A.x, A.pi + e, A.b_act + (i * A.T + A.t) * ad + j);
         }
         return;
     }
     MwState w(A.st, ring);
-    for (int i = 0; i < A.rows; ++i) ro_explore_row(A, w, zs, i);
+    for (int i = 0; i < A.rows; ++i) ro_explore_row(A.x, w, zs, A.pi + (long long)i * ad, A.b_act + ((long long)i * A.T + A.t) * ad);
     w.store(A.st);
 }
 
@@ -128,8 +159,93 @@ __global__ __launch_bounds__(MW_THREADS) void k_rollout_step_streams(const Rollo
     const int i = blockIdx.x;
     MtState *st = A.st + i;
     MwState w(st, ring);
-    ro_explore_row(A, w, zs, i);
+    ro_explore_row(A.x, w, zs, A.pi + (long long)i * A.ad, A.b_act + ((long long)i * A.T + A.t) * A.ad);
     w.store(st);
+}
+
+// ---- whole episodes in one launch ------------------------------------------------------------------------------------------
+struct EpisodesArgs {
+    PolicyArgs P;                  // the policy call of hp_agent_act_dev (obs / g / x / actions unused: the rows come from LDS)
+    double *b_obs, *b_ag, *b_g, *b_act;   // block arrays, already offset to episode `first`
+    MtState *st;                   // stream of row 0 of the wave (explore != 0)
+    int rows, T, explore;
+    ExploreArgs x;
+    hp_env_desc env;
+    float *success;                // [rows]
+};
+
+// what a workgroup of k_rollout_episodes keeps beside the policy slab: one environment, one row of observations, one action row
+// and -- exploring -- one MT19937 ring per row
+template <class Env>
+struct EpisodesLds {
+    Env env[4];
+    double obs[4][Env::OBS], ag[4][Env::GOAL], g[4][Env::GOAL];
+    double zs[4][RO_MAX_ACT];
+    float pi[4][RO_MAX_ACT];
+    uint32_t ring[4][4][MT_N];
+};
+
+// LDS: 111552 bytes of policy slab + 39936 of rings + the rows: one workgroup per CU, which is what the policy slab's weight ring
+// asks for anyway.  Wave r < 4 owns row r outside the policy slab: its lane 0 steps the environment, its lanes j < act_dim hold
+// action j (s8_policy_slab's emit), and the whole wave walks the row's stream.  Barriers per timestep: one __syncthreads() behind
+// observe, the policy slab's own, none in the draws (wave-local: the rejection loops of different rows need not agree on a trip count).
+template <class Env>
+__global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_rollout_episodes(const EpisodesArgs A) {
+    __shared__ s8ro::PolicyLds L;
+    __shared__ EpisodesLds<Env> E;
+    constexpr int OD = Env::OBS, GD = Env::GOAL, AD = Env::ACT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const long long row0 = (long long)blockIdx.x * 4;
+    const int nrows = A.rows - row0 < 4 ? (int)(A.rows - row0) : 4;
+    const bool mine = wave < nrows;              // this wave owns row row0 + wave
+    const long long row = row0 + wave;
+    const int T = A.T;
+    MwState w;
+    if (mine) {
+        if (lane == 0) E.env[wave].load(A.env, row);
+        if (A.explore) w.load(A.st + row, E.ring[wave]);
+    }
+    // record the rows observed into E at timestep t (t == T: the closing record, no goal row)
+    auto record = [&](int t) {
+        const int per = OD + GD + (t < T ? GD : 0);
+        for (int e = tid; e < nrows * per; e += S8_THREADS) {
+            const int r = e / per, c = e - r * per;
+            const long long i = row0 + r;
+            if (c < OD) A.b_obs[(i * (T + 1) + t) * OD + c] = E.obs[r][c];
+            else if (c < OD + GD) A.b_ag[(i * (T + 1) + t) * GD + (c - OD)] = E.ag[r][c - OD];
+            else A.b_g[(i * T + t) * GD + (c - OD - GD)] = E.g[r][c - OD - GD];
+        }
+    };
+    for (int t = 0; t < T; ++t) {
+        if (mine && lane == 0) E.env[wave].observe(E.obs[wave], E.ag[wave], E.g[wave]);
+        __syncthreads();
+        record(t);
+        s8ro::s8_policy_slab(A.P, L, (size_t)row0,
+            [&](int r, int c) -> float {
+                if (c < OD) return s8ro::s8_policy_input(E.obs[r][c], A.P.clip_obs, A.P.onz->mean[c], A.P.onz->std[c], A.P.clip_o);
+                const int j = c - OD;
+                return s8ro::s8_policy_input(E.g[r][j], A.P.clip_obs, A.P.gnz->mean[j], A.P.gnz->std[j], A.P.clip_g);
+            },
+            [&](int r, int j, float a) { E.pi[r][j] = a; });
+        if (mine) {
+            mw_sync();
+            double *act = A.b_act + (row * T + t) * AD;
+            if (A.explore) ro_explore_row(A.x, w, E.zs[wave], E.pi[wave], act);
+            else if (lane < AD) ro_plain_element(A.x, &E.pi[wave][lane], act + lane);
+            mw_sync();
+            if (lane == 0) E.env[wave].step(E.pi[wave]);
+        }
+    }
+    if (mine && lane == 0) E.env[wave].observe(E.obs[wave], E.ag[wave], E.g[wave]);
+    __syncthreads();
+    record(T);
+    if (mine) {
+        if (lane == 0) {
+            A.success[row] = E.env[wave].is_success() ? 1.f : 0.f;
+            E.env[wave].store(A.env, row);
+        }
+        if (A.explore) w.store(A.st + row);
+    }
 }
 
 static int rollout_launch(hp_rollout *ro, RolloutStepArgs &A, int t, bool per_env_streams = false) {
@@ -169,10 +285,23 @@ static int rollout_step(const char *entry, hp_rollout *ro, hp_agent *a, hp_norm 
     A.pi = actions_f32_dev;
     A.st = st;
     A.explore = explore ? 1 : 0;
-    A.amax = amax;
-    A.noise_scale = noise_eps * amax;
-    A.random_eps = random_eps; A.qn = qn; A.clip_abs = clip_abs;
+    A.x.ad = ro->ad;
+    A.x.amax = amax;
+    A.x.noise_scale = noise_eps * amax;
+    A.x.random_eps = random_eps; A.x.qn = qn; A.x.clip_abs = clip_abs;
     return rollout_launch(ro, A, t, per_env_streams && explore);   // explore == 0 touches no stream: the single-stream kernel's path
+}
+
+// the launch of one environment kind; dimensions of the kind against the block's first
+template <class Env>
+static int rollout_episodes_launch(hp_rollout *ro, EpisodesArgs &A) {
+    HP_REQUIRE(ro->od == Env::OBS && ro->gd == Env::GOAL && ro->ad == Env::ACT, HP_ERR_INVALID,
+               "hp_rollout_episodes: env->kind %d has dimensions %d / %d / %d, the block has %d / %d / %d", (int)A.env.kind, Env::OBS,
+               Env::GOAL, Env::ACT, ro->od, ro->gd, ro->ad);
+    static_assert(Env::ACT <= 4 && Env::ACT <= RO_MAX_ACT && Env::OBS + Env::GOAL <= S8_LDX, "an environment of the policy slab's shape");
+    hipLaunchKernelGGL(k_rollout_episodes<Env>, dim3((unsigned)((ro->rows + 3) / 4)), dim3(S8_THREADS), 0, ro->ctx->stream, A);
+    HP_CHECK_HIP(hipGetLastError());
+    return HP_OK;
 }
 
 extern "C" {
@@ -252,6 +381,54 @@ int hp_rollout_step_streams(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *g
     HP_REQUIRE(!explore || (random_eps >= 0.0 && random_eps <= 1.0), HP_ERR_INVALID, "p < 0, p > 1 or p is NaN");
     return rollout_step("hp_rollout_step_streams", ro, a, on, gn, streams ? streams->d_state : nullptr, true, t, obs_dev, ag_dev, g_dev, explore, noise_eps,
                         random_eps, qn, clip_abs, actions_f32_dev);
+}
+
+int hp_rollout_episodes(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, hp_rng_streams *streams, const hp_env_desc *env,
+                        int32_t explore, double noise_eps, double random_eps, double qn, double clip_abs, float *success_dev) {
+    HP_REQUIRE(ro && a && on && gn && env && success_dev, HP_ERR_INVALID, "hp_rollout_episodes: null argument");
+    HP_SERIALISE(ro);
+    HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx && (!streams || streams->ctx == ro->ctx), HP_ERR_INVALID,
+               "hp_rollout_episodes: handles belong to different contexts");
+    HP_REQUIRE(env->kind == HP_ENV_POINT_MASS, HP_ERR_INVALID, "hp_rollout_episodes: env->kind %d is not an environment kind of this build",
+               (int)env->kind);
+    HP_REQUIRE(a->slab8 && a->H == 256 && a->ldx <= 48 && a->cfg.act_dim <= 4, HP_ERR_INVALID,
+               "hp_rollout_episodes: the agent is not slab-shaped (hidden %d, padded input width %d, act_dim %d, engine %s): it keeps "
+               "the per-step calls", a->H, a->ldx, a->cfg.act_dim, a->slab8 ? "slab8" : "other");
+    HP_REQUIRE(a->cfg.act_dim == ro->ad && on->size == ro->od && gn->size == ro->gd && on->size + gn->size == a->xdim, HP_ERR_INVALID,
+               "hp_rollout_episodes: agent / normalizer dimensions differ from the block's");
+    HP_REQUIRE(!explore || streams, HP_ERR_INVALID, "hp_rollout_episodes: explore != 0 needs `streams`");
+    HP_REQUIRE(!explore || ro->rows <= streams->n, HP_ERR_INVALID,
+               "hp_rollout_episodes: a wave of %lld environments is wider than the array of %lld streams", (long long)ro->rows,
+               (long long)streams->n);
+    HP_REQUIRE(!explore || (random_eps >= 0.0 && random_eps <= 1.0), HP_ERR_INVALID, "p < 0, p > 1 or p is NaN");
+    for (int k = 0; k < 3; ++k)
+        HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "hp_rollout_episodes: env->state_dev[%d] is null", k);
+    EpisodesArgs A;
+    memset(&A, 0, sizeof(A));
+    PolicyArgs &P = A.P;
+    P.od = on->size; P.gd = gn->size;
+    P.onz = on->d; P.gnz = gn->d;
+    P.clip_obs = INFINITY; P.clip_o = on->clip; P.clip_g = gn->clip;   // agent_act_dev with clip_obs = 0
+    P.rows = (int)ro->rows;
+    P.net = SlabNetPtrs{a->fragF, a->fragD, a->params};
+    P.la = a->la; P.H = a->H; P.act_dim = a->cfg.act_dim; P.max_action = (float)a->cfg.max_action;
+    A.b_obs = ro->block + ro->first * (ro->T + 1) * ro->od;
+    A.b_ag = ro->block + ro->o_ag + ro->first * (ro->T + 1) * ro->gd;
+    A.b_g = ro->block + ro->o_g + ro->first * ro->T * ro->gd;
+    A.b_act = ro->block + ro->o_act + ro->first * ro->T * ro->ad;
+    A.st = explore ? streams->d_state : nullptr;
+    A.rows = (int)ro->rows; A.T = ro->T; A.explore = explore ? 1 : 0;
+    A.x.ad = ro->ad;
+    A.x.amax = a->cfg.max_action;
+    A.x.noise_scale = noise_eps * a->cfg.max_action;
+    A.x.random_eps = random_eps; A.x.qn = qn; A.x.clip_abs = clip_abs;
+    A.env = *env;
+    A.success = success_dev;
+    switch (env->kind) {   // one case per environment kind (env_device.h)
+        case HP_ENV_POINT_MASS: return rollout_episodes_launch<PointMassEnvDev>(ro, A);
+        default: break;
+    }
+    return HP_ERR_INVALID;
 }
 
 int hp_rollout_set_action_max(hp_rollout *ro, double action_max) {

@@ -776,6 +776,7 @@ __device__ __forceinline__ void s8_l2_warm(const FbSlabArgs &P, int widx, float 
     s8_l2_warm_at(P, P.xcd_split ? (int)((blockIdx.x & 7) >> 2) : 2, P.n_pref >> 3, widx >> 3, sink);
 }
 
+#ifndef S8_DEVICE_ONLY   // a translation unit that only borrows the device functions (rollout.hip) compiles no kernel of this file
 __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_fb_slab8(const FbSlabArgs P) {
     const FwdSlabArgs &A = P.f;
     const BwdSlabArgs &Bk = P.b;
@@ -973,20 +974,37 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     }
 }
 
+#endif  // S8_DEVICE_ONLY
+
 #if S8_NRG == 1
-// actions = max_action * tanh(actor(normalise(obs | g)))  (ddpg_agent._preproc_inputs :163-171, models.py:19-26): the actor
-// half of the chain kernel above as its own launch -- same device functions, so the same bits as the training forward
-__global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_policy_slab8(const PolicyArgs P) {
-    __shared__ __attribute__((aligned(16))) float xin[S8_ROWS * S8_LDX];
-    __shared__ __attribute__((aligned(16))) float bufA[S8_ROWS * S8_LD];
-    __shared__ __attribute__((aligned(16))) float bufB[S8_ROWS * S8_LD];
-    __shared__ __attribute__((aligned(16))) float pbuf[S8_ROWS * 256];
-    __shared__ __attribute__((aligned(16))) RingSlot wring[S8_WAVES][S8_RING];
+// one network input out of a float64 row value (ddpg_agent._preproc_inputs :163-171, normalizer.py:67-70)
+__device__ __forceinline__ float s8_policy_input(double raw, double clip_obs, float mean, double std, double clip) {
+    double t = fmin(fmax(raw, -clip_obs), clip_obs);
+    t = __ddiv_rn(__dsub_rn(t, (double)mean), std);
+    return (float)fmin(fmax(t, -clip), clip);
+}
+
+// The LDS of one policy slab (k_policy_slab8; k_rollout_episodes keeps one for all its timesteps)
+struct PolicyLds {
+    float xin[S8_ROWS * S8_LDX] __attribute__((aligned(16)));
+    float bufA[S8_ROWS * S8_LD] __attribute__((aligned(16)));
+    float bufB[S8_ROWS * S8_LD] __attribute__((aligned(16)));
+    float pbuf[S8_ROWS * 256] __attribute__((aligned(16)));
+    RingSlot wring[S8_WAVES][S8_RING] __attribute__((aligned(16)));
+};
+
+// actions = max_action * tanh(actor(normalise(obs | g)))  (ddpg_agent._preproc_inputs :163-171, models.py:19-26) for the 4-row slab
+// at row0: the actor half of the chain kernel above -- same device functions, so the same bits as the training forward.  The one
+// body of the policy launch and of the launch that loops over a whole episode: input(r, c) = network input c of the slab's row r
+// (called for rows and columns that exist); emit(r, j, a) is called by lane j < act_dim of wave r with row r's action j.  On entry
+// no weight transfer is in flight and the LDS is free (a barrier lies between a previous use and this call).
+template <class Input, class Emit>
+__device__ __forceinline__ void s8_policy_slab(const PolicyArgs &P, PolicyLds &L, size_t row0, Input input, Emit emit) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const size_t row0 = (size_t)blockIdx.x * S8_ROWS;
     const NetLayout &la = P.la;
     const int ad = P.act_dim, H = P.H, w = P.od + P.gd;
-    RingSlot *ring = wring[wave];
+    float *xin = L.xin, *bufA = L.bufA, *bufB = L.bufB, *pbuf = L.pbuf;
+    RingSlot *ring = L.wring[wave];
     int rbase = 0;
     float4 wba[6], wh[4];
     s8_small_prefetch(P.net.wf + la.w1, la.K1, wba);
@@ -998,20 +1016,7 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         const int r = idx / S8_LDX, c = idx - r * S8_LDX;
         const size_t m = row0 + r;
         float v = 0.f;
-        if ((int)m < P.rows && c < w) {
-            if (P.x) {
-                v = P.x[m * w + c];
-            } else if (c < P.od) {
-                double t = fmin(fmax(P.obs[m * P.od + c], -P.clip_obs), P.clip_obs);
-                t = __ddiv_rn(__dsub_rn(t, (double)P.onz->mean[c]), P.onz->std[c]);
-                v = (float)fmin(fmax(t, -P.clip_o), P.clip_o);
-            } else {
-                const int j = c - P.od;
-                double t = fmin(fmax(P.g[m * P.gd + j], -P.clip_obs), P.clip_obs);
-                t = __ddiv_rn(__dsub_rn(t, (double)P.gnz->mean[j]), P.gnz->std[j]);
-                v = (float)fmin(fmax(t, -P.clip_g), P.clip_g);
-            }
-        }
+        if ((int)m < P.rows && c < w) v = input(r, c);
         xin[idx] = v;
     }
     s8_ring_prologue(ring, rbase, P.net.wf + la.w2);
@@ -1022,13 +1027,28 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     for (int i = 0; i < S8_RPW; ++i) {
         const int rr = wave + S8_WAVES * i;
         const float z = s8_rowdots(bufA, S8_LD, rr < S8_ROWS ? rr : 0, ad, wh);
-        if (lane < ad && rr < S8_ROWS && (int)(row0 + rr) < P.rows)
-            P.actions[(row0 + rr) * ad + lane] = P.max_action * tanhf(z + bh);
+        if (lane < ad && rr < S8_ROWS && (int)(row0 + rr) < P.rows) emit(rr, lane, P.max_action * tanhf(z + bh));
     }
 }
+
+#ifndef S8_DEVICE_ONLY
+__global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_policy_slab8(const PolicyArgs P) {
+    __shared__ PolicyLds L;
+    const size_t row0 = (size_t)blockIdx.x * S8_ROWS;
+    s8_policy_slab(P, L, row0,
+        [&](int r, int c) -> float {
+            const size_t m = row0 + r;
+            if (P.x) return P.x[m * (P.od + P.gd) + c];
+            if (c < P.od) return s8_policy_input(P.obs[m * P.od + c], P.clip_obs, P.onz->mean[c], P.onz->std[c], P.clip_o);
+            const int j = c - P.od;
+            return s8_policy_input(P.g[m * P.gd + j], P.clip_obs, P.gnz->mean[j], P.gnz->std[j], P.clip_g);
+        },
+        [&](int r, int j, float a) { P.actions[(row0 + r) * P.act_dim + j] = a; });
+}
+#endif
 #endif
 
-#if S8_NRG == 1   // the split launch exists for 4-row slabs (8-row: built, measured, lost -- agent.hip at the slab-height table)
+#if S8_NRG == 1 && !defined(S8_DEVICE_ONLY)   // the split launch exists for 4-row slabs (8-row: built, measured, lost -- agent.hip at the slab-height table)
 #include "slab8_split.h"
 #endif
 

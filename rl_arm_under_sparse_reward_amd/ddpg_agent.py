@@ -51,6 +51,8 @@ class ddpg_agent:
         self.vec_env = env if getattr(env, "is_device_vec_env", False) else None
         self._rollouts = {}              # DeviceEpisodes blocks by episode count
         self.explore_streams = None      # random.DeviceRandomStreams: one exploration stream per environment (enable_explore_streams)
+        self.rollout_form = None         # 'fused' | 'stepped': how the most recent wave of collect_episodes_device was collected
+        self.rollout_reason = None       # ... and, when stepped, why (device_env.fused_rollout_reason)
         self.env_params = env_params
         self.ctx = ctx or _lib.Context.default()
         self.lib = self.ctx.lib
@@ -69,7 +71,8 @@ class ddpg_agent:
         self.actor_target_network = actor(env_params)       # re-initialised from the online nets below
         self.critic_target_network = critic(env_params)
         cfg = _lib.AgentCfg(
-            obs_dim=env_params['obs'], goal_dim=env_params['goal'], act_dim=env_params['action'], hidden=256,
+            obs_dim=env_params['obs'], goal_dim=env_params['goal'], act_dim=env_params['action'],
+            hidden=int(env_params.get('hidden', 256)),
             batch=int(args.batch_size), grad_world_size=self.comm.world_size,
             max_action=float(env_params['action_max']), gamma=float(args.gamma), action_l2=float(args.action_l2),
             lr_actor=float(args.lr_actor), lr_critic=float(args.lr_critic), polyak=float(args.polyak),
@@ -652,11 +655,13 @@ class ddpg_agent:
     def collect_episodes_device(self, vec_env=None, n_rollouts=None, epoch=0, explore=True, success_out=None):
         """`collect_episodes` for a vectorised device environment (device_env.py): `n_rollouts` episodes (default: one wave of
         vec_env.n_envs) in waves of n_envs, T timesteps of two launches each (csrc/rollout.hip) on torch's current stream, no
-        host copy and no host wait per timestep.  Exploration (:174-184, the +-0.15 clip from epoch 100) is drawn on the device
+        host copy and no host wait per timestep -- or, for a native environment, a slab-shaped agent and draws that are
+        independent across environments (`device_env.fused_rollout_reason`), ONE launch per wave (hp_rollout_episodes), the same
+        bits; `self.rollout_form` says which form the last wave took.  Exploration (:174-184, the +-0.15 clip from epoch 100) is drawn on the device
         from `self.rng`, for env 0 .. n-1 in turn like the host lockstep path -- or, after `enable_explore_streams`, for every
         environment from its own stream (a wave of k < n_envs rows advances the streams of those k only).  Returns a `DeviceEpisodes` handle for
         `train_cycle` / `buffer.store_episode`; `.numpy()` gives the four arrays `collect_episodes` returns."""
-        from .device_env import DeviceEpisodes, binomial1_qn
+        from .device_env import DeviceEpisodes, binomial1_qn, fused_rollout_reason
         vec_env = vec_env or self.vec_env
         n_total = int(n_rollouts or vec_env.n_envs)
         T, ad = int(self.env_params['max_timesteps']), int(self.env_params['action'])
@@ -673,9 +678,30 @@ class ddpg_agent:
             raise ValueError(f"collect_episodes_device: {len(streams)} exploration streams for {vec_env.n_envs} environments")
         step, stream_h = ((self.lib.hp_rollout_step_streams, streams.h) if streams is not None
                           else (self.lib.hp_rollout_step, self.rng.h))
+        self.rollout_reason = fused_rollout_reason(getattr(vec_env, "is_native_device_env", False), self._slab_shaped(), explore,
+                                                   streams is not None)
+        self.rollout_form = 'fused' if self.rollout_reason is None else 'stepped'
         while done < n_total:
             k = min(vec_env.n_envs, n_total - done)
             o = vec_env.reset() if k == vec_env.n_envs else vec_env.reset(k)
+            if self.rollout_form == 'fused':
+                desc = vec_env.native_desc()
+                env = _lib.EnvDesc(kind=int(desc["kind"]))
+                for i, v in enumerate(desc["params"]):
+                    env.params[i] = float(v)
+                for i, t in enumerate(desc["state"]):
+                    env.state_dev[i] = t.data_ptr()
+                success = torch.empty(k, dtype=torch.float32, device=o['observation'].device)
+                with self.ctx.torch_bridge():
+                    _lib.check(self.lib.hp_rollout_begin(eps.h, done, k))
+                    _lib.check(self.lib.hp_rollout_episodes(eps.h, self.h, self.o_norm.h, self.g_norm.h,
+                                                            streams.h if streams is not None else None, C.byref(env),
+                                                            1 if explore else 0, float(self.args.noise_eps),
+                                                            float(self.args.random_eps), qn, clip_abs, p(success)))
+                if success_out is not None:
+                    success_out.append(success)
+                done += k
+                continue
             actions = torch.empty((k, ad), dtype=torch.float32, device=o['observation'].device)
             with self.ctx.torch_bridge():       # the whole wave in torch's stream order, between the environment's own kernels
                 _lib.check(self.lib.hp_rollout_begin(eps.h, done, k))
@@ -693,6 +719,14 @@ class ddpg_agent:
         if explore and streams is None:     # (the streams keep no host copy of their cached normals: nothing to invalidate)
             self.rng.mark_normals_drawn()
         return eps
+
+    def _slab_shaped(self):
+        """Whether policy calls on this agent are the one-launch slab kernel (hp_agent_engine reports the 4x4x1 slab engine)."""
+        if getattr(self, "_slab8", None) is None:
+            e = C.c_int32()
+            _lib.check(self.lib.hp_agent_engine(self.h, C.byref(e), None, None))
+            self._slab8 = e.value == 8
+        return self._slab8
 
     def _select_actions(self, pi):
         """ddpg_agent.py:174-184: Gaussian noise, clip, epsilon-random (numpy global RNG, like the reference).  `action`

@@ -17,6 +17,15 @@ With such an environment `ddpg_agent.collect_episodes_device` runs T timesteps o
 host copy in between, the exploration noise of ddpg_agent.py:174-184 drawn on the device from the reference's MT19937 stream, and
 returns a `DeviceEpisodes` handle that `train_cycle` / `buffer.store_episode` consume without the episodes ever visiting the host.
 
+**Native environments.**  An environment whose dynamics the library evaluates itself (csrc/env_device.h) additionally has
+
+    env.is_native_device_env == True
+    env.native_desc()        -> {'kind': int, 'params': [float, ...], 'state': [tensor, ...]}     (hp_env_desc)
+
+and a whole wave of its episodes is ONE launch (hp_rollout_episodes: every workgroup loops over the T timesteps of its four rows)
+whenever `fused_rollout_reason` finds nothing against it; `reset` stays on the host, `step` stays available, and after a fused
+wave the state tensors hold what T `step` calls would have left.  `NativePointMassVecEnv` is the first such environment.
+
 Draw order with n environments: per timestep, for env i = 0 .. n-1: randn(action), uniform(action), binomial(1) -- the order of
 the host lockstep path (`collect_episodes` on a list of environments); with one environment it is the reference's own order.
 
@@ -51,6 +60,18 @@ def binomial1_qn(p):
     reflected = not (p <= 0.5)
     pe = 1.0 - p if reflected else p
     return math.exp(math.log(1.0 - pe)), reflected
+
+
+def fused_rollout_reason(env_native, agent_slab, explore, has_streams):
+    """Why a wave cannot be collected by the one-launch form (hp_rollout_episodes), or None when it can.  The single shared
+    stream with explore=True stays per-step: its walk visits the environments one after the other by definition."""
+    if not env_native:
+        return "the environment is not native: its dynamics run in torch, one launch boundary per timestep"
+    if not agent_slab:
+        return "the agent is not slab-shaped (hidden 256, padded input width <= 48, at most 4 action components)"
+    if explore and not has_streams:
+        return "exploring from the single shared stream is a sequential walk across the environments (enable_explore_streams)"
+    return None
 
 
 class DeviceEpisodes:
@@ -159,3 +180,18 @@ class PointMassVecEnv:
         success = (self._distance(observation['achieved_goal'], self.goal) < self.distance_threshold).to(torch.float32)
         info = {'is_success': success}
         return observation, self.compute_reward(observation['achieved_goal'], self.goal, info), False, info
+
+
+class NativePointMassVecEnv(PointMassVecEnv):
+    """`PointMassVecEnv` whose dynamics the library also evaluates itself (PointMassEnvDev, csrc/env_device.h: the same float64
+    operations, one by one): `collect_episodes_device` collects a wave of its episodes in one launch.  `reset` and `step` are the
+    parent's, so the per-step protocol works on it unchanged -- and with device="cpu" it is simply the parent."""
+
+    is_native_device_env = True
+
+    def native_desc(self):
+        """hp_env_desc of the environments stepped now: kind, params [step_scale, distance_threshold], state [pos, vel, goal]
+        (float64 [active, 3] each, contiguous; the launch reads all three and writes pos and vel in place)."""
+        self.pos, self.vel, self.goal = self.pos.contiguous(), self.vel.contiguous(), self.goal.contiguous()
+        return {"kind": _lib.ENV_POINT_MASS, "params": [self.step_scale, self.distance_threshold],
+                "state": [self.pos, self.vel, self.goal]}

@@ -85,7 +85,8 @@ class actor(_DeviceMLP):
     head_name = "action_out"
 
     def __init__(self, env_params):
-        super().__init__(env_params, env_params['obs'] + env_params['goal'], env_params['action'])
+        super().__init__(env_params, env_params['obs'] + env_params['goal'], env_params['action'],
+                         hidden=int(env_params.get('hidden', 256)))
 
     def forward(self, x):
         """models.py:19-26 on the device: x [rows, obs+goal] float32 -> actions [rows, action]."""
@@ -99,7 +100,8 @@ class critic(_DeviceMLP):
     head_name = "q_out"
 
     def __init__(self, env_params):
-        super().__init__(env_params, env_params['obs'] + env_params['goal'] + env_params['action'], 1)
+        super().__init__(env_params, env_params['obs'] + env_params['goal'] + env_params['action'], 1,
+                         hidden=int(env_params.get('hidden', 256)))
 
     def forward(self, x, actions):
         """models.py:36-44 on the device: x [rows, obs+goal] float32, actions [rows, action] -> q [rows, 1].  (Inside the
