@@ -398,11 +398,38 @@ enum { HP_ENV_POINT_MASS = 1 };
 typedef struct {
     int32_t kind, reserved;
     double params[8];         /* point mass: [0] step_scale, [1] distance_threshold */
-    double *state_dev[4];     /* point mass: [0] pos [n][3], [1] vel [n][3], [2] goal [n][3]; read at entry, pos / vel written at exit */
+    double *state_dev[4];     /* point mass: [0] pos [n][3], [1] vel [n][3], [2] goal [n][3]; read at entry, written at exit */
 } hp_env_desc;
 int hp_rollout_episodes(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, hp_rng_streams *streams,
                         const hp_env_desc *env, int32_t explore, double noise_eps, double random_eps, double qn,
                         double clip_abs, float *success_dev);
+
+/* ---- environments reset on the device; all waves of a call in one launch ------------------------------------------------------
+ * An environment kind may declare a reset (csrc/env_device.h): a fixed number of random_uniform(low, range) draws out of the
+ * environment's own reset stream -- stream i of an hp_rng_streams, np.random.RandomState's legacy state like the exploration
+ * streams -- and the fresh state built from them.  Point mass: six draws of uniform(0, 0.5), pos = u[0:3], goal = u[3:6], vel = 0,
+ * the twelve words of the host twin's two uniform(0, 0.5, 3) calls.
+ * hp_env_reset resets environments 0 .. rows-1 of the arrays of `env` (one wave per environment: load stream i, draw, write the
+ * state, commit the stream in numpy's lazy form); environments and streams >= rows are untouched.  Asynchronous on the context's
+ * stream (or a borrowed one).
+ * hp_rollout_waves is hp_rollout_episodes for a call of more episodes than environments: the `rows` episodes selected by
+ * hp_rollout_begin (rows may exceed n_envs) are collected as ceil(rows / n_envs) waves inside ONE launch.  The state arrays of
+ * `env` hold n_envs environments.  Workgroup b owns environments 4b .. 4b+3 and loops over the waves: environment i takes part in
+ * wave w if w * n_envs + i < rows, is then reset from reset stream i, runs T timesteps as in hp_rollout_episodes and is recorded
+ * as episode first + w * n_envs + i; success_dev[w * n_envs + i] receives its flag.  Exploration stream i runs on across the waves
+ * of a launch; a partial last wave touches neither stream of the environments it leaves out.  At the end every environment's
+ * state, goal included, and every stream are written back once.  The bits are those of ceil(rows / n_envs) calls of hp_env_reset
+ * + hp_rollout_episodes.  A launch holds at most HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS timesteps (whole waves of T, at least one):
+ * longer calls are issued as consecutive launches, and *launches_out (may be NULL) receives how many there were.  4096: at the
+ * measured 9.3 us (up to 64 environments) to 31 us (1024 environments) per timestep of the fused kernel a launch ends after 40 to
+ * 130 ms, well under a second on a device other work shares.
+ * HP_ERR_INVALID, naming the entry point, for: a null argument, handles of different contexts, fewer reset streams than n_envs
+ * (hp_env_reset: than rows), episodes outside the block, a kind without a reset, and everything hp_rollout_episodes refuses. */
+#define HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS 4096
+int hp_env_reset(hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *reset_streams, int64_t rows);
+int hp_rollout_waves(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, hp_rng_streams *streams,
+                     hp_rng_streams *reset_streams, const hp_env_desc *env, int64_t n_envs, int32_t explore, double noise_eps,
+                     double random_eps, double qn, double clip_abs, float *success_dev, int32_t *launches_out);
 
 /* Policy calls that do not queue behind training: hp_agent_policy_snapshot copies the online actor and both normalizers'
  * statistics (stream-ordered with the updates, no host wait); hp_agent_act_snapshot evaluates the most recent COMPLETE

@@ -79,6 +79,10 @@ int hp_agent_debug_timeline(hp_agent *ag, uint64_t *out192);
 int hp_state_debug_dirty_scan(hp_buffer *buf, const uint32_t *stamps_host, int64_t current_size, uint32_t since, int64_t max_dirty,
                               int64_t *slots_out, int64_t *n_dirty, int32_t *overflow);
 
+/* test hook: the most timesteps (waves x T) one launch of hp_rollout_waves on this block may hold, in place of
+ * HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS (0 = that default again), so that a small call is issued as several launches */
+int hp_rollout_debug_set_launch_cap(hp_rollout *ro, int64_t timesteps);
+
 /* diagnostic: a ~200 us calibration of the box this process landed on, so that a slow box can be told from a regression in a
  * bench line (about one box in seven of the pool ran every kernel of this path ~1.4 x slower at the same shader clock):
  *   out[0] launch floor, us per dependent trivial kernel in a captured hipGraph

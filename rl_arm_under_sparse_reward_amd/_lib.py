@@ -56,6 +56,7 @@ class EnvDesc(C.Structure):
 
 
 ENV_POINT_MASS = 1
+ROLLOUT_MAX_LAUNCH_TIMESTEPS = 4096   # HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS: what one launch of hp_rollout_waves holds at most
 
 
 class StateDims(C.Structure):
@@ -73,7 +74,7 @@ PARALLEL_DRAW_MIN_BATCH = 65536   # HP_PARALLEL_DRAW_MIN_BATCH: the measured cro
 DEBUG_SYMBOLS = {"hp_ctx_launch_floor", "hp_ctx_event_pair_us", "hp_ctx_clock_mhz", "hp_ctx_calibrate", "hp_buffer_sample_device_us",
                  "hp_buffer_sample_dev_us", "hp_buffer_sample_dev_fast_us",
                  "hp_mt_jump_poly", "hp_rng_parallel_info", "hp_rng_debug_set_window", "hp_rng_debug_table_ms",
-                 "hp_state_debug_dirty_scan",
+                 "hp_state_debug_dirty_scan", "hp_rollout_debug_set_launch_cap",
                  "hp_agent_set_adam", "hp_agent_debug_chain", "hp_agent_debug_timeline", "hp_agent_update_kernels"}
 
 # name -> (restype, argtypes); every symbol declared in include/rlarm_hip.h and include/rlarm_hip_debug.h
@@ -189,6 +190,11 @@ PROTOTYPES = {
                                           C.c_void_p]),
     "hp_rollout_episodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EnvDesc), C.c_int32,
                                       C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    "hp_env_reset": (C.c_int, [C.c_void_p, C.POINTER(EnvDesc), C.c_void_p, C.c_int64]),
+    "hp_rollout_waves": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EnvDesc),
+                                   C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                   C.POINTER(C.c_int32)]),
+    "hp_rollout_debug_set_launch_cap": (C.c_int, [C.c_void_p, C.c_int64]),
     "hp_agent_policy_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hp_agent_act_snapshot": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int64, C.c_double, f32p]),
     "hp_agent_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,

@@ -20,6 +20,13 @@
 // (or nothing is drawn).  Workgroup b owns rows 4b .. 4b+3 and loops over t by itself -- no cross-workgroup hand-off, no grid-wide
 // wait, no host in the loop -- through the SAME device functions: the policy slab of k_policy_slab8 (s8_policy_slab), ro_explore_row
 // and the noise-free branch of k_rollout_step (ro_plain_row).
+//
+// All waves of a call are ONE launch too (hp_rollout_waves) once the environment is reset on the device (env_device.h: reset out
+// of one reset stream per environment): the same kernel loops over the waves, resets a row's environment between two episodes on
+// the row's own wave, and writes every environment and every stream back once.  hp_env_reset is that reset as a launch of its own,
+// for the per-step path.
+#include <algorithm>
+
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wundefined-inline"   // agent_device.h declares the 32-row engine's fragment map, which no code here calls
 #include "agent_device.h"
@@ -44,6 +51,7 @@ struct hp_rollout {
     int32_t T = 0, od = 0, gd = 0, ad = 0;
     int64_t first = 0, rows = 0;   // the wave being collected: episodes [first, first + rows)
     double action_max = 1.0;       // of the policy whose outputs a teacher-forced step is handed (hp_rollout_set_action_max)
+    int64_t launch_cap = HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS;   // timesteps (waves x T) one launch of hp_rollout_waves may hold
     double *block = nullptr;
     int64_t o_ag = 0, o_g = 0, o_act = 0, elems = 0;   // offsets in float64 elements (feeder._Layout)
 };
@@ -167,8 +175,10 @@ __global__ __launch_bounds__(MW_THREADS) void k_rollout_step_streams(const Rollo
 struct EpisodesArgs {
     PolicyArgs P;                  // the policy call of hp_agent_act_dev (obs / g / x / actions unused: the rows come from LDS)
     double *b_obs, *b_ag, *b_g, *b_act;   // block arrays, already offset to episode `first`
-    MtState *st;                   // stream of row 0 of the wave (explore != 0)
-    int rows, T, explore;
+    MtState *st;                   // exploration stream of environment 0 (explore != 0)
+    MtState *reset_st;             // reset stream of environment 0; nullptr: the environments were reset by the caller
+    int rows, T, explore;          // rows: episodes of the launch = waves of n_envs environments, the last one possibly partial
+    int n_envs, waves;             // (hp_rollout_episodes: n_envs = rows, one wave)
     ExploreArgs x;
     hp_env_desc env;
     float *success;                // [rows]
@@ -189,6 +199,17 @@ struct EpisodesLds {
 // asks for anyway.  Wave r < 4 owns row r outside the policy slab: its lane 0 steps the environment, its lanes j < act_dim hold
 // action j (s8_policy_slab's emit), and the whole wave walks the row's stream.  Barriers per timestep: one __syncthreads() behind
 // observe, the policy slab's own, none in the draws (wave-local: the rejection loops of different rows need not agree on a trip count).
+//
+// The wave loop.  Workgroup b owns ENVIRONMENTS 4b .. 4b+3 for the whole launch (A.P.rows = the environments that take part at
+// all); environment i collects episode w * n_envs + i in wave w if that is < rows, and sits the wave out otherwise (only in the
+// last wave, only a suffix of the environments: the rows of a slab that take part are its first `nrows`).  Whether a row takes part
+// is wave-uniform, everything it does between two episodes is wave-local, and a row that sits out still reaches every workgroup
+// barrier of the timestep loop.  With reset streams a row's wave, before each of its episodes: commits the exploration stream out
+// of its ring (mt_commit's rule: numpy's lazy form), loads the environment's reset stream INTO THE SAME RING (a second ring per
+// row does not fit the 160 KiB four times), draws the reset, commits that stream, and loads the exploration stream again -- 2.5 KB
+// read per stream and episode, and a key written only when the walk left its block.  The weight ring has drained when s8_trunk
+// returns and the next s8_ring_prologue is issued after all of this, so its counted waits stay exact.  One wave and no reset stream
+// is hp_rollout_episodes' launch, unchanged.
 template <class Env>
 __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_rollout_episodes(const EpisodesArgs A) {
     __shared__ s8ro::PolicyLds L;
@@ -196,55 +217,110 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     constexpr int OD = Env::OBS, GD = Env::GOAL, AD = Env::ACT;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const long long row0 = (long long)blockIdx.x * 4;
-    const int nrows = A.rows - row0 < 4 ? (int)(A.rows - row0) : 4;
-    const bool mine = wave < nrows;              // this wave owns row row0 + wave
-    const long long row = row0 + wave;
+    const int nenv = A.P.rows - row0 < 4 ? (int)(A.P.rows - row0) : 4;   // environments of this slab
+    const bool mine = wave < nenv;               // this wave owns environment row0 + wave
+    const long long env = row0 + wave;
     const int T = A.T;
     MwState w;
     if (mine) {
-        if (lane == 0) E.env[wave].load(A.env, row);
-        if (A.explore) w.load(A.st + row, E.ring[wave]);
+        if (lane == 0) E.env[wave].load(A.env, env);
+        if (A.explore && !A.reset_st) w.load(A.st + env, E.ring[wave]);
     }
-    // record the rows observed into E at timestep t (t == T: the closing record, no goal row)
-    auto record = [&](int t) {
-        const int per = OD + GD + (t < T ? GD : 0);
-        for (int e = tid; e < nrows * per; e += S8_THREADS) {
-            const int r = e / per, c = e - r * per;
-            const long long i = row0 + r;
-            if (c < OD) A.b_obs[(i * (T + 1) + t) * OD + c] = E.obs[r][c];
-            else if (c < OD + GD) A.b_ag[(i * (T + 1) + t) * GD + (c - OD)] = E.ag[r][c - OD];
-            else A.b_g[(i * T + t) * GD + (c - OD - GD)] = E.g[r][c - OD - GD];
+    for (int wv = 0; wv < A.waves; ++wv) {
+        const long long ep0 = (long long)wv * A.n_envs + row0;               // episode of the slab's row 0 in this wave
+        const int nrows = A.rows - ep0 < nenv ? (A.rows - ep0 < 0 ? 0 : (int)(A.rows - ep0)) : nenv;
+        const bool part = wave < nrows;          // this wave's environment collects episode ep0 + wave
+        const long long row = ep0 + wave;
+        if constexpr (Env::RESET_DRAWS > 0) {
+            if (A.reset_st && part) {
+                // what the exploration stream's commit writes from lane 0 stays in registers across the detour, so the reload
+                // depends on no other lane's global store: each lane reads back only the key words it wrote itself
+                const bool resume = A.explore && wv > 0;
+                long long xblock = 0;
+                int xpos = 0, xhas = 0;
+                double xgauss = 0.0;
+                if (resume) {
+                    mt_final_block(w.g.cursor, xblock, xpos);
+                    xhas = w.has_gauss;
+                    xgauss = w.gauss;
+                    w.store(A.st + env);
+                    mw_sync();                   // the commit has read the ring before the next stream's key overwrites it
+                }
+                w.load(A.reset_st + env, E.ring[wave]);
+                env_reset_draw<Env>(w, E.zs[wave]);
+                w.store(A.reset_st + env);
+                if (lane == 0) E.env[wave].reset(E.zs[wave]);
+                mw_sync();
+                if (A.explore) w.load(A.st + env, E.ring[wave]);
+                if (resume) {
+                    w.g.cursor = xpos;
+                    w.has_gauss = xhas;
+                    w.gauss = xgauss;
+                }
+            }
         }
-    };
-    for (int t = 0; t < T; ++t) {
-        if (mine && lane == 0) E.env[wave].observe(E.obs[wave], E.ag[wave], E.g[wave]);
+        // record the rows observed into E at timestep t (t == T: the closing record, no goal row)
+        auto record = [&](int t) {
+            const int per = OD + GD + (t < T ? GD : 0);
+            for (int e = tid; e < nrows * per; e += S8_THREADS) {
+                const int r = e / per, c = e - r * per;
+                const long long i = ep0 + r;
+                if (c < OD) A.b_obs[(i * (T + 1) + t) * OD + c] = E.obs[r][c];
+                else if (c < OD + GD) A.b_ag[(i * (T + 1) + t) * GD + (c - OD)] = E.ag[r][c - OD];
+                else A.b_g[(i * T + t) * GD + (c - OD - GD)] = E.g[r][c - OD - GD];
+            }
+        };
+        for (int t = 0; t < T; ++t) {
+            if (part && lane == 0) E.env[wave].observe(E.obs[wave], E.ag[wave], E.g[wave]);
+            __syncthreads();
+            record(t);
+            s8ro::s8_policy_slab(A.P, L, (size_t)row0,
+                [&](int r, int c) -> float {
+                    if (r >= nrows) return 0.f;  // an environment that sits this wave out
+                    if (c < OD) return s8ro::s8_policy_input(E.obs[r][c], A.P.clip_obs, A.P.onz->mean[c], A.P.onz->std[c], A.P.clip_o);
+                    const int j = c - OD;
+                    return s8ro::s8_policy_input(E.g[r][j], A.P.clip_obs, A.P.gnz->mean[j], A.P.gnz->std[j], A.P.clip_g);
+                },
+                [&](int r, int j, float a) { E.pi[r][j] = a; });
+            if (part) {
+                mw_sync();
+                double *act = A.b_act + (row * T + t) * AD;
+                if (A.explore) ro_explore_row(A.x, w, E.zs[wave], E.pi[wave], act);
+                else if (lane < AD) ro_plain_element(A.x, &E.pi[wave][lane], act + lane);
+                mw_sync();
+                if (lane == 0) E.env[wave].step(E.pi[wave]);
+            }
+        }
+        if (part && lane == 0) E.env[wave].observe(E.obs[wave], E.ag[wave], E.g[wave]);
         __syncthreads();
-        record(t);
-        s8ro::s8_policy_slab(A.P, L, (size_t)row0,
-            [&](int r, int c) -> float {
-                if (c < OD) return s8ro::s8_policy_input(E.obs[r][c], A.P.clip_obs, A.P.onz->mean[c], A.P.onz->std[c], A.P.clip_o);
-                const int j = c - OD;
-                return s8ro::s8_policy_input(E.g[r][j], A.P.clip_obs, A.P.gnz->mean[j], A.P.gnz->std[j], A.P.clip_g);
-            },
-            [&](int r, int j, float a) { E.pi[r][j] = a; });
-        if (mine) {
-            mw_sync();
-            double *act = A.b_act + (row * T + t) * AD;
-            if (A.explore) ro_explore_row(A.x, w, E.zs[wave], E.pi[wave], act);
-            else if (lane < AD) ro_plain_element(A.x, &E.pi[wave][lane], act + lane);
-            mw_sync();
-            if (lane == 0) E.env[wave].step(E.pi[wave]);
-        }
+        record(T);
+        if (part && lane == 0) A.success[row] = E.env[wave].is_success() ? 1.f : 0.f;
+        if (wv + 1 < A.waves) __syncthreads();   // record(T) has read the rows the next wave's first observe rewrites
     }
-    if (mine && lane == 0) E.env[wave].observe(E.obs[wave], E.ag[wave], E.g[wave]);
-    __syncthreads();
-    record(T);
     if (mine) {
-        if (lane == 0) {
-            A.success[row] = E.env[wave].is_success() ? 1.f : 0.f;
-            E.env[wave].store(A.env, row);
+        if (lane == 0) E.env[wave].store(A.env, env);
+        if (A.explore) w.store(A.st + env);
+    }
+}
+
+// A reset as a launch of its own (hp_env_reset): workgroup i = one wave = environment i, like k_rollout_step_streams -- load reset
+// stream i, draw, commit it by mt_commit's rule, and lane 0 writes the fresh state.
+template <class Env>
+__global__ __launch_bounds__(MW_THREADS) void k_env_reset(const hp_env_desc env, MtState *reset_st) {
+    __shared__ uint32_t ring[4][MT_N];
+    __shared__ double u[Env::RESET_DRAWS > 0 ? Env::RESET_DRAWS : 1];
+    if constexpr (Env::RESET_DRAWS > 0) {
+        const long long i = blockIdx.x;
+        MtState *st = reset_st + i;
+        MwState w(st, ring);
+        env_reset_draw<Env>(w, u);
+        w.store(st);
+        if (mw_lane() == 0) {
+            Env e;
+            e.load(env, i);      // the parameters; the state it reads is replaced
+            e.reset(u);
+            e.store(env, i);
         }
-        if (A.explore) w.store(A.st + row);
     }
 }
 
@@ -292,16 +368,101 @@ static int rollout_step(const char *entry, hp_rollout *ro, hp_agent *a, hp_norm 
     return rollout_launch(ro, A, t, per_env_streams && explore);   // explore == 0 touches no stream: the single-stream kernel's path
 }
 
-// the launch of one environment kind; dimensions of the kind against the block's first
+// The launches of one environment kind; dimensions of the kind against the block's first.  A (hp_rollout_episodes, or
+// hp_rollout_waves with A.reset_st and A.n_envs set) describes the whole call: episodes [first, first + rows) of the block; it is
+// issued as consecutive launches of at most ro->launch_cap timesteps (whole waves, at least one), each a call of its own on the
+// episodes, flags and final states the one before it left.
 template <class Env>
-static int rollout_episodes_launch(hp_rollout *ro, EpisodesArgs &A) {
+static int rollout_episodes_launch(const char *entry, hp_rollout *ro, EpisodesArgs A, int32_t *launches) {
     HP_REQUIRE(ro->od == Env::OBS && ro->gd == Env::GOAL && ro->ad == Env::ACT, HP_ERR_INVALID,
-               "hp_rollout_episodes: env->kind %d has dimensions %d / %d / %d, the block has %d / %d / %d", (int)A.env.kind, Env::OBS,
+               "%s: env->kind %d has dimensions %d / %d / %d, the block has %d / %d / %d", entry, (int)A.env.kind, Env::OBS,
                Env::GOAL, Env::ACT, ro->od, ro->gd, ro->ad);
+    HP_REQUIRE(!A.reset_st || Env::RESET_DRAWS > 0, HP_ERR_INVALID, "%s: env->kind %d has no reset on the device", entry, (int)A.env.kind);
     static_assert(Env::ACT <= 4 && Env::ACT <= RO_MAX_ACT && Env::OBS + Env::GOAL <= S8_LDX, "an environment of the policy slab's shape");
-    hipLaunchKernelGGL(k_rollout_episodes<Env>, dim3((unsigned)((ro->rows + 3) / 4)), dim3(S8_THREADS), 0, ro->ctx->stream, A);
+    static_assert(Env::RESET_DRAWS <= RO_MAX_ACT, "the reset's values pass through the row's zs");
+    const int64_t total = A.rows, n_envs = A.n_envs;
+    int64_t per = ro->launch_cap / (ro->T > 0 ? ro->T : 1);   // waves per launch
+    if (per < 1) per = 1;
+    int n = 0;
+    for (int64_t done = 0; done < total; ++n) {
+        const int64_t left = total - done, waves = std::min<int64_t>((left + n_envs - 1) / n_envs, per);
+        const int64_t rows = std::min(left, waves * n_envs), live = std::min(rows, n_envs);
+        EpisodesArgs L = A;
+        L.b_obs += done * (ro->T + 1) * ro->od;
+        L.b_ag += done * (ro->T + 1) * ro->gd;
+        L.b_g += done * ro->T * ro->gd;
+        L.b_act += done * ro->T * ro->ad;
+        L.success += done;
+        L.rows = (int)rows; L.waves = (int)waves;
+        L.P.rows = (int)live;              // the environments that take part in the launch at all
+        hipLaunchKernelGGL(k_rollout_episodes<Env>, dim3((unsigned)((live + 3) / 4)), dim3(S8_THREADS), 0, ro->ctx->stream, L);
+        HP_CHECK_HIP(hipGetLastError());
+        done += rows;
+    }
+    if (launches) *launches = n;
+    return HP_OK;
+}
+
+template <class Env>
+static int env_reset_launch(hp_ctx *ctx, const hp_env_desc &env, MtState *st, int64_t rows) {
+    HP_REQUIRE(Env::RESET_DRAWS > 0, HP_ERR_INVALID, "hp_env_reset: env->kind %d has no reset on the device", (int)env.kind);
+    hipLaunchKernelGGL(k_env_reset<Env>, dim3((unsigned)rows), dim3(MW_THREADS), 0, ctx->stream, env, st);
     HP_CHECK_HIP(hipGetLastError());
     return HP_OK;
+}
+
+// what hp_rollout_episodes and hp_rollout_waves share: the checks on agent, normalizers, block and streams, and the arguments of the
+// kernel (`entry` names the caller in every refusal).  reset_streams == nullptr: one wave of ro->rows environments
+static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, hp_rng_streams *streams,
+                            hp_rng_streams *reset_streams, const hp_env_desc *env, int64_t n_envs, int32_t explore, double noise_eps,
+                            double random_eps, double qn, double clip_abs, float *success_dev, int32_t *launches) {
+    HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx && (!streams || streams->ctx == ro->ctx) &&
+                   (!reset_streams || reset_streams->ctx == ro->ctx),
+               HP_ERR_INVALID, "%s: handles belong to different contexts", entry);
+    HP_REQUIRE(env->kind == HP_ENV_POINT_MASS, HP_ERR_INVALID, "%s: env->kind %d is not an environment kind of this build", entry,
+               (int)env->kind);
+    HP_REQUIRE(a->slab8 && a->H == 256 && a->ldx <= 48 && a->cfg.act_dim <= 4, HP_ERR_INVALID,
+               "%s: the agent is not slab-shaped (hidden %d, padded input width %d, act_dim %d, engine %s): it keeps "
+               "the per-step calls", entry, a->H, a->ldx, a->cfg.act_dim, a->slab8 ? "slab8" : "other");
+    HP_REQUIRE(a->cfg.act_dim == ro->ad && on->size == ro->od && gn->size == ro->gd && on->size + gn->size == a->xdim, HP_ERR_INVALID,
+               "%s: agent / normalizer dimensions differ from the block's", entry);
+    HP_REQUIRE(!explore || streams, HP_ERR_INVALID, "%s: explore != 0 needs `streams`", entry);
+    const int64_t width = std::min<int64_t>(ro->rows, n_envs);   // the widest wave of the call
+    HP_REQUIRE(!explore || width <= streams->n, HP_ERR_INVALID,
+               "%s: a wave of %lld environments is wider than the array of %lld streams", entry, (long long)width,
+               (long long)streams->n);
+    HP_REQUIRE(!reset_streams || n_envs <= reset_streams->n, HP_ERR_INVALID,
+               "%s: %lld environments, but the array holds %lld reset streams", entry, (long long)n_envs, (long long)reset_streams->n);
+    HP_REQUIRE(!explore || (random_eps >= 0.0 && random_eps <= 1.0), HP_ERR_INVALID, "p < 0, p > 1 or p is NaN");
+    for (int k = 0; k < 3; ++k)
+        HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "%s: env->state_dev[%d] is null", entry, k);
+    EpisodesArgs A;
+    memset(&A, 0, sizeof(A));
+    PolicyArgs &P = A.P;
+    P.od = on->size; P.gd = gn->size;
+    P.onz = on->d; P.gnz = gn->d;
+    P.clip_obs = INFINITY; P.clip_o = on->clip; P.clip_g = gn->clip;   // agent_act_dev with clip_obs = 0
+    P.net = SlabNetPtrs{a->fragF, a->fragD, a->params};
+    P.la = a->la; P.H = a->H; P.act_dim = a->cfg.act_dim; P.max_action = (float)a->cfg.max_action;
+    A.b_obs = ro->block + ro->first * (ro->T + 1) * ro->od;
+    A.b_ag = ro->block + ro->o_ag + ro->first * (ro->T + 1) * ro->gd;
+    A.b_g = ro->block + ro->o_g + ro->first * ro->T * ro->gd;
+    A.b_act = ro->block + ro->o_act + ro->first * ro->T * ro->ad;
+    A.st = explore ? streams->d_state : nullptr;
+    A.reset_st = reset_streams ? reset_streams->d_state : nullptr;
+    A.rows = (int)ro->rows; A.T = ro->T; A.explore = explore ? 1 : 0;
+    A.n_envs = (int)n_envs;
+    A.x.ad = ro->ad;
+    A.x.amax = a->cfg.max_action;
+    A.x.noise_scale = noise_eps * a->cfg.max_action;
+    A.x.random_eps = random_eps; A.x.qn = qn; A.x.clip_abs = clip_abs;
+    A.env = *env;
+    A.success = success_dev;
+    switch (env->kind) {   // one case per environment kind (env_device.h)
+        case HP_ENV_POINT_MASS: return rollout_episodes_launch<PointMassEnvDev>(entry, ro, A, launches);
+        default: break;
+    }
+    return HP_ERR_INVALID;
 }
 
 extern "C" {
@@ -387,48 +548,43 @@ int hp_rollout_episodes(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, h
                         int32_t explore, double noise_eps, double random_eps, double qn, double clip_abs, float *success_dev) {
     HP_REQUIRE(ro && a && on && gn && env && success_dev, HP_ERR_INVALID, "hp_rollout_episodes: null argument");
     HP_SERIALISE(ro);
-    HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx && (!streams || streams->ctx == ro->ctx), HP_ERR_INVALID,
-               "hp_rollout_episodes: handles belong to different contexts");
-    HP_REQUIRE(env->kind == HP_ENV_POINT_MASS, HP_ERR_INVALID, "hp_rollout_episodes: env->kind %d is not an environment kind of this build",
-               (int)env->kind);
-    HP_REQUIRE(a->slab8 && a->H == 256 && a->ldx <= 48 && a->cfg.act_dim <= 4, HP_ERR_INVALID,
-               "hp_rollout_episodes: the agent is not slab-shaped (hidden %d, padded input width %d, act_dim %d, engine %s): it keeps "
-               "the per-step calls", a->H, a->ldx, a->cfg.act_dim, a->slab8 ? "slab8" : "other");
-    HP_REQUIRE(a->cfg.act_dim == ro->ad && on->size == ro->od && gn->size == ro->gd && on->size + gn->size == a->xdim, HP_ERR_INVALID,
-               "hp_rollout_episodes: agent / normalizer dimensions differ from the block's");
-    HP_REQUIRE(!explore || streams, HP_ERR_INVALID, "hp_rollout_episodes: explore != 0 needs `streams`");
-    HP_REQUIRE(!explore || ro->rows <= streams->n, HP_ERR_INVALID,
-               "hp_rollout_episodes: a wave of %lld environments is wider than the array of %lld streams", (long long)ro->rows,
-               (long long)streams->n);
-    HP_REQUIRE(!explore || (random_eps >= 0.0 && random_eps <= 1.0), HP_ERR_INVALID, "p < 0, p > 1 or p is NaN");
+    return rollout_episodes("hp_rollout_episodes", ro, a, on, gn, streams, nullptr, env, ro->rows, explore, noise_eps, random_eps, qn,
+                            clip_abs, success_dev, nullptr);
+}
+
+int hp_rollout_waves(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, hp_rng_streams *streams, hp_rng_streams *reset_streams,
+                     const hp_env_desc *env, int64_t n_envs, int32_t explore, double noise_eps, double random_eps, double qn,
+                     double clip_abs, float *success_dev, int32_t *launches_out) {
+    HP_REQUIRE(ro && a && on && gn && reset_streams && env && success_dev, HP_ERR_INVALID, "hp_rollout_waves: null argument");
+    HP_SERIALISE(ro);
+    HP_REQUIRE(n_envs > 0 && n_envs < (1 << 24), HP_ERR_INVALID, "hp_rollout_waves: n_envs %lld out of range", (long long)n_envs);
+    HP_REQUIRE(ro->rows > 0 && ro->first + ro->rows <= ro->n, HP_ERR_INVALID, "hp_rollout_waves: episodes [%lld, %lld) outside the block of %lld",
+               (long long)ro->first, (long long)(ro->first + ro->rows), (long long)ro->n);
+    return rollout_episodes("hp_rollout_waves", ro, a, on, gn, streams, reset_streams, env, n_envs, explore, noise_eps, random_eps, qn,
+                            clip_abs, success_dev, launches_out);
+}
+
+int hp_env_reset(hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *reset_streams, int64_t rows) {
+    HP_REQUIRE(ctx && env && reset_streams, HP_ERR_INVALID, "hp_env_reset: null argument");
+    CtxGuard guard(ctx);
+    HP_REQUIRE(reset_streams->ctx == ctx, HP_ERR_INVALID, "hp_env_reset: handles belong to different contexts");
+    HP_REQUIRE(rows > 0 && rows <= reset_streams->n, HP_ERR_INVALID,
+               "hp_env_reset: %lld environments, but the array holds %lld reset streams", (long long)rows, (long long)reset_streams->n);
     for (int k = 0; k < 3; ++k)
-        HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "hp_rollout_episodes: env->state_dev[%d] is null", k);
-    EpisodesArgs A;
-    memset(&A, 0, sizeof(A));
-    PolicyArgs &P = A.P;
-    P.od = on->size; P.gd = gn->size;
-    P.onz = on->d; P.gnz = gn->d;
-    P.clip_obs = INFINITY; P.clip_o = on->clip; P.clip_g = gn->clip;   // agent_act_dev with clip_obs = 0
-    P.rows = (int)ro->rows;
-    P.net = SlabNetPtrs{a->fragF, a->fragD, a->params};
-    P.la = a->la; P.H = a->H; P.act_dim = a->cfg.act_dim; P.max_action = (float)a->cfg.max_action;
-    A.b_obs = ro->block + ro->first * (ro->T + 1) * ro->od;
-    A.b_ag = ro->block + ro->o_ag + ro->first * (ro->T + 1) * ro->gd;
-    A.b_g = ro->block + ro->o_g + ro->first * ro->T * ro->gd;
-    A.b_act = ro->block + ro->o_act + ro->first * ro->T * ro->ad;
-    A.st = explore ? streams->d_state : nullptr;
-    A.rows = (int)ro->rows; A.T = ro->T; A.explore = explore ? 1 : 0;
-    A.x.ad = ro->ad;
-    A.x.amax = a->cfg.max_action;
-    A.x.noise_scale = noise_eps * a->cfg.max_action;
-    A.x.random_eps = random_eps; A.x.qn = qn; A.x.clip_abs = clip_abs;
-    A.env = *env;
-    A.success = success_dev;
+        HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "hp_env_reset: env->state_dev[%d] is null", k);
     switch (env->kind) {   // one case per environment kind (env_device.h)
-        case HP_ENV_POINT_MASS: return rollout_episodes_launch<PointMassEnvDev>(ro, A);
+        case HP_ENV_POINT_MASS: return env_reset_launch<PointMassEnvDev>(ctx, *env, reset_streams->d_state, rows);
         default: break;
     }
+    hp_set_error("hp_env_reset: env->kind %d is not an environment kind of this build", (int)env->kind);
     return HP_ERR_INVALID;
+}
+
+int hp_rollout_debug_set_launch_cap(hp_rollout *ro, int64_t timesteps) {
+    HP_REQUIRE(ro && timesteps >= 0, HP_ERR_INVALID, "hp_rollout_debug_set_launch_cap: bad argument");
+    HP_SERIALISE(ro);
+    ro->launch_cap = timesteps ? timesteps : HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS;
+    return HP_OK;
 }
 
 int hp_rollout_set_action_max(hp_rollout *ro, double action_max) {

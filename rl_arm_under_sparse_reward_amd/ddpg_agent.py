@@ -52,6 +52,7 @@ class ddpg_agent:
         self._rollouts = {}              # DeviceEpisodes blocks by episode count
         self.explore_streams = None      # random.DeviceRandomStreams: one exploration stream per environment (enable_explore_streams)
         self.rollout_form = None         # 'fused' | 'stepped': how the most recent wave of collect_episodes_device was collected
+        self.rollout_launches = None     # rollout launches of the most recent collect_episodes_device call (fused form)
         self.rollout_reason = None       # ... and, when stepped, why (device_env.fused_rollout_reason)
         self.env_params = env_params
         self.ctx = ctx or _lib.Context.default()
@@ -659,7 +660,10 @@ class ddpg_agent:
         independent across environments (`device_env.fused_rollout_reason`), ONE launch per wave (hp_rollout_episodes), the same
         bits; `self.rollout_form` says which form the last wave took.  Exploration (:174-184, the +-0.15 clip from epoch 100) is drawn on the device
         from `self.rng`, for env 0 .. n-1 in turn like the host lockstep path -- or, after `enable_explore_streams`, for every
-        environment from its own stream (a wave of k < n_envs rows advances the streams of those k only).  Returns a `DeviceEpisodes` handle for
+        environment from its own stream (a wave of k < n_envs rows advances the streams of those k only).  With an environment that is
+        reset on the device (`vec_env.enable_device_reset()`) the fused form issues ALL waves of the call as one launch
+        (hp_rollout_waves; `self.rollout_launches` says how many the launch cap made of it), calls no `vec_env.reset()` and hands
+        `success_out` one tensor of n_rollouts flags.  Returns a `DeviceEpisodes` handle for
         `train_cycle` / `buffer.store_episode`; `.numpy()` gives the four arrays `collect_episodes` returns."""
         from .device_env import DeviceEpisodes, binomial1_qn, fused_rollout_reason
         vec_env = vec_env or self.vec_env
@@ -681,6 +685,24 @@ class ddpg_agent:
         self.rollout_reason = fused_rollout_reason(getattr(vec_env, "is_native_device_env", False), self._slab_shaped(), explore,
                                                    streams is not None)
         self.rollout_form = 'fused' if self.rollout_reason is None else 'stepped'
+        self.rollout_launches = 0 if self.rollout_form == 'fused' else None
+        reset_streams = getattr(vec_env, "reset_streams", None)
+        if self.rollout_form == 'fused' and reset_streams is not None:
+            # reset on the device: all waves of the call in one launch (or the few the launch cap dictates), no host reset
+            env = vec_env.env_desc()
+            success = torch.empty(n_total, dtype=torch.float32, device=vec_env.pos.device)
+            launches = C.c_int32()
+            with self.ctx.torch_bridge():
+                _lib.check(self.lib.hp_rollout_begin(eps.h, 0, n_total))
+                _lib.check(self.lib.hp_rollout_waves(eps.h, self.h, self.o_norm.h, self.g_norm.h,
+                                                     streams.h if streams is not None else None, reset_streams.h, C.byref(env),
+                                                     vec_env.n_envs, 1 if explore else 0, float(self.args.noise_eps),
+                                                     float(self.args.random_eps), qn, clip_abs, p(success), C.byref(launches)))
+            self.rollout_launches = int(launches.value)
+            vec_env.active = (n_total - 1) % vec_env.n_envs + 1      # the environments of the last wave
+            if success_out is not None:
+                success_out.append(success)
+            return eps
         while done < n_total:
             k = min(vec_env.n_envs, n_total - done)
             o = vec_env.reset() if k == vec_env.n_envs else vec_env.reset(k)
@@ -700,6 +722,7 @@ class ddpg_agent:
                                                             float(self.args.random_eps), qn, clip_abs, p(success)))
                 if success_out is not None:
                     success_out.append(success)
+                self.rollout_launches += 1
                 done += k
                 continue
             actions = torch.empty((k, ad), dtype=torch.float32, device=o['observation'].device)
@@ -787,6 +810,8 @@ class ddpg_agent:
         state_path, resume, first_epoch = getattr(self.args, "state_path", None), getattr(self.args, "resume", None), 0
         if self.vec_env is not None and getattr(self.args, "explore_streams", False) and self.explore_streams is None:
             self.enable_explore_streams()    # args.explore_streams: before a resume, whose state carries the streams' states
+        if self.vec_env is not None and getattr(self.args, "device_reset", False) and getattr(self.vec_env, "reset_streams", None) is None:
+            self.vec_env.enable_device_reset(self.ctx)   # args.device_reset: likewise before a resume
         if resume:
             self._resume_state(resume)
             first_epoch = self.resumed_at[0]
@@ -844,7 +869,8 @@ class ddpg_agent:
         the device and copied to the host once at the end."""
         flags, remaining = [], int(self.args.n_test_rollouts)
         while remaining > 0:
-            k = min(self.vec_env.n_envs, remaining)
+            # one call per wave; with reset on the device one call for all of them (one launch: hp_rollout_waves)
+            k = remaining if getattr(self.vec_env, "reset_streams", None) is not None else min(self.vec_env.n_envs, remaining)
             self.collect_episodes_device(n_rollouts=k, explore=False, success_out=flags)
             remaining -= k
         wins = torch.cat([f.reshape(-1).to(torch.float64) for f in flags]).cpu().numpy()

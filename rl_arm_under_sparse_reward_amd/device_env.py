@@ -26,6 +26,12 @@ and a whole wave of its episodes is ONE launch (hp_rollout_episodes: every workg
 whenever `fused_rollout_reason` finds nothing against it; `reset` stays on the host, `step` stays available, and after a fused
 wave the state tensors hold what T `step` calls would have left.  `NativePointMassVecEnv` is the first such environment.
 
+**Reset on the device** (opt-in: `env.enable_device_reset()`, `args.device_reset`).  The environment's reset generators move into
+one device stream per environment (`env.reset_streams`, a `random.DeviceRandomStreams` holding the very states of `env.rs`), and
+`reset(k)` becomes one launch (hp_env_reset) with no host loop, no upload and no host wait.  `collect_episodes_device` then
+issues ALL waves of a call as one launch (hp_rollout_waves: the kernel resets an environment between two of its episodes), or the
+few launches `_lib.ROLLOUT_MAX_LAUNCH_TIMESTEPS` dictates; `agent.rollout_launches` says how many.  Same bits as the host reset.
+
 Draw order with n environments: per timestep, for env i = 0 .. n-1: randn(action), uniform(action), binomial(1) -- the order of
 the host lockstep path (`collect_episodes` on a list of environments); with one environment it is the reference's own order.
 
@@ -188,10 +194,82 @@ class NativePointMassVecEnv(PointMassVecEnv):
     parent's, so the per-step protocol works on it unchanged -- and with device="cpu" it is simply the parent."""
 
     is_native_device_env = True
+    reset_streams = None     # random.DeviceRandomStreams after enable_device_reset(): reset stream i = the state of rs[i]
 
     def native_desc(self):
         """hp_env_desc of the environments stepped now: kind, params [step_scale, distance_threshold], state [pos, vel, goal]
-        (float64 [active, 3] each, contiguous; the launch reads all three and writes pos and vel in place)."""
+        (float64 [active, 3] each, contiguous; the launch reads all three and writes them in place).  With device reset the
+        tensors are [n_envs, 3] for good and the environments stepped now are their first `active` rows."""
         self.pos, self.vel, self.goal = self.pos.contiguous(), self.vel.contiguous(), self.goal.contiguous()
         return {"kind": _lib.ENV_POINT_MASS, "params": [self.step_scale, self.distance_threshold],
                 "state": [self.pos, self.vel, self.goal]}
+
+    def env_desc(self):
+        """`native_desc()` as the library's struct (hp_env_desc)."""
+        desc = self.native_desc()
+        env = _lib.EnvDesc(kind=int(desc["kind"]))
+        for i, v in enumerate(desc["params"]):
+            env.params[i] = float(v)
+        for i, t in enumerate(desc["state"]):
+            env.state_dev[i] = t.data_ptr()
+        return env
+
+    def enable_device_reset(self, ctx=None):
+        """Reset on the device from now on (hp_env_reset; inside the launch of hp_rollout_waves): reset stream i takes over the
+        current state of `self.rs[i]`, so enabling it mid-run continues the same sequence -- on a fresh environment stream i is
+        RandomState(seed + i) -- and the host generators are not advanced any more.  The state tensors become [n_envs, 3] for the
+        life of the environment (the rows stepped now keep their values); `reset(k)`, `step` and `_observation` work on the
+        first k rows.  `ctx`: the library context of the agent that collects from this environment (default: the default one)."""
+        from .random import DeviceRandomStreams
+        if self.device.type != "cuda":
+            raise ValueError(f"enable_device_reset: the environment lives on device '{self.device}': a reset on the device needs "
+                             "a GPU environment (device='cuda')")
+        if self.reset_streams is not None:
+            return self.reset_streams
+        self.ctx = ctx or _lib.Context.default()
+        streams = DeviceRandomStreams(self.n_envs, ctx=self.ctx)
+        streams.set_states([r.get_state() for r in self.rs])
+        full = []
+        for t in (self.pos, self.vel, self.goal):
+            f = torch.zeros((self.n_envs, 3), dtype=torch.float64, device=self.device)
+            f[:t.shape[0]] = t
+            full.append(f)
+        self.pos, self.vel, self.goal = full
+        self.reset_streams = streams
+        return streams
+
+    def _observation(self):
+        if self.reset_streams is None:
+            return super()._observation()
+        k = self.active
+        obs = torch.zeros((k, 27), dtype=torch.float64, device=self.device)
+        obs[:, 0:3] = self.pos[:k]
+        obs[:, 3:6] = self.vel[:k]
+        obs[:, 12:15] = self.pos[:k]
+        return {'observation': obs, 'achieved_goal': self.pos[:k].clone(), 'desired_goal': self.goal[:k].clone()}
+
+    def reset(self, n_active=None):
+        if self.reset_streams is None:
+            return super().reset(n_active)
+        k = self.n_envs if n_active is None else int(n_active)
+        if not 0 < k <= self.n_envs:
+            raise ValueError("n_active outside [1, n_envs]")
+        env = self.env_desc()
+        with self.ctx.torch_bridge():       # on torch's current stream, in order with the environment's own kernels
+            _lib.check(self.ctx.lib.hp_env_reset(self.ctx.h, C.byref(env), self.reset_streams.h, k))
+        self.active = k
+        return self._observation()
+
+    def step(self, actions):
+        if self.reset_streams is None:
+            return super().step(actions)
+        k = self.active
+        a = torch.clamp(actions.to(torch.float64), -0.5, 0.5)
+        scaled = self.step_scale * a[:, :3]                 # the parent's operations on the first `active` rows, in place
+        new = torch.clamp(self.pos[:k] + scaled, 0.0, 0.5)
+        self.vel[:k] = new - self.pos[:k]
+        self.pos[:k] = new
+        observation = self._observation()
+        success = (self._distance(observation['achieved_goal'], self.goal[:k]) < self.distance_threshold).to(torch.float32)
+        info = {'is_success': success}
+        return observation, self.compute_reward(observation['achieved_goal'], self.goal[:k], info), False, info

@@ -13,6 +13,9 @@ File: ONE uncompressed .npz of named arrays a person can open with numpy --
     np_random_key  success_rates  extra  manifest
     explore_stream_{keys,pos,has_gauss,gauss}      only when the agent explores with one stream per environment
                                                    (ddpg_agent.enable_explore_streams): uint32 [n, 624], int32 [n], int32 [n], float64 [n]
+    reset_stream_{keys,pos,has_gauss,gauss}        only when the agent's environment is reset on the device
+                                                   (device_env.NativePointMassVecEnv.enable_device_reset): the same four, one
+                                                   reset stream per environment; manifest field 'reset_streams'
 
 `manifest` is JSON text: format version, dims, capacity, T, rank, world size, library ABI, dtype / shape / checksum (A, B) of every
 device array, and the host scalars.  It is written to a temporary name and renamed, so a killed process never leaves a half-written
@@ -32,7 +35,7 @@ the buffer as the episodes written since the full state FULL was captured --
 
     buffer_delta_slots                      int64 [n_dirty], ascending
     buffer_delta_{obs,ag,g,actions}         float64 [n_dirty, ...]: the rows of those slots
-    buffer_counters, host arrays, exploration-stream arrays as in a full state
+    buffer_counters, host arrays, exploration- and reset-stream arrays as in a full state
 
 with manifest format 2, "kind": "delta", its own "capture_epoch", "dims" with the NEW current_size and
 "base": {name, lineage, capture_epoch, current_size, sums of the base's four buffer arrays}.  A full state's manifest carries
@@ -105,16 +108,19 @@ def expected_shapes(dims: dict) -> dict:
     return out
 
 
-def stream_shapes(n: int) -> dict:
-    """name -> (dtype, shape) of the arrays that carry n per-environment exploration streams (random.DeviceRandomStreams): numpy's
-    legacy state of every stream -- key, position, has_gauss, cached normal.  A state saved without such streams has none of
-    them and no 'explore_streams' field in its manifest."""
+def stream_shapes(n: int, family: str = "explore") -> dict:
+    """name -> (dtype, shape) of the arrays that carry n per-environment streams (random.DeviceRandomStreams) of one family --
+    'explore': the exploration streams, 'reset': the environments' reset streams: numpy's legacy state of every stream -- key,
+    position, has_gauss, cached normal.  A state saved without the streams of a family has none of its arrays and no
+    '<family>_streams' field in its manifest."""
     n = int(n)
-    return {"explore_stream_keys": ("<u4", (n, 624)), "explore_stream_pos": ("<i4", (n,)),
-            "explore_stream_has_gauss": ("<i4", (n,)), "explore_stream_gauss": ("<f8", (n,))}
+    return {f"{family}_stream_keys": ("<u4", (n, 624)), f"{family}_stream_pos": ("<i4", (n,)),
+            f"{family}_stream_has_gauss": ("<i4", (n,)), f"{family}_stream_gauss": ("<f8", (n,))}
 
 
+STREAM_FAMILIES = ("explore", "reset")
 STREAM_ARRAYS = tuple(stream_shapes(0))
+RESET_STREAM_ARRAYS = tuple(stream_shapes(0, "reset"))
 DEVICE_ARRAYS = tuple(expected_shapes({"obs": 1, "goal": 1, "action": 1, "hidden": 1, "T": 1, "current_size": 0}))
 
 
@@ -243,30 +249,33 @@ def check_arrays(arrays, manifest, sums=True, where="state"):
 
 
 def check_stream_arrays(arrays, manifest, where="state"):
-    """The per-environment exploration streams of a state: all four arrays or none, as the manifest's 'explore_streams' field
-    says, shaped for its stream count, positions inside [0, 624], and summing to what it records (they are a few KB per stream and
-    reach the device by a plain copy, so their sums are always checked here, on the host)."""
-    rec = manifest.get("explore_streams")
-    if rec is None:
-        extra = [n for n in STREAM_ARRAYS if n in arrays]
-        if extra:
-            raise StateError(f"{where}: array '{extra[0]}' is present but the manifest has no 'explore_streams' field")
-        return
-    want = stream_shapes(rec["n"])
-    for name in STREAM_ARRAYS:
-        _check_array(where, name, arrays, rec["arrays"], want[name], f"{rec['n']} streams", True, entry=False)
-    pos = arrays["explore_stream_pos"]
-    if pos.size and (int(pos.min()) < 0 or int(pos.max()) > 624):
-        raise StateError(f"{where}: array 'explore_stream_pos' holds a position outside [0, 624]")
+    """The per-environment streams of a state, family by family (exploration streams: field 'explore_streams'; the environments'
+    reset streams: 'reset_streams'): all four arrays or none, as the manifest's field says, shaped for its stream count, positions
+    inside [0, 624], and summing to what it records (they are a few KB per stream and reach the device by a plain copy, so their
+    sums are always checked here, on the host)."""
+    for family in STREAM_FAMILIES:
+        field, names = f"{family}_streams", tuple(stream_shapes(0, family))
+        rec = manifest.get(field)
+        if rec is None:
+            extra = [n for n in names if n in arrays]
+            if extra:
+                raise StateError(f"{where}: array '{extra[0]}' is present but the manifest has no '{field}' field")
+            continue
+        want = stream_shapes(rec["n"], family)
+        for name in names:
+            _check_array(where, name, arrays, rec["arrays"], want[name], f"{rec['n']} streams", True, entry=False)
+        pos = arrays[f"{family}_stream_pos"]
+        if pos.size and (int(pos.min()) < 0 or int(pos.max()) > 624):
+            raise StateError(f"{where}: array '{family}_stream_pos' holds a position outside [0, 624]")
 
 
-def stream_record(keys, pos, has_gauss, gauss):
-    """(arrays, manifest field) of n exploration streams, as a state file stores them."""
+def stream_record(keys, pos, has_gauss, gauss, family="explore"):
+    """(arrays, manifest field) of n streams of one family, as a state file stores them."""
     n = int(np.asarray(pos).size)
-    arrays = {}
-    for (name, (dt, shape)), a in zip(stream_shapes(n).items(), (keys, pos, has_gauss, gauss)):
+    arrays, shapes = {}, stream_shapes(n, family)
+    for (name, (dt, shape)), a in zip(shapes.items(), (keys, pos, has_gauss, gauss)):
         arrays[name] = np.ascontiguousarray(a, dtype=dt).reshape(shape)
-    rec = {"n": n, "arrays": {k: {"dtype": stream_shapes(n)[k][0], "shape": list(a.shape), "sum": list(checksum(a))}
+    rec = {"n": n, "arrays": {k: {"dtype": shapes[k][0], "shape": list(a.shape), "sum": list(checksum(a))}
                               for k, a in arrays.items()}}
     return arrays, rec
 
@@ -449,6 +458,11 @@ def known_base(agent, base_path):
     return key, rec[0], rec[1]
 
 
+def _reset_streams(agent):
+    """The reset streams of the agent's vectorised environment, or None (no such environment, or it is reset on the host)."""
+    return getattr(getattr(agent, "vec_env", None), "reset_streams", None)
+
+
 class PendingSave:
     """A capture in flight (`save_training_state(wait=False)`): the device part was snapshotted in stream order when this object
     was made, the host part (numpy's stream, success_rates, savetime) copied at the same moment; training may go on.
@@ -487,6 +501,10 @@ class PendingSave:
         if streams is not None:
             # copied now (a few KB per stream; synchronises), so rollouts that follow a wait=False capture do not move them
             stream_arrays, self.host["explore_streams"] = stream_record(*streams.get_arrays())
+            self.host_arrays.update(stream_arrays)
+        reset_streams = _reset_streams(agent)
+        if reset_streams is not None:      # the environments' reset generators (device_env: enable_device_reset), likewise
+            stream_arrays, self.host["reset_streams"] = stream_record(*reset_streams.get_arrays(), family="reset")
             self.host_arrays.update(stream_arrays)
 
     def done(self):
@@ -580,6 +598,16 @@ def load(agent, path, verify_host=False, base=None):
                          "agent has none: call enable_explore_streams() (args.explore_streams) before loading")
     if streams is not None and int(rec["n"]) != len(streams):
         raise StateError(f"{where}: array 'explore_stream_keys' holds {rec['n']} streams, the agent has {len(streams)} environments")
+    resets, rrec = _reset_streams(agent), manifest.get("reset_streams")
+    rnames = ", ".join(f"'{n}'" for n in RESET_STREAM_ARRAYS)
+    if resets is not None and rrec is None:
+        raise StateError(f"{where}: the agent's environment is reset on the device, but the state was saved without reset streams: "
+                         f"arrays {rnames} are missing")
+    if resets is None and rrec is not None:
+        raise StateError(f"{where}: the state carries {rrec['n']} per-environment reset streams (arrays {rnames}), but the agent's "
+                         "environment is reset on the host: call vec_env.enable_device_reset() (args.device_reset) before loading")
+    if resets is not None and int(rrec["n"]) != len(resets):
+        raise StateError(f"{where}: array 'reset_stream_keys' holds {rrec['n']} streams, the agent has {len(resets)} environments")
     check_arrays(arrays, manifest, sums=verify_host, where=where)
     agent._flush_updates()
     sections, total = _layout(agent, mine["current_size"])
@@ -612,6 +640,8 @@ def load(agent, path, verify_host=False, base=None):
     agent.rng._gauss = (int(manifest["rng_gauss"][0]), float(manifest["rng_gauss"][1]))
     if streams is not None:
         streams.set_arrays(*(arrays[n] for n in STREAM_ARRAYS))
+    if resets is not None:
+        resets.set_arrays(*(arrays[n] for n in RESET_STREAM_ARRAYS))
     agent.success_rates = [float(x) for x in arrays["success_rates"]]
     agent.savetime = int(manifest["savetime"])
     return arrays["extra"].tobytes(), manifest

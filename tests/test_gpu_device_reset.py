@@ -1,0 +1,312 @@
+"""Native environments reset on the device (hp_env_reset, k_env_reset) and all waves of a call in one launch (hp_rollout_waves, the
+wave loop of k_rollout_episodes in csrc/rollout.hip; device_env.NativePointMassVecEnv.enable_device_reset).  Every comparison is
+bit for bit between two agents built identically on NativePointMassVecEnv: A as it stands (host reset, one launch per wave), B with
+`enable_device_reset()`."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import bits
+from rl_arm_under_sparse_reward_amd import _lib
+from rl_arm_under_sparse_reward_amd import train_state as ts
+from rl_arm_under_sparse_reward_amd.ddpg_agent import NET_ACTOR, NET_CRITIC
+from rl_arm_under_sparse_reward_amd.device_env import DeviceEpisodes, NativePointMassVecEnv, PointMassVecEnv, binomial1_qn
+from rl_arm_under_sparse_reward_amd.random import DeviceRandomStreams
+from test_gpu_device_rollout import make, primed
+from test_gpu_explore_streams import assert_states_bit_equal
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+p = lambda t: C.c_void_p(t.data_ptr())
+
+
+def agent_on(n_envs, T, streams=True, reset=False, env_seed=10, base=900, before_reset=None, **kw):
+    torch.manual_seed(0)
+    kw.setdefault("noise_eps", 0.05)
+    a = make(NativePointMassVecEnv(n_envs, seed=env_seed, device=DEV, max_timesteps=T), T=T, **kw)
+    primed(a)
+    if streams:
+        a.enable_explore_streams(base_seed=base)
+    if before_reset:
+        before_reset(a)
+    if reset:
+        a.vec_env.enable_device_reset(a.ctx)
+    return a
+
+
+def both(n_envs, T, **kw):
+    """(A: host reset, one launch per wave; B: the same with enable_device_reset())"""
+    return agent_on(n_envs, T, reset=False, **kw), agent_on(n_envs, T, reset=True, **kw)
+
+
+def assert_calls_equal(A, B, form="fused", launches=1, **kw):
+    """One collect_episodes_device call on both agents: episode bytes, success flags, the environments stepped last, exploration
+    and reset stream states (B's reset streams against A's host generators)."""
+    flags, got = ([], []), []
+    for a, f in zip((A, B), flags):
+        learner = a.rng.get_state()
+        got.append(a.collect_episodes_device(success_out=f, **kw).numpy())
+        if a.explore_streams is not None or not kw.get("explore", True):
+            assert_states_bit_equal(a.rng.get_state(), learner, "learner stream")
+    assert A.rollout_form == B.rollout_form == form, (A.rollout_form, B.rollout_form, B.rollout_reason)
+    if form == "fused":
+        assert B.rollout_launches == launches, B.rollout_launches
+    for name, x, y in zip(("obs", "ag", "g", "actions"), *got):
+        assert x.shape == y.shape and np.array_equal(bits(x), bits(y)), name
+    fa, fb = (torch.cat([f.reshape(-1) for f in fl]) for fl in flags)
+    assert fa.dtype == fb.dtype == torch.float32 and fa.shape == fb.shape and torch.equal(fa, fb)
+    if form == "fused":
+        assert len(flags[1]) == 1                                       # one tensor of n_rollouts flags
+    k = B.vec_env.active
+    assert k == A.vec_env.pos.shape[0] == A.vec_env.active
+    for name in ("pos", "vel", "goal"):
+        x, y = getattr(A.vec_env, name), getattr(B.vec_env, name)
+        assert tuple(y.shape) == (B.vec_env.n_envs, 3)
+        assert np.array_equal(bits(x.cpu().numpy()), bits(y[:k].cpu().numpy())), name
+    if A.explore_streams is not None:
+        for i, (x, y) in enumerate(zip(A.explore_streams.get_states(), B.explore_streams.get_states())):
+            assert_states_bit_equal(x, y, ("exploration stream", i))
+    for i, (r, y) in enumerate(zip(A.vec_env.rs, B.vec_env.reset_streams.get_states())):
+        assert_states_bit_equal(r.get_state(), y, ("reset stream", i))
+    return got[1]
+
+
+# --------------------------------------------------------------------------------------------------- 1. the stand-alone reset
+@pytest.mark.parametrize("n_envs", [1, 3, 5])
+def test_reset_equals_the_host_reset(n_envs):
+    """reset(k), full and partial, against PointMassVecEnv.reset: state, observation rows and stream states; the streams behind k
+    are untouched and a cached normal survives (the reset draws no normals)."""
+    host, env = PointMassVecEnv(n_envs, seed=21, device=DEV), NativePointMassVecEnv(n_envs, seed=21, device=DEV)
+    last = n_envs - 1
+    cached = host.rs[last].get_state()
+    cached = (cached[0], cached[1], cached[2], 1, 0.3125)
+    host.rs[last].set_state(cached)
+    env.rs[last].set_state(cached)
+    streams = env.enable_device_reset()
+    assert env.reset_streams is streams and len(streams) == n_envs and env.enable_device_reset() is streams
+    for k in (n_envs, max(1, n_envs - 2), n_envs, 1):
+        before = streams.get_states()
+        want, got = host.reset(k), env.reset(None if k == n_envs else k)
+        assert env.active == k
+        for key in want:
+            assert got[key].shape == want[key].shape and np.array_equal(bits(got[key].cpu().numpy()), bits(want[key].cpu().numpy())), (k, key)
+        for name in ("pos", "vel", "goal"):
+            x, y = getattr(host, name), getattr(env, name)
+            assert tuple(y.shape) == (n_envs, 3) and np.array_equal(bits(x.cpu().numpy()), bits(y[:k].cpu().numpy())), (k, name)
+        after = streams.get_states()
+        for i in range(n_envs):
+            assert_states_bit_equal(host.rs[i].get_state(), after[i], (k, i))
+            if i >= k:
+                assert_states_bit_equal(before[i], after[i], (k, i, "untouched"))
+        assert after[last][3] == 1 and after[last][4] == 0.3125
+    # the per-step protocol on the first `active` rows
+    host.reset(max(1, n_envs - 1)); env.reset(max(1, n_envs - 1))
+    act = torch.from_numpy(np.random.RandomState(0).uniform(-0.7, 0.7, (env.active, 4)).astype(np.float32)).to(DEV)
+    (oa, ra, _, ia), (ob, rb, _, ib) = host.step(act), env.step(act)
+    for key in oa:
+        assert np.array_equal(bits(oa[key].cpu().numpy()), bits(ob[key].cpu().numpy())), key
+    assert torch.equal(ra, rb) and torch.equal(ia["is_success"], ib["is_success"])
+
+
+# ------------------------------------------------------------------------- 2. one launch, many waves, exploring with streams
+@pytest.mark.parametrize("epoch", [0, 100])
+@pytest.mark.parametrize("n_envs,n_rollouts", [(1, 1), (3, 3), (4, 7), (5, 3), (9, 20), (2, 25)])
+def test_all_waves_in_one_launch_equal_one_launch_per_wave(n_envs, n_rollouts, epoch):
+    """Full slabs, partial slabs and partial waves: a partial last wave leaves the streams of the environments it leaves out where
+    the wave before left them (A's host generators and exploration streams say where that is)."""
+    A, B = both(n_envs, 20)
+    assert_calls_equal(A, B, n_rollouts=n_rollouts, epoch=epoch)
+    assert B.vec_env.active == (n_rollouts - 1) % n_envs + 1
+
+
+# ------------------------------------------------------------------------------------------------------------ 3. noise-free
+@pytest.mark.parametrize("streams", [True, False])
+def test_noise_free_waves_equal(streams):
+    A, B = both(4, 20, streams=streams)
+    before = B.explore_streams.get_states() if streams else None
+    assert_calls_equal(A, B, explore=False, n_rollouts=7)
+    if streams:
+        for i, (x, y) in enumerate(zip(before, B.explore_streams.get_states())):
+            assert_states_bit_equal(x, y, i)
+
+
+@pytest.mark.parametrize("n_test", [3, 10])
+def test_evaluation_returns_the_same_rate_in_one_launch(n_test):
+    A, B = both(4, 20, n_test_rollouts=n_test)
+    rates = [a._eval_agent() for a in (A, B)]
+    assert A.rollout_form == B.rollout_form == "fused" and B.rollout_launches == 1
+    assert isinstance(rates[1], float) and rates[0] == rates[1], rates
+    for i, (r, y) in enumerate(zip(A.vec_env.rs, B.vec_env.reset_streams.get_states())):
+        assert_states_bit_equal(r.get_state(), y, i)
+
+
+# ------------------------------------------------------------------- 4. a block boundary in the reset stream inside a launch
+@pytest.mark.parametrize("start_pos", [None, 618])
+def test_the_reset_stream_crosses_a_block_inside_a_launch(start_pos):
+    """Twelve words per reset: from a fresh stream the 624-word block ends after 52 resets, so the key is regenerated and committed
+    mid-launch; from pos = 618 the very first reset straddles a block."""
+    def shift(rs):
+        if start_pos is not None:
+            st = rs.get_state()
+            rs.set_state((st[0], st[1], start_pos, 0, 0.0))
+
+    A, B = both(1, 2, before_reset=lambda a: shift(a.vec_env.rs[0]))
+    key0 = B.vec_env.reset_streams.get_state(0)[1].copy()
+    assert_calls_equal(A, B, n_rollouts=60)
+    host = np.random.RandomState(10)
+    shift(host)
+    for _ in range(60):
+        host.uniform(0.0, 0.5, 3); host.uniform(0.0, 0.5, 3)
+    got = B.vec_env.reset_streams.get_state(0)
+    assert_states_bit_equal(host.get_state(), got, "60 resets")
+    assert not np.array_equal(got[1], key0) and 0 < got[2] < 624
+
+
+# -------------------------------------------------------------------------------------- 5. the per-step path with device reset
+def test_the_shared_stream_stays_per_step_and_resets_on_the_device():
+    A, B = both(3, 20, streams=False)
+    assert_calls_equal(A, B, form="stepped", n_rollouts=5)
+    assert "single shared stream" in B.rollout_reason and B.rollout_launches is None
+    sa, sb = A.rng.get_state(), B.rng.get_state()
+    assert np.array_equal(sa[1], sb[1]) and sa[2:] == sb[2:]
+
+
+# ------------------------------------------------------------------------------------------------------ 6. enabling mid-run
+def test_enabling_mid_run_continues_the_sequence():
+    A, B = agent_on(3, 20), agent_on(3, 20)
+    first = [a.collect_episodes_device(n_rollouts=2).numpy() for a in (A, B)]       # a partial wave on the host reset: [2, 3] tensors
+    for x, y in zip(*first):
+        assert np.array_equal(bits(x), bits(y))
+    B.vec_env.enable_device_reset(B.ctx)
+    assert tuple(B.vec_env.pos.shape) == (3, 3) and B.vec_env.active == 2
+    assert np.array_equal(bits(A.vec_env.pos.cpu().numpy()), bits(B.vec_env.pos[:2].cpu().numpy()))
+    assert_calls_equal(A, B, n_rollouts=3)
+    assert_calls_equal(A, B, n_rollouts=4)
+
+
+# ---------------------------------------------------------------------------------------------------------- 7. the launch cap
+@pytest.mark.parametrize("cap,launches", [(10, 2), (1, 3)])
+def test_a_call_split_by_the_launch_cap_gives_the_same_bits(cap, launches):
+    """T = 5, eight episodes on three environments = three waves; a cap of ten timesteps holds two waves, a cap below T one."""
+    T, n, total = 5, 3, 8
+    A, B = both(n, T)
+    B._rollouts[total] = DeviceEpisodes(B.ctx, B.buffer._dev, total)
+    _lib.check(B.lib.hp_rollout_debug_set_launch_cap(B._rollouts[total].h, cap))
+    assert_calls_equal(A, B, launches=launches, n_rollouts=total)
+    _lib.check(B.lib.hp_rollout_debug_set_launch_cap(B._rollouts[total].h, 0))
+    assert_calls_equal(A, B, launches=1, n_rollouts=total)
+
+
+# --------------------------------------------------------------------------------------- 8. a cycle on top, the training state
+def test_cycles_and_the_training_state(tmp_path):
+    T, n, kw = 10, 3, dict(n_batches=3, buffer_episodes=20, seed=12)
+
+    def same_learner(x, y):
+        for slot in (NET_ACTOR, NET_CRITIC):
+            assert np.array_equal(bits(x._get_flat(slot)), bits(y._get_flat(slot))), slot
+        sa, sb = x.rng.get_state(), y.rng.get_state()
+        assert np.array_equal(sa[1], sb[1]) and sa[2:] == sb[2:]
+
+    A, B = both(n, T, **kw)
+    for a in (A, B):
+        a.train_cycle(a.collect_episodes_device(n_rollouts=5))
+    assert B.rollout_launches == 1 and A.buffer.current_size == B.buffer.current_size == 5
+    same_learner(A, B)
+    path = B.save_training_state(tmp_path / "mid.npz")
+    arrays, manifest = ts.read_state(path)
+    assert manifest["reset_streams"]["n"] == n and manifest["explore_streams"]["n"] == n
+    for name, a in zip(ts.RESET_STREAM_ARRAYS, B.vec_env.reset_streams.get_arrays()):
+        assert np.array_equal(bits(arrays[name]), bits(a)), name
+    ts.verify(path)
+    for a in (A, B):
+        a.train_cycle(a.collect_episodes_device(n_rollouts=5))
+    same_learner(A, B)
+
+    R = agent_on(n, T, reset=True, env_seed=77, base=1, **kw)            # other reset generators, other exploration streams
+    R.load_training_state(path)
+    got = R.collect_episodes_device(n_rollouts=5)
+    want = B._rollouts[5].numpy()
+    for x, y in zip(got.numpy(), want):
+        assert np.array_equal(bits(x), bits(y))
+    R.train_cycle(got)
+    same_learner(B, R)
+    for x, y in zip(R.vec_env.reset_streams.get_arrays(), B.vec_env.reset_streams.get_arrays()):
+        assert np.array_equal(bits(x), bits(y))
+    # a delta carries them too
+    delta = B.save_training_state(tmp_path / "d.npz", base=path)
+    assert ts.read_manifest(delta)["reset_streams"]["n"] == n and ts.verify(delta, base=path)["kind"] == "delta"
+
+
+# ------------------------------------------------------------------------------------------------------------ 9. refusals
+def test_refusals_carry_the_librarys_message(tmp_path):
+    T, n = 10, 4
+    B = agent_on(n, T, reset=True)
+    env, lib = B.vec_env, B.lib
+    eps = DeviceEpisodes(B.ctx, B.buffer._dev, n)
+    success = torch.empty(n, dtype=torch.float32, device=DEV)
+    narrow = DeviceRandomStreams(2, base_seed=1, ctx=B.ctx)
+    env.reset()
+    state = (env.reset_streams.get_arrays(), narrow.get_arrays(), B.explore_streams.get_arrays(), env.pos.clone(), env.goal.clone())
+
+    def waves(reset_h, desc, n_envs=n):
+        with B.ctx.torch_bridge():
+            _lib.check(lib.hp_rollout_waves(eps.h, B.h, B.o_norm.h, B.g_norm.h, B.explore_streams.h, reset_h, C.byref(desc), n_envs, 1,
+                                            0.05, 0.3, binomial1_qn(0.3)[0], 0.0, p(success), None))
+
+    def reset(reset_h, desc, rows):
+        with B.ctx.torch_bridge():
+            _lib.check(lib.hp_env_reset(B.ctx.h, C.byref(desc), reset_h, rows))
+
+    def desc(kind=None, null=None):
+        d = env.env_desc()
+        if kind is not None:
+            d.kind = kind
+        if null is not None:
+            d.state_dev[null] = None
+        return d
+
+    with pytest.raises(ValueError, match=r"hp_rollout_waves: 4 environments, but the array holds 2 reset streams"):
+        waves(narrow.h, desc())
+    with pytest.raises(ValueError, match=r"hp_env_reset: 3 environments, but the array holds 2 reset streams"):
+        reset(narrow.h, desc(), 3)
+    with pytest.raises(ValueError, match=r"hp_rollout_begin: episodes \[0, 5\) outside the block of 4"):
+        _lib.check(lib.hp_rollout_begin(eps.h, 0, n + 1))
+    with pytest.raises(ValueError, match=r"hp_rollout_waves: env->state_dev\[1\] is null"):
+        waves(env.reset_streams.h, desc(null=1))
+    with pytest.raises(ValueError, match=r"hp_env_reset: env->state_dev\[2\] is null"):
+        reset(env.reset_streams.h, desc(null=2), n)
+    with pytest.raises(ValueError, match=r"hp_rollout_waves: null argument"):
+        waves(None, desc())
+    with pytest.raises(ValueError, match=r"hp_env_reset: null argument"):
+        reset(None, desc(), n)
+    with pytest.raises(ValueError, match=r"hp_rollout_waves: env->kind 7 is not an environment kind"):
+        waves(env.reset_streams.h, desc(kind=7))
+    with pytest.raises(ValueError, match=r"hp_env_reset: env->kind 7 is not an environment kind"):
+        reset(env.reset_streams.h, desc(kind=7), n)
+    other = _lib.Context(0)
+    foreign = DeviceRandomStreams(n, base_seed=1, ctx=other)
+    with pytest.raises(ValueError, match=r"hp_rollout_waves: handles belong to different contexts"):
+        waves(foreign.h, desc())
+    with pytest.raises(ValueError, match=r"hp_env_reset: handles belong to different contexts"):
+        reset(foreign.h, desc(), n)
+    after = (env.reset_streams.get_arrays(), narrow.get_arrays(), B.explore_streams.get_arrays(), env.pos, env.goal)
+    for x, y in zip(state[:3], after[:3]):
+        assert all(np.array_equal(bits(u), bits(v)) for u, v in zip(x, y))                                  # nothing ran
+    assert torch.equal(state[3], after[3]) and torch.equal(state[4], after[4])
+    waves(env.reset_streams.h, desc())                                                                     # ... and a good call does
+    assert not torch.equal(state[4], env.goal)
+
+    # the training state, both directions and the count
+    A = agent_on(n, T, reset=False)
+    with_streams, without = B.save_training_state(tmp_path / "b.npz"), A.save_training_state(tmp_path / "a.npz")
+    with pytest.raises(ts.StateError, match=r"the state carries 4 per-environment reset streams .*call vec_env.enable_device_reset"):
+        A.load_training_state(with_streams)
+    with pytest.raises(ts.StateError, match=r"the agent's environment is reset on the device, but the state was saved without reset streams"):
+        B.load_training_state(without)
+    wide = agent_on(n + 1, T, reset=True)
+    wide.explore_streams = B.explore_streams                     # (the exploration streams' own count check comes first)
+    with pytest.raises(ts.StateError, match=r"array 'reset_stream_keys' holds 4 streams, the agent has 5 environments"):
+        wide.load_training_state(with_streams)
+    A.load_training_state(without)                               # a state without the field loads as before
