@@ -391,22 +391,30 @@ int hp_rollout_step_streams(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_no
  * width <= 48, at most 4 action components: hp_agent_engine reports 8); any other agent is refused and keeps the per-step calls.
  * HP_ERR_INVALID names the field for: an unknown kind, dimensions of block / agent / normalizers / environment that differ, a
  * wave wider than the stream array, explore != 0 without streams, an agent of another shape.
- * Adding an environment kind is a build-time change in two places: one struct in csrc/env_device.h (load, observe, step,
- * is_success, store over the arrays of hp_env_desc, with its dimensions as constants) and one case in the dispatch of
- * hp_rollout_episodes (csrc/rollout.hip) next to HP_ENV_POINT_MASS; the kernel is a template over that struct. */
+ * Adding an environment kind is a build-time change: one struct in csrc/env_device.h (load, observe, step, is_success, store
+ * over the arrays of hp_env_desc, with its dimensions as constants), one case in the dispatches of csrc/rollout.hip next to
+ * HP_ENV_POINT_MASS, and a translation unit that instantiates the kernel templates (csrc/rollout_episodes.h) for that struct.
+ * HP_ENV_PUSH_BLOCK is a kinematic planar push: the achieved goal is a block that moves only while the gripper touches it, and
+ * its reset redraws block and target until they are min_separation apart (at most 100 attempts: csrc/env_device.h). */
 enum { HP_ENV_POINT_MASS = 1 };
+enum { HP_ENV_PUSH_BLOCK = 2 };
 typedef struct {
     int32_t kind, reserved;
-    double params[8];         /* point mass: [0] step_scale, [1] distance_threshold */
-    double *state_dev[4];     /* point mass: [0] pos [n][3], [1] vel [n][3], [2] goal [n][3]; read at entry, written at exit */
+    double params[8];         /* point mass: [0] step_scale, [1] distance_threshold
+                               * push block: [0] step_scale, [1] distance_threshold, [2] half_width, [3] z_touch, [4] min_separation,
+                               *             [5] table_z, [6] [7] gripper start x, y */
+    double *state_dev[4];     /* read at entry, written at exit; a kind's unused slots are ignored
+                               * point mass: [0] pos [n][3], [1] vel [n][3], [2] goal [n][3]
+                               * push block: [0] gripper [n][3], [1] block [n][3], [2] goal [n][3], [3] velocities [n][6] (gripper, block) */
 } hp_env_desc;
 int hp_rollout_episodes(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, hp_rng_streams *streams,
                         const hp_env_desc *env, int32_t explore, double noise_eps, double random_eps, double qn,
                         double clip_abs, float *success_dev);
 
 /* ---- environments reset on the device; all waves of a call in one launch ------------------------------------------------------
- * An environment kind may declare a reset (csrc/env_device.h): a fixed number of random_uniform(low, range) draws out of the
- * environment's own reset stream -- stream i of an hp_rng_streams, np.random.RandomState's legacy state like the exploration
+ * An environment kind may declare a reset (csrc/env_device.h): a fixed number of random_uniform(low, range) draws -- or, for a
+ * kind whose host reset is a rejection loop (push block), that many draws per attempt, repeated until the attempt is accepted
+ * or the kind's attempts are spent -- out of the environment's own reset stream -- stream i of an hp_rng_streams, np.random.RandomState's legacy state like the exploration
  * streams -- and the fresh state built from them.  Point mass: six draws of uniform(0, 0.5), pos = u[0:3], goal = u[3:6], vel = 0,
  * the twelve words of the host twin's two uniform(0, 0.5, 3) calls.
  * hp_env_reset resets environments 0 .. rows-1 of the arrays of `env` (one wave per environment: load stream i, draw, write the

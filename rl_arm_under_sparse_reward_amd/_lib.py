@@ -56,6 +56,7 @@ class EnvDesc(C.Structure):
 
 
 ENV_POINT_MASS = 1
+ENV_PUSH_BLOCK = 2      # HP_ENV_PUSH_BLOCK
 ROLLOUT_MAX_LAUNCH_TIMESTEPS = 4096   # HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS: what one launch of hp_rollout_waves holds at most
 
 

@@ -8,18 +8,32 @@
 //     step(action_f32)                         advance by one timestep with the float32 action [ACT] the policy side produced
 //     is_success()                             the `is_success` flag of the state just reached
 //     store(desc, i)                           write the state back (every array: a reset on the device changes the goal too)
+//     static constexpr int STATE_ARRAYS         how many arrays of hp_env_desc.state_dev the kind uses (the null check on the host)
 // A kind that can be reset on the device (hp_env_reset, the wave loop of k_rollout_episodes) also declares
-//     static constexpr int RESET_DRAWS         uniform draws of one reset, taken from the environment's own reset stream
+//     static constexpr int RESET_DRAWS         uniform draws of one reset ATTEMPT, taken from the environment's own reset stream
 //     reset_bounds(k, low, range)              draw k = random_uniform(low, range) = low + range * next_double, in draw order
+//                                              (range is the float64 difference high - low, as numpy computes it, never a literal)
 //     reset(u)                                 the fresh state out of those RESET_DRAWS values
 // and RESET_DRAWS = 0 says the kind has no device reset.  The row's wave draws (env_reset_draw below, mw_draw_uniform) and hands the
 // values to lane 0 through LDS.
+// A reset with a data-dependent number of draws (a rejection loop on the host: redraw until the state is acceptable) declares
+//     static constexpr int RESET_ATTEMPTS      attempts at most (default 1: absent, the reset is one fixed set of draws)
+//     bool reset(u)                            builds the state of this attempt and returns whether it is accepted; the state of the
+//                                              last attempt is kept, accepted or not
+// The row's wave then repeats env_reset_draw + reset until an attempt is accepted or RESET_ATTEMPTS are spent (env_reset_run below):
+// lane 0 writes the verdict to one int of the wave's own LDS, every lane reads it behind mw_sync(), so the exit of the loop is
+// wave-uniform and the cooperative draws stay under wave-uniform control flow.  The stream is committed once, after the loop.  With
+// RESET_ATTEMPTS = 1 there is no loop and no verdict: the code is the fixed reset's.
 // Every float64 operation whose rounding the host twin of the environment fixes is an explicit IEEE operation (__dmul_rn, ...), so
 // that no contraction can change a bit relative to the elementwise torch / numpy ops of that twin.
-// Adding a kind: a struct here, an HP_ENV_* constant in rlarm_hip.h and a case in the dispatches of hp_rollout_episodes / hp_rollout_waves
-// and hp_env_reset (rollout.hip).
+// Adding a kind: a struct here, an HP_ENV_* constant in rlarm_hip.h, a case in env_state_arrays and in the dispatches of
+// hp_rollout_episodes / hp_rollout_waves and hp_env_reset (rollout.hip) -- and, so that rollout.hip keeps compiling one instantiation
+// of each kernel, a translation unit of its own that instantiates k_rollout_episodes / k_env_reset (rollout_episodes.h) for the kind
+// and exports the two launchers those dispatches call (env_push_block.hip is the model).
 #pragma once
 #include "internal.h"
+#include <type_traits>
+
 #include "mt19937_wave.h"
 
 // device_env.PointMassVecEnv (the tensor twin of synthetic.PointMassGoalEnv), operation for operation:
@@ -30,7 +44,7 @@
 //     words of one draw of six
 // params: [0] step_scale, [1] distance_threshold;  state_dev: [0] pos [n][3], [1] vel [n][3], [2] goal [n][3]
 struct PointMassEnvDev {
-    static constexpr int OBS = 27, GOAL = 3, ACT = 4, RESET_DRAWS = 6;
+    static constexpr int OBS = 27, GOAL = 3, ACT = 4, RESET_DRAWS = 6, STATE_ARRAYS = 3;
     double pos[3], vel[3], goal[3], step_scale, threshold;
 
     static __device__ __forceinline__ void reset_bounds(int, double &low, double &range) {
@@ -93,6 +107,116 @@ struct PointMassEnvDev {
     }
 };
 
+// device_env.PushBlockVecEnv (the tensor twin of synthetic.PushBlockGoalEnv), operation for operation: a kinematic planar push.
+// The achieved goal is a block (a square of half width r resting on the table) that moves only while the gripper touches it:
+//     a = clamp(float64(action), -0.5, 0.5), a[3] ignored;  new = clamp(grip + step_scale * a[0:3], lo, hi);  gvel = new - grip
+//     dx = blk.x - grip.x, dy = blk.y - grip.y;  contact = grip.z < z_touch and |dx| < r and |dy| < r
+//     contact: px = r - |dx|, py = r - |dy|;  px <= py ? blk.x = grip.x + (dx >= 0 ? r : -r) : blk.y = grip.y + (dy >= 0 ? r : -r),
+//              then blk.x, blk.y clamped into the workspace;  bvel = blk_new - blk_old (zero without contact)
+//     obs = zeros(27) with [0:3] = grip, [6:9] = gvel, [12:15] = blk, [18:21] = blk - grip, [21:24] = bvel;  ag = blk;  g = goal
+//     is_success: the point mass's, between block and goal
+//     reset: at most 100 attempts of bx = uniform(0.15, 0.35), by = uniform(0.2, 0.5), gx = uniform(0.0, 0.35), gy = uniform(0.2, 0.5),
+//     accepted when sqrt(ddx ddx + ddy ddy) >= min_separation (bmirobot_env_push_F.py:117-132); the last attempt is kept
+// No division and no square root inside step: adds, subtracts, multiplies, compares and clamps only.
+// params: [0] step_scale, [1] distance_threshold, [2] half_width r, [3] z_touch, [4] min_separation, [5] table_z, [6], [7] gripper
+// start x, y;  state_dev: [0] grip [n][3], [1] blk [n][3], [2] goal [n][3], [3] velocities [n][6] (gripper, then block)
+struct PushBlockEnvDev {
+    static constexpr int OBS = 27, GOAL = 3, ACT = 4, RESET_DRAWS = 4, RESET_ATTEMPTS = 100, STATE_ARRAYS = 4;
+    // the workspace: x, y of gripper and block; the gripper's z runs from the table to Z_HI and starts at START_Z
+    static constexpr double X_LO = 0.0, X_HI = 0.5, Y_LO = 0.0, Y_HI = 0.7, Z_HI = 0.5, START_Z = 0.3;
+    double grip[3], blk[3], goal[3], gvel[3], bvel[3];
+    double step_scale, threshold, r, z_touch, min_sep, table_z, start_x, start_y;
+
+    static __device__ __forceinline__ void reset_bounds(int k, double &low, double &range) {
+        // numpy: low + (high - low) * next_double, the difference in float64 (0.35 - 0.15 is not 0.2)
+        constexpr double lo[4] = {0.15, 0.2, 0.0, 0.2}, hi[4] = {0.35, 0.5, 0.35, 0.5};
+        low = lo[k];
+        range = hi[k] - lo[k];
+    }
+    __device__ __forceinline__ bool reset(const double *u) {
+        const double ddx = __dsub_rn(u[0], u[2]), ddy = __dsub_rn(u[1], u[3]);
+        const double d = __dsqrt_rn(__dadd_rn(__dmul_rn(ddx, ddx), __dmul_rn(ddy, ddy)));
+        blk[0] = u[0]; blk[1] = u[1]; blk[2] = table_z;
+        goal[0] = u[2]; goal[1] = u[3]; goal[2] = table_z;
+        grip[0] = start_x; grip[1] = start_y; grip[2] = START_Z;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gvel[c] = bvel[c] = 0.0;
+        return d >= min_sep;
+    }
+
+    __device__ __forceinline__ void load(const hp_env_desc &d, long long i) {
+        step_scale = d.params[0]; threshold = d.params[1]; r = d.params[2]; z_touch = d.params[3];
+        min_sep = d.params[4]; table_z = d.params[5]; start_x = d.params[6]; start_y = d.params[7];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            grip[c] = d.state_dev[0][3 * i + c];
+            blk[c] = d.state_dev[1][3 * i + c];
+            goal[c] = d.state_dev[2][3 * i + c];
+            gvel[c] = d.state_dev[3][6 * i + c];
+            bvel[c] = d.state_dev[3][6 * i + 3 + c];
+        }
+    }
+    __device__ __forceinline__ void observe(double *obs, double *ag, double *g) const {
+#pragma unroll
+        for (int c = 0; c < OBS; ++c) obs[c] = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            obs[c] = grip[c];
+            obs[6 + c] = gvel[c];
+            obs[12 + c] = blk[c];
+            obs[18 + c] = __dsub_rn(blk[c], grip[c]);
+            obs[21 + c] = bvel[c];
+            ag[c] = blk[c];
+            g[c] = goal[c];
+        }
+    }
+    __device__ __forceinline__ void step(const float *action) {
+        const double lo[3] = {X_LO, Y_LO, table_z}, hi[3] = {X_HI, Y_HI, Z_HI};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double a = fmin(fmax((double)action[c], -0.5), 0.5);
+            const double scaled = __dmul_rn(step_scale, a);
+            const double moved = fmin(fmax(__dadd_rn(grip[c], scaled), lo[c]), hi[c]);
+            gvel[c] = __dsub_rn(moved, grip[c]);
+            grip[c] = moved;
+        }
+        const double dx = __dsub_rn(blk[0], grip[0]), dy = __dsub_rn(blk[1], grip[1]);
+        const double adx = fabs(dx), ady = fabs(dy);
+        const double ox = blk[0], oy = blk[1];
+        if (grip[2] < z_touch && adx < r && ady < r) {
+            const double px = __dsub_rn(r, adx), py = __dsub_rn(r, ady);   // how deep the gripper is inside the block, per axis
+            if (px <= py) blk[0] = __dadd_rn(grip[0], dx >= 0.0 ? r : -r);  // out along the axis of least penetration
+            else blk[1] = __dadd_rn(grip[1], dy >= 0.0 ? r : -r);
+            blk[0] = fmin(fmax(blk[0], X_LO), X_HI);
+            blk[1] = fmin(fmax(blk[1], Y_LO), Y_HI);
+        }
+        bvel[0] = __dsub_rn(blk[0], ox);
+        bvel[1] = __dsub_rn(blk[1], oy);
+        bvel[2] = 0.0;                       // blk.z stays table_z
+    }
+    __device__ __forceinline__ bool is_success() const {
+        const double dx = __dsub_rn(blk[0], goal[0]), dy = __dsub_rn(blk[1], goal[1]), dz = __dsub_rn(blk[2], goal[2]);
+        const double s = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+        return __dsqrt_rn(s) < threshold;
+    }
+    __device__ __forceinline__ void store(const hp_env_desc &d, long long i) const {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            d.state_dev[0][3 * i + c] = grip[c];
+            d.state_dev[1][3 * i + c] = blk[c];
+            d.state_dev[2][3 * i + c] = goal[c];
+            d.state_dev[3][6 * i + c] = gvel[c];
+            d.state_dev[3][6 * i + 3 + c] = bvel[c];
+        }
+    }
+};
+
+// RESET_ATTEMPTS of a kind, 1 where it declares none
+template <class Env, class = void>
+struct EnvResetAttempts { static constexpr int value = 1; };
+template <class Env>
+struct EnvResetAttempts<Env, std::void_t<decltype(Env::RESET_ATTEMPTS)>> { static constexpr int value = Env::RESET_ATTEMPTS; };
+
 // The draws of one reset out of the stream loaded into w, by the row's wave: consecutive draws with the same bounds are one
 // mw_draw_uniform call (the point mass: one call of six).  u: RESET_DRAWS doubles of LDS of this wave's own, readable by every
 // lane on return.
@@ -112,4 +236,25 @@ __device__ __forceinline__ void env_reset_draw(MwState &w, double *u) {
         k += n;
     }
     mw_sync();
+}
+
+// One whole reset of environment e out of the stream loaded into w, by the row's wave (the caller commits the stream afterwards,
+// once): the draws of an attempt, lane 0 builds the state -- and, for a kind with RESET_ATTEMPTS > 1, says through *verdict
+// whether the attempt stands; the wave goes round again until one does or the attempts are spent.  e: lane 0's (LDS, or its own
+// registers); u: RESET_DRAWS doubles and verdict: one int, both LDS of this wave's own.
+template <class Env>
+__device__ __forceinline__ void env_reset_run(MwState &w, Env &e, double *u, int *verdict) {
+    if constexpr (EnvResetAttempts<Env>::value == 1) {
+        env_reset_draw<Env>(w, u);
+        if (mw_lane() == 0) e.reset(u);
+    } else {
+        for (int attempt = 0; attempt < EnvResetAttempts<Env>::value; ++attempt) {
+            env_reset_draw<Env>(w, u);
+            if (mw_lane() == 0) *verdict = e.reset(u) ? 1 : 0;
+            mw_sync();
+            const int accepted = __builtin_amdgcn_readfirstlane(*verdict);   // the same int for every lane: a scalar branch
+            mw_sync();                       // every lane has read u and the verdict before the next attempt rewrites them
+            if (accepted) break;
+        }
+    }
 }

@@ -31,8 +31,6 @@
 #pragma clang diagnostic ignored "-Wundefined-inline"   // agent_device.h declares the 32-row engine's fragment map, which no code here calls
 #include "agent_device.h"
 #pragma clang diagnostic pop
-#include "env_device.h"
-#include "mt19937_wave.h"
 
 // the 4-row policy slab's device functions (no kernel of slab8.h is compiled here)
 #define S8_DEVICE_ONLY
@@ -43,7 +41,7 @@
 #undef S8_NS
 #undef S8_DEVICE_ONLY
 
-#define RO_MAX_ACT 16
+#include "rollout_episodes.h"   // ExploreArgs, ro_explore_row, and the kernel templates of a whole wave / of all waves of a call
 
 struct hp_rollout {
     hp_ctx *ctx = nullptr;
@@ -54,13 +52,6 @@ struct hp_rollout {
     int64_t launch_cap = HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS;   // timesteps (waves x T) one launch of hp_rollout_waves may hold
     double *block = nullptr;
     int64_t o_ag = 0, o_g = 0, o_act = 0, elems = 0;   // offsets in float64 elements (feeder._Layout)
-};
-
-// what turns a policy output into an action: the constants of ddpg_agent._select_actions (:174-184) and of the +-0.15 clip (:118-119)
-struct ExploreArgs {
-    int ad;
-    double noise_scale;            // noise_eps * action_max (the reference's float64 product)
-    double amax, random_eps, qn, clip_abs;
 };
 
 struct RolloutStepArgs {
@@ -89,43 +80,6 @@ __device__ __forceinline__ void ro_record(const RolloutStepArgs &A, long long e0
             A.b_g[(i * A.T + A.t) * A.gd + c] = A.g[k];
         }
     }
-}
-
-// ddpg_agent._select_actions (:174-184) for one row, out of the stream loaded into w: randn(act), uniform(act), binomial(1).
-// pi: the row's policy outputs in, its actions out (float32 [ad]); act: its place in the block (float64 [ad]); zs: ad doubles of
-// LDS of this wave's own.  One wave, wave-local barriers (mt19937_wave.h).  Shared by the single-stream walk, the per-environment
-// form and the whole-episode kernel, so one stream gives the same bits in all three.
-__device__ __forceinline__ void ro_explore_row(const ExploreArgs &A, MwState &w, double *zs, float *pi, double *act) {
-    const int lane = mw_lane(), ad = A.ad;
-    const float amax = (float)A.amax, clipf = (float)A.clip_abs;
-    // :177 action += noise_eps * max_action * randn(act): float32 array += float64 array, rounded once
-    mw_draw_normal(w, ad, [&](long long k, double z) { zs[k] = z; });
-    mw_sync();
-    float a = 0.f;
-    if (lane < ad) {
-        a = pi[lane];
-        a = (float)__dadd_rn((double)a, __dmul_rn(A.noise_scale, zs[lane]));
-        a = fminf(fmaxf(a, -amax), amax);                                          // :178 np.clip in float32
-    }
-    mw_sync();   // zs is rewritten by the next normals
-    double ra = 0.0;
-    mw_draw_uniform(w, -A.amax, __dsub_rn(A.amax, -A.amax), ad, [&](int, double u) { ra = u; });   // :179-180
-    const int b = mw_draw_binomial1(w, A.random_eps, A.qn);                        // :182
-    if (lane < ad) {
-        // :182 action += binomial * (random_actions - action), float64 arithmetic rounded to float32 once
-        a = (float)__dadd_rn((double)a, __dmul_rn((double)b, __dsub_rn(ra, (double)a)));
-        if (A.clip_abs > 0) a = fminf(fmaxf(a, -clipf), clipf);                    // :118-119, float32
-        pi[lane] = a;
-        act[lane] = (double)a;
-    }
-}
-
-// ddpg_agent.collect_episodes with explore=False for one element: action = pi.astype(float64), clipped in float64 from epoch 100 on
-__device__ __forceinline__ void ro_plain_element(const ExploreArgs &A, float *pi, double *act) {
-    double a = (double)*pi;
-    if (A.clip_abs > 0) a = fmin(fmax(a, -A.clip_abs), A.clip_abs);
-    *act = a;
-    *pi = (float)a;
 }
 
 __global__ __launch_bounds__(MW_THREADS) void k_rollout_step(const RolloutStepArgs A) {
@@ -169,159 +123,6 @@ __global__ __launch_bounds__(MW_THREADS) void k_rollout_step_streams(const Rollo
     MwState w(st, ring);
     ro_explore_row(A.x, w, zs, A.pi + (long long)i * A.ad, A.b_act + ((long long)i * A.T + A.t) * A.ad);
     w.store(st);
-}
-
-// ---- whole episodes in one launch ------------------------------------------------------------------------------------------
-struct EpisodesArgs {
-    PolicyArgs P;                  // the policy call of hp_agent_act_dev (obs / g / x / actions unused: the rows come from LDS)
-    double *b_obs, *b_ag, *b_g, *b_act;   // block arrays, already offset to episode `first`
-    MtState *st;                   // exploration stream of environment 0 (explore != 0)
-    MtState *reset_st;             // reset stream of environment 0; nullptr: the environments were reset by the caller
-    int rows, T, explore;          // rows: episodes of the launch = waves of n_envs environments, the last one possibly partial
-    int n_envs, waves;             // (hp_rollout_episodes: n_envs = rows, one wave)
-    ExploreArgs x;
-    hp_env_desc env;
-    float *success;                // [rows]
-};
-
-// what a workgroup of k_rollout_episodes keeps beside the policy slab: one environment, one row of observations, one action row
-// and -- exploring -- one MT19937 ring per row
-template <class Env>
-struct EpisodesLds {
-    Env env[4];
-    double obs[4][Env::OBS], ag[4][Env::GOAL], g[4][Env::GOAL];
-    double zs[4][RO_MAX_ACT];
-    float pi[4][RO_MAX_ACT];
-    uint32_t ring[4][4][MT_N];
-};
-
-// LDS: 111552 bytes of policy slab + 39936 of rings + the rows: one workgroup per CU, which is what the policy slab's weight ring
-// asks for anyway.  Wave r < 4 owns row r outside the policy slab: its lane 0 steps the environment, its lanes j < act_dim hold
-// action j (s8_policy_slab's emit), and the whole wave walks the row's stream.  Barriers per timestep: one __syncthreads() behind
-// observe, the policy slab's own, none in the draws (wave-local: the rejection loops of different rows need not agree on a trip count).
-//
-// The wave loop.  Workgroup b owns ENVIRONMENTS 4b .. 4b+3 for the whole launch (A.P.rows = the environments that take part at
-// all); environment i collects episode w * n_envs + i in wave w if that is < rows, and sits the wave out otherwise (only in the
-// last wave, only a suffix of the environments: the rows of a slab that take part are its first `nrows`).  Whether a row takes part
-// is wave-uniform, everything it does between two episodes is wave-local, and a row that sits out still reaches every workgroup
-// barrier of the timestep loop.  With reset streams a row's wave, before each of its episodes: commits the exploration stream out
-// of its ring (mt_commit's rule: numpy's lazy form), loads the environment's reset stream INTO THE SAME RING (a second ring per
-// row does not fit the 160 KiB four times), draws the reset, commits that stream, and loads the exploration stream again -- 2.5 KB
-// read per stream and episode, and a key written only when the walk left its block.  The weight ring has drained when s8_trunk
-// returns and the next s8_ring_prologue is issued after all of this, so its counted waits stay exact.  One wave and no reset stream
-// is hp_rollout_episodes' launch, unchanged.
-template <class Env>
-__global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_rollout_episodes(const EpisodesArgs A) {
-    __shared__ s8ro::PolicyLds L;
-    __shared__ EpisodesLds<Env> E;
-    constexpr int OD = Env::OBS, GD = Env::GOAL, AD = Env::ACT;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const long long row0 = (long long)blockIdx.x * 4;
-    const int nenv = A.P.rows - row0 < 4 ? (int)(A.P.rows - row0) : 4;   // environments of this slab
-    const bool mine = wave < nenv;               // this wave owns environment row0 + wave
-    const long long env = row0 + wave;
-    const int T = A.T;
-    MwState w;
-    if (mine) {
-        if (lane == 0) E.env[wave].load(A.env, env);
-        if (A.explore && !A.reset_st) w.load(A.st + env, E.ring[wave]);
-    }
-    for (int wv = 0; wv < A.waves; ++wv) {
-        const long long ep0 = (long long)wv * A.n_envs + row0;               // episode of the slab's row 0 in this wave
-        const int nrows = A.rows - ep0 < nenv ? (A.rows - ep0 < 0 ? 0 : (int)(A.rows - ep0)) : nenv;
-        const bool part = wave < nrows;          // this wave's environment collects episode ep0 + wave
-        const long long row = ep0 + wave;
-        if constexpr (Env::RESET_DRAWS > 0) {
-            if (A.reset_st && part) {
-                // what the exploration stream's commit writes from lane 0 stays in registers across the detour, so the reload
-                // depends on no other lane's global store: each lane reads back only the key words it wrote itself
-                const bool resume = A.explore && wv > 0;
-                long long xblock = 0;
-                int xpos = 0, xhas = 0;
-                double xgauss = 0.0;
-                if (resume) {
-                    mt_final_block(w.g.cursor, xblock, xpos);
-                    xhas = w.has_gauss;
-                    xgauss = w.gauss;
-                    w.store(A.st + env);
-                    mw_sync();                   // the commit has read the ring before the next stream's key overwrites it
-                }
-                w.load(A.reset_st + env, E.ring[wave]);
-                env_reset_draw<Env>(w, E.zs[wave]);
-                w.store(A.reset_st + env);
-                if (lane == 0) E.env[wave].reset(E.zs[wave]);
-                mw_sync();
-                if (A.explore) w.load(A.st + env, E.ring[wave]);
-                if (resume) {
-                    w.g.cursor = xpos;
-                    w.has_gauss = xhas;
-                    w.gauss = xgauss;
-                }
-            }
-        }
-        // record the rows observed into E at timestep t (t == T: the closing record, no goal row)
-        auto record = [&](int t) {
-            const int per = OD + GD + (t < T ? GD : 0);
-            for (int e = tid; e < nrows * per; e += S8_THREADS) {
-                const int r = e / per, c = e - r * per;
-                const long long i = ep0 + r;
-                if (c < OD) A.b_obs[(i * (T + 1) + t) * OD + c] = E.obs[r][c];
-                else if (c < OD + GD) A.b_ag[(i * (T + 1) + t) * GD + (c - OD)] = E.ag[r][c - OD];
-                else A.b_g[(i * T + t) * GD + (c - OD - GD)] = E.g[r][c - OD - GD];
-            }
-        };
-        for (int t = 0; t < T; ++t) {
-            if (part && lane == 0) E.env[wave].observe(E.obs[wave], E.ag[wave], E.g[wave]);
-            __syncthreads();
-            record(t);
-            s8ro::s8_policy_slab(A.P, L, (size_t)row0,
-                [&](int r, int c) -> float {
-                    if (r >= nrows) return 0.f;  // an environment that sits this wave out
-                    if (c < OD) return s8ro::s8_policy_input(E.obs[r][c], A.P.clip_obs, A.P.onz->mean[c], A.P.onz->std[c], A.P.clip_o);
-                    const int j = c - OD;
-                    return s8ro::s8_policy_input(E.g[r][j], A.P.clip_obs, A.P.gnz->mean[j], A.P.gnz->std[j], A.P.clip_g);
-                },
-                [&](int r, int j, float a) { E.pi[r][j] = a; });
-            if (part) {
-                mw_sync();
-                double *act = A.b_act + (row * T + t) * AD;
-                if (A.explore) ro_explore_row(A.x, w, E.zs[wave], E.pi[wave], act);
-                else if (lane < AD) ro_plain_element(A.x, &E.pi[wave][lane], act + lane);
-                mw_sync();
-                if (lane == 0) E.env[wave].step(E.pi[wave]);
-            }
-        }
-        if (part && lane == 0) E.env[wave].observe(E.obs[wave], E.ag[wave], E.g[wave]);
-        __syncthreads();
-        record(T);
-        if (part && lane == 0) A.success[row] = E.env[wave].is_success() ? 1.f : 0.f;
-        if (wv + 1 < A.waves) __syncthreads();   // record(T) has read the rows the next wave's first observe rewrites
-    }
-    if (mine) {
-        if (lane == 0) E.env[wave].store(A.env, env);
-        if (A.explore) w.store(A.st + env);
-    }
-}
-
-// A reset as a launch of its own (hp_env_reset): workgroup i = one wave = environment i, like k_rollout_step_streams -- load reset
-// stream i, draw, commit it by mt_commit's rule, and lane 0 writes the fresh state.
-template <class Env>
-__global__ __launch_bounds__(MW_THREADS) void k_env_reset(const hp_env_desc env, MtState *reset_st) {
-    __shared__ uint32_t ring[4][MT_N];
-    __shared__ double u[Env::RESET_DRAWS > 0 ? Env::RESET_DRAWS : 1];
-    if constexpr (Env::RESET_DRAWS > 0) {
-        const long long i = blockIdx.x;
-        MtState *st = reset_st + i;
-        MwState w(st, ring);
-        env_reset_draw<Env>(w, u);
-        w.store(st);
-        if (mw_lane() == 0) {
-            Env e;
-            e.load(env, i);      // the parameters; the state it reads is replaced
-            e.reset(u);
-            e.store(env, i);
-        }
-    }
 }
 
 static int rollout_launch(hp_rollout *ro, RolloutStepArgs &A, int t, bool per_env_streams = false) {
@@ -368,18 +169,13 @@ static int rollout_step(const char *entry, hp_rollout *ro, hp_agent *a, hp_norm 
     return rollout_launch(ro, A, t, per_env_streams && explore);   // explore == 0 touches no stream: the single-stream kernel's path
 }
 
-// The launches of one environment kind; dimensions of the kind against the block's first.  A (hp_rollout_episodes, or
-// hp_rollout_waves with A.reset_st and A.n_envs set) describes the whole call: episodes [first, first + rows) of the block; it is
-// issued as consecutive launches of at most ro->launch_cap timesteps (whole waves, at least one), each a call of its own on the
-// episodes, flags and final states the one before it left.
-template <class Env>
-static int rollout_episodes_launch(const char *entry, hp_rollout *ro, EpisodesArgs A, int32_t *launches) {
-    HP_REQUIRE(ro->od == Env::OBS && ro->gd == Env::GOAL && ro->ad == Env::ACT, HP_ERR_INVALID,
-               "%s: env->kind %d has dimensions %d / %d / %d, the block has %d / %d / %d", entry, (int)A.env.kind, Env::OBS,
-               Env::GOAL, Env::ACT, ro->od, ro->gd, ro->ad);
-    HP_REQUIRE(!A.reset_st || Env::RESET_DRAWS > 0, HP_ERR_INVALID, "%s: env->kind %d has no reset on the device", entry, (int)A.env.kind);
-    static_assert(Env::ACT <= 4 && Env::ACT <= RO_MAX_ACT && Env::OBS + Env::GOAL <= S8_LDX, "an environment of the policy slab's shape");
-    static_assert(Env::RESET_DRAWS <= RO_MAX_ACT, "the reset's values pass through the row's zs");
+// A call of hp_rollout_episodes / hp_rollout_waves as launches.  A (hp_rollout_episodes, or hp_rollout_waves with A.reset_st and
+// A.n_envs set) describes the whole call: episodes [first, first + rows) of the block; it is issued as consecutive launches of at
+// most ro->launch_cap timesteps (whole waves, at least one), each a call of its own on the episodes, flags and final states the one
+// before it left.  launch(blocks, L) issues one of them on ro->ctx->stream with the kernel of the environment's kind and returns
+// its hipError_t: this loop is the same for every kind.
+template <class Launch>
+static int rollout_split_launches(hp_rollout *ro, const EpisodesArgs &A, int32_t *launches, Launch launch) {
     const int64_t total = A.rows, n_envs = A.n_envs;
     int64_t per = ro->launch_cap / (ro->T > 0 ? ro->T : 1);   // waves per launch
     if (per < 1) per = 1;
@@ -395,20 +191,39 @@ static int rollout_episodes_launch(const char *entry, hp_rollout *ro, EpisodesAr
         L.success += done;
         L.rows = (int)rows; L.waves = (int)waves;
         L.P.rows = (int)live;              // the environments that take part in the launch at all
-        hipLaunchKernelGGL(k_rollout_episodes<Env>, dim3((unsigned)((live + 3) / 4)), dim3(S8_THREADS), 0, ro->ctx->stream, L);
-        HP_CHECK_HIP(hipGetLastError());
+        HP_CHECK_HIP(launch((unsigned)((live + 3) / 4), L));
         done += rows;
     }
     if (launches) *launches = n;
     return HP_OK;
 }
 
+// What a kind must be for these kernels, and its dimensions against the block's, before any launch
 template <class Env>
-static int env_reset_launch(hp_ctx *ctx, const hp_env_desc &env, MtState *st, int64_t rows) {
-    HP_REQUIRE(Env::RESET_DRAWS > 0, HP_ERR_INVALID, "hp_env_reset: env->kind %d has no reset on the device", (int)env.kind);
-    hipLaunchKernelGGL(k_env_reset<Env>, dim3((unsigned)rows), dim3(MW_THREADS), 0, ctx->stream, env, st);
-    HP_CHECK_HIP(hipGetLastError());
+static int rollout_episodes_check(const char *entry, hp_rollout *ro, const EpisodesArgs &A) {
+    HP_REQUIRE(ro->od == Env::OBS && ro->gd == Env::GOAL && ro->ad == Env::ACT, HP_ERR_INVALID,
+               "%s: env->kind %d has dimensions %d / %d / %d, the block has %d / %d / %d", entry, (int)A.env.kind, Env::OBS,
+               Env::GOAL, Env::ACT, ro->od, ro->gd, ro->ad);
+    HP_REQUIRE(!A.reset_st || Env::RESET_DRAWS > 0, HP_ERR_INVALID, "%s: env->kind %d has no reset on the device", entry, (int)A.env.kind);
+    static_assert(Env::ACT <= 4 && Env::ACT <= RO_MAX_ACT && Env::OBS + Env::GOAL <= S8_LDX, "an environment of the policy slab's shape");
+    static_assert(Env::RESET_DRAWS <= RO_MAX_ACT, "the reset's values pass through the row's zs");
+    static_assert(Env::STATE_ARRAYS >= 1 && Env::STATE_ARRAYS <= 4, "hp_env_desc has four state arrays");
     return HP_OK;
+}
+
+template <class Env>
+static int env_reset_check(int kind) {
+    HP_REQUIRE(Env::RESET_DRAWS > 0, HP_ERR_INVALID, "hp_env_reset: env->kind %d has no reset on the device", kind);
+    return HP_OK;
+}
+
+// state arrays of hp_env_desc a kind uses; 0: not an environment kind of this build
+static int env_state_arrays(int kind) {
+    switch (kind) {
+        case HP_ENV_POINT_MASS: return PointMassEnvDev::STATE_ARRAYS;
+        case HP_ENV_PUSH_BLOCK: return PushBlockEnvDev::STATE_ARRAYS;
+        default: return 0;
+    }
 }
 
 // what hp_rollout_episodes and hp_rollout_waves share: the checks on agent, normalizers, block and streams, and the arguments of the
@@ -419,7 +234,7 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx && (!streams || streams->ctx == ro->ctx) &&
                    (!reset_streams || reset_streams->ctx == ro->ctx),
                HP_ERR_INVALID, "%s: handles belong to different contexts", entry);
-    HP_REQUIRE(env->kind == HP_ENV_POINT_MASS, HP_ERR_INVALID, "%s: env->kind %d is not an environment kind of this build", entry,
+    HP_REQUIRE(env_state_arrays(env->kind) > 0, HP_ERR_INVALID, "%s: env->kind %d is not an environment kind of this build", entry,
                (int)env->kind);
     HP_REQUIRE(a->slab8 && a->H == 256 && a->ldx <= 48 && a->cfg.act_dim <= 4, HP_ERR_INVALID,
                "%s: the agent is not slab-shaped (hidden %d, padded input width %d, act_dim %d, engine %s): it keeps "
@@ -434,7 +249,7 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     HP_REQUIRE(!reset_streams || n_envs <= reset_streams->n, HP_ERR_INVALID,
                "%s: %lld environments, but the array holds %lld reset streams", entry, (long long)n_envs, (long long)reset_streams->n);
     HP_REQUIRE(!explore || (random_eps >= 0.0 && random_eps <= 1.0), HP_ERR_INVALID, "p < 0, p > 1 or p is NaN");
-    for (int k = 0; k < 3; ++k)
+    for (int k = 0; k < env_state_arrays(env->kind); ++k)
         HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "%s: env->state_dev[%d] is null", entry, k);
     EpisodesArgs A;
     memset(&A, 0, sizeof(A));
@@ -452,6 +267,7 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     A.reset_st = reset_streams ? reset_streams->d_state : nullptr;
     A.rows = (int)ro->rows; A.T = ro->T; A.explore = explore ? 1 : 0;
     A.n_envs = (int)n_envs;
+    A.waves = (int)((ro->rows + n_envs - 1) / n_envs);   // of the whole call; a launch holds at most launch_cap / T of them
     A.x.ad = ro->ad;
     A.x.amax = a->cfg.max_action;
     A.x.noise_scale = noise_eps * a->cfg.max_action;
@@ -459,7 +275,17 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     A.env = *env;
     A.success = success_dev;
     switch (env->kind) {   // one case per environment kind (env_device.h)
-        case HP_ENV_POINT_MASS: return rollout_episodes_launch<PointMassEnvDev>(entry, ro, A, launches);
+        case HP_ENV_POINT_MASS:
+            HP_TRY(rollout_episodes_check<PointMassEnvDev>(entry, ro, A));
+            return rollout_split_launches(ro, A, launches, [&](unsigned blocks, const EpisodesArgs &L) {
+                hipLaunchKernelGGL(k_rollout_episodes<PointMassEnvDev>, dim3(blocks), dim3(S8_THREADS), 0, ro->ctx->stream, L);
+                return hipGetLastError();
+            });
+        case HP_ENV_PUSH_BLOCK:
+            HP_TRY(rollout_episodes_check<PushBlockEnvDev>(entry, ro, A));
+            return rollout_split_launches(ro, A, launches, [&](unsigned blocks, const EpisodesArgs &L) {
+                return push_block_launch_episodes(ro->ctx->stream, blocks, L);
+            });
         default: break;
     }
     return HP_ERR_INVALID;
@@ -570,13 +396,22 @@ int hp_env_reset(hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *reset_stre
     HP_REQUIRE(reset_streams->ctx == ctx, HP_ERR_INVALID, "hp_env_reset: handles belong to different contexts");
     HP_REQUIRE(rows > 0 && rows <= reset_streams->n, HP_ERR_INVALID,
                "hp_env_reset: %lld environments, but the array holds %lld reset streams", (long long)rows, (long long)reset_streams->n);
-    for (int k = 0; k < 3; ++k)
+    HP_REQUIRE(env_state_arrays(env->kind) > 0, HP_ERR_INVALID, "hp_env_reset: env->kind %d is not an environment kind of this build",
+               (int)env->kind);
+    for (int k = 0; k < env_state_arrays(env->kind); ++k)
         HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "hp_env_reset: env->state_dev[%d] is null", k);
     switch (env->kind) {   // one case per environment kind (env_device.h)
-        case HP_ENV_POINT_MASS: return env_reset_launch<PointMassEnvDev>(ctx, *env, reset_streams->d_state, rows);
+        case HP_ENV_POINT_MASS:
+            HP_TRY(env_reset_check<PointMassEnvDev>(env->kind));
+            hipLaunchKernelGGL(k_env_reset<PointMassEnvDev>, dim3((unsigned)rows), dim3(MW_THREADS), 0, ctx->stream, *env, reset_streams->d_state);
+            HP_CHECK_HIP(hipGetLastError());
+            return HP_OK;
+        case HP_ENV_PUSH_BLOCK:
+            HP_TRY(env_reset_check<PushBlockEnvDev>(env->kind));
+            HP_CHECK_HIP(push_block_launch_reset(ctx->stream, *env, reset_streams->d_state, rows));
+            return HP_OK;
         default: break;
     }
-    hp_set_error("hp_env_reset: env->kind %d is not an environment kind of this build", (int)env->kind);
     return HP_ERR_INVALID;
 }
 

@@ -24,7 +24,10 @@ returns a `DeviceEpisodes` handle that `train_cycle` / `buffer.store_episode` co
 
 and a whole wave of its episodes is ONE launch (hp_rollout_episodes: every workgroup loops over the T timesteps of its four rows)
 whenever `fused_rollout_reason` finds nothing against it; `reset` stays on the host, `step` stays available, and after a fused
-wave the state tensors hold what T `step` calls would have left.  `NativePointMassVecEnv` is the first such environment.
+wave the state tensors hold what T `step` calls would have left.  `NativePointMassVecEnv` is the first such environment and
+`NativePushBlockVecEnv` the second: a kinematic planar push whose achieved goal is a block that moves only on contact, and whose
+reset is a rejection loop (a data-dependent number of draws).  `env.state_names` lists the attributes that hold the state tensors,
+in the order of `native_desc()['state']`.
 
 **Reset on the device** (opt-in: `env.enable_device_reset()`, `args.device_reset`).  The environment's reset generators move into
 one device stream per environment (`env.reset_streams`, a `random.DeviceRandomStreams` holding the very states of `env.rs`), and
@@ -35,7 +38,7 @@ few launches `_lib.ROLLOUT_MAX_LAUNCH_TIMESTEPS` dictates; `agent.rollout_launch
 Draw order with n environments: per timestep, for env i = 0 .. n-1: randn(action), uniform(action), binomial(1) -- the order of
 the host lockstep path (`collect_episodes` on a list of environments); with one environment it is the reference's own order.
 
-`PointMassVecEnv` is the tensor twin of `synthetic.PointMassGoalEnv`.
+`PointMassVecEnv` is the tensor twin of `synthetic.PointMassGoalEnv`, `PushBlockVecEnv` that of `synthetic.PushBlockGoalEnv`.
 """
 from __future__ import annotations
 
@@ -46,6 +49,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from .synthetic import (PUSH_RESET_ATTEMPTS, PUSH_RESET_BOUNDS, PUSH_START_Z, PUSH_X_HI, PUSH_X_LO, PUSH_Y_HI, PUSH_Y_LO,
+                        PUSH_Z_HI)
 
 
 def wave_layout(n_envs, T, obs, goal, act):
@@ -118,6 +123,7 @@ class PointMassVecEnv:
     device="cpu" too."""
 
     is_device_vec_env = True
+    state_names = ("pos", "vel", "goal")     # the attributes that hold the state tensors
 
     def __init__(self, n_envs, seed=0, device="cuda", max_timesteps=100, distance_threshold=0.05, reward_type='sparse',
                  step_scale=0.1):
@@ -188,21 +194,12 @@ class PointMassVecEnv:
         return observation, self.compute_reward(observation['achieved_goal'], self.goal, info), False, info
 
 
-class NativePointMassVecEnv(PointMassVecEnv):
-    """`PointMassVecEnv` whose dynamics the library also evaluates itself (PointMassEnvDev, csrc/env_device.h: the same float64
-    operations, one by one): `collect_episodes_device` collects a wave of its episodes in one launch.  `reset` and `step` are the
-    parent's, so the per-step protocol works on it unchanged -- and with device="cpu" it is simply the parent."""
+class _NativeEnv:
+    """What the native environments share: the descriptor as the library's struct, and the switch to reset on the device.  The
+    class it is mixed into has `state_names`, `native_desc()`, `rs`, `n_envs`, `device` and `active`."""
 
     is_native_device_env = True
     reset_streams = None     # random.DeviceRandomStreams after enable_device_reset(): reset stream i = the state of rs[i]
-
-    def native_desc(self):
-        """hp_env_desc of the environments stepped now: kind, params [step_scale, distance_threshold], state [pos, vel, goal]
-        (float64 [active, 3] each, contiguous; the launch reads all three and writes them in place).  With device reset the
-        tensors are [n_envs, 3] for good and the environments stepped now are their first `active` rows."""
-        self.pos, self.vel, self.goal = self.pos.contiguous(), self.vel.contiguous(), self.goal.contiguous()
-        return {"kind": _lib.ENV_POINT_MASS, "params": [self.step_scale, self.distance_threshold],
-                "state": [self.pos, self.vel, self.goal]}
 
     def env_desc(self):
         """`native_desc()` as the library's struct (hp_env_desc)."""
@@ -217,7 +214,7 @@ class NativePointMassVecEnv(PointMassVecEnv):
     def enable_device_reset(self, ctx=None):
         """Reset on the device from now on (hp_env_reset; inside the launch of hp_rollout_waves): reset stream i takes over the
         current state of `self.rs[i]`, so enabling it mid-run continues the same sequence -- on a fresh environment stream i is
-        RandomState(seed + i) -- and the host generators are not advanced any more.  The state tensors become [n_envs, 3] for the
+        RandomState(seed + i) -- and the host generators are not advanced any more.  The state tensors become [n_envs, ...] for the
         life of the environment (the rows stepped now keep their values); `reset(k)`, `step` and `_observation` work on the
         first k rows.  `ctx`: the library context of the agent that collects from this environment (default: the default one)."""
         from .random import DeviceRandomStreams
@@ -229,14 +226,38 @@ class NativePointMassVecEnv(PointMassVecEnv):
         self.ctx = ctx or _lib.Context.default()
         streams = DeviceRandomStreams(self.n_envs, ctx=self.ctx)
         streams.set_states([r.get_state() for r in self.rs])
-        full = []
-        for t in (self.pos, self.vel, self.goal):
-            f = torch.zeros((self.n_envs, 3), dtype=torch.float64, device=self.device)
+        for name in self.state_names:
+            t = getattr(self, name)
+            f = torch.zeros((self.n_envs,) + tuple(t.shape[1:]), dtype=torch.float64, device=self.device)
             f[:t.shape[0]] = t
-            full.append(f)
-        self.pos, self.vel, self.goal = full
+            setattr(self, name, f)
         self.reset_streams = streams
         return streams
+
+    def _reset_on_device(self, n_active):
+        """`reset(n_active)` as one launch (hp_env_reset) on torch's current stream, in order with the environment's own kernels"""
+        k = self.n_envs if n_active is None else int(n_active)
+        if not 0 < k <= self.n_envs:
+            raise ValueError("n_active outside [1, n_envs]")
+        env = self.env_desc()
+        with self.ctx.torch_bridge():
+            _lib.check(self.ctx.lib.hp_env_reset(self.ctx.h, C.byref(env), self.reset_streams.h, k))
+        self.active = k
+        return self._observation()
+
+
+class NativePointMassVecEnv(_NativeEnv, PointMassVecEnv):
+    """`PointMassVecEnv` whose dynamics the library also evaluates itself (PointMassEnvDev, csrc/env_device.h: the same float64
+    operations, one by one): `collect_episodes_device` collects a wave of its episodes in one launch.  `reset` and `step` are the
+    parent's, so the per-step protocol works on it unchanged -- and with device="cpu" it is simply the parent."""
+
+    def native_desc(self):
+        """hp_env_desc of the environments stepped now: kind, params [step_scale, distance_threshold], state [pos, vel, goal]
+        (float64 [active, 3] each, contiguous; the launch reads all three and writes them in place).  With device reset the
+        tensors are [n_envs, 3] for good and the environments stepped now are their first `active` rows."""
+        self.pos, self.vel, self.goal = self.pos.contiguous(), self.vel.contiguous(), self.goal.contiguous()
+        return {"kind": _lib.ENV_POINT_MASS, "params": [self.step_scale, self.distance_threshold],
+                "state": [self.pos, self.vel, self.goal]}
 
     def _observation(self):
         if self.reset_streams is None:
@@ -251,14 +272,7 @@ class NativePointMassVecEnv(PointMassVecEnv):
     def reset(self, n_active=None):
         if self.reset_streams is None:
             return super().reset(n_active)
-        k = self.n_envs if n_active is None else int(n_active)
-        if not 0 < k <= self.n_envs:
-            raise ValueError("n_active outside [1, n_envs]")
-        env = self.env_desc()
-        with self.ctx.torch_bridge():       # on torch's current stream, in order with the environment's own kernels
-            _lib.check(self.ctx.lib.hp_env_reset(self.ctx.h, C.byref(env), self.reset_streams.h, k))
-        self.active = k
-        return self._observation()
+        return self._reset_on_device(n_active)
 
     def step(self, actions):
         if self.reset_streams is None:
@@ -273,3 +287,127 @@ class NativePointMassVecEnv(PointMassVecEnv):
         success = (self._distance(observation['achieved_goal'], self.goal[:k]) < self.distance_threshold).to(torch.float32)
         info = {'is_success': success}
         return observation, self.compute_reward(observation['achieved_goal'], self.goal[:k], info), False, info
+
+
+class PushBlockVecEnv:
+    """n `synthetic.PushBlockGoalEnv`s as tensors: env i resets from RandomState(seed + i) on the host -- the same rejection loop,
+    four scalars per attempt -- and `step` is the host environment's operations elementwise in float64, one torch op per
+    rounding, `torch.where` for its branches.  State: `grip`, `blk`, `goal` [rows, 3] and `vel` [rows, 6] (gripper, then block);
+    `reset`, `step` and `_observation` work on the first `active` rows, which are all of them unless the tensors were widened to
+    n_envs rows for good (`NativePushBlockVecEnv.enable_device_reset`).  Works with device="cpu" too."""
+
+    is_device_vec_env = True
+    state_names = ("grip", "blk", "goal", "vel")
+
+    def __init__(self, n_envs, seed=0, device="cuda", max_timesteps=100, distance_threshold=0.05, reward_type='sparse',
+                 step_scale=0.1, half_width=0.04, z_touch=0.25, min_separation=0.15, table_z=0.2, grip_start=(0.25, 0.1)):
+        self.n_envs = int(n_envs)
+        self.device = torch.device(device)
+        self.rs = [np.random.RandomState(seed + i) for i in range(self.n_envs)]
+        self.max_timesteps = int(max_timesteps)
+        self.distance_threshold = float(distance_threshold)
+        self.reward_type = reward_type
+        self.step_scale, self.half_width, self.z_touch = float(step_scale), float(half_width), float(z_touch)
+        self.min_separation, self.table_z = float(min_separation), float(table_z)
+        self.grip_start = (float(grip_start[0]), float(grip_start[1]))
+        self.active = self.n_envs
+        self.reset_attempts = [0] * self.n_envs      # attempts the last host reset of each environment took
+        z = torch.zeros((self.n_envs, 3), dtype=torch.float64, device=self.device)
+        self.grip, self.blk, self.goal = z, z.clone(), z.clone()
+        self.vel = torch.zeros((self.n_envs, 6), dtype=torch.float64, device=self.device)
+
+    @property
+    def env_params(self):
+        return {'obs': 27, 'goal': 3, 'action': 4, 'action_max': 0.5, 'max_timesteps': self.max_timesteps}
+
+    @property
+    def pos(self):
+        """The gripper's position: the tensor `collect_episodes_device` takes the environment's device from."""
+        return self.grip
+
+    def params(self):
+        """hp_env_desc.params of the kind"""
+        return [self.step_scale, self.distance_threshold, self.half_width, self.z_touch, self.min_separation, self.table_z,
+                self.grip_start[0], self.grip_start[1]]
+
+    def _observation(self):
+        k = self.active
+        grip, blk, vel = self.grip[:k], self.blk[:k], self.vel[:k]
+        obs = torch.zeros((k, 27), dtype=torch.float64, device=self.device)
+        obs[:, 0:3] = grip
+        obs[:, 6:9] = vel[:, 0:3]
+        obs[:, 12:15] = blk
+        obs[:, 18:21] = blk - grip
+        obs[:, 21:24] = vel[:, 3:6]
+        return {'observation': obs, 'achieved_goal': blk.clone(), 'desired_goal': self.goal[:k].clone()}
+
+    def reset(self, n_active=None):
+        """Reset the first `n_active` environments (default: all): only those draw from their streams."""
+        k = self.n_envs if n_active is None else int(n_active)
+        if not 0 < k <= self.n_envs:
+            raise ValueError("n_active outside [1, n_envs]")
+        fresh = np.empty((3, k, 3))
+        for i in range(k):
+            for attempt in range(PUSH_RESET_ATTEMPTS):
+                bx, by, gx, gy = (self.rs[i].uniform(low, high) for low, high in PUSH_RESET_BOUNDS)
+                ddx, ddy = bx - gx, by - gy
+                if np.sqrt(ddx * ddx + ddy * ddy) >= self.min_separation:
+                    break
+            self.reset_attempts[i] = attempt + 1
+            fresh[0, i] = (self.grip_start[0], self.grip_start[1], PUSH_START_Z)
+            fresh[1, i] = (bx, by, self.table_z)
+            fresh[2, i] = (gx, gy, self.table_z)
+        dev = torch.from_numpy(fresh).to(self.device)
+        self.grip, self.blk, self.goal = dev[0].contiguous(), dev[1].contiguous(), dev[2].contiguous()
+        self.vel = torch.zeros((k, 6), dtype=torch.float64, device=self.device)
+        self.active = k
+        return self._observation()
+
+    _distance = PointMassVecEnv._distance
+    compute_reward = PointMassVecEnv.compute_reward
+
+    def step(self, actions):
+        k, r = self.active, self.half_width
+        grip, blk = self.grip[:k], self.blk[:k]
+        lo = torch.tensor([PUSH_X_LO, PUSH_Y_LO, self.table_z], dtype=torch.float64, device=self.device)
+        hi = torch.tensor([PUSH_X_HI, PUSH_Y_HI, PUSH_Z_HI], dtype=torch.float64, device=self.device)
+        a = torch.clamp(actions.to(torch.float64), -0.5, 0.5)
+        scaled = self.step_scale * a[:, :3]                 # multiply, then add: two roundings, like numpy
+        new = torch.minimum(torch.maximum(grip + scaled, lo), hi)
+        gvel = new - grip
+        dx, dy = blk[:, 0] - new[:, 0], blk[:, 1] - new[:, 1]
+        adx, ady = dx.abs(), dy.abs()
+        contact = (new[:, 2] < self.z_touch) & (adx < r) & (ady < r)
+        along_x = (r - adx) <= (r - ady)                    # the axis of least penetration
+        plus, minus = torch.full_like(dx, r), torch.full_like(dx, -r)
+        bx = torch.where(contact & along_x, new[:, 0] + torch.where(dx >= 0, plus, minus), blk[:, 0])
+        by = torch.where(contact & ~along_x, new[:, 1] + torch.where(dy >= 0, plus, minus), blk[:, 1])
+        bx = torch.where(contact, torch.clamp(bx, PUSH_X_LO, PUSH_X_HI), bx)
+        by = torch.where(contact, torch.clamp(by, PUSH_Y_LO, PUSH_Y_HI), by)
+        moved = torch.stack([bx, by, blk[:, 2]], dim=1)
+        bvel = moved - blk
+        self.grip[:k], self.blk[:k] = new, moved
+        self.vel[:k, 0:3], self.vel[:k, 3:6] = gvel, bvel
+        observation = self._observation()
+        success = (self._distance(observation['achieved_goal'], self.goal[:k]) < self.distance_threshold).to(torch.float32)
+        info = {'is_success': success}
+        return observation, self.compute_reward(observation['achieved_goal'], self.goal[:k], info), False, info
+
+
+class NativePushBlockVecEnv(_NativeEnv, PushBlockVecEnv):
+    """`PushBlockVecEnv` whose dynamics the library also evaluates itself (PushBlockEnvDev, csrc/env_device.h: the same float64
+    operations, one by one): `collect_episodes_device` collects a wave of its episodes in one launch, and after
+    `enable_device_reset()` the rejection loop of its reset runs on the device too -- every environment for as many attempts as its
+    own draws ask for.  `step` is the parent's, so the per-step protocol works on it unchanged."""
+
+    def native_desc(self):
+        """hp_env_desc of the environments stepped now: kind, the eight params, state [grip, blk, goal, vel] (float64, contiguous;
+        the launch reads all four and writes them in place): [active, 3] and [active, 6], or n_envs rows with device reset."""
+        for name in self.state_names:
+            setattr(self, name, getattr(self, name).contiguous())
+        return {"kind": _lib.ENV_PUSH_BLOCK, "params": self.params(), "state": [getattr(self, name) for name in self.state_names]}
+
+    def reset(self, n_active=None):
+        if self.reset_streams is None:
+            return super().reset(n_active)
+        return self._reset_on_device(n_active)

@@ -118,3 +118,95 @@ class PointMassGoalEnv:
         info = {'is_success': self._is_success(observation['achieved_goal'], self.goal)}
         reward = self.compute_reward(observation['achieved_goal'], self.goal, info)
         return observation, reward, False, info
+
+
+# the workspace of the push-block environments (synthetic.PushBlockGoalEnv, device_env.PushBlockVecEnv, PushBlockEnvDev in
+# csrc/env_device.h): x, y of gripper and block; the gripper's z runs from the table up to PUSH_Z_HI and starts at PUSH_START_Z
+PUSH_X_LO, PUSH_X_HI, PUSH_Y_LO, PUSH_Y_HI, PUSH_Z_HI, PUSH_START_Z = 0.0, 0.5, 0.0, 0.7, 0.5, 0.3
+# the four draws of one reset attempt, in draw order: block x, y, goal x, y (low, high)
+PUSH_RESET_BOUNDS = ((0.15, 0.35), (0.2, 0.5), (0.0, 0.35), (0.2, 0.5))
+PUSH_RESET_ATTEMPTS = 100
+
+
+class PushBlockGoalEnv:
+    """A kinematic planar push with the GoalEnv surface of `PointMassGoalEnv`: the setting of the reference's Push task
+    (bmirobot_env_push_F.py) in which the achieved goal is a block that moves only on contact, so that most actions leave it
+    where it is and the reward is sparse in earnest.  The block is a square of half width `half_width` resting on the table; the
+    first three action components move the gripper (the fourth, the fingers, is ignored: :94); while the gripper is below
+    `z_touch` and inside the square, the block is pushed out along the axis of least penetration.  `step` is adds, subtracts,
+    multiplies, compares and clamps only -- no division, no square root -- so that the tensor twin and the device struct agree
+    with it bit for bit by construction.  `reset` redraws block and target until they are `min_separation` apart (:117-132, at
+    most 100 attempts; the last attempt is kept either way), four scalars per attempt from the environment's own RandomState."""
+
+    def __init__(self, seed=0, max_timesteps=100, distance_threshold=0.05, reward_type='sparse', step_scale=0.1, half_width=0.04,
+                 z_touch=0.25, min_separation=0.15, table_z=0.2, grip_start=(0.25, 0.1)):
+        self.rs = np.random.RandomState(seed)
+        self.max_timesteps = int(max_timesteps)
+        self.distance_threshold = float(distance_threshold)
+        self.reward_type = reward_type
+        self.step_scale, self.half_width, self.z_touch = float(step_scale), float(half_width), float(z_touch)
+        self.min_separation, self.table_z = float(min_separation), float(table_z)
+        self.grip_start = (float(grip_start[0]), float(grip_start[1]))
+        self.grip, self.blk, self.goal = np.zeros(3), np.zeros(3), np.zeros(3)
+        self.gvel, self.bvel = np.zeros(3), np.zeros(3)
+        self.reset_attempts = 0              # attempts the last reset took
+
+    @property
+    def env_params(self):
+        return {'obs': 27, 'goal': 3, 'action': 4, 'action_max': 0.5, 'max_timesteps': self.max_timesteps}
+
+    def _observation(self):
+        obs = np.zeros(27)                   # the bmirobot layout (:208-222): nine blocks of three
+        obs[0:3] = self.grip
+        obs[6:9] = self.gvel
+        obs[12:15] = self.blk
+        obs[18:21] = self.blk - self.grip
+        obs[21:24] = self.bvel
+        return {'observation': obs, 'achieved_goal': self.blk.copy(), 'desired_goal': self.goal.copy()}
+
+    def reset(self):
+        for attempt in range(PUSH_RESET_ATTEMPTS):
+            bx, by, gx, gy = (self.rs.uniform(low, high) for low, high in PUSH_RESET_BOUNDS)
+            ddx, ddy = bx - gx, by - gy
+            if np.sqrt(ddx * ddx + ddy * ddy) >= self.min_separation:
+                break
+        self.reset_attempts = attempt + 1
+        self.blk = np.array([bx, by, self.table_z])
+        self.goal = np.array([gx, gy, self.table_z])
+        self.grip = np.array([self.grip_start[0], self.grip_start[1], PUSH_START_Z])
+        self.gvel, self.bvel = np.zeros(3), np.zeros(3)
+        return self._observation()
+
+    def compute_reward(self, achieved_goal, goal, info):
+        diff = np.asarray(achieved_goal) - np.asarray(goal)
+        d = np.linalg.norm(diff, axis=-1)
+        if self.reward_type == 'sparse':
+            return -(d > self.distance_threshold).astype(np.float32)
+        return -d
+
+    def _is_success(self, achieved_goal, desired_goal):
+        return (np.linalg.norm(achieved_goal - desired_goal, axis=-1) < self.distance_threshold).astype(np.float32)
+
+    def step(self, action):
+        r = self.half_width
+        action = np.clip(np.asarray(action, dtype=np.float64), -0.5, 0.5)
+        lo = np.array([PUSH_X_LO, PUSH_Y_LO, self.table_z])
+        hi = np.array([PUSH_X_HI, PUSH_Y_HI, PUSH_Z_HI])
+        new = np.clip(self.grip + self.step_scale * action[:3], lo, hi)
+        self.gvel = new - self.grip
+        self.grip = new
+        old = self.blk.copy()
+        dx, dy = self.blk[0] - self.grip[0], self.blk[1] - self.grip[1]
+        if self.grip[2] < self.z_touch and abs(dx) < r and abs(dy) < r:
+            px, py = r - abs(dx), r - abs(dy)          # how deep the gripper is inside the block, per axis
+            if px <= py:                               # out along the axis of least penetration
+                self.blk[0] = self.grip[0] + (r if dx >= 0 else -r)
+            else:
+                self.blk[1] = self.grip[1] + (r if dy >= 0 else -r)
+            self.blk[0] = min(max(self.blk[0], PUSH_X_LO), PUSH_X_HI)
+            self.blk[1] = min(max(self.blk[1], PUSH_Y_LO), PUSH_Y_HI)
+        self.bvel = self.blk - old
+        observation = self._observation()
+        info = {'is_success': self._is_success(observation['achieved_goal'], self.goal)}
+        reward = self.compute_reward(observation['achieved_goal'], self.goal, info)
+        return observation, reward, False, info
