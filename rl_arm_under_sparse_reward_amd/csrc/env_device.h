@@ -1,8 +1,8 @@
-// env_device.h -- environments the library steps itself: the seam of k_rollout_episodes (rollout.hip).
+// env_device.h -- environments the library steps itself: the seam of k_rollout_episodes (rollout_episodes.h).
 //
 // An environment kind is one struct of __device__ functions over the state of ONE environment; the kernel keeps one instance per
 // row of its slab in LDS and calls every function from one lane (lane 0 of the row's wave):
-//     static constexpr int OBS, GOAL, ACT     dimensions, compared with the block's on the host before the launch
+//     static constexpr int OBS, GOAL, ACT     dimensions, compared with the block's on the host before the launch (the kind's row)
 //     load(desc, i)                            state of environment i out of the arrays of hp_env_desc (and the parameters)
 //     observe(obs, ag, g)                      write the current observation row [OBS], achieved goal [GOAL], desired goal [GOAL]
 //     step(action_f32)                         advance by one timestep with the float32 action [ACT] the policy side produced
@@ -26,10 +26,12 @@
 // RESET_ATTEMPTS = 1 there is no loop and no verdict: the code is the fixed reset's.
 // Every float64 operation whose rounding the host twin of the environment fixes is an explicit IEEE operation (__dmul_rn, ...), so
 // that no contraction can change a bit relative to the elementwise torch / numpy ops of that twin.
-// Adding a kind: a struct here, an HP_ENV_* constant in rlarm_hip.h, a case in env_state_arrays and in the dispatches of
-// hp_rollout_episodes / hp_rollout_waves and hp_env_reset (rollout.hip) -- and, so that rollout.hip keeps compiling one instantiation
-// of each kernel, a translation unit of its own that instantiates k_rollout_episodes / k_env_reset (rollout_episodes.h) for the kind
-// and exports the two launchers those dispatches call (env_push_block.hip is the model).
+// Adding a kind touches this and nothing else: a struct here; an HP_ENV_* constant in rlarm_hip.h and its twin in _lib.py; a unit
+// env_<kind>.hip of three lines -- the include of rollout_episodes.h and `const EnvKind env_kind_<kind> = env_kind_entry<Struct>(HP_ENV_...)`,
+// which instantiates both kernels for the kind and checks at compile time what a kind must be for them -- with its entry in the
+// Makefile's EXACT_SRCS; the row's declaration in rollout_episodes.h and its address in the table of env_kind() (rollout.hip); and
+// one Python class pair in device_env.py (the tensor twin, and a native class that names the constant).  No entry point, dispatch or
+// check names a kind: they read the row (env_point_mass.hip and env_push_block.hip are the two models).
 #pragma once
 #include "internal.h"
 #include <type_traits>

@@ -25,23 +25,13 @@
 // of one reset stream per environment): the same kernel loops over the waves, resets a row's environment between two episodes on
 // the row's own wave, and writes every environment and every stream back once.  hp_env_reset is that reset as a launch of its own,
 // for the per-step path.
+//
+// This unit compiles the two per-step kernels and the host side of every entry.  The whole-episode kernels and the reset are
+// templates over an environment kind (rollout_episodes.h) that each kind's own unit instantiates (env_point_mass.hip,
+// env_push_block.hip); the entries here reach them through the kind's row of the table below (env_kind) and know no kind by name.
 #include <algorithm>
 
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wundefined-inline"   // agent_device.h declares the 32-row engine's fragment map, which no code here calls
-#include "agent_device.h"
-#pragma clang diagnostic pop
-
-// the 4-row policy slab's device functions (no kernel of slab8.h is compiled here)
-#define S8_DEVICE_ONLY
-#define S8_NRG 1
-#define S8_NS s8ro
-#include "slab8.h"
-#undef S8_NRG
-#undef S8_NS
-#undef S8_DEVICE_ONLY
-
-#include "rollout_episodes.h"   // ExploreArgs, ro_explore_row, and the kernel templates of a whole wave / of all waves of a call
+#include "rollout_episodes.h"   // ExploreArgs, ro_explore_row, PolicyArgs (slab8.h), EpisodesArgs and EnvKind
 
 struct hp_rollout {
     hp_ctx *ctx = nullptr;
@@ -125,11 +115,17 @@ __global__ __launch_bounds__(MW_THREADS) void k_rollout_step_streams(const Rollo
     w.store(st);
 }
 
-static int rollout_launch(hp_rollout *ro, RolloutStepArgs &A, int t, bool per_env_streams = false) {
+// the block's four arrays, offset to episode ro->first (RolloutStepArgs and EpisodesArgs)
+template <class Args>
+static void rollout_block_arrays(const hp_rollout *ro, Args &A) {
     A.b_obs = ro->block + ro->first * (ro->T + 1) * ro->od;
     A.b_ag = ro->block + ro->o_ag + ro->first * (ro->T + 1) * ro->gd;
     A.b_g = ro->block + ro->o_g + ro->first * ro->T * ro->gd;
     A.b_act = ro->block + ro->o_act + ro->first * ro->T * ro->ad;
+}
+
+static int rollout_launch(hp_rollout *ro, RolloutStepArgs &A, int t, bool per_env_streams = false) {
+    rollout_block_arrays(ro, A);
     A.rows = (int)ro->rows; A.T = ro->T; A.t = t; A.od = ro->od; A.gd = ro->gd; A.ad = ro->ad;
     const long long elems = ro->rows * (ro->od + 2 * ro->gd);
     long long nb = (elems + 4 * MW_THREADS - 1) / (4 * MW_THREADS);   // four elements per thread
@@ -142,11 +138,25 @@ static int rollout_launch(hp_rollout *ro, RolloutStepArgs &A, int t, bool per_en
     return HP_OK;
 }
 
-// the part of a step both stream forms share: the policy launch, then the draw + record launch.  `st` is the single stream's state
-// or -- per_env_streams -- the first of one state per row
-static int rollout_step(const char *entry, hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, MtState *st, bool per_env_streams, int32_t t,
-                        const double *obs_dev, const double *ag_dev, const double *g_dev, int32_t explore, double noise_eps,
-                        double random_eps, double qn, double clip_abs, float *actions_f32_dev) {
+// A step of either stream form: the checks, the policy launch, then the draw + record launch.  `st` is the single stream's state
+// (n_streams < 0) or the first of n_streams states, one per row; st_ctx is the context of its handle and `what` names that handle
+// in a refusal.  st == nullptr: the caller passed no handle
+static int rollout_step(const char *entry, const char *what, hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, hp_ctx *st_ctx,
+                        MtState *st, int64_t n_streams, int32_t t, const double *obs_dev, const double *ag_dev, const double *g_dev,
+                        int32_t explore, double noise_eps, double random_eps, double qn, double clip_abs, float *actions_f32_dev) {
+    const bool per_env_streams = n_streams >= 0;
+    HP_REQUIRE(ro && obs_dev && ag_dev && g_dev && actions_f32_dev, HP_ERR_INVALID, "%s: null argument", entry);
+    HP_REQUIRE(!explore || st, HP_ERR_INVALID, "%s: exploration needs the %s", entry, what);
+    HP_REQUIRE(!a || (on && gn), HP_ERR_INVALID, "%s: the policy needs both normalizers", entry);
+    HP_SERIALISE(ro);
+    HP_REQUIRE(t >= 0 && t < ro->T, HP_ERR_INVALID, "%s: t=%d outside [0, %d)", entry, t, ro->T);
+    HP_REQUIRE(!st || st_ctx == ro->ctx, HP_ERR_INVALID, "%s: %s belongs to another context", entry, what);
+    if (per_env_streams) {
+        HP_REQUIRE(!explore || ro->rows <= n_streams, HP_ERR_INVALID, "%s: a wave of %lld environments is wider than the array of %lld streams",
+                   entry, (long long)ro->rows, (long long)n_streams);
+        HP_REQUIRE(ro->ad <= RO_MAX_ACT, HP_ERR_INVALID, "%s: at most %d action components", entry, RO_MAX_ACT);
+    }
+    HP_REQUIRE(!explore || (random_eps >= 0.0 && random_eps <= 1.0), HP_ERR_INVALID, "p < 0, p > 1 or p is NaN");
     double amax = ro->action_max;
     if (a) {   // a == NULL: actions_f32_dev already holds the policy outputs (teacher-forced tests)
         HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx, HP_ERR_INVALID,
@@ -172,10 +182,10 @@ static int rollout_step(const char *entry, hp_rollout *ro, hp_agent *a, hp_norm 
 // A call of hp_rollout_episodes / hp_rollout_waves as launches.  A (hp_rollout_episodes, or hp_rollout_waves with A.reset_st and
 // A.n_envs set) describes the whole call: episodes [first, first + rows) of the block; it is issued as consecutive launches of at
 // most ro->launch_cap timesteps (whole waves, at least one), each a call of its own on the episodes, flags and final states the one
-// before it left.  launch(blocks, L) issues one of them on ro->ctx->stream with the kernel of the environment's kind and returns
-// its hipError_t: this loop is the same for every kind.
-template <class Launch>
-static int rollout_split_launches(hp_rollout *ro, const EpisodesArgs &A, int32_t *launches, Launch launch) {
+// before it left.  launch (EnvKind::launch_episodes) issues one of them with the kernel of the environment's kind and returns its
+// hipError_t: this loop is the same for every kind.
+static int rollout_split_launches(hp_rollout *ro, const EpisodesArgs &A, int32_t *launches,
+                                  hipError_t (*launch)(hipStream_t, unsigned, const EpisodesArgs &)) {
     const int64_t total = A.rows, n_envs = A.n_envs;
     int64_t per = ro->launch_cap / (ro->T > 0 ? ro->T : 1);   // waves per launch
     if (per < 1) per = 1;
@@ -191,39 +201,19 @@ static int rollout_split_launches(hp_rollout *ro, const EpisodesArgs &A, int32_t
         L.success += done;
         L.rows = (int)rows; L.waves = (int)waves;
         L.P.rows = (int)live;              // the environments that take part in the launch at all
-        HP_CHECK_HIP(launch((unsigned)((live + 3) / 4), L));
+        HP_CHECK_HIP(launch(ro->ctx->stream, (unsigned)((live + 3) / 4), L));
         done += rows;
     }
     if (launches) *launches = n;
     return HP_OK;
 }
 
-// What a kind must be for these kernels, and its dimensions against the block's, before any launch
-template <class Env>
-static int rollout_episodes_check(const char *entry, hp_rollout *ro, const EpisodesArgs &A) {
-    HP_REQUIRE(ro->od == Env::OBS && ro->gd == Env::GOAL && ro->ad == Env::ACT, HP_ERR_INVALID,
-               "%s: env->kind %d has dimensions %d / %d / %d, the block has %d / %d / %d", entry, (int)A.env.kind, Env::OBS,
-               Env::GOAL, Env::ACT, ro->od, ro->gd, ro->ad);
-    HP_REQUIRE(!A.reset_st || Env::RESET_DRAWS > 0, HP_ERR_INVALID, "%s: env->kind %d has no reset on the device", entry, (int)A.env.kind);
-    static_assert(Env::ACT <= 4 && Env::ACT <= RO_MAX_ACT && Env::OBS + Env::GOAL <= S8_LDX, "an environment of the policy slab's shape");
-    static_assert(Env::RESET_DRAWS <= RO_MAX_ACT, "the reset's values pass through the row's zs");
-    static_assert(Env::STATE_ARRAYS >= 1 && Env::STATE_ARRAYS <= 4, "hp_env_desc has four state arrays");
-    return HP_OK;
-}
-
-template <class Env>
-static int env_reset_check(int kind) {
-    HP_REQUIRE(Env::RESET_DRAWS > 0, HP_ERR_INVALID, "hp_env_reset: env->kind %d has no reset on the device", kind);
-    return HP_OK;
-}
-
-// state arrays of hp_env_desc a kind uses; 0: not an environment kind of this build
-static int env_state_arrays(int kind) {
-    switch (kind) {
-        case HP_ENV_POINT_MASS: return PointMassEnvDev::STATE_ARRAYS;
-        case HP_ENV_PUSH_BLOCK: return PushBlockEnvDev::STATE_ARRAYS;
-        default: return 0;
-    }
+// The table of environment kinds: one row per kind, defined by the kind's own unit.  nullptr: not an environment kind of this build
+static const EnvKind *env_kind(int kind) {
+    static const EnvKind *const kinds[] = {&env_kind_point_mass, &env_kind_push_block};
+    for (const EnvKind *k : kinds)
+        if (k->kind == kind) return k;
+    return nullptr;
 }
 
 // what hp_rollout_episodes and hp_rollout_waves share: the checks on agent, normalizers, block and streams, and the arguments of the
@@ -234,8 +224,8 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx && (!streams || streams->ctx == ro->ctx) &&
                    (!reset_streams || reset_streams->ctx == ro->ctx),
                HP_ERR_INVALID, "%s: handles belong to different contexts", entry);
-    HP_REQUIRE(env_state_arrays(env->kind) > 0, HP_ERR_INVALID, "%s: env->kind %d is not an environment kind of this build", entry,
-               (int)env->kind);
+    const EnvKind *kind = env_kind(env->kind);
+    HP_REQUIRE(kind, HP_ERR_INVALID, "%s: env->kind %d is not an environment kind of this build", entry, (int)env->kind);
     HP_REQUIRE(a->slab8 && a->H == 256 && a->ldx <= 48 && a->cfg.act_dim <= 4, HP_ERR_INVALID,
                "%s: the agent is not slab-shaped (hidden %d, padded input width %d, act_dim %d, engine %s): it keeps "
                "the per-step calls", entry, a->H, a->ldx, a->cfg.act_dim, a->slab8 ? "slab8" : "other");
@@ -249,8 +239,12 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     HP_REQUIRE(!reset_streams || n_envs <= reset_streams->n, HP_ERR_INVALID,
                "%s: %lld environments, but the array holds %lld reset streams", entry, (long long)n_envs, (long long)reset_streams->n);
     HP_REQUIRE(!explore || (random_eps >= 0.0 && random_eps <= 1.0), HP_ERR_INVALID, "p < 0, p > 1 or p is NaN");
-    for (int k = 0; k < env_state_arrays(env->kind); ++k)
+    for (int k = 0; k < kind->state_arrays; ++k)
         HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "%s: env->state_dev[%d] is null", entry, k);
+    HP_REQUIRE(ro->od == kind->obs && ro->gd == kind->goal && ro->ad == kind->act, HP_ERR_INVALID,
+               "%s: env->kind %d has dimensions %d / %d / %d, the block has %d / %d / %d", entry, (int)env->kind, kind->obs, kind->goal,
+               kind->act, ro->od, ro->gd, ro->ad);
+    HP_REQUIRE(!reset_streams || kind->reset_draws > 0, HP_ERR_INVALID, "%s: env->kind %d has no reset on the device", entry, (int)env->kind);
     EpisodesArgs A;
     memset(&A, 0, sizeof(A));
     PolicyArgs &P = A.P;
@@ -259,10 +253,7 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     P.clip_obs = INFINITY; P.clip_o = on->clip; P.clip_g = gn->clip;   // agent_act_dev with clip_obs = 0
     P.net = SlabNetPtrs{a->fragF, a->fragD, a->params};
     P.la = a->la; P.H = a->H; P.act_dim = a->cfg.act_dim; P.max_action = (float)a->cfg.max_action;
-    A.b_obs = ro->block + ro->first * (ro->T + 1) * ro->od;
-    A.b_ag = ro->block + ro->o_ag + ro->first * (ro->T + 1) * ro->gd;
-    A.b_g = ro->block + ro->o_g + ro->first * ro->T * ro->gd;
-    A.b_act = ro->block + ro->o_act + ro->first * ro->T * ro->ad;
+    rollout_block_arrays(ro, A);
     A.st = explore ? streams->d_state : nullptr;
     A.reset_st = reset_streams ? reset_streams->d_state : nullptr;
     A.rows = (int)ro->rows; A.T = ro->T; A.explore = explore ? 1 : 0;
@@ -274,21 +265,7 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     A.x.random_eps = random_eps; A.x.qn = qn; A.x.clip_abs = clip_abs;
     A.env = *env;
     A.success = success_dev;
-    switch (env->kind) {   // one case per environment kind (env_device.h)
-        case HP_ENV_POINT_MASS:
-            HP_TRY(rollout_episodes_check<PointMassEnvDev>(entry, ro, A));
-            return rollout_split_launches(ro, A, launches, [&](unsigned blocks, const EpisodesArgs &L) {
-                hipLaunchKernelGGL(k_rollout_episodes<PointMassEnvDev>, dim3(blocks), dim3(S8_THREADS), 0, ro->ctx->stream, L);
-                return hipGetLastError();
-            });
-        case HP_ENV_PUSH_BLOCK:
-            HP_TRY(rollout_episodes_check<PushBlockEnvDev>(entry, ro, A));
-            return rollout_split_launches(ro, A, launches, [&](unsigned blocks, const EpisodesArgs &L) {
-                return push_block_launch_episodes(ro->ctx->stream, blocks, L);
-            });
-        default: break;
-    }
-    return HP_ERR_INVALID;
+    return rollout_split_launches(ro, A, launches, kind->launch_episodes);
 }
 
 extern "C" {
@@ -341,32 +318,15 @@ int hp_rollout_block(hp_rollout *ro, void **block_dev, int64_t *n_episodes, int6
 int hp_rollout_step(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, hp_rng *rng, int32_t t, const double *obs_dev,
                     const double *ag_dev, const double *g_dev, int32_t explore, double noise_eps, double random_eps, double qn,
                     double clip_abs, float *actions_f32_dev) {
-    HP_REQUIRE(ro && obs_dev && ag_dev && g_dev && actions_f32_dev, HP_ERR_INVALID, "hp_rollout_step: null argument");
-    HP_REQUIRE(!explore || rng, HP_ERR_INVALID, "hp_rollout_step: exploration needs the random stream");
-    HP_REQUIRE(!a || (on && gn), HP_ERR_INVALID, "hp_rollout_step: the policy needs both normalizers");
-    HP_SERIALISE(ro);
-    HP_REQUIRE(t >= 0 && t < ro->T, HP_ERR_INVALID, "hp_rollout_step: t=%d outside [0, %d)", t, ro->T);
-    HP_REQUIRE(!rng || rng->ctx == ro->ctx, HP_ERR_INVALID, "hp_rollout_step: random stream belongs to another context");
-    HP_REQUIRE(!explore || (random_eps >= 0.0 && random_eps <= 1.0), HP_ERR_INVALID, "p < 0, p > 1 or p is NaN");
-    return rollout_step("hp_rollout_step", ro, a, on, gn, rng ? rng->d_state : nullptr, false, t, obs_dev, ag_dev, g_dev, explore, noise_eps, random_eps, qn,
-                        clip_abs, actions_f32_dev);
+    return rollout_step("hp_rollout_step", "random stream", ro, a, on, gn, rng ? rng->ctx : nullptr, rng ? rng->d_state : nullptr, -1, t,
+                        obs_dev, ag_dev, g_dev, explore, noise_eps, random_eps, qn, clip_abs, actions_f32_dev);
 }
 
 int hp_rollout_step_streams(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, hp_rng_streams *streams, int32_t t,
                             const double *obs_dev, const double *ag_dev, const double *g_dev, int32_t explore, double noise_eps,
                             double random_eps, double qn, double clip_abs, float *actions_f32_dev) {
-    HP_REQUIRE(ro && obs_dev && ag_dev && g_dev && actions_f32_dev, HP_ERR_INVALID, "hp_rollout_step_streams: null argument");
-    HP_REQUIRE(!explore || streams, HP_ERR_INVALID, "hp_rollout_step_streams: exploration needs the stream array");
-    HP_REQUIRE(!a || (on && gn), HP_ERR_INVALID, "hp_rollout_step_streams: the policy needs both normalizers");
-    HP_SERIALISE(ro);
-    HP_REQUIRE(t >= 0 && t < ro->T, HP_ERR_INVALID, "hp_rollout_step_streams: t=%d outside [0, %d)", t, ro->T);
-    HP_REQUIRE(!streams || streams->ctx == ro->ctx, HP_ERR_INVALID, "hp_rollout_step_streams: stream array belongs to another context");
-    HP_REQUIRE(!explore || ro->rows <= streams->n, HP_ERR_INVALID,
-               "hp_rollout_step_streams: a wave of %lld environments is wider than the array of %lld streams", (long long)ro->rows,
-               (long long)streams->n);
-    HP_REQUIRE(ro->ad <= RO_MAX_ACT, HP_ERR_INVALID, "hp_rollout_step_streams: at most %d action components", RO_MAX_ACT);
-    HP_REQUIRE(!explore || (random_eps >= 0.0 && random_eps <= 1.0), HP_ERR_INVALID, "p < 0, p > 1 or p is NaN");
-    return rollout_step("hp_rollout_step_streams", ro, a, on, gn, streams ? streams->d_state : nullptr, true, t, obs_dev, ag_dev, g_dev, explore, noise_eps,
+    return rollout_step("hp_rollout_step_streams", "stream array", ro, a, on, gn, streams ? streams->ctx : nullptr,
+                        streams ? streams->d_state : nullptr, streams ? streams->n : 0, t, obs_dev, ag_dev, g_dev, explore, noise_eps,
                         random_eps, qn, clip_abs, actions_f32_dev);
 }
 
@@ -396,23 +356,13 @@ int hp_env_reset(hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *reset_stre
     HP_REQUIRE(reset_streams->ctx == ctx, HP_ERR_INVALID, "hp_env_reset: handles belong to different contexts");
     HP_REQUIRE(rows > 0 && rows <= reset_streams->n, HP_ERR_INVALID,
                "hp_env_reset: %lld environments, but the array holds %lld reset streams", (long long)rows, (long long)reset_streams->n);
-    HP_REQUIRE(env_state_arrays(env->kind) > 0, HP_ERR_INVALID, "hp_env_reset: env->kind %d is not an environment kind of this build",
-               (int)env->kind);
-    for (int k = 0; k < env_state_arrays(env->kind); ++k)
+    const EnvKind *kind = env_kind(env->kind);
+    HP_REQUIRE(kind, HP_ERR_INVALID, "hp_env_reset: env->kind %d is not an environment kind of this build", (int)env->kind);
+    for (int k = 0; k < kind->state_arrays; ++k)
         HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "hp_env_reset: env->state_dev[%d] is null", k);
-    switch (env->kind) {   // one case per environment kind (env_device.h)
-        case HP_ENV_POINT_MASS:
-            HP_TRY(env_reset_check<PointMassEnvDev>(env->kind));
-            hipLaunchKernelGGL(k_env_reset<PointMassEnvDev>, dim3((unsigned)rows), dim3(MW_THREADS), 0, ctx->stream, *env, reset_streams->d_state);
-            HP_CHECK_HIP(hipGetLastError());
-            return HP_OK;
-        case HP_ENV_PUSH_BLOCK:
-            HP_TRY(env_reset_check<PushBlockEnvDev>(env->kind));
-            HP_CHECK_HIP(push_block_launch_reset(ctx->stream, *env, reset_streams->d_state, rows));
-            return HP_OK;
-        default: break;
-    }
-    return HP_ERR_INVALID;
+    HP_REQUIRE(kind->reset_draws > 0, HP_ERR_INVALID, "hp_env_reset: env->kind %d has no reset on the device", (int)env->kind);
+    HP_CHECK_HIP(kind->launch_reset(ctx->stream, *env, reset_streams->d_state, rows));
+    return HP_OK;
 }
 
 int hp_rollout_debug_set_launch_cap(hp_rollout *ro, int64_t timesteps) {

@@ -1,10 +1,26 @@
 // rollout_episodes.h -- whole episodes in one launch: the kernels of hp_rollout_episodes / hp_rollout_waves and hp_env_reset as
-// templates over an environment kind (env_device.h), with their argument block and LDS layout.
+// templates over an environment kind (env_device.h), with their argument block and LDS layout, and the table row of a kind
+// (EnvKind, env_kind_entry) through which rollout.hip reaches them.
 //
-// A translation unit instantiates them for the kinds it launches: rollout.hip for PointMassEnvDev, and one unit per further kind
-// (env_push_block.hip), so that no unit compiles the policy slab's kernel body more than once.  The includer has included
-// agent_device.h and the 4-row policy slab's device functions as namespace s8ro first (the S8_DEVICE_ONLY block of rollout.hip).
+// Nothing is instantiated here and nothing in rollout.hip: every kind has a translation unit of its own (env_point_mass.hip,
+// env_push_block.hip) that includes this file and defines the kind's row, and env_kind_entry<Env> is the one place that names the
+// kernels of a kind -- so each unit compiles the policy slab's body (the bulk of its compile) exactly once.  What the kernels
+// borrow comes in with this file: agent_device.h and the 4-row policy slab's device functions as namespace s8ro.
 #pragma once
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wundefined-inline"   // agent_device.h declares the 32-row engine's fragment map, which no code here calls
+#include "agent_device.h"
+#pragma clang diagnostic pop
+
+// the 4-row policy slab's device functions (no kernel of slab8.h is compiled by an includer of this file)
+#define S8_DEVICE_ONLY
+#define S8_NRG 1
+#define S8_NS s8ro
+#include "slab8.h"
+#undef S8_NRG
+#undef S8_NS
+#undef S8_DEVICE_ONLY
+
 #include "env_device.h"
 #include "mt19937_wave.h"
 
@@ -207,8 +223,35 @@ __global__ __launch_bounds__(MW_THREADS) void k_env_reset(const hp_env_desc env,
     }
 }
 
-// The launchers of the kinds instantiated outside rollout.hip, called by its dispatches: one launch of k_rollout_episodes<Env> over
-// `blocks` workgroups with the arguments of that launch (the split by the launch cap stays in rollout.hip), and k_env_reset<Env>
-// over `rows` environments.  Each returns the launch's hipError_t.
-hipError_t push_block_launch_episodes(hipStream_t stream, unsigned blocks, const EpisodesArgs &L);   // env_push_block.hip
-hipError_t push_block_launch_reset(hipStream_t stream, const hp_env_desc &env, MtState *reset_st, int64_t rows);
+// ---- the table of kinds ------------------------------------------------------------------------------------------------------
+// What the host side of rollout.hip knows of a kind: its constant, what it compares with the block and the descriptor before any
+// launch, and how to launch its two kernels.  launch_episodes issues one launch of k_rollout_episodes over `blocks` workgroups with
+// the arguments of that launch (the split by the launch cap stays in rollout.hip), launch_reset one of k_env_reset over `rows`
+// environments; each returns the launch's hipError_t.
+struct EnvKind {
+    int kind, obs, goal, act, state_arrays, reset_draws;
+    hipError_t (*launch_episodes)(hipStream_t stream, unsigned blocks, const EpisodesArgs &L);
+    hipError_t (*launch_reset)(hipStream_t stream, const hp_env_desc &env, MtState *reset_st, int64_t rows);
+};
+
+// The row of kind `kind` = the struct Env of env_device.h: what a kind must be for these kernels, and the kernels' instantiation
+// (in the one unit that calls this for Env).
+template <class Env>
+EnvKind env_kind_entry(int kind) {
+    static_assert(Env::ACT <= 4 && Env::ACT <= RO_MAX_ACT && Env::OBS + Env::GOAL <= S8_LDX, "an environment of the policy slab's shape");
+    static_assert(Env::RESET_DRAWS <= RO_MAX_ACT, "the reset's values pass through the row's zs");
+    static_assert(Env::STATE_ARRAYS >= 1 && Env::STATE_ARRAYS <= 4, "hp_env_desc has four state arrays");
+    return EnvKind{kind, Env::OBS, Env::GOAL, Env::ACT, Env::STATE_ARRAYS, Env::RESET_DRAWS,
+                   [](hipStream_t stream, unsigned blocks, const EpisodesArgs &L) {
+                       hipLaunchKernelGGL(k_rollout_episodes<Env>, dim3(blocks), dim3(S8_THREADS), 0, stream, L);
+                       return hipGetLastError();
+                   },
+                   [](hipStream_t stream, const hp_env_desc &env, MtState *reset_st, int64_t rows) {
+                       hipLaunchKernelGGL(k_env_reset<Env>, dim3((unsigned)rows), dim3(MW_THREADS), 0, stream, env, reset_st);
+                       return hipGetLastError();
+                   }};
+}
+
+// the rows, one per unit (the table itself: env_kind() in rollout.hip)
+extern const EnvKind env_kind_point_mass;   // env_point_mass.hip
+extern const EnvKind env_kind_push_block;   // env_push_block.hip

@@ -655,93 +655,102 @@ class ddpg_agent:
 
     def collect_episodes_device(self, vec_env=None, n_rollouts=None, epoch=0, explore=True, success_out=None):
         """`collect_episodes` for a vectorised device environment (device_env.py): `n_rollouts` episodes (default: one wave of
-        vec_env.n_envs) in waves of n_envs, T timesteps of two launches each (csrc/rollout.hip) on torch's current stream, no
-        host copy and no host wait per timestep -- or, for a native environment, a slab-shaped agent and draws that are
-        independent across environments (`device_env.fused_rollout_reason`), ONE launch per wave (hp_rollout_episodes), the same
-        bits; `self.rollout_form` says which form the last wave took.  Exploration (:174-184, the +-0.15 clip from epoch 100) is drawn on the device
-        from `self.rng`, for env 0 .. n-1 in turn like the host lockstep path -- or, after `enable_explore_streams`, for every
-        environment from its own stream (a wave of k < n_envs rows advances the streams of those k only).  With an environment that is
-        reset on the device (`vec_env.enable_device_reset()`) the fused form issues ALL waves of the call as one launch
-        (hp_rollout_waves; `self.rollout_launches` says how many the launch cap made of it), calls no `vec_env.reset()` and hands
-        `success_out` one tensor of n_rollouts flags.  Returns a `DeviceEpisodes` handle for
-        `train_cycle` / `buffer.store_episode`; `.numpy()` gives the four arrays `collect_episodes` returns."""
+        vec_env.n_envs) on torch's current stream, no host copy and no host wait per timestep, in one of three forms with the
+        same bits; `self.rollout_form` / `self.rollout_reason` say which the call took and why, `self.rollout_launches` how many
+        launches a fused call was.
+          stepped (`_collect_wave_stepped`): waves of n_envs, T timesteps of two launches each (csrc/rollout.hip).
+          fused, one launch per wave (`_collect_wave_fused`): a native environment, a slab-shaped agent and draws that are
+            independent across environments (`device_env.fused_rollout_reason`).
+          fused, all waves in one launch (`_collect_all_waves`): the same with an environment that is reset on the device
+            (`vec_env.enable_device_reset()`); calls no `vec_env.reset()`, hands `success_out` one tensor of n_rollouts flags,
+            and the launch cap may make a few launches of it.
+        Exploration (:174-184, the +-0.15 clip from epoch 100) is drawn on the device from `self.rng`, for env 0 .. n-1 in turn
+        like the host lockstep path -- or, after `enable_explore_streams`, for every environment from its own stream (a wave of
+        k < n_envs rows advances the streams of those k only).  Returns a `DeviceEpisodes` handle for `train_cycle` /
+        `buffer.store_episode`; `.numpy()` gives the four arrays `collect_episodes` returns."""
         from .device_env import DeviceEpisodes, binomial1_qn, fused_rollout_reason
         vec_env = vec_env or self.vec_env
         n_total = int(n_rollouts or vec_env.n_envs)
-        T, ad = int(self.env_params['max_timesteps']), int(self.env_params['action'])
         eps = self._rollouts.get(n_total)
         if eps is None:
             eps = self._rollouts[n_total] = DeviceEpisodes(self.ctx, self.buffer._dev, n_total)
         qn = binomial1_qn(self.args.random_eps)[0] if explore else 1.0
         clip_abs = 0.15 if epoch >= 100 else 0.0                                  # ddpg_agent.py:118-119
         self._flush_updates()
-        done = 0
-        p = lambda t: C.c_void_p(t.data_ptr())
         streams = self.explore_streams
         if streams is not None and len(streams) != vec_env.n_envs:
             raise ValueError(f"collect_episodes_device: {len(streams)} exploration streams for {vec_env.n_envs} environments")
-        step, stream_h = ((self.lib.hp_rollout_step_streams, streams.h) if streams is not None
-                          else (self.lib.hp_rollout_step, self.rng.h))
         self.rollout_reason = fused_rollout_reason(getattr(vec_env, "is_native_device_env", False), self._slab_shaped(), explore,
                                                    streams is not None)
         self.rollout_form = 'fused' if self.rollout_reason is None else 'stepped'
         self.rollout_launches = 0 if self.rollout_form == 'fused' else None
-        reset_streams = getattr(vec_env, "reset_streams", None)
-        if self.rollout_form == 'fused' and reset_streams is not None:
-            # reset on the device: all waves of the call in one launch (or the few the launch cap dictates), no host reset
-            env = vec_env.env_desc()
-            success = torch.empty(n_total, dtype=torch.float32, device=vec_env.pos.device)
-            launches = C.c_int32()
-            with self.ctx.torch_bridge():
-                _lib.check(self.lib.hp_rollout_begin(eps.h, 0, n_total))
-                _lib.check(self.lib.hp_rollout_waves(eps.h, self.h, self.o_norm.h, self.g_norm.h,
-                                                     streams.h if streams is not None else None, reset_streams.h, C.byref(env),
-                                                     vec_env.n_envs, 1 if explore else 0, float(self.args.noise_eps),
-                                                     float(self.args.random_eps), qn, clip_abs, p(success), C.byref(launches)))
-            self.rollout_launches = int(launches.value)
-            vec_env.active = (n_total - 1) % vec_env.n_envs + 1      # the environments of the last wave
+        # what every entry takes behind its handles: the explore flag, the constants of _select_actions, the clip
+        how = (1 if explore else 0, float(self.args.noise_eps), float(self.args.random_eps), qn, clip_abs)
+        if self.rollout_form == 'fused' and getattr(vec_env, "reset_streams", None) is not None:
+            success = self._collect_all_waves(vec_env, eps, n_total, streams, how)
             if success_out is not None:
                 success_out.append(success)
             return eps
+        done = 0
         while done < n_total:
             k = min(vec_env.n_envs, n_total - done)
             o = vec_env.reset() if k == vec_env.n_envs else vec_env.reset(k)
             if self.rollout_form == 'fused':
-                desc = vec_env.native_desc()
-                env = _lib.EnvDesc(kind=int(desc["kind"]))
-                for i, v in enumerate(desc["params"]):
-                    env.params[i] = float(v)
-                for i, t in enumerate(desc["state"]):
-                    env.state_dev[i] = t.data_ptr()
-                success = torch.empty(k, dtype=torch.float32, device=o['observation'].device)
-                with self.ctx.torch_bridge():
-                    _lib.check(self.lib.hp_rollout_begin(eps.h, done, k))
-                    _lib.check(self.lib.hp_rollout_episodes(eps.h, self.h, self.o_norm.h, self.g_norm.h,
-                                                            streams.h if streams is not None else None, C.byref(env),
-                                                            1 if explore else 0, float(self.args.noise_eps),
-                                                            float(self.args.random_eps), qn, clip_abs, p(success)))
-                if success_out is not None:
-                    success_out.append(success)
-                self.rollout_launches += 1
-                done += k
-                continue
-            actions = torch.empty((k, ad), dtype=torch.float32, device=o['observation'].device)
-            with self.ctx.torch_bridge():       # the whole wave in torch's stream order, between the environment's own kernels
-                _lib.check(self.lib.hp_rollout_begin(eps.h, done, k))
-                for t in range(T):
-                    obs, ag, g = (o[key].contiguous() for key in ('observation', 'achieved_goal', 'desired_goal'))
-                    _lib.check(step(eps.h, self.h, self.o_norm.h, self.g_norm.h, stream_h, t, p(obs), p(ag), p(g),
-                                    1 if explore else 0, float(self.args.noise_eps), float(self.args.random_eps), qn, clip_abs,
-                                    p(actions)))
-                    o, _, _, info = vec_env.step(actions)
-                obs, ag = o['observation'].contiguous(), o['achieved_goal'].contiguous()
-                _lib.check(self.lib.hp_rollout_finish(eps.h, p(obs), p(ag)))
+                success = self._collect_wave_fused(vec_env, eps, done, k, streams, how)
+            else:
+                success = self._collect_wave_stepped(vec_env, eps, done, k, o, streams, how)
             if success_out is not None:
-                success_out.append(info['is_success'])
+                success_out.append(success)
             done += k
         if explore and streams is None:     # (the streams keep no host copy of their cached normals: nothing to invalidate)
             self.rng.mark_normals_drawn()
         return eps
+
+    def _collect_all_waves(self, vec_env, eps, n_total, streams, how):
+        """All `n_total` episodes as one launch (hp_rollout_waves), or the few the launch cap dictates; the environments are
+        reset inside it.  Returns the n_total success flags."""
+        env = vec_env.env_desc()
+        success = torch.empty(n_total, dtype=torch.float32, device=vec_env.device)
+        launches = C.c_int32()
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_rollout_begin(eps.h, 0, n_total))
+            _lib.check(self.lib.hp_rollout_waves(eps.h, self.h, self.o_norm.h, self.g_norm.h,
+                                                 streams.h if streams is not None else None, vec_env.reset_streams.h,
+                                                 C.byref(env), vec_env.n_envs, *how, C.c_void_p(success.data_ptr()),
+                                                 C.byref(launches)))
+        self.rollout_launches = int(launches.value)
+        vec_env.active = (n_total - 1) % vec_env.n_envs + 1      # the environments of the last wave
+        return success
+
+    def _collect_wave_fused(self, vec_env, eps, first, k, streams, how):
+        """Episodes [first, first + k) out of the k environments just reset, as one launch (hp_rollout_episodes).  Returns their
+        success flags."""
+        env = vec_env.env_desc()
+        success = torch.empty(k, dtype=torch.float32, device=vec_env.device)
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_rollout_begin(eps.h, first, k))
+            _lib.check(self.lib.hp_rollout_episodes(eps.h, self.h, self.o_norm.h, self.g_norm.h,
+                                                    streams.h if streams is not None else None, C.byref(env), *how,
+                                                    C.c_void_p(success.data_ptr())))
+        self.rollout_launches += 1
+        return success
+
+    def _collect_wave_stepped(self, vec_env, eps, first, k, o, streams, how):
+        """Episodes [first, first + k) out of the k environments just reset (`o`: what the reset returned), two launches per
+        timestep around `vec_env.step` and one closing record.  Returns the success flags of the last step."""
+        p = lambda t: C.c_void_p(t.data_ptr())
+        step, stream_h = ((self.lib.hp_rollout_step_streams, streams.h) if streams is not None
+                          else (self.lib.hp_rollout_step, self.rng.h))
+        actions = torch.empty((k, int(self.env_params['action'])), dtype=torch.float32, device=o['observation'].device)
+        with self.ctx.torch_bridge():       # the whole wave in torch's stream order, between the environment's own kernels
+            _lib.check(self.lib.hp_rollout_begin(eps.h, first, k))
+            for t in range(int(self.env_params['max_timesteps'])):
+                obs, ag, g = (o[key].contiguous() for key in ('observation', 'achieved_goal', 'desired_goal'))
+                _lib.check(step(eps.h, self.h, self.o_norm.h, self.g_norm.h, stream_h, t, p(obs), p(ag), p(g), *how, p(actions)))
+                o, _, _, info = vec_env.step(actions)
+            obs, ag = o['observation'].contiguous(), o['achieved_goal'].contiguous()
+            _lib.check(self.lib.hp_rollout_finish(eps.h, p(obs), p(ag)))
+        return info['is_success']
 
     def _slab_shaped(self):
         """Whether policy calls on this agent are the one-launch slab kernel (hp_agent_engine reports the 4x4x1 slab engine)."""
@@ -827,42 +836,41 @@ class ddpg_agent:
                 self.train_cycle(episodes)
                 if share:
                     np.random.set_state(self.rng.get_state())
-            self.ctx.synchronize()
-            self.check_exchange()
-            print(str(time.time() - start))
-            rate = self._eval_agent()
-            self.success_rates.append(rate)
-            if self.comm.rank == 0:
-                print('[{}] epoch is: {}, eval success rate is: {:.3f}'.format(datetime.now(), epoch, rate))
-                self.save_checkpoint()
-            if state_path:
-                self._save_epoch_state(state_path, epoch + 1)
+            self._finish_epoch(epoch, start, state_path)
+
+    def _finish_epoch(self, epoch, start, state_path, before_save=None):
+        """What closes an epoch of learn() on either path (:151-161): wait for its cycles, print the time they took, evaluate,
+        checkpoint on rank 0, and save the training state where one is asked for (`before_save()` first)."""
+        self.ctx.synchronize()
+        self.check_exchange()
+        print(str(time.time() - start))
+        rate = self._eval_agent()
+        self.success_rates.append(rate)
+        if self.comm.rank == 0:
+            print('[{}] epoch is: {}, eval success rate is: {:.3f}'.format(datetime.now(), epoch, rate))
+            self.save_checkpoint()
+        if state_path:
+            if before_save is not None:
+                before_save()
+            self._save_epoch_state(state_path, epoch + 1)
 
     def _learn_device(self, share, state_path, first_epoch):
         """learn() with a vectorised device environment: every draw of a cycle -- exploration, overflow slots, HER indices --
         comes from the device stream, so the single stream stays on the device for the whole run: numpy's state is handed over
         once here and handed back at the end and wherever a training state is saved (not twice per cycle), and nothing
         synchronises between the rollout and the learner phase of a cycle."""
+        def hand_back():
+            if share:
+                np.random.set_state(self.rng.get_state())
+
         if share:
             self.rng.set_state(np.random.get_state())
         for epoch in range(first_epoch, self.args.n_epochs):
             start = time.time()
             for _ in range(self.args.n_cycles):
                 self.train_cycle(self.collect_episodes_device(n_rollouts=self.args.num_rollouts_per_mpi, epoch=epoch))
-            self.ctx.synchronize()
-            self.check_exchange()
-            print(str(time.time() - start))
-            rate = self._eval_agent()
-            self.success_rates.append(rate)
-            if self.comm.rank == 0:
-                print('[{}] epoch is: {}, eval success rate is: {:.3f}'.format(datetime.now(), epoch, rate))
-                self.save_checkpoint()
-            if state_path:
-                if share:
-                    np.random.set_state(self.rng.get_state())
-                self._save_epoch_state(state_path, epoch + 1)
-        if share:
-            np.random.set_state(self.rng.get_state())
+            self._finish_epoch(epoch, start, state_path, before_save=hand_back)
+        hand_back()
 
     def _eval_agent_device(self):
         """_eval_agent on the device path: noise-free lockstep rollouts, the success flags of each wave's last step gathered on
@@ -874,6 +882,10 @@ class ddpg_agent:
             self.collect_episodes_device(n_rollouts=k, explore=False, success_out=flags)
             remaining -= k
         wins = torch.cat([f.reshape(-1).to(torch.float64) for f in flags]).cpu().numpy()
+        return self._success_rate(wins)
+
+    def _success_rate(self, wins):
+        """The mean of this rank's success flags, averaged over the ranks"""
         local = torch.tensor([float(np.mean(wins))], dtype=torch.float64)
         if self.comm.world_size > 1:
             local = local.to(f"cuda:{self.ctx.device_id}")
@@ -901,11 +913,7 @@ class ddpg_agent:
                     last[i] = float(info.get('is_success', last[i]))
             wins.extend(last)
             remaining -= len(envs)
-        local = torch.tensor([float(np.mean(wins))], dtype=torch.float64)
-        if self.comm.world_size > 1:
-            local = local.to(f"cuda:{self.ctx.device_id}")
-        self.comm.allreduce_mean_(local)
-        return float(local.item())
+        return self._success_rate(wins)
 
     def __del__(self):
         try:

@@ -38,7 +38,9 @@ few launches `_lib.ROLLOUT_MAX_LAUNCH_TIMESTEPS` dictates; `agent.rollout_launch
 Draw order with n environments: per timestep, for env i = 0 .. n-1: randn(action), uniform(action), binomial(1) -- the order of
 the host lockstep path (`collect_episodes` on a list of environments); with one environment it is the reference's own order.
 
-`PointMassVecEnv` is the tensor twin of `synthetic.PointMassGoalEnv`, `PushBlockVecEnv` that of `synthetic.PushBlockGoalEnv`.
+`PointMassVecEnv` is the tensor twin of `synthetic.PointMassGoalEnv`, `PushBlockVecEnv` that of `synthetic.PushBlockGoalEnv`; what
+they share (`_GoalVecEnv`) includes the rule that an environment works on the first `active` rows of its state tensors.  A native
+class is one of them behind `_NativeEnv` -- descriptor, device reset -- plus the constant of its kind.
 """
 from __future__ import annotations
 
@@ -117,16 +119,15 @@ class DeviceEpisodes:
             pass
 
 
-class PointMassVecEnv:
-    """n `synthetic.PointMassGoalEnv`s as tensors: env i resets from RandomState(seed + i) on the host (one upload per episode),
-    `step` is elementwise float64 torch -- multiply and add as separate ops, so the bits are the host environment's.  Works with
-    device="cpu" too."""
+class _GoalVecEnv:
+    """What the vectorised environments share: n environments as float64 tensors, env i reset from RandomState(seed + i) on the
+    host; `reset`, `step` and `_observation` of a subclass work on the first `active` rows of its state tensors, in place -- all
+    of them unless the tensors were widened to n_envs rows for good (`_NativeEnv.enable_device_reset`).  A subclass has
+    `state_names`, the attributes that hold the state tensors (`goal` among them), and `_observation()`."""
 
     is_device_vec_env = True
-    state_names = ("pos", "vel", "goal")     # the attributes that hold the state tensors
 
-    def __init__(self, n_envs, seed=0, device="cuda", max_timesteps=100, distance_threshold=0.05, reward_type='sparse',
-                 step_scale=0.1):
+    def __init__(self, n_envs, seed, device, max_timesteps, distance_threshold, reward_type, step_scale):
         self.n_envs = int(n_envs)
         self.device = torch.device(device)
         self.rs = [np.random.RandomState(seed + i) for i in range(self.n_envs)]
@@ -135,36 +136,23 @@ class PointMassVecEnv:
         self.reward_type = reward_type
         self.step_scale = float(step_scale)
         self.active = self.n_envs
-        z = torch.zeros((self.n_envs, 3), dtype=torch.float64, device=self.device)
-        self.pos, self.vel, self.goal = z, z.clone(), z.clone()
 
     @property
     def env_params(self):
         return {'obs': 27, 'goal': 3, 'action': 4, 'action_max': 0.5, 'max_timesteps': self.max_timesteps}
 
-    def _observation(self):
-        n = self.pos.shape[0]
-        obs = torch.zeros((n, 27), dtype=torch.float64, device=self.device)
-        obs[:, 0:3] = self.pos
-        obs[:, 3:6] = self.vel
-        obs[:, 12:15] = self.pos
-        return {'observation': obs, 'achieved_goal': self.pos.clone(), 'desired_goal': self.goal.clone()}
-
-    def reset(self, n_active=None):
-        """Reset the first `n_active` environments (default: all) -- only those draw from their streams, like the host lockstep
-        path, which resets only the environments of the wave -- and step those from now on."""
+    def _n_active(self, n_active):
+        """The `n_active` of a reset (default: all environments), validated"""
         k = self.n_envs if n_active is None else int(n_active)
         if not 0 < k <= self.n_envs:
             raise ValueError("n_active outside [1, n_envs]")
-        both = np.empty((2, k, 3))
-        for i in range(k):
-            both[0, i] = self.rs[i].uniform(0.0, 0.5, 3)
-            both[1, i] = self.rs[i].uniform(0.0, 0.5, 3)
-        dev = torch.from_numpy(both).to(self.device)
-        self.pos, self.goal = dev[0].contiguous(), dev[1].contiguous()
-        self.vel = torch.zeros_like(self.pos)
-        self.active = k
-        return self._observation()
+        return k
+
+    def _rows(self, *names):
+        """The first `active` rows of the named state tensors -- the tensors themselves where that is all their rows, which
+        spares the per-step path (host-bound: a dozen small kernels per timestep) one slice per tensor and call"""
+        k = self.active
+        return [t if t.shape[0] == k else t[:k] for t in (getattr(self, name) for name in names)]
 
     def _distance(self, a, b):
         d = a - b
@@ -182,24 +170,164 @@ class PointMassVecEnv:
             return -(d > self.distance_threshold).to(torch.float32)
         return -d
 
+    def _stepped(self):
+        """What `step` returns, out of the state it has just written"""
+        goal, = self._rows("goal")
+        observation = self._observation()
+        success = (self._distance(observation['achieved_goal'], goal) < self.distance_threshold).to(torch.float32)
+        info = {'is_success': success}
+        return observation, self.compute_reward(observation['achieved_goal'], goal, info), False, info
+
+
+class PointMassVecEnv(_GoalVecEnv):
+    """n `synthetic.PointMassGoalEnv`s as tensors: env i resets from RandomState(seed + i) on the host (one upload per episode),
+    `step` is elementwise float64 torch -- multiply and add as separate ops, so the bits are the host environment's.  State:
+    `pos`, `vel`, `goal` [rows, 3].  Works with device="cpu" too."""
+
+    state_names = ("pos", "vel", "goal")     # the attributes that hold the state tensors
+
+    def __init__(self, n_envs, seed=0, device="cuda", max_timesteps=100, distance_threshold=0.05, reward_type='sparse',
+                 step_scale=0.1):
+        super().__init__(n_envs, seed, device, max_timesteps, distance_threshold, reward_type, step_scale)
+        z = torch.zeros((self.n_envs, 3), dtype=torch.float64, device=self.device)
+        self.pos, self.vel, self.goal = z, z.clone(), z.clone()
+
+    def params(self):
+        """hp_env_desc.params of the kind"""
+        return [self.step_scale, self.distance_threshold]
+
+    def _observation(self):
+        pos, vel, goal = self._rows("pos", "vel", "goal")
+        obs = torch.zeros((self.active, 27), dtype=torch.float64, device=self.device)
+        obs[:, 0:3] = pos
+        obs[:, 3:6] = vel
+        obs[:, 12:15] = pos
+        return {'observation': obs, 'achieved_goal': pos.clone(), 'desired_goal': goal.clone()}
+
+    def reset(self, n_active=None):
+        """Reset the first `n_active` environments (default: all) -- only those draw from their streams, like the host lockstep
+        path, which resets only the environments of the wave -- and step those from now on."""
+        k = self._n_active(n_active)
+        both = np.empty((2, k, 3))
+        for i in range(k):
+            both[0, i] = self.rs[i].uniform(0.0, 0.5, 3)
+            both[1, i] = self.rs[i].uniform(0.0, 0.5, 3)
+        dev = torch.from_numpy(both).to(self.device)
+        self.pos, self.goal = dev[0].contiguous(), dev[1].contiguous()
+        self.vel = torch.zeros_like(self.pos)
+        self.active = k
+        return self._observation()
+
     def step(self, actions):
+        pos, vel = self._rows("pos", "vel")
         a = torch.clamp(actions.to(torch.float64), -0.5, 0.5)
         scaled = self.step_scale * a[:, :3]                 # multiply, then add: two roundings, like numpy
-        new = torch.clamp(self.pos + scaled, 0.0, 0.5)
-        self.vel = new - self.pos
-        self.pos = new
-        observation = self._observation()
-        success = (self._distance(observation['achieved_goal'], self.goal) < self.distance_threshold).to(torch.float32)
-        info = {'is_success': success}
-        return observation, self.compute_reward(observation['achieved_goal'], self.goal, info), False, info
+        new = torch.clamp(pos + scaled, 0.0, 0.5)
+        torch.sub(new, pos, out=vel)                        # vel = new - pos, then pos = new: written into the rows
+        pos.copy_(new)
+        return self._stepped()
+
+
+class PushBlockVecEnv(_GoalVecEnv):
+    """n `synthetic.PushBlockGoalEnv`s as tensors: env i resets from RandomState(seed + i) on the host -- the same rejection loop,
+    four scalars per attempt -- and `step` is the host environment's operations elementwise in float64, one torch op per
+    rounding, `torch.where` for its branches.  State: `grip`, `blk`, `goal` [rows, 3] and `vel` [rows, 6] (gripper, then block).
+    Works with device="cpu" too."""
+
+    state_names = ("grip", "blk", "goal", "vel")
+
+    def __init__(self, n_envs, seed=0, device="cuda", max_timesteps=100, distance_threshold=0.05, reward_type='sparse',
+                 step_scale=0.1, half_width=0.04, z_touch=0.25, min_separation=0.15, table_z=0.2, grip_start=(0.25, 0.1)):
+        super().__init__(n_envs, seed, device, max_timesteps, distance_threshold, reward_type, step_scale)
+        self.half_width, self.z_touch = float(half_width), float(z_touch)
+        self.min_separation, self.table_z = float(min_separation), float(table_z)
+        self.grip_start = (float(grip_start[0]), float(grip_start[1]))
+        self.reset_attempts = [0] * self.n_envs      # attempts the last host reset of each environment took
+        z = torch.zeros((self.n_envs, 3), dtype=torch.float64, device=self.device)
+        self.grip, self.blk, self.goal = z, z.clone(), z.clone()
+        self.vel = torch.zeros((self.n_envs, 6), dtype=torch.float64, device=self.device)
+
+    @property
+    def pos(self):
+        """The gripper's position (nothing in the package reads it)."""
+        return self.grip
+
+    def params(self):
+        """hp_env_desc.params of the kind"""
+        return [self.step_scale, self.distance_threshold, self.half_width, self.z_touch, self.min_separation, self.table_z,
+                self.grip_start[0], self.grip_start[1]]
+
+    def _observation(self):
+        k = self.active
+        grip, blk, vel = self.grip[:k], self.blk[:k], self.vel[:k]
+        obs = torch.zeros((k, 27), dtype=torch.float64, device=self.device)
+        obs[:, 0:3] = grip
+        obs[:, 6:9] = vel[:, 0:3]
+        obs[:, 12:15] = blk
+        obs[:, 18:21] = blk - grip
+        obs[:, 21:24] = vel[:, 3:6]
+        return {'observation': obs, 'achieved_goal': blk.clone(), 'desired_goal': self.goal[:k].clone()}
+
+    def reset(self, n_active=None):
+        """Reset the first `n_active` environments (default: all): only those draw from their streams."""
+        k = self._n_active(n_active)
+        fresh = np.empty((3, k, 3))
+        for i in range(k):
+            for attempt in range(PUSH_RESET_ATTEMPTS):
+                bx, by, gx, gy = (self.rs[i].uniform(low, high) for low, high in PUSH_RESET_BOUNDS)
+                ddx, ddy = bx - gx, by - gy
+                if np.sqrt(ddx * ddx + ddy * ddy) >= self.min_separation:
+                    break
+            self.reset_attempts[i] = attempt + 1
+            fresh[0, i] = (self.grip_start[0], self.grip_start[1], PUSH_START_Z)
+            fresh[1, i] = (bx, by, self.table_z)
+            fresh[2, i] = (gx, gy, self.table_z)
+        dev = torch.from_numpy(fresh).to(self.device)
+        self.grip, self.blk, self.goal = dev[0].contiguous(), dev[1].contiguous(), dev[2].contiguous()
+        self.vel = torch.zeros((k, 6), dtype=torch.float64, device=self.device)
+        self.active = k
+        return self._observation()
+
+    def step(self, actions):
+        k, r = self.active, self.half_width
+        grip, blk = self.grip[:k], self.blk[:k]
+        lo = torch.tensor([PUSH_X_LO, PUSH_Y_LO, self.table_z], dtype=torch.float64, device=self.device)
+        hi = torch.tensor([PUSH_X_HI, PUSH_Y_HI, PUSH_Z_HI], dtype=torch.float64, device=self.device)
+        a = torch.clamp(actions.to(torch.float64), -0.5, 0.5)
+        scaled = self.step_scale * a[:, :3]                 # multiply, then add: two roundings, like numpy
+        new = torch.minimum(torch.maximum(grip + scaled, lo), hi)
+        gvel = new - grip
+        dx, dy = blk[:, 0] - new[:, 0], blk[:, 1] - new[:, 1]
+        adx, ady = dx.abs(), dy.abs()
+        contact = (new[:, 2] < self.z_touch) & (adx < r) & (ady < r)
+        along_x = (r - adx) <= (r - ady)                    # the axis of least penetration
+        plus, minus = torch.full_like(dx, r), torch.full_like(dx, -r)
+        bx = torch.where(contact & along_x, new[:, 0] + torch.where(dx >= 0, plus, minus), blk[:, 0])
+        by = torch.where(contact & ~along_x, new[:, 1] + torch.where(dy >= 0, plus, minus), blk[:, 1])
+        bx = torch.where(contact, torch.clamp(bx, PUSH_X_LO, PUSH_X_HI), bx)
+        by = torch.where(contact, torch.clamp(by, PUSH_Y_LO, PUSH_Y_HI), by)
+        moved = torch.stack([bx, by, blk[:, 2]], dim=1)
+        bvel = moved - blk
+        self.grip[:k], self.blk[:k] = new, moved
+        self.vel[:k, 0:3], self.vel[:k, 3:6] = gvel, bvel
+        return self._stepped()
 
 
 class _NativeEnv:
-    """What the native environments share: the descriptor as the library's struct, and the switch to reset on the device.  The
-    class it is mixed into has `state_names`, `native_desc()`, `rs`, `n_envs`, `device` and `active`."""
+    """What the native environments share: the descriptor, and the switch to reset on the device.  Mixed in before a
+    `_GoalVecEnv` that has `params()`; the subclass names the library's kind."""
 
     is_native_device_env = True
+    kind = None              # _lib.ENV_*: the struct of csrc/env_device.h that evaluates the same float64 operations
     reset_streams = None     # random.DeviceRandomStreams after enable_device_reset(): reset stream i = the state of rs[i]
+
+    def native_desc(self):
+        """hp_env_desc of the environments stepped now: kind, `params()`, and the state tensors in the order of `state_names`
+        (float64, made contiguous; a launch reads all of them and writes them in place).  They have `active` rows, or n_envs
+        rows for good with device reset -- the environments stepped now are then their first `active` rows."""
+        for name in self.state_names:
+            setattr(self, name, getattr(self, name).contiguous())
+        return {"kind": self.kind, "params": self.params(), "state": [getattr(self, name) for name in self.state_names]}
 
     def env_desc(self):
         """`native_desc()` as the library's struct (hp_env_desc)."""
@@ -234,11 +362,12 @@ class _NativeEnv:
         self.reset_streams = streams
         return streams
 
-    def _reset_on_device(self, n_active):
-        """`reset(n_active)` as one launch (hp_env_reset) on torch's current stream, in order with the environment's own kernels"""
-        k = self.n_envs if n_active is None else int(n_active)
-        if not 0 < k <= self.n_envs:
-            raise ValueError("n_active outside [1, n_envs]")
+    def reset(self, n_active=None):
+        """The host reset -- or, after `enable_device_reset`, one launch (hp_env_reset) on torch's current stream, in order with
+        the environment's own kernels"""
+        if self.reset_streams is None:
+            return super().reset(n_active)
+        k = self._n_active(n_active)
         env = self.env_desc()
         with self.ctx.torch_bridge():
             _lib.check(self.ctx.lib.hp_env_reset(self.ctx.h, C.byref(env), self.reset_streams.h, k))
@@ -248,150 +377,10 @@ class _NativeEnv:
 
 class NativePointMassVecEnv(_NativeEnv, PointMassVecEnv):
     """`PointMassVecEnv` whose dynamics the library also evaluates itself (PointMassEnvDev, csrc/env_device.h: the same float64
-    operations, one by one): `collect_episodes_device` collects a wave of its episodes in one launch.  `reset` and `step` are the
-    parent's, so the per-step protocol works on it unchanged -- and with device="cpu" it is simply the parent."""
+    operations, one by one): `collect_episodes_device` collects a wave of its episodes in one launch.  `step` is the parent's,
+    so the per-step protocol works on it unchanged -- and with device="cpu" it is simply the parent."""
 
-    def native_desc(self):
-        """hp_env_desc of the environments stepped now: kind, params [step_scale, distance_threshold], state [pos, vel, goal]
-        (float64 [active, 3] each, contiguous; the launch reads all three and writes them in place).  With device reset the
-        tensors are [n_envs, 3] for good and the environments stepped now are their first `active` rows."""
-        self.pos, self.vel, self.goal = self.pos.contiguous(), self.vel.contiguous(), self.goal.contiguous()
-        return {"kind": _lib.ENV_POINT_MASS, "params": [self.step_scale, self.distance_threshold],
-                "state": [self.pos, self.vel, self.goal]}
-
-    def _observation(self):
-        if self.reset_streams is None:
-            return super()._observation()
-        k = self.active
-        obs = torch.zeros((k, 27), dtype=torch.float64, device=self.device)
-        obs[:, 0:3] = self.pos[:k]
-        obs[:, 3:6] = self.vel[:k]
-        obs[:, 12:15] = self.pos[:k]
-        return {'observation': obs, 'achieved_goal': self.pos[:k].clone(), 'desired_goal': self.goal[:k].clone()}
-
-    def reset(self, n_active=None):
-        if self.reset_streams is None:
-            return super().reset(n_active)
-        return self._reset_on_device(n_active)
-
-    def step(self, actions):
-        if self.reset_streams is None:
-            return super().step(actions)
-        k = self.active
-        a = torch.clamp(actions.to(torch.float64), -0.5, 0.5)
-        scaled = self.step_scale * a[:, :3]                 # the parent's operations on the first `active` rows, in place
-        new = torch.clamp(self.pos[:k] + scaled, 0.0, 0.5)
-        self.vel[:k] = new - self.pos[:k]
-        self.pos[:k] = new
-        observation = self._observation()
-        success = (self._distance(observation['achieved_goal'], self.goal[:k]) < self.distance_threshold).to(torch.float32)
-        info = {'is_success': success}
-        return observation, self.compute_reward(observation['achieved_goal'], self.goal[:k], info), False, info
-
-
-class PushBlockVecEnv:
-    """n `synthetic.PushBlockGoalEnv`s as tensors: env i resets from RandomState(seed + i) on the host -- the same rejection loop,
-    four scalars per attempt -- and `step` is the host environment's operations elementwise in float64, one torch op per
-    rounding, `torch.where` for its branches.  State: `grip`, `blk`, `goal` [rows, 3] and `vel` [rows, 6] (gripper, then block);
-    `reset`, `step` and `_observation` work on the first `active` rows, which are all of them unless the tensors were widened to
-    n_envs rows for good (`NativePushBlockVecEnv.enable_device_reset`).  Works with device="cpu" too."""
-
-    is_device_vec_env = True
-    state_names = ("grip", "blk", "goal", "vel")
-
-    def __init__(self, n_envs, seed=0, device="cuda", max_timesteps=100, distance_threshold=0.05, reward_type='sparse',
-                 step_scale=0.1, half_width=0.04, z_touch=0.25, min_separation=0.15, table_z=0.2, grip_start=(0.25, 0.1)):
-        self.n_envs = int(n_envs)
-        self.device = torch.device(device)
-        self.rs = [np.random.RandomState(seed + i) for i in range(self.n_envs)]
-        self.max_timesteps = int(max_timesteps)
-        self.distance_threshold = float(distance_threshold)
-        self.reward_type = reward_type
-        self.step_scale, self.half_width, self.z_touch = float(step_scale), float(half_width), float(z_touch)
-        self.min_separation, self.table_z = float(min_separation), float(table_z)
-        self.grip_start = (float(grip_start[0]), float(grip_start[1]))
-        self.active = self.n_envs
-        self.reset_attempts = [0] * self.n_envs      # attempts the last host reset of each environment took
-        z = torch.zeros((self.n_envs, 3), dtype=torch.float64, device=self.device)
-        self.grip, self.blk, self.goal = z, z.clone(), z.clone()
-        self.vel = torch.zeros((self.n_envs, 6), dtype=torch.float64, device=self.device)
-
-    @property
-    def env_params(self):
-        return {'obs': 27, 'goal': 3, 'action': 4, 'action_max': 0.5, 'max_timesteps': self.max_timesteps}
-
-    @property
-    def pos(self):
-        """The gripper's position: the tensor `collect_episodes_device` takes the environment's device from."""
-        return self.grip
-
-    def params(self):
-        """hp_env_desc.params of the kind"""
-        return [self.step_scale, self.distance_threshold, self.half_width, self.z_touch, self.min_separation, self.table_z,
-                self.grip_start[0], self.grip_start[1]]
-
-    def _observation(self):
-        k = self.active
-        grip, blk, vel = self.grip[:k], self.blk[:k], self.vel[:k]
-        obs = torch.zeros((k, 27), dtype=torch.float64, device=self.device)
-        obs[:, 0:3] = grip
-        obs[:, 6:9] = vel[:, 0:3]
-        obs[:, 12:15] = blk
-        obs[:, 18:21] = blk - grip
-        obs[:, 21:24] = vel[:, 3:6]
-        return {'observation': obs, 'achieved_goal': blk.clone(), 'desired_goal': self.goal[:k].clone()}
-
-    def reset(self, n_active=None):
-        """Reset the first `n_active` environments (default: all): only those draw from their streams."""
-        k = self.n_envs if n_active is None else int(n_active)
-        if not 0 < k <= self.n_envs:
-            raise ValueError("n_active outside [1, n_envs]")
-        fresh = np.empty((3, k, 3))
-        for i in range(k):
-            for attempt in range(PUSH_RESET_ATTEMPTS):
-                bx, by, gx, gy = (self.rs[i].uniform(low, high) for low, high in PUSH_RESET_BOUNDS)
-                ddx, ddy = bx - gx, by - gy
-                if np.sqrt(ddx * ddx + ddy * ddy) >= self.min_separation:
-                    break
-            self.reset_attempts[i] = attempt + 1
-            fresh[0, i] = (self.grip_start[0], self.grip_start[1], PUSH_START_Z)
-            fresh[1, i] = (bx, by, self.table_z)
-            fresh[2, i] = (gx, gy, self.table_z)
-        dev = torch.from_numpy(fresh).to(self.device)
-        self.grip, self.blk, self.goal = dev[0].contiguous(), dev[1].contiguous(), dev[2].contiguous()
-        self.vel = torch.zeros((k, 6), dtype=torch.float64, device=self.device)
-        self.active = k
-        return self._observation()
-
-    _distance = PointMassVecEnv._distance
-    compute_reward = PointMassVecEnv.compute_reward
-
-    def step(self, actions):
-        k, r = self.active, self.half_width
-        grip, blk = self.grip[:k], self.blk[:k]
-        lo = torch.tensor([PUSH_X_LO, PUSH_Y_LO, self.table_z], dtype=torch.float64, device=self.device)
-        hi = torch.tensor([PUSH_X_HI, PUSH_Y_HI, PUSH_Z_HI], dtype=torch.float64, device=self.device)
-        a = torch.clamp(actions.to(torch.float64), -0.5, 0.5)
-        scaled = self.step_scale * a[:, :3]                 # multiply, then add: two roundings, like numpy
-        new = torch.minimum(torch.maximum(grip + scaled, lo), hi)
-        gvel = new - grip
-        dx, dy = blk[:, 0] - new[:, 0], blk[:, 1] - new[:, 1]
-        adx, ady = dx.abs(), dy.abs()
-        contact = (new[:, 2] < self.z_touch) & (adx < r) & (ady < r)
-        along_x = (r - adx) <= (r - ady)                    # the axis of least penetration
-        plus, minus = torch.full_like(dx, r), torch.full_like(dx, -r)
-        bx = torch.where(contact & along_x, new[:, 0] + torch.where(dx >= 0, plus, minus), blk[:, 0])
-        by = torch.where(contact & ~along_x, new[:, 1] + torch.where(dy >= 0, plus, minus), blk[:, 1])
-        bx = torch.where(contact, torch.clamp(bx, PUSH_X_LO, PUSH_X_HI), bx)
-        by = torch.where(contact, torch.clamp(by, PUSH_Y_LO, PUSH_Y_HI), by)
-        moved = torch.stack([bx, by, blk[:, 2]], dim=1)
-        bvel = moved - blk
-        self.grip[:k], self.blk[:k] = new, moved
-        self.vel[:k, 0:3], self.vel[:k, 3:6] = gvel, bvel
-        observation = self._observation()
-        success = (self._distance(observation['achieved_goal'], self.goal[:k]) < self.distance_threshold).to(torch.float32)
-        info = {'is_success': success}
-        return observation, self.compute_reward(observation['achieved_goal'], self.goal[:k], info), False, info
+    kind = _lib.ENV_POINT_MASS
 
 
 class NativePushBlockVecEnv(_NativeEnv, PushBlockVecEnv):
@@ -400,14 +389,4 @@ class NativePushBlockVecEnv(_NativeEnv, PushBlockVecEnv):
     `enable_device_reset()` the rejection loop of its reset runs on the device too -- every environment for as many attempts as its
     own draws ask for.  `step` is the parent's, so the per-step protocol works on it unchanged."""
 
-    def native_desc(self):
-        """hp_env_desc of the environments stepped now: kind, the eight params, state [grip, blk, goal, vel] (float64, contiguous;
-        the launch reads all four and writes them in place): [active, 3] and [active, 6], or n_envs rows with device reset."""
-        for name in self.state_names:
-            setattr(self, name, getattr(self, name).contiguous())
-        return {"kind": _lib.ENV_PUSH_BLOCK, "params": self.params(), "state": [getattr(self, name) for name in self.state_names]}
-
-    def reset(self, n_active=None):
-        if self.reset_streams is None:
-            return super().reset(n_active)
-        return self._reset_on_device(n_active)
+    kind = _lib.ENV_PUSH_BLOCK

@@ -7,7 +7,8 @@ import pytest
 import torch
 
 from conftest import bits
-from rl_arm_under_sparse_reward_amd.device_env import PointMassVecEnv, binomial1_qn, wave_layout
+from rl_arm_under_sparse_reward_amd.device_env import (NativePointMassVecEnv, NativePushBlockVecEnv, PointMassVecEnv, binomial1_qn,
+                                                       wave_layout)
 from rl_arm_under_sparse_reward_amd.feeder import _Layout
 from rl_arm_under_sparse_reward_amd.synthetic import PointMassGoalEnv
 
@@ -53,6 +54,54 @@ def test_partial_wave_resets_only_the_first_environments():
     assert o["observation"].shape == (2, 27)
     want = PointMassGoalEnv(seed=7)
     assert np.array_equal(vec.reset()["achieved_goal"].numpy()[2], want.reset()["achieved_goal"])   # env 2 untouched by the wave of 2
+
+
+def test_point_mass_works_on_the_first_active_rows_of_wider_state_tensors():
+    """The rule of the shared base, on the plain class: with state tensors widened to n_envs rows (what `enable_device_reset` does
+    to a native environment) and `active` = 3, `step` and `_observation` read and write rows 0-2 in place, leave rows 3-4 alone,
+    and give the bits of a 3-environment `PointMassVecEnv` handed the same actions."""
+    n, k, seed = 5, 3, 9
+    wide, ref = PointMassVecEnv(n, seed=seed, device="cpu"), PointMassVecEnv(k, seed=seed, device="cpu")
+    o_w, o_r = wide.reset(k), ref.reset()
+    sentinel = {}
+    for j, name in enumerate(wide.state_names):
+        t = getattr(wide, name)
+        f = torch.full((n, 3), -7.0 - j, dtype=torch.float64)
+        f[:k] = t
+        setattr(wide, name, f)
+        sentinel[name] = f[k:].clone()
+    wide.active = k
+    o_w = wide._observation()
+    tensors = {name: getattr(wide, name) for name in wide.state_names}
+    rs = np.random.RandomState(4)
+    for t in range(12):
+        for key in ("observation", "achieved_goal", "desired_goal"):
+            assert o_w[key].shape[0] == k and o_w[key].is_contiguous()
+            assert np.array_equal(bits(o_w[key].numpy()), bits(o_r[key].numpy())), (t, key)
+        a = torch.from_numpy((rs.uniform(-0.7, 0.7, (k, 4)) * (1.0 if t % 5 else 30.0)).astype(np.float32))   # some steps hit the walls
+        (o_w, r_w, _, i_w), (o_r, r_r, _, i_r) = wide.step(a), ref.step(a)
+        assert r_w.shape == (k,) and torch.equal(r_w, r_r) and torch.equal(i_w["is_success"], i_r["is_success"])
+        for name in wide.state_names:
+            w = getattr(wide, name)
+            assert w is tensors[name] and tuple(w.shape) == (n, 3), name                 # in place: the same tensors, still wide
+            assert np.array_equal(bits(w[:k].numpy()), bits(getattr(ref, name).numpy())), (t, name)
+            assert np.array_equal(bits(w[k:].numpy()), bits(sentinel[name].numpy())), (t, name)
+    assert float(wide.vel[:k].abs().sum()) > 0       # the rows did move
+
+
+def test_a_native_class_is_its_kind_and_nothing_else():
+    """What keeps the duplication from growing back: the native classes inherit reset, step, the observation and the descriptor
+    (`_NativeEnv`, the vectorised parent) and define only their kind."""
+    for cls, kind in ((NativePointMassVecEnv, 1), (NativePushBlockVecEnv, 2)):
+        assert not {"reset", "step", "_observation", "native_desc"} & set(vars(cls)), sorted(vars(cls))
+        assert vars(cls)["kind"] == kind
+        env = cls(3, seed=2, device="cpu")
+        env.reset(2)
+        d = env.native_desc()
+        assert d["kind"] == kind and d["params"] == env.params()
+        assert [t is getattr(env, name) and t.is_contiguous() for t, name in zip(d["state"], env.state_names)] == [True] * len(env.state_names)
+        with pytest.raises(ValueError, match=r"n_active outside \[1, n_envs\]"):
+            env.reset(4)
 
 
 @pytest.mark.parametrize("shape", [(2, 100, 27, 3, 4), (7, 13, 10, 2, 3)])

@@ -40,11 +40,12 @@ def test_abi_table_and_header_carry_the_entry_points():
 
 
 def test_the_wave_loop_kernel_uses_no_scratch(tmp_path):
-    """The device assembly of csrc/rollout.hip, compiled as the Makefile compiles it: the kernel that runs the wave loop is the one
-    instantiation of k_rollout_episodes, with private_segment_fixed_size 0, no spilled vector register and LDS within the 160 KiB
-    of a CU; the stand-alone reset kernel has no scratch either."""
+    """The device assembly of csrc/env_point_mass.hip (the unit that instantiates the point mass's kernels), compiled as the Makefile
+    compiles it: the kernel that runs the wave loop is the one instantiation of k_rollout_episodes, with private_segment_fixed_size
+    0, no spilled vector register and LDS within the 160 KiB of a CU; the stand-alone reset kernel has no scratch either."""
     csrc = os.path.join(REPO, "rl_arm_under_sparse_reward_amd", "csrc")
     mk = open(os.path.join(csrc, "Makefile")).read()
+    assert "env_point_mass.hip" in re.search(r"^EXACT_SRCS := (.*)$", mk, flags=re.M).group(1).split()
     hipcc = re.search(r"^HIPCC \?= (\S+)", mk, flags=re.M).group(1)
     if not os.path.exists(hipcc):
         hipcc = shutil.which("hipcc")
@@ -52,8 +53,8 @@ def test_the_wave_loop_kernel_uses_no_scratch(tmp_path):
     common = re.search(r"^COMMON := (.*)$", mk, flags=re.M).group(1)
     exact = re.search(r"^EXACT := (.*)$", mk, flags=re.M).group(1)
     flags = common.replace("$(ARCH)", "gfx950").replace("$(INC)", f"-I{os.path.join(REPO, 'include')} -I{csrc}").split()
-    out = tmp_path / "rollout.s"
-    subprocess.check_call([hipcc, *flags, *exact.split(), "--cuda-device-only", "-S", os.path.join(csrc, "rollout.hip"), "-o", str(out)])
+    out = tmp_path / "env_point_mass.s"
+    subprocess.check_call([hipcc, *flags, *exact.split(), "--cuda-device-only", "-S", os.path.join(csrc, "env_point_mass.hip"), "-o", str(out)])
     meta = {}
     for block in out.read_text().split("- .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)
@@ -61,9 +62,12 @@ def test_the_wave_loop_kernel_uses_no_scratch(tmp_path):
                       for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count")}
     fused = [k for k in meta if "k_rollout_episodes" in k]
     assert len(fused) == 1 and "PointMassEnvDev" in fused[0], sorted(meta)
-    # the wave loop lives in that kernel: the host entry of hp_rollout_waves launches it and no other
+    # the wave loop lives in that kernel: the host entry of hp_rollout_waves (rollout.hip) launches it and no other, through the
+    # one launch of the kind's table row (env_kind_entry, rollout_episodes.h)
     src = open(os.path.join(csrc, "rollout.hip")).read()
-    assert len(re.findall(r"hipLaunchKernelGGL\(k_rollout_episodes<", src)) == 1 and "A.waves" in src
+    units = src + open(os.path.join(csrc, "rollout_episodes.h")).read() + open(os.path.join(csrc, "env_point_mass.hip")).read()
+    assert len(re.findall(r"hipLaunchKernelGGL\(k_rollout_episodes<", units)) == 1 and "A.waves" in src
+    assert "kind->launch_episodes" in src
     m = meta[fused[0]]
     print("k_rollout_episodes:", m)
     assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, m

@@ -61,7 +61,8 @@ def test_abi_table_and_header_carry_the_entry_point():
 
 
 def test_the_fused_kernel_uses_no_scratch(tmp_path):
-    """The device assembly of csrc/rollout.hip, compiled as the Makefile compiles it: k_rollout_episodes has
+    """The device assembly of csrc/env_point_mass.hip (the unit that instantiates the point mass's kernels), compiled as the Makefile
+    compiles it: k_rollout_episodes has
     private_segment_fixed_size 0 and no spilled vector register, and its LDS fits the 160 KiB of a CU."""
     csrc = os.path.join(REPO, "rl_arm_under_sparse_reward_amd", "csrc")
     mk = open(os.path.join(csrc, "Makefile")).read()
@@ -72,8 +73,8 @@ def test_the_fused_kernel_uses_no_scratch(tmp_path):
     common = re.search(r"^COMMON := (.*)$", mk, flags=re.M).group(1)
     exact = re.search(r"^EXACT := (.*)$", mk, flags=re.M).group(1)
     flags = common.replace("$(ARCH)", "gfx950").replace("$(INC)", f"-I{os.path.join(REPO, 'include')} -I{csrc}").split()
-    out = tmp_path / "rollout.s"
-    subprocess.check_call([hipcc, *flags, *exact.split(), "--cuda-device-only", "-S", os.path.join(csrc, "rollout.hip"), "-o", str(out)])
+    out = tmp_path / "env_point_mass.s"
+    subprocess.check_call([hipcc, *flags, *exact.split(), "--cuda-device-only", "-S", os.path.join(csrc, "env_point_mass.hip"), "-o", str(out)])
     meta = {}
     for block in out.read_text().split("- .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)

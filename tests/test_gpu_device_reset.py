@@ -9,10 +9,13 @@ import pytest
 import torch
 
 from conftest import bits
+from gpu_common import fresh_rng
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd import train_state as ts
-from rl_arm_under_sparse_reward_amd.ddpg_agent import NET_ACTOR, NET_CRITIC
-from rl_arm_under_sparse_reward_amd.device_env import DeviceEpisodes, NativePointMassVecEnv, PointMassVecEnv, binomial1_qn
+from rl_arm_under_sparse_reward_amd.arguments import Args
+from rl_arm_under_sparse_reward_amd.ddpg_agent import NET_ACTOR, NET_CRITIC, ddpg_agent
+from rl_arm_under_sparse_reward_amd.device_env import (DeviceEpisodes, NativePointMassVecEnv, NativePushBlockVecEnv, PointMassVecEnv,
+                                                       binomial1_qn)
 from rl_arm_under_sparse_reward_amd.random import DeviceRandomStreams
 from test_gpu_device_rollout import make, primed
 from test_gpu_explore_streams import assert_states_bit_equal
@@ -310,3 +313,65 @@ def test_refusals_carry_the_librarys_message(tmp_path):
     with pytest.raises(ts.StateError, match=r"array 'reset_stream_keys' holds 4 streams, the agent has 5 environments"):
         wide.load_training_state(with_streams)
     A.load_training_state(without)                               # a state without the field loads as before
+
+
+@pytest.mark.parametrize("cls", [NativePointMassVecEnv, NativePushBlockVecEnv])
+def test_the_row_of_a_kind_refuses_on_the_host(cls):
+    """What the entries check against a kind's row of the library's table, for both kinds, where no other test does: dimensions
+    other than the block's (both rollout entries) and a null LAST state array (both rollout entries; hp_env_reset and the unknown
+    kind are covered above and in test_gpu_push_block.py).  5 environments = one full slab and one of a single row, 7 episodes =
+    two waves, the second partial.  Nothing is launched: environments, streams and block keep their bytes."""
+    T, n, total = 3, 5, 7
+    torch.manual_seed(0)
+    agent = make(cls(n, seed=10, device=DEV, max_timesteps=T), T=T, noise_eps=0.05)
+    primed(agent)
+    agent.enable_explore_streams(base_seed=900)
+    env = agent.vec_env
+    env.enable_device_reset(agent.ctx)
+    env.reset()
+    last = len(env.state_names) - 1
+    eps = DeviceEpisodes(agent.ctx, agent.buffer._dev, total)
+    success = torch.zeros(total, dtype=torch.float32, device=DEV)
+    # an agent and a block of other dimensions, in the same context
+    torch.manual_seed(0)
+    small = ddpg_agent(Args(batch_size=256, buffer_size=200), None,
+                       {'obs': 10, 'goal': 2, 'action': 3, 'action_max': 0.5, 'max_timesteps': T}, ctx=agent.ctx, rng=fresh_rng(3))
+    other = DeviceEpisodes(small.ctx, small.buffer._dev, total)
+
+    def snapshot():
+        return ([getattr(env, name).clone() for name in env.state_names] + [success.clone()],
+                [*env.reset_streams.get_arrays(), *agent.explore_streams.get_arrays(), *eps.numpy(), *other.numpy()])
+
+    def desc(null=None):
+        d = env.env_desc()
+        if null is not None:
+            d.state_dev[null] = None
+        return d
+
+    launches = C.c_int32(-1)
+
+    def waves(a, block, d):
+        with a.ctx.torch_bridge():
+            _lib.check(a.lib.hp_rollout_begin(block.h, 0, total))
+            _lib.check(a.lib.hp_rollout_waves(block.h, a.h, a.o_norm.h, a.g_norm.h, agent.explore_streams.h, env.reset_streams.h,
+                                              C.byref(d), n, 1, 0.05, 0.3, binomial1_qn(0.3)[0], 0.0, p(success), C.byref(launches)))
+
+    def episodes(a, block, d):
+        with a.ctx.torch_bridge():
+            _lib.check(a.lib.hp_rollout_begin(block.h, 0, n))
+            _lib.check(a.lib.hp_rollout_episodes(block.h, a.h, a.o_norm.h, a.g_norm.h, agent.explore_streams.h, C.byref(d), 1, 0.05, 0.3,
+                                                 binomial1_qn(0.3)[0], 0.0, p(success)))
+
+    kind = env.kind
+    tensors, arrays = snapshot()
+    for entry, call in (("hp_rollout_waves", waves), ("hp_rollout_episodes", episodes)):
+        with pytest.raises(ValueError, match=rf"{entry}: env->kind {kind} has dimensions 27 / 3 / 4, the block has 10 / 2 / 3"):
+            call(small, other, desc())
+        with pytest.raises(ValueError, match=rf"{entry}: env->state_dev\[{last}\] is null"):
+            call(agent, eps, desc(null=last))
+    after_t, after_a = snapshot()
+    assert all(torch.equal(x, y) for x, y in zip(tensors, after_t))                                         # nothing ran
+    assert all(np.array_equal(bits(x), bits(y)) for x, y in zip(arrays, after_a)) and launches.value == -1
+    waves(agent, eps, desc())                                                                               # ... and a good call does
+    assert launches.value == 1
+    assert not all(np.array_equal(bits(x), bits(y)) for x, y in zip(arrays, snapshot()[1]))

@@ -274,6 +274,7 @@ def test_the_push_block_kernels_use_no_scratch(tmp_path):
         print(name, m)
         assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, (name, m)
         assert m["group_segment_fixed_size"] <= 160 * 1024, (name, m)
-    # the split by the launch cap stays in one place: this unit launches what it is told to
-    src = open(os.path.join(csrc, "env_push_block.hip")).read()
+    # the split by the launch cap stays in one place: this unit launches what it is told to, through the one launch of its table
+    # row (env_kind_entry, rollout_episodes.h)
+    src = open(os.path.join(csrc, "env_push_block.hip")).read() + open(os.path.join(csrc, "rollout_episodes.h")).read()
     assert "launch_cap" not in src and len(re.findall(r"hipLaunchKernelGGL\(k_rollout_episodes<", src)) == 1
