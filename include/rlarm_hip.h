@@ -439,6 +439,45 @@ int hp_rollout_waves(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_norm *g_n
                      hp_rng_streams *reset_streams, const hp_env_desc *env, int64_t n_envs, int32_t explore, double noise_eps,
                      double random_eps, double qn, double clip_abs, float *success_dev, int32_t *launches_out);
 
+/* ---- demonstration episodes from a scripted controller, generated on the device ---------------------------------------------
+ * The reference fills its replay buffer with episodes a scripted push controller produced (get_demo_data_push.py:24-94) and
+ * keeps the successful ones.  hp_demo_script holds that controller's numbers (defaults: the reference's, in
+ * synthetic.DemoScript): timestep t = 1 .. T is in phase p if it is <= phase_end[p] and in no earlier phase, in the sixth phase
+ * behind phase_end[4].  Phase one: the constant action `lift`; two and five: go behind the block,
+ * ((g - b) * behind + b) - grip; three and six: push, g - b; four: to the waypoint, waypoint - grip (fourth component 0 from
+ * phase two on), with grip = obs[0:3], b = obs[12:15], g the desired goal; and the action is all zeros once
+ * sqrt(dx dx + dy dy + dz dz) < stop_radius between b and g.  Every float64 operation is rounded on its own, sums left to right.
+ * hp_demo_episodes collects `n_episodes` scripted episodes of a native environment kind with a reset on the device into episodes
+ * [first_episode, first_episode + n_episodes) of `block` (the block of an hp_rollout: T and the dimensions are its own), as
+ * ceil(n_episodes / n_envs) waves: workgroup i is one wave and owns environment i and reset stream i; episode w * n_envs + i is
+ * environment i's w-th -- reset from its stream, then T timesteps of observe, controller, record, step -- and an environment
+ * whose episode number falls behind n_episodes touches neither its stream nor its state.  The controller's float64 action is
+ * recorded as it is; the environment clips what it applies.  success_dev [n_episodes] and step_success_dev [n_episodes][T]
+ * (float32) receive is_success after the last and after every step.  No agent, no weights.  Streams and environment states are
+ * written back once per launch; a launch holds at most HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS timesteps as in hp_rollout_waves (the
+ * block's own cap), *launches_out (may be NULL) says how many there were.
+ * hp_demo_compact is the success filter, order preserving: episode e of the first n_episodes of `src` with success_dev[e] != 0
+ * and rank r among those is copied -- obs, ag, g, actions and its row of step_success_dev -- to episode kept + r of `dst` (and
+ * row kept + r of dst_step_success_dev) if that is < n_demos; *kept_dev (int32, device) receives min(kept + successes, n_demos).
+ * `kept` is what the caller read after the previous round (0 at first).
+ * Both asynchronous on the context's stream (or a borrowed one).  HP_ERR_INVALID, naming the entry point, for: a null argument,
+ * handles of different contexts, an unknown kind or one without a reset on the device, a null state array, n_envs wider than
+ * the stream array, T or dimensions that differ from the block's (hp_demo_compact: between the blocks), episodes outside a
+ * block, phase ends that are not increasing. */
+typedef struct {
+    int32_t phase_end[5];     /* last timestep (counted from 1) of phases one to five */
+    int32_t reserved;
+    double lift[4];           /* the action of phase one */
+    double waypoint[3];       /* where phase four takes the gripper */
+    double behind;            /* -0.5: how far behind the block, in units of the block-to-goal vector */
+    double stop_radius;       /* 0.05 */
+} hp_demo_script;
+int hp_demo_episodes(hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *reset_streams, const hp_demo_script *script,
+                     int64_t n_envs, int64_t first_episode, int64_t n_episodes, int32_t T, hp_rollout *block, float *success_dev,
+                     float *step_success_dev, int32_t *launches_out);
+int hp_demo_compact(hp_ctx *ctx, hp_rollout *src, const float *success_dev, const float *step_success_dev, int64_t n_episodes,
+                    hp_rollout *dst, float *dst_step_success_dev, int64_t n_demos, int64_t kept, int32_t *kept_dev);
+
 /* Policy calls that do not queue behind training: hp_agent_policy_snapshot copies the online actor and both normalizers'
  * statistics (stream-ordered with the updates, no host wait); hp_agent_act_snapshot evaluates the most recent COMPLETE
  * snapshot on a second stream, so a feeder can step its environments while a training cycle runs (its policy lags the

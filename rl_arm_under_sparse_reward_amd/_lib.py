@@ -55,6 +55,12 @@ class EnvDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("params", C.c_double * 8), ("state_dev", C.c_void_p * 4)]
 
 
+class DemoScriptDesc(C.Structure):
+    """hp_demo_script: the scripted controller's numbers (hp_demo_episodes; synthetic.DemoScript holds the same fields)"""
+    _fields_ = [("phase_end", C.c_int32 * 5), ("reserved", C.c_int32), ("lift", C.c_double * 4), ("waypoint", C.c_double * 3),
+                ("behind", C.c_double), ("stop_radius", C.c_double)]
+
+
 ENV_POINT_MASS = 1
 ENV_PUSH_BLOCK = 2      # HP_ENV_PUSH_BLOCK
 ROLLOUT_MAX_LAUNCH_TIMESTEPS = 4096   # HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS: what one launch of hp_rollout_waves holds at most
@@ -196,6 +202,10 @@ PROTOTYPES = {
                                    C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                    C.POINTER(C.c_int32)]),
     "hp_rollout_debug_set_launch_cap": (C.c_int, [C.c_void_p, C.c_int64]),
+    "hp_demo_episodes": (C.c_int, [C.c_void_p, C.POINTER(EnvDesc), C.c_void_p, C.POINTER(DemoScriptDesc), C.c_int64, C.c_int64,
+                                   C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "hp_demo_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.c_int64, C.c_void_p]),
     "hp_agent_policy_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hp_agent_act_snapshot": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int64, C.c_double, f32p]),
     "hp_agent_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,

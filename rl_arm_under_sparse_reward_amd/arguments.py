@@ -31,6 +31,10 @@ class Args:
     num_rollouts_per_mpi: int = 2
     add_demo: bool = False
     demo_name: str = "bmirobot_1000_push_demo.npz"
+    demo_source: str = "file"           # add_demo: "file" = preload demo_name (the reference); "device" = generate demo_episodes
+                                        # scripted demonstrations on the device (device_env.generate_demos; a native environment)
+    demo_episodes: int = 1000           # get_demo_data_push.py:13 demo_num
+    demo_max_episodes: int = 10000      # get_demo_data_push.py:27: episodes attempted at most
     train_type: str = "push"
     env_name: str = "bmirobot_push seed125"
     distance_threshold: float = 0.05    # bmirobot_push_F.py:20 / bmirobot_pickandplace_v2.py:19

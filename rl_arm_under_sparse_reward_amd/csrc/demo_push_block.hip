@@ -1,0 +1,6 @@
+// demo_push_block.hip -- the push-block environment's instantiation of the scripted-episode kernel (demo_episodes.h): the third
+// launch of its table row (env_push_block.hip).  A unit of its own: it needs no policy slab, and the unit of the rollout kernels
+// compiles what it compiled before.
+#include "demo_episodes.h"
+
+template hipError_t env_launch_demo<PushBlockEnvDev>(hipStream_t, unsigned, const DemoArgs &);

@@ -6,6 +6,8 @@
 //     load(desc, i)                            state of environment i out of the arrays of hp_env_desc (and the parameters)
 //     observe(obs, ag, g)                      write the current observation row [OBS], achieved goal [GOAL], desired goal [GOAL]
 //     step(action_f32)                         advance by one timestep with the float32 action [ACT] the policy side produced
+//     step(action_f64)                         the same operations on a float64 action (a scripted controller's: demo_episodes.h);
+//                                              both are step_with, whose first operation widens the component to float64
 //     is_success()                             the `is_success` flag of the state just reached
 //     store(desc, i)                           write the state back (every array: a reset on the device changes the goal too)
 //     static constexpr int STATE_ARRAYS         how many arrays of hp_env_desc.state_dev the kind uses (the null check on the host)
@@ -28,7 +30,9 @@
 // that no contraction can change a bit relative to the elementwise torch / numpy ops of that twin.
 // Adding a kind touches this and nothing else: a struct here; an HP_ENV_* constant in rlarm_hip.h and its twin in _lib.py; a unit
 // env_<kind>.hip of three lines -- the include of rollout_episodes.h and `const EnvKind env_kind_<kind> = env_kind_entry<Struct>(HP_ENV_...)`,
-// which instantiates both kernels for the kind and checks at compile time what a kind must be for them -- with its entry in the
+// which instantiates both kernels for the kind and checks at compile time what a kind must be for them -- and a unit
+// demo_<kind>.hip of two, the explicit instantiation of env_launch_demo<Struct> (demo_episodes.h: the scripted-episode kernel, the
+// row's third launch), both with their entries in the
 // Makefile's EXACT_SRCS; the row's declaration in rollout_episodes.h and its address in the table of env_kind() (rollout.hip); and
 // one Python class pair in device_env.py (the tensor twin, and a native class that names the constant).  No entry point, dispatch or
 // check names a kind: they read the row (env_point_mass.hip and env_push_block.hip are the two models).
@@ -84,7 +88,8 @@ struct PointMassEnvDev {
             g[c] = goal[c];
         }
     }
-    __device__ __forceinline__ void step(const float *action) {
+    template <class A>
+    __device__ __forceinline__ void step_with(const A *action) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const double a = fmin(fmax((double)action[c], -0.5), 0.5);
@@ -94,6 +99,8 @@ struct PointMassEnvDev {
             pos[c] = moved;
         }
     }
+    __device__ __forceinline__ void step(const float *action) { step_with(action); }
+    __device__ __forceinline__ void step(const double *action) { step_with(action); }
     __device__ __forceinline__ bool is_success() const {
         const double dx = __dsub_rn(pos[0], goal[0]), dy = __dsub_rn(pos[1], goal[1]), dz = __dsub_rn(pos[2], goal[2]);
         const double s = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
@@ -172,7 +179,8 @@ struct PushBlockEnvDev {
             g[c] = goal[c];
         }
     }
-    __device__ __forceinline__ void step(const float *action) {
+    template <class A>
+    __device__ __forceinline__ void step_with(const A *action) {
         const double lo[3] = {X_LO, Y_LO, table_z}, hi[3] = {X_HI, Y_HI, Z_HI};
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -196,6 +204,8 @@ struct PushBlockEnvDev {
         bvel[1] = __dsub_rn(blk[1], oy);
         bvel[2] = 0.0;                       // blk.z stays table_z
     }
+    __device__ __forceinline__ void step(const float *action) { step_with(action); }
+    __device__ __forceinline__ void step(const double *action) { step_with(action); }
     __device__ __forceinline__ bool is_success() const {
         const double dx = __dsub_rn(blk[0], goal[0]), dy = __dsub_rn(blk[1], goal[1]), dz = __dsub_rn(blk[2], goal[2]);
         const double s = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));

@@ -32,6 +32,7 @@
 #include <algorithm>
 
 #include "rollout_episodes.h"   // ExploreArgs, ro_explore_row, PolicyArgs (slab8.h), EpisodesArgs and EnvKind
+#include "demo_episodes.h"      // DemoArgs (the kernel is instantiated by the kinds' demo units, through EnvKind::launch_demo), CompactArgs
 
 struct hp_rollout {
     hp_ctx *ctx = nullptr;
@@ -268,6 +269,8 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     return rollout_split_launches(ro, A, launches, kind->launch_episodes);
 }
 
+
+
 extern "C" {
 
 int hp_rollout_create(hp_ctx *ctx, hp_buffer *buf, int64_t n_envs, hp_rollout **out) {
@@ -362,6 +365,93 @@ int hp_env_reset(hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *reset_stre
         HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "hp_env_reset: env->state_dev[%d] is null", k);
     HP_REQUIRE(kind->reset_draws > 0, HP_ERR_INVALID, "hp_env_reset: env->kind %d has no reset on the device", (int)env->kind);
     HP_CHECK_HIP(kind->launch_reset(ctx->stream, *env, reset_streams->d_state, rows));
+    return HP_OK;
+}
+
+int hp_demo_episodes(hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *reset_streams, const hp_demo_script *script, int64_t n_envs,
+                     int64_t first_episode, int64_t n_episodes, int32_t T, hp_rollout *block, float *success_dev, float *step_success_dev,
+                     int32_t *launches_out) {
+    HP_REQUIRE(ctx && env && reset_streams && script && block && success_dev && step_success_dev, HP_ERR_INVALID,
+               "hp_demo_episodes: null argument");
+    CtxGuard guard(ctx);
+    hp_rollout *ro = block;
+    HP_REQUIRE(reset_streams->ctx == ctx && ro->ctx == ctx, HP_ERR_INVALID, "hp_demo_episodes: handles belong to different contexts");
+    HP_REQUIRE(n_envs > 0 && n_envs < (1 << 24), HP_ERR_INVALID, "hp_demo_episodes: n_envs %lld out of range", (long long)n_envs);
+    HP_REQUIRE(n_envs <= reset_streams->n, HP_ERR_INVALID, "hp_demo_episodes: %lld environments, but the array holds %lld reset streams",
+               (long long)n_envs, (long long)reset_streams->n);
+    HP_REQUIRE(first_episode >= 0 && n_episodes > 0 && first_episode + n_episodes <= ro->n, HP_ERR_INVALID,
+               "hp_demo_episodes: episodes [%lld, %lld) outside the block of %lld", (long long)first_episode,
+               (long long)(first_episode + n_episodes), (long long)ro->n);
+    HP_REQUIRE(T == ro->T, HP_ERR_INVALID, "hp_demo_episodes: T = %d, the block has T = %d", (int)T, (int)ro->T);
+    const EnvKind *kind = env_kind(env->kind);
+    HP_REQUIRE(kind, HP_ERR_INVALID, "hp_demo_episodes: env->kind %d is not an environment kind of this build", (int)env->kind);
+    for (int k = 0; k < kind->state_arrays; ++k)
+        HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "hp_demo_episodes: env->state_dev[%d] is null", k);
+    HP_REQUIRE(ro->od == kind->obs && ro->gd == kind->goal && ro->ad == kind->act, HP_ERR_INVALID,
+               "hp_demo_episodes: env->kind %d has dimensions %d / %d / %d, the block has %d / %d / %d", (int)env->kind, kind->obs,
+               kind->goal, kind->act, ro->od, ro->gd, ro->ad);
+    HP_REQUIRE(kind->reset_draws > 0, HP_ERR_INVALID, "hp_demo_episodes: env->kind %d has no reset on the device", (int)env->kind);
+    for (int k = 0; k < 5; ++k)
+        HP_REQUIRE(script->phase_end[k] >= 0 && (k == 0 || script->phase_end[k] > script->phase_end[k - 1]), HP_ERR_INVALID,
+                   "hp_demo_episodes: script->phase_end[%d] = %d: the phase ends must be increasing", k, (int)script->phase_end[k]);
+    DemoArgs A;
+    memset(&A, 0, sizeof(A));
+    A.b_obs = ro->block + first_episode * (ro->T + 1) * ro->od;
+    A.b_ag = ro->block + ro->o_ag + first_episode * (ro->T + 1) * ro->gd;
+    A.b_g = ro->block + ro->o_g + first_episode * ro->T * ro->gd;
+    A.b_act = ro->block + ro->o_act + first_episode * ro->T * ro->ad;
+    A.reset_st = reset_streams->d_state;
+    A.T = ro->T; A.n_envs = (int)n_envs;
+    A.s = *script;
+    A.env = *env;
+    // the launch-length rule of rollout_split_launches: whole waves, at most launch_cap timesteps, the next launch on the states
+    // and streams the one before it wrote back
+    int64_t per = ro->launch_cap / (ro->T > 0 ? ro->T : 1);
+    if (per < 1) per = 1;
+    int n = 0;
+    for (int64_t done = 0; done < n_episodes; ++n) {
+        const int64_t left = n_episodes - done, waves = std::min<int64_t>((left + n_envs - 1) / n_envs, per);
+        const int64_t rows = std::min(left, waves * n_envs), live = std::min(rows, n_envs);
+        DemoArgs L = A;
+        L.b_obs += done * (ro->T + 1) * ro->od;
+        L.b_ag += done * (ro->T + 1) * ro->gd;
+        L.b_g += done * ro->T * ro->gd;
+        L.b_act += done * ro->T * ro->ad;
+        L.success = success_dev + done;
+        L.step_success = step_success_dev + done * ro->T;
+        L.rows = (int)rows; L.waves = (int)waves;
+        HP_CHECK_HIP(kind->launch_demo(ctx->stream, (unsigned)live, L));
+        done += rows;
+    }
+    if (launches_out) *launches_out = n;
+    return HP_OK;
+}
+
+int hp_demo_compact(hp_ctx *ctx, hp_rollout *src, const float *success_dev, const float *step_success_dev, int64_t n_episodes,
+                    hp_rollout *dst, float *dst_step_success_dev, int64_t n_demos, int64_t kept, int32_t *kept_dev) {
+    HP_REQUIRE(ctx && src && success_dev && step_success_dev && dst && dst_step_success_dev && kept_dev, HP_ERR_INVALID,
+               "hp_demo_compact: null argument");
+    CtxGuard guard(ctx);
+    HP_REQUIRE(src->ctx == ctx && dst->ctx == ctx, HP_ERR_INVALID, "hp_demo_compact: handles belong to different contexts");
+    HP_REQUIRE(src != dst, HP_ERR_INVALID, "hp_demo_compact: source and destination are the same block");
+    HP_REQUIRE(src->T == dst->T && src->od == dst->od && src->gd == dst->gd && src->ad == dst->ad, HP_ERR_INVALID,
+               "hp_demo_compact: the source block has T %d and dimensions %d / %d / %d, the destination %d and %d / %d / %d", src->T,
+               src->od, src->gd, src->ad, dst->T, dst->od, dst->gd, dst->ad);
+    HP_REQUIRE(n_episodes > 0 && n_episodes <= src->n && n_episodes < (1 << 24), HP_ERR_INVALID,
+               "hp_demo_compact: episodes [0, %lld) outside the source block of %lld", (long long)n_episodes, (long long)src->n);
+    HP_REQUIRE(n_demos > 0 && n_demos <= dst->n, HP_ERR_INVALID, "hp_demo_compact: episodes [0, %lld) outside the destination block of %lld",
+               (long long)n_demos, (long long)dst->n);
+    HP_REQUIRE(kept >= 0 && kept <= n_demos, HP_ERR_INVALID, "hp_demo_compact: kept = %lld outside [0, %lld]", (long long)kept,
+               (long long)n_demos);
+    CompactArgs A;
+    memset(&A, 0, sizeof(A));
+    A.s_obs = src->block; A.s_ag = src->block + src->o_ag; A.s_g = src->block + src->o_g; A.s_act = src->block + src->o_act;
+    A.d_obs = dst->block; A.d_ag = dst->block + dst->o_ag; A.d_g = dst->block + dst->o_g; A.d_act = dst->block + dst->o_act;
+    A.success = success_dev; A.s_step = step_success_dev; A.d_step = dst_step_success_dev;
+    A.n = (int)n_episodes; A.T = src->T; A.od = src->od; A.gd = src->gd; A.ad = src->ad;
+    A.kept = kept; A.n_demos = n_demos;
+    A.kept_out = kept_dev;
+    HP_CHECK_HIP(demo_launch_compact(ctx->stream, (unsigned)n_episodes, A));
     return HP_OK;
 }
 

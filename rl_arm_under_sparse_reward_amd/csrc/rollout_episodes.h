@@ -225,13 +225,19 @@ __global__ __launch_bounds__(MW_THREADS) void k_env_reset(const hp_env_desc env,
 
 // ---- the table of kinds ------------------------------------------------------------------------------------------------------
 // What the host side of rollout.hip knows of a kind: its constant, what it compares with the block and the descriptor before any
-// launch, and how to launch its two kernels.  launch_episodes issues one launch of k_rollout_episodes over `blocks` workgroups with
+// launch, and how to launch its three kernels.  launch_episodes issues one launch of k_rollout_episodes over `blocks` workgroups with
 // the arguments of that launch (the split by the launch cap stays in rollout.hip), launch_reset one of k_env_reset over `rows`
-// environments; each returns the launch's hipError_t.
+// environments, launch_demo one of k_demo_episodes (demo_episodes.h: scripted episodes, no policy) over `blocks` environments;
+// each returns the launch's hipError_t.  The third kernel is compiled by a unit of its own (demo_<kind>.hip), which this file
+// names only by the launch function's declaration.
+struct DemoArgs;                                 // demo_episodes.h
+template <class Env> hipError_t env_launch_demo(hipStream_t stream, unsigned blocks, const DemoArgs &L);   // defined there too
+
 struct EnvKind {
     int kind, obs, goal, act, state_arrays, reset_draws;
     hipError_t (*launch_episodes)(hipStream_t stream, unsigned blocks, const EpisodesArgs &L);
     hipError_t (*launch_reset)(hipStream_t stream, const hp_env_desc &env, MtState *reset_st, int64_t rows);
+    hipError_t (*launch_demo)(hipStream_t stream, unsigned blocks, const DemoArgs &L);
 };
 
 // The row of kind `kind` = the struct Env of env_device.h: what a kind must be for these kernels, and the kernels' instantiation
@@ -249,7 +255,8 @@ EnvKind env_kind_entry(int kind) {
                    [](hipStream_t stream, const hp_env_desc &env, MtState *reset_st, int64_t rows) {
                        hipLaunchKernelGGL(k_env_reset<Env>, dim3((unsigned)rows), dim3(MW_THREADS), 0, stream, env, reset_st);
                        return hipGetLastError();
-                   }};
+                   },
+                   &env_launch_demo<Env>};
 }
 
 // the rows, one per unit (the table itself: env_kind() in rollout.hip)

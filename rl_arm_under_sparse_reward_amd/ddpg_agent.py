@@ -508,7 +508,32 @@ class ddpg_agent:
             plt.show()
 
     def _init_demo_buffer(self):
-        """ddpg_agent.py:82-90: keys obs, acs, ag, g of a get_demo_data_*.py file (info is ignored)."""
+        """ddpg_agent.py:82-90: keys obs, acs, ag, g of a get_demo_data_*.py file (info is ignored).  With
+        `args.demo_source == "device"` and a native vectorised environment the demonstrations are generated instead
+        (`device_env.generate_demos`: args.demo_episodes successful episodes of the scripted push controller) and stored out of
+        their device block, in order, as ONE store_episode call like the file's -- the device path has no size limit of its
+        own -- and fewer kept than asked is an error.  If the environment is not reset on the device yet but args.device_reset
+        asks for it, the preload waits for learn(), which enables the reset first."""
+        source = getattr(self.args, "demo_source", "file")
+        if source not in ("file", "device"):
+            raise ValueError("demo_source must be 'file' (the reference's preload) or 'device'")
+        if source == "device":
+            from .device_env import generate_demos
+            if self.vec_env is None or not getattr(self.vec_env, "is_native_device_env", False):
+                raise ValueError("demo_source='device' needs a native vectorised device environment (device_env.py)")
+            if getattr(self.vec_env, "reset_streams", None) is None and getattr(self.args, "device_reset", False):
+                self._demo_preload_pending = True
+                return
+            self._demo_preload_pending = False
+            want = int(getattr(self.args, "demo_episodes", 1000))
+            demos = generate_demos(self.vec_env, want, max_episodes=int(getattr(self.args, "demo_max_episodes", 10000)), ctx=self.ctx)
+            self.demo_stats = {"kept": demos.kept, "attempted": demos.attempted, "launches": demos.launches}
+            if demos.kept < want:
+                raise RuntimeError(f"demo_source='device': only {demos.kept} of {want} scripted episodes succeeded in "
+                                   f"{demos.attempted} attempts")
+            self.buffer.store_episode(demos.episodes)
+            self.ctx.synchronize()           # the block is freed with `demos`: the store has read it
+            return
         demo = np.load(self.args.demo_name, allow_pickle=True)
         self.buffer.store_episode([np.array(demo['obs']), np.array(demo['ag']), np.array(demo['g']),
                                    np.array(demo['acs'])])
@@ -821,6 +846,8 @@ class ddpg_agent:
             self.enable_explore_streams()    # args.explore_streams: before a resume, whose state carries the streams' states
         if self.vec_env is not None and getattr(self.args, "device_reset", False) and getattr(self.vec_env, "reset_streams", None) is None:
             self.vec_env.enable_device_reset(self.ctx)   # args.device_reset: likewise before a resume
+        if getattr(self, "_demo_preload_pending", False):
+            self._init_demo_buffer()                     # demo_source='device': generated now that the reset is on the device
         if resume:
             self._resume_state(resume)
             first_epoch = self.resumed_at[0]

@@ -38,6 +38,11 @@ few launches `_lib.ROLLOUT_MAX_LAUNCH_TIMESTEPS` dictates; `agent.rollout_launch
 Draw order with n environments: per timestep, for env i = 0 .. n-1: randn(action), uniform(action), binomial(1) -- the order of
 the host lockstep path (`collect_episodes` on a list of environments); with one environment it is the reference's own order.
 
+**Demonstrations.**  `generate_demos(vec_env, n_demos)` runs the reference's scripted push controller
+(`synthetic.scripted_action`, get_demo_data_push.py:39-61) on a native environment that is reset on the device and keeps the
+successful episodes in order -- whole episodes, all waves of a round in one launch (hp_demo_episodes), the filter one more
+(hp_demo_compact), no policy and no weights; `synthetic.scripted_demos` on host twins seeded alike gives the same bits.
+
 `PointMassVecEnv` is the tensor twin of `synthetic.PointMassGoalEnv`, `PushBlockVecEnv` that of `synthetic.PushBlockGoalEnv`; what
 they share (`_GoalVecEnv`) includes the rule that an environment works on the first `active` rows of its state tensors.  A native
 class is one of them behind `_NativeEnv` -- descriptor, device reset -- plus the constant of its kind.
@@ -51,7 +56,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .synthetic import (PUSH_RESET_ATTEMPTS, PUSH_RESET_BOUNDS, PUSH_START_Z, PUSH_X_HI, PUSH_X_LO, PUSH_Y_HI, PUSH_Y_LO,
+from .synthetic import (DemoScript, write_demo_npz_from, PUSH_RESET_ATTEMPTS, PUSH_RESET_BOUNDS, PUSH_START_Z, PUSH_X_HI, PUSH_X_LO, PUSH_Y_HI, PUSH_Y_LO,
                         PUSH_Z_HI)
 
 
@@ -390,3 +395,127 @@ class NativePushBlockVecEnv(_NativeEnv, PushBlockVecEnv):
     own draws ask for.  `step` is the parent's, so the per-step protocol works on it unchanged."""
 
     kind = _lib.ENV_PUSH_BLOCK
+
+
+# ---- demonstrations from the scripted controller ---------------------------------------------------------------------------------
+DEMO_ROUND_EPISODES = 2048       # episodes a round of generate_demos aims at by default (a block of 56 MB at T = 100)
+
+
+def default_round_waves(n_demos, n_envs):
+    """Waves per round of `generate_demos` when the caller names none: a rule of (n_demos, n_envs) alone.  A round should hold
+    about twice the demonstrations asked for -- at the ten per cent or so of scripted push episodes that succeed, a handful of
+    rounds -- but no more than DEMO_ROUND_EPISODES episodes, and at least one wave:
+    clamp(ceil(2 n_demos / n_envs), 1, max(1, DEMO_ROUND_EPISODES // n_envs))."""
+    n_demos, n_envs = int(n_demos), int(n_envs)
+    return max(1, min(-(-2 * n_demos // n_envs), max(1, DEMO_ROUND_EPISODES // n_envs)))
+
+
+def script_desc(script=None):
+    """`synthetic.DemoScript` (None: the reference's numbers) as the library's struct (hp_demo_script)."""
+    s = script or DemoScript()
+    d = _lib.DemoScriptDesc()
+    for i, v in enumerate(s.phase_end):
+        d.phase_end[i] = v
+    for i, v in enumerate(s.lift):
+        d.lift[i] = v
+    for i, v in enumerate(s.waypoint):
+        d.waypoint[i] = v
+    d.behind, d.stop_radius = s.behind, s.stop_radius
+    return d
+
+
+class DeviceDemos:
+    """What `generate_demos` returns: `.episodes`, a `DeviceEpisodes` of the `.kept` successful episodes in order (None if none
+    was kept) -- `buffer.store_episode` / `train_cycle` take it as it is; `.info`, their is_success flags after every step
+    (float32 tensor [kept, T]); `.attempted`, the episodes run; `.launches`, the launches of hp_demo_episodes.  `.numpy()`
+    copies (obs, ag, g, actions, info) to the host; `.save(path)` writes them in the reference's demo schema."""
+
+    def __init__(self, episodes, info, kept, attempted, launches, shapes):
+        self.episodes, self.info, self.kept, self.attempted, self.launches = episodes, info, kept, attempted, launches
+        self._shapes = shapes
+
+    def __len__(self):
+        return self.kept
+
+    def numpy(self):
+        if self.episodes is None:
+            return [np.empty((0,) + s, dtype=np.float32 if j == 4 else np.float64) for j, s in enumerate(self._shapes)]
+        return [*self.episodes.numpy(), self.info.cpu().numpy()]
+
+    def save(self, path):
+        """A demo file in the schema of get_demo_data_push.py:91-94 (`synthetic.write_demo_npz_from`): it preloads through
+        `ddpg_agent._init_demo_buffer` and through the reference's own."""
+        obs, ag, g, actions, info = self.numpy()
+        write_demo_npz_from(path, obs, ag, g, actions, info)
+
+
+def generate_demos(vec_env, n_demos, round_waves=None, max_episodes=10000, script=None, ctx=None, *, launch_cap=None):
+    """`n_demos` successful episodes of the scripted push controller (`synthetic.DemoScript`, default: the reference's numbers)
+    on the native environment `vec_env`, generated and filtered on the device: the device form of `synthetic.scripted_demos`,
+    bit for bit what that returns for host twins in the states of `vec_env`'s reset streams.
+
+    Rounds as there: a round attempts n_envs * round_waves episodes, cut to what `max_episodes` leaves (episode e = w * n_envs
+    + i is environment i's w-th of the round, reset from reset stream i) as one launch of hp_demo_episodes -- or the few the
+    launch cap dictates -- and hp_demo_compact appends its successes, in order, behind those kept so far; whole rounds until
+    n_demos are kept or max_episodes attempted.  The result is a pure function of (environment parameters and reset-stream
+    states, n_demos, round_waves, max_episodes, script).  `round_waves=None`: `default_round_waves(n_demos, n_envs)`.
+
+    The count of kept episodes is read back ONCE PER ROUND (4 bytes, synchronising): generation is a one-off at start-up and
+    the host has to know when to stop.  Nothing else visits the host.  Touches no exploration stream and no sampler stream; the
+    environment's state tensors hold the last episode's final state afterwards, like after `collect_episodes_device`.
+
+    Needs a native environment with `enable_device_reset()` done (ValueError otherwise).  Returns a `DeviceDemos`;
+    `kept < n_demos` there says max_episodes ran out.  `launch_cap` (tests): the timesteps one launch may hold
+    (hp_rollout_debug_set_launch_cap on the round's block) in place of `_lib.ROLLOUT_MAX_LAUNCH_TIMESTEPS`."""
+    if not getattr(vec_env, "is_native_device_env", False):
+        raise ValueError("generate_demos: the environment is not native (device_env.NativePointMassVecEnv, NativePushBlockVecEnv): "
+                         "scripted episodes on the device need dynamics the library evaluates itself")
+    if getattr(vec_env, "reset_streams", None) is None:
+        raise ValueError("generate_demos: the environment is not reset on the device: call vec_env.enable_device_reset() first "
+                         "(args.device_reset)")
+    n_demos, max_episodes, n_envs = int(n_demos), int(max_episodes), int(vec_env.n_envs)
+    if n_demos < 1:
+        raise ValueError("generate_demos: n_demos must be positive")
+    round_waves = default_round_waves(n_demos, n_envs) if round_waves is None else int(round_waves)
+    if round_waves < 1:
+        raise ValueError("generate_demos: round_waves must be positive")
+    ctx = ctx or vec_env.ctx
+    lib, dev = ctx.lib, vec_env.device
+    from .replay_buffer import DeviceEpisodeBuffer
+    p, T = vec_env.env_params, int(vec_env.max_timesteps)
+    shape = DeviceEpisodeBuffer(1, T, p['obs'], p['goal'], p['action'], ctx=ctx)     # T and the dimensions of the blocks
+    per_round = min(n_envs * round_waves, max(max_episodes, 1))
+    src, dst = DeviceEpisodes(ctx, shape, per_round), DeviceEpisodes(ctx, shape, n_demos)
+    if launch_cap is not None:
+        _lib.check(lib.hp_rollout_debug_set_launch_cap(src.h, int(launch_cap)))
+    success = torch.zeros(per_round, dtype=torch.float32, device=dev)
+    step_success = torch.zeros((per_round, T), dtype=torch.float32, device=dev)
+    info = torch.zeros((n_demos, T), dtype=torch.float32, device=dev)
+    kept_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+    sd, launches = script_desc(script), C.c_int32()
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    kept = attempted = total_launches = 0
+    while kept < n_demos and attempted < max_episodes:
+        n = min(n_envs * round_waves, max_episodes - attempted)
+        env = vec_env.env_desc()
+        with ctx.torch_bridge():
+            _lib.check(lib.hp_demo_episodes(ctx.h, C.byref(env), vec_env.reset_streams.h, C.byref(sd), n_envs, 0, n, T, src.h,
+                                            ptr(success), ptr(step_success), C.byref(launches)))
+            _lib.check(lib.hp_demo_compact(ctx.h, src.h, ptr(success), ptr(step_success), n, dst.h, ptr(info), n_demos, kept,
+                                           ptr(kept_dev)))
+        vec_env.active = (n - 1) % n_envs + 1                 # the environments of the round's last wave
+        kept = int(kept_dev.item())                           # the one synchronising read of the round
+        attempted += n
+        total_launches += int(launches.value)
+    shapes = ((T + 1, p['obs']), (T + 1, p['goal']), (T, p['goal']), (T, p['action']), (T,))
+    if kept == n_demos:
+        return DeviceDemos(dst, info, kept, attempted, total_launches, shapes)
+    if kept == 0:
+        return DeviceDemos(None, info[:0], 0, attempted, total_launches, shapes)
+    # fewer than asked: a block of exactly `kept` episodes (what store_episode takes), by the filter with every flag set
+    short, short_info = DeviceEpisodes(ctx, shape, kept), torch.zeros((kept, T), dtype=torch.float32, device=dev)
+    ones = torch.ones(kept, dtype=torch.float32, device=dev)
+    with ctx.torch_bridge():
+        _lib.check(lib.hp_demo_compact(ctx.h, dst.h, ptr(ones), ptr(info), kept, short.h, ptr(short_info), kept, 0, ptr(kept_dev)))
+    torch.cuda.current_stream(dev).synchronize()              # `dst` and `ones` go out of scope here
+    return DeviceDemos(short, short_info, kept, attempted, total_launches, shapes)

@@ -210,3 +210,107 @@ class PushBlockGoalEnv:
         info = {'is_success': self._is_success(observation['achieved_goal'], self.goal)}
         reward = self.compute_reward(observation['achieved_goal'], self.goal, info)
         return observation, reward, False, info
+
+
+# ---- demonstrations from a scripted controller (the reference's get_demo_data_push.py) ------------------------------------------
+class DemoScript:
+    """The numbers of the reference's push schedule (get_demo_data_push.py:39-61); the defaults are the reference's.
+    `phase_end`: the last timestep, counted from 1, of phases one to five (:43, :45, :49, :51, :53; the sixth runs to T);
+    `lift`: the constant action of phase one (:44); `waypoint`: where phase four takes the gripper (:52); `behind`: the factor
+    that places the gripper behind the block (:46-48); `stop_radius`: block-to-goal distance under which the action is zero
+    (:59-61).  hp_demo_script of include/rlarm_hip.h holds the same fields."""
+
+    def __init__(self, phase_end=(10, 20, 40, 60, 80), lift=(0.0, -0.1, 0.1, 0.0), waypoint=(0.241, 0.3265, 0.294), behind=-0.5,
+                 stop_radius=0.05):
+        self.phase_end = tuple(int(e) for e in phase_end)
+        self.lift = tuple(float(v) for v in lift)
+        self.waypoint = tuple(float(v) for v in waypoint)
+        self.behind, self.stop_radius = float(behind), float(stop_radius)
+        if len(self.phase_end) != 5 or len(self.lift) != 4 or len(self.waypoint) != 3:
+            raise ValueError("DemoScript: five phase ends, four lift components, three waypoint components")
+        if self.phase_end[0] < 0 or any(b <= a for a, b in zip(self.phase_end, self.phase_end[1:])):
+            raise ValueError(f"DemoScript: the phase ends {self.phase_end} must be increasing")
+
+
+def scripted_action(t, obs, g, script=None):
+    """The reference's push controller (get_demo_data_push.py:39-61) for timestep t = 1 .. T: the float64 action [4], unclipped,
+    out of the observation row -- gripper obs[0:3], block obs[12:15] -- and the desired goal.  It reads the bmirobot layout only,
+    so it serves every environment that keeps it.  One float64 operation per rounding, sums left to right: csrc/demo_episodes.h
+    (demo_action) repeats them one by one."""
+    s = script or DemoScript()
+    grip = [float(obs[0]), float(obs[1]), float(obs[2])]
+    b = [float(obs[12]), float(obs[13]), float(obs[14])]
+    g = [float(g[0]), float(g[1]), float(g[2])]
+    e = s.phase_end
+    k = s.behind
+    if t <= e[0]:                                     # :43-44 lift and retreat
+        action = list(s.lift)
+    elif t <= e[1] or e[3] < t <= e[4]:               # :45-48, :53-56 go behind the block
+        action = [(g[0] - b[0]) * k + b[0] - grip[0],
+                  (g[1] - b[1]) * k + b[1] - grip[1],
+                  b[2] + (g[2] - b[2]) * k - grip[2], 0.0]
+    elif e[2] < t <= e[3]:                            # :51-52 return to the waypoint
+        action = [s.waypoint[0] - grip[0], s.waypoint[1] - grip[1], s.waypoint[2] - grip[2], 0.0]
+    else:                                             # :49-50, :57-58 push
+        action = [g[0] - b[0], g[1] - b[1], g[2] - b[2], 0.0]
+    dx, dy, dz = b[0] - g[0], b[1] - g[1], b[2] - g[2]
+    if np.sqrt(dx * dx + dy * dy + dz * dz) < s.stop_radius:     # :59-61 the stop rule, on top of every phase
+        action = [0.0, 0.0, 0.0, 0.0]
+    return np.array(action, dtype=np.float64)
+
+
+def scripted_episode(env, script=None):
+    """One episode of `scripted_action` on a host environment, reset from its own `rs` (get_demo_data_push.py:34-74):
+    (obs [T+1, obs], ag [T+1, goal], g [T, goal], actions [T, act], is_success after every step [T])."""
+    T = int(env.max_timesteps)
+    o = env.reset()
+    obs, ag, g = o['observation'], o['achieved_goal'], o['desired_goal']
+    ep_obs, ep_ag, ep_g, ep_act, ep_ok = [], [], [], [], []
+    for t in range(1, T + 1):
+        action = scripted_action(t, obs, g, script)
+        o, _, _, info = env.step(action)
+        ep_obs.append(obs.copy()); ep_ag.append(ag.copy()); ep_g.append(g.copy()); ep_act.append(action)
+        ep_ok.append(np.float32(info['is_success']))
+        obs, ag = o['observation'], o['achieved_goal']
+    ep_obs.append(obs.copy()); ep_ag.append(ag.copy())
+    return np.array(ep_obs), np.array(ep_ag), np.array(ep_g), np.array(ep_act), np.array(ep_ok, dtype=np.float32)
+
+
+def scripted_demos(envs, n_demos, round_waves, max_episodes=10000, script=None):
+    """Successful scripted episodes of the host environments `envs` (PointMassGoalEnv / PushBlockGoalEnv), a pure function of its
+    inputs -- the host statement of `device_env.generate_demos`.  A round attempts len(envs) * round_waves episodes, cut to what
+    `max_episodes` leaves; episode e = w * n_envs + i of a round is environment i's w-th, reset from that environment's own `rs`
+    (the numbering of hp_rollout_waves).  An episode is kept if `is_success` is 1 after its last step; kept episodes stay in
+    order of round, then of e, and the first `n_demos` are returned.  Rounds are whole: the surplus of the last round is dropped
+    but its resets are consumed.  Generation stops when n_demos are kept or max_episodes attempted.  Returns
+    (obs [k, T+1, obs], ag [k, T+1, goal], g [k, T, goal], actions [k, T, act], info [k, T] float32, attempted).  With one
+    environment this is the reference's loop (get_demo_data_push.py:27-90) with its order of kept episodes."""
+    n_envs, n_demos, round_waves = len(envs), int(n_demos), int(round_waves)
+    if n_envs < 1 or n_demos < 1 or round_waves < 1:
+        raise ValueError("scripted_demos: at least one environment, one demonstration and one wave per round")
+    kept, attempted = [], 0
+    while len(kept) < n_demos and attempted < max_episodes:
+        n = min(n_envs * round_waves, max_episodes - attempted)
+        for e in range(n):
+            ep = scripted_episode(envs[e % n_envs], script)
+            if ep[4][-1] == 1.0:
+                kept.append(ep)
+        attempted += n
+    kept = kept[:n_demos]
+    T, p = int(envs[0].max_timesteps), envs[0].env_params
+    shapes = ((T + 1, p['obs']), (T + 1, p['goal']), (T, p['goal']), (T, p['action']), (T,))
+    out = [np.array([ep[j] for ep in kept], dtype=np.float32 if j == 4 else np.float64).reshape((len(kept),) + shapes[j])
+           for j in range(5)]
+    return (*out, attempted)
+
+
+def write_demo_npz_from(path, obs, ag, g, actions, info):
+    """Write episodes in the schema get_demo_data_push.py:91-94 produces: keys acs, obs, info, g, ag, with `info` an object
+    array [n, T] of per-step dicts {'is_success': float32} (`info` here: the flags [n, T]).  Such a file preloads through
+    `ddpg_agent._init_demo_buffer` and through the reference's own."""
+    flags = np.asarray(info)
+    boxed = np.empty(flags.shape, dtype=object)
+    for idx in np.ndindex(*flags.shape):
+        boxed[idx] = {"is_success": np.float32(flags[idx])}
+    np.savez_compressed(path, acs=np.asarray(actions, dtype=np.float64), obs=np.asarray(obs, dtype=np.float64), info=boxed,
+                        g=np.asarray(g, dtype=np.float64), ag=np.asarray(ag, dtype=np.float64))

@@ -798,6 +798,48 @@ def gen_reference_demo(out, demo_num=6):
     print(os.path.basename(dst), {k: (d[k].shape, str(d[k].dtype)) for k in d.files})
 
 
+def gen_reference_push_demo(out, demo_num=2):
+    """A demo file written by the reference's own generator on the push-block stand-in: get_push_demo
+    (get_demo_data_push.py:24-94, executed unmodified, extracted like gen_reference_demo's) driving
+    synthetic.PushBlockGoalEnv(seed=0) until `demo_num` scripted episodes succeeded.  The file is the reference program's
+    output as it wrote it; beside it goes the number of episodes it attempted (the resets it asked for), which the file itself
+    does not record.  synthetic.scripted_demos has to reproduce both (tests/test_scripted_demos_cpu.py)."""
+    import json
+    import math
+
+    from rl_arm_under_sparse_reward_amd.synthetic import PushBlockGoalEnv
+
+    fn = _extract_function(os.path.join(REF, "get_demo_data_push.py"), "get_push_demo")
+    ns = {"np": np, "math": math, "demo_num": demo_num, "print": lambda *a, **k: None}
+    exec(compile(ast.Module(body=[fn], type_ignores=[]), "get_demo_data_push.py:24-94", "exec"), ns)
+    env = PushBlockGoalEnv(seed=0)
+    attempted, reset = [0], env.reset
+
+    def counted_reset():
+        attempted[0] += 1
+        return reset()
+
+    env.reset = counted_reset
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as tmp:
+        os.chdir(tmp)
+        try:
+            ns["get_push_demo"](env, env.env_params)
+        finally:
+            os.chdir(cwd)
+        files = os.listdir(tmp)
+        assert files == [f"bmirobot_{demo_num}_push_demo.npz"], files
+        blob = open(os.path.join(tmp, files[0]), "rb").read()
+    dst = os.path.join(out, f"ref_written_{demo_num}_push_block_demo.npz")
+    with open(dst, "wb") as f:
+        f.write(blob)
+    with open(os.path.join(out, f"ref_written_{demo_num}_push_block_demo.json"), "w") as f:
+        json.dump({"attempted": attempted[0], "env": "synthetic.PushBlockGoalEnv(seed=0)", "demo_num": demo_num}, f)
+        f.write("\n")
+    d = np.load(dst, allow_pickle=True)
+    print(os.path.basename(dst), {k: (d[k].shape, str(d[k].dtype)) for k in d.files}, "attempted", attempted[0])
+
+
 def reference_env_full(reward_type="sparse", distance_threshold=0.05):
     """Dummy env carrying the reference's compute_reward AND _is_success bodies (bmirobot_env_push_F.py:84-90,243-245)."""
     path = os.path.join(REF, "bmirobot_env", "bmirobot_env_push_F.py")
@@ -932,7 +974,7 @@ def main():
     os.makedirs(a.out, exist_ok=True)
     ref = load_reference()
     todo = a.only.split(",") if a.only else ["rng", "her", "reward", "storage", "norm", "ddpg", "ddpg_hparams", "demo", "ckpt", "ourckpt",
-                                             "refdemo", "dense", "rollout"]
+                                             "refdemo", "refpushdemo", "dense", "rollout"]
     if "rng" in todo:
         gen_rng_kat(ref, a.out)
     if "her" in todo:
@@ -955,6 +997,8 @@ def main():
         gen_our_checkpoint(ref, a.out)
     if "refdemo" in todo:
         gen_reference_demo(a.out)
+    if "refpushdemo" in todo:
+        gen_reference_push_demo(a.out)
     if "dense" in todo:
         gen_dense_reward(a.out)
     if "rollout" in todo:
