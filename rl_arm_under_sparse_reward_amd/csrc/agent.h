@@ -224,6 +224,10 @@ struct hp_agent {
     bool dw64 = false;                   // RLARM_DW64: default from batch 1536
     int dw_S = 3;                        // (RLARM_DW64=s<n>)
     DevBuf dw_part, dw_ticket;           // partial tiles / arrival counters
+    // RLARM_ENGINE=chain_wt | chain_plain (A/B; alone or behind an engine name and a comma): store policy of chain outputs that only a
+    // later launch reads (slab8.h, "store policy").  -1: each engine's default -- ordinary stores for the actor-side chains of the
+    // split launch, write-through in k_fb_slab8; 1 (chain_wt) / 0 (chain_plain): write-through / ordinary stores in both
+    int chain_wt = -1;
     bool keep_grads_dbg = false;   // RLARM_KEEP_GRADS=1 (parity tests): the peer optimizer kernels also write the summed gradients out
     bool upd_graph_ok = true;   // hp_agent_sample_and_update replays cached graphs (RLARM_UPDATE_GRAPH=0: eager launches, for A/B)
     bool gather_ahead = true;   // merged kernel: spare workgroups gather update u+1's inputs during update u (while CUs are free)

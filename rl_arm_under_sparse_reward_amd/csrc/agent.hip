@@ -279,8 +279,19 @@ int hp_agent_create(hp_ctx *ctx, const hp_agent_cfg *cfg, hp_agent **out) {
     A(&a->loss_log, LOSS_LOG * 2);
     A(&a->fragF, a->n_arena); A(&a->fragD, a->n_arena); A(&a->fragFT, a->n_arena); A(&a->part, 3 * (Mp / 4));
     {
-        // RLARM_ENGINE = slab8 | slab32 | layers overrides the table below (A/B runs, debugging)
-        const char *e = getenv("RLARM_ENGINE");
+        // RLARM_ENGINE = slab8 | slab32 | layers overrides the table below (A/B runs, debugging).  A second token, alone or behind a
+        // comma, selects a build variant of the engine the table (or the first token) gives: chain_wt | chain_plain, the store
+        // policy of chain outputs that only a later launch reads (agent.h: chain_wt; slab8.h, "store policy")
+        const char *e_all = getenv("RLARM_ENGINE");
+        char e_name[16] = "";
+        for (const char *t = e_all; t && *t;) {
+            const size_t n = strcspn(t, ",");
+            if (n == 8 && strncmp(t, "chain_wt", n) == 0) a->chain_wt = 1;
+            else if (n == 11 && strncmp(t, "chain_plain", n) == 0) a->chain_wt = 0;
+            else if (n < sizeof(e_name)) { memcpy(e_name, t, n); e_name[n] = 0; }
+            t += n + (t[n] == ',' ? 1 : 0);
+        }
+        const char *e = e_name[0] ? e_name : nullptr;
         // the slab engines are specialised: 256-wide hidden layers, network inputs of at most 48 columns (obs + goal +
         // action, padded to 16) and at most 4 action components; any other shape takes the layer-per-launch engine
         const bool slab_shape = a->H == 256 && a->ldx <= 48 && cfg->act_dim <= 4;

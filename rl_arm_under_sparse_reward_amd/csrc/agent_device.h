@@ -134,6 +134,19 @@ __device__ __forceinline__ void wt_store4(float *p, const float4 v) {
     // 5.7 item 1; found when an experiment put this store in front of arithmetic that reused the registers: NaNs)
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
 }
+// Output store of a chain role under its compile-time policy (slab8.h, "store policy"): WT = write-through as above, for bytes a
+// workgroup of the SAME launch loads; otherwise an ordinary store that stays in the XCD's L2 until the kernel-end release writes it
+// back -- for bytes whose first reader is a later launch
+template <bool WT>
+__device__ __forceinline__ void out_store(float *p, float v) {
+    if constexpr (WT) wt_store(p, v);
+    else *p = v;
+}
+template <bool WT>
+__device__ __forceinline__ void out_store4(float *p, const float4 v) {
+    if constexpr (WT) wt_store4(p, v);
+    else *reinterpret_cast<float4 *>(p) = v;
+}
 
 // four consecutive arena elements at once (idx0 a multiple of 4): one vector load per state array, so the cold-cache
 // latency of p / m / v is paid once, not once per element (scalar version: the store to p[idx] may alias the next

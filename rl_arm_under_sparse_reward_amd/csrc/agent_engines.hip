@@ -805,12 +805,15 @@ int enqueue_forward_backward_slab(hp_agent *a, const GatherCtx *gc, bool fuse_ad
         P.n_pref = fit >= 16 ? 16 : (fit >= 8 ? 8 : 0);
         const unsigned grid = n_chain + P.n_plan + P.n_ahead + P.n_pref;
         HP_KLOG("k_fb_slab8");
+        // store policy of the chains' outputs (slab8.h): write-through unless RLARM_ENGINE=chain_plain -- ordinary stores measured no gain
+        // in this launch (batch 512 k8 and 1024)
+        const bool wt = a->chain_wt != 0;
         if (a->s8_rows == 4)
-            hipLaunchKernelGGL(s8r4::k_fb_slab8, dim3(grid), dim3(S8_THREADS), 0, s, P);
+            hipLaunchKernelGGL(wt ? s8r4::k_fb_slab8 : s8r4::k_fb_slab8_plain, dim3(grid), dim3(S8_THREADS), 0, s, P);
         else if (a->s8_rows == 8)
-            hipLaunchKernelGGL(s8r8::k_fb_slab8, dim3(grid), dim3(S8_THREADS), 0, s, P);
+            hipLaunchKernelGGL(wt ? s8r8::k_fb_slab8 : s8r8::k_fb_slab8_plain, dim3(grid), dim3(S8_THREADS), 0, s, P);
         else
-            hipLaunchKernelGGL(s8r16::k_fb_slab8, dim3(grid), dim3(S8_THREADS), 0, s, P);
+            hipLaunchKernelGGL(wt ? s8r16::k_fb_slab8 : s8r16::k_fb_slab8_plain, dim3(grid), dim3(S8_THREADS), 0, s, P);
         HP_CHECK_HIP(hipGetLastError());
     } else {
         // 32-row slabs, forward + backward of a chain in one workgroup; inputs come gathered (enqueue_updates)
@@ -846,19 +849,23 @@ int enqueue_forward_backward_slab(hp_agent *a, const GatherCtx *gc, bool fuse_ad
 
 // ---- one update in the split form: k_fb_split8 (chains + the critic's tiles and optimizer step), then the actor's tiles
 // k_fb_split8 with its role table as leading scalar arguments: word r = role r, byte x = its workgroups on XCD x
-static void launch_split(unsigned grid, hipStream_t s, const FbSplitArgs &Q, int tiles_mode = SPLIT_TILES_ADAM) {
+// TILES: the instantiation of a tiles mode; a_wt: the actor-side chains store write-through (RLARM_ENGINE=chain_wt: k_fb_split8_wt)
+// instead of with ordinary stores (slab8.h, "store policy")
+template <int TILES>
+static void launch_split_as(unsigned grid, hipStream_t s, const FbSplitArgs &Q, const unsigned long long (&w)[SR_N], bool a_wt) {
+    hipLaunchKernelGGL(a_wt ? s8r4::k_fb_split8_wt<TILES> : s8r4::k_fb_split8<TILES>, dim3(grid), dim3(S8_THREADS), 0, s, w[0], w[1], w[2],
+                       w[3], w[4], w[5], w[6], Q);
+}
+static void launch_split(unsigned grid, hipStream_t s, const FbSplitArgs &Q, int tiles_mode, bool a_wt) {
     unsigned long long w[SR_N];
     for (int r = 0; r < SR_N; ++r) {
         w[r] = 0ull;
         for (int x = 0; x < 8; ++x) w[r] |= ((Q.nrole[x] >> (8 * r)) & 0xffull) << (8 * x);
     }
     HP_KLOG(tiles_mode == SPLIT_TILES_PEER ? "k_fb_split8<1>" : (tiles_mode == SPLIT_TILES_GRADS ? "k_fb_split8<2>" : "k_fb_split8<0>"));
-    if (tiles_mode == SPLIT_TILES_PEER)
-        hipLaunchKernelGGL(s8r4::k_fb_split8<SPLIT_TILES_PEER>, dim3(grid), dim3(S8_THREADS), 0, s, w[0], w[1], w[2], w[3], w[4], w[5], w[6], Q);
-    else if (tiles_mode == SPLIT_TILES_GRADS)
-        hipLaunchKernelGGL(s8r4::k_fb_split8<SPLIT_TILES_GRADS>, dim3(grid), dim3(S8_THREADS), 0, s, w[0], w[1], w[2], w[3], w[4], w[5], w[6], Q);
-    else
-        hipLaunchKernelGGL(s8r4::k_fb_split8<SPLIT_TILES_ADAM>, dim3(grid), dim3(S8_THREADS), 0, s, w[0], w[1], w[2], w[3], w[4], w[5], w[6], Q);
+    if (tiles_mode == SPLIT_TILES_PEER) launch_split_as<SPLIT_TILES_PEER>(grid, s, Q, w, a_wt);
+    else if (tiles_mode == SPLIT_TILES_GRADS) launch_split_as<SPLIT_TILES_GRADS>(grid, s, Q, w, a_wt);
+    else launch_split_as<SPLIT_TILES_ADAM>(grid, s, Q, w, a_wt);
 }
 static void split_common(hp_agent *a, FbSplitArgs &Q, int set) {
     Q.sync = a->k1_sync + (set & 1) * SPLIT_SET_WORDS;
@@ -911,7 +918,7 @@ static int enqueue_split_update(hp_agent *a, const GatherCtx *gc, FbBuilt &built
     const unsigned grid = build_split_roles(a, Q, true, gc->t_plan != nullptr, P.n_plan, P.n_ahead, L.tiles);
     {
         ProfScope ps(a, PROF_GEMM_FWD);
-        launch_split(grid, s, Q, mode);
+        launch_split(grid, s, Q, mode, a->chain_wt == 1);
         HP_CHECK_HIP(hipGetLastError());
     }
     // the actor's weight gradients (+ optimizer step): 144 tiles at the reference shapes, one per CU.  The launch clears this
@@ -949,7 +956,7 @@ int enqueue_split_prologue(hp_agent *a, const GatherCtx *gc) {
     const unsigned grid = build_split_roles(a, Q, false, true, 0, 0, 0);
     ProfScope ps(a, PROF_PLAN);   // (once per sequence, with the index draws: not an update's launch)
     // (no tiles here: the instantiation the sequence's updates run, so that a rank executes ONE k_fb_split8)
-    launch_split(grid, a->ctx->stream, Q, gc->seq->tiles_mode);
+    launch_split(grid, a->ctx->stream, Q, gc->seq->tiles_mode, a->chain_wt == 1);
     HP_CHECK_HIP(hipGetLastError());
     return HP_OK;
 }

@@ -28,10 +28,12 @@
 #define S8_LD 260
 #define S8_LDX 52
 #ifdef SLAB_TIMELINE
+#define S8_TL_BUILD 1
 #define S8_STAMP(k) do { if (slab == 0 && threadIdx.x == 0) A.tl[chain * 32 + (k)] = wall_clock64(); } while (0)
 #define S8_TSTAMP(tl, k) do { if ((tl) && threadIdx.x == 0) (tl)[k] = wall_clock64(); } while (0)
 #define S8_WSTAMP(tl, k) do { if ((tl) && (threadIdx.x & 63) == 0) (tl)[(k) + (threadIdx.x >> 6)] = wall_clock64(); } while (0)
 #else
+#define S8_TL_BUILD 0
 #define S8_STAMP(k) do { } while (0)
 #define S8_TSTAMP(tl, k) do { } while (0)
 #define S8_WSTAMP(tl, k) do { } while (0)
@@ -65,10 +67,31 @@ __host__ __device__ __forceinline__ void frag8_offsets(const ArenaMap &am, int i
     if (layer >= 2) off_d = base + w0 + frag8_dx_index(n, k, N);
 }
 
-// Chain outputs are stored WRITE-THROUGH (wt_store, agent_device.h): neutral on its own (40.8 vs 41.1 us/update), and what the
-// split weight-gradient kernels' partial-tile exchange (dw64.h, gemm_lds.h) needs.  (Round 2 also ran the weight-gradient tiles
-// as a second phase of this kernel -- one launch per update: 48.2 vs 40.8 us, removed in round 3; DESIGN.md 3.2,
-// profiles/r02_fused_single_launch.txt.)
+// Store policy of a chain's outputs (template argument WT of the functions below, out_store / out_store4 in agent_device.h):
+//   WT = true   write-through: the bytes are in memory once the wave's stores have drained.  What an in-launch reader needs: the
+//               critic chains (C) of the split launch, whose dA3 / dA2 / dA1 / dQA, h1..h3 and gathered inputs the gated tiles of the
+//               SAME launch load (slab8_split.h), the target chains' Q', and the step scalars (adam_prepare_wt).
+//   WT = false  ordinary stores: they are acknowledged from the XCD's L2 and the kernel-end release publishes them.  For outputs whose
+//               first reader is a LATER launch -- a write-through store is acknowledged from memory across the fabric, and a chain
+//               that ends on one waits a cold round trip for a guarantee nobody uses.
+// The actor-side chain (A, slab8_actor_side.inc) of the split launch k_fb_split8<0|1|2> -- output: first reader
+//   XP gathered input columns (s8_gather, first update of a sequence only)   W1 tiles of the actor's tile launch (k_gemm_lds_adam*, _peer*: next launch)
+//   APh1 / APh2 / APh3 (h1..h3 copies, s8_trunk)                              W2 / W3 / W4 tiles of that launch
+//   dZ, dK3 (s8_small_layer), dK2, dK1 (s8_big_layer)                         W4 / W3 / W2 / W1 tiles of that launch
+//   part[nslab + slab], part[2 nslab + slab] (loss partials)                  loss_finalize: that launch's loss-log workgroup / tile 0
+//   (XP action columns, TP, QP: ordinary stores all along; nothing but diagnostics reads them)
+// None of these has a reader inside the split launch: its tiles load the CRITIC's operands only (build_dw_half(critic)), the gate
+// counters 3-5 carry no data (split_bump: relaxed atomics that order nothing -- the tiles they release overwrite parameters the A
+// chains have finished READING), split_publish is the C chains', the warmers touch weights, the plan / gather workgroups the replay
+// buffer and the other input set.  <1> / <2> (data-parallel ranks) change what the critic's tiles do behind their products, not
+// what they load; a rank's exchange never reads another rank's chain outputs.  So every A-side output takes WT = false in the
+// split launch (RLARM_ENGINE=chain_wt: the write-through instantiation, for A/B), and no A-side output keeps write-through.
+// k_fb_slab8 (both chains; every output's first reader is the weight-gradient launch behind it) stays write-through: ordinary
+// stores (k_fb_slab8_plain, RLARM_ENGINE=chain_plain) measured no gain at batch 512 k8 and a loss at 1024.
+// (History: write-through everywhere measured neutral on the one-kernel engine of round 2, 40.8 vs 41.1 us/update, and the
+// weight-gradient kernels' partial-tile exchange (dw64.h, gemm_lds.h) still needs it for ITS stores.  Round 2 also ran the
+// weight-gradient tiles as a second phase of this kernel -- one launch per update: 48.2 vs 40.8 us, removed in round 3; DESIGN.md
+// 3.2, profiles/r02_fused_single_launch.txt.)
 
 // arguments of k_fb_slab8 (both row counts)
 struct FbSlabArgs {
@@ -233,7 +256,7 @@ __device__ __forceinline__ void s8_ring_step(f32x4 (&c)[S8_NRG], RingSlot *ring,
 // + kh 1's either way), applies the epilogue and writes them out.  Until round 5 the kh 0 waves did all of it while the kh 1 waves
 // waited: at 8 rows the layer's tail was 1.2 us (profiles/r05_ab_chain_small_levers.txt).  A mask word keeps one BYTE per half
 // (bit 8 kh + index of the row among the half's rows), so the two waves of a column write different bytes.
-template <int HH>
+template <int HH, bool WT>
 __device__ __forceinline__ void s8_finish_half(const f32x4 (&c)[S8_NRG], int epi, const float *e, float *pbuf, float *lout,
                                                int ld_out, const s8_mask_t *mask_in, s8_mask_t *mask_out, float *gout, int col,
                                                unsigned long long *wtl) {
@@ -269,10 +292,11 @@ __device__ __forceinline__ void s8_finish_half(const f32x4 (&c)[S8_NRG], int epi
         lout[row * ld_out + col] = o;
         // global copy for the weight-gradient GEMM straight from the register (a wavefront writes 64
         // consecutive floats of one row): no second pass over the LDS slab before the next layer can start
-        if (gout) wt_store(gout + (size_t)row * 256 + col, o);   // operand of the weight-gradient tiles
+        if (gout) out_store<WT>(gout + (size_t)row * 256 + col, o);   // operand of the weight-gradient tiles
     }
     if (mask_out) reinterpret_cast<unsigned char *>(mask_out)[2 * col + HH] = (unsigned char)outbits;
 }
+template <bool WT = true>
 __device__ __forceinline__ void s8_finish(const f32x4 (&c)[S8_NRG], int epi, const float *e, float *pbuf, float *lout,
                                           int ld_out, const s8_mask_t *mask_in = nullptr,
                                           s8_mask_t *mask_out = nullptr, float *gout = nullptr,
@@ -281,8 +305,8 @@ __device__ __forceinline__ void s8_finish(const f32x4 (&c)[S8_NRG], int epi, con
     const int col = 64 * cg + lane;
     static_assert(2 * S8_NRG <= 8 && sizeof(s8_mask_t) == 2, "a half's rows fit one byte of a mask word");
 #if S8_BOTH_HALVES
-    if (kh == 0) s8_finish_half<0>(c, epi, e, pbuf, lout, ld_out, mask_in, mask_out, gout, col, wtl);
-    else s8_finish_half<1>(c, epi, e, pbuf, lout, ld_out, mask_in, mask_out, gout, col, wtl);
+    if (kh == 0) s8_finish_half<0, WT>(c, epi, e, pbuf, lout, ld_out, mask_in, mask_out, gout, col, wtl);
+    else s8_finish_half<1, WT>(c, epi, e, pbuf, lout, ld_out, mask_in, mask_out, gout, col, wtl);
 #else
     // 4-row slabs: the kh 0 waves finish all four rows (measured with both halves finishing two each: 37.16 vs 37.13 us/update at batch
     // 256, 45.03 vs 44.42 at 512 k8 -- the layer is bound by its weight transfers there and four more waves issuing stores only add to
@@ -322,7 +346,7 @@ __device__ __forceinline__ void s8_finish(const f32x4 (&c)[S8_NRG], int epi, con
                 lout[row * ld_out + col] = o;
                 // global copy for the weight-gradient GEMM straight from the register (a wavefront writes 64
                 // consecutive floats of one row): no second pass over the LDS slab before the next layer can start
-                if (gout) wt_store(gout + (size_t)row * 256 + col, o);   // operand of the weight-gradient tiles
+                if (gout) out_store<WT>(gout + (size_t)row * 256 + col, o);   // operand of the weight-gradient tiles
             }
         if (mask_out) mask_out[col] = (s8_mask_t)outbits;
     }
@@ -344,6 +368,8 @@ __device__ __forceinline__ void s8_epi_load(float (&e)[8], int epi, const float 
 
 // out[8][256] = epi(in[8][256] . W): DMA-ring fed.  The first S8_RING blocks of `wlayer` must be in flight at
 // ring base `rbase`; on return the first S8_RING blocks of `nxt` are (if nxt != nullptr) and rbase has advanced.
+// WT: store policy of the global copy gout (see "store policy" at the top of this file)
+template <bool WT = true>
 __device__ __forceinline__ void s8_big_layer(const float *lin, int ld_in, RingSlot *ring, int &rbase,
                                              const float *__restrict__ wlayer, const float *__restrict__ nxt, int epi,
                                              const float *__restrict__ aux, int ldaux, float *pbuf, float *lout,
@@ -371,7 +397,7 @@ __device__ __forceinline__ void s8_big_layer(const float *lin, int ld_in, RingSl
     __builtin_amdgcn_sched_barrier(0);
     S8_TSTAMP(tl2, k2 + 1);
     S8_WSTAMP(wtl, 8);
-    s8_finish(c, epi, e, pbuf, lout, ld_out, mask_in, mask_out, gout, wtl);
+    s8_finish<WT>(c, epi, e, pbuf, lout, ld_out, mask_in, mask_out, gout, wtl);
     S8_TSTAMP(tl2, k2 + 2);
 }
 
@@ -394,6 +420,7 @@ __device__ __forceinline__ void s8_small_prefetch(const float *__restrict__ wlay
 }
 
 // small layer: weights already in registers (s8_small_prefetch), no ring
+template <bool WT = true>
 __device__ __forceinline__ void s8_small_layer(const float *lin, int ld_in, int Kred, const float4 (&b)[6], int epi,
                                                const float *__restrict__ aux, int ldaux, float *pbuf, float *lout,
                                                int ld_out, const s8_mask_t *mask_in = nullptr,
@@ -415,7 +442,7 @@ __device__ __forceinline__ void s8_small_layer(const float *lin, int ld_in, int 
         case 6: s8_small_steps<0, 6>(c, b, a); break;
         default: break;   // other input widths are rejected on the host
     }
-    s8_finish(c, epi, e, pbuf, lout, ld_out, mask_in, mask_out, gout);
+    s8_finish<WT>(c, epi, e, pbuf, lout, ld_out, mask_in, mask_out, gout);
 }
 
 // nout (<= 4) dot products of length 256 for ONE row (wavefront-wide; callers walk rows wave, wave + 8, ... and clamp
@@ -492,11 +519,12 @@ __device__ __forceinline__ float s8_rowdots(const float *lin, int ld_in, int row
     return mine;
 }
 
+template <bool WT = true>
 __device__ __forceinline__ void s8_store(const float *l, int ld, int width, float *g, int ldg) {
     const int per_row = width >> 2;
     for (int f = threadIdx.x; f < S8_ROWS * per_row; f += S8_THREADS) {
         const int r = f / per_row, c4 = f - r * per_row;
-        wt_store4(g + (size_t)r * ldg + 4 * c4, *reinterpret_cast<const float4 *>(l + r * ld + 4 * c4));
+        out_store4<WT>(g + (size_t)r * ldg + 4 * c4, *reinterpret_cast<const float4 *>(l + r * ld + 4 * c4));
     }
 }
 
@@ -518,6 +546,7 @@ __device__ __forceinline__ PlanRec s8_plan_rec(const GatherSrc &G, size_t row0, 
     return G.plan_any[m < G.B ? m : G.B - 1];
 }
 
+template <bool WT = true>   // store policy of the gathered rows' global copy Xout
 __device__ __forceinline__ void s8_gather(float *xin, const GatherSrc &G, const PlanRec rec, int which, size_t row0, int ldx,
                                           int act_off, int act_dim, float max_action, float *Xout,
                                           float *rew_lds = nullptr) {
@@ -548,7 +577,7 @@ __device__ __forceinline__ void s8_gather(float *xin, const GatherSrc &G, const 
             }
         }
         xin[r * S8_LDX + c] = x;
-        if (Xout && (which == 1 || c < act_off)) wt_store(Xout + m * ldx + c, x);
+        if (Xout && (which == 1 || c < act_off)) out_store<WT>(Xout + m * ldx + c, x);
     }
     if (which == 1 && l == 63) {
         float rew = 0.f;
@@ -569,7 +598,8 @@ __device__ __forceinline__ void s8_gather(float *xin, const GatherSrc &G, const 
 }
 
 // xin (K1 wide) -> h1 -> h2 -> h3.  Ring: layer 2 in flight on entry, `nxt` on exit.  m1..m3 (LDS, may be null):
-// ReLU masks of h1..h3 for the backward stages of a merged kernel.
+// ReLU masks of h1..h3 for the backward stages of a merged kernel.  WT: store policy of the global copies g1..g3.
+template <bool WT = true>
 __device__ __forceinline__ void s8_trunk(const float *xin, const NetLayout &l, const float4 (&wb1)[6], const float *wf,
                                          const float *canon, int H,
                                          float *bufA, float *bufB, float *pbuf, float *g1, float *g2, float *g3,
@@ -589,15 +619,15 @@ __device__ __forceinline__ void s8_trunk(const float *xin, const NetLayout &l, c
         if (S8_BOTH_HALVES || (w_ >> 2) == 0) { eb2 = canon[l.b2 + col_]; eb3 = canon[l.b3 + col_]; }
     }
     const float *pe2 = &eb2, *pe3 = &eb3;
-    s8_small_layer(xin, S8_LDX, l.K1, wb1, SE_BIAS_RELU, canon + l.b1, 0, pbuf, bufA, S8_LD, nullptr, m1,
+    s8_small_layer<WT>(xin, S8_LDX, l.K1, wb1, SE_BIAS_RELU, canon + l.b1, 0, pbuf, bufA, S8_LD, nullptr, m1,
                    g1 ? g1 + row0 * H : nullptr, pre3);
     s8_sync();
     S8_TSTAMP(tl, tbase + 1);
-    s8_big_layer(bufA, S8_LD, ring, rbase, wf + l.w2, wf + l.w3, SE_BIAS_RELU, canon + l.b2, 0, pbuf, bufB, S8_LD, nullptr, m2,
+    s8_big_layer<WT>(bufA, S8_LD, ring, rbase, wf + l.w2, wf + l.w3, SE_BIAS_RELU, canon + l.b2, 0, pbuf, bufB, S8_LD, nullptr, m2,
                  tl, 24, g2 ? g2 + row0 * H : nullptr, pe2);
     s8_sync();
     S8_TSTAMP(tl, tbase + 2);
-    s8_big_layer(bufB, S8_LD, ring, rbase, wf + l.w3, nxt, SE_BIAS_RELU, canon + l.b3, 0, pbuf, bufA, S8_LD, nullptr, m3, nullptr,
+    s8_big_layer<WT>(bufB, S8_LD, ring, rbase, wf + l.w3, nxt, SE_BIAS_RELU, canon + l.b3, 0, pbuf, bufA, S8_LD, nullptr, m3, nullptr,
                  0, g3 ? g3 + row0 * H : nullptr, pe3);
     s8_sync();
     S8_TSTAMP(tl, tbase + 3);
@@ -777,7 +807,10 @@ __device__ __forceinline__ void s8_l2_warm(const FbSlabArgs &P, int widx, float 
 }
 
 #ifndef S8_DEVICE_ONLY   // a translation unit that only borrows the device functions (rollout.hip) compiles no kernel of this file
-__global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_fb_slab8(const FbSlabArgs P) {
+// OUT_WT: store policy of both chains' outputs ("store policy" at the top of this file): nothing in this launch loads them.
+// The body of k_fb_slab8 (write-through, the default) and k_fb_slab8_plain (RLARM_ENGINE=chain_plain) below.
+template <bool OUT_WT>
+__device__ __forceinline__ void fb_slab8_body(const FbSlabArgs &P) {
     const FwdSlabArgs &A = P.f;
     const BwdSlabArgs &Bk = P.b;
     __shared__ __attribute__((aligned(16))) float xin[S8_ROWS * S8_LDX];
@@ -845,7 +878,7 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         __builtin_amdgcn_sched_barrier(0);
         if (A.gs.plan) {
             s8_gather(xin, A.gs, rec, 0, row0, A.ldx, A.act_off, ad, A.max_action, nullptr);
-            s8_gather(xin2, A.gs, rec, 1, row0, A.ldx, A.act_off, ad, A.max_action, const_cast<float *>(A.XA), rows[2]);
+            s8_gather<OUT_WT>(xin2, A.gs, rec, 1, row0, A.ldx, A.act_off, ad, A.max_action, const_cast<float *>(A.XA), rows[2]);
         } else {
             s8_load(xin, S8_LDX, A.ldx, A.XT + row0 * A.ldx, A.ldx);
             s8_load(xin2, S8_LDX, A.ldx, A.XA + row0 * A.ldx, A.ldx);
@@ -909,7 +942,7 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         }
         S8_TSTAMP(tl, 13);
         // critic(x, a): forward with global copies (weight gradients) and masks (dX chain below)
-        s8_trunk(xin2, lc, wbcA, on.wf + ca, on.canon + ca, H, bufA, bufB, pbuf, A.CAh1, A.CAh2, A.CAh3, row0, ring, rbase,
+        s8_trunk<OUT_WT>(xin2, lc, wbcA, on.wf + ca, on.canon + ca, H, bufA, bufB, pbuf, A.CAh1, A.CAh2, A.CAh3, row0, ring, rbase,
                  on.wd + ca + lc.w3, tl, 14, msk[0], msk[1], nullptr, pA);
         {
 #pragma unroll
@@ -943,18 +976,19 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         s8_head_bwd_inplace_td(rows, (int)row0, Bk.B, Bk.gamma, Bk.clip_ret, invB, w4c, bufA);   // bufA holds h3 of critic(x, a)
         s8_sync();
         S8_TSTAMP(tl, 19);
-        s8_store(bufA, S8_LD, H, Bk.dA3 + row0 * H, H);
-        s8_big_layer(bufA, S8_LD, ring, rbase, on.wd + ca + lc.w3, on.wd + ca + lc.w2, SE_MASK, nullptr, 0, pbuf, bufB, S8_LD,
+        s8_store<OUT_WT>(bufA, S8_LD, H, Bk.dA3 + row0 * H, H);
+        s8_big_layer<OUT_WT>(bufA, S8_LD, ring, rbase, on.wd + ca + lc.w3, on.wd + ca + lc.w2, SE_MASK, nullptr, 0, pbuf, bufB, S8_LD,
                      msk[1], nullptr, nullptr, 0, Bk.dA2 + row0 * H);
         s8_sync();
         S8_TSTAMP(tl, 20);
-        s8_big_layer(bufB, S8_LD, ring, rbase, on.wd + ca + lc.w2, nullptr, SE_MASK, nullptr, 0, pbuf, bufA, S8_LD, msk[0],
+        s8_big_layer<OUT_WT>(bufB, S8_LD, ring, rbase, on.wd + ca + lc.w2, nullptr, SE_MASK, nullptr, 0, pbuf, bufA, S8_LD, msk[0],
                      nullptr, nullptr, 0, Bk.dA1 + row0 * H);
-        s8_sync();
+        // (plain stores: the barrier only serves the time-line stamp behind it; write-through: the parent's code, kept for A/B)
+        if (OUT_WT || S8_TL_BUILD) s8_sync();
         S8_TSTAMP(tl, 21);
         if (tid < S8_ROWS) {
-            wt_store(Bk.dQA + (row0 + tid) * 16, keep_g);
-            if (tid == 0) wt_store(Bk.part + slab, keep_a);
+            out_store<OUT_WT>(Bk.dQA + (row0 + tid) * 16, keep_g);
+            if (tid == 0) out_store<OUT_WT>(Bk.part + slab, keep_a);
         }
         if (slab == 0 && tid == 0) {   // Adam step scalars for the optimizer kernel that follows
             Bk.st->step += 1;
@@ -966,12 +1000,20 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 #define S8_AFTER_CRITIC_FWD do { } while (0)
 #define S8_AFTER_CRITIC_DX1 do { } while (0)
 #define S8_AFTER_CRITIC_DX do { } while (0)
+#define S8_CHAIN_WT OUT_WT
 #include "slab8_actor_side.inc"
+#undef S8_CHAIN_WT
 #undef S8_AFTER_CRITIC_FWD
 #undef S8_AFTER_CRITIC_DX1
 #undef S8_AFTER_CRITIC_DX
     }
     }
+}
+__global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_fb_slab8(const FbSlabArgs P) {
+    fb_slab8_body<true>(P);
+}
+__global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_fb_slab8_plain(const FbSlabArgs P) {
+    fb_slab8_body<false>(P);
 }
 
 #endif  // S8_DEVICE_ONLY

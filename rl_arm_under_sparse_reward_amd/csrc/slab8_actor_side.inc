@@ -1,7 +1,9 @@
 // slab8_actor_side.inc -- the actor-side chain of the thin-slab engine: actor -> critic(x, pi(x)) -> Q_pi, actor loss, dX through
 // the critic and the actor (ddpg_agent.py:265-277 up to the weight gradients).  Textually included by k_fb_slab8 (slab8.h) and by
 // the split launch k_fb_split8 (slab8_split.h), which both declare the names it uses (A, Bk, on, la, lc, ca, ad, H, ring, rbase,
-// xin, bufA, bufB, pbuf, dq, rows, dz, w1t, msk, row0, slab, nslab, tid, wave, lane, invB, tl) and the hooks S8_AFTER_CRITIC_FWD / _DX1 / _DX.
+// xin, bufA, bufB, pbuf, dq, rows, dz, w1t, msk, row0, slab, nslab, tid, wave, lane, invB, tl) and the hooks S8_AFTER_CRITIC_FWD / _DX1 / _DX
+// and S8_CHAIN_WT, the store policy of this chain's outputs (slab8.h, "store policy": true = write-through, false = ordinary stores
+// for outputs only a later launch reads).
     s8_ring_prologue<0, S8_PRO_FIRST>(ring, rbase, on.wf + la.w2);   // (as on the critic side: -0.4 us/update at batch 1024, neutral at 256)
     const PlanRec rec = s8_plan_rec(A.gs, row0);
     float4 wba[6], wbc[6], wh[4], wq[4], wb4[6];
@@ -14,7 +16,7 @@
     if (ekh0_) ebP[0] = on.canon[la.b1 + ecol_];
 #endif
     __builtin_amdgcn_sched_barrier(0);   // (as on the critic side: what the first layer does not need follows the input loads)
-    if (A.gs.plan) s8_gather(xin, A.gs, rec, 2, row0, A.ldx, A.act_off, ad, A.max_action, A.XP);
+    if (A.gs.plan) s8_gather<S8_CHAIN_WT>(xin, A.gs, rec, 2, row0, A.ldx, A.act_off, ad, A.max_action, A.XP);
     else s8_load(xin, S8_LDX, A.ldx, A.XP + row0 * A.ldx, A.ldx);
     s8_ring_prologue<S8_PRO_FIRST, S8_RING>(ring, rbase, on.wf + la.w2);
     __builtin_amdgcn_sched_barrier(0);
@@ -43,7 +45,7 @@
 #endif
     __builtin_amdgcn_sched_barrier(0);
     s8_sync();
-    s8_trunk(xin, la, wba, on.wf, on.canon, H, bufA, bufB, pbuf, A.APh1, A.APh2, A.APh3, row0, ring, rbase, on.wf + ca + lc.w2,
+    s8_trunk<S8_CHAIN_WT>(xin, la, wba, on.wf, on.canon, H, bufA, bufB, pbuf, A.APh1, A.APh2, A.APh3, row0, ring, rbase, on.wf + ca + lc.w2,
              tl, 1, msk[2], msk[3], msk[4], pP);
     S8_TSTAMP(tl, 5);
     float u_mine[S8_RPW], th_mine[S8_RPW];
@@ -140,25 +142,29 @@
                     v = gt * (1.f - th_mine[i] * th_mine[i]);
                 }
                 dz[rr * 20 + lane] = v;
-                wt_store(Bk.dZ + m * 16 + lane, v);
+                out_store<S8_CHAIN_WT>(Bk.dZ + m * 16 + lane, v);
             }
         }
     }
     s8_sync();
     S8_TSTAMP(tl, 17);
-    s8_small_layer(dz, 20, 16, wb4, SE_MASK, nullptr, 0, pbuf, bufB, S8_LD, msk[4], nullptr, Bk.dK3 + row0 * H);
+    s8_small_layer<S8_CHAIN_WT>(dz, 20, 16, wb4, SE_MASK, nullptr, 0, pbuf, bufB, S8_LD, msk[4], nullptr, Bk.dK3 + row0 * H);
     s8_sync();
     S8_TSTAMP(tl, 18);
-    s8_big_layer(bufB, S8_LD, ring, rbase, on.wd + la.w3, on.wd + la.w2, SE_MASK, nullptr, 0, pbuf, bufA, S8_LD, msk[3], nullptr,
+    s8_big_layer<S8_CHAIN_WT>(bufB, S8_LD, ring, rbase, on.wd + la.w3, on.wd + la.w2, SE_MASK, nullptr, 0, pbuf, bufA, S8_LD, msk[3], nullptr,
                  nullptr, 0, Bk.dK2 + row0 * H);
     s8_sync();
     S8_TSTAMP(tl, 19);
-    s8_big_layer(bufA, S8_LD, ring, rbase, on.wd + la.w2, nullptr, SE_MASK, nullptr, 0, pbuf, bufB, S8_LD, msk[2], nullptr,
+    s8_big_layer<S8_CHAIN_WT>(bufA, S8_LD, ring, rbase, on.wd + la.w2, nullptr, SE_MASK, nullptr, 0, pbuf, bufB, S8_LD, msk[2], nullptr,
                  nullptr, 0, Bk.dK1 + row0 * H);
-    s8_sync();
+    // The end of the chain.  Nothing below reads the LDS or another wave's registers: the loss partials are in thread 0's registers
+    // since the actor loss above, so they need no barrier.  With ordinary stores nothing waits for publication either -- no drain, no
+    // barrier: each wave ends behind its own last store and the kernel-end release publishes them.  What stays: the barrier of the
+    // time-line build (stamp 20 = EVERY wave has issued its dK1 stores), and the write-through instantiation as it was (A/B).
+    if (S8_CHAIN_WT || S8_TL_BUILD) s8_sync();
     S8_TSTAMP(tl, 20);
     if (tid == 0) {
-        wt_store(Bk.part + nslab + slab, keep_q);
-        wt_store(Bk.part + 2 * nslab + slab, keep_u);
+        out_store<S8_CHAIN_WT>(Bk.part + nslab + slab, keep_q);
+        out_store<S8_CHAIN_WT>(Bk.part + 2 * nslab + slab, keep_u);
     }
     S8_TSTAMP(tl, 21);

@@ -92,10 +92,13 @@ __device__ __forceinline__ void adam_prepare_wt(AgentDevState *st, const AdamCfg
 
 // TILES: what the in-launch tiles do behind their products (slab8_split_args.h: SPLIT_TILES_*); one kernel per form, so that the
 // single-rank launch keeps its own register allocation and code placement
-template <int TILES>
-__global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void k_fb_split8(unsigned long long r0, unsigned long long r1, unsigned long long r2, unsigned long long r3, unsigned long long r4,
-                 unsigned long long r5, unsigned long long r6, const FbSplitArgs Q) {
+// A_WT: store policy of the actor-side chains' outputs (slab8.h, "store policy"): false = ordinary stores, the default -- every one
+// of them is first read by the launch behind this one; true = write-through as the C and T chains' (RLARM_ENGINE=chain_wt, for A/B)
+// The body of the two kernels below (k_fb_split8<TILES>, k_fb_split8_wt<TILES>): a profiler lists the default under the name it
+// always had.
+template <int TILES, bool A_WT>
+__device__ __forceinline__ void fb_split8_body(unsigned long long r0, unsigned long long r1, unsigned long long r2, unsigned long long r3,
+                                               unsigned long long r4, unsigned long long r5, unsigned long long r6, const FbSplitArgs &Q) {
     static_assert(SR_N == 7, "the role table is seven preloaded words");
     const SplitRoles R{{r0, r1, r2, r3, r4, r5, r6}};
     const FbSlabArgs &P = Q.s;
@@ -357,10 +360,25 @@ void k_fb_split8(unsigned long long r0, unsigned long long r1, unsigned long lon
 #define S8_AFTER_CRITIC_FWD do { split_bump(Q.sync, 3); } while (0)
 #define S8_AFTER_CRITIC_DX1 do { split_bump(Q.sync, 4); } while (0)
 #define S8_AFTER_CRITIC_DX do { split_bump(Q.sync, 5); SPLIT_STAMP(1); } while (0)
+#define S8_CHAIN_WT A_WT
 #include "slab8_actor_side.inc"
+#undef S8_CHAIN_WT
 #undef S8_AFTER_CRITIC_FWD
 #undef S8_AFTER_CRITIC_DX1
 #undef S8_AFTER_CRITIC_DX
         SPLIT_STAMP(3);
     }
+}
+
+template <int TILES>
+__global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_fb_split8(unsigned long long r0, unsigned long long r1, unsigned long long r2, unsigned long long r3, unsigned long long r4,
+                 unsigned long long r5, unsigned long long r6, const FbSplitArgs Q) {
+    fb_split8_body<TILES, false>(r0, r1, r2, r3, r4, r5, r6, Q);
+}
+template <int TILES>   // RLARM_ENGINE=chain_wt: the actor-side chains store write-through too
+__global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_fb_split8_wt(unsigned long long r0, unsigned long long r1, unsigned long long r2, unsigned long long r3, unsigned long long r4,
+                    unsigned long long r5, unsigned long long r6, const FbSplitArgs Q) {
+    fb_split8_body<TILES, true>(r0, r1, r2, r3, r4, r5, r6, Q);
 }
