@@ -79,6 +79,12 @@ int hp_agent_debug_timeline(hp_agent *ag, uint64_t *out192);
 int hp_state_debug_dirty_scan(hp_buffer *buf, const uint32_t *stamps_host, int64_t current_size, uint32_t since, int64_t max_dirty,
                               int64_t *slots_out, int64_t *n_dirty, int32_t *overflow);
 
+/* diagnostic: the staging behind hp_agent_train_cycle as the host sees it (no device work, no synchronisation): *gen = the
+ * generation captured cycles are keyed on (moves whenever what they read moves), *ring_bytes = size of each block of the pinned ring
+ * the opening launch reads fresh episodes from (0: none allocated), *ring_block = the block of the most recent cycle, -1 when its
+ * episodes went through an H2D copy instead.  Any pointer may be NULL. */
+int hp_buffer_debug_stage_info(hp_buffer *buf, uint64_t *gen, uint64_t *ring_bytes, int32_t *ring_block);
+
 /* test hook: the most timesteps (waves x T) one launch of hp_rollout_waves on this block may hold, in place of
  * HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS (0 = that default again), so that a small call is issued as several launches */
 int hp_rollout_debug_set_launch_cap(hp_rollout *ro, int64_t timesteps);

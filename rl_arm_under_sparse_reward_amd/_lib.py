@@ -81,7 +81,7 @@ PARALLEL_DRAW_MIN_BATCH = 65536   # HP_PARALLEL_DRAW_MIN_BATCH: the measured cro
 DEBUG_SYMBOLS = {"hp_ctx_launch_floor", "hp_ctx_event_pair_us", "hp_ctx_clock_mhz", "hp_ctx_calibrate", "hp_buffer_sample_device_us",
                  "hp_buffer_sample_dev_us", "hp_buffer_sample_dev_fast_us",
                  "hp_mt_jump_poly", "hp_rng_parallel_info", "hp_rng_debug_set_window", "hp_rng_debug_table_ms",
-                 "hp_state_debug_dirty_scan", "hp_rollout_debug_set_launch_cap",
+                 "hp_state_debug_dirty_scan", "hp_rollout_debug_set_launch_cap", "hp_buffer_debug_stage_info",
                  "hp_agent_set_adam", "hp_agent_debug_chain", "hp_agent_debug_timeline", "hp_agent_update_kernels"}
 
 # name -> (restype, argtypes); every symbol declared in include/rlarm_hip.h and include/rlarm_hip_debug.h
@@ -128,6 +128,7 @@ PROTOTYPES = {
     "hp_buffer_store_done": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_int32)]),
     "hp_buffer_info": (C.c_int, [C.c_void_p, i64p, i64p, i64p, C.POINTER(C.c_int32)]),
     "hp_buffer_last_slots": (C.c_int, [C.c_void_p, i64p, C.c_int64]),
+    "hp_buffer_debug_stage_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     "hp_buffer_read": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, f64p]),
     "hp_buffer_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.POINTER(SampleOut)]),
     "hp_buffer_sample_device_us": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, f64p,

@@ -162,12 +162,17 @@ struct SeqKey {
     double future_p, sq_threshold;
     bool open;          // the cycle opens with k_cycle_open
     uint64_t gen;       // hp_buffer::gen
+    int ring_slot;      // block of hp_buffer::ring that k_cycle_open reads (its address is a kernel argument); -1: the device staging
     bool operator==(const SeqKey &o) const {
         return kind == o.kind && b == o.b && on == o.on && gn == o.gn && rng == o.rng && n == o.n && n_new == o.n_new &&
-               future_p == o.future_p && sq_threshold == o.sq_threshold && open == o.open && gen == o.gen;
+               future_p == o.future_p && sq_threshold == o.sq_threshold && open == o.open && gen == o.gen &&
+               ring_slot == o.ring_slot;
     }
 };
-// One cycle graph and up to eight update graphs (a loop uses one or two chunk lengths), oldest evicted first.
+// Cycle graphs: one per block of the pinned ring plus one for the forms that read the device staging (ring_slot -1: the _pinned
+// and _dev entry points, RLARM_CYCLE_OPEN=copy), which covers a run that keeps ONE n_new and n_batches -- what a training run
+// does; a caller that alternates several n_new recaptures (one stream synchronisation each), as it did with the single cycle graph
+// before the ring.  Up to eight update graphs (a loop uses one or two chunk lengths).  Oldest evicted first.
 struct GraphCache {
     struct Entry {
         SeqKey key;
@@ -184,7 +189,7 @@ struct GraphCache {
     }
     hipGraphExec_t put(const SeqKey &k, GraphExec &&x) {
         const auto same_kind = [&](const Entry &e) { return e.key.kind == k.kind; };
-        if (std::count_if(entries.begin(), entries.end(), same_kind) >= (k.kind == SeqKey::CYCLE ? 1 : 8))
+        if (std::count_if(entries.begin(), entries.end(), same_kind) >= (k.kind == SeqKey::CYCLE ? decltype(hp_buffer::ring)::SLOTS + 1 : 8))
             entries.erase(std::find_if(entries.begin(), entries.end(), same_kind));
         entries.push_back({k, std::move(x)});
         return entries.back().exec.h;
@@ -276,6 +281,7 @@ struct hp_agent {
     unsigned *fault_host = nullptr;      // pinned + mapped mirror of the fault word (agent_check_fault), and its device address
     unsigned *fault_host_dev = nullptr;
     bool cycle_open = true;              // RLARM_CYCLE_OPEN=0: slots / scatter / plans / normalizer as separate launches
+    bool cycle_open_copy = false;        // RLARM_CYCLE_OPEN=copy: the opening launch behind an H2D copy of the episodes (A/B, tests)
     // profiling
     bool prof = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -509,6 +515,7 @@ int enqueue_adam(hp_agent *a, const GatherCtx *gc = nullptr, unsigned *reset_syn
 int enqueue_polyak(hp_agent *a);
 // cycle_open.hip: slots + scatter + normalizer update + first minibatch plans of a cycle as one launch
 bool cycle_open_fits(const hp_agent *a, int64_t n_new);
+bool cycle_open_direct_fits(const hp_buffer *b, int64_t n_new);   // can it load the episodes from the pinned ring itself?
 int cycle_open_launch(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, PlanRec *norm_plan, int n_first,
                       double future_p, bool recompute);
 // utils.sync_grads (utils.py:43-48) + both Adam steps of update gc->u as the peer exchange's optimizer kernel(s) (peer.hip)

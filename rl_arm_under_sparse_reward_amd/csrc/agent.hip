@@ -327,6 +327,8 @@ int hp_agent_create(hp_ctx *ctx, const hp_agent_cfg *cfg, hp_agent **out) {
         a->upd_graph_ok = tri("RLARM_UPDATE_GRAPH") != 0;
         a->keep_grads_dbg = tri("RLARM_KEEP_GRADS") == 1;
         a->cycle_open = tri("RLARM_CYCLE_OPEN") != 0;
+        const char *co = getenv("RLARM_CYCLE_OPEN");
+        a->cycle_open_copy = co && strcmp(co, "copy") == 0;
         a->split_mode = tri("RLARM_SPLIT");
         // weight gradients: 64 x 64 tiles with split batch rows (dw64.h) where the 32 x 32 tiles are L2-bound
         // (us/update, 32 x 32 tiles vs dw64: 56.6 / 58.9 at batch 1024, 85.8 / 85.1 at 1536, 93.9 / 92.2 at 2048, 146 / 128 at 4096)
@@ -515,7 +517,7 @@ int hp_agent_sample_and_update(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *
     HP_TRY(peer_check_alive(a->peer, "hp_agent_sample_and_update"));
     HP_TRY(agent_check_fault(a, "hp_agent_sample_and_update"));
     HP_REQUIRE(b->current_size > 0, HP_ERR_EMPTY, "high <= 0");
-    return run_seq(a, {SeqKey::UPDATES, b, on, gn, rng, n_updates, 0, future_p, sq_threshold, false, b->gen});
+    return run_seq(a, {SeqKey::UPDATES, b, on, gn, rng, n_updates, 0, future_p, sq_threshold, false, b->gen, -1});
 }
 
 int hp_agent_forward_backward(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, double future_p,
@@ -726,12 +728,16 @@ int hp_agent_train_cycle(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp
     HP_SERIALISE(a);
     HP_REQUIRE(obs && ag_host && g && actions, HP_ERR_INVALID, "hp_agent_train_cycle: null episode array");
     HP_TRY(train_cycle_checks(a, b, n_new, n_batches, "hp_agent_train_cycle"));
-    // 1. episodes -> pinned -> device staging (eager: the source pointers change per call); slots and scatter: part of the
-    // opening launch of the graph, or eager launches as well when that launch is switched off / would not fit the CUs
+    // 1. episodes -> a block of the pinned ring, which the opening launch of the graph reads in place (one cached graph per block:
+    // the block's address is a kernel argument) and whose fence goes behind that graph.  RLARM_CYCLE_OPEN=copy, or episodes too
+    // long for the launch's registers: pinned -> H2D copy -> device staging in front of the graph instead.  Slots and scatter:
+    // part of the opening launch, or eager launches as well when that launch is switched off / would not fit the CUs
     const bool open = a->cycle_open && cycle_open_fits(a, n_new);
-    if (open) HP_TRY(buffer_stage_for_cycle(b, obs, ag_host, g, actions, n_new));
+    const bool direct = open && !a->cycle_open_copy && cycle_open_direct_fits(b, n_new);
+    if (open) HP_TRY(buffer_stage_for_cycle(b, obs, ag_host, g, actions, n_new, direct));
     else HP_TRY(buffer_stage_and_store(b, rng, obs, ag_host, g, actions, n_new));
-    return run_seq(a, {SeqKey::CYCLE, b, on, gn, rng, n_batches, n_new, future_p, sq_threshold, open, b->gen});
+    HP_TRY(run_seq(a, {SeqKey::CYCLE, b, on, gn, rng, n_batches, n_new, future_p, sq_threshold, open, b->gen, direct ? b->ring_cur : -1}));
+    return direct ? buffer_mark_cycle_block(b) : HP_OK;
 }
 
 // The same cycle on episodes that lie in a host block registered with the device (hp_host_register: the feeder's shared-memory
@@ -744,7 +750,7 @@ int hp_agent_train_cycle_pinned(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm 
     HP_TRY(train_cycle_checks(a, b, n_new, n_batches, "hp_agent_train_cycle_pinned"));
     const bool open = a->cycle_open && cycle_open_fits(a, n_new);
     HP_TRY(buffer_stage_pinned(b, rng, block, n_new, ticket, !open));
-    return run_seq(a, {SeqKey::CYCLE, b, on, gn, rng, n_batches, n_new, future_p, sq_threshold, open, b->gen});
+    return run_seq(a, {SeqKey::CYCLE, b, on, gn, rng, n_batches, n_new, future_p, sq_threshold, open, b->gen, -1});
 }
 
 // The same cycle on episodes that lie in DEVICE memory in that layout (a wave collected by hp_rollout_step): the staging is a
@@ -757,7 +763,7 @@ int hp_agent_train_cycle_dev(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn
     HP_TRY(train_cycle_checks(a, b, n_new, n_batches, "hp_agent_train_cycle_dev"));
     const bool open = a->cycle_open && cycle_open_fits(a, n_new);
     HP_TRY(buffer_stage_dev(b, rng, block_dev, n_new, !open));
-    return run_seq(a, {SeqKey::CYCLE, b, on, gn, rng, n_batches, n_new, future_p, sq_threshold, open, b->gen});
+    return run_seq(a, {SeqKey::CYCLE, b, on, gn, rng, n_batches, n_new, future_p, sq_threshold, open, b->gen, -1});
 }
 
 // which launch structure a sequence of n_updates sampled updates WITH optimizer steps takes on this agent: 0 = chain launch +

@@ -600,6 +600,7 @@ static int buffer_stage(hp_buffer *b, const double *obs, const double *ag, const
     HP_CHECK_HIP(hipMemcpyAsync(dst, h, n0 + n1 + n2 + n3, hipMemcpyHostToDevice, s));
     HP_TRY(b->pin.mark(s));
     b->staged_n = n_new;
+    b->ring_cur = -1;
     return HP_OK;
 }
 
@@ -645,6 +646,7 @@ int buffer_stage_pinned(hp_buffer *b, hp_rng *rng, const double *block, int64_t 
     HP_CHECK_HIP(hipEventRecord(ev, s));
     if (ticket) *ticket = t;
     b->staged_n = n_new;
+    b->ring_cur = -1;
     if (store_now) {
         HP_TRY(rng_launch_slots(rng, b, n_new, b->st_slots.as<int64_t>()));
         hipLaunchKernelGGL(k_store_scatter, dim3((unsigned)(n_new * STORE_PARTS)), dim3(256), 0, s, b->st_slots.as<long long>(),
@@ -672,6 +674,7 @@ int buffer_stage_dev(hp_buffer *b, hp_rng *rng, const double *block_dev, int64_t
     b->st_act = reinterpret_cast<double *>(dst + n0 + n1 + n2);
     HP_CHECK_HIP(hipMemcpyAsync(dst, block_dev, n0 + n1 + n2 + n3, hipMemcpyDeviceToDevice, s));
     b->staged_n = n_new;
+    b->ring_cur = -1;
     if (store_now) {
         HP_TRY(rng_launch_slots(rng, b, n_new, b->st_slots.as<int64_t>()));
         hipLaunchKernelGGL(k_store_scatter, dim3((unsigned)(n_new * STORE_PARTS)), dim3(256), 0, s, b->st_slots.as<long long>(),
@@ -685,10 +688,47 @@ int buffer_stage_dev(hp_buffer *b, hp_rng *rng, const double *block_dev, int64_t
     return HP_OK;
 }
 
+// direct form: the episodes go as far as a block of the pinned ring; k_cycle_open loads them from there and fills st_* itself
+static int buffer_stage_ring(hp_buffer *b, const double *obs, const double *ag, const double *g, const double *actions,
+                             int64_t n_new) {
+    const size_t n0 = n_new * b->ep_obs() * 8, n1 = n_new * b->ep_ag() * 8, n2 = n_new * b->ep_g() * 8,
+                 n3 = n_new * b->ep_act() * 8;
+    HP_TRY(stage_ensure(b, b->st_obs, n0 + n1 + n2 + n3));
+    char *dst = b->st_obs.as<char>();
+    b->st_ag = reinterpret_cast<double *>(dst + n0);
+    b->st_g = reinterpret_cast<double *>(dst + n0 + n1);
+    b->st_act = reinterpret_cast<double *>(dst + n0 + n1 + n2);
+    HipStageApi api;
+    int idx = -1;
+    bool moved = false;
+    HP_TRY(b->ring.acquire(api, n0 + n1 + n2 + n3, &idx, &moved));   // waits for the launch that last read this block
+    if (moved) ++b->gen;
+    char *h = static_cast<char *>(b->ring.slot[idx].host);
+    memcpy(h, obs, n0);
+    memcpy(h + n0, ag, n1);
+    memcpy(h + n0 + n1, g, n2);
+    memcpy(h + n0 + n1 + n2, actions, n3);
+    b->staged_n = n_new;
+    b->ring_cur = idx;
+    return HP_OK;
+}
+
+// the ring block of the cycle just enqueued may be overwritten once that cycle's opening launch has run.  The cycle IS enqueued
+// when this is called: if the fence cannot be placed, the stream is drained instead, so the block is never left readable by a
+// queued launch and unfenced; the failure is still reported.
+int buffer_mark_cycle_block(hp_buffer *b) {
+    if (b->ring_cur < 0) return HP_OK;
+    HipStageApi api;
+    const int st = b->ring.mark(api, b->ring_cur, b->ctx->stream);
+    if (st != HP_OK) (void)hipStreamSynchronize(b->ctx->stream);
+    return st;
+}
+
 int buffer_stage_for_cycle(hp_buffer *b, const double *obs, const double *ag, const double *g, const double *actions,
-                           int64_t n_new) {
+                           int64_t n_new, bool direct) {
     HP_TRY(stage_ensure(b, b->st_slots, n_new * 8));
-    HP_TRY(buffer_stage(b, obs, ag, g, actions, n_new));
+    if (direct) HP_TRY(buffer_stage_ring(b, obs, ag, g, actions, n_new));
+    else HP_TRY(buffer_stage(b, obs, ag, g, actions, n_new));
     b->current_size = (b->current_size + n_new < b->size) ? b->current_size + n_new : b->size;
     b->n_transitions_stored += (int64_t)b->T * n_new;
     return HP_OK;
@@ -819,6 +859,15 @@ int hp_buffer_info(hp_buffer *b, int64_t *size, int64_t *current_size, int64_t *
     if (current_size) *current_size = b->current_size;
     if (n_transitions_stored) *n_transitions_stored = b->n_transitions_stored;
     if (T) *T = b->T;
+    return HP_OK;
+}
+
+int hp_buffer_debug_stage_info(hp_buffer *b, uint64_t *gen, uint64_t *ring_bytes, int32_t *ring_block) {
+    HP_REQUIRE(b, HP_ERR_INVALID, "hp_buffer_debug_stage_info: null handle");
+    HP_SERIALISE(b);
+    if (gen) *gen = b->gen;
+    if (ring_bytes) *ring_bytes = b->ring.bytes;
+    if (ring_block) *ring_block = b->ring_cur;
     return HP_OK;
 }
 
@@ -1284,6 +1333,10 @@ void hp_buffer_destroy(hp_buffer *b) {
     b->st_obs.release();
     b->st_slots.release();
     b->pin.release();
+    {
+        HipStageApi api;
+        b->ring.release(api);
+    }
     b->plan.release();
     b->out.release();
     delete b;

@@ -16,6 +16,13 @@
 // results with agent-scope loads.  The launch is 2 + OPEN_PARTS * n_new workgroups -- far fewer than the CUs, all resident at
 // once, so the polls cannot starve the producer; they are bounded all the same (a timeout is counted in AgentDevState and
 // reported by hp_agent_get_losses).  The last workgroup to leave clears the flags for the next replay of the graph.
+//
+// Direct form (hp_agent_train_cycle; OpenArgs::pin): the staged episodes are not on the device yet -- they lie in a pinned host
+// block (hp_buffer::ring) and no copy runs in front of the launch.  The scatter workgroups load the block over the bus as their
+// FIRST act, 16 bytes per lane and every load of a thread before its first store, while workgroup 0 is still drawing the slots;
+// they write the device staging st_* from registers (write-through, then a count in sync[3]), wait for the slots as before and
+// write the buffer rows from the same registers.  The normalizer gathers by index, which must not cross the bus: it waits for
+// sync[3] to reach the number of scatter workgroups as well as for its plan, and reads the device staging with agent-scope loads.
 #include "mt19937_device.h"
 #include "norm_device.h"
 #include "store_device.h"
@@ -52,7 +59,11 @@ struct OpenArgs {
     int o_std_f32, g_std_f32;
     int chunk_rows;
     // hand-off
-    unsigned *sync;               // [0] slots ready, [1] normalizer plan ready, [2] workgroups that have left
+    unsigned *sync;               // [0] slots ready, [1] normalizer plan ready, [2] workgroups that have left,
+                                  // [3] direct form: scatter workgroups whose share of the device staging is written
+    // direct form: the staged batch in a pinned host block (device address; nullptr: s_obs .. s_act were filled by a copy)
+    const double *pin;
+    StageBlock blk;
     AgentDevState *dev;
     unsigned *fault, *fault_host; // the agent's sticky fault word and its pinned host mirror (agent.h: handoff_fault)
 };
@@ -65,11 +76,12 @@ __device__ __forceinline__ void open_publish(unsigned *flag) {
 
 // false (to every thread of the workgroup): the poll gave up -- the caller must NOT consume what it waited for (slots or plan
 // that are not ready would corrupt the replay buffer / the normalizer silently); the fault word makes the next host call fail
-__device__ __forceinline__ bool open_wait(unsigned *flag, const OpenArgs &A) {
+__device__ __forceinline__ bool open_wait(unsigned *flag, const OpenArgs &A, unsigned want = 1u) {
     __shared__ int s_open_ok;
+    __syncthreads();   // (a second wait of the same workgroup: everyone has read the first one's verdict)
     if (threadIdx.x == 0) {
         int spins = 0;
-        while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u && ++spins < (1 << 22))
+        while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want && ++spins < (1 << 22))
             __builtin_amdgcn_s_sleep(2);
         if (spins >= (1 << 22)) {
             atomicAdd(&A.dev->open_timeouts, 1u);
@@ -87,7 +99,33 @@ __device__ __forceinline__ void open_leave(unsigned *sync) {   // thread 0 of ev
         __hip_atomic_store(sync + 0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(sync + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(sync + 3, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+
+// a scatter workgroup of the direct form (w of n_wg)
+__device__ __forceinline__ void open_scatter_direct(const OpenArgs &A, int w, int n_wg, char *lds) {
+    const unsigned gtid = (unsigned)w * OPEN_THREADS + threadIdx.x, nthreads = (unsigned)n_wg * OPEN_THREADS;
+    double v[STORE_DIRECT_CHUNKS][2];
+    stage_block_load(A.pin, A.blk.nd, gtid, nthreads, v);
+    stage_block_put(const_cast<double *>(A.s_obs), A.blk.nd, gtid, nthreads, v);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave: its write-through stores have completed
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_fetch_add(A.sync + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!open_wait(A.sync + 0, A)) return;
+    // win[e]: slot of staged episode e, -1 where a later one has the same slot (store_device.h)
+    long long *raw = reinterpret_cast<long long *>(lds), *win = raw + A.inc;
+    for (long long e = threadIdx.x; e < A.inc; e += OPEN_THREADS)
+        raw[e] = __hip_atomic_load(A.slots + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    for (long long e = threadIdx.x; e < A.inc; e += OPEN_THREADS) {
+        int dup = 0;
+        for (long long j = e + 1; j < A.inc; ++j) dup |= (raw[j] == raw[e]);
+        win[e] = dup ? -1ll : raw[e];
+    }
+    if (threadIdx.x == 0) A.slot_epoch[raw[w / OPEN_PARTS]] = *A.epoch;   // as store_scatter_share: one stamp per (episode, part)
+    __syncthreads();
+    stage_block_scatter(A.blk, win, gtid, nthreads, v, A.obs, A.ag, A.g, A.act);
 }
 
 __global__ __launch_bounds__(OPEN_THREADS) void k_cycle_open(const OpenArgs A) {
@@ -112,11 +150,20 @@ __global__ __launch_bounds__(OPEN_THREADS) void k_cycle_open(const OpenArgs A) {
             A.meta->n_transitions_stored += (long long)A.T * A.inc;   // replay_buffer.py:43
             open_leave(A.sync);
         }
+    } else if (role == 1 && A.pin) {
+        if (open_wait(A.sync + 1, A) && open_wait(A.sync + 3, A, gridDim.x - 2u))
+            norm_update_from_plan_body<true, true>(A.onz, A.gnz, A.norm_plan, (long long)A.T, A.s_obs, A.s_ag, A.s_g, A.T, A.obs_dim,
+                                                   A.goal_dim, A.clip_obs, A.recompute, A.o_eps_sq, A.o_std_f32, A.g_eps_sq,
+                                                   A.g_std_f32, A.chunk_rows, open_lds);
+        if (threadIdx.x == 0) open_leave(A.sync);
     } else if (role == 1) {
         if (open_wait(A.sync + 1, A))
             norm_update_from_plan_body<true>(A.onz, A.gnz, A.norm_plan, (long long)A.T, A.s_obs, A.s_ag, A.s_g, A.T, A.obs_dim,
                                              A.goal_dim, A.clip_obs, A.recompute, A.o_eps_sq, A.o_std_f32, A.g_eps_sq, A.g_std_f32,
                                              A.chunk_rows, open_lds);
+        if (threadIdx.x == 0) open_leave(A.sync);
+    } else if (A.pin) {
+        open_scatter_direct(A, role - 2, (int)gridDim.x - 2, open_lds);
         if (threadIdx.x == 0) open_leave(A.sync);
     } else {
         const int w = role - 2;
@@ -131,6 +178,15 @@ __global__ __launch_bounds__(OPEN_THREADS) void k_cycle_open(const OpenArgs A) {
 // can the cycle open as one launch?  (every workgroup must be resident at once: the consumers poll)
 bool cycle_open_fits(const hp_agent *a, int64_t n_new) {
     return 2 + OPEN_PARTS * n_new <= (int64_t)a->ctx->cu_count;
+}
+
+// Can the scatter workgroups take the staged batch from the pinned ring themselves?  Every thread keeps its chunks in registers
+// across the wait for the slots, and the winners' table lies in the launch's LDS (at least the draw's 4 x 624 words).
+bool cycle_open_direct_fits(const hp_buffer *b, int64_t n_new) {
+    const uint64_t nd = (uint64_t)n_new * (b->ep_obs() + b->ep_ag() + b->ep_g() + b->ep_act());
+    const uint64_t threads = (uint64_t)OPEN_PARTS * n_new * OPEN_THREADS;
+    return nd < (1ull << 31) && (nd + 1) / 2 <= STORE_DIRECT_CHUNKS * threads &&
+           (uint64_t)n_new * 2 * sizeof(long long) <= 4 * MT_N * sizeof(uint32_t);
 }
 
 // The staged episodes of `b` (buffer_stage) -> slots, scatter, normalizer update, first `n_first` minibatch plans.
@@ -175,6 +231,15 @@ int cycle_open_launch(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rn
     size_t norm_bytes = 0;
     A.chunk_rows = norm_plan_chunk(b->obs_dim, b->goal_dim, b->T, &norm_bytes);
     A.sync = a->open_sync;
+    A.pin = b->ring_cur >= 0 ? static_cast<const double *>(b->ring.slot[b->ring_cur].dev) : nullptr;
+    A.blk.n_obs = (unsigned)(A.inc * A.ep_obs);
+    A.blk.n_ag = (unsigned)(A.inc * A.ep_ag);
+    A.blk.n_g = (unsigned)(A.inc * A.ep_g);
+    A.blk.ep_obs = (unsigned)A.ep_obs;
+    A.blk.ep_ag = (unsigned)A.ep_ag;
+    A.blk.ep_g = (unsigned)A.ep_g;
+    A.blk.ep_act = (unsigned)A.ep_act;
+    A.blk.nd = (unsigned)(A.inc * (A.ep_obs + A.ep_ag + A.ep_g + A.ep_act));
     A.dev = a->d_state;
     A.fault = a->k1_sync + SPLIT_FAULT;
     A.fault_host = a->fault_host_dev;

@@ -12,6 +12,7 @@
 
 #include "rlarm_hip.h"
 #include "rlarm_hip_debug.h"
+#include "stage_ring.h"
 
 // ------------------------------------------------------------------ error plumbing
 void hp_set_error(const char *fmt, ...);
@@ -172,6 +173,32 @@ struct PinnedBuf {
     }
 };
 
+// The HIP side of StageRing (stage_ring.h): blocks the device reads in place through their mapped address.
+struct HipStageApi {
+    using Event = hipEvent_t;
+    using Stream = hipStream_t;
+    int alloc(size_t bytes, void **host, void **dev) {
+        *host = *dev = nullptr;
+        HP_CHECK_HIP(hipHostMalloc(host, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+        HP_CHECK_HIP(hipHostGetDevicePointer(dev, *host, 0));
+        return HP_OK;
+    }
+    void free_block(void *host) { (void)hipHostFree(host); }
+    int event_create(Event *e) {
+        HP_CHECK_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        return HP_OK;
+    }
+    int event_sync(Event e) {
+        HP_CHECK_HIP(hipEventSynchronize(e));
+        return HP_OK;
+    }
+    int event_record(Event e, Stream s) {
+        HP_CHECK_HIP(hipEventRecord(e, s));
+        return HP_OK;
+    }
+    void event_destroy(Event e) { (void)hipEventDestroy(e); }
+};
+
 // ------------------------------------------------------------------ random stream
 #define MT_N 624
 struct MtState {  // device-resident, same fields as numpy's legacy state tuple
@@ -249,7 +276,12 @@ struct hp_buffer {
     // one allocation (st_obs) holds obs | ag | g | actions of the staged batch, so the upload is ONE copy
     DevBuf st_obs, st_slots;
     double *st_ag = nullptr, *st_g = nullptr, *st_act = nullptr;
-    PinnedBuf pin;
+    PinnedBuf pin;                     // eager stores, and the cycle path in its copy form (RLARM_CYCLE_OPEN=copy)
+    // hp_agent_train_cycle, opening launch on: the fresh episodes stay in a pinned block of this ring, in the same
+    // obs | ag | g | actions layout, and k_cycle_open reads them there (no H2D copy); it fills st_obs .. st_act itself.
+    // ring_cur: the block of the cycle being enqueued, -1 = the staging was (or will be) filled by a copy.
+    StageRing<HipStageApi> ring;
+    int ring_cur = -1;
     int64_t staged_n = 0;
     // hp_buffer_store_pinned: tickets of the asynchronous copies out of caller-registered host blocks
     static constexpr int PIN_RING = 16;
@@ -335,9 +367,12 @@ int buffer_launch_gather_dict(hp_buffer *buf, const PlanRec *d_plan, int64_t bat
                               double *d_out, float *d_r, double *d_r64);
 int buffer_stage_and_store(hp_buffer *b, hp_rng *rng, const double *obs, const double *ag, const double *g,
                            const double *actions, int64_t n_new);
-// the staging half alone (+ the host mirror of the counters): slots and scatter follow in k_cycle_open (cycle_open.hip)
+// the staging half alone (+ the host mirror of the counters): slots and scatter follow in k_cycle_open (cycle_open.hip).
+// direct: the episodes go into the next block of b->ring and no further (k_cycle_open reads them there; the caller marks the block
+// behind that launch, buffer_mark_cycle_block); otherwise pinned copy + H2D into the device staging
 int buffer_stage_for_cycle(hp_buffer *b, const double *obs, const double *ag, const double *g, const double *actions,
-                           int64_t n_new);
+                           int64_t n_new, bool direct);
+int buffer_mark_cycle_block(hp_buffer *b);
 // the same out of a device-registered host block (feeder ring); store_now: slots + scatter follow at once
 int buffer_stage_pinned(hp_buffer *b, hp_rng *rng, const double *block, int64_t n_new, uint64_t *ticket, bool store_now);
 // the same out of a DEVICE block (a rollout wave collected on the device, rollout.hip): a device-to-device copy, no ticket

@@ -39,7 +39,8 @@ __device__ __forceinline__ void norm_recompute_column(NormDev *nz, int c, int si
 // per trip).  recompute != 0 (single rank): recompute_stats of both normalizers follows in the same launch.
 #define NORM_THREADS 1024
 // Executed by one NORM_THREADS-thread workgroup; norm_lds = chunk_rows * (sizeof(PlanRec) + (obs_dim + goal_dim) * 8) bytes.
-template <bool SC1_PLAN>
+// SC1_PLAN / SC1_STAGE: the plan / the staged episodes were written by another workgroup of this launch (agent-scope loads).
+template <bool SC1_PLAN, bool SC1_STAGE = false>
 __device__ __forceinline__ void norm_update_from_plan_body(
     NormDev *onz, NormDev *gnz, const PlanRec *__restrict__ plan, long long rows, const double *__restrict__ s_obs,
     const double *__restrict__ s_ag, const double *__restrict__ s_g, int T, int obs_dim, int goal_dim, double clip_obs,
@@ -76,7 +77,10 @@ __device__ __forceinline__ void norm_update_from_plan_body(
             const double *src = col < obs_dim ? s_obs + ((long long)p.e * (T + 1) + p.t) * obs_dim + col
                                               : (p.her ? s_ag + ((long long)p.e * (T + 1) + p.fut) * goal_dim + k
                                                        : s_g + ((long long)p.e * T + p.t) * goal_dim + k);
-            sv[idx] = clipd(*src, -clip_obs, clip_obs);
+            const double x = SC1_STAGE ? __longlong_as_double(__hip_atomic_load(reinterpret_cast<const long long *>(src), __ATOMIC_RELAXED,
+                                                                                 __HIP_MEMORY_SCOPE_AGENT))
+                                       : *src;
+            sv[idx] = clipd(x, -clip_obs, clip_obs);
         }
         __syncthreads();
         if (act) {

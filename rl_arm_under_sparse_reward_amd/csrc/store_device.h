@@ -26,3 +26,72 @@ __device__ __forceinline__ void store_scatter_share(SlotOf slot_of, long long i,
     for (long long k = t0; k < ep_g; k += step) g[slot * ep_g + k] = s_g[i * ep_g + k];
     for (long long k = t0; k < ep_act; k += step) act[slot * ep_act + k] = s_act[i * ep_act + k];
 }
+
+// ---- the direct form of the cycle-opening kernel: the staged batch still lies in a pinned HOST block (hp_buffer::ring), laid out
+// obs | ag | g | actions back to back like the device staging, `nd` doubles in all.  The block is cut into 16-byte chunks, chunk c
+// belonging to thread c mod `nthreads` of the scatter workgroups together; a thread holds at most STORE_DIRECT_CHUNKS of them in
+// registers (cycle_open_direct_fits).  The block's base is page aligned, so every chunk load is; only the LAST chunk of a block
+// with an odd number of doubles is half a chunk, loaded as 8 bytes -- nothing is read past the block.
+#define STORE_DIRECT_CHUNKS 4
+
+struct StageBlock {   // the four arrays of a staged batch as one run of doubles
+    unsigned n_obs, n_ag, n_g;           // doubles of the first three arrays (n_new episodes each)
+    unsigned ep_obs, ep_ag, ep_g, ep_act;
+    unsigned nd;
+};
+
+// all of a thread's loads, issued back to back before anything waits for them (one PCIe round trip)
+__device__ __forceinline__ void stage_block_load(const double *__restrict__ blk, unsigned nd, unsigned gtid, unsigned nthreads,
+                                                 double (&v)[STORE_DIRECT_CHUNKS][2]) {
+#pragma unroll
+    for (int it = 0; it < STORE_DIRECT_CHUNKS; ++it) {
+        const unsigned d = 2u * (gtid + (unsigned)it * nthreads);
+        v[it][0] = v[it][1] = 0.0;
+        if (d + 1u < nd) {
+            const double2 x = *reinterpret_cast<const double2 *>(blk + d);
+            v[it][0] = x.x;
+            v[it][1] = x.y;
+        } else if (d < nd) {
+            v[it][0] = blk[d];
+        }
+    }
+}
+
+// the same chunks into the device staging (same layout), as write-through stores: the normalizer workgroup of the SAME launch
+// reads them behind a counter
+__device__ __forceinline__ void stage_block_put(double *stage, unsigned nd, unsigned gtid, unsigned nthreads,
+                                                const double (&v)[STORE_DIRECT_CHUNKS][2]) {
+#pragma unroll
+    for (int it = 0; it < STORE_DIRECT_CHUNKS; ++it) {
+        const unsigned d = 2u * (gtid + (unsigned)it * nthreads);
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            if (d + h < nd)
+                __hip_atomic_store(reinterpret_cast<long long *>(stage) + d + h, __double_as_longlong(v[it][h]), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// ... and into the buffer rows of their episodes' slots.  win[e]: the slot of staged episode e, or -1 where a later staged episode
+// has the same slot (the rule at the top of this file).
+__device__ __forceinline__ void stage_block_scatter(const StageBlock &L, const long long *win, unsigned gtid, unsigned nthreads,
+                                                    const double (&v)[STORE_DIRECT_CHUNKS][2], double *obs, double *ag, double *g,
+                                                    double *act) {
+#pragma unroll
+    for (int it = 0; it < STORE_DIRECT_CHUNKS; ++it) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const unsigned d = 2u * (gtid + (unsigned)it * nthreads) + h;
+            if (d >= L.nd) continue;
+            unsigned r = d, len;
+            double *arr;
+            if (r < L.n_obs) { arr = obs; len = L.ep_obs; }
+            else if ((r -= L.n_obs) < L.n_ag) { arr = ag; len = L.ep_ag; }
+            else if ((r -= L.n_ag) < L.n_g) { arr = g; len = L.ep_g; }
+            else { r -= L.n_g; arr = act; len = L.ep_act; }
+            const unsigned e = r / len, k = r - e * len;
+            const long long slot = win[e];
+            if (slot >= 0) arr[slot * (long long)len + k] = v[it][h];
+        }
+    }
+}
