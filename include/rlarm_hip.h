@@ -392,20 +392,30 @@ int hp_rollout_step_streams(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_no
  * HP_ERR_INVALID names the field for: an unknown kind, dimensions of block / agent / normalizers / environment that differ, a
  * wave wider than the stream array, explore != 0 without streams, an agent of another shape.
  * Adding an environment kind is a build-time change: one struct in csrc/env_device.h (load, observe, step, is_success, store
- * over the arrays of hp_env_desc, with its dimensions as constants), one case in the dispatches of csrc/rollout.hip next to
- * HP_ENV_POINT_MASS, and a translation unit that instantiates the kernel templates (csrc/rollout_episodes.h) for that struct.
+ * over the arrays of hp_env_desc, with its dimensions as constants), its row in the table of kinds of csrc/rollout.hip, and
+ * translation units that instantiate the kernel templates (csrc/rollout_episodes.h, csrc/demo_episodes.h) for that struct; the
+ * header of csrc/env_device.h has the whole list.
  * HP_ENV_PUSH_BLOCK is a kinematic planar push: the achieved goal is a block that moves only while the gripper touches it, and
- * its reset redraws block and target until they are min_separation apart (at most 100 attempts: csrc/env_device.h). */
+ * its reset redraws block and target until they are min_separation apart (at most 100 attempts: csrc/env_device.h).
+ * HP_ENV_PICK_PLACE is a kinematic pick-and-place: the goal hangs in the air, the block is a cube that moves only in a closed
+ * hand -- grasped when open fingers close with the finger pads inside it, and never released (the environment keeps a held
+ * block's fingers closing, the reference's finger lock) -- the fourth action component moves the fingers, and the reset is the
+ * push block's rejection loop in three dimensions, five draws an attempt. */
 enum { HP_ENV_POINT_MASS = 1 };
 enum { HP_ENV_PUSH_BLOCK = 2 };
+enum { HP_ENV_PICK_PLACE = 3 };
 typedef struct {
     int32_t kind, reserved;
     double params[8];         /* point mass: [0] step_scale, [1] distance_threshold
                                * push block: [0] step_scale, [1] distance_threshold, [2] half_width, [3] z_touch, [4] min_separation,
-                               *             [5] table_z, [6] [7] gripper start x, y */
+                               *             [5] table_z, [6] [7] gripper start x, y
+                               * pick and place: [0] step_scale, [1] distance_threshold, [2] half_width, [3] finger_scale,
+                               *             [4] min_separation, [5] table_z, [6] [7] gripper start x, y */
     double *state_dev[4];     /* read at entry, written at exit; a kind's unused slots are ignored
                                * point mass: [0] pos [n][3], [1] vel [n][3], [2] goal [n][3]
-                               * push block: [0] gripper [n][3], [1] block [n][3], [2] goal [n][3], [3] velocities [n][6] (gripper, block) */
+                               * push block: [0] gripper [n][3], [1] block [n][3], [2] goal [n][3], [3] velocities [n][6] (gripper, block)
+                               * pick and place: [0] gripper [n][3], [1] block [n][3], [2] goal [n][3], [3] [n][8] = gripper velocity,
+                               *             block velocity, finger opening, held (0.0 or 1.0) */
 } hp_env_desc;
 int hp_rollout_episodes(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, hp_rng_streams *streams,
                         const hp_env_desc *env, int32_t explore, double noise_eps, double random_eps, double qn,
@@ -463,7 +473,13 @@ int hp_rollout_waves(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_norm *g_n
  * Both asynchronous on the context's stream (or a borrowed one).  HP_ERR_INVALID, naming the entry point, for: a null argument,
  * handles of different contexts, an unknown kind or one without a reset on the device, a null state array, n_envs wider than
  * the stream array, T or dimensions that differ from the block's (hp_demo_compact: between the blocks), episodes outside a
- * block, phase ends that are not increasing. */
+ * block, phase ends that are not increasing.
+ * hp_demo_episodes_pick is hp_demo_episodes with the reference's pick-and-place schedule (get_demo_data_pick.py:54-67,
+ * synthetic.pick_scripted_action) in place of the push schedule, and hp_pick_script holds its numbers (defaults in
+ * synthetic.PickScript): phases as above; one: the constant action `lift`; two: (b - grip) + approach; three: the fingers,
+ * (0, 0, 0, open); four: (b - grip) + grasp; five: (0, 0, 0, -open); six: g - b (fourth component 0 in two, four and six).  No
+ * stop rule.  Everything else -- arguments, waves, launches, refusals (naming hp_demo_episodes_pick) -- is hp_demo_episodes'.
+ * A controller is no property of an environment kind: either entry runs on any kind with a reset on the device. */
 typedef struct {
     int32_t phase_end[5];     /* last timestep (counted from 1) of phases one to five */
     int32_t reserved;
@@ -475,6 +491,13 @@ typedef struct {
 int hp_demo_episodes(hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *reset_streams, const hp_demo_script *script,
                      int64_t n_envs, int64_t first_episode, int64_t n_episodes, int32_t T, hp_rollout *block, float *success_dev,
                      float *step_success_dev, int32_t *launches_out);
+typedef struct {
+    int32_t phase_end[5], reserved;   /* last timestep (counted from 1) of phases one to five */
+    double lift[4], approach[3], grasp[3], open;   /* the action of phase one; the offsets of phases two and four; the finger action */
+} hp_pick_script;
+int hp_demo_episodes_pick(hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *reset_streams, const hp_pick_script *script,
+                          int64_t n_envs, int64_t first_episode, int64_t n_episodes, int32_t T, hp_rollout *block, float *success_dev,
+                          float *step_success_dev, int32_t *launches_out);
 int hp_demo_compact(hp_ctx *ctx, hp_rollout *src, const float *success_dev, const float *step_success_dev, int64_t n_episodes,
                     hp_rollout *dst, float *dst_step_success_dev, int64_t n_demos, int64_t kept, int32_t *kept_dev);
 

@@ -61,8 +61,15 @@ class DemoScriptDesc(C.Structure):
                 ("behind", C.c_double), ("stop_radius", C.c_double)]
 
 
+class PickScriptDesc(C.Structure):
+    """hp_pick_script: the pick-and-place controller's numbers (hp_demo_episodes_pick; synthetic.PickScript holds the same fields)"""
+    _fields_ = [("phase_end", C.c_int32 * 5), ("reserved", C.c_int32), ("lift", C.c_double * 4), ("approach", C.c_double * 3),
+                ("grasp", C.c_double * 3), ("open", C.c_double)]
+
+
 ENV_POINT_MASS = 1
 ENV_PUSH_BLOCK = 2      # HP_ENV_PUSH_BLOCK
+ENV_PICK_PLACE = 3      # HP_ENV_PICK_PLACE
 ROLLOUT_MAX_LAUNCH_TIMESTEPS = 4096   # HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS: what one launch of hp_rollout_waves holds at most
 
 
@@ -205,6 +212,8 @@ PROTOTYPES = {
     "hp_rollout_debug_set_launch_cap": (C.c_int, [C.c_void_p, C.c_int64]),
     "hp_demo_episodes": (C.c_int, [C.c_void_p, C.POINTER(EnvDesc), C.c_void_p, C.POINTER(DemoScriptDesc), C.c_int64, C.c_int64,
                                    C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "hp_demo_episodes_pick": (C.c_int, [C.c_void_p, C.POINTER(EnvDesc), C.c_void_p, C.POINTER(PickScriptDesc), C.c_int64, C.c_int64,
+                                        C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "hp_demo_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                   C.c_int64, C.c_void_p]),
     "hp_agent_policy_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,6 +1,9 @@
 // demo_episodes.h -- demonstration episodes from a scripted controller: the kernel of hp_demo_episodes as a template over an
-// environment kind (env_device.h), its argument block, and the controller (get_demo_data_push.py:39-61, stated on the host as
-// synthetic.scripted_action).
+// environment kind (env_device.h), its argument block, and the two controllers: the push schedule (get_demo_data_push.py:39-61,
+// stated on the host as synthetic.scripted_action) and the pick-and-place schedule (get_demo_data_pick.py:54-67,
+// synthetic.pick_scripted_action).  Which one runs is a value of the argument block (DemoArgs::controller), the same for every
+// workgroup of a launch: a controller is no property of a kind -- either runs on any kind that keeps the bmirobot layout -- so
+// the table of kinds has no column for it and a kind's demo unit still holds ONE kernel.
 //
 // No policy: the mapping is the stand-alone reset kernel's (k_env_reset) grown by a timestep loop.  Workgroup i is ONE wave and
 // owns environment i with reset stream i in an LDS ring for the whole launch; for each wave of the round it draws the reset
@@ -20,9 +23,12 @@ struct DemoArgs {
     float *success, *step_success;        // [rows], [rows][T]
     int rows, T;                          // rows: episodes of the launch = waves of n_envs environments, the last possibly partial
     int n_envs, waves;
+    int controller;                       // DEMO_PUSH: demo_action on `s`; DEMO_PICK: demo_action_pick on `p` (the other is zero)
     hp_demo_script s;
+    hp_pick_script p;
     hp_env_desc env;
 };
+enum { DEMO_PUSH = 0, DEMO_PICK = 1 };
 
 // The controller for timestep `step` = 1 .. T out of the observation row (bmirobot layout: gripper [0:3], block [12:15]) and the
 // desired goal: act[0:4], float64, unclipped.  One explicit IEEE operation per rounding of the host statement.
@@ -49,6 +55,29 @@ __device__ __forceinline__ void demo_action(const hp_demo_script &S, int step, c
     if (__dsqrt_rn(s) < S.stop_radius) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) act[c] = 0.0;
+    }
+}
+
+// The pick-and-place controller (get_demo_data_pick.py:54-67, synthetic.pick_scripted_action) for timestep `step` = 1 .. T, out
+// of the same two places of the observation row: act[0:4], float64, unclipped.  No stop rule.  The offset is added also where it
+// is 0.0, as the host statement adds it.
+__device__ __forceinline__ void demo_action_pick(const hp_pick_script &S, int step, const double *obs, const double *g, double *act) {
+    const double *grip = obs, *b = obs + 12;
+    const int phase = step <= S.phase_end[0] ? 0 : step <= S.phase_end[1] ? 1 : step <= S.phase_end[2] ? 2 : step <= S.phase_end[3] ? 3 :
+                      step <= S.phase_end[4] ? 4 : 5;
+    if (phase == 0) {                                               // :54-55 lift and retreat
+#pragma unroll
+        for (int c = 0; c < 4; ++c) act[c] = S.lift[c];
+    } else if (phase == 2 || phase == 4) {                          // :59-60 open the fingers, :64-65 close them
+        act[0] = act[1] = act[2] = 0.0;
+        act[3] = phase == 2 ? S.open : -S.open;
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (phase == 5) act[c] = __dsub_rn(g[c], b[c]);        // :66-67 carry the block to the goal
+            else act[c] = __dadd_rn(__dsub_rn(b[c], grip[c]), phase == 1 ? S.approach[c] : S.grasp[c]);   // :56-58, :61-63
+        }
+        act[3] = 0.0;
     }
 }
 
@@ -79,7 +108,8 @@ __global__ __launch_bounds__(MW_THREADS) void k_demo_episodes(const DemoArgs A) 
             for (int t = 0; t < T; ++t) {
                 if (lane == 0) {
                     e.observe(row, ag, g);
-                    demo_action(A.s, t + 1, row, g, act);
+                    if (A.controller == DEMO_PICK) demo_action_pick(A.p, t + 1, row, g, act);   // workgroup-uniform
+                    else demo_action(A.s, t + 1, row, g, act);
                     e.step(act);
                     flag = e.is_success() ? 1.f : 0.f;
                     A.step_success[ep * T + t] = flag;

@@ -28,14 +28,18 @@
 // RESET_ATTEMPTS = 1 there is no loop and no verdict: the code is the fixed reset's.
 // Every float64 operation whose rounding the host twin of the environment fixes is an explicit IEEE operation (__dmul_rn, ...), so
 // that no contraction can change a bit relative to the elementwise torch / numpy ops of that twin.
-// Adding a kind touches this and nothing else: a struct here; an HP_ENV_* constant in rlarm_hip.h and its twin in _lib.py; a unit
+// Adding a kind touches this list and nothing else (the third kind, PickPlaceEnvDev, was added by it and found two items it had
+// left out: the comments of hp_env_desc and the default script): a struct here; an HP_ENV_* constant in rlarm_hip.h with the
+// kind's lines in the params / state_dev comments of hp_env_desc there, and the constant's twin in _lib.py; a unit
 // env_<kind>.hip of three lines -- the include of rollout_episodes.h and `const EnvKind env_kind_<kind> = env_kind_entry<Struct>(HP_ENV_...)`,
 // which instantiates both kernels for the kind and checks at compile time what a kind must be for them -- and a unit
 // demo_<kind>.hip of two, the explicit instantiation of env_launch_demo<Struct> (demo_episodes.h: the scripted-episode kernel, the
 // row's third launch), both with their entries in the
 // Makefile's EXACT_SRCS; the row's declaration in rollout_episodes.h and its address in the table of env_kind() (rollout.hip); and
-// one Python class pair in device_env.py (the tensor twin, and a native class that names the constant).  No entry point, dispatch or
-// check names a kind: they read the row (env_point_mass.hip and env_push_block.hip are the two models).
+// one Python class pair in device_env.py (the tensor twin, and a native class that names the constant -- and, where the task's
+// scripted controller is not the push schedule, its default_demo_script()).  No entry point, dispatch or check names a kind: they
+// read the row (env_point_mass.hip, env_push_block.hip and env_pick_place.hip are the models).  A scripted controller is NOT part
+// of a kind: the two of demo_episodes.h run on any kind with the bmirobot layout, chosen per call (DemoArgs::controller).
 #pragma once
 #include "internal.h"
 #include <type_traits>
@@ -220,6 +224,135 @@ struct PushBlockEnvDev {
             d.state_dev[3][6 * i + c] = gvel[c];
             d.state_dev[3][6 * i + 3 + c] = bvel[c];
         }
+    }
+};
+
+// device_env.PickPlaceVecEnv (the tensor twin of synthetic.PickPlaceGoalEnv), operation for operation: a kinematic pick-and-place.
+// The achieved goal is a cube of half width r that moves only in a closed hand; the finger pads sit at grip + TOOL:
+//     a = clamp(float64(action), -0.5, 0.5), all four;  inside(grip) = |blk - (grip + TOOL)| < r on every axis
+//     near = held or inside(grip):  a[3] = -1  (the finger lock of bmirobot_env_pickandplace_v2.py:93-95, behind the clip)
+//     f_old = finger;  finger = clamp(finger + finger_scale * a[3], 0, FINGER_MAX)
+//     new = clamp(grip + step_scale * a[0:3], lo, hi);  gvel = new - grip;  grip = new
+//     held: blk = clamp(blk + gvel, lo, hi);  otherwise inside(new) and f_old > GRASP_WIDTH and finger <= GRASP_WIDTH: held = 1
+//     (the block stays where it is in the step of the grasp; the lock keeps a held block's fingers closing: a grasp never opens)
+//     bvel = blk_new - blk_old
+//     obs = zeros(27) with [0:3] = grip, [6:9] = gvel, [9] = finger, [10] = held, [12:15] = blk, [18:21] = blk - grip,
+//     [21:24] = bvel;  ag = blk;  g = goal;  is_success: the push block's
+//     reset: at most 100 attempts of bx = uniform(0.15, 0.35), by = uniform(0.2, 0.5), gx = uniform(0.0, 0.35),
+//     gy = uniform(0.3, 0.55), gz = uniform(0.3, 0.5), accepted when sqrt(ddx ddx + ddy ddy + ddz ddz) >= min_separation with
+//     ddz = table_z - gz (:116-131 without the orientation draws); the last attempt is kept.  Five bounds, all different: five
+//     one-value calls of env_reset_draw
+// No division and no square root inside step.
+// params: [0] step_scale, [1] distance_threshold, [2] half_width r, [3] finger_scale, [4] min_separation, [5] table_z, [6], [7]
+// gripper start x, y;  state_dev: [0] grip [n][3], [1] blk [n][3], [2] goal [n][3], [3] [n][8] = gripper velocity, block velocity,
+// finger opening, held (0.0 or 1.0)
+struct PickPlaceEnvDev {
+    static constexpr int OBS = 27, GOAL = 3, ACT = 4, RESET_DRAWS = 5, RESET_ATTEMPTS = 100, STATE_ARRAYS = 4;
+    // the workspace of gripper and block alike (z from the table to Z_HI); the gripper starts at START_Z
+    static constexpr double X_LO = 0.0, X_HI = 0.5, Y_LO = 0.0, Y_HI = 0.7, Z_HI = 0.6, START_Z = 0.3;
+    // the finger pads relative to the gripper; the widest opening; the opening at and below which the fingers hold the cube
+    static constexpr double TOOL_X = 0.0, TOOL_Y = 0.05, TOOL_Z = -0.05, FINGER_MAX = 0.08, GRASP_WIDTH = 0.04;
+    double grip[3], blk[3], goal[3], gvel[3], bvel[3], finger, held;
+    double step_scale, threshold, r, finger_scale, min_sep, table_z, start_x, start_y;
+
+    static __device__ __forceinline__ void reset_bounds(int k, double &low, double &range) {
+        constexpr double lo[5] = {0.15, 0.2, 0.0, 0.3, 0.3}, hi[5] = {0.35, 0.5, 0.35, 0.55, 0.5};
+        low = lo[k];
+        range = hi[k] - lo[k];
+    }
+    __device__ __forceinline__ bool reset(const double *u) {
+        const double ddx = __dsub_rn(u[0], u[2]), ddy = __dsub_rn(u[1], u[3]), ddz = __dsub_rn(table_z, u[4]);
+        const double d = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(ddx, ddx), __dmul_rn(ddy, ddy)), __dmul_rn(ddz, ddz)));
+        blk[0] = u[0]; blk[1] = u[1]; blk[2] = table_z;
+        goal[0] = u[2]; goal[1] = u[3]; goal[2] = u[4];
+        grip[0] = start_x; grip[1] = start_y; grip[2] = START_Z;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gvel[c] = bvel[c] = 0.0;
+        finger = held = 0.0;
+        return d >= min_sep;
+    }
+
+    __device__ __forceinline__ void load(const hp_env_desc &d, long long i) {
+        step_scale = d.params[0]; threshold = d.params[1]; r = d.params[2]; finger_scale = d.params[3];
+        min_sep = d.params[4]; table_z = d.params[5]; start_x = d.params[6]; start_y = d.params[7];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            grip[c] = d.state_dev[0][3 * i + c];
+            blk[c] = d.state_dev[1][3 * i + c];
+            goal[c] = d.state_dev[2][3 * i + c];
+            gvel[c] = d.state_dev[3][8 * i + c];
+            bvel[c] = d.state_dev[3][8 * i + 3 + c];
+        }
+        finger = d.state_dev[3][8 * i + 6];
+        held = d.state_dev[3][8 * i + 7];
+    }
+    __device__ __forceinline__ void observe(double *obs, double *ag, double *g) const {
+#pragma unroll
+        for (int c = 0; c < OBS; ++c) obs[c] = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            obs[c] = grip[c];
+            obs[6 + c] = gvel[c];
+            obs[12 + c] = blk[c];
+            obs[18 + c] = __dsub_rn(blk[c], grip[c]);
+            obs[21 + c] = bvel[c];
+            ag[c] = blk[c];
+            g[c] = goal[c];
+        }
+        obs[9] = finger;
+        obs[10] = held;
+    }
+    // every finger pad coordinate is less than r from the block centre
+    __device__ __forceinline__ bool pads_inside() const {
+        return fabs(__dsub_rn(blk[0], __dadd_rn(grip[0], TOOL_X))) < r && fabs(__dsub_rn(blk[1], __dadd_rn(grip[1], TOOL_Y))) < r &&
+               fabs(__dsub_rn(blk[2], __dadd_rn(grip[2], TOOL_Z))) < r;
+    }
+    template <class A>
+    __device__ __forceinline__ void step_with(const A *action) {
+        const double lo[3] = {X_LO, Y_LO, table_z}, hi[3] = {X_HI, Y_HI, Z_HI};
+        double a3 = fmin(fmax((double)action[3], -0.5), 0.5);
+        if (held != 0.0 || pads_inside()) a3 = -1.0;         // the finger lock, on the state before the move
+        const double f_old = finger;
+        finger = fmin(fmax(__dadd_rn(finger, __dmul_rn(finger_scale, a3)), 0.0), FINGER_MAX);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double a = fmin(fmax((double)action[c], -0.5), 0.5);
+            const double scaled = __dmul_rn(step_scale, a);
+            const double moved = fmin(fmax(__dadd_rn(grip[c], scaled), lo[c]), hi[c]);
+            gvel[c] = __dsub_rn(moved, grip[c]);
+            grip[c] = moved;
+        }
+        if (held != 0.0) {                                   // carried: the gripper's clipped displacement, clipped again
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const double carried = fmin(fmax(__dadd_rn(blk[c], gvel[c]), lo[c]), hi[c]);
+                bvel[c] = __dsub_rn(carried, blk[c]);
+                blk[c] = carried;
+            }
+        } else {
+            if (pads_inside() && f_old > GRASP_WIDTH && finger <= GRASP_WIDTH) held = 1.0;   // the block moves from the next step on
+#pragma unroll
+            for (int c = 0; c < 3; ++c) bvel[c] = __dsub_rn(blk[c], blk[c]);
+        }
+    }
+    __device__ __forceinline__ void step(const float *action) { step_with(action); }
+    __device__ __forceinline__ void step(const double *action) { step_with(action); }
+    __device__ __forceinline__ bool is_success() const {
+        const double dx = __dsub_rn(blk[0], goal[0]), dy = __dsub_rn(blk[1], goal[1]), dz = __dsub_rn(blk[2], goal[2]);
+        const double s = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+        return __dsqrt_rn(s) < threshold;
+    }
+    __device__ __forceinline__ void store(const hp_env_desc &d, long long i) const {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            d.state_dev[0][3 * i + c] = grip[c];
+            d.state_dev[1][3 * i + c] = blk[c];
+            d.state_dev[2][3 * i + c] = goal[c];
+            d.state_dev[3][8 * i + c] = gvel[c];
+            d.state_dev[3][8 * i + 3 + c] = bvel[c];
+        }
+        d.state_dev[3][8 * i + 6] = finger;
+        d.state_dev[3][8 * i + 7] = held;
     }
 };
 

@@ -211,7 +211,7 @@ static int rollout_split_launches(hp_rollout *ro, const EpisodesArgs &A, int32_t
 
 // The table of environment kinds: one row per kind, defined by the kind's own unit.  nullptr: not an environment kind of this build
 static const EnvKind *env_kind(int kind) {
-    static const EnvKind *const kinds[] = {&env_kind_point_mass, &env_kind_push_block};
+    static const EnvKind *const kinds[] = {&env_kind_point_mass, &env_kind_push_block, &env_kind_pick_place};
     for (const EnvKind *k : kinds)
         if (k->kind == kind) return k;
     return nullptr;
@@ -269,6 +269,70 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     return rollout_split_launches(ro, A, launches, kind->launch_episodes);
 }
 
+// what hp_demo_episodes and hp_demo_episodes_pick share -- everything but the type of the script: the checks (`entry` names the
+// caller in every refusal), the arguments of the kernel and the split into launches.  Exactly one of push / pick is given, and
+// which one says which controller the launches run (DemoArgs::controller): a value of the call, not a property of the kind
+static int demo_episodes(const char *entry, hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *reset_streams, const hp_demo_script *push,
+                         const hp_pick_script *pick, int64_t n_envs, int64_t first_episode, int64_t n_episodes, int32_t T,
+                         hp_rollout *block, float *success_dev, float *step_success_dev, int32_t *launches_out) {
+    HP_REQUIRE(ctx && env && reset_streams && (push || pick) && block && success_dev && step_success_dev, HP_ERR_INVALID,
+               "%s: null argument", entry);
+    CtxGuard guard(ctx);
+    hp_rollout *ro = block;
+    HP_REQUIRE(reset_streams->ctx == ctx && ro->ctx == ctx, HP_ERR_INVALID, "%s: handles belong to different contexts", entry);
+    HP_REQUIRE(n_envs > 0 && n_envs < (1 << 24), HP_ERR_INVALID, "%s: n_envs %lld out of range", entry, (long long)n_envs);
+    HP_REQUIRE(n_envs <= reset_streams->n, HP_ERR_INVALID, "%s: %lld environments, but the array holds %lld reset streams", entry,
+               (long long)n_envs, (long long)reset_streams->n);
+    HP_REQUIRE(first_episode >= 0 && n_episodes > 0 && first_episode + n_episodes <= ro->n, HP_ERR_INVALID,
+               "%s: episodes [%lld, %lld) outside the block of %lld", entry, (long long)first_episode,
+               (long long)(first_episode + n_episodes), (long long)ro->n);
+    HP_REQUIRE(T == ro->T, HP_ERR_INVALID, "%s: T = %d, the block has T = %d", entry, (int)T, (int)ro->T);
+    const EnvKind *kind = env_kind(env->kind);
+    HP_REQUIRE(kind, HP_ERR_INVALID, "%s: env->kind %d is not an environment kind of this build", entry, (int)env->kind);
+    for (int k = 0; k < kind->state_arrays; ++k)
+        HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "%s: env->state_dev[%d] is null", entry, k);
+    HP_REQUIRE(ro->od == kind->obs && ro->gd == kind->goal && ro->ad == kind->act, HP_ERR_INVALID,
+               "%s: env->kind %d has dimensions %d / %d / %d, the block has %d / %d / %d", entry, (int)env->kind, kind->obs,
+               kind->goal, kind->act, ro->od, ro->gd, ro->ad);
+    HP_REQUIRE(kind->reset_draws > 0, HP_ERR_INVALID, "%s: env->kind %d has no reset on the device", entry, (int)env->kind);
+    const int32_t *phase_end = push ? push->phase_end : pick->phase_end;
+    for (int k = 0; k < 5; ++k)
+        HP_REQUIRE(phase_end[k] >= 0 && (k == 0 || phase_end[k] > phase_end[k - 1]), HP_ERR_INVALID,
+                   "%s: script->phase_end[%d] = %d: the phase ends must be increasing", entry, k, (int)phase_end[k]);
+    DemoArgs A;
+    memset(&A, 0, sizeof(A));
+    A.b_obs = ro->block + first_episode * (ro->T + 1) * ro->od;
+    A.b_ag = ro->block + ro->o_ag + first_episode * (ro->T + 1) * ro->gd;
+    A.b_g = ro->block + ro->o_g + first_episode * ro->T * ro->gd;
+    A.b_act = ro->block + ro->o_act + first_episode * ro->T * ro->ad;
+    A.reset_st = reset_streams->d_state;
+    A.T = ro->T; A.n_envs = (int)n_envs;
+    A.controller = push ? DEMO_PUSH : DEMO_PICK;
+    if (push) A.s = *push;
+    else A.p = *pick;
+    A.env = *env;
+    // the launch-length rule of rollout_split_launches: whole waves, at most launch_cap timesteps, the next launch on the states
+    // and streams the one before it wrote back
+    int64_t per = ro->launch_cap / (ro->T > 0 ? ro->T : 1);
+    if (per < 1) per = 1;
+    int n = 0;
+    for (int64_t done = 0; done < n_episodes; ++n) {
+        const int64_t left = n_episodes - done, waves = std::min<int64_t>((left + n_envs - 1) / n_envs, per);
+        const int64_t rows = std::min(left, waves * n_envs), live = std::min(rows, n_envs);
+        DemoArgs L = A;
+        L.b_obs += done * (ro->T + 1) * ro->od;
+        L.b_ag += done * (ro->T + 1) * ro->gd;
+        L.b_g += done * ro->T * ro->gd;
+        L.b_act += done * ro->T * ro->ad;
+        L.success = success_dev + done;
+        L.step_success = step_success_dev + done * ro->T;
+        L.rows = (int)rows; L.waves = (int)waves;
+        HP_CHECK_HIP(kind->launch_demo(ctx->stream, (unsigned)live, L));
+        done += rows;
+    }
+    if (launches_out) *launches_out = n;
+    return HP_OK;
+}
 
 
 extern "C" {
@@ -371,60 +435,15 @@ int hp_env_reset(hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *reset_stre
 int hp_demo_episodes(hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *reset_streams, const hp_demo_script *script, int64_t n_envs,
                      int64_t first_episode, int64_t n_episodes, int32_t T, hp_rollout *block, float *success_dev, float *step_success_dev,
                      int32_t *launches_out) {
-    HP_REQUIRE(ctx && env && reset_streams && script && block && success_dev && step_success_dev, HP_ERR_INVALID,
-               "hp_demo_episodes: null argument");
-    CtxGuard guard(ctx);
-    hp_rollout *ro = block;
-    HP_REQUIRE(reset_streams->ctx == ctx && ro->ctx == ctx, HP_ERR_INVALID, "hp_demo_episodes: handles belong to different contexts");
-    HP_REQUIRE(n_envs > 0 && n_envs < (1 << 24), HP_ERR_INVALID, "hp_demo_episodes: n_envs %lld out of range", (long long)n_envs);
-    HP_REQUIRE(n_envs <= reset_streams->n, HP_ERR_INVALID, "hp_demo_episodes: %lld environments, but the array holds %lld reset streams",
-               (long long)n_envs, (long long)reset_streams->n);
-    HP_REQUIRE(first_episode >= 0 && n_episodes > 0 && first_episode + n_episodes <= ro->n, HP_ERR_INVALID,
-               "hp_demo_episodes: episodes [%lld, %lld) outside the block of %lld", (long long)first_episode,
-               (long long)(first_episode + n_episodes), (long long)ro->n);
-    HP_REQUIRE(T == ro->T, HP_ERR_INVALID, "hp_demo_episodes: T = %d, the block has T = %d", (int)T, (int)ro->T);
-    const EnvKind *kind = env_kind(env->kind);
-    HP_REQUIRE(kind, HP_ERR_INVALID, "hp_demo_episodes: env->kind %d is not an environment kind of this build", (int)env->kind);
-    for (int k = 0; k < kind->state_arrays; ++k)
-        HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "hp_demo_episodes: env->state_dev[%d] is null", k);
-    HP_REQUIRE(ro->od == kind->obs && ro->gd == kind->goal && ro->ad == kind->act, HP_ERR_INVALID,
-               "hp_demo_episodes: env->kind %d has dimensions %d / %d / %d, the block has %d / %d / %d", (int)env->kind, kind->obs,
-               kind->goal, kind->act, ro->od, ro->gd, ro->ad);
-    HP_REQUIRE(kind->reset_draws > 0, HP_ERR_INVALID, "hp_demo_episodes: env->kind %d has no reset on the device", (int)env->kind);
-    for (int k = 0; k < 5; ++k)
-        HP_REQUIRE(script->phase_end[k] >= 0 && (k == 0 || script->phase_end[k] > script->phase_end[k - 1]), HP_ERR_INVALID,
-                   "hp_demo_episodes: script->phase_end[%d] = %d: the phase ends must be increasing", k, (int)script->phase_end[k]);
-    DemoArgs A;
-    memset(&A, 0, sizeof(A));
-    A.b_obs = ro->block + first_episode * (ro->T + 1) * ro->od;
-    A.b_ag = ro->block + ro->o_ag + first_episode * (ro->T + 1) * ro->gd;
-    A.b_g = ro->block + ro->o_g + first_episode * ro->T * ro->gd;
-    A.b_act = ro->block + ro->o_act + first_episode * ro->T * ro->ad;
-    A.reset_st = reset_streams->d_state;
-    A.T = ro->T; A.n_envs = (int)n_envs;
-    A.s = *script;
-    A.env = *env;
-    // the launch-length rule of rollout_split_launches: whole waves, at most launch_cap timesteps, the next launch on the states
-    // and streams the one before it wrote back
-    int64_t per = ro->launch_cap / (ro->T > 0 ? ro->T : 1);
-    if (per < 1) per = 1;
-    int n = 0;
-    for (int64_t done = 0; done < n_episodes; ++n) {
-        const int64_t left = n_episodes - done, waves = std::min<int64_t>((left + n_envs - 1) / n_envs, per);
-        const int64_t rows = std::min(left, waves * n_envs), live = std::min(rows, n_envs);
-        DemoArgs L = A;
-        L.b_obs += done * (ro->T + 1) * ro->od;
-        L.b_ag += done * (ro->T + 1) * ro->gd;
-        L.b_g += done * ro->T * ro->gd;
-        L.b_act += done * ro->T * ro->ad;
-        L.success = success_dev + done;
-        L.step_success = step_success_dev + done * ro->T;
-        L.rows = (int)rows; L.waves = (int)waves;
-        HP_CHECK_HIP(kind->launch_demo(ctx->stream, (unsigned)live, L));
-        done += rows;
-    }
-    if (launches_out) *launches_out = n;
-    return HP_OK;
+    return demo_episodes("hp_demo_episodes", ctx, env, reset_streams, script, nullptr, n_envs, first_episode, n_episodes, T, block,
+                         success_dev, step_success_dev, launches_out);
+}
+
+int hp_demo_episodes_pick(hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *reset_streams, const hp_pick_script *script, int64_t n_envs,
+                          int64_t first_episode, int64_t n_episodes, int32_t T, hp_rollout *block, float *success_dev,
+                          float *step_success_dev, int32_t *launches_out) {
+    return demo_episodes("hp_demo_episodes_pick", ctx, env, reset_streams, nullptr, script, n_envs, first_episode, n_episodes, T, block,
+                         success_dev, step_success_dev, launches_out);
 }
 
 int hp_demo_compact(hp_ctx *ctx, hp_rollout *src, const float *success_dev, const float *step_success_dev, int64_t n_episodes,

@@ -43,7 +43,15 @@ the host lockstep path (`collect_episodes` on a list of environments); with one 
 successful episodes in order -- whole episodes, all waves of a round in one launch (hp_demo_episodes), the filter one more
 (hp_demo_compact), no policy and no weights; `synthetic.scripted_demos` on host twins seeded alike gives the same bits.
 
-`PointMassVecEnv` is the tensor twin of `synthetic.PointMassGoalEnv`, `PushBlockVecEnv` that of `synthetic.PushBlockGoalEnv`; what
+With a `synthetic.PickScript` the controller is the reference's pick-and-place schedule (`synthetic.pick_scripted_action`,
+get_demo_data_pick.py:54-67; hp_demo_episodes_pick); `script=None` takes the environment's own `default_demo_script()`.
+
+`NativePickPlaceVecEnv` is the third native environment: a kinematic pick-and-place whose fourth action component moves the
+fingers, whose block is grasped by closing open fingers around it and never released, and whose reset is the rejection loop in
+three dimensions.
+
+`PointMassVecEnv` is the tensor twin of `synthetic.PointMassGoalEnv`, `PushBlockVecEnv` that of `synthetic.PushBlockGoalEnv`,
+`PickPlaceVecEnv` that of `synthetic.PickPlaceGoalEnv`; what
 they share (`_GoalVecEnv`) includes the rule that an environment works on the first `active` rows of its state tensors.  A native
 class is one of them behind `_NativeEnv` -- descriptor, device reset -- plus the constant of its kind.
 """
@@ -58,6 +66,8 @@ import torch
 from . import _lib
 from .synthetic import (DemoScript, write_demo_npz_from, PUSH_RESET_ATTEMPTS, PUSH_RESET_BOUNDS, PUSH_START_Z, PUSH_X_HI, PUSH_X_LO, PUSH_Y_HI, PUSH_Y_LO,
                         PUSH_Z_HI)
+from .synthetic import (PickScript, PICK_FINGER_MAX, PICK_GRASP_WIDTH, PICK_RESET_ATTEMPTS, PICK_RESET_BOUNDS, PICK_START_Z, PICK_TOOL,
+                        PICK_X_HI, PICK_X_LO, PICK_Y_HI, PICK_Y_LO, PICK_Z_HI)
 
 
 def wave_layout(n_envs, T, obs, goal, act):
@@ -318,6 +328,93 @@ class PushBlockVecEnv(_GoalVecEnv):
         return self._stepped()
 
 
+class PickPlaceVecEnv(_GoalVecEnv):
+    """n `synthetic.PickPlaceGoalEnv`s as tensors: env i resets from RandomState(seed + i) on the host -- the same rejection loop,
+    five scalars per attempt -- and `step` is the host environment's operations elementwise in float64, one torch op per
+    rounding, `torch.where` for its branches.  State: `grip`, `blk`, `goal` [rows, 3] and `aux` [rows, 8] = gripper velocity,
+    block velocity, finger opening, held (0.0 or 1.0).  Works with device="cpu" too."""
+
+    state_names = ("grip", "blk", "goal", "aux")
+
+    def __init__(self, n_envs, seed=0, device="cuda", max_timesteps=100, distance_threshold=0.05, reward_type='sparse',
+                 step_scale=0.2, half_width=0.04, finger_scale=0.05, min_separation=0.15, table_z=0.2, grip_start=(0.25, 0.1)):
+        super().__init__(n_envs, seed, device, max_timesteps, distance_threshold, reward_type, step_scale)
+        self.half_width, self.finger_scale = float(half_width), float(finger_scale)
+        self.min_separation, self.table_z = float(min_separation), float(table_z)
+        self.grip_start = (float(grip_start[0]), float(grip_start[1]))
+        self.reset_attempts = [0] * self.n_envs      # attempts the last host reset of each environment took
+        z = torch.zeros((self.n_envs, 3), dtype=torch.float64, device=self.device)
+        self.grip, self.blk, self.goal = z, z.clone(), z.clone()
+        self.aux = torch.zeros((self.n_envs, 8), dtype=torch.float64, device=self.device)
+
+    @property
+    def pos(self):
+        """The gripper's position (nothing in the package reads it)."""
+        return self.grip
+
+    def params(self):
+        """hp_env_desc.params of the kind"""
+        return [self.step_scale, self.distance_threshold, self.half_width, self.finger_scale, self.min_separation, self.table_z,
+                self.grip_start[0], self.grip_start[1]]
+
+    def _observation(self):
+        k = self.active
+        grip, blk, aux = self.grip[:k], self.blk[:k], self.aux[:k]
+        obs = torch.zeros((k, 27), dtype=torch.float64, device=self.device)
+        obs[:, 0:3] = grip
+        obs[:, 6:9] = aux[:, 0:3]
+        obs[:, 9:11] = aux[:, 6:8]
+        obs[:, 12:15] = blk
+        obs[:, 18:21] = blk - grip
+        obs[:, 21:24] = aux[:, 3:6]
+        return {'observation': obs, 'achieved_goal': blk.clone(), 'desired_goal': self.goal[:k].clone()}
+
+    def reset(self, n_active=None):
+        """Reset the first `n_active` environments (default: all): only those draw from their streams."""
+        k = self._n_active(n_active)
+        fresh = np.empty((3, k, 3))
+        for i in range(k):
+            for attempt in range(PICK_RESET_ATTEMPTS):
+                bx, by, gx, gy, gz = (self.rs[i].uniform(low, high) for low, high in PICK_RESET_BOUNDS)
+                ddx, ddy, ddz = bx - gx, by - gy, self.table_z - gz
+                if np.sqrt(ddx * ddx + ddy * ddy + ddz * ddz) >= self.min_separation:
+                    break
+            self.reset_attempts[i] = attempt + 1
+            fresh[0, i] = (self.grip_start[0], self.grip_start[1], PICK_START_Z)
+            fresh[1, i] = (bx, by, self.table_z)
+            fresh[2, i] = (gx, gy, gz)
+        dev = torch.from_numpy(fresh).to(self.device)
+        self.grip, self.blk, self.goal = dev[0].contiguous(), dev[1].contiguous(), dev[2].contiguous()
+        self.aux = torch.zeros((k, 8), dtype=torch.float64, device=self.device)
+        self.active = k
+        return self._observation()
+
+    def _pads_inside(self, grip, blk):
+        tool = torch.tensor(PICK_TOOL, dtype=torch.float64, device=self.device)
+        return ((blk - (grip + tool)).abs() < self.half_width).all(dim=1)
+
+    def step(self, actions):
+        k = self.active
+        grip, blk, aux = self.grip[:k], self.blk[:k], self.aux[:k]
+        lo = torch.tensor([PICK_X_LO, PICK_Y_LO, self.table_z], dtype=torch.float64, device=self.device)
+        hi = torch.tensor([PICK_X_HI, PICK_Y_HI, PICK_Z_HI], dtype=torch.float64, device=self.device)
+        a = torch.clamp(actions.to(torch.float64), -0.5, 0.5)
+        held, f_old = aux[:, 7] != 0, aux[:, 6]
+        near = held | self._pads_inside(grip, blk)          # the finger lock, on the state before the move
+        a3 = torch.where(near, torch.full_like(f_old, -1.0), a[:, 3])
+        finger = torch.clamp(f_old + self.finger_scale * a3, 0.0, PICK_FINGER_MAX)
+        scaled = self.step_scale * a[:, :3]                 # multiply, then add: two roundings, like numpy
+        new = torch.minimum(torch.maximum(grip + scaled, lo), hi)
+        gvel = new - grip
+        carried = torch.minimum(torch.maximum(blk + gvel, lo), hi)
+        moved = torch.where(held[:, None], carried, blk)
+        grasp = ~held & self._pads_inside(new, blk) & (f_old > PICK_GRASP_WIDTH) & (finger <= PICK_GRASP_WIDTH)
+        bvel = moved - blk
+        self.aux[:k] = torch.cat([gvel, bvel, finger[:, None], (held | grasp).to(torch.float64)[:, None]], dim=1)
+        self.grip[:k], self.blk[:k] = new, moved
+        return self._stepped()
+
+
 class _NativeEnv:
     """What the native environments share: the descriptor, and the switch to reset on the device.  Mixed in before a
     `_GoalVecEnv` that has `params()`; the subclass names the library's kind."""
@@ -325,6 +422,10 @@ class _NativeEnv:
     is_native_device_env = True
     kind = None              # _lib.ENV_*: the struct of csrc/env_device.h that evaluates the same float64 operations
     reset_streams = None     # random.DeviceRandomStreams after enable_device_reset(): reset stream i = the state of rs[i]
+
+    def default_demo_script(self):
+        """The scripted controller `generate_demos` runs on this environment when the caller names none: the task's own"""
+        return DemoScript()
 
     def native_desc(self):
         """hp_env_desc of the environments stepped now: kind, `params()`, and the state tensors in the order of `state_names`
@@ -397,6 +498,18 @@ class NativePushBlockVecEnv(_NativeEnv, PushBlockVecEnv):
     kind = _lib.ENV_PUSH_BLOCK
 
 
+class NativePickPlaceVecEnv(_NativeEnv, PickPlaceVecEnv):
+    """`PickPlaceVecEnv` whose dynamics the library also evaluates itself (PickPlaceEnvDev, csrc/env_device.h: the same float64
+    operations, one by one): one launch per wave, the three-dimensional rejection loop of its reset on the device after
+    `enable_device_reset()`, and the reference's pick-and-place schedule as its scripted controller.  `step` is the parent's, so
+    the per-step protocol works on it unchanged."""
+
+    kind = _lib.ENV_PICK_PLACE
+
+    def default_demo_script(self):
+        return PickScript()
+
+
 # ---- demonstrations from the scripted controller ---------------------------------------------------------------------------------
 DEMO_ROUND_EPISODES = 2048       # episodes a round of generate_demos aims at by default (a block of 56 MB at T = 100)
 
@@ -411,8 +524,16 @@ def default_round_waves(n_demos, n_envs):
 
 
 def script_desc(script=None):
-    """`synthetic.DemoScript` (None: the reference's numbers) as the library's struct (hp_demo_script)."""
+    """`synthetic.DemoScript` (None: the reference's numbers) as the library's struct (hp_demo_script), or a
+    `synthetic.PickScript` as its own (hp_pick_script)."""
     s = script or DemoScript()
+    if isinstance(s, PickScript):
+        d = _lib.PickScriptDesc()
+        for name in ("phase_end", "lift", "approach", "grasp"):
+            for i, v in enumerate(getattr(s, name)):
+                getattr(d, name)[i] = v
+        d.open = s.open
+        return d
     d = _lib.DemoScriptDesc()
     for i, v in enumerate(s.phase_end):
         d.phase_end[i] = v
@@ -450,9 +571,11 @@ class DeviceDemos:
 
 
 def generate_demos(vec_env, n_demos, round_waves=None, max_episodes=10000, script=None, ctx=None, *, launch_cap=None):
-    """`n_demos` successful episodes of the scripted push controller (`synthetic.DemoScript`, default: the reference's numbers)
-    on the native environment `vec_env`, generated and filtered on the device: the device form of `synthetic.scripted_demos`,
-    bit for bit what that returns for host twins in the states of `vec_env`'s reset streams.
+    """`n_demos` successful episodes of a scripted controller -- `script`: a `synthetic.DemoScript` (the push schedule,
+    hp_demo_episodes) or a `synthetic.PickScript` (the pick-and-place schedule, hp_demo_episodes_pick); None: the environment's
+    `default_demo_script()`, the reference's numbers for its task -- on the native environment `vec_env`, generated and filtered
+    on the device: the device form of `synthetic.scripted_demos`, bit for bit what that returns for host twins in the states of
+    `vec_env`'s reset streams.
 
     Rounds as there: a round attempts n_envs * round_waves episodes, cut to what `max_episodes` leaves (episode e = w * n_envs
     + i is environment i's w-th of the round, reset from reset stream i) as one launch of hp_demo_episodes -- or the few the
@@ -492,15 +615,18 @@ def generate_demos(vec_env, n_demos, round_waves=None, max_episodes=10000, scrip
     step_success = torch.zeros((per_round, T), dtype=torch.float32, device=dev)
     info = torch.zeros((n_demos, T), dtype=torch.float32, device=dev)
     kept_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+    if script is None and hasattr(vec_env, "default_demo_script"):
+        script = vec_env.default_demo_script()
     sd, launches = script_desc(script), C.c_int32()
+    demo_episodes = lib.hp_demo_episodes_pick if isinstance(sd, _lib.PickScriptDesc) else lib.hp_demo_episodes
     ptr = lambda t: C.c_void_p(t.data_ptr())
     kept = attempted = total_launches = 0
     while kept < n_demos and attempted < max_episodes:
         n = min(n_envs * round_waves, max_episodes - attempted)
         env = vec_env.env_desc()
         with ctx.torch_bridge():
-            _lib.check(lib.hp_demo_episodes(ctx.h, C.byref(env), vec_env.reset_streams.h, C.byref(sd), n_envs, 0, n, T, src.h,
-                                            ptr(success), ptr(step_success), C.byref(launches)))
+            _lib.check(demo_episodes(ctx.h, C.byref(env), vec_env.reset_streams.h, C.byref(sd), n_envs, 0, n, T, src.h,
+                                     ptr(success), ptr(step_success), C.byref(launches)))
             _lib.check(lib.hp_demo_compact(ctx.h, src.h, ptr(success), ptr(step_success), n, dst.h, ptr(info), n_demos, kept,
                                            ptr(kept_dev)))
         vec_env.active = (n - 1) % n_envs + 1                 # the environments of the round's last wave

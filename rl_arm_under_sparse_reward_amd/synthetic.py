@@ -212,6 +212,105 @@ class PushBlockGoalEnv:
         return observation, reward, False, info
 
 
+# the workspace of the pick-and-place environments (synthetic.PickPlaceGoalEnv, device_env.PickPlaceVecEnv, PickPlaceEnvDev in
+# csrc/env_device.h): x, y, z of gripper and block alike, z from the table up to PICK_Z_HI; the gripper starts at PICK_START_Z
+PICK_X_LO, PICK_X_HI, PICK_Y_LO, PICK_Y_HI, PICK_Z_HI, PICK_START_Z = 0.0, 0.5, 0.0, 0.7, 0.6, 0.3
+# the finger pads relative to the reported gripper position: the offsets of get_demo_data_pick.py:62-63 negated, so that the
+# scripted grasp pose puts the pads on the block centre
+PICK_TOOL = (0.0, 0.05, -0.05)
+PICK_FINGER_MAX, PICK_GRASP_WIDTH = 0.08, 0.04
+# the five draws of one reset attempt, in draw order: block x, y, goal x, y, z (low, high)
+PICK_RESET_BOUNDS = ((0.15, 0.35), (0.2, 0.5), (0.0, 0.35), (0.3, 0.55), (0.3, 0.5))
+PICK_RESET_ATTEMPTS = 100
+
+
+class PickPlaceGoalEnv:
+    """A kinematic pick-and-place with the GoalEnv surface of `PushBlockGoalEnv`: the setting of the reference's PickAndPlace task
+    (bmirobot_env_pickandplace_v2.py), in which the goal hangs in the air and the block gets there only in a closed hand.  The
+    block is a cube of half width `half_width`; the finger pads sit at grip + PICK_TOOL.  The first three action components move
+    the gripper, the fourth opens (+) and closes (-) the fingers, `finger_scale` per unit.  While the pads are inside the cube --
+    or the block is held -- the environment overwrites the fourth component with -1 behind the clip (the reference's finger lock,
+    :93-95).  The block is grasped in the step in which fingers wider than PICK_GRASP_WIDTH close to it or below with the pads
+    inside the cube, and a held block follows the gripper from the next step on.  The lock keeps closing a held block's fingers,
+    so a grasp never opens: the reference's quirk, kept (release and gravity are not modelled).  A gripper that arrives closed
+    passes through the block.  `step` is adds, subtracts, multiplies, compares and clamps only, so that the tensor twin and the
+    device struct agree with it bit for bit by construction.  `reset` redraws block and target until they are `min_separation`
+    apart in three dimensions (:116-131 without the orientation draws; at most 100 attempts, the last one kept either way), five
+    scalars per attempt from the environment's own RandomState."""
+
+    def __init__(self, seed=0, max_timesteps=100, distance_threshold=0.05, reward_type='sparse', step_scale=0.2, half_width=0.04,
+                 finger_scale=0.05, min_separation=0.15, table_z=0.2, grip_start=(0.25, 0.1)):
+        self.rs = np.random.RandomState(seed)
+        self.max_timesteps = int(max_timesteps)
+        self.distance_threshold = float(distance_threshold)
+        self.reward_type = reward_type
+        self.step_scale, self.half_width, self.finger_scale = float(step_scale), float(half_width), float(finger_scale)
+        self.min_separation, self.table_z = float(min_separation), float(table_z)
+        self.grip_start = (float(grip_start[0]), float(grip_start[1]))
+        self.grip, self.blk, self.goal = np.zeros(3), np.zeros(3), np.zeros(3)
+        self.gvel, self.bvel = np.zeros(3), np.zeros(3)
+        self.finger, self.held = 0.0, 0.0    # the opening of the fingers; 1.0 once the block is grasped
+        self.reset_attempts = 0              # attempts the last reset took
+
+    @property
+    def env_params(self):
+        return {'obs': 27, 'goal': 3, 'action': 4, 'action_max': 0.5, 'max_timesteps': self.max_timesteps}
+
+    def _observation(self):
+        obs = np.zeros(27)                   # the bmirobot layout: nine blocks of three
+        obs[0:3] = self.grip
+        obs[6:9] = self.gvel
+        obs[9] = self.finger
+        obs[10] = self.held
+        obs[12:15] = self.blk
+        obs[18:21] = self.blk - self.grip
+        obs[21:24] = self.bvel
+        return {'observation': obs, 'achieved_goal': self.blk.copy(), 'desired_goal': self.goal.copy()}
+
+    def reset(self):
+        for attempt in range(PICK_RESET_ATTEMPTS):
+            bx, by, gx, gy, gz = (self.rs.uniform(low, high) for low, high in PICK_RESET_BOUNDS)
+            ddx, ddy, ddz = bx - gx, by - gy, self.table_z - gz
+            if np.sqrt(ddx * ddx + ddy * ddy + ddz * ddz) >= self.min_separation:
+                break
+        self.reset_attempts = attempt + 1
+        self.blk = np.array([bx, by, self.table_z])
+        self.goal = np.array([gx, gy, gz])
+        self.grip = np.array([self.grip_start[0], self.grip_start[1], PICK_START_Z])
+        self.gvel, self.bvel = np.zeros(3), np.zeros(3)
+        self.finger, self.held = 0.0, 0.0
+        return self._observation()
+
+    compute_reward = PushBlockGoalEnv.compute_reward
+    _is_success = PushBlockGoalEnv._is_success
+
+    def _pads_inside(self):
+        """Every finger pad coordinate is less than half_width from the block centre"""
+        return all(abs(self.blk[c] - (self.grip[c] + PICK_TOOL[c])) < self.half_width for c in range(3))
+
+    def step(self, action):
+        action = np.clip(np.asarray(action, dtype=np.float64), -0.5, 0.5)
+        if self.held != 0.0 or self._pads_inside():          # :93-95 the finger lock, behind the clip
+            action[3] = -1.0
+        f_old = self.finger
+        self.finger = min(max(self.finger + self.finger_scale * action[3], 0.0), PICK_FINGER_MAX)
+        lo = np.array([PICK_X_LO, PICK_Y_LO, self.table_z])
+        hi = np.array([PICK_X_HI, PICK_Y_HI, PICK_Z_HI])
+        new = np.clip(self.grip + self.step_scale * action[:3], lo, hi)
+        self.gvel = new - self.grip
+        self.grip = new
+        old = self.blk.copy()
+        if self.held != 0.0:                                  # carried: the gripper's clipped displacement, clipped again
+            self.blk = np.clip(self.blk + self.gvel, lo, hi)
+        elif self._pads_inside() and f_old > PICK_GRASP_WIDTH and self.finger <= PICK_GRASP_WIDTH:
+            self.held = 1.0                                   # grasped; the block moves from the next step on
+        self.bvel = self.blk - old
+        observation = self._observation()
+        info = {'is_success': self._is_success(observation['achieved_goal'], self.goal)}
+        reward = self.compute_reward(observation['achieved_goal'], self.goal, info)
+        return observation, reward, False, info
+
+
 # ---- demonstrations from a scripted controller (the reference's get_demo_data_push.py) ------------------------------------------
 class DemoScript:
     """The numbers of the reference's push schedule (get_demo_data_push.py:39-61); the defaults are the reference's.
@@ -259,15 +358,62 @@ def scripted_action(t, obs, g, script=None):
     return np.array(action, dtype=np.float64)
 
 
+class PickScript:
+    """The numbers of the reference's pick-and-place schedule (get_demo_data_pick.py:54-67); the defaults are the reference's.
+    `phase_end`: the last timestep, counted from 1, of phases one to five (the sixth runs to T); `lift`: the constant action of
+    phase one (:55); `approach`: what phase two adds to block - gripper (:57-58); `grasp`: what phase four adds to it (:62-63);
+    `open`: the finger action of phase three (:60), and negated that of phase five (:65).  hp_pick_script of include/rlarm_hip.h
+    holds the same fields."""
+
+    def __init__(self, phase_end=(10, 30, 50, 70, 90), lift=(0.0, -0.1, 0.1, 0.0), approach=(0.0, -0.2, 0.1), grasp=(0.0, -0.05, 0.05),
+                 open=0.1):
+        self.phase_end = tuple(int(e) for e in phase_end)
+        self.lift = tuple(float(v) for v in lift)
+        self.approach = tuple(float(v) for v in approach)
+        self.grasp = tuple(float(v) for v in grasp)
+        self.open = float(open)
+        if len(self.phase_end) != 5 or len(self.lift) != 4 or len(self.approach) != 3 or len(self.grasp) != 3:
+            raise ValueError("PickScript: five phase ends, four lift components, three approach and three grasp components")
+        if self.phase_end[0] < 0 or any(b <= a for a, b in zip(self.phase_end, self.phase_end[1:])):
+            raise ValueError(f"PickScript: the phase ends {self.phase_end} must be increasing")
+
+
+def pick_scripted_action(t, obs, g, script=None):
+    """The reference's pick-and-place controller (get_demo_data_pick.py:54-67) for timestep t = 1 .. T: the float64 action [4],
+    unclipped, out of the observation row -- gripper obs[0:3], block obs[12:15] -- and the desired goal.  No stop rule.  One
+    float64 operation per rounding; the offset is always added, also where it is 0.0: csrc/demo_episodes.h (demo_action_pick)
+    repeats the operations one by one."""
+    s = script or PickScript()
+    grip = [float(obs[0]), float(obs[1]), float(obs[2])]
+    b = [float(obs[12]), float(obs[13]), float(obs[14])]
+    g = [float(g[0]), float(g[1]), float(g[2])]
+    e = s.phase_end
+    if t <= e[0]:                                     # :54-55 lift and retreat
+        action = list(s.lift)
+    elif t <= e[1]:                                   # :56-58 above and in front of the block
+        action = [(b[c] - grip[c]) + s.approach[c] for c in range(3)] + [0.0]
+    elif t <= e[2]:                                   # :59-60 open the fingers
+        action = [0.0, 0.0, 0.0, s.open]
+    elif t <= e[3]:                                   # :61-63 the pads onto the block
+        action = [(b[c] - grip[c]) + s.grasp[c] for c in range(3)] + [0.0]
+    elif t <= e[4]:                                   # :64-65 close the fingers
+        action = [0.0, 0.0, 0.0, -s.open]
+    else:                                             # :66-67 carry the block to the goal
+        action = [g[0] - b[0], g[1] - b[1], g[2] - b[2], 0.0]
+    return np.array(action, dtype=np.float64)
+
+
 def scripted_episode(env, script=None):
-    """One episode of `scripted_action` on a host environment, reset from its own `rs` (get_demo_data_push.py:34-74):
+    """One episode of a scripted controller on a host environment, reset from its own `rs` (get_demo_data_push.py:34-74) --
+    `pick_scripted_action` with a `PickScript`, `scripted_action` with a `DemoScript` or None:
     (obs [T+1, obs], ag [T+1, goal], g [T, goal], actions [T, act], is_success after every step [T])."""
     T = int(env.max_timesteps)
+    controller = pick_scripted_action if isinstance(script, PickScript) else scripted_action
     o = env.reset()
     obs, ag, g = o['observation'], o['achieved_goal'], o['desired_goal']
     ep_obs, ep_ag, ep_g, ep_act, ep_ok = [], [], [], [], []
     for t in range(1, T + 1):
-        action = scripted_action(t, obs, g, script)
+        action = controller(t, obs, g, script)
         o, _, _, info = env.step(action)
         ep_obs.append(obs.copy()); ep_ag.append(ag.copy()); ep_g.append(g.copy()); ep_act.append(action)
         ep_ok.append(np.float32(info['is_success']))
@@ -277,7 +423,8 @@ def scripted_episode(env, script=None):
 
 
 def scripted_demos(envs, n_demos, round_waves, max_episodes=10000, script=None):
-    """Successful scripted episodes of the host environments `envs` (PointMassGoalEnv / PushBlockGoalEnv), a pure function of its
+    """Successful scripted episodes of the host environments `envs` (PointMassGoalEnv / PushBlockGoalEnv / PickPlaceGoalEnv;
+    `script`: a `DemoScript`, a `PickScript` or None as in `scripted_episode`), a pure function of its
     inputs -- the host statement of `device_env.generate_demos`.  A round attempts len(envs) * round_waves episodes, cut to what
     `max_episodes` leaves; episode e = w * n_envs + i of a round is environment i's w-th, reset from that environment's own `rs`
     (the numbering of hp_rollout_waves).  An episode is kept if `is_success` is 1 after its last step; kept episodes stay in

@@ -1,0 +1,364 @@
+"""The pick-and-place environment and its scripted controller without a device: `synthetic.PickPlaceGoalEnv` (the specification)
+on cases written out by hand, the draws of its reset counted against a second generator, the tensor twin
+`device_env.PickPlaceVecEnv` on the CPU against it bit for bit, `synthetic.pick_scripted_action` against the reference's six
+expressions, what the controller achieves, and the pinned constants of header and ABI table."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import bits
+from rl_arm_under_sparse_reward_amd import _lib
+from rl_arm_under_sparse_reward_amd.device_env import (NativePickPlaceVecEnv, NativePointMassVecEnv, NativePushBlockVecEnv, PickPlaceVecEnv,
+                                                       fused_rollout_reason, script_desc)
+from rl_arm_under_sparse_reward_amd.synthetic import (PICK_FINGER_MAX, PICK_GRASP_WIDTH, PICK_RESET_ATTEMPTS, PICK_RESET_BOUNDS, PICK_START_Z,
+                                                      PICK_TOOL, PICK_X_HI, PICK_X_LO, PICK_Y_HI, PICK_Y_LO, PICK_Z_HI, DemoScript,
+                                                      PickPlaceGoalEnv, PickScript, PushBlockGoalEnv, pick_scripted_action, scripted_action,
+                                                      scripted_demos, scripted_episode)
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+T = 12
+SHORT = PickScript(phase_end=(1, 4, 6, 9, 10), open=0.5)      # all six phases inside T = 12
+
+
+def placed(grip, blk, finger=0.0, held=0.0, goal=(0.1, 0.4, 0.4), **kw):
+    """An environment put into a state by hand"""
+    e = PickPlaceGoalEnv(**kw)
+    e.reset()
+    e.grip, e.blk, e.goal = np.array(grip, dtype=np.float64), np.array(blk, dtype=np.float64), np.array(goal, dtype=np.float64)
+    e.finger, e.held = float(finger), float(held)
+    return e
+
+
+def on_block(blk):
+    """The gripper position that puts the finger pads on the block centre"""
+    return [blk[c] - PICK_TOOL[c] for c in range(3)]
+
+
+# ------------------------------------------------------------------------------------------------------- 1. step, by hand
+def test_a_closed_gripper_passes_through_the_block():
+    blk = [0.25, 0.3, 0.2]
+    start = on_block(blk)
+    start[1] -= 0.1                                       # 10 cm in front of the block, fingers closed
+    e = placed(start, blk, finger=0.0, step_scale=0.2)
+    for k in range(4):                                    # 5 cm a step along y: outside, on the centre, outside, outside
+        o, _, _, _ = e.step([0.0, 0.25, 0.0, 0.5])
+        assert e.held == 0.0 and np.array_equal(e.blk, blk) and not e.bvel.any(), k
+        assert o['observation'][10] == 0.0
+    # the fourth component opened the fingers outside the cube (steps one and four; two was locked, three closed what one opened)
+    assert e.grip[1] == pytest.approx(start[1] + 0.2) and e.finger == 0.05 * 0.5
+
+
+def test_open_fingers_entering_the_cube_grasp_on_the_following_step():
+    blk = [0.25, 0.3, 0.2]
+    start = on_block(blk)
+    start[1] -= 0.05
+    e = placed(start, blk, finger=PICK_FINGER_MAX, step_scale=0.2)
+    o, _, _, _ = e.step([0.0, 0.25, 0.0, 0.0])            # enters: near was judged before the move, the fingers stay open
+    assert e.held == 0.0 and e.finger == PICK_FINGER_MAX and np.array_equal(e.blk, blk)
+    o, _, _, _ = e.step([0.0, 0.0, 0.0, 0.5])             # inside: the lock overwrites +0.5 with -1, 0.08 - 0.05 <= 0.04
+    assert e.held == 1.0 and e.finger == PICK_FINGER_MAX + 0.05 * -1.0 and np.array_equal(e.blk, blk) and not e.bvel.any()
+    assert o['observation'][9] == e.finger and o['observation'][10] == 1.0
+    before = e.grip.copy()
+    o, _, _, _ = e.step([0.25, 0.0, 0.25, 0.5])           # held: the block follows from the next step on, the lock stays
+    assert e.gvel[0] == (before[0] + 0.2 * 0.25) - before[0] and e.gvel[1] == 0.0 and e.gvel[2] > 0.04
+    assert np.array_equal(e.bvel, (np.array(blk) + e.gvel) - np.array(blk)) and np.array_equal(e.blk, np.array(blk) + e.gvel)
+    assert e.finger == 0.0 and e.held == 1.0
+    assert np.array_equal(o['observation'][21:24], e.bvel) and np.array_equal(o['observation'][18:21], e.blk - e.grip)
+    assert np.array_equal(o['achieved_goal'], e.blk)
+    # fingers that are half closed already (0.04 is not > GRASP_WIDTH) never grasp
+    e = placed(on_block(blk), blk, finger=PICK_GRASP_WIDTH, step_scale=0.2)
+    e.step([0.0, 0.0, 0.0, 0.5])
+    assert e.held == 0.0 and e.finger == 0.0
+
+
+def test_a_held_block_follows_and_is_clipped_where_the_gripper_is_not():
+    # the table: the block 3 cm above the pads' height at z = 0.22, the gripper comes down 5 cm and is nowhere near its own bound
+    e = placed([0.25, 0.25, 0.3], [0.25, 0.3, 0.22], held=1.0, step_scale=0.2)
+    e.step([0.0, 0.0, -0.25, 0.0])
+    assert e.grip[2] == 0.3 + 0.2 * -0.25 and e.gvel[2] == e.grip[2] - 0.3
+    assert e.blk[2] == e.table_z == 0.2 and e.bvel[2] == 0.2 - 0.22 and e.bvel[2] != e.gvel[2]
+    # the ceiling, with a cube wide enough to be held 18 cm above the pads
+    e = placed([0.25, 0.25, 0.45], [0.25, 0.3, 0.58], held=1.0, step_scale=0.2, half_width=0.2)
+    e.step([0.0, 0.0, 0.5, 0.0])
+    assert e.grip[2] == 0.45 + 0.2 * 0.5 < PICK_Z_HI and e.blk[2] == PICK_Z_HI and e.bvel[2] == PICK_Z_HI - 0.58
+    # x and y: the workspace of the push block
+    e = placed([0.45, 0.6, 0.4], [0.49, 0.69, 0.35], held=1.0, step_scale=0.2, half_width=0.2)
+    e.step([0.5, 0.5, 0.0, 0.0])
+    assert np.array_equal(e.blk[:2], [PICK_X_HI, PICK_Y_HI]) and np.array_equal(e.grip[:2], [0.5, 0.7])
+    assert (PICK_X_LO, PICK_Y_LO, PICK_START_Z) == (0.0, 0.0, 0.3)
+
+
+def test_the_fourth_component_is_overwritten_only_when_near():
+    blk = [0.25, 0.3, 0.2]
+    far = placed([0.25, 0.1, 0.3], blk, finger=0.04, step_scale=0.2)
+    far.step([0.0, 0.0, 0.0, 0.7])                        # clipped to 0.5 first
+    assert far.finger == 0.04 + 0.05 * 0.5
+    near = placed(on_block(blk), blk, finger=0.04, step_scale=0.2)
+    near.step([0.0, 0.0, 0.0, 0.7])
+    assert near.finger == 0.0                             # 0.04 + 0.05 * -1 clipped at 0: -1 is not clipped to -0.5
+    # one axis outside the cube is not near
+    edge = on_block(blk)
+    edge[2] += 0.05                                       # x and y on the centre, z a centimetre past the face
+    e = placed(edge, blk, finger=0.04, step_scale=0.2)
+    e.step([0.0, 0.0, 0.0, 0.5])
+    assert e.finger == 0.04 + 0.05 * 0.5
+    # the action handed in is not written to
+    a = np.array([0.0, 0.0, 0.0, 0.7])
+    near.step(a)
+    assert a[3] == 0.7
+
+
+# ------------------------------------------------------------------------------------------------------------ 2. the reset
+@pytest.mark.parametrize("min_separation", [0.15, 0.3, 0.5])
+def test_the_reset_consumes_five_uniforms_an_attempt(min_separation):
+    """64 seeds.  min_separation = 0.3: 47 of the 64 resets take more than one attempt, 12 at most; 0.5 is near the farthest
+    the ranges allow (0.58), so 62 of the 64 resets spend all 100 attempts and keep the last (seeds 55 and 56 are accepted at
+    attempts 56 and 40)."""
+    attempts = []
+    for seed in range(64):
+        e, shadow = PickPlaceGoalEnv(seed=seed, min_separation=min_separation), np.random.RandomState(seed)
+        o = e.reset()
+        attempts.append(e.reset_attempts)
+        for _ in range(e.reset_attempts):
+            u = [shadow.uniform(low, high) for low, high in PICK_RESET_BOUNDS]
+        assert_states_equal(e.rs.get_state(), shadow.get_state())
+        assert np.array_equal(e.blk, [u[0], u[1], e.table_z]) and np.array_equal(e.goal, u[2:5])
+        assert np.array_equal(e.grip, [0.25, 0.1, PICK_START_Z]) and e.finger == 0.0 and e.held == 0.0
+        assert not o['observation'][6:12].any() and np.array_equal(o['observation'][18:21], e.blk - e.grip)
+        d = np.sqrt((u[0] - u[2]) ** 2 + (u[1] - u[3]) ** 2 + (e.table_z - u[4]) ** 2)
+        assert e.reset_attempts == PICK_RESET_ATTEMPTS or d >= min_separation
+    print(min_separation, "attempts:", attempts)
+    if min_separation == 0.3:
+        assert sum(a > 1 for a in attempts) > 32 and 1 in attempts and 2 < max(attempts) < PICK_RESET_ATTEMPTS
+    if min_separation == 0.5:
+        assert PICK_RESET_ATTEMPTS == 100 and attempts[:55] == [100] * 55 and attempts.count(100) == 62 and min(attempts) >= 40
+
+
+def assert_states_equal(a, b):
+    assert a[0] == b[0] and np.array_equal(a[1], b[1]) and a[2:] == b[2:]
+
+
+def test_reset_ranges_are_float64_differences():
+    assert len(PICK_RESET_BOUNDS) == 5 and len({(low, high - low) for low, high in PICK_RESET_BOUNDS}) == 5    # five one-value draws
+    rs, raw = np.random.RandomState(3), np.random.RandomState(3)
+    for low, high in PICK_RESET_BOUNDS * 40:
+        assert rs.uniform(low, high) == low + (high - low) * raw.random_sample()
+    struct = open(os.path.join(REPO, "rl_arm_under_sparse_reward_amd", "csrc", "env_device.h")).read()
+    struct = struct[struct.index("struct PickPlaceEnvDev"):]
+    lo, hi = (", ".join(repr(b[k]) for b in PICK_RESET_BOUNDS) for k in (0, 1))
+    assert f"lo[5] = {{{lo}}}, hi[5] = {{{hi}}}" in struct and "range = hi[k] - lo[k];" in struct
+    assert "RESET_DRAWS = 5, RESET_ATTEMPTS = 100, STATE_ARRAYS = 4" in struct
+    assert f"X_LO = {PICK_X_LO}, X_HI = {PICK_X_HI}, Y_LO = {PICK_Y_LO}, Y_HI = {PICK_Y_HI}, Z_HI = {PICK_Z_HI}, START_Z = {PICK_START_Z}" in struct
+    assert (f"TOOL_X = {PICK_TOOL[0]}, TOOL_Y = {PICK_TOOL[1]}, TOOL_Z = {PICK_TOOL[2]}, FINGER_MAX = {PICK_FINGER_MAX}, "
+            f"GRASP_WIDTH = {PICK_GRASP_WIDTH}") in struct
+
+
+# -------------------------------------------------------------------------------------------------------- 3. the controller
+def test_the_controller_is_the_references_six_expressions():
+    rs = np.random.RandomState(5)
+    for _ in range(200):
+        obs, g = rs.uniform(-1, 1, 27), rs.uniform(-1, 1, 3)
+        grip_pos, blocK_pos = obs[:3], obs[12:15]
+        want = {
+            1: [0, -0.1, 0.1, 0],
+            2: [blocK_pos[0] - grip_pos[0], blocK_pos[1] - grip_pos[1] - 0.2, blocK_pos[2] - grip_pos[2] + 0.1, 0],
+            3: [0, 0, 0, 0.1],
+            4: [blocK_pos[0] - grip_pos[0], blocK_pos[1] - grip_pos[1] - 0.05, blocK_pos[2] - grip_pos[2] + 0.05, 0],
+            5: [0, 0, 0, -0.1],
+            6: [g[0] - blocK_pos[0], g[1] - blocK_pos[1], g[2] - blocK_pos[2], 0],
+        }
+        for t, phase in ((1, 1), (10, 1), (11, 2), (30, 2), (31, 3), (50, 3), (51, 4), (70, 4), (71, 5), (90, 5), (91, 6), (100, 6)):
+            for script in (None, PickScript()):
+                got = pick_scripted_action(t, obs, g, script)
+                assert got.dtype == np.float64 and got.shape == (4,)
+                assert np.array_equal(got, np.array(want[phase], dtype=np.float64)), (t, phase)
+    # the short schedule visits the same phases at its own ends; the offsets are added one rounding at a time
+    obs, g = rs.uniform(0, 0.5, 27), rs.uniform(0, 0.5, 3)
+    s = PickScript(phase_end=(1, 4, 6, 9, 10), approach=(0.01, -0.3, 0.2), grasp=(0.02, 0.03, 0.04), open=0.5, lift=(0.1, 0.2, 0.3, 0.4))
+    d = [obs[12 + c] - obs[c] for c in range(3)]
+    assert np.array_equal(pick_scripted_action(1, obs, g, s), [0.1, 0.2, 0.3, 0.4])
+    assert np.array_equal(pick_scripted_action(4, obs, g, s), [d[0] + 0.01, d[1] + -0.3, d[2] + 0.2, 0.0])
+    assert np.array_equal(pick_scripted_action(6, obs, g, s), [0, 0, 0, 0.5])
+    assert np.array_equal(pick_scripted_action(7, obs, g, s), [d[0] + 0.02, d[1] + 0.03, d[2] + 0.04, 0.0])
+    assert np.array_equal(pick_scripted_action(10, obs, g, s), [0, 0, 0, -0.5])
+    assert np.array_equal(pick_scripted_action(11, obs, g, s), [g[c] - obs[12 + c] for c in range(3)] + [0.0])
+
+
+def test_the_script_validates_like_the_push_script():
+    s = PickScript()
+    assert s.phase_end == (10, 30, 50, 70, 90) and s.lift == (0.0, -0.1, 0.1, 0.0) and s.approach == (0.0, -0.2, 0.1)
+    assert s.grasp == (0.0, -0.05, 0.05) and s.open == 0.1
+    assert tuple(-v for v in s.grasp) == tuple(float(v) for v in PICK_TOOL)      # the grasp pose puts the pads on the block centre
+    with pytest.raises(ValueError, match="must be increasing"):
+        PickScript(phase_end=(2, 4, 4, 10, 12))
+    with pytest.raises(ValueError, match="PickScript: five phase ends"):
+        PickScript(grasp=(0.0, 0.1))
+
+
+def run_script(script, steps, step_scale, n=64):
+    """(successes, grasps) of n scripted episodes, one per seed"""
+    ok = held = 0
+    for seed in range(n):
+        e = PickPlaceGoalEnv(seed=seed, max_timesteps=steps, step_scale=step_scale)
+        ok += int(scripted_episode(e, script)[4][-1] == 1.0)
+        held += int(e.held)
+    return ok, held
+
+
+def test_the_controller_reaches_a_grasp_and_the_goal():
+    """Measured on the host twin, 64 seeds: the reference's schedule at T = 100 succeeds in 64 of 64 episodes at step_scale 0.2,
+    in 28 at 0.15 and in none at 0.1 (all 64 grasped every time: a short step leaves the carry phase too short).  The short
+    schedule (1, 4, 6, 9, 10) with open = 0.5 at T = 12: 45 of 64 at step_scale 0.6, and 10 of 64 at 0.5 with all 64 grasped.
+    The configuration the device tests use -- short schedule, step_scale 0.6 -- keeps some episodes and rejects others."""
+    full = run_script(PickScript(), 100, 0.2)
+    print("default schedule, T = 100, step_scale 0.2:", full)
+    assert full == (64, 64)
+    for scale in (0.6, 0.5):
+        ok, held = run_script(SHORT, T, scale)
+        print(f"short schedule, T = {T}, step_scale {scale}: {ok} of 64 succeed, {held} grasped")
+        assert 1 <= ok <= 63 and held >= ok
+    # through scripted_demos: rounds, kept in order, the surplus of the last round dropped
+    envs = [PickPlaceGoalEnv(seed=i, max_timesteps=T, step_scale=0.6) for i in range(5)]
+    obs, ag, g, actions, info, attempted = scripted_demos(envs, 4, 2, max_episodes=40, script=SHORT)
+    assert obs.shape == (4, T + 1, 27) and actions.shape == (4, T, 4) and attempted % 10 == 0 and 4 <= attempted <= 40
+    assert np.all(info[:, -1] == 1.0) and np.all(obs[:, -1, 10] == 1.0) and np.array_equal(ag, obs[:, :, 12:15])
+    assert np.array_equal(actions[:, 0], np.tile(SHORT.lift, (4, 1))) and np.all(actions[:, 5, 3] == 0.5) and np.all(actions[:, 9, 3] == -0.5)
+
+
+def test_either_script_runs_on_either_environment_and_none_is_the_push_script():
+    """scripted_episode picks the controller by the script's type; with a DemoScript or None it is what it was"""
+    for script in (None, DemoScript(phase_end=(1, 2, 3, 4, 5))):
+        a, b = PushBlockGoalEnv(seed=4, max_timesteps=T), PushBlockGoalEnv(seed=4, max_timesteps=T)
+        ep = scripted_episode(a, script)
+        o = b.reset()
+        for t in range(1, T + 1):
+            action = scripted_action(t, o['observation'], o['desired_goal'], script)
+            assert np.array_equal(bits(ep[3][t - 1]), bits(action)) and np.array_equal(bits(ep[0][t - 1]), bits(o['observation']))
+            o = b.step(action)[0]
+    pick_on_push = scripted_episode(PushBlockGoalEnv(seed=4, max_timesteps=T), SHORT)
+    assert np.array_equal(pick_on_push[3][5], [0, 0, 0, 0.5])
+    push_on_pick = scripted_episode(PickPlaceGoalEnv(seed=4, max_timesteps=T), DemoScript(phase_end=(1, 2, 3, 4, 5)))
+    assert np.array_equal(push_on_pick[3][0], DemoScript().lift) and not push_on_pick[3][:, 3].any()
+
+
+# ---------------------------------------------------------------------------------------------------- 4. the tensor twin
+@pytest.mark.parametrize("cls", [PickPlaceVecEnv, NativePickPlaceVecEnv])
+def test_the_tensor_twin_equals_the_host_twins_on_the_cpu(cls):
+    """Four waves of T steps on five environments, scripted actions (grasps, carried blocks) and random ones in turn, full and
+    partial waves: observations, flags, rewards and the state tensors, bit for bit."""
+    n, kw = 5, dict(step_scale=0.6, max_timesteps=T, min_separation=0.3)
+    hosts = [PickPlaceGoalEnv(seed=3 + i, **kw) for i in range(n)]
+    vec = cls(n, seed=3, device="cpu", **kw)
+    rs, grasped = np.random.RandomState(0), 0
+    for wave, k in enumerate((n, 3, n, 1)):
+        ho, vo = [h.reset() for h in hosts[:k]], vec.reset(None if k == n else k)
+        assert vec.active == k and vec.reset_attempts[:k] == [h.reset_attempts for h in hosts[:k]]
+        for t in range(1, T + 1):
+            for key in vo:
+                assert np.array_equal(bits(vo[key].numpy()), bits(np.stack([o[key] for o in ho]))), (wave, t, key)
+            if wave % 2 == 0:
+                acts = np.stack([pick_scripted_action(t, o['observation'], o['desired_goal'], SHORT) for o in ho])
+            else:
+                acts = rs.uniform(-0.7, 0.7, (k, 4))
+            acts = acts.astype(np.float32)
+            out = [h.step(acts[i]) for i, h in enumerate(hosts[:k])]
+            ho = [o[0] for o in out]
+            vo, reward, _, info = vec.step(torch.from_numpy(acts))
+            assert np.array_equal(info['is_success'].numpy(), np.array([o[3]['is_success'] for o in out], dtype=np.float32))
+            assert np.array_equal(reward.numpy(), np.array([o[1] for o in out], dtype=np.float32))
+        for i, h in enumerate(hosts[:k]):
+            want = {"grip": h.grip, "blk": h.blk, "goal": h.goal, "aux": np.concatenate([h.gvel, h.bvel, [h.finger, h.held]])}
+            for name, v in want.items():
+                assert np.array_equal(bits(getattr(vec, name)[i].numpy()), bits(v)), (wave, i, name)
+        grasped += sum(int(h.held) for h in hosts[:k])
+    assert grasped >= 2
+
+
+# ------------------------------------------------------------------------------------------------------------------ 5. ABI
+def test_header_and_abi_table_carry_the_kind_and_the_script():
+    header = open(os.path.join(REPO, "include", "rlarm_hip.h")).read()
+    assert re.search(r"^enum\s*\{\s*HP_ENV_PICK_PLACE\s*=\s*3\s*\};\s*$", header, flags=re.M) and _lib.ENV_PICK_PLACE == 3
+    assert re.search(r"enum\s*\{\s*HP_ENV_PUSH_BLOCK\s*=\s*2\s*\}", header) and re.search(r"enum\s*\{\s*HP_ENV_POINT_MASS\s*=\s*1\s*\}", header)
+    assert re.search(r"#define\s+HP_ABI_VERSION\s+4\b", header) and _lib.ABI_VERSION == 4
+    assert "hp_demo_episodes_pick" in _lib.PROTOTYPES and "hp_demo_episodes_pick" not in _lib.DEBUG_SYMBOLS
+    assert re.search(r"\bint\s+hp_demo_episodes_pick\s*\(", header)
+    assert len(_lib.PROTOTYPES["hp_demo_episodes_pick"][1]) == len(_lib.PROTOTYPES["hp_demo_episodes"][1])
+    # hp_pick_script, field for field: five phase ends + padding, four + three + three + one doubles
+    body = re.search(r"typedef struct \{([^}]*)\}\s*hp_pick_script;", header).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = re.findall(r"(\w+)(?:\[(\d+)\])?\s*[;,]", body)
+    assert [(n, int(k or 1)) for n, k in fields] == [("phase_end", 5), ("reserved", 1), ("lift", 4), ("approach", 3), ("grasp", 3), ("open", 1)]
+    assert [f[0] for f in _lib.PickScriptDesc._fields_] == [n for n, _ in fields] and C.sizeof(_lib.PickScriptDesc) == 24 + 11 * 8
+    d = script_desc(PickScript())
+    assert isinstance(d, _lib.PickScriptDesc) and list(d.phase_end) == [10, 30, 50, 70, 90] and d.reserved == 0
+    assert list(d.lift) == [0.0, -0.1, 0.1, 0.0] and list(d.approach) == [0.0, -0.2, 0.1] and list(d.grasp) == [0.0, -0.05, 0.05] and d.open == 0.1
+    assert isinstance(script_desc(), _lib.DemoScriptDesc) and isinstance(script_desc(DemoScript()), _lib.DemoScriptDesc)
+    # the native class
+    env = NativePickPlaceVecEnv(4, seed=1, device="cpu", step_scale=0.07, distance_threshold=0.03, grip_start=(0.2, 0.15))
+    assert env.is_device_vec_env and env.is_native_device_env and env.reset_streams is None and env.kind == _lib.ENV_PICK_PLACE
+    assert fused_rollout_reason(env.is_native_device_env, True, True, True) is None
+    env.reset(3)
+    nd = env.native_desc()
+    assert sorted(nd) == ["kind", "params", "state"] and nd["kind"] == 3
+    assert nd["params"] == [0.07, 0.03, 0.04, 0.05, 0.15, 0.2, 0.2, 0.15] and len(nd["params"]) == len(_lib.EnvDesc().params) == 8
+    assert env.state_names == ("grip", "blk", "goal", "aux") and len(nd["state"]) == len(_lib.EnvDesc().state_dev) == 4
+    for t, name, width in zip(nd["state"], env.state_names, (3, 3, 3, 8)):
+        assert t is getattr(env, name) and t.dtype == torch.float64 and tuple(t.shape) == (3, width) and t.is_contiguous()
+    desc = env.env_desc()
+    assert desc.kind == 3 and desc.reserved == 0 and list(desc.params) == nd["params"]
+    assert [desc.state_dev[i] for i in range(4)] == [t.data_ptr() for t in nd["state"]]
+    with pytest.raises(ValueError, match="enable_device_reset: the environment lives on device 'cpu'"):
+        env.enable_device_reset()
+    # every native class names its task's controller
+    assert isinstance(env.default_demo_script(), PickScript)
+    for cls in (NativePointMassVecEnv, NativePushBlockVecEnv):
+        assert type(cls(1, device="cpu").default_demo_script()) is DemoScript
+
+
+def test_the_kind_is_a_struct_and_a_row():
+    """What adding the kind touched in csrc/: its two units in the Makefile, its row's declaration and its address in the table
+    -- and no entry point, dispatch or check that names it."""
+    csrc = os.path.join(REPO, "rl_arm_under_sparse_reward_amd", "csrc")
+    units = re.search(r"^EXACT_SRCS := (.*)$", open(os.path.join(csrc, "Makefile")).read(), flags=re.M).group(1).split()
+    assert "env_pick_place.hip" in units and "demo_pick_place.hip" in units
+    assert "extern const EnvKind env_kind_pick_place;" in open(os.path.join(csrc, "rollout_episodes.h")).read()
+    rollout = open(os.path.join(csrc, "rollout.hip")).read()
+    assert "&env_kind_pick_place}" in rollout and rollout.count("pick_place") == 1
+    for name in ("HP_ENV_PICK_PLACE", "HP_ENV_PUSH_BLOCK", "HP_ENV_POINT_MASS", "PickPlaceEnvDev"):
+        assert name not in rollout, name
+    assert "env_kind_entry<PickPlaceEnvDev>(HP_ENV_PICK_PLACE)" in open(os.path.join(csrc, "env_pick_place.hip")).read()
+    assert "env_launch_demo<PickPlaceEnvDev>" in open(os.path.join(csrc, "demo_pick_place.hip")).read()
+
+
+def test_the_demo_kernel_of_the_kind_is_one_kernel_without_scratch(tmp_path):
+    """csrc/demo_pick_place.hip compiled as the Makefile compiles it: the second controller is a value of the argument block,
+    so the unit still holds one kernel; no scratch, no spill, the ring and one row of LDS."""
+    csrc = os.path.join(REPO, "rl_arm_under_sparse_reward_amd", "csrc")
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    hipcc = re.search(r"^HIPCC \?= (\S+)", mk, flags=re.M).group(1)
+    if not os.path.exists(hipcc):
+        hipcc = shutil.which("hipcc")
+    assert hipcc, "hipcc is needed to build the library at all"
+    common = re.search(r"^COMMON := (.*)$", mk, flags=re.M).group(1)
+    exact = re.search(r"^EXACT := (.*)$", mk, flags=re.M).group(1)
+    flags = common.replace("$(ARCH)", "gfx950").replace("$(INC)", f"-I{os.path.join(REPO, 'include')} -I{csrc}").split()
+    out = tmp_path / "demo_pick_place.s"
+    subprocess.check_call([hipcc, *flags, *exact.split(), "--cuda-device-only", "-S", os.path.join(csrc, "demo_pick_place.hip"), "-o", str(out)])
+    meta = {}
+    for block in out.read_text().split("- .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block).group(1)
+        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", block).group(1))
+                      for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count")}
+    assert len(meta) == 1, sorted(meta)
+    (name, m), = meta.items()
+    print(name, m)
+    assert "k_demo_episodes" in name and "PickPlaceEnvDev" in name
+    assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, m
+    ring, row = 4 * 624 * 4, (27 + 3 + 3 + 4) * 8
+    assert ring + row <= m["group_segment_fixed_size"] <= ring + row + 128, m
