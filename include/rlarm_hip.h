@@ -501,6 +501,40 @@ int hp_demo_episodes_pick(hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *r
 int hp_demo_compact(hp_ctx *ctx, hp_rollout *src, const float *success_dev, const float *step_success_dev, int64_t n_episodes,
                     hp_rollout *dst, float *dst_step_success_dev, int64_t n_demos, int64_t kept, int32_t *kept_dev);
 
+/* ---- episode metrics on the device ------------------------------------------------------------
+ * The reference records info['is_success'] at every step of every evaluation episode and keeps the last (ddpg_agent.py:280-304);
+ * these entries keep the rest, computed where the episodes lie.  ag_dev is [n_episodes][T + 1][goal_dim] and g_dev
+ * [n_episodes][T][goal_dim], float64 and contiguous: the layout of a block's own arrays (hp_rollout_block).  Step t = 0 .. T-1
+ * compares ag[t + 1] with g[t] (her.py:38, _is_success); d[t] = sqrt(((dx dx + dy dy) + dz dz) ...), every product, sum and the
+ * root rounded on its own, summed left to right over goal_dim -- np.linalg.norm(a - b, axis=-1) for goal_dim < 8; is_success is
+ * hp_is_success_dev's rule and the reward hp_compute_reward_dev's sparse one.  stats_dev [n_episodes][HP_EPISODE_STATS], float64:
+ *   [0] ret                 sum over t of the sparse reward, started at +0.0 (an episode that succeeds throughout: +0.0)
+ *   [1] final_distance      d[T-1]
+ *   [2] min_distance        min over t of d[t]
+ *   [3] first_success_step  the smallest t with is_success, T if there is none
+ *   [4] success_steps       the number of steps with is_success
+ *   [5] final_success       0.0 or 1.0: is_success of step T-1, what success_dev of hp_rollout_episodes / hp_rollout_waves holds
+ * step_success_dev [n_episodes][T] (float32, may be NULL) receives the flag of every step: the reference's per_success_rate, the
+ * step_success_dev of hp_demo_episodes.  One wave per episode; every reduction (a sum of exact small integers, two minima, a
+ * count) is order independent, so the bits are those of the host twin (synthetic.episode_stats) whatever the mapping.  Inputs
+ * must be finite.  hp_episode_stats_block is the same on episodes [first_episode, first_episode + n_episodes) of a block, with T,
+ * goal_dim and the arrays taken from the handle.
+ * hp_episode_stats_summary reduces n_episodes rows of stats to summary_dev [HP_EPISODE_SUMMARY] (float64): the means of ret,
+ * final_distance, min_distance and first_success_step, the success rate (mean of [5]) and the share of episodes with
+ * success_steps > 0 -- each a left-to-right sum in episode order divided by n_episodes (one lane walks the rows: the order is
+ * fixed, synthetic.episode_stats_summary is the same loop), so an evaluation reads 48 bytes once.
+ * All three asynchronous on the context's stream (or a borrowed one); nothing is allocated.  HP_ERR_INVALID, naming the entry
+ * point, for: a null argument (step_success_dev excepted), n_episodes < 1 (or 2^24 and more), T < 1, goal_dim outside
+ * [1, HP_EPISODE_MAX_GOAL_DIM], episodes outside the block. */
+#define HP_EPISODE_STATS 6
+#define HP_EPISODE_SUMMARY 6
+#define HP_EPISODE_MAX_GOAL_DIM 256   /* what a normalizer holds */
+int hp_episode_stats(hp_ctx *ctx, const double *ag_dev, const double *g_dev, int64_t n_episodes, int32_t T, int32_t goal_dim,
+                     double distance_threshold, double *stats_dev, float *step_success_dev);
+int hp_episode_stats_block(hp_rollout *ro, int64_t first_episode, int64_t n_episodes, double distance_threshold, double *stats_dev,
+                           float *step_success_dev);
+int hp_episode_stats_summary(hp_ctx *ctx, const double *stats_dev, int64_t n_episodes, double *summary_dev);
+
 /* Policy calls that do not queue behind training: hp_agent_policy_snapshot copies the online actor and both normalizers'
  * statistics (stream-ordered with the updates, no host wait); hp_agent_act_snapshot evaluates the most recent COMPLETE
  * snapshot on a second stream, so a feeder can step its environments while a training cycle runs (its policy lags the

@@ -70,6 +70,7 @@ class PickScriptDesc(C.Structure):
 ENV_POINT_MASS = 1
 ENV_PUSH_BLOCK = 2      # HP_ENV_PUSH_BLOCK
 ENV_PICK_PLACE = 3      # HP_ENV_PICK_PLACE
+EPISODE_STATS, EPISODE_SUMMARY, EPISODE_MAX_GOAL_DIM = 6, 6, 256   # HP_EPISODE_STATS, HP_EPISODE_SUMMARY, HP_EPISODE_MAX_GOAL_DIM
 ROLLOUT_MAX_LAUNCH_TIMESTEPS = 4096   # HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS: what one launch of hp_rollout_waves holds at most
 
 
@@ -216,6 +217,10 @@ PROTOTYPES = {
                                         C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "hp_demo_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                   C.c_int64, C.c_void_p]),
+    "hp_episode_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_void_p,
+                                   C.c_void_p]),
+    "hp_episode_stats_block": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
+    "hp_episode_stats_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "hp_agent_policy_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hp_agent_act_snapshot": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int64, C.c_double, f32p]),
     "hp_agent_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,

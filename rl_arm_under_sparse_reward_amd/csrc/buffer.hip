@@ -1247,7 +1247,7 @@ static int goal_reward_launch(hp_ctx *ctx, const double *ag, const double *g, in
 
 // smallest double s whose correctly rounded square root is > thr (strict) or >= thr: the predicates d > thr and
 // !(d < thr) in the squared domain (sqrt_rn is monotone), so no device square root and no rounding mismatch
-static double squared_bound(double thr, bool strict) {
+extern "C++" double squared_bound(double thr, bool strict) {   // internal.h: episode_stats.hip takes its thresholds from here too
     if (!(thr >= 0.0)) return 0.0;
     double s = thr * thr;
     auto hit = [&](double v) { const double r = std::sqrt(v); return strict ? r > thr : r >= thr; };

@@ -325,6 +325,23 @@ struct hp_norm {
     bool in_recompute = false;
 };
 
+// ------------------------------------------------------------------ rollout block
+// A block of n episodes in the staging layout (rollout.hip); episode_stats.hip reads its ag and g arrays in place.
+struct hp_rollout {
+    hp_ctx *ctx = nullptr;
+    int64_t n = 0;                 // episodes the block holds
+    int32_t T = 0, od = 0, gd = 0, ad = 0;
+    int64_t first = 0, rows = 0;   // the wave being collected: episodes [first, first + rows)
+    double action_max = 1.0;       // of the policy whose outputs a teacher-forced step is handed (hp_rollout_set_action_max)
+    int64_t launch_cap = HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS;   // timesteps (waves x T) one launch of hp_rollout_waves may hold
+    double *block = nullptr;
+    int64_t o_ag = 0, o_g = 0, o_act = 0, elems = 0;   // offsets in float64 elements (feeder._Layout)
+};
+
+// smallest double s whose correctly rounded square root is > thr (strict) or >= thr (buffer.hip): the predicates d > thr and
+// !(d < thr) of compute_reward / _is_success in the squared domain
+double squared_bound(double thr, bool strict);
+
 // Reward of a relabelled transition from the squared goal distance s (compute_reward, bmirobot_env_push_F.py:84-90):
 //   sq_threshold >= 0: sparse, -(d > thr) == -(s >= sq_threshold) with sq_threshold the smallest double whose correctly
 //                      rounded square root exceeds thr -- no square root on the device;

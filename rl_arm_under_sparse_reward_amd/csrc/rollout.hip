@@ -34,17 +34,6 @@
 #include "rollout_episodes.h"   // ExploreArgs, ro_explore_row, PolicyArgs (slab8.h), EpisodesArgs and EnvKind
 #include "demo_episodes.h"      // DemoArgs (the kernel is instantiated by the kinds' demo units, through EnvKind::launch_demo), CompactArgs
 
-struct hp_rollout {
-    hp_ctx *ctx = nullptr;
-    int64_t n = 0;                 // episodes the block holds
-    int32_t T = 0, od = 0, gd = 0, ad = 0;
-    int64_t first = 0, rows = 0;   // the wave being collected: episodes [first, first + rows)
-    double action_max = 1.0;       // of the policy whose outputs a teacher-forced step is handed (hp_rollout_set_action_max)
-    int64_t launch_cap = HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS;   // timesteps (waves x T) one launch of hp_rollout_waves may hold
-    double *block = nullptr;
-    int64_t o_ag = 0, o_g = 0, o_act = 0, elems = 0;   // offsets in float64 elements (feeder._Layout)
-};
-
 struct RolloutStepArgs {
     const double *obs, *ag, *g;    // this timestep's rows [rows][dim] (g == nullptr: the closing record of row T)
     double *b_obs, *b_ag, *b_g, *b_act;   // block arrays, already offset to episode `first`

@@ -142,6 +142,7 @@ class ddpg_agent:
         self._defer_updates = os.environ.get("RLARM_DEFER_UPDATES", "1") != "0"
         self._stage_lock = threading.RLock()   # orders "store a wave, then sample ITS staged episodes" across feeder threads
         self.success_rates = []
+        self.eval_metrics = []           # args.eval_metrics: one dict per evaluation, keyed by synthetic.EPISODE_SUMMARY
         self.model_path = os.path.join(self.args.save_dir, self.args.env_name)
 
     def close_comm(self):
@@ -499,6 +500,10 @@ class ddpg_agent:
         os.makedirs(saved_dir, exist_ok=True)
         np.save(saved_dir + str(self.args.seed) + '_' + str(self.args.add_demo) + '_success_rates.npy',
                 np.array(self.success_rates))
+        if getattr(self.args, "eval_metrics", False):      # [evaluations, 6] in the columns of synthetic.EPISODE_SUMMARY
+            from .synthetic import EPISODE_SUMMARY
+            np.save(saved_dir + str(self.args.seed) + '_' + str(self.args.add_demo) + '_eval_metrics.npy',
+                    np.array([[m[k] for k in EPISODE_SUMMARY] for m in self.eval_metrics], dtype=np.float64).reshape(-1, len(EPISODE_SUMMARY)))
         try:
             import matplotlib.pyplot as plt
         except Exception:
@@ -678,7 +683,7 @@ class ddpg_agent:
         self.explore_streams = _random.DeviceRandomStreams(n, seeds=seeds, base_seed=base_seed, ctx=self.ctx)
         return self.explore_streams
 
-    def collect_episodes_device(self, vec_env=None, n_rollouts=None, epoch=0, explore=True, success_out=None):
+    def collect_episodes_device(self, vec_env=None, n_rollouts=None, epoch=0, explore=True, success_out=None, stats_out=None):
         """`collect_episodes` for a vectorised device environment (device_env.py): `n_rollouts` episodes (default: one wave of
         vec_env.n_envs) on torch's current stream, no host copy and no host wait per timestep, in one of three forms with the
         same bits; `self.rollout_form` / `self.rollout_reason` say which the call took and why, `self.rollout_launches` how many
@@ -692,7 +697,10 @@ class ddpg_agent:
         Exploration (:174-184, the +-0.15 clip from epoch 100) is drawn on the device from `self.rng`, for env 0 .. n-1 in turn
         like the host lockstep path -- or, after `enable_explore_streams`, for every environment from its own stream (a wave of
         k < n_envs rows advances the streams of those k only).  Returns a `DeviceEpisodes` handle for `train_cycle` /
-        `buffer.store_episode`; `.numpy()` gives the four arrays `collect_episodes` returns."""
+        `buffer.store_episode`; `.numpy()` gives the four arrays `collect_episodes` returns.
+        `stats_out`: a list that receives ONE device tensor [n_rollouts, 6] per call, the metrics of this call's episodes
+        (`DeviceEpisodes.stats` at `vec_env.distance_threshold`: one more small launch behind the rollout, in any of the three
+        forms, no host wait); with None nothing more is launched."""
         from .device_env import DeviceEpisodes, binomial1_qn, fused_rollout_reason
         vec_env = vec_env or self.vec_env
         n_total = int(n_rollouts or vec_env.n_envs)
@@ -715,6 +723,8 @@ class ddpg_agent:
             success = self._collect_all_waves(vec_env, eps, n_total, streams, how)
             if success_out is not None:
                 success_out.append(success)
+            if stats_out is not None:
+                stats_out.append(eps.stats(vec_env.distance_threshold, 0, n_total))
             return eps
         done = 0
         while done < n_total:
@@ -729,7 +739,27 @@ class ddpg_agent:
             done += k
         if explore and streams is None:     # (the streams keep no host copy of their cached normals: nothing to invalidate)
             self.rng.mark_normals_drawn()
+        if stats_out is not None:
+            stats_out.append(eps.stats(vec_env.distance_threshold, 0, n_total))
         return eps
+
+    def episode_stats_host(self, episode_batch, distance_threshold):
+        """The metrics of host episodes -- the four arrays `collect_episodes` returns, or a feeder slot's (obs, ag, g, actions) --
+        from the kernel the device path uses (hp_episode_stats): `ag` and `g` are uploaded, the result comes back as numpy
+        (stats [n, 6] float64 in the columns of `synthetic.EPISODE_STATS`, step_success [n, T] float32).  Synchronises."""
+        ag = torch.from_numpy(np.ascontiguousarray(episode_batch[1], dtype=np.float64))
+        g = torch.from_numpy(np.ascontiguousarray(episode_batch[2], dtype=np.float64))
+        if ag.ndim != 3 or g.ndim != 3 or ag.shape[0] != g.shape[0] or ag.shape[1] != g.shape[1] + 1 or ag.shape[2] != g.shape[2]:
+            raise ValueError("episode_stats_host: ag [n, T+1, goal] and g [n, T, goal] expected")
+        dev = torch.device("cuda", self.ctx.device_id)
+        ag, g = ag.to(dev), g.to(dev)
+        n, T, gd = g.shape
+        stats = torch.empty((n, _lib.EPISODE_STATS), dtype=torch.float64, device=dev)
+        flags = torch.empty((n, T), dtype=torch.float32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_episode_stats(self.ctx.h, p(ag), p(g), n, T, gd, float(distance_threshold), p(stats), p(flags)))
+        return stats.cpu().numpy(), flags.cpu().numpy()
 
     def _collect_all_waves(self, vec_env, eps, n_total, streams, how):
         """All `n_total` episodes as one launch (hp_rollout_waves), or the few the launch cap dictates; the environments are
@@ -903,13 +933,35 @@ class ddpg_agent:
         """_eval_agent on the device path: noise-free lockstep rollouts, the success flags of each wave's last step gathered on
         the device and copied to the host once at the end."""
         flags, remaining = [], int(self.args.n_test_rollouts)
+        stats = [] if getattr(self.args, "eval_metrics", False) else None
         while remaining > 0:
             # one call per wave; with reset on the device one call for all of them (one launch: hp_rollout_waves)
             k = remaining if getattr(self.vec_env, "reset_streams", None) is not None else min(self.vec_env.n_envs, remaining)
-            self.collect_episodes_device(n_rollouts=k, explore=False, success_out=flags)
+            self.collect_episodes_device(n_rollouts=k, explore=False, success_out=flags, stats_out=stats)
             remaining -= k
-        wins = torch.cat([f.reshape(-1).to(torch.float64) for f in flags]).cpu().numpy()
-        return self._success_rate(wins)
+        wins = torch.cat([f.reshape(-1).to(torch.float64) for f in flags])
+        if stats is None:
+            return self._success_rate(wins.cpu().numpy())
+        # args.eval_metrics: the summary of all evaluation episodes (hp_episode_stats_summary) rides behind the flags in the one
+        # copy to the host; what is done with the flags is unchanged
+        rows = stats[0] if len(stats) == 1 else torch.cat(stats)
+        summary = torch.empty(_lib.EPISODE_SUMMARY, dtype=torch.float64, device=rows.device)
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_episode_stats_summary(self.ctx.h, C.c_void_p(rows.data_ptr()), rows.shape[0],
+                                                         C.c_void_p(summary.data_ptr())))
+        both = torch.cat([wins, summary]).cpu().numpy()
+        rate = self._success_rate(both[:-_lib.EPISODE_SUMMARY])
+        self._record_eval_metrics(both[-_lib.EPISODE_SUMMARY:])
+        return rate
+
+    def _record_eval_metrics(self, summary):
+        """One evaluation's summary (this rank's six means), averaged over the ranks like the success rate, onto `eval_metrics`"""
+        from .synthetic import EPISODE_SUMMARY
+        local = torch.tensor(np.asarray(summary, dtype=np.float64), dtype=torch.float64)
+        if self.comm.world_size > 1:
+            local = local.to(f"cuda:{self.ctx.device_id}")
+        self.comm.allreduce_mean_(local)
+        self.eval_metrics.append(dict(zip(EPISODE_SUMMARY, (float(v) for v in local.cpu().numpy()))))
 
     def _success_rate(self, wins):
         """The mean of this rank's success flags, averaged over the ranks"""
@@ -925,6 +977,8 @@ class ddpg_agent:
         if self.vec_env is not None:
             return self._eval_agent_device()
         wins = []
+        metrics = bool(getattr(self.args, "eval_metrics", False))
+        ep_ag, ep_g = [], []             # args.eval_metrics: achieved goals [T + 1] and desired goals [T] of every episode
         remaining = int(self.args.n_test_rollouts)
         while remaining > 0:
             envs = self.envs[:remaining]
@@ -932,15 +986,29 @@ class ddpg_agent:
             obs = [o['observation'] for o in first]
             g = [o['desired_goal'] for o in first]
             last = [0.0] * len(envs)
+            if metrics:
+                ags = [[np.array(o['achieved_goal'], dtype=np.float64)] for o in first]
+                gs = [[] for _ in envs]
             for _t in range(int(self.env_params['max_timesteps'])):
                 actions = self.act(np.stack(obs), np.stack(g))
                 for i, env in enumerate(envs):
                     observation_new, _, _, info = env.step(actions[i])
+                    if metrics:
+                        gs[i].append(np.array(g[i], dtype=np.float64))
+                        ags[i].append(np.array(observation_new['achieved_goal'], dtype=np.float64))
                     obs[i], g[i] = observation_new['observation'], observation_new['desired_goal']
                     last[i] = float(info.get('is_success', last[i]))
             wins.extend(last)
+            if metrics:
+                ep_ag.extend(ags)
+                ep_g.extend(gs)
             remaining -= len(envs)
-        return self._success_rate(wins)
+        rate = self._success_rate(wins)
+        if metrics:
+            from .synthetic import episode_stats, episode_stats_summary
+            thr = getattr(self.env, "distance_threshold", getattr(self.args, "distance_threshold", 0.05))
+            self._record_eval_metrics(episode_stats_summary(episode_stats(np.array(ep_ag), np.array(ep_g), thr)[0]))
+        return rate
 
     def __del__(self):
         try:

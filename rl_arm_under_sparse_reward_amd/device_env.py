@@ -127,6 +127,21 @@ class DeviceEpisodes:
             _lib.check(self.lib.hp_rollout_read(self.h, which, _lib.ptr(a, C.c_double)))
         return out
 
+    def stats(self, distance_threshold, first=0, n=None, step_success=False):
+        """The metrics of episodes [first, first + n) (default: all of them behind `first`), computed where they lie
+        (hp_episode_stats_block): a float64 device tensor [n, 6] in the columns of `synthetic.EPISODE_STATS` -- and, with
+        `step_success=True`, the float32 flags [n, T] of every step beside it.  One launch on torch's current stream; no copy and
+        no synchronisation.  `synthetic.episode_stats` on `.numpy()` gives the same bits."""
+        first = int(first)
+        n = self.n - first if n is None else int(n)
+        dev = torch.device("cuda", self.ctx.device_id)
+        stats = torch.empty((max(n, 0), _lib.EPISODE_STATS), dtype=torch.float64, device=dev)
+        flags = torch.empty((max(n, 0), self.T), dtype=torch.float32, device=dev) if step_success else None
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_episode_stats_block(self.h, first, n, float(distance_threshold), C.c_void_p(stats.data_ptr()),
+                                                       C.c_void_p(flags.data_ptr()) if step_success else None))
+        return (stats, flags) if step_success else stats
+
     def __del__(self):
         try:
             self.lib.hp_rollout_destroy(self.h)
@@ -562,6 +577,15 @@ class DeviceDemos:
         if self.episodes is None:
             return [np.empty((0,) + s, dtype=np.float32 if j == 4 else np.float64) for j, s in enumerate(self._shapes)]
         return [*self.episodes.numpy(), self.info.cpu().numpy()]
+
+    def stats(self, distance_threshold, step_success=False):
+        """`DeviceEpisodes.stats` of the kept episodes ([0, 6] and [0, T] when none was kept): how close the scripted
+        controller came, when it first succeeded -- its `step_success` is `.info` computed again from the block."""
+        if self.episodes is None:
+            dev = self.info.device
+            stats = torch.empty((0, _lib.EPISODE_STATS), dtype=torch.float64, device=dev)
+            return (stats, torch.empty((0,) + self._shapes[4], dtype=torch.float32, device=dev)) if step_success else stats
+        return self.episodes.stats(distance_threshold, 0, self.kept, step_success=step_success)
 
     def save(self, path):
         """A demo file in the schema of get_demo_data_push.py:91-94 (`synthetic.write_demo_npz_from`): it preloads through

@@ -451,6 +451,56 @@ def scripted_demos(envs, n_demos, round_waves, max_episodes=10000, script=None):
     return (*out, attempted)
 
 
+EPISODE_STATS = ("ret", "final_distance", "min_distance", "first_success_step", "success_steps", "final_success")
+EPISODE_SUMMARY = ("ret", "final_distance", "min_distance", "first_success_step", "success_rate", "any_success_rate")
+
+
+def episode_stats(ag, g, distance_threshold):
+    """The host twin of hp_episode_stats, in plain numpy: `ag` [n, T+1, goal] and `g` [n, T, goal] -> (stats [n, 6] float64 in the
+    columns of EPISODE_STATS, step_success [n, T] float32).  Step t compares ag[t + 1] with g[t] (her.py:38); the distance is the
+    root of the squares summed left to right over the goal components, which is `np.linalg.norm(a - b, axis=-1)` for fewer than
+    8 of them; success is d < threshold (_is_success) and the reward -(d > threshold) in float32 (compute_reward, sparse).  `ret`
+    is numpy's own sum of those rewards: +0.0 for an episode that succeeds at every step.  first_success_step is T where there
+    is no success."""
+    ag, g = np.asarray(ag, dtype=np.float64), np.asarray(g, dtype=np.float64)
+    if ag.ndim != 3 or g.ndim != 3 or ag.shape[0] != g.shape[0] or ag.shape[1] != g.shape[1] + 1 or ag.shape[2] != g.shape[2]:
+        raise ValueError("episode_stats: ag [n, T+1, goal] and g [n, T, goal] expected")
+    n, T, thr = g.shape[0], g.shape[1], float(distance_threshold)
+    diff = ag[:, 1:] - g
+    sq = diff * diff
+    s = sq[..., 0]
+    for c in range(1, sq.shape[-1]):
+        s = s + sq[..., c]
+    d = np.sqrt(s)
+    ok = d < thr
+    reward = -(d > thr).astype(np.float32)
+    stats = np.empty((n, len(EPISODE_STATS)), dtype=np.float64)
+    stats[:, 0] = reward.astype(np.float64).sum(axis=1)
+    stats[:, 1] = d[:, -1]
+    stats[:, 2] = d.min(axis=1)
+    stats[:, 3] = np.where(ok.any(axis=1), ok.argmax(axis=1), T)
+    stats[:, 4] = ok.sum(axis=1)
+    stats[:, 5] = ok[:, -1]
+    return stats, ok.astype(np.float32)
+
+
+def episode_stats_summary(stats):
+    """The host twin of hp_episode_stats_summary: the columns of EPISODE_SUMMARY, each a left-to-right float64 sum over the rows
+    of `stats` in order, divided by their number -- the device's loop, not numpy's pairwise mean."""
+    stats = np.asarray(stats, dtype=np.float64)
+    if stats.ndim != 2 or stats.shape[1] != len(EPISODE_STATS) or stats.shape[0] < 1:
+        raise ValueError("episode_stats_summary: stats [n >= 1, 6] expected")
+    total = np.zeros(len(EPISODE_SUMMARY), dtype=np.float64)
+    for row in stats:
+        total[0] += row[0]
+        total[1] += row[1]
+        total[2] += row[2]
+        total[3] += row[3]
+        total[4] += row[5]
+        total[5] += 1.0 if row[4] > 0.0 else 0.0
+    return total / np.float64(stats.shape[0])
+
+
 def write_demo_npz_from(path, obs, ag, g, actions, info):
     """Write episodes in the schema get_demo_data_push.py:91-94 produces: keys acs, obs, info, g, ag, with `info` an object
     array [n, T] of per-step dicts {'is_success': float32} (`info` here: the flags [n, T]).  Such a file preloads through
