@@ -50,9 +50,7 @@ __device__ __forceinline__ void demo_action(const hp_demo_script &S, int step, c
         act[3] = 0.0;
     }
     // :59-61 the stop rule, on top of every phase
-    const double dx = __dsub_rn(b[0], g[0]), dy = __dsub_rn(b[1], g[1]), dz = __dsub_rn(b[2], g[2]);
-    const double s = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-    if (__dsqrt_rn(s) < S.stop_radius) {
+    if (env_within(b, g, S.stop_radius)) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) act[c] = 0.0;
     }

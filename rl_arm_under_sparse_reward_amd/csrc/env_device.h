@@ -35,16 +35,99 @@
 // which instantiates both kernels for the kind and checks at compile time what a kind must be for them -- and a unit
 // demo_<kind>.hip of two, the explicit instantiation of env_launch_demo<Struct> (demo_episodes.h: the scripted-episode kernel, the
 // row's third launch), both with their entries in the
-// Makefile's EXACT_SRCS; the row's declaration in rollout_episodes.h and its address in the table of env_kind() (rollout.hip); and
+// Makefile's EXACT_SRCS; the row's declaration in rollout_episodes.h and its address in the table of env_kind_lookup() (rollout.hip); and
 // one Python class pair in device_env.py (the tensor twin, and a native class that names the constant -- and, where the task's
 // scripted controller is not the push schedule, its default_demo_script()).  No entry point, dispatch or check names a kind: they
 // read the row (env_point_mass.hip, env_push_block.hip and env_pick_place.hip are the models).  A scripted controller is NOT part
 // of a kind: the two of demo_episodes.h run on any kind with the bmirobot layout, chosen per call (DemoArgs::controller).
+// A gripper-and-block kind (a fourth task of the bmirobot family) derives its struct from GripBlockEnvDev<STRIDE> below and
+// writes only what is its own: the constants, its parameters and their lines of load, reset_bounds, the separation test of reset
+// in front of place(), the dynamics of step_with behind env_clipped_move, is_success as env_within(blk, goal, threshold), and
+// whatever it keeps in array 3 behind the six velocities (load / store / observe call the base's and add those columns).
 #pragma once
 #include "internal.h"
 #include <type_traits>
 
 #include "mt19937_wave.h"
+
+// ---- what the kinds share ------------------------------------------------------------------------------------------------------
+// |achieved - goal| < threshold over three components: seven explicit IEEE operations -- three differences, three products, two
+// sums left to right, one root (numpy's norm) -- and the comparison.  Every kind's is_success, and the stop rule of demo_action.
+__device__ __forceinline__ bool env_within(const double *achieved, const double *goal, double threshold) {
+    const double dx = __dsub_rn(achieved[0], goal[0]), dy = __dsub_rn(achieved[1], goal[1]), dz = __dsub_rn(achieved[2], goal[2]);
+    const double s = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+    return __dsqrt_rn(s) < threshold;
+}
+
+// The clipped move of every kind: a = clamp(float64(action), -0.5, 0.5); scaled = step_scale * a; moved = clamp(p + scaled, lo, hi);
+// v = moved - p; p = moved, per component.  A: float (the policy's action) or double (a scripted controller's).
+template <class A>
+__device__ __forceinline__ void env_clipped_move(double *__restrict__ p, double *__restrict__ v, const A *__restrict__ action, double step_scale,
+                                                 const double *__restrict__ lo, const double *__restrict__ hi) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double a = fmin(fmax((double)action[c], -0.5), 0.5);
+        const double scaled = __dmul_rn(step_scale, a);
+        const double moved = fmin(fmax(__dadd_rn(p[c], scaled), lo[c]), hi[c]);
+        v[c] = __dsub_rn(moved, p[c]);
+        p[c] = moved;
+    }
+}
+
+// The core of a gripper-and-block kind: gripper, block, goal and the two velocities; state_dev [0] grip [n][3], [1] blk [n][3],
+// [2] goal [n][3], [3] [n][STRIDE] whose first six columns are the gripper's velocity, then the block's (a kind keeps what else it
+// has behind them).  The observation's common columns: [0:3] = grip, [6:9] = gvel, [12:15] = blk, [18:21] = blk - grip,
+// [21:24] = bvel, zero elsewhere;  ag = blk;  g = goal.  No constructor and no initialiser: the kernels keep the structs in LDS.
+template <int STRIDE>
+struct GripBlockEnvDev {
+    static_assert(STRIDE >= 6, "array 3 starts with the two velocities");
+    double grip[3], blk[3], goal[3], gvel[3], bvel[3];
+
+    // the placement half of a rejection reset: block on the table, goal, gripper at its start, velocities zero
+    __device__ __forceinline__ void place(double bx, double by, double table_z, double gx, double gy, double gz, double start_x,
+                                          double start_y, double start_z) {
+        blk[0] = bx; blk[1] = by; blk[2] = table_z;
+        goal[0] = gx; goal[1] = gy; goal[2] = gz;
+        grip[0] = start_x; grip[1] = start_y; grip[2] = start_z;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gvel[c] = bvel[c] = 0.0;
+    }
+    __device__ __forceinline__ void load(const hp_env_desc &d, long long i) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            grip[c] = d.state_dev[0][3 * i + c];
+            blk[c] = d.state_dev[1][3 * i + c];
+            goal[c] = d.state_dev[2][3 * i + c];
+            gvel[c] = d.state_dev[3][STRIDE * i + c];
+            bvel[c] = d.state_dev[3][STRIDE * i + 3 + c];
+        }
+    }
+    __device__ __forceinline__ void store(const hp_env_desc &d, long long i) const {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            d.state_dev[0][3 * i + c] = grip[c];
+            d.state_dev[1][3 * i + c] = blk[c];
+            d.state_dev[2][3 * i + c] = goal[c];
+            d.state_dev[3][STRIDE * i + c] = gvel[c];
+            d.state_dev[3][STRIDE * i + 3 + c] = bvel[c];
+        }
+    }
+    template <int OBS>
+    __device__ __forceinline__ void observe(double *obs, double *ag, double *g) const {
+#pragma unroll
+        for (int c = 0; c < OBS; ++c) obs[c] = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            obs[c] = grip[c];
+            obs[6 + c] = gvel[c];
+            obs[12 + c] = blk[c];
+            obs[18 + c] = __dsub_rn(blk[c], grip[c]);
+            obs[21 + c] = bvel[c];
+            ag[c] = blk[c];
+            g[c] = goal[c];
+        }
+    }
+};
 
 // device_env.PointMassVecEnv (the tensor twin of synthetic.PointMassGoalEnv), operation for operation:
 //     a = clamp(float64(action), -0.5, 0.5);  scaled = step_scale * a[0:3];  new = clamp(pos + scaled, 0, 0.5);  vel = new - pos
@@ -94,22 +177,12 @@ struct PointMassEnvDev {
     }
     template <class A>
     __device__ __forceinline__ void step_with(const A *action) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double a = fmin(fmax((double)action[c], -0.5), 0.5);
-            const double scaled = __dmul_rn(step_scale, a);
-            const double moved = fmin(fmax(__dadd_rn(pos[c], scaled), 0.0), 0.5);
-            vel[c] = __dsub_rn(moved, pos[c]);
-            pos[c] = moved;
-        }
+        const double lo[3] = {0.0, 0.0, 0.0}, hi[3] = {0.5, 0.5, 0.5};
+        env_clipped_move(pos, vel, action, step_scale, lo, hi);
     }
     __device__ __forceinline__ void step(const float *action) { step_with(action); }
     __device__ __forceinline__ void step(const double *action) { step_with(action); }
-    __device__ __forceinline__ bool is_success() const {
-        const double dx = __dsub_rn(pos[0], goal[0]), dy = __dsub_rn(pos[1], goal[1]), dz = __dsub_rn(pos[2], goal[2]);
-        const double s = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-        return __dsqrt_rn(s) < threshold;
-    }
+    __device__ __forceinline__ bool is_success() const { return env_within(pos, goal, threshold); }
     __device__ __forceinline__ void store(const hp_env_desc &d, long long i) const {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -133,11 +206,10 @@ struct PointMassEnvDev {
 // No division and no square root inside step: adds, subtracts, multiplies, compares and clamps only.
 // params: [0] step_scale, [1] distance_threshold, [2] half_width r, [3] z_touch, [4] min_separation, [5] table_z, [6], [7] gripper
 // start x, y;  state_dev: [0] grip [n][3], [1] blk [n][3], [2] goal [n][3], [3] velocities [n][6] (gripper, then block)
-struct PushBlockEnvDev {
+struct PushBlockEnvDev : GripBlockEnvDev<6> {
     static constexpr int OBS = 27, GOAL = 3, ACT = 4, RESET_DRAWS = 4, RESET_ATTEMPTS = 100, STATE_ARRAYS = 4;
     // the workspace: x, y of gripper and block; the gripper's z runs from the table to Z_HI and starts at START_Z
     static constexpr double X_LO = 0.0, X_HI = 0.5, Y_LO = 0.0, Y_HI = 0.7, Z_HI = 0.5, START_Z = 0.3;
-    double grip[3], blk[3], goal[3], gvel[3], bvel[3];
     double step_scale, threshold, r, z_touch, min_sep, table_z, start_x, start_y;
 
     static __device__ __forceinline__ void reset_bounds(int k, double &low, double &range) {
@@ -149,51 +221,20 @@ struct PushBlockEnvDev {
     __device__ __forceinline__ bool reset(const double *u) {
         const double ddx = __dsub_rn(u[0], u[2]), ddy = __dsub_rn(u[1], u[3]);
         const double d = __dsqrt_rn(__dadd_rn(__dmul_rn(ddx, ddx), __dmul_rn(ddy, ddy)));
-        blk[0] = u[0]; blk[1] = u[1]; blk[2] = table_z;
-        goal[0] = u[2]; goal[1] = u[3]; goal[2] = table_z;
-        grip[0] = start_x; grip[1] = start_y; grip[2] = START_Z;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) gvel[c] = bvel[c] = 0.0;
+        place(u[0], u[1], table_z, u[2], u[3], table_z, start_x, start_y, START_Z);
         return d >= min_sep;
     }
 
     __device__ __forceinline__ void load(const hp_env_desc &d, long long i) {
         step_scale = d.params[0]; threshold = d.params[1]; r = d.params[2]; z_touch = d.params[3];
         min_sep = d.params[4]; table_z = d.params[5]; start_x = d.params[6]; start_y = d.params[7];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            grip[c] = d.state_dev[0][3 * i + c];
-            blk[c] = d.state_dev[1][3 * i + c];
-            goal[c] = d.state_dev[2][3 * i + c];
-            gvel[c] = d.state_dev[3][6 * i + c];
-            bvel[c] = d.state_dev[3][6 * i + 3 + c];
-        }
+        GripBlockEnvDev::load(d, i);
     }
-    __device__ __forceinline__ void observe(double *obs, double *ag, double *g) const {
-#pragma unroll
-        for (int c = 0; c < OBS; ++c) obs[c] = 0.0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            obs[c] = grip[c];
-            obs[6 + c] = gvel[c];
-            obs[12 + c] = blk[c];
-            obs[18 + c] = __dsub_rn(blk[c], grip[c]);
-            obs[21 + c] = bvel[c];
-            ag[c] = blk[c];
-            g[c] = goal[c];
-        }
-    }
+    __device__ __forceinline__ void observe(double *obs, double *ag, double *g) const { GripBlockEnvDev::observe<OBS>(obs, ag, g); }
     template <class A>
     __device__ __forceinline__ void step_with(const A *action) {
         const double lo[3] = {X_LO, Y_LO, table_z}, hi[3] = {X_HI, Y_HI, Z_HI};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double a = fmin(fmax((double)action[c], -0.5), 0.5);
-            const double scaled = __dmul_rn(step_scale, a);
-            const double moved = fmin(fmax(__dadd_rn(grip[c], scaled), lo[c]), hi[c]);
-            gvel[c] = __dsub_rn(moved, grip[c]);
-            grip[c] = moved;
-        }
+        env_clipped_move(grip, gvel, action, step_scale, lo, hi);
         const double dx = __dsub_rn(blk[0], grip[0]), dy = __dsub_rn(blk[1], grip[1]);
         const double adx = fabs(dx), ady = fabs(dy);
         const double ox = blk[0], oy = blk[1];
@@ -210,21 +251,7 @@ struct PushBlockEnvDev {
     }
     __device__ __forceinline__ void step(const float *action) { step_with(action); }
     __device__ __forceinline__ void step(const double *action) { step_with(action); }
-    __device__ __forceinline__ bool is_success() const {
-        const double dx = __dsub_rn(blk[0], goal[0]), dy = __dsub_rn(blk[1], goal[1]), dz = __dsub_rn(blk[2], goal[2]);
-        const double s = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-        return __dsqrt_rn(s) < threshold;
-    }
-    __device__ __forceinline__ void store(const hp_env_desc &d, long long i) const {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            d.state_dev[0][3 * i + c] = grip[c];
-            d.state_dev[1][3 * i + c] = blk[c];
-            d.state_dev[2][3 * i + c] = goal[c];
-            d.state_dev[3][6 * i + c] = gvel[c];
-            d.state_dev[3][6 * i + 3 + c] = bvel[c];
-        }
-    }
+    __device__ __forceinline__ bool is_success() const { return env_within(blk, goal, threshold); }
 };
 
 // device_env.PickPlaceVecEnv (the tensor twin of synthetic.PickPlaceGoalEnv), operation for operation: a kinematic pick-and-place.
@@ -246,13 +273,13 @@ struct PushBlockEnvDev {
 // params: [0] step_scale, [1] distance_threshold, [2] half_width r, [3] finger_scale, [4] min_separation, [5] table_z, [6], [7]
 // gripper start x, y;  state_dev: [0] grip [n][3], [1] blk [n][3], [2] goal [n][3], [3] [n][8] = gripper velocity, block velocity,
 // finger opening, held (0.0 or 1.0)
-struct PickPlaceEnvDev {
+struct PickPlaceEnvDev : GripBlockEnvDev<8> {
     static constexpr int OBS = 27, GOAL = 3, ACT = 4, RESET_DRAWS = 5, RESET_ATTEMPTS = 100, STATE_ARRAYS = 4;
     // the workspace of gripper and block alike (z from the table to Z_HI); the gripper starts at START_Z
     static constexpr double X_LO = 0.0, X_HI = 0.5, Y_LO = 0.0, Y_HI = 0.7, Z_HI = 0.6, START_Z = 0.3;
     // the finger pads relative to the gripper; the widest opening; the opening at and below which the fingers hold the cube
     static constexpr double TOOL_X = 0.0, TOOL_Y = 0.05, TOOL_Z = -0.05, FINGER_MAX = 0.08, GRASP_WIDTH = 0.04;
-    double grip[3], blk[3], goal[3], gvel[3], bvel[3], finger, held;
+    double finger, held;
     double step_scale, threshold, r, finger_scale, min_sep, table_z, start_x, start_y;
 
     static __device__ __forceinline__ void reset_bounds(int k, double &low, double &range) {
@@ -263,11 +290,7 @@ struct PickPlaceEnvDev {
     __device__ __forceinline__ bool reset(const double *u) {
         const double ddx = __dsub_rn(u[0], u[2]), ddy = __dsub_rn(u[1], u[3]), ddz = __dsub_rn(table_z, u[4]);
         const double d = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(ddx, ddx), __dmul_rn(ddy, ddy)), __dmul_rn(ddz, ddz)));
-        blk[0] = u[0]; blk[1] = u[1]; blk[2] = table_z;
-        goal[0] = u[2]; goal[1] = u[3]; goal[2] = u[4];
-        grip[0] = start_x; grip[1] = start_y; grip[2] = START_Z;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) gvel[c] = bvel[c] = 0.0;
+        place(u[0], u[1], table_z, u[2], u[3], u[4], start_x, start_y, START_Z);
         finger = held = 0.0;
         return d >= min_sep;
     }
@@ -275,30 +298,12 @@ struct PickPlaceEnvDev {
     __device__ __forceinline__ void load(const hp_env_desc &d, long long i) {
         step_scale = d.params[0]; threshold = d.params[1]; r = d.params[2]; finger_scale = d.params[3];
         min_sep = d.params[4]; table_z = d.params[5]; start_x = d.params[6]; start_y = d.params[7];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            grip[c] = d.state_dev[0][3 * i + c];
-            blk[c] = d.state_dev[1][3 * i + c];
-            goal[c] = d.state_dev[2][3 * i + c];
-            gvel[c] = d.state_dev[3][8 * i + c];
-            bvel[c] = d.state_dev[3][8 * i + 3 + c];
-        }
+        GripBlockEnvDev::load(d, i);
         finger = d.state_dev[3][8 * i + 6];
         held = d.state_dev[3][8 * i + 7];
     }
     __device__ __forceinline__ void observe(double *obs, double *ag, double *g) const {
-#pragma unroll
-        for (int c = 0; c < OBS; ++c) obs[c] = 0.0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            obs[c] = grip[c];
-            obs[6 + c] = gvel[c];
-            obs[12 + c] = blk[c];
-            obs[18 + c] = __dsub_rn(blk[c], grip[c]);
-            obs[21 + c] = bvel[c];
-            ag[c] = blk[c];
-            g[c] = goal[c];
-        }
+        GripBlockEnvDev::observe<OBS>(obs, ag, g);
         obs[9] = finger;
         obs[10] = held;
     }
@@ -314,14 +319,7 @@ struct PickPlaceEnvDev {
         if (held != 0.0 || pads_inside()) a3 = -1.0;         // the finger lock, on the state before the move
         const double f_old = finger;
         finger = fmin(fmax(__dadd_rn(finger, __dmul_rn(finger_scale, a3)), 0.0), FINGER_MAX);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double a = fmin(fmax((double)action[c], -0.5), 0.5);
-            const double scaled = __dmul_rn(step_scale, a);
-            const double moved = fmin(fmax(__dadd_rn(grip[c], scaled), lo[c]), hi[c]);
-            gvel[c] = __dsub_rn(moved, grip[c]);
-            grip[c] = moved;
-        }
+        env_clipped_move(grip, gvel, action, step_scale, lo, hi);
         if (held != 0.0) {                                   // carried: the gripper's clipped displacement, clipped again
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
@@ -337,24 +335,18 @@ struct PickPlaceEnvDev {
     }
     __device__ __forceinline__ void step(const float *action) { step_with(action); }
     __device__ __forceinline__ void step(const double *action) { step_with(action); }
-    __device__ __forceinline__ bool is_success() const {
-        const double dx = __dsub_rn(blk[0], goal[0]), dy = __dsub_rn(blk[1], goal[1]), dz = __dsub_rn(blk[2], goal[2]);
-        const double s = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-        return __dsqrt_rn(s) < threshold;
-    }
+    __device__ __forceinline__ bool is_success() const { return env_within(blk, goal, threshold); }
     __device__ __forceinline__ void store(const hp_env_desc &d, long long i) const {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            d.state_dev[0][3 * i + c] = grip[c];
-            d.state_dev[1][3 * i + c] = blk[c];
-            d.state_dev[2][3 * i + c] = goal[c];
-            d.state_dev[3][8 * i + c] = gvel[c];
-            d.state_dev[3][8 * i + 3 + c] = bvel[c];
-        }
+        GripBlockEnvDev::store(d, i);
         d.state_dev[3][8 * i + 6] = finger;
         d.state_dev[3][8 * i + 7] = held;
     }
 };
+
+// The kernels keep the structs in LDS (EpisodesLds<Env>::env[4]): no constructor runs there, and a base must not change a size
+static_assert(std::is_trivially_default_constructible<PointMassEnvDev>::value && sizeof(PointMassEnvDev) == 88, "11 doubles");
+static_assert(std::is_trivially_default_constructible<PushBlockEnvDev>::value && sizeof(PushBlockEnvDev) == 184, "15 + 8 doubles");
+static_assert(std::is_trivially_default_constructible<PickPlaceEnvDev>::value && sizeof(PickPlaceEnvDev) == 200, "15 + 2 + 8 doubles");
 
 // RESET_ATTEMPTS of a kind, 1 where it declares none
 template <class Env, class = void>

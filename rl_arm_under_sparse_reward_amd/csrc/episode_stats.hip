@@ -141,9 +141,9 @@ int hp_episode_stats_block(hp_rollout *ro, int64_t first_episode, int64_t n_epis
     HP_REQUIRE(first_episode >= 0 && n_episodes >= 1 && first_episode <= ro->n && n_episodes <= ro->n - first_episode, HP_ERR_INVALID,
                "hp_episode_stats_block: episodes [%lld, %lld) outside the block of %lld", (long long)first_episode,
                (long long)(first_episode + n_episodes), (long long)ro->n);
-    const double *ag = ro->block + ro->o_ag + first_episode * (ro->T + 1) * ro->gd;
-    const double *g = ro->block + ro->o_g + first_episode * ro->T * ro->gd;
-    return episode_stats_launch("hp_episode_stats_block", ro->ctx->stream, ag, g, n_episodes, ro->T, ro->gd, distance_threshold,
+    struct { const double *b_obs, *b_ag, *b_g, *b_act; } at;
+    rollout_arrays_at(ro, first_episode, at);
+    return episode_stats_launch("hp_episode_stats_block", ro->ctx->stream, at.b_ag, at.b_g, n_episodes, ro->T, ro->gd, distance_threshold,
                                 stats_dev, step_success_dev);
 }
 

@@ -338,6 +338,15 @@ struct hp_rollout {
     int64_t o_ag = 0, o_g = 0, o_act = 0, elems = 0;   // offsets in float64 elements (feeder._Layout)
 };
 
+// the block's four arrays at episode `episode`, into an argument block that names them b_obs / b_ag / b_g / b_act
+template <class Args>
+inline void rollout_arrays_at(const hp_rollout *ro, int64_t episode, Args &A) {
+    A.b_obs = ro->block + episode * (ro->T + 1) * ro->od;
+    A.b_ag = ro->block + ro->o_ag + episode * (ro->T + 1) * ro->gd;
+    A.b_g = ro->block + ro->o_g + episode * ro->T * ro->gd;
+    A.b_act = ro->block + ro->o_act + episode * ro->T * ro->ad;
+}
+
 // smallest double s whose correctly rounded square root is > thr (strict) or >= thr (buffer.hip): the predicates d > thr and
 // !(d < thr) of compute_reward / _is_success in the squared domain
 double squared_bound(double thr, bool strict);

@@ -28,7 +28,7 @@
 //
 // This unit compiles the two per-step kernels and the host side of every entry.  The whole-episode kernels and the reset are
 // templates over an environment kind (rollout_episodes.h) that each kind's own unit instantiates (env_point_mass.hip,
-// env_push_block.hip); the entries here reach them through the kind's row of the table below (env_kind) and know no kind by name.
+// env_push_block.hip); the entries here reach them through the kind's row of the table below (env_kind_lookup) and know no kind by name.
 #include <algorithm>
 
 #include "rollout_episodes.h"   // ExploreArgs, ro_explore_row, PolicyArgs (slab8.h), EpisodesArgs and EnvKind
@@ -105,17 +105,8 @@ __global__ __launch_bounds__(MW_THREADS) void k_rollout_step_streams(const Rollo
     w.store(st);
 }
 
-// the block's four arrays, offset to episode ro->first (RolloutStepArgs and EpisodesArgs)
-template <class Args>
-static void rollout_block_arrays(const hp_rollout *ro, Args &A) {
-    A.b_obs = ro->block + ro->first * (ro->T + 1) * ro->od;
-    A.b_ag = ro->block + ro->o_ag + ro->first * (ro->T + 1) * ro->gd;
-    A.b_g = ro->block + ro->o_g + ro->first * ro->T * ro->gd;
-    A.b_act = ro->block + ro->o_act + ro->first * ro->T * ro->ad;
-}
-
 static int rollout_launch(hp_rollout *ro, RolloutStepArgs &A, int t, bool per_env_streams = false) {
-    rollout_block_arrays(ro, A);
+    rollout_arrays_at(ro, ro->first, A);
     A.rows = (int)ro->rows; A.T = ro->T; A.t = t; A.od = ro->od; A.gd = ro->gd; A.ad = ro->ad;
     const long long elems = ro->rows * (ro->od + 2 * ro->gd);
     long long nb = (elems + 4 * MW_THREADS - 1) / (4 * MW_THREADS);   // four elements per thread
@@ -169,41 +160,55 @@ static int rollout_step(const char *entry, const char *what, hp_rollout *ro, hp_
     return rollout_launch(ro, A, t, per_env_streams && explore);   // explore == 0 touches no stream: the single-stream kernel's path
 }
 
-// A call of hp_rollout_episodes / hp_rollout_waves as launches.  A (hp_rollout_episodes, or hp_rollout_waves with A.reset_st and
-// A.n_envs set) describes the whole call: episodes [first, first + rows) of the block; it is issued as consecutive launches of at
-// most ro->launch_cap timesteps (whole waves, at least one), each a call of its own on the episodes, flags and final states the one
-// before it left.  launch (EnvKind::launch_episodes) issues one of them with the kernel of the environment's kind and returns its
-// hipError_t: this loop is the same for every kind.
-static int rollout_split_launches(hp_rollout *ro, const EpisodesArgs &A, int32_t *launches,
-                                  hipError_t (*launch)(hipStream_t, unsigned, const EpisodesArgs &)) {
-    const int64_t total = A.rows, n_envs = A.n_envs;
+// A call over episodes [first, first + total) of the block as launches, for either argument block (EpisodesArgs, DemoArgs).  A
+// describes the whole call; it is issued as consecutive launches of at most ro->launch_cap timesteps (whole waves of n_envs
+// environments, at least one), each a call of its own on the episodes, flags, streams and final states the one before it left.
+// The loop sets what every launch has -- its block arrays, rows and waves -- and launch(L, live, done) adds what is the form's own
+// and issues it, returning the hipError_t: live = the environments that take part in the launch at all, done = the episodes of
+// the launches before it.  The same for every kind.
+template <class Args, class Launch>
+static int rollout_split_launches(const hp_rollout *ro, const Args &A, int64_t first, int64_t total, int64_t n_envs, int32_t *launches,
+                                  Launch launch) {
     int64_t per = ro->launch_cap / (ro->T > 0 ? ro->T : 1);   // waves per launch
     if (per < 1) per = 1;
     int n = 0;
     for (int64_t done = 0; done < total; ++n) {
         const int64_t left = total - done, waves = std::min<int64_t>((left + n_envs - 1) / n_envs, per);
         const int64_t rows = std::min(left, waves * n_envs), live = std::min(rows, n_envs);
-        EpisodesArgs L = A;
-        L.b_obs += done * (ro->T + 1) * ro->od;
-        L.b_ag += done * (ro->T + 1) * ro->gd;
-        L.b_g += done * ro->T * ro->gd;
-        L.b_act += done * ro->T * ro->ad;
-        L.success += done;
+        Args L = A;
+        rollout_arrays_at(ro, first + done, L);
         L.rows = (int)rows; L.waves = (int)waves;
-        L.P.rows = (int)live;              // the environments that take part in the launch at all
-        HP_CHECK_HIP(launch(ro->ctx->stream, (unsigned)((live + 3) / 4), L));
+        HP_CHECK_HIP(launch(L, live, done));
         done += rows;
     }
     if (launches) *launches = n;
     return HP_OK;
 }
 
-// The table of environment kinds: one row per kind, defined by the kind's own unit.  nullptr: not an environment kind of this build
-static const EnvKind *env_kind(int kind) {
+// The table of environment kinds: one row per kind, defined by the kind's own unit -- and the refusal of every entry for a
+// descriptor whose kind has no row
+static int env_kind_lookup(const char *entry, const hp_env_desc *env, const EnvKind *&kind) {
     static const EnvKind *const kinds[] = {&env_kind_point_mass, &env_kind_push_block, &env_kind_pick_place};
+    kind = nullptr;
     for (const EnvKind *k : kinds)
-        if (k->kind == kind) return k;
-    return nullptr;
+        if (k->kind == env->kind) {
+            kind = k;
+            break;
+        }
+    HP_REQUIRE(kind, HP_ERR_INVALID, "%s: env->kind %d is not an environment kind of this build", entry, (int)env->kind);
+    return HP_OK;
+}
+
+// A descriptor against its kind's row, in the order every entry refuses in: the state arrays, the block's dimensions (ro ==
+// nullptr: the entry has no block), the reset on the device where the entry needs one
+static int env_desc_check(const char *entry, const EnvKind *kind, const hp_env_desc *env, const hp_rollout *ro, bool needs_reset) {
+    for (int k = 0; k < kind->state_arrays; ++k)
+        HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "%s: env->state_dev[%d] is null", entry, k);
+    HP_REQUIRE(!ro || (ro->od == kind->obs && ro->gd == kind->goal && ro->ad == kind->act), HP_ERR_INVALID,
+               "%s: env->kind %d has dimensions %d / %d / %d, the block has %d / %d / %d", entry, (int)env->kind, kind->obs, kind->goal,
+               kind->act, ro ? ro->od : 0, ro ? ro->gd : 0, ro ? ro->ad : 0);
+    HP_REQUIRE(!needs_reset || kind->reset_draws > 0, HP_ERR_INVALID, "%s: env->kind %d has no reset on the device", entry, (int)env->kind);
+    return HP_OK;
 }
 
 // what hp_rollout_episodes and hp_rollout_waves share: the checks on agent, normalizers, block and streams, and the arguments of the
@@ -214,8 +219,8 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx && (!streams || streams->ctx == ro->ctx) &&
                    (!reset_streams || reset_streams->ctx == ro->ctx),
                HP_ERR_INVALID, "%s: handles belong to different contexts", entry);
-    const EnvKind *kind = env_kind(env->kind);
-    HP_REQUIRE(kind, HP_ERR_INVALID, "%s: env->kind %d is not an environment kind of this build", entry, (int)env->kind);
+    const EnvKind *kind;
+    HP_TRY(env_kind_lookup(entry, env, kind));
     HP_REQUIRE(a->slab8 && a->H == 256 && a->ldx <= 48 && a->cfg.act_dim <= 4, HP_ERR_INVALID,
                "%s: the agent is not slab-shaped (hidden %d, padded input width %d, act_dim %d, engine %s): it keeps "
                "the per-step calls", entry, a->H, a->ldx, a->cfg.act_dim, a->slab8 ? "slab8" : "other");
@@ -229,12 +234,7 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     HP_REQUIRE(!reset_streams || n_envs <= reset_streams->n, HP_ERR_INVALID,
                "%s: %lld environments, but the array holds %lld reset streams", entry, (long long)n_envs, (long long)reset_streams->n);
     HP_REQUIRE(!explore || (random_eps >= 0.0 && random_eps <= 1.0), HP_ERR_INVALID, "p < 0, p > 1 or p is NaN");
-    for (int k = 0; k < kind->state_arrays; ++k)
-        HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "%s: env->state_dev[%d] is null", entry, k);
-    HP_REQUIRE(ro->od == kind->obs && ro->gd == kind->goal && ro->ad == kind->act, HP_ERR_INVALID,
-               "%s: env->kind %d has dimensions %d / %d / %d, the block has %d / %d / %d", entry, (int)env->kind, kind->obs, kind->goal,
-               kind->act, ro->od, ro->gd, ro->ad);
-    HP_REQUIRE(!reset_streams || kind->reset_draws > 0, HP_ERR_INVALID, "%s: env->kind %d has no reset on the device", entry, (int)env->kind);
+    HP_TRY(env_desc_check(entry, kind, env, ro, reset_streams != nullptr));
     EpisodesArgs A;
     memset(&A, 0, sizeof(A));
     PolicyArgs &P = A.P;
@@ -243,7 +243,6 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     P.clip_obs = INFINITY; P.clip_o = on->clip; P.clip_g = gn->clip;   // agent_act_dev with clip_obs = 0
     P.net = SlabNetPtrs{a->fragF, a->fragD, a->params};
     P.la = a->la; P.H = a->H; P.act_dim = a->cfg.act_dim; P.max_action = (float)a->cfg.max_action;
-    rollout_block_arrays(ro, A);
     A.st = explore ? streams->d_state : nullptr;
     A.reset_st = reset_streams ? reset_streams->d_state : nullptr;
     A.rows = (int)ro->rows; A.T = ro->T; A.explore = explore ? 1 : 0;
@@ -255,7 +254,11 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     A.x.random_eps = random_eps; A.x.qn = qn; A.x.clip_abs = clip_abs;
     A.env = *env;
     A.success = success_dev;
-    return rollout_split_launches(ro, A, launches, kind->launch_episodes);
+    return rollout_split_launches(ro, A, ro->first, ro->rows, n_envs, launches, [&](EpisodesArgs &L, int64_t live, int64_t done) {
+        L.success += done;
+        L.P.rows = (int)live;              // the environments that take part in the launch at all
+        return kind->launch_episodes(ro->ctx->stream, (unsigned)((live + 3) / 4), L);
+    });
 }
 
 // what hp_demo_episodes and hp_demo_episodes_pick share -- everything but the type of the script: the checks (`entry` names the
@@ -276,53 +279,27 @@ static int demo_episodes(const char *entry, hp_ctx *ctx, const hp_env_desc *env,
                "%s: episodes [%lld, %lld) outside the block of %lld", entry, (long long)first_episode,
                (long long)(first_episode + n_episodes), (long long)ro->n);
     HP_REQUIRE(T == ro->T, HP_ERR_INVALID, "%s: T = %d, the block has T = %d", entry, (int)T, (int)ro->T);
-    const EnvKind *kind = env_kind(env->kind);
-    HP_REQUIRE(kind, HP_ERR_INVALID, "%s: env->kind %d is not an environment kind of this build", entry, (int)env->kind);
-    for (int k = 0; k < kind->state_arrays; ++k)
-        HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "%s: env->state_dev[%d] is null", entry, k);
-    HP_REQUIRE(ro->od == kind->obs && ro->gd == kind->goal && ro->ad == kind->act, HP_ERR_INVALID,
-               "%s: env->kind %d has dimensions %d / %d / %d, the block has %d / %d / %d", entry, (int)env->kind, kind->obs,
-               kind->goal, kind->act, ro->od, ro->gd, ro->ad);
-    HP_REQUIRE(kind->reset_draws > 0, HP_ERR_INVALID, "%s: env->kind %d has no reset on the device", entry, (int)env->kind);
+    const EnvKind *kind;
+    HP_TRY(env_kind_lookup(entry, env, kind));
+    HP_TRY(env_desc_check(entry, kind, env, ro, true));
     const int32_t *phase_end = push ? push->phase_end : pick->phase_end;
     for (int k = 0; k < 5; ++k)
         HP_REQUIRE(phase_end[k] >= 0 && (k == 0 || phase_end[k] > phase_end[k - 1]), HP_ERR_INVALID,
                    "%s: script->phase_end[%d] = %d: the phase ends must be increasing", entry, k, (int)phase_end[k]);
     DemoArgs A;
     memset(&A, 0, sizeof(A));
-    A.b_obs = ro->block + first_episode * (ro->T + 1) * ro->od;
-    A.b_ag = ro->block + ro->o_ag + first_episode * (ro->T + 1) * ro->gd;
-    A.b_g = ro->block + ro->o_g + first_episode * ro->T * ro->gd;
-    A.b_act = ro->block + ro->o_act + first_episode * ro->T * ro->ad;
     A.reset_st = reset_streams->d_state;
     A.T = ro->T; A.n_envs = (int)n_envs;
     A.controller = push ? DEMO_PUSH : DEMO_PICK;
     if (push) A.s = *push;
     else A.p = *pick;
     A.env = *env;
-    // the launch-length rule of rollout_split_launches: whole waves, at most launch_cap timesteps, the next launch on the states
-    // and streams the one before it wrote back
-    int64_t per = ro->launch_cap / (ro->T > 0 ? ro->T : 1);
-    if (per < 1) per = 1;
-    int n = 0;
-    for (int64_t done = 0; done < n_episodes; ++n) {
-        const int64_t left = n_episodes - done, waves = std::min<int64_t>((left + n_envs - 1) / n_envs, per);
-        const int64_t rows = std::min(left, waves * n_envs), live = std::min(rows, n_envs);
-        DemoArgs L = A;
-        L.b_obs += done * (ro->T + 1) * ro->od;
-        L.b_ag += done * (ro->T + 1) * ro->gd;
-        L.b_g += done * ro->T * ro->gd;
-        L.b_act += done * ro->T * ro->ad;
+    return rollout_split_launches(ro, A, first_episode, n_episodes, n_envs, launches_out, [&](DemoArgs &L, int64_t live, int64_t done) {
         L.success = success_dev + done;
         L.step_success = step_success_dev + done * ro->T;
-        L.rows = (int)rows; L.waves = (int)waves;
-        HP_CHECK_HIP(kind->launch_demo(ctx->stream, (unsigned)live, L));
-        done += rows;
-    }
-    if (launches_out) *launches_out = n;
-    return HP_OK;
+        return kind->launch_demo(ctx->stream, (unsigned)live, L);
+    });
 }
-
 
 extern "C" {
 
@@ -412,11 +389,9 @@ int hp_env_reset(hp_ctx *ctx, const hp_env_desc *env, hp_rng_streams *reset_stre
     HP_REQUIRE(reset_streams->ctx == ctx, HP_ERR_INVALID, "hp_env_reset: handles belong to different contexts");
     HP_REQUIRE(rows > 0 && rows <= reset_streams->n, HP_ERR_INVALID,
                "hp_env_reset: %lld environments, but the array holds %lld reset streams", (long long)rows, (long long)reset_streams->n);
-    const EnvKind *kind = env_kind(env->kind);
-    HP_REQUIRE(kind, HP_ERR_INVALID, "hp_env_reset: env->kind %d is not an environment kind of this build", (int)env->kind);
-    for (int k = 0; k < kind->state_arrays; ++k)
-        HP_REQUIRE(env->state_dev[k], HP_ERR_INVALID, "hp_env_reset: env->state_dev[%d] is null", k);
-    HP_REQUIRE(kind->reset_draws > 0, HP_ERR_INVALID, "hp_env_reset: env->kind %d has no reset on the device", (int)env->kind);
+    const EnvKind *kind;
+    HP_TRY(env_kind_lookup("hp_env_reset", env, kind));
+    HP_TRY(env_desc_check("hp_env_reset", kind, env, nullptr, true));
     HP_CHECK_HIP(kind->launch_reset(ctx->stream, *env, reset_streams->d_state, rows));
     return HP_OK;
 }

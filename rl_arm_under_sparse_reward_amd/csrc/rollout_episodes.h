@@ -259,7 +259,7 @@ EnvKind env_kind_entry(int kind) {
                    &env_launch_demo<Env>};
 }
 
-// the rows, one per unit (the table itself: env_kind() in rollout.hip)
+// the rows, one per unit (the table itself: env_kind_lookup() in rollout.hip)
 extern const EnvKind env_kind_point_mass;   // env_point_mass.hip
 extern const EnvKind env_kind_push_block;   // env_push_block.hip
 extern const EnvKind env_kind_pick_place;   // env_pick_place.hip

@@ -52,7 +52,8 @@ three dimensions.
 
 `PointMassVecEnv` is the tensor twin of `synthetic.PointMassGoalEnv`, `PushBlockVecEnv` that of `synthetic.PushBlockGoalEnv`,
 `PickPlaceVecEnv` that of `synthetic.PickPlaceGoalEnv`; what
-they share (`_GoalVecEnv`) includes the rule that an environment works on the first `active` rows of its state tensors.  A native
+they share (`_GoalVecEnv`) includes the rule that an environment works on the first `active` rows of its state tensors, and the
+two gripper-and-block twins share their state, reset and observation columns one level below it (`_GripBlockVecEnv`).  A native
 class is one of them behind `_NativeEnv` -- descriptor, device reset -- plus the constant of its kind.
 """
 from __future__ import annotations
@@ -64,10 +65,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .synthetic import (DemoScript, write_demo_npz_from, PUSH_RESET_ATTEMPTS, PUSH_RESET_BOUNDS, PUSH_START_Z, PUSH_X_HI, PUSH_X_LO, PUSH_Y_HI, PUSH_Y_LO,
-                        PUSH_Z_HI)
-from .synthetic import (PickScript, PICK_FINGER_MAX, PICK_GRASP_WIDTH, PICK_RESET_ATTEMPTS, PICK_RESET_BOUNDS, PICK_START_Z, PICK_TOOL,
-                        PICK_X_HI, PICK_X_LO, PICK_Y_HI, PICK_Y_LO, PICK_Z_HI)
+from .synthetic import (DemoScript, rejection_reset, write_demo_npz_from, push_separated, PUSH_RESET_ATTEMPTS, PUSH_RESET_BOUNDS, PUSH_START_Z,
+                        PUSH_X_HI, PUSH_X_LO, PUSH_Y_HI, PUSH_Y_LO, PUSH_Z_HI)
+from .synthetic import (PickScript, pick_separated, PICK_FINGER_MAX, PICK_GRASP_WIDTH, PICK_RESET_ATTEMPTS, PICK_RESET_BOUNDS, PICK_START_Z,
+                        PICK_TOOL, PICK_X_HI, PICK_X_LO, PICK_Y_HI, PICK_Y_LO, PICK_Z_HI)
 
 
 def wave_layout(n_envs, T, obs, goal, act):
@@ -258,38 +259,31 @@ class PointMassVecEnv(_GoalVecEnv):
         return self._stepped()
 
 
-class PushBlockVecEnv(_GoalVecEnv):
-    """n `synthetic.PushBlockGoalEnv`s as tensors: env i resets from RandomState(seed + i) on the host -- the same rejection loop,
-    four scalars per attempt -- and `step` is the host environment's operations elementwise in float64, one torch op per
-    rounding, `torch.where` for its branches.  State: `grip`, `blk`, `goal` [rows, 3] and `vel` [rows, 6] (gripper, then block).
-    Works with device="cpu" too."""
+class _GripBlockVecEnv(_GoalVecEnv):
+    """What the tensor twins of the two gripper-and-block tasks share: the constructor arguments of the table, the state tensors
+    `grip`, `blk`, `goal` [rows, 3] and a fourth one -- named by `state_names[3]`, `_aux_width` columns, the gripper's and the
+    block's velocity in its first six -- the rejection reset on the host with its upload, and the observation's common columns.
+    A subclass has `_reset = (bounds, attempts, separated, gripper start z)`, `params()` and `step`."""
 
-    state_names = ("grip", "blk", "goal", "vel")
-
-    def __init__(self, n_envs, seed=0, device="cuda", max_timesteps=100, distance_threshold=0.05, reward_type='sparse',
-                 step_scale=0.1, half_width=0.04, z_touch=0.25, min_separation=0.15, table_z=0.2, grip_start=(0.25, 0.1)):
+    def __init__(self, n_envs, seed, device, max_timesteps, distance_threshold, reward_type, step_scale, half_width, min_separation,
+                 table_z, grip_start):
         super().__init__(n_envs, seed, device, max_timesteps, distance_threshold, reward_type, step_scale)
-        self.half_width, self.z_touch = float(half_width), float(z_touch)
+        self.half_width = float(half_width)
         self.min_separation, self.table_z = float(min_separation), float(table_z)
         self.grip_start = (float(grip_start[0]), float(grip_start[1]))
         self.reset_attempts = [0] * self.n_envs      # attempts the last host reset of each environment took
         z = torch.zeros((self.n_envs, 3), dtype=torch.float64, device=self.device)
         self.grip, self.blk, self.goal = z, z.clone(), z.clone()
-        self.vel = torch.zeros((self.n_envs, 6), dtype=torch.float64, device=self.device)
+        setattr(self, self.state_names[3], torch.zeros((self.n_envs, self._aux_width), dtype=torch.float64, device=self.device))
 
     @property
     def pos(self):
         """The gripper's position (nothing in the package reads it)."""
         return self.grip
 
-    def params(self):
-        """hp_env_desc.params of the kind"""
-        return [self.step_scale, self.distance_threshold, self.half_width, self.z_touch, self.min_separation, self.table_z,
-                self.grip_start[0], self.grip_start[1]]
-
     def _observation(self):
         k = self.active
-        grip, blk, vel = self.grip[:k], self.blk[:k], self.vel[:k]
+        grip, blk, vel = self.grip[:k], self.blk[:k], getattr(self, self.state_names[3])[:k]
         obs = torch.zeros((k, 27), dtype=torch.float64, device=self.device)
         obs[:, 0:3] = grip
         obs[:, 6:9] = vel[:, 0:3]
@@ -301,22 +295,39 @@ class PushBlockVecEnv(_GoalVecEnv):
     def reset(self, n_active=None):
         """Reset the first `n_active` environments (default: all): only those draw from their streams."""
         k = self._n_active(n_active)
+        bounds, attempts, separated, start_z = self._reset
         fresh = np.empty((3, k, 3))
         for i in range(k):
-            for attempt in range(PUSH_RESET_ATTEMPTS):
-                bx, by, gx, gy = (self.rs[i].uniform(low, high) for low, high in PUSH_RESET_BOUNDS)
-                ddx, ddy = bx - gx, by - gy
-                if np.sqrt(ddx * ddx + ddy * ddy) >= self.min_separation:
-                    break
-            self.reset_attempts[i] = attempt + 1
-            fresh[0, i] = (self.grip_start[0], self.grip_start[1], PUSH_START_Z)
-            fresh[1, i] = (bx, by, self.table_z)
-            fresh[2, i] = (gx, gy, self.table_z)
+            u, self.reset_attempts[i] = rejection_reset(self.rs[i], bounds, attempts, lambda *u: separated(self, *u))
+            fresh[0, i] = (self.grip_start[0], self.grip_start[1], start_z)
+            fresh[1, i] = (u[0], u[1], self.table_z)
+            fresh[2, i] = (u[2], u[3], u[4] if len(u) > 4 else self.table_z)     # a fifth draw is the goal's height
         dev = torch.from_numpy(fresh).to(self.device)
         self.grip, self.blk, self.goal = dev[0].contiguous(), dev[1].contiguous(), dev[2].contiguous()
-        self.vel = torch.zeros((k, 6), dtype=torch.float64, device=self.device)
+        setattr(self, self.state_names[3], torch.zeros((k, self._aux_width), dtype=torch.float64, device=self.device))
         self.active = k
         return self._observation()
+
+
+class PushBlockVecEnv(_GripBlockVecEnv):
+    """n `synthetic.PushBlockGoalEnv`s as tensors: env i resets from RandomState(seed + i) on the host -- the same rejection loop,
+    four scalars per attempt -- and `step` is the host environment's operations elementwise in float64, one torch op per
+    rounding, `torch.where` for its branches.  State: `grip`, `blk`, `goal` [rows, 3] and `vel` [rows, 6] (gripper, then block).
+    Works with device="cpu" too."""
+
+    state_names, _aux_width = ("grip", "blk", "goal", "vel"), 6
+    _reset = (PUSH_RESET_BOUNDS, PUSH_RESET_ATTEMPTS, push_separated, PUSH_START_Z)
+
+    def __init__(self, n_envs, seed=0, device="cuda", max_timesteps=100, distance_threshold=0.05, reward_type='sparse',
+                 step_scale=0.1, half_width=0.04, z_touch=0.25, min_separation=0.15, table_z=0.2, grip_start=(0.25, 0.1)):
+        super().__init__(n_envs, seed, device, max_timesteps, distance_threshold, reward_type, step_scale, half_width, min_separation,
+                         table_z, grip_start)
+        self.z_touch = float(z_touch)
+
+    def params(self):
+        """hp_env_desc.params of the kind"""
+        return [self.step_scale, self.distance_threshold, self.half_width, self.z_touch, self.min_separation, self.table_z,
+                self.grip_start[0], self.grip_start[1]]
 
     def step(self, actions):
         k, r = self.active, self.half_width
@@ -343,29 +354,20 @@ class PushBlockVecEnv(_GoalVecEnv):
         return self._stepped()
 
 
-class PickPlaceVecEnv(_GoalVecEnv):
+class PickPlaceVecEnv(_GripBlockVecEnv):
     """n `synthetic.PickPlaceGoalEnv`s as tensors: env i resets from RandomState(seed + i) on the host -- the same rejection loop,
     five scalars per attempt -- and `step` is the host environment's operations elementwise in float64, one torch op per
     rounding, `torch.where` for its branches.  State: `grip`, `blk`, `goal` [rows, 3] and `aux` [rows, 8] = gripper velocity,
     block velocity, finger opening, held (0.0 or 1.0).  Works with device="cpu" too."""
 
-    state_names = ("grip", "blk", "goal", "aux")
+    state_names, _aux_width = ("grip", "blk", "goal", "aux"), 8
+    _reset = (PICK_RESET_BOUNDS, PICK_RESET_ATTEMPTS, pick_separated, PICK_START_Z)
 
     def __init__(self, n_envs, seed=0, device="cuda", max_timesteps=100, distance_threshold=0.05, reward_type='sparse',
                  step_scale=0.2, half_width=0.04, finger_scale=0.05, min_separation=0.15, table_z=0.2, grip_start=(0.25, 0.1)):
-        super().__init__(n_envs, seed, device, max_timesteps, distance_threshold, reward_type, step_scale)
-        self.half_width, self.finger_scale = float(half_width), float(finger_scale)
-        self.min_separation, self.table_z = float(min_separation), float(table_z)
-        self.grip_start = (float(grip_start[0]), float(grip_start[1]))
-        self.reset_attempts = [0] * self.n_envs      # attempts the last host reset of each environment took
-        z = torch.zeros((self.n_envs, 3), dtype=torch.float64, device=self.device)
-        self.grip, self.blk, self.goal = z, z.clone(), z.clone()
-        self.aux = torch.zeros((self.n_envs, 8), dtype=torch.float64, device=self.device)
-
-    @property
-    def pos(self):
-        """The gripper's position (nothing in the package reads it)."""
-        return self.grip
+        super().__init__(n_envs, seed, device, max_timesteps, distance_threshold, reward_type, step_scale, half_width, min_separation,
+                         table_z, grip_start)
+        self.finger_scale = float(finger_scale)
 
     def params(self):
         """hp_env_desc.params of the kind"""
@@ -373,36 +375,9 @@ class PickPlaceVecEnv(_GoalVecEnv):
                 self.grip_start[0], self.grip_start[1]]
 
     def _observation(self):
-        k = self.active
-        grip, blk, aux = self.grip[:k], self.blk[:k], self.aux[:k]
-        obs = torch.zeros((k, 27), dtype=torch.float64, device=self.device)
-        obs[:, 0:3] = grip
-        obs[:, 6:9] = aux[:, 0:3]
-        obs[:, 9:11] = aux[:, 6:8]
-        obs[:, 12:15] = blk
-        obs[:, 18:21] = blk - grip
-        obs[:, 21:24] = aux[:, 3:6]
-        return {'observation': obs, 'achieved_goal': blk.clone(), 'desired_goal': self.goal[:k].clone()}
-
-    def reset(self, n_active=None):
-        """Reset the first `n_active` environments (default: all): only those draw from their streams."""
-        k = self._n_active(n_active)
-        fresh = np.empty((3, k, 3))
-        for i in range(k):
-            for attempt in range(PICK_RESET_ATTEMPTS):
-                bx, by, gx, gy, gz = (self.rs[i].uniform(low, high) for low, high in PICK_RESET_BOUNDS)
-                ddx, ddy, ddz = bx - gx, by - gy, self.table_z - gz
-                if np.sqrt(ddx * ddx + ddy * ddy + ddz * ddz) >= self.min_separation:
-                    break
-            self.reset_attempts[i] = attempt + 1
-            fresh[0, i] = (self.grip_start[0], self.grip_start[1], PICK_START_Z)
-            fresh[1, i] = (bx, by, self.table_z)
-            fresh[2, i] = (gx, gy, gz)
-        dev = torch.from_numpy(fresh).to(self.device)
-        self.grip, self.blk, self.goal = dev[0].contiguous(), dev[1].contiguous(), dev[2].contiguous()
-        self.aux = torch.zeros((k, 8), dtype=torch.float64, device=self.device)
-        self.active = k
-        return self._observation()
+        o = super()._observation()
+        o['observation'][:, 9:11] = self.aux[:self.active, 6:8]      # finger opening, held
+        return o
 
     def _pads_inside(self, grip, blk):
         tool = torch.tensor(PICK_TOOL, dtype=torch.float64, device=self.device)
@@ -438,9 +413,7 @@ class _NativeEnv:
     kind = None              # _lib.ENV_*: the struct of csrc/env_device.h that evaluates the same float64 operations
     reset_streams = None     # random.DeviceRandomStreams after enable_device_reset(): reset stream i = the state of rs[i]
 
-    def default_demo_script(self):
-        """The scripted controller `generate_demos` runs on this environment when the caller names none: the task's own"""
-        return DemoScript()
+    default_demo_script = DemoScript   # the script type `generate_demos` runs here when the caller names none: the task's own
 
     def native_desc(self):
         """hp_env_desc of the environments stepped now: kind, `params()`, and the state tensors in the order of `state_names`
@@ -521,8 +494,7 @@ class NativePickPlaceVecEnv(_NativeEnv, PickPlaceVecEnv):
 
     kind = _lib.ENV_PICK_PLACE
 
-    def default_demo_script(self):
-        return PickScript()
+    default_demo_script = PickScript
 
 
 # ---- demonstrations from the scripted controller ---------------------------------------------------------------------------------
@@ -538,25 +510,22 @@ def default_round_waves(n_demos, n_envs):
     return max(1, min(-(-2 * n_demos // n_envs), max(1, DEMO_ROUND_EPISODES // n_envs)))
 
 
+# a script type's struct, and the fields both carry under the same names: the arrays, the scalars
+_DEMO_SCRIPT_FIELDS = (_lib.DemoScriptDesc, ("phase_end", "lift", "waypoint"), ("behind", "stop_radius"))
+_PICK_SCRIPT_FIELDS = (_lib.PickScriptDesc, ("phase_end", "lift", "approach", "grasp"), ("open",))
+
+
 def script_desc(script=None):
     """`synthetic.DemoScript` (None: the reference's numbers) as the library's struct (hp_demo_script), or a
     `synthetic.PickScript` as its own (hp_pick_script)."""
     s = script or DemoScript()
-    if isinstance(s, PickScript):
-        d = _lib.PickScriptDesc()
-        for name in ("phase_end", "lift", "approach", "grasp"):
-            for i, v in enumerate(getattr(s, name)):
-                getattr(d, name)[i] = v
-        d.open = s.open
-        return d
-    d = _lib.DemoScriptDesc()
-    for i, v in enumerate(s.phase_end):
-        d.phase_end[i] = v
-    for i, v in enumerate(s.lift):
-        d.lift[i] = v
-    for i, v in enumerate(s.waypoint):
-        d.waypoint[i] = v
-    d.behind, d.stop_radius = s.behind, s.stop_radius
+    struct, arrays, scalars = _PICK_SCRIPT_FIELDS if isinstance(s, PickScript) else _DEMO_SCRIPT_FIELDS
+    d = struct()
+    for name in arrays:
+        for i, v in enumerate(getattr(s, name)):
+            getattr(d, name)[i] = v
+    for name in scalars:
+        setattr(d, name, getattr(s, name))
     return d
 
 

@@ -63,7 +63,53 @@ def write_demo_npz(path, n_episodes=8, seed=7, T=100):
     return obs, ag, g, actions
 
 
-class PointMassGoalEnv:
+class _HostGoalEnv:
+    """What the host environments share: the environment's own RandomState, the GoalEnv surface that does not depend on the
+    task -- `env_params`, `compute_reward` vectorised over leading dims (bmirobot_env_push_F.py:84-90), `_is_success` (:243-245)
+    -- and what `step` returns once the task has moved its state (:103-108).  A task has `goal`, `_observation()`, `reset()` and
+    `step(action)`."""
+
+    def __init__(self, seed, max_timesteps, distance_threshold, reward_type, step_scale):
+        self.rs = np.random.RandomState(seed)
+        self.max_timesteps = int(max_timesteps)
+        self.distance_threshold = float(distance_threshold)
+        self.reward_type = reward_type
+        self.step_scale = float(step_scale)
+
+    @property
+    def env_params(self):
+        return {'obs': 27, 'goal': 3, 'action': 4, 'action_max': 0.5, 'max_timesteps': self.max_timesteps}
+
+    def compute_reward(self, achieved_goal, goal, info):
+        diff = np.asarray(achieved_goal) - np.asarray(goal)
+        d = np.linalg.norm(diff, axis=-1)
+        if self.reward_type == 'sparse':
+            return -(d > self.distance_threshold).astype(np.float32)
+        return -d
+
+    def _is_success(self, achieved_goal, desired_goal):
+        return (np.linalg.norm(achieved_goal - desired_goal, axis=-1) < self.distance_threshold).astype(np.float32)
+
+    def _stepped(self):
+        """What `step` returns, out of the state it has just written"""
+        observation = self._observation()
+        info = {'is_success': self._is_success(observation['achieved_goal'], self.goal)}
+        reward = self.compute_reward(observation['achieved_goal'], self.goal, info)
+        return observation, reward, False, info
+
+
+def rejection_reset(rs, bounds, attempts, accept):
+    """The rejection loop of a reset (bmirobot_env_push_F.py:117-132): at most `attempts` times, one `rs.uniform(low, high)` per
+    pair of `bounds`, in order, until `accept(*draws)`; the last attempt is kept either way.  Returns (draws, attempts taken).
+    The host environments and the host reset of their tensor twins (device_env.py) draw through it."""
+    for attempt in range(attempts):
+        draws = tuple(rs.uniform(low, high) for low, high in bounds)
+        if accept(*draws):
+            break
+    return draws, attempt + 1
+
+
+class PointMassGoalEnv(_HostGoalEnv):
     """Stand-in for the PyBullet arm environments (the real ones need pybullet + gym, absent here): the
     gym GoalEnv surface the learner's rollout loop uses -- reset() / step(action) returning the dict observation
     {'observation', 'achieved_goal', 'desired_goal'} (bmirobot_env_push_F.py:233-237), step's 4-tuple with
@@ -73,18 +119,10 @@ class PointMassGoalEnv:
     numpy's global stream, which belongs to the exploration noise."""
 
     def __init__(self, seed=0, max_timesteps=100, distance_threshold=0.05, reward_type='sparse', step_scale=0.1):
-        self.rs = np.random.RandomState(seed)
-        self.max_timesteps = int(max_timesteps)
-        self.distance_threshold = float(distance_threshold)
-        self.reward_type = reward_type
-        self.step_scale = float(step_scale)
+        super().__init__(seed, max_timesteps, distance_threshold, reward_type, step_scale)
         self.pos = np.zeros(3)
         self.vel = np.zeros(3)
         self.goal = np.zeros(3)
-
-    @property
-    def env_params(self):
-        return {'obs': 27, 'goal': 3, 'action': 4, 'action_max': 0.5, 'max_timesteps': self.max_timesteps}
 
     def _observation(self):
         obs = np.zeros(27)
@@ -99,25 +137,12 @@ class PointMassGoalEnv:
         self.vel = np.zeros(3)
         return self._observation()
 
-    def compute_reward(self, achieved_goal, goal, info):
-        diff = np.asarray(achieved_goal) - np.asarray(goal)
-        d = np.linalg.norm(diff, axis=-1)
-        if self.reward_type == 'sparse':
-            return -(d > self.distance_threshold).astype(np.float32)
-        return -d
-
-    def _is_success(self, achieved_goal, desired_goal):
-        return (np.linalg.norm(achieved_goal - desired_goal, axis=-1) < self.distance_threshold).astype(np.float32)
-
     def step(self, action):
         action = np.clip(np.asarray(action, dtype=np.float64), -0.5, 0.5)
         new = np.clip(self.pos + self.step_scale * action[:3], 0.0, 0.5)
         self.vel = new - self.pos
         self.pos = new
-        observation = self._observation()
-        info = {'is_success': self._is_success(observation['achieved_goal'], self.goal)}
-        reward = self.compute_reward(observation['achieved_goal'], self.goal, info)
-        return observation, reward, False, info
+        return self._stepped()
 
 
 # the workspace of the push-block environments (synthetic.PushBlockGoalEnv, device_env.PushBlockVecEnv, PushBlockEnvDev in
@@ -128,7 +153,13 @@ PUSH_RESET_BOUNDS = ((0.15, 0.35), (0.2, 0.5), (0.0, 0.35), (0.2, 0.5))
 PUSH_RESET_ATTEMPTS = 100
 
 
-class PushBlockGoalEnv:
+def push_separated(env, bx, by, gx, gy):
+    """Whether one attempt of the push block's reset stands: block and target `env.min_separation` apart on the table"""
+    ddx, ddy = bx - gx, by - gy
+    return np.sqrt(ddx * ddx + ddy * ddy) >= env.min_separation
+
+
+class PushBlockGoalEnv(_HostGoalEnv):
     """A kinematic planar push with the GoalEnv surface of `PointMassGoalEnv`: the setting of the reference's Push task
     (bmirobot_env_push_F.py) in which the achieved goal is a block that moves only on contact, so that most actions leave it
     where it is and the reward is sparse in earnest.  The block is a square of half width `half_width` resting on the table; the
@@ -140,20 +171,13 @@ class PushBlockGoalEnv:
 
     def __init__(self, seed=0, max_timesteps=100, distance_threshold=0.05, reward_type='sparse', step_scale=0.1, half_width=0.04,
                  z_touch=0.25, min_separation=0.15, table_z=0.2, grip_start=(0.25, 0.1)):
-        self.rs = np.random.RandomState(seed)
-        self.max_timesteps = int(max_timesteps)
-        self.distance_threshold = float(distance_threshold)
-        self.reward_type = reward_type
-        self.step_scale, self.half_width, self.z_touch = float(step_scale), float(half_width), float(z_touch)
+        super().__init__(seed, max_timesteps, distance_threshold, reward_type, step_scale)
+        self.half_width, self.z_touch = float(half_width), float(z_touch)
         self.min_separation, self.table_z = float(min_separation), float(table_z)
         self.grip_start = (float(grip_start[0]), float(grip_start[1]))
         self.grip, self.blk, self.goal = np.zeros(3), np.zeros(3), np.zeros(3)
         self.gvel, self.bvel = np.zeros(3), np.zeros(3)
         self.reset_attempts = 0              # attempts the last reset took
-
-    @property
-    def env_params(self):
-        return {'obs': 27, 'goal': 3, 'action': 4, 'action_max': 0.5, 'max_timesteps': self.max_timesteps}
 
     def _observation(self):
         obs = np.zeros(27)                   # the bmirobot layout (:208-222): nine blocks of three
@@ -165,27 +189,13 @@ class PushBlockGoalEnv:
         return {'observation': obs, 'achieved_goal': self.blk.copy(), 'desired_goal': self.goal.copy()}
 
     def reset(self):
-        for attempt in range(PUSH_RESET_ATTEMPTS):
-            bx, by, gx, gy = (self.rs.uniform(low, high) for low, high in PUSH_RESET_BOUNDS)
-            ddx, ddy = bx - gx, by - gy
-            if np.sqrt(ddx * ddx + ddy * ddy) >= self.min_separation:
-                break
-        self.reset_attempts = attempt + 1
+        (bx, by, gx, gy), self.reset_attempts = rejection_reset(self.rs, PUSH_RESET_BOUNDS, PUSH_RESET_ATTEMPTS,
+                                                                 lambda *u: push_separated(self, *u))
         self.blk = np.array([bx, by, self.table_z])
         self.goal = np.array([gx, gy, self.table_z])
         self.grip = np.array([self.grip_start[0], self.grip_start[1], PUSH_START_Z])
         self.gvel, self.bvel = np.zeros(3), np.zeros(3)
         return self._observation()
-
-    def compute_reward(self, achieved_goal, goal, info):
-        diff = np.asarray(achieved_goal) - np.asarray(goal)
-        d = np.linalg.norm(diff, axis=-1)
-        if self.reward_type == 'sparse':
-            return -(d > self.distance_threshold).astype(np.float32)
-        return -d
-
-    def _is_success(self, achieved_goal, desired_goal):
-        return (np.linalg.norm(achieved_goal - desired_goal, axis=-1) < self.distance_threshold).astype(np.float32)
 
     def step(self, action):
         r = self.half_width
@@ -206,10 +216,7 @@ class PushBlockGoalEnv:
             self.blk[0] = min(max(self.blk[0], PUSH_X_LO), PUSH_X_HI)
             self.blk[1] = min(max(self.blk[1], PUSH_Y_LO), PUSH_Y_HI)
         self.bvel = self.blk - old
-        observation = self._observation()
-        info = {'is_success': self._is_success(observation['achieved_goal'], self.goal)}
-        reward = self.compute_reward(observation['achieved_goal'], self.goal, info)
-        return observation, reward, False, info
+        return self._stepped()
 
 
 # the workspace of the pick-and-place environments (synthetic.PickPlaceGoalEnv, device_env.PickPlaceVecEnv, PickPlaceEnvDev in
@@ -224,7 +231,13 @@ PICK_RESET_BOUNDS = ((0.15, 0.35), (0.2, 0.5), (0.0, 0.35), (0.3, 0.55), (0.3, 0
 PICK_RESET_ATTEMPTS = 100
 
 
-class PickPlaceGoalEnv:
+def pick_separated(env, bx, by, gx, gy, gz):
+    """Whether one attempt of the pick-and-place's reset stands: the block on the table and the target `env.min_separation` apart"""
+    ddx, ddy, ddz = bx - gx, by - gy, env.table_z - gz
+    return np.sqrt(ddx * ddx + ddy * ddy + ddz * ddz) >= env.min_separation
+
+
+class PickPlaceGoalEnv(_HostGoalEnv):
     """A kinematic pick-and-place with the GoalEnv surface of `PushBlockGoalEnv`: the setting of the reference's PickAndPlace task
     (bmirobot_env_pickandplace_v2.py), in which the goal hangs in the air and the block gets there only in a closed hand.  The
     block is a cube of half width `half_width`; the finger pads sit at grip + PICK_TOOL.  The first three action components move
@@ -240,21 +253,14 @@ class PickPlaceGoalEnv:
 
     def __init__(self, seed=0, max_timesteps=100, distance_threshold=0.05, reward_type='sparse', step_scale=0.2, half_width=0.04,
                  finger_scale=0.05, min_separation=0.15, table_z=0.2, grip_start=(0.25, 0.1)):
-        self.rs = np.random.RandomState(seed)
-        self.max_timesteps = int(max_timesteps)
-        self.distance_threshold = float(distance_threshold)
-        self.reward_type = reward_type
-        self.step_scale, self.half_width, self.finger_scale = float(step_scale), float(half_width), float(finger_scale)
+        super().__init__(seed, max_timesteps, distance_threshold, reward_type, step_scale)
+        self.half_width, self.finger_scale = float(half_width), float(finger_scale)
         self.min_separation, self.table_z = float(min_separation), float(table_z)
         self.grip_start = (float(grip_start[0]), float(grip_start[1]))
         self.grip, self.blk, self.goal = np.zeros(3), np.zeros(3), np.zeros(3)
         self.gvel, self.bvel = np.zeros(3), np.zeros(3)
         self.finger, self.held = 0.0, 0.0    # the opening of the fingers; 1.0 once the block is grasped
         self.reset_attempts = 0              # attempts the last reset took
-
-    @property
-    def env_params(self):
-        return {'obs': 27, 'goal': 3, 'action': 4, 'action_max': 0.5, 'max_timesteps': self.max_timesteps}
 
     def _observation(self):
         obs = np.zeros(27)                   # the bmirobot layout: nine blocks of three
@@ -268,21 +274,14 @@ class PickPlaceGoalEnv:
         return {'observation': obs, 'achieved_goal': self.blk.copy(), 'desired_goal': self.goal.copy()}
 
     def reset(self):
-        for attempt in range(PICK_RESET_ATTEMPTS):
-            bx, by, gx, gy, gz = (self.rs.uniform(low, high) for low, high in PICK_RESET_BOUNDS)
-            ddx, ddy, ddz = bx - gx, by - gy, self.table_z - gz
-            if np.sqrt(ddx * ddx + ddy * ddy + ddz * ddz) >= self.min_separation:
-                break
-        self.reset_attempts = attempt + 1
+        (bx, by, gx, gy, gz), self.reset_attempts = rejection_reset(self.rs, PICK_RESET_BOUNDS, PICK_RESET_ATTEMPTS,
+                                                                     lambda *u: pick_separated(self, *u))
         self.blk = np.array([bx, by, self.table_z])
         self.goal = np.array([gx, gy, gz])
         self.grip = np.array([self.grip_start[0], self.grip_start[1], PICK_START_Z])
         self.gvel, self.bvel = np.zeros(3), np.zeros(3)
         self.finger, self.held = 0.0, 0.0
         return self._observation()
-
-    compute_reward = PushBlockGoalEnv.compute_reward
-    _is_success = PushBlockGoalEnv._is_success
 
     def _pads_inside(self):
         """Every finger pad coordinate is less than half_width from the block centre"""
@@ -305,13 +304,16 @@ class PickPlaceGoalEnv:
         elif self._pads_inside() and f_old > PICK_GRASP_WIDTH and self.finger <= PICK_GRASP_WIDTH:
             self.held = 1.0                                   # grasped; the block moves from the next step on
         self.bvel = self.blk - old
-        observation = self._observation()
-        info = {'is_success': self._is_success(observation['achieved_goal'], self.goal)}
-        reward = self.compute_reward(observation['achieved_goal'], self.goal, info)
-        return observation, reward, False, info
+        return self._stepped()
 
 
 # ---- demonstrations from a scripted controller (the reference's get_demo_data_push.py) ------------------------------------------
+def _check_phase_ends(name, phase_end):
+    """The rule of both schedules: the first phase end is not negative and every later one lies behind the one before it"""
+    if phase_end[0] < 0 or any(b <= a for a, b in zip(phase_end, phase_end[1:])):
+        raise ValueError(f"{name}: the phase ends {phase_end} must be increasing")
+
+
 class DemoScript:
     """The numbers of the reference's push schedule (get_demo_data_push.py:39-61); the defaults are the reference's.
     `phase_end`: the last timestep, counted from 1, of phases one to five (:43, :45, :49, :51, :53; the sixth runs to T);
@@ -327,8 +329,7 @@ class DemoScript:
         self.behind, self.stop_radius = float(behind), float(stop_radius)
         if len(self.phase_end) != 5 or len(self.lift) != 4 or len(self.waypoint) != 3:
             raise ValueError("DemoScript: five phase ends, four lift components, three waypoint components")
-        if self.phase_end[0] < 0 or any(b <= a for a, b in zip(self.phase_end, self.phase_end[1:])):
-            raise ValueError(f"DemoScript: the phase ends {self.phase_end} must be increasing")
+        _check_phase_ends("DemoScript", self.phase_end)
 
 
 def scripted_action(t, obs, g, script=None):
@@ -374,8 +375,7 @@ class PickScript:
         self.open = float(open)
         if len(self.phase_end) != 5 or len(self.lift) != 4 or len(self.approach) != 3 or len(self.grasp) != 3:
             raise ValueError("PickScript: five phase ends, four lift components, three approach and three grasp components")
-        if self.phase_end[0] < 0 or any(b <= a for a, b in zip(self.phase_end, self.phase_end[1:])):
-            raise ValueError(f"PickScript: the phase ends {self.phase_end} must be increasing")
+        _check_phase_ends("PickScript", self.phase_end)
 
 
 def pick_scripted_action(t, obs, g, script=None):

@@ -5,12 +5,11 @@ loop against plain Python accumulation, the ABI's new entries, and the static fi
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 
 from conftest import GOLDEN, REPO, bits, load_golden
+from kernel_metadata import kernel_metadata
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd.synthetic import (EPISODE_STATS, EPISODE_SUMMARY, DemoScript, PointMassGoalEnv, episode_stats,
                                                       episode_stats_summary, scripted_demos)
@@ -128,33 +127,10 @@ def test_header_ctypes_table_and_exports_carry_the_new_entries():
     assert Args().eval_metrics is False
 
 
-def _kernel_metadata(tmp_path, unit):
-    """The kernels of one unit of csrc/, compiled as the Makefile compiles it: name -> the figures of its metadata"""
-    csrc = os.path.join(REPO, "rl_arm_under_sparse_reward_amd", "csrc")
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    assert unit in re.search(r"^EXACT_SRCS := (.*)$", mk, flags=re.M).group(1).split()
-    hipcc = re.search(r"^HIPCC \?= (\S+)", mk, flags=re.M).group(1)
-    if not os.path.exists(hipcc):
-        hipcc = shutil.which("hipcc")
-    assert hipcc, "hipcc is needed to build the library at all"
-    common = re.search(r"^COMMON := (.*)$", mk, flags=re.M).group(1)
-    exact = re.search(r"^EXACT := (.*)$", mk, flags=re.M).group(1)
-    flags = common.replace("$(ARCH)", "gfx950").replace("$(INC)", f"-I{os.path.join(REPO, 'include')} -I{csrc}").split()
-    out = tmp_path / (unit + ".s")
-    subprocess.check_call([hipcc, *flags, *exact.split(), "--cuda-device-only", "-S", os.path.join(csrc, unit), "-o", str(out)])
-    meta = {}
-    for block in out.read_text().split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", block).group(1))
-                      for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count",
-                                "vgpr_count", "sgpr_count")}
-    return meta
-
-
 def test_the_two_kernels_use_no_scratch_and_no_lds(tmp_path):
     """Exactly two kernels in the unit; private_segment_fixed_size 0, no spilled register, LDS under 1 KB (none at all: the
     reductions cross the wave through ds_swizzle and readlane).  The figures are DESIGN 3.7's."""
-    meta = _kernel_metadata(tmp_path, "episode_stats.hip")
+    meta = kernel_metadata(tmp_path, "episode_stats.hip")
     print(meta)
     assert len(meta) == 2, sorted(meta)
     assert all("k_episode_stats" in n for n in meta) and sum("k_episode_stats_summary" in n for n in meta) == 1, sorted(meta)

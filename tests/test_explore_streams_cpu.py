@@ -2,13 +2,12 @@
 verify on synthetic arrays), the default of the switch, the ABI table, and the draw kernel's device assembly (no scratch)."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import REPO
+from kernel_metadata import kernel_metadata
 from rl_arm_under_sparse_reward_amd import train_state as ts
 from rl_arm_under_sparse_reward_amd.arguments import Args
 from test_train_state_cpu import synthetic_state
@@ -109,23 +108,7 @@ def test_ctypes_table_binds_the_stream_entry_points():
 def test_the_stream_step_kernel_uses_no_scratch(tmp_path):
     """The device assembly of csrc/rollout.hip, compiled as the Makefile compiles it: k_rollout_step_streams (and the
     single-stream kernel beside it) have private_segment_fixed_size 0, and one workgroup's LDS lets 16 of them share a CU."""
-    csrc = os.path.join(REPO, "rl_arm_under_sparse_reward_amd", "csrc")
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    hipcc = re.search(r"^HIPCC \?= (\S+)", mk, flags=re.M).group(1)
-    if not os.path.exists(hipcc):
-        hipcc = shutil.which("hipcc")
-    assert hipcc, "hipcc is needed to build the library at all"
-    common = re.search(r"^COMMON := (.*)$", mk, flags=re.M).group(1)
-    exact = re.search(r"^EXACT := (.*)$", mk, flags=re.M).group(1)
-    assert "-ffp-contract=off" in exact and "rollout.hip" in re.search(r"^EXACT_SRCS := (.*)$", mk, flags=re.M).group(1)
-    flags = common.replace("$(ARCH)", "gfx950").replace("$(INC)", f"-I{os.path.join(REPO, 'include')} -I{csrc}").split()
-    out = tmp_path / "rollout.s"
-    subprocess.check_call([hipcc, *flags, *exact.split(), "--cuda-device-only", "-S", os.path.join(csrc, "rollout.hip"), "-o", str(out)])
-    asm = out.read_text()
-    meta = {}
-    for block in asm.split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", block).group(1)) for k in ("private_segment_fixed_size", "group_segment_fixed_size")}
+    meta = kernel_metadata(tmp_path, "rollout.hip")
     streams = [k for k in meta if "k_rollout_step_streams" in k]
     assert len(streams) == 1 and any("k_rollout_step" in k and "streams" not in k for k in meta), sorted(meta)
     for k, m in meta.items():

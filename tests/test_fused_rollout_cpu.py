@@ -3,13 +3,12 @@
 fused kernel's device assembly (no scratch, LDS within a CU's)."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import torch
 
 from conftest import REPO, bits
+from kernel_metadata import kernel_metadata
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd.device_env import NativePointMassVecEnv, PointMassVecEnv, fused_rollout_reason
 
@@ -64,22 +63,7 @@ def test_the_fused_kernel_uses_no_scratch(tmp_path):
     """The device assembly of csrc/env_point_mass.hip (the unit that instantiates the point mass's kernels), compiled as the Makefile
     compiles it: k_rollout_episodes has
     private_segment_fixed_size 0 and no spilled vector register, and its LDS fits the 160 KiB of a CU."""
-    csrc = os.path.join(REPO, "rl_arm_under_sparse_reward_amd", "csrc")
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    hipcc = re.search(r"^HIPCC \?= (\S+)", mk, flags=re.M).group(1)
-    if not os.path.exists(hipcc):
-        hipcc = shutil.which("hipcc")
-    assert hipcc, "hipcc is needed to build the library at all"
-    common = re.search(r"^COMMON := (.*)$", mk, flags=re.M).group(1)
-    exact = re.search(r"^EXACT := (.*)$", mk, flags=re.M).group(1)
-    flags = common.replace("$(ARCH)", "gfx950").replace("$(INC)", f"-I{os.path.join(REPO, 'include')} -I{csrc}").split()
-    out = tmp_path / "env_point_mass.s"
-    subprocess.check_call([hipcc, *flags, *exact.split(), "--cuda-device-only", "-S", os.path.join(csrc, "env_point_mass.hip"), "-o", str(out)])
-    meta = {}
-    for block in out.read_text().split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", block).group(1))
-                      for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count")}
+    meta = kernel_metadata(tmp_path, "env_point_mass.hip")
     fused = [k for k in meta if "k_rollout_episodes" in k]
     assert len(fused) == 1 and "PointMassEnvDev" in fused[0], sorted(meta)
     m = meta[fused[0]]

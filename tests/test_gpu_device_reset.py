@@ -15,7 +15,7 @@ from rl_arm_under_sparse_reward_amd import train_state as ts
 from rl_arm_under_sparse_reward_amd.arguments import Args
 from rl_arm_under_sparse_reward_amd.ddpg_agent import NET_ACTOR, NET_CRITIC, ddpg_agent
 from rl_arm_under_sparse_reward_amd.device_env import (DeviceEpisodes, NativePointMassVecEnv, NativePushBlockVecEnv, PointMassVecEnv,
-                                                       binomial1_qn)
+                                                       binomial1_qn, script_desc)
 from rl_arm_under_sparse_reward_amd.random import DeviceRandomStreams
 from test_gpu_device_rollout import make, primed
 from test_gpu_explore_streams import assert_states_bit_equal
@@ -375,3 +375,65 @@ def test_the_row_of_a_kind_refuses_on_the_host(cls):
     waves(agent, eps, desc())                                                                               # ... and a good call does
     assert launches.value == 1
     assert not all(np.array_equal(bits(x), bits(y)) for x, y in zip(arrays, snapshot()[1]))
+
+
+def test_the_shared_descriptor_check_keeps_every_entrys_order():
+    """Two faults in one call, for every entry that reads a descriptor: the refusal is the one the first failing check gives, in
+    the order every entry has had -- the kind's row first, then the state arrays, then the block's dimensions.  An unknown kind
+    with a null state_dev[0] is refused for the kind; a null state_dev[0] with a block of other dimensions is refused for the
+    array (hp_env_reset takes no block: there the array is the only fault).  4 environments, T = 4; everything is refused on the
+    host: nothing is launched, and the environments keep their bytes."""
+    T, n = 4, 4
+    torch.manual_seed(0)
+    agent = make(NativePushBlockVecEnv(n, seed=10, device=DEV, max_timesteps=T), T=T, noise_eps=0.05)
+    primed(agent)
+    agent.enable_explore_streams(base_seed=900)
+    env = agent.vec_env
+    env.enable_device_reset(agent.ctx)
+    env.reset()
+    eps = DeviceEpisodes(agent.ctx, agent.buffer._dev, n)
+    torch.manual_seed(0)
+    small = ddpg_agent(Args(batch_size=256, buffer_size=200), None,
+                       {'obs': 10, 'goal': 2, 'action': 3, 'action_max': 0.5, 'max_timesteps': T}, ctx=agent.ctx, rng=fresh_rng(3))
+    other = DeviceEpisodes(small.ctx, small.buffer._dev, n)
+    success = torch.zeros(n, dtype=torch.float32, device=DEV)
+    step_success = torch.zeros((n, T), dtype=torch.float32, device=DEV)
+    launches, lib, ctx = C.c_int32(-1), agent.lib, agent.ctx
+    script = script_desc()
+    qn = binomial1_qn(0.3)[0]
+
+    def episodes(a, block, d):
+        _lib.check(lib.hp_rollout_begin(block.h, 0, n))
+        _lib.check(lib.hp_rollout_episodes(block.h, a.h, a.o_norm.h, a.g_norm.h, agent.explore_streams.h, C.byref(d), 1, 0.05, 0.3, qn,
+                                           0.0, p(success)))
+
+    def waves(a, block, d):
+        _lib.check(lib.hp_rollout_begin(block.h, 0, n))
+        _lib.check(lib.hp_rollout_waves(block.h, a.h, a.o_norm.h, a.g_norm.h, agent.explore_streams.h, env.reset_streams.h, C.byref(d),
+                                        n, 1, 0.05, 0.3, qn, 0.0, p(success), C.byref(launches)))
+
+    def demos(a, block, d):
+        _lib.check(lib.hp_demo_episodes(ctx.h, C.byref(d), env.reset_streams.h, C.byref(script), n, 0, n, T, block.h, p(success),
+                                        p(step_success), C.byref(launches)))
+
+    def reset(a, block, d):
+        _lib.check(lib.hp_env_reset(ctx.h, C.byref(d), env.reset_streams.h, n))
+
+    def desc(kind=None):
+        d = env.env_desc()
+        d.state_dev[0] = None
+        if kind is not None:
+            d.kind = kind
+        return d
+
+    before = [getattr(env, name).clone() for name in env.state_names], env.reset_streams.get_arrays()
+    with ctx.torch_bridge():
+        for entry, call in (("hp_rollout_episodes", episodes), ("hp_rollout_waves", waves), ("hp_demo_episodes", demos),
+                            ("hp_env_reset", reset)):
+            with pytest.raises(ValueError, match=rf"^{entry}: env->kind 99 is not an environment kind of this build$"):
+                call(agent, eps, desc(kind=99))
+            with pytest.raises(ValueError, match=rf"^{entry}: env->state_dev\[0\] is null$"):
+                call(small, other, desc())
+    assert launches.value == -1
+    assert all(torch.equal(x, getattr(env, name)) for x, name in zip(before[0], env.state_names))
+    assert all(np.array_equal(bits(x), bits(y)) for x, y in zip(before[1], env.reset_streams.get_arrays()))

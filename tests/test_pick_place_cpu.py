@@ -5,14 +5,13 @@ expressions, what the controller achieves, and the pinned constants of header an
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from conftest import bits
+from kernel_metadata import kernel_metadata
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd.device_env import (NativePickPlaceVecEnv, NativePointMassVecEnv, NativePushBlockVecEnv, PickPlaceVecEnv,
                                                        fused_rollout_reason, script_desc)
@@ -339,22 +338,7 @@ def test_the_kind_is_a_struct_and_a_row():
 def test_the_demo_kernel_of_the_kind_is_one_kernel_without_scratch(tmp_path):
     """csrc/demo_pick_place.hip compiled as the Makefile compiles it: the second controller is a value of the argument block,
     so the unit still holds one kernel; no scratch, no spill, the ring and one row of LDS."""
-    csrc = os.path.join(REPO, "rl_arm_under_sparse_reward_amd", "csrc")
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    hipcc = re.search(r"^HIPCC \?= (\S+)", mk, flags=re.M).group(1)
-    if not os.path.exists(hipcc):
-        hipcc = shutil.which("hipcc")
-    assert hipcc, "hipcc is needed to build the library at all"
-    common = re.search(r"^COMMON := (.*)$", mk, flags=re.M).group(1)
-    exact = re.search(r"^EXACT := (.*)$", mk, flags=re.M).group(1)
-    flags = common.replace("$(ARCH)", "gfx950").replace("$(INC)", f"-I{os.path.join(REPO, 'include')} -I{csrc}").split()
-    out = tmp_path / "demo_pick_place.s"
-    subprocess.check_call([hipcc, *flags, *exact.split(), "--cuda-device-only", "-S", os.path.join(csrc, "demo_pick_place.hip"), "-o", str(out)])
-    meta = {}
-    for block in out.read_text().split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", block).group(1))
-                      for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count")}
+    meta = kernel_metadata(tmp_path, "demo_pick_place.hip")
     assert len(meta) == 1, sorted(meta)
     (name, m), = meta.items()
     print(name, m)

@@ -4,14 +4,13 @@ of `reset` counted through the stream position, the pinned constants of header a
 translation unit that instantiates the kernels for the kind (csrc/env_push_block.hip)."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from conftest import REPO, bits
+from kernel_metadata import kernel_metadata
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd.device_env import NativePushBlockVecEnv, PushBlockVecEnv, fused_rollout_reason
 from rl_arm_under_sparse_reward_amd.synthetic import (PUSH_RESET_BOUNDS, PUSH_START_Z, PUSH_X_HI, PUSH_X_LO, PUSH_Y_HI, PUSH_Y_LO,
@@ -251,22 +250,7 @@ def test_the_push_block_kernels_use_no_scratch(tmp_path):
     """The device assembly of csrc/env_push_block.hip, compiled as the Makefile compiles it: the one push-block instantiation of
     each kernel, private_segment_fixed_size 0, no spilled vector register, LDS within the 160 KiB of a CU."""
     csrc = os.path.join(REPO, "rl_arm_under_sparse_reward_amd", "csrc")
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    assert "env_push_block.hip" in re.search(r"^EXACT_SRCS := (.*)$", mk, flags=re.M).group(1).split()
-    hipcc = re.search(r"^HIPCC \?= (\S+)", mk, flags=re.M).group(1)
-    if not os.path.exists(hipcc):
-        hipcc = shutil.which("hipcc")
-    assert hipcc, "hipcc is needed to build the library at all"
-    common = re.search(r"^COMMON := (.*)$", mk, flags=re.M).group(1)
-    exact = re.search(r"^EXACT := (.*)$", mk, flags=re.M).group(1)
-    flags = common.replace("$(ARCH)", "gfx950").replace("$(INC)", f"-I{os.path.join(REPO, 'include')} -I{csrc}").split()
-    out = tmp_path / "env_push_block.s"
-    subprocess.check_call([hipcc, *flags, *exact.split(), "--cuda-device-only", "-S", os.path.join(csrc, "env_push_block.hip"), "-o", str(out)])
-    meta = {}
-    for block in out.read_text().split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", block).group(1))
-                      for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count")}
+    meta = kernel_metadata(tmp_path, "env_push_block.hip")
     fused, reset = [k for k in meta if "k_rollout_episodes" in k], [k for k in meta if "k_env_reset" in k]
     assert len(meta) == 2 and len(fused) == 1 and len(reset) == 1 and all("PushBlockEnvDev" in k for k in meta), sorted(meta)
     for name in (fused[0], reset[0]):

@@ -9,14 +9,13 @@ import json
 import math
 import os
 import re
-import shutil
-import subprocess
 import types
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, REPO, bits
+from kernel_metadata import kernel_metadata
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd.synthetic import (DemoScript, PointMassGoalEnv, PushBlockGoalEnv, scripted_action,
                                                       scripted_demos, scripted_episode, write_demo_npz_from)
@@ -203,35 +202,13 @@ def test_generate_demos_refuses_an_environment_it_cannot_run():
         generate_demos(NativePushBlockVecEnv(2, device="cpu"), 1)
 
 
-def _kernel_metadata(tmp_path, unit):
-    """The kernels of one unit of csrc/, compiled as the Makefile compiles it: name -> the figures of its metadata"""
-    csrc = os.path.join(REPO, "rl_arm_under_sparse_reward_amd", "csrc")
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    assert unit in re.search(r"^EXACT_SRCS := (.*)$", mk, flags=re.M).group(1).split()
-    hipcc = re.search(r"^HIPCC \?= (\S+)", mk, flags=re.M).group(1)
-    if not os.path.exists(hipcc):
-        hipcc = shutil.which("hipcc")
-    assert hipcc, "hipcc is needed to build the library at all"
-    common = re.search(r"^COMMON := (.*)$", mk, flags=re.M).group(1)
-    exact = re.search(r"^EXACT := (.*)$", mk, flags=re.M).group(1)
-    flags = common.replace("$(ARCH)", "gfx950").replace("$(INC)", f"-I{os.path.join(REPO, 'include')} -I{csrc}").split()
-    out = tmp_path / (unit + ".s")
-    subprocess.check_call([hipcc, *flags, *exact.split(), "--cuda-device-only", "-S", os.path.join(csrc, unit), "-o", str(out)])
-    meta = {}
-    for block in out.read_text().split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", block).group(1))
-                      for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count", "vgpr_count", "sgpr_count")}
-    return meta
-
-
 @pytest.mark.parametrize("unit, kernel, kind", [("demo_push_block.hip", "k_demo_episodes", "PushBlockEnvDev"),
                                                 ("demo_point_mass.hip", "k_demo_episodes", "PointMassEnvDev"),
                                                 ("demo_compact.hip", "k_demo_compact", "")])
 def test_the_new_kernels_use_no_scratch(tmp_path, unit, kernel, kind):
     """private_segment_fixed_size 0 and no spilled vector register for both new kernels; k_demo_episodes keeps about the reset
     kernel's LDS (the ring) plus one row, so a CU's workgroups are bounded by its wave slots."""
-    meta = _kernel_metadata(tmp_path, unit)
+    meta = kernel_metadata(tmp_path, unit)
     assert len(meta) == 1, sorted(meta)
     (name, m), = meta.items()
     print(name, m)
