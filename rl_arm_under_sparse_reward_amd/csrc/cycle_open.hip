@@ -29,7 +29,8 @@
 #include "agent.h"
 
 #define OPEN_THREADS NORM_THREADS
-#define OPEN_PARTS 2   // workgroups per staged episode (2 x 1024 threads: the 8 x 256 of k_store_scatter)
+#define OPEN_PARTS STAGE_WG_PER_EPISODE   // workgroups per staged episode (2 x 1024 threads: the 8 x 256 of k_store_scatter)
+static_assert(OPEN_THREADS == STAGE_WG_THREADS, "stage_block_direct_fits counts the scatter threads of this launch");
 static_assert(MT_THREADS == 2 * NORM_MAX, "the draw and the normalizer columns use the same 512 threads");
 
 struct OpenArgs {
@@ -183,10 +184,8 @@ bool cycle_open_fits(const hp_agent *a, int64_t n_new) {
 // Can the scatter workgroups take the staged batch from the pinned ring themselves?  Every thread keeps its chunks in registers
 // across the wait for the slots, and the winners' table lies in the launch's LDS (at least the draw's 4 x 624 words).
 bool cycle_open_direct_fits(const hp_buffer *b, int64_t n_new) {
-    const uint64_t nd = (uint64_t)n_new * (b->ep_obs() + b->ep_ag() + b->ep_g() + b->ep_act());
-    const uint64_t threads = (uint64_t)OPEN_PARTS * n_new * OPEN_THREADS;
-    return nd < (1ull << 31) && (nd + 1) / 2 <= STORE_DIRECT_CHUNKS * threads &&
-           (uint64_t)n_new * 2 * sizeof(long long) <= 4 * MT_N * sizeof(uint32_t);
+    const uint64_t ep = (uint64_t)(b->ep_obs() + b->ep_ag() + b->ep_g() + b->ep_act());
+    return stage_block_direct_fits(ep, n_new, 4 * MT_N * sizeof(uint32_t));
 }
 
 // The staged episodes of `b` (buffer_stage) -> slots, scatter, normalizer update, first `n_first` minibatch plans.
@@ -232,14 +231,7 @@ int cycle_open_launch(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rn
     A.chunk_rows = norm_plan_chunk(b->obs_dim, b->goal_dim, b->T, &norm_bytes);
     A.sync = a->open_sync;
     A.pin = b->ring_cur >= 0 ? static_cast<const double *>(b->ring.slot[b->ring_cur].dev) : nullptr;
-    A.blk.n_obs = (unsigned)(A.inc * A.ep_obs);
-    A.blk.n_ag = (unsigned)(A.inc * A.ep_ag);
-    A.blk.n_g = (unsigned)(A.inc * A.ep_g);
-    A.blk.ep_obs = (unsigned)A.ep_obs;
-    A.blk.ep_ag = (unsigned)A.ep_ag;
-    A.blk.ep_g = (unsigned)A.ep_g;
-    A.blk.ep_act = (unsigned)A.ep_act;
-    A.blk.nd = (unsigned)(A.inc * (A.ep_obs + A.ep_ag + A.ep_g + A.ep_act));
+    A.blk = stage_block_of(A.inc, A.ep_obs, A.ep_ag, A.ep_g, A.ep_act);
     A.dev = a->d_state;
     A.fault = a->k1_sync + SPLIT_FAULT;
     A.fault_host = a->fault_host_dev;

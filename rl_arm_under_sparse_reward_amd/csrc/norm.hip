@@ -115,12 +115,8 @@ __global__ void k_norm_set(NormDev *nz, const float *mean, const double *std, in
 // ------------------------------------------------------------------------------ launchers
 int norm_launch_update_from_plan(hp_norm *o, hp_norm *g, hp_buffer *b, const PlanRec *d_plan, int64_t rows,
                                  double clip_obs, bool recompute) {
-    // rows per chunk: what 48 KB of LDS hold (plan record + one float64 per column and row), at most 256
-    const int W = b->obs_dim + b->goal_dim;
-    int chunk = (int)((48 * 1024) / (sizeof(PlanRec) + (size_t)W * 8));
-    chunk = chunk > 256 ? 256 : chunk;
-    chunk = rows < chunk ? (int)rows : chunk;
-    const size_t lds = (size_t)chunk * (sizeof(PlanRec) + (size_t)W * 8);
+    size_t lds = 0;
+    const int chunk = norm_plan_chunk(b->obs_dim, b->goal_dim, rows, &lds);
     HP_KLOG("k_norm_update_from_plan");
     hipLaunchKernelGGL(k_norm_update_from_plan, dim3(1), dim3(NORM_THREADS), lds, o->ctx->stream, o->d, g->d, d_plan,
                        (long long)rows, b->st_obs.as<double>(), b->st_ag, b->st_g, (int)b->T,

@@ -2,6 +2,7 @@
 // (cycle_open.hip).  Arithmetic contract: norm.hip's header.
 #pragma once
 #include "internal.h"
+#include "stage_block.h"
 
 __device__ __forceinline__ double clipd(double v, double lo, double hi) {
     // np.clip == minimum(maximum(v, lo), hi)
@@ -120,12 +121,5 @@ __device__ __forceinline__ void norm_update_from_plan_body(
     }
 }
 
-// LDS rows per chunk of norm_update_from_plan_body and the bytes they take
-inline int norm_plan_chunk(int obs_dim, int goal_dim, long long rows, size_t *lds_bytes) {
-    const int W = obs_dim + goal_dim;
-    int chunk = (int)((48 * 1024) / (sizeof(PlanRec) + (size_t)W * 8));
-    chunk = chunk > 256 ? 256 : chunk;
-    chunk = rows < chunk ? (int)rows : chunk;
-    *lds_bytes = (size_t)chunk * (sizeof(PlanRec) + (size_t)W * 8);
-    return chunk;
-}
+// LDS rows per chunk and the bytes they take: norm_plan_chunk (stage_block.h)
+static_assert(sizeof(PlanRec) == NORM_PLAN_REC_BYTES, "norm_plan_chunk sizes the LDS by the plan record");

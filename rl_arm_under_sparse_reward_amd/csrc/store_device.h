@@ -2,6 +2,7 @@
 // k_store_scatter and the cycle-opening kernel (cycle_open.hip).
 #pragma once
 #include "internal.h"
+#include "stage_block.h"
 
 // Episode i of the staged batch goes to slot slots[i] unless a LATER staged episode has the same slot (numpy's
 // `buffers[idxs] = mb` lets the last occurrence win).  One of `parts` workgroups per episode copies a strided share of its
@@ -31,27 +32,21 @@ __device__ __forceinline__ void store_scatter_share(SlotOf slot_of, long long i,
 // obs | ag | g | actions back to back like the device staging, `nd` doubles in all.  The block is cut into 16-byte chunks, chunk c
 // belonging to thread c mod `nthreads` of the scatter workgroups together; a thread holds at most STORE_DIRECT_CHUNKS of them in
 // registers (cycle_open_direct_fits).  The block's base is page aligned, so every chunk load is; only the LAST chunk of a block
-// with an odd number of doubles is half a chunk, loaded as 8 bytes -- nothing is read past the block.
-#define STORE_DIRECT_CHUNKS 4
-
-struct StageBlock {   // the four arrays of a staged batch as one run of doubles
-    unsigned n_obs, n_ag, n_g;           // doubles of the first three arrays (n_new episodes each)
-    unsigned ep_obs, ep_ag, ep_g, ep_act;
-    unsigned nd;
-};
+// with an odd number of doubles is half a chunk, loaded as 8 bytes -- nothing is read past the block.  Which chunk is whose, what
+// of it lies in the block and where a double of the block goes: stage_block.h (StageBlock, STORE_DIRECT_CHUNKS).
 
 // all of a thread's loads, issued back to back before anything waits for them (one PCIe round trip)
 __device__ __forceinline__ void stage_block_load(const double *__restrict__ blk, unsigned nd, unsigned gtid, unsigned nthreads,
                                                  double (&v)[STORE_DIRECT_CHUNKS][2]) {
 #pragma unroll
     for (int it = 0; it < STORE_DIRECT_CHUNKS; ++it) {
-        const unsigned d = 2u * (gtid + (unsigned)it * nthreads);
+        const unsigned d = stage_chunk_first(gtid, it, nthreads), m = stage_chunk_doubles(d, nd);
         v[it][0] = v[it][1] = 0.0;
-        if (d + 1u < nd) {
+        if (m == 2u) {
             const double2 x = *reinterpret_cast<const double2 *>(blk + d);
             v[it][0] = x.x;
             v[it][1] = x.y;
-        } else if (d < nd) {
+        } else if (m == 1u) {
             v[it][0] = blk[d];
         }
     }
@@ -63,10 +58,10 @@ __device__ __forceinline__ void stage_block_put(double *stage, unsigned nd, unsi
                                                 const double (&v)[STORE_DIRECT_CHUNKS][2]) {
 #pragma unroll
     for (int it = 0; it < STORE_DIRECT_CHUNKS; ++it) {
-        const unsigned d = 2u * (gtid + (unsigned)it * nthreads);
+        const unsigned d = stage_chunk_first(gtid, it, nthreads), m = stage_chunk_doubles(d, nd);
 #pragma unroll
         for (int h = 0; h < 2; ++h)
-            if (d + h < nd)
+            if ((unsigned)h < m)
                 __hip_atomic_store(reinterpret_cast<long long *>(stage) + d + h, __double_as_longlong(v[it][h]), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -79,19 +74,14 @@ __device__ __forceinline__ void stage_block_scatter(const StageBlock &L, const l
                                                     double *act) {
 #pragma unroll
     for (int it = 0; it < STORE_DIRECT_CHUNKS; ++it) {
+        const unsigned d = stage_chunk_first(gtid, it, nthreads), m = stage_chunk_doubles(d, L.nd);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const unsigned d = 2u * (gtid + (unsigned)it * nthreads) + h;
-            if (d >= L.nd) continue;
-            unsigned r = d, len;
-            double *arr;
-            if (r < L.n_obs) { arr = obs; len = L.ep_obs; }
-            else if ((r -= L.n_obs) < L.n_ag) { arr = ag; len = L.ep_ag; }
-            else if ((r -= L.n_ag) < L.n_g) { arr = g; len = L.ep_g; }
-            else { r -= L.n_g; arr = act; len = L.ep_act; }
-            const unsigned e = r / len, k = r - e * len;
-            const long long slot = win[e];
-            if (slot >= 0) arr[slot * (long long)len + k] = v[it][h];
+            if ((unsigned)h >= m) continue;
+            const StageLoc p = stage_block_locate(L, d + (unsigned)h);
+            double *arr = p.arr == 0u ? obs : p.arr == 1u ? ag : p.arr == 2u ? g : act;
+            const long long slot = win[p.e];
+            if (slot >= 0) arr[slot * (long long)p.len + p.k] = v[it][h];
         }
     }
 }

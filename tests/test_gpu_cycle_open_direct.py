@@ -18,7 +18,22 @@ Shapes: T = 100, obs 27 / goal 3 / action 4, batch 16, n_batches 2 unless a case
                  hp_buffer_debug_stage_info after every cycle: block size 1, 1, 2, 2, 3, 3 episodes, generation + 1 at each step up.
   odd            goal 3 / action 3.
   odd_total      T = 7, obs 5 / goal 2 / action 3: 91 doubles per episode, so with n_new = 1 and 3 the block ends in half a
-                 16-byte chunk (loaded as 8 bytes: nothing is read past the block)."""
+                 16-byte chunk (loaded as 8 bytes: nothing is read past the block).
+
+Shapes at which the launch's loops take further trips (every shape above takes one): a scatter thread of the direct form owns the
+16-byte chunks gtid + it * nthreads, it = 0 .. 3, of the block, 2 x 1024 threads per staged episode, so register trip `it` holds
+doubles [4096 it, 4096 (it + 1)) of every episode; the normalizer workgroup sums min(256, 49152 / (16 + 8 (obs + goal))) plan rows
+per LDS chunk.  TRIPS_AND_CHUNKS states what each case reaches and a test derives it from the shape.  These cases synchronise with
+the host after every cycle and are compared with the CPU oracle as well: both normalizers, buffer, slots and random stream.
+  wide60         obs 60 / goal 3 / action 7, n_new = 1, 2, 3, 2: 7363 doubles per episode (odd) -- register trips 0 and 1, the half
+                 chunk in trip 1 when n_new is odd; two normalizer chunks (94 + 6 rows).
+  wide130        130 / 5 / 6, n_new = 1, 3, 2: 14735 doubles -- all four register trips; three normalizer chunks (44 + 44 + 12).
+  long300        T = 300 at 27 / 3 / 4 (the slab engine's shape), n_new = 2, 1, 3: 11130 doubles -- trips 0 to 2; chunks 192 + 108,
+                 the first of them the launch's largest LDS request (49152 bytes).
+  last_fit       152 / 3 / 4, n_new = 1, 2: 16355 doubles, the widest observation that still fits the direct form (16384 doubles
+                 per episode is the limit, cycle_open_direct_fits); trip 3 is nearly full.  Normalizer chunks 39 + 39 + 22.
+  first_unfit    153 / 3 / 4, n_new = 1, 2: 16456 doubles do not fit, so the "direct" child takes the copy form by itself
+                 (ASSERTED: no ring block, no ring bytes) and still computes the oracle's bits.  Chunks 38 + 38 + 24."""
 import os
 import subprocess
 import sys
@@ -41,7 +56,22 @@ CASES = {
     "grow": (STD, [1, 1, 2, 2, 3, 1], False),
     "odd": (dict(STD, action=3), [2, 1, 3, 2], False),
     "odd_total": ({"obs": 5, "goal": 2, "action": 3, "action_max": 0.5, "max_timesteps": 7}, [1, 3, 1, 2, 3, 1], False),
+    "wide60": (dict(STD, obs=60, action=7), [1, 2, 3, 2], True),
+    "wide130": (dict(STD, obs=130, goal=5, action=6), [1, 3, 2], True),
+    "long300": (dict(STD, max_timesteps=300), [2, 1, 3], True),
+    "last_fit": (dict(STD, obs=152), [1, 2], True),
+    "first_unfit": (dict(STD, obs=153), [1, 2], True),
 }
+# name: (doubles per episode, register trips of the direct form one episode needs, plan rows of every normalizer chunk)
+TRIPS_AND_CHUNKS = {
+    "wide60": (7363, 2, (94, 6)),
+    "wide130": (14735, 4, (44, 44, 12)),
+    "long300": (11130, 3, (192, 108)),
+    "last_fit": (16355, 4, (39, 39, 22)),
+    "first_unfit": (16456, 5, (38, 38, 24)),
+}
+DIRECT_TRIPS = 4   # STORE_DIRECT_CHUNKS (csrc/stage_block.h): more trips than this do not fit the direct form
+ORACLE_CASES = ("n1", "n2", "n3") + tuple(TRIPS_AND_CHUNKS)
 
 
 def _episodes(case):
@@ -54,7 +84,7 @@ def _episodes(case):
 
 
 def _oracle(case):
-    """The same cycles on the CPU oracle: every cycle's slots, the final store."""
+    """The same cycles on the CPU oracle: every cycle's slots, the final store, both normalizers and the random stream."""
     sys.path.insert(0, REPO)
     from oracle.her_replay import EpisodeStore, future_probability
     from oracle.running_norm import RunningNorm, update_normalizers
@@ -71,7 +101,7 @@ def _oracle(case):
         update_normalizers(on, gn, eps, fp, rs)
         for _ in range(N_BATCHES):
             st.sample(BATCH, fp, rs)
-    return slots, st
+    return slots, st, on, gn, rs
 
 
 def _child(form, out_path):
@@ -166,7 +196,7 @@ def test_direct_form_gives_the_bits_of_the_copy_form(case, runs):
 
 @pytest.mark.parametrize("case", ["n1", "n2", "n3"])
 def test_slots_and_buffer_match_the_oracle_and_the_seed_collides(case, runs):
-    slots, st = _oracle(case)
+    slots, st = _oracle(case)[:2]
     n_news = CASES[case][1]
     if n_news[0] >= 2:   # the later-wins rule is exercised: two staged episodes of one cycle draw the same slot
         assert any(len(set(s.tolist())) < len(s) for s in slots[1:]), [s.tolist() for s in slots]
@@ -177,10 +207,61 @@ def test_slots_and_buffer_match_the_oracle_and_the_seed_collides(case, runs):
             assert _same_bits(runs[form][f"{case}/buf_{k}"], np.asarray(st.buffers[k], dtype=np.float64)), (form, k)
 
 
-def _episode_bytes(case):
+NORM_STATS = ("mean", "std", "total_sum", "total_sumsq", "total_count", "local_sum", "local_sumsq", "local_count")
+
+
+@pytest.mark.parametrize("case", ORACLE_CASES)
+def test_both_forms_give_the_oracles_normalizers_buffer_slots_and_stream(case, runs):
+    """The normalizer of the opening launch against the CPU oracle (not only direct against copy, the kernel against itself):
+    every statistic of both normalizers after the last cycle, with the buffer, every cycle's slots and the random stream."""
+    slots, st, on, gn, rs = _oracle(case)
+    n_news = CASES[case][1]
+    for form in ("direct", "copy"):
+        run = runs[form]
+        for tag, ref in (("o", on), ("g", gn)):
+            stats = sorted(k.rsplit("_norm_", 1)[1] for k in run.files if k.startswith(f"{case}/{tag}_norm_"))
+            assert stats == sorted(NORM_STATS), stats   # everything normalizer._get() returns
+            for nm in NORM_STATS:
+                assert _same_bits(run[f"{case}/{tag}_norm_{nm}"], np.asarray(getattr(ref, nm))), (form, tag, nm)
+        for k in ("obs", "ag", "g", "actions"):
+            assert _same_bits(run[f"{case}/buf_{k}"], np.asarray(st.buffers[k], dtype=np.float64)), (form, k)
+        for i in range(len(n_news)):
+            assert np.array_equal(run[f"{case}/slots{i}"], slots[1 + i]), (form, i)
+        key, pos = rs.get_state()[1:3]
+        assert np.array_equal(run[f"{case}/rng_key"], np.asarray(key, dtype=np.uint32)) and int(run[f"{case}/rng_pos"][0]) == int(pos), form
+
+
+def _episode_doubles(case):
     p = CASES[case][0]
     T = p["max_timesteps"]
-    return 8 * ((T + 1) * (p["obs"] + p["goal"]) + T * (p["goal"] + p["action"]))
+    return (T + 1) * (p["obs"] + p["goal"]) + T * (p["goal"] + p["action"])
+
+
+def _episode_bytes(case):
+    return 8 * _episode_doubles(case)
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_every_case_reaches_the_register_trip_and_chunk_count_it_claims(case):
+    """From the shapes' arithmetic alone: the old cases stay within register trip 0 and one normalizer chunk, the new ones reach
+    what TRIPS_AND_CHUNKS (and the docstring above) says -- a later change to a shape or to the LDS budget shows here."""
+    p = CASES[case][0]
+    T, D = p["max_timesteps"], _episode_doubles(case)
+    ceil_div = lambda a, b: -(-a // b)   # noqa: E731
+    trips = ceil_div(ceil_div(D, 2), 2048)   # 2048 chunks of 16 bytes per episode and trip
+    chunk = min(256, 49152 // (16 + 8 * (p["obs"] + p["goal"])))
+    n_chunks = ceil_div(T, chunk)
+    rows = (chunk,) * (n_chunks - 1) + (T - chunk * (n_chunks - 1),)
+    if case not in TRIPS_AND_CHUNKS:
+        assert trips == 1 and n_chunks == 1, (D, trips, rows)
+        return
+    assert (D, trips, rows) == TRIPS_AND_CHUNKS[case]
+    assert (trips <= DIRECT_TRIPS) == (case != "first_unfit")
+    assert D % 2 == 0 or any(n % 2 for n in CASES[case][1])   # where D is odd, an odd block (half a chunk at its end) occurs
+    assert n_chunks >= 2
+    # last_fit really is the widest observation that fits at this goal / action / T, first_unfit the next one
+    if case == "last_fit":
+        assert D + (T + 1) > DIRECT_TRIPS * 4096 >= D
 
 
 def test_the_ring_really_grows_rotates_and_moves_the_generation(runs):
@@ -189,6 +270,12 @@ def test_the_ring_really_grows_rotates_and_moves_the_generation(runs):
     for case in CASES:   # the copy form never touches the ring
         st = copy[f"stage:{case}"]
         assert np.all(st[:, 1] == 0) and np.all(st[:, 2] == -1), (case, st.tolist())
+    for case in TRIPS_AND_CHUNKS:
+        st = direct[f"stage:{case}"]
+        if case == "first_unfit":   # too long for the registers: the copy form by itself (its bits: the oracle test above)
+            assert np.all(st[:, 1] == 0) and np.all(st[:, 2] == -1), (case, st.tolist())
+        else:                       # every cycle, the fill's included, read its episodes from a ring block
+            assert np.all(st[:, 2] >= 0) and np.all(st[:, 1] == CAP * _episode_bytes(case)), (case, st.tolist())
     st, ep = direct["stage:grow"], _episode_bytes("grow")
     gen0 = int(st[0, 0])
     assert st[0, 1:].tolist() == [0, -1]                                     # the eager fill: no ring yet

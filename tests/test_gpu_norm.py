@@ -6,8 +6,8 @@ import pytest
 import torch
 
 from conftest import bits, load_golden
-from gpu_common import DeviceEpisodeBuffer, ctx, fresh_rng, state_equal
-from oracle.her_replay import future_probability
+from gpu_common import DeviceEpisodeBuffer, ctx, fresh_rng, make_shape_episodes, state_equal
+from oracle.her_replay import draw_her_indices, future_probability
 from oracle.running_norm import RunningNorm, update_normalizers
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd.normalizer import normalizer
@@ -106,6 +106,61 @@ def test_update_normalizer_from_staged_episodes_matches_oracle():
         _lib.check(buf.lib.hp_norm_update_from_staged(buf.h, dev.h, on.h, gn.h, fp, 200.0))
         on.recompute_stats(); gn.recompute_stats()
         update_normalizers(ron, rgn, eps, fp, rs)
+        for a, b in ((on, ron), (gn, rgn)):
+            for nm in NAMES:
+                assert np.array_equal(bits(getattr(a, nm)), bits(getattr(b, nm))), (cycle, nm)
+        assert state_equal(dev, *rs.get_state()[1:3])
+
+
+# (obs, goal, action, T), the rows of every LDS chunk of norm_update_from_plan_body, std dtype.  chunk = min(256, 49152 / (16 +
+# 8 (obs + goal))) rows (norm_plan_chunk, csrc/stage_block.h); every shape of the rest of the suite takes ONE chunk, like the first.
+MULTI_CHUNK = [
+    ((60, 3, 7, 94), (94,), None),             # one full chunk: the control
+    ((60, 3, 7, 95), (94, 1), None),           # last chunk of a single row
+    ((60, 3, 7, 100), (94, 6), None),          # short last chunk
+    ((60, 3, 7, 188), (94, 94), None),         # exact multiple: the loop ends without an empty trip
+    ((130, 5, 6, 100), (44, 44, 12), None),    # three chunks
+    ((10, 3, 4, 300), (256, 44), None),        # the 256-row cap, T above it
+    ((27, 3, 4, 300), (192, 108), None),       # 49152 bytes of dynamic LDS, the most this launch ever asks for
+    ((256, 256, 1, 30), (11, 11, 8), None),    # both normalizers at NORM_MAX: all 512 column threads live
+    ((60, 3, 7, 100), (94, 6), "float32"),
+]
+
+
+@pytest.mark.parametrize("shape,chunks,std_dtype", MULTI_CHUNK, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_update_normalizer_from_staged_episodes_at_multi_chunk_shapes(shape, chunks, std_dtype):
+    """The same update at episode shapes whose T plan rows do not fit one LDS chunk: the carry of the column sums across chunks,
+    the offset into the plan, a short (down to one row) last chunk and the 256-row cap.  A value beyond +-200 lies in a row of
+    the LAST chunk for each normalizer, so the clip runs there.  3 cycles of 2 fresh episodes, everything bit for bit."""
+    obs_dim, goal_dim, act_dim, T = shape
+    chunk = min(256, 49152 // (16 + 8 * (obs_dim + goal_dim)))
+    n_chunks = -(-T // chunk)
+    assert n_chunks == 1 if shape == MULTI_CHUNK[0][0] else n_chunks >= 2, (chunk, n_chunks)
+    assert chunks == (chunk,) * (n_chunks - 1) + (T - chunk * (n_chunks - 1),) and 0 < chunks[-1] <= chunk
+    fp = future_probability("future", 4)
+    dev = fresh_rng(125)
+    rs = np.random.RandomState(125)
+    buf = DeviceEpisodeBuffer(6, T, obs_dim, goal_dim, act_dim)
+    on = normalizer(obs_dim, default_clip_range=5, std_dtype=std_dtype)
+    gn = normalizer(goal_dim, default_clip_range=5, std_dtype=std_dtype)
+    ron = RunningNorm(obs_dim, default_clip_range=5, std_dtype=std_dtype)
+    rgn = RunningNorm(goal_dim, default_clip_range=5, std_dtype=std_dtype)
+    for cycle in range(3):
+        eps = make_shape_episodes(2, obs_dim, goal_dim, act_dim, T, seed=60 + cycle)
+        peek = np.random.RandomState()
+        peek.set_state(rs.get_state())
+        e, t, her, fut = draw_her_indices(peek, 2, T, T, fp)   # what the plan's last row will read (the draw is replayed below)
+        r = T - 1
+        eps[0][e[r], t[r], obs_dim - 1] = 1e4
+        if her[r]:
+            eps[1][e[r], fut[r], 0] = -1e4
+        else:
+            eps[2][e[r], t[r], 0] = -1e4
+        buf.store(dev, eps)
+        _lib.check(buf.lib.hp_norm_update_from_staged(buf.h, dev.h, on.h, gn.h, fp, 200.0))
+        on.recompute_stats(); gn.recompute_stats()
+        o, g = update_normalizers(ron, rgn, eps, fp, rs)
+        assert r >= chunk * (n_chunks - 1) and o[r, obs_dim - 1] == 200.0 and g[r, 0] == -200.0   # clipped, in the last chunk
         for a, b in ((on, ron), (gn, rgn)):
             for nm in NAMES:
                 assert np.array_equal(bits(getattr(a, nm)), bits(getattr(b, nm))), (cycle, nm)
