@@ -535,6 +535,50 @@ int hp_episode_stats_block(hp_rollout *ro, int64_t first_episode, int64_t n_epis
                            float *step_success_dev);
 int hp_episode_stats_summary(hp_ctx *ctx, const double *stats_dev, int64_t n_episodes, double *summary_dev);
 
+/* ---- critic audit on the device ----------------------------------------------------------------
+ * What the critic believes of an episode block beside what the episodes went on to collect: whether Q(s_t, a_t) tracks the
+ * discounted return, sits on the target clip -1 / (1 - gamma) (ddpg_agent.py:259-260) or overestimates.
+ *
+ * hp_episode_q: q_dev[e][t] (float32) = critic(normalise(obs[e][t] | g[e][t]), actions[e][t] / max_action) for t = 0 .. T-1 of
+ * n_episodes episodes in ONE launch.  obs_dev is [n_episodes][T + 1][obs_dim], g_dev [n_episodes][T][goal_dim], actions_dev
+ * [n_episodes][T][act_dim], float64 and contiguous: a block's own arrays.  net is HP_NET_CRITIC or HP_NET_CRITIC_TARGET.  A row
+ * enters the critic exactly as a transition enters an update: clip to +-clip_obs (<= 0: no clip), subtract the mean, divide by
+ * the std, clip to the normalizer's range, each in float64 and rounded once, then float32; the action narrowed to float32 and
+ * divided by max_action in float32.  The forward is the training chain's critic forward (same device functions, 4-row slabs), on
+ * the weights every update launch form leaves behind, in stream order.  hp_episode_q_block is the same on episodes
+ * [first_episode, first_episode + n_episodes) of a block.  Both asynchronous on the context's stream (or a borrowed one); nothing
+ * is allocated.  Refused before anything is launched, naming the entry point: a null argument, handles of different contexts, a
+ * net that is not a critic, episodes outside the block, normalizer or block dimensions that differ from the agent's (all
+ * HP_ERR_INVALID), an agent that is not slab-shaped (HP_ERR_STATE, like hp_agent_policy_snapshot), n_episodes or T outside
+ * [1, 2^24], more than 2^31 steps.
+ *
+ * hp_episode_returns: returns_dev[e][t] (float64) = G_t with G_t = r_t + gamma G_{t+1}, every operation rounded on its own;
+ * r_t is compute_reward's on (ag[t + 1], g[t]) in float64 -- reward_type 0: sparse, -(d > distance_threshold), 1: dense, -d --
+ * with the squared distance formed as hp_episode_stats forms it.  tail 0: G_T = +0.0; tail 1: G_T = r_{T-1} / (1 - gamma), the
+ * last step's reward held for ever.  gamma must lie in [0, 1], and gamma = 1 with tail 1 is refused.  With q_dev [n][T]
+ * (float32, hp_episode_q's output) and critic_stats_dev [n][HP_CRITIC_STATS] (float64; both or neither) every episode also gets
+ *   [0] q_mean          mean over t of Q            [3] abs_error       mean of |Q - G|
+ *   [1] return_mean     mean of G                   [4] max_abs_error   max of |Q - G|
+ *   [2] bias            mean of Q - G               [5] floor_steps     steps with Q <= -1 / (1 - gamma) (0 when gamma = 1)
+ * each sum accumulated in float64 in the order of the recursion, t = T-1 down to 0, and divided by T: the order is fixed, and
+ * synthetic.episode_returns / episode_critic_stats are the same loops, so the bits are the host twin's.  One wave per episode.
+ * hp_episode_returns_block is the same on a block's episodes.  hp_episode_critic_summary reduces n_episodes rows to the six
+ * column means, left to right in episode order (synthetic.episode_critic_summary).  All asynchronous, nothing allocated;
+ * HP_ERR_INVALID, naming the entry point, for a null argument (q_dev / critic_stats_dev excepted), n_episodes, T or goal_dim out
+ * of range as for hp_episode_stats, an unknown reward_type or tail, gamma outside [0, 1], episodes outside the block. */
+#define HP_CRITIC_STATS 6
+int hp_episode_q(hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, int32_t net, const double *obs_dev, const double *g_dev,
+                 const double *actions_dev, int64_t n_episodes, int32_t T, double clip_obs, float *q_dev);
+int hp_episode_q_block(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, int32_t net, int64_t first_episode,
+                       int64_t n_episodes, double clip_obs, float *q_dev);
+int hp_episode_returns(hp_ctx *ctx, const double *ag_dev, const double *g_dev, int64_t n_episodes, int32_t T, int32_t goal_dim,
+                       double distance_threshold, int32_t reward_type, double gamma, int32_t tail, double *returns_dev,
+                       const float *q_dev, double *critic_stats_dev);
+int hp_episode_returns_block(hp_rollout *ro, int64_t first_episode, int64_t n_episodes, double distance_threshold,
+                             int32_t reward_type, double gamma, int32_t tail, double *returns_dev, const float *q_dev,
+                             double *critic_stats_dev);
+int hp_episode_critic_summary(hp_ctx *ctx, const double *critic_stats_dev, int64_t n_episodes, double *summary_dev);
+
 /* Policy calls that do not queue behind training: hp_agent_policy_snapshot copies the online actor and both normalizers'
  * statistics (stream-ordered with the updates, no host wait); hp_agent_act_snapshot evaluates the most recent COMPLETE
  * snapshot on a second stream, so a feeder can step its environments while a training cycle runs (its policy lags the

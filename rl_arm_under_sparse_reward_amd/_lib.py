@@ -71,6 +71,7 @@ ENV_POINT_MASS = 1
 ENV_PUSH_BLOCK = 2      # HP_ENV_PUSH_BLOCK
 ENV_PICK_PLACE = 3      # HP_ENV_PICK_PLACE
 EPISODE_STATS, EPISODE_SUMMARY, EPISODE_MAX_GOAL_DIM = 6, 6, 256   # HP_EPISODE_STATS, HP_EPISODE_SUMMARY, HP_EPISODE_MAX_GOAL_DIM
+CRITIC_STATS = 6       # HP_CRITIC_STATS: the columns of synthetic.CRITIC_STATS
 ROLLOUT_MAX_LAUNCH_TIMESTEPS = 4096   # HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS: what one launch of hp_rollout_waves holds at most
 
 
@@ -221,6 +222,15 @@ PROTOTYPES = {
                                    C.c_void_p]),
     "hp_episode_stats_block": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
     "hp_episode_stats_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hp_episode_q": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                               C.c_double, C.c_void_p]),
+    "hp_episode_q_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_double,
+                                     C.c_void_p]),
+    "hp_episode_returns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                     C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hp_episode_returns_block": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "hp_episode_critic_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "hp_agent_policy_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hp_agent_act_snapshot": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int64, C.c_double, f32p]),
     "hp_agent_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,

@@ -1073,6 +1073,41 @@ __device__ __forceinline__ void s8_policy_slab(const PolicyArgs &P, PolicyLds &L
     }
 }
 
+// Q = critic(x | a / max_action) (models.py:28-44) for the 4-row slab at row0: the critic half of the chain kernel above -- the
+// target critic's forward of fb_slab8_body with the network as an argument, same device functions, so the same bits as the training
+// forward.  net: the forward fragments and the canonical arena of the WHOLE parameter set, the critic's segment at offset ca.
+// input(r, c) = column c < S8_LDX of the slab's row r (called for rows that exist; it returns 0 for the padding columns);
+// emit(r, q) is called by lane 0 of wave r with row r's Q.  The frame, the LDS and the entry condition are s8_policy_slab's.
+template <class Input, class Emit>
+__device__ __forceinline__ void s8_critic_slab(const SlabNetPtrs &net, const NetLayout &lc, int ca, int H, long long rows, PolicyLds &L,
+                                               size_t row0, Input input, Emit emit) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const float *wf = net.wf + ca, *canon = net.canon + ca;
+    float *xin = L.xin, *bufA = L.bufA, *bufB = L.bufB, *pbuf = L.pbuf;
+    RingSlot *ring = L.wring[wave];
+    int rbase = 0;
+    float4 wbc[6], wq[4];
+    s8_small_prefetch(wf + lc.w1, lc.K1, wbc);
+    wq[0] = *reinterpret_cast<const float4 *>(canon + lc.w4 + 4 * lane);
+    const float bq = canon[lc.b4];
+    for (int idx = tid; idx < S8_ROWS * S8_LDX; idx += S8_THREADS) {
+        const int r = idx / S8_LDX, c = idx - r * S8_LDX;
+        const size_t m = row0 + r;
+        float v = 0.f;
+        if ((long long)m < rows) v = input(r, c);
+        xin[idx] = v;
+    }
+    s8_ring_prologue(ring, rbase, wf + lc.w2);
+    s8_sync();
+    s8_trunk(xin, lc, wbc, wf, canon, H, bufA, bufB, pbuf, nullptr, nullptr, nullptr, row0, ring, rbase, nullptr, nullptr, 0);
+#pragma unroll
+    for (int i = 0; i < S8_RPW; ++i) {
+        const int rr = wave + S8_WAVES * i;
+        const float q = s8_rowdots(bufA, S8_LD, rr < S8_ROWS ? rr : 0, 1, wq);
+        if (lane == 0 && rr < S8_ROWS && (long long)(row0 + rr) < rows) emit(rr, q + bq);
+    }
+}
+
 #ifndef S8_DEVICE_ONLY
 __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_policy_slab8(const PolicyArgs P) {
     __shared__ PolicyLds L;

@@ -143,6 +143,7 @@ class ddpg_agent:
         self._stage_lock = threading.RLock()   # orders "store a wave, then sample ITS staged episodes" across feeder threads
         self.success_rates = []
         self.eval_metrics = []           # args.eval_metrics: one dict per evaluation, keyed by synthetic.EPISODE_SUMMARY
+        self.eval_critic = []            # args.eval_critic: one dict per evaluation, keyed by synthetic.CRITIC_STATS
         self.model_path = os.path.join(self.args.save_dir, self.args.env_name)
 
     def close_comm(self):
@@ -761,6 +762,58 @@ class ddpg_agent:
             _lib.check(self.lib.hp_episode_stats(self.ctx.h, p(ag), p(g), n, T, gd, float(distance_threshold), p(stats), p(flags)))
         return stats.cpu().numpy(), flags.cpu().numpy()
 
+    def episode_q(self, episodes, target=False, first=0, n=None):
+        """What the critic believes of episodes [first, first + n) of a `DeviceEpisodes` (a collection's, an evaluation's, or
+        `generate_demos(...).episodes`: what the critic thinks of the demonstrations): Q(s_t, a_t) of every recorded step, a
+        float32 device tensor [n, T], from one launch on torch's current stream (hp_episode_q_block) -- the training chain's
+        critic forward on rows that enter it exactly as they enter an update (clip_obs from `args`, the normalizers' current
+        statistics, the recorded action over max_action).  `target=True`: the target critic.  No copy, no synchronisation."""
+        first = int(first)
+        n = len(episodes) - first if n is None else int(n)
+        q = torch.empty((max(n, 0), episodes.T), dtype=torch.float32, device=torch.device("cuda", self.ctx.device_id))
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_episode_q_block(episodes.h, self.h, self.o_norm.h, self.g_norm.h,
+                                                   NET_CRITIC_TARGET if target else NET_CRITIC, first, n, float(self.args.clip_obs),
+                                                   C.c_void_p(q.data_ptr())))
+        return q
+
+    def episode_critic_stats(self, episodes, distance_threshold=None, target=False, tail="persist", first=0, n=None):
+        """The critic audited on episodes [first, first + n) of a `DeviceEpisodes`: (stats [n, 6] float64 in the columns of
+        `synthetic.CRITIC_STATS`, q [n, T] float32, returns [n, T] float64), device tensors from two launches (`episode_q`,
+        `DeviceEpisodes.returns`).  The threshold defaults to `vec_env.distance_threshold`; gamma and reward_type are `args`'."""
+        if distance_threshold is None:
+            distance_threshold = self.vec_env.distance_threshold
+        q = self.episode_q(episodes, target=target, first=first, n=n)
+        returns, stats = episodes.returns(distance_threshold, float(self.args.gamma), getattr(self.args, "reward_type", "sparse"),
+                                          tail, first=first, n=n, q=q)
+        return stats, q, returns
+
+    def episode_critic_stats_host(self, episode_batch, distance_threshold, target=False, tail="persist"):
+        """`episode_critic_stats` for host episodes -- the four arrays `collect_episodes` returns, or a feeder slot's (obs, ag, g,
+        actions): they are uploaded, the same kernels run (hp_episode_q, hp_episode_returns) and the result comes back as numpy
+        (stats [n, 6] float64, q [n, T] float32, returns [n, T] float64).  Synchronises."""
+        from .synthetic import _reward_kind, _tail_kind
+        obs, ag, g, act = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)) for a in episode_batch[:4])
+        if (any(a.ndim != 3 for a in (obs, ag, g, act)) or len({a.shape[0] for a in (obs, ag, g, act)}) != 1
+                or not obs.shape[1] == ag.shape[1] == g.shape[1] + 1 == act.shape[1] + 1 or ag.shape[2] != g.shape[2]):
+            raise ValueError("episode_critic_stats_host: obs [n, T+1, obs], ag [n, T+1, goal], g [n, T, goal] and actions [n, T, act] expected")
+        if (obs.shape[2], g.shape[2], act.shape[2]) != tuple(int(self.env_params[k]) for k in ('obs', 'goal', 'action')):
+            raise ValueError("episode_critic_stats_host: the episodes' dimensions differ from the agent's")
+        dev = torch.device("cuda", self.ctx.device_id)
+        obs, ag, g, act = obs.to(dev), ag.to(dev), g.to(dev), act.to(dev)
+        n, T, gd = g.shape
+        q = torch.empty((n, T), dtype=torch.float32, device=dev)
+        returns = torch.empty((n, T), dtype=torch.float64, device=dev)
+        stats = torch.empty((n, _lib.CRITIC_STATS), dtype=torch.float64, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_episode_q(self.h, self.o_norm.h, self.g_norm.h, NET_CRITIC_TARGET if target else NET_CRITIC,
+                                             p(obs), p(g), p(act), n, T, float(self.args.clip_obs), p(q)))
+            _lib.check(self.lib.hp_episode_returns(self.ctx.h, p(ag), p(g), n, T, gd, float(distance_threshold),
+                                                   _reward_kind(getattr(self.args, "reward_type", "sparse")), float(self.args.gamma),
+                                                   _tail_kind(tail), p(returns), p(q), p(stats)))
+        return stats.cpu().numpy(), q.cpu().numpy(), returns.cpu().numpy()
+
     def _collect_all_waves(self, vec_env, eps, n_total, streams, how):
         """All `n_total` episodes as one launch (hp_rollout_waves), or the few the launch cap dictates; the environments are
         reset inside it.  Returns the n_total success flags."""
@@ -934,24 +987,35 @@ class ddpg_agent:
         the device and copied to the host once at the end."""
         flags, remaining = [], int(self.args.n_test_rollouts)
         stats = [] if getattr(self.args, "eval_metrics", False) else None
+        critic = [] if getattr(self.args, "eval_critic", False) else None
         while remaining > 0:
             # one call per wave; with reset on the device one call for all of them (one launch: hp_rollout_waves)
             k = remaining if getattr(self.vec_env, "reset_streams", None) is not None else min(self.vec_env.n_envs, remaining)
-            self.collect_episodes_device(n_rollouts=k, explore=False, success_out=flags, stats_out=stats)
+            eps = self.collect_episodes_device(n_rollouts=k, explore=False, success_out=flags, stats_out=stats)
+            if critic is not None:       # args.eval_critic: two more launches behind the call, before the next one rewrites the block
+                critic.append(self.episode_critic_stats(eps, first=0, n=k)[0])
             remaining -= k
         wins = torch.cat([f.reshape(-1).to(torch.float64) for f in flags])
-        if stats is None:
+        if stats is None and critic is None:
             return self._success_rate(wins.cpu().numpy())
-        # args.eval_metrics: the summary of all evaluation episodes (hp_episode_stats_summary) rides behind the flags in the one
-        # copy to the host; what is done with the flags is unchanged
-        rows = stats[0] if len(stats) == 1 else torch.cat(stats)
-        summary = torch.empty(_lib.EPISODE_SUMMARY, dtype=torch.float64, device=rows.device)
-        with self.ctx.torch_bridge():
-            _lib.check(self.lib.hp_episode_stats_summary(self.ctx.h, C.c_void_p(rows.data_ptr()), rows.shape[0],
-                                                         C.c_void_p(summary.data_ptr())))
-        both = torch.cat([wins, summary]).cpu().numpy()
-        rate = self._success_rate(both[:-_lib.EPISODE_SUMMARY])
-        self._record_eval_metrics(both[-_lib.EPISODE_SUMMARY:])
+        # args.eval_metrics / args.eval_critic: the summaries of all evaluation episodes (hp_episode_stats_summary,
+        # hp_episode_critic_summary) ride behind the flags in the one copy to the host; what is done with the flags is unchanged
+        riders = []
+        for rows, entry, width in ((stats, self.lib.hp_episode_stats_summary, _lib.EPISODE_SUMMARY),
+                                   (critic, self.lib.hp_episode_critic_summary, _lib.CRITIC_STATS)):
+            if rows is None:
+                continue
+            rows = rows[0] if len(rows) == 1 else torch.cat(rows)
+            summary = torch.empty(width, dtype=torch.float64, device=rows.device)
+            with self.ctx.torch_bridge():
+                _lib.check(entry(self.ctx.h, C.c_void_p(rows.data_ptr()), rows.shape[0], C.c_void_p(summary.data_ptr())))
+            riders.append(summary)
+        both, n_wins = torch.cat([wins, *riders]).cpu().numpy(), wins.numel()
+        rate = self._success_rate(both[:n_wins])
+        if stats is not None:
+            self._record_eval_metrics(both[n_wins:n_wins + _lib.EPISODE_SUMMARY])
+        if critic is not None:
+            self._record_eval_critic(both[-_lib.CRITIC_STATS:])
         return rate
 
     def _record_eval_metrics(self, summary):
@@ -962,6 +1026,15 @@ class ddpg_agent:
             local = local.to(f"cuda:{self.ctx.device_id}")
         self.comm.allreduce_mean_(local)
         self.eval_metrics.append(dict(zip(EPISODE_SUMMARY, (float(v) for v in local.cpu().numpy()))))
+
+    def _record_eval_critic(self, summary):
+        """One evaluation's critic summary (this rank's six means), averaged over the ranks like the success rate, onto `eval_critic`"""
+        from .synthetic import CRITIC_STATS
+        local = torch.tensor(np.asarray(summary, dtype=np.float64), dtype=torch.float64)
+        if self.comm.world_size > 1:
+            local = local.to(f"cuda:{self.ctx.device_id}")
+        self.comm.allreduce_mean_(local)
+        self.eval_critic.append(dict(zip(CRITIC_STATS, (float(v) for v in local.cpu().numpy()))))
 
     def _success_rate(self, wins):
         """The mean of this rank's success flags, averaged over the ranks"""
@@ -977,8 +1050,10 @@ class ddpg_agent:
         if self.vec_env is not None:
             return self._eval_agent_device()
         wins = []
-        metrics = bool(getattr(self.args, "eval_metrics", False))
+        audit = bool(getattr(self.args, "eval_critic", False))
+        metrics = bool(getattr(self.args, "eval_metrics", False)) or audit
         ep_ag, ep_g = [], []             # args.eval_metrics: achieved goals [T + 1] and desired goals [T] of every episode
+        ep_obs, ep_act = [], []          # args.eval_critic: observations [T + 1] and actions [T] beside them
         remaining = int(self.args.n_test_rollouts)
         while remaining > 0:
             envs = self.envs[:remaining]
@@ -989,10 +1064,16 @@ class ddpg_agent:
             if metrics:
                 ags = [[np.array(o['achieved_goal'], dtype=np.float64)] for o in first]
                 gs = [[] for _ in envs]
+            if audit:
+                obss = [[np.array(o['observation'], dtype=np.float64)] for o in first]
+                acts = [[] for _ in envs]
             for _t in range(int(self.env_params['max_timesteps'])):
                 actions = self.act(np.stack(obs), np.stack(g))
                 for i, env in enumerate(envs):
                     observation_new, _, _, info = env.step(actions[i])
+                    if audit:
+                        acts[i].append(np.array(actions[i], dtype=np.float64))
+                        obss[i].append(np.array(observation_new['observation'], dtype=np.float64))
                     if metrics:
                         gs[i].append(np.array(g[i], dtype=np.float64))
                         ags[i].append(np.array(observation_new['achieved_goal'], dtype=np.float64))
@@ -1002,12 +1083,19 @@ class ddpg_agent:
             if metrics:
                 ep_ag.extend(ags)
                 ep_g.extend(gs)
+            if audit:
+                ep_obs.extend(obss)
+                ep_act.extend(acts)
             remaining -= len(envs)
         rate = self._success_rate(wins)
-        if metrics:
+        thr = getattr(self.env, "distance_threshold", getattr(self.args, "distance_threshold", 0.05))
+        if getattr(self.args, "eval_metrics", False):
             from .synthetic import episode_stats, episode_stats_summary
-            thr = getattr(self.env, "distance_threshold", getattr(self.args, "distance_threshold", 0.05))
             self._record_eval_metrics(episode_stats_summary(episode_stats(np.array(ep_ag), np.array(ep_g), thr)[0]))
+        if audit:
+            from .synthetic import episode_critic_summary
+            batch = [np.array(ep_obs), np.array(ep_ag), np.array(ep_g), np.array(ep_act)]
+            self._record_eval_critic(episode_critic_summary(self.episode_critic_stats_host(batch, thr)[0]))
         return rate
 
     def __del__(self):

@@ -143,6 +143,31 @@ class DeviceEpisodes:
                                                        C.c_void_p(flags.data_ptr()) if step_success else None))
         return (stats, flags) if step_success else stats
 
+    def returns(self, distance_threshold, gamma, reward_type="sparse", tail="persist", first=0, n=None, q=None):
+        """The discounted return every step of episodes [first, first + n) went on to collect, computed where they lie
+        (hp_episode_returns_block): a float64 device tensor [n, T].  `reward_type` 'sparse' | 'dense' is compute_reward's; `tail`
+        'persist' holds the last step's reward for ever (G_T = r_{T-1} / (1 - gamma), what an infinite-horizon critic is trained
+        towards), 'zero' ends the sum with the episode.  With `q` (a float32 device tensor [n, T], `ddpg_agent.episode_q`) the
+        same launch also fills the critic columns: returns (returns, stats [n, 6] in the columns of `synthetic.CRITIC_STATS`).
+        One launch on torch's current stream; no copy and no synchronisation.  `synthetic.episode_returns` /
+        `episode_critic_stats` on `.numpy()` give the same bits."""
+        from .synthetic import _reward_kind, _tail_kind
+        first = int(first)
+        n = self.n - first if n is None else int(n)
+        dev = torch.device("cuda", self.ctx.device_id)
+        out = torch.empty((max(n, 0), self.T), dtype=torch.float64, device=dev)
+        stats = None
+        if q is not None:
+            if q.dtype != torch.float32 or tuple(q.shape) != tuple(out.shape) or not q.is_contiguous() or q.device != out.device:
+                raise ValueError(f"DeviceEpisodes.returns: q must be a contiguous float32 device tensor [{max(n, 0)}, {self.T}]")
+            stats = torch.empty((max(n, 0), _lib.CRITIC_STATS), dtype=torch.float64, device=dev)
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_episode_returns_block(self.h, first, n, float(distance_threshold), _reward_kind(reward_type),
+                                                         float(gamma), _tail_kind(tail), C.c_void_p(out.data_ptr()),
+                                                         C.c_void_p(q.data_ptr()) if q is not None else None,
+                                                         C.c_void_p(stats.data_ptr()) if q is not None else None))
+        return out if q is None else (out, stats)
+
     def __del__(self):
         try:
             self.lib.hp_rollout_destroy(self.h)

@@ -501,6 +501,111 @@ def episode_stats_summary(stats):
     return total / np.float64(stats.shape[0])
 
 
+CRITIC_STATS = ("q_mean", "return_mean", "bias", "abs_error", "max_abs_error", "floor_steps")
+
+
+def _reward_kind(reward_type):
+    if reward_type in ("sparse", 0):
+        return 0
+    if reward_type in ("dense", 1):
+        return 1
+    raise ValueError(f"reward_type {reward_type!r} is neither 'sparse' nor 'dense'")
+
+
+def _tail_kind(tail):
+    if tail in ("zero", 0):
+        return 0
+    if tail in ("persist", 1):
+        return 1
+    raise ValueError(f"tail {tail!r} is neither 'zero' nor 'persist'")
+
+
+def _check_gamma(gamma, tail):
+    gamma = float(gamma)
+    if not 0.0 <= gamma <= 1.0:
+        raise ValueError(f"gamma {gamma} outside [0, 1]")
+    if gamma == 1.0 and tail == 1:
+        raise ValueError("gamma 1 with tail 'persist' has no finite return")
+    return np.float64(gamma)
+
+
+def episode_returns(ag, g, distance_threshold, gamma, reward_type="sparse", tail="persist"):
+    """The host twin of hp_episode_returns, as plain loops: `ag` [n, T+1, goal] and `g` [n, T, goal] -> G [n, T] float64, the
+    discounted return every step went on to collect.  r[t] is compute_reward's on (ag[t + 1], g[t]) in float64 -- sparse:
+    -(d > threshold) (the float32 of `episode_stats`, widened), dense: -d -- with d the root of the squares summed left to right.
+    G[T] = +0.0 (tail 'zero') or r[T-1] / (1 - gamma) (tail 'persist': the last step's reward held for ever, what an
+    infinite-horizon critic is trained towards); G[t] = r[t] + gamma * G[t+1], one rounding per operation.  gamma must lie in
+    [0, 1]; gamma = 1 with tail 'persist' raises."""
+    ag, g = np.asarray(ag, dtype=np.float64), np.asarray(g, dtype=np.float64)
+    if ag.ndim != 3 or g.ndim != 3 or ag.shape[0] != g.shape[0] or ag.shape[1] != g.shape[1] + 1 or ag.shape[2] != g.shape[2]:
+        raise ValueError("episode_returns: ag [n, T+1, goal] and g [n, T, goal] expected")
+    kind, tail = _reward_kind(reward_type), _tail_kind(tail)
+    gamma = _check_gamma(gamma, tail)
+    n, T, thr = g.shape[0], g.shape[1], float(distance_threshold)
+    diff = ag[:, 1:] - g
+    sq = diff * diff
+    s = sq[..., 0]
+    for c in range(1, sq.shape[-1]):
+        s = s + sq[..., c]
+    d = np.sqrt(s)
+    r = (-(d > thr).astype(np.float32)).astype(np.float64) if kind == 0 else -d
+    G = np.empty((n, T), dtype=np.float64)
+    gamma = float(gamma)                     # Python floats from here on: IEEE float64, one rounding per operation
+    for e in range(n):
+        row = r[e].tolist()
+        acc = row[T - 1] / (1.0 - gamma) if tail == 1 else 0.0
+        for t in range(T - 1, -1, -1):
+            acc = row[t] + gamma * acc
+            row[t] = acc
+        G[e] = row
+    return G
+
+
+def episode_critic_stats(q, returns, gamma):
+    """The host twin of the critic columns of hp_episode_returns: `q` [n, T] float32 and `returns` [n, T] float64 -> [n, 6]
+    float64 in the columns of CRITIC_STATS.  One accumulator per column, Q widened to float64, summed in the order of the
+    recursion -- t = T-1 down to 0 -- and divided by T; max_abs_error and floor_steps (steps with Q <= -1 / (1 - gamma), the target
+    clip of ddpg_agent.py:259-260; 0 when gamma = 1) are not divided.  The device's loop, not numpy's pairwise mean."""
+    q, returns = np.asarray(q), np.asarray(returns, dtype=np.float64)
+    if q.dtype != np.float32 or q.ndim != 2 or q.shape != returns.shape or q.shape[1] < 1:
+        raise ValueError("episode_critic_stats: q [n, T] float32 and returns [n, T] float64 expected")
+    gamma = float(_check_gamma(gamma, 0))    # Python floats from here on: IEEE float64, one rounding per operation
+    has_floor = gamma < 1.0
+    floor = -(1.0 / (1.0 - gamma)) if has_floor else 0.0
+    n, T = q.shape
+    out = np.empty((n, len(CRITIC_STATS)), dtype=np.float64)
+    for e in range(n):
+        qs, Gs = q[e].astype(np.float64).tolist(), returns[e].tolist()
+        sum_q = sum_g = sum_b = sum_a = max_a = 0.0
+        steps = 0
+        for t in range(T - 1, -1, -1):
+            qd, G = qs[t], Gs[t]
+            d = qd - G
+            a = abs(d)
+            sum_q = sum_q + qd
+            sum_g = sum_g + G
+            sum_b = sum_b + d
+            sum_a = sum_a + a
+            max_a = a if a > max_a else max_a
+            steps += 1 if (has_floor and qd <= floor) else 0
+        dT = float(T)
+        out[e] = (sum_q / dT, sum_g / dT, sum_b / dT, sum_a / dT, max_a, float(steps))
+    return out
+
+
+def episode_critic_summary(stats):
+    """The host twin of hp_episode_critic_summary: the six column means over the episodes, each a left-to-right float64 sum in
+    episode order divided by their number."""
+    stats = np.asarray(stats, dtype=np.float64)
+    if stats.ndim != 2 or stats.shape[1] != len(CRITIC_STATS) or stats.shape[0] < 1:
+        raise ValueError("episode_critic_summary: stats [n >= 1, 6] expected")
+    total = np.zeros(len(CRITIC_STATS), dtype=np.float64)
+    for row in stats:
+        for k in range(len(CRITIC_STATS)):
+            total[k] = total[k] + row[k]
+    return total / np.float64(stats.shape[0])
+
+
 def write_demo_npz_from(path, obs, ag, g, actions, info):
     """Write episodes in the schema get_demo_data_push.py:91-94 produces: keys acs, obs, info, g, ag, with `info` an object
     array [n, T] of per-step dicts {'is_success': float32} (`info` here: the flags [n, T]).  Such a file preloads through
