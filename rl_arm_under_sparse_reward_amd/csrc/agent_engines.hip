@@ -14,6 +14,7 @@
 #endif
 #include "agent_device.h"
 #include "gemm_lds.h"
+#include "transition_device.h"
 
 // gradients: barrier + rank-ordered sum + Adam.  n4 = arena floats / 4; u = index of the update in its sequence.
 __global__ __launch_bounds__(256) void k_peer_adam(const PeerDev D, const AdamFuse F, int n4, int u, int mean) {
@@ -255,14 +256,12 @@ __global__ __launch_bounds__(256) void k_gather_fused(const double *__restrict__
     const int t = rec.t;
     const double *obs_row = obs + (e * (T + 1) + t) * obs_dim;
     const double *ag_next = ag + (e * (T + 1) + t + 1) * goal_dim;
-    const double *g_src = rec.her ? ag + (e * (T + 1) + rec.fut) * goal_dim : g + (e * T + t) * goal_dim;
+    const double *g_src = TR_GOAL_SRC(rec, ag, g, T, goal_dim);
     const double *act_row = act + (e * T + t) * act_dim;
     float *xa = XA + (long long)i * ldx, *xp = XP + (long long)i * ldx, *xt = XT + (long long)i * ldx;
     for (int c = lane; c < 2 * obs_dim; c += 64) {
         const int col = (c < obs_dim) ? c : c - obs_dim;
-        double v = fmin(fmax(obs_row[c], -clip_obs), clip_obs);                       // _preproc_og
-        v = __ddiv_rn(__dsub_rn(v, (double)onz->mean[col]), onz->std[col]);           // normalize
-        const float x = (float)fmin(fmax(v, -clip_range), clip_range);
+        const float x = tr_net_input(obs_row[c], clip_obs, onz->mean[col], onz->std[col], clip_range);
         if (c < obs_dim) {
             xa[col] = x;
             xp[col] = x;
@@ -271,23 +270,13 @@ __global__ __launch_bounds__(256) void k_gather_fused(const double *__restrict__
         }
     }
     for (int c = lane; c < goal_dim; c += 64) {
-        double v = fmin(fmax(g_src[c], -clip_obs), clip_obs);
-        v = __ddiv_rn(__dsub_rn(v, (double)gnz->mean[c]), gnz->std[c]);
-        const float x = (float)fmin(fmax(v, -clip_range), clip_range);
+        const float x = tr_net_input(g_src[c], clip_obs, gnz->mean[c], gnz->std[c], clip_range);
         xa[obs_dim + c] = x;
         xp[obs_dim + c] = x;
         xt[obs_dim + c] = x;   // g_next := g (ddpg_agent.py:231)
     }
     for (int c = lane; c < act_dim; c += 64) xa[act_off + c] = (float)act_row[c] / max_action;  // models.py:38
-    if (lane == 0) {
-        double s = 0.0;
-        for (int c = 0; c < goal_dim; ++c) {
-            const double d = __dsub_rn(ag_next[c], g_src[c]);
-            const double sq = __dmul_rn(d, d);
-            s = (c == 0) ? sq : __dadd_rn(s, sq);
-        }
-        R[i] = hp_reward(s, sq_threshold);
-    }
+    if (lane == 0) R[i] = hp_reward(tr_sq_distance(ag_next, g_src, goal_dim), sq_threshold);
 }
 
 // slab engine: Adam that also refreshes the fragment-ordered copies and finishes the loss log
@@ -332,8 +321,7 @@ __global__ void k_pack_rows(const float *__restrict__ src, int rows, int width, 
     dst[(long long)r * ld + col0 + c] = src[idx];
 }
 
-// rollout inputs (ddpg_agent._preproc_inputs :163-171): normalised, clipped observation | goal rows in float32, the same
-// float64 arithmetic as the sampled minibatch rows (slab8.h s8_gather)
+// rollout inputs (ddpg_agent._preproc_inputs :163-171): normalised, clipped observation | goal rows in float32 (tr_net_input)
 __global__ void k_policy_inputs(const double *__restrict__ obs, const double *__restrict__ g, int rows, int od, int gd,
                                 const NormDev *__restrict__ onz, const NormDev *__restrict__ gnz, double clip_obs,
                                 double clip_o, double clip_g, float *X, int ld) {
@@ -341,18 +329,9 @@ __global__ void k_policy_inputs(const double *__restrict__ obs, const double *__
     const int w = od + gd;
     if (idx >= (long long)rows * w) return;
     const int r = (int)(idx / w), c = (int)(idx - (long long)r * w);
-    double v;
-    if (c < od) {
-        v = fmin(fmax(obs[(long long)r * od + c], -clip_obs), clip_obs);
-        v = __ddiv_rn(__dsub_rn(v, (double)onz->mean[c]), onz->std[c]);
-        v = fmin(fmax(v, -clip_o), clip_o);
-    } else {
-        const int j = c - od;
-        v = fmin(fmax(g[(long long)r * gd + j], -clip_obs), clip_obs);
-        v = __ddiv_rn(__dsub_rn(v, (double)gnz->mean[j]), gnz->std[j]);
-        v = fmin(fmax(v, -clip_g), clip_g);
-    }
-    X[(long long)r * ld + c] = (float)v;
+    const int j = c - od;
+    X[(long long)r * ld + c] = c < od ? tr_net_input(obs[(long long)r * od + c], clip_obs, onz->mean[c], onz->std[c], clip_o)
+                                      : tr_net_input(g[(long long)r * gd + j], clip_obs, gnz->mean[j], gnz->std[j], clip_g);
 }
 
 // critic input: action block = actions / max_action (models.py:38)

@@ -8,9 +8,9 @@
 // A sampled transition touches obs[e][t..t+1] (one contiguous 2*obs_dim run), ag[e][t..t+1],
 // g[e][t], actions[e][t] and, when relabelled, ag[e][future_t].
 //
-// Built with -ffp-contract=off: the reward must round exactly like numpy's
-// (x0*x0 + x1*x1) + x2*x2 in float64, so no multiply-add may be fused.
+// The arithmetic of a transition (reward, network input, relabelled goal): transition_device.h.
 #include "store_device.h"
+#include "transition_device.h"
 
 #include <cmath>
 
@@ -32,8 +32,7 @@ __global__ __launch_bounds__(256) void k_gather_dict(const double *__restrict__ 
     const int t = rec.t;
     const double *obs_row = obs + (e * (T + 1) + t) * obs_dim;        // rows t and t+1 are adjacent
     const double *ag_row = ag + (e * (T + 1) + t) * goal_dim;
-    const double *g_src = rec.her ? ag + (e * (T + 1) + rec.fut) * goal_dim  // her.py:35-36
-                                  : g + (e * T + t) * goal_dim;
+    const double *g_src = TR_GOAL_SRC(rec, ag, g, T, goal_dim);
     const double *act_row = act + (e * T + t) * act_dim;
     for (int c = lane; c < obs_dim; c += 64) {
         o_obs[i * obs_dim + c] = obs_row[c];
@@ -46,13 +45,12 @@ __global__ __launch_bounds__(256) void k_gather_dict(const double *__restrict__ 
     }
     for (int c = lane; c < act_dim; c += 64) o_act[i * act_dim + c] = act_row[c];
     if (lane == 0) {
-        // goal_distance: sqrt(sum((ag_next - g)^2)) > thr  <=>  sum >= sq_threshold  (sqrt is monotone;
-        // sq_threshold is the smallest double whose correctly rounded sqrt exceeds thr).  numpy's
-        // add.reduce over a contiguous axis of < 8 elements is a plain left-to-right sum.
+        // tr_sq_distance (transition_device.h), written out: the index goal_dim + c is summed in int, as the copy loop above sums it;
+        // handing ag_row + goal_dim to the function forms that address in 64 bits and costs the kernel two VGPRs and two SGPRs
         double s = 0.0;
         for (int c = 0; c < goal_dim; ++c) {
-            double d = __dsub_rn(ag_row[goal_dim + c], g_src[c]);
-            double sq = __dmul_rn(d, d);
+            const double d = __dsub_rn(ag_row[goal_dim + c], g_src[c]);
+            const double sq = __dmul_rn(d, d);
             s = (c == 0) ? sq : __dadd_rn(s, sq);
         }
         o_r[i] = hp_reward(s, sq_threshold);  // -(d > thr).astype(float32), or float32(-d)
@@ -161,7 +159,7 @@ __global__ __launch_bounds__(256) void k_gather_fused(const FusedSampleArgs A) {
             const long long e = rec[k].e;
             const int t = rec[k].t;
             obs0[k] = A.obs + (e * (A.T + 1) + t) * od;
-            g_src[k] = rec[k].her ? A.ag + (e * (A.T + 1) + rec[k].fut) * gd : A.g + (e * A.T + t) * gd;   // her.py:35-36
+            g_src[k] = TR_GOAL_SRC(rec[k], A.ag, A.g, A.T, gd);
             ra[k] = A.ag[(e * (A.T + 1) + t + 1) * gd + rc];
             rg[k] = g_src[k][rc];
         }
@@ -186,9 +184,7 @@ __global__ __launch_bounds__(256) void k_gather_fused(const FusedSampleArgs A) {
                 const long long m = base + k;
                 if (m >= A.batch) continue;
                 if (kind <= 1 || kind == 3) {
-                    double c = fmin(fmax(v[k], -A.clip_obs), A.clip_obs);                 // _preproc_og
-                    c = __ddiv_rn(__dsub_rn(c, (double)mu), sd);                          // normalizer.normalize
-                    const float x = (float)fmin(fmax(c, -clip), clip);
+                    const float x = tr_net_input(v[k], A.clip_obs, mu, sd, clip);
                     if (kind == 0) { if (A.x) A.x[m * ldx + j] = x; }
                     else if (kind == 1) { if (A.xn) A.xn[m * ldx + j] = x; }
                     else {
@@ -200,18 +196,11 @@ __global__ __launch_bounds__(256) void k_gather_fused(const FusedSampleArgs A) {
                 }
             }
         }
-        // reward: lanes < gd hold (ag_next - g')^2 of their component, lane 0 adds them in index order (numpy's add.reduce
-        // over < 8 contiguous elements is a left-to-right sum)
+        // reward: lanes < gd hold (ag_next - g')^2 of their component (tr_sq_distance_lanes)
 #pragma unroll
         for (int k = 0; k < FLIGHT; ++k) {
             const long long m = base + k;
-            const double d = __dsub_rn(ra[k], rg[k]);
-            const double sq = __dmul_rn(d, d);
-            double s = 0.0;
-            for (int c = 0; c < gd; ++c) {
-                const double sc = __shfl(sq, c);
-                s = (c == 0) ? sc : __dadd_rn(s, sc);
-            }
+            const double s = tr_sq_distance_lanes(tr_sq_term(ra[k], rg[k]), 0, gd);
             if (m < A.batch && lane == 0) {
                 if (A.r) A.r[m] = hp_reward(s, A.sq_threshold);
                 if (A.o_e) A.o_e[m] = rec[k].e;
@@ -306,7 +295,7 @@ __global__ __launch_bounds__(256) void k_gather_fused2(const FusedSampleArgs A) 
             const long long e = rec[k].e;
             const int t = rec[k].t;
             const double *obs0 = A.obs + (e * (A.T + 1) + t) * od;
-            const double *g_src = rec[k].her ? A.ag + (e * (A.T + 1) + rec[k].fut) * gd : A.g + (e * A.T + t) * gd;   // her.py:35-36
+            const double *g_src = TR_GOAL_SRC(rec[k], A.ag, A.g, A.T, gd);
             const double *p = unit == 0 ? obs0 + e0 : unit == 1 ? g_src + e0 : unit == 2 ? A.act + (e * A.T + t) * ad + e0 : obs0;
             v[k] = *reinterpret_cast<const fs_d2 *>(p);
             ra[k] = A.ag[(e * (A.T + 1) + t + 1) * gd + rc];
@@ -318,21 +307,13 @@ __global__ __launch_bounds__(256) void k_gather_fused2(const FusedSampleArgs A) 
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const double val = s ? v[k].y : v[k].x;
-                double c = fmin(fmax(val, -cobs[s]), cobs[s]);                           // _preproc_og
-                c = __ddiv_rn(__dsub_rn(c, (double)mu[s]), sd[s]);                       // normalizer.normalize
-                const float x = (float)fmin(fmax(c, -clip[s]), clip[s]);
+                const float x = tr_net_input(val, cobs[s], mu[s], sd[s], clip[s]);
                 if (live && p0[s]) p0[s][m * stride0[s] + off[s]] = x;
                 if (live && p1[s]) p1[s][m * ldx + off[s]] = x;
             }
-            // reward (her.py:38): (ag_next - g')^2 per component in lanes l < gd, lane 0 of the half adds them left to right
+            // reward (her.py:38): (ag_next - g')^2 per component in lanes l < gd of the half (tr_sq_distance_lanes)
             const double gx = __shfl(v[k].x, g_lane), gy = __shfl(v[k].y, g_lane);
-            const double d = __dsub_rn(ra[k], g_slot ? gy : gx);
-            const double sq = __dmul_rn(d, d);
-            double sum = 0.0;
-            for (int c = 0; c < gd; ++c) {
-                const double sc = __shfl(sq, (h << 5) + c);
-                sum = (c == 0) ? sc : __dadd_rn(sum, sc);
-            }
+            const double sum = tr_sq_distance_lanes(tr_sq_term(ra[k], g_slot ? gy : gx), h << 5, gd);
             if (live && l == 0) {
                 if (A.r) A.r[m] = hp_reward(sum, A.sq_threshold);
                 if (A.o_e) A.o_e[m] = rec[k].e;
@@ -461,7 +442,8 @@ __global__ __launch_bounds__(256) void k_gather_packed(const PackedSampleArgs P)
             const int t = rec[k].t;
             const float *row = P.p_row + (e * (A.T + 1) + t) * rw;
             const double *goal_t = P.p_goal + (e * (A.T + 1) + t) * gw;
-            // g': the ag half of goal row future_t, or the g half (doubles gd ..) of goal row t
+            // g': the ag half of goal row future_t, or the g half (doubles gd ..) of goal row t -- her.py:35-36 on the packed goal
+            // rows [ag_t | g_t], another layout than tr_goal_src's, so the selection is written out here
             const double *gsrc = rec[k].her ? P.p_goal + (e * (A.T + 1) + rec[k].fut) * gw : goal_t + gd;
             const void *p = load == 0 ? (const void *)(row + 4 * l) : load == 1 ? (const void *)(gsrc + 2 * gj)
                           : load == 2 ? (const void *)(goal_t + gw + 2 * (l - 16)) : (const void *)row;
@@ -477,23 +459,15 @@ __global__ __launch_bounds__(256) void k_gather_packed(const PackedSampleArgs P)
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const float raw = s ? hi : lo;
-                double x = goal[s] ? v[k].d[s] : (double)raw;
-                x = fmin(fmax(x, -cobs[s]), cobs[s]);                                  // _preproc_og
-                x = __ddiv_rn(__dsub_rn(x, (double)mu[s]), sd[s]);                      // normalizer.normalize
-                const float o = (float)fmin(fmax(x, -clip[s]), clip[s]);
+                const double x = goal[s] ? v[k].d[s] : (double)raw;
+                const float o = tr_net_input(x, cobs[s], mu[s], sd[s], clip[s]);
                 if (live && p0[s]) p0[s][m * stride0[s] + off[s]] = o;
                 if (live && p1[s]) p1[s][m * ldx + off[s]] = o;
             }
-            // reward (her.py:38) on the float64 goals: the same left-to-right sum as every other gather
+            // reward (her.py:38) on the float64 goals (tr_sq_distance_lanes)
             const double ax = __shfl(v[k].d[0], a_lane), ay = __shfl(v[k].d[1], a_lane);
             const double gx = __shfl(v[k].d[0], g_lane), gy = __shfl(v[k].d[1], g_lane);
-            const double d = __dsub_rn(r_slot ? ay : ax, r_slot ? gy : gx);
-            const double sq = __dmul_rn(d, d);
-            double sum = 0.0;
-            for (int c = 0; c < gd; ++c) {
-                const double sc = __shfl(sq, (h << 5) + c);
-                sum = (c == 0) ? sc : __dadd_rn(sum, sc);
-            }
+            const double sum = tr_sq_distance_lanes(tr_sq_term(r_slot ? ay : ax, r_slot ? gy : gx), h << 5, gd);
             if (live && l == 0) {
                 if (A.r) A.r[m] = hp_reward(sum, A.sq_threshold);
                 if (A.o_e) A.o_e[m] = rec[k].e;
@@ -514,12 +488,7 @@ __global__ __launch_bounds__(256) void k_goal_reward(const double *__restrict__ 
                                                      double *out64) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    double s = 0.0;
-    for (int c = 0; c < goal_dim; ++c) {   // numpy add.reduce over < 8 contiguous elements: left to right
-        const double d = __dsub_rn(ag[i * goal_dim + c], g[i * goal_dim + c]);
-        const double sq = __dmul_rn(d, d);
-        s = (c == 0) ? sq : __dadd_rn(s, sq);
-    }
+    const double s = tr_sq_distance(ag + i * goal_dim, g + i * goal_dim, goal_dim);
     if (mode == 0) out32[i] = (s >= thr_sq) ? -1.0f : -0.0f;
     else if (mode == 1) out64[i] = -__dsqrt_rn(s);
     else out32[i] = (s < thr_sq) ? 1.0f : 0.0f;

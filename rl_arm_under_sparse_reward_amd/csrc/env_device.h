@@ -45,18 +45,16 @@
 // in front of place(), the dynamics of step_with behind env_clipped_move, is_success as env_within(blk, goal, threshold), and
 // whatever it keeps in array 3 behind the six velocities (load / store / observe call the base's and add those columns).
 #pragma once
-#include "internal.h"
+#include "transition_device.h"
 #include <type_traits>
 
 #include "mt19937_wave.h"
 
 // ---- what the kinds share ------------------------------------------------------------------------------------------------------
-// |achieved - goal| < threshold over three components: seven explicit IEEE operations -- three differences, three products, two
-// sums left to right, one root (numpy's norm) -- and the comparison.  Every kind's is_success, and the stop rule of demo_action.
+// |achieved - goal| < threshold over three components: the root (numpy's norm) of tr_sq_distance, (dx dx + dy dy) + dz dz, and
+// the comparison.  Every kind's is_success, and the stop rule of demo_action.
 __device__ __forceinline__ bool env_within(const double *achieved, const double *goal, double threshold) {
-    const double dx = __dsub_rn(achieved[0], goal[0]), dy = __dsub_rn(achieved[1], goal[1]), dz = __dsub_rn(achieved[2], goal[2]);
-    const double s = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-    return __dsqrt_rn(s) < threshold;
+    return __dsqrt_rn(tr_sq_distance(achieved, goal, 3)) < threshold;
 }
 
 // The clipped move of every kind: a = clamp(float64(action), -0.5, 0.5); scaled = step_scale * a; moved = clamp(p + scaled, lo, hi);
@@ -219,8 +217,7 @@ struct PushBlockEnvDev : GripBlockEnvDev<6> {
         range = hi[k] - lo[k];
     }
     __device__ __forceinline__ bool reset(const double *u) {
-        const double ddx = __dsub_rn(u[0], u[2]), ddy = __dsub_rn(u[1], u[3]);
-        const double d = __dsqrt_rn(__dadd_rn(__dmul_rn(ddx, ddx), __dmul_rn(ddy, ddy)));
+        const double d = __dsqrt_rn(tr_sq_distance(u, u + 2, 2));   // block (u[0], u[1]) against goal (u[2], u[3])
         place(u[0], u[1], table_z, u[2], u[3], table_z, start_x, start_y, START_Z);
         return d >= min_sep;
     }
@@ -289,6 +286,7 @@ struct PickPlaceEnvDev : GripBlockEnvDev<8> {
     }
     __device__ __forceinline__ bool reset(const double *u) {
         const double ddx = __dsub_rn(u[0], u[2]), ddy = __dsub_rn(u[1], u[3]), ddz = __dsub_rn(table_z, u[4]);
+        // tr_sq_distance's order, written out: the block's z is table_z, not a draw, so the operands are not two contiguous vectors
         const double d = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(ddx, ddx), __dmul_rn(ddy, ddy)), __dmul_rn(ddz, ddz)));
         place(u[0], u[1], table_z, u[2], u[3], u[4], start_x, start_y, START_Z);
         finger = held = 0.0;

@@ -1,0 +1,57 @@
+// episode_audit.h -- the frame the three units of the episode audit share (episode_stats.hip, episode_returns.hip, episode_q.hip):
+// the bound on episodes and steps, the refusals every entry makes of a block's shape, the range check of the *_block entries with
+// the block's four arrays behind it, and the summary of a per-episode table.  The arithmetic of a step: transition_device.h.
+#pragma once
+#include "transition_device.h"
+
+#define HP_EPISODE_MAX (1 << 24)   // episodes of one call (exclusive) and steps of one episode (inclusive)
+static_assert(HP_EPISODE_MAX_GOAL_DIM == NORM_MAX, "a goal is as wide as a normalizer can hold");
+constexpr int EPISODE_COLS = 6;    // columns of a per-episode table and of its summary
+static_assert(HP_EPISODE_STATS == EPISODE_COLS && HP_EPISODE_SUMMARY == EPISODE_COLS && HP_CRITIC_STATS == EPISODE_COLS, "one summary loop");
+
+// n_episodes, T, goal_dim, refused in this order under the entry's name (hp_episode_q* take no goal_dim of their own -- theirs is
+// the goal normalizer's -- and leave it out)
+static inline int episode_check_shape(const char *entry, int64_t n, int32_t T, int32_t gd = 1) {
+    HP_REQUIRE(n >= 1 && n < HP_EPISODE_MAX, HP_ERR_INVALID, "%s: n_episodes %lld outside [1, %d)", entry, (long long)n, HP_EPISODE_MAX);
+    HP_REQUIRE(T >= 1 && T <= HP_EPISODE_MAX, HP_ERR_INVALID, "%s: T %d outside [1, %d]", entry, (int)T, HP_EPISODE_MAX);
+    HP_REQUIRE(gd >= 1 && gd <= HP_EPISODE_MAX_GOAL_DIM, HP_ERR_INVALID, "%s: goal_dim %d outside [1, %d]", entry, (int)gd,
+               HP_EPISODE_MAX_GOAL_DIM);
+    return HP_OK;
+}
+
+// episodes [first, first + n) of a rollout block: refused when they leave it, else the block's arrays at `first`
+struct RolloutArrays { const double *b_obs, *b_ag, *b_g, *b_act; };
+static inline int episode_block_range(const char *entry, const hp_rollout *ro, int64_t first, int64_t n, RolloutArrays &at) {
+    HP_REQUIRE(first >= 0 && n >= 1 && first <= ro->n && n <= ro->n - first, HP_ERR_INVALID, "%s: episodes [%lld, %lld) outside the block of %lld",
+               entry, (long long)first, (long long)(first + n), (long long)ro->n);
+    rollout_arrays_at(ro, first, at);
+    return HP_OK;
+}
+
+// Summary of a table [n][EPISODE_COLS] into out[EPISODE_COLS]: one wave, and lane 0 walks the rows -- every mean is the left-to-right float64 sum in
+// episode order divided by n.  A fixed order on purpose (float64 means of distances depend on it; the host twins in synthetic are
+// the same loop), not numpy's pairwise mean.  term(r, k) is what row r adds to column k.
+template <class Term>
+__device__ __forceinline__ void episode_summary_body(const double *__restrict__ table, long long n, double *__restrict__ out, Term term) {
+    if (threadIdx.x != 0) return;
+    double sum[EPISODE_COLS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (long long e = 0; e < n; ++e) {
+        const double *r = table + e * EPISODE_COLS;
+#pragma unroll
+        for (int k = 0; k < EPISODE_COLS; ++k) sum[k] = __dadd_rn(sum[k], term(r, k));
+    }
+    const double dn = (double)n;
+#pragma unroll
+    for (int k = 0; k < EPISODE_COLS; ++k) out[k] = __ddiv_rn(sum[k], dn);
+}
+
+// the entry of a summary: hp_episode_stats_summary, hp_episode_critic_summary
+static inline int episode_summary_launch(const char *entry, hp_ctx *ctx, void (*kernel)(const double *, long long, double *),
+                                         const double *table, int64_t n, double *out) {
+    HP_REQUIRE(ctx && table && out, HP_ERR_INVALID, "%s: null argument", entry);
+    CtxGuard guard(ctx);
+    HP_REQUIRE(n >= 1, HP_ERR_INVALID, "%s: n_episodes %lld is not positive", entry, (long long)n);
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, ctx->stream, table, (long long)n, out);
+    HP_CHECK_HIP(hipGetLastError());
+    return HP_OK;
+}

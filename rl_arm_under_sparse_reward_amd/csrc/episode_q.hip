@@ -8,7 +8,7 @@
 // the network as an argument) inside the frame of the policy launch (k_policy_slab8): a 4-row slab per workgroup, the policy slab's
 // LDS, one workgroup per CU.  Flat row m = e T + t; workgroup b owns rows 4b .. 4b+3, so a slab may straddle two episodes; obs has
 // T + 1 rows per episode, g and actions T.  A row's input is built by the operations a transition meets on its way into an update
-// (s8_gather): clip, subtract, divide, clip in float64 one rounding each (s8_policy_input), the action narrowed to float32 and
+// (s8_gather): clip, subtract, divide, clip in float64 one rounding each (tr_net_input), the action narrowed to float32 and
 // divided by max_action in float32 -- so a recorded transition enters the critic here exactly as it enters an update.
 //
 // Which weights.  Every launch form of an update sequence (one chain launch, the split launch with its tile launches, the
@@ -33,6 +33,8 @@
 #undef S8_NS
 #undef S8_DEVICE_ONLY
 
+#include "episode_audit.h"
+
 struct EpisodeQArgs {
     const double *obs, *g, *act;   // [n][T + 1][od], [n][T][gd], [n][T][ad], already offset to the first episode
     float *q;                      // [n][T]
@@ -54,10 +56,10 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             const long long m = row0 + r, e = m / A.T;
             const int t = (int)(m - e * A.T);
             if (c < A.od)
-                return s8eq::s8_policy_input(A.obs[(e * (A.T + 1) + t) * A.od + c], A.clip_obs, A.onz->mean[c], A.onz->std[c], A.clip_o);
+                return tr_net_input(A.obs[(e * (A.T + 1) + t) * A.od + c], A.clip_obs, A.onz->mean[c], A.onz->std[c], A.clip_o);
             if (c < A.od + A.gd) {
                 const int j = c - A.od;
-                return s8eq::s8_policy_input(A.g[m * A.gd + j], A.clip_obs, A.gnz->mean[j], A.gnz->std[j], A.clip_g);
+                return tr_net_input(A.g[m * A.gd + j], A.clip_obs, A.gnz->mean[j], A.gnz->std[j], A.clip_g);
             }
             const int j = c - A.act_off;
             if (j >= 0 && j < A.ad) return (float)A.act[m * A.ad + j] / A.max_action;   // s8_gather, k_pack_scaled_actions
@@ -65,8 +67,6 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         },
         [&](int r, float q) { A.q[row0 + r] = q; });
 }
-
-#define EQ_MAX_EPISODES (1 << 24)
 
 // everything behind the entry's own checks (null arguments, contexts, the block's range): the remaining refusals in the order the
 // header lists them, then the one launch
@@ -82,8 +82,7 @@ static int episode_q_launch(const char *entry, hp_agent *a, hp_norm *on, hp_norm
     HP_REQUIRE(block_od < 0 || (block_od == on->size && block_gd == gn->size && block_ad == a->cfg.act_dim), HP_ERR_INVALID,
                "%s: the block has dimensions %d / %d / %d, normalizers and agent have %d / %d / %d", entry, block_od, block_gd, block_ad,
                (int)on->size, (int)gn->size, a->cfg.act_dim);
-    HP_REQUIRE(n >= 1 && n < EQ_MAX_EPISODES, HP_ERR_INVALID, "%s: n_episodes %lld outside [1, %d)", entry, (long long)n, EQ_MAX_EPISODES);
-    HP_REQUIRE(T >= 1 && T <= EQ_MAX_EPISODES, HP_ERR_INVALID, "%s: T %d outside [1, %d]", entry, (int)T, EQ_MAX_EPISODES);
+    HP_TRY(episode_check_shape(entry, n, T));
     const long long rows = (long long)n * T;
     HP_REQUIRE(rows < (1LL << 31), HP_ERR_INVALID, "%s: %lld steps are more than one launch holds (2^31)", entry, rows);
     static_assert(sizeof(s8eq::PolicyLds) <= 160 * 1024, "the policy slab's LDS fits a CU");
@@ -118,11 +117,8 @@ int hp_episode_q_block(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, in
     HP_SERIALISE(ro);
     HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx, HP_ERR_INVALID,
                "hp_episode_q_block: handles belong to different contexts");
-    HP_REQUIRE(first_episode >= 0 && n_episodes >= 1 && first_episode <= ro->n && n_episodes <= ro->n - first_episode, HP_ERR_INVALID,
-               "hp_episode_q_block: episodes [%lld, %lld) outside the block of %lld", (long long)first_episode,
-               (long long)(first_episode + n_episodes), (long long)ro->n);
-    struct { const double *b_obs, *b_ag, *b_g, *b_act; } at;
-    rollout_arrays_at(ro, first_episode, at);
+    RolloutArrays at;
+    HP_TRY(episode_block_range("hp_episode_q_block", ro, first_episode, n_episodes, at));
     return episode_q_launch("hp_episode_q_block", a, on, gn, net, at.b_obs, at.b_g, at.b_act, ro->od, ro->gd, ro->ad, n_episodes, ro->T,
                             clip_obs, q_dev);
 }

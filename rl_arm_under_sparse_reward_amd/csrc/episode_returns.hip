@@ -3,9 +3,8 @@
 // zero; whether Q(s_t, a_t) (episode_q.hip) tracks G_t, sits on the target clip -1 / (1 - gamma) (ddpg_agent.py:259-260) or
 // overestimates is what says that learning is happening.
 //
-// Step t = 0 .. T-1 of an episode compares ag[t + 1] with g[t]; s[t] is the squared distance exactly as k_episode_stats forms it
-// (products and sums rounded one by one, left to right over the goal components) and the reward is compute_reward's
-// (bmirobot_env_push_F.py:84-90) in float64: sparse -(d > thr) taken on s against squared_bound's threshold, dense -sqrt(s).
+// Step t = 0 .. T-1 of an episode compares ag[t + 1] with g[t]; s[t] is the squared distance (tr_sq_distance,
+// transition_device.h) and the reward is compute_reward's in float64 (hp_reward64 there).
 //   G_T = +0.0 (tail 0)  or  r[T-1] / (1 - gamma) (tail 1: the last step's reward held for ever, what an infinite-horizon critic is
 //   trained towards);   G_t = r[t] + gamma G_{t+1}  for t = T-1 .. 0, every operation rounded on its own.
 // The critic columns (HP_CRITIC_STATS) are accumulated in the SAME walk, t = T-1 down to 0, one accumulator per column with Q
@@ -13,7 +12,7 @@
 // -- so the host twin (synthetic.episode_returns / episode_critic_stats: plain loops) is compared bit for bit.
 #include <cmath>
 
-#include "internal.h"
+#include "episode_audit.h"
 
 struct EpisodeReturnsArgs {
     const double *ag, *g;          // [n][T + 1][gd], [n][T][gd], already offset to the first episode
@@ -24,13 +23,6 @@ struct EpisodeReturnsArgs {
     double gamma, q_floor;         // q_floor = -1 / (1 - gamma), the target clip (has_floor: gamma < 1)
     int T, gd, tail, has_floor;
 };
-
-// x of lane l, l wave-uniform
-__device__ __forceinline__ double er_lane_d(double x, int l) {
-    const long long b = __double_as_longlong(x);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), l);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 
 // k_episode_returns.  One wave per episode.  T is a run-time value (up to 2^24), so the episode is walked in chunks of 64 steps
 // from the last chunk down: the lanes form the chunk's 64 rewards side by side (lane l: step base + l; a wave reads one
@@ -55,23 +47,16 @@ __global__ __launch_bounds__(64) void k_episode_returns(const EpisodeReturnsArgs
         double r = 0.0;
         float qv = 0.f;
         if (lane < cnt) {
-            const double *a = ag + (long long)(t + 1) * gd, *b = g + (long long)t * gd;
-            double s = 0.0;
-            for (int c = 0; c < gd; ++c) {
-                const double d = __dsub_rn(a[c], b[c]);
-                const double sq = __dmul_rn(d, d);
-                s = (c == 0) ? sq : __dadd_rn(s, sq);
-            }
-            r = hp_reward64(s, A.sq_reward);
+            r = hp_reward64(tr_sq_distance(ag + (long long)(t + 1) * gd, g + (long long)t * gd, gd), A.sq_reward);
             if (q) qv = q[t];
         }
         if (first) {
-            if (A.tail) G = __ddiv_rn(er_lane_d(r, cnt - 1), __dsub_rn(1.0, gamma));
+            if (A.tail) G = __ddiv_rn(lane_read_d(r, cnt - 1), __dsub_rn(1.0, gamma));
             first = false;
         }
         double mine = 0.0;
         for (int i = cnt - 1; i >= 0; --i) {
-            G = __dadd_rn(er_lane_d(r, i), __dmul_rn(gamma, G));
+            G = __dadd_rn(lane_read_d(r, i), __dmul_rn(gamma, G));
             mine = (lane == i) ? G : mine;
             if (q) {
                 const double qd = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(qv), i));
@@ -98,30 +83,18 @@ __global__ __launch_bounds__(64) void k_episode_returns(const EpisodeReturnsArgs
     }
 }
 
-// k_episode_critic_summary.  One wave, and lane 0 walks the rows: every column's mean is the left-to-right float64 sum in episode
-// order divided by n (synthetic.episode_critic_summary is the same loop), like k_episode_stats_summary.
+// k_episode_critic_summary (episode_summary_body): the mean of every critic column (synthetic.episode_critic_summary)
+struct CriticSummaryTerm {
+    __device__ double operator()(const double *r, int k) const { return r[k]; }
+};
 __global__ __launch_bounds__(64) void k_episode_critic_summary(const double *__restrict__ stats, long long n, double *__restrict__ out) {
-    if (threadIdx.x != 0) return;
-    double sum[HP_CRITIC_STATS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (long long e = 0; e < n; ++e) {
-        const double *r = stats + e * HP_CRITIC_STATS;
-#pragma unroll
-        for (int k = 0; k < HP_CRITIC_STATS; ++k) sum[k] = __dadd_rn(sum[k], r[k]);
-    }
-    const double dn = (double)n;
-#pragma unroll
-    for (int k = 0; k < HP_CRITIC_STATS; ++k) out[k] = __ddiv_rn(sum[k], dn);
+    episode_summary_body(stats, n, out, CriticSummaryTerm{});
 }
-
-#define ER_MAX_EPISODES (1 << 24)
 
 static int episode_returns_launch(const char *entry, hipStream_t stream, const double *ag, const double *g, int64_t n, int32_t T,
                                   int32_t gd, double thr, int32_t reward_type, double gamma, int32_t tail, double *returns,
                                   const float *q, double *cstats) {
-    HP_REQUIRE(n >= 1 && n < ER_MAX_EPISODES, HP_ERR_INVALID, "%s: n_episodes %lld outside [1, %d)", entry, (long long)n, ER_MAX_EPISODES);
-    HP_REQUIRE(T >= 1 && T <= ER_MAX_EPISODES, HP_ERR_INVALID, "%s: T %d outside [1, %d]", entry, (int)T, ER_MAX_EPISODES);
-    HP_REQUIRE(gd >= 1 && gd <= HP_EPISODE_MAX_GOAL_DIM, HP_ERR_INVALID, "%s: goal_dim %d outside [1, %d]", entry, (int)gd,
-               HP_EPISODE_MAX_GOAL_DIM);
+    HP_TRY(episode_check_shape(entry, n, T, gd));
     HP_REQUIRE(reward_type == 0 || reward_type == 1, HP_ERR_INVALID, "%s: reward_type %d is neither 0 (sparse) nor 1 (dense)", entry,
                (int)reward_type);
     HP_REQUIRE(tail == 0 || tail == 1, HP_ERR_INVALID, "%s: tail %d is neither 0 (zero) nor 1 (persist)", entry, (int)tail);
@@ -155,22 +128,14 @@ int hp_episode_returns_block(hp_rollout *ro, int64_t first_episode, int64_t n_ep
                              double gamma, int32_t tail, double *returns_dev, const float *q_dev, double *critic_stats_dev) {
     HP_REQUIRE(ro && returns_dev, HP_ERR_INVALID, "hp_episode_returns_block: null argument");
     HP_SERIALISE(ro);
-    HP_REQUIRE(first_episode >= 0 && n_episodes >= 1 && first_episode <= ro->n && n_episodes <= ro->n - first_episode, HP_ERR_INVALID,
-               "hp_episode_returns_block: episodes [%lld, %lld) outside the block of %lld", (long long)first_episode,
-               (long long)(first_episode + n_episodes), (long long)ro->n);
-    struct { const double *b_obs, *b_ag, *b_g, *b_act; } at;
-    rollout_arrays_at(ro, first_episode, at);
+    RolloutArrays at;
+    HP_TRY(episode_block_range("hp_episode_returns_block", ro, first_episode, n_episodes, at));
     return episode_returns_launch("hp_episode_returns_block", ro->ctx->stream, at.b_ag, at.b_g, n_episodes, ro->T, ro->gd,
                                   distance_threshold, reward_type, gamma, tail, returns_dev, q_dev, critic_stats_dev);
 }
 
 int hp_episode_critic_summary(hp_ctx *ctx, const double *critic_stats_dev, int64_t n_episodes, double *summary_dev) {
-    HP_REQUIRE(ctx && critic_stats_dev && summary_dev, HP_ERR_INVALID, "hp_episode_critic_summary: null argument");
-    CtxGuard guard(ctx);
-    HP_REQUIRE(n_episodes >= 1, HP_ERR_INVALID, "hp_episode_critic_summary: n_episodes %lld is not positive", (long long)n_episodes);
-    hipLaunchKernelGGL(k_episode_critic_summary, dim3(1), dim3(64), 0, ctx->stream, critic_stats_dev, (long long)n_episodes, summary_dev);
-    HP_CHECK_HIP(hipGetLastError());
-    return HP_OK;
+    return episode_summary_launch("hp_episode_critic_summary", ctx, k_episode_critic_summary, critic_stats_dev, n_episodes, summary_dev);
 }
 
 }  // extern "C"

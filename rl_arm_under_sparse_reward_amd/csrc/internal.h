@@ -348,24 +348,8 @@ inline void rollout_arrays_at(const hp_rollout *ro, int64_t episode, Args &A) {
 }
 
 // smallest double s whose correctly rounded square root is > thr (strict) or >= thr (buffer.hip): the predicates d > thr and
-// !(d < thr) of compute_reward / _is_success in the squared domain
+// !(d < thr) of compute_reward / _is_success in the squared domain (the device side: hp_reward, transition_device.h)
 double squared_bound(double thr, bool strict);
-
-// Reward of a relabelled transition from the squared goal distance s (compute_reward, bmirobot_env_push_F.py:84-90):
-//   sq_threshold >= 0: sparse, -(d > thr) == -(s >= sq_threshold) with sq_threshold the smallest double whose correctly
-//                      rounded square root exceeds thr -- no square root on the device;
-//   sq_threshold <  0: dense, -d (the env returns it in float64; the learner narrows it to float32, ddpg_agent.py:243).
-#ifdef __HIPCC__
-__device__ __forceinline__ float hp_reward(double s, double sq_threshold) {
-    if (sq_threshold < 0.0) return (float)(-__dsqrt_rn(s));
-    return (s >= sq_threshold) ? -1.0f : -0.0f;
-}
-// the value compute_reward itself returns: float32 widened (sparse) or float64 -d (dense)
-__device__ __forceinline__ double hp_reward64(double s, double sq_threshold) {
-    if (sq_threshold < 0.0) return -__dsqrt_rn(s);
-    return (s >= sq_threshold) ? -1.0 : -0.0;
-}
-#endif
 
 // rank exchange (comm.hip): one RCCL communicator bound to the context's stream
 struct hp_comm {

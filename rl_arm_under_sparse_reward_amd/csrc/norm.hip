@@ -81,14 +81,13 @@ __global__ void k_norm_end(NormDev *nz, int size, double eps_sq, int std_f32) {
     if (c == 0) nz->total_count[0] = cnt;
 }
 
-// normalizer.normalize (:67-70): clip((v - mean) / std, -clip, clip), float64
+// normalizer.normalize (:67-70) on float64 rows: tr_normalize
 __global__ void k_norm_normalize(const NormDev *nz, const double *__restrict__ v, long long n, int size, double clip,
                                  double *out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int c = (int)(i % size);
-    const double z = __ddiv_rn(__dsub_rn(v[i], (double)nz->mean[c]), nz->std[c]);
-    out[i] = clipd(z, -clip, clip);
+    out[i] = tr_normalize(v[i], nz->mean[c], nz->std[c], clip);
 }
 
 __global__ void k_norm_init(NormDev *nz) {

@@ -1,13 +1,8 @@
 // norm_device.h -- device side of the running normalizer shared by norm.hip's kernels and the cycle-opening kernel
 // (cycle_open.hip).  Arithmetic contract: norm.hip's header.
 #pragma once
-#include "internal.h"
+#include "transition_device.h"
 #include "stage_block.h"
-
-__device__ __forceinline__ double clipd(double v, double lo, double hi) {
-    // np.clip == minimum(maximum(v, lo), hi)
-    return fmin(fmax(v, lo), hi);
-}
 
 // recompute_stats (normalizer.py:40-57) for one column, begin and end in one go (single rank: nothing to exchange in
 // between).  ls / lss / lc: the local accumulators as they stood; same expressions as k_norm_begin + k_norm_end.
@@ -76,8 +71,7 @@ __device__ __forceinline__ void norm_update_from_plan_body(
             const PlanRec p = sp[r];
             const int k = col - obs_dim;
             const double *src = col < obs_dim ? s_obs + ((long long)p.e * (T + 1) + p.t) * obs_dim + col
-                                              : (p.her ? s_ag + ((long long)p.e * (T + 1) + p.fut) * goal_dim + k
-                                                       : s_g + ((long long)p.e * T + p.t) * goal_dim + k);
+                                              : TR_GOAL_SRC(p, s_ag + k, s_g + k, T, goal_dim);
             const double x = SC1_STAGE ? __longlong_as_double(__hip_atomic_load(reinterpret_cast<const long long *>(src), __ATOMIC_RELAXED,
                                                                                  __HIP_MEMORY_SCOPE_AGENT))
                                        : *src;

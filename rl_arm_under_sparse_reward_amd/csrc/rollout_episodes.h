@@ -178,9 +178,9 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             s8ro::s8_policy_slab(A.P, L, (size_t)row0,
                 [&](int r, int c) -> float {
                     if (r >= nrows) return 0.f;  // an environment that sits this wave out
-                    if (c < OD) return s8ro::s8_policy_input(E.obs[r][c], A.P.clip_obs, A.P.onz->mean[c], A.P.onz->std[c], A.P.clip_o);
+                    if (c < OD) return tr_net_input(E.obs[r][c], A.P.clip_obs, A.P.onz->mean[c], A.P.onz->std[c], A.P.clip_o);
                     const int j = c - OD;
-                    return s8ro::s8_policy_input(E.g[r][j], A.P.clip_obs, A.P.gnz->mean[j], A.P.gnz->std[j], A.P.clip_g);
+                    return tr_net_input(E.g[r][j], A.P.clip_obs, A.P.gnz->mean[j], A.P.gnz->std[j], A.P.clip_g);
                 },
                 [&](int r, int j, float a) { E.pi[r][j] = a; });
             if (part) {

@@ -123,6 +123,7 @@ struct PolicyArgs {
 };
 
 #include "slab8_split_args.h"
+#include "transition_device.h"   // the arithmetic of a gathered row, one definition for every slab height's namespace
 
 #endif  // RLARM_SLAB8_SHARED
 
@@ -536,7 +537,7 @@ __device__ __forceinline__ void s8_load(float *l, int ld, int width, const float
     }
 }
 
-// HER gather for the rows of a slab (same arithmetic as k_gather_fused); one wavefront per row
+// HER gather for the rows of a slab (arithmetic: transition_device.h); one wavefront per row
 // this thread's row of the index plan: the first load of the kernel (everything else in the gather depends on it).
 // Unconditional (rows past the batch re-read the last record, plan_any is never null): a load under a branch is
 // merged with its default through a register copy, which makes the compiler wait for it on the spot.
@@ -558,11 +559,14 @@ __device__ __forceinline__ void s8_gather(float *xin, const GatherSrc &G, const 
     const long long e = rc.e;
     const int t = rc.t, od = G.obs_dim, gd = G.goal_dim;
     const double *obs_row = G.obs + (e * (G.T + 1) + t + (which == 0 ? 1 : 0)) * od;
-    const double *g_src = rc.her ? G.ag + (e * (G.T + 1) + rc.fut) * gd : G.g + (e * G.T + t) * gd;
+    const double *g_src = TR_GOAL_SRC(rc, G.ag, G.g, G.T, gd);
     if (l < ldx) {
         const int c = l;
         float x = 0.f;
         if (live) {
+            // tr_net_input (transition_device.h), written out twice: G lies in the kernel's argument block, and with the clips read
+            // once per call instead of once per use the compiler lays out k_fb_slab8's scalar loads of that block differently
+            // (SGPR spill counts 101 -> 78, 116 -> 87; each of the two calls alone moves them, profiles/transition_arithmetic_refactor.txt)
             if (c < od) {
                 double v = fmin(fmax(obs_row[c], -G.clip_obs), G.clip_obs);
                 v = __ddiv_rn(__dsub_rn(v, (double)G.onz->mean[c]), G.onz->std[c]);
@@ -581,16 +585,7 @@ __device__ __forceinline__ void s8_gather(float *xin, const GatherSrc &G, const 
     }
     if (which == 1 && l == 63) {
         float rew = 0.f;
-        if (live) {
-            const double *ag_next = G.ag + (e * (G.T + 1) + t + 1) * gd;
-            double s = 0.0;
-            for (int c = 0; c < gd; ++c) {
-                const double d = __dsub_rn(ag_next[c], g_src[c]);
-                const double sq = __dmul_rn(d, d);
-                s = (c == 0) ? sq : __dadd_rn(s, sq);
-            }
-            rew = hp_reward(s, G.sq_threshold);
-        }
+        if (live) rew = hp_reward(tr_sq_distance(G.ag + (e * (G.T + 1) + t + 1) * gd, g_src, gd), G.sq_threshold);
         G.R[m] = rew;
         if (rew_lds) rew_lds[r] = rew;
     }
@@ -644,8 +639,8 @@ __device__ __forceinline__ void s8_trunk(const float *xin, const NetLayout &l, c
 // forward fragment copies into the dX copies without draining.  Arithmetic and summation order are those of
 // the separate forward and backward kernels this one replaced (same device functions): it reproduced their results bit for bit.
 
-// HER gather of rows [g * per, (g + 1) * per) of a minibatch into global input sets (same arithmetic as s8_gather:
-// her.py:26-38, ddpg_agent.py:228-243, normalizer.py:67-70).  One wavefront per row, 4 rows in flight per wavefront.
+// HER gather of rows [g * per, (g + 1) * per) of a minibatch into global input sets (arithmetic: transition_device.h).
+// One wavefront per row, 4 rows in flight per wavefront.
 __device__ __forceinline__ void s8_gather_ahead(const GatherSrc &G, float *XT, float *XA, float *XP, int ldx, int act_off,
                                                 int act_dim, float max_action, int g, int ng) {
     const int wave = threadIdx.x >> 6, c = threadIdx.x & 63;
@@ -667,7 +662,7 @@ __device__ __forceinline__ void s8_gather_ahead(const GatherSrc &G, float *XT, f
             const long long e = rec[k].e;
             const int t = rec[k].t;
             const double *obs0 = G.obs + (e * (G.T + 1) + t) * od;
-            const double *g_src = rec[k].her ? G.ag + (e * (G.T + 1) + rec[k].fut) * gd : G.g + (e * G.T + t) * gd;
+            const double *g_src = TR_GOAL_SRC(rec[k], G.ag, G.g, G.T, gd);
             const double *ag_next = G.ag + (e * (G.T + 1) + t + 1) * gd;
             // address-selected, unconditional loads (padding lanes re-read element 0)
             const double *p0 = is_obs ? obs0 + od + c : (is_goal ? g_src + (c - od) : obs0);
@@ -685,12 +680,8 @@ __device__ __forceinline__ void s8_gather_ahead(const GatherSrc &G, float *XT, f
             if (c < ldx) {
                 float x0 = 0.f, x1 = 0.f;
                 if (is_obs || is_goal) {
-                    double a = fmin(fmax(v0[k], -G.clip_obs), G.clip_obs);
-                    a = __ddiv_rn(__dsub_rn(a, (double)mu), sd);
-                    x0 = (float)fmin(fmax(a, -G.clip_range), G.clip_range);
-                    double b = fmin(fmax(v1[k], -G.clip_obs), G.clip_obs);
-                    b = __ddiv_rn(__dsub_rn(b, (double)mu), sd);
-                    x1 = (float)fmin(fmax(b, -G.clip_range), G.clip_range);
+                    x0 = tr_net_input(v0[k], G.clip_obs, mu, sd, G.clip_range);
+                    x1 = tr_net_input(v1[k], G.clip_obs, mu, sd, G.clip_range);
                 } else if (is_act) {
                     x1 = (float)v1[k] / max_action;
                 }
@@ -700,15 +691,7 @@ __device__ __forceinline__ void s8_gather_ahead(const GatherSrc &G, float *XT, f
                 }
                 XA[(size_t)m * ldx + c] = x1;
             }
-            // reward: d^2 summed in index order by lane 0 (values of lanes 0..gd-1 via shuffles, same operation order
-            // as the in-kernel gather)
-            const double d = __dsub_rn(an[k], gs[k]);
-            const double sq = __dmul_rn(d, d);
-            double ssum = 0.0;
-            for (int j = 0; j < gd; ++j) {
-                const double sj = __shfl(sq, j);
-                ssum = (j == 0) ? sj : __dadd_rn(ssum, sj);
-            }
+            const double ssum = tr_sq_distance_lanes(tr_sq_term(an[k], gs[k]), 0, gd);   // lanes 0 .. gd - 1 hold the squares
             if (c == 0) G.R[m] = hp_reward(ssum, G.sq_threshold);
         }
     }
@@ -1019,13 +1002,6 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 #endif  // S8_DEVICE_ONLY
 
 #if S8_NRG == 1
-// one network input out of a float64 row value (ddpg_agent._preproc_inputs :163-171, normalizer.py:67-70)
-__device__ __forceinline__ float s8_policy_input(double raw, double clip_obs, float mean, double std, double clip) {
-    double t = fmin(fmax(raw, -clip_obs), clip_obs);
-    t = __ddiv_rn(__dsub_rn(t, (double)mean), std);
-    return (float)fmin(fmax(t, -clip), clip);
-}
-
 // The LDS of one policy slab (k_policy_slab8; k_rollout_episodes keeps one for all its timesteps)
 struct PolicyLds {
     float xin[S8_ROWS * S8_LDX] __attribute__((aligned(16)));
@@ -1116,9 +1092,9 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         [&](int r, int c) -> float {
             const size_t m = row0 + r;
             if (P.x) return P.x[m * (P.od + P.gd) + c];
-            if (c < P.od) return s8_policy_input(P.obs[m * P.od + c], P.clip_obs, P.onz->mean[c], P.onz->std[c], P.clip_o);
+            if (c < P.od) return tr_net_input(P.obs[m * P.od + c], P.clip_obs, P.onz->mean[c], P.onz->std[c], P.clip_o);
             const int j = c - P.od;
-            return s8_policy_input(P.g[m * P.gd + j], P.clip_obs, P.gnz->mean[j], P.gnz->std[j], P.clip_g);
+            return tr_net_input(P.g[m * P.gd + j], P.clip_obs, P.gnz->mean[j], P.gnz->std[j], P.clip_g);
         },
         [&](int r, int j, float a) { P.actions[(row0 + r) * P.act_dim + j] = a; });
 }
