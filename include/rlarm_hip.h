@@ -579,6 +579,48 @@ int hp_episode_returns_block(hp_rollout *ro, int64_t first_episode, int64_t n_ep
                              double *critic_stats_dev);
 int hp_episode_critic_summary(hp_ctx *ctx, const double *critic_stats_dev, int64_t n_episodes, double *summary_dev);
 
+/* ---- policy audit on the device ----------------------------------------------------------------
+ * What the actor's objective sees of an episode block: pi(s_t) and Q(s_t, pi(s_t)) beside the recorded action and hp_episode_q's
+ * Q(s_t, a_t) -- whether the critic ranks a demonstration's action above the policy's (the Q-filter), how far the recorded
+ * actions lie from the policy, whether the actor saturates its tanh; the two terms of the actor loss (ddpg_agent.py:265-267).
+ *
+ * hp_episode_policy: pi_dev[e][t][j] (float32) = max_action * tanh(actor(normalise(obs[e][t] | g[e][t]))) and q_pi_dev[e][t]
+ * (float32) = critic(the same input, (max_action * tanh) / max_action) for t = 0 .. T-1 of n_episodes episodes in ONE launch:
+ * the forward half of an update's actor-side chain (same device functions, 4-row slabs, the action input formed in float32
+ * exactly as there) on rows that enter it as hp_episode_q's do.  obs_dev is [n_episodes][T + 1][obs_dim], g_dev
+ * [n_episodes][T][goal_dim], float64 and contiguous.  target 0: online actor and critic; 1: target actor and target critic.
+ * hp_episode_policy_block is the same on episodes [first_episode, first_episode + n_episodes) of a block.  Both asynchronous on
+ * the context's stream (or a borrowed one), behind whatever wrote the weights; nothing is allocated.  Refusals are
+ * hp_episode_q's, naming the entry point (target outside {0, 1} takes the place of the net).
+ *
+ * hp_episode_policy_stats: stats_dev [n][HP_POLICY_STATS] (float64) out of pi_dev, q_pi_dev, the recorded actions_dev
+ * [n][T][act_dim] (float64) and q_dev [n][T] (float32, hp_episode_q's output on the same episodes; may be NULL: [1] and [2] are
+ * then NaN).  With M = (double)(float)max_action:
+ *   [0] q_pi_mean        sum_t Q(s_t, pi(s_t)) / T
+ *   [1] advantage_mean   sum_t (Q(s_t, pi(s_t)) - Q(s_t, a_t)) / T
+ *   [2] q_filter_share   #{t : Q(s_t, a_t) > Q(s_t, pi(s_t))} / T (float32 compare)
+ *   [3] action_gap_mean  (sum_t sqrt(sum_j d_j d_j)) / M / T, d_j = a[t][j] - pi[t][j]
+ *   [4] saturated_share  #{(t, j) : |pi[t][j]| >= sat * M} / (T act_dim), sat in [0, 1]
+ *   [5] action_l2_mean   sum_t (sum_j v_j v_j / act_dim) / T, v_j = pi[t][j] / M
+ * every float32 widened to float64, every sum started at 0 and accumulated in ascending t (inner j ascending), every operation
+ * rounded on its own: the order is fixed and synthetic.episode_policy_stats is the same loop, so the bits are the host twin's.  One
+ * wave per episode.  hp_episode_policy_stats_block takes the actions of a block's episodes.  hp_episode_policy_summary reduces
+ * n_episodes rows to the six column means, left to right in episode order (synthetic.episode_policy_summary).  All asynchronous,
+ * nothing allocated; HP_ERR_INVALID, naming the entry point, for a null argument (q_dev excepted), n_episodes or T out of range
+ * as for hp_episode_stats, act_dim outside [1, HP_POLICY_MAX_ACT_DIM], max_action not positive and finite, sat outside [0, 1],
+ * episodes outside the block. */
+#define HP_POLICY_STATS 6
+#define HP_POLICY_MAX_ACT_DIM 256
+int hp_episode_policy(hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, int32_t target, const double *obs_dev, const double *g_dev,
+                      int64_t n_episodes, int32_t T, double clip_obs, float *pi_dev, float *q_pi_dev);
+int hp_episode_policy_block(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, int32_t target, int64_t first_episode,
+                            int64_t n_episodes, double clip_obs, float *pi_dev, float *q_pi_dev);
+int hp_episode_policy_stats(hp_ctx *ctx, const float *pi_dev, const float *q_pi_dev, const double *actions_dev, const float *q_dev,
+                            int64_t n_episodes, int32_t T, int32_t act_dim, double max_action, double sat, double *stats_dev);
+int hp_episode_policy_stats_block(hp_rollout *ro, const float *pi_dev, const float *q_pi_dev, const float *q_dev,
+                                  int64_t first_episode, int64_t n_episodes, double max_action, double sat, double *stats_dev);
+int hp_episode_policy_summary(hp_ctx *ctx, const double *policy_stats_dev, int64_t n_episodes, double *summary_dev);
+
 /* Policy calls that do not queue behind training: hp_agent_policy_snapshot copies the online actor and both normalizers'
  * statistics (stream-ordered with the updates, no host wait); hp_agent_act_snapshot evaluates the most recent COMPLETE
  * snapshot on a second stream, so a feeder can step its environments while a training cycle runs (its policy lags the

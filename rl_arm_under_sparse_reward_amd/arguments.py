@@ -44,6 +44,7 @@ class Args:
     device_reset: bool = False          # native device environments: reset on the device, all waves of a call in one launch
     eval_metrics: bool = False          # learn(): also keep return, goal distances and first success of every evaluation (agent.eval_metrics)
     eval_critic: bool = False           # learn(): also audit the critic on every evaluation's episodes, Q beside the discounted return (agent.eval_critic)
+    audit_policy: bool = False          # learn(): once per epoch, audit the policy on the last cycle's exploring episodes, pi(s) and Q(s, pi(s)) beside the recorded actions (agent.policy_audit)
     state_full_every: int = 0           # learn() with args.state_path: 0 = every save is a full state; k >= 1 = every k-th save
                                         # rewrites the base, the saves between rewrite one cumulative delta beside it (train_state.py)
     grad_reduce: str = "sum"            # data-parallel gradient exchange: "sum" = utils.py:47 (reference), or "mean"

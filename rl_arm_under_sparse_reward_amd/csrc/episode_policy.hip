@@ -1,0 +1,244 @@
+// episode_policy.hip -- what the actor's objective sees of an episode block, computed where the block lies (hp_episode_policy,
+// hp_episode_policy_block): pi(s_t) and Q(s_t, pi(s_t)) for t = 0 .. T-1 of every episode in ONE launch, and the columns that set
+// them beside the recorded actions and hp_episode_q's Q(s_t, a_t) (hp_episode_policy_stats, hp_episode_policy_stats_block,
+// hp_episode_policy_summary): whether the critic ranks a demonstration's action above the policy's (the Q-filter), how far the
+// recorded actions lie from the policy (what exploration or a script adds), and whether the actor saturates its tanh -- the two terms
+// of the actor loss, -Q(s, pi(s)) and (pi / max_action)^2 (ddpg_agent.py:265-267), on real episodes.
+//
+// k_episode_policy is the forward half of the actor-side chain of an update (slab8_actor_side.inc) inside the frame of k_episode_q
+// (episode_q.hip): flat row m = e T + t, workgroup b owns rows 4b .. 4b+3, obs has T + 1 rows per episode and g T, one PolicyLds.
+// s8_policy_slab runs on the slab with the inputs of s8_gather (tr_net_input: clip, subtract, divide, clip in float64, one rounding
+// each); its emit writes pi[m][j] and puts u_j = (max_action * th_j) / max_action, float32, at act_off of the row's input in the
+// LDS -- the expression and the place of the actor-side chain.  One barrier, which is the entry condition of s8_critic_slab (the
+// actor's trunk has drained its weight ring, nothing reads the LDS any more), and s8_critic_slab runs on the same four rows.
+//
+// The normalised obs | g columns are KEPT, not recomputed: the actor's trunk reads the input rows and leaves them alone, the
+// critic's input has the same columns at the same places (its own begin at act_off >= od + gd, and s8_policy_slab zeroed what lies
+// between), so the critic's input function hands every thread back the word it is about to store.  The float64 divisions of
+// tr_net_input -- what a gather is bound by -- are done once per row, as in an update.
+//
+// Which weights: the four buffers episode_q.hip's header names (a->fragF / a->params, a->fragFT / a->targets), the actor's segment at
+// 0 and the critic's at la.total, on the context's stream behind whatever wrote them.  target: both target networks together.
+#include <cmath>
+
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wundefined-inline"   // agent_device.h declares the 32-row engine's fragment map, which no code here calls
+#include "agent_device.h"
+#pragma clang diagnostic pop
+
+// the 4-row slab's device functions (no kernel of slab8.h is compiled here)
+#define S8_DEVICE_ONLY
+#define S8_NRG 1
+#define S8_NS s8ep
+#include "slab8.h"
+#undef S8_NRG
+#undef S8_NS
+#undef S8_DEVICE_ONLY
+
+#include "episode_audit.h"
+
+static_assert(HP_POLICY_STATS == EPISODE_COLS, "one summary loop");
+
+struct EpisodePolicyArgs {
+    PolicyArgs P;                  // the actor: obs / g at the first episode (indexed here, not by s8_policy_slab), rows = n T
+    float *pi, *q_pi;              // [n][T][ad], [n][T]
+    NetLayout lc;
+    int T, act_off, ca;            // the critic's segment starts at ca = la.total
+};
+
+__global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_episode_policy(const EpisodePolicyArgs A) {
+    __shared__ s8ep::PolicyLds L;
+    const long long row0 = (long long)blockIdx.x * 4;
+    const PolicyArgs &P = A.P;
+    s8ep::s8_policy_slab(P, L, (size_t)row0,
+        [&](int r, int c) -> float {
+            const long long m = row0 + r, e = m / A.T;
+            const int t = (int)(m - e * A.T);
+            if (c < P.od) return tr_net_input(P.obs[(e * (A.T + 1) + t) * P.od + c], P.clip_obs, P.onz->mean[c], P.onz->std[c], P.clip_o);
+            const int j = c - P.od;
+            return tr_net_input(P.g[m * P.gd + j], P.clip_obs, P.gnz->mean[j], P.gnz->std[j], P.clip_g);
+        },
+        [&](int r, int j, float a) {
+            A.pi[(row0 + r) * P.act_dim + j] = a;
+            L.xin[r * S8_LDX + A.act_off + j] = a / P.max_action;   // a = max_action * th: the actor-side chain's u
+        });
+    s8ep::s8_sync();
+    s8ep::s8_critic_slab(P.net, A.lc, A.ca, P.H, (long long)P.rows, L, (size_t)row0,
+        [&](int r, int c) -> float { return L.xin[r * S8_LDX + c]; },
+        [&](int r, float q) { A.q_pi[row0 + r] = q; });
+}
+
+// everything behind the entry's own checks (null arguments, contexts, the block's range): the remaining refusals in hp_episode_q's
+// order, then the one launch
+static int episode_policy_launch(const char *entry, hp_agent *a, hp_norm *on, hp_norm *gn, int32_t target, const double *obs,
+                                 const double *g, int block_od, int block_gd, int block_ad, int64_t n, int32_t T, double clip_obs,
+                                 float *pi, float *q_pi) {
+    HP_REQUIRE(target == 0 || target == 1, HP_ERR_INVALID, "%s: target %d is neither 0 (online) nor 1 (target networks)", entry, (int)target);
+    HP_REQUIRE(a->slab8 && a->H == 256 && a->ldx <= 48 && a->cfg.act_dim <= 4, HP_ERR_STATE,
+               "%s: the agent is not slab-shaped (hidden %d, padded input width %d, act_dim %d, engine %s)", entry, a->H, a->ldx,
+               a->cfg.act_dim, a->slab8 ? "slab8" : "other");
+    HP_REQUIRE(on->size + gn->size == a->xdim, HP_ERR_INVALID, "%s: normalizer sizes %d+%d do not match the network input %d", entry,
+               (int)on->size, (int)gn->size, a->xdim);
+    HP_REQUIRE(block_od < 0 || (block_od == on->size && block_gd == gn->size && block_ad == a->cfg.act_dim), HP_ERR_INVALID,
+               "%s: the block has dimensions %d / %d / %d, normalizers and agent have %d / %d / %d", entry, block_od, block_gd, block_ad,
+               (int)on->size, (int)gn->size, a->cfg.act_dim);
+    HP_TRY(episode_check_shape(entry, n, T));
+    const long long rows = (long long)n * T;
+    HP_REQUIRE(rows < (1LL << 31), HP_ERR_INVALID, "%s: %lld steps are more than one launch holds (2^31)", entry, rows);
+    static_assert(sizeof(s8ep::PolicyLds) <= 160 * 1024, "the policy slab's LDS fits a CU");
+    EpisodePolicyArgs A;
+    memset(&A, 0, sizeof(A));
+    PolicyArgs &P = A.P;
+    P.obs = obs; P.g = g;
+    P.rows = (int)rows;
+    P.od = on->size; P.gd = gn->size;
+    P.onz = on->d; P.gnz = gn->d;
+    P.clip_obs = clip_obs > 0 ? clip_obs : INFINITY; P.clip_o = on->clip; P.clip_g = gn->clip;
+    P.net = target ? SlabNetPtrs{a->fragFT, nullptr, a->targets} : SlabNetPtrs{a->fragF, a->fragD, a->params};
+    P.la = a->la; P.H = a->H; P.act_dim = a->cfg.act_dim; P.max_action = (float)a->cfg.max_action;
+    A.pi = pi; A.q_pi = q_pi;
+    A.lc = a->lc; A.T = T; A.act_off = a->act_off; A.ca = a->la.total;
+    hipLaunchKernelGGL(k_episode_policy, dim3((unsigned)((rows + 3) / 4)), dim3(S8_THREADS), 0, a->ctx->stream, A);
+    HP_CHECK_HIP(hipGetLastError());
+    return HP_OK;
+}
+
+// ---- the columns (HP_POLICY_STATS) --------------------------------------------------------------------------------------------------
+struct PolicyStatsArgs {
+    const float *pi, *q_pi, *q;    // [n][T][ad], [n][T], [n][T] or nullptr
+    const double *act;             // [n][T][ad], already offset to the first episode
+    double *stats;                 // [n][HP_POLICY_STATS]
+    double max_action, sat_bound;  // (double)(float)max_action; sat * max_action
+    int T, ad;
+};
+
+// k_episode_policy_stats.  One wave per episode, T a run-time value walked in chunks of 64 steps as k_episode_returns walks it, here
+// from the first chunk up.  The lanes form their steps' terms side by side -- lane l: step base + l, its inner sums over j ascending
+// -- then the sums over t run wave-uniformly over the chunk in ascending t, step base + i taking its terms out of lane i
+// (v_readlane: no LDS, no barrier).  Float64 sums of values that are not small integers depend on that order; the twin
+// (synthetic.episode_policy_stats) is the same loop.  The two counts are exact whatever the order.
+__global__ __launch_bounds__(64) void k_episode_policy_stats(const PolicyStatsArgs A) {
+    const int lane = threadIdx.x, T = A.T, ad = A.ad;
+    const long long e = blockIdx.x;
+    const float *pi = A.pi + e * (long long)T * ad, *q_pi = A.q_pi + e * (long long)T;
+    const float *q = A.q ? A.q + e * (long long)T : nullptr;
+    const double *act = A.act + e * (long long)T * ad;
+    double sum_qpi = 0.0, sum_adv = 0.0, sum_gap = 0.0, sum_l2 = 0.0;
+    long long filtered = 0, saturated = 0;
+    for (int base = 0; base < T; base += 64) {
+        const int cnt = T - base < 64 ? T - base : 64;
+        const int t = base + lane;
+        double qpd = 0.0, adv = 0.0, gap = 0.0, l2 = 0.0;
+        int filt = 0, nsat = 0;
+        if (lane < cnt) {
+            const float qp = q_pi[t];
+            qpd = (double)qp;
+            if (q) {
+                const float qv = q[t];
+                adv = __dsub_rn(qpd, (double)qv);
+                filt = qv > qp ? 1 : 0;
+            }
+            double dd = 0.0, vv = 0.0;
+            for (int j = 0; j < ad; ++j) {
+                const double p = (double)pi[(long long)t * ad + j];
+                const double d = __dsub_rn(act[(long long)t * ad + j], p);
+                const double v = __ddiv_rn(p, A.max_action);
+                dd = __dadd_rn(dd, __dmul_rn(d, d));
+                vv = __dadd_rn(vv, __dmul_rn(v, v));
+                nsat += fabs(p) >= A.sat_bound ? 1 : 0;
+            }
+            gap = __dsqrt_rn(dd);
+            l2 = __ddiv_rn(vv, (double)ad);
+        }
+        for (int i = 0; i < cnt; ++i) {
+            sum_qpi = __dadd_rn(sum_qpi, lane_read_d(qpd, i));
+            sum_adv = __dadd_rn(sum_adv, lane_read_d(adv, i));
+            sum_gap = __dadd_rn(sum_gap, lane_read_d(gap, i));
+            sum_l2 = __dadd_rn(sum_l2, lane_read_d(l2, i));
+            filtered += __builtin_amdgcn_readlane(filt, i);
+            saturated += __builtin_amdgcn_readlane(nsat, i);
+        }
+    }
+    if (lane == 0) {
+        double *out = A.stats + e * HP_POLICY_STATS;
+        const double dT = (double)T, none = __longlong_as_double(0x7ff8000000000000LL);
+        out[0] = __ddiv_rn(sum_qpi, dT);
+        out[1] = q ? __ddiv_rn(sum_adv, dT) : none;
+        out[2] = q ? __ddiv_rn((double)filtered, dT) : none;
+        out[3] = __ddiv_rn(__ddiv_rn(sum_gap, A.max_action), dT);
+        out[4] = __ddiv_rn((double)saturated, (double)((long long)T * ad));
+        out[5] = __ddiv_rn(sum_l2, dT);
+    }
+}
+
+// k_episode_policy_summary (episode_summary_body): the mean of every column (synthetic.episode_policy_summary)
+struct PolicySummaryTerm {
+    __device__ double operator()(const double *r, int k) const { return r[k]; }
+};
+__global__ __launch_bounds__(64) void k_episode_policy_summary(const double *__restrict__ stats, long long n, double *__restrict__ out) {
+    episode_summary_body(stats, n, out, PolicySummaryTerm{});
+}
+
+static int policy_stats_launch(const char *entry, hipStream_t stream, const float *pi, const float *q_pi, const double *act,
+                               const float *q, int64_t n, int32_t T, int32_t ad, double max_action, double sat, double *stats) {
+    HP_TRY(episode_check_shape(entry, n, T));
+    HP_REQUIRE(ad >= 1 && ad <= HP_POLICY_MAX_ACT_DIM, HP_ERR_INVALID, "%s: act_dim %d outside [1, %d]", entry, (int)ad,
+               HP_POLICY_MAX_ACT_DIM);
+    HP_REQUIRE(max_action > 0.0 && std::isfinite(max_action), HP_ERR_INVALID, "%s: max_action %g is not a positive number", entry, max_action);
+    HP_REQUIRE(sat >= 0.0 && sat <= 1.0, HP_ERR_INVALID, "%s: sat %g outside [0, 1]", entry, sat);
+    PolicyStatsArgs A;
+    A.pi = pi; A.q_pi = q_pi; A.q = q; A.act = act; A.stats = stats;
+    A.max_action = (double)(float)max_action;       // the networks' own: float32
+    A.sat_bound = sat * A.max_action;
+    A.T = T; A.ad = ad;
+    hipLaunchKernelGGL(k_episode_policy_stats, dim3((unsigned)n), dim3(64), 0, stream, A);
+    HP_CHECK_HIP(hipGetLastError());
+    return HP_OK;
+}
+
+extern "C" {
+
+int hp_episode_policy(hp_agent *a, hp_norm *on, hp_norm *gn, int32_t target, const double *obs_dev, const double *g_dev,
+                      int64_t n_episodes, int32_t T, double clip_obs, float *pi_dev, float *q_pi_dev) {
+    HP_REQUIRE(a && on && gn && obs_dev && g_dev && pi_dev && q_pi_dev, HP_ERR_INVALID, "hp_episode_policy: null argument");
+    HP_SERIALISE(a);
+    HP_REQUIRE(on->ctx == a->ctx && gn->ctx == a->ctx, HP_ERR_INVALID, "hp_episode_policy: handles belong to different contexts");
+    return episode_policy_launch("hp_episode_policy", a, on, gn, target, obs_dev, g_dev, -1, -1, -1, n_episodes, T, clip_obs, pi_dev,
+                                 q_pi_dev);
+}
+
+int hp_episode_policy_block(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, int32_t target, int64_t first_episode,
+                            int64_t n_episodes, double clip_obs, float *pi_dev, float *q_pi_dev) {
+    HP_REQUIRE(ro && a && on && gn && pi_dev && q_pi_dev, HP_ERR_INVALID, "hp_episode_policy_block: null argument");
+    HP_SERIALISE(ro);
+    HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx, HP_ERR_INVALID,
+               "hp_episode_policy_block: handles belong to different contexts");
+    RolloutArrays at;
+    HP_TRY(episode_block_range("hp_episode_policy_block", ro, first_episode, n_episodes, at));
+    return episode_policy_launch("hp_episode_policy_block", a, on, gn, target, at.b_obs, at.b_g, ro->od, ro->gd, ro->ad, n_episodes, ro->T,
+                                 clip_obs, pi_dev, q_pi_dev);
+}
+
+int hp_episode_policy_stats(hp_ctx *ctx, const float *pi_dev, const float *q_pi_dev, const double *actions_dev, const float *q_dev,
+                            int64_t n_episodes, int32_t T, int32_t act_dim, double max_action, double sat, double *stats_dev) {
+    HP_REQUIRE(ctx && pi_dev && q_pi_dev && actions_dev && stats_dev, HP_ERR_INVALID, "hp_episode_policy_stats: null argument");
+    CtxGuard guard(ctx);
+    return policy_stats_launch("hp_episode_policy_stats", ctx->stream, pi_dev, q_pi_dev, actions_dev, q_dev, n_episodes, T, act_dim,
+                               max_action, sat, stats_dev);
+}
+
+int hp_episode_policy_stats_block(hp_rollout *ro, const float *pi_dev, const float *q_pi_dev, const float *q_dev, int64_t first_episode,
+                                  int64_t n_episodes, double max_action, double sat, double *stats_dev) {
+    HP_REQUIRE(ro && pi_dev && q_pi_dev && stats_dev, HP_ERR_INVALID, "hp_episode_policy_stats_block: null argument");
+    HP_SERIALISE(ro);
+    RolloutArrays at;
+    HP_TRY(episode_block_range("hp_episode_policy_stats_block", ro, first_episode, n_episodes, at));
+    return policy_stats_launch("hp_episode_policy_stats_block", ro->ctx->stream, pi_dev, q_pi_dev, at.b_act, q_dev, n_episodes, ro->T,
+                               ro->ad, max_action, sat, stats_dev);
+}
+
+int hp_episode_policy_summary(hp_ctx *ctx, const double *policy_stats_dev, int64_t n_episodes, double *summary_dev) {
+    return episode_summary_launch("hp_episode_policy_summary", ctx, k_episode_policy_summary, policy_stats_dev, n_episodes, summary_dev);
+}
+
+}  // extern "C"

@@ -144,6 +144,8 @@ class ddpg_agent:
         self.success_rates = []
         self.eval_metrics = []           # args.eval_metrics: one dict per evaluation, keyed by synthetic.EPISODE_SUMMARY
         self.eval_critic = []            # args.eval_critic: one dict per evaluation, keyed by synthetic.CRITIC_STATS
+        self.policy_audit = []           # args.audit_policy: one dict per epoch, keyed by synthetic.POLICY_STATS
+        self._policy_audit_pending = None
         self.model_path = os.path.join(self.args.save_dir, self.args.env_name)
 
     def close_comm(self):
@@ -814,6 +816,64 @@ class ddpg_agent:
                                                    _tail_kind(tail), p(returns), p(q), p(stats)))
         return stats.cpu().numpy(), q.cpu().numpy(), returns.cpu().numpy()
 
+    def episode_policy(self, episodes, target=False, first=0, n=None):
+        """What the actor's objective sees of episodes [first, first + n) of a `DeviceEpisodes`: (pi [n, T, act] float32, the
+        policy's action at every recorded state, q_pi [n, T] float32, Q(s_t, pi(s_t))), device tensors from one launch on
+        torch's current stream (hp_episode_policy_block) -- the forward half of an update's actor-side chain on rows that enter
+        it exactly as they enter an update.  `target=True`: target actor and target critic.  No copy, no synchronisation."""
+        first = int(first)
+        n = len(episodes) - first if n is None else int(n)
+        dev = torch.device("cuda", self.ctx.device_id)
+        pi = torch.empty((max(n, 0), episodes.T, int(self.env_params['action'])), dtype=torch.float32, device=dev)
+        q_pi = torch.empty((max(n, 0), episodes.T), dtype=torch.float32, device=dev)
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_episode_policy_block(episodes.h, self.h, self.o_norm.h, self.g_norm.h, 1 if target else 0, first, n,
+                                                        float(self.args.clip_obs), C.c_void_p(pi.data_ptr()),
+                                                        C.c_void_p(q_pi.data_ptr())))
+        return pi, q_pi
+
+    def episode_policy_stats(self, episodes, target=False, sat=0.99, first=0, n=None):
+        """The policy audited on episodes [first, first + n) of a `DeviceEpisodes` (a collection's, an evaluation's, or
+        `generate_demos(...).episodes`, where the q_filter_share column is the Q-filter rate): (stats [n, 6] float64 in the
+        columns of `synthetic.POLICY_STATS`, pi, q_pi, q), device tensors from three launches (`episode_q`, `episode_policy`,
+        the columns: hp_episode_policy_stats_block).  No copy, no synchronisation."""
+        q = self.episode_q(episodes, target=target, first=first, n=n)
+        pi, q_pi = self.episode_policy(episodes, target=target, first=first, n=n)
+        stats = torch.empty((q.shape[0], _lib.POLICY_STATS), dtype=torch.float64, device=q.device)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_episode_policy_stats_block(episodes.h, p(pi), p(q_pi), p(q), int(first), q.shape[0],
+                                                              float(self.env_params['action_max']), float(sat), p(stats)))
+        return stats, pi, q_pi, q
+
+    def episode_policy_stats_host(self, episode_batch, target=False, sat=0.99):
+        """`episode_policy_stats` for host episodes -- the four arrays `collect_episodes` returns, or a feeder slot's (obs, ag, g,
+        actions): they are uploaded, the same kernels run (hp_episode_q, hp_episode_policy, hp_episode_policy_stats) and the
+        result comes back as numpy (stats [n, 6] float64, pi [n, T, act] float32, q_pi [n, T] float32, q [n, T] float32).
+        Synchronises."""
+        obs, ag, g, act = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)) for a in episode_batch[:4])
+        if (any(a.ndim != 3 for a in (obs, ag, g, act)) or len({a.shape[0] for a in (obs, ag, g, act)}) != 1
+                or not obs.shape[1] == ag.shape[1] == g.shape[1] + 1 == act.shape[1] + 1 or ag.shape[2] != g.shape[2]):
+            raise ValueError("episode_policy_stats_host: obs [n, T+1, obs], ag [n, T+1, goal], g [n, T, goal] and actions [n, T, act] expected")
+        if (obs.shape[2], g.shape[2], act.shape[2]) != tuple(int(self.env_params[k]) for k in ('obs', 'goal', 'action')):
+            raise ValueError("episode_policy_stats_host: the episodes' dimensions differ from the agent's")
+        dev = torch.device("cuda", self.ctx.device_id)
+        obs, g, act = obs.to(dev), g.to(dev), act.to(dev)
+        n, T, ad = act.shape
+        q = torch.empty((n, T), dtype=torch.float32, device=dev)
+        q_pi = torch.empty((n, T), dtype=torch.float32, device=dev)
+        pi = torch.empty((n, T, ad), dtype=torch.float32, device=dev)
+        stats = torch.empty((n, _lib.POLICY_STATS), dtype=torch.float64, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_episode_q(self.h, self.o_norm.h, self.g_norm.h, NET_CRITIC_TARGET if target else NET_CRITIC,
+                                             p(obs), p(g), p(act), n, T, float(self.args.clip_obs), p(q)))
+            _lib.check(self.lib.hp_episode_policy(self.h, self.o_norm.h, self.g_norm.h, 1 if target else 0, p(obs), p(g), n, T,
+                                                  float(self.args.clip_obs), p(pi), p(q_pi)))
+            _lib.check(self.lib.hp_episode_policy_stats(self.ctx.h, p(pi), p(q_pi), p(act), p(q), n, T, ad,
+                                                        float(self.env_params['action_max']), float(sat), p(stats)))
+        return stats.cpu().numpy(), pi.cpu().numpy(), q_pi.cpu().numpy(), q.cpu().numpy()
+
     def _collect_all_waves(self, vec_env, eps, n_total, streams, how):
         """All `n_total` episodes as one launch (hp_rollout_waves), or the few the launch cap dictates; the environments are
         reset inside it.  Returns the n_total success flags."""
@@ -937,8 +997,10 @@ class ddpg_agent:
         print("initial buffer size:", self.buffer.current_size)                  # :97
         if self.vec_env is not None:
             return self._learn_device(share, state_path, first_epoch)
+        audit = bool(getattr(self.args, "audit_policy", False))
         for epoch in range(first_epoch, self.args.n_epochs):
             start = time.time()
+            episodes = None
             for _ in range(self.args.n_cycles):
                 episodes = self.collect_episodes(self.args.num_rollouts_per_mpi, epoch)
                 if share:
@@ -946,6 +1008,8 @@ class ddpg_agent:
                 self.train_cycle(episodes)
                 if share:
                     np.random.set_state(self.rng.get_state())
+            if audit and episodes is not None:
+                self._policy_audit_pending = episodes    # host arrays: audited behind _finish_epoch's synchronise
             self._finish_epoch(epoch, start, state_path)
 
     def _finish_epoch(self, epoch, start, state_path, before_save=None):
@@ -954,6 +1018,7 @@ class ddpg_agent:
         self.ctx.synchronize()
         self.check_exchange()
         print(str(time.time() - start))
+        self._record_policy_audit()      # args.audit_policy: before the evaluation, which may collect into the same block
         rate = self._eval_agent()
         self.success_rates.append(rate)
         if self.comm.rank == 0:
@@ -975,10 +1040,22 @@ class ddpg_agent:
 
         if share:
             self.rng.set_state(np.random.get_state())
+        audit = bool(getattr(self.args, "audit_policy", False))
         for epoch in range(first_epoch, self.args.n_epochs):
             start = time.time()
+            eps = None
             for _ in range(self.args.n_cycles):
-                self.train_cycle(self.collect_episodes_device(n_rollouts=self.args.num_rollouts_per_mpi, epoch=epoch))
+                eps = self.collect_episodes_device(n_rollouts=self.args.num_rollouts_per_mpi, epoch=epoch)
+                self.train_cycle(eps)
+            if audit and eps is not None:
+                # args.audit_policy: the last cycle's exploring episodes under the networks as they now stand -- four launches behind
+                # the cycle, nothing waits; the 48 bytes are read behind _finish_epoch's synchronise
+                stats = self.episode_policy_stats(eps, first=0, n=self.args.num_rollouts_per_mpi)[0]
+                summary = torch.empty(_lib.POLICY_STATS, dtype=torch.float64, device=stats.device)
+                with self.ctx.torch_bridge():
+                    _lib.check(self.lib.hp_episode_policy_summary(self.ctx.h, C.c_void_p(stats.data_ptr()), stats.shape[0],
+                                                                  C.c_void_p(summary.data_ptr())))
+                self._policy_audit_pending = summary
             self._finish_epoch(epoch, start, state_path, before_save=hand_back)
         hand_back()
 
@@ -1026,6 +1103,24 @@ class ddpg_agent:
             local = local.to(f"cuda:{self.ctx.device_id}")
         self.comm.allreduce_mean_(local)
         self.eval_metrics.append(dict(zip(EPISODE_SUMMARY, (float(v) for v in local.cpu().numpy()))))
+
+    def _record_policy_audit(self):
+        """args.audit_policy: the epoch's pending audit -- the device path's summary (six means, already computed) or the host
+        path's episodes (audited now: `episode_policy_stats_host`) -- averaged over the ranks like the success rate, onto
+        `policy_audit`"""
+        pending, self._policy_audit_pending = self._policy_audit_pending, None
+        if pending is None:
+            return
+        from .synthetic import POLICY_STATS, episode_policy_summary
+        if isinstance(pending, torch.Tensor):
+            summary = pending.cpu().numpy()
+        else:
+            summary = episode_policy_summary(self.episode_policy_stats_host(pending)[0])
+        local = torch.tensor(np.asarray(summary, dtype=np.float64), dtype=torch.float64)
+        if self.comm.world_size > 1:
+            local = local.to(f"cuda:{self.ctx.device_id}")
+        self.comm.allreduce_mean_(local)
+        self.policy_audit.append(dict(zip(POLICY_STATS, (float(v) for v in local.cpu().numpy()))))
 
     def _record_eval_critic(self, summary):
         """One evaluation's critic summary (this rank's six means), averaged over the ranks like the success rate, onto `eval_critic`"""

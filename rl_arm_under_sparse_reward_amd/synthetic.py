@@ -16,6 +16,8 @@ reward values and near-threshold distances in the parity tests).
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 ENV_PARAMS = {"obs": 27, "goal": 3, "action": 4, "action_max": 0.5, "max_timesteps": 100}
@@ -602,6 +604,76 @@ def episode_critic_summary(stats):
     total = np.zeros(len(CRITIC_STATS), dtype=np.float64)
     for row in stats:
         for k in range(len(CRITIC_STATS)):
+            total[k] = total[k] + row[k]
+    return total / np.float64(stats.shape[0])
+
+
+POLICY_STATS = ("q_pi_mean", "advantage_mean", "q_filter_share", "action_gap_mean", "saturated_share", "action_l2_mean")
+
+
+def episode_policy_stats(pi, q_pi, actions, max_action, q=None, sat=0.99):
+    """The host twin of hp_episode_policy_stats, as plain loops: `pi` [n, T, act] float32 (the policy's actions), `q_pi` [n, T]
+    float32 (Q(s, pi(s))), `actions` [n, T, act] float64 (the recorded ones) and optionally `q` [n, T] float32 (Q(s, a),
+    `episode_q` of the same episodes) -> [n, 6] float64 in the columns of POLICY_STATS.  max_action is the networks' float32,
+    widened; every float32 is widened, every sum starts at 0 and runs in ascending t (inner j ascending), one rounding per
+    operation, and is divided once at the end: q_pi_mean; advantage_mean, the mean of Q(s, pi(s)) - Q(s, a); q_filter_share, the
+    share of steps with Q(s, a) > Q(s, pi(s)) compared in float32; action_gap_mean, (sum of the Euclidean distances a - pi) /
+    max_action / T; saturated_share, the share of components with |pi| >= sat * max_action; action_l2_mean, the mean over t of
+    sum_j (pi_j / max_action)^2 / act -- the regulariser's term of the actor loss (ddpg_agent.py:267).  Without `q` the second and
+    third column are NaN."""
+    pi, q_pi, actions = np.asarray(pi), np.asarray(q_pi), np.asarray(actions, dtype=np.float64)
+    if (pi.dtype != np.float32 or q_pi.dtype != np.float32 or pi.ndim != 3 or q_pi.shape != pi.shape[:2] or actions.shape != pi.shape
+            or pi.shape[1] < 1 or pi.shape[2] < 1):
+        raise ValueError("episode_policy_stats: pi [n, T, act] float32, q_pi [n, T] float32 and actions [n, T, act] expected")
+    if q is not None:
+        q = np.asarray(q)
+        if q.dtype != np.float32 or q.shape != q_pi.shape:
+            raise ValueError("episode_policy_stats: q [n, T] float32 expected")
+    sat = float(sat)
+    if not 0.0 <= sat <= 1.0:
+        raise ValueError(f"sat {sat} outside [0, 1]")
+    ma = float(np.float32(max_action))       # Python floats from here on: IEEE float64, one rounding per operation
+    if not (ma > 0.0 and math.isfinite(ma)):
+        raise ValueError(f"max_action {max_action} is not a positive number")
+    bound = sat * ma
+    n, T, ad = pi.shape
+    out = np.empty((n, len(POLICY_STATS)), dtype=np.float64)
+    for e in range(n):
+        ps, acts, qps = pi[e].astype(np.float64).tolist(), actions[e].tolist(), q_pi[e].astype(np.float64).tolist()
+        qs = q[e].astype(np.float64).tolist() if q is not None else None
+        sum_qpi = sum_adv = sum_gap = sum_l2 = 0.0
+        filtered = saturated = 0
+        for t in range(T):
+            sum_qpi = sum_qpi + qps[t]
+            if qs is not None:
+                sum_adv = sum_adv + (qps[t] - qs[t])
+                filtered += 1 if q[e, t] > q_pi[e, t] else 0
+            dd = vv = 0.0
+            for j in range(ad):
+                p = ps[t][j]
+                d = acts[t][j] - p
+                v = p / ma
+                dd = dd + d * d
+                vv = vv + v * v
+                saturated += 1 if abs(p) >= bound else 0
+            sum_gap = sum_gap + math.sqrt(dd)
+            sum_l2 = sum_l2 + vv / float(ad)
+        dT = float(T)
+        out[e] = (sum_qpi / dT, sum_adv / dT if qs is not None else float("nan"),
+                  float(filtered) / dT if qs is not None else float("nan"), sum_gap / ma / dT,
+                  float(saturated) / float(T * ad), sum_l2 / dT)
+    return out
+
+
+def episode_policy_summary(stats):
+    """The host twin of hp_episode_policy_summary: the six column means over the episodes, each a left-to-right float64 sum in
+    episode order divided by their number."""
+    stats = np.asarray(stats, dtype=np.float64)
+    if stats.ndim != 2 or stats.shape[1] != len(POLICY_STATS) or stats.shape[0] < 1:
+        raise ValueError("episode_policy_summary: stats [n >= 1, 6] expected")
+    total = np.zeros(len(POLICY_STATS), dtype=np.float64)
+    for row in stats:
+        for k in range(len(POLICY_STATS)):
             total[k] = total[k] + row[k]
     return total / np.float64(stats.shape[0])
 

@@ -1,0 +1,495 @@
+"""The policy audit on the device (csrc/episode_policy.hip: hp_episode_policy, hp_episode_policy_block, hp_episode_policy_stats,
+hp_episode_policy_stats_block, hp_episode_policy_summary; ddpg_agent.episode_policy, episode_policy_stats,
+episode_policy_stats_host, args.audit_policy).
+
+pi and Q(s, pi(s)) are compared with the oracle's actor and critic (oracle.ddpg_update.actor_forward, critic_forward: the critic
+on the ORACLE's action, the whole chain on the host) on inputs prepared in numpy, at the project's own bar for a forward, rtol 1e-5
+/ atol 1e-6, no row excluded.  On noise-free episodes both are compared bit for bit with what the rollout recorded and with
+episode_q.  The columns and their summary are compared bit for bit with the host twins (synthetic.episode_policy_stats /
+episode_policy_summary): their orders are fixed."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import bits
+from gpu_common import ctx, fresh_rng, make_shape_episodes
+from oracle import ddpg_update as oupd
+from rl_arm_under_sparse_reward_amd import _lib
+from rl_arm_under_sparse_reward_amd import train_state as ts
+from rl_arm_under_sparse_reward_amd.arguments import Args
+from rl_arm_under_sparse_reward_amd.ddpg_agent import NET_ACTOR, NET_ACTOR_TARGET, NET_CRITIC, NET_CRITIC_TARGET, ddpg_agent
+from rl_arm_under_sparse_reward_amd.device_env import (NativePickPlaceVecEnv, NativePointMassVecEnv, NativePushBlockVecEnv, PushBlockVecEnv,
+                                                       generate_demos)
+from rl_arm_under_sparse_reward_amd.synthetic import POLICY_STATS, episode_policy_stats, episode_policy_summary
+from test_gpu_device_rollout import make, primed
+from test_gpu_episode_critic import oracle_q, refused, shaped_agent
+from test_gpu_episode_stats import learner
+from test_gpu_pick_place import agent_on as pick_agent_on
+from test_gpu_push_block import CONTACT, agent_on as push_agent_on
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+RTOL, ATOL = 1e-5, 1e-6
+NAN = np.uint64(0x7FF8000000000000)
+p = lambda t: C.c_void_p(t.data_ptr())
+host = lambda *ts_: [v.cpu().numpy() for v in ts_]
+
+
+# ------------------------------------------------------------------------------------------ helpers
+def oracle_policy(agent, obs, g, target=False):
+    """The oracle's actor, and its critic on that action, on rows prepared in numpy from the agent's CURRENT parameters
+    (hp_agent_get_params) and normalizer statistics: (pi [n, T, act], q_pi [n, T])"""
+    n, T = g.shape[:2]
+    amax = float(agent.env_params['action_max'])
+    _, x, _ = oracle_q(agent, obs, g, np.zeros((n, T, int(agent.env_params['action']))), target)
+    actor = agent.actor_target_network if target else agent.actor_network
+    critic = agent.critic_target_network if target else agent.critic_network
+    pa = {k: v.detach().clone() for k, v in actor.state_dict().items()}
+    pc = {k: v.detach().clone() for k, v in critic.state_dict().items()}
+    xt = torch.from_numpy(x)
+    pi = oupd.actor_forward(pa, xt, amax)
+    q_pi = oupd.critic_forward(pc, xt, pi, amax)
+    return pi.numpy().reshape(n, T, -1), q_pi.numpy().reshape(n, T), x
+
+
+def raw_policy(agent, obs, g, target=False):
+    """hp_episode_policy on uploaded arrays, into poisoned tensors, in torch's stream order"""
+    o, gg = (torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(DEV) for v in (obs, g))
+    n, T = g.shape[:2]
+    pi = torch.full((n, T, int(agent.env_params['action'])), float("nan"), dtype=torch.float32, device=DEV)
+    q_pi = torch.full((n, T), float("nan"), dtype=torch.float32, device=DEV)
+    with agent.ctx.torch_bridge():
+        _lib.check(agent.lib.hp_episode_policy(agent.h, agent.o_norm.h, agent.g_norm.h, 1 if target else 0, p(o), p(gg), n, T,
+                                               float(agent.args.clip_obs), p(pi), p(q_pi)))
+    return pi.cpu().numpy(), q_pi.cpu().numpy()
+
+
+def assert_close(got, want, what):
+    err = np.abs(got.astype(np.float64) - want.astype(np.float64))
+    print(f"{what}: max |device - oracle| {err.max():.3e} on values up to {np.abs(want).max():.3e}")
+    assert got.dtype == np.float32 and got.shape == want.shape and np.isfinite(got).all(), what
+    assert np.allclose(got, want, rtol=RTOL, atol=ATOL), (what, float(err.max()))
+    return float(err.max())
+
+
+def assert_policy(agent, obs, g, pi, q_pi, what, target=False):
+    want_pi, want_q, x = oracle_policy(agent, obs, g, target)
+    return assert_close(pi, want_pi, what + ": pi"), assert_close(q_pi, want_q, what + ": Q(s, pi(s))"), x
+
+
+def move_actor(agent, seed):
+    """An online actor moved away from its initialisation (far enough that some tanh saturate) and a target actor made different
+    from it by one soft update"""
+    rs = np.random.RandomState(seed)
+    flat = agent._get_flat(NET_ACTOR)
+    agent._set_flat(NET_ACTOR, flat * 1.5 + rs.normal(0, 0.01, flat.size).astype(np.float32))
+    agent._soft_update_target_network()
+    assert not np.array_equal(agent._get_flat(NET_ACTOR), agent._get_flat(NET_ACTOR_TARGET))
+    assert not np.array_equal(agent._get_flat(NET_CRITIC), agent._get_flat(NET_CRITIC_TARGET))
+    return agent
+
+
+def twin_of(agent, stats, pi, q_pi, q, actions, sat=0.99):
+    """The six columns of an audit against the twin fed the device's pi, q_pi, q and the recorded actions, by bytes"""
+    stats, pi, q_pi, q = (v.cpu().numpy() if isinstance(v, torch.Tensor) else v for v in (stats, pi, q_pi, q))
+    want = episode_policy_stats(pi, q_pi, actions, agent.env_params['action_max'], q=q, sat=sat)
+    assert stats.dtype == np.float64 and stats.shape == (pi.shape[0], 6) and np.array_equal(bits(stats), bits(want)), (stats, want)
+    return want
+
+
+def device_summary(c, stats):
+    out = torch.full((6,), float("nan"), dtype=torch.float64, device=DEV)
+    with c.torch_bridge():
+        _lib.check(c.lib.hp_episode_policy_summary(c.h, p(stats), stats.shape[0], p(out)))
+    return out.cpu().numpy()
+
+
+SHAPES = [(3, 5), (1, 1)]     # 15 rows: the last slab has three, slabs straddle episodes, T / T + 1 strides; and a single row
+
+
+# ------------------------------------------------------------------------------------------ 1. against the oracle
+@pytest.mark.parametrize("obs_dim,goal_dim,act_dim,amax,clips", [(27, 3, 4, 0.5, None), (20, 1, 3, 0.7, None), (29, 3, 1, 2.0, None),
+                                                                  (27, 3, 4, 0.5, (0.8, 1.5))])
+def test_pi_and_q_pi_of_random_blocks_equal_the_oracle(obs_dim, goal_dim, act_dim, amax, clips):
+    kw = dict(clip_obs=clips[0], clip_range=clips[1]) if clips else {}
+    agent = move_actor(shaped_agent(obs_dim, goal_dim, act_dim, amax, **kw), obs_dim)
+    rs = np.random.RandomState(17)
+    far = [0.0, 0.0]
+    for n, T in SHAPES:
+        obs = rs.normal(0.1, 0.6, (n, T + 1, obs_dim))
+        obs[:, T] = 1e30                                   # the closing observation of every episode: no step reads it
+        g = rs.normal(0.2, 0.5, (n, T, goal_dim))
+        for target in (False, True):
+            pi, q_pi = raw_policy(agent, obs, g, target)
+            e_pi, e_q, x = assert_policy(agent, obs, g, pi, q_pi, f"{(obs_dim, goal_dim, act_dim, amax)} n {n} T {T} target {target}", target)
+            far = [max(far[0], e_pi), max(far[1], e_q)]
+            assert (np.abs(pi) <= np.float32(amax)).all()
+            if clips and n * T > 4:
+                assert np.mean(np.abs(obs[:, :T]) > clips[0]) > 0.1 and np.mean(np.abs(x) == clips[1]) > 0.05      # both clips bite
+    a, b = raw_policy(agent, obs, g, False), raw_policy(agent, obs, g, True)
+    assert not np.array_equal(a[0], b[0]) and not np.array_equal(a[1], b[1])
+    print(f"largest deviation seen: pi {far[0]:.3e}, Q(s, pi(s)) {far[1]:.3e}")
+
+
+# ------------------------------------------------------------------------------------------ 2. after training
+def test_pi_and_q_pi_after_training_cycles_read_the_stepped_weights():
+    """Two train_cycles on a small buffer at batch 64, one in each launch form of an update sequence (3 updates: chain launch + tile
+    launch per update; 13: the split launch), then both pairs of networks against the oracle on the parameters
+    hp_agent_get_params returns: a fragment copy that a launch form did not step would fail here."""
+    T, n_eps, batch = 20, 8, 64
+    torch.manual_seed(0)
+    env = {"obs": 27, "goal": 3, "action": 4, "action_max": 0.5, "max_timesteps": T}
+    agent = ddpg_agent(Args(batch_size=batch, buffer_size=4 * n_eps * T, lr_critic=0.01, lr_actor=0.01), None, env, rng=fresh_rng(3))
+    before = agent._get_flat(NET_ACTOR)
+    form, forms = C.c_int32(), []
+    for cycle, n_batches in enumerate((3, 13)):
+        agent.train_cycle(make_shape_episodes(n_eps, 27, 3, 4, T, seed=20 + cycle), n_batches=n_batches)
+        _lib.check(agent.lib.hp_agent_update_form(agent.h, n_batches, C.byref(form)))
+        forms.append(form.value)
+    print(f"batch {batch}: update forms of the two sequences {forms}; engine {agent.engine()['engine']}")
+    assert forms == [0, 1], forms
+    after, after_t = agent._get_flat(NET_ACTOR), agent._get_flat(NET_ACTOR_TARGET)
+    assert np.abs(after - before).max() > 1e-3 and not np.array_equal(after, after_t) and not np.array_equal(after_t, before)
+    obs, _, g, _ = make_shape_episodes(5, 27, 3, 4, 33, seed=31)
+    for target in (True, False):
+        pi, q_pi = raw_policy(agent, obs, g, target)
+        assert_policy(agent, obs, g, pi, q_pi, f"batch {batch} target {target}", target)
+    want = oracle_policy(agent, obs, g)[0]
+    agent._set_flat(NET_ACTOR, before)
+    moved = np.abs(raw_policy(agent, obs, g)[0] - want).max()            # the bar does tell the weights before from those after
+    assert moved > 100 * ATOL, moved
+
+
+# ------------------------------------------------------------------------------------------ 3. self-consistency, bit for bit
+@pytest.mark.parametrize("form", ["stepped", "fused", "waves"])
+def test_noise_free_episodes_give_back_their_own_actions_and_q(form):
+    """Noise-free episodes (epoch 0: no clip of the action) with no update between collection and audit: the rollout's policy
+    slab and this launch's run the same device functions on the same bits -- native observations lie inside clip_obs -- so pi is
+    the recorded action, Q(s, pi(s)) is episode_q's Q(s, a), and three columns are exactly 0."""
+    cls = PushBlockVecEnv if form == "stepped" else NativePushBlockVecEnv
+    a = push_agent_on(cls, 4, env_kw=CONTACT, reset=(form == "waves"))
+    eps = a.collect_episodes_device(n_rollouts=7, explore=False, epoch=0)
+    assert a.rollout_form == ("stepped" if form == "stepped" else "fused") and (form != "waves" or a.rollout_launches == 1)
+    obs, _, g, actions = eps.numpy()
+    assert np.abs(obs).max() < float(a.args.clip_obs)
+    stats, pi, q_pi, q = a.episode_policy_stats(eps)
+    assert stats.is_cuda and pi.dtype == q_pi.dtype == torch.float32
+    assert tuple(pi.shape) == (7, eps.T, actions.shape[2]) and tuple(q_pi.shape) == (7, eps.T)
+    stats, pi, q_pi, q = host(stats, pi, q_pi, q)
+    assert np.array_equal(bits(pi), bits(actions.astype(np.float32))) and np.array_equal(pi.astype(np.float64), actions)
+    assert np.array_equal(bits(q_pi), bits(q)) and np.array_equal(bits(q), bits(a.episode_q(eps).cpu().numpy()))
+    assert not stats[:, 1:4].any(), stats
+    twin_of(a, stats, pi, q_pi, q, actions)
+    assert_policy(a, obs, g, pi, q_pi, form)
+    t_stats, t_pi, t_q_pi, t_q = host(*a.episode_policy_stats(eps, target=True))        # the target pair against the oracle's
+    assert_policy(a, obs, g, t_pi, t_q_pi, form + " target", target=True)
+    twin_of(a, t_stats, t_pi, t_q_pi, t_q, actions)
+
+
+# ------------------------------------------------------------------------------------------ 4. exploring episodes
+def raw_stats(c, pi, q_pi, actions, q, amax, sat):
+    """hp_episode_policy_stats on uploaded arrays (q may be None), and the summary of its rows"""
+    n, T, ad = pi.shape
+    d = [torch.from_numpy(np.ascontiguousarray(v)).to(DEV) if v is not None else None for v in (pi, q_pi, actions, q)]
+    stats = torch.full((n, 6), float("nan"), dtype=torch.float64, device=DEV)
+    with c.torch_bridge():
+        _lib.check(c.lib.hp_episode_policy_stats(c.h, p(d[0]), p(d[1]), p(d[2]), p(d[3]) if q is not None else None, n, T, ad,
+                                                 float(amax), float(sat), p(stats)))
+    return stats.cpu().numpy(), device_summary(c, stats)
+
+
+@pytest.mark.parametrize("T", [1, 63, 64, 65, 130])
+def test_columns_of_exploring_pick_and_place_episodes_equal_the_twin(T):
+    """Less than a chunk of steps, exactly one, one more, and a third chunk; five episodes on three environments with their
+    exploration streams; with and without Q(s, a); the default bound of saturation, two that bite and both ends."""
+    a = move_actor(pick_agent_on(NativePickPlaceVecEnv, 3, T=T, random_eps=0.3), 7)
+    eps = a.collect_episodes_device(n_rollouts=5, epoch=0)
+    actions = eps.numpy()[3]
+    stats, pi, q_pi, q = a.episode_policy_stats(eps)
+    want = twin_of(a, stats, pi, q_pi, q, actions)
+    assert (want[:, 3] > 0).all() and ((0 <= want[:, [2, 4]]) & (want[:, [2, 4]] <= 1)).all() and (want[:, 5] > 0).all(), want
+    assert np.array_equal(bits(device_summary(a.ctx, stats)), bits(episode_policy_summary(want)))
+    pi, q_pi, q = host(pi, q_pi, q)
+    amax = a.env_params['action_max']
+    for sat in (0.99, 0.3, 0.0, 1.0):
+        sub = a.episode_policy_stats(eps, sat=sat, first=1, n=3)
+        want = twin_of(a, *sub, actions[1:4], sat=sat)
+        assert np.array_equal(bits(want), bits(episode_policy_stats(pi[1:4], q_pi[1:4], actions[1:4], amax, q=q[1:4], sat=sat)))
+    mid = float(np.median(np.abs(pi))) / float(np.float32(amax))       # a bound about half of the components reach
+    got, summary = raw_stats(a.ctx, pi, q_pi, actions, None, amax, mid)
+    want = episode_policy_stats(pi, q_pi, actions, amax, sat=mid)
+    assert np.array_equal(bits(got), bits(want)) and (np.ascontiguousarray(got[:, 1:3]).view(np.uint64) == NAN).all()
+    assert np.array_equal(bits(summary), bits(episode_policy_summary(want))) and np.isnan(summary[1:3]).all()
+    assert 0 < mid < 1 and 0 < want[:, 4].mean() < 1, (mid, want[:, 4])       # the bound bites
+
+
+# ------------------------------------------------------------------------------------------ 5. sub-ranges of a block
+def block_policy(a, eps, first, n, rows):
+    pi = torch.full((rows, eps.T, int(a.env_params['action'])), float("nan"), dtype=torch.float32, device=DEV)
+    q_pi = torch.full((rows, eps.T), float("nan"), dtype=torch.float32, device=DEV)
+    with a.ctx.torch_bridge():
+        _lib.check(a.lib.hp_episode_policy_block(eps.h, a.h, a.o_norm.h, a.g_norm.h, 0, first, n, float(a.args.clip_obs), p(pi[first:]),
+                                                 p(q_pi[first:])))
+    return pi.cpu().numpy(), q_pi.cpu().numpy()
+
+
+def test_sub_ranges_of_a_push_block_collection():
+    """Nine episodes of T = 20 on eight environments.  first * T is a multiple of 4 for every `first`, so every sub-range starts
+    on a slab boundary of the whole-block call; a block of T = 5 has sub-ranges that do not."""
+    a = push_agent_on(NativePushBlockVecEnv, 8, env_kw=CONTACT, random_eps=0.3)
+    eps = a.collect_episodes_device(n_rollouts=9)
+    batch = eps.numpy()
+    whole = host(*a.episode_policy(eps))
+    assert_policy(a, batch[0], batch[2], *whole, "whole block")
+    for first, n in ((3, 4), (0, 1), (8, 1), (1, 8)):
+        got = block_policy(a, eps, first, n, 9)
+        for x, w in zip(got, whole):
+            assert (first * eps.T) % 4 == 0 and np.array_equal(bits(x[first:first + n]), bits(w[first:first + n])), (first, n)
+            assert np.isnan(x[:first]).all() and np.isnan(x[first + n:]).all()           # nothing outside [first, first + n)
+        for x, w in zip(host(*a.episode_policy(eps, first=first, n=n)), whole):
+            assert np.array_equal(bits(x), bits(w[first:first + n]))
+    for x, w in zip(host(*a.episode_policy(eps, first=7)), whole):
+        assert np.array_equal(bits(x), bits(w[7:]))
+    # T = 5: episodes 1, 2, 3 start in the middle of a slab of the whole-block call
+    torch.manual_seed(0)
+    b = make(NativePointMassVecEnv(3, seed=4, device=DEV, max_timesteps=5), T=5)
+    primed(b)
+    eps = b.collect_episodes_device(n_rollouts=6, explore=False)
+    batch = eps.numpy()
+    whole = host(*b.episode_policy(eps))
+    want = oracle_policy(b, batch[0], batch[2])[:2]
+    assert_policy(b, batch[0], batch[2], *whole, "T = 5, whole block")
+    for first, n in ((1, 2), (2, 3), (3, 3), (4, 1), (5, 1)):
+        got = block_policy(b, eps, first, n, 6)
+        for x, w, o, name in zip(got, whole, want, ("pi", "Q(s, pi(s))")):
+            assert_close(x[first:first + n], o[first:first + n], f"T = 5, episodes [{first}, {first + n}): {name}")
+            assert np.isnan(x[:first]).all() and np.isnan(x[first + n:]).all()
+            same = np.array_equal(bits(x[first:first + n]), bits(w[first:first + n]))
+            print(f"first {first} (row {first * 5}, {'on' if first * 5 % 4 == 0 else 'off'} a slab boundary): {name} bit-equal to the whole-block call: {same}")
+            if first * 5 % 4 == 0:
+                assert same
+
+
+# ------------------------------------------------------------------------------------------ 6. demonstrations, host episodes
+def test_the_q_filter_rate_of_pick_and_place_demonstrations():
+    env = NativePickPlaceVecEnv(4, seed=0, device=DEV, max_timesteps=100, step_scale=0.2)
+    env.enable_device_reset(ctx())
+    demos = generate_demos(env, 4)
+    assert demos.kept == 4
+    torch.manual_seed(0)
+    a = make(env, T=100)
+    primed(a)
+    stats, pi, q_pi, q = a.episode_policy_stats(demos.episodes)
+    obs, ag, g, actions, info = demos.numpy()
+    want = twin_of(a, stats, pi, q_pi, q, actions)
+    assert_policy(a, obs, g, *host(pi, q_pi), "demonstrations")
+    assert ((0 <= want[:, 2]) & (want[:, 2] <= 1)).all() and (want[:, 3] > 0).all()       # a script is not the policy
+    print("Q-filter rate of the demonstrations per episode:", want[:, 2])
+
+
+def test_host_episodes_through_the_same_kernels():
+    """Episodes collected on the device, read back and handed in as host arrays: the same bits as the block's own audit"""
+    a = move_actor(pick_agent_on(NativePickPlaceVecEnv, 3, T=30, random_eps=0.3), 7)
+    eps = a.collect_episodes_device(n_rollouts=5, epoch=0)
+    batch = eps.numpy()
+    for target, sat in ((False, 0.99), (True, 0.5)):
+        on_device = host(*a.episode_policy_stats(eps, target=target, sat=sat))
+        out = a.episode_policy_stats_host(batch, target=target, sat=sat)
+        assert all(isinstance(v, np.ndarray) for v in out) and len(out) == 4
+        for x, y in zip(out, on_device):
+            assert x.dtype == y.dtype and np.array_equal(bits(x), bits(y))
+        twin_of(a, *out, batch[3], sat=sat)
+    one = a.episode_policy_stats_host([v[:1, :2] if i in (0, 1) else v[:1, :1] for i, v in enumerate(batch)])       # n = 1, T = 1
+    twin_of(a, *one, batch[3][:1, :1])
+    with pytest.raises(ValueError, match="episode_policy_stats_host: obs"):
+        a.episode_policy_stats_host([batch[0], batch[1][:, :-1], batch[2], batch[3]])
+    with pytest.raises(ValueError, match="dimensions differ from the agent's"):
+        a.episode_policy_stats_host([batch[0][:, :, :20], batch[1], batch[2], batch[3]])
+
+
+# ------------------------------------------------------------------------------------------ 7. learn()
+def tree_bytes(root):
+    out = {}
+    for d, _, files in os.walk(root):
+        for f in files:
+            out[os.path.relpath(os.path.join(d, f), root)] = open(os.path.join(d, f), "rb").read()
+    return out
+
+
+def test_audit_policy_is_the_twins_and_changes_nothing_else(tmp_path, capsys):
+    """Two epochs of learn() on two native environments with the option on and off (eval_metrics and eval_critic on in both): the
+    same rates, metrics, printed lines, checkpoint files, training state and streams to the byte, an empty list with it off; with it
+    on, one dict per epoch.  A third run whose audit call is wrapped keeps what the device computed on each epoch's last collection:
+    its entries are the same, and they are the twins' on those arrays."""
+    kw = dict(eval_metrics=True, eval_critic=True)
+    on = learner(tmp_path, "on", False, audit_policy=True, state_path=str(tmp_path / "on.npz"), **kw)
+    off = learner(tmp_path, "off", False, state_path=str(tmp_path / "off.npz"), **kw)
+    probe = learner(tmp_path, "probe", False, audit_policy=True, **kw)
+    kept, collected = [], []
+    audit, collect = probe.episode_policy_stats, probe.collect_episodes_device
+
+    def audit_and_keep(eps, **kwargs):
+        out = audit(eps, **kwargs)
+        assert eps is collected[-1][0] and collected[-1][1] and kwargs["n"] == probe.args.num_rollouts_per_mpi
+        kept.append(host(*out) + [eps.numpy()[3][:kwargs["n"]]])
+        return out
+
+    def collect_and_note(*args, **kwargs):
+        eps = collect(*args, **kwargs)
+        collected.append((eps, kwargs.get("explore", True)))
+        return eps
+
+    probe.episode_policy_stats, probe.collect_episodes_device = audit_and_keep, collect_and_note
+    printed, finals = [], []
+    for a in (on, off, probe):
+        np.random.seed(11)
+        a.learn()
+        printed.append([line for line in capsys.readouterr().out.splitlines() if "eval success rate" in line or "buffer size" in line])
+        finals.append((a.rng.get_state(), np.random.get_state()))
+    assert off.policy_audit == [] and len(on.policy_audit) == 2 and len(on.success_rates) == 2
+    assert on.success_rates == off.success_rates and on.eval_metrics == off.eval_metrics and on.eval_critic == off.eval_critic
+    assert len(on.eval_critic) == 2
+    strip = lambda lines: [line.split("] ", 1)[-1] for line in lines]
+    assert strip(printed[0]) == strip(printed[1]) and len(printed[0]) == 3
+    for x, y in zip(finals[0], finals[1]):                     # the device stream and numpy's, as learn() leaves them
+        assert all(np.array_equal(u, v) for u, v in zip(x, y))
+    files_on, files_off = tree_bytes(tmp_path / "on"), tree_bytes(tmp_path / "off")
+    assert sorted(files_on) == sorted(files_off) and len(files_on) >= 1 and all(files_on[k] == files_off[k] for k in files_on)
+    for slot in (NET_ACTOR, NET_CRITIC, NET_ACTOR_TARGET, NET_CRITIC_TARGET):
+        assert np.array_equal(bits(on._get_flat(slot)), bits(off._get_flat(slot))), slot
+    sa, sb = ts.read_state(ts.rank_path(str(tmp_path / "on.npz"), 0)), ts.read_state(ts.rank_path(str(tmp_path / "off.npz"), 0))
+    assert sorted(sa[0]) == sorted(sb[0])
+    for name in sa[0]:
+        assert np.array_equal(bits(sa[0][name]), bits(sb[0][name])), name
+    # the entries
+    assert probe.policy_audit == on.policy_audit and probe.success_rates == on.success_rates and len(kept) == 2
+    for m, (stats, pi, q_pi, q, actions) in zip(on.policy_audit, kept):
+        assert tuple(m) == POLICY_STATS
+        want = twin_of(on, stats, pi, q_pi, q, actions)
+        assert np.array_equal(bits(np.array([m[k] for k in POLICY_STATS])), bits(episode_policy_summary(want))), (m, want)
+        assert m["action_gap_mean"] > 0 and 0 <= m["q_filter_share"] <= 1 and 0 <= m["saturated_share"] <= 1 and m["action_l2_mean"] > 0
+    assert not np.array_equal(kept[0][1], kept[1][1])          # two collections, two sets of weights
+
+
+def test_audit_policy_on_the_host_path(tmp_path, capsys):
+    """learn() with host environments goes through episode_policy_stats_host on the last collect_episodes result, and leaves the
+    run as it is without the option"""
+    from rl_arm_under_sparse_reward_amd.synthetic import PointMassGoalEnv
+    runs = []
+    for audit in (True, False):
+        torch.manual_seed(0)
+        np.random.seed(11)
+        env = PointMassGoalEnv(seed=30, max_timesteps=10, distance_threshold=0.15)
+        a = make(env, T=10, seed=5, n_epochs=2, n_cycles=2, n_batches=2, n_test_rollouts=2, buffer_episodes=40, num_rollouts_per_mpi=2,
+                 save_dir=str(tmp_path / f"host{int(audit)}"), env_name="pm", audit_policy=audit)
+        primed(a)
+        if audit:
+            stats_host, kept = a.episode_policy_stats_host, []
+            a.episode_policy_stats_host = lambda batch, **kwargs: kept.append((batch, stats_host(batch, **kwargs))) or kept[-1][1]
+        a.learn()
+        capsys.readouterr()
+        runs.append((a, [a._get_flat(s) for s in (NET_ACTOR, NET_CRITIC)], np.random.get_state()))
+    (a, flat_a, np_a), (b, flat_b, np_b) = runs
+    assert b.policy_audit == [] and len(a.policy_audit) == 2 and a.success_rates == b.success_rates
+    assert all(np.array_equal(bits(x), bits(y)) for x, y in zip(flat_a, flat_b))
+    assert all(np.array_equal(u, v) for u, v in zip(np_a, np_b))
+    assert len(kept) == 2
+    for m, (batch, (stats, pi, q_pi, q)) in zip(a.policy_audit, kept):
+        assert batch[3].shape[0] == 2 and tuple(m) == POLICY_STATS
+        want = twin_of(a, stats, pi, q_pi, q, batch[3])
+        assert np.array_equal(bits(np.array([m[k] for k in POLICY_STATS])), bits(episode_policy_summary(want)))
+        assert m["action_gap_mean"] > 0
+
+
+# ------------------------------------------------------------------------------------------ 8. refusals
+def test_refusals_carry_the_librarys_message(monkeypatch):
+    torch.manual_seed(0)
+    a = make(NativePointMassVecEnv(2, seed=1, device=DEV, max_timesteps=10), T=10)
+    primed(a)
+    lib, c = a.lib, a.ctx
+    eps = a.collect_episodes_device(n_rollouts=3, explore=False)
+    obs, g = torch.zeros((3, 11, 27), dtype=torch.float64, device=DEV), torch.zeros((3, 10, 3), dtype=torch.float64, device=DEV)
+    act = torch.zeros((3, 10, 4), dtype=torch.float64, device=DEV)
+    pi, q = torch.zeros((4, 10, 4), dtype=torch.float32, device=DEV), torch.zeros((4, 10), dtype=torch.float32, device=DEV)
+    q_pi = torch.zeros((4, 10), dtype=torch.float32, device=DEV)
+    stats, summary = torch.zeros((4, 6), dtype=torch.float64, device=DEV), torch.zeros(6, dtype=torch.float64, device=DEV)
+    h, on, gn = a.h, a.o_norm.h, a.g_norm.h
+    # hp_episode_policy
+    good = [h, on, gn, 0, p(obs), p(g), 3, 10, 200.0, p(pi), p(q_pi)]
+    swap = lambda k, x: [x if i == k else v for i, v in enumerate(good)]
+    for k in (0, 1, 2, 4, 5, 9, 10):
+        refused(lib.hp_episode_policy(*swap(k, None)), "hp_episode_policy: null argument")
+    for target in (2, -1):
+        refused(lib.hp_episode_policy(*swap(3, target)), "hp_episode_policy: target .* is neither 0")
+    refused(lib.hp_episode_policy(h, gn, gn, 0, p(obs), p(g), 3, 10, 200.0, p(pi), p(q_pi)),
+            r"hp_episode_policy: normalizer sizes 3\+3 do not match the network input 30")
+    refused(lib.hp_episode_policy(*swap(6, 0)), r"hp_episode_policy: n_episodes 0 outside \[1, ")
+    refused(lib.hp_episode_policy(*swap(7, 0)), r"hp_episode_policy: T 0 outside \[1, ")
+    refused(lib.hp_episode_policy(*[(1 << 23) if i == 6 else (1 << 20) if i == 7 else v for i, v in enumerate(good)]),
+            "hp_episode_policy: .* more than one launch holds")
+    other = _lib.Context(0)                                     # a second context on the same device
+    from rl_arm_under_sparse_reward_amd.normalizer import normalizer
+    foreign = normalizer(27, default_clip_range=5, ctx=other)
+    refused(lib.hp_episode_policy(*swap(1, foreign.h)), "hp_episode_policy: handles belong to different contexts")
+    # hp_episode_policy_block
+    good = [eps.h, h, on, gn, 0, 0, 3, 200.0, p(pi), p(q_pi)]
+    for k in (0, 1, 2, 3, 8, 9):
+        refused(lib.hp_episode_policy_block(*swap(k, None)), "hp_episode_policy_block: null argument")
+    refused(lib.hp_episode_policy_block(*swap(2, foreign.h)), "hp_episode_policy_block: handles belong to different contexts")
+    refused(lib.hp_episode_policy_block(*swap(4, 3)), "hp_episode_policy_block: target 3 is neither 0")
+    for first, n in ((0, 4), (2, 2), (-1, 2), (0, 0)):
+        refused(lib.hp_episode_policy_block(eps.h, h, on, gn, 0, first, n, 200.0, p(pi), p(q_pi)),
+                rf"hp_episode_policy_block: episodes \[{first}, {first + n}\) outside the block of 3")
+    with pytest.raises(ValueError, match="outside the block of 3"):
+        a.episode_policy(eps, first=1, n=3)
+    with pytest.raises(ValueError, match="outside the block of 3"):
+        a.episode_policy_stats(eps, first=2, n=2)
+    small = shaped_agent(20, 1, 3, 0.7)                         # its normalizers fit itself, not the block
+    refused(lib.hp_episode_policy_block(eps.h, small.h, small.o_norm.h, small.g_norm.h, 0, 0, 3, 200.0, p(pi), p(q_pi)),
+            "hp_episode_policy_block: the block has dimensions 27 / 3 / 4, normalizers and agent have 20 / 1 / 3")
+    refused(lib.hp_episode_policy_block(eps.h, small.h, on, gn, 0, 0, 3, 200.0, p(pi), p(q_pi)),
+            r"hp_episode_policy_block: normalizer sizes 27\+3 do not match the network input 21")
+    # an agent that is not slab-shaped: HP_ERR_STATE
+    monkeypatch.setenv("RLARM_ENGINE", "layers")
+    layers = make(None, T=10)
+    monkeypatch.delenv("RLARM_ENGINE")
+    refused(lib.hp_episode_policy(layers.h, layers.o_norm.h, layers.g_norm.h, 0, p(obs), p(g), 3, 10, 200.0, p(pi), p(q_pi)),
+            "hp_episode_policy: the agent is not slab-shaped", code=-5)
+    refused(lib.hp_episode_policy_block(eps.h, layers.h, layers.o_norm.h, layers.g_norm.h, 0, 0, 3, 200.0, p(pi), p(q_pi)),
+            "hp_episode_policy_block: the agent is not slab-shaped", code=-5)
+    narrow = ddpg_agent(Args(batch_size=64, buffer_size=80), None,             # hidden != 256
+                        {"obs": 27, "goal": 3, "action": 4, "action_max": 0.5, "max_timesteps": 10, "hidden": 128}, rng=fresh_rng(5))
+    refused(lib.hp_episode_policy(narrow.h, narrow.o_norm.h, narrow.g_norm.h, 0, p(obs), p(g), 3, 10, 200.0, p(pi), p(q_pi)),
+            r"hp_episode_policy: the agent is not slab-shaped \(hidden 128", code=-5)
+    refused(lib.hp_episode_policy_block(eps.h, narrow.h, narrow.o_norm.h, narrow.g_norm.h, 0, 0, 3, 200.0, p(pi), p(q_pi)),
+            r"hp_episode_policy_block: the agent is not slab-shaped \(hidden 128", code=-5)
+    # hp_episode_policy_stats
+    good = [c.h, p(pi), p(q_pi), p(act), p(q), 3, 10, 4, 0.5, 0.99, p(stats)]
+    for k in (0, 1, 2, 3, 10):
+        refused(lib.hp_episode_policy_stats(*swap(k, None)), "hp_episode_policy_stats: null argument")
+    refused(lib.hp_episode_policy_stats(*swap(5, 0)), r"hp_episode_policy_stats: n_episodes 0 outside \[1, ")
+    refused(lib.hp_episode_policy_stats(*swap(6, 0)), r"hp_episode_policy_stats: T 0 outside \[1, ")
+    for ad in (0, 257):
+        refused(lib.hp_episode_policy_stats(*swap(7, ad)), rf"hp_episode_policy_stats: act_dim {ad} outside \[1, 256\]")
+    for amax in (0.0, -0.5, float("inf"), float("nan")):
+        refused(lib.hp_episode_policy_stats(*swap(8, amax)), "hp_episode_policy_stats: max_action .* is not a positive number")
+    for sat in (-0.1, 1.5, float("nan")):
+        refused(lib.hp_episode_policy_stats(*swap(9, sat)), r"hp_episode_policy_stats: sat .* outside \[0, 1\]")
+    # hp_episode_policy_stats_block
+    good = [eps.h, p(pi), p(q_pi), p(q), 0, 3, 0.5, 0.99, p(stats)]
+    for k in (0, 1, 2, 8):
+        refused(lib.hp_episode_policy_stats_block(*swap(k, None)), "hp_episode_policy_stats_block: null argument")
+    for first, n in ((0, 4), (2, 2), (-1, 2), (0, 0)):
+        refused(lib.hp_episode_policy_stats_block(eps.h, p(pi), p(q_pi), p(q), first, n, 0.5, 0.99, p(stats)),
+                rf"hp_episode_policy_stats_block: episodes \[{first}, {first + n}\) outside the block of 3")
+    refused(lib.hp_episode_policy_stats_block(*swap(7, 2.0)), r"hp_episode_policy_stats_block: sat 2 outside \[0, 1\]")
+    # hp_episode_policy_summary
+    refused(lib.hp_episode_policy_summary(None, p(stats), 3, p(summary)), "hp_episode_policy_summary: null argument")
+    refused(lib.hp_episode_policy_summary(c.h, None, 3, p(summary)), "hp_episode_policy_summary: null argument")
+    refused(lib.hp_episode_policy_summary(c.h, p(stats), 3, None), "hp_episode_policy_summary: null argument")
+    refused(lib.hp_episode_policy_summary(c.h, p(stats), 0, p(summary)), "hp_episode_policy_summary: n_episodes 0 is not positive")
+    c.synchronize()
+    assert not pi.any() and not q_pi.any() and not stats.any() and not summary.any()          # a refused call launches nothing

@@ -1,0 +1,142 @@
+"""What the policy audit costs (args.audit_policy: hp_episode_q_block + hp_episode_policy_block + hp_episode_policy_stats_block
+behind a collection, then hp_episode_policy_summary): an evaluation-sized block of 25 episodes of T = 100 on 2 native point-mass
+environments with the reset on the device (one rollout launch), in three forms on the same box in alternating rounds:
+
+    off    the collection alone (up to, not including, the download of the flags)
+    on     the same with the audit: four more launches (Q(s, a), pi and Q(s, pi(s)) of the 2500 steps, the columns, the summary),
+           nothing read
+    host   the alternative the kernels replace: the collection, then DeviceEpisodes.numpy() (synchronises, four float64 arrays to
+           the host), agent.act on the T + 1-strided rows (upload, one launch, download, wait), clip / normalise in numpy,
+           critic_network(x, a) and critic_network(x, pi) through hp_agent_critic_forward (two uploads, seven launches, a download
+           and a wait each), synthetic.episode_policy_stats + episode_policy_summary
+
+Every (round, form) is a child process of its own under its own `timeout`: it warms the path up, then times `--reps` calls:
+`enqueue_ms`, the host clock around the call alone, and `wall_ms`, the same + one device synchronise.  The device is idle when a
+timed call begins.  The parent alternates the forms, stops at the first child that does not end cleanly, and reports the median
+and min .. max over all rounds' repetitions.  No time is fixed in advance: `on` is compared with `off` of the same build in the
+same run.  Not measured here: the kernels alone, large n, exploring collections (the audit's launches do not depend on them).
+
+    python tools/ubench/episode_policy.py --out profiles/episode_policy.json
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, REPO)
+T, N_ENVS, N_TEST = 100, 2, 25
+FORMS = ("off", "on", "host")
+
+
+def child(form, reps):
+    import numpy as np
+    import torch
+
+    from rl_arm_under_sparse_reward_amd import _lib
+    from rl_arm_under_sparse_reward_amd.arguments import Args
+    from rl_arm_under_sparse_reward_amd.ddpg_agent import ddpg_agent
+    from rl_arm_under_sparse_reward_amd.device_env import NativePointMassVecEnv
+    from rl_arm_under_sparse_reward_amd.random import DeviceRandomState
+    from rl_arm_under_sparse_reward_amd.synthetic import episode_policy_stats, episode_policy_summary
+
+    assert torch.cuda.is_available(), "this measures the MI355X; there is no CPU form of it"
+    ctx = _lib.Context(0)
+    torch.manual_seed(0)
+    env = NativePointMassVecEnv(N_ENVS, seed=1, device="cuda:0", max_timesteps=T)
+    agent = ddpg_agent(Args(buffer_size=8 * T, n_test_rollouts=N_TEST, num_rollouts_per_mpi=2), env, env.env_params, ctx=ctx,
+                       rng=DeviceRandomState(1, ctx=ctx))
+    rs = np.random.RandomState(0)
+    agent.o_norm.update(rs.normal(0.2, 0.3, size=(400, 27))); agent.o_norm.recompute_stats()
+    agent.g_norm.update(rs.normal(0.25, 0.1, size=(400, 3))); agent.g_norm.recompute_stats()
+    agent.enable_explore_streams(base_seed=5)
+    env.enable_device_reset(ctx)
+    summary = torch.empty(_lib.POLICY_STATS, dtype=torch.float64, device="cuda:0")
+
+    def work():
+        flags = []
+        eps = agent.collect_episodes_device(n_rollouts=N_TEST, explore=False, success_out=flags)
+        if form == "on":
+            stats = agent.episode_policy_stats(eps)[0]
+            with ctx.torch_bridge():
+                _lib.check(ctx.lib.hp_episode_policy_summary(ctx.h, C.c_void_p(stats.data_ptr()), N_TEST, C.c_void_p(summary.data_ptr())))
+        elif form == "host":
+            obs, ag, g, actions = eps.numpy()
+            o, gg = agent._preproc_og(obs[:, :T], g)
+            x = np.concatenate([agent.o_norm.normalize(o), agent.g_norm.normalize(gg)], axis=-1).astype(np.float32).reshape(N_TEST * T, -1)
+            pi = agent.act(obs[:, :T].reshape(N_TEST * T, -1), g.reshape(N_TEST * T, -1)).astype(np.float32)
+            q = agent.critic_network(x, actions.astype(np.float32).reshape(N_TEST * T, -1)).reshape(N_TEST, T)
+            q_pi = agent.critic_network(x, pi).reshape(N_TEST, T)
+            return episode_policy_summary(episode_policy_stats(pi.reshape(N_TEST, T, -1), q_pi, actions, env.env_params['action_max'], q=q))
+        return flags
+
+    for _ in range(2):
+        work()
+    torch.cuda.synchronize()
+    assert agent.rollout_form == "fused" and agent.rollout_launches == 1, (agent.rollout_form, agent.rollout_launches)
+    enqueue, wall = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        work()
+        t1 = time.perf_counter()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        enqueue.append((t1 - t0) * 1e3)
+        wall.append((t2 - t0) * 1e3)
+    print("RESULT " + json.dumps({"form": form, "device": ctx.name, "enqueue_ms": enqueue, "wall_ms": wall}), flush=True)
+    return 0
+
+
+def spread(v):
+    return {"median": statistics.median(v), "min": min(v), "max": max(v), "samples": len(v)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=5, help="timed calls per round and form")
+    ap.add_argument("--timeout", type=int, default=120, help="seconds one (round, form) child may take")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--child", default=None, choices=FORMS)
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child, a.reps)
+    samples = {f: {"enqueue_ms": [], "wall_ms": []} for f in FORMS}
+    device = None
+    for r in range(a.rounds):
+        for form in FORMS:                                   # alternate the forms
+            cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", form, "--reps", str(a.reps)]
+            done = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
+            if done.returncode != 0:
+                print(f"round {r} form {form}: the child ended with status {done.returncode}; nothing further is started", flush=True)
+                return 1
+            rec = json.loads([ln for ln in done.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+            device = rec["device"]
+            for key in ("enqueue_ms", "wall_ms"):
+                samples[form][key] += rec[key]
+            print(f"round {r} form {form}: done", flush=True)
+    result = {"device": device, "T": T, "n_envs": N_ENVS, "episodes": N_TEST, "rounds": a.rounds, "reps_per_round": a.reps,
+              "unit": "ms per block: enqueue_ms = host clock around the call, wall_ms = the same + one device synchronise",
+              "forms": {}}
+    for form in FORMS:
+        result["forms"][form] = {key: spread(samples[form][key]) for key in ("enqueue_ms", "wall_ms")}
+        for key in ("enqueue_ms", "wall_ms"):
+            s = result["forms"][form][key]
+            print(f"{form:5s} {key:10s}: {s['median']:8.3f} ms [{s['min']:.3f} .. {s['max']:.3f}]", flush=True)
+    w = {f: result["forms"][f]["wall_ms"] for f in FORMS}
+    result["on_cheaper_than_host_beyond_spread"] = bool(w["on"]["max"] < w["host"]["min"])
+    result["on_minus_off_wall_ms_median"] = w["on"]["median"] - w["off"]["median"]
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
