@@ -1,16 +1,18 @@
-// episode_audit.h -- the frame the three units of the episode audit share (episode_stats.hip, episode_returns.hip, episode_q.hip):
-// the bound on episodes and steps, the refusals every entry makes of a block's shape, the range check of the *_block entries with
-// the block's four arrays behind it, and the summary of a per-episode table.  The arithmetic of a step: transition_device.h.
+// episode_audit.h -- the frame the four units of the episode audit share (episode_stats.hip, episode_returns.hip, episode_q.hip,
+// episode_policy.hip): the bound on episodes and steps, the refusals every entry makes of a block's shape, the range check of the
+// *_block entries with the block's four arrays behind it, and the summary of a per-episode table.  The arithmetic of a step:
+// transition_device.h.
 #pragma once
 #include "transition_device.h"
 
 #define HP_EPISODE_MAX (1 << 24)   // episodes of one call (exclusive) and steps of one episode (inclusive)
 static_assert(HP_EPISODE_MAX_GOAL_DIM == NORM_MAX, "a goal is as wide as a normalizer can hold");
 constexpr int EPISODE_COLS = 6;    // columns of a per-episode table and of its summary
-static_assert(HP_EPISODE_STATS == EPISODE_COLS && HP_EPISODE_SUMMARY == EPISODE_COLS && HP_CRITIC_STATS == EPISODE_COLS, "one summary loop");
+static_assert(HP_EPISODE_STATS == EPISODE_COLS && HP_EPISODE_SUMMARY == EPISODE_COLS && HP_CRITIC_STATS == EPISODE_COLS &&
+              HP_POLICY_STATS == EPISODE_COLS, "one summary loop");
 
-// n_episodes, T, goal_dim, refused in this order under the entry's name (hp_episode_q* take no goal_dim of their own -- theirs is
-// the goal normalizer's -- and leave it out)
+// n_episodes, T, goal_dim, refused in this order under the entry's name (the entries of episode_q.hip and episode_policy.hip
+// take no goal_dim of their own -- theirs is the goal normalizer's, or none -- and leave it out)
 static inline int episode_check_shape(const char *entry, int64_t n, int32_t T, int32_t gd = 1) {
     HP_REQUIRE(n >= 1 && n < HP_EPISODE_MAX, HP_ERR_INVALID, "%s: n_episodes %lld outside [1, %d)", entry, (long long)n, HP_EPISODE_MAX);
     HP_REQUIRE(T >= 1 && T <= HP_EPISODE_MAX, HP_ERR_INVALID, "%s: T %d outside [1, %d]", entry, (int)T, HP_EPISODE_MAX);
@@ -45,7 +47,7 @@ __device__ __forceinline__ void episode_summary_body(const double *__restrict__ 
     for (int k = 0; k < EPISODE_COLS; ++k) out[k] = __ddiv_rn(sum[k], dn);
 }
 
-// the entry of a summary: hp_episode_stats_summary, hp_episode_critic_summary
+// the entry of a summary: hp_episode_stats_summary, hp_episode_critic_summary, hp_episode_policy_summary
 static inline int episode_summary_launch(const char *entry, hp_ctx *ctx, void (*kernel)(const double *, long long, double *),
                                          const double *table, int64_t n, double *out) {
     HP_REQUIRE(ctx && table && out, HP_ERR_INVALID, "%s: null argument", entry);

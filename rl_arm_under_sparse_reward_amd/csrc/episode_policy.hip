@@ -1,7 +1,8 @@
 // episode_policy.hip -- what the actor's objective sees of an episode block, computed where the block lies (hp_episode_policy,
 // hp_episode_policy_block): pi(s_t) and Q(s_t, pi(s_t)) for t = 0 .. T-1 of every episode in ONE launch, and the columns that set
-// them beside the recorded actions and hp_episode_q's Q(s_t, a_t) (hp_episode_policy_stats, hp_episode_policy_stats_block,
-// hp_episode_policy_summary): whether the critic ranks a demonstration's action above the policy's (the Q-filter), how far the
+// them beside the recorded actions and hp_episode_q's Q(s_t, a_t) (hp_episode_policy_stats, hp_episode_policy_stats_block; their
+// means, hp_episode_policy_summary, are episode_returns.hip's k_episode_column_means): whether the critic ranks a
+// demonstration's action above the policy's (the Q-filter), how far the
 // recorded actions lie from the policy (what exploration or a script adds), and whether the actor saturates its tanh -- the two terms
 // of the actor loss, -Q(s, pi(s)) and (pi / max_action)^2 (ddpg_agent.py:265-267), on real episodes.
 //
@@ -36,8 +37,6 @@
 #undef S8_DEVICE_ONLY
 
 #include "episode_audit.h"
-
-static_assert(HP_POLICY_STATS == EPISODE_COLS, "one summary loop");
 
 struct EpisodePolicyArgs {
     PolicyArgs P;                  // the actor: obs / g at the first episode (indexed here, not by s8_policy_slab), rows = n T
@@ -171,14 +170,6 @@ __global__ __launch_bounds__(64) void k_episode_policy_stats(const PolicyStatsAr
     }
 }
 
-// k_episode_policy_summary (episode_summary_body): the mean of every column (synthetic.episode_policy_summary)
-struct PolicySummaryTerm {
-    __device__ double operator()(const double *r, int k) const { return r[k]; }
-};
-__global__ __launch_bounds__(64) void k_episode_policy_summary(const double *__restrict__ stats, long long n, double *__restrict__ out) {
-    episode_summary_body(stats, n, out, PolicySummaryTerm{});
-}
-
 static int policy_stats_launch(const char *entry, hipStream_t stream, const float *pi, const float *q_pi, const double *act,
                                const float *q, int64_t n, int32_t T, int32_t ad, double max_action, double sat, double *stats) {
     HP_TRY(episode_check_shape(entry, n, T));
@@ -235,10 +226,6 @@ int hp_episode_policy_stats_block(hp_rollout *ro, const float *pi_dev, const flo
     HP_TRY(episode_block_range("hp_episode_policy_stats_block", ro, first_episode, n_episodes, at));
     return policy_stats_launch("hp_episode_policy_stats_block", ro->ctx->stream, pi_dev, q_pi_dev, at.b_act, q_dev, n_episodes, ro->T,
                                ro->ad, max_action, sat, stats_dev);
-}
-
-int hp_episode_policy_summary(hp_ctx *ctx, const double *policy_stats_dev, int64_t n_episodes, double *summary_dev) {
-    return episode_summary_launch("hp_episode_policy_summary", ctx, k_episode_policy_summary, policy_stats_dev, n_episodes, summary_dev);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // episode_returns.hip -- the discounted return every step of an episode block went on to collect, and the critic's Q beside it
-// (hp_episode_returns, hp_episode_returns_block, hp_episode_critic_summary).  For most of a sparse-reward run the success rate is
-// zero; whether Q(s_t, a_t) (episode_q.hip) tracks G_t, sits on the target clip -1 / (1 - gamma) (ddpg_agent.py:259-260) or
-// overestimates is what says that learning is happening.
+// (hp_episode_returns, hp_episode_returns_block, hp_episode_critic_summary; hp_episode_policy_summary is the same kernel).  For
+// most of a sparse-reward run the success rate is zero; whether Q(s_t, a_t) (episode_q.hip) tracks G_t, sits on the target
+// clip -1 / (1 - gamma) (ddpg_agent.py:259-260) or overestimates is what says that learning is happening.
 //
 // Step t = 0 .. T-1 of an episode compares ag[t + 1] with g[t]; s[t] is the squared distance (tr_sq_distance,
 // transition_device.h) and the reward is compute_reward's in float64 (hp_reward64 there).
@@ -83,12 +83,13 @@ __global__ __launch_bounds__(64) void k_episode_returns(const EpisodeReturnsArgs
     }
 }
 
-// k_episode_critic_summary (episode_summary_body): the mean of every critic column (synthetic.episode_critic_summary)
-struct CriticSummaryTerm {
+// k_episode_column_means (episode_summary_body): the mean of every column of a per-episode table -- the critic's and the policy's
+// (synthetic.episode_critic_summary, episode_policy_summary: one loop)
+struct ColumnMeanTerm {
     __device__ double operator()(const double *r, int k) const { return r[k]; }
 };
-__global__ __launch_bounds__(64) void k_episode_critic_summary(const double *__restrict__ stats, long long n, double *__restrict__ out) {
-    episode_summary_body(stats, n, out, CriticSummaryTerm{});
+__global__ __launch_bounds__(64) void k_episode_column_means(const double *__restrict__ stats, long long n, double *__restrict__ out) {
+    episode_summary_body(stats, n, out, ColumnMeanTerm{});
 }
 
 static int episode_returns_launch(const char *entry, hipStream_t stream, const double *ag, const double *g, int64_t n, int32_t T,
@@ -135,7 +136,11 @@ int hp_episode_returns_block(hp_rollout *ro, int64_t first_episode, int64_t n_ep
 }
 
 int hp_episode_critic_summary(hp_ctx *ctx, const double *critic_stats_dev, int64_t n_episodes, double *summary_dev) {
-    return episode_summary_launch("hp_episode_critic_summary", ctx, k_episode_critic_summary, critic_stats_dev, n_episodes, summary_dev);
+    return episode_summary_launch("hp_episode_critic_summary", ctx, k_episode_column_means, critic_stats_dev, n_episodes, summary_dev);
+}
+
+int hp_episode_policy_summary(hp_ctx *ctx, const double *policy_stats_dev, int64_t n_episodes, double *summary_dev) {
+    return episode_summary_launch("hp_episode_policy_summary", ctx, k_episode_column_means, policy_stats_dev, n_episodes, summary_dev);
 }
 
 }  // extern "C"

@@ -30,6 +30,7 @@ import torch
 
 from . import _lib
 from . import random as _random
+from .episode_audit import EpisodeAudit
 from .her import her_sampler
 from .models import actor, critic
 from .normalizer import normalizer
@@ -39,7 +40,7 @@ from .utils import Communicator
 NET_ACTOR, NET_CRITIC, NET_ACTOR_TARGET, NET_CRITIC_TARGET = 0, 1, 2, 3
 
 
-class ddpg_agent:
+class ddpg_agent(EpisodeAudit):
     def __init__(self, args, env, env_params, comm: Communicator | None = None, ctx=None, rng=None):
         self.savetime = 0
         self.args = args
@@ -746,134 +747,6 @@ class ddpg_agent:
             stats_out.append(eps.stats(vec_env.distance_threshold, 0, n_total))
         return eps
 
-    def episode_stats_host(self, episode_batch, distance_threshold):
-        """The metrics of host episodes -- the four arrays `collect_episodes` returns, or a feeder slot's (obs, ag, g, actions) --
-        from the kernel the device path uses (hp_episode_stats): `ag` and `g` are uploaded, the result comes back as numpy
-        (stats [n, 6] float64 in the columns of `synthetic.EPISODE_STATS`, step_success [n, T] float32).  Synchronises."""
-        ag = torch.from_numpy(np.ascontiguousarray(episode_batch[1], dtype=np.float64))
-        g = torch.from_numpy(np.ascontiguousarray(episode_batch[2], dtype=np.float64))
-        if ag.ndim != 3 or g.ndim != 3 or ag.shape[0] != g.shape[0] or ag.shape[1] != g.shape[1] + 1 or ag.shape[2] != g.shape[2]:
-            raise ValueError("episode_stats_host: ag [n, T+1, goal] and g [n, T, goal] expected")
-        dev = torch.device("cuda", self.ctx.device_id)
-        ag, g = ag.to(dev), g.to(dev)
-        n, T, gd = g.shape
-        stats = torch.empty((n, _lib.EPISODE_STATS), dtype=torch.float64, device=dev)
-        flags = torch.empty((n, T), dtype=torch.float32, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        with self.ctx.torch_bridge():
-            _lib.check(self.lib.hp_episode_stats(self.ctx.h, p(ag), p(g), n, T, gd, float(distance_threshold), p(stats), p(flags)))
-        return stats.cpu().numpy(), flags.cpu().numpy()
-
-    def episode_q(self, episodes, target=False, first=0, n=None):
-        """What the critic believes of episodes [first, first + n) of a `DeviceEpisodes` (a collection's, an evaluation's, or
-        `generate_demos(...).episodes`: what the critic thinks of the demonstrations): Q(s_t, a_t) of every recorded step, a
-        float32 device tensor [n, T], from one launch on torch's current stream (hp_episode_q_block) -- the training chain's
-        critic forward on rows that enter it exactly as they enter an update (clip_obs from `args`, the normalizers' current
-        statistics, the recorded action over max_action).  `target=True`: the target critic.  No copy, no synchronisation."""
-        first = int(first)
-        n = len(episodes) - first if n is None else int(n)
-        q = torch.empty((max(n, 0), episodes.T), dtype=torch.float32, device=torch.device("cuda", self.ctx.device_id))
-        with self.ctx.torch_bridge():
-            _lib.check(self.lib.hp_episode_q_block(episodes.h, self.h, self.o_norm.h, self.g_norm.h,
-                                                   NET_CRITIC_TARGET if target else NET_CRITIC, first, n, float(self.args.clip_obs),
-                                                   C.c_void_p(q.data_ptr())))
-        return q
-
-    def episode_critic_stats(self, episodes, distance_threshold=None, target=False, tail="persist", first=0, n=None):
-        """The critic audited on episodes [first, first + n) of a `DeviceEpisodes`: (stats [n, 6] float64 in the columns of
-        `synthetic.CRITIC_STATS`, q [n, T] float32, returns [n, T] float64), device tensors from two launches (`episode_q`,
-        `DeviceEpisodes.returns`).  The threshold defaults to `vec_env.distance_threshold`; gamma and reward_type are `args`'."""
-        if distance_threshold is None:
-            distance_threshold = self.vec_env.distance_threshold
-        q = self.episode_q(episodes, target=target, first=first, n=n)
-        returns, stats = episodes.returns(distance_threshold, float(self.args.gamma), getattr(self.args, "reward_type", "sparse"),
-                                          tail, first=first, n=n, q=q)
-        return stats, q, returns
-
-    def episode_critic_stats_host(self, episode_batch, distance_threshold, target=False, tail="persist"):
-        """`episode_critic_stats` for host episodes -- the four arrays `collect_episodes` returns, or a feeder slot's (obs, ag, g,
-        actions): they are uploaded, the same kernels run (hp_episode_q, hp_episode_returns) and the result comes back as numpy
-        (stats [n, 6] float64, q [n, T] float32, returns [n, T] float64).  Synchronises."""
-        from .synthetic import _reward_kind, _tail_kind
-        obs, ag, g, act = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)) for a in episode_batch[:4])
-        if (any(a.ndim != 3 for a in (obs, ag, g, act)) or len({a.shape[0] for a in (obs, ag, g, act)}) != 1
-                or not obs.shape[1] == ag.shape[1] == g.shape[1] + 1 == act.shape[1] + 1 or ag.shape[2] != g.shape[2]):
-            raise ValueError("episode_critic_stats_host: obs [n, T+1, obs], ag [n, T+1, goal], g [n, T, goal] and actions [n, T, act] expected")
-        if (obs.shape[2], g.shape[2], act.shape[2]) != tuple(int(self.env_params[k]) for k in ('obs', 'goal', 'action')):
-            raise ValueError("episode_critic_stats_host: the episodes' dimensions differ from the agent's")
-        dev = torch.device("cuda", self.ctx.device_id)
-        obs, ag, g, act = obs.to(dev), ag.to(dev), g.to(dev), act.to(dev)
-        n, T, gd = g.shape
-        q = torch.empty((n, T), dtype=torch.float32, device=dev)
-        returns = torch.empty((n, T), dtype=torch.float64, device=dev)
-        stats = torch.empty((n, _lib.CRITIC_STATS), dtype=torch.float64, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        with self.ctx.torch_bridge():
-            _lib.check(self.lib.hp_episode_q(self.h, self.o_norm.h, self.g_norm.h, NET_CRITIC_TARGET if target else NET_CRITIC,
-                                             p(obs), p(g), p(act), n, T, float(self.args.clip_obs), p(q)))
-            _lib.check(self.lib.hp_episode_returns(self.ctx.h, p(ag), p(g), n, T, gd, float(distance_threshold),
-                                                   _reward_kind(getattr(self.args, "reward_type", "sparse")), float(self.args.gamma),
-                                                   _tail_kind(tail), p(returns), p(q), p(stats)))
-        return stats.cpu().numpy(), q.cpu().numpy(), returns.cpu().numpy()
-
-    def episode_policy(self, episodes, target=False, first=0, n=None):
-        """What the actor's objective sees of episodes [first, first + n) of a `DeviceEpisodes`: (pi [n, T, act] float32, the
-        policy's action at every recorded state, q_pi [n, T] float32, Q(s_t, pi(s_t))), device tensors from one launch on
-        torch's current stream (hp_episode_policy_block) -- the forward half of an update's actor-side chain on rows that enter
-        it exactly as they enter an update.  `target=True`: target actor and target critic.  No copy, no synchronisation."""
-        first = int(first)
-        n = len(episodes) - first if n is None else int(n)
-        dev = torch.device("cuda", self.ctx.device_id)
-        pi = torch.empty((max(n, 0), episodes.T, int(self.env_params['action'])), dtype=torch.float32, device=dev)
-        q_pi = torch.empty((max(n, 0), episodes.T), dtype=torch.float32, device=dev)
-        with self.ctx.torch_bridge():
-            _lib.check(self.lib.hp_episode_policy_block(episodes.h, self.h, self.o_norm.h, self.g_norm.h, 1 if target else 0, first, n,
-                                                        float(self.args.clip_obs), C.c_void_p(pi.data_ptr()),
-                                                        C.c_void_p(q_pi.data_ptr())))
-        return pi, q_pi
-
-    def episode_policy_stats(self, episodes, target=False, sat=0.99, first=0, n=None):
-        """The policy audited on episodes [first, first + n) of a `DeviceEpisodes` (a collection's, an evaluation's, or
-        `generate_demos(...).episodes`, where the q_filter_share column is the Q-filter rate): (stats [n, 6] float64 in the
-        columns of `synthetic.POLICY_STATS`, pi, q_pi, q), device tensors from three launches (`episode_q`, `episode_policy`,
-        the columns: hp_episode_policy_stats_block).  No copy, no synchronisation."""
-        q = self.episode_q(episodes, target=target, first=first, n=n)
-        pi, q_pi = self.episode_policy(episodes, target=target, first=first, n=n)
-        stats = torch.empty((q.shape[0], _lib.POLICY_STATS), dtype=torch.float64, device=q.device)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        with self.ctx.torch_bridge():
-            _lib.check(self.lib.hp_episode_policy_stats_block(episodes.h, p(pi), p(q_pi), p(q), int(first), q.shape[0],
-                                                              float(self.env_params['action_max']), float(sat), p(stats)))
-        return stats, pi, q_pi, q
-
-    def episode_policy_stats_host(self, episode_batch, target=False, sat=0.99):
-        """`episode_policy_stats` for host episodes -- the four arrays `collect_episodes` returns, or a feeder slot's (obs, ag, g,
-        actions): they are uploaded, the same kernels run (hp_episode_q, hp_episode_policy, hp_episode_policy_stats) and the
-        result comes back as numpy (stats [n, 6] float64, pi [n, T, act] float32, q_pi [n, T] float32, q [n, T] float32).
-        Synchronises."""
-        obs, ag, g, act = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)) for a in episode_batch[:4])
-        if (any(a.ndim != 3 for a in (obs, ag, g, act)) or len({a.shape[0] for a in (obs, ag, g, act)}) != 1
-                or not obs.shape[1] == ag.shape[1] == g.shape[1] + 1 == act.shape[1] + 1 or ag.shape[2] != g.shape[2]):
-            raise ValueError("episode_policy_stats_host: obs [n, T+1, obs], ag [n, T+1, goal], g [n, T, goal] and actions [n, T, act] expected")
-        if (obs.shape[2], g.shape[2], act.shape[2]) != tuple(int(self.env_params[k]) for k in ('obs', 'goal', 'action')):
-            raise ValueError("episode_policy_stats_host: the episodes' dimensions differ from the agent's")
-        dev = torch.device("cuda", self.ctx.device_id)
-        obs, g, act = obs.to(dev), g.to(dev), act.to(dev)
-        n, T, ad = act.shape
-        q = torch.empty((n, T), dtype=torch.float32, device=dev)
-        q_pi = torch.empty((n, T), dtype=torch.float32, device=dev)
-        pi = torch.empty((n, T, ad), dtype=torch.float32, device=dev)
-        stats = torch.empty((n, _lib.POLICY_STATS), dtype=torch.float64, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        with self.ctx.torch_bridge():
-            _lib.check(self.lib.hp_episode_q(self.h, self.o_norm.h, self.g_norm.h, NET_CRITIC_TARGET if target else NET_CRITIC,
-                                             p(obs), p(g), p(act), n, T, float(self.args.clip_obs), p(q)))
-            _lib.check(self.lib.hp_episode_policy(self.h, self.o_norm.h, self.g_norm.h, 1 if target else 0, p(obs), p(g), n, T,
-                                                  float(self.args.clip_obs), p(pi), p(q_pi)))
-            _lib.check(self.lib.hp_episode_policy_stats(self.ctx.h, p(pi), p(q_pi), p(act), p(q), n, T, ad,
-                                                        float(self.env_params['action_max']), float(sat), p(stats)))
-        return stats.cpu().numpy(), pi.cpu().numpy(), q_pi.cpu().numpy(), q.cpu().numpy()
-
     def _collect_all_waves(self, vec_env, eps, n_total, streams, how):
         """All `n_total` episodes as one launch (hp_rollout_waves), or the few the launch cap dictates; the environments are
         reset inside it.  Returns the n_total success flags."""
@@ -1094,42 +967,6 @@ class ddpg_agent:
         if critic is not None:
             self._record_eval_critic(both[-_lib.CRITIC_STATS:])
         return rate
-
-    def _record_eval_metrics(self, summary):
-        """One evaluation's summary (this rank's six means), averaged over the ranks like the success rate, onto `eval_metrics`"""
-        from .synthetic import EPISODE_SUMMARY
-        local = torch.tensor(np.asarray(summary, dtype=np.float64), dtype=torch.float64)
-        if self.comm.world_size > 1:
-            local = local.to(f"cuda:{self.ctx.device_id}")
-        self.comm.allreduce_mean_(local)
-        self.eval_metrics.append(dict(zip(EPISODE_SUMMARY, (float(v) for v in local.cpu().numpy()))))
-
-    def _record_policy_audit(self):
-        """args.audit_policy: the epoch's pending audit -- the device path's summary (six means, already computed) or the host
-        path's episodes (audited now: `episode_policy_stats_host`) -- averaged over the ranks like the success rate, onto
-        `policy_audit`"""
-        pending, self._policy_audit_pending = self._policy_audit_pending, None
-        if pending is None:
-            return
-        from .synthetic import POLICY_STATS, episode_policy_summary
-        if isinstance(pending, torch.Tensor):
-            summary = pending.cpu().numpy()
-        else:
-            summary = episode_policy_summary(self.episode_policy_stats_host(pending)[0])
-        local = torch.tensor(np.asarray(summary, dtype=np.float64), dtype=torch.float64)
-        if self.comm.world_size > 1:
-            local = local.to(f"cuda:{self.ctx.device_id}")
-        self.comm.allreduce_mean_(local)
-        self.policy_audit.append(dict(zip(POLICY_STATS, (float(v) for v in local.cpu().numpy()))))
-
-    def _record_eval_critic(self, summary):
-        """One evaluation's critic summary (this rank's six means), averaged over the ranks like the success rate, onto `eval_critic`"""
-        from .synthetic import CRITIC_STATS
-        local = torch.tensor(np.asarray(summary, dtype=np.float64), dtype=torch.float64)
-        if self.comm.world_size > 1:
-            local = local.to(f"cuda:{self.ctx.device_id}")
-        self.comm.allreduce_mean_(local)
-        self.eval_critic.append(dict(zip(CRITIC_STATS, (float(v) for v in local.cpu().numpy()))))
 
     def _success_rate(self, wins):
         """The mean of this rank's success flags, averaged over the ranks"""

@@ -1,0 +1,187 @@
+"""The three audits of recorded episodes as the agent runs them: the metrics (hp_episode_stats*), the critic audit
+(hp_episode_q*, hp_episode_returns*) and the policy audit (hp_episode_policy*), each on a `DeviceEpisodes` block in place or on
+host episodes that are uploaded first, and what puts an epoch's summary onto the agent's lists.  `ddpg_agent` inherits these
+methods; they use its `lib`, `ctx`, `h`, `o_norm`, `g_norm`, `args`, `env_params`, `vec_env` and `comm`."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _upload(agent, episode_batch, who, arrays=4):
+    """The first `arrays` of (obs, ag, g, actions) of host episodes as float64 device tensors, refused under `who`'s name when their
+    shapes do not belong together or (with obs and actions among them) differ from the agent's.  arrays=2: ag and g alone."""
+    if arrays == 2:
+        ag, g = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)) for a in episode_batch[1:3])
+        if ag.ndim != 3 or g.ndim != 3 or ag.shape[0] != g.shape[0] or ag.shape[1] != g.shape[1] + 1 or ag.shape[2] != g.shape[2]:
+            raise ValueError(f"{who}: ag [n, T+1, goal] and g [n, T, goal] expected")
+        host = (ag, g)
+    else:
+        obs, ag, g, act = host = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)) for a in episode_batch[:4])
+        if (any(a.ndim != 3 for a in host) or len({a.shape[0] for a in host}) != 1
+                or not obs.shape[1] == ag.shape[1] == g.shape[1] + 1 == act.shape[1] + 1 or ag.shape[2] != g.shape[2]):
+            raise ValueError(f"{who}: obs [n, T+1, obs], ag [n, T+1, goal], g [n, T, goal] and actions [n, T, act] expected")
+        if (obs.shape[2], g.shape[2], act.shape[2]) != tuple(int(agent.env_params[k]) for k in ('obs', 'goal', 'action')):
+            raise ValueError(f"{who}: the episodes' dimensions differ from the agent's")
+    dev = torch.device("cuda", agent.ctx.device_id)
+    return tuple(a.to(dev) for a in host)
+
+
+def _span(episodes, first, n):
+    """(first, n) of a call on a `DeviceEpisodes`: n defaults to the episodes from `first` on"""
+    first = int(first)
+    return first, (len(episodes) - first if n is None else int(n))
+
+
+def _record(agent, names, summary, onto):
+    """One summary (this rank's means, in the columns `names`), averaged over the ranks like the success rate, onto the list"""
+    local = torch.tensor(np.asarray(summary, dtype=np.float64), dtype=torch.float64)
+    if agent.comm.world_size > 1:
+        local = local.to(f"cuda:{agent.ctx.device_id}")
+    agent.comm.allreduce_mean_(local)
+    onto.append(dict(zip(names, (float(v) for v in local.cpu().numpy()))))
+
+
+class EpisodeAudit:
+    def episode_stats_host(self, episode_batch, distance_threshold):
+        """The metrics of host episodes -- the four arrays `collect_episodes` returns, or a feeder slot's (obs, ag, g, actions) --
+        from the kernel the device path uses (hp_episode_stats): `ag` and `g` are uploaded, the result comes back as numpy
+        (stats [n, 6] float64 in the columns of `synthetic.EPISODE_STATS`, step_success [n, T] float32).  Synchronises."""
+        ag, g = _upload(self, episode_batch, "episode_stats_host", arrays=2)
+        n, T, gd = g.shape
+        stats = torch.empty((n, _lib.EPISODE_STATS), dtype=torch.float64, device=g.device)
+        flags = torch.empty((n, T), dtype=torch.float32, device=g.device)
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_episode_stats(self.ctx.h, _p(ag), _p(g), n, T, gd, float(distance_threshold), _p(stats), _p(flags)))
+        return stats.cpu().numpy(), flags.cpu().numpy()
+
+    # ---- the two network forwards and the policy columns: one place per entry pair.  `episodes`: a DeviceEpisodes, whose
+    # episodes [first, first + n) are read in place (the *_block entry); None: the uploaded arrays are (the plain entry)
+    def _q(self, episodes, first, n, T, target, obs=None, g=None, act=None):
+        from .ddpg_agent import NET_CRITIC, NET_CRITIC_TARGET
+        q = torch.empty((max(n, 0), T), dtype=torch.float32, device=torch.device("cuda", self.ctx.device_id))
+        nets = (self.h, self.o_norm.h, self.g_norm.h, NET_CRITIC_TARGET if target else NET_CRITIC)
+        with self.ctx.torch_bridge():
+            if episodes is not None:
+                _lib.check(self.lib.hp_episode_q_block(episodes.h, *nets, first, n, float(self.args.clip_obs), _p(q)))
+            else:
+                _lib.check(self.lib.hp_episode_q(*nets, _p(obs), _p(g), _p(act), n, T, float(self.args.clip_obs), _p(q)))
+        return q
+
+    def _policy(self, episodes, first, n, T, target, obs=None, g=None):
+        dev = torch.device("cuda", self.ctx.device_id)
+        pi = torch.empty((max(n, 0), T, int(self.env_params['action'])), dtype=torch.float32, device=dev)
+        q_pi = torch.empty((max(n, 0), T), dtype=torch.float32, device=dev)
+        nets = (self.h, self.o_norm.h, self.g_norm.h, 1 if target else 0)
+        with self.ctx.torch_bridge():
+            if episodes is not None:
+                _lib.check(self.lib.hp_episode_policy_block(episodes.h, *nets, first, n, float(self.args.clip_obs), _p(pi), _p(q_pi)))
+            else:
+                _lib.check(self.lib.hp_episode_policy(*nets, _p(obs), _p(g), n, T, float(self.args.clip_obs), _p(pi), _p(q_pi)))
+        return pi, q_pi
+
+    def _policy_columns(self, episodes, first, pi, q_pi, q, sat, act=None):
+        n, T, ad = pi.shape
+        stats = torch.empty((n, _lib.POLICY_STATS), dtype=torch.float64, device=q.device)
+        tail = (float(self.env_params['action_max']), float(sat), _p(stats))
+        with self.ctx.torch_bridge():
+            if episodes is not None:
+                _lib.check(self.lib.hp_episode_policy_stats_block(episodes.h, _p(pi), _p(q_pi), _p(q), first, n, *tail))
+            else:
+                _lib.check(self.lib.hp_episode_policy_stats(self.ctx.h, _p(pi), _p(q_pi), _p(act), _p(q), n, T, ad, *tail))
+        return stats
+
+    def episode_q(self, episodes, target=False, first=0, n=None):
+        """What the critic believes of episodes [first, first + n) of a `DeviceEpisodes` (a collection's, an evaluation's, or
+        `generate_demos(...).episodes`: what the critic thinks of the demonstrations): Q(s_t, a_t) of every recorded step, a
+        float32 device tensor [n, T], from one launch on torch's current stream (hp_episode_q_block) -- the training chain's
+        critic forward on rows that enter it exactly as they enter an update (clip_obs from `args`, the normalizers' current
+        statistics, the recorded action over max_action).  `target=True`: the target critic.  No copy, no synchronisation."""
+        return self._q(episodes, *_span(episodes, first, n), episodes.T, target)
+
+    def episode_critic_stats(self, episodes, distance_threshold=None, target=False, tail="persist", first=0, n=None):
+        """The critic audited on episodes [first, first + n) of a `DeviceEpisodes`: (stats [n, 6] float64 in the columns of
+        `synthetic.CRITIC_STATS`, q [n, T] float32, returns [n, T] float64), device tensors from two launches (`episode_q`,
+        `DeviceEpisodes.returns`).  The threshold defaults to `vec_env.distance_threshold`; gamma and reward_type are `args`'."""
+        if distance_threshold is None:
+            distance_threshold = self.vec_env.distance_threshold
+        q = self.episode_q(episodes, target=target, first=first, n=n)
+        returns, stats = episodes.returns(distance_threshold, float(self.args.gamma), getattr(self.args, "reward_type", "sparse"),
+                                          tail, first=first, n=n, q=q)
+        return stats, q, returns
+
+    def episode_critic_stats_host(self, episode_batch, distance_threshold, target=False, tail="persist"):
+        """`episode_critic_stats` for host episodes -- the four arrays `collect_episodes` returns, or a feeder slot's (obs, ag, g,
+        actions): they are uploaded, the same kernels run (hp_episode_q, hp_episode_returns) and the result comes back as numpy
+        (stats [n, 6] float64, q [n, T] float32, returns [n, T] float64).  Synchronises."""
+        from .synthetic import _reward_kind, _tail_kind
+        obs, ag, g, act = _upload(self, episode_batch, "episode_critic_stats_host")
+        n, T, gd = g.shape
+        q = self._q(None, 0, n, T, target, obs, g, act)
+        returns = torch.empty((n, T), dtype=torch.float64, device=g.device)
+        stats = torch.empty((n, _lib.CRITIC_STATS), dtype=torch.float64, device=g.device)
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_episode_returns(self.ctx.h, _p(ag), _p(g), n, T, gd, float(distance_threshold),
+                                                   _reward_kind(getattr(self.args, "reward_type", "sparse")), float(self.args.gamma),
+                                                   _tail_kind(tail), _p(returns), _p(q), _p(stats)))
+        return stats.cpu().numpy(), q.cpu().numpy(), returns.cpu().numpy()
+
+    def episode_policy(self, episodes, target=False, first=0, n=None):
+        """What the actor's objective sees of episodes [first, first + n) of a `DeviceEpisodes`: (pi [n, T, act] float32, the
+        policy's action at every recorded state, q_pi [n, T] float32, Q(s_t, pi(s_t))), device tensors from one launch on
+        torch's current stream (hp_episode_policy_block) -- the forward half of an update's actor-side chain on rows that enter
+        it exactly as they enter an update.  `target=True`: target actor and target critic.  No copy, no synchronisation."""
+        return self._policy(episodes, *_span(episodes, first, n), episodes.T, target)
+
+    def episode_policy_stats(self, episodes, target=False, sat=0.99, first=0, n=None):
+        """The policy audited on episodes [first, first + n) of a `DeviceEpisodes` (a collection's, an evaluation's, or
+        `generate_demos(...).episodes`, where the q_filter_share column is the Q-filter rate): (stats [n, 6] float64 in the
+        columns of `synthetic.POLICY_STATS`, pi, q_pi, q), device tensors from three launches (`episode_q`, `episode_policy`,
+        the columns: hp_episode_policy_stats_block).  No copy, no synchronisation."""
+        q = self.episode_q(episodes, target=target, first=first, n=n)
+        pi, q_pi = self.episode_policy(episodes, target=target, first=first, n=n)
+        return self._policy_columns(episodes, int(first), pi, q_pi, q, sat), pi, q_pi, q
+
+    def episode_policy_stats_host(self, episode_batch, target=False, sat=0.99):
+        """`episode_policy_stats` for host episodes -- the four arrays `collect_episodes` returns, or a feeder slot's (obs, ag, g,
+        actions): they are uploaded, the same kernels run (hp_episode_q, hp_episode_policy, hp_episode_policy_stats) and the
+        result comes back as numpy (stats [n, 6] float64, pi [n, T, act] float32, q_pi [n, T] float32, q [n, T] float32).
+        Synchronises."""
+        obs, _, g, act = _upload(self, episode_batch, "episode_policy_stats_host")
+        n, T, _ = act.shape
+        q = self._q(None, 0, n, T, target, obs, g, act)
+        pi, q_pi = self._policy(None, 0, n, T, target, obs, g)
+        stats = self._policy_columns(None, 0, pi, q_pi, q, sat, act)
+        return stats.cpu().numpy(), pi.cpu().numpy(), q_pi.cpu().numpy(), q.cpu().numpy()
+
+    def _record_eval_metrics(self, summary):
+        """One evaluation's summary (this rank's six means), averaged over the ranks like the success rate, onto `eval_metrics`"""
+        from .synthetic import EPISODE_SUMMARY
+        _record(self, EPISODE_SUMMARY, summary, self.eval_metrics)
+
+    def _record_policy_audit(self):
+        """args.audit_policy: the epoch's pending audit -- the device path's summary (six means, already computed) or the host
+        path's episodes (audited now: `episode_policy_stats_host`) -- averaged over the ranks like the success rate, onto
+        `policy_audit`"""
+        pending, self._policy_audit_pending = self._policy_audit_pending, None
+        if pending is None:
+            return
+        from .synthetic import POLICY_STATS, episode_policy_summary
+        if isinstance(pending, torch.Tensor):
+            summary = pending.cpu().numpy()
+        else:
+            summary = episode_policy_summary(self.episode_policy_stats_host(pending)[0])
+        _record(self, POLICY_STATS, summary, self.policy_audit)
+
+    def _record_eval_critic(self, summary):
+        """One evaluation's critic summary (this rank's six means), averaged over the ranks like the success rate, onto `eval_critic`"""
+        from .synthetic import CRITIC_STATS
+        _record(self, CRITIC_STATS, summary, self.eval_critic)

@@ -595,17 +595,22 @@ def episode_critic_stats(q, returns, gamma):
     return out
 
 
+def _column_means(who, names, stats):
+    """The one loop behind episode_critic_summary and episode_policy_summary: left-to-right float64 sums in episode order"""
+    stats = np.asarray(stats, dtype=np.float64)
+    if stats.ndim != 2 or stats.shape[1] != len(names) or stats.shape[0] < 1:
+        raise ValueError(f"{who}: stats [n >= 1, {len(names)}] expected")
+    total = np.zeros(len(names), dtype=np.float64)
+    for row in stats:
+        for k in range(len(names)):
+            total[k] = total[k] + row[k]
+    return total / np.float64(stats.shape[0])
+
+
 def episode_critic_summary(stats):
     """The host twin of hp_episode_critic_summary: the six column means over the episodes, each a left-to-right float64 sum in
     episode order divided by their number."""
-    stats = np.asarray(stats, dtype=np.float64)
-    if stats.ndim != 2 or stats.shape[1] != len(CRITIC_STATS) or stats.shape[0] < 1:
-        raise ValueError("episode_critic_summary: stats [n >= 1, 6] expected")
-    total = np.zeros(len(CRITIC_STATS), dtype=np.float64)
-    for row in stats:
-        for k in range(len(CRITIC_STATS)):
-            total[k] = total[k] + row[k]
-    return total / np.float64(stats.shape[0])
+    return _column_means("episode_critic_summary", CRITIC_STATS, stats)
 
 
 POLICY_STATS = ("q_pi_mean", "advantage_mean", "q_filter_share", "action_gap_mean", "saturated_share", "action_l2_mean")
@@ -668,14 +673,7 @@ def episode_policy_stats(pi, q_pi, actions, max_action, q=None, sat=0.99):
 def episode_policy_summary(stats):
     """The host twin of hp_episode_policy_summary: the six column means over the episodes, each a left-to-right float64 sum in
     episode order divided by their number."""
-    stats = np.asarray(stats, dtype=np.float64)
-    if stats.ndim != 2 or stats.shape[1] != len(POLICY_STATS) or stats.shape[0] < 1:
-        raise ValueError("episode_policy_summary: stats [n >= 1, 6] expected")
-    total = np.zeros(len(POLICY_STATS), dtype=np.float64)
-    for row in stats:
-        for k in range(len(POLICY_STATS)):
-            total[k] = total[k] + row[k]
-    return total / np.float64(stats.shape[0])
+    return _column_means("episode_policy_summary", POLICY_STATS, stats)
 
 
 def write_demo_npz_from(path, obs, ag, g, actions, info):

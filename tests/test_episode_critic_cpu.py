@@ -198,7 +198,7 @@ def test_the_returns_kernels_use_no_scratch_and_no_lds(tmp_path):
     meta = kernel_metadata(tmp_path, "episode_returns.hip")
     print(meta)
     assert len(meta) == 2, sorted(meta)
-    assert sum("k_episode_returns" in n for n in meta) == 1 and sum("k_episode_critic_summary" in n for n in meta) == 1, sorted(meta)
+    assert sum("k_episode_returns" in n for n in meta) == 1 and sum("k_episode_column_means" in n for n in meta) == 1, sorted(meta)
     for name, m in meta.items():
         assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, (name, m)
         assert m["group_segment_fixed_size"] < 1024, (name, m)

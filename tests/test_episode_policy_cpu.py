@@ -155,14 +155,16 @@ def test_header_ctypes_table_and_exports_carry_the_new_entries():
 
 
 def test_the_new_units_kernels_use_no_scratch(tmp_path):
-    """episode_policy.hip holds exactly three kernels.  None uses scratch or spills a register; k_episode_policy has the policy
-    slab's LDS (one workgroup per CU, below the 160 KiB of a CU) at 512 threads and two waves per SIMD; the two one-wave kernels
-    have no LDS to speak of.  The figures read here are DESIGN 3.7's."""
+    """episode_policy.hip holds exactly two kernels, and its summary is episode_returns.hip's column means.  None uses scratch or
+    spills a register; k_episode_policy has the policy slab's LDS (one workgroup per CU, below the 160 KiB of a CU) at 512 threads
+    and two waves per SIMD; the two one-wave kernels have no LDS to speak of.  The figures read here are DESIGN 3.7's."""
     meta = kernel_metadata(tmp_path, "episode_policy.hip")
+    assert len(meta) == 2, sorted(meta)
+    meta.update({n: m for n, m in kernel_metadata(tmp_path, "episode_returns.hip").items() if "k_episode_column_means" in n})
     print(meta)
     assert len(meta) == 3, sorted(meta)
     named = {want: [n for n in meta if re.search(rf"{want}(?![a-z_])", n)] for want in
-             ("k_episode_policy", "k_episode_policy_stats", "k_episode_policy_summary")}
+             ("k_episode_policy", "k_episode_policy_stats", "k_episode_column_means")}
     assert all(len(v) == 1 for v in named.values()), (named, sorted(meta))
     for name, m in meta.items():
         assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, (name, m)
@@ -171,6 +173,6 @@ def test_the_new_units_kernels_use_no_scratch(tmp_path):
     q_only = next(iter(kernel_metadata(tmp_path, "episode_q.hip").values()))
     assert slab["group_segment_fixed_size"] == q_only["group_segment_fixed_size"]       # one PolicyLds and nothing else
     assert slab["vgpr_count"] <= 128, slab                                             # 512 threads at two waves per SIMD
-    for want in ("k_episode_policy_stats", "k_episode_policy_summary"):
+    for want in ("k_episode_policy_stats", "k_episode_column_means"):
         m = meta[named[want][0]]
         assert m["group_segment_fixed_size"] < 1024 and m["vgpr_count"] <= 64, (want, m)

@@ -1,22 +1,30 @@
-"""What the policy audit costs (args.audit_policy: hp_episode_q_block + hp_episode_policy_block + hp_episode_policy_stats_block
-behind a collection, then hp_episode_policy_summary): an evaluation-sized block of 25 episodes of T = 100 on 2 native point-mass
-environments with the reset on the device (one rollout launch), in three forms on the same box in alternating rounds:
+"""What an audit of recorded episodes costs: `--audit metrics` (args.eval_metrics: hp_episode_stats_block +
+hp_episode_stats_summary behind the rollout), `--audit critic` (args.eval_critic: hp_episode_q_block + hp_episode_returns_block,
+then hp_episode_critic_summary) or `--audit policy` (args.audit_policy: hp_episode_q_block + hp_episode_policy_block +
+hp_episode_policy_stats_block, then hp_episode_policy_summary).  The block is the noise-free evaluation of 25 episodes of T = 100 on
+2 native point-mass environments with the reset on the device (one rollout launch), in three forms on the same box in alternating
+rounds:
 
-    off    the collection alone (up to, not including, the download of the flags)
-    on     the same with the audit: four more launches (Q(s, a), pi and Q(s, pi(s)) of the 2500 steps, the columns, the summary),
-           nothing read
+    off    the collection of _eval_agent_device as it is without the option (the `eval25` / device_reset row of
+           tools/ubench/rollout_device_reset.py: up to, not including, the download of the flags)
+    on     the same with the audit, nothing read.  metrics: stats_out and the summary launch (two more small launches); critic:
+           three more launches (Q of the 2500 steps, returns + critic columns, summary); policy: four more (Q(s, a), pi and
+           Q(s, pi(s)) of the 2500 steps, the columns, the summary)
     host   the alternative the kernels replace: the collection, then DeviceEpisodes.numpy() (synchronises, four float64 arrays to
-           the host), agent.act on the T + 1-strided rows (upload, one launch, download, wait), clip / normalise in numpy,
-           critic_network(x, a) and critic_network(x, pi) through hp_agent_critic_forward (two uploads, seven launches, a download
-           and a wait each), synthetic.episode_policy_stats + episode_policy_summary
+           the host) and the host twins of synthetic.  critic: clip / normalise / scale in numpy, critic_network(x, a) through
+           hp_agent_critic_forward (two uploads, seven launches, a download, a wait) in front of them; policy: agent.act on the
+           T + 1-strided rows (upload, one launch, download, wait) and critic_network(x, a), critic_network(x, pi)
 
 Every (round, form) is a child process of its own under its own `timeout`: it warms the path up, then times `--reps` calls:
 `enqueue_ms`, the host clock around the call alone, and `wall_ms`, the same + one device synchronise.  The device is idle when a
 timed call begins.  The parent alternates the forms, stops at the first child that does not end cleanly, and reports the median
 and min .. max over all rounds' repetitions.  No time is fixed in advance: `on` is compared with `off` of the same build in the
-same run.  Not measured here: the kernels alone, large n, exploring collections (the audit's launches do not depend on them).
+same run.  Not measured here: the kernels alone (they are a few microseconds inside a call of milliseconds), large n, exploring
+collections (the audits' launches do not depend on them).
 
-    python tools/ubench/episode_policy.py --out profiles/episode_policy.json
+    python tools/ubench/episode_audit.py --audit metrics --out profiles/episode_stats.json
+    python tools/ubench/episode_audit.py --audit critic --out profiles/episode_critic.json
+    python tools/ubench/episode_audit.py --audit policy --out profiles/episode_policy.json
 """
 import argparse
 import ctypes as C
@@ -31,9 +39,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, REPO)
 T, N_ENVS, N_TEST = 100, 2, 25
 FORMS = ("off", "on", "host")
+AUDITS = {"metrics": ("EPISODE_SUMMARY", "hp_episode_stats_summary", "evaluation"),     # summary width, summary entry, the unit's noun
+          "critic": ("CRITIC_STATS", "hp_episode_critic_summary", "evaluation"),
+          "policy": ("POLICY_STATS", "hp_episode_policy_summary", "block")}
 
 
-def child(form, reps):
+def child(audit, form, reps):
     import numpy as np
     import torch
 
@@ -42,7 +53,7 @@ def child(form, reps):
     from rl_arm_under_sparse_reward_amd.ddpg_agent import ddpg_agent
     from rl_arm_under_sparse_reward_amd.device_env import NativePointMassVecEnv
     from rl_arm_under_sparse_reward_amd.random import DeviceRandomState
-    from rl_arm_under_sparse_reward_amd.synthetic import episode_policy_stats, episode_policy_summary
+    from rl_arm_under_sparse_reward_amd import synthetic as syn
 
     assert torch.cuda.is_available(), "this measures the MI355X; there is no CPU form of it"
     ctx = _lib.Context(0)
@@ -55,15 +66,42 @@ def child(form, reps):
     agent.g_norm.update(rs.normal(0.25, 0.1, size=(400, 3))); agent.g_norm.recompute_stats()
     agent.enable_explore_streams(base_seed=5)
     env.enable_device_reset(ctx)
-    summary = torch.empty(_lib.POLICY_STATS, dtype=torch.float64, device="cuda:0")
+    width, summary_entry, _ = AUDITS[audit]
+    summary = torch.empty(getattr(_lib, width), dtype=torch.float64, device="cuda:0")
 
-    def work():
+    def summarise(stats):
+        with ctx.torch_bridge():
+            _lib.check(getattr(ctx.lib, summary_entry)(ctx.h, C.c_void_p(stats.data_ptr()), N_TEST, C.c_void_p(summary.data_ptr())))
+
+    def work_metrics():
+        flags, stats = [], ([] if form == "on" else None)
+        eps = agent.collect_episodes_device(n_rollouts=N_TEST, explore=False, success_out=flags, stats_out=stats)
+        if form == "on":
+            summarise(stats[0])
+        elif form == "host":
+            _, ag, g, _ = eps.numpy()
+            return syn.episode_stats_summary(syn.episode_stats(ag, g, env.distance_threshold)[0])
+        return flags
+
+    def work_critic():
         flags = []
         eps = agent.collect_episodes_device(n_rollouts=N_TEST, explore=False, success_out=flags)
         if form == "on":
-            stats = agent.episode_policy_stats(eps)[0]
-            with ctx.torch_bridge():
-                _lib.check(ctx.lib.hp_episode_policy_summary(ctx.h, C.c_void_p(stats.data_ptr()), N_TEST, C.c_void_p(summary.data_ptr())))
+            summarise(agent.episode_critic_stats(eps)[0])
+        elif form == "host":
+            obs, ag, g, actions = eps.numpy()
+            o, gg = agent._preproc_og(obs[:, :T], g)
+            x = np.concatenate([agent.o_norm.normalize(o), agent.g_norm.normalize(gg)], axis=-1).astype(np.float32).reshape(N_TEST * T, -1)
+            q = agent.critic_network(x, actions.astype(np.float32).reshape(N_TEST * T, -1)).reshape(N_TEST, T)
+            G = syn.episode_returns(ag, g, env.distance_threshold, agent.args.gamma, agent.args.reward_type, "persist")
+            return syn.episode_critic_summary(syn.episode_critic_stats(q, G, agent.args.gamma))
+        return flags
+
+    def work_policy():
+        flags = []
+        eps = agent.collect_episodes_device(n_rollouts=N_TEST, explore=False, success_out=flags)
+        if form == "on":
+            summarise(agent.episode_policy_stats(eps)[0])
         elif form == "host":
             obs, ag, g, actions = eps.numpy()
             o, gg = agent._preproc_og(obs[:, :T], g)
@@ -71,9 +109,10 @@ def child(form, reps):
             pi = agent.act(obs[:, :T].reshape(N_TEST * T, -1), g.reshape(N_TEST * T, -1)).astype(np.float32)
             q = agent.critic_network(x, actions.astype(np.float32).reshape(N_TEST * T, -1)).reshape(N_TEST, T)
             q_pi = agent.critic_network(x, pi).reshape(N_TEST, T)
-            return episode_policy_summary(episode_policy_stats(pi.reshape(N_TEST, T, -1), q_pi, actions, env.env_params['action_max'], q=q))
+            return syn.episode_policy_summary(syn.episode_policy_stats(pi.reshape(N_TEST, T, -1), q_pi, actions, env.env_params['action_max'], q=q))
         return flags
 
+    work = {"metrics": work_metrics, "critic": work_critic, "policy": work_policy}[audit]
     for _ in range(2):
         work()
     torch.cuda.synchronize()
@@ -101,15 +140,17 @@ def main():
     ap.add_argument("--reps", type=int, default=5, help="timed calls per round and form")
     ap.add_argument("--timeout", type=int, default=120, help="seconds one (round, form) child may take")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--audit", required=True, choices=tuple(AUDITS))
     ap.add_argument("--child", default=None, choices=FORMS)
     a = ap.parse_args()
     if a.child:
-        return child(a.child, a.reps)
+        return child(a.audit, a.child, a.reps)
     samples = {f: {"enqueue_ms": [], "wall_ms": []} for f in FORMS}
     device = None
     for r in range(a.rounds):
         for form in FORMS:                                   # alternate the forms
-            cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", form, "--reps", str(a.reps)]
+            cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--audit", a.audit, "--child", form,
+                   "--reps", str(a.reps)]
             done = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
             if done.returncode != 0:
                 print(f"round {r} form {form}: the child ended with status {done.returncode}; nothing further is started", flush=True)
@@ -120,7 +161,7 @@ def main():
                 samples[form][key] += rec[key]
             print(f"round {r} form {form}: done", flush=True)
     result = {"device": device, "T": T, "n_envs": N_ENVS, "episodes": N_TEST, "rounds": a.rounds, "reps_per_round": a.reps,
-              "unit": "ms per block: enqueue_ms = host clock around the call, wall_ms = the same + one device synchronise",
+              "unit": f"ms per {AUDITS[a.audit][2]}: enqueue_ms = host clock around the call, wall_ms = the same + one device synchronise",
               "forms": {}}
     for form in FORMS:
         result["forms"][form] = {key: spread(samples[form][key]) for key in ("enqueue_ms", "wall_ms")}
