@@ -103,7 +103,7 @@ def philox4x32_10(c0, c1, c2, c3, k0, k1):
 def draw_her_indices_fast(n_episodes: int, T: int, batch: int, future_p: float, seed: int, call: int):
     """The four draws of her.py:24-33 for transition m of call `call` from Philox4x32-10(counter (m, call), key seed):
     e = floor(r0 N / 2^32), t = floor(r1 T / 2^32), her = r2 2^-32 < future_p, future_t = t + 1 + floor(r3 (T - t) / 2^32)
-    (csrc/buffer.hip: fs_fast_rec is the device twin)."""
+    (csrc/sampler.hip: fs_fast_rec is the device twin)."""
     m = np.arange(batch, dtype=np.uint64)
     mask = np.uint64(0xFFFFFFFF)
     r0, r1, r2, r3 = philox4x32_10(m & mask, m >> np.uint64(32), np.uint64(call & 0xFFFFFFFF), np.uint64((call >> 32) & 0xFFFFFFFF),

@@ -372,9 +372,10 @@ int rng_launch_plan_sample(hp_rng *rng, const BufMeta *d_meta, int32_t T, int64_
 int rng_launch_plan2(hp_rng *rng, int64_t n_first, int32_t T, int64_t batch_first, PlanRec *d_plan_first,
                      const BufMeta *d_meta, int64_t batch, int32_t n_batches, double future_p, PlanRec *d_plan);
 
-// buffer.hip
+// sampler.hip
 int buffer_launch_gather_dict(hp_buffer *buf, const PlanRec *d_plan, int64_t batch, double sq_threshold,
                               double *d_out, float *d_r, double *d_r64);
+// buffer.hip
 int buffer_stage_and_store(hp_buffer *b, hp_rng *rng, const double *obs, const double *ag, const double *g,
                            const double *actions, int64_t n_new);
 // the staging half alone (+ the host mirror of the counters): slots and scatter follow in k_cycle_open (cycle_open.hip).

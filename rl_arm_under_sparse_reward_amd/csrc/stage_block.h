@@ -1,8 +1,8 @@
 // stage_block.h -- the index and size arithmetic of the cycle-opening launch (cycle_open.hip) and of the chunked normalizer update
 // (norm_device.h), with no loads or stores: which doubles of a staged block a scatter thread owns, where a double of the block
-// goes, whether a batch fits the direct form, and how many plan rows one LDS trip of the normalizer takes.  Plain C++ for host
-// and device, so all of it runs on the CPU under a sanitizer (tests/host/stage_block_main.cpp); store_device.h, norm_device.h,
-// norm.hip and cycle_open.hip call it.
+// goes, whether a batch fits the direct form, how many plan rows one LDS trip of the normalizer takes, and the byte carve of a
+// staged batch (buffer.hip).  Plain C++ for host and device, so all of it runs on the CPU under a sanitizer
+// (tests/host/stage_block_main.cpp); store_device.h, norm_device.h, norm.hip, cycle_open.hip and buffer.hip call it.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -12,6 +12,24 @@
 #else
 #define STAGE_HD inline
 #endif
+
+// ---- a staged batch in bytes (buffer.hip): the float64 arrays obs | ag | g | actions of n_new episodes back to back, on the device
+// (st_obs .. st_act) and in every host block that is copied there
+struct StageBytes {
+    size_t obs, ag, g, act, total;
+    size_t at_ag() const { return obs; }              // where each array after the first begins
+    size_t at_g() const { return obs + ag; }
+    size_t at_act() const { return obs + ag + g; }
+};
+inline StageBytes stage_bytes_of(long long n_new, size_t ep_obs, size_t ep_ag, size_t ep_g, size_t ep_act) {
+    StageBytes n;
+    n.obs = (size_t)n_new * ep_obs * 8;
+    n.ag = (size_t)n_new * ep_ag * 8;
+    n.g = (size_t)n_new * ep_g * 8;
+    n.act = (size_t)n_new * ep_act * 8;
+    n.total = n.obs + n.ag + n.g + n.act;
+    return n;
+}
 
 // ---- the direct form: the staged batch lies in a pinned HOST block, obs | ag | g | actions back to back, `nd` doubles in all
 // (store_device.h).  The block is cut into 16-byte chunks, chunk c belonging to thread c mod `nthreads` of the scatter workgroups

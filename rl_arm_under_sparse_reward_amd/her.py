@@ -6,7 +6,7 @@ Same constructor and method as her.py:3-41:
     .sample_her_transitions(episode_batch, batch_size_in_transitions) -> dict of ndarrays
 
 but the index draw (her.py:24-33), gather (:26), goal relabel (:35-36) and reward (:38 ->
-bmirobot_env_push_F.py:84-90) run as HIP kernels; see csrc/rng.hip and csrc/buffer.hip.
+bmirobot_env_push_F.py:84-90) run as HIP kernels; see csrc/rng.hip and csrc/sampler.hip.
 
 `reward_func` cannot be an arbitrary Python callable on the device.  The reference always
 passes `env.compute_reward` of a bmirobot env whose reward is sparse with

@@ -116,6 +116,18 @@ static void check_block(const Shape &s, int n_new) {
     for (unsigned d = 0; d < nd; ++d) blk[d] = 1.0 + (double)d;
     const long long len[4] = {ep_obs, ep_ag, ep_g, ep_act};
     const unsigned start[4] = {0u, L.n_obs, L.n_obs + L.n_ag, L.n_obs + L.n_ag + L.n_g};
+    // the same block in bytes (buffer.hip's carve and host fill): each array begins where StageBlock says, and copying four exactly
+    // sized arrays to those offsets of an exactly sized block gives the block
+    const StageBytes nb = stage_bytes_of(n_new, (size_t)ep_obs, (size_t)ep_ag, (size_t)ep_g, (size_t)ep_act);
+    const size_t at[4] = {0, nb.at_ag(), nb.at_g(), nb.at_act()}, bytes[4] = {nb.obs, nb.ag, nb.g, nb.act};
+    CHECK(nb.total == (size_t)nd * 8 && at[3] + nb.act == nb.total);
+    std::vector<char> carved(nb.total);
+    for (int a = 0; a < 4; ++a) {
+        CHECK(at[a] == (size_t)start[a] * 8 && bytes[a] == (size_t)n_new * (size_t)len[a] * 8);
+        const std::vector<double> arr(blk.begin() + start[a], blk.begin() + start[a] + n_new * len[a]);
+        std::memcpy(carved.data() + at[a], arr.data(), bytes[a]);
+    }
+    CHECK(std::memcmp(carved.data(), blk.data(), nb.total) == 0);
     std::vector<double> want[4], got[4];
     for (int a = 0; a < 4; ++a) {
         want[a].assign((size_t)(cap * len[a]), 0.0);

@@ -107,7 +107,7 @@ def _pairs_as_one_step_episodes(ag, g, od, ad):
     return [np.zeros((M, 2, od)), agm, g[:, None, :].copy(), np.zeros((M, 1, ad))]
 
 
-# Which kernel a case takes is the launch rule of hp_buffer_sample_dev (buffer.hip): float32 rows -> k_gather_packed; else
+# Which kernel a case takes is the launch rule of hp_buffer_sample_dev (sampler.hip: launch_gather): float32 rows -> k_gather_packed; else
 # obs + ceil(goal / 2) + ceil(act / 2) <= 32 -> k_gather_fused2; else k_gather_fused; each with 4 transitions (pairs) in flight
 # per wavefront from a batch of 16384 on, 1 below.  The labels restate that rule; nothing here observes the dispatch.
 @pytest.mark.parametrize("form,od,gd,ad,B,f32_rows", [
