@@ -56,6 +56,12 @@ int hp_rng_debug_table_ms(hp_rng *rng, double *ms);
  * number of optimizer steps already taken (shared by both optimizers, ddpg_agent.py:272,277 step together) */
 int hp_agent_set_adam(hp_agent *ag, int32_t net, const float *m_host, const float *v_host, int64_t n, int64_t step);
 
+/* test hook, read-only: the network inputs and rewards the update launches gathered for themselves, as they lie in the agent's
+ * arena.  set 0 = XA, XP, XT, R; set 1 = XA2, XP2, XT2, R2 (the other half of the gather-ahead ping-pong).  x*_host[Mp * ldx] and
+ * r_host[Mp] include the padded rows and columns; dims[6] = batch, Mp, ldx, act_off, act_dim, obs_dim + goal_dim.  Any output may
+ * be NULL.  Host code only: synchronises the context's stream and copies; launches nothing, writes nothing on the device. */
+int hp_agent_debug_inputs(hp_agent *ag, int32_t set, float *xa_host, float *xp_host, float *xt_host, float *r_host, int32_t *dims);
+
 /* diagnostic: microseconds per launch of ONE stage of the update, repeated n times in a captured
  * hipGraph (kind: 6 optimizer kernel, 8 polyak, 10 forward + backward of the active engine, 11 its chain kernel only,
  * 12 its weight-gradient launch + optimizer only) -- the per-stage numbers quoted in DESIGN.md / bench.py */

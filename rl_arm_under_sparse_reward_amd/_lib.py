@@ -92,7 +92,8 @@ DEBUG_SYMBOLS = {"hp_ctx_launch_floor", "hp_ctx_event_pair_us", "hp_ctx_clock_mh
                  "hp_buffer_sample_dev_us", "hp_buffer_sample_dev_fast_us",
                  "hp_mt_jump_poly", "hp_rng_parallel_info", "hp_rng_debug_set_window", "hp_rng_debug_table_ms",
                  "hp_state_debug_dirty_scan", "hp_rollout_debug_set_launch_cap", "hp_buffer_debug_stage_info",
-                 "hp_agent_set_adam", "hp_agent_debug_chain", "hp_agent_debug_timeline", "hp_agent_update_kernels"}
+                 "hp_agent_set_adam", "hp_agent_debug_chain", "hp_agent_debug_timeline", "hp_agent_update_kernels",
+                 "hp_agent_debug_inputs"}
 
 # name -> (restype, argtypes); every symbol declared in include/rlarm_hip.h and include/rlarm_hip_debug.h
 PROTOTYPES = {
@@ -276,6 +277,7 @@ PROTOTYPES = {
                                            C.c_double, C.c_double, C.c_int32]),
     "hp_agent_debug_chain": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, f64p]),
     "hp_agent_debug_timeline": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "hp_agent_debug_inputs": (C.c_int, [C.c_void_p, C.c_int32, f32p, f32p, f32p, f32p, C.POINTER(C.c_int32)]),
     "hp_agent_update_kernels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                           C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
     "hp_agent_engine": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -468,6 +468,27 @@ int hp_agent_set_adam(hp_agent *a, int32_t net, const float *m_host, const float
     return HP_OK;
 }
 
+// test hook: the network inputs and rewards an update launch gathered for itself, as they lie in the arena (padded rows and
+// columns included).  set 0 = XA, XP, XT, R; set 1 = the other half of the gather-ahead ping-pong.  Host code only: waits for
+// the stream, copies out, writes nothing on the device.
+int hp_agent_debug_inputs(hp_agent *a, int32_t set, float *xa_host, float *xp_host, float *xt_host, float *r_host, int32_t *dims) {
+    HP_REQUIRE(a, HP_ERR_INVALID, "hp_agent_debug_inputs: null handle");
+    HP_SERIALISE(a);
+    HP_REQUIRE(set == 0 || set == 1, HP_ERR_INVALID, "hp_agent_debug_inputs: set=%d not in 0..1", set);
+    hipStream_t s = a->ctx->stream;
+    const size_t nx = sizeof(float) * (size_t)a->Mp * a->ldx;
+    const float *src[4] = {set ? a->XA2 : a->XA, set ? a->XP2 : a->XP, set ? a->XT2 : a->XT, set ? a->R2 : a->R};
+    float *dst[4] = {xa_host, xp_host, xt_host, r_host};
+    HP_CHECK_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < 4; ++i)
+        if (dst[i]) HP_CHECK_HIP(hipMemcpyAsync(dst[i], src[i], i < 3 ? nx : sizeof(float) * (size_t)a->Mp, hipMemcpyDeviceToHost, s));
+    HP_CHECK_HIP(hipStreamSynchronize(s));
+    if (dims) {
+        dims[0] = a->B; dims[1] = a->Mp; dims[2] = a->ldx; dims[3] = a->act_off; dims[4] = a->cfg.act_dim; dims[5] = a->xdim;
+    }
+    return HP_OK;
+}
+
 int hp_agent_sync_targets(hp_agent *a) {
     HP_REQUIRE(a, HP_ERR_INVALID, "hp_agent_sync_targets: null handle");
     HP_SERIALISE(a);

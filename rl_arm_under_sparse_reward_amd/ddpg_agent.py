@@ -204,6 +204,21 @@ class ddpg_agent(EpisodeAudit):
         _lib.check(self.lib.hp_agent_set_adam(self.h, slot, _lib.ptr(m, C.c_float), _lib.ptr(v, C.c_float), m.size,
                                               int(step)))
 
+    def debug_inputs(self, which=0):
+        """The network inputs an update launch gathered for itself (test hook, hp_agent_debug_inputs; synchronises): input set
+        `which` of the gather-ahead ping-pong as {'XA', 'XP', 'XT': float32 [Mp, ldx], 'R': float32 [Mp], 'B', 'Mp', 'ldx',
+        'act_off', 'act_dim', 'xdim'}, padded rows and columns included."""
+        dims = (C.c_int32 * 6)()
+        _lib.check(self.lib.hp_agent_debug_inputs(self.h, int(which), None, None, None, None, dims))
+        out = dict(zip(("B", "Mp", "ldx", "act_off", "act_dim", "xdim"), (int(d) for d in dims)))
+        for key in ("XA", "XP", "XT"):
+            out[key] = np.empty((out["Mp"], out["ldx"]), np.float32)
+        out["R"] = np.empty(out["Mp"], np.float32)
+        f = C.c_float
+        _lib.check(self.lib.hp_agent_debug_inputs(self.h, int(which), _lib.ptr(out["XA"], f), _lib.ptr(out["XP"], f),
+                                                  _lib.ptr(out["XT"], f), _lib.ptr(out["R"], f), dims))
+        return out
+
     def _broadcast_params(self, comm):
         if not comm.active:
             return

@@ -129,8 +129,8 @@ def test_reward_bits_on_adversarial_pairs_through_every_device_gather(form, od, 
     pairs within three ulps of the radius, expected bits from the oracle's compute_reward on the CPU) go through every
     hp_buffer_sample_dev kernel, whose lanes hold one square each and add them in index order: one-step episodes with
     future_p = 0, padded with zero observations and actions, every reward bit-equal and (nearly) every pair seen.  The gathers
-    inside an update launch (s8_gather, s8_gather_ahead) leave their reward vector in the agent's arena, which no entry point
-    exposes; they call the same two functions."""
+    inside an update launch (s8_gather, s8_gather_ahead) leave their reward vector in the agent's arena: the same pairs go
+    through them in tests/test_gpu_update_inputs.py."""
     from rl_arm_under_sparse_reward_amd.normalizer import normalizer
     from gpu_common import ctx
 
