@@ -31,18 +31,18 @@ def _linear_init(out_f, in_f, gen):
     return w.float(), b.float()
 
 
-def init_actor(obs, goal, action, seed):
+def init_actor(obs, goal, action, seed, hidden=HIDDEN):
     gen = torch.Generator().manual_seed(seed)
-    dims = [(HIDDEN, obs + goal), (HIDDEN, HIDDEN), (HIDDEN, HIDDEN), (action, HIDDEN)]
+    dims = [(hidden, obs + goal), (hidden, hidden), (hidden, hidden), (action, hidden)]
     p = {}
     for k, (o, i) in zip(ACTOR_KEYS, dims):
         p[k + ".weight"], p[k + ".bias"] = _linear_init(o, i, gen)
     return p
 
 
-def init_critic(obs, goal, action, seed):
+def init_critic(obs, goal, action, seed, hidden=HIDDEN):
     gen = torch.Generator().manual_seed(seed)
-    dims = [(HIDDEN, obs + goal + action), (HIDDEN, HIDDEN), (HIDDEN, HIDDEN), (1, HIDDEN)]
+    dims = [(hidden, obs + goal + action), (hidden, hidden), (hidden, hidden), (1, hidden)]
     p = {}
     for k, (o, i) in zip(CRITIC_KEYS, dims):
         p[k + ".weight"], p[k + ".bias"] = _linear_init(o, i, gen)

@@ -10,7 +10,11 @@ __host__ __device__ __forceinline__ int frag8_dx_index(int n, int k, int N);
 __host__ __device__ __forceinline__ void frag32_offsets(const ArenaMap &am, int idx, int &off_f, int &off_d);
 
 __host__ __device__ __forceinline__ void frag_offsets_any(const ArenaMap &am, int idx, int &off_f, int &off_d) {
-    if (am.mode == 2) frag32_offsets(am, idx, off_f, off_d);
+    // mode 0, the layer-per-launch engine: nothing reads fragment copies, and the fragment orders are only defined for hidden
+    // widths that are multiples of 64 (frag8_fwd_index / frag8_dx_index deal whole 64-row blocks: at hidden 32, 96 or 288 the
+    // offsets run past the tensor and, for the last tensor, past the arena)
+    if (am.mode == 0) off_f = off_d = -1;
+    else if (am.mode == 2) frag32_offsets(am, idx, off_f, off_d);
     else frag8_offsets(am, idx, off_f, off_d);
 }
 

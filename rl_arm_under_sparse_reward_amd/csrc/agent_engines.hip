@@ -377,7 +377,7 @@ static ArenaMap arena_map(const hp_agent *a) {
     am.la = a->la;
     am.lc = a->lc;
     am.H = a->H;
-    am.mode = a->slab32 ? 2 : 1;
+    am.mode = a->slab32 ? 2 : a->slab ? 1 : 0;
     return am;
 }
 

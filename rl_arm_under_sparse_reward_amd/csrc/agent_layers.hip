@@ -1,7 +1,11 @@
 // agent_layers.hip -- layer-per-launch fallback engine: every dependency level of the update as one grouped GEMM launch
 // (gemm_lds.h through launch_group), loss / head / optimizer as small kernels: ~20 launches per update.  Selected
 // automatically for network shapes the slab engines are not specialised for (hidden != 256, inputs wider than 48 columns,
-// more than 4 action components) and by RLARM_ENGINE=layers; held to the same oracle bar (test_other_env_shapes_track_oracle).
+// more than 4 action components) and by RLARM_ENGINE=layers; held to the same oracle bar: test_other_env_shapes_track_oracle,
+// the "layers" cases of tests/test_gpu_teacher_forced.py and, for hidden 32 / 96 / 128 / 288 / 512 and a 263-column input,
+// test_every_update_meets_the_bar_at_other_hidden_widths, test_forward_entry_points_match_oracle_at_other_hidden_widths, the
+// hidden cases of test_train_cycle_graph_equals_eager_bitwise / test_repeated_runs_are_bit_identical and
+// test_resume_equals_not_stopping[hidden_128].  No fragment-ordered weight copies exist on this engine (ArenaMap::mode 0).
 // Reference: models.py:11-44, ddpg_agent.py:250-277.
 #include "agent.h"
 

@@ -16,7 +16,7 @@
 struct ArenaMap {  // enough of the arena geometry to find (layer, n, k) of a flat index on the device
     NetLayout la, lc;
     int H;
-    int mode;      // 1: thin-slab fragment order (slab8.h), 2: 32-row order (slab32.h)
+    int mode;      // 1: thin-slab fragment order (slab8.h), 2: 32-row order (slab32.h), 0: no fragment copies (layer engine)
 };
 
 enum { SE_BIAS_RELU = 0, SE_MASK = 1 };

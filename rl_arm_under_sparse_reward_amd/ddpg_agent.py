@@ -578,6 +578,9 @@ class ddpg_agent(EpisodeAudit):
     def load_checkpoint(self, path):
         """Warm start from a reference-format checkpoint (the block commented out at ddpg_agent.py:54-62)."""
         o_mean, o_std, g_mean, g_std, model = torch.load(path, map_location="cpu", weights_only=False)
+        have, mine = int(model["fc2.weight"].shape[0]), int(self.env_params.get("hidden", 256))
+        if have != mine:      # before load_state_dict: it copies the tensors that do fit (the head's bias) and then raises
+            raise ValueError(f"load_checkpoint: {path} holds an actor with hidden width {have}, this agent's is {mine}")
         self.actor_network.load_state_dict(model)
         self.o_norm.set_stats(o_mean, o_std)
         self.g_norm.set_stats(g_mean, g_std)

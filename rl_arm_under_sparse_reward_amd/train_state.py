@@ -386,7 +386,8 @@ def rank_path(path, rank):
 # ---------------------------------------------------------------------------------------------------- device side
 def _dims_of(agent, current_size):
     ep = agent.env_params
-    return {"obs": int(ep["obs"]), "goal": int(ep["goal"]), "action": int(ep["action"]), "hidden": 256,
+    return {"obs": int(ep["obs"]), "goal": int(ep["goal"]), "action": int(ep["action"]),
+            "hidden": int(ep.get("hidden", 256)),     # the width ddpg_agent gave hp_agent_create
             "T": int(agent.buffer._dev.T), "capacity": int(agent.buffer._dev.size), "current_size": int(current_size)}
 
 

@@ -144,12 +144,13 @@ def _teach(agent, learner):
 
 
 def _run(batch, k, comm=None, n_steps=N_STEPS, n_eps=64, env_params=None, hp=None, before_step=None, on_minibatch=None,
-         polyak_every=10, spare_eps=0):
+         polyak_every=10, spare_eps=0, torch_seed=0):
     """`n_steps` teacher-forced updates.  env_params: the GoalEnv shape and action_max (bmirobot's 27/3/4 and 0.5 when None;
     other shapes get gpu_common.make_shape_episodes); hp: Args overrides of the learner's hyperparameters, given to the
     device agent, the oracle learner, the normalizers, the Adam twins and the float64 yardstick alike.  before_step(i, side)
     may change the oracle's state before it is taught to the device; on_minibatch(i, side, mb) sees each step's minibatch
-    before the oracle's update; spare_eps: room in the replay buffer for that many more episodes.  Returns the worst
+    before the oracle's update; spare_eps: room in the replay buffer for that many more episodes; torch_seed: of the initial
+    weights.  Returns the worst
     numbers, the agent and `side`: the oracle's learner, store, normalizers and RNG, the episodes and the settings."""
     torch.set_num_threads(4)
     ep = dict(env_params or ENV_PARAMS)
@@ -160,7 +161,7 @@ def _run(batch, k, comm=None, n_steps=N_STEPS, n_eps=64, env_params=None, hp=Non
         eps = make_episodes(n_eps, seed=3, mode="walk")
     else:
         eps = make_shape_episodes(n_eps, od, gd, ad, T, seed=3)
-    torch.manual_seed(0)
+    torch.manual_seed(torch_seed)
     rng = fresh_rng(7)
     agent = ddpg_agent(args, None, ep, comm=comm, rng=rng)
     a0 = {kk: v.detach().clone() for kk, v in agent.actor_network.state_dict().items()}
@@ -471,6 +472,86 @@ def test_every_update_meets_the_bar_at_other_env_shapes(shape, launch, monkeypat
     worst, agent, _ = _run(256, 4, n_steps=CASE_STEPS, n_eps=24, env_params=env, polyak_every=4)
     _expect_engine(agent, launch, "slab32" if launch == "slab32" else engine)
     _report(f"shape {o}/{g}/{a} action_max {amax} {launch}", worst, agent, CASE_STEPS)
+
+
+# Case E: hidden widths other than 256 and network inputs wider than 256 columns -- what hp_agent_create accepts (any multiple of
+# 32) and only the layer-per-launch engine runs.  WIDE: the widest input the rest of the learner accepts -- 256 observation columns
+# is the normalizers' limit (NORM_MAX), 7 goal columns the HER sampler's (her.py refuses goal_dim >= 8: the device sums the squared
+# goal distance in index order, numpy pairwise from 8 elements on; a 250 / 10 / 4 shape is therefore refused).  xdim 263: the actor's
+# first layer reduces over 272 columns and the critic's over 288, a full 256-column chunk of the staged reduction (gemm_lds.h,
+# gemm_tile) and a remainder chunk of 16 / 32; the critic's first-layer dX and dW have 9 column tiles.
+WIDE_ENV = {"obs": 256, "goal": 7, "action": 4, "action_max": 0.7, "max_timesteps": 20}
+# (hidden, batch, env, episodes, torch seed of the initial weights): what each case reaches -- and, last, its number of (step,
+# network) pairs, of 2 x 12, whose smallest float64 pre-activation lies below RELU_NOISE, counted on the CPU with the oracle alone
+# (relu_tie_upper_bound below): an upper bound on what the cap of 3 ReLU ties can ever be asked to excuse.  The wider the layers,
+# the more pre-activations per update and the more often one of them is that small: with _run's seed 0 the count is 4 at
+# hidden 128, 6 at 512, 6 and 4 for the wide input at 256 and 288: these four take the first seed with the smallest count among
+# 0 .. 23 (128: 0 at seed 1; 512: 1 at seed 4; 256 wide: 0 at seed 12; 288 wide: 2 at seed 3).
+WIDTH_CASES = {
+    # one 32-wide column tile per problem; reductions of 32 (kc 32: 2 of 8 waves have products); the heads' dX reduces over 16
+    "h32": (32, 256, HP_ENV, 64, 0),                # ties <= 0
+    # no multiple of 64; 6 super-steps for 8 waves; three column tiles
+    "h96": (96, 256, HP_ENV, 64, 0),                # ties <= 0
+    # the width the refusal tests of the fused entry points name
+    "h128": (128, 256, HP_ENV, 64, 1),              # ties <= 0
+    # the first width whose staged reduction takes a second chunk: 256 + 32, the barrier in between and a remainder chunk
+    "h288": (288, 256, HP_ENV, 64, 0),              # ties <= 3
+    # two full chunks, 16 column tiles, arena and launch order twice as large
+    "h512": (512, 256, HP_ENV, 64, 4),              # ties <= 1
+    # Mp 32: weight gradients on the staged k-major x k-major path with K 32 and padded rows
+    "h96_b7": (96, 7, HP_ENV, 64, 0),               # ties <= 0
+    # weight gradients on the ring path, 1/B no power of two, a partial last block of batch rows
+    "h96_b449": (96, 449, HP_ENV, 64, 0),           # ties <= 1
+    # the first layer's forward reduction takes a remainder chunk; 9 column tiles in the critic's first-layer dX and dW
+    "h256_wide": (256, 256, WIDE_ENV, 24, 12),      # ties <= 0
+    # both reductions loop
+    "h288_wide": (288, 256, WIDE_ENV, 24, 3),       # ties <= 2
+}
+
+
+def relu_tie_upper_bound(case, n_steps=CASE_STEPS, polyak_every=4, torch_seed=None):
+    """The oracle's half of _run for a WIDTH_CASES entry, on the CPU (no device is touched: the networks are the host containers
+    ddpg_agent would build from the same torch seed): how many (step, network) pairs have a float64 pre-activation below
+    RELU_NOISE.  Not a test; `python -c "import test_gpu_teacher_forced as t; print(t.relu_tie_upper_bound('h512'))"` from tests/."""
+    from rl_arm_under_sparse_reward_amd.models import actor, critic
+    hidden, batch, env, n_eps, seed = WIDTH_CASES[case]
+    ep, args = dict(env, hidden=hidden), Args(batch_size=batch, replay_k=4, **HP)
+    od, gd, ad, T = ep["obs"], ep["goal"], ep["action"], ep["max_timesteps"]
+    eps = make_shape_episodes(n_eps, od, gd, ad, T, seed=3)
+    torch.manual_seed(seed if torch_seed is None else torch_seed)
+    a0, c0 = actor(ep).state_dict(), critic(ep).state_dict()
+    amax = float(ep["action_max"])
+    learner = oupd.DDPGLearner(a0, c0, max_action=amax, gamma=args.gamma, action_l2=args.action_l2, lr_actor=args.lr_actor,
+                               lr_critic=args.lr_critic, polyak=args.polyak)
+    rs, st, fp = np.random.RandomState(7), EpisodeStore(T, od, gd, ad, n_eps * T), future_probability("future", 4)
+    on, gn = RunningNorm(od, default_clip_range=args.clip_range), RunningNorm(gd, default_clip_range=args.clip_range)
+    st.store_episode(eps, rs)
+    update_normalizers(on, gn, [a[-2:] for a in eps], fp, rs, clip_obs=args.clip_obs)
+    count = 0
+    for i in range(n_steps):
+        mb = oupd.minibatch_tensors(st.sample(batch, fp, rs)[0], on, gn, clip_obs=args.clip_obs)
+        lo = _f64_gradients(learner.actor, learner.critic, learner.actor_target, learner.critic_target, *mb, max_action=amax,
+                            gamma=args.gamma, action_l2=args.action_l2)["min_preact"]
+        count += int(lo["actor"] < RELU_NOISE) + int(lo["critic"] < RELU_NOISE)
+        learner.update(*mb)
+        if i % polyak_every == polyak_every - 1:
+            learner.soft_update()
+    return count
+
+
+@pytest.mark.parametrize("case", list(WIDTH_CASES))
+def test_every_update_meets_the_bar_at_other_hidden_widths(case, monkeypatch):
+    """Case E: HP at hidden widths 32 .. 512 and with a 263-column input, on the layer-per-launch engine, which is what
+    hp_agent_create gives every such shape; the bars of the file, unchanged.  The wide input is 256 / 7 / 4, not 250 / 10 / 4:
+    the HER sampler refuses goals of 8 or more components (her.py: bit-exact rewards are only claimed below numpy's pairwise
+    summation), so the goal has 7 and the observation the normalizers' 256; the padded widths are the same 272 and 288."""
+    hidden, batch, env, n_eps, seed = WIDTH_CASES[case]
+    _launch("default", monkeypatch)
+    worst, agent, _ = _run(batch, 4, n_steps=CASE_STEPS, n_eps=n_eps, hp=HP, env_params=dict(env, hidden=hidden), polyak_every=4,
+                           torch_seed=seed)
+    _expect_engine(agent, "default", "layers")
+    assert agent.actor_network.fc2.weight.shape == (hidden, hidden) and agent.critic_network.fc1.weight.shape[0] == hidden
+    _report(f"width {case} hidden {hidden} batch {batch} input {env['obs']}/{env['goal']}/{env['action']}", worst, agent, CASE_STEPS)
 
 
 def _load_learner(learner, agent):

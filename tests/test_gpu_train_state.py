@@ -21,9 +21,9 @@ N_BATCHES = 14          # >= 12 updates per sequence: batch 256 takes the split 
 EPS_PER_CYCLE = 2
 
 
-def build(batch=256, ep=None, cap_eps=40, torch_seed=0, rng_seed=7, f32=False):
+def build(batch=256, ep=None, cap_eps=40, torch_seed=0, rng_seed=7, f32=False, n_batches=N_BATCHES):
     ep = dict(ep or ENV_PARAMS)
-    args = Args(batch_size=batch, buffer_size=cap_eps * ep["max_timesteps"], n_batches=N_BATCHES)
+    args = Args(batch_size=batch, buffer_size=cap_eps * ep["max_timesteps"], n_batches=n_batches)
     torch.manual_seed(torch_seed)
     agent = ddpg_agent(args, None, ep, rng=fresh_rng(rng_seed))
     if f32:
@@ -79,6 +79,8 @@ CASES = {
     "shape_20_1_3_T50": dict(batch=256, ep={"obs": 20, "goal": 1, "action": 3, "action_max": 0.7, "max_timesteps": 50}),
     "shape_25_2_5_layers": dict(batch=256, ep={"obs": 25, "goal": 2, "action": 5, "action_max": 1.3, "max_timesteps": 50}),
     "f32_rows": dict(batch=256, f32=True),
+    # another hidden width (layer engine), small: 2 + 2 cycles of 3 updates, 16 episodes of room
+    "hidden_128": dict(batch=64, cap_eps=16, ep=dict(ENV_PARAMS, hidden=128), n=2, m=2, n_batches=3),
 }
 
 
@@ -87,24 +89,33 @@ def test_resume_equals_not_stopping(case, tmp_path, monkeypatch):
     c = dict(CASES[case])
     for k, v in c.pop("env", {}).items():
         monkeypatch.setenv(k, v)
-    ep, n, m = c.get("ep"), 3, 2
-    kw = dict(batch=c["batch"], ep=ep, cap_eps=c.get("cap_eps", 40), f32=c.get("f32", False))
+    ep, n, m, nb = c.get("ep"), c.get("n", 3), c.get("m", 2), c.get("n_batches", N_BATCHES)
+    kw = dict(batch=c["batch"], ep=ep, cap_eps=c.get("cap_eps", 40), f32=c.get("f32", False), n_batches=nb)
     a = build(**kw)
     form = C.c_int32()
-    _lib.check(a.lib.hp_agent_update_form(a.h, N_BATCHES, C.byref(form)))
+    _lib.check(a.lib.hp_agent_update_form(a.h, nb, C.byref(form)))
     if case == "b256_split":
         assert form.value == 1
-    if case in ("b1024_no_split", "layers_engine", "shape_25_2_5_layers"):
+    if case in ("b1024_no_split", "layers_engine", "shape_25_2_5_layers", "hidden_128"):
         assert form.value == 0
     cycles(a, ep, 0, n + m)
-    want, want_losses = fingerprint(a), a.last_losses(m * N_BATCHES)
+    want, want_losses = fingerprint(a), a.last_losses(m * nb)
     if case == "overflowing_buffer":
         assert want["buffer_counters"][0] == 5 and want["buffer_counters"][1] == (n + m) * EPS_PER_CYCLE * 100
     # run B: n cycles, save, drop everything, fresh objects that start from other weights and another stream, load, m cycles
     b = build(**kw)
     cycles(b, ep, 0, n)
     path = b.save_training_state(tmp_path / "state.npz", epoch=1, cycle=n)
-    ts.verify(path)                                   # the numpy twin agrees with the sums the device put into the manifest
+    manifest = ts.verify(path)                        # the numpy twin agrees with the sums the device put into the manifest
+    assert manifest["dims"]["hidden"] == (ep or {}).get("hidden", 256)
+    if case == "hidden_128":
+        assert b.engine()["engine"] == "layers" and b.actor_network.fc2.weight.shape == (128, 128)
+        wide = build(torch_seed=5, rng_seed=11, **dict(kw, ep=None))          # a 256-wide agent refuses the 128-wide state, untouched
+        fp = fingerprint(wide)
+        with pytest.raises(ValueError, match="hidden of the state is 128"):
+            wide.load_training_state(path)
+        assert_same(fingerprint(wide), fp, "refused width")
+        del wide
     del b
     b2 = build(torch_seed=99, rng_seed=4321, **kw)
     before = fingerprint(b2)
@@ -114,7 +125,7 @@ def test_resume_equals_not_stopping(case, tmp_path, monkeypatch):
         b2.last_losses(1)
     cycles(b2, ep, n, m)
     assert_same(fingerprint(b2), want, case)
-    assert b2.last_losses(m * N_BATCHES).tobytes() == want_losses.tobytes()
+    assert b2.last_losses(m * nb).tobytes() == want_losses.tobytes()
     if c.get("f32"):
         sa = a.buffer.sample_device(256, a.o_norm, a.g_norm, f32_rows=True)
         sb = b2.buffer.sample_device(256, b2.o_norm, b2.g_norm, f32_rows=True)

@@ -276,10 +276,14 @@ def test_split_weight_gradient_kernel_tracks_oracle(batch, split, monkeypatch):
     test_updates_track_oracle_over_a_cycle(batch, 4)
 
 
-@pytest.mark.parametrize("n_batches,n_eps,n_new", [(5, 16, 2), (1, 16, 2), (2, 16, 2),   # 1 and 2: shorter than the two-update lead of the index plans
-                                                   (3, 64, 2),      # room in the buffer: replay_buffer.py:59-61, no slot draw
-                                                   (3, 200, 130)])  # more episodes per cycle than k_cycle_open has workgroups for
-def test_train_cycle_graph_equals_eager_bitwise(n_batches, n_eps, n_new, monkeypatch):
+@pytest.mark.parametrize("n_batches,n_eps,n_new,hidden", [
+    (5, 16, 2, 256), (1, 16, 2, 256), (2, 16, 2, 256),   # 1 and 2: shorter than the two-update lead of the index plans
+    (3, 64, 2, 256),       # room in the buffer: replay_buffer.py:59-61, no slot draw
+    (3, 200, 130, 256),    # more episodes per cycle than k_cycle_open has workgroups for
+    (5, 16, 2, 96),        # the layer engine's ~20 launches per update as one cycle graph, at widths whose launch lists differ from
+    (5, 16, 2, 288)],      # 256's: 3 column tiles per problem / 9 and a two-chunk reduction
+    ids=["5-16-2", "1-16-2", "2-16-2", "3-64-2", "3-200-130", "5-16-2-hidden96", "5-16-2-hidden288"])
+def test_train_cycle_graph_equals_eager_bitwise(n_batches, n_eps, n_new, hidden, monkeypatch):
     """The cached hipGraph cycle (its opening launch k_cycle_open included: slots, scatter, normalizer, first plans), the
     call-by-call path with its cached per-call graphs and the same path on plain eager launches must produce identical bits
     -- with a buffer that overflows in the first cycle (replay_buffer.py:62-67), one that has room, and a wave of episodes
@@ -288,7 +292,9 @@ def test_train_cycle_graph_equals_eager_bitwise(n_batches, n_eps, n_new, monkeyp
     for mode in ("eager", "update_graph", "cycle_graph"):
         monkeypatch.setenv("RLARM_UPDATE_GRAPH", "0" if mode == "eager" else "1")   # read by hp_agent_create
         torch.manual_seed(0)                                        # same initial weights in every run
-        agent, rng = make_agent(batch=256, n_eps=n_eps, seed=11)    # n_eps = 16: small buffer, cycles overflow it
+        agent, rng = make_agent(batch=256, n_eps=n_eps, seed=11,    # n_eps = 16: small buffer, cycles overflow it
+                                env_params=None if hidden == 256 else dict(ENV_PARAMS, hidden=hidden))
+        assert (agent.engine()["engine"] == "layers") == (hidden != 256)
         agent.buffer.store_episode(make_episodes(15, seed=9, mode="walk"))
         for cycle in range(4 if n_new < 100 else 2):
             eps = make_episodes(n_new, seed=100 + cycle, mode="walk")
@@ -448,11 +454,34 @@ def test_forward_entry_points_match_oracle_at_other_action_scales(obs_dim, goal_
     """actor_network(x), critic_network(x, a) and act(obs, g, clip_obs=...) at action_max != 0.5 (the scale multiplies the
     tanh and divides the critic's action columns: not exact unless a power of two) and one or three actions, with clip_obs
     0.8 / clip_range 1.5 clipping a good part of the raw and of the normalised inputs of act."""
-    T, n_eps = 20, 8
-    env = {"obs": obs_dim, "goal": goal_dim, "action": act_dim, "action_max": amax, "max_timesteps": T}
+    _forward_entry_points({"obs": obs_dim, "goal": goal_dim, "action": act_dim, "action_max": amax, "max_timesteps": 20}, 37, 41)
+
+
+@pytest.mark.parametrize("rows", [1, 33])      # one padded 32-row tile / a full tile and a second one with a single row
+@pytest.mark.parametrize("hidden,obs_dim,goal_dim,act_dim,amax", [
+    (32, 29, 3, 1, 0.7),      # every layer one 32-wide column tile, reductions of 32: 2 of gemm_lds.h's 8 waves have products
+    (96, 29, 3, 1, 0.7),      # 6 super-steps for 8 waves, three column tiles
+    (288, 29, 3, 1, 0.7),     # the hidden layers' reduction takes a second, 32-column chunk
+    (96, 256, 7, 4, 0.7)])    # the first layer's does: 272 columns in the actor, 288 in the critic (256 / 7: the widest observation
+                              # the normalizers take and the widest goal the HER sampler takes)
+def test_forward_entry_points_match_oracle_at_other_hidden_widths(hidden, obs_dim, goal_dim, act_dim, amax, rows):
+    """The same three entry points, same bar, at hidden widths other than 256 (layer-per-launch GEMMs: actor_rows / critic_rows)
+    and with a network input wider than one 256-column chunk; the weights come from the oracle's own initialiser at that width."""
+    env = {"obs": obs_dim, "goal": goal_dim, "action": act_dim, "action_max": amax, "max_timesteps": 20, "hidden": hidden}
+    _forward_entry_points(env, rows, rows, oracle_init=True)
+
+
+def _forward_entry_points(env, rows_net, rows_act, oracle_init=False):
+    obs_dim, goal_dim, act_dim, amax, T, n_eps = env["obs"], env["goal"], env["action"], env["action_max"], env["max_timesteps"], 8
     torch.manual_seed(0)
     rng = fresh_rng(5)
     agent = ddpg_agent(Args(batch_size=64, buffer_size=n_eps * T, clip_obs=0.8, clip_range=1.5), None, env, rng=rng)
+    if oracle_init:
+        hidden = env["hidden"]
+        assert agent.engine()["engine"] == "layers"
+        agent._set_flat(NET_ACTOR, oupd.flatten(oupd.init_actor(obs_dim, goal_dim, act_dim, 11, hidden=hidden).values()))
+        agent._set_flat(NET_CRITIC, oupd.flatten(oupd.init_critic(obs_dim, goal_dim, act_dim, 12, hidden=hidden).values()))
+        assert agent.actor_network.state_dict()["fc3.weight"].shape == (hidden, hidden)
     eps = make_shape_episodes(n_eps, obs_dim, goal_dim, act_dim, T, seed=6)
     agent._update_normalizer(eps)
     on, gn = RunningNorm(obs_dim, default_clip_range=1.5), RunningNorm(goal_dim, default_clip_range=1.5)
@@ -460,23 +489,23 @@ def test_forward_entry_points_match_oracle_at_other_action_scales(obs_dim, goal_
     assert np.array_equal(bits(agent.o_norm.mean), bits(on.mean)) and np.array_equal(bits(agent.g_norm.std), bits(gn.std))
     rs = np.random.RandomState(3)
     xdim = obs_dim + goal_dim
-    x = rs.normal(size=(37, xdim)).astype(np.float32)
+    x = rs.normal(size=(rows_net, xdim)).astype(np.float32)
     pa = {k: v.detach().clone() for k, v in agent.actor_network.state_dict().items()}
     want = oupd.actor_forward(pa, torch.from_numpy(x), amax).numpy()
     got = agent.actor_network(torch.from_numpy(x)).numpy()
-    assert got.shape == (37, act_dim) and np.allclose(got, want, rtol=1e-5, atol=1e-6 * amax)
-    a = rs.uniform(-amax, amax, size=(37, act_dim)).astype(np.float32)
+    assert got.shape == (rows_net, act_dim) and np.allclose(got, want, rtol=1e-5, atol=1e-6 * amax)
+    a = rs.uniform(-amax, amax, size=(rows_net, act_dim)).astype(np.float32)
     pc = {k: v.detach() for k, v in agent.critic_network.state_dict().items()}
     want_q = oupd.critic_forward(pc, torch.from_numpy(x), torch.from_numpy(a), amax).numpy()
     got_q = agent.critic_network(torch.from_numpy(x), torch.from_numpy(a)).numpy()
-    assert got_q.shape == (37, 1) and np.allclose(got_q, want_q, rtol=1e-5, atol=1e-6)
-    obs, g = rs.uniform(-1.6, 1.6, size=(41, obs_dim)), rs.uniform(-1.6, 1.6, size=(41, goal_dim))
+    assert got_q.shape == (rows_net, 1) and np.allclose(got_q, want_q, rtol=1e-5, atol=1e-6)
+    obs, g = rs.uniform(-1.6, 1.6, size=(rows_act, obs_dim)), rs.uniform(-1.6, 1.6, size=(rows_act, goal_dim))
     o_c, g_c = np.clip(obs, -0.8, 0.8), np.clip(g, -0.8, 0.8)
     xin = np.concatenate([on.normalize(o_c), gn.normalize(g_c)], axis=1)
     assert np.mean(np.abs(obs) > 0.8) > 0.2 and np.mean(np.abs(xin) == 1.5) > 0.05      # both clips bite
     want_act = oupd.actor_forward(pa, torch.tensor(xin, dtype=torch.float32), amax).numpy()
     got_act = agent.act(obs, g, clip_obs=0.8)
-    assert got_act.shape == (41, act_dim) and np.allclose(got_act, want_act, rtol=1e-5, atol=1e-6 * amax)
+    assert got_act.shape == (rows_act, act_dim) and np.allclose(got_act, want_act, rtol=1e-5, atol=1e-6 * amax)
 
 
 def test_checkpoint_format_roundtrip(tmp_path):
@@ -493,6 +522,27 @@ def test_checkpoint_format_roundtrip(tmp_path):
     other.load_checkpoint(path)
     assert np.array_equal(other._get_flat(NET_ACTOR), agent._get_flat(NET_ACTOR))
     assert np.array_equal(other.o_norm.mean, o_mean)
+    # another hidden width: save, load into a fresh agent of that width -- parameters and act() bit for bit -- and a refusal,
+    # naming both widths, by an agent of another width, which keeps its weights
+    torch.manual_seed(3)
+    narrow, _ = make_agent(env_params=dict(ENV_PARAMS, hidden=96))
+    narrow.o_norm.update(np.random.RandomState(1).normal(size=(50, 27))); narrow.o_norm.recompute_stats()
+    narrow.g_norm.update(np.random.RandomState(2).normal(size=(50, 3))); narrow.g_norm.recompute_stats()
+    path96 = narrow.save_checkpoint(str(tmp_path / "96_model.pt"))
+    model96 = torch.load(path96, map_location="cpu", weights_only=False)[4]
+    assert model96["fc1.weight"].shape == (96, 30) and model96["fc3.weight"].shape == (96, 96) and model96["action_out.weight"].shape == (4, 96)
+    fresh, _ = make_agent(seed=1, env_params=dict(ENV_PARAMS, hidden=96))
+    assert not np.array_equal(fresh._get_flat(NET_ACTOR), narrow._get_flat(NET_ACTOR))
+    fresh.load_checkpoint(path96)
+    assert np.array_equal(bits(fresh._get_flat(NET_ACTOR)), bits(narrow._get_flat(NET_ACTOR)))
+    rs = np.random.RandomState(4)
+    obs, g = rs.normal(size=(33, 27)), rs.normal(size=(33, 3))
+    assert np.array_equal(bits(fresh.act(obs, g)), bits(narrow.act(obs, g)))
+    before = other._get_flat(NET_ACTOR)
+    with pytest.raises(ValueError, match="hidden width 96, this agent's is 256"):
+        other.load_checkpoint(path96)
+    assert np.array_equal(other._get_flat(NET_ACTOR), before) and np.array_equal(other.o_norm.mean, o_mean)
+    assert np.array_equal(other.actor_network.flat_parameters(), before)       # the host container took nothing either
 
 
 def test_demo_npz_preload():
@@ -703,15 +753,17 @@ def test_split_launch_is_bit_identical(batch, n_updates, monkeypatch):
             assert np.array_equal(bits(np.asarray(a)), bits(np.asarray(b)))
 
 
-@pytest.mark.parametrize("batch", [256, 1024, 2048, 3072])
-def test_repeated_runs_are_bit_identical(batch, monkeypatch):
+@pytest.mark.parametrize("batch,hidden", [(256, 256), (1024, 256), (2048, 256), (3072, 256), (256, 96)],
+                         ids=["256", "1024", "2048", "3072", "256-hidden96"])
+def test_repeated_runs_are_bit_identical(batch, hidden, monkeypatch):
     """Race check for the concurrent pieces of a cycle (index plans drawn two updates ahead, next minibatch gathered by
     spare workgroups, input sets ping-ponging): 60 cycles = 2400 updates twice, then once in the two-launch form --
     identical parameters and sampler state every time.  Batch 256 runs 4-row slabs, 1024 8-row slabs, 3072 the 32-row
-    engine whose weight-gradient workgroups meet through tickets (dw64.h: the sum order must not depend on who arrives last)."""
+    engine whose weight-gradient workgroups meet through tickets (dw64.h: the sum order must not depend on who arrives last);
+    hidden 96 the layer-per-launch engine (the launch structure does not matter to it: three identical runs)."""
     def run():
         torch.manual_seed(0)
-        agent, rng = make_agent(batch=batch, n_eps=32, seed=21)
+        agent, rng = make_agent(batch=batch, n_eps=32, seed=21, env_params=None if hidden == 256 else dict(ENV_PARAMS, hidden=hidden))
         agent.buffer.store_episode(make_episodes(15, seed=9, mode="walk"))
         for c in range(60):
             agent.train_cycle(make_episodes(2, seed=300 + c % 7, mode="walk"), 40)

@@ -187,3 +187,22 @@ def test_ddpg_update_hparams_golden():
     assert np.allclose(learner.flat("actor_target")[pa], g["actor_target_after_polyak"], rtol=0, atol=1e-6)
     assert np.allclose(learner.flat("critic_target")[pc], g["critic_target_after_polyak"], rtol=0, atol=1e-6)
     assert rs.get_state()[2] == int(g["pos"]) and np.array_equal(rs.get_state()[1], g["key"])
+
+
+def test_oracle_init_takes_a_hidden_width():
+    """init_actor / init_critic(hidden=...): the default is the 256 of every fixture, bit for bit; another width gives
+    models.py's shapes at that width, drawn from the same generator, and a learner built from them updates."""
+    for init, keys, head in ((oupd.init_actor, oupd.ACTOR_KEYS, 4), (oupd.init_critic, oupd.CRITIC_KEYS, 1)):
+        d, w = init(27, 3, 4, 5), init(27, 3, 4, 5, hidden=oupd.HIDDEN)
+        assert list(d) == list(w) and all(torch.equal(d[k], w[k]) for k in d)
+        in1 = 30 if head == 4 else 34
+        for hidden in (32, 96, 288):
+            p = init(27, 3, 4, 5, hidden=hidden)
+            assert [tuple(p[k + ".weight"].shape) for k in keys] == [(hidden, in1), (hidden, hidden), (hidden, hidden), (head, hidden)]
+            assert [tuple(p[k + ".bias"].shape) for k in keys] == [(hidden,), (hidden,), (hidden,), (head,)]
+            assert float(p["fc2.weight"].abs().max()) <= 1.0 / np.sqrt(hidden)
+    learner = oupd.DDPGLearner(oupd.init_actor(27, 3, 4, 0, hidden=96), oupd.init_critic(27, 3, 4, 1, hidden=96))
+    gen = torch.Generator().manual_seed(2)
+    x, xn = torch.randn(8, 30, generator=gen), torch.randn(8, 30, generator=gen)
+    res = learner.update(x, xn, torch.rand(8, 4, generator=gen) - 0.5, -torch.ones(8, 1))
+    assert res["actor_grads"].size == 96 * 30 + 96 + 2 * (96 * 96 + 96) + 4 * 96 + 4 and np.isfinite(res["critic_loss"])

@@ -146,3 +146,16 @@ def test_an_interrupted_write_never_shows_under_the_final_name(tmp_path, monkeyp
 def test_rank_paths():
     assert ts.rank_path("runs/state.npz", 3) == "runs/state_rank3.npz"
     assert ts.rank_path("state", 0) == "state_rank0"
+
+
+def test_dims_of_takes_the_hidden_width_from_the_agent():
+    """The manifest's `hidden` sizes the parameter arrays (expected_shapes) and is what hp_state_restore compares with the receiving
+    agent's width: it is the width the agent was built with (env_params['hidden'], 256 when absent), not a constant."""
+    from types import SimpleNamespace as NS
+    buf = NS(_dev=NS(T=4, size=7))
+    ep = {"obs": 5, "goal": 2, "action": 3, "action_max": 1.0, "max_timesteps": 4}
+    assert ts._dims_of(NS(env_params=ep, buffer=buf), 3) == dict(DIMS, hidden=256)
+    for hidden in (32, 128, 288):
+        dims = ts._dims_of(NS(env_params=dict(ep, hidden=hidden), buffer=buf), 3)
+        assert dims == dict(DIMS, hidden=hidden)
+        assert ts.expected_shapes(dims)["actor"][1] == (hidden * 7 + hidden + 2 * (hidden * hidden + hidden) + 3 * hidden + 3,)
