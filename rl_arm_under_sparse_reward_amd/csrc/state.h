@@ -1,6 +1,15 @@
 // state.h -- device side of the training state (state.hip): the order of a state's sections, the map between the reference's
 // flat named_parameters() order (utils.py:18-27) and the padded parameter arena (agent.h), and the position-weighted checksum.
 // Library-internal, not part of the C ABI.
+//
+// Section order.  ONE function of state.hip, state_layout(agent, buffer, norms, delta, n_episodes, S), writes the table of either
+// kind of state -- the 27 small sections, then the buffer --, makes the one offset pass (256-byte boundaries) and returns the size:
+//    0 ..  8   actor critic actor_target critic_target adam_actor_m adam_actor_v adam_critic_m adam_critic_v adam_step
+//    9 .. 26   o_norm_<field> g_norm_<field> (the eight NORM_FIELDS of each normalizer), rng_key rng_pos
+//   full       27 .. 30 buffer_obs buffer_ag buffer_g buffer_actions (n_episodes = current_size), 31 buffer_counters
+//   delta      27 buffer_delta_header, 28 buffer_delta_slots, 29 .. 32 buffer_delta_obs buffer_delta_ag buffer_delta_g
+//              buffer_delta_actions (room for n_episodes = max_dirty episodes), 33 buffer_counters
+// hp_state_layout / hp_state_layout_delta report it; capture, drain, fetch and restore all work from it.
 #pragma once
 #include "agent.h"
 

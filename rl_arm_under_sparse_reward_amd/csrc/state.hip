@@ -29,7 +29,7 @@ struct StateArena {
     uint64_t ticket = 0;          // of the most recent capture
     bool pending = false;         // ... which has not been fetched (or abandoned) yet
     size_t bytes = 0;             // ... and its blob size
-    int n_sections = ST_SECTIONS; // ... and its section count: ST_SECTIONS (full) or DS_SECTIONS (delta)
+    bool delta = false;           // ... and its kind: a full state (ST_SECTIONS sections) or a delta (DS_SECTIONS)
     size_t hdr_off = 0;           // ... a delta's header section in the blob
     uint32_t capture_epoch = 0;   // the buffer epoch the most recent capture recorded (host mirror)
 };
@@ -314,9 +314,25 @@ static const char *const k_norm_field[NORM_FIELDS] = {"local_sum", "local_sumsq"
                                                       "total_sumsq", "total_count", "mean", "std"};
 static const int k_elem_bytes[5] = {4, 8, 8, 4, 4};
 
-static size_t state_layout(const hp_agent *a, const hp_buffer *b, const hp_norm *on, const hp_norm *gn, int64_t cs,
-                           hp_state_section *S) {
-    memset(S, 0, sizeof(hp_state_section) * ST_SECTIONS);
+static int n_sections(bool delta) { return delta ? DS_SECTIONS : ST_SECTIONS; }
+
+// the buffer's four row arrays: where they live and how many doubles an episode has in each
+struct BufRows {
+    double *dev[4];
+    long long ep[4];
+};
+static BufRows buffer_rows(const hp_buffer *b) {
+    return {{b->d_obs, b->d_ag, b->d_g, b->d_act},
+            {(long long)b->ep_obs(), (long long)b->ep_ag(), (long long)b->ep_g(), (long long)b->ep_act()}};
+}
+
+// THE layout of a training state (state.h has the section order): the small sections, then the buffer -- of a full state as the
+// rows of its first n_episodes episodes, of a delta as header, slot list and packed rows with room for n_episodes dirty ones --
+// then the counters.  Fills S[0 .. n_sections(delta)) and returns the blob's size.
+static size_t state_layout(const hp_agent *a, const hp_buffer *b, const hp_norm *on, const hp_norm *gn, bool delta,
+                           int64_t n_episodes, hp_state_section *S) {
+    const int nsec = n_sections(delta);
+    memset(S, 0, sizeof(hp_state_section) * nsec);
     auto set = [&](int i, const char *name, int dtype, int64_t count) {
         snprintf(S[i].name, sizeof(S[i].name), "%s", name);
         S[i].dtype = dtype;
@@ -324,14 +340,9 @@ static size_t state_layout(const hp_agent *a, const hp_buffer *b, const hp_norm 
         S[i].count = count;
     };
     const int64_t na = flat_map(a, false).n, nc = flat_map(a, true).n;
-    set(ST_ACTOR, "actor", SD_F32, na);
-    set(ST_CRITIC, "critic", SD_F32, nc);
-    set(ST_ACTOR_TARGET, "actor_target", SD_F32, na);
-    set(ST_CRITIC_TARGET, "critic_target", SD_F32, nc);
-    set(ST_ADAM_ACTOR_M, "adam_actor_m", SD_F32, na);
-    set(ST_ADAM_ACTOR_V, "adam_actor_v", SD_F32, na);
-    set(ST_ADAM_CRITIC_M, "adam_critic_m", SD_F32, nc);
-    set(ST_ADAM_CRITIC_V, "adam_critic_v", SD_F32, nc);
+    static const char *const k_flat[8] = {"actor", "critic", "actor_target", "critic_target",
+                                          "adam_actor_m", "adam_actor_v", "adam_critic_m", "adam_critic_v"};
+    for (int v = 0; v < 8; ++v) set(ST_ACTOR + v, k_flat[v], SD_F32, (v == 1 || v == 3 || v >= 6) ? nc : na);   // as k_state_flat
     set(ST_ADAM_STEP, "adam_step", SD_I64, 1);
     for (int k = 0; k < 2; ++k)
         for (int f = 0; f < NORM_FIELDS; ++f) {
@@ -342,41 +353,17 @@ static size_t state_layout(const hp_agent *a, const hp_buffer *b, const hp_norm 
         }
     set(ST_RNG_KEY, "rng_key", SD_U32, MT_N);
     set(ST_RNG_POS, "rng_pos", SD_I32, 1);
-    set(ST_BUF_OBS, "buffer_obs", SD_F64, cs * (int64_t)b->ep_obs());
-    set(ST_BUF_AG, "buffer_ag", SD_F64, cs * (int64_t)b->ep_ag());
-    set(ST_BUF_G, "buffer_g", SD_F64, cs * (int64_t)b->ep_g());
-    set(ST_BUF_ACT, "buffer_actions", SD_F64, cs * (int64_t)b->ep_act());
-    set(ST_BUF_COUNTERS, "buffer_counters", SD_I64, 2);
-    size_t off = 0;
-    for (int i = 0; i < ST_SECTIONS; ++i) {
-        S[i].offset = (int64_t)off;
-        off += ((size_t)S[i].count * S[i].elem_bytes + ST_ALIGN - 1) / ST_ALIGN * ST_ALIGN;
+    static const char *const k_rows[2][4] = {{"buffer_obs", "buffer_ag", "buffer_g", "buffer_actions"},
+                                             {"buffer_delta_obs", "buffer_delta_ag", "buffer_delta_g", "buffer_delta_actions"}};
+    if (delta) {
+        set(DS_HEADER, "buffer_delta_header", SD_I64, 4);
+        set(DS_SLOTS, "buffer_delta_slots", SD_I64, n_episodes);
     }
-    return off;
-}
-
-// a delta with room for max_dirty episodes: the small sections of a full state at their indices, then DS_HEADER .. DS_COUNTERS
-static size_t delta_layout(const hp_agent *a, const hp_buffer *b, const hp_norm *on, const hp_norm *gn, int64_t max_dirty,
-                           hp_state_section *S) {
-    hp_state_section F[ST_SECTIONS];
-    (void)state_layout(a, b, on, gn, 0, F);
-    memset(S, 0, sizeof(hp_state_section) * DS_SECTIONS);
-    memcpy(S, F, sizeof(hp_state_section) * (ST_RNG_POS + 1));
-    auto set = [&](int i, const char *name, int dtype, int64_t count) {
-        snprintf(S[i].name, sizeof(S[i].name), "%s", name);
-        S[i].dtype = dtype;
-        S[i].elem_bytes = k_elem_bytes[dtype];
-        S[i].count = count;
-    };
-    set(DS_HEADER, "buffer_delta_header", SD_I64, 4);
-    set(DS_SLOTS, "buffer_delta_slots", SD_I64, max_dirty);
-    set(DS_OBS, "buffer_delta_obs", SD_F64, max_dirty * (int64_t)b->ep_obs());
-    set(DS_AG, "buffer_delta_ag", SD_F64, max_dirty * (int64_t)b->ep_ag());
-    set(DS_G, "buffer_delta_g", SD_F64, max_dirty * (int64_t)b->ep_g());
-    set(DS_ACT, "buffer_delta_actions", SD_F64, max_dirty * (int64_t)b->ep_act());
-    set(DS_COUNTERS, "buffer_counters", SD_I64, 2);
+    const BufRows R = buffer_rows(b);
+    for (int k = 0; k < 4; ++k) set((delta ? DS_OBS : ST_BUF_OBS) + k, k_rows[delta][k], SD_F64, n_episodes * R.ep[k]);
+    set(nsec - 1, "buffer_counters", SD_I64, 2);
     size_t off = 0;
-    for (int i = 0; i < DS_SECTIONS; ++i) {
+    for (int i = 0; i < nsec; ++i) {
         S[i].offset = (int64_t)off;
         off += ((size_t)S[i].count * S[i].elem_bytes + ST_ALIGN - 1) / ST_ALIGN * ST_ALIGN;
     }
@@ -408,38 +395,66 @@ static int arena_get(hp_agent *a, StateArena **out) {
     return HP_OK;
 }
 
-// grow the snapshot arena (nobody reads it: the caller has made sure no drain is in flight)
-static int arena_ensure(StateArena *A, size_t need) {
-    if (need <= A->dev_bytes) return HP_OK;
-    if (A->dev) (void)hipFree(A->dev);
-    A->dev = nullptr;
-    A->dev_bytes = 0;
-    HP_CHECK_HIP(hipMalloc((void **)&A->dev, need));
-    A->dev_bytes = need;
+// grow the snapshot arena and, for a capture, its pinned copy (nobody reads them: the caller has made sure no drain is in flight)
+static int arena_ensure(StateArena *A, size_t need, bool pinned) {
+    if (need > A->dev_bytes) {
+        if (A->dev) (void)hipFree(A->dev);
+        A->dev = nullptr;
+        A->dev_bytes = 0;
+        HP_CHECK_HIP(hipMalloc((void **)&A->dev, need));
+        A->dev_bytes = need;
+    }
+    if (pinned && need > A->pin_bytes) {
+        if (A->pin) (void)hipHostFree(A->pin);
+        A->pin = nullptr;
+        A->pin_bytes = 0;
+        HP_CHECK_HIP(hipHostMalloc((void **)&A->pin, need, hipHostMallocDefault));
+        A->pin_bytes = need;
+    }
     return HP_OK;
+}
+
+// workgroups of a checksum over nwords 8-byte words: four 16-byte loads per lane and trip
+static unsigned checksum_grid(u64 nwords) {
+    return (unsigned)std::min<u64>(std::max<u64>((nwords / 2 + 256 * 4 - 1) / (256 * 4), 1), 2048);
 }
 
 static int launch_checksum(const void *dev, size_t bytes, u64 *d_out, hipStream_t s, int blocks = 0) {
     const u64 nwords = bytes / 8;
-    if (blocks <= 0) {
-        const u64 want = (nwords / 2 + 256 * 4 - 1) / (256 * 4);   // four 16-byte loads per lane and trip
-        blocks = (int)std::min<u64>(std::max<u64>(want, 1), 2048);
-    }
     HP_KLOG("k_checksum");
-    hipLaunchKernelGGL(k_checksum, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const u64 *>(dev), nwords,
-                       (unsigned)(bytes % 8), d_out);
+    hipLaunchKernelGGL(k_checksum, dim3(blocks > 0 ? (unsigned)blocks : checksum_grid(nwords)), dim3(256), 0, s,
+                       static_cast<const u64 *>(dev), nwords, (unsigned)(bytes % 8), d_out);
     HP_CHECK_HIP(hipGetLastError());
     return HP_OK;
 }
 
-static int checksum_sections(StateArena *A, const hp_state_section *S, hipStream_t s) {
-    HP_CHECK_HIP(hipMemsetAsync(A->d_sums, 0, sizeof(u64) * 2 * ST_SECTIONS, s));
-    for (int i = 0; i < ST_SECTIONS; ++i)
-        HP_TRY(launch_checksum(A->dev + S[i].offset, (size_t)S[i].count * S[i].elem_bytes, A->d_sums + 2 * i, s));
+// The sums of the nsec sections of the layout S in the arena, on stream s: whole sections, but of a delta (hdr = its header in the
+// arena) the used prefix of the slot list and of the four row sections -- nothing at all where there is no room for a slot.
+static int checksum_layout(StateArena *A, const hp_state_section *S, int nsec, hipStream_t s, const long long *hdr,
+                           int64_t max_dirty) {
+    HP_CHECK_HIP(hipMemsetAsync(A->d_sums, 0, sizeof(u64) * 2 * nsec, s));
+    for (int i = 0; i < nsec; ++i) {
+        if (!hdr || i < DS_SLOTS || i > DS_ACT) {
+            HP_TRY(launch_checksum(A->dev + S[i].offset, (size_t)S[i].count * S[i].elem_bytes, A->d_sums + 2 * i, s));
+            continue;
+        }
+        if (max_dirty == 0) continue;
+        HP_KLOG("k_checksum_prefix");
+        hipLaunchKernelGGL(k_checksum_prefix, dim3(checksum_grid((u64)S[i].count)), dim3(256), 0, s,
+                           reinterpret_cast<const u64 *>(A->dev + S[i].offset), hdr, (u64)(S[i].count / max_dirty),   // words per episode
+                           (long long)max_dirty, A->d_sums + 2 * i);
+        HP_CHECK_HIP(hipGetLastError());
+    }
     return HP_OK;
 }
 
-static FlatArgs flat_args(hp_agent *a, char *base, const hp_state_section *S) {
+// k_state_flat + k_state_small between the live objects and the layout S at `base`, on the learner's stream; `counters` is the
+// index of S's buffer_counters section (the small sections sit at the same indices in both kinds of state).  A restore rebuilds
+// every derived copy of the parameters between the two, as hp_agent_set_params / hp_agent_sync_targets do.
+template <bool RESTORE>
+static int launch_state_pair(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, char *base, const hp_state_section *S,
+                             int counters) {
+    hipStream_t s = a->ctx->stream;
     FlatArgs F;
     float *arena[8] = {a->params, a->params, a->targets, a->targets, a->adam_m, a->adam_v, a->adam_m, a->adam_v};
     for (int v = 0; v < 8; ++v) {
@@ -448,17 +463,24 @@ static FlatArgs flat_args(hp_agent *a, char *base, const hp_state_section *S) {
     }
     F.m[0] = flat_map(a, false);
     F.m[1] = flat_map(a, true);
-    return F;
-}
-
-static SmallArgs small_args(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, char *base,
-                            const hp_state_section *S) {
+    const int nmax = std::max(F.m[0].n, F.m[1].n);
+    if (!RESTORE) HP_KLOG("k_state_flat");
+    hipLaunchKernelGGL(k_state_flat<RESTORE>, dim3((unsigned)((nmax + 255) / 256), 8), dim3(256), 0, s, F);
+    HP_CHECK_HIP(hipGetLastError());
+    if (RESTORE) {
+        HP_TRY(enqueue_relayout(a, false));
+        HP_TRY(enqueue_relayout(a, true));
+    }
     SmallArgs M;
     M.nz[0] = on->d; M.nz[1] = gn->d;
     M.size[0] = on->size; M.size[1] = gn->size;
     M.rng = rng->d_state; M.st = a->d_state; M.meta = b->d_meta; M.base = base;
     for (int i = 0; i < ST_SECTIONS; ++i) M.off[i] = S[i].offset;
-    return M;
+    M.off[ST_BUF_COUNTERS] = S[counters].offset;
+    if (!RESTORE) HP_KLOG("k_state_small");
+    hipLaunchKernelGGL(k_state_small<RESTORE>, dim3(1), dim3(256), 0, s, M);
+    HP_CHECK_HIP(hipGetLastError());
+    return HP_OK;
 }
 
 // The dirty scan of `cs` slots of b on stream s: hdr[0] = n_dirty, hdr[1] = overflow, slots[0 .. min(n_dirty, max_dirty)).
@@ -506,22 +528,27 @@ void state_arena_destroy(hp_agent *a) {
 }
 
 // --------------------------------------------------------------------------------- C ABI
-extern "C" {
-
-int hp_state_layout(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, int64_t current_size, hp_state_section *out,
-                    int32_t *n, size_t *total_bytes) {
-    HP_REQUIRE(a && b && on && gn && n, HP_ERR_INVALID, "hp_state_layout: null argument");
+// hp_state_layout (n_episodes = current_size, < 0: the buffer's) and hp_state_layout_delta (n_episodes = max_dirty)
+static int layout_entry(const char *who, bool delta, hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, int64_t n_episodes,
+                        hp_state_section *out, int32_t *n, size_t *total_bytes) {
+    HP_REQUIRE(a && b && on && gn && n, HP_ERR_INVALID, "%s: null argument", who);
     HP_SERIALISE(a);
-    if (current_size < 0) current_size = b->current_size;
-    HP_REQUIRE(current_size <= b->size, HP_ERR_INVALID, "hp_state_layout: current_size %lld exceeds the buffer's capacity %lld",
-               (long long)current_size, (long long)b->size);
-    hp_state_section S[ST_SECTIONS];
-    const size_t total = state_layout(a, b, on, gn, current_size, S);
-    if (out) {
-        HP_REQUIRE(*n >= ST_SECTIONS, HP_ERR_INVALID, "hp_state_layout: room for %d sections, %d needed", *n, ST_SECTIONS);
-        memcpy(out, S, sizeof(S));
+    if (delta) {
+        HP_REQUIRE(n_episodes >= 0 && n_episodes <= b->size, HP_ERR_INVALID, "%s: max_dirty %lld outside [0, %lld]", who,
+                   (long long)n_episodes, (long long)b->size);
+    } else {
+        if (n_episodes < 0) n_episodes = b->current_size;
+        HP_REQUIRE(n_episodes <= b->size, HP_ERR_INVALID, "%s: current_size %lld exceeds the buffer's capacity %lld", who,
+                   (long long)n_episodes, (long long)b->size);
     }
-    *n = ST_SECTIONS;
+    hp_state_section S[DS_SECTIONS];
+    const int nsec = n_sections(delta);
+    const size_t total = state_layout(a, b, on, gn, delta, n_episodes, S);
+    if (out) {
+        HP_REQUIRE(*n >= nsec, HP_ERR_INVALID, "%s: room for %d sections, %d needed", who, *n, nsec);
+        memcpy(out, S, sizeof(hp_state_section) * nsec);
+    }
+    *n = nsec;
     if (total_bytes) *total_bytes = total;
     return HP_OK;
 }
@@ -550,29 +577,13 @@ static int state_capture(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp
                    (long long)max_dirty, (long long)cs);
     }
     hp_state_section S[DS_SECTIONS];
-    const int nsec = delta ? DS_SECTIONS : ST_SECTIONS;
-    const size_t total = delta ? delta_layout(a, b, on, gn, max_dirty, S) : state_layout(a, b, on, gn, cs, S);
+    const int nsec = n_sections(delta);
+    const size_t total = state_layout(a, b, on, gn, delta, delta ? max_dirty : cs, S);
     // the previous ticket was fetched, so its drain is over: arena and pinned copy are free
-    HP_TRY(arena_ensure(A, total));
-    if (total > A->pin_bytes) {
-        if (A->pin) (void)hipHostFree(A->pin);
-        A->pin = nullptr;
-        A->pin_bytes = 0;
-        HP_CHECK_HIP(hipHostMalloc((void **)&A->pin, total, hipHostMallocDefault));
-        A->pin_bytes = total;
-    }
+    HP_TRY(arena_ensure(A, total, true));
     // learner's stream: the snapshot itself, nothing else
-    const FlatArgs F = flat_args(a, A->dev, S);
-    const int nmax = std::max(F.m[0].n, F.m[1].n);
-    HP_KLOG("k_state_flat");
-    hipLaunchKernelGGL(k_state_flat<false>, dim3((unsigned)((nmax + 255) / 256), 8), dim3(256), 0, s, F);
-    HP_CHECK_HIP(hipGetLastError());
-    SmallArgs M = small_args(a, b, on, gn, rng, A->dev, S);
-    if (delta) M.off[ST_BUF_COUNTERS] = S[DS_COUNTERS].offset;   // (the small sections sit at a full state's indices)
-    HP_KLOG("k_state_small");
-    hipLaunchKernelGGL(k_state_small<false>, dim3(1), dim3(256), 0, s, M);
-    HP_CHECK_HIP(hipGetLastError());
-    const double *rows[4] = {b->d_obs, b->d_ag, b->d_g, b->d_act};
+    HP_TRY(launch_state_pair<false>(a, b, on, gn, rng, A->dev, S, nsec - 1));
+    const BufRows R = buffer_rows(b);
     long long *hdr = nullptr;
     if (delta) {
         hdr = reinterpret_cast<long long *>(A->dev + S[DS_HEADER].offset);
@@ -580,14 +591,11 @@ static int state_capture(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp
         HP_TRY(launch_dirty_scan(b, cs, since, max_dirty, hdr, slots, s));
         if (max_dirty > 0) {
             PackArgs P;
-            P.hdr = hdr;
-            P.slots = slots;
-            P.max_dirty = max_dirty;
-            const long long ep[4] = {(long long)b->ep_obs(), (long long)b->ep_ag(), (long long)b->ep_g(), (long long)b->ep_act()};
+            P.hdr = hdr; P.slots = slots; P.max_dirty = max_dirty;
             for (int k = 0; k < 4; ++k) {
-                P.src[k] = rows[k];
+                P.src[k] = R.dev[k];
                 P.dst[k] = reinterpret_cast<double *>(A->dev + S[DS_OBS + k].offset);
-                P.ep[k] = ep[k];
+                P.ep[k] = R.ep[k];
             }
             HP_KLOG("k_delta_pack");
             hipLaunchKernelGGL(k_delta_pack, dim3((unsigned)(std::min<int64_t>(max_dirty, 4096) * DS_PACK_PARTS)), dim3(256), 0, s, P);
@@ -595,7 +603,7 @@ static int state_capture(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp
         }
     } else {
         for (int k = 0; k < 4 && cs > 0; ++k)
-            HP_CHECK_HIP(hipMemcpyAsync(A->dev + S[ST_BUF_OBS + k].offset, rows[k], (size_t)S[ST_BUF_OBS + k].count * 8,
+            HP_CHECK_HIP(hipMemcpyAsync(A->dev + S[ST_BUF_OBS + k].offset, R.dev[k], (size_t)S[ST_BUF_OBS + k].count * 8,
                                         hipMemcpyDeviceToDevice, s));
     }
     HP_KLOG("k_epoch_advance");
@@ -605,23 +613,7 @@ static int state_capture(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp
     HP_CHECK_HIP(hipEventRecord(A->captured, s));
     // drain stream: checksums of the snapshot, then the snapshot and the sums to pinned memory
     HP_CHECK_HIP(hipStreamWaitEvent(A->drain, A->captured, 0));
-    if (delta) {
-        HP_CHECK_HIP(hipMemsetAsync(A->d_sums, 0, sizeof(u64) * 2 * DS_SECTIONS, A->drain));
-        for (int i = 0; i < DS_SECTIONS; ++i) {
-            if (i < DS_SLOTS || i > DS_ACT) {
-                HP_TRY(launch_checksum(A->dev + S[i].offset, (size_t)S[i].count * S[i].elem_bytes, A->d_sums + 2 * i, A->drain));
-                continue;
-            }
-            if (max_dirty == 0) continue;
-            const u64 per_ep = (u64)(S[i].count / max_dirty);   // 8-byte words per episode
-            const u64 want = ((u64)S[i].count / 2 + 256 * 4 - 1) / (256 * 4);
-            HP_KLOG("k_checksum_prefix");
-            hipLaunchKernelGGL(k_checksum_prefix, dim3((unsigned)std::min<u64>(std::max<u64>(want, 1), 2048)), dim3(256), 0, A->drain,
-                               reinterpret_cast<const u64 *>(A->dev + S[i].offset), hdr, per_ep, (long long)max_dirty,
-                               A->d_sums + 2 * i);
-            HP_CHECK_HIP(hipGetLastError());
-        }
-    } else HP_TRY(checksum_sections(A, S, A->drain));
+    HP_TRY(checksum_layout(A, S, nsec, A->drain, hdr, max_dirty));
     for (size_t off = 0; off < total; off += ST_DRAIN_CHUNK)
         HP_CHECK_HIP(hipMemcpyAsync(A->pin + off, A->dev + off, std::min<size_t>(ST_DRAIN_CHUNK, total - off),
                                     hipMemcpyDeviceToHost, A->drain));
@@ -629,11 +621,23 @@ static int state_capture(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp
     HP_CHECK_HIP(hipEventRecord(A->drained, A->drain));
     A->pending = true;
     A->bytes = total;
-    A->n_sections = nsec;
+    A->delta = delta;
     A->hdr_off = delta ? (size_t)S[DS_HEADER].offset : 0;
     *ticket = ++A->ticket;
     if (bytes) *bytes = total;
     return HP_OK;
+}
+
+extern "C" {
+
+int hp_state_layout(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, int64_t current_size, hp_state_section *out,
+                    int32_t *n, size_t *total_bytes) {
+    return layout_entry("hp_state_layout", false, a, b, on, gn, current_size, out, n, total_bytes);
+}
+
+int hp_state_layout_delta(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, int64_t max_dirty, hp_state_section *out, int32_t *n,
+                          size_t *total_bytes) {
+    return layout_entry("hp_state_layout_delta", true, a, b, on, gn, max_dirty, out, n, total_bytes);
 }
 
 int hp_state_capture(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, uint64_t *ticket, size_t *bytes) {
@@ -643,23 +647,6 @@ int hp_state_capture(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng
 int hp_state_capture_delta(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng *rng, uint32_t since_epoch, int64_t max_dirty,
                            uint64_t *ticket, size_t *bytes) {
     return state_capture(a, b, on, gn, rng, true, since_epoch, max_dirty, ticket, bytes);
-}
-
-int hp_state_layout_delta(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, int64_t max_dirty, hp_state_section *out, int32_t *n,
-                          size_t *total_bytes) {
-    HP_REQUIRE(a && b && on && gn && n, HP_ERR_INVALID, "hp_state_layout_delta: null argument");
-    HP_SERIALISE(a);
-    HP_REQUIRE(max_dirty >= 0 && max_dirty <= b->size, HP_ERR_INVALID, "hp_state_layout_delta: max_dirty %lld outside [0, %lld]",
-               (long long)max_dirty, (long long)b->size);
-    hp_state_section S[DS_SECTIONS];
-    const size_t total = delta_layout(a, b, on, gn, max_dirty, S);
-    if (out) {
-        HP_REQUIRE(*n >= DS_SECTIONS, HP_ERR_INVALID, "hp_state_layout_delta: room for %d sections, %d needed", *n, DS_SECTIONS);
-        memcpy(out, S, sizeof(S));
-    }
-    *n = DS_SECTIONS;
-    if (total_bytes) *total_bytes = total;
-    return HP_OK;
 }
 
 int hp_state_epochs(hp_agent *a, hp_buffer *b, uint32_t *capture_epoch, uint32_t *epoch, uint32_t *min_since) {
@@ -695,10 +682,10 @@ int hp_state_fetch(hp_agent *a, uint64_t ticket, int32_t wait, void *host_out, s
     }
     // (the pinned copy cannot change under this: a new capture is refused while this ticket is pending)
     long long hdr[2] = {0, 0};
-    if (A->n_sections == DS_SECTIONS) memcpy(hdr, A->pin + A->hdr_off, sizeof(hdr));
+    if (A->delta) memcpy(hdr, A->pin + A->hdr_off, sizeof(hdr));
     if (host_out && !hdr[1]) {
         memcpy(host_out, A->pin, A->bytes);
-        if (sums) memcpy(sums, A->pin_sums, sizeof(u64) * 2 * A->n_sections);
+        if (sums) memcpy(sums, A->pin_sums, sizeof(u64) * 2 * n_sections(A->delta));
     }
     {
         HP_SERIALISE(a);
@@ -730,7 +717,7 @@ int hp_state_restore(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng
     HP_REQUIRE(cs >= 0 && cs <= b->size, HP_ERR_INVALID, "hp_state_restore: current_size %lld outside [0, %lld]", (long long)cs,
                (long long)b->size);
     hp_state_section S[ST_SECTIONS];
-    const size_t total = state_layout(a, b, on, gn, cs, S);
+    const size_t total = state_layout(a, b, on, gn, false, cs, S);
     HP_REQUIRE(bytes == total, HP_ERR_INVALID, "hp_state_restore: a state of %lld episodes is %zu bytes, the caller gave %zu",
                (long long)cs, total, bytes);
     const char *in = static_cast<const char *>(host_in);
@@ -747,10 +734,10 @@ int hp_state_restore(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng
     // a capture still draining reads the arena: let it finish (its pinned copy stays fetchable)
     if (A->pending) HP_CHECK_HIP(hipEventSynchronize(A->drained));
     hipStream_t s = a->ctx->stream;
-    HP_TRY(arena_ensure(A, total));
+    HP_TRY(arena_ensure(A, total, false));
     // 1. upload into the arena and sum it THERE: nothing live is touched before the sums agree with the caller's
     HP_CHECK_HIP(hipMemcpyAsync(A->dev, host_in, total, hipMemcpyHostToDevice, s));
-    HP_TRY(checksum_sections(A, S, s));
+    HP_TRY(checksum_layout(A, S, ST_SECTIONS, s, nullptr, 0));
     u64 got[2 * ST_SECTIONS];
     HP_CHECK_HIP(hipMemcpyAsync(got, A->d_sums, sizeof(got), hipMemcpyDeviceToHost, s));
     HP_CHECK_HIP(hipStreamSynchronize(s));
@@ -760,17 +747,10 @@ int hp_state_restore(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, hp_rng
                    "was restored", S[i].name, got[2 * i], got[2 * i + 1], (u64)sums[2 * i], (u64)sums[2 * i + 1]);
     // 2. commit.  Parameters, targets and optimizer state into the arenas, then every derived copy as hp_agent_set_params /
     // hp_agent_sync_targets rebuild them
-    const FlatArgs F = flat_args(a, A->dev, S);
-    const int nmax = std::max(F.m[0].n, F.m[1].n);
-    hipLaunchKernelGGL(k_state_flat<true>, dim3((unsigned)((nmax + 255) / 256), 8), dim3(256), 0, s, F);
-    HP_CHECK_HIP(hipGetLastError());
-    HP_TRY(enqueue_relayout(a, false));
-    HP_TRY(enqueue_relayout(a, true));
-    hipLaunchKernelGGL(k_state_small<true>, dim3(1), dim3(256), 0, s, small_args(a, b, on, gn, rng, A->dev, S));
-    HP_CHECK_HIP(hipGetLastError());
-    double *rows[4] = {b->d_obs, b->d_ag, b->d_g, b->d_act};
+    HP_TRY(launch_state_pair<true>(a, b, on, gn, rng, A->dev, S, ST_BUF_COUNTERS));
+    const BufRows R = buffer_rows(b);
     for (int k = 0; k < 4 && cs > 0; ++k)
-        HP_CHECK_HIP(hipMemcpyAsync(rows[k], A->dev + S[ST_BUF_OBS + k].offset, (size_t)S[ST_BUF_OBS + k].count * 8,
+        HP_CHECK_HIP(hipMemcpyAsync(R.dev[k], A->dev + S[ST_BUF_OBS + k].offset, (size_t)S[ST_BUF_OBS + k].count * 8,
                                     hipMemcpyDeviceToDevice, s));
     HP_TRY(buffer_launch_pack_range(b, 0, cs));   // throughput rows, when the receiver has them
     b->current_size = cs;

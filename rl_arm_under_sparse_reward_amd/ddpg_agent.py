@@ -619,10 +619,9 @@ class ddpg_agent(EpisodeAudit):
         take = base
         if os.path.exists(delta):
             try:
-                cited, key = ts.read_manifest(delta)["base"], ts.base_key(ts.read_manifest(base), where=base)
-                if all(cited[f] == key[f] for f in ("lineage", "capture_epoch", "current_size", "sums")):
+                if ts.cites(ts.read_manifest(delta), ts.read_manifest(base), where=base) is None:
                     take = delta
-            except (ts.StateError, KeyError):
+            except (ValueError, KeyError, TypeError):     # (StateError is a ValueError) a delta or base that cannot be read as one
                 pass
         print("resuming from", take, "(delta over %s)" % base if take is delta else "(full state)")
         self.load_training_state(take, base=base if take is delta else None)

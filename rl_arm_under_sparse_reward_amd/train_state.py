@@ -118,9 +118,29 @@ def stream_shapes(n: int, family: str = "explore") -> dict:
             f"{family}_stream_has_gauss": ("<i4", (n,)), f"{family}_stream_gauss": ("<f8", (n,))}
 
 
-STREAM_FAMILIES = ("explore", "reset")
-STREAM_ARRAYS = tuple(stream_shapes(0))
-RESET_STREAM_ARRAYS = tuple(stream_shapes(0, "reset"))
+def _family(name, find, saved_without, agent_without):
+    """One family of per-environment streams: how to find the agent's (`find(agent)` -> DeviceRandomStreams or None), its array
+    names, its manifest field, and what load() says when agent and state disagree about it."""
+    return {"find": find, "arrays": tuple(stream_shapes(0, name)), "field": f"{name}_streams",
+            "saved_without": saved_without, "agent_without": agent_without}
+
+
+# in the order load() refuses them
+STREAM_FAMILIES = {
+    "explore": _family(
+        "explore", lambda agent: getattr(agent, "explore_streams", None),
+        "the agent explores with one stream per environment, but the state was saved without: arrays {names} are missing",
+        "the state carries {n} per-environment exploration streams (arrays {names}), but the agent has none: call "
+        "enable_explore_streams() (args.explore_streams) before loading"),
+    # the environments' reset generators (device_env: enable_device_reset); None: no such environment, or it is reset on the host
+    "reset": _family(
+        "reset", lambda agent: getattr(getattr(agent, "vec_env", None), "reset_streams", None),
+        "the agent's environment is reset on the device, but the state was saved without reset streams: arrays {names} are missing",
+        "the state carries {n} per-environment reset streams (arrays {names}), but the agent's environment is reset on the host: "
+        "call vec_env.enable_device_reset() (args.device_reset) before loading"),
+}
+STREAM_ARRAYS = STREAM_FAMILIES["explore"]["arrays"]
+RESET_STREAM_ARRAYS = STREAM_FAMILIES["reset"]["arrays"]
 DEVICE_ARRAYS = tuple(expected_shapes({"obs": 1, "goal": 1, "action": 1, "hidden": 1, "T": 1, "current_size": 0}))
 
 
@@ -150,13 +170,18 @@ def write_state(path, arrays: dict, manifest: dict):
     return path
 
 
-def read_state(path):
-    """-> (arrays, manifest).  Nothing is executed: the file holds arrays and JSON text only (allow_pickle=False)."""
+def _read_npz(path, take):
+    """take(the open .npz); whatever makes the file unreadable becomes a StateError."""
     try:
         with np.load(os.fspath(path), allow_pickle=False) as z:
-            arrays = {k: z[k] for k in z.files}
+            return take(z)
     except (zipfile.BadZipFile, EOFError, OSError, ValueError, KeyError) as e:
         raise StateError(f"{path}: not a readable training state ({type(e).__name__}: {e})") from e
+
+
+def read_state(path):
+    """-> (arrays, manifest).  Nothing is executed: the file holds arrays and JSON text only (allow_pickle=False)."""
+    arrays = _read_npz(path, lambda z: {k: z[k] for k in z.files})
     if "manifest" not in arrays:
         raise StateError(f"{path}: array 'manifest' is missing")
     try:
@@ -172,11 +197,7 @@ def read_state(path):
 
 def read_manifest(path):
     """The manifest alone (the arrays of an .npz are read on access: a 150 MB base costs nothing here)."""
-    try:
-        with np.load(os.fspath(path), allow_pickle=False) as z:
-            return json.loads(str(z["manifest"][()]))
-    except (zipfile.BadZipFile, EOFError, OSError, ValueError, KeyError) as e:
-        raise StateError(f"{path}: not a readable training state ({type(e).__name__}: {e})") from e
+    return _read_npz(path, lambda z: json.loads(str(z["manifest"][()])))
 
 
 def is_delta(manifest) -> bool:
@@ -212,6 +233,19 @@ def _key_tuple(key):
     return (key["lineage"], key["capture_epoch"], key["current_size"], tuple(tuple(key["sums"][n]) for n in BUFFER_ARRAYS))
 
 
+def cites(delta_manifest, base_manifest, where="base"):
+    """Does the delta cite this full state as its base?  The first thing that disagrees -- 'lineage', 'capture_epoch',
+    'current_size', or the name of the buffer array whose sums differ -- or None.  StateError when the state cannot be a base."""
+    key, cited = base_key(base_manifest, where=where), delta_manifest["base"]
+    for field in ("lineage", "capture_epoch", "current_size"):
+        if key[field] != type(key[field])(cited[field]):
+            return field
+    for name in BUFFER_ARRAYS:
+        if key["sums"][name] != [int(x) for x in cited["sums"][name]]:
+            return name
+    return None
+
+
 def _check_array(where, name, arrays, listed, want, implied_by, sums, entry=True):
     """One array of a state: present, listed in the manifest, of the dtype and shape `implied_by` implies (`want`) and
     (entry=True) its manifest entry records, and (sums=True) summing to the (A, B) recorded there."""
@@ -232,13 +266,17 @@ def _check_array(where, name, arrays, listed, want, implied_by, sums, entry=True
                              f"({said[0]:016x}, {said[1]:016x})")
 
 
-def check_arrays(arrays, manifest, sums=True, where="state"):
-    """Every device array present, shaped as the manifest's dims imply and as the manifest records, and (sums=True) its bytes
-    summing to the manifest's (A, B).  Raises StateError naming the array."""
-    want = expected_shapes(manifest["dims"])
-    listed = manifest["arrays"]
-    for name in DEVICE_ARRAYS:
-        _check_array(where, name, arrays, listed, want[name], "the manifest's dims", sums)
+def _check_listed(arrays, manifest, sums, where, shapes, implied_by="the manifest's dims"):
+    """The device arrays of `shapes` (name -> (dtype, shape), implied by `implied_by`), each as _check_array checks one."""
+    for name, want in shapes.items():
+        _check_array(where, name, arrays, manifest["arrays"], want, implied_by, sums)
+
+
+def _check_state(arrays, manifest, sums, where, *groups):
+    """What a full state and a delta are checked for alike: the device arrays of every (shapes, implied_by) group, buffer_counters
+    against the manifest's current_size, the host arrays, the per-environment streams."""
+    for group in groups:
+        _check_listed(arrays, manifest, sums, where, *group)
     if int(arrays["buffer_counters"][0]) != int(manifest["dims"]["current_size"]):
         raise StateError(f"{where}: array 'buffer_counters' says current_size {int(arrays['buffer_counters'][0])}, "
                          f"the manifest {manifest['dims']['current_size']}")
@@ -248,13 +286,19 @@ def check_arrays(arrays, manifest, sums=True, where="state"):
     check_stream_arrays(arrays, manifest, where=where)
 
 
+def check_arrays(arrays, manifest, sums=True, where="state"):
+    """Every device array present, shaped as the manifest's dims imply and as the manifest records, and (sums=True) its bytes
+    summing to the manifest's (A, B).  Raises StateError naming the array."""
+    _check_state(arrays, manifest, sums, where, (expected_shapes(manifest["dims"]),))
+
+
 def check_stream_arrays(arrays, manifest, where="state"):
     """The per-environment streams of a state, family by family (exploration streams: field 'explore_streams'; the environments'
     reset streams: 'reset_streams'): all four arrays or none, as the manifest's field says, shaped for its stream count, positions
     inside [0, 624], and summing to what it records (they are a few KB per stream and reach the device by a plain copy, so their
     sums are always checked here, on the host)."""
-    for family in STREAM_FAMILIES:
-        field, names = f"{family}_streams", tuple(stream_shapes(0, family))
+    for family, fam in STREAM_FAMILIES.items():
+        field, names = fam["field"], fam["arrays"]
         rec = manifest.get(field)
         if rec is None:
             extra = [n for n in names if n in arrays]
@@ -284,17 +328,10 @@ def check_delta_arrays(arrays, manifest, sums=True, where="delta"):
     """A delta by itself: every small device array as the dims imply, the slot list and the four row arrays shaped for
     manifest['n_dirty'] and (sums=True) summing to what the manifest records, the slot list strictly ascending inside
     [0, current_size) and holding every slot of the grown region [base current_size, current_size)."""
-    dims, listed = manifest["dims"], manifest["arrays"]
-    want = expected_shapes(dims)
-    for name in DEVICE_ARRAYS:
-        if name not in BUFFER_ARRAYS:
-            _check_array(where, name, arrays, listed, want[name], "the manifest's dims", sums)
-    n = int(manifest["n_dirty"])
-    for name, w in delta_shapes(dims, n).items():
-        _check_array(where, name, arrays, listed, w, f"the manifest's dims and n_dirty {n}", sums)
+    dims, n = manifest["dims"], int(manifest["n_dirty"])
+    small = {name: want for name, want in expected_shapes(dims).items() if name not in BUFFER_ARRAYS}
+    _check_state(arrays, manifest, sums, where, (small,), (delta_shapes(dims, n), f"the manifest's dims and n_dirty {n}"))
     cs, cs0 = int(dims["current_size"]), int(manifest["base"]["current_size"])
-    if int(arrays["buffer_counters"][0]) != cs:
-        raise StateError(f"{where}: array 'buffer_counters' says current_size {int(arrays['buffer_counters'][0])}, the manifest {cs}")
     if not 0 <= cs0 <= cs:
         raise StateError(f"{where}: manifest 'base' has current_size {cs0}, the delta {cs}: a buffer does not shrink")
     slots = arrays["buffer_delta_slots"]
@@ -305,10 +342,6 @@ def check_delta_arrays(arrays, manifest, sums=True, where="delta"):
     grown = np.arange(cs0, cs, dtype=np.int64)
     if grown.size and not np.array_equal(slots[slots >= cs0], grown):
         raise StateError(f"{where}: array 'buffer_delta_slots' does not list every slot of the grown region [{cs0}, {cs})")
-    for name in ("np_random_key", "success_rates", "extra"):
-        if name not in arrays:
-            raise StateError(f"{where}: array '{name}' is missing")
-    check_stream_arrays(arrays, manifest, where=where)
 
 
 def compose(base_path, delta_path_, sums=True):
@@ -322,19 +355,17 @@ def compose(base_path, delta_path_, sums=True):
         raise StateError(f"{where}: manifest 'kind' is not 'delta'")
     b_arrays, b_manifest = read_state(base_where)
     key, cited = base_key(b_manifest, where=base_where), manifest["base"]
-    for field in ("lineage", "capture_epoch", "current_size"):
-        if key[field] != type(key[field])(cited[field]):
-            raise StateError(f"{base_where}: '{field}' of the base is {key[field]!r}, the delta {where} cites {cited[field]!r}")
-    for name in BUFFER_ARRAYS:
-        if key["sums"][name] != [int(x) for x in cited["sums"][name]]:
-            raise StateError(f"{base_where}: array '{name}' of the base sums to {tuple(key['sums'][name])}, the delta {where} cites "
-                             f"{tuple(cited['sums'][name])}: not the state this delta was taken against")
+    off = cites(manifest, b_manifest, where=base_where)
+    if off in BUFFER_ARRAYS:
+        raise StateError(f"{base_where}: array '{off}' of the base sums to {tuple(key['sums'][off])}, the delta {where} cites "
+                         f"{tuple(cited['sums'][off])}: not the state this delta was taken against")
+    if off is not None:
+        raise StateError(f"{base_where}: '{off}' of the base is {key[off]!r}, the delta {where} cites {cited[off]!r}")
     for f in ("obs", "goal", "action", "hidden", "T", "capacity"):
         if int(b_manifest["dims"][f]) != int(manifest["dims"][f]):
             raise StateError(f"{base_where}: {f} of the base is {b_manifest['dims'][f]}, of the delta {manifest['dims'][f]}")
-    want0 = expected_shapes(b_manifest["dims"])
-    for name in BUFFER_ARRAYS:       # the base's rows are what its manifest (and so the delta) says
-        _check_array(base_where, name, b_arrays, b_manifest["arrays"], want0[name], "the manifest's dims", sums)
+    want0 = expected_shapes(b_manifest["dims"])      # the base's rows are what its manifest (and so the delta) says
+    _check_listed(b_arrays, b_manifest, sums, base_where, {name: want0[name] for name in BUFFER_ARRAYS})
     check_delta_arrays(arrays, manifest, sums=sums, where=where)
     dims, cs0 = manifest["dims"], key["current_size"]
     want, slots = expected_shapes(dims), arrays["buffer_delta_slots"]
@@ -391,22 +422,15 @@ def _dims_of(agent, current_size):
             "T": int(agent.buffer._dev.T), "capacity": int(agent.buffer._dev.size), "current_size": int(current_size)}
 
 
-def _layout(agent, current_size=-1):
+def _layout(agent, n=-1, delta=False):
+    """([(name, dtype, count, offset) of every section], blob bytes) as the library lays out a full state of n episodes (-1: the
+    buffer's current_size) or (delta=True) a delta with room for n dirty episodes."""
     from . import _lib
-    secs = (_lib.StateSection * _lib.STATE_SECTIONS)()
-    n, total = C.c_int32(_lib.STATE_SECTIONS), C.c_size_t()
-    _lib.check(agent.lib.hp_state_layout(agent.h, agent.buffer._dev.h, agent.o_norm.h, agent.g_norm.h, int(current_size), secs,
-                                         C.byref(n), C.byref(total)))
-    return [(s.name.decode(), _DTYPES[s.dtype], int(s.count), int(s.offset)) for s in secs[:n.value]], int(total.value)
-
-
-def _layout_delta(agent, max_dirty):
-    from . import _lib
-    secs = (_lib.StateSection * _lib.STATE_DELTA_SECTIONS)()
-    n, total = C.c_int32(_lib.STATE_DELTA_SECTIONS), C.c_size_t()
-    _lib.check(agent.lib.hp_state_layout_delta(agent.h, agent.buffer._dev.h, agent.o_norm.h, agent.g_norm.h, int(max_dirty), secs,
-                                               C.byref(n), C.byref(total)))
-    return [(s.name.decode(), _DTYPES[s.dtype], int(s.count), int(s.offset)) for s in secs[:n.value]], int(total.value)
+    room = _lib.STATE_DELTA_SECTIONS if delta else _lib.STATE_SECTIONS
+    entry = agent.lib.hp_state_layout_delta if delta else agent.lib.hp_state_layout
+    secs, count, total = (_lib.StateSection * room)(), C.c_int32(room), C.c_size_t()
+    _lib.check(entry(agent.h, agent.buffer._dev.h, agent.o_norm.h, agent.g_norm.h, int(n), secs, C.byref(count), C.byref(total)))
+    return [(s.name.decode(), _DTYPES[s.dtype], int(s.count), int(s.offset)) for s in secs[:count.value]], int(total.value)
 
 
 def _buffer_counts(agent):
@@ -459,11 +483,6 @@ def known_base(agent, base_path):
     return key, rec[0], rec[1]
 
 
-def _reset_streams(agent):
-    """The reset streams of the agent's vectorised environment, or None (no such environment, or it is reset on the host)."""
-    return getattr(getattr(agent, "vec_env", None), "reset_streams", None)
-
-
 class PendingSave:
     """A capture in flight (`save_training_state(wait=False)`): the device part was snapshotted in stream order when this object
     was made, the host part (numpy's stream, success_rates, savetime) copied at the same moment; training may go on.
@@ -486,7 +505,7 @@ class PendingSave:
         else:
             self.max_dirty = min(self.episodes - episodes0, cs)
             _lib.check(agent.lib.hp_state_capture_delta(*agent._handles(), since, self.max_dirty, C.byref(ticket), C.byref(nbytes)))
-            self.sections, total = _layout_delta(agent, self.max_dirty)
+            self.sections, total = _layout(agent, self.max_dirty, delta=True)
         self.ticket, self.nbytes = ticket.value, nbytes.value
         assert total == self.nbytes, (total, self.nbytes)
         self.capture_epoch = _epochs(agent)[0]
@@ -498,15 +517,12 @@ class PendingSave:
         self.host_arrays = {"np_random_key": np.array(st[1], dtype=np.uint32),
                             "success_rates": np.array(agent.success_rates, dtype=np.float64),
                             "extra": np.frombuffer(bytes(extra or b""), dtype=np.uint8).copy()}
-        streams = getattr(agent, "explore_streams", None)
-        if streams is not None:
-            # copied now (a few KB per stream; synchronises), so rollouts that follow a wait=False capture do not move them
-            stream_arrays, self.host["explore_streams"] = stream_record(*streams.get_arrays())
-            self.host_arrays.update(stream_arrays)
-        reset_streams = _reset_streams(agent)
-        if reset_streams is not None:      # the environments' reset generators (device_env: enable_device_reset), likewise
-            stream_arrays, self.host["reset_streams"] = stream_record(*reset_streams.get_arrays(), family="reset")
-            self.host_arrays.update(stream_arrays)
+        for family, fam in STREAM_FAMILIES.items():
+            streams = fam["find"](agent)
+            if streams is not None:
+                # copied now (a few KB per stream; synchronises), so rollouts that follow a wait=False capture do not move them
+                stream_arrays, self.host[fam["field"]] = stream_record(*streams.get_arrays(), family=family)
+                self.host_arrays.update(stream_arrays)
 
     def done(self):
         return self._done is not None
@@ -589,26 +605,18 @@ def load(agent, path, verify_host=False, base=None):
     for key in ("obs", "goal", "action", "hidden", "T", "capacity"):
         if int(manifest["dims"][key]) != mine[key]:
             raise StateError(f"{where}: {key} of the state is {manifest['dims'][key]}, the receiver has {mine[key]}")
-    streams, rec = getattr(agent, "explore_streams", None), manifest.get("explore_streams")
-    names = ", ".join(f"'{n}'" for n in STREAM_ARRAYS)
-    if streams is not None and rec is None:
-        raise StateError(f"{where}: the agent explores with one stream per environment, but the state was saved without: arrays "
-                         f"{names} are missing")
-    if streams is None and rec is not None:
-        raise StateError(f"{where}: the state carries {rec['n']} per-environment exploration streams (arrays {names}), but the "
-                         "agent has none: call enable_explore_streams() (args.explore_streams) before loading")
-    if streams is not None and int(rec["n"]) != len(streams):
-        raise StateError(f"{where}: array 'explore_stream_keys' holds {rec['n']} streams, the agent has {len(streams)} environments")
-    resets, rrec = _reset_streams(agent), manifest.get("reset_streams")
-    rnames = ", ".join(f"'{n}'" for n in RESET_STREAM_ARRAYS)
-    if resets is not None and rrec is None:
-        raise StateError(f"{where}: the agent's environment is reset on the device, but the state was saved without reset streams: "
-                         f"arrays {rnames} are missing")
-    if resets is None and rrec is not None:
-        raise StateError(f"{where}: the state carries {rrec['n']} per-environment reset streams (arrays {rnames}), but the agent's "
-                         "environment is reset on the host: call vec_env.enable_device_reset() (args.device_reset) before loading")
-    if resets is not None and int(rrec["n"]) != len(resets):
-        raise StateError(f"{where}: array 'reset_stream_keys' holds {rrec['n']} streams, the agent has {len(resets)} environments")
+    live = {}                           # family -> the agent's streams that the state will be put into
+    for family, fam in STREAM_FAMILIES.items():
+        streams, rec = fam["find"](agent), manifest.get(fam["field"])
+        names = ", ".join(f"'{n}'" for n in fam["arrays"])
+        if streams is not None and rec is None:
+            raise StateError(f"{where}: " + fam["saved_without"].format(names=names))
+        if streams is None and rec is not None:
+            raise StateError(f"{where}: " + fam["agent_without"].format(n=rec["n"], names=names))
+        if streams is not None and int(rec["n"]) != len(streams):
+            raise StateError(f"{where}: array '{family}_stream_keys' holds {rec['n']} streams, the agent has {len(streams)} environments")
+        if streams is not None:
+            live[family] = streams
     check_arrays(arrays, manifest, sums=verify_host, where=where)
     agent._flush_updates()
     sections, total = _layout(agent, mine["current_size"])
@@ -639,10 +647,8 @@ def load(agent, path, verify_host=False, base=None):
     np.random.set_state(("MT19937", arrays["np_random_key"], int(r["pos"]), int(r["has_gauss"]), float(r["cached_gaussian"])))
     agent.rng.seeded = True
     agent.rng._gauss = (int(manifest["rng_gauss"][0]), float(manifest["rng_gauss"][1]))
-    if streams is not None:
-        streams.set_arrays(*(arrays[n] for n in STREAM_ARRAYS))
-    if resets is not None:
-        resets.set_arrays(*(arrays[n] for n in RESET_STREAM_ARRAYS))
+    for family, streams in live.items():
+        streams.set_arrays(*(arrays[n] for n in STREAM_FAMILIES[family]["arrays"]))
     agent.success_rates = [float(x) for x in arrays["success_rates"]]
     agent.savetime = int(manifest["savetime"])
     return arrays["extra"].tobytes(), manifest

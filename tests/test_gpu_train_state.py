@@ -311,6 +311,46 @@ def test_refusals_leave_the_receiver_untouched(tmp_path):
     assert_same(fingerprint(recv), fingerprint(src), "good file")
 
 
+def test_the_librarys_section_table_is_pythons_for_both_kinds():
+    """hp_state_layout / hp_state_layout_delta against expected_shapes / delta_shapes, at a shape where obs, goal, action, T, T + 1
+    and the hidden width all differ: names in order, dtype and count of every section, and the offsets -- multiples of 256, each
+    the one before plus that section's bytes padded to 256 (so they increase wherever a section holds anything: with room for no
+    episode the row sections are empty and share an offset), the total closing the last.  No training."""
+    ep = {"obs": 13, "goal": 3, "action": 4, "action_max": 0.7, "max_timesteps": 50, "hidden": 128}
+    agent = build(batch=64, ep=ep, cap_eps=16, n_batches=3)
+
+    def padded(dt, count):
+        return (count * np.dtype(dt).itemsize + 255) // 256 * 256
+
+    def check(secs, total, want, what):
+        assert [s[0] for s in secs] == list(want), what
+        for name, dt, count, _ in secs:
+            assert (dt, count) == (want[name][0], int(np.prod(want[name][1]))), (what, name)
+        offs = [s[3] for s in secs]
+        assert offs[0] == 0 and all(o % 256 == 0 for o in offs), what
+        for (name, dt, count, off), nxt in zip(secs, offs[1:] + [total]):
+            assert nxt == off + padded(dt, count) and (nxt > off or count == 0), (what, name)
+
+    fulls = []
+    for cs in (0, 1, 16):
+        secs, total = ts._layout(agent, cs)
+        assert len(secs) == _lib.STATE_SECTIONS
+        check(secs, total, ts.expected_shapes(ts._dims_of(agent, cs)), f"full, current_size {cs}")
+        fulls.append(secs)
+    for max_dirty in (0, 1, 16):
+        dims = ts._dims_of(agent, 16)
+        full = ts.expected_shapes(dims)
+        want = {k: v for k, v in full.items() if k not in ts.BUFFER_ARRAYS + ("buffer_counters",)}
+        want["buffer_delta_header"] = ("<i8", (4,))
+        want.update(ts.delta_shapes(dims, max_dirty))
+        want["buffer_counters"] = full["buffer_counters"]
+        secs, total = ts._layout(agent, max_dirty, delta=True)
+        assert len(secs) == _lib.STATE_DELTA_SECTIONS
+        check(secs, total, want, f"delta, max_dirty {max_dirty}")
+        for f in fulls:                                # the small sections: a full state's, entry for entry
+            assert secs[:27] == f[:27] and secs[26][0] == "rng_pos"
+
+
 @pytest.mark.parametrize("nbytes", [0, 1, 8, 4096 + 3, (64 << 20) + 5])
 def test_checksum_kernel_equals_the_numpy_twin(nbytes):
     c = ctx()

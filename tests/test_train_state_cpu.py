@@ -159,3 +159,27 @@ def test_dims_of_takes_the_hidden_width_from_the_agent():
         dims = ts._dims_of(NS(env_params=dict(ep, hidden=hidden), buffer=buf), 3)
         assert dims == dict(DIMS, hidden=hidden)
         assert ts.expected_shapes(dims)["actor"][1] == (hidden * 7 + hidden + 2 * (hidden * hidden + hidden) + 3 * hidden + 3,)
+
+
+@pytest.mark.parametrize("family, other", [("explore", "reset"), ("reset", "explore")])
+def test_verify_treats_the_two_stream_families_alike(tmp_path, family, other):
+    """The families of per-environment streams are rows of one table (ts.STREAM_FAMILIES): a state with two streams of ONE family
+    verifies; without one of that family's four arrays it fails naming the array; with an array of the OTHER family, whose manifest
+    field it does not have, it fails naming that array."""
+    from test_explore_streams_cpu import stream_arrays
+    assert list(ts.STREAM_FAMILIES) == ["explore", "reset"]
+    arrays, manifest = synthetic_state()
+    extra, manifest[f"{family}_streams"] = ts.stream_record(*stream_arrays(2), family=family)
+    arrays.update(extra)
+    names = tuple(ts.stream_shapes(0, family))
+    assert tuple(extra) == names == ts.STREAM_FAMILIES[family]["arrays"] and len(names) == 4
+    assert ts.STREAM_FAMILIES[family]["field"] == f"{family}_streams" and f"{other}_streams" not in manifest
+    assert ts.verify(ts.write_state(tmp_path / "ok.npz", arrays, manifest))[f"{family}_streams"]["n"] == 2
+    for name in names:
+        gone = {k: v for k, v in arrays.items() if k != name}
+        with pytest.raises(ts.StateError, match=f"array '{name}' is missing"):
+            ts.verify(ts.write_state(tmp_path / "gone.npz", gone, manifest))
+    stray, _ = ts.stream_record(*stream_arrays(2), family=other)
+    for name, a in stray.items():
+        with pytest.raises(ts.StateError, match=f"array '{name}' is present but the manifest has no '{other}_streams' field"):
+            ts.verify(ts.write_state(tmp_path / "stray.npz", dict(arrays, **{name: a}), manifest))
