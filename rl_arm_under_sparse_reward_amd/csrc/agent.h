@@ -2,7 +2,9 @@
 // part of the C ABI):
 //   agent.hip           lifecycle, parameter / optimizer-state access, update sequences, the cycle hipGraph, C ABI
 //   agent_engines.hip   the row-slab engines (slab8.h, slab32.h), weight-gradient launches (gemm_lds.h, dw64.h), optimizer
-//                       and exchange kernels, forward-only entry points
+//                       and exchange kernels
+//   agent_forward.hip   the rollout-side forward: policy calls and the stand-alone critic, host code (policy_call.h: what a policy
+//                       call is made of, shared with rollout.hip and the episode audits; forward_kernels.h: its pack kernels)
 //   agent_layers.hip    layer-per-launch fallback engine for network shapes the slab engines do not cover
 // Reference: models.py:11-44, ddpg_agent.py:214-277, torch.optim.Adam (ddpg_agent.py:42-43).
 //
@@ -238,7 +240,7 @@ struct hp_agent {
     bool gather_ahead = true;   // merged kernel: spare workgroups gather update u+1's inputs during update u (while CUs are free)
     DevBuf plan, norm_plan;
     int plan_batches = 0;
-    DevBuf fwd_ws;          // actor_forward scratch
+    DevBuf fwd_ws;          // scratch of the policy calls on the context's stream (agent_forward.hip)
     // policy snapshots for a feeder that steps environments while cycles run (hp_agent_policy_snapshot / _act_snapshot)
     struct PolicySnap {
         float *params = nullptr, *fragF = nullptr;   // actor segment of the arenas

@@ -1,7 +1,9 @@
 // agent_engines.hip -- the update's device code and its launch logic on gfx950: row-slab chain kernels (slab8.h: 4/8/16-row
 // slabs on v_mfma_f32_4x4x1, slab32.h: 32-row slabs on v_mfma_f32_32x32x2), weight-gradient launches (gemm_lds.h 32 x 32
 // tiles, dw64.h split 64 x 64 tiles) with the optimizer in their epilogue and the sampler's look-ahead riding along,
-// the peer-exchange optimizer kernels, polyak, and the forward-only entry points (policy / critic rows).
+// the peer-exchange optimizer kernels and polyak.  (The rollout-side forward -- policy / critic rows -- is agent_forward.hip; of it
+// this unit compiles the kernels: the policy slab's, beside the chain kernels whose device functions it is made of, with its
+// launcher, and the four pack kernels of forward_kernels.h.)
 // Reference: models.py:11-44, ddpg_agent.py:214-277, torch.optim.Adam (ddpg_agent.py:42-43).
 //
 // ---- why it is shaped like this (measured) -------------------------------------
@@ -313,49 +315,23 @@ __global__ void k_polyak_frag(float *__restrict__ tgt, const float *__restrict__
     if (of >= 0) fragFT[of] = t;
 }
 
-// actor forward for rollouts: x [rows, xdim] -> padded input rows
-__global__ void k_pack_rows(const float *__restrict__ src, int rows, int width, float *dst, int ld, int col0) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= rows * width) return;
-    const int r = idx / width, c = idx - r * width;
-    dst[(long long)r * ld + col0 + c] = src[idx];
-}
-
-// rollout inputs (ddpg_agent._preproc_inputs :163-171): normalised, clipped observation | goal rows in float32 (tr_net_input)
-__global__ void k_policy_inputs(const double *__restrict__ obs, const double *__restrict__ g, int rows, int od, int gd,
-                                const NormDev *__restrict__ onz, const NormDev *__restrict__ gnz, double clip_obs,
-                                double clip_o, double clip_g, float *X, int ld) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int w = od + gd;
-    if (idx >= (long long)rows * w) return;
-    const int r = (int)(idx / w), c = (int)(idx - (long long)r * w);
-    const int j = c - od;
-    X[(long long)r * ld + c] = c < od ? tr_net_input(obs[(long long)r * od + c], clip_obs, onz->mean[c], onz->std[c], clip_o)
-                                      : tr_net_input(g[(long long)r * gd + j], clip_obs, gnz->mean[j], gnz->std[j], clip_g);
-}
-
-// critic input: action block = actions / max_action (models.py:38)
-__global__ void k_pack_scaled_actions(const float *__restrict__ src, int rows, int act_dim, float *dst, int ld, int act_off,
-                                      float max_action) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= rows * act_dim) return;
-    const int r = idx / act_dim, c = idx - r * act_dim;
-    dst[(long long)r * ld + act_off + c] = src[idx] / max_action;
-}
-
-__global__ void k_unpack_actions(const float *__restrict__ X, int rows, int ld, int act_off, int act_dim,
-                                 float max_action, float *out) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= rows * act_dim) return;
-    const int r = idx / act_dim, c = idx - r * act_dim;
-    out[idx] = X[(long long)r * ld + act_off + c] * max_action;   // stored value is actions / max_action
-}
+// the layer-per-launch forward chain's pack kernels (launched by agent_forward.hip), compiled where they always were
+#define FORWARD_KERNELS_HERE
+#include "forward_kernels.h"
 
 // ------------------------------------------------------------------------------- host side
 int launch_group(hp_agent *a, const Launch &L, int which) {
     ProfScope ps(a, which);
     HP_KLOG(L.g.uni ? "k_gemm_lds_u" : "k_gemm_lds");
     hipLaunchKernelGGL(L.g.uni ? k_gemm_lds_u : k_gemm_lds, dim3(L.tiles), dim3(GL_THREADS), 0, a->ctx->stream, L.g);
+    HP_CHECK_HIP(hipGetLastError());
+    return HP_OK;
+}
+
+// k_policy_slab8 and its grid rule, a workgroup per 4 rows: the one launch site of the policy calls (agent_forward.hip)
+int launch_policy_slab(hipStream_t stream, const PolicyArgs &P) {
+    static_assert(sizeof(s8r4::PolicyLds) <= 160 * 1024, "the policy slab's LDS fits a CU");
+    hipLaunchKernelGGL(s8r4::k_policy_slab8, dim3((unsigned)((P.rows + 3) / 4)), dim3(S8_THREADS), 0, stream, P);
     HP_CHECK_HIP(hipGetLastError());
     return HP_OK;
 }
@@ -995,305 +971,6 @@ int enqueue_peer_adam(hp_agent *a, const GatherCtx *gc, unsigned *reset_sync) {
     ProfScope ps(a, PROF_ADAM);
     return peer_enqueue_adam(a->peer, F, a->n_arena, gc->u, a->grad_mean);
 }
-
-// actor rows on the device.  Scratch layout: [head_bytes of caller data] | X rows | h1 | h2 | h3 | tanh | actions; `fill`
-// enqueues whatever turns the caller data into X (zeroed beforehand).
-template <typename Fill>
-static int actor_rows(hp_agent *a, int32_t net, int64_t rows, size_t head_bytes, float *actions_host, Fill fill,
-                      float *actions_dev = nullptr) {
-    const int H = a->H, ldx = a->ldx, ad = a->cfg.act_dim;
-    const int Mp = roundup((int)rows, 32);
-    hipStream_t s = a->ctx->stream;
-    const size_t nX = (size_t)Mp * ldx, nH = (size_t)Mp * H, nT = (size_t)Mp * 16;
-    head_bytes = (head_bytes + 15) & ~(size_t)15;
-    HP_TRY(a->fwd_ws.ensure(head_bytes + (nX + 3 * nH + nT + (size_t)rows * ad) * 4));
-    char *head = a->fwd_ws.as<char>();
-    float *X = reinterpret_cast<float *>(head + head_bytes), *h1 = X + nX, *h2 = h1 + nH, *h3 = h2 + nH, *tp = h3 + nH,
-          *outp = tp + nT;
-    HP_CHECK_HIP(hipMemsetAsync(X, 0, nX * 4, s));
-    HP_TRY(fill(head, X, s));
-    const NetLayout &l = a->la;
-    const float *P = (net == HP_NET_ACTOR) ? a->params : a->targets;
-    { Launch L; add_fwd(L, X, ldx, l.K1, P + l.w1, P + l.b1, h1, H, Mp, H, EPI_BIAS_RELU); HP_TRY(launch_group(a, L, PROF_GEMM_FWD)); }
-    { Launch L; add_fwd(L, h1, H, H, P + l.w2, P + l.b2, h2, H, Mp, H, EPI_BIAS_RELU); HP_TRY(launch_group(a, L, PROF_GEMM_FWD)); }
-    { Launch L; add_fwd(L, h2, H, H, P + l.w3, P + l.b3, h3, H, Mp, H, EPI_BIAS_RELU); HP_TRY(launch_group(a, L, PROF_GEMM_FWD)); }
-    {
-        Launch L;
-        add_fwd(L, h3, H, H, P + l.w4, P + l.b4, X + a->act_off, ldx, Mp, 16, EPI_BIAS_TANH);
-        L.g.p[0].n_store = ad; L.g.p[0].C2 = tp; L.g.p[0].ldc2 = 16; L.g.p[0].max_action = (float)a->cfg.max_action;
-        HP_TRY(launch_group(a, L, PROF_GEMM_FWD));
-    }
-    // actions = max_action * tanh(.)  (models.py:24); tp holds tanh
-    hipLaunchKernelGGL(k_unpack_actions, dim3((unsigned)((rows * ad + 255) / 256)), dim3(256), 0, s, tp, (int)rows, 16, 0, ad,
-                       (float)a->cfg.max_action, outp);
-    HP_CHECK_HIP(hipGetLastError());
-    if (actions_dev) {   // device caller (agent_act_dev): the actions stay on the device, in stream order, no host wait
-        HP_CHECK_HIP(hipMemcpyAsync(actions_dev, outp, (size_t)rows * ad * 4, hipMemcpyDeviceToDevice, s));
-        return HP_OK;
-    }
-    HP_CHECK_HIP(hipMemcpyAsync(actions_host, outp, (size_t)rows * ad * 4, hipMemcpyDeviceToHost, s));
-    HP_CHECK_HIP(hipStreamSynchronize(s));
-    return HP_OK;
-}
-
-// stand-alone critic rows (models.py:28-44): Q(x, a) for host inputs, on the layer-per-launch GEMMs
-static int critic_rows(hp_agent *a, int32_t net, int64_t rows, const float *x_host, const float *act_host, float *q_host) {
-    const int H = a->H, ldx = a->ldx, xd = a->xdim, ad = a->cfg.act_dim;
-    const int Mp = roundup((int)rows, 32);
-    hipStream_t s = a->ctx->stream;
-    const size_t n_x = (size_t)rows * xd, n_a = (size_t)rows * ad, nX = (size_t)Mp * ldx, nH = (size_t)Mp * H,
-                 nT = (size_t)Mp * 16;
-    const size_t head = ((n_x + n_a) * 4 + 15) & ~(size_t)15;
-    HP_TRY(a->fwd_ws.ensure(head + (nX + 3 * nH + nT + (size_t)rows) * 4));
-    char *base = a->fwd_ws.as<char>();
-    float *raw_x = reinterpret_cast<float *>(base), *raw_a = raw_x + n_x;
-    float *X = reinterpret_cast<float *>(base + head), *h1 = X + nX, *h2 = h1 + nH, *h3 = h2 + nH, *q16 = h3 + nH,
-          *outp = q16 + nT;
-    HP_CHECK_HIP(hipMemsetAsync(X, 0, nX * 4, s));
-    HP_CHECK_HIP(hipMemcpyAsync(raw_x, x_host, n_x * 4, hipMemcpyHostToDevice, s));
-    HP_CHECK_HIP(hipMemcpyAsync(raw_a, act_host, n_a * 4, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_pack_rows, dim3((unsigned)((n_x + 255) / 256)), dim3(256), 0, s, raw_x, (int)rows, xd, X, ldx, 0);
-    hipLaunchKernelGGL(k_pack_scaled_actions, dim3((unsigned)((n_a + 255) / 256)), dim3(256), 0, s, raw_a, (int)rows, ad, X,
-                       ldx, a->act_off, (float)a->cfg.max_action);
-    HP_CHECK_HIP(hipGetLastError());
-    const NetLayout &l = a->lc;
-    const float *P = ((net == HP_NET_CRITIC) ? a->params : a->targets) + a->la.total;
-    { Launch L; add_fwd(L, X, ldx, l.K1, P + l.w1, P + l.b1, h1, H, Mp, H, EPI_BIAS_RELU); HP_TRY(launch_group(a, L, PROF_GEMM_FWD)); }
-    { Launch L; add_fwd(L, h1, H, H, P + l.w2, P + l.b2, h2, H, Mp, H, EPI_BIAS_RELU); HP_TRY(launch_group(a, L, PROF_GEMM_FWD)); }
-    { Launch L; add_fwd(L, h2, H, H, P + l.w3, P + l.b3, h3, H, Mp, H, EPI_BIAS_RELU); HP_TRY(launch_group(a, L, PROF_GEMM_FWD)); }
-    {
-        Launch L;
-        add_fwd(L, h3, H, H, P + l.w4, P + l.b4, q16, 16, Mp, 16, EPI_BIAS);
-        L.g.p[0].n_store = 1;
-        HP_TRY(launch_group(a, L, PROF_GEMM_FWD));
-    }
-    hipLaunchKernelGGL(k_unpack_actions, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, q16, (int)rows, 16, 0, 1, 1.0f, outp);
-    HP_CHECK_HIP(hipGetLastError());
-    HP_CHECK_HIP(hipMemcpyAsync(q_host, outp, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
-    HP_CHECK_HIP(hipStreamSynchronize(s));
-    return HP_OK;
-}
-
-// slab engines: the whole policy call is one launch (k_policy_slab8).  `head` = float32 inputs (x != null) or the float64
-// observation rows followed by the goal rows.
-static int policy_rows_slab(hp_agent *a, hp_norm *on, hp_norm *gn, int32_t net, int64_t rows, const void *host_a,
-                            size_t bytes_a, const void *host_b, size_t bytes_b, bool f32_inputs, double clip_obs,
-                            float *actions_host) {
-    hipStream_t s = a->ctx->stream;
-    const int ad = a->cfg.act_dim;
-    const size_t head = (bytes_a + bytes_b + 15) & ~(size_t)15;
-    HP_TRY(a->fwd_ws.ensure(head + (size_t)rows * ad * 4));
-    char *d = a->fwd_ws.as<char>();
-    float *d_act = reinterpret_cast<float *>(d + head);
-    HP_CHECK_HIP(hipMemcpyAsync(d, host_a, bytes_a, hipMemcpyHostToDevice, s));
-    if (bytes_b) HP_CHECK_HIP(hipMemcpyAsync(d + bytes_a, host_b, bytes_b, hipMemcpyHostToDevice, s));
-    PolicyArgs P;
-    memset(&P, 0, sizeof(P));
-    if (f32_inputs) {
-        P.x = reinterpret_cast<const float *>(d);
-        P.od = a->xdim; P.gd = 0;
-    } else {
-        P.obs = reinterpret_cast<const double *>(d);
-        P.g = reinterpret_cast<const double *>(d + bytes_a);
-        P.od = on->size; P.gd = gn->size;
-        P.onz = on->d; P.gnz = gn->d;
-        P.clip_obs = clip_obs; P.clip_o = on->clip; P.clip_g = gn->clip;
-    }
-    P.rows = (int)rows;
-    P.net = (net == HP_NET_ACTOR) ? SlabNetPtrs{a->fragF, a->fragD, a->params} : SlabNetPtrs{a->fragFT, nullptr, a->targets};
-    P.la = a->la; P.H = a->H; P.act_dim = ad; P.max_action = (float)a->cfg.max_action;
-    P.actions = d_act;
-    hipLaunchKernelGGL(s8r4::k_policy_slab8, dim3((unsigned)((rows + 3) / 4)), dim3(S8_THREADS), 0, s, P);
-    HP_CHECK_HIP(hipGetLastError());
-    HP_CHECK_HIP(hipMemcpyAsync(actions_host, d_act, (size_t)rows * ad * 4, hipMemcpyDeviceToHost, s));
-    HP_CHECK_HIP(hipStreamSynchronize(s));
-    return HP_OK;
-}
-
-// hp_agent_act for rows that already lie in device memory (a vectorised simulator's tensors, rollout.hip): the same kernels on the
-// caller's pointers -- k_policy_slab8 reads obs / g and writes the actions in place, nothing is copied and nothing waits.
-int agent_act_dev(hp_agent *a, hp_norm *on, hp_norm *gn, int32_t net, const double *obs_dev, const double *g_dev, int64_t rows,
-                  double clip_obs, float *actions_dev) {
-    HP_REQUIRE(net == HP_NET_ACTOR || net == HP_NET_ACTOR_TARGET, HP_ERR_INVALID, "hp_agent_act_dev: net must be an actor");
-    HP_REQUIRE(rows > 0 && rows < (1 << 24), HP_ERR_INVALID, "hp_agent_act_dev: rows out of range");
-    const int od = on->size, gd = gn->size;
-    HP_REQUIRE(od + gd == a->xdim, HP_ERR_INVALID, "hp_agent_act_dev: normalizer sizes %d+%d do not match the actor input %d", od,
-               gd, a->xdim);
-    const double co = clip_obs > 0 ? clip_obs : INFINITY;
-    hipStream_t s = a->ctx->stream;
-    if (a->slab8) {
-        PolicyArgs P;
-        memset(&P, 0, sizeof(P));
-        P.obs = obs_dev; P.g = g_dev;
-        P.od = od; P.gd = gd;
-        P.onz = on->d; P.gnz = gn->d;
-        P.clip_obs = co; P.clip_o = on->clip; P.clip_g = gn->clip;
-        P.rows = (int)rows;
-        P.net = (net == HP_NET_ACTOR) ? SlabNetPtrs{a->fragF, a->fragD, a->params} : SlabNetPtrs{a->fragFT, nullptr, a->targets};
-        P.la = a->la; P.H = a->H; P.act_dim = a->cfg.act_dim; P.max_action = (float)a->cfg.max_action;
-        P.actions = actions_dev;
-        hipLaunchKernelGGL(s8r4::k_policy_slab8, dim3((unsigned)((rows + 3) / 4)), dim3(S8_THREADS), 0, s, P);
-        HP_CHECK_HIP(hipGetLastError());
-        return HP_OK;
-    }
-    return actor_rows(a, net, rows, 0, nullptr, [&](char *, float *X, hipStream_t st) -> int {
-        const long long n = (long long)rows * (od + gd);
-        hipLaunchKernelGGL(k_policy_inputs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, obs_dev, g_dev, (int)rows, od, gd,
-                           on->d, gn->d, co, on->clip, gn->clip, X, a->ldx);
-        HP_CHECK_HIP(hipGetLastError());
-        return (int)HP_OK;
-    }, actions_dev);
-}
-
-extern "C" {
-
-int hp_agent_act_dev(hp_agent *a, hp_norm *on, hp_norm *gn, int32_t net, const double *obs_dev, const double *g_dev,
-                     int64_t rows, double clip_obs, float *actions_dev) {
-    HP_REQUIRE(a && on && gn && obs_dev && g_dev && actions_dev, HP_ERR_INVALID, "hp_agent_act_dev: null argument");
-    HP_SERIALISE(a);
-    HP_REQUIRE(on->ctx == a->ctx && gn->ctx == a->ctx, HP_ERR_INVALID, "hp_agent_act_dev: handles belong to different contexts");
-    return agent_act_dev(a, on, gn, net, obs_dev, g_dev, rows, clip_obs, actions_dev);
-}
-
-int hp_agent_actor_forward(hp_agent *a, int32_t net, const float *x_host, int64_t rows, float *actions_host) {
-    HP_REQUIRE(a && x_host && actions_host, HP_ERR_INVALID, "hp_agent_actor_forward: null argument");
-    HP_SERIALISE(a);
-    HP_REQUIRE(net == HP_NET_ACTOR || net == HP_NET_ACTOR_TARGET, HP_ERR_INVALID, "hp_agent_actor_forward: net must be an actor");
-    HP_REQUIRE(rows > 0 && rows < (1 << 24), HP_ERR_INVALID, "hp_agent_actor_forward: rows out of range");
-    const int xd = a->xdim, ldx = a->ldx;
-    const size_t n_raw = (size_t)rows * xd;
-    if (a->slab8) return policy_rows_slab(a, nullptr, nullptr, net, rows, x_host, n_raw * 4, nullptr, 0, true, 0.0, actions_host);
-    return actor_rows(a, net, rows, n_raw * 4, actions_host, [&](char *head, float *X, hipStream_t s) -> int {
-        float *raw = reinterpret_cast<float *>(head);
-        HP_CHECK_HIP(hipMemcpyAsync(raw, x_host, n_raw * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_pack_rows, dim3((unsigned)((n_raw + 255) / 256)), dim3(256), 0, s, raw, (int)rows, xd, X, ldx, 0);
-        HP_CHECK_HIP(hipGetLastError());
-        return (int)HP_OK;
-    });
-}
-
-int hp_agent_critic_forward(hp_agent *a, int32_t net, const float *x_host, const float *actions_host, int64_t rows,
-                            float *q_host) {
-    HP_REQUIRE(a && x_host && actions_host && q_host, HP_ERR_INVALID, "hp_agent_critic_forward: null argument");
-    HP_SERIALISE(a);
-    HP_REQUIRE(net == HP_NET_CRITIC || net == HP_NET_CRITIC_TARGET, HP_ERR_INVALID, "hp_agent_critic_forward: net must be a critic");
-    HP_REQUIRE(rows > 0 && rows < (1 << 24), HP_ERR_INVALID, "hp_agent_critic_forward: rows out of range");
-    return critic_rows(a, net, rows, x_host, actions_host, q_host);
-}
-
-int hp_agent_act(hp_agent *a, hp_norm *on, hp_norm *gn, int32_t net, const double *obs_host, const double *g_host,
-                 int64_t rows, double clip_obs, float *actions_host) {
-    HP_REQUIRE(a && on && gn && obs_host && g_host && actions_host, HP_ERR_INVALID, "hp_agent_act: null argument");
-    HP_SERIALISE(a);
-    HP_REQUIRE(on->ctx == a->ctx && gn->ctx == a->ctx, HP_ERR_INVALID, "hp_agent_act: handles belong to different contexts");
-    HP_REQUIRE(net == HP_NET_ACTOR || net == HP_NET_ACTOR_TARGET, HP_ERR_INVALID, "hp_agent_act: net must be an actor");
-    HP_REQUIRE(rows > 0 && rows < (1 << 24), HP_ERR_INVALID, "hp_agent_act: rows out of range");
-    const int od = on->size, gd = gn->size;
-    HP_REQUIRE(od + gd == a->xdim, HP_ERR_INVALID, "hp_agent_act: normalizer sizes %d+%d do not match the actor input %d", od,
-               gd, a->xdim);
-    const size_t nb_o = (size_t)rows * od * 8, nb_g = (size_t)rows * gd * 8;
-    const double co = clip_obs > 0 ? clip_obs : INFINITY;
-    if (a->slab8) return policy_rows_slab(a, on, gn, net, rows, obs_host, nb_o, g_host, nb_g, false, co, actions_host);
-    return actor_rows(a, net, rows, nb_o + nb_g, actions_host, [&](char *head, float *X, hipStream_t s) -> int {
-        double *d_obs = reinterpret_cast<double *>(head), *d_g = reinterpret_cast<double *>(head + nb_o);
-        HP_CHECK_HIP(hipMemcpyAsync(d_obs, obs_host, nb_o, hipMemcpyHostToDevice, s));
-        HP_CHECK_HIP(hipMemcpyAsync(d_g, g_host, nb_g, hipMemcpyHostToDevice, s));
-        const long long n = (long long)rows * (od + gd);
-        hipLaunchKernelGGL(k_policy_inputs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_obs, d_g, (int)rows, od, gd,
-                           on->d, gn->d, co, on->clip, gn->clip, X, a->ldx);
-        HP_CHECK_HIP(hipGetLastError());
-        return (int)HP_OK;
-    });
-}
-
-}  // extern "C"
-
-extern "C" {
-
-int hp_agent_policy_snapshot(hp_agent *a, hp_norm *on, hp_norm *gn) {
-    HP_REQUIRE(a && on && gn, HP_ERR_INVALID, "hp_agent_policy_snapshot: null argument");
-    HP_SERIALISE(a);
-    HP_REQUIRE(a->slab8, HP_ERR_STATE, "hp_agent_policy_snapshot: needs the fused policy kernel (slab8 engine)");
-    HP_REQUIRE(on->size + gn->size == a->xdim, HP_ERR_INVALID, "hp_agent_policy_snapshot: normalizer sizes do not match the actor");
-    hipStream_t s = a->ctx->stream;
-    if (!a->act_stream) {
-        HP_CHECK_HIP(hipStreamCreateWithFlags(&a->act_stream, hipStreamNonBlocking));
-        HP_CHECK_HIP(hipEventCreateWithFlags(&a->act_done, hipEventDisableTiming));
-        for (auto &ps : a->snap) {
-            HP_CHECK_HIP(hipMalloc((void **)&ps.params, sizeof(float) * a->la.total));
-            HP_CHECK_HIP(hipMalloc((void **)&ps.fragF, sizeof(float) * a->la.total));
-            HP_CHECK_HIP(hipMalloc((void **)&ps.on, sizeof(NormDev)));
-            HP_CHECK_HIP(hipMalloc((void **)&ps.gn, sizeof(NormDev)));
-            HP_CHECK_HIP(hipEventCreateWithFlags(&ps.ready, hipEventDisableTiming));
-        }
-    }
-    const int target = (a->snap_cur == 0) ? 1 : 0;        // never the set policy calls are reading
-    hp_agent::PolicySnap &ps = a->snap[target];
-    if (a->act_recorded) HP_CHECK_HIP(hipStreamWaitEvent(s, a->act_done, 0));
-    const size_t nb = sizeof(float) * a->la.total;
-    HP_CHECK_HIP(hipMemcpyAsync(ps.params, a->params, nb, hipMemcpyDeviceToDevice, s));
-    HP_CHECK_HIP(hipMemcpyAsync(ps.fragF, a->fragF, nb, hipMemcpyDeviceToDevice, s));
-    HP_CHECK_HIP(hipMemcpyAsync(ps.on, on->d, sizeof(NormDev), hipMemcpyDeviceToDevice, s));
-    HP_CHECK_HIP(hipMemcpyAsync(ps.gn, gn->d, sizeof(NormDev), hipMemcpyDeviceToDevice, s));
-    ps.clip_o = on->clip; ps.clip_g = gn->clip; ps.od = on->size; ps.gd = gn->size;
-    HP_CHECK_HIP(hipEventRecord(ps.ready, s));
-    a->snap_pending = target;
-    return HP_OK;
-}
-
-int hp_agent_act_snapshot(hp_agent *a, const double *obs_host, const double *g_host, int64_t rows, double clip_obs,
-                          float *actions_host) {
-    HP_REQUIRE(a && obs_host && g_host && actions_host, HP_ERR_INVALID, "hp_agent_act_snapshot: null argument");
-    HP_REQUIRE(rows > 0 && rows < (1 << 24), HP_ERR_INVALID, "hp_agent_act_snapshot: rows out of range");
-    hipStream_t s = nullptr;
-    {
-        HP_SERIALISE(a);
-        HP_REQUIRE(a->snap_cur >= 0 || a->snap_pending >= 0, HP_ERR_STATE, "hp_agent_act_snapshot: no snapshot taken yet");
-        if (a->snap_pending >= 0) {
-            hipEvent_t ev = a->snap[a->snap_pending].ready;
-            hipError_t q = hipEventQuery(ev);
-            if (q == hipErrorNotReady && a->snap_cur < 0) {   // the very first snapshot: nothing older to fall back to
-                HP_CHECK_HIP(hipEventSynchronize(ev));
-                q = hipSuccess;
-            }
-            (void)hipGetLastError();
-            if (q == hipSuccess) {
-                a->snap_cur = a->snap_pending;
-                a->snap_pending = -1;
-            }
-        }
-        const hp_agent::PolicySnap &ps = a->snap[a->snap_cur];
-        s = a->act_stream;
-        const int ad = a->cfg.act_dim;
-        const size_t nb_o = (size_t)rows * ps.od * 8, nb_g = (size_t)rows * ps.gd * 8;
-        const size_t head = (nb_o + nb_g + 15) & ~(size_t)15;
-        HP_TRY(a->act_ws.ensure(head + (size_t)rows * ad * 4));
-        char *d = a->act_ws.as<char>();
-        float *d_act = reinterpret_cast<float *>(d + head);
-        HP_CHECK_HIP(hipMemcpyAsync(d, obs_host, nb_o, hipMemcpyHostToDevice, s));
-        HP_CHECK_HIP(hipMemcpyAsync(d + nb_o, g_host, nb_g, hipMemcpyHostToDevice, s));
-        PolicyArgs P;
-        memset(&P, 0, sizeof(P));
-        P.obs = reinterpret_cast<const double *>(d);
-        P.g = reinterpret_cast<const double *>(d + nb_o);
-        P.od = ps.od; P.gd = ps.gd;
-        P.onz = ps.on; P.gnz = ps.gn;
-        P.clip_obs = clip_obs > 0 ? clip_obs : INFINITY; P.clip_o = ps.clip_o; P.clip_g = ps.clip_g;
-        P.rows = (int)rows;
-        P.net = SlabNetPtrs{ps.fragF, nullptr, ps.params};
-        P.la = a->la; P.H = a->H; P.act_dim = ad; P.max_action = (float)a->cfg.max_action;
-        P.actions = d_act;
-        hipLaunchKernelGGL(s8r4::k_policy_slab8, dim3((unsigned)((rows + 3) / 4)), dim3(S8_THREADS), 0, s, P);
-        HP_CHECK_HIP(hipGetLastError());
-        HP_CHECK_HIP(hipMemcpyAsync(actions_host, d_act, (size_t)rows * ad * 4, hipMemcpyDeviceToHost, s));
-        HP_CHECK_HIP(hipEventRecord(a->act_done, s));
-        a->act_recorded = true;
-    }
-    HP_CHECK_HIP(hipStreamSynchronize(s));   // outside the context lock: the trainer keeps enqueueing meanwhile
-    return HP_OK;
-}
-
-}  // extern "C"
 
 extern "C" {
 

@@ -37,6 +37,7 @@
 #undef S8_DEVICE_ONLY
 
 #include "episode_audit.h"
+#include "policy_call.h"
 
 struct EpisodePolicyArgs {
     PolicyArgs P;                  // the actor: obs / g at the first episode (indexed here, not by s8_policy_slab), rows = n T
@@ -73,9 +74,7 @@ static int episode_policy_launch(const char *entry, hp_agent *a, hp_norm *on, hp
                                  const double *g, int block_od, int block_gd, int block_ad, int64_t n, int32_t T, double clip_obs,
                                  float *pi, float *q_pi) {
     HP_REQUIRE(target == 0 || target == 1, HP_ERR_INVALID, "%s: target %d is neither 0 (online) nor 1 (target networks)", entry, (int)target);
-    HP_REQUIRE(a->slab8 && a->H == 256 && a->ldx <= 48 && a->cfg.act_dim <= 4, HP_ERR_STATE,
-               "%s: the agent is not slab-shaped (hidden %d, padded input width %d, act_dim %d, engine %s)", entry, a->H, a->ldx,
-               a->cfg.act_dim, a->slab8 ? "slab8" : "other");
+    HP_TRY(require_slab_shaped(entry, a, HP_ERR_STATE));
     HP_REQUIRE(on->size + gn->size == a->xdim, HP_ERR_INVALID, "%s: normalizer sizes %d+%d do not match the network input %d", entry,
                (int)on->size, (int)gn->size, a->xdim);
     HP_REQUIRE(block_od < 0 || (block_od == on->size && block_gd == gn->size && block_ad == a->cfg.act_dim), HP_ERR_INVALID,
@@ -87,14 +86,8 @@ static int episode_policy_launch(const char *entry, hp_agent *a, hp_norm *on, hp
     static_assert(sizeof(s8ep::PolicyLds) <= 160 * 1024, "the policy slab's LDS fits a CU");
     EpisodePolicyArgs A;
     memset(&A, 0, sizeof(A));
-    PolicyArgs &P = A.P;
-    P.obs = obs; P.g = g;
-    P.rows = (int)rows;
-    P.od = on->size; P.gd = gn->size;
-    P.onz = on->d; P.gnz = gn->d;
-    P.clip_obs = clip_obs > 0 ? clip_obs : INFINITY; P.clip_o = on->clip; P.clip_g = gn->clip;
-    P.net = target ? SlabNetPtrs{a->fragFT, nullptr, a->targets} : SlabNetPtrs{a->fragF, a->fragD, a->params};
-    P.la = a->la; P.H = a->H; P.act_dim = a->cfg.act_dim; P.max_action = (float)a->cfg.max_action;
+    A.P = policy_args(a, slab_net(a, target != 0), norm_view(on), norm_view(gn), clip_or_inf(clip_obs), rows);
+    A.P.obs = obs; A.P.g = g;
     A.pi = pi; A.q_pi = q_pi;
     A.lc = a->lc; A.T = T; A.act_off = a->act_off; A.ca = a->la.total;
     hipLaunchKernelGGL(k_episode_policy, dim3((unsigned)((rows + 3) / 4)), dim3(S8_THREADS), 0, a->ctx->stream, A);

@@ -14,7 +14,7 @@
 // Which weights.  Every launch form of an update sequence (one chain launch, the split launch with its tile launches, the
 // layer-per-launch engine's Adam pass) writes the optimizer step through AdamFuse into ONE set of buffers: a->params (canonical)
 // and a->fragF (forward fragments), and the polyak step into a->targets / a->fragFT (adam_fuse / adam_block in agent_engines.hip are
-// the one place that names them; hp_agent_set_params / hp_agent_soft_update / hp_state_restore go through k_relayout / k_polyak_frag
+// the one place that writes them, slab_net in policy_call.h the one that reads them here; hp_agent_set_params / hp_agent_soft_update / hp_state_restore go through k_relayout / k_polyak_frag
 // onto the same buffers).  There is no second copy to go stale: this launch reads those four, the critic's segment at la.total, on the
 // context's stream behind whatever wrote them.
 #include <cmath>
@@ -34,7 +34,9 @@
 #undef S8_DEVICE_ONLY
 
 #include "episode_audit.h"
+#include "policy_call.h"
 
+// (od / gd / onz / gnz / clip_obs / clip_o / clip_g keep PolicyArgs' names: set_norm_inputs, policy_call.h, fills them by name)
 struct EpisodeQArgs {
     const double *obs, *g, *act;   // [n][T + 1][od], [n][T][gd], [n][T][ad], already offset to the first episode
     float *q;                      // [n][T]
@@ -74,9 +76,7 @@ static int episode_q_launch(const char *entry, hp_agent *a, hp_norm *on, hp_norm
                             const double *g, const double *act, int block_od, int block_gd, int block_ad, int64_t n, int32_t T,
                             double clip_obs, float *q) {
     HP_REQUIRE(net == HP_NET_CRITIC || net == HP_NET_CRITIC_TARGET, HP_ERR_INVALID, "%s: net must be a critic", entry);
-    HP_REQUIRE(a->slab8 && a->H == 256 && a->ldx <= 48 && a->cfg.act_dim <= 4, HP_ERR_STATE,
-               "%s: the agent is not slab-shaped (hidden %d, padded input width %d, act_dim %d, engine %s)", entry, a->H, a->ldx,
-               a->cfg.act_dim, a->slab8 ? "slab8" : "other");
+    HP_TRY(require_slab_shaped(entry, a, HP_ERR_STATE));
     HP_REQUIRE(on->size + gn->size == a->xdim, HP_ERR_INVALID, "%s: normalizer sizes %d+%d do not match the critic input %d", entry,
                (int)on->size, (int)gn->size, a->xdim);
     HP_REQUIRE(block_od < 0 || (block_od == on->size && block_gd == gn->size && block_ad == a->cfg.act_dim), HP_ERR_INVALID,
@@ -90,10 +90,9 @@ static int episode_q_launch(const char *entry, hp_agent *a, hp_norm *on, hp_norm
     memset(&A, 0, sizeof(A));
     A.obs = obs; A.g = g; A.act = act; A.q = q;
     A.rows = rows; A.T = T;
-    A.od = on->size; A.gd = gn->size; A.ad = a->cfg.act_dim; A.act_off = a->act_off;
-    A.onz = on->d; A.gnz = gn->d;
-    A.clip_obs = clip_obs > 0 ? clip_obs : INFINITY; A.clip_o = on->clip; A.clip_g = gn->clip;
-    A.net = (net == HP_NET_CRITIC) ? SlabNetPtrs{a->fragF, a->fragD, a->params} : SlabNetPtrs{a->fragFT, nullptr, a->targets};
+    set_norm_inputs(A, norm_view(on), norm_view(gn), clip_or_inf(clip_obs));   // the normalizer half, as PolicyArgs names it
+    A.ad = a->cfg.act_dim; A.act_off = a->act_off;
+    A.net = slab_net(a, net != HP_NET_CRITIC);
     A.lc = a->lc; A.ca = a->la.total; A.H = a->H;
     A.max_action = (float)a->cfg.max_action;
     hipLaunchKernelGGL(k_episode_q, dim3((unsigned)((rows + 3) / 4)), dim3(S8_THREADS), 0, a->ctx->stream, A);

@@ -1,4 +1,4 @@
-// gemm_lds.h -- grouped FP32-MFMA GEMM, LDS-staged operands (included by agent_engines.hip; the layer-per-launch engine of agent_layers.hip launches it through launch_group).
+// gemm_lds.h -- grouped FP32-MFMA GEMM, LDS-staged operands (included by agent_engines.hip; the layer-per-launch engine of agent_layers.hip and the forward chain of agent_forward.hip, mlp_rows, launch it through launch_group).
 //
 // Why a second kernel: the first version fed v_mfma_f32_16x16x4_f32 straight from global memory
 // with one dword per lane, i.e. 16 rows x 16 B per wave-instruction for K-contiguous operands.

@@ -389,7 +389,10 @@ int buffer_stage_pinned(hp_buffer *b, hp_rng *rng, const double *block, int64_t 
 // the same out of a DEVICE block (a rollout wave collected on the device, rollout.hip): a device-to-device copy, no ticket
 int buffer_stage_dev(hp_buffer *b, hp_rng *rng, const double *block_dev, int64_t n_new, bool store_now);
 
-// agent_engines.hip: hp_agent_act on device rows, actions left on the device, nothing copied, no host wait
+// agent_engines.hip: the one launch of k_policy_slab8 (slab8.h), a workgroup per 4 rows of P
+struct PolicyArgs;
+int launch_policy_slab(hipStream_t stream, const PolicyArgs &P);
+// agent_forward.hip: hp_agent_act on device rows, actions left on the device, nothing copied, no host wait
 int agent_act_dev(hp_agent *a, hp_norm *on, hp_norm *gn, int32_t net, const double *obs_dev, const double *g_dev, int64_t rows,
                   double clip_obs, float *actions_dev);
 

@@ -33,6 +33,7 @@
 
 #include "rollout_episodes.h"   // ExploreArgs, ro_explore_row, PolicyArgs (slab8.h), EpisodesArgs and EnvKind
 #include "demo_episodes.h"      // DemoArgs (the kernel is instantiated by the kinds' demo units, through EnvKind::launch_demo), CompactArgs
+#include "policy_call.h"        // policy_args, slab_net, require_slab_shaped
 
 struct RolloutStepArgs {
     const double *obs, *ag, *g;    // this timestep's rows [rows][dim] (g == nullptr: the closing record of row T)
@@ -221,9 +222,7 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
                HP_ERR_INVALID, "%s: handles belong to different contexts", entry);
     const EnvKind *kind;
     HP_TRY(env_kind_lookup(entry, env, kind));
-    HP_REQUIRE(a->slab8 && a->H == 256 && a->ldx <= 48 && a->cfg.act_dim <= 4, HP_ERR_INVALID,
-               "%s: the agent is not slab-shaped (hidden %d, padded input width %d, act_dim %d, engine %s): it keeps "
-               "the per-step calls", entry, a->H, a->ldx, a->cfg.act_dim, a->slab8 ? "slab8" : "other");
+    HP_TRY(require_slab_shaped(entry, a, HP_ERR_INVALID, ": it keeps the per-step calls"));
     HP_REQUIRE(a->cfg.act_dim == ro->ad && on->size == ro->od && gn->size == ro->gd && on->size + gn->size == a->xdim, HP_ERR_INVALID,
                "%s: agent / normalizer dimensions differ from the block's", entry);
     HP_REQUIRE(!explore || streams, HP_ERR_INVALID, "%s: explore != 0 needs `streams`", entry);
@@ -237,12 +236,7 @@ static int rollout_episodes(const char *entry, hp_rollout *ro, hp_agent *a, hp_n
     HP_TRY(env_desc_check(entry, kind, env, ro, reset_streams != nullptr));
     EpisodesArgs A;
     memset(&A, 0, sizeof(A));
-    PolicyArgs &P = A.P;
-    P.od = on->size; P.gd = gn->size;
-    P.onz = on->d; P.gnz = gn->d;
-    P.clip_obs = INFINITY; P.clip_o = on->clip; P.clip_g = gn->clip;   // agent_act_dev with clip_obs = 0
-    P.net = SlabNetPtrs{a->fragF, a->fragD, a->params};
-    P.la = a->la; P.H = a->H; P.act_dim = a->cfg.act_dim; P.max_action = (float)a->cfg.max_action;
+    A.P = policy_args(a, slab_net(a, false), norm_view(on), norm_view(gn), clip_or_inf(0.0), 0);   // agent_act_dev with clip_obs = 0; rows: per launch
     A.st = explore ? streams->d_state : nullptr;
     A.reset_st = reset_streams ? reset_streams->d_state : nullptr;
     A.rows = (int)ro->rows; A.T = ro->T; A.explore = explore ? 1 : 0;

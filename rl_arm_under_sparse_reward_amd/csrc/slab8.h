@@ -108,7 +108,8 @@ struct FbSlabArgs {
     float *aXT, *aXA, *aXP;      // its input sets (the chains of THIS launch use f.XT / f.XA / f.XP)
 };
 
-// Rollout-side policy call (hp_agent_act / hp_agent_actor_forward): one 4-row slab per workgroup through the actor
+// Rollout-side policy call: one 4-row slab per workgroup through the actor (s8_policy_slab, k_policy_slab8 below).  Filled by
+// policy_args (policy_call.h), which leaves obs / g / x / actions to the caller; launched by launch_policy_slab (agent_engines.hip)
 struct PolicyArgs {
     const double *obs, *g;        // raw float64 rows (hp_agent_act) ...
     const float *x;               // ... or already normalised float32 rows [rows][od + gd] (hp_agent_actor_forward)
@@ -126,6 +127,8 @@ struct PolicyArgs {
 #include "transition_device.h"   // the arithmetic of a gathered row, one definition for every slab height's namespace
 
 #endif  // RLARM_SLAB8_SHARED
+
+#ifndef S8_SHARED_ONLY   // (a host-only unit that wants the argument blocks above and no slab height: agent_forward.hip)
 
 // ---- everything below is compiled once per slab height: S8_NRG row groups of 4 (S8_NRG = 1: 4-row slabs, the
 // small-batch choice; S8_NRG = 2 / 4: 8- / 16-row slabs, less weight traffic per row for batches that fill the chip),
@@ -1106,3 +1109,4 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 #endif
 
 }  // namespace S8_NS
+#endif  // S8_SHARED_ONLY

@@ -1,6 +1,6 @@
 // transition_device.h -- the arithmetic of one transition, stated once: the squared goal distance and the reward taken on it, a
 // network input out of a float64 row value, where a sampled transition's goal lies, and the move of a double between lanes.
-// Every gather (sampler.hip, agent_engines.hip, slab8.h), the normalizer (norm.hip, norm_device.h), the episode audit
+// Every gather (sampler.hip, agent_engines.hip, agent_forward.hip, slab8.h), the normalizer (norm.hip, norm_device.h), the episode audit
 // (episode_stats.hip, episode_returns.hip, episode_q.hip) and the environments' success test (env_device.h) call these.  Two
 // sites keep an expression written out, with a comment that points here (k_gather_dict's distance loop, s8_gather's two inputs:
 // the generated code is the reason, profiles/transition_arithmetic_refactor.txt).  They sit outside every S8_NS namespace, so slab8.h's instantiations share one definition.

@@ -96,7 +96,7 @@ def fused_rollout_reason(env_native, agent_slab, explore, has_streams):
     stream with explore=True stays per-step: its walk visits the environments one after the other by definition."""
     if not env_native:
         return "the environment is not native: its dynamics run in torch, one launch boundary per timestep"
-    if not agent_slab:
+    if not agent_slab:       # the rule is require_slab_shaped's (csrc/policy_call.h); this sentence restates it
         return "the agent is not slab-shaped (hidden 256, padded input width <= 48, at most 4 action components)"
     if explore and not has_streams:
         return "exploring from the single shared stream is a sequential walk across the environments (enable_explore_streams)"

@@ -50,6 +50,16 @@ def test_act_device_equals_act(rows):
             assert np.array_equal(bits(got.cpu().numpy()), bits(want)), (rows, target, clip_obs)
 
 
+@pytest.mark.parametrize("rows", [1, 5, 33])                     # 33: past the 32-row padding of the GEMMs' Mp
+def test_act_device_equals_act_on_the_layer_engine(rows, monkeypatch):
+    """The same on the layer-per-launch engine, whose device-to-device tail (mlp_rows, agent_forward.hip) the default engine never
+    takes: act_device leaves in device memory the bits act downloads."""
+    monkeypatch.setenv("RLARM_ENGINE", "layers")
+    probe = make(None)                                           # the switch took: no fused policy kernel to snapshot (HP_ERR_STATE)
+    assert probe.lib.hp_agent_policy_snapshot(probe.h, probe.o_norm.h, probe.g_norm.h) == -5
+    test_act_device_equals_act(rows)
+
+
 def test_draw_hooks_follow_numpy():
     """standard_normal / binomial1 consume numpy's words (state, cached normal included); binomials equal, normals within 4 ulp
     (device log: 1 ulp; sqrt, divide, multiply exactly rounded)."""
