@@ -621,6 +621,57 @@ int hp_episode_policy_stats_block(hp_rollout *ro, const float *pi_dev, const flo
                                   int64_t first_episode, int64_t n_episodes, double max_action, double sat, double *stats_dev);
 int hp_episode_policy_summary(hp_ctx *ctx, const double *policy_stats_dev, int64_t n_episodes, double *summary_dev);
 
+/* ---- actor-signal audit on the device ------------------------------------------------------------
+ * The quantity that moves the actor, for every step of an episode block: a sample's actor update is dQ/da at a = pi(s), minus
+ * the action_l2 pull, passed through tanh' (ddpg_agent.py:265-267 through the critic of models.py:28-44).  Where the critic is
+ * flat in the action the actor learns nothing, or only shrinks towards zero under the regulariser; a demonstration helps only
+ * where the gradient at pi(s) points towards the demonstrated action.
+ *
+ * hp_episode_action_grad: dq_du_dev[e][t][j] (float32) = d Q(s_t, u) / d u_j, u the critic's action input a / max_action, for
+ * t = 0 .. T-1 of n_episodes episodes in ONE launch: an update's actor-side chain (same device functions, 4-row slabs) up to the
+ * action columns of the critic's input gradient, seeded with dQ/dq = 1 for every row instead of an update's -1 / B.  dQ/da is
+ * dq_du / max_action; it is not stored.  at 0: at the policy, u = (max_action * tanh) / max_action as hp_episode_policy forms it;
+ * pi_dev[e][t][j] and q_dev[e][t] = Q(s_t, pi(s_t)) are hp_episode_policy's, bit for bit.  at 1: at the recorded action,
+ * u = (float)actions[e][t][j] / max_action as hp_episode_q forms it; q_dev[e][t] = Q(s_t, a_t) is hp_episode_q's, bit for bit;
+ * no actor runs and pi_dev is not written (it may be NULL; actions_dev may be NULL with at 0).  Arrays and clip_obs as for
+ * hp_episode_policy / hp_episode_q.  target 0: the online networks.  target 1 is refused with HP_ERR_STATE: the target networks
+ * keep no dX-order weight fragments (no update differentiates through them) and this call builds none.
+ * hp_episode_action_grad_block is the same on episodes [first_episode, first_episode + n_episodes) of a block, whose recorded
+ * actions it reads.  Both asynchronous on the context's stream (or a borrowed one), behind whatever wrote the weights; nothing
+ * is allocated.  Refusals are hp_episode_policy's in its order, naming the entry point; behind target: at outside {0, 1}, at 1
+ * without actions_dev, at 0 without pi_dev (HP_ERR_INVALID); behind the agent's shape: target 1 (HP_ERR_STATE).
+ *
+ * hp_episode_signal_stats: stats_dev [n][HP_SIGNAL_STATS] (float64) out of pi_dev and dq_du_dev (both of at 0) and the recorded
+ * actions_dev [n][T][act_dim] (float64).  With M = (double)(float)max_action, lambda = action_l2, and per step g_j = dq_du[t][j],
+ * v_j = pi[t][j] / M, d_j = (a[t][j] - pi[t][j]) / M, |x| = sqrt(sum_j x_j x_j):
+ *   [0] grad_norm        sum_t |g| / T
+ *   [1] flat_share       #{t : |g| < flat} / T
+ *   [2] reg_share        #{t : (lambda * (2 / act_dim)) * |v| > |g|} / T: the regulariser outweighs the critic
+ *   [3] toward_recorded  sum_t c_t / T, c_t = (sum_j g_j d_j) / (|g| * |d|), 0 where that product is 0
+ *   [4] linear_adv       sum_t (sum_j g_j d_j) / T: the first-order estimate of Q(s, a) - Q(s, pi(s)), to be read beside
+ *                        hp_episode_policy_stats' advantage_mean (which is Q(s, pi(s)) - Q(s, a))
+ *   [5] trunk_signal     sum_t |s| / T, s_j = (g_j - ((lambda * 2) * v_j) / act_dim) * (1 - v_j v_j): what reaches the actor's
+ *                        trunk behind the tanh, per sample
+ * every float32 widened to float64, every sum started at 0 and accumulated in ascending t (inner j ascending), every operation
+ * rounded on its own: the order is fixed and synthetic.episode_signal_stats is the same loop, so the bits are the host twin's.  One
+ * wave per episode.  hp_episode_signal_stats_block takes the actions of a block's episodes.  hp_episode_signal_summary reduces
+ * n_episodes rows to the six column means, left to right in episode order (synthetic.episode_signal_summary).  All asynchronous,
+ * nothing allocated; HP_ERR_INVALID, naming the entry point, for a null argument, n_episodes or T out of range as for
+ * hp_episode_stats, act_dim outside [1, HP_POLICY_MAX_ACT_DIM], max_action not positive and finite, action_l2 or flat negative or
+ * not finite, episodes outside the block. */
+#define HP_SIGNAL_STATS 6
+int hp_episode_action_grad(hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, int32_t target, int32_t at, const double *obs_dev,
+                           const double *g_dev, const double *actions_dev, int64_t n_episodes, int32_t T, double clip_obs,
+                           float *pi_dev, float *q_dev, float *dq_du_dev);
+int hp_episode_action_grad_block(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, int32_t target, int32_t at,
+                                 int64_t first_episode, int64_t n_episodes, double clip_obs, float *pi_dev, float *q_dev,
+                                 float *dq_du_dev);
+int hp_episode_signal_stats(hp_ctx *ctx, const float *pi_dev, const float *dq_du_dev, const double *actions_dev, int64_t n_episodes,
+                            int32_t T, int32_t act_dim, double max_action, double action_l2, double flat, double *stats_dev);
+int hp_episode_signal_stats_block(hp_rollout *ro, const float *pi_dev, const float *dq_du_dev, int64_t first_episode,
+                                  int64_t n_episodes, double max_action, double action_l2, double flat, double *stats_dev);
+int hp_episode_signal_summary(hp_ctx *ctx, const double *signal_stats_dev, int64_t n_episodes, double *summary_dev);
+
 /* Policy calls that do not queue behind training: hp_agent_policy_snapshot copies the online actor and both normalizers'
  * statistics (stream-ordered with the updates, no host wait); hp_agent_act_snapshot evaluates the most recent COMPLETE
  * snapshot on a second stream, so a feeder can step its environments while a training cycle runs (its policy lags the

@@ -1,5 +1,5 @@
-// episode_audit.h -- the frame the four units of the episode audit share (episode_stats.hip, episode_returns.hip, episode_q.hip,
-// episode_policy.hip): the bound on episodes and steps, the refusals every entry makes of a block's shape, the range check of the
+// episode_audit.h -- the frame the five units of the episode audit share (episode_stats.hip, episode_returns.hip, episode_q.hip,
+// episode_policy.hip, episode_action_grad.hip): the bound on episodes and steps, the refusals every entry makes of a block's shape, the range check of the
 // *_block entries with the block's four arrays behind it, and the summary of a per-episode table.  The arithmetic of a step:
 // transition_device.h.
 #pragma once

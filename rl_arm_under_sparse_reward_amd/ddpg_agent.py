@@ -147,6 +147,8 @@ class ddpg_agent(EpisodeAudit):
         self.eval_critic = []            # args.eval_critic: one dict per evaluation, keyed by synthetic.CRITIC_STATS
         self.policy_audit = []           # args.audit_policy: one dict per epoch, keyed by synthetic.POLICY_STATS
         self._policy_audit_pending = None
+        self.actor_signal_audit = []     # args.audit_actor_signal: one dict per epoch, keyed by synthetic.SIGNAL_STATS
+        self._actor_signal_pending = None
         self.model_path = os.path.join(self.args.save_dir, self.args.env_name)
 
     def close_comm(self):
@@ -887,7 +889,7 @@ class ddpg_agent(EpisodeAudit):
         print("initial buffer size:", self.buffer.current_size)                  # :97
         if self.vec_env is not None:
             return self._learn_device(share, state_path, first_epoch)
-        audit = bool(getattr(self.args, "audit_policy", False))
+        audit, audit_signal = bool(getattr(self.args, "audit_policy", False)), bool(getattr(self.args, "audit_actor_signal", False))
         for epoch in range(first_epoch, self.args.n_epochs):
             start = time.time()
             episodes = None
@@ -900,6 +902,8 @@ class ddpg_agent(EpisodeAudit):
                     np.random.set_state(self.rng.get_state())
             if audit and episodes is not None:
                 self._policy_audit_pending = episodes    # host arrays: audited behind _finish_epoch's synchronise
+            if audit_signal and episodes is not None:
+                self._actor_signal_pending = episodes
             self._finish_epoch(epoch, start, state_path)
 
     def _finish_epoch(self, epoch, start, state_path, before_save=None):
@@ -909,6 +913,7 @@ class ddpg_agent(EpisodeAudit):
         self.check_exchange()
         print(str(time.time() - start))
         self._record_policy_audit()      # args.audit_policy: before the evaluation, which may collect into the same block
+        self._record_actor_signal_audit()     # args.audit_actor_signal: likewise
         rate = self._eval_agent()
         self.success_rates.append(rate)
         if self.comm.rank == 0:
@@ -930,7 +935,7 @@ class ddpg_agent(EpisodeAudit):
 
         if share:
             self.rng.set_state(np.random.get_state())
-        audit = bool(getattr(self.args, "audit_policy", False))
+        audit, audit_signal = bool(getattr(self.args, "audit_policy", False)), bool(getattr(self.args, "audit_actor_signal", False))
         for epoch in range(first_epoch, self.args.n_epochs):
             start = time.time()
             eps = None
@@ -946,6 +951,11 @@ class ddpg_agent(EpisodeAudit):
                     _lib.check(self.lib.hp_episode_policy_summary(self.ctx.h, C.c_void_p(stats.data_ptr()), stats.shape[0],
                                                                   C.c_void_p(summary.data_ptr())))
                 self._policy_audit_pending = summary
+            if audit_signal and eps is not None:
+                # args.audit_actor_signal: the same episodes, three launches (dQ/du at the policy, the columns, their means)
+                # behind the cycle; nothing waits, the 48 bytes are read behind _finish_epoch's synchronise
+                stats = self.episode_signal_stats(eps, first=0, n=self.args.num_rollouts_per_mpi)[0]
+                self._actor_signal_pending = self._signal_summary(stats)
             self._finish_epoch(epoch, start, state_path, before_save=hand_back)
         hand_back()
 

@@ -1,5 +1,6 @@
-"""The three audits of recorded episodes as the agent runs them: the metrics (hp_episode_stats*), the critic audit
-(hp_episode_q*, hp_episode_returns*) and the policy audit (hp_episode_policy*), each on a `DeviceEpisodes` block in place or on
+"""The four audits of recorded episodes as the agent runs them: the metrics (hp_episode_stats*), the critic audit
+(hp_episode_q*, hp_episode_returns*), the policy audit (hp_episode_policy*) and the actor-signal audit (hp_episode_action_grad*,
+hp_episode_signal_stats*), each on a `DeviceEpisodes` block in place or on
 host episodes that are uploaded first, and what puts an epoch's summary onto the agent's lists.  `ddpg_agent` inherits these
 methods; they use its `lib`, `ctx`, `h`, `o_norm`, `g_norm`, `args`, `env_params`, `vec_env` and `comm`."""
 from __future__ import annotations
@@ -161,6 +162,85 @@ class EpisodeAudit:
         pi, q_pi = self._policy(None, 0, n, T, target, obs, g)
         stats = self._policy_columns(None, 0, pi, q_pi, q, sat, act)
         return stats.cpu().numpy(), pi.cpu().numpy(), q_pi.cpu().numpy(), q.cpu().numpy()
+
+    # ---- the actor signal: dQ/du of every step (hp_episode_action_grad*) and its columns (hp_episode_signal_stats*)
+    def _action_grad(self, episodes, first, n, T, target, at, obs=None, g=None, act=None):
+        if at not in ("policy", "recorded"):
+            raise ValueError(f"episode_action_grad: at {at!r} is neither 'policy' nor 'recorded'")
+        dev = torch.device("cuda", self.ctx.device_id)
+        ad, at_policy = int(self.env_params['action']), at == "policy"
+        dq_du = torch.empty((max(n, 0), T, ad), dtype=torch.float32, device=dev)
+        pi = torch.empty((max(n, 0), T, ad), dtype=torch.float32, device=dev) if at_policy else None
+        q = torch.empty((max(n, 0), T), dtype=torch.float32, device=dev)
+        nets = (self.h, self.o_norm.h, self.g_norm.h, 1 if target else 0, 0 if at_policy else 1)
+        tail = (float(self.args.clip_obs), _p(pi) if at_policy else None, _p(q), _p(dq_du))
+        with self.ctx.torch_bridge():
+            if episodes is not None:
+                _lib.check(self.lib.hp_episode_action_grad_block(episodes.h, *nets, first, n, *tail))
+            else:
+                _lib.check(self.lib.hp_episode_action_grad(*nets, _p(obs), _p(g), _p(act) if act is not None else None, n, T, *tail))
+        return dq_du, pi, q
+
+    def _signal_columns(self, episodes, first, pi, dq_du, flat, act=None):
+        n, T, ad = pi.shape
+        stats = torch.empty((n, _lib.SIGNAL_STATS), dtype=torch.float64, device=pi.device)
+        tail = (float(self.env_params['action_max']), float(self.args.action_l2), float(flat), _p(stats))
+        with self.ctx.torch_bridge():
+            if episodes is not None:
+                _lib.check(self.lib.hp_episode_signal_stats_block(episodes.h, _p(pi), _p(dq_du), first, n, *tail))
+            else:
+                _lib.check(self.lib.hp_episode_signal_stats(self.ctx.h, _p(pi), _p(dq_du), _p(act), n, T, ad, *tail))
+        return stats
+
+    def episode_action_grad(self, episodes, target=False, at="policy", first=0, n=None):
+        """The quantity that moves the actor, on episodes [first, first + n) of a `DeviceEpisodes`: (dq_du [n, T, act] float32,
+        pi [n, T, act] float32 or None, q [n, T] float32), device tensors from one launch on torch's current stream
+        (hp_episode_action_grad_block) -- an update's actor-side chain up to the action columns of the critic's input gradient,
+        seeded with 1 per row.  dq_du is the derivative with respect to the critic's action input u = a / max_action; dQ/da is
+        dq_du / max_action.  at="policy": at u = pi(s) / max_action; pi and q = Q(s, pi(s)) are `episode_policy`'s bits.
+        at="recorded": at the recorded action; pi is None and q = Q(s, a) is `episode_q`'s bits.  `target=True` is refused by
+        the library: the target networks keep no dX-order fragments.  No copy, no synchronisation."""
+        return self._action_grad(episodes, *_span(episodes, first, n), episodes.T, target, at)
+
+    def episode_signal_stats(self, episodes, flat=1e-3, first=0, n=None):
+        """The actor's learning signal audited on episodes [first, first + n) of a `DeviceEpisodes`: (stats [n, 6] float64 in
+        the columns of `synthetic.SIGNAL_STATS`, dq_du, pi, q_pi), device tensors from two launches (`episode_action_grad` at
+        the policy, the columns: hp_episode_signal_stats_block, with `args.action_l2` as the regulariser's weight).  No copy, no
+        synchronisation."""
+        dq_du, pi, q_pi = self.episode_action_grad(episodes, first=first, n=n)
+        return self._signal_columns(episodes, int(first), pi, dq_du, flat), dq_du, pi, q_pi
+
+    def episode_signal_stats_host(self, episode_batch, flat=1e-3):
+        """`episode_signal_stats` for host episodes -- the four arrays `collect_episodes` returns, or a feeder slot's (obs, ag, g,
+        actions): they are uploaded, the same kernels run (hp_episode_action_grad, hp_episode_signal_stats) and the result comes
+        back as numpy (stats [n, 6] float64, dq_du [n, T, act] float32, pi [n, T, act] float32, q_pi [n, T] float32).
+        Synchronises."""
+        obs, _, g, act = _upload(self, episode_batch, "episode_signal_stats_host")
+        n, T, _ = act.shape
+        dq_du, pi, q_pi = self._action_grad(None, 0, n, T, False, "policy", obs, g, act)
+        stats = self._signal_columns(None, 0, pi, dq_du, flat, act)
+        return stats.cpu().numpy(), dq_du.cpu().numpy(), pi.cpu().numpy(), q_pi.cpu().numpy()
+
+    def _signal_summary(self, stats):
+        """The six column means of a device table of signal columns, a device tensor (hp_episode_signal_summary)"""
+        summary = torch.empty(_lib.SIGNAL_STATS, dtype=torch.float64, device=stats.device)
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_episode_signal_summary(self.ctx.h, _p(stats), stats.shape[0], _p(summary)))
+        return summary
+
+    def _record_actor_signal_audit(self):
+        """args.audit_actor_signal: the epoch's pending audit -- the device path's summary (six means, already computed) or the
+        host path's episodes (audited now: `episode_signal_stats_host`) -- averaged over the ranks like the success rate, onto
+        `actor_signal_audit`"""
+        pending, self._actor_signal_pending = self._actor_signal_pending, None
+        if pending is None:
+            return
+        from .synthetic import SIGNAL_STATS, episode_signal_summary
+        if isinstance(pending, torch.Tensor):
+            summary = pending.cpu().numpy()
+        else:
+            summary = episode_signal_summary(self.episode_signal_stats_host(pending)[0])
+        _record(self, SIGNAL_STATS, summary, self.actor_signal_audit)
 
     def _record_eval_metrics(self, summary):
         """One evaluation's summary (this rank's six means), averaged over the ranks like the success rate, onto `eval_metrics`"""

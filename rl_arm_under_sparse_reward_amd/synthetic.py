@@ -676,6 +676,71 @@ def episode_policy_summary(stats):
     return _column_means("episode_policy_summary", POLICY_STATS, stats)
 
 
+SIGNAL_STATS = ("grad_norm", "flat_share", "reg_share", "toward_recorded", "linear_adv", "trunk_signal")
+
+
+def episode_signal_stats(pi, dq_du, actions, max_action, action_l2=1.0, flat=1e-3):
+    """The host twin of hp_episode_signal_stats, as plain loops: `pi` [n, T, act] float32 (the policy's actions), `dq_du`
+    [n, T, act] float32 (dQ/du at u = pi / max_action, `episode_action_grad` of the same episodes) and `actions` [n, T, act]
+    float64 (the recorded ones) -> [n, 6] float64 in the columns of SIGNAL_STATS.  max_action is the networks' float32, widened;
+    every float32 is widened, every sum starts at 0 and runs in ascending t (inner j ascending), one rounding per operation, and
+    is divided once at the end.  Per step g_j = dq_du_j, v_j = pi_j / M, d_j = (a_j - pi_j) / M, |x| = sqrt(sum_j x_j x_j):
+    grad_norm, the mean of |g|; flat_share, the share of steps with |g| < flat; reg_share, the share with
+    (action_l2 * (2 / act)) * |v| > |g| -- the regulariser outweighs the critic; toward_recorded, the mean of
+    (sum_j g_j d_j) / (|g| * |d|), a step counting 0 where that product is 0; linear_adv, the mean of sum_j g_j d_j -- the
+    first-order estimate of Q(s, a) - Q(s, pi(s)); trunk_signal, the mean of |s| with
+    s_j = (g_j - ((action_l2 * 2) * v_j) / act) * (1 - v_j v_j), what reaches the actor's trunk behind the tanh
+    (ddpg_agent.py:265-267)."""
+    pi, dq_du, actions = np.asarray(pi), np.asarray(dq_du), np.asarray(actions, dtype=np.float64)
+    if (pi.dtype != np.float32 or dq_du.dtype != np.float32 or pi.ndim != 3 or dq_du.shape != pi.shape or actions.shape != pi.shape
+            or pi.shape[1] < 1 or pi.shape[2] < 1):
+        raise ValueError("episode_signal_stats: pi [n, T, act] float32, dq_du [n, T, act] float32 and actions [n, T, act] expected")
+    ma, lam, flat = float(np.float32(max_action)), float(action_l2), float(flat)
+    if not (ma > 0.0 and math.isfinite(ma)):
+        raise ValueError(f"max_action {max_action} is not a positive number")
+    if not (lam >= 0.0 and math.isfinite(lam)):
+        raise ValueError(f"action_l2 {action_l2} is not a finite number >= 0")
+    if not (flat >= 0.0 and math.isfinite(flat)):
+        raise ValueError(f"flat {flat} is not a finite number >= 0")
+    n, T, ad = pi.shape
+    dad = float(ad)
+    lam2, reg_scale = lam * 2.0, lam * (2.0 / dad)
+    out = np.empty((n, len(SIGNAL_STATS)), dtype=np.float64)
+    for e in range(n):
+        ps, gs, acts = pi[e].astype(np.float64).tolist(), dq_du[e].astype(np.float64).tolist(), actions[e].tolist()
+        sum_gn = sum_cos = sum_dot = sum_trunk = 0.0
+        n_flat = n_reg = 0
+        for t in range(T):
+            gg = vv = dd = dot = ss = 0.0
+            for j in range(ad):
+                p, gj = ps[t][j], gs[t][j]
+                v = p / ma
+                d = (acts[t][j] - p) / ma
+                gg = gg + gj * gj
+                vv = vv + v * v
+                dd = dd + d * d
+                dot = dot + gj * d
+                s = (gj - (lam2 * v) / dad) * (1.0 - v * v)
+                ss = ss + s * s
+            gn, vn = math.sqrt(gg), math.sqrt(vv)
+            den = gn * math.sqrt(dd)
+            n_flat += 1 if gn < flat else 0
+            n_reg += 1 if reg_scale * vn > gn else 0
+            sum_gn = sum_gn + gn
+            sum_cos = sum_cos + (dot / den if den > 0.0 else 0.0)
+            sum_dot = sum_dot + dot
+            sum_trunk = sum_trunk + math.sqrt(ss)
+        dT = float(T)
+        out[e] = (sum_gn / dT, float(n_flat) / dT, float(n_reg) / dT, sum_cos / dT, sum_dot / dT, sum_trunk / dT)
+    return out
+
+
+def episode_signal_summary(stats):
+    """The host twin of hp_episode_signal_summary: the six column means over the episodes, each a left-to-right float64 sum in
+    episode order divided by their number."""
+    return _column_means("episode_signal_summary", SIGNAL_STATS, stats)
+
+
 def write_demo_npz_from(path, obs, ag, g, actions, info):
     """Write episodes in the schema get_demo_data_push.py:91-94 produces: keys acs, obs, info, g, ag, with `info` an object
     array [n, T] of per-step dicts {'is_success': float32} (`info` here: the flags [n, T]).  Such a file preloads through

@@ -1,7 +1,8 @@
 """What an audit of recorded episodes costs: `--audit metrics` (args.eval_metrics: hp_episode_stats_block +
 hp_episode_stats_summary behind the rollout), `--audit critic` (args.eval_critic: hp_episode_q_block + hp_episode_returns_block,
 then hp_episode_critic_summary) or `--audit policy` (args.audit_policy: hp_episode_q_block + hp_episode_policy_block +
-hp_episode_policy_stats_block, then hp_episode_policy_summary).  The block is the noise-free evaluation of 25 episodes of T = 100 on
+hp_episode_policy_stats_block, then hp_episode_policy_summary) or `--audit signal` (args.audit_actor_signal:
+hp_episode_action_grad_block + hp_episode_signal_stats_block, then hp_episode_signal_summary).  The block is the noise-free evaluation of 25 episodes of T = 100 on
 2 native point-mass environments with the reset on the device (one rollout launch), in three forms on the same box in alternating
 rounds:
 
@@ -9,11 +10,13 @@ rounds:
            tools/ubench/rollout_device_reset.py: up to, not including, the download of the flags)
     on     the same with the audit, nothing read.  metrics: stats_out and the summary launch (two more small launches); critic:
            three more launches (Q of the 2500 steps, returns + critic columns, summary); policy: four more (Q(s, a), pi and
-           Q(s, pi(s)) of the 2500 steps, the columns, the summary)
+           Q(s, pi(s)) of the 2500 steps, the columns, the summary); signal: three more (pi, Q(s, pi(s)) and dQ/du of the 2500
+           steps, the columns, the summary)
     host   the alternative the kernels replace: the collection, then DeviceEpisodes.numpy() (synchronises, four float64 arrays to
            the host) and the host twins of synthetic.  critic: clip / normalise / scale in numpy, critic_network(x, a) through
            hp_agent_critic_forward (two uploads, seven launches, a download, a wait) in front of them; policy: agent.act on the
-           T + 1-strided rows (upload, one launch, download, wait) and critic_network(x, a), critic_network(x, pi)
+           T + 1-strided rows (upload, one launch, download, wait) and critic_network(x, a), critic_network(x, pi); signal:
+           the weights pulled to the host (state_dict), the actor and the critic in torch on the CPU, autograd for dQ/du
 
 Every (round, form) is a child process of its own under its own `timeout`: it warms the path up, then times `--reps` calls:
 `enqueue_ms`, the host clock around the call alone, and `wall_ms`, the same + one device synchronise.  The device is idle when a
@@ -25,6 +28,9 @@ collections (the audits' launches do not depend on them).
     python tools/ubench/episode_audit.py --audit metrics --out profiles/episode_stats.json
     python tools/ubench/episode_audit.py --audit critic --out profiles/episode_critic.json
     python tools/ubench/episode_audit.py --audit policy --out profiles/episode_policy.json
+    python tools/ubench/episode_audit.py --audit signal --out profiles/episode_action_grad.json
+
+The signal audit's yardstick is the policy audit's forward half: record `--audit policy` of the same run on the same box beside it.
 """
 import argparse
 import ctypes as C
@@ -41,7 +47,8 @@ T, N_ENVS, N_TEST = 100, 2, 25
 FORMS = ("off", "on", "host")
 AUDITS = {"metrics": ("EPISODE_SUMMARY", "hp_episode_stats_summary", "evaluation"),     # summary width, summary entry, the unit's noun
           "critic": ("CRITIC_STATS", "hp_episode_critic_summary", "evaluation"),
-          "policy": ("POLICY_STATS", "hp_episode_policy_summary", "block")}
+          "policy": ("POLICY_STATS", "hp_episode_policy_summary", "block"),
+          "signal": ("SIGNAL_STATS", "hp_episode_signal_summary", "block")}
 
 
 def child(audit, form, reps):
@@ -112,7 +119,35 @@ def child(audit, form, reps):
             return syn.episode_policy_summary(syn.episode_policy_stats(pi.reshape(N_TEST, T, -1), q_pi, actions, env.env_params['action_max'], q=q))
         return flags
 
-    work = {"metrics": work_metrics, "critic": work_critic, "policy": work_policy}[audit]
+    def work_signal():
+        flags = []
+        eps = agent.collect_episodes_device(n_rollouts=N_TEST, explore=False, success_out=flags)
+        if form == "on":
+            summarise(agent.episode_signal_stats(eps)[0])
+        elif form == "host":
+            import torch.nn.functional as F
+            obs, ag, g, actions = eps.numpy()
+            o, gg = agent._preproc_og(obs[:, :T], g)
+            x = torch.from_numpy(np.concatenate([agent.o_norm.normalize(o), agent.g_norm.normalize(gg)], axis=-1).astype(np.float32)
+                                 .reshape(N_TEST * T, -1))
+            pa, pc = agent.actor_network.state_dict(), agent.critic_network.state_dict()       # downloads the weights
+            amax = float(env.env_params['action_max'])
+
+            def trunk(p, h):
+                for k in ("fc1", "fc2", "fc3"):
+                    h = F.relu(F.linear(h, p[k + ".weight"], p[k + ".bias"]))
+                return h
+
+            with torch.no_grad():
+                pi = amax * torch.tanh(F.linear(trunk(pa, x), pa["action_out.weight"], pa["action_out.bias"]))
+            u = (pi / amax).requires_grad_(True)
+            q = F.linear(trunk(pc, torch.cat([x, u], dim=1)), pc["q_out.weight"], pc["q_out.bias"])
+            (dq_du,) = torch.autograd.grad(q.sum(), u)
+            return syn.episode_signal_summary(syn.episode_signal_stats(pi.numpy().reshape(N_TEST, T, -1), dq_du.numpy().reshape(N_TEST, T, -1),
+                                                                       actions, amax, action_l2=agent.args.action_l2))
+        return flags
+
+    work = {"metrics": work_metrics, "critic": work_critic, "policy": work_policy, "signal": work_signal}[audit]
     for _ in range(2):
         work()
     torch.cuda.synchronize()
