@@ -67,8 +67,9 @@ class PickScriptDesc(C.Structure):
                 ("grasp", C.c_double * 3), ("open", C.c_double)]
 
 
+NET_ACTOR, NET_CRITIC, NET_ACTOR_TARGET, NET_CRITIC_TARGET = 0, 1, 2, 3      # HP_NET_*: an agent's four parameter sets
 ENV_POINT_MASS = 1
-ENV_PUSH_BLOCK = 2      # HP_ENV_PUSH_BLOCK
+ENV_PUSH_BLOCK = 2     # HP_ENV_PUSH_BLOCK
 ENV_PICK_PLACE = 3      # HP_ENV_PICK_PLACE
 EPISODE_STATS, EPISODE_SUMMARY, EPISODE_MAX_GOAL_DIM = 6, 6, 256   # HP_EPISODE_STATS, HP_EPISODE_SUMMARY, HP_EPISODE_MAX_GOAL_DIM
 CRITIC_STATS = 6       # HP_CRITIC_STATS: the columns of synthetic.CRITIC_STATS
@@ -481,7 +482,10 @@ class Context:
         (hp_ctx_borrow_stream / hp_ctx_return_stream): `with ctx.torch_bridge(): ...`.  The launches inside land in torch's
         stream order -- the caching allocator's assumption for memory it handed out, and what the consumer of the outputs runs
         in -- behind what the context's own stream held; the own stream catches up lazily when it is next used, so a fused
-        learner on the same context keeps its stream and its cached graphs.  No host synchronisation either way."""
+        learner on the same context keeps its stream and its cached graphs.  No host synchronisation either way.  The calling
+        thread holds the context's (recursive) lock for the whole `with` body: another thread's library call on this context, a
+        feeder's store for one, waits until the body ends.  A failing return of the stream raises, unless the body is already
+        raising: then the body's error stands and the return's is attached to it as a note."""
         import contextlib
 
         import torch
@@ -492,8 +496,12 @@ class Context:
             check(self.lib.hp_ctx_borrow_stream(self.h, cur))
             try:
                 yield
-            finally:
-                self.lib.hp_ctx_return_stream(self.h)
+            except BaseException as e:
+                status = self.lib.hp_ctx_return_stream(self.h)
+                if status and hasattr(e, "add_note"):
+                    e.add_note(f"torch_bridge: and the borrowed stream was not returned (hp_status {status})")
+                raise
+            check(self.lib.hp_ctx_return_stream(self.h))
         return bridge()
 
     def synchronize(self):

@@ -12,8 +12,9 @@ pieces on the hot path:
     save_checkpoint()                 :158-161  (same 5-element list, same state_dict keys)
 
 plus `train_cycle(episode_batch)`: lines :143-150 (store -> normalizer -> n_batches updates ->
-polyak) as ONE cached hipGraph launch.  The rollout half (`learn`, :92-161) is host-side glue
-around any gym-GoalEnv-like object and lives in `learn()`.
+polyak) as ONE cached hipGraph launch.  `learn()` (:92-161) is the epoch loop around both halves; the rollout half -- policy
+calls, exploration, collection from host or device environments, evaluation -- is rollouts.py, the episode audits are
+episode_audit.py, and the agent inherits both.
 
 Data never leaves the device between sampling and the optimizer step; the methods that
 return numpy (`buffer.sample`, normalizer attributes, `state_dict`) copy out on demand.
@@ -22,6 +23,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import sys
+import threading
 import time
 from datetime import datetime
 
@@ -30,17 +33,18 @@ import torch
 
 from . import _lib
 from . import random as _random
+from ._lib import NET_ACTOR, NET_ACTOR_TARGET, NET_CRITIC, NET_CRITIC_TARGET      # (callers import them from here)
+from .arguments import Args
 from .episode_audit import EpisodeAudit
 from .her import her_sampler
 from .models import actor, critic
 from .normalizer import normalizer
 from .replay_buffer import replay_buffer
+from .rollouts import Rollouts
 from .utils import Communicator
 
-NET_ACTOR, NET_CRITIC, NET_ACTOR_TARGET, NET_CRITIC_TARGET = 0, 1, 2, 3
 
-
-class ddpg_agent(EpisodeAudit):
+class ddpg_agent(Rollouts, EpisodeAudit):
     def __init__(self, args, env, env_params, comm: Communicator | None = None, ctx=None, rng=None):
         self.savetime = 0
         self.args = args
@@ -55,6 +59,11 @@ class ddpg_agent(EpisodeAudit):
         self.rollout_form = None         # 'fused' | 'stepped': how the most recent wave of collect_episodes_device was collected
         self.rollout_launches = None     # rollout launches of the most recent collect_episodes_device call (fused form)
         self.rollout_reason = None       # ... and, when stepped, why (device_env.fused_rollout_reason)
+        self._slab8 = None               # whether policy calls are the one-launch slab kernel (_slab_shaped asks once)
+        self._demo_preload_pending = False     # demo_source='device' with args.device_reset: the preload waits for learn()
+        self.demo_stats = None           # demo_source='device': {'kept', 'attempted', 'launches'} of the generated demonstrations
+        self.resumed_at = None           # (epoch, cycle) of the training state most recently loaded
+        self._state_saves = 0            # saves of _save_epoch_state since the base was last rewritten
         self.env_params = env_params
         self.ctx = ctx or _lib.Context.default()
         self.lib = self.ctx.lib
@@ -111,25 +120,22 @@ class ddpg_agent(EpisodeAudit):
             self._native_comm = self.comm.attach_native(self.ctx)
             if self._native_comm is not None:
                 _lib.check(self.lib.hp_agent_set_comm(self.h, self._native_comm))
-        self._grad_mean = str(getattr(args, "grad_reduce", "sum")).lower() == "mean"
-        if getattr(args, "grad_reduce", "sum") not in ("sum", "mean"):
+        if self._arg("grad_reduce") not in ("sum", "mean"):
             raise ValueError("grad_reduce must be 'sum' (reference semantics) or 'mean'")
+        self._grad_mean = self._arg("grad_reduce") == "mean"
         _lib.check(self.lib.hp_agent_set_grad_reduce(self.h, int(self._grad_mean)))
         self._broadcast_params(self.comm)                       # sync_networks x2 (ddpg_agent.py:27-28)
         _lib.check(self.lib.hp_agent_sync_targets(self.h))      # targets := online (ddpg_agent.py:33-34)
         # her sampler + replay buffer (ddpg_agent.py:45-47)
         reward_func = getattr(self.env, "compute_reward", None)
+        owner = getattr(reward_func, "__self__", None)      # an environment that states its own threshold / reward type keeps it
         self.her_module = her_sampler(args.replay_strategy, args.replay_k, reward_func,
-                                      distance_threshold=None if reward_func is not None and hasattr(
-                                          getattr(reward_func, "__self__", None), "distance_threshold")
-                                      else getattr(args, "distance_threshold", 0.05),
-                                      reward_type=None if reward_func is not None and hasattr(
-                                          getattr(reward_func, "__self__", None), "reward_type")
-                                      else getattr(args, "reward_type", "sparse"), rng=self.rng,
-                                      goal_dim=env_params['goal'])
+                                      distance_threshold=None if hasattr(owner, "distance_threshold") else self._arg("distance_threshold"),
+                                      reward_type=None if hasattr(owner, "reward_type") else self._arg("reward_type"),
+                                      rng=self.rng, goal_dim=env_params['goal'])
         self.buffer = replay_buffer(self.env_params, self.args.buffer_size, self.her_module.sample_her_transitions,
                                     rng=self.rng, ctx=self.ctx)
-        if getattr(self.args, "add_demo", False):
+        if self._arg("add_demo"):
             self._init_demo_buffer()
         # normalizers (ddpg_agent.py:52-53)
         self.o_norm = normalizer(size=env_params['obs'], default_clip_range=self.args.clip_range, ctx=self.ctx,
@@ -137,9 +143,9 @@ class ddpg_agent(EpisodeAudit):
         self.g_norm = normalizer(size=env_params['goal'], default_clip_range=self.args.clip_range, ctx=self.ctx,
                                  comm=self.comm)
         self._norm_stage = None          # staging buffer of _update_normalizer(episode_batch)
-        import threading
         self._pending_updates = 0              # argument-less _update_network() calls not issued yet (_lib.py: deferred updates)
         self._pending_parked = False           # their last flush failed: not retried until the caller asks (see _flush_updates)
+        self._pending_site = "?"               # where the first of them was called: named if their flush fails
         self._defer_updates = os.environ.get("RLARM_DEFER_UPDATES", "1") != "0"
         self._stage_lock = threading.RLock()   # orders "store a wave, then sample ITS staged episodes" across feeder threads
         self.success_rates = []
@@ -150,6 +156,20 @@ class ddpg_agent(EpisodeAudit):
         self.actor_signal_audit = []     # args.audit_actor_signal: one dict per epoch, keyed by synthetic.SIGNAL_STATS
         self._actor_signal_pending = None
         self.model_path = os.path.join(self.args.save_dir, self.args.env_name)
+
+    def _arg(self, name):
+        """An optional argument: the caller's `args` value where it has one (the reference's Args lacks the newer fields), else the
+        default `arguments.Args` states for that field, else None (`state_path`, `resume`: fields Args does not have)."""
+        if hasattr(self.args, name):
+            return getattr(self.args, name)
+        field = Args.__dataclass_fields__.get(name)
+        return field.default if field is not None else None
+
+    @property
+    def _library_exchanges(self):
+        """Whether update sequences and cycles are the library's own launches: a single rank, or ranks whose gradients the library
+        exchanges itself (RCCL or peer memory attached).  False: collectives go through torch.distributed from a host-driven loop."""
+        return not self.comm.active or self._native_comm is not None or self._peer is not None
 
     def close_comm(self):
         """Detach and destroy the library-side RCCL communicator (call on every rank before
@@ -278,10 +298,9 @@ class ddpg_agent(EpisodeAudit):
         calls that follow it, as soon as anything else touches the library or `n_batches` of them have come (_lib.py,
         "deferred updates"): the same updates bit for bit, 40.5 instead of 51 us each at batch 256."""
         if n_updates is None:
-            if self._defer_updates and (not self.comm.active or self._native_comm is not None or self._peer is not None):
+            if self._defer_updates and self._library_exchanges:
                 with _lib.pending_lock:
                     if self._pending_updates == 0:      # where the first of these deferred calls was made: named if their flush fails
-                        import sys
                         f = sys._getframe(1)
                         self._pending_site = f"{f.f_code.co_filename}:{f.f_lineno}"
                     self._pending_updates += 1
@@ -325,7 +344,7 @@ class ddpg_agent(EpisodeAudit):
                 except Exception as e:
                     self._pending_updates += n                 # nothing of this chunk was enqueued: still owed ...
                     self._pending_parked = True                # ... but not retried behind the caller's back
-                    note = (f"deferred _update_network() x {n}, first called at {getattr(self, '_pending_site', '?')} "
+                    note = (f"deferred _update_network() x {n}, first called at {self._pending_site} "
                             "(issued by a later library call, _lib.py 'deferred updates')")
                     if hasattr(e, "add_note"):
                         e.add_note(note)
@@ -354,7 +373,7 @@ class ddpg_agent(EpisodeAudit):
 
     def _issue_updates(self, n_updates):
         fp, sq = float(self.her_module.future_p), float(self.her_module.sq_threshold)
-        if not self.comm.active or self._native_comm is not None or self._peer is not None:
+        if self._library_exchanges:
             # single rank, or the library exchanges the gradients itself between backward and Adam
             _lib.check(self.lib.hp_agent_sample_and_update(*self._handles(), fp, sq, int(n_updates)))
             return
@@ -423,7 +442,7 @@ class ddpg_agent(EpisodeAudit):
         communicator; otherwise the loop is driven from the host."""
         n_batches = int(n_batches or self.args.n_batches)
         device_block = hasattr(episode_batch, "block") and hasattr(episode_batch, "numpy")    # device_env.DeviceEpisodes
-        if self.comm.active and self._native_comm is None and self._peer is None:   # collectives on torch.distributed: host-driven loop
+        if not self._library_exchanges:      # collectives on torch.distributed: host-driven loop
             if device_block:
                 with self._stage_lock:       # store + normalizer update on the episodes the store just staged, as one unit
                     self.buffer.store_episode(episode_batch)
@@ -453,7 +472,7 @@ class ddpg_agent(EpisodeAudit):
         registered shared-memory slot (no CPU copy), the normalizer samples the staged episodes, the updates replay their
         cached graph.  Asynchronous; ranks of a data-parallel group call it in step like train_cycle."""
         n_batches = int(n_batches or self.args.n_batches)
-        if not self.comm.active or self._native_comm is not None or self._peer is not None:
+        if self._library_exchanges:
             # the whole cycle as one cached graph behind the DMA (hp_agent_train_cycle_pinned): same launches as train_cycle
             with self._stage_lock:
                 feeder.train_cycle_wave(slot, n_batches)
@@ -470,10 +489,9 @@ class ddpg_agent(EpisodeAudit):
         capture, nothing executes).  {'open': [...], 'prologue': [...], 'updates': [[...] per update], 'close': [...]}."""
         self._flush_updates()
         n = int(n_updates or self.args.n_batches)
-        host_loop = self.comm.active and self._native_comm is None and self._peer is None
         buf = C.create_string_buffer(1 << 16)
         _lib.check(self.lib.hp_agent_update_kernels(*self._handles(), float(self.her_module.future_p),
-                                                    float(self.her_module.sq_threshold), n, 1 if host_loop else 0, buf, len(buf)))
+                                                    float(self.her_module.sq_threshold), n, 0 if self._library_exchanges else 1, buf, len(buf)))
         out, cur = {"open": [], "prologue": [], "updates": [], "close": []}, None
         for tok in buf.value.decode().split(","):
             if tok == "#update":
@@ -521,7 +539,7 @@ class ddpg_agent(EpisodeAudit):
         os.makedirs(saved_dir, exist_ok=True)
         np.save(saved_dir + str(self.args.seed) + '_' + str(self.args.add_demo) + '_success_rates.npy',
                 np.array(self.success_rates))
-        if getattr(self.args, "eval_metrics", False):      # [evaluations, 6] in the columns of synthetic.EPISODE_SUMMARY
+        if self._arg("eval_metrics"):      # [evaluations, 6] in the columns of synthetic.EPISODE_SUMMARY
             from .synthetic import EPISODE_SUMMARY
             np.save(saved_dir + str(self.args.seed) + '_' + str(self.args.add_demo) + '_eval_metrics.npy',
                     np.array([[m[k] for k in EPISODE_SUMMARY] for m in self.eval_metrics], dtype=np.float64).reshape(-1, len(EPISODE_SUMMARY)))
@@ -540,19 +558,20 @@ class ddpg_agent(EpisodeAudit):
         their device block, in order, as ONE store_episode call like the file's -- the device path has no size limit of its
         own -- and fewer kept than asked is an error.  If the environment is not reset on the device yet but args.device_reset
         asks for it, the preload waits for learn(), which enables the reset first."""
-        source = getattr(self.args, "demo_source", "file")
+        arg = lambda name: ddpg_agent._arg(self, name)      # unbound: any object with `args` and `buffer` can be preloaded
+        source = arg("demo_source")
         if source not in ("file", "device"):
             raise ValueError("demo_source must be 'file' (the reference's preload) or 'device'")
         if source == "device":
             from .device_env import generate_demos
             if self.vec_env is None or not getattr(self.vec_env, "is_native_device_env", False):
                 raise ValueError("demo_source='device' needs a native vectorised device environment (device_env.py)")
-            if getattr(self.vec_env, "reset_streams", None) is None and getattr(self.args, "device_reset", False):
+            if getattr(self.vec_env, "reset_streams", None) is None and arg("device_reset"):
                 self._demo_preload_pending = True
                 return
             self._demo_preload_pending = False
-            want = int(getattr(self.args, "demo_episodes", 1000))
-            demos = generate_demos(self.vec_env, want, max_episodes=int(getattr(self.args, "demo_max_episodes", 10000)), ctx=self.ctx)
+            want = int(arg("demo_episodes"))
+            demos = generate_demos(self.vec_env, want, max_episodes=int(arg("demo_max_episodes")), ctx=self.ctx)
             self.demo_stats = {"kept": demos.kept, "attempted": demos.attempted, "launches": demos.launches}
             if demos.kept < want:
                 raise RuntimeError(f"demo_source='device': only {demos.kept} of {want} scripted episodes succeeded in "
@@ -633,11 +652,11 @@ class ddpg_agent(EpisodeAudit):
         saves between rewrite ONE cumulative delta beside it against that base; 0: every save is full."""
         from . import train_state as ts
         base = ts.rank_path(state_path, self.comm.rank)
-        every = int(getattr(self.args, "state_full_every", 0) or 0)
+        every = int(self._arg("state_full_every") or 0)
         if every <= 0:
             return self.save_training_state(base, epoch=epoch)
         delta = ts.rank_path(ts.delta_path(state_path), self.comm.rank)
-        n = getattr(self, "_state_saves", 0)
+        n = self._state_saves
         self._state_saves = n + 1
         if n % every != 0:
             try:
@@ -654,216 +673,6 @@ class ddpg_agent(EpisodeAudit):
             os.unlink(delta)
         return out
 
-    # ------------------------------------------------------------------ rollout side (host glue)
-    def _preproc_inputs(self, obs, g):
-        inputs = np.concatenate([self.o_norm.normalize(obs), self.g_norm.normalize(g)])
-        return torch.tensor(inputs, dtype=torch.float32).unsqueeze(0)
-
-    def act(self, obs, g, target=False, clip_obs=0.0):
-        """_preproc_inputs (:163-171) + actor (:114-116) for a stack of environments in ONE device call: obs [n, obs] and
-        g [n, goal] float64 (or single rows) -> actions [n, action] float32.  clip_obs > 0 also clips the raw values to
-        +-clip_obs first, which is what the checkpoint reader demo_push.py:15-22 does (the rollouts do not)."""
-        obs, g = _lib.as_f64(obs), _lib.as_f64(g)
-        o2, g2 = obs.reshape(-1, obs.shape[-1]), g.reshape(-1, g.shape[-1])
-        if o2.shape[0] != g2.shape[0]:
-            raise ValueError("act: observation and goal stacks differ in length")
-        out = np.empty((o2.shape[0], self.env_params['action']), np.float32)
-        d = C.c_double
-        _lib.check(self.lib.hp_agent_act(self.h, self.o_norm.h, self.g_norm.h, NET_ACTOR_TARGET if target else NET_ACTOR,
-                                         _lib.ptr(o2, d), _lib.ptr(g2, d), o2.shape[0], float(clip_obs),
-                                         _lib.ptr(out, C.c_float)))
-        return out.reshape(obs.shape[:-1] + (out.shape[-1],))
-
-    def act_device(self, obs_t, g_t, target=False, clip_obs=0.0):
-        """`act` for float64 device tensors [n, obs] / [n, goal] (or single rows): the same kernels on the tensors' memory, a
-        float32 device tensor back.  Runs in torch's current stream order; no copy, no synchronisation."""
-        if obs_t.dtype != torch.float64 or g_t.dtype != torch.float64 or not obs_t.is_cuda or not g_t.is_cuda:
-            raise ValueError("act_device: float64 tensors on the context's device expected")
-        o2 = obs_t.reshape(-1, obs_t.shape[-1]).contiguous()
-        g2 = g_t.reshape(-1, g_t.shape[-1]).contiguous()
-        if o2.shape[0] != g2.shape[0]:
-            raise ValueError("act: observation and goal stacks differ in length")
-        out = torch.empty((o2.shape[0], self.env_params['action']), dtype=torch.float32, device=o2.device)
-        self._flush_updates()
-        with self.ctx.torch_bridge():
-            _lib.check(self.lib.hp_agent_act_dev(self.h, self.o_norm.h, self.g_norm.h, NET_ACTOR_TARGET if target else NET_ACTOR,
-                                                 C.c_void_p(o2.data_ptr()), C.c_void_p(g2.data_ptr()), o2.shape[0],
-                                                 float(clip_obs), C.c_void_p(out.data_ptr())))
-        return out.reshape(tuple(obs_t.shape[:-1]) + (out.shape[-1],))
-
-    def enable_explore_streams(self, base_seed=None, seeds=None):
-        """Give every environment of the vectorised simulator its own exploration stream (random.DeviceRandomStreams,
-        hp_rollout_step_streams): env i draws `_select_actions` out of `RandomState(seeds[i])` alone -- n reference workers
-        (one environment and one stream seeded `seed + rank` each, train.py:34-39) side by side -- so its trajectory depends
-        neither on n_envs nor on the wave it is part of, and the draw of a timestep is one wave per environment instead of one
-        wave for all.  Default seeds: base_seed + i with base_seed = args.seed + rank * n_envs, distinct over all environments
-        of all ranks.  `self.rng` then serves the learner alone (overflow slots, HER indices)."""
-        if self.vec_env is None:
-            raise ValueError("enable_explore_streams: the agent has no vectorised device environment")
-        n = int(self.vec_env.n_envs)
-        if seeds is None and base_seed is None:
-            base_seed = int(self.args.seed) + self.comm.rank * n
-        self.explore_streams = _random.DeviceRandomStreams(n, seeds=seeds, base_seed=base_seed, ctx=self.ctx)
-        return self.explore_streams
-
-    def collect_episodes_device(self, vec_env=None, n_rollouts=None, epoch=0, explore=True, success_out=None, stats_out=None):
-        """`collect_episodes` for a vectorised device environment (device_env.py): `n_rollouts` episodes (default: one wave of
-        vec_env.n_envs) on torch's current stream, no host copy and no host wait per timestep, in one of three forms with the
-        same bits; `self.rollout_form` / `self.rollout_reason` say which the call took and why, `self.rollout_launches` how many
-        launches a fused call was.
-          stepped (`_collect_wave_stepped`): waves of n_envs, T timesteps of two launches each (csrc/rollout.hip).
-          fused, one launch per wave (`_collect_wave_fused`): a native environment, a slab-shaped agent and draws that are
-            independent across environments (`device_env.fused_rollout_reason`).
-          fused, all waves in one launch (`_collect_all_waves`): the same with an environment that is reset on the device
-            (`vec_env.enable_device_reset()`); calls no `vec_env.reset()`, hands `success_out` one tensor of n_rollouts flags,
-            and the launch cap may make a few launches of it.
-        Exploration (:174-184, the +-0.15 clip from epoch 100) is drawn on the device from `self.rng`, for env 0 .. n-1 in turn
-        like the host lockstep path -- or, after `enable_explore_streams`, for every environment from its own stream (a wave of
-        k < n_envs rows advances the streams of those k only).  Returns a `DeviceEpisodes` handle for `train_cycle` /
-        `buffer.store_episode`; `.numpy()` gives the four arrays `collect_episodes` returns.
-        `stats_out`: a list that receives ONE device tensor [n_rollouts, 6] per call, the metrics of this call's episodes
-        (`DeviceEpisodes.stats` at `vec_env.distance_threshold`: one more small launch behind the rollout, in any of the three
-        forms, no host wait); with None nothing more is launched."""
-        from .device_env import DeviceEpisodes, binomial1_qn, fused_rollout_reason
-        vec_env = vec_env or self.vec_env
-        n_total = int(n_rollouts or vec_env.n_envs)
-        eps = self._rollouts.get(n_total)
-        if eps is None:
-            eps = self._rollouts[n_total] = DeviceEpisodes(self.ctx, self.buffer._dev, n_total)
-        qn = binomial1_qn(self.args.random_eps)[0] if explore else 1.0
-        clip_abs = 0.15 if epoch >= 100 else 0.0                                  # ddpg_agent.py:118-119
-        self._flush_updates()
-        streams = self.explore_streams
-        if streams is not None and len(streams) != vec_env.n_envs:
-            raise ValueError(f"collect_episodes_device: {len(streams)} exploration streams for {vec_env.n_envs} environments")
-        self.rollout_reason = fused_rollout_reason(getattr(vec_env, "is_native_device_env", False), self._slab_shaped(), explore,
-                                                   streams is not None)
-        self.rollout_form = 'fused' if self.rollout_reason is None else 'stepped'
-        self.rollout_launches = 0 if self.rollout_form == 'fused' else None
-        # what every entry takes behind its handles: the explore flag, the constants of _select_actions, the clip
-        how = (1 if explore else 0, float(self.args.noise_eps), float(self.args.random_eps), qn, clip_abs)
-        if self.rollout_form == 'fused' and getattr(vec_env, "reset_streams", None) is not None:
-            success = self._collect_all_waves(vec_env, eps, n_total, streams, how)
-            if success_out is not None:
-                success_out.append(success)
-            if stats_out is not None:
-                stats_out.append(eps.stats(vec_env.distance_threshold, 0, n_total))
-            return eps
-        done = 0
-        while done < n_total:
-            k = min(vec_env.n_envs, n_total - done)
-            o = vec_env.reset() if k == vec_env.n_envs else vec_env.reset(k)
-            if self.rollout_form == 'fused':
-                success = self._collect_wave_fused(vec_env, eps, done, k, streams, how)
-            else:
-                success = self._collect_wave_stepped(vec_env, eps, done, k, o, streams, how)
-            if success_out is not None:
-                success_out.append(success)
-            done += k
-        if explore and streams is None:     # (the streams keep no host copy of their cached normals: nothing to invalidate)
-            self.rng.mark_normals_drawn()
-        if stats_out is not None:
-            stats_out.append(eps.stats(vec_env.distance_threshold, 0, n_total))
-        return eps
-
-    def _collect_all_waves(self, vec_env, eps, n_total, streams, how):
-        """All `n_total` episodes as one launch (hp_rollout_waves), or the few the launch cap dictates; the environments are
-        reset inside it.  Returns the n_total success flags."""
-        env = vec_env.env_desc()
-        success = torch.empty(n_total, dtype=torch.float32, device=vec_env.device)
-        launches = C.c_int32()
-        with self.ctx.torch_bridge():
-            _lib.check(self.lib.hp_rollout_begin(eps.h, 0, n_total))
-            _lib.check(self.lib.hp_rollout_waves(eps.h, self.h, self.o_norm.h, self.g_norm.h,
-                                                 streams.h if streams is not None else None, vec_env.reset_streams.h,
-                                                 C.byref(env), vec_env.n_envs, *how, C.c_void_p(success.data_ptr()),
-                                                 C.byref(launches)))
-        self.rollout_launches = int(launches.value)
-        vec_env.active = (n_total - 1) % vec_env.n_envs + 1      # the environments of the last wave
-        return success
-
-    def _collect_wave_fused(self, vec_env, eps, first, k, streams, how):
-        """Episodes [first, first + k) out of the k environments just reset, as one launch (hp_rollout_episodes).  Returns their
-        success flags."""
-        env = vec_env.env_desc()
-        success = torch.empty(k, dtype=torch.float32, device=vec_env.device)
-        with self.ctx.torch_bridge():
-            _lib.check(self.lib.hp_rollout_begin(eps.h, first, k))
-            _lib.check(self.lib.hp_rollout_episodes(eps.h, self.h, self.o_norm.h, self.g_norm.h,
-                                                    streams.h if streams is not None else None, C.byref(env), *how,
-                                                    C.c_void_p(success.data_ptr())))
-        self.rollout_launches += 1
-        return success
-
-    def _collect_wave_stepped(self, vec_env, eps, first, k, o, streams, how):
-        """Episodes [first, first + k) out of the k environments just reset (`o`: what the reset returned), two launches per
-        timestep around `vec_env.step` and one closing record.  Returns the success flags of the last step."""
-        p = lambda t: C.c_void_p(t.data_ptr())
-        step, stream_h = ((self.lib.hp_rollout_step_streams, streams.h) if streams is not None
-                          else (self.lib.hp_rollout_step, self.rng.h))
-        actions = torch.empty((k, int(self.env_params['action'])), dtype=torch.float32, device=o['observation'].device)
-        with self.ctx.torch_bridge():       # the whole wave in torch's stream order, between the environment's own kernels
-            _lib.check(self.lib.hp_rollout_begin(eps.h, first, k))
-            for t in range(int(self.env_params['max_timesteps'])):
-                obs, ag, g = (o[key].contiguous() for key in ('observation', 'achieved_goal', 'desired_goal'))
-                _lib.check(step(eps.h, self.h, self.o_norm.h, self.g_norm.h, stream_h, t, p(obs), p(ag), p(g), *how, p(actions)))
-                o, _, _, info = vec_env.step(actions)
-            obs, ag = o['observation'].contiguous(), o['achieved_goal'].contiguous()
-            _lib.check(self.lib.hp_rollout_finish(eps.h, p(obs), p(ag)))
-        return info['is_success']
-
-    def _slab_shaped(self):
-        """Whether policy calls on this agent are the one-launch slab kernel (hp_agent_engine reports the 4x4x1 slab engine)."""
-        if getattr(self, "_slab8", None) is None:
-            e = C.c_int32()
-            _lib.check(self.lib.hp_agent_engine(self.h, C.byref(e), None, None))
-            self._slab8 = e.value == 8
-        return self._slab8
-
-    def _select_actions(self, pi):
-        """ddpg_agent.py:174-184: Gaussian noise, clip, epsilon-random (numpy global RNG, like the reference).  `action`
-        stays the float32 array the policy returned and is updated in place, so every step rounds to float32 exactly
-        where the reference's `action += ...` does."""
-        amax = self.env_params['action_max']
-        action = (pi.cpu().numpy() if isinstance(pi, torch.Tensor) else np.array(pi, dtype=np.float32)).squeeze()
-        action += self.args.noise_eps * amax * np.random.randn(*action.shape)
-        action = np.clip(action, -amax, amax)
-        random_actions = np.random.uniform(low=-amax, high=amax, size=self.env_params['action'])
-        action += np.random.binomial(1, self.args.random_eps, 1)[0] * (random_actions - action)
-        return action
-
-    def collect_episodes(self, n_rollouts, epoch=0, explore=True):
-        """Rollout half of learn() (:101-137) for `n_rollouts` episodes; returns the four episode arrays.  The
-        environments in self.envs are stepped in lockstep, one batched policy call per timestep; with a single
-        environment this is the reference's loop, including the order of its draws from numpy's global stream."""
-        T = int(self.env_params['max_timesteps'])
-        mb = ([], [], [], [])
-        done = 0
-        while done < n_rollouts:
-            envs = self.envs[:n_rollouts - done]
-            k = len(envs)
-            first = [env.reset() for env in envs]
-            obs = [o['observation'] for o in first]
-            ag = [o['achieved_goal'] for o in first]
-            g = [o['desired_goal'] for o in first]
-            ep = [([], [], [], []) for _ in envs]
-            for _t in range(T):
-                pi = self.act(np.stack(obs), np.stack(g))
-                for i, env in enumerate(envs):
-                    action = self._select_actions(pi[i]) if explore else pi[i].astype(np.float64)
-                    if epoch >= 100:
-                        action = np.clip(action, -0.15, 0.15)            # ddpg_agent.py:118-119
-                    observation_new, _, _, info = env.step(action)
-                    for dst, v in zip(ep[i], (obs[i], ag[i], g[i], action)):
-                        dst.append(np.array(v, dtype=np.float64))
-                    obs[i], ag[i] = observation_new['observation'], observation_new['achieved_goal']
-            for i in range(k):
-                ep[i][0].append(np.array(obs[i], dtype=np.float64)); ep[i][1].append(np.array(ag[i], dtype=np.float64))
-                for dst, src in zip(mb, ep[i]):
-                    dst.append(src)
-            done += k
-        return [np.array(a) for a in mb]
-
     def learn(self):
         """ddpg_agent.py:92-161 with the learner half on the device.
 
@@ -872,39 +681,51 @@ class ddpg_agent(EpisodeAudit):
         is handed to the device for the learner phase of every cycle and taken back before the next rollout, so a run
         seeded like train.py:34-39 consumes exactly the reference's random words in the reference's order (with one
         environment; a list of environments is stepped in lockstep, which reorders the exploration draws).  The
-        hand-back synchronises, which the next rollout needs anyway: it evaluates the updated actor."""
-        share = bool(getattr(self.args, "share_numpy_stream", True))
+        hand-back synchronises, which the next rollout needs anyway: it evaluates the updated actor.
+
+        With a vectorised device environment every draw of a cycle comes from the device stream, so the stream stays on the device
+        for the whole run: numpy's state is handed over once and handed back at the end and wherever a training state is saved,
+        and nothing synchronises between the rollout and the learner phase of a cycle."""
+        share, device = bool(self._arg("share_numpy_stream")), self.vec_env is not None
         # optional: args.resume = a training state to continue from (ddpg_agent.py:54-62), args.state_path = where to save one
         # after every epoch's evaluation; each rank has its own file (its buffer is its shard of the episodes)
-        state_path, resume, first_epoch = getattr(self.args, "state_path", None), getattr(self.args, "resume", None), 0
-        if self.vec_env is not None and getattr(self.args, "explore_streams", False) and self.explore_streams is None:
+        state_path, resume, first_epoch = self._arg("state_path"), self._arg("resume"), 0
+        if device and self._arg("explore_streams") and self.explore_streams is None:
             self.enable_explore_streams()    # args.explore_streams: before a resume, whose state carries the streams' states
-        if self.vec_env is not None and getattr(self.args, "device_reset", False) and getattr(self.vec_env, "reset_streams", None) is None:
+        if device and self._arg("device_reset") and getattr(self.vec_env, "reset_streams", None) is None:
             self.vec_env.enable_device_reset(self.ctx)   # args.device_reset: likewise before a resume
-        if getattr(self, "_demo_preload_pending", False):
+        if self._demo_preload_pending:
             self._init_demo_buffer()                     # demo_source='device': generated now that the reset is on the device
         if resume:
             self._resume_state(resume)
             first_epoch = self.resumed_at[0]
         print("initial buffer size:", self.buffer.current_size)                  # :97
-        if self.vec_env is not None:
-            return self._learn_device(share, state_path, first_epoch)
-        audit, audit_signal = bool(getattr(self.args, "audit_policy", False)), bool(getattr(self.args, "audit_actor_signal", False))
+
+        def hand_over():
+            if share:
+                self.rng.set_state(np.random.get_state())
+
+        def hand_back():
+            if share:
+                np.random.set_state(self.rng.get_state())
+
+        collect = self.collect_episodes_device if device else self.collect_episodes
+        if device:
+            hand_over()
         for epoch in range(first_epoch, self.args.n_epochs):
             start = time.time()
             episodes = None
             for _ in range(self.args.n_cycles):
-                episodes = self.collect_episodes(self.args.num_rollouts_per_mpi, epoch)
-                if share:
-                    self.rng.set_state(np.random.get_state())
+                episodes = collect(n_rollouts=self.args.num_rollouts_per_mpi, epoch=epoch)
+                if not device:
+                    hand_over()
                 self.train_cycle(episodes)
-                if share:
-                    np.random.set_state(self.rng.get_state())
-            if audit and episodes is not None:
-                self._policy_audit_pending = episodes    # host arrays: audited behind _finish_epoch's synchronise
-            if audit_signal and episodes is not None:
-                self._actor_signal_pending = episodes
-            self._finish_epoch(epoch, start, state_path)
+                if not device:
+                    hand_back()
+            self._queue_epoch_audits(episodes)       # args.audit_policy / args.audit_actor_signal: recorded by _finish_epoch
+            self._finish_epoch(epoch, start, state_path, before_save=hand_back if device else None)
+        if device:
+            hand_back()
 
     def _finish_epoch(self, epoch, start, state_path, before_save=None):
         """What closes an epoch of learn() on either path (:151-161): wait for its cycles, print the time they took, evaluate,
@@ -923,139 +744,6 @@ class ddpg_agent(EpisodeAudit):
             if before_save is not None:
                 before_save()
             self._save_epoch_state(state_path, epoch + 1)
-
-    def _learn_device(self, share, state_path, first_epoch):
-        """learn() with a vectorised device environment: every draw of a cycle -- exploration, overflow slots, HER indices --
-        comes from the device stream, so the single stream stays on the device for the whole run: numpy's state is handed over
-        once here and handed back at the end and wherever a training state is saved (not twice per cycle), and nothing
-        synchronises between the rollout and the learner phase of a cycle."""
-        def hand_back():
-            if share:
-                np.random.set_state(self.rng.get_state())
-
-        if share:
-            self.rng.set_state(np.random.get_state())
-        audit, audit_signal = bool(getattr(self.args, "audit_policy", False)), bool(getattr(self.args, "audit_actor_signal", False))
-        for epoch in range(first_epoch, self.args.n_epochs):
-            start = time.time()
-            eps = None
-            for _ in range(self.args.n_cycles):
-                eps = self.collect_episodes_device(n_rollouts=self.args.num_rollouts_per_mpi, epoch=epoch)
-                self.train_cycle(eps)
-            if audit and eps is not None:
-                # args.audit_policy: the last cycle's exploring episodes under the networks as they now stand -- four launches behind
-                # the cycle, nothing waits; the 48 bytes are read behind _finish_epoch's synchronise
-                stats = self.episode_policy_stats(eps, first=0, n=self.args.num_rollouts_per_mpi)[0]
-                summary = torch.empty(_lib.POLICY_STATS, dtype=torch.float64, device=stats.device)
-                with self.ctx.torch_bridge():
-                    _lib.check(self.lib.hp_episode_policy_summary(self.ctx.h, C.c_void_p(stats.data_ptr()), stats.shape[0],
-                                                                  C.c_void_p(summary.data_ptr())))
-                self._policy_audit_pending = summary
-            if audit_signal and eps is not None:
-                # args.audit_actor_signal: the same episodes, three launches (dQ/du at the policy, the columns, their means)
-                # behind the cycle; nothing waits, the 48 bytes are read behind _finish_epoch's synchronise
-                stats = self.episode_signal_stats(eps, first=0, n=self.args.num_rollouts_per_mpi)[0]
-                self._actor_signal_pending = self._signal_summary(stats)
-            self._finish_epoch(epoch, start, state_path, before_save=hand_back)
-        hand_back()
-
-    def _eval_agent_device(self):
-        """_eval_agent on the device path: noise-free lockstep rollouts, the success flags of each wave's last step gathered on
-        the device and copied to the host once at the end."""
-        flags, remaining = [], int(self.args.n_test_rollouts)
-        stats = [] if getattr(self.args, "eval_metrics", False) else None
-        critic = [] if getattr(self.args, "eval_critic", False) else None
-        while remaining > 0:
-            # one call per wave; with reset on the device one call for all of them (one launch: hp_rollout_waves)
-            k = remaining if getattr(self.vec_env, "reset_streams", None) is not None else min(self.vec_env.n_envs, remaining)
-            eps = self.collect_episodes_device(n_rollouts=k, explore=False, success_out=flags, stats_out=stats)
-            if critic is not None:       # args.eval_critic: two more launches behind the call, before the next one rewrites the block
-                critic.append(self.episode_critic_stats(eps, first=0, n=k)[0])
-            remaining -= k
-        wins = torch.cat([f.reshape(-1).to(torch.float64) for f in flags])
-        if stats is None and critic is None:
-            return self._success_rate(wins.cpu().numpy())
-        # args.eval_metrics / args.eval_critic: the summaries of all evaluation episodes (hp_episode_stats_summary,
-        # hp_episode_critic_summary) ride behind the flags in the one copy to the host; what is done with the flags is unchanged
-        riders = []
-        for rows, entry, width in ((stats, self.lib.hp_episode_stats_summary, _lib.EPISODE_SUMMARY),
-                                   (critic, self.lib.hp_episode_critic_summary, _lib.CRITIC_STATS)):
-            if rows is None:
-                continue
-            rows = rows[0] if len(rows) == 1 else torch.cat(rows)
-            summary = torch.empty(width, dtype=torch.float64, device=rows.device)
-            with self.ctx.torch_bridge():
-                _lib.check(entry(self.ctx.h, C.c_void_p(rows.data_ptr()), rows.shape[0], C.c_void_p(summary.data_ptr())))
-            riders.append(summary)
-        both, n_wins = torch.cat([wins, *riders]).cpu().numpy(), wins.numel()
-        rate = self._success_rate(both[:n_wins])
-        if stats is not None:
-            self._record_eval_metrics(both[n_wins:n_wins + _lib.EPISODE_SUMMARY])
-        if critic is not None:
-            self._record_eval_critic(both[-_lib.CRITIC_STATS:])
-        return rate
-
-    def _success_rate(self, wins):
-        """The mean of this rank's success flags, averaged over the ranks"""
-        local = torch.tensor([float(np.mean(wins))], dtype=torch.float64)
-        if self.comm.world_size > 1:
-            local = local.to(f"cuda:{self.ctx.device_id}")
-        self.comm.allreduce_mean_(local)
-        return float(local.item())
-
-    def _eval_agent(self):
-        """ddpg_agent.py:280-304: success at the last step of n_test_rollouts noise-free episodes, averaged over ranks;
-        the environments in self.envs run in lockstep with one batched policy call per timestep."""
-        if self.vec_env is not None:
-            return self._eval_agent_device()
-        wins = []
-        audit = bool(getattr(self.args, "eval_critic", False))
-        metrics = bool(getattr(self.args, "eval_metrics", False)) or audit
-        ep_ag, ep_g = [], []             # args.eval_metrics: achieved goals [T + 1] and desired goals [T] of every episode
-        ep_obs, ep_act = [], []          # args.eval_critic: observations [T + 1] and actions [T] beside them
-        remaining = int(self.args.n_test_rollouts)
-        while remaining > 0:
-            envs = self.envs[:remaining]
-            first = [env.reset() for env in envs]
-            obs = [o['observation'] for o in first]
-            g = [o['desired_goal'] for o in first]
-            last = [0.0] * len(envs)
-            if metrics:
-                ags = [[np.array(o['achieved_goal'], dtype=np.float64)] for o in first]
-                gs = [[] for _ in envs]
-            if audit:
-                obss = [[np.array(o['observation'], dtype=np.float64)] for o in first]
-                acts = [[] for _ in envs]
-            for _t in range(int(self.env_params['max_timesteps'])):
-                actions = self.act(np.stack(obs), np.stack(g))
-                for i, env in enumerate(envs):
-                    observation_new, _, _, info = env.step(actions[i])
-                    if audit:
-                        acts[i].append(np.array(actions[i], dtype=np.float64))
-                        obss[i].append(np.array(observation_new['observation'], dtype=np.float64))
-                    if metrics:
-                        gs[i].append(np.array(g[i], dtype=np.float64))
-                        ags[i].append(np.array(observation_new['achieved_goal'], dtype=np.float64))
-                    obs[i], g[i] = observation_new['observation'], observation_new['desired_goal']
-                    last[i] = float(info.get('is_success', last[i]))
-            wins.extend(last)
-            if metrics:
-                ep_ag.extend(ags)
-                ep_g.extend(gs)
-            if audit:
-                ep_obs.extend(obss)
-                ep_act.extend(acts)
-            remaining -= len(envs)
-        rate = self._success_rate(wins)
-        thr = getattr(self.env, "distance_threshold", getattr(self.args, "distance_threshold", 0.05))
-        if getattr(self.args, "eval_metrics", False):
-            from .synthetic import episode_stats, episode_stats_summary
-            self._record_eval_metrics(episode_stats_summary(episode_stats(np.array(ep_ag), np.array(ep_g), thr)[0]))
-        if audit:
-            from .synthetic import episode_critic_summary
-            batch = [np.array(ep_obs), np.array(ep_ag), np.array(ep_g), np.array(ep_act)]
-            self._record_eval_critic(episode_critic_summary(self.episode_critic_stats_host(batch, thr)[0]))
-        return rate
 
     def __del__(self):
         try:

@@ -2,7 +2,7 @@
 (hp_episode_q*, hp_episode_returns*), the policy audit (hp_episode_policy*) and the actor-signal audit (hp_episode_action_grad*,
 hp_episode_signal_stats*), each on a `DeviceEpisodes` block in place or on
 host episodes that are uploaded first, and what puts an epoch's summary onto the agent's lists.  `ddpg_agent` inherits these
-methods; they use its `lib`, `ctx`, `h`, `o_norm`, `g_norm`, `args`, `env_params`, `vec_env` and `comm`."""
+methods; they use its `lib`, `ctx`, `h`, `o_norm`, `g_norm`, `args`, `_arg`, `env_params`, `vec_env` and `comm`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import NET_CRITIC, NET_CRITIC_TARGET
 
 
 def _p(t):
@@ -67,7 +68,6 @@ class EpisodeAudit:
     # ---- the two network forwards and the policy columns: one place per entry pair.  `episodes`: a DeviceEpisodes, whose
     # episodes [first, first + n) are read in place (the *_block entry); None: the uploaded arrays are (the plain entry)
     def _q(self, episodes, first, n, T, target, obs=None, g=None, act=None):
-        from .ddpg_agent import NET_CRITIC, NET_CRITIC_TARGET
         q = torch.empty((max(n, 0), T), dtype=torch.float32, device=torch.device("cuda", self.ctx.device_id))
         nets = (self.h, self.o_norm.h, self.g_norm.h, NET_CRITIC_TARGET if target else NET_CRITIC)
         with self.ctx.torch_bridge():
@@ -115,7 +115,7 @@ class EpisodeAudit:
         if distance_threshold is None:
             distance_threshold = self.vec_env.distance_threshold
         q = self.episode_q(episodes, target=target, first=first, n=n)
-        returns, stats = episodes.returns(distance_threshold, float(self.args.gamma), getattr(self.args, "reward_type", "sparse"),
+        returns, stats = episodes.returns(distance_threshold, float(self.args.gamma), self._arg("reward_type"),
                                           tail, first=first, n=n, q=q)
         return stats, q, returns
 
@@ -131,7 +131,7 @@ class EpisodeAudit:
         stats = torch.empty((n, _lib.CRITIC_STATS), dtype=torch.float64, device=g.device)
         with self.ctx.torch_bridge():
             _lib.check(self.lib.hp_episode_returns(self.ctx.h, _p(ag), _p(g), n, T, gd, float(distance_threshold),
-                                                   _reward_kind(getattr(self.args, "reward_type", "sparse")), float(self.args.gamma),
+                                                   _reward_kind(self._arg("reward_type")), float(self.args.gamma),
                                                    _tail_kind(tail), _p(returns), _p(q), _p(stats)))
         return stats.cpu().numpy(), q.cpu().numpy(), returns.cpu().numpy()
 
@@ -221,26 +221,42 @@ class EpisodeAudit:
         stats = self._signal_columns(None, 0, pi, dq_du, flat, act)
         return stats.cpu().numpy(), dq_du.cpu().numpy(), pi.cpu().numpy(), q_pi.cpu().numpy()
 
-    def _signal_summary(self, stats):
-        """The six column means of a device table of signal columns, a device tensor (hp_episode_signal_summary)"""
-        summary = torch.empty(_lib.SIGNAL_STATS, dtype=torch.float64, device=stats.device)
+    def _column_means(self, entry, rows):
+        """The column means of a per-episode table on the device, a float64 device tensor of rows.shape[1] values from one launch
+        of `entry` (hp_episode_stats_summary, hp_episode_critic_summary, hp_episode_policy_summary or hp_episode_signal_summary)"""
+        summary = torch.empty(rows.shape[1], dtype=torch.float64, device=rows.device)
         with self.ctx.torch_bridge():
-            _lib.check(self.lib.hp_episode_signal_summary(self.ctx.h, _p(stats), stats.shape[0], _p(summary)))
+            _lib.check(entry(self.ctx.h, _p(rows), rows.shape[0], _p(summary)))
         return summary
 
-    def _record_actor_signal_audit(self):
-        """args.audit_actor_signal: the epoch's pending audit -- the device path's summary (six means, already computed) or the
-        host path's episodes (audited now: `episode_signal_stats_host`) -- averaged over the ranks like the success rate, onto
-        `actor_signal_audit`"""
-        pending, self._actor_signal_pending = self._actor_signal_pending, None
-        if pending is None:
+    def _queue_epoch_audits(self, episodes):
+        """args.audit_policy / args.audit_actor_signal: queue an epoch's last exploring episodes for `_record_policy_audit` /
+        `_record_actor_signal_audit`, under the networks as they now stand.  A `DeviceEpisodes`: the columns and their means are
+        launched now behind the cycle (four launches for the policy, then three for the signal: dQ/du at the policy, the columns,
+        their means), nothing waits, and the summary tensor is kept -- its 48 bytes are read behind the epoch's synchronise.
+        Host arrays are kept as they are and audited there."""
+        if episodes is None:
             return
+        span = dict(first=0, n=len(episodes)) if hasattr(episodes, "block") else None      # a DeviceEpisodes: all of its episodes
+        if self._arg("audit_policy"):
+            self._policy_audit_pending = episodes if span is None else self._column_means(
+                self.lib.hp_episode_policy_summary, self.episode_policy_stats(episodes, **span)[0])
+        if self._arg("audit_actor_signal"):
+            self._actor_signal_pending = episodes if span is None else self._column_means(
+                self.lib.hp_episode_signal_summary, self.episode_signal_stats(episodes, **span)[0])
+
+    def _record_pending(self, pending, names, host_summary, onto):
+        """An epoch's pending audit -- the device path's summary (six means, already computed) or the host path's episodes (audited
+        now: `host_summary(episodes)`) -- averaged over the ranks like the success rate, onto the list; None: nothing is pending"""
+        if pending is not None:
+            _record(self, names, pending.cpu().numpy() if isinstance(pending, torch.Tensor) else host_summary(pending), onto)
+
+    def _record_actor_signal_audit(self):
+        """args.audit_actor_signal: the epoch's pending audit (host episodes: `episode_signal_stats_host`) onto `actor_signal_audit`"""
         from .synthetic import SIGNAL_STATS, episode_signal_summary
-        if isinstance(pending, torch.Tensor):
-            summary = pending.cpu().numpy()
-        else:
-            summary = episode_signal_summary(self.episode_signal_stats_host(pending)[0])
-        _record(self, SIGNAL_STATS, summary, self.actor_signal_audit)
+        pending, self._actor_signal_pending = self._actor_signal_pending, None
+        self._record_pending(pending, SIGNAL_STATS, lambda eps: episode_signal_summary(self.episode_signal_stats_host(eps)[0]),
+                             self.actor_signal_audit)
 
     def _record_eval_metrics(self, summary):
         """One evaluation's summary (this rank's six means), averaged over the ranks like the success rate, onto `eval_metrics`"""
@@ -248,18 +264,11 @@ class EpisodeAudit:
         _record(self, EPISODE_SUMMARY, summary, self.eval_metrics)
 
     def _record_policy_audit(self):
-        """args.audit_policy: the epoch's pending audit -- the device path's summary (six means, already computed) or the host
-        path's episodes (audited now: `episode_policy_stats_host`) -- averaged over the ranks like the success rate, onto
-        `policy_audit`"""
-        pending, self._policy_audit_pending = self._policy_audit_pending, None
-        if pending is None:
-            return
+        """args.audit_policy: the epoch's pending audit (host episodes: `episode_policy_stats_host`) onto `policy_audit`"""
         from .synthetic import POLICY_STATS, episode_policy_summary
-        if isinstance(pending, torch.Tensor):
-            summary = pending.cpu().numpy()
-        else:
-            summary = episode_policy_summary(self.episode_policy_stats_host(pending)[0])
-        _record(self, POLICY_STATS, summary, self.policy_audit)
+        pending, self._policy_audit_pending = self._policy_audit_pending, None
+        self._record_pending(pending, POLICY_STATS, lambda eps: episode_policy_summary(self.episode_policy_stats_host(eps)[0]),
+                             self.policy_audit)
 
     def _record_eval_critic(self, summary):
         """One evaluation's critic summary (this rank's six means), averaged over the ranks like the success rate, onto `eval_critic`"""

@@ -118,9 +118,11 @@ class DeviceEpisodeBuffer:
 
     def sample_device(self, rng, o_norm, g_norm, batch, future_p, sq_threshold, clip_obs, with_indices=False, f32_rows=False, fast=None):
         """hp_buffer_sample_dev: the minibatch as the learner consumes it (ddpg_agent.py:227-243) in torch CUDA tensors
-        allocated here: x, x_next [B, obs+goal], actions [B, act], r [B, 1], float32.  The kernels run on the CONTEXT's stream,
-        ordered with torch's current stream by events on both sides (_lib.Context.torch_bridge): the context is not rebound, so
-        a fused learner on the same context keeps replaying its cached graphs, and no host synchronisation happens."""
+        allocated here: x, x_next [B, obs+goal], actions [B, act], r [B, 1], float32.  The kernels run on TORCH's current stream,
+        which the context borrows for this call (_lib.Context.torch_bridge: behind what the context's own stream held; the own
+        stream catches up when it is next used): the context is not rebound, so a fused learner on the same context keeps
+        replaying its cached graphs, and no host synchronisation happens.  The context's lock is held while the call runs, so
+        another thread's library call on this context (a feeder's store) waits for it."""
         import torch
 
         B = int(batch)
