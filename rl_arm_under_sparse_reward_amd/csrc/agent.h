@@ -465,8 +465,8 @@ struct GatherCtx {   // one update of a sequence: where its minibatch comes from
     hp_norm *on, *gn;
     const PlanRec *plan;
     double sq;
-    const SeqPlan *seq = nullptr;
-    int u = 0;            // index of this update in its sequence (the tile-wise exchange's epoch)
+    const SeqPlan *seq = nullptr;   // the sequence's launch form (seq_plan): every sampled update carries it
+    int u = 0;           // index of this update in its sequence (the tile-wise exchange's epoch)
     // the draw of a LATER update's index plan (seq->ride)
     hp_rng *rng = nullptr;
     PlanRec *next_plan = nullptr;
@@ -496,13 +496,14 @@ int enqueue_gather(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, const Pl
                    hipStream_t stream = nullptr);
 int enqueue_relayout(hp_agent *a, bool targets);
 Launch build_dw_group(const hp_agent *a, const float *sXA, const float *sXP, float *grads = nullptr);
-// forwards + losses + backwards of one update.  Inputs: gc == nullptr -> already in XA/XP/XT/R (minibatch API), else sampled
-// (HER gather fused into the chain kernel / k_gather_fused).  fuse_adam: the caller wants the optimizer step applied too;
-// the slab engines then do it in the weight-gradient launch's epilogue and the caller must NOT enqueue Adam again (*fused).
-// A sampled update of a sequence takes the optimizer placement of gc->seq (fuse_adam: OPT_TILES / OPT_PEER_TILES).
-int enqueue_forward_backward(hp_agent *a, const GatherCtx *gc = nullptr, bool fuse_adam = false, bool *fused = nullptr);
+// forwards + losses + backwards of one update.  A sampled update (gc; HER gather fused into the chain kernel / k_gather_fused) takes
+// everything about its launches from its sequence's plan, gc->seq, the optimizer's placement included.  gc == nullptr: the inputs
+// are already in XA/XP/XT/R (minibatch API) and there is no sequence; staged_step: the caller wants the optimizer step applied too.
+// Where tiles_step(a) holds the weight-gradient launch then does it in its epilogue and the caller must NOT enqueue Adam again.
+int enqueue_forward_backward(hp_agent *a, const GatherCtx *gc = nullptr, bool staged_step = false);
+static inline bool tiles_step(const hp_agent *a) { return a->slab && a->fuse_adam_ok; }
 // only = 1 / 2: just the chain kernel / just the weight-gradient launch (timing diagnostics, hp_agent_debug_chain)
-int enqueue_forward_backward_slab(hp_agent *a, const GatherCtx *gc, bool fuse_adam, int only = 0);
+int enqueue_forward_backward_slab(hp_agent *a, const GatherCtx *gc, int only = 0, bool staged_step = false);
 // split launch: does this agent's shape fit it (4-row slabs, three kinds of chains + spare workgroups on the CUs)?
 bool split_fits(const hp_agent *a);
 bool split_fits_rows(const hp_agent *a, int rows);

@@ -156,7 +156,7 @@ static int enqueue_updates(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, 
         gc.polyak_after = P.fold && u == n_updates - 1;
         // epoch base is even: parity of epoch base + u + 1
         if (P.opt == SeqPlan::OPT_PEER_KERNEL) gc.grads_out = peer_grad_buffer(a->peer, u + 1);
-        HP_TRY(enqueue_forward_backward(a, &gc, P.opt == SeqPlan::OPT_TILES || P.opt == SeqPlan::OPT_PEER_TILES));
+        HP_TRY(enqueue_forward_backward(a, &gc));   // (P.opt in the tiles: the step is part of it)
         // a split launch whose tiles wrote gradients only: the optimizer launch behind the exchange clears its counter set
         unsigned *reset = P.split && P.tiles_mode == SPLIT_TILES_GRADS ? split_set(a, u) : nullptr;
         if (P.opt == SeqPlan::OPT_PEER_KERNEL) {
@@ -521,9 +521,8 @@ int hp_agent_update_minibatch(hp_agent *a, const float *x, const float *x_next, 
     HP_CHECK_HIP(hipMemcpyAsync(a->XT, hxt.data(), hxt.size() * 4, hipMemcpyHostToDevice, s));
     HP_CHECK_HIP(hipMemcpyAsync(a->R, hr.data(), hr.size() * 4, hipMemcpyHostToDevice, s));
     HP_CHECK_HIP(hipStreamSynchronize(s));
-    bool fused = false;
-    HP_TRY(enqueue_forward_backward(a, nullptr, true, &fused));
-    if (!fused) HP_TRY(enqueue_adam(a));
+    HP_TRY(enqueue_forward_backward(a, nullptr, true));
+    if (!tiles_step(a)) HP_TRY(enqueue_adam(a));
     a->host_steps += 1;
     if (losses_host) HP_TRY(hp_agent_get_losses(a, losses_host, 1));
     else HP_CHECK_HIP(hipStreamSynchronize(s));

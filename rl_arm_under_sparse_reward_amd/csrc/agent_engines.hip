@@ -18,6 +18,19 @@
 #include "gemm_lds.h"
 #include "transition_device.h"
 
+// One row per kernel: the name the launch log records (hp_agent_update_kernels) beside the kernel launched under it.  Each launch
+// family of the host side has ONE place that maps its run-time choice to a row, and launch_row reads both from it: the log cannot
+// name another kernel than the one enqueued.
+template <class... A> struct KernRow { const char *name; void (*fn)(A...); };
+template <class... A> static KernRow<A...> row(const char *name, void (*fn)(A...)) { return {name, fn}; }
+template <class... A, class... B>
+static int launch_row(const KernRow<A...> &k, unsigned grid, unsigned threads, hipStream_t s, const B &...args) {
+    HP_KLOG(k.name);
+    hipLaunchKernelGGL(k.fn, dim3(grid), dim3(threads), 0, s, args...);
+    HP_CHECK_HIP(hipGetLastError());
+    return HP_OK;
+}
+
 // gradients: barrier + rank-ordered sum + Adam.  n4 = arena floats / 4; u = index of the update in its sequence.
 __global__ __launch_bounds__(256) void k_peer_adam(const PeerDev D, const AdamFuse F, int n4, int u, int mean) {
     const unsigned long long epoch = D.epoch[0] + (unsigned long long)u + 1ull;
@@ -74,15 +87,10 @@ static int peer_enqueue_adam(hp_peer *p, const AdamFuse &F, int n_arena, int u, 
     if (p->phases == 2) {
         HP_TRY(peer_enqueue_reduce_slice(p, n4, u, mean));
         HP_TRY(peer_enqueue_gate(p, 3, u));
-        HP_KLOG("k_peer_adam2");
-        hipLaunchKernelGGL(k_peer_adam2, dim3((n4 + 255) / 256), dim3(256), 0, p->ctx->stream, p->dev, F, n4, u);
-    } else {
-        HP_TRY(peer_enqueue_gate(p, 1, u));
-        HP_KLOG("k_peer_adam");
-        hipLaunchKernelGGL(k_peer_adam, dim3((n4 + 255) / 256), dim3(256), 0, p->ctx->stream, p->dev, F, n4, u, mean ? 1 : 0);
+        return launch_row(row("k_peer_adam2", k_peer_adam2), (n4 + 255) / 256, 256, p->ctx->stream, p->dev, F, n4, u);
     }
-    HP_CHECK_HIP(hipGetLastError());
-    return HP_OK;
+    HP_TRY(peer_enqueue_gate(p, 1, u));
+    return launch_row(row("k_peer_adam", k_peer_adam), (n4 + 255) / 256, 256, p->ctx->stream, p->dev, F, n4, u, mean ? 1 : 0);
 }
 
 // the 4x4x1 slab engine, compiled for two slab heights (see slab8.h)
@@ -322,10 +330,7 @@ __global__ void k_polyak_frag(float *__restrict__ tgt, const float *__restrict__
 // ------------------------------------------------------------------------------- host side
 int launch_group(hp_agent *a, const Launch &L, int which) {
     ProfScope ps(a, which);
-    HP_KLOG(L.g.uni ? "k_gemm_lds_u" : "k_gemm_lds");
-    hipLaunchKernelGGL(L.g.uni ? k_gemm_lds_u : k_gemm_lds, dim3(L.tiles), dim3(GL_THREADS), 0, a->ctx->stream, L.g);
-    HP_CHECK_HIP(hipGetLastError());
-    return HP_OK;
+    return launch_row(L.g.uni ? row("k_gemm_lds_u", k_gemm_lds_u) : row("k_gemm_lds", k_gemm_lds), L.tiles, GL_THREADS, a->ctx->stream, L.g);
 }
 
 // k_policy_slab8 and its grid rule, a workgroup per 4 rows: the one launch site of the policy calls (agent_forward.hip)
@@ -339,13 +344,10 @@ int launch_policy_slab(hipStream_t stream, const PolicyArgs &P) {
 int enqueue_gather(hp_agent *a, hp_buffer *b, hp_norm *on, hp_norm *gn, const PlanRec *plan, double sq, int xset,
                    hipStream_t stream) {
     ProfScope ps(a, PROF_SAMPLE);
-    HP_KLOG("k_gather_fused");
-    hipLaunchKernelGGL(k_gather_fused, dim3((a->B + 3) / 4), dim3(256), 0, stream ? stream : a->ctx->stream, b->d_obs, b->d_ag,
-                       b->d_g, b->d_act, plan, a->B, (int)b->T, (int)b->obs_dim, (int)b->goal_dim, (int)b->act_dim, sq, on->d,
-                       gn->d, a->cfg.clip_obs, a->cfg.clip_range, (float)a->cfg.max_action, a->ldx, a->act_off,
-                       xset ? a->XA2 : a->XA, xset ? a->XP2 : a->XP, xset ? a->XT2 : a->XT, xset ? a->R2 : a->R);
-    HP_CHECK_HIP(hipGetLastError());
-    return HP_OK;
+    return launch_row(row("k_gather_fused", k_gather_fused), (a->B + 3) / 4, 256, stream ? stream : a->ctx->stream, b->d_obs, b->d_ag,
+                      b->d_g, b->d_act, plan, a->B, (int)b->T, (int)b->obs_dim, (int)b->goal_dim, (int)b->act_dim, sq, on->d,
+                      gn->d, a->cfg.clip_obs, a->cfg.clip_range, (float)a->cfg.max_action, a->ldx, a->act_off,
+                      xset ? a->XA2 : a->XA, xset ? a->XP2 : a->XP, xset ? a->XT2 : a->XT, xset ? a->R2 : a->R);
 }
 
 static ArenaMap arena_map(const hp_agent *a) {
@@ -417,30 +419,43 @@ int enqueue_relayout(hp_agent *a, bool targets) {
     return HP_OK;
 }
 
-// all weight gradients of one update: the only products that reduce over the batch (input sets sXA / sXP)
+// ---- the eight weight-gradient problems of one update: the only products that reduce over the batch.  Each is stated once
+// (add_dw_prob); a launch is a list of them.
+enum { DW_ACTOR = 0, DW_CRITIC = 1 };
+struct DwProb { int net, layer; };   // layer 1-4 of the actor / the critic
+// dW = dY^T X, db = column sums of dY of one layer.  sX: the input set its network read (X operand of layer 1); grads: base of the
+// gradient arena [actor | critic]
+static void add_dw_prob(const hp_agent *a, Launch &L, DwProb q, const float *sX, float *grads) {
+    const bool c = q.net == DW_CRITIC;
+    const NetLayout &l = c ? a->lc : a->la;
+    const int H = a->H;
+    const struct { const float *dY, *X; int w, b; } of[4] = {
+        {c ? a->dA1 : a->dK1, sX, l.w1, l.b1},
+        {c ? a->dA2 : a->dK2, c ? a->CA.h1 : a->AP.h1, l.w2, l.b2},
+        {c ? a->dA3 : a->dK3, c ? a->CA.h2 : a->AP.h2, l.w3, l.b3},
+        {c ? a->dQA : a->dZ, c ? a->CA.h3 : a->AP.h3, l.w4, l.b4}};
+    const auto &p = of[q.layer - 1];
+    const int ny = q.layer == 4 ? 16 : H;   // outputs = dY's row stride: the heads are [Mp][16]
+    float *G = grads + (c ? a->la.total : 0);
+    add_dw(L, p.dY, ny, ny, p.X, q.layer == 1 ? a->ldx : H, q.layer == 1 ? l.K1 : H, G + p.w, G + p.b, a->Mp, q.layer);
+}
+
+// all of them as one launch (input sets sXA / sXP)
 Launch build_dw_group(const hp_agent *a, const float *sXA, const float *sXP, float *grads) {
-    const int H = a->H, Mp = a->Mp, ldx = a->ldx;
-    const NetLayout &la = a->la, &lc = a->lc;
+    const int Mp = a->Mp;
     if (!grads) grads = a->grads;
-    float *Ga = grads, *Gc = grads + la.total;
-    Launch L;
-    // the four 256 x 256 problems first: Launch::place_on_xcds gives each of them one pair of XCDs
-    add_dw(L, a->dA3, H, H, a->CA.h2, H, H, Gc + lc.w3, Gc + lc.b3, Mp, 3);
-    add_dw(L, a->dA2, H, H, a->CA.h1, H, H, Gc + lc.w2, Gc + lc.b2, Mp, 2);
-    add_dw(L, a->dK3, H, H, a->AP.h2, H, H, Ga + la.w3, Ga + la.b3, Mp, 3);
-    add_dw(L, a->dK2, H, H, a->AP.h1, H, H, Ga + la.w2, Ga + la.b2, Mp, 2);
-    // the narrow problems (heads, first layers: 40 tiles at the reference shapes) follow as second workgroups on CUs that
+    // the four 256 x 256 problems first: Launch::place_on_xcds gives each of them one pair of XCDs.
+    // The narrow problems (heads, first layers: 40 tiles at the reference shapes) follow as second workgroups on CUs that
     // already hold a 256 x 256 tile; with a long reduction their batch rows are split over ks workgroups each, so that no CU
     // carries two full tiles (gemm_lds.h)
+    static const DwProb joint[8] = {{DW_CRITIC, 3}, {DW_CRITIC, 2}, {DW_ACTOR, 3}, {DW_ACTOR, 2},
+                                    {DW_CRITIC, 4}, {DW_CRITIC, 1}, {DW_ACTOR, 4}, {DW_ACTOR, 1}};
     const int ks = (!a->dw64 && a->gl_part && a->dw_ksplit > 1 && Mp >= GL_RING_MIN_K) ? a->dw_ksplit : 1;   // ring path only
-    add_dw(L, a->dQA, 16, 16, a->CA.h3, H, H, Gc + lc.w4, Gc + lc.b4, Mp, 4);
-    if (ks > 1) L.split_last(ks);
-    add_dw(L, a->dA1, H, H, sXA, ldx, lc.K1, Gc + lc.w1, Gc + lc.b1, Mp, 1);
-    if (ks > 1) L.split_last(ks);
-    add_dw(L, a->dZ, 16, 16, a->AP.h3, H, H, Ga + la.w4, Ga + la.b4, Mp, 4);
-    if (ks > 1) L.split_last(ks);
-    add_dw(L, a->dK1, H, H, sXP, ldx, la.K1, Ga + la.w1, Ga + la.b1, Mp, 1);
-    if (ks > 1) L.split_last(ks);
+    Launch L;
+    for (int i = 0; i < 8; ++i) {
+        add_dw_prob(a, L, joint[i], joint[i].net == DW_CRITIC ? sXA : sXP, grads);
+        if (i >= 4 && ks > 1) L.split_last(ks);
+    }
     L.g.part = a->gl_part;
     L.g.ticket = a->gl_ticket;
     L.g.uni = (Mp > 256 && Mp <= 640) ? 1 : 0;   // gemm_lds.h, note at `wave`
@@ -571,60 +586,132 @@ static unsigned build_split_roles(const hp_agent *a, FbSplitArgs &Q, bool chains
 }
 
 // the weight-gradient problems of one network (critic: inside the split launch; actor: the launch behind it)
+// The critic's list is the order in which the critic chains publish the operands: W3, W4 (stage 0), W2 (stage 1), W1 (stage 2).
+// The two tables behind it follow THAT order, 4 bits per problem, and change with it: SPLIT_TILE_STAGE, the counter that says a
+// problem's operands are published (FbSplitArgs::tile_stage), and SPLIT_TILE_GATE, the counter its optimizer step waits on -- W3c
+// after the actor-side chains' first critic dX layer (counter 4), W4c / W1c after their critic forward (3), W2c after the second
+// dX layer (5).
+static const DwProb DW_CRITIC_ORDER[4] = {{DW_CRITIC, 3}, {DW_CRITIC, 4}, {DW_CRITIC, 2}, {DW_CRITIC, 1}};
+static const unsigned SPLIT_TILE_STAGE = 0u | (0u << 4) | (1u << 8) | (2u << 12);
+static const unsigned SPLIT_TILE_GATE = 4u | (3u << 4) | (5u << 8) | (3u << 12);
+// The actor's: its two 256 x 256 problems first, four XCDs each (gemm_tile: placed2)
+static const DwProb DW_ACTOR_ORDER[4] = {{DW_ACTOR, 3}, {DW_ACTOR, 2}, {DW_ACTOR, 4}, {DW_ACTOR, 1}};
 static Launch build_dw_half(const hp_agent *a, bool critic, const float *sX, float *grads) {
-    const int H = a->H, Mp = a->Mp, ldx = a->ldx;
-    const NetLayout &la = a->la, &lc = a->lc;
-    if (!grads) grads = a->grads;
-    float *Ga = grads, *Gc = grads + la.total;
+    const int Mp = a->Mp;
     Launch L;
-    if (critic) {
-        // in the order the critic chains publish the operands (slab8_split.h: stages 0, 0, 1, 2)
-        add_dw(L, a->dA3, H, H, a->CA.h2, H, H, Gc + lc.w3, Gc + lc.b3, Mp, 3);
-        add_dw(L, a->dQA, 16, 16, a->CA.h3, H, H, Gc + lc.w4, Gc + lc.b4, Mp, 4);
-        add_dw(L, a->dA2, H, H, a->CA.h1, H, H, Gc + lc.w2, Gc + lc.b2, Mp, 2);
-        add_dw(L, a->dA1, H, H, sX, ldx, lc.K1, Gc + lc.w1, Gc + lc.b1, Mp, 1);
-    } else {
-        add_dw(L, a->dK3, H, H, a->AP.h2, H, H, Ga + la.w3, Ga + la.b3, Mp, 3);
-        add_dw(L, a->dK2, H, H, a->AP.h1, H, H, Ga + la.w2, Ga + la.b2, Mp, 2);
-        add_dw(L, a->dZ, 16, 16, a->AP.h3, H, H, Ga + la.w4, Ga + la.b4, Mp, 4);
-        add_dw(L, a->dK1, H, H, sX, ldx, la.K1, Ga + la.w1, Ga + la.b1, Mp, 1);
-        // two 256 x 256 problems: four XCDs each (gemm_tile: placed2)
-        if (L.g.p[0].tiles_n == 8 && L.g.p[0].M == 256 && L.g.p[1].tile0 == 64 && L.g.p[1].tiles_n == 8 && L.g.p[1].M == 256)
-            L.g.xcd = 2;
-    }
+    for (int i = 0; i < 4; ++i) add_dw_prob(a, L, (critic ? DW_CRITIC_ORDER : DW_ACTOR_ORDER)[i], sX, grads ? grads : a->grads);
+    if (!critic && L.g.p[0].tiles_n == 8 && L.g.p[0].M == 256 && L.g.p[1].tile0 == 64 && L.g.p[1].tiles_n == 8 && L.g.p[1].M == 256)
+        L.g.xcd = 2;
     L.g.uni = (Mp > 256 && Mp <= 640) ? 1 : 0;
     return L;
 }
 
-// the look-ahead gather: update u + 1's inputs (plan gc->ahead_plan) into the input set this update does not read (chain kernel,
-// split launch, riders of the weight-gradient launch)
-template <class T> static void aim_ahead(const hp_agent *a, const GatherCtx *gc, const GatherSrc &gs, T &X) {
-    const bool xs = gc->xset != 0;
-    X.ahead = gs;
-    X.ahead.plan = gc->ahead_plan;
-    X.ahead.plan_any = gc->ahead_plan;
-    X.ahead.R = xs ? a->R : a->R2;
-    X.aXT = xs ? a->XT : a->XT2; X.aXA = xs ? a->XA : a->XA2; X.aXP = xs ? a->XP : a->XP2;
+// ---- the riders of one update: the draw of a LATER update's index plan and the look-ahead gather of update u + 1's inputs (plan
+// gc->ahead_plan) into the input set this update does not read.  Decided here, once per update: whether each runs, where -- in
+// spare workgroups of the chain launch (split launch included) or behind the tiles of the weight-gradient launch (seq->ride ==
+// RIDE_DW) --, with how many workgroups, and on what.  Both argument blocks are filled from the result (riders_into_chain,
+// riders_into_tiles).
+struct Riders {
+    enum Where { NOWHERE, CHAIN, TILES };
+    Where plan = NOWHERE, gather = NOWHERE;
+    int gather_wgs = 0;
+    int n_plan(Where w) const { return plan == w ? 1 : 0; }   // workgroups of each job in the launch `w`
+    int n_ahead(Where w) const { return gather == w ? gather_wgs : 0; }
+    // the draw (mt_her_plan)
+    MtState *rng = nullptr;
+    const BufMeta *meta = nullptr;
+    PlanRec *next_plan = nullptr;
+    double future_p = 0.0;
+    int T = 0;
+    // the gather (s8_gather_ahead): the next update's plan, reward vector and input sets
+    const PlanRec *ahead_plan = nullptr;
+    float *R = nullptr, *XT = nullptr, *XA = nullptr, *XP = nullptr;
+};
+static Riders riders_of(const hp_agent *a, const GatherCtx *gc) {
+    Riders r;
+    if (!gc) return r;   // staged minibatch: nothing to draw or gather
+    const Riders::Where at = gc->seq->ride == SeqPlan::RIDE_DW ? Riders::TILES : Riders::CHAIN;
+    if (gc->next_plan && gc->rng) {
+        r.plan = at;
+        r.rng = gc->rng->d_state; r.meta = gc->b->d_meta; r.next_plan = gc->next_plan; r.future_p = gc->future_p; r.T = gc->b->T;
+    }
+    if (gc->ahead_plan) {
+        r.gather = at;
+        // behind the tiles: one pass of 32 rows (8 waves x 4 rows in flight) per gather workgroup: each pass is two dependent HBM
+        // latencies, so fewer, longer workgroups made that launch 3 us longer than its tiles (61.0 vs 58.6 us/update at
+        // batch 1024 with 8 vs 32 of them)
+        r.gather_wgs = at == Riders::CHAIN ? S8_AHEAD_WGS : std::min((a->B + 31) / 32, 64);
+        const bool xs = gc->xset != 0;
+        r.ahead_plan = gc->ahead_plan;
+        r.R = xs ? a->R : a->R2; r.XT = xs ? a->XT : a->XT2; r.XA = xs ? a->XA : a->XA2; r.XP = xs ? a->XP : a->XP2;
+    }
+    return r;
+}
+// the gather's source and destinations, as both argument blocks hold them (gs: this update's own source)
+static void aim_ahead(const Riders &r, const GatherSrc &gs, GatherSrc &ahead, float *&aXT, float *&aXA, float *&aXP) {
+    ahead = gs;
+    ahead.plan = r.ahead_plan;
+    ahead.plan_any = r.ahead_plan;
+    ahead.R = r.R;
+    aXT = r.XT; aXA = r.XA; aXP = r.XP;
+}
+// spare workgroups of the chain launch (P.f.gs is set)
+static void riders_into_chain(const hp_agent *a, const Riders &r, FbSlabArgs &P) {
+    const bool draw = r.plan == Riders::CHAIN;
+    P.b.rng = draw ? r.rng : nullptr;
+    P.b.meta = draw ? r.meta : nullptr;
+    P.b.next_plan = draw ? r.next_plan : nullptr;
+    P.b.future_p = draw ? r.future_p : 0.0;
+    P.b.T = draw ? r.T : 0;
+    P.b.plan_batch = a->B;
+    P.n_plan = r.n_plan(Riders::CHAIN);
+    P.n_ahead = r.n_ahead(Riders::CHAIN);
+    P.ahead = P.f.gs;
+    P.aXT = P.aXA = P.aXP = nullptr;
+    if (P.n_ahead) aim_ahead(r, P.f.gs, P.ahead, P.aXT, P.aXA, P.aXP);   // next update's inputs into the other set
+}
+// workgroups behind the tiles of the weight-gradient launch (all zero: no riders there)
+static void riders_into_tiles(const hp_agent *a, const Riders &r, const GatherSrc &gs, RideArgs &R) {
+    memset(&R, 0, sizeof(R));
+    R.n_plan = r.n_plan(Riders::TILES);
+    R.n_ahead = r.n_ahead(Riders::TILES);
+    if (R.n_plan) {
+        R.rng = r.rng; R.meta = r.meta; R.next_plan = r.next_plan; R.future_p = r.future_p;
+        R.T = r.T; R.plan_batch = a->B;
+    }
+    if (R.n_ahead) {
+        aim_ahead(r, gs, R.ahead, R.aXT, R.aXA, R.aXP);
+        R.ldx = a->ldx; R.act_off = a->act_off; R.act_dim = a->cfg.act_dim; R.max_action = (float)a->cfg.max_action;
+    }
 }
 
-// argument blocks of the chain kernels for one update (gc as in enqueue_forward_backward_slab), with the plan draw and the
-// look-ahead gather in spare workgroups unless they ride in the weight-gradient launch
+// argument blocks of the chain kernels for one update (gc as in enqueue_forward_backward_slab), with the riders the chain launch
+// carries
 struct FbBuilt {
     FbSlabArgs P;
-    int nslab, xs;
-    float *sXA, *sXP, *sXT, *sR;
-    bool ride_dw, ride;
+    int nslab;
+    float *sXA, *sXP;
 };
-static void build_fb_args(hp_agent *a, const GatherCtx *gc, FbBuilt &O) {
-    const int H = a->H, Mp = a->Mp, ldx = a->ldx;
-    const NetLayout &la = a->la, &lc = a->lc;
+static void build_fb_args(hp_agent *a, const GatherCtx *gc, const Riders &riders, FbBuilt &O) {
+    const int Mp = a->Mp;
     const int nslab = Mp / (a->slab8 ? a->s8_rows : S32_ROWS);
     FbSlabArgs &P = O.P;
     const int xs = gc ? gc->xset : 0;
     float *sXA = xs ? a->XA2 : a->XA, *sXP = xs ? a->XP2 : a->XP, *sXT = xs ? a->XT2 : a->XT, *sR = xs ? a->R2 : a->R;
-    const SlabNetPtrs online = SlabNetPtrs{a->fragF, a->fragD, a->params};
+    // what the forward and the backward half both take: the online nets, layouts, dims, activations, Q vectors
+    auto shared = [&](auto &A) {
+        A.online = SlabNetPtrs{a->fragF, a->fragD, a->params};
+        A.la = a->la; A.lc = a->lc; A.H = a->H; A.ldx = a->ldx; A.act_off = a->act_off; A.act_dim = a->cfg.act_dim; A.Mp = Mp;
+        A.max_action = (float)a->cfg.max_action;
+        A.XP = sXP; A.TP = a->TP;
+        A.CAh1 = a->CA.h1; A.CAh2 = a->CA.h2; A.CAh3 = a->CA.h3;
+        A.APh1 = a->AP.h1; A.APh2 = a->AP.h2; A.APh3 = a->AP.h3;
+        A.CPh1 = a->CP.h1; A.CPh2 = a->CP.h2; A.CPh3 = a->CP.h3;
+        A.QT = a->QT; A.QA = a->QA; A.QP = a->QP;
+    };
     {
         FwdSlabArgs &A = P.f;
+        shared(A);
         A.tl = a->timeline;
         memset(&A.gs, 0, sizeof(A.gs));
         A.gs.plan_any = a->plan.as<PlanRec>();
@@ -638,51 +725,25 @@ static void build_fb_args(hp_agent *a, const GatherCtx *gc, FbBuilt &O) {
             A.gs.T = b->T; A.gs.obs_dim = b->obs_dim; A.gs.goal_dim = b->goal_dim; A.gs.B = a->B;
             A.gs.R = sR;
         }
-        A.online = online;
         A.target = SlabNetPtrs{a->fragFT, nullptr, a->targets};
-        A.la = la; A.lc = lc; A.H = H; A.ldx = ldx; A.act_off = a->act_off; A.act_dim = a->cfg.act_dim; A.Mp = Mp;
-        A.max_action = (float)a->cfg.max_action;
-        A.XA = sXA; A.XT = sXT; A.XP = sXP; A.TP = a->TP;
-        A.CAh1 = a->CA.h1; A.CAh2 = a->CA.h2; A.CAh3 = a->CA.h3;
-        A.APh1 = a->AP.h1; A.APh2 = a->AP.h2; A.APh3 = a->AP.h3;
-        A.CPh1 = a->CP.h1; A.CPh2 = a->CP.h2; A.CPh3 = a->CP.h3;
-        A.QT = a->QT; A.QA = a->QA; A.QP = a->QP;
+        A.XA = sXA; A.XT = sXT;
     }
-    const bool ride_dw = gc && gc->seq && gc->seq->ride == SeqPlan::RIDE_DW;
-    const bool ride = gc && gc->next_plan && gc->rng && !ride_dw;
     {
         BwdSlabArgs &A = P.b;
+        shared(A);
         A.tl = a->timeline + 96;
-        A.online = online;
-        A.la = la; A.lc = lc; A.H = H; A.ldx = ldx; A.act_off = a->act_off; A.act_dim = a->cfg.act_dim;
-        A.B = a->B; A.Mp = Mp;
-        A.max_action = (float)a->cfg.max_action; A.gamma = (float)a->cfg.gamma;
+        A.B = a->B;
+        A.gamma = (float)a->cfg.gamma;
         A.clip_ret = (float)(1.0 / (1.0 - a->cfg.gamma)); A.action_l2 = (float)a->cfg.action_l2;
-        A.QT = a->QT; A.QA = a->QA; A.QP = a->QP; A.R = sR; A.XP = sXP; A.TP = a->TP;
-        A.CAh1 = a->CA.h1; A.CAh2 = a->CA.h2; A.CAh3 = a->CA.h3;
-        A.APh1 = a->AP.h1; A.APh2 = a->AP.h2; A.APh3 = a->AP.h3;
-        A.CPh1 = a->CP.h1; A.CPh2 = a->CP.h2; A.CPh3 = a->CP.h3;
+        A.R = sR;
         A.dQA = a->dQA; A.dA3 = a->dA3; A.dA2 = a->dA2; A.dA1 = a->dA1;
         A.dZ = a->dZ; A.dK3 = a->dK3; A.dK2 = a->dK2; A.dK1 = a->dK1;
         A.part = a->part; A.st = a->d_state; A.adam = adam_cfg(a);
         A.nslab = nslab;
-        A.rng = ride ? gc->rng->d_state : nullptr;
-        A.meta = ride ? gc->b->d_meta : nullptr;
-        A.next_plan = ride ? gc->next_plan : nullptr;
-        A.future_p = ride ? gc->future_p : 0.0;
-        A.T = ride ? gc->b->T : 0;
-        A.plan_batch = a->B;
     }
-    P.n_plan = ride ? 1 : 0;
-    P.n_ahead = 0;
-    P.ahead = P.f.gs;
-    P.aXT = P.aXA = P.aXP = nullptr;
-    if (gc && gc->ahead_plan && !ride_dw) {   // next update's inputs into the other set
-        P.n_ahead = S8_AHEAD_WGS;
-        aim_ahead(a, gc, P.f.gs, P);
-    }
+    riders_into_chain(a, riders, P);
     P.xcd_split = P.n_pref = 0;
-    O.nslab = nslab; O.xs = xs; O.sXA = sXA; O.sXP = sXP; O.sXT = sXT; O.sR = sR; O.ride_dw = ride_dw; O.ride = ride;
+    O.nslab = nslab; O.sXA = sXA; O.sXP = sXP;
 }
 
 // bias gradients + their optimizer step in workgroups of their own behind the tiles (gemm_lds.h: gemm_bias_tile; the ring path's
@@ -703,47 +764,62 @@ static int launch_dw(hp_agent *a, Launch &L, const AdamFuse *F, const RideArgs &
         Dw64Args X;
         HP_TRY(dw64_args(a, L, X));
         const unsigned grid = X.n_wg + riders;
-        HP_KLOG(F ? "k_dw64_adam" : "k_dw64");
-        if (F) hipLaunchKernelGGL(k_dw64_adam, dim3(grid), dim3(DW_THREADS), 0, s, L.g, *F, R, X);
-        else hipLaunchKernelGGL(k_dw64, dim3(grid), dim3(DW_THREADS), 0, s, L.g, R, X);
-    } else if (peer_u >= 0) {
+        if (F) return launch_row(row("k_dw64_adam", k_dw64_adam), grid, DW_THREADS, s, L.g, *F, R, X);
+        return launch_row(row("k_dw64", k_dw64), grid, DW_THREADS, s, L.g, R, X);
+    }
+    if (peer_u >= 0) {
         // data-parallel ranks: the tiles exchange by themselves; riders, if any, behind them
         HP_REQUIRE(F && a->peer && row0 + L.tiles <= HP_PEER_TILES, HP_ERR_STATE, "tile-wise exchange: %d tiles exceed the flag rows",
                    row0 + L.tiles);
-        HP_KLOG(uni ? "k_gemm_lds_adam_peer_u" : "k_gemm_lds_adam_peer");
-        hipLaunchKernelGGL(uni ? k_gemm_lds_adam_peer_u : k_gemm_lds_adam_peer, dim3(L.tiles + riders), dim3(GL_THREADS), 0, s, L.head(0),
-                           L.head(1), L.g, *F, R, L.tiles, a->peer->dev, peer_u, a->grad_mean ? 1 : 0, row0);
-    } else {
-        // tiles, then the bias panels, then the riders; with the optimizer, the loss log's own workgroup last
-        const int front = L.tiles + (sep_bias_on(a) ? L.separate_bias() : 0);
-        if (F) L.g.loss_wg = a->loss_wg;
-        const unsigned grid = front + riders + L.g.loss_wg;
-        if (F && riders) {
-            HP_KLOG(uni ? "k_gemm_lds_adam_ride_u" : "k_gemm_lds_adam_ride");
-            hipLaunchKernelGGL(uni ? k_gemm_lds_adam_ride_u : k_gemm_lds_adam_ride, dim3(grid), dim3(GL_THREADS), 0, s, L.head(0), L.head(1),
-                               front, L.g, *F, R);
-        } else if (riders) {
-            HP_KLOG(uni ? "k_gemm_lds_ride_u" : "k_gemm_lds_ride");
-            hipLaunchKernelGGL(uni ? k_gemm_lds_ride_u : k_gemm_lds_ride, dim3(grid), dim3(GL_THREADS), 0, s, L.g, R, front);
-        } else {
-            HP_KLOG(uni ? "k_gemm_lds_adam_u" : "k_gemm_lds_adam");
-            hipLaunchKernelGGL(uni ? k_gemm_lds_adam_u : k_gemm_lds_adam, dim3(grid), dim3(GL_THREADS), 0, s, L.head(0), L.head(1), L.g, *F);
-        }
+        return launch_row(uni ? row("k_gemm_lds_adam_peer_u", k_gemm_lds_adam_peer_u) : row("k_gemm_lds_adam_peer", k_gemm_lds_adam_peer),
+                          L.tiles + riders, GL_THREADS, s, L.head(0), L.head(1), L.g, *F, R, L.tiles, a->peer->dev, peer_u,
+                          a->grad_mean ? 1 : 0, row0);
     }
-    HP_CHECK_HIP(hipGetLastError());
-    return HP_OK;
+    // tiles, then the bias panels, then the riders; with the optimizer, the loss log's own workgroup last
+    const int front = L.tiles + (sep_bias_on(a) ? L.separate_bias() : 0);
+    if (F) L.g.loss_wg = a->loss_wg;
+    const unsigned grid = front + riders + L.g.loss_wg;
+    if (F && riders)
+        return launch_row(uni ? row("k_gemm_lds_adam_ride_u", k_gemm_lds_adam_ride_u) : row("k_gemm_lds_adam_ride", k_gemm_lds_adam_ride),
+                          grid, GL_THREADS, s, L.head(0), L.head(1), front, L.g, *F, R);
+    if (riders)
+        return launch_row(uni ? row("k_gemm_lds_ride_u", k_gemm_lds_ride_u) : row("k_gemm_lds_ride", k_gemm_lds_ride), grid, GL_THREADS, s,
+                          L.g, R, front);
+    return launch_row(uni ? row("k_gemm_lds_adam_u", k_gemm_lds_adam_u) : row("k_gemm_lds_adam", k_gemm_lds_adam), grid, GL_THREADS, s,
+                      L.head(0), L.head(1), L.g, *F);
+}
+
+// The chain launch's kernel: slab height x store policy of the chains' outputs (slab8.h) -- write-through unless
+// RLARM_ENGINE=chain_plain: ordinary stores measured no gain in this launch (batch 512 k8 and 1024); the log names
+// both k_fb_slab8 -- or the 32-row engine's
+static KernRow<FbSlabArgs> chain_kernel(const hp_agent *a) {
+    if (!a->slab8) return row("k_fb_slab32", s32::k_fb_slab32);
+    const bool wt = a->chain_wt != 0;
+    return row("k_fb_slab8", a->s8_rows == 4   ? (wt ? s8r4::k_fb_slab8 : s8r4::k_fb_slab8_plain)
+                             : a->s8_rows == 8 ? (wt ? s8r8::k_fb_slab8 : s8r8::k_fb_slab8_plain)
+                                               : (wt ? s8r16::k_fb_slab8 : s8r16::k_fb_slab8_plain));
+}
+
+// The plan an update is launched by: a sampled update's is its sequence's (seq_plan, agent.hip).  A staged minibatch has no sequence
+// and takes a default one -- no riders, no split launch, the optimizer in the tiles' epilogue (staged_step) or nowhere.
+static const SeqPlan &plan_of(const GatherCtx *gc, bool staged_step) {
+    static const SeqPlan none, step = [] { SeqPlan p; p.opt = SeqPlan::OPT_TILES; return p; }();
+    return gc ? *gc->seq : staged_step ? step : none;
 }
 
 // slab engines: forwards + losses + backwards of one update (inputs in XA/XP/XT/R): chain kernel + weight-gradient launch
 // only = 1 / 2: just the chain kernel / just the weight-gradient launch (timing diagnostics, hp_agent_debug_chain)
 static int enqueue_split_update(hp_agent *a, const GatherCtx *gc, FbBuilt &built, int only);
-int enqueue_forward_backward_slab(hp_agent *a, const GatherCtx *gc, bool fuse_adam, int only) {
+int enqueue_forward_backward_slab(hp_agent *a, const GatherCtx *gc, int only, bool staged_step) {
+    HP_REQUIRE(!gc || gc->seq, HP_ERR_INVALID, "a sampled update without its sequence's plan");
+    const SeqPlan &seq = plan_of(gc, staged_step);
     hipStream_t s = a->ctx->stream;
+    const Riders riders = riders_of(a, gc);
     FbBuilt built;
-    build_fb_args(a, gc, built);
+    build_fb_args(a, gc, riders, built);
     FbSlabArgs &P = built.P;
     const int nslab = built.nslab;
-    if (gc && gc->seq && gc->seq->split) return enqueue_split_update(a, gc, built, only);
+    if (seq.split) return enqueue_split_update(a, gc, built, only);
     if (only == 2) {
     } else if (a->slab8) {
         // one launch: each workgroup carries its rows through forward AND backward (k_fb_slab8)
@@ -758,76 +834,87 @@ int enqueue_forward_backward_slab(hp_agent *a, const GatherCtx *gc, bool fuse_ad
         // further gain (40.0 / 40.0 vs 39.95 with 16).
         const int fit = a->ctx->cu_count - (n_chain + P.n_plan + P.n_ahead);
         P.n_pref = fit >= 16 ? 16 : (fit >= 8 ? 8 : 0);
-        const unsigned grid = n_chain + P.n_plan + P.n_ahead + P.n_pref;
-        HP_KLOG("k_fb_slab8");
-        // store policy of the chains' outputs (slab8.h): write-through unless RLARM_ENGINE=chain_plain -- ordinary stores measured no gain
-        // in this launch (batch 512 k8 and 1024)
-        const bool wt = a->chain_wt != 0;
-        if (a->s8_rows == 4)
-            hipLaunchKernelGGL(wt ? s8r4::k_fb_slab8 : s8r4::k_fb_slab8_plain, dim3(grid), dim3(S8_THREADS), 0, s, P);
-        else if (a->s8_rows == 8)
-            hipLaunchKernelGGL(wt ? s8r8::k_fb_slab8 : s8r8::k_fb_slab8_plain, dim3(grid), dim3(S8_THREADS), 0, s, P);
-        else
-            hipLaunchKernelGGL(wt ? s8r16::k_fb_slab8 : s8r16::k_fb_slab8_plain, dim3(grid), dim3(S8_THREADS), 0, s, P);
-        HP_CHECK_HIP(hipGetLastError());
+        HP_TRY(launch_row(chain_kernel(a), n_chain + P.n_plan + P.n_ahead + P.n_pref, S8_THREADS, s, P));
     } else {
         // 32-row slabs, forward + backward of a chain in one workgroup; inputs come gathered (enqueue_updates)
         ProfScope ps(a, PROF_GEMM_FWD);
-        HP_KLOG("k_fb_slab32");
-        hipLaunchKernelGGL(s32::k_fb_slab32, dim3(2 * nslab + P.n_plan), dim3(S32_THREADS), 0, s, P);
-        HP_CHECK_HIP(hipGetLastError());
+        HP_TRY(launch_row(chain_kernel(a), 2 * nslab + P.n_plan, S32_THREADS, s, P));
     }
     if (only == 1) return HP_OK;
-    // all weight gradients (+ the optimizer when no gradient exchange follows) as their own launch
+    // all weight gradients (+ the optimizer where the plan puts it in their epilogue) as their own launch
     Launch L = build_dw_group(a, built.sXA, built.sXP, gc ? gc->grads_out : nullptr);
     RideArgs R;
-    memset(&R, 0, sizeof(R));
-    if (built.ride_dw) {
-        if (gc->next_plan && gc->rng) {
-            R.n_plan = 1;
-            R.rng = gc->rng->d_state; R.meta = gc->b->d_meta; R.next_plan = gc->next_plan; R.future_p = gc->future_p;
-            R.T = gc->b->T; R.plan_batch = a->B;
-        }
-        if (gc->ahead_plan) {
-            // one pass of 32 rows (8 waves x 4 rows in flight) per gather workgroup: each pass is two dependent HBM
-            // latencies, so fewer, longer workgroups made this launch 3 us longer than its tiles (61.0 vs 58.6 us/update at
-            // batch 1024 with 8 vs 32 of them)
-            R.n_ahead = (a->B + 31) / 32 < 64 ? (a->B + 31) / 32 : 64;
-            aim_ahead(a, gc, P.f.gs, R);
-            R.ldx = a->ldx; R.act_off = a->act_off; R.act_dim = a->cfg.act_dim; R.max_action = (float)a->cfg.max_action;
-        }
-    }
+    riders_into_tiles(a, riders, P.f.gs, R);
     const AdamFuse F = adam_block(a, gc);
-    const bool peer = fuse_adam && gc && gc->seq && gc->seq->opt == SeqPlan::OPT_PEER_TILES;
-    return launch_dw(a, L, fuse_adam ? &F : nullptr, R, peer ? gc->u : -1);
+    const bool step = seq.opt == SeqPlan::OPT_TILES || seq.opt == SeqPlan::OPT_PEER_TILES;
+    return launch_dw(a, L, step ? &F : nullptr, R, seq.opt == SeqPlan::OPT_PEER_TILES ? gc->u : -1);
 }
 
 // ---- one update in the split form: k_fb_split8 (chains + the critic's tiles and optimizer step), then the actor's tiles
-// k_fb_split8 with its role table as leading scalar arguments: word r = role r, byte x = its workgroups on XCD x
-// TILES: the instantiation of a tiles mode; a_wt: the actor-side chains store write-through (RLARM_ENGINE=chain_wt: k_fb_split8_wt)
-// instead of with ordinary stores (slab8.h, "store policy")
-template <int TILES>
-static void launch_split_as(unsigned grid, hipStream_t s, const FbSplitArgs &Q, const unsigned long long (&w)[SR_N], bool a_wt) {
-    hipLaunchKernelGGL(a_wt ? s8r4::k_fb_split8_wt<TILES> : s8r4::k_fb_split8<TILES>, dim3(grid), dim3(S8_THREADS), 0, s, w[0], w[1], w[2],
-                       w[3], w[4], w[5], w[6], Q);
+// The split launch's kernel: the instantiation of a tiles mode x the store policy of the actor-side chains -- write-through
+// (a_wt, RLARM_ENGINE=chain_wt: k_fb_split8_wt) instead of ordinary stores (slab8.h, "store policy"); the log names both k_fb_split8<n>
+static auto split_kernel(int tiles_mode, bool a_wt) {
+    using namespace s8r4;
+    switch (tiles_mode) {
+        case SPLIT_TILES_PEER: return row("k_fb_split8<1>", a_wt ? k_fb_split8_wt<SPLIT_TILES_PEER> : k_fb_split8<SPLIT_TILES_PEER>);
+        case SPLIT_TILES_GRADS: return row("k_fb_split8<2>", a_wt ? k_fb_split8_wt<SPLIT_TILES_GRADS> : k_fb_split8<SPLIT_TILES_GRADS>);
+        default: return row("k_fb_split8<0>", a_wt ? k_fb_split8_wt<SPLIT_TILES_ADAM> : k_fb_split8<SPLIT_TILES_ADAM>);
+    }
 }
-static void launch_split(unsigned grid, hipStream_t s, const FbSplitArgs &Q, int tiles_mode, bool a_wt) {
+// k_fb_split8 with its role table as leading scalar arguments: word r = role r, byte x = its workgroups on XCD x
+static int launch_split(const hp_agent *a, unsigned grid, const FbSplitArgs &Q, int tiles_mode) {
     unsigned long long w[SR_N];
     for (int r = 0; r < SR_N; ++r) {
         w[r] = 0ull;
         for (int x = 0; x < 8; ++x) w[r] |= ((Q.nrole[x] >> (8 * r)) & 0xffull) << (8 * x);
     }
-    HP_KLOG(tiles_mode == SPLIT_TILES_PEER ? "k_fb_split8<1>" : (tiles_mode == SPLIT_TILES_GRADS ? "k_fb_split8<2>" : "k_fb_split8<0>"));
-    if (tiles_mode == SPLIT_TILES_PEER) launch_split_as<SPLIT_TILES_PEER>(grid, s, Q, w, a_wt);
-    else if (tiles_mode == SPLIT_TILES_GRADS) launch_split_as<SPLIT_TILES_GRADS>(grid, s, Q, w, a_wt);
-    else launch_split_as<SPLIT_TILES_ADAM>(grid, s, Q, w, a_wt);
+    return launch_row(split_kernel(tiles_mode, a->chain_wt == 1), grid, S8_THREADS, a->ctx->stream, w[0], w[1], w[2], w[3], w[4], w[5],
+                      w[6], Q);
 }
-static void split_common(hp_agent *a, FbSplitArgs &Q, int set) {
+
+// The argument block of a split launch and its grid.  An update's launch (`tiles`: the critic's weight-gradient problems): every kind
+// of chain, the riders of P, the critic's tiles behind their gates, counter set gc->qset, target chains on the NEXT update's plan
+// (gc->t_plan; none: the sequence's last update).  The sequence's prologue (tiles == nullptr): target chains only, on the first
+// update's OWN plan (gc->plan) into Q' set 0 -- no A / C chains, no tiles (need_c = 0), an optimizer block that steps nothing, set 1
+// (sync_other = set 0, the first update's), reset_sync: it clears the counters.
+static unsigned build_split_args(hp_agent *a, const GatherCtx *gc, const FbSlabArgs &P, const Launch *tiles, FbSplitArgs &Q) {
+    const bool prologue = tiles == nullptr;
+    const int set = prologue ? 1 : gc->qset;
+    const PlanRec *t_plan = prologue ? gc->plan : gc->t_plan;
+    static FbSplitArgs Qz;   // zero template (the struct has padding the kernel never reads)
+    Q = Qz;
+    Q.s = P;
+    Q.tgs = P.f.gs;
+    if (t_plan) {
+        Q.tgs.plan = t_plan;
+        Q.tgs.plan_any = t_plan;
+    }
+    Q.tgs.R = nullptr;
+    Q.qt_in = set ? a->QT2 : a->QT;
+    Q.qt_out = set ? a->QT : a->QT2;
     Q.sync = a->k1_sync + (set & 1) * SPLIT_SET_WORDS;
     Q.sync_other = a->k1_sync + ((set + 1) & 1) * SPLIT_SET_WORDS;
     Q.fault = a->k1_sync + SPLIT_FAULT;
     Q.fault_host = a->fault_host_dev;
     Q.wait_ticks = SPLIT_WAIT_TICKS;
+    if (prologue) {
+        Q.reset_sync = 1;
+        Q.adam = adam_block(a, nullptr);
+        return build_split_roles(a, Q, false, true, 0, 0, 0);
+    }
+    const unsigned nslab = (unsigned)P.b.nslab;
+    Q.tile_stage = SPLIT_TILE_STAGE;
+    Q.tiles = tiles->g;
+    Q.need_c = nslab;
+    // time-line builds: the last launch with target chains AND a plan workgroup stamps
+    Q.tl_mark = (t_plan != nullptr && P.n_plan > 0) ? 1 : 0;
+    Q.adam = adam_block(a, gc, {OptGates::IN_TILES, Q.sync, nslab, SPLIT_TILE_GATE, Q.tl_mark});
+    if (gc->seq->tiles_mode == SPLIT_TILES_PEER) {
+        Q.peer = a->peer->d_dev;
+        Q.peer_u = gc->u;
+        Q.peer_mean = a->grad_mean ? 1 : 0;
+    }
+    return build_split_roles(a, Q, true, t_plan != nullptr, P.n_plan, P.n_ahead, tiles->tiles);
 }
 
 static int enqueue_split_update(hp_agent *a, const GatherCtx *gc, FbBuilt &built, int only) {
@@ -836,45 +923,17 @@ static int enqueue_split_update(hp_agent *a, const GatherCtx *gc, FbBuilt &built
     // exchange + the step (data-parallel ranks on a device each, gemm_lds.h PEER), or nothing -- the caller exchanges the gradient
     // vector and steps in launches of its own (RCCL; two-phase / gated peer memory)
     const int mode = gc->seq->tiles_mode;
-    hipStream_t s = a->ctx->stream;
-    FbSlabArgs &P = built.P;
-    const int nslab = built.nslab;
-    static FbSplitArgs Qz;   // zero template (the struct has padding the kernel never reads)
-    FbSplitArgs Q = Qz;
-    Q.tgs = P.f.gs;
-    if (gc->t_plan) {
-        Q.tgs.plan = gc->t_plan;
-        Q.tgs.plan_any = gc->t_plan;
-    }
-    Q.tgs.R = nullptr;
-    Q.qt_in = gc->qset ? a->QT2 : a->QT;
-    Q.qt_out = gc->qset ? a->QT : a->QT2;
-    split_common(a, Q, gc->qset);
-    // tile problems in the order their operands are published: the critic's W3, W4 (stage 0), W2 (stage 1), W1 (stage 2).  Gates
-    // of the optimizer steps: W3c after the actor-side chains' first critic dX layer (counter 4), W4c / W1c after their critic
-    // forward (3), W2c after the second dX layer (5).  The actor's tiles are the launch behind this one (the form that held them
-    // in this launch too, behind an "actor-side chains done" counter, measured 45.7 vs 38.0 us/update in round 4 and is gone).
+    // The critic's tiles ride in the split launch; the actor's are the launch behind it (the form that held them in the split launch
+    // too, behind an "actor-side chains done" counter, measured 45.7 vs 38.0 us/update in round 4 and is gone).
     Launch L = build_dw_half(a, true, built.sXA, mode == SPLIT_TILES_GRADS ? gc->grads_out : nullptr);
     Launch La = build_dw_half(a, false, built.sXP, mode == SPLIT_TILES_GRADS ? gc->grads_out : nullptr);
-    Q.tile_stage = 0u | (0u << 4) | (1u << 8) | (2u << 12);
-    Q.tiles = L.g;
-    Q.need_c = (unsigned)nslab;
-    // time-line builds: the last launch with target chains AND a plan workgroup stamps
-    Q.tl_mark = (gc->t_plan != nullptr && P.n_plan > 0) ? 1 : 0;
-    Q.adam = adam_block(a, gc, {OptGates::IN_TILES, Q.sync, (unsigned)nslab, 4u | (3u << 4) | (5u << 8) | (3u << 12), Q.tl_mark});
-    Q.s = P;
-    if (mode == SPLIT_TILES_PEER) {
-        HP_REQUIRE(a->peer && a->peer->d_dev && L.tiles + La.tiles <= HP_PEER_TILES, HP_ERR_STATE,
-                   "tile-wise exchange in the split launch: %d + %d tiles exceed the flag rows", L.tiles, La.tiles);
-        Q.peer = a->peer->d_dev;
-        Q.peer_u = gc->u;
-        Q.peer_mean = a->grad_mean ? 1 : 0;
-    }
-    const unsigned grid = build_split_roles(a, Q, true, gc->t_plan != nullptr, P.n_plan, P.n_ahead, L.tiles);
+    HP_REQUIRE(mode != SPLIT_TILES_PEER || (a->peer && a->peer->d_dev && L.tiles + La.tiles <= HP_PEER_TILES), HP_ERR_STATE,
+               "tile-wise exchange in the split launch: %d + %d tiles exceed the flag rows", L.tiles, La.tiles);
+    FbSplitArgs Q;
+    const unsigned grid = build_split_args(a, gc, built.P, &L, Q);
     {
         ProfScope ps(a, PROF_GEMM_FWD);
-        launch_split(grid, s, Q, mode, a->chain_wt == 1);
-        HP_CHECK_HIP(hipGetLastError());
+        HP_TRY(launch_split(a, grid, Q, mode));
     }
     // the actor's weight gradients (+ optimizer step): 144 tiles at the reference shapes, one per CU.  The launch clears this
     // launch's counter set, so that every split launch starts from a clean set whatever the parity of the sequence before it
@@ -885,35 +944,20 @@ static int enqueue_split_update(hp_agent *a, const GatherCtx *gc, FbBuilt &built
     g.reset_sync = Q.sync;
     const AdamFuse Fa = adam_block(a, gc, g);
     RideArgs R;
-    memset(&R, 0, sizeof(R));
+    riders_into_tiles(a, Riders(), built.P.f.gs, R);   // (a split sequence's riders are the split launch's spare workgroups)
     return launch_dw(a, La, mode == SPLIT_TILES_GRADS ? nullptr : &Fa, R, mode == SPLIT_TILES_PEER ? gc->u : -1, L.tiles);
 }
 
 // target chains of the sequence's first update (its plan: gc->plan) -> Q' set 0; also clears the first update's counter set
 int enqueue_split_prologue(hp_agent *a, const GatherCtx *gc) {
-    HP_REQUIRE(gc && split_fits(a), HP_ERR_STATE, "split launch: not available for this engine");
+    HP_REQUIRE(gc && gc->seq && split_fits(a), HP_ERR_STATE, "split launch: not available for this engine");
     FbBuilt built;
-    build_fb_args(a, gc, built);   // (the sequence's first gc: its own inputs, no riders)
-    FbSlabArgs &P = built.P;
-    static FbSplitArgs Qz;
-    FbSplitArgs Q = Qz;
-    Q.tgs = P.f.gs;
-    Q.tgs.plan = gc->plan;
-    Q.tgs.plan_any = gc->plan;
-    Q.tgs.R = nullptr;
-    Q.qt_in = a->QT2;
-    Q.qt_out = a->QT;
-    split_common(a, Q, 1);        // sync_other = set 0, the first update's
-    Q.need_c = 0u;
-    Q.reset_sync = 1;
-    Q.adam = adam_block(a, nullptr);
-    Q.s = P;
-    const unsigned grid = build_split_roles(a, Q, false, true, 0, 0, 0);
+    build_fb_args(a, gc, Riders(), built);   // (the sequence's first gc: its own inputs, no riders)
+    FbSplitArgs Q;
+    const unsigned grid = build_split_args(a, gc, built.P, nullptr, Q);
     ProfScope ps(a, PROF_PLAN);   // (once per sequence, with the index draws: not an update's launch)
     // (no tiles here: the instantiation the sequence's updates run, so that a rank executes ONE k_fb_split8)
-    launch_split(grid, a->ctx->stream, Q, gc->seq->tiles_mode, a->chain_wt == 1);
-    HP_CHECK_HIP(hipGetLastError());
-    return HP_OK;
+    return launch_split(a, grid, Q, gc->seq->tiles_mode);
 }
 
 int enqueue_adam(hp_agent *a, const GatherCtx *gc, unsigned *reset_sync) {
@@ -924,41 +968,31 @@ int enqueue_adam(hp_agent *a, const GatherCtx *gc, unsigned *reset_sync) {
     g.reset_sync = reset_sync;
     const AdamFuse F = adam_block(a, gc, g);
     const int n = a->n_arena;
-    const bool by4 = n % 4 == 0 && a->la.total % 4 == 0;
-    HP_KLOG(by4 ? "k_adam_frag4" : "k_adam_frag");
-    if (by4)
-        hipLaunchKernelGGL(k_adam_frag4, dim3((n / 4 + 255) / 256), dim3(256), 0, a->ctx->stream, F, a->grads, n / 4);
-    else
-        hipLaunchKernelGGL(k_adam_frag, dim3((n + 255) / 256), dim3(256), 0, a->ctx->stream, F, a->grads, n);
-    HP_CHECK_HIP(hipGetLastError());
-    return HP_OK;
+    if (n % 4 == 0 && a->la.total % 4 == 0)
+        return launch_row(row("k_adam_frag4", k_adam_frag4), (n / 4 + 255) / 256, 256, a->ctx->stream, F, a->grads, n / 4);
+    return launch_row(row("k_adam_frag", k_adam_frag), (n + 255) / 256, 256, a->ctx->stream, F, a->grads, n);
 }
 
 int enqueue_polyak(hp_agent *a) {
     ProfScope ps(a, PROF_ADAM);
     const int n = a->n_arena;
     const double om = 1.0 - a->cfg.polyak;
-    if (a->slab) {
-        HP_KLOG("k_polyak_frag");
-        hipLaunchKernelGGL(k_polyak_frag, dim3((n + 255) / 256), dim3(256), 0, a->ctx->stream, a->targets, a->params,
-                           a->fragFT, n, (float)om, (float)a->cfg.polyak, arena_map(a));
-        HP_CHECK_HIP(hipGetLastError());
-        return HP_OK;
-    }
+    if (a->slab)
+        return launch_row(row("k_polyak_frag", k_polyak_frag), (n + 255) / 256, 256, a->ctx->stream, a->targets, a->params, a->fragFT, n,
+                          (float)om, (float)a->cfg.polyak, arena_map(a));
     return layers_enqueue_polyak(a);
 }
 
-// one update's forwards + backwards.  gc == nullptr: the minibatch is already staged in XA/XP/XT/R.
-// fuse_adam: the optimizer step follows immediately on this rank (no gradient exchange): the slab engines then apply
-// it in the weight-gradient GEMM's epilogue and the caller must NOT enqueue Adam again (returns that via *fused).
-int enqueue_forward_backward(hp_agent *a, const GatherCtx *gc, bool fuse_adam, bool *fused) {
+// one update's forwards + backwards.  A sampled update (gc) is launched by its sequence's plan, gc->seq, the optimizer's placement
+// included.  gc == nullptr: the minibatch is already staged in XA/XP/XT/R and there is no sequence; staged_step: the optimizer step
+// follows immediately on this rank: where tiles_step(a) says so the slab engines apply it in the weight-gradient GEMM's epilogue and
+// the caller must NOT enqueue Adam again.
+int enqueue_forward_backward(hp_agent *a, const GatherCtx *gc, bool staged_step) {
     // Adam in the weight-gradient GEMM's epilogue (k_gemm_lds_adam).  The first version (one element at a time: four
     // serialised cold round trips per thread for p/m/v) measured 92.9 vs 67.5 us per update and was parked; with four
     // elements per thread (one float4 load per state array, float4 store into the forward fragment copy) it is the
     // faster path, 57.2 vs 60.5 us, and the default.  RLARM_FUSE_ADAM=0 keeps the separate k_adam_frag4 launch for A/B.
-    fuse_adam = fuse_adam && a->fuse_adam_ok;
-    if (fused) *fused = a->slab && fuse_adam;
-    if (a->slab) return enqueue_forward_backward_slab(a, gc, fuse_adam);   // gather fused into the forward kernel
+    if (a->slab) return enqueue_forward_backward_slab(a, gc, 0, staged_step && tiles_step(a));   // gather fused into the forward kernel
     if (gc) HP_TRY(enqueue_gather(a, gc->b, gc->on, gc->gn, gc->plan, gc->sq));
     return enqueue_forward_backward_layers(a);
 }
@@ -986,8 +1020,8 @@ int hp_agent_debug_chain(hp_agent *a, int32_t kind, int32_t n, double *us_per_la
             case 6: return enqueue_adam(a);
             case 8: return enqueue_polyak(a);
             case 10: return enqueue_forward_backward(a);   // whole forward+backward of the active engine
-            case 11: return a->slab ? enqueue_forward_backward_slab(a, nullptr, true, 1) : (int)HP_ERR_STATE;  // chain kernel(s) only
-            case 12: return a->slab ? enqueue_forward_backward_slab(a, nullptr, true, 2) : (int)HP_ERR_STATE;  // weight gradients + Adam only
+            case 11: return a->slab ? enqueue_forward_backward_slab(a, nullptr, 1, true) : (int)HP_ERR_STATE;  // chain kernel(s) only
+            case 12: return a->slab ? enqueue_forward_backward_slab(a, nullptr, 2, true) : (int)HP_ERR_STATE;  // weight gradients + Adam only
             default: hp_set_error("hp_agent_debug_chain: unknown kind %d", kind); return HP_ERR_INVALID;
         }
     };
