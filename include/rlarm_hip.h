@@ -672,6 +672,54 @@ int hp_episode_signal_stats_block(hp_rollout *ro, const float *pi_dev, const flo
                                   int64_t n_episodes, double max_action, double action_l2, double flat, double *stats_dev);
 int hp_episode_signal_summary(hp_ctx *ctx, const double *signal_stats_dev, int64_t n_episodes, double *summary_dev);
 
+/* ---- Bellman audit on the device -----------------------------------------------------------------
+ * The quantity the critic is trained on, for every step of an episode block: the residual of ddpg_agent.py:249-263,
+ *   y_t = clamp(r_t + gamma Q'(s_{t+1}, pi'(s_{t+1})), -1 / (1 - gamma), 0),   delta_t = y_t - Q(s_t, a_t).
+ * The critic audit sets Q beside the discounted return of the recorded episode, which for exploring episodes belongs to another
+ * policy than the one the target bootstraps from; a critic can sit far from that return and still have no TD error.
+ *
+ * hp_episode_bellman: for t = 0 .. T-1 of n_episodes episodes in ONE launch (an update's target chain and its critic forward, same
+ * device functions, 4-row slabs), all float32 [n][T]:
+ *   q_next_dev  Q'(s_{t+1}, pi'(s_{t+1})): target actor, then target critic, on obs[e][t + 1] and the row's goal G(e, t), the action
+ *               formed as (max_action * tanh) / max_action as hp_episode_policy forms it; pi' is not stored
+ *   q_dev       Q(s_t, a_t): the online critic on obs[e][t], G(e, t) and the recorded action; with HP_GOAL_DESIRED hp_episode_q's bits
+ *   r_dev       the reward of the transition under G(e, t): compute_reward on (ag[e][t + 1], G(e, t)), narrowed to float32 as the
+ *               learner narrows it; distance_threshold and reward_type (0 sparse, 1 dense) as for hp_episode_returns
+ *   y_dev       y = r + gamma * q_next; y = fminf(fmaxf(y, -clip_ret), 0) in float32, with the two float32 values the agent hands its
+ *               own update kernels (gamma and 1 / (1 - gamma) of its configuration): an update's target for that row
+ * goal_mode HP_GOAL_DESIRED: G(e, t) = g[e][t], the update's rule for an unrelabelled transition (g_next = g).  HP_GOAL_FINAL:
+ * G(e, t) = ag[e][T] for every t, the episode's last achieved goal -- the relabel under which every episode ends in success; g_dev
+ * is not read (it must still be given).  Arrays: obs_dev [n][T + 1][obs], ag_dev [n][T + 1][goal], g_dev [n][T][goal], actions_dev
+ * [n][T][act], float64; clip_obs as for hp_episode_q.  hp_episode_bellman_block is the same on episodes [first_episode,
+ * first_episode + n_episodes) of a block.  Both asynchronous on the context's stream (or a borrowed one), behind whatever wrote
+ * the weights; no copy, nothing allocated.  Refusals are hp_episode_policy's in its order, naming the entry point (the agent's
+ * shape: HP_ERR_STATE); behind the row count: goal_mode outside {0, 1}, then reward_type outside {0, 1} (HP_ERR_INVALID).
+ *
+ * hp_episode_bellman_stats: stats_dev [n][HP_BELLMAN_STATS] (float64) out of the four arrays.  With d_t = (double)y_t - (double)q_t:
+ *   [0] td_mean        sum_t d_t / T
+ *   [1] td_abs         sum_t |d_t| / T
+ *   [2] td_sq          sum_t d_t d_t / T: the critic loss of these rows
+ *   [3] target_mean    sum_t y_t / T
+ *   [4] clipped_share  #{t : r_t + (float)gamma * q_next_t, in float32, is not y_t} / T: the steps whose clamp changed the value
+ *   [5] reward_mean    sum_t r_t / T
+ * every float32 widened to float64, every sum started at 0 and accumulated in ascending t, every operation rounded on its own:
+ * synthetic.episode_bellman_stats is the same loop, so the bits are the host twin's.  gamma is narrowed to float32 as the agent
+ * narrows its own.  One wave per episode.  hp_episode_bellman_summary reduces n_episodes rows to the six column means, left to
+ * right in episode order (synthetic.episode_bellman_summary).  Asynchronous, nothing allocated; HP_ERR_INVALID, naming the entry
+ * point, for a null argument, n_episodes or T out of range as for hp_episode_stats, gamma outside [0, 1]. */
+#define HP_BELLMAN_STATS 6
+#define HP_GOAL_DESIRED 0
+#define HP_GOAL_FINAL 1
+int hp_episode_bellman(hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, int32_t goal_mode, const double *obs_dev, const double *ag_dev,
+                       const double *g_dev, const double *actions_dev, int64_t n_episodes, int32_t T, double distance_threshold,
+                       int32_t reward_type, double clip_obs, float *q_dev, float *q_next_dev, float *r_dev, float *y_dev);
+int hp_episode_bellman_block(hp_rollout *ro, hp_agent *ag, hp_norm *o_norm, hp_norm *g_norm, int32_t goal_mode, int64_t first_episode,
+                             int64_t n_episodes, double distance_threshold, int32_t reward_type, double clip_obs, float *q_dev,
+                             float *q_next_dev, float *r_dev, float *y_dev);
+int hp_episode_bellman_stats(hp_ctx *ctx, const float *q_dev, const float *q_next_dev, const float *r_dev, const float *y_dev,
+                             int64_t n_episodes, int32_t T, double gamma, double *stats_dev);
+int hp_episode_bellman_summary(hp_ctx *ctx, const double *bellman_stats_dev, int64_t n_episodes, double *summary_dev);
+
 /* Policy calls that do not queue behind training: hp_agent_policy_snapshot copies the online actor and both normalizers'
  * statistics (stream-ordered with the updates, no host wait); hp_agent_act_snapshot evaluates the most recent COMPLETE
  * snapshot on a second stream, so a feeder can step its environments while a training cycle runs (its policy lags the

@@ -75,6 +75,8 @@ EPISODE_STATS, EPISODE_SUMMARY, EPISODE_MAX_GOAL_DIM = 6, 6, 256   # HP_EPISODE_
 CRITIC_STATS = 6       # HP_CRITIC_STATS: the columns of synthetic.CRITIC_STATS
 POLICY_STATS = 6       # HP_POLICY_STATS: the columns of synthetic.POLICY_STATS
 SIGNAL_STATS = 6       # HP_SIGNAL_STATS: the columns of synthetic.SIGNAL_STATS
+BELLMAN_STATS = 6      # HP_BELLMAN_STATS: the columns of synthetic.BELLMAN_STATS
+GOAL_DESIRED, GOAL_FINAL = 0, 1   # HP_GOAL_DESIRED, HP_GOAL_FINAL: the goal a Bellman audit's rows are taken under
 ROLLOUT_MAX_LAUNCH_TIMESTEPS = 4096   # HP_ROLLOUT_MAX_LAUNCH_TIMESTEPS: what one launch of hp_rollout_waves holds at most
 
 
@@ -253,6 +255,14 @@ PROTOTYPES = {
     "hp_episode_signal_stats_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_double,
                                                 C.c_double, C.c_void_p]),
     "hp_episode_signal_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hp_episode_bellman": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "hp_episode_bellman_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_double,
+                                           C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hp_episode_bellman_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double,
+                                           C.c_void_p]),
+    "hp_episode_bellman_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "hp_agent_policy_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hp_agent_act_snapshot": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int64, C.c_double, f32p]),
     "hp_agent_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,

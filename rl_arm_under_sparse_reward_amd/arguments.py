@@ -46,6 +46,7 @@ class Args:
     eval_critic: bool = False           # learn(): also audit the critic on every evaluation's episodes, Q beside the discounted return (agent.eval_critic)
     audit_policy: bool = False          # learn(): once per epoch, audit the policy on the last cycle's exploring episodes, pi(s) and Q(s, pi(s)) beside the recorded actions (agent.policy_audit)
     audit_actor_signal: bool = False    # learn(): once per epoch, audit the actor's learning signal on the last cycle's exploring episodes, dQ/da at pi(s) beside the regulariser and the recorded actions (agent.actor_signal_audit)
+    audit_bellman: object = False       # learn(): False, "desired" or "final" -- once per epoch, audit the critic's TD error on the last cycle's exploring episodes under the desired goal or under each episode's final achieved goal (agent.bellman_audit)
     state_full_every: int = 0           # learn() with args.state_path: 0 = every save is a full state; k >= 1 = every k-th save
                                         # rewrites the base, the saves between rewrite one cumulative delta beside it (train_state.py)
     grad_reduce: str = "sum"            # data-parallel gradient exchange: "sum" = utils.py:47 (reference), or "mean"

@@ -1,5 +1,5 @@
-// episode_audit.h -- the frame the five units of the episode audit share (episode_stats.hip, episode_returns.hip, episode_q.hip,
-// episode_policy.hip, episode_action_grad.hip): the bound on episodes and steps, the refusals every entry makes of a block's shape, the range check of the
+// episode_audit.h -- the frame the six units of the episode audit share (episode_stats.hip, episode_returns.hip, episode_q.hip,
+// episode_policy.hip, episode_action_grad.hip, episode_bellman.hip): the bound on episodes and steps, the refusals every entry makes of a block's shape, the range check of the
 // *_block entries with the block's four arrays behind it, and the summary of a per-episode table.  The arithmetic of a step:
 // transition_device.h.
 #pragma once
@@ -9,7 +9,7 @@
 static_assert(HP_EPISODE_MAX_GOAL_DIM == NORM_MAX, "a goal is as wide as a normalizer can hold");
 constexpr int EPISODE_COLS = 6;    // columns of a per-episode table and of its summary
 static_assert(HP_EPISODE_STATS == EPISODE_COLS && HP_EPISODE_SUMMARY == EPISODE_COLS && HP_CRITIC_STATS == EPISODE_COLS &&
-              HP_POLICY_STATS == EPISODE_COLS, "one summary loop");
+              HP_POLICY_STATS == EPISODE_COLS && HP_BELLMAN_STATS == EPISODE_COLS, "one summary loop");
 
 // n_episodes, T, goal_dim, refused in this order under the entry's name (the entries of episode_q.hip and episode_policy.hip
 // take no goal_dim of their own -- theirs is the goal normalizer's, or none -- and leave it out)
@@ -47,7 +47,8 @@ __device__ __forceinline__ void episode_summary_body(const double *__restrict__ 
     for (int k = 0; k < EPISODE_COLS; ++k) out[k] = __ddiv_rn(sum[k], dn);
 }
 
-// the entry of a summary: hp_episode_stats_summary, hp_episode_critic_summary, hp_episode_policy_summary
+// the entry of a summary: hp_episode_stats_summary, hp_episode_critic_summary, hp_episode_policy_summary, hp_episode_signal_summary,
+// hp_episode_bellman_summary
 static inline int episode_summary_launch(const char *entry, hp_ctx *ctx, void (*kernel)(const double *, long long, double *),
                                          const double *table, int64_t n, double *out) {
     HP_REQUIRE(ctx && table && out, HP_ERR_INVALID, "%s: null argument", entry);

@@ -1,6 +1,6 @@
 // episode_returns.hip -- the discounted return every step of an episode block went on to collect, and the critic's Q beside it
-// (hp_episode_returns, hp_episode_returns_block, hp_episode_critic_summary; hp_episode_policy_summary and hp_episode_signal_summary
-// are the same kernel).  For
+// (hp_episode_returns, hp_episode_returns_block, hp_episode_critic_summary; hp_episode_policy_summary, hp_episode_signal_summary and
+// hp_episode_bellman_summary are the same kernel).  For
 // most of a sparse-reward run the success rate is zero; whether Q(s_t, a_t) (episode_q.hip) tracks G_t, sits on the target
 // clip -1 / (1 - gamma) (ddpg_agent.py:259-260) or overestimates is what says that learning is happening.
 //
@@ -85,7 +85,8 @@ __global__ __launch_bounds__(64) void k_episode_returns(const EpisodeReturnsArgs
 }
 
 // k_episode_column_means (episode_summary_body): the mean of every column of a per-episode table -- the critic's and the policy's
-// and the actor signal's (synthetic.episode_critic_summary, episode_policy_summary, episode_signal_summary: one loop)
+// the actor signal's and the Bellman audit's (synthetic.episode_critic_summary, episode_policy_summary, episode_signal_summary,
+// episode_bellman_summary: one loop)
 struct ColumnMeanTerm {
     __device__ double operator()(const double *r, int k) const { return r[k]; }
 };
@@ -146,6 +147,10 @@ int hp_episode_policy_summary(hp_ctx *ctx, const double *policy_stats_dev, int64
 
 int hp_episode_signal_summary(hp_ctx *ctx, const double *signal_stats_dev, int64_t n_episodes, double *summary_dev) {
     return episode_summary_launch("hp_episode_signal_summary", ctx, k_episode_column_means, signal_stats_dev, n_episodes, summary_dev);
+}
+
+int hp_episode_bellman_summary(hp_ctx *ctx, const double *bellman_stats_dev, int64_t n_episodes, double *summary_dev) {
+    return episode_summary_launch("hp_episode_bellman_summary", ctx, k_episode_column_means, bellman_stats_dev, n_episodes, summary_dev);
 }
 
 }  // extern "C"

@@ -155,6 +155,8 @@ class ddpg_agent(Rollouts, EpisodeAudit):
         self._policy_audit_pending = None
         self.actor_signal_audit = []     # args.audit_actor_signal: one dict per epoch, keyed by synthetic.SIGNAL_STATS
         self._actor_signal_pending = None
+        self.bellman_audit = []          # args.audit_bellman: one dict per epoch, keyed by synthetic.BELLMAN_STATS
+        self._bellman_pending = None
         self.model_path = os.path.join(self.args.save_dir, self.args.env_name)
 
     def _arg(self, name):
@@ -722,7 +724,7 @@ class ddpg_agent(Rollouts, EpisodeAudit):
                 self.train_cycle(episodes)
                 if not device:
                     hand_back()
-            self._queue_epoch_audits(episodes)       # args.audit_policy / args.audit_actor_signal: recorded by _finish_epoch
+            self._queue_epoch_audits(episodes)       # args.audit_policy / audit_actor_signal / audit_bellman: recorded by _finish_epoch
             self._finish_epoch(epoch, start, state_path, before_save=hand_back if device else None)
         if device:
             hand_back()
@@ -735,6 +737,7 @@ class ddpg_agent(Rollouts, EpisodeAudit):
         print(str(time.time() - start))
         self._record_policy_audit()      # args.audit_policy: before the evaluation, which may collect into the same block
         self._record_actor_signal_audit()     # args.audit_actor_signal: likewise
+        self._record_bellman_audit()          # args.audit_bellman: likewise
         rate = self._eval_agent()
         self.success_rates.append(rate)
         if self.comm.rank == 0:

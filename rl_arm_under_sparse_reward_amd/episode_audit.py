@@ -1,6 +1,6 @@
-"""The four audits of recorded episodes as the agent runs them: the metrics (hp_episode_stats*), the critic audit
-(hp_episode_q*, hp_episode_returns*), the policy audit (hp_episode_policy*) and the actor-signal audit (hp_episode_action_grad*,
-hp_episode_signal_stats*), each on a `DeviceEpisodes` block in place or on
+"""The five audits of recorded episodes as the agent runs them: the metrics (hp_episode_stats*), the critic audit
+(hp_episode_q*, hp_episode_returns*), the policy audit (hp_episode_policy*), the actor-signal audit (hp_episode_action_grad*,
+hp_episode_signal_stats*) and the Bellman audit (hp_episode_bellman*), each on a `DeviceEpisodes` block in place or on
 host episodes that are uploaded first, and what puts an epoch's summary onto the agent's lists.  `ddpg_agent` inherits these
 methods; they use its `lib`, `ctx`, `h`, `o_norm`, `g_norm`, `args`, `_arg`, `env_params`, `vec_env` and `comm`."""
 from __future__ import annotations
@@ -41,6 +41,15 @@ def _span(episodes, first, n):
     """(first, n) of a call on a `DeviceEpisodes`: n defaults to the episodes from `first` on"""
     first = int(first)
     return first, (len(episodes) - first if n is None else int(n))
+
+
+def _goal_mode(goal):
+    """HP_GOAL_DESIRED / HP_GOAL_FINAL of a Bellman audit's `goal`"""
+    if goal == "desired":
+        return _lib.GOAL_DESIRED
+    if goal == "final":
+        return _lib.GOAL_FINAL
+    raise ValueError(f"episode_bellman: goal {goal!r} is neither 'desired' nor 'final'")
 
 
 def _record(agent, names, summary, onto):
@@ -221,19 +230,71 @@ class EpisodeAudit:
         stats = self._signal_columns(None, 0, pi, dq_du, flat, act)
         return stats.cpu().numpy(), dq_du.cpu().numpy(), pi.cpu().numpy(), q_pi.cpu().numpy()
 
+    # ---- the Bellman residual: Q, Q' of the next state, reward and target of every step (hp_episode_bellman*) and its columns
+    def _bellman(self, episodes, first, n, T, goal, distance_threshold, obs=None, ag=None, g=None, act=None):
+        from .synthetic import _reward_kind
+        mode = _goal_mode(goal)
+        dev = torch.device("cuda", self.ctx.device_id)
+        q, q_next, r, y = out = tuple(torch.empty((max(n, 0), T), dtype=torch.float32, device=dev) for _ in range(4))
+        tail = (float(distance_threshold), _reward_kind(self._arg("reward_type")), float(self.args.clip_obs), *(_p(v) for v in out))
+        nets = (self.h, self.o_norm.h, self.g_norm.h, mode)
+        with self.ctx.torch_bridge():
+            if episodes is not None:
+                _lib.check(self.lib.hp_episode_bellman_block(episodes.h, *nets, first, n, *tail))
+            else:
+                _lib.check(self.lib.hp_episode_bellman(*nets, _p(obs), _p(ag), _p(g), _p(act), n, T, *tail))
+        return out
+
+    def _bellman_columns(self, q, q_next, r, y):
+        stats = torch.empty((q.shape[0], _lib.BELLMAN_STATS), dtype=torch.float64, device=q.device)
+        with self.ctx.torch_bridge():
+            _lib.check(self.lib.hp_episode_bellman_stats(self.ctx.h, _p(q), _p(q_next), _p(r), _p(y), q.shape[0], q.shape[1],
+                                                         float(self.args.gamma), _p(stats)))
+        return stats
+
+    def episode_bellman(self, episodes, goal="desired", distance_threshold=None, first=0, n=None):
+        """The quantity the critic is trained on, on episodes [first, first + n) of a `DeviceEpisodes` (a collection's, an
+        evaluation's, or `generate_demos(...).episodes`): (q, q_next, r, y), float32 device tensors [n, T] from one launch on
+        torch's current stream (hp_episode_bellman_block) -- q = Q(s_t, a_t) of the online critic, q_next =
+        Q'(s_{t+1}, pi'(s_{t+1})) of the target networks, r the transition's reward and y = clamp(r + gamma q_next,
+        -1 / (1 - gamma), 0) by an update's own float32 operations; the TD error is y - q.  goal="desired": under the block's own
+        goals, as an unrelabelled transition enters an update (q is `episode_q`'s bits).  goal="final": every step of an episode
+        under the goal the episode achieved last, the hindsight relabel under which every episode ends in success.  The
+        threshold defaults to `vec_env.distance_threshold`; gamma and reward_type are `args`'.  No copy, no synchronisation."""
+        if distance_threshold is None:
+            distance_threshold = self.vec_env.distance_threshold
+        return self._bellman(episodes, *_span(episodes, first, n), episodes.T, goal, distance_threshold)
+
+    def episode_bellman_stats(self, episodes, goal="desired", distance_threshold=None, first=0, n=None):
+        """The Bellman residual audited on episodes [first, first + n) of a `DeviceEpisodes`: (stats [n, 6] float64 in the
+        columns of `synthetic.BELLMAN_STATS`, q, q_next, r, y), device tensors from two launches (`episode_bellman`, the columns:
+        hp_episode_bellman_stats).  No copy, no synchronisation."""
+        out = self.episode_bellman(episodes, goal=goal, distance_threshold=distance_threshold, first=first, n=n)
+        return (self._bellman_columns(*out), *out)
+
+    def episode_bellman_stats_host(self, episode_batch, distance_threshold, goal="desired"):
+        """`episode_bellman_stats` for host episodes -- the four arrays `collect_episodes` returns, or a feeder slot's (obs, ag, g,
+        actions): they are uploaded, the same kernels run (hp_episode_bellman, hp_episode_bellman_stats) and the result comes
+        back as numpy (stats [n, 6] float64, q, q_next, r, y [n, T] float32).  Synchronises."""
+        obs, ag, g, act = _upload(self, episode_batch, "episode_bellman_stats_host")
+        n, T, _ = g.shape
+        out = self._bellman(None, 0, n, T, goal, distance_threshold, obs, ag, g, act)
+        return tuple(v.cpu().numpy() for v in (self._bellman_columns(*out), *out))
+
     def _column_means(self, entry, rows):
         """The column means of a per-episode table on the device, a float64 device tensor of rows.shape[1] values from one launch
-        of `entry` (hp_episode_stats_summary, hp_episode_critic_summary, hp_episode_policy_summary or hp_episode_signal_summary)"""
+        of `entry` (hp_episode_stats_summary, hp_episode_critic_summary, hp_episode_policy_summary, hp_episode_signal_summary or
+        hp_episode_bellman_summary)"""
         summary = torch.empty(rows.shape[1], dtype=torch.float64, device=rows.device)
         with self.ctx.torch_bridge():
             _lib.check(entry(self.ctx.h, _p(rows), rows.shape[0], _p(summary)))
         return summary
 
     def _queue_epoch_audits(self, episodes):
-        """args.audit_policy / args.audit_actor_signal: queue an epoch's last exploring episodes for `_record_policy_audit` /
-        `_record_actor_signal_audit`, under the networks as they now stand.  A `DeviceEpisodes`: the columns and their means are
-        launched now behind the cycle (four launches for the policy, then three for the signal: dQ/du at the policy, the columns,
-        their means), nothing waits, and the summary tensor is kept -- its 48 bytes are read behind the epoch's synchronise.
+        """args.audit_policy / args.audit_actor_signal / args.audit_bellman: queue an epoch's last exploring episodes for
+        `_record_policy_audit` / `_record_actor_signal_audit` / `_record_bellman_audit`, under the networks as they now stand.  A
+        `DeviceEpisodes`: the columns and their means are launched now behind the cycle (four launches for the policy, then three
+        for the signal: dQ/du at the policy, the columns, their means; then three for the Bellman residual), nothing waits, and the summary tensor is kept -- its 48 bytes are read behind the epoch's synchronise.
         Host arrays are kept as they are and audited there."""
         if episodes is None:
             return
@@ -244,6 +305,11 @@ class EpisodeAudit:
         if self._arg("audit_actor_signal"):
             self._actor_signal_pending = episodes if span is None else self._column_means(
                 self.lib.hp_episode_signal_summary, self.episode_signal_stats(episodes, **span)[0])
+        goal = self._arg("audit_bellman")
+        if goal:
+            _goal_mode(goal)
+            self._bellman_pending = episodes if span is None else self._column_means(
+                self.lib.hp_episode_bellman_summary, self.episode_bellman_stats(episodes, goal=goal, **span)[0])
 
     def _record_pending(self, pending, names, host_summary, onto):
         """An epoch's pending audit -- the device path's summary (six means, already computed) or the host path's episodes (audited
@@ -257,6 +323,18 @@ class EpisodeAudit:
         pending, self._actor_signal_pending = self._actor_signal_pending, None
         self._record_pending(pending, SIGNAL_STATS, lambda eps: episode_signal_summary(self.episode_signal_stats_host(eps)[0]),
                              self.actor_signal_audit)
+
+    def _record_bellman_audit(self):
+        """args.audit_bellman: the epoch's pending audit (host episodes: `episode_bellman_stats_host` at the environment's
+        threshold, as the host evaluation takes it) onto `bellman_audit`"""
+        from .synthetic import BELLMAN_STATS, episode_bellman_summary
+        pending, self._bellman_pending = self._bellman_pending, None
+
+        def host_summary(eps):
+            thr = self.env.distance_threshold if hasattr(self.env, "distance_threshold") else self._arg("distance_threshold")
+            return episode_bellman_summary(self.episode_bellman_stats_host(eps, thr, goal=self._arg("audit_bellman"))[0])
+
+        self._record_pending(pending, BELLMAN_STATS, host_summary, self.bellman_audit)
 
     def _record_eval_metrics(self, summary):
         """One evaluation's summary (this rank's six means), averaged over the ranks like the success rate, onto `eval_metrics`"""

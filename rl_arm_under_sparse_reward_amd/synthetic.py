@@ -741,6 +741,69 @@ def episode_signal_summary(stats):
     return _column_means("episode_signal_summary", SIGNAL_STATS, stats)
 
 
+BELLMAN_STATS = ("td_mean", "td_abs", "td_sq", "target_mean", "clipped_share", "reward_mean")
+
+
+def bellman_constants(gamma):
+    """(gamma32, clip32): the two float32 values an agent with `args.gamma` hands its update kernels -- gamma narrowed, and
+    1 / (1 - gamma) formed in float64 and narrowed (ddpg_agent.py:259)."""
+    gamma = float(gamma)
+    if not 0.0 <= gamma < 1.0:
+        raise ValueError(f"gamma {gamma} outside [0, 1)")
+    return np.float32(gamma), np.float32(1.0 / (1.0 - gamma))
+
+
+def episode_bellman_targets(q_next, r, gamma32, clip32):
+    """The host twin of the target of hp_episode_bellman: `q_next` and `r` [n, T] float32 -> y [n, T] float32 by the update's two
+    float32 operations, y = r + gamma32 * q_next; y = min(max(y, -clip32), 0) (ddpg_agent.py:256-260), one rounding each."""
+    q_next, r = np.asarray(q_next), np.asarray(r)
+    if q_next.dtype != np.float32 or r.dtype != np.float32 or q_next.ndim != 2 or r.shape != q_next.shape:
+        raise ValueError("episode_bellman_targets: q_next [n, T] float32 and r [n, T] float32 expected")
+    gamma32, clip32 = np.float32(gamma32), np.float32(clip32)
+    y = r + gamma32 * q_next
+    return np.minimum(np.maximum(y, -clip32), np.float32(0.0))
+
+
+def episode_bellman_stats(q, q_next, r, y, gamma32):
+    """The host twin of hp_episode_bellman_stats, as plain loops: `q`, `q_next`, `r`, `y` [n, T] float32 -> [n, 6] float64 in the
+    columns of BELLMAN_STATS.  With d = float64(y) - float64(q) per step: td_mean, the mean of d; td_abs, the mean of |d|; td_sq,
+    the mean of d * d -- the critic loss of these rows; target_mean, the mean of y; clipped_share, the share of steps where
+    r + gamma32 * q_next, the target's own float32 expression, is not y -- the clamp changed the value; reward_mean, the mean of
+    r.  Every sum starts at 0 and runs in ascending t, one rounding per operation, and is divided once at the end (so a mean of
+    rewards that are all -0.0 is +0.0: the sums begin at +0.0)."""
+    q, q_next, r, y = (np.asarray(v) for v in (q, q_next, r, y))
+    if any(v.dtype != np.float32 or v.shape != q.shape for v in (q, q_next, r, y)) or q.ndim != 2 or q.shape[1] < 1:
+        raise ValueError("episode_bellman_stats: q, q_next, r and y [n, T] float32 expected")
+    gamma32 = np.float32(gamma32)
+    if not 0.0 <= float(gamma32) <= 1.0:
+        raise ValueError(f"gamma {float(gamma32)} outside [0, 1]")
+    n, T = q.shape
+    raw = r + gamma32 * q_next               # float32, one rounding per operation
+    changed = (raw != y).tolist()
+    out = np.empty((n, len(BELLMAN_STATS)), dtype=np.float64)
+    for e in range(n):
+        qs, ys, rs = (v[e].astype(np.float64).tolist() for v in (q, y, r))    # Python floats from here on: IEEE float64
+        sum_d = sum_abs = sum_sq = sum_y = sum_r = 0.0
+        clipped = 0
+        for t in range(T):
+            d = ys[t] - qs[t]
+            sum_d = sum_d + d
+            sum_abs = sum_abs + abs(d)
+            sum_sq = sum_sq + d * d
+            sum_y = sum_y + ys[t]
+            sum_r = sum_r + rs[t]
+            clipped += 1 if changed[e][t] else 0
+        dT = float(T)
+        out[e] = (sum_d / dT, sum_abs / dT, sum_sq / dT, sum_y / dT, float(clipped) / dT, sum_r / dT)
+    return out
+
+
+def episode_bellman_summary(stats):
+    """The host twin of hp_episode_bellman_summary: the six column means over the episodes, each a left-to-right float64 sum in
+    episode order divided by their number."""
+    return _column_means("episode_bellman_summary", BELLMAN_STATS, stats)
+
+
 def write_demo_npz_from(path, obs, ag, g, actions, info):
     """Write episodes in the schema get_demo_data_push.py:91-94 produces: keys acs, obs, info, g, ag, with `info` an object
     array [n, T] of per-step dicts {'is_success': float32} (`info` here: the flags [n, T]).  Such a file preloads through

@@ -1,0 +1,375 @@
+"""The Bellman audit on the device (csrc/episode_bellman.hip: hp_episode_bellman, hp_episode_bellman_block,
+hp_episode_bellman_stats, hp_episode_bellman_summary; ddpg_agent.episode_bellman, episode_bellman_stats,
+episode_bellman_stats_host, args.audit_bellman).
+
+q = Q(s_t, a_t) and q_next = Q'(s_{t+1}, pi'(s_{t+1})) are compared with the oracle's actor and critic
+(oracle.ddpg_update.actor_forward / critic_forward, the whole chain on the host) on rows prepared in numpy, at the project's bar
+for a forward, rtol 1e-5 / atol 1e-6, no row excluded; y against the oracle's clamped target at the same bar (the clamp is
+1-Lipschitz and gamma < 1).  r is compared bit for bit with compute_reward, y with synthetic.episode_bellman_targets fed the device's
+q_next and r, q with hp_episode_q, q_next with hp_episode_policy(target) one step on, the columns and their summary with the host
+twins."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import bellman_cases as cases
+from conftest import bits
+from gpu_common import ctx, fresh_rng
+from rl_arm_under_sparse_reward_amd import _lib
+from rl_arm_under_sparse_reward_amd import train_state as ts
+from rl_arm_under_sparse_reward_amd.arguments import Args
+from rl_arm_under_sparse_reward_amd.ddpg_agent import NET_ACTOR, NET_ACTOR_TARGET, NET_CRITIC, NET_CRITIC_TARGET, ddpg_agent
+from rl_arm_under_sparse_reward_amd.device_env import NativePickPlaceVecEnv, NativePointMassVecEnv, NativePushBlockVecEnv, generate_demos
+from rl_arm_under_sparse_reward_amd.goal_env import GoalDistanceReward
+from rl_arm_under_sparse_reward_amd.synthetic import (BELLMAN_STATS, bellman_constants, episode_bellman_stats, episode_bellman_summary,
+                                                      episode_bellman_targets)
+from test_gpu_device_reset import agent_on as point_agent_on
+from test_gpu_device_rollout import make, primed
+from test_gpu_episode_critic import oracle_q, raw_q, refused, shaped_agent
+from test_gpu_episode_policy import move_actor, oracle_policy, raw_policy, tree_bytes
+from test_gpu_episode_stats import learner
+from test_gpu_pick_place import agent_on as pick_agent_on
+from test_gpu_push_block import CONTACT, agent_on as push_agent_on
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+RTOL, ATOL = 1e-5, 1e-6
+p = lambda t: C.c_void_p(t.data_ptr())
+host = lambda *ts_: [v.cpu().numpy() for v in ts_]
+GUARD = 4        # rows behind the block in every output: the last slab's dead rows store nothing
+NAMES = ("q", "q_next", "r", "y")
+
+
+# ------------------------------------------------------------------------------------------ helpers
+def raw_bellman(agent, obs, ag, g, actions, goal, thr, kind="sparse"):
+    """hp_episode_bellman on uploaded arrays, into poisoned tensors with GUARD rows behind them: (q, q_next, r, y) [n, T]"""
+    arrays = [torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(DEV) for v in (obs, ag, g, actions)]
+    n, T = g.shape[:2]
+    out = [torch.full((n * T + GUARD,), float("nan"), dtype=torch.float32, device=DEV) for _ in NAMES]
+    with agent.ctx.torch_bridge():
+        _lib.check(agent.lib.hp_episode_bellman(agent.h, agent.o_norm.h, agent.g_norm.h, cases.GOALS.index(goal), *(p(v) for v in arrays),
+                                                n, T, float(thr), cases.KINDS.index(kind), float(agent.args.clip_obs), *(p(v) for v in out)))
+    out = host(*out)
+    assert all(np.isnan(v[n * T:]).all() and not np.isnan(v[:n * T]).any() for v in out), (goal, kind)
+    return [v[:n * T].reshape(n, T) for v in out]
+
+
+def reward_of(ag, G, thr, kind):
+    """compute_reward on (ag[:, 1:], G), narrowed to float32 as the learner narrows it"""
+    return GoalDistanceReward(thr, kind, ctx=ctx()).compute_reward(ag[:, 1:], G).astype(np.float32)
+
+
+def oracle_bellman(agent, obs, ag, g, actions, goal, thr, kind):
+    """The oracle's q, q_next and y from the agent's CURRENT parameters and statistics, rows prepared in numpy"""
+    G = cases.goals_of(ag, g, goal)
+    q = oracle_q(agent, obs, G, actions)[0]
+    shifted = np.concatenate([obs[:, 1:], obs[:, :1]], axis=1)          # oracle_policy reads rows 0 .. T-1: s_{t+1}
+    q_next = oracle_policy(agent, shifted, G, target=True)[1]
+    gamma32, clip32 = bellman_constants(agent.args.gamma)
+    y = torch.clamp(torch.from_numpy(reward_of(ag, G, thr, kind)) + float(gamma32) * torch.from_numpy(q_next), -float(clip32), 0.0)
+    return q, q_next, y.numpy()
+
+
+def assert_close(got, want, what):
+    err = float(np.abs(got.astype(np.float64) - want.astype(np.float64)).max())
+    assert got.dtype == np.float32 and got.shape == want.shape and np.isfinite(got).all(), what
+    assert np.allclose(got, want, rtol=RTOL, atol=ATOL), (what, err)
+    return err
+
+
+def assert_consistent(agent, obs, ag, g, actions, goal, thr, kind, out, what):
+    """What holds bit for bit of one launch's four arrays"""
+    q, q_next, r, y = out
+    G = cases.goals_of(ag, g, goal)
+    assert np.array_equal(bits(r), bits(reward_of(ag, G, thr, kind))), what
+    assert np.array_equal(bits(y), bits(episode_bellman_targets(q_next, r, *bellman_constants(agent.args.gamma)))), what
+    assert np.array_equal(bits(q), bits(raw_q(agent, obs, G, actions))), what
+    if goal == "final":
+        zero = GoalDistanceReward(thr, kind, ctx=ctx()).compute_reward(ag[:, -1], ag[:, -1]).astype(np.float32)
+        assert np.array_equal(bits(r[:, -1]), bits(zero)) and (r[:, -1] == 0).all(), what          # the reward of distance 0
+
+
+def twin_of(agent, stats, q, q_next, r, y):
+    """The six columns of an audit against the twin fed the device's arrays, by bytes"""
+    stats, q, q_next, r, y = (v.cpu().numpy() if isinstance(v, torch.Tensor) else v for v in (stats, q, q_next, r, y))
+    want = episode_bellman_stats(q, q_next, r, y, bellman_constants(agent.args.gamma)[0])
+    assert stats.dtype == np.float64 and stats.shape == (q.shape[0], 6) and np.array_equal(bits(stats), bits(want)), (stats, want)
+    return want
+
+
+def device_columns(agent, q, q_next, r, y):
+    """hp_episode_bellman_stats and hp_episode_bellman_summary on uploaded arrays, into poisoned tensors with a guard row"""
+    n, T = q.shape
+    arrays = [torch.from_numpy(np.ascontiguousarray(v)).to(DEV) for v in (q, q_next, r, y)]
+    stats = torch.full((n + 1, 6), float("nan"), dtype=torch.float64, device=DEV)
+    summary = torch.full((7,), float("nan"), dtype=torch.float64, device=DEV)
+    with agent.ctx.torch_bridge():
+        _lib.check(agent.lib.hp_episode_bellman_stats(agent.ctx.h, *(p(v) for v in arrays), n, T, float(agent.args.gamma), p(stats)))
+        _lib.check(agent.lib.hp_episode_bellman_summary(agent.ctx.h, p(stats), n, p(summary)))
+    stats, summary = host(stats, summary)
+    assert np.isnan(stats[n]).all() and np.isnan(summary[6])
+    return stats[:n], summary[:6]
+
+
+# ------------------------------------------------------------------------------------------ 1. against the oracle, and bit for bit
+@pytest.mark.parametrize("shape", cases.SHAPES)
+def test_q_q_next_r_and_y_of_random_blocks(shape):
+    agent = move_actor(shaped_agent(*shape), shape[0])
+    thr, far, default_clip = cases.THRESHOLD, dict.fromkeys(("q", "q_next", "y"), 0.0), agent.args.clip_obs
+    for block in cases.BLOCKS:
+        obs, ag, g, actions = cases.block_inputs(shape, block)
+        for clip_obs in cases.CLIPS:
+            agent.args.clip_obs = clip_obs
+            if clip_obs < 1.0 and block[0] * block[1] > 4:
+                assert np.mean(np.abs(obs) > clip_obs) > 0.1          # the clip bites
+            modes = {}
+            for goal in cases.GOALS:
+                for kind in cases.KINDS:
+                    what = f"{shape} block {block} clip_obs {clip_obs} goal {goal} reward {kind}"
+                    out = modes[goal, kind] = raw_bellman(agent, obs, ag, g, actions, goal, thr, kind)
+                    want = oracle_bellman(agent, obs, ag, g, actions, goal, thr, kind)
+                    for name, got, w in zip(("q", "q_next", "y"), (out[0], out[1], out[3]), want):
+                        far[name] = max(far[name], assert_close(got, w, f"{what}: {name}"))
+                    assert_consistent(agent, obs, ag, g, actions, goal, thr, kind, out, what)
+                    stats, summary = device_columns(agent, *out)
+                    twin = twin_of(agent, stats, *out)
+                    assert np.array_equal(bits(summary), bits(episode_bellman_summary(twin))), what
+                # the reward kind moves r and y alone
+                for k in (0, 1):
+                    assert np.array_equal(bits(modes[goal, "sparse"][k]), bits(modes[goal, "dense"][k]))
+            if block[0] * block[1] > 4:
+                sparse = modes["desired", "sparse"][2]
+                assert (sparse == 0).any() and (sparse == -1).any() and not np.array_equal(sparse, modes["desired", "dense"][2])
+                assert not np.array_equal(modes["desired", "sparse"][0], modes["final", "sparse"][0])
+            # final mode is desired mode on arrays whose g was overwritten with the last achieved goal
+            over = raw_bellman(agent, obs, ag, cases.goals_of(ag, g, "final"), actions, "desired", thr)
+            for x, w in zip(over, modes["final", "sparse"]):
+                assert np.array_equal(bits(x), bits(w)), (shape, block, clip_obs)
+            # g constant along each episode: q_next of step t is the target networks' Q(s, pi(s)) of step t + 1
+            T = block[1]
+            if T > 1:
+                g_const = np.repeat(g[:, :1], T, axis=1)
+                q_next = raw_bellman(agent, obs, ag, g_const, actions, "desired", thr)[1]
+                q_pi = raw_policy(agent, obs, g_const, target=True)[1]
+                assert np.array_equal(bits(q_next[:, :-1]), bits(q_pi[:, 1:])), (shape, block, clip_obs)
+    agent.args.clip_obs = default_clip
+    print(f"{shape}: largest |device - oracle|: q {far['q']:.3e}, q_next {far['q_next']:.3e}, y {far['y']:.3e}")
+
+
+# ------------------------------------------------------------------------------------------ 2. blocks in place
+def assert_block_equals_plain(a, eps, batch, spans):
+    """episode_bellman on a block in place against the plain entry on the same arrays copied to the host, both goal modes"""
+    thr = a.vec_env.distance_threshold
+    for goal in cases.GOALS:
+        whole = raw_bellman(a, *batch, goal, thr, a._arg("reward_type"))
+        assert_consistent(a, *batch, goal, thr, a._arg("reward_type"), whole, goal)
+        for first, n in spans:
+            got = host(*a.episode_bellman(eps, goal=goal, first=first, n=n))
+            stop = len(eps) if n is None else first + n
+            for name, x, w in zip(NAMES, got, whole):
+                assert x.dtype == np.float32 and np.array_equal(bits(x), bits(w[first:stop])), (goal, first, n, name)
+        stats, *arrays = a.episode_bellman_stats(eps, goal=goal)
+        assert stats.is_cuda and all(v.dtype == torch.float32 and tuple(v.shape) == batch[2].shape[:2] for v in arrays)
+        twin_of(a, stats, *arrays)
+        out = a.episode_bellman_stats_host(batch, thr, goal=goal)
+        assert len(out) == 5 and all(isinstance(v, np.ndarray) for v in out)
+        for x, w in zip(out, host(stats, *arrays)):
+            assert x.dtype == w.dtype and np.array_equal(bits(x), bits(w)), goal
+    return whole
+
+
+def test_a_point_mass_collection_in_place():
+    a = move_actor(point_agent_on(2, 10, random_eps=0.3), 3)
+    eps = a.collect_episodes_device(n_rollouts=3)
+    final = assert_block_equals_plain(a, eps, eps.numpy(), ((0, None), (1, 2), (2, 1)))
+    assert (final[2][:, -1] == 0).all()
+    with pytest.raises(ValueError, match="outside the block of 3"):
+        a.episode_bellman(eps, first=2, n=2)
+    with pytest.raises(ValueError, match="neither 'desired' nor 'final'"):
+        a.episode_bellman(eps, goal="future")
+    with pytest.raises(ValueError, match="episode_bellman_stats_host: obs"):
+        batch = eps.numpy()
+        a.episode_bellman_stats_host([batch[0], batch[1][:, :-1], batch[2], batch[3]], 0.15)
+
+
+def primed_agent(env, T):
+    a = make(env, T=T)
+    primed(a)
+    return a
+
+
+def test_a_push_block_collection_in_place():
+    a = move_actor(push_agent_on(NativePushBlockVecEnv, 8, env_kw=CONTACT, random_eps=0.3), 5)
+    eps = a.collect_episodes_device(n_rollouts=9)
+    assert_block_equals_plain(a, eps, eps.numpy(), ((0, None), (3, 4), (8, 1), (1, 8)))
+
+
+def test_a_pick_and_place_collection_and_demonstrations_in_place():
+    a = move_actor(pick_agent_on(NativePickPlaceVecEnv, 3, T=10, random_eps=0.3), 7)
+    eps = a.collect_episodes_device(n_rollouts=5, epoch=0)
+    assert_block_equals_plain(a, eps, eps.numpy(), ((0, None), (2, 3)))
+    env = NativePickPlaceVecEnv(4, seed=0, device=DEV, max_timesteps=100, step_scale=0.2)
+    env.enable_device_reset(ctx())
+    demos = generate_demos(env, 4)
+    assert demos.kept == 4
+    torch.manual_seed(0)
+    b = move_actor(primed_agent(env, 100), 9)
+    whole = assert_block_equals_plain(b, demos.episodes, demos.numpy()[:4], ((0, None), (1, 2)))
+    print("reward_mean of the demonstrations under their final goal:", whole[2].mean(axis=1))
+
+
+# ------------------------------------------------------------------------------------------ 3. learn()
+def test_audit_bellman_is_the_twins_and_changes_nothing_else(tmp_path, capsys):
+    """Two epochs of learn() on two native point-mass environments with the option off, "desired" and "final" (audit_policy on in
+    all three): the same rates, policy audit, printed lines, checkpoint files, training state and streams to the byte, an empty
+    list with it off; with it on, one dict per epoch, and they are the twins' on what the device computed."""
+    kw = dict(audit_policy=True)
+    runs = {mode: learner(tmp_path, str(mode), False, audit_bellman=mode, state_path=str(tmp_path / f"{mode}.npz"), **kw)
+            for mode in (False, "desired", "final")}
+    kept = {mode: [] for mode in runs}
+    for mode, a in runs.items():
+        def audit_and_keep(eps, audit=a.episode_bellman_stats, mode=mode, a=a, **kwargs):
+            out = audit(eps, **kwargs)
+            assert kwargs["goal"] == mode and kwargs["n"] == a.args.num_rollouts_per_mpi
+            kept[mode].append(host(*out))
+            return out
+        a.episode_bellman_stats = audit_and_keep
+    printed, finals = {}, {}
+    for mode, a in runs.items():
+        np.random.seed(11)
+        a.learn()
+        printed[mode] = [line for line in capsys.readouterr().out.splitlines() if "eval success rate" in line or "buffer size" in line]
+        finals[mode] = (a.rng.get_state(), np.random.get_state())
+    off = runs[False]
+    assert off.bellman_audit == [] and kept[False] == []
+    strip = lambda lines: [line.split("] ", 1)[-1] for line in lines]
+    files_off = tree_bytes(tmp_path / "False")
+    state_off = ts.read_state(ts.rank_path(str(tmp_path / "False.npz"), 0))
+    for mode in ("desired", "final"):
+        on = runs[mode]
+        assert len(on.bellman_audit) == 2 and len(on.success_rates) == 2 and len(kept[mode]) == 2
+        assert on.success_rates == off.success_rates and on.policy_audit == off.policy_audit and len(on.policy_audit) == 2
+        assert on.eval_metrics == off.eval_metrics and on.eval_critic == off.eval_critic and on.actor_signal_audit == off.actor_signal_audit
+        assert strip(printed[mode]) == strip(printed[False]) and len(printed[mode]) == 3
+        for x, y in zip(finals[mode], finals[False]):                     # the device stream and numpy's, as learn() leaves them
+            assert all(np.array_equal(u, v) for u, v in zip(x, y))
+        files_on = tree_bytes(tmp_path / mode)
+        assert sorted(files_on) == sorted(files_off) and len(files_on) >= 1 and all(files_on[k] == files_off[k] for k in files_on)
+        for slot in (NET_ACTOR, NET_CRITIC, NET_ACTOR_TARGET, NET_CRITIC_TARGET):
+            assert np.array_equal(bits(on._get_flat(slot)), bits(off._get_flat(slot))), slot
+        state_on = ts.read_state(ts.rank_path(str(tmp_path / f"{mode}.npz"), 0))
+        assert sorted(state_on[0]) == sorted(state_off[0])
+        for name in state_on[0]:
+            assert np.array_equal(bits(state_on[0][name]), bits(state_off[0][name])), name
+        for m, (stats, q, q_next, r, y) in zip(on.bellman_audit, kept[mode]):
+            assert tuple(m) == BELLMAN_STATS
+            want = twin_of(on, stats, q, q_next, r, y)
+            assert np.array_equal(bits(np.array([m[k] for k in BELLMAN_STATS])), bits(episode_bellman_summary(want))), (m, want)
+            assert m["td_abs"] > 0 and m["td_sq"] > 0 and 0 <= m["clipped_share"] <= 1 and -1 <= m["reward_mean"] <= 0
+            if mode == "final":
+                assert (r[:, -1] == 0).all()
+        assert not np.array_equal(kept[mode][0][1], kept[mode][1][1])          # two collections, two sets of weights
+    assert runs["desired"].bellman_audit != runs["final"].bellman_audit
+
+
+def test_audit_bellman_on_the_host_path(tmp_path, capsys):
+    """learn() with a host environment goes through episode_bellman_stats_host on the last collect_episodes result, and leaves the
+    run as it is without the option"""
+    from rl_arm_under_sparse_reward_amd.synthetic import PointMassGoalEnv
+    runs = []
+    for audit in ("final", False):
+        torch.manual_seed(0)
+        np.random.seed(11)
+        env = PointMassGoalEnv(seed=30, max_timesteps=10, distance_threshold=0.15)
+        a = make(env, T=10, seed=5, n_epochs=2, n_cycles=2, n_batches=2, n_test_rollouts=2, buffer_episodes=40, num_rollouts_per_mpi=2,
+                 save_dir=str(tmp_path / f"host{audit}"), env_name="pm", audit_bellman=audit)
+        primed(a)
+        if audit:
+            stats_host, kept = a.episode_bellman_stats_host, []
+            a.episode_bellman_stats_host = lambda batch, thr, **kwargs: kept.append((thr, kwargs, stats_host(batch, thr, **kwargs))) or kept[-1][2]
+        a.learn()
+        capsys.readouterr()
+        runs.append((a, [a._get_flat(s) for s in (NET_ACTOR, NET_CRITIC)], np.random.get_state()))
+    (a, flat_a, np_a), (b, flat_b, np_b) = runs
+    assert b.bellman_audit == [] and len(a.bellman_audit) == 2 and a.success_rates == b.success_rates
+    assert all(np.array_equal(bits(x), bits(y)) for x, y in zip(flat_a, flat_b))
+    assert all(np.array_equal(u, v) for u, v in zip(np_a, np_b))
+    assert len(kept) == 2
+    for m, (thr, kwargs, out) in zip(a.bellman_audit, kept):
+        assert thr == 0.15 and kwargs == dict(goal="final") and tuple(m) == BELLMAN_STATS and out[1].shape == (2, 10)
+        want = twin_of(a, *out)
+        assert np.array_equal(bits(np.array([m[k] for k in BELLMAN_STATS])), bits(episode_bellman_summary(want)))
+
+
+# ------------------------------------------------------------------------------------------ 4. refusals
+def test_refusals_carry_the_librarys_message():
+    torch.manual_seed(0)
+    a = primed_agent(NativePointMassVecEnv(2, seed=1, device=DEV, max_timesteps=10), 10)
+    lib, c = a.lib, a.ctx
+    eps = a.collect_episodes_device(n_rollouts=3, explore=False)
+    obs, ag = (torch.zeros((3, 11, k), dtype=torch.float64, device=DEV) for k in (27, 3))
+    g, act = (torch.zeros((3, 10, k), dtype=torch.float64, device=DEV) for k in (3, 4))
+    poison = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=DEV)
+    q, qn, r, y = outs = [poison(4, 10) for _ in NAMES]
+    stats, summary = (torch.full(shape, float("nan"), dtype=torch.float64, device=DEV) for shape in ((4, 6), (6,)))
+    h, on, gn = a.h, a.o_norm.h, a.g_norm.h
+    swap = lambda k, x: [x if i == k else v for i, v in enumerate(good)]
+    # hp_episode_bellman
+    name = "hp_episode_bellman"
+    good = [h, on, gn, 0, p(obs), p(ag), p(g), p(act), 3, 10, 0.05, 0, 200.0, p(q), p(qn), p(r), p(y)]
+    for k in (0, 1, 2, 4, 5, 6, 7, 13, 14, 15, 16):
+        refused(lib.hp_episode_bellman(*swap(k, None)), f"{name}: null argument")
+    other = _lib.Context(0)                                     # a second context on the same device
+    from rl_arm_under_sparse_reward_amd.normalizer import normalizer
+    foreign = normalizer(27, default_clip_range=5, ctx=other)
+    refused(lib.hp_episode_bellman(*swap(1, foreign.h)), f"{name}: handles belong to different contexts")
+    refused(lib.hp_episode_bellman(*swap(1, gn)), rf"{name}: normalizer sizes 3\+3 do not match the network input 30")
+    refused(lib.hp_episode_bellman(*swap(8, 0)), rf"{name}: n_episodes 0 outside \[1, ")
+    refused(lib.hp_episode_bellman(*swap(9, 0)), rf"{name}: T 0 outside \[1, ")
+    refused(lib.hp_episode_bellman(*[(1 << 23) if i == 8 else (1 << 20) if i == 9 else v for i, v in enumerate(good)]),
+            f"{name}: .* more than one launch holds")
+    for mode in (2, -1):
+        refused(lib.hp_episode_bellman(*swap(3, mode)), f"{name}: goal_mode {mode} is neither 0")
+    refused(lib.hp_episode_bellman(*swap(11, 2)), f"{name}: reward_type 2 is neither 0")
+    # the order: the agent's shape before the normalizers, the shape of the block before the goal mode
+    refused(lib.hp_episode_bellman(*[0 if i == 8 else 5 if i == 3 else v for i, v in enumerate(good)]), rf"{name}: n_episodes 0 outside")
+    narrow = ddpg_agent(Args(batch_size=64, buffer_size=80), None,
+                        {"obs": 27, "goal": 3, "action": 4, "action_max": 0.5, "max_timesteps": 10, "hidden": 128}, rng=fresh_rng(5))
+    refused(lib.hp_episode_bellman(narrow.h, narrow.o_norm.h, narrow.g_norm.h, 0, *good[4:]),
+            rf"{name}: the agent is not slab-shaped \(hidden 128", code=-5)
+    # hp_episode_bellman_block
+    name = "hp_episode_bellman_block"
+    good = [eps.h, h, on, gn, 0, 0, 3, 0.05, 0, 200.0, p(q), p(qn), p(r), p(y)]
+    for k in (0, 1, 2, 3, 10, 11, 12, 13):
+        refused(lib.hp_episode_bellman_block(*swap(k, None)), f"{name}: null argument")
+    refused(lib.hp_episode_bellman_block(*swap(2, foreign.h)), f"{name}: handles belong to different contexts")
+    for first, n in ((0, 4), (2, 2), (-1, 2), (0, 0)):
+        refused(lib.hp_episode_bellman_block(*[first if i == 5 else n if i == 6 else v for i, v in enumerate(good)]),
+                rf"{name}: episodes \[{first}, {first + n}\) outside the block of 3")
+    refused(lib.hp_episode_bellman_block(*swap(4, 7)), f"{name}: goal_mode 7 is neither 0")
+    refused(lib.hp_episode_bellman_block(*swap(8, -1)), f"{name}: reward_type -1 is neither 0")
+    refused(lib.hp_episode_bellman_block(eps.h, narrow.h, narrow.o_norm.h, narrow.g_norm.h, *good[4:]),
+            rf"{name}: the agent is not slab-shaped \(hidden 128", code=-5)
+    small = ddpg_agent(Args(batch_size=64, buffer_size=160), None,
+                       {"obs": 20, "goal": 1, "action": 3, "action_max": 0.7, "max_timesteps": 20}, rng=fresh_rng(5))
+    refused(lib.hp_episode_bellman_block(eps.h, small.h, small.o_norm.h, small.g_norm.h, *good[4:]),
+            f"{name}: the block has dimensions 27 / 3 / 4, normalizers and agent have 20 / 1 / 3")
+    # hp_episode_bellman_stats, hp_episode_bellman_summary
+    name = "hp_episode_bellman_stats"
+    good = [c.h, p(q), p(qn), p(r), p(y), 3, 10, 0.98, p(stats)]
+    for k in (0, 1, 2, 3, 4, 8):
+        refused(lib.hp_episode_bellman_stats(*swap(k, None)), f"{name}: null argument")
+    refused(lib.hp_episode_bellman_stats(*swap(5, 0)), rf"{name}: n_episodes 0 outside \[1, ")
+    refused(lib.hp_episode_bellman_stats(*swap(6, 0)), rf"{name}: T 0 outside \[1, ")
+    for gamma in (-0.1, 1.5, float("nan")):
+        refused(lib.hp_episode_bellman_stats(*swap(7, gamma)), rf"{name}: gamma .* outside \[0, 1\]")
+    name = "hp_episode_bellman_summary"
+    refused(lib.hp_episode_bellman_summary(None, p(stats), 3, p(summary)), f"{name}: null argument")
+    refused(lib.hp_episode_bellman_summary(c.h, None, 3, p(summary)), f"{name}: null argument")
+    refused(lib.hp_episode_bellman_summary(c.h, p(stats), 3, None), f"{name}: null argument")
+    refused(lib.hp_episode_bellman_summary(c.h, p(stats), 0, p(summary)), f"{name}: n_episodes 0 is not positive")
+    c.synchronize()
+    for v in outs + [stats, summary]:
+        assert torch.isnan(v).all()                          # a refused call launches nothing: the poison is intact
