@@ -20,39 +20,21 @@
 // Which weights: the online set's three buffers (a->fragF, a->fragD, a->params; episode_q.hip's header), the critic's segment at
 // la.total.  The target networks keep no dX-order fragments (slab_net, policy_call.h: fragFT and targets alone -- no update ever
 // differentiates through them), and this audit builds no second set: target = 1 is refused with HP_ERR_STATE.
-#include <cmath>
-
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wundefined-inline"   // agent_device.h declares the 32-row engine's fragment map, which no code here calls
-#include "agent_device.h"
-#pragma clang diagnostic pop
-
-// the 4-row slab's device functions (no kernel of slab8.h is compiled here).  S8_NRG stays defined: critic_action_grad_slab below
-// is written in the slab height's macros (S8_ROWS, S8_RPW) like the functions of slab8.h
-#define S8_DEVICE_ONLY
-#define S8_NRG 1
-#define S8_NS s8ag
-#include "slab8.h"
-#undef S8_NS
-#undef S8_DEVICE_ONLY
-
-#include "episode_audit.h"
-#include "policy_call.h"
+#include "episode_nets.h"   // S8_NRG stays defined behind it: critic_action_grad_slab below is written in the slab height's macros
 
 static_assert(HP_SIGNAL_STATS == EPISODE_COLS, "one summary loop");
 
 struct ActionGradLds {
-    s8ag::PolicyLds P;
-    s8ag::s8_mask_t msk[2][256];                       // ReLU masks of the critic's h1, h2
+    s8en::PolicyLds P;
+    s8en::s8_mask_t msk[2][256];                       // ReLU masks of the critic's h1, h2
     float w1t[4 * 256] __attribute__((aligned(16)));   // the action columns of the critic's first layer, [column][unit]
 };
 
-struct ActionGradArgs {
-    PolicyArgs P;                  // the actor and the rows: obs / g at the first episode (indexed here), rows = n T
+struct ActionGradArgs : EpisodeNetArgs {   // P.net: the online parameter set
+    using Lds = ActionGradLds;
     const double *act;             // [n][T][ad] (at = 1)
     float *pi, *q, *dq_du;         // [n][T][ad] (at = 0), [n][T], [n][T][ad]
-    NetLayout lc;
-    int T, act_off, ca, at;        // the critic's segment starts at ca = la.total
+    int at;
 };
 
 // s8_critic_slab (slab8.h) with the masks kept and the chain's backward steps behind it.  net.wd must exist.  input / emit_q as
@@ -61,7 +43,7 @@ template <class Input, class EmitQ, class EmitG>
 __device__ __forceinline__ void critic_action_grad_slab(const SlabNetPtrs &net, const NetLayout &lc, int ca, int H, int act_off, int ad,
                                                         long long rows, ActionGradLds &L, size_t row0, Input input, EmitQ emit_q,
                                                         EmitG emit_g) {
-    using namespace s8ag;
+    using namespace s8en;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float *wf = net.wf + ca, *wd = net.wd + ca, *canon = net.canon + ca;
     float *xin = L.P.xin, *bufA = L.P.bufA, *bufB = L.P.bufB, *pbuf = L.P.pbuf;
@@ -118,31 +100,26 @@ __device__ __forceinline__ void critic_action_grad_slab(const SlabNetPtrs &net, 
 }
 
 __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_episode_action_grad(const ActionGradArgs A) {
-    __shared__ ActionGradLds L;
+    __shared__ ActionGradArgs::Lds L;
     const long long row0 = (long long)blockIdx.x * 4;
     const PolicyArgs &P = A.P;
     auto net_input = [&](int r, int c) -> float {
-        const long long m = row0 + r, e = m / A.T;
-        const int t = (int)(m - e * A.T);
-        if (c < P.od) return tr_net_input(P.obs[(e * (A.T + 1) + t) * P.od + c], P.clip_obs, P.onz->mean[c], P.onz->std[c], P.clip_o);
-        const int j = c - P.od;
-        return tr_net_input(P.g[m * P.gd + j], P.clip_obs, P.gnz->mean[j], P.gnz->std[j], P.clip_g);
+        const EpisodeRow w = episode_row(row0 + r, A.T);
+        return episode_state_column(P, w.e * (A.T + 1) + w.t, P.g + w.m * P.gd, c);
     };
     if (A.at == 0) {
-        s8ag::s8_policy_slab(P, L.P, (size_t)row0, net_input,
+        s8en::s8_policy_slab(P, L.P, (size_t)row0, net_input,
             [&](int r, int j, float a) {
                 A.pi[(row0 + r) * P.act_dim + j] = a;
                 L.P.xin[r * S8_LDX + A.act_off + j] = a / P.max_action;   // a = max_action * th: the actor-side chain's u
             });
-        s8ag::s8_sync();
+        s8en::s8_sync();
     }
     critic_action_grad_slab(P.net, A.lc, A.ca, P.H, A.act_off, P.act_dim, (long long)P.rows, L, (size_t)row0,
         [&](int r, int c) -> float {
             if (A.at == 0) return L.P.xin[r * S8_LDX + c];               // kept, as in k_episode_policy
             if (c < P.od + P.gd) return net_input(r, c);
-            const int j = c - A.act_off;
-            if (j >= 0 && j < P.act_dim) return (float)A.act[(row0 + r) * P.act_dim + j] / P.max_action;   // s8_gather, k_episode_q
-            return 0.f;
+            return episode_action_column(P, A.act, row0 + r, A.act_off, c);   // k_episode_q's
         },
         [&](int r, float q) { A.q[row0 + r] = q; },
         [&](int r, int j, float v) { A.dq_du[(row0 + r) * P.act_dim + j] = v; });
@@ -151,35 +128,20 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 // everything behind the entry's own checks (null arguments, contexts, the block's range): the remaining refusals in
 // hp_episode_policy's order -- `at` and what it needs behind `target`, the missing target fragments behind the agent's shape --
 // then the one launch
-static int action_grad_launch(const char *entry, hp_agent *a, hp_norm *on, hp_norm *gn, int32_t target, int32_t at, const double *obs,
-                              const double *g, const double *act, int block_od, int block_gd, int block_ad, int64_t n, int32_t T,
+static int action_grad_launch(const char *entry, hp_agent *a, hp_norm *on, hp_norm *gn, int32_t target, int32_t at, const EpisodeRows &R,
                               double clip_obs, float *pi, float *q, float *dq_du) {
     HP_REQUIRE(target == 0 || target == 1, HP_ERR_INVALID, "%s: target %d is neither 0 (online) nor 1 (target networks)", entry, (int)target);
     HP_REQUIRE(at == 0 || at == 1, HP_ERR_INVALID, "%s: at %d is neither 0 (the policy's action) nor 1 (the recorded action)", entry, (int)at);
-    HP_REQUIRE(at == 0 || act, HP_ERR_INVALID, "%s: at 1 (the recorded action) needs actions_dev", entry);
+    HP_REQUIRE(at == 0 || R.act, HP_ERR_INVALID, "%s: at 1 (the recorded action) needs actions_dev", entry);
     HP_REQUIRE(at == 1 || pi, HP_ERR_INVALID, "%s: at 0 (the policy's action) needs pi_dev", entry);
     HP_TRY(require_slab_shaped(entry, a, HP_ERR_STATE));
     const SlabNetPtrs net = slab_net(a, target != 0);
     HP_REQUIRE(net.wd, HP_ERR_STATE, "%s: the target networks keep no dX-order fragments (no update differentiates through them): target 1 is not available",
                entry);
-    HP_REQUIRE(on->size + gn->size == a->xdim, HP_ERR_INVALID, "%s: normalizer sizes %d+%d do not match the network input %d", entry,
-               (int)on->size, (int)gn->size, a->xdim);
-    HP_REQUIRE(block_od < 0 || (block_od == on->size && block_gd == gn->size && block_ad == a->cfg.act_dim), HP_ERR_INVALID,
-               "%s: the block has dimensions %d / %d / %d, normalizers and agent have %d / %d / %d", entry, block_od, block_gd, block_ad,
-               (int)on->size, (int)gn->size, a->cfg.act_dim);
-    HP_TRY(episode_check_shape(entry, n, T));
-    const long long rows = (long long)n * T;
-    HP_REQUIRE(rows < (1LL << 31), HP_ERR_INVALID, "%s: %lld steps are more than one launch holds (2^31)", entry, rows);
-    static_assert(sizeof(ActionGradLds) <= 160 * 1024, "the policy slab's LDS, two mask planes and the action columns fit a CU");
-    ActionGradArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = policy_args(a, net, norm_view(on), norm_view(gn), clip_or_inf(clip_obs), rows);
-    A.P.obs = obs; A.P.g = g;
-    A.act = act; A.pi = pi; A.q = q; A.dq_du = dq_du;
-    A.lc = a->lc; A.T = T; A.act_off = a->act_off; A.ca = a->la.total; A.at = at;
-    hipLaunchKernelGGL(k_episode_action_grad, dim3((unsigned)((rows + 3) / 4)), dim3(S8_THREADS), 0, a->ctx->stream, A);
-    HP_CHECK_HIP(hipGetLastError());
-    return HP_OK;
+    ActionGradArgs A = {};
+    HP_TRY(episode_net_rows(entry, a, on, gn, "network", net, R, 1, clip_obs, A));
+    A.act = R.act; A.pi = pi; A.q = q; A.dq_du = dq_du; A.at = at;
+    return episode_net_launch(k_episode_action_grad, a, A);
 }
 
 // ---- the columns (HP_SIGNAL_STATS) --------------------------------------------------------------------------------------------------
@@ -191,62 +153,47 @@ struct SignalStatsArgs {
     int T, ad;
 };
 
-// k_episode_signal_stats.  One wave per episode, T walked in chunks of 64 steps from the first chunk up, as k_episode_policy_stats
-// walks it: the lanes form their steps' terms side by side (inner sums over j ascending), then the sums over t run wave-uniformly
-// in ascending t, step base + i taking its terms out of lane i (v_readlane).  The twin (synthetic.episode_signal_stats) is the same
-// loop.  Per step, with M = max_action, lambda = action_l2: g_j = dq_du_j, v_j = pi_j / M, d_j = (act_j - pi_j) / M.
+// k_episode_signal_stats: episode_column_walk (episode_audit.h) over four sums and two counts; a step's inner sums over j ascending.
+// Per step, with M = max_action, lambda = action_l2: g_j = dq_du_j, v_j = pi_j / M, d_j = (act_j - pi_j) / M.
 __global__ __launch_bounds__(64) void k_episode_signal_stats(const SignalStatsArgs A) {
-    const int lane = threadIdx.x, T = A.T, ad = A.ad;
+    const int T = A.T, ad = A.ad;
     const long long e = blockIdx.x;
     const float *pi = A.pi + e * (long long)T * ad, *dq = A.dq_du + e * (long long)T * ad;
     const double *act = A.act + e * (long long)T * ad;
     const double dad = (double)ad, lam2 = __dmul_rn(A.action_l2, 2.0), reg_scale = __dmul_rn(A.action_l2, __ddiv_rn(2.0, dad));
-    double sum_gn = 0.0, sum_cos = 0.0, sum_dot = 0.0, sum_trunk = 0.0;
-    long long n_flat = 0, n_reg = 0;
-    for (int base = 0; base < T; base += 64) {
-        const int cnt = T - base < 64 ? T - base : 64;
-        const int t = base + lane;
-        double gn = 0.0, cs = 0.0, dot = 0.0, trunk = 0.0;
-        int is_flat = 0, is_reg = 0;
-        if (lane < cnt) {
-            double gg = 0.0, vv = 0.0, dd = 0.0, ss = 0.0;
-            for (int j = 0; j < ad; ++j) {
-                const double p = (double)pi[(long long)t * ad + j];
-                const double gj = (double)dq[(long long)t * ad + j];
-                const double v = __ddiv_rn(p, A.max_action);
-                const double d = __ddiv_rn(__dsub_rn(act[(long long)t * ad + j], p), A.max_action);
-                gg = __dadd_rn(gg, __dmul_rn(gj, gj));
-                vv = __dadd_rn(vv, __dmul_rn(v, v));
-                dd = __dadd_rn(dd, __dmul_rn(d, d));
-                dot = __dadd_rn(dot, __dmul_rn(gj, d));
-                const double s = __dmul_rn(__dsub_rn(gj, __ddiv_rn(__dmul_rn(lam2, v), dad)), __dsub_rn(1.0, __dmul_rn(v, v)));
-                ss = __dadd_rn(ss, __dmul_rn(s, s));
-            }
-            gn = __dsqrt_rn(gg);
-            const double vn = __dsqrt_rn(vv), den = __dmul_rn(gn, __dsqrt_rn(dd));
-            is_flat = gn < A.flat ? 1 : 0;
-            is_reg = __dmul_rn(reg_scale, vn) > gn ? 1 : 0;
-            cs = den > 0.0 ? __ddiv_rn(dot, den) : 0.0;       // a step counts 0 when either norm is 0
-            trunk = __dsqrt_rn(ss);
+    double sum[4];                 // |g|, the cosine, g . d, the trunk's signal
+    long long count[2];            // flat, regulariser above the gradient
+    episode_column_walk(T, sum, count, [&](int t, double (&s)[4], int (&c)[2]) {
+        double gg = 0.0, vv = 0.0, dd = 0.0, ss = 0.0, dot = 0.0;
+        for (int j = 0; j < ad; ++j) {
+            const double p = (double)pi[(long long)t * ad + j];
+            const double gj = (double)dq[(long long)t * ad + j];
+            const double v = __ddiv_rn(p, A.max_action);
+            const double d = __ddiv_rn(__dsub_rn(act[(long long)t * ad + j], p), A.max_action);
+            gg = __dadd_rn(gg, __dmul_rn(gj, gj));
+            vv = __dadd_rn(vv, __dmul_rn(v, v));
+            dd = __dadd_rn(dd, __dmul_rn(d, d));
+            dot = __dadd_rn(dot, __dmul_rn(gj, d));
+            const double sj = __dmul_rn(__dsub_rn(gj, __ddiv_rn(__dmul_rn(lam2, v), dad)), __dsub_rn(1.0, __dmul_rn(v, v)));
+            ss = __dadd_rn(ss, __dmul_rn(sj, sj));
         }
-        for (int i = 0; i < cnt; ++i) {
-            sum_gn = __dadd_rn(sum_gn, lane_read_d(gn, i));
-            sum_cos = __dadd_rn(sum_cos, lane_read_d(cs, i));
-            sum_dot = __dadd_rn(sum_dot, lane_read_d(dot, i));
-            sum_trunk = __dadd_rn(sum_trunk, lane_read_d(trunk, i));
-            n_flat += __builtin_amdgcn_readlane(is_flat, i);
-            n_reg += __builtin_amdgcn_readlane(is_reg, i);
-        }
-    }
-    if (lane == 0) {
+        const double gn = __dsqrt_rn(gg), vn = __dsqrt_rn(vv), den = __dmul_rn(gn, __dsqrt_rn(dd));
+        c[0] = gn < A.flat ? 1 : 0;
+        c[1] = __dmul_rn(reg_scale, vn) > gn ? 1 : 0;
+        s[0] = gn;
+        s[1] = den > 0.0 ? __ddiv_rn(dot, den) : 0.0;       // a step counts 0 when either norm is 0
+        s[2] = dot;
+        s[3] = __dsqrt_rn(ss);
+    });
+    if (threadIdx.x == 0) {
         double *out = A.stats + e * HP_SIGNAL_STATS;
         const double dT = (double)T;
-        out[0] = __ddiv_rn(sum_gn, dT);
-        out[1] = __ddiv_rn((double)n_flat, dT);
-        out[2] = __ddiv_rn((double)n_reg, dT);
-        out[3] = __ddiv_rn(sum_cos, dT);
-        out[4] = __ddiv_rn(sum_dot, dT);
-        out[5] = __ddiv_rn(sum_trunk, dT);
+        out[0] = __ddiv_rn(sum[0], dT);
+        out[1] = __ddiv_rn((double)count[0], dT);
+        out[2] = __ddiv_rn((double)count[1], dT);
+        out[3] = __ddiv_rn(sum[1], dT);
+        out[4] = __ddiv_rn(sum[2], dT);
+        out[5] = __ddiv_rn(sum[3], dT);
     }
 }
 
@@ -275,21 +222,18 @@ int hp_episode_action_grad(hp_agent *a, hp_norm *on, hp_norm *gn, int32_t target
                            float *dq_du_dev) {
     HP_REQUIRE(a && on && gn && obs_dev && g_dev && q_dev && dq_du_dev, HP_ERR_INVALID, "hp_episode_action_grad: null argument");
     HP_SERIALISE(a);
-    HP_REQUIRE(on->ctx == a->ctx && gn->ctx == a->ctx, HP_ERR_INVALID, "hp_episode_action_grad: handles belong to different contexts");
-    return action_grad_launch("hp_episode_action_grad", a, on, gn, target, at, obs_dev, g_dev, actions_dev, -1, -1, -1, n_episodes, T,
-                              clip_obs, pi_dev, q_dev, dq_du_dev);
+    HP_TRY(episode_one_context("hp_episode_action_grad", a, on, gn));
+    return action_grad_launch("hp_episode_action_grad", a, on, gn, target, at,
+                              EpisodeRows{obs_dev, nullptr, g_dev, actions_dev, -1, -1, -1, n_episodes, T}, clip_obs, pi_dev, q_dev, dq_du_dev);
 }
 
 int hp_episode_action_grad_block(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, int32_t target, int32_t at, int64_t first_episode,
                                  int64_t n_episodes, double clip_obs, float *pi_dev, float *q_dev, float *dq_du_dev) {
     HP_REQUIRE(ro && a && on && gn && q_dev && dq_du_dev, HP_ERR_INVALID, "hp_episode_action_grad_block: null argument");
     HP_SERIALISE(ro);
-    HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx, HP_ERR_INVALID,
-               "hp_episode_action_grad_block: handles belong to different contexts");
-    RolloutArrays arr;
-    HP_TRY(episode_block_range("hp_episode_action_grad_block", ro, first_episode, n_episodes, arr));
-    return action_grad_launch("hp_episode_action_grad_block", a, on, gn, target, at, arr.b_obs, arr.b_g, arr.b_act, ro->od, ro->gd, ro->ad,
-                              n_episodes, ro->T, clip_obs, pi_dev, q_dev, dq_du_dev);
+    EpisodeRows rows;
+    HP_TRY(episode_block_rows("hp_episode_action_grad_block", ro, a, on, gn, first_episode, n_episodes, rows));
+    return action_grad_launch("hp_episode_action_grad_block", a, on, gn, target, at, rows, clip_obs, pi_dev, q_dev, dq_du_dev);
 }
 
 int hp_episode_signal_stats(hp_ctx *ctx, const float *pi_dev, const float *dq_du_dev, const double *actions_dev, int64_t n_episodes,

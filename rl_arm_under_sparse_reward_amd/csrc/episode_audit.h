@@ -1,7 +1,8 @@
-// episode_audit.h -- the frame the six units of the episode audit share (episode_stats.hip, episode_returns.hip, episode_q.hip,
-// episode_policy.hip, episode_action_grad.hip, episode_bellman.hip): the bound on episodes and steps, the refusals every entry makes of a block's shape, the range check of the
-// *_block entries with the block's four arrays behind it, and the summary of a per-episode table.  The arithmetic of a step:
-// transition_device.h.
+// episode_audit.h -- the frame the six units of the episode audit share (episode_stats.hip and episode_returns.hip directly; episode_q.hip,
+// episode_policy.hip, episode_action_grad.hip and episode_bellman.hip through episode_nets.h, which adds what running a network over a
+// block takes): the bound on episodes and steps, the refusals every entry makes of a block's shape, the range check of the
+// *_block entries with the block's four arrays behind it, the walk that turns an episode's steps into its columns, and the summary
+// of a per-episode table.  No slab here.  The arithmetic of a step: transition_device.h.
 #pragma once
 #include "transition_device.h"
 
@@ -28,6 +29,38 @@ static inline int episode_block_range(const char *entry, const hp_rollout *ro, i
                entry, (long long)first, (long long)(first + n), (long long)ro->n);
     rollout_arrays_at(ro, first, at);
     return HP_OK;
+}
+
+// The columns of one episode out of its per-step arrays (k_episode_policy_stats, k_episode_signal_stats, k_episode_bellman_stats):
+// one wave per episode, T a run-time value walked in chunks of 64 steps as k_episode_returns walks it, here from the first chunk
+// up.  The lanes form their steps' terms side by side -- terms(t, s, c): step t's NS float64 terms and NC integer ones, preset to
+// 0 -- then the sums over t run wave-uniformly over the chunk in ascending t, step base + i taking its terms out of lane i
+// (v_readlane: no LDS, no barrier), one __dadd_rn per column per step.  Float64 sums of values that are not small integers depend
+// on that order; the twins (synthetic.episode_policy_stats, episode_signal_stats, episode_bellman_stats) are the same loop.  The
+// counts are exact whatever the order.  Every lane returns with the same sums.
+template <int NS, int NC, class Terms>
+__device__ __forceinline__ void episode_column_walk(int T, double (&sum)[NS], long long (&count)[NC], Terms terms) {
+    const int lane = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) sum[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) count[k] = 0;
+    for (int base = 0; base < T; base += 64) {
+        const int cnt = T - base < 64 ? T - base : 64;
+        double s[NS];
+        int c[NC];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) c[k] = 0;
+        if (lane < cnt) terms(base + lane, s, c);
+        for (int i = 0; i < cnt; ++i) {
+#pragma unroll
+            for (int k = 0; k < NS; ++k) sum[k] = __dadd_rn(sum[k], lane_read_d(s[k], i));
+#pragma unroll
+            for (int k = 0; k < NC; ++k) count[k] += __builtin_amdgcn_readlane(c[k], i);
+        }
+    }
 }
 
 // Summary of a table [n][EPISODE_COLS] into out[EPISODE_COLS]: one wave, and lane 0 walks the rows -- every mean is the left-to-right float64 sum in

@@ -23,113 +23,72 @@
 //
 // Rows past n T in the last slab take part in every barrier, read nothing (the slabs call the input functions for rows that exist)
 // and store nothing.  Which weights: the four buffers episode_q.hip's header names, on the context's stream behind whatever wrote them.
-#include <cmath>
+#include "episode_nets.h"
 
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wundefined-inline"   // agent_device.h declares the 32-row engine's fragment map, which no code here calls
-#include "agent_device.h"
-#pragma clang diagnostic pop
-
-// the 4-row slab's device functions (no kernel of slab8.h is compiled here)
-#define S8_DEVICE_ONLY
-#define S8_NRG 1
-#define S8_NS s8eb
-#include "slab8.h"
-#undef S8_NRG
-#undef S8_NS
-#undef S8_DEVICE_ONLY
-
-#include "episode_audit.h"
-#include "policy_call.h"
-
-struct EpisodeBellmanArgs {
-    PolicyArgs P;                  // the target actor: obs / g at the first episode (indexed here, not by s8_policy_slab), rows = n T
-    SlabNetPtrs online;            // the online parameter set (P.net: the target one)
+struct EpisodeBellmanArgs : EpisodeNetArgs {   // P.net: the target parameter set
+    using Lds = s8en::PolicyLds;
+    SlabNetPtrs online;            // the online parameter set
     const double *ag, *act;        // [n][T + 1][gd], [n][T][ad], already offset to the first episode
     float *q, *q_next, *r, *y;     // [n][T] each
-    NetLayout lc;
     double sq_threshold;           // sparse: squared_bound(thr, true); dense: < 0 (hp_reward's rule)
     float gamma, clip_ret;         // what the agent hands its update kernels
-    int T, act_off, ca, goal_mode; // the critic's segment starts at ca = la.total
+    int goal_mode;
 };
 
 __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_episode_bellman(const EpisodeBellmanArgs A) {
-    __shared__ s8eb::PolicyLds L;
+    __shared__ EpisodeBellmanArgs::Lds L;
     const long long row0 = (long long)blockIdx.x * 4;
     const PolicyArgs &P = A.P;
     const int T = A.T, gd = P.gd;
-    // the goal of row m = e T + t: the block's own at t, or the episode's last achieved one
-    auto goal_of = [&](long long m, long long e) -> const double * {
-        return A.goal_mode == HP_GOAL_FINAL ? A.ag + (e * (T + 1) + T) * gd : P.g + m * gd;
+    // the goal of a row: the block's own at t, or the episode's last achieved one
+    auto goal_of = [&](const EpisodeRow &w) -> const double * {
+        return A.goal_mode == HP_GOAL_FINAL ? A.ag + (w.e * (T + 1) + T) * gd : P.g + w.m * gd;
     };
-    s8eb::s8_policy_slab(P, L, (size_t)row0,
+    s8en::s8_policy_slab(P, L, (size_t)row0,
         [&](int r, int c) -> float {
-            const long long m = row0 + r, e = m / T;
-            const int t = (int)(m - e * T);
-            if (c < P.od) return tr_net_input(P.obs[(e * (T + 1) + t + 1) * P.od + c], P.clip_obs, P.onz->mean[c], P.onz->std[c], P.clip_o);
-            const int j = c - P.od;
-            return tr_net_input(goal_of(m, e)[j], P.clip_obs, P.gnz->mean[j], P.gnz->std[j], P.clip_g);
+            const EpisodeRow w = episode_row(row0 + r, T);
+            return episode_state_column(P, w.e * (T + 1) + w.t + 1, goal_of(w), c);
         },
         [&](int r, int j, float a) { L.xin[r * S8_LDX + A.act_off + j] = a / P.max_action; });   // a = max_action * th: the actor-side chain's u
-    s8eb::s8_sync();
-    s8eb::s8_critic_slab(P.net, A.lc, A.ca, P.H, (long long)P.rows, L, (size_t)row0,
+    s8en::s8_sync();
+    s8en::s8_critic_slab(P.net, A.lc, A.ca, P.H, (long long)P.rows, L, (size_t)row0,
         [&](int r, int c) -> float { return L.xin[r * S8_LDX + c]; },
         [&](int r, float qn) {
-            const long long m = row0 + r, e = m / T;
-            const int t = (int)(m - e * T);
-            const float rw = hp_reward(tr_sq_distance(A.ag + (e * (T + 1) + t + 1) * gd, goal_of(m, e), gd), A.sq_threshold);
+            const EpisodeRow w = episode_row(row0 + r, T);
+            const float rw = hp_reward(tr_sq_distance(A.ag + (w.e * (T + 1) + w.t + 1) * gd, goal_of(w), gd), A.sq_threshold);
             float y = rw + A.gamma * qn;
             y = fminf(fmaxf(y, -A.clip_ret), 0.f);
-            A.q_next[m] = qn; A.r[m] = rw; A.y[m] = y;
+            A.q_next[w.m] = qn; A.r[w.m] = rw; A.y[w.m] = y;
         });
-    s8eb::s8_sync();
-    s8eb::s8_critic_slab(A.online, A.lc, A.ca, P.H, (long long)P.rows, L, (size_t)row0,
+    s8en::s8_sync();
+    s8en::s8_critic_slab(A.online, A.lc, A.ca, P.H, (long long)P.rows, L, (size_t)row0,
         [&](int r, int c) -> float {
-            const long long m = row0 + r, e = m / T;
-            const int t = (int)(m - e * T);
-            if (c < P.od) return tr_net_input(P.obs[(e * (T + 1) + t) * P.od + c], P.clip_obs, P.onz->mean[c], P.onz->std[c], P.clip_o);
+            const EpisodeRow w = episode_row(row0 + r, T);
+            if (c < P.od) return episode_state_column(P, w.e * (T + 1) + w.t, nullptr, c);
             if (c < P.od + gd) return L.xin[r * S8_LDX + c];      // kept: this thread is about to store the word it reads
-            const int j = c - A.act_off;
-            if (j >= 0 && j < P.act_dim) return (float)A.act[m * P.act_dim + j] / P.max_action;   // s8_gather, k_episode_q
-            return 0.f;
+            return episode_action_column(P, A.act, w.m, A.act_off, c);   // k_episode_q's
         },
         [&](int r, float q) { A.q[row0 + r] = q; });
 }
 
 // everything behind the entry's own checks (null arguments, contexts, the block's range): the remaining refusals in
 // hp_episode_policy's order -- the goal mode and the reward kind behind the row count -- then the one launch
-static int episode_bellman_launch(const char *entry, hp_agent *a, hp_norm *on, hp_norm *gn, int32_t goal_mode, const double *obs,
-                                  const double *ag, const double *g, const double *act, int block_od, int block_gd, int block_ad,
-                                  int64_t n, int32_t T, double thr, int32_t reward_type, double clip_obs, float *q, float *q_next,
-                                  float *r, float *y) {
-    HP_TRY(require_slab_shaped(entry, a, HP_ERR_STATE));
-    HP_REQUIRE(on->size + gn->size == a->xdim, HP_ERR_INVALID, "%s: normalizer sizes %d+%d do not match the network input %d", entry,
-               (int)on->size, (int)gn->size, a->xdim);
-    HP_REQUIRE(block_od < 0 || (block_od == on->size && block_gd == gn->size && block_ad == a->cfg.act_dim), HP_ERR_INVALID,
-               "%s: the block has dimensions %d / %d / %d, normalizers and agent have %d / %d / %d", entry, block_od, block_gd, block_ad,
-               (int)on->size, (int)gn->size, a->cfg.act_dim);
-    HP_TRY(episode_check_shape(entry, n, T, (int32_t)gn->size));
-    const long long rows = (long long)n * T;
-    HP_REQUIRE(rows < (1LL << 31), HP_ERR_INVALID, "%s: %lld steps are more than one launch holds (2^31)", entry, rows);
+static int episode_bellman_launch(const char *entry, hp_agent *a, hp_norm *on, hp_norm *gn, int32_t goal_mode, const EpisodeRows &R,
+                                  double thr, int32_t reward_type, double clip_obs, float *q, float *q_next, float *r, float *y) {
+    EpisodeBellmanArgs A = {};
+    HP_TRY(episode_net_args(entry, a, on, gn, "network", slab_net(a, true), R, (int32_t)gn->size, clip_obs, A));
     HP_REQUIRE(goal_mode == HP_GOAL_DESIRED || goal_mode == HP_GOAL_FINAL, HP_ERR_INVALID,
                "%s: goal_mode %d is neither 0 (the desired goal) nor 1 (the episode's final achieved goal)", entry, (int)goal_mode);
     HP_REQUIRE(reward_type == 0 || reward_type == 1, HP_ERR_INVALID, "%s: reward_type %d is neither 0 (sparse) nor 1 (dense)", entry,
                (int)reward_type);
-    static_assert(sizeof(s8eb::PolicyLds) <= 160 * 1024, "the policy slab's LDS fits a CU");
-    EpisodeBellmanArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = policy_args(a, slab_net(a, true), norm_view(on), norm_view(gn), clip_or_inf(clip_obs), rows);
-    A.P.obs = obs; A.P.g = g;
     A.online = slab_net(a, false);
-    A.ag = ag; A.act = act;
+    A.ag = R.ag; A.act = R.act;
     A.q = q; A.q_next = q_next; A.r = r; A.y = y;
-    A.lc = a->lc; A.T = T; A.act_off = a->act_off; A.ca = a->la.total; A.goal_mode = goal_mode;
+    A.goal_mode = goal_mode;
     A.sq_threshold = reward_type == 0 ? squared_bound(thr, true) : -1.0;
     A.gamma = (float)a->cfg.gamma;                                   // agent_engines.hip, agent_layers.hip: the update kernels' two
     A.clip_ret = (float)(1.0 / (1.0 - a->cfg.gamma));
-    hipLaunchKernelGGL(k_episode_bellman, dim3((unsigned)((rows + 3) / 4)), dim3(S8_THREADS), 0, a->ctx->stream, A);
-    HP_CHECK_HIP(hipGetLastError());
-    return HP_OK;
+    return episode_net_launch(k_episode_bellman, a, A);
 }
 
 // ---- the columns (HP_BELLMAN_STATS) -------------------------------------------------------------------------------------------------
@@ -140,49 +99,34 @@ struct BellmanStatsArgs {
     int T;
 };
 
-// k_episode_bellman_stats.  One wave per episode, T walked in chunks of 64 steps from the first chunk up, as k_episode_policy_stats
-// walks it: the lanes form their steps' terms side by side, then the sums over t run wave-uniformly in ascending t, step base + i
-// taking its terms out of lane i (v_readlane).  The twin (synthetic.episode_bellman_stats) is the same loop.  Per step
+// k_episode_bellman_stats: episode_column_walk (episode_audit.h) over five sums and one count.  Per step
 // d = (double)y - (double)q; a step counts as clipped when r + gamma * q_next, the float32 expression of the target, is not y.
 __global__ __launch_bounds__(64) void k_episode_bellman_stats(const BellmanStatsArgs A) {
-    const int lane = threadIdx.x, T = A.T;
+    const int T = A.T;
     const long long e = blockIdx.x;
     const float *q = A.q + e * (long long)T, *q_next = A.q_next + e * (long long)T, *r = A.r + e * (long long)T, *y = A.y + e * (long long)T;
-    double sum_d = 0.0, sum_abs = 0.0, sum_sq = 0.0, sum_y = 0.0, sum_r = 0.0;
-    long long clipped = 0;
-    for (int base = 0; base < T; base += 64) {
-        const int cnt = T - base < 64 ? T - base : 64;
-        const int t = base + lane;
-        double d = 0.0, ab = 0.0, sq = 0.0, yd = 0.0, rd = 0.0;
-        int clip = 0;
-        if (lane < cnt) {
-            const float yv = y[t], rv = r[t];
-            yd = (double)yv;
-            rd = (double)rv;
-            d = __dsub_rn(yd, (double)q[t]);
-            ab = fabs(d);
-            sq = __dmul_rn(d, d);
-            const float raw = rv + A.gamma * q_next[t];
-            clip = raw != yv ? 1 : 0;
-        }
-        for (int i = 0; i < cnt; ++i) {
-            sum_d = __dadd_rn(sum_d, lane_read_d(d, i));
-            sum_abs = __dadd_rn(sum_abs, lane_read_d(ab, i));
-            sum_sq = __dadd_rn(sum_sq, lane_read_d(sq, i));
-            sum_y = __dadd_rn(sum_y, lane_read_d(yd, i));
-            sum_r = __dadd_rn(sum_r, lane_read_d(rd, i));
-            clipped += __builtin_amdgcn_readlane(clip, i);
-        }
-    }
-    if (lane == 0) {
+    double sum[5];                 // d, |d|, d^2, y, r
+    long long count[1];            // clipped
+    episode_column_walk(T, sum, count, [&](int t, double (&s)[5], int (&c)[1]) {
+        const float yv = y[t], rv = r[t];
+        const double d = __dsub_rn((double)yv, (double)q[t]);
+        s[0] = d;
+        s[1] = fabs(d);
+        s[2] = __dmul_rn(d, d);
+        s[3] = (double)yv;
+        s[4] = (double)rv;
+        const float raw = rv + A.gamma * q_next[t];
+        c[0] = raw != yv ? 1 : 0;
+    });
+    if (threadIdx.x == 0) {
         double *out = A.stats + e * HP_BELLMAN_STATS;
         const double dT = (double)T;
-        out[0] = __ddiv_rn(sum_d, dT);
-        out[1] = __ddiv_rn(sum_abs, dT);
-        out[2] = __ddiv_rn(sum_sq, dT);
-        out[3] = __ddiv_rn(sum_y, dT);
-        out[4] = __ddiv_rn((double)clipped, dT);
-        out[5] = __ddiv_rn(sum_r, dT);
+        out[0] = __ddiv_rn(sum[0], dT);
+        out[1] = __ddiv_rn(sum[1], dT);
+        out[2] = __ddiv_rn(sum[2], dT);
+        out[3] = __ddiv_rn(sum[3], dT);
+        out[4] = __ddiv_rn((double)count[0], dT);
+        out[5] = __ddiv_rn(sum[4], dT);
     }
 }
 
@@ -194,9 +138,10 @@ int hp_episode_bellman(hp_agent *a, hp_norm *on, hp_norm *gn, int32_t goal_mode,
     HP_REQUIRE(a && on && gn && obs_dev && ag_dev && g_dev && actions_dev && q_dev && q_next_dev && r_dev && y_dev, HP_ERR_INVALID,
                "hp_episode_bellman: null argument");
     HP_SERIALISE(a);
-    HP_REQUIRE(on->ctx == a->ctx && gn->ctx == a->ctx, HP_ERR_INVALID, "hp_episode_bellman: handles belong to different contexts");
-    return episode_bellman_launch("hp_episode_bellman", a, on, gn, goal_mode, obs_dev, ag_dev, g_dev, actions_dev, -1, -1, -1, n_episodes, T,
-                                  distance_threshold, reward_type, clip_obs, q_dev, q_next_dev, r_dev, y_dev);
+    HP_TRY(episode_one_context("hp_episode_bellman", a, on, gn));
+    return episode_bellman_launch("hp_episode_bellman", a, on, gn, goal_mode,
+                                  EpisodeRows{obs_dev, ag_dev, g_dev, actions_dev, -1, -1, -1, n_episodes, T}, distance_threshold, reward_type,
+                                  clip_obs, q_dev, q_next_dev, r_dev, y_dev);
 }
 
 int hp_episode_bellman_block(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, int32_t goal_mode, int64_t first_episode,
@@ -204,12 +149,10 @@ int hp_episode_bellman_block(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *
                              float *q_next_dev, float *r_dev, float *y_dev) {
     HP_REQUIRE(ro && a && on && gn && q_dev && q_next_dev && r_dev && y_dev, HP_ERR_INVALID, "hp_episode_bellman_block: null argument");
     HP_SERIALISE(ro);
-    HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx, HP_ERR_INVALID,
-               "hp_episode_bellman_block: handles belong to different contexts");
-    RolloutArrays at;
-    HP_TRY(episode_block_range("hp_episode_bellman_block", ro, first_episode, n_episodes, at));
-    return episode_bellman_launch("hp_episode_bellman_block", a, on, gn, goal_mode, at.b_obs, at.b_ag, at.b_g, at.b_act, ro->od, ro->gd,
-                                  ro->ad, n_episodes, ro->T, distance_threshold, reward_type, clip_obs, q_dev, q_next_dev, r_dev, y_dev);
+    EpisodeRows rows;
+    HP_TRY(episode_block_rows("hp_episode_bellman_block", ro, a, on, gn, first_episode, n_episodes, rows));
+    return episode_bellman_launch("hp_episode_bellman_block", a, on, gn, goal_mode, rows, distance_threshold, reward_type, clip_obs, q_dev,
+                                  q_next_dev, r_dev, y_dev);
 }
 
 int hp_episode_bellman_stats(hp_ctx *ctx, const float *q_dev, const float *q_next_dev, const float *r_dev, const float *y_dev,

@@ -20,79 +20,41 @@
 //
 // Which weights: the four buffers episode_q.hip's header names (a->fragF / a->params, a->fragFT / a->targets), the actor's segment at
 // 0 and the critic's at la.total, on the context's stream behind whatever wrote them.  target: both target networks together.
-#include <cmath>
+#include "episode_nets.h"
 
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wundefined-inline"   // agent_device.h declares the 32-row engine's fragment map, which no code here calls
-#include "agent_device.h"
-#pragma clang diagnostic pop
-
-// the 4-row slab's device functions (no kernel of slab8.h is compiled here)
-#define S8_DEVICE_ONLY
-#define S8_NRG 1
-#define S8_NS s8ep
-#include "slab8.h"
-#undef S8_NRG
-#undef S8_NS
-#undef S8_DEVICE_ONLY
-
-#include "episode_audit.h"
-#include "policy_call.h"
-
-struct EpisodePolicyArgs {
-    PolicyArgs P;                  // the actor: obs / g at the first episode (indexed here, not by s8_policy_slab), rows = n T
+struct EpisodePolicyArgs : EpisodeNetArgs {   // P.net: the actor's and the critic's parameter set
+    using Lds = s8en::PolicyLds;
     float *pi, *q_pi;              // [n][T][ad], [n][T]
-    NetLayout lc;
-    int T, act_off, ca;            // the critic's segment starts at ca = la.total
 };
 
 __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_episode_policy(const EpisodePolicyArgs A) {
-    __shared__ s8ep::PolicyLds L;
+    __shared__ EpisodePolicyArgs::Lds L;
     const long long row0 = (long long)blockIdx.x * 4;
     const PolicyArgs &P = A.P;
-    s8ep::s8_policy_slab(P, L, (size_t)row0,
+    s8en::s8_policy_slab(P, L, (size_t)row0,
         [&](int r, int c) -> float {
-            const long long m = row0 + r, e = m / A.T;
-            const int t = (int)(m - e * A.T);
-            if (c < P.od) return tr_net_input(P.obs[(e * (A.T + 1) + t) * P.od + c], P.clip_obs, P.onz->mean[c], P.onz->std[c], P.clip_o);
-            const int j = c - P.od;
-            return tr_net_input(P.g[m * P.gd + j], P.clip_obs, P.gnz->mean[j], P.gnz->std[j], P.clip_g);
+            const EpisodeRow w = episode_row(row0 + r, A.T);
+            return episode_state_column(P, w.e * (A.T + 1) + w.t, P.g + w.m * P.gd, c);
         },
         [&](int r, int j, float a) {
             A.pi[(row0 + r) * P.act_dim + j] = a;
             L.xin[r * S8_LDX + A.act_off + j] = a / P.max_action;   // a = max_action * th: the actor-side chain's u
         });
-    s8ep::s8_sync();
-    s8ep::s8_critic_slab(P.net, A.lc, A.ca, P.H, (long long)P.rows, L, (size_t)row0,
+    s8en::s8_sync();
+    s8en::s8_critic_slab(P.net, A.lc, A.ca, P.H, (long long)P.rows, L, (size_t)row0,
         [&](int r, int c) -> float { return L.xin[r * S8_LDX + c]; },
         [&](int r, float q) { A.q_pi[row0 + r] = q; });
 }
 
 // everything behind the entry's own checks (null arguments, contexts, the block's range): the remaining refusals in hp_episode_q's
 // order, then the one launch
-static int episode_policy_launch(const char *entry, hp_agent *a, hp_norm *on, hp_norm *gn, int32_t target, const double *obs,
-                                 const double *g, int block_od, int block_gd, int block_ad, int64_t n, int32_t T, double clip_obs,
-                                 float *pi, float *q_pi) {
+static int episode_policy_launch(const char *entry, hp_agent *a, hp_norm *on, hp_norm *gn, int32_t target, const EpisodeRows &R,
+                                 double clip_obs, float *pi, float *q_pi) {
     HP_REQUIRE(target == 0 || target == 1, HP_ERR_INVALID, "%s: target %d is neither 0 (online) nor 1 (target networks)", entry, (int)target);
-    HP_TRY(require_slab_shaped(entry, a, HP_ERR_STATE));
-    HP_REQUIRE(on->size + gn->size == a->xdim, HP_ERR_INVALID, "%s: normalizer sizes %d+%d do not match the network input %d", entry,
-               (int)on->size, (int)gn->size, a->xdim);
-    HP_REQUIRE(block_od < 0 || (block_od == on->size && block_gd == gn->size && block_ad == a->cfg.act_dim), HP_ERR_INVALID,
-               "%s: the block has dimensions %d / %d / %d, normalizers and agent have %d / %d / %d", entry, block_od, block_gd, block_ad,
-               (int)on->size, (int)gn->size, a->cfg.act_dim);
-    HP_TRY(episode_check_shape(entry, n, T));
-    const long long rows = (long long)n * T;
-    HP_REQUIRE(rows < (1LL << 31), HP_ERR_INVALID, "%s: %lld steps are more than one launch holds (2^31)", entry, rows);
-    static_assert(sizeof(s8ep::PolicyLds) <= 160 * 1024, "the policy slab's LDS fits a CU");
-    EpisodePolicyArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = policy_args(a, slab_net(a, target != 0), norm_view(on), norm_view(gn), clip_or_inf(clip_obs), rows);
-    A.P.obs = obs; A.P.g = g;
+    EpisodePolicyArgs A = {};
+    HP_TRY(episode_net_args(entry, a, on, gn, "network", slab_net(a, target != 0), R, 1, clip_obs, A));
     A.pi = pi; A.q_pi = q_pi;
-    A.lc = a->lc; A.T = T; A.act_off = a->act_off; A.ca = a->la.total;
-    hipLaunchKernelGGL(k_episode_policy, dim3((unsigned)((rows + 3) / 4)), dim3(S8_THREADS), 0, a->ctx->stream, A);
-    HP_CHECK_HIP(hipGetLastError());
-    return HP_OK;
+    return episode_net_launch(k_episode_policy, a, A);
 }
 
 // ---- the columns (HP_POLICY_STATS) --------------------------------------------------------------------------------------------------
@@ -104,62 +66,44 @@ struct PolicyStatsArgs {
     int T, ad;
 };
 
-// k_episode_policy_stats.  One wave per episode, T a run-time value walked in chunks of 64 steps as k_episode_returns walks it, here
-// from the first chunk up.  The lanes form their steps' terms side by side -- lane l: step base + l, its inner sums over j ascending
-// -- then the sums over t run wave-uniformly over the chunk in ascending t, step base + i taking its terms out of lane i
-// (v_readlane: no LDS, no barrier).  Float64 sums of values that are not small integers depend on that order; the twin
-// (synthetic.episode_policy_stats) is the same loop.  The two counts are exact whatever the order.
+// k_episode_policy_stats: episode_column_walk (episode_audit.h) over four sums and two counts; a step's inner sums over j ascending
 __global__ __launch_bounds__(64) void k_episode_policy_stats(const PolicyStatsArgs A) {
-    const int lane = threadIdx.x, T = A.T, ad = A.ad;
+    const int T = A.T, ad = A.ad;
     const long long e = blockIdx.x;
     const float *pi = A.pi + e * (long long)T * ad, *q_pi = A.q_pi + e * (long long)T;
     const float *q = A.q ? A.q + e * (long long)T : nullptr;
     const double *act = A.act + e * (long long)T * ad;
-    double sum_qpi = 0.0, sum_adv = 0.0, sum_gap = 0.0, sum_l2 = 0.0;
-    long long filtered = 0, saturated = 0;
-    for (int base = 0; base < T; base += 64) {
-        const int cnt = T - base < 64 ? T - base : 64;
-        const int t = base + lane;
-        double qpd = 0.0, adv = 0.0, gap = 0.0, l2 = 0.0;
-        int filt = 0, nsat = 0;
-        if (lane < cnt) {
-            const float qp = q_pi[t];
-            qpd = (double)qp;
-            if (q) {
-                const float qv = q[t];
-                adv = __dsub_rn(qpd, (double)qv);
-                filt = qv > qp ? 1 : 0;
-            }
-            double dd = 0.0, vv = 0.0;
-            for (int j = 0; j < ad; ++j) {
-                const double p = (double)pi[(long long)t * ad + j];
-                const double d = __dsub_rn(act[(long long)t * ad + j], p);
-                const double v = __ddiv_rn(p, A.max_action);
-                dd = __dadd_rn(dd, __dmul_rn(d, d));
-                vv = __dadd_rn(vv, __dmul_rn(v, v));
-                nsat += fabs(p) >= A.sat_bound ? 1 : 0;
-            }
-            gap = __dsqrt_rn(dd);
-            l2 = __ddiv_rn(vv, (double)ad);
+    double sum[4];                 // q_pi, q - q_pi, the action gap, the regulariser
+    long long count[2];            // filtered, saturated
+    episode_column_walk(T, sum, count, [&](int t, double (&s)[4], int (&c)[2]) {
+        const float qp = q_pi[t];
+        s[0] = (double)qp;
+        if (q) {
+            const float qv = q[t];
+            s[1] = __dsub_rn(s[0], (double)qv);
+            c[0] = qv > qp ? 1 : 0;
         }
-        for (int i = 0; i < cnt; ++i) {
-            sum_qpi = __dadd_rn(sum_qpi, lane_read_d(qpd, i));
-            sum_adv = __dadd_rn(sum_adv, lane_read_d(adv, i));
-            sum_gap = __dadd_rn(sum_gap, lane_read_d(gap, i));
-            sum_l2 = __dadd_rn(sum_l2, lane_read_d(l2, i));
-            filtered += __builtin_amdgcn_readlane(filt, i);
-            saturated += __builtin_amdgcn_readlane(nsat, i);
+        double dd = 0.0, vv = 0.0;
+        for (int j = 0; j < ad; ++j) {
+            const double p = (double)pi[(long long)t * ad + j];
+            const double d = __dsub_rn(act[(long long)t * ad + j], p);
+            const double v = __ddiv_rn(p, A.max_action);
+            dd = __dadd_rn(dd, __dmul_rn(d, d));
+            vv = __dadd_rn(vv, __dmul_rn(v, v));
+            c[1] += fabs(p) >= A.sat_bound ? 1 : 0;
         }
-    }
-    if (lane == 0) {
+        s[2] = __dsqrt_rn(dd);
+        s[3] = __ddiv_rn(vv, (double)ad);
+    });
+    if (threadIdx.x == 0) {
         double *out = A.stats + e * HP_POLICY_STATS;
         const double dT = (double)T, none = __longlong_as_double(0x7ff8000000000000LL);
-        out[0] = __ddiv_rn(sum_qpi, dT);
-        out[1] = q ? __ddiv_rn(sum_adv, dT) : none;
-        out[2] = q ? __ddiv_rn((double)filtered, dT) : none;
-        out[3] = __ddiv_rn(__ddiv_rn(sum_gap, A.max_action), dT);
-        out[4] = __ddiv_rn((double)saturated, (double)((long long)T * ad));
-        out[5] = __ddiv_rn(sum_l2, dT);
+        out[0] = __ddiv_rn(sum[0], dT);
+        out[1] = q ? __ddiv_rn(sum[1], dT) : none;
+        out[2] = q ? __ddiv_rn((double)count[0], dT) : none;
+        out[3] = __ddiv_rn(__ddiv_rn(sum[2], A.max_action), dT);
+        out[4] = __ddiv_rn((double)count[1], (double)((long long)T * ad));
+        out[5] = __ddiv_rn(sum[3], dT);
     }
 }
 
@@ -186,21 +130,18 @@ int hp_episode_policy(hp_agent *a, hp_norm *on, hp_norm *gn, int32_t target, con
                       int64_t n_episodes, int32_t T, double clip_obs, float *pi_dev, float *q_pi_dev) {
     HP_REQUIRE(a && on && gn && obs_dev && g_dev && pi_dev && q_pi_dev, HP_ERR_INVALID, "hp_episode_policy: null argument");
     HP_SERIALISE(a);
-    HP_REQUIRE(on->ctx == a->ctx && gn->ctx == a->ctx, HP_ERR_INVALID, "hp_episode_policy: handles belong to different contexts");
-    return episode_policy_launch("hp_episode_policy", a, on, gn, target, obs_dev, g_dev, -1, -1, -1, n_episodes, T, clip_obs, pi_dev,
-                                 q_pi_dev);
+    HP_TRY(episode_one_context("hp_episode_policy", a, on, gn));
+    return episode_policy_launch("hp_episode_policy", a, on, gn, target, EpisodeRows{obs_dev, nullptr, g_dev, nullptr, -1, -1, -1, n_episodes, T},
+                                 clip_obs, pi_dev, q_pi_dev);
 }
 
 int hp_episode_policy_block(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, int32_t target, int64_t first_episode,
                             int64_t n_episodes, double clip_obs, float *pi_dev, float *q_pi_dev) {
     HP_REQUIRE(ro && a && on && gn && pi_dev && q_pi_dev, HP_ERR_INVALID, "hp_episode_policy_block: null argument");
     HP_SERIALISE(ro);
-    HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx, HP_ERR_INVALID,
-               "hp_episode_policy_block: handles belong to different contexts");
-    RolloutArrays at;
-    HP_TRY(episode_block_range("hp_episode_policy_block", ro, first_episode, n_episodes, at));
-    return episode_policy_launch("hp_episode_policy_block", a, on, gn, target, at.b_obs, at.b_g, ro->od, ro->gd, ro->ad, n_episodes, ro->T,
-                                 clip_obs, pi_dev, q_pi_dev);
+    EpisodeRows rows;
+    HP_TRY(episode_block_rows("hp_episode_policy_block", ro, a, on, gn, first_episode, n_episodes, rows));
+    return episode_policy_launch("hp_episode_policy_block", a, on, gn, target, rows, clip_obs, pi_dev, q_pi_dev);
 }
 
 int hp_episode_policy_stats(hp_ctx *ctx, const float *pi_dev, const float *q_pi_dev, const double *actions_dev, const float *q_dev,

@@ -17,87 +17,36 @@
 // the one place that writes them, slab_net in policy_call.h the one that reads them here; hp_agent_set_params / hp_agent_soft_update / hp_state_restore go through k_relayout / k_polyak_frag
 // onto the same buffers).  There is no second copy to go stale: this launch reads those four, the critic's segment at la.total, on the
 // context's stream behind whatever wrote them.
-#include <cmath>
+#include "episode_nets.h"
 
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wundefined-inline"   // agent_device.h declares the 32-row engine's fragment map, which no code here calls
-#include "agent_device.h"
-#pragma clang diagnostic pop
-
-// the 4-row slab's device functions (no kernel of slab8.h is compiled here)
-#define S8_DEVICE_ONLY
-#define S8_NRG 1
-#define S8_NS s8eq
-#include "slab8.h"
-#undef S8_NRG
-#undef S8_NS
-#undef S8_DEVICE_ONLY
-
-#include "episode_audit.h"
-#include "policy_call.h"
-
-// (od / gd / onz / gnz / clip_obs / clip_o / clip_g keep PolicyArgs' names: set_norm_inputs, policy_call.h, fills them by name)
-struct EpisodeQArgs {
-    const double *obs, *g, *act;   // [n][T + 1][od], [n][T][gd], [n][T][ad], already offset to the first episode
+struct EpisodeQArgs : EpisodeNetArgs {   // P.net: the critic's parameter set (the actor's layout P.la goes unread)
+    using Lds = s8en::PolicyLds;
+    const double *act;             // [n][T][ad], already offset to the first episode
     float *q;                      // [n][T]
-    long long rows;                // n T
-    int T, od, gd, ad, act_off;
-    const NormDev *onz, *gnz;
-    double clip_obs, clip_o, clip_g;
-    SlabNetPtrs net;               // forward fragments + canonical arena of the parameter set to evaluate
-    NetLayout lc;
-    int ca, H;                     // the critic's segment starts at ca = la.total
-    float max_action;
 };
 
 __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_episode_q(const EpisodeQArgs A) {
-    __shared__ s8eq::PolicyLds L;
+    __shared__ EpisodeQArgs::Lds L;
     const long long row0 = (long long)blockIdx.x * 4;
-    s8eq::s8_critic_slab(A.net, A.lc, A.ca, A.H, A.rows, L, (size_t)row0,
+    const PolicyArgs &P = A.P;
+    s8en::s8_critic_slab(P.net, A.lc, A.ca, P.H, (long long)P.rows, L, (size_t)row0,
         [&](int r, int c) -> float {
-            const long long m = row0 + r, e = m / A.T;
-            const int t = (int)(m - e * A.T);
-            if (c < A.od)
-                return tr_net_input(A.obs[(e * (A.T + 1) + t) * A.od + c], A.clip_obs, A.onz->mean[c], A.onz->std[c], A.clip_o);
-            if (c < A.od + A.gd) {
-                const int j = c - A.od;
-                return tr_net_input(A.g[m * A.gd + j], A.clip_obs, A.gnz->mean[j], A.gnz->std[j], A.clip_g);
-            }
-            const int j = c - A.act_off;
-            if (j >= 0 && j < A.ad) return (float)A.act[m * A.ad + j] / A.max_action;   // s8_gather, k_pack_scaled_actions
-            return 0.f;
+            const EpisodeRow w = episode_row(row0 + r, A.T);
+            if (c < P.od + P.gd) return episode_state_column(P, w.e * (A.T + 1) + w.t, P.g + w.m * P.gd, c);
+            return episode_action_column(P, A.act, w.m, A.act_off, c);
         },
         [&](int r, float q) { A.q[row0 + r] = q; });
 }
 
 // everything behind the entry's own checks (null arguments, contexts, the block's range): the remaining refusals in the order the
 // header lists them, then the one launch
-static int episode_q_launch(const char *entry, hp_agent *a, hp_norm *on, hp_norm *gn, int32_t net, const double *obs,
-                            const double *g, const double *act, int block_od, int block_gd, int block_ad, int64_t n, int32_t T,
-                            double clip_obs, float *q) {
+static int episode_q_launch(const char *entry, hp_agent *a, hp_norm *on, hp_norm *gn, int32_t net, const EpisodeRows &R, double clip_obs,
+                            float *q) {
     HP_REQUIRE(net == HP_NET_CRITIC || net == HP_NET_CRITIC_TARGET, HP_ERR_INVALID, "%s: net must be a critic", entry);
-    HP_TRY(require_slab_shaped(entry, a, HP_ERR_STATE));
-    HP_REQUIRE(on->size + gn->size == a->xdim, HP_ERR_INVALID, "%s: normalizer sizes %d+%d do not match the critic input %d", entry,
-               (int)on->size, (int)gn->size, a->xdim);
-    HP_REQUIRE(block_od < 0 || (block_od == on->size && block_gd == gn->size && block_ad == a->cfg.act_dim), HP_ERR_INVALID,
-               "%s: the block has dimensions %d / %d / %d, normalizers and agent have %d / %d / %d", entry, block_od, block_gd, block_ad,
-               (int)on->size, (int)gn->size, a->cfg.act_dim);
-    HP_TRY(episode_check_shape(entry, n, T));
-    const long long rows = (long long)n * T;
-    HP_REQUIRE(rows < (1LL << 31), HP_ERR_INVALID, "%s: %lld steps are more than one launch holds (2^31)", entry, rows);
-    static_assert(sizeof(s8eq::PolicyLds) <= 160 * 1024, "the policy slab's LDS fits a CU");
-    EpisodeQArgs A;
-    memset(&A, 0, sizeof(A));
-    A.obs = obs; A.g = g; A.act = act; A.q = q;
-    A.rows = rows; A.T = T;
-    set_norm_inputs(A, norm_view(on), norm_view(gn), clip_or_inf(clip_obs));   // the normalizer half, as PolicyArgs names it
-    A.ad = a->cfg.act_dim; A.act_off = a->act_off;
-    A.net = slab_net(a, net != HP_NET_CRITIC);
-    A.lc = a->lc; A.ca = a->la.total; A.H = a->H;
-    A.max_action = (float)a->cfg.max_action;
-    hipLaunchKernelGGL(k_episode_q, dim3((unsigned)((rows + 3) / 4)), dim3(S8_THREADS), 0, a->ctx->stream, A);
-    HP_CHECK_HIP(hipGetLastError());
-    return HP_OK;
+    EpisodeQArgs A = {};
+    HP_TRY(episode_net_args(entry, a, on, gn, "critic", slab_net(a, net != HP_NET_CRITIC), R, 1, clip_obs, A));
+    A.act = R.act; A.q = q;
+    return episode_net_launch(k_episode_q, a, A);
 }
 
 extern "C" {
@@ -106,20 +55,18 @@ int hp_episode_q(hp_agent *a, hp_norm *on, hp_norm *gn, int32_t net, const doubl
                  const double *actions_dev, int64_t n_episodes, int32_t T, double clip_obs, float *q_dev) {
     HP_REQUIRE(a && on && gn && obs_dev && g_dev && actions_dev && q_dev, HP_ERR_INVALID, "hp_episode_q: null argument");
     HP_SERIALISE(a);
-    HP_REQUIRE(on->ctx == a->ctx && gn->ctx == a->ctx, HP_ERR_INVALID, "hp_episode_q: handles belong to different contexts");
-    return episode_q_launch("hp_episode_q", a, on, gn, net, obs_dev, g_dev, actions_dev, -1, -1, -1, n_episodes, T, clip_obs, q_dev);
+    HP_TRY(episode_one_context("hp_episode_q", a, on, gn));
+    return episode_q_launch("hp_episode_q", a, on, gn, net, EpisodeRows{obs_dev, nullptr, g_dev, actions_dev, -1, -1, -1, n_episodes, T},
+                            clip_obs, q_dev);
 }
 
 int hp_episode_q_block(hp_rollout *ro, hp_agent *a, hp_norm *on, hp_norm *gn, int32_t net, int64_t first_episode, int64_t n_episodes,
                        double clip_obs, float *q_dev) {
     HP_REQUIRE(ro && a && on && gn && q_dev, HP_ERR_INVALID, "hp_episode_q_block: null argument");
     HP_SERIALISE(ro);
-    HP_REQUIRE(a->ctx == ro->ctx && on->ctx == ro->ctx && gn->ctx == ro->ctx, HP_ERR_INVALID,
-               "hp_episode_q_block: handles belong to different contexts");
-    RolloutArrays at;
-    HP_TRY(episode_block_range("hp_episode_q_block", ro, first_episode, n_episodes, at));
-    return episode_q_launch("hp_episode_q_block", a, on, gn, net, at.b_obs, at.b_g, at.b_act, ro->od, ro->gd, ro->ad, n_episodes, ro->T,
-                            clip_obs, q_dev);
+    EpisodeRows rows;
+    HP_TRY(episode_block_rows("hp_episode_q_block", ro, a, on, gn, first_episode, n_episodes, rows));
+    return episode_q_launch("hp_episode_q_block", a, on, gn, net, rows, clip_obs, q_dev);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // policy_call.h -- what a policy call is made of, host side: which parameter set, which normalizer statistics, which clips, the
 // argument block of the policy slab (PolicyArgs, slab8.h) and the refusals every caller shares.  One definition for the policy
-// calls themselves (agent_forward.hip), the rollouts (rollout.hip) and the episode audits (episode_q.hip, episode_policy.hip).
+// calls themselves (agent_forward.hip), the rollouts (rollout.hip) and the episode audits (episode_nets.h: episode_q.hip, episode_policy.hip,
+// episode_action_grad.hip, episode_bellman.hip).
 // Include it behind slab8.h (any slab height, S8_DEVICE_ONLY or not): PolicyArgs and SlabNetPtrs come from there.
 #pragma once
 #include <cmath>
@@ -23,10 +24,9 @@ struct NormView {
 };
 inline NormView norm_view(const hp_norm *n) { return NormView{n->d, n->clip, (int)n->size}; }
 
-// the normalizer half of an argument block that names it od / gd / onz / gnz / clip_obs / clip_o / clip_g (PolicyArgs, EpisodeQArgs);
+// the normalizer half of a PolicyArgs (the one argument block that carries one: the episode audits' kernels carry a PolicyArgs);
 // clip_obs as clip_or_inf returns it
-template <class Args>
-inline void set_norm_inputs(Args &A, const NormView &on, const NormView &gn, double clip_obs) {
+inline void set_norm_inputs(PolicyArgs &A, const NormView &on, const NormView &gn, double clip_obs) {
     A.od = on.size; A.gd = gn.size;
     A.onz = on.d; A.gnz = gn.d;
     A.clip_obs = clip_obs; A.clip_o = on.clip; A.clip_g = gn.clip;

@@ -10,12 +10,13 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, synthetic
 from ._lib import NET_CRITIC, NET_CRITIC_TARGET
 
 
 def _p(t):
-    return C.c_void_p(t.data_ptr())
+    """a device tensor's address; None (an array the call does not take) stays None"""
+    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _upload(agent, episode_batch, who, arrays=4):
@@ -76,14 +77,21 @@ class EpisodeAudit:
 
     # ---- the two network forwards and the policy columns: one place per entry pair.  `episodes`: a DeviceEpisodes, whose
     # episodes [first, first + n) are read in place (the *_block entry); None: the uploaded arrays are (the plain entry)
+    def _entry_pair(self, episodes, block, block_args, plain, plain_args):
+        """One call of an entry pair on torch's current stream: `block(episodes.h, *block_args)` for a DeviceEpisodes, else
+        `plain(*plain_args)`"""
+        with self.ctx.torch_bridge():
+            if episodes is not None:
+                _lib.check(block(episodes.h, *block_args))
+            else:
+                _lib.check(plain(*plain_args))
+
     def _q(self, episodes, first, n, T, target, obs=None, g=None, act=None):
         q = torch.empty((max(n, 0), T), dtype=torch.float32, device=torch.device("cuda", self.ctx.device_id))
         nets = (self.h, self.o_norm.h, self.g_norm.h, NET_CRITIC_TARGET if target else NET_CRITIC)
-        with self.ctx.torch_bridge():
-            if episodes is not None:
-                _lib.check(self.lib.hp_episode_q_block(episodes.h, *nets, first, n, float(self.args.clip_obs), _p(q)))
-            else:
-                _lib.check(self.lib.hp_episode_q(*nets, _p(obs), _p(g), _p(act), n, T, float(self.args.clip_obs), _p(q)))
+        tail = (float(self.args.clip_obs), _p(q))
+        self._entry_pair(episodes, self.lib.hp_episode_q_block, (*nets, first, n, *tail),
+                         self.lib.hp_episode_q, (*nets, _p(obs), _p(g), _p(act), n, T, *tail))
         return q
 
     def _policy(self, episodes, first, n, T, target, obs=None, g=None):
@@ -91,22 +99,17 @@ class EpisodeAudit:
         pi = torch.empty((max(n, 0), T, int(self.env_params['action'])), dtype=torch.float32, device=dev)
         q_pi = torch.empty((max(n, 0), T), dtype=torch.float32, device=dev)
         nets = (self.h, self.o_norm.h, self.g_norm.h, 1 if target else 0)
-        with self.ctx.torch_bridge():
-            if episodes is not None:
-                _lib.check(self.lib.hp_episode_policy_block(episodes.h, *nets, first, n, float(self.args.clip_obs), _p(pi), _p(q_pi)))
-            else:
-                _lib.check(self.lib.hp_episode_policy(*nets, _p(obs), _p(g), n, T, float(self.args.clip_obs), _p(pi), _p(q_pi)))
+        tail = (float(self.args.clip_obs), _p(pi), _p(q_pi))
+        self._entry_pair(episodes, self.lib.hp_episode_policy_block, (*nets, first, n, *tail),
+                         self.lib.hp_episode_policy, (*nets, _p(obs), _p(g), n, T, *tail))
         return pi, q_pi
 
     def _policy_columns(self, episodes, first, pi, q_pi, q, sat, act=None):
         n, T, ad = pi.shape
         stats = torch.empty((n, _lib.POLICY_STATS), dtype=torch.float64, device=q.device)
         tail = (float(self.env_params['action_max']), float(sat), _p(stats))
-        with self.ctx.torch_bridge():
-            if episodes is not None:
-                _lib.check(self.lib.hp_episode_policy_stats_block(episodes.h, _p(pi), _p(q_pi), _p(q), first, n, *tail))
-            else:
-                _lib.check(self.lib.hp_episode_policy_stats(self.ctx.h, _p(pi), _p(q_pi), _p(act), _p(q), n, T, ad, *tail))
+        self._entry_pair(episodes, self.lib.hp_episode_policy_stats_block, (_p(pi), _p(q_pi), _p(q), first, n, *tail),
+                         self.lib.hp_episode_policy_stats, (self.ctx.h, _p(pi), _p(q_pi), _p(act), _p(q), n, T, ad, *tail))
         return stats
 
     def episode_q(self, episodes, target=False, first=0, n=None):
@@ -182,23 +185,17 @@ class EpisodeAudit:
         pi = torch.empty((max(n, 0), T, ad), dtype=torch.float32, device=dev) if at_policy else None
         q = torch.empty((max(n, 0), T), dtype=torch.float32, device=dev)
         nets = (self.h, self.o_norm.h, self.g_norm.h, 1 if target else 0, 0 if at_policy else 1)
-        tail = (float(self.args.clip_obs), _p(pi) if at_policy else None, _p(q), _p(dq_du))
-        with self.ctx.torch_bridge():
-            if episodes is not None:
-                _lib.check(self.lib.hp_episode_action_grad_block(episodes.h, *nets, first, n, *tail))
-            else:
-                _lib.check(self.lib.hp_episode_action_grad(*nets, _p(obs), _p(g), _p(act) if act is not None else None, n, T, *tail))
+        tail = (float(self.args.clip_obs), _p(pi), _p(q), _p(dq_du))
+        self._entry_pair(episodes, self.lib.hp_episode_action_grad_block, (*nets, first, n, *tail),
+                         self.lib.hp_episode_action_grad, (*nets, _p(obs), _p(g), _p(act), n, T, *tail))
         return dq_du, pi, q
 
     def _signal_columns(self, episodes, first, pi, dq_du, flat, act=None):
         n, T, ad = pi.shape
         stats = torch.empty((n, _lib.SIGNAL_STATS), dtype=torch.float64, device=pi.device)
         tail = (float(self.env_params['action_max']), float(self.args.action_l2), float(flat), _p(stats))
-        with self.ctx.torch_bridge():
-            if episodes is not None:
-                _lib.check(self.lib.hp_episode_signal_stats_block(episodes.h, _p(pi), _p(dq_du), first, n, *tail))
-            else:
-                _lib.check(self.lib.hp_episode_signal_stats(self.ctx.h, _p(pi), _p(dq_du), _p(act), n, T, ad, *tail))
+        self._entry_pair(episodes, self.lib.hp_episode_signal_stats_block, (_p(pi), _p(dq_du), first, n, *tail),
+                         self.lib.hp_episode_signal_stats, (self.ctx.h, _p(pi), _p(dq_du), _p(act), n, T, ad, *tail))
         return stats
 
     def episode_action_grad(self, episodes, target=False, at="policy", first=0, n=None):
@@ -238,11 +235,8 @@ class EpisodeAudit:
         q, q_next, r, y = out = tuple(torch.empty((max(n, 0), T), dtype=torch.float32, device=dev) for _ in range(4))
         tail = (float(distance_threshold), _reward_kind(self._arg("reward_type")), float(self.args.clip_obs), *(_p(v) for v in out))
         nets = (self.h, self.o_norm.h, self.g_norm.h, mode)
-        with self.ctx.torch_bridge():
-            if episodes is not None:
-                _lib.check(self.lib.hp_episode_bellman_block(episodes.h, *nets, first, n, *tail))
-            else:
-                _lib.check(self.lib.hp_episode_bellman(*nets, _p(obs), _p(ag), _p(g), _p(act), n, T, *tail))
+        self._entry_pair(episodes, self.lib.hp_episode_bellman_block, (*nets, first, n, *tail),
+                         self.lib.hp_episode_bellman, (*nets, _p(obs), _p(ag), _p(g), _p(act), n, T, *tail))
         return out
 
     def _bellman_columns(self, q, q_next, r, y):
@@ -311,42 +305,49 @@ class EpisodeAudit:
             self._bellman_pending = episodes if span is None else self._column_means(
                 self.lib.hp_episode_bellman_summary, self.episode_bellman_stats(episodes, goal=goal, **span)[0])
 
-    def _record_pending(self, pending, names, host_summary, onto):
+    def _bellman_host_stats(self, eps):
+        """`episode_bellman_stats_host` at the environment's threshold, as the host evaluation takes it, under args.audit_bellman"""
+        thr = self.env.distance_threshold if hasattr(self.env, "distance_threshold") else self._arg("distance_threshold")
+        return self.episode_bellman_stats_host(eps, thr, goal=self._arg("audit_bellman"))
+
+    # an epoch's audit: the pending attribute, the columns and the summary of `synthetic` (the objects themselves: a wrong name fails
+    # when the module is imported), the host path's audit -- looked up on the agent at the call, so that whoever wraps an agent's
+    # `episode_*_stats_host` sees the call -- and the target list
+    _EPOCH_AUDITS = {
+        "policy": ("_policy_audit_pending", synthetic.POLICY_STATS, synthetic.episode_policy_summary,
+                   lambda agent, eps: agent.episode_policy_stats_host(eps), "policy_audit"),
+        "actor_signal": ("_actor_signal_pending", synthetic.SIGNAL_STATS, synthetic.episode_signal_summary,
+                         lambda agent, eps: agent.episode_signal_stats_host(eps), "actor_signal_audit"),
+        "bellman": ("_bellman_pending", synthetic.BELLMAN_STATS, synthetic.episode_bellman_summary,
+                    lambda agent, eps: agent._bellman_host_stats(eps), "bellman_audit"),
+    }
+
+    def _record_epoch_audit(self, which):
         """An epoch's pending audit -- the device path's summary (six means, already computed) or the host path's episodes (audited
-        now: `host_summary(episodes)`) -- averaged over the ranks like the success rate, onto the list; None: nothing is pending"""
+        now) -- averaged over the ranks like the success rate, onto its list; None: nothing is pending"""
+        attr, names, summary, host_stats, onto = self._EPOCH_AUDITS[which]
+        pending = getattr(self, attr)
+        setattr(self, attr, None)
         if pending is not None:
-            _record(self, names, pending.cpu().numpy() if isinstance(pending, torch.Tensor) else host_summary(pending), onto)
+            means = pending.cpu().numpy() if isinstance(pending, torch.Tensor) else summary(host_stats(self, pending)[0])
+            _record(self, names, means, getattr(self, onto))
+
+    def _record_policy_audit(self):
+        """args.audit_policy: the epoch's pending audit (host episodes: `episode_policy_stats_host`) onto `policy_audit`"""
+        self._record_epoch_audit("policy")
 
     def _record_actor_signal_audit(self):
         """args.audit_actor_signal: the epoch's pending audit (host episodes: `episode_signal_stats_host`) onto `actor_signal_audit`"""
-        from .synthetic import SIGNAL_STATS, episode_signal_summary
-        pending, self._actor_signal_pending = self._actor_signal_pending, None
-        self._record_pending(pending, SIGNAL_STATS, lambda eps: episode_signal_summary(self.episode_signal_stats_host(eps)[0]),
-                             self.actor_signal_audit)
+        self._record_epoch_audit("actor_signal")
 
     def _record_bellman_audit(self):
-        """args.audit_bellman: the epoch's pending audit (host episodes: `episode_bellman_stats_host` at the environment's
-        threshold, as the host evaluation takes it) onto `bellman_audit`"""
-        from .synthetic import BELLMAN_STATS, episode_bellman_summary
-        pending, self._bellman_pending = self._bellman_pending, None
-
-        def host_summary(eps):
-            thr = self.env.distance_threshold if hasattr(self.env, "distance_threshold") else self._arg("distance_threshold")
-            return episode_bellman_summary(self.episode_bellman_stats_host(eps, thr, goal=self._arg("audit_bellman"))[0])
-
-        self._record_pending(pending, BELLMAN_STATS, host_summary, self.bellman_audit)
+        """args.audit_bellman: the epoch's pending audit (host episodes: `episode_bellman_stats_host`) onto `bellman_audit`"""
+        self._record_epoch_audit("bellman")
 
     def _record_eval_metrics(self, summary):
         """One evaluation's summary (this rank's six means), averaged over the ranks like the success rate, onto `eval_metrics`"""
         from .synthetic import EPISODE_SUMMARY
         _record(self, EPISODE_SUMMARY, summary, self.eval_metrics)
-
-    def _record_policy_audit(self):
-        """args.audit_policy: the epoch's pending audit (host episodes: `episode_policy_stats_host`) onto `policy_audit`"""
-        from .synthetic import POLICY_STATS, episode_policy_summary
-        pending, self._policy_audit_pending = self._policy_audit_pending, None
-        self._record_pending(pending, POLICY_STATS, lambda eps: episode_policy_summary(self.episode_policy_stats_host(eps)[0]),
-                             self.policy_audit)
 
     def _record_eval_critic(self, summary):
         """One evaluation's critic summary (this rank's six means), averaged over the ranks like the success rate, onto `eval_critic`"""
