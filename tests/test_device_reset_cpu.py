@@ -9,13 +9,12 @@ import pytest
 import torch
 
 from conftest import REPO, bits
+from cpu_common import stream_arrays, synthetic_state
 from kernel_metadata import kernel_metadata
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd import train_state as ts
 from rl_arm_under_sparse_reward_amd.arguments import Args
 from rl_arm_under_sparse_reward_amd.device_env import NativePointMassVecEnv, PointMassVecEnv
-from test_explore_streams_cpu import stream_arrays
-from test_train_state_cpu import synthetic_state
 
 NEW = ("hp_env_reset", "hp_rollout_waves")
 

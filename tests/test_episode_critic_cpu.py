@@ -10,11 +10,11 @@ import numpy as np
 import pytest
 
 from conftest import REPO, bits, load_golden
+from cpu_common import pairs_as_episodes
 from kernel_metadata import kernel_metadata
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd.synthetic import (CRITIC_STATS, episode_critic_stats, episode_critic_summary, episode_returns,
                                                       episode_stats)
-from test_episode_stats_cpu import pairs_as_episodes
 
 
 def along_one_axis(dist, gd=3):

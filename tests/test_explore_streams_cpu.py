@@ -7,22 +7,10 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+from cpu_common import stream_arrays, synthetic_state
 from kernel_metadata import kernel_metadata
 from rl_arm_under_sparse_reward_amd import train_state as ts
 from rl_arm_under_sparse_reward_amd.arguments import Args
-from test_train_state_cpu import synthetic_state
-
-
-def stream_arrays(n, pending=(1,)):
-    """States of RandomState(40 + i) after a few draws; the streams in `pending` hold a cached normal."""
-    keys, pos, has, val = np.empty((n, 624), np.uint32), np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n)
-    for i in range(n):
-        rs = np.random.RandomState(40 + i)
-        rs.randn(3 if i in pending else 4)
-        rs.uniform(size=i)
-        st = rs.get_state()
-        keys[i], pos[i], has[i], val[i] = st[1], st[2], st[3], st[4]
-    return keys, pos, has, val
 
 
 def state_with_streams(n=3):

@@ -3,6 +3,7 @@ wave loop of k_rollout_episodes in csrc/rollout.hip; device_env.NativePointMassV
 bit for bit between two agents built identically on NativePointMassVecEnv: A as it stands (host reset, one launch per wave), B with
 `enable_device_reset()`."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -17,63 +18,27 @@ from rl_arm_under_sparse_reward_amd.ddpg_agent import NET_ACTOR, NET_CRITIC, ddp
 from rl_arm_under_sparse_reward_amd.device_env import (DeviceEpisodes, NativePointMassVecEnv, NativePushBlockVecEnv, PointMassVecEnv,
                                                        binomial1_qn, script_desc)
 from rl_arm_under_sparse_reward_amd.random import DeviceRandomStreams
-from test_gpu_device_rollout import make, primed
-from test_gpu_explore_streams import assert_states_bit_equal
+from rollout_common import (DEV, agent_on as any_agent_on, agent_pair, assert_forms, assert_reset_streams_follow_host,
+                            assert_states_bit_equal, assert_widened_states, collect_both, dev_ptr as p, make, primed)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-p = lambda t: C.c_void_p(t.data_ptr())
-
-
-def agent_on(n_envs, T, streams=True, reset=False, env_seed=10, base=900, before_reset=None, **kw):
-    torch.manual_seed(0)
-    kw.setdefault("noise_eps", 0.05)
-    a = make(NativePointMassVecEnv(n_envs, seed=env_seed, device=DEV, max_timesteps=T), T=T, **kw)
-    primed(a)
-    if streams:
-        a.enable_explore_streams(base_seed=base)
-    if before_reset:
-        before_reset(a)
-    if reset:
-        a.vec_env.enable_device_reset(a.ctx)
-    return a
-
-
-def both(n_envs, T, **kw):
-    """(A: host reset, one launch per wave; B: the same with enable_device_reset())"""
-    return agent_on(n_envs, T, reset=False, **kw), agent_on(n_envs, T, reset=True, **kw)
+agent_on = functools.partial(any_agent_on, NativePointMassVecEnv, env_seed=10)
+# (A: host reset, one launch per wave; B: the same with enable_device_reset())
+both = functools.partial(agent_pair, NativePointMassVecEnv, env_seed=10)
 
 
 def assert_calls_equal(A, B, form="fused", launches=1, **kw):
-    """One collect_episodes_device call on both agents: episode bytes, success flags, the environments stepped last, exploration
-    and reset stream states (B's reset streams against A's host generators)."""
-    flags, got = ([], []), []
-    for a, f in zip((A, B), flags):
-        learner = a.rng.get_state()
-        got.append(a.collect_episodes_device(success_out=f, **kw).numpy())
-        if a.explore_streams is not None or not kw.get("explore", True):
-            assert_states_bit_equal(a.rng.get_state(), learner, "learner stream")
-    assert A.rollout_form == B.rollout_form == form, (A.rollout_form, B.rollout_form, B.rollout_reason)
+    """collect_both, the form, and with the fused form one launch count and one tensor of n_rollouts flags; A's state tensors hold
+    the last wave's rows alone, B's stay [n_envs, 3]; B's reset streams against A's host generators."""
+    got, flags = collect_both(A, B, **kw)
+    assert_forms(A, B, form, form)
     if form == "fused":
         assert B.rollout_launches == launches, B.rollout_launches
-    for name, x, y in zip(("obs", "ag", "g", "actions"), *got):
-        assert x.shape == y.shape and np.array_equal(bits(x), bits(y)), name
-    fa, fb = (torch.cat([f.reshape(-1) for f in fl]) for fl in flags)
-    assert fa.dtype == fb.dtype == torch.float32 and fa.shape == fb.shape and torch.equal(fa, fb)
-    if form == "fused":
         assert len(flags[1]) == 1                                       # one tensor of n_rollouts flags
-    k = B.vec_env.active
-    assert k == A.vec_env.pos.shape[0] == A.vec_env.active
-    for name in ("pos", "vel", "goal"):
-        x, y = getattr(A.vec_env, name), getattr(B.vec_env, name)
-        assert tuple(y.shape) == (B.vec_env.n_envs, 3)
-        assert np.array_equal(bits(x.cpu().numpy()), bits(y[:k].cpu().numpy())), name
-    if A.explore_streams is not None:
-        for i, (x, y) in enumerate(zip(A.explore_streams.get_states(), B.explore_streams.get_states())):
-            assert_states_bit_equal(x, y, ("exploration stream", i))
-    for i, (r, y) in enumerate(zip(A.vec_env.rs, B.vec_env.reset_streams.get_states())):
-        assert_states_bit_equal(r.get_state(), y, ("reset stream", i))
-    return got[1]
+    assert B.vec_env.active == A.vec_env.pos.shape[0]
+    assert_widened_states(B.vec_env, (3, 3, 3))
+    assert_reset_streams_follow_host(A, B)
+    return got
 
 
 # --------------------------------------------------------------------------------------------------- 1. the stand-alone reset

@@ -25,16 +25,10 @@ from rl_arm_under_sparse_reward_amd.arguments import Args
 from rl_arm_under_sparse_reward_amd.ddpg_agent import NET_ACTOR, NET_ACTOR_TARGET, NET_CRITIC, NET_CRITIC_TARGET, ddpg_agent
 from rl_arm_under_sparse_reward_amd.device_env import NativePickPlaceVecEnv, NativePointMassVecEnv, NativePushBlockVecEnv, generate_demos
 from rl_arm_under_sparse_reward_amd.synthetic import SIGNAL_STATS, episode_signal_stats, episode_signal_summary
-from test_gpu_device_rollout import make, primed
-from test_gpu_episode_critic import raw_q, refused
-from test_gpu_episode_policy import move_actor, raw_policy, tree_bytes
-from test_gpu_episode_stats import learner
-from test_gpu_pick_place import agent_on as pick_agent_on
-from test_gpu_push_block import CONTACT, agent_on as push_agent_on
+from episode_common import learner, move_actor, raw_policy, raw_q, refused, tree_bytes
+from rollout_common import CONTACT, DEV, agent_on, dev_ptr as p, make, primed
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
 host = lambda *ts_: [v.cpu().numpy() if v is not None else None for v in ts_]
 GUARD = 4        # rows behind the block in every output: the last slab's dead rows store nothing
 
@@ -179,7 +173,7 @@ def test_dq_du_after_training_cycles_reads_the_stepped_weights():
 # ------------------------------------------------------------------------------------------ 3. the columns
 @pytest.mark.parametrize("T", [10, 70])
 def test_columns_of_exploring_pick_and_place_episodes_equal_the_twin(T):
-    a = move_actor(pick_agent_on(NativePickPlaceVecEnv, 3, T=T, random_eps=0.3), 7)
+    a = move_actor(agent_on(NativePickPlaceVecEnv, 3, T, env_seed=21, random_eps=0.3), 7)
     eps = a.collect_episodes_device(n_rollouts=5, epoch=0)
     actions = eps.numpy()[3]
     stats, dq_du, pi, q_pi = a.episode_signal_stats(eps)
@@ -215,7 +209,7 @@ def test_sub_ranges_of_a_push_block_collection_and_host_episodes():
     """Nine episodes of T = 20 on eight environments: first * T is a multiple of 4 for every `first`, so every sub-range starts
     on a slab boundary of the whole-block call and has its bits.  The same episodes read back and handed in as host arrays go
     through the same kernels: the same bits again."""
-    a = push_agent_on(NativePushBlockVecEnv, 8, env_kw=CONTACT, random_eps=0.3)
+    a = agent_on(NativePushBlockVecEnv, 8, 20, env_seed=21, env_kw=CONTACT, random_eps=0.3)
     eps = a.collect_episodes_device(n_rollouts=9)
     batch = eps.numpy()
     whole = host(*a.episode_signal_stats(eps))

@@ -8,8 +8,6 @@ for a forward, rtol 1e-5 / atol 1e-6, no row excluded; y against the oracle's cl
 1-Lipschitz and gamma < 1).  r is compared bit for bit with compute_reward, y with synthetic.episode_bellman_targets fed the device's
 q_next and r, q with hp_episode_q, q_next with hp_episode_policy(target) one step on, the columns and their summary with the host
 twins."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -25,18 +23,11 @@ from rl_arm_under_sparse_reward_amd.device_env import NativePickPlaceVecEnv, Nat
 from rl_arm_under_sparse_reward_amd.goal_env import GoalDistanceReward
 from rl_arm_under_sparse_reward_amd.synthetic import (BELLMAN_STATS, bellman_constants, episode_bellman_stats, episode_bellman_summary,
                                                       episode_bellman_targets)
-from test_gpu_device_reset import agent_on as point_agent_on
-from test_gpu_device_rollout import make, primed
-from test_gpu_episode_critic import oracle_q, raw_q, refused, shaped_agent
-from test_gpu_episode_policy import move_actor, oracle_policy, raw_policy, tree_bytes
-from test_gpu_episode_stats import learner
-from test_gpu_pick_place import agent_on as pick_agent_on
-from test_gpu_push_block import CONTACT, agent_on as push_agent_on
+from episode_common import learner, move_actor, oracle_policy, oracle_q, raw_policy, raw_q, refused, shaped_agent, tree_bytes
+from rollout_common import CONTACT, DEV, agent_on, dev_ptr as p, make, primed
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 RTOL, ATOL = 1e-5, 1e-6
-p = lambda t: C.c_void_p(t.data_ptr())
 host = lambda *ts_: [v.cpu().numpy() for v in ts_]
 GUARD = 4        # rows behind the block in every output: the last slab's dead rows store nothing
 NAMES = ("q", "q_next", "r", "y")
@@ -181,7 +172,7 @@ def assert_block_equals_plain(a, eps, batch, spans):
 
 
 def test_a_point_mass_collection_in_place():
-    a = move_actor(point_agent_on(2, 10, random_eps=0.3), 3)
+    a = move_actor(agent_on(NativePointMassVecEnv, 2, 10, env_seed=10, random_eps=0.3), 3)
     eps = a.collect_episodes_device(n_rollouts=3)
     final = assert_block_equals_plain(a, eps, eps.numpy(), ((0, None), (1, 2), (2, 1)))
     assert (final[2][:, -1] == 0).all()
@@ -201,13 +192,13 @@ def primed_agent(env, T):
 
 
 def test_a_push_block_collection_in_place():
-    a = move_actor(push_agent_on(NativePushBlockVecEnv, 8, env_kw=CONTACT, random_eps=0.3), 5)
+    a = move_actor(agent_on(NativePushBlockVecEnv, 8, 20, env_seed=21, env_kw=CONTACT, random_eps=0.3), 5)
     eps = a.collect_episodes_device(n_rollouts=9)
     assert_block_equals_plain(a, eps, eps.numpy(), ((0, None), (3, 4), (8, 1), (1, 8)))
 
 
 def test_a_pick_and_place_collection_and_demonstrations_in_place():
-    a = move_actor(pick_agent_on(NativePickPlaceVecEnv, 3, T=10, random_eps=0.3), 7)
+    a = move_actor(agent_on(NativePickPlaceVecEnv, 3, 10, env_seed=21, random_eps=0.3), 7)
     eps = a.collect_episodes_device(n_rollouts=5, epoch=0)
     assert_block_equals_plain(a, eps, eps.numpy(), ((0, None), (2, 3)))
     env = NativePickPlaceVecEnv(4, seed=0, device=DEV, max_timesteps=100, step_scale=0.2)

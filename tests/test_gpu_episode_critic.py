@@ -15,7 +15,6 @@ import torch
 
 from conftest import bits
 from gpu_common import ctx, fresh_rng, make_shape_episodes
-from oracle import ddpg_update as oupd
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd import train_state as ts
 from rl_arm_under_sparse_reward_amd.arguments import Args
@@ -24,46 +23,14 @@ from rl_arm_under_sparse_reward_amd.device_env import (NativePickPlaceVecEnv, Na
                                                        generate_demos)
 from rl_arm_under_sparse_reward_amd.synthetic import (CRITIC_STATS, EPISODE_SUMMARY, episode_critic_stats, episode_critic_summary,
                                                       episode_returns)
-from test_gpu_device_rollout import make, primed
-from test_gpu_episode_stats import learner
-from test_gpu_push_block import CONTACT, agent_on as push_agent_on
+from episode_common import learner, oracle_q, raw_q, refused, shaped_agent
+from rollout_common import CONTACT, DEV, agent_on, dev_ptr as p, make, primed
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 RTOL, ATOL = 1e-5, 1e-6
-p = lambda t: C.c_void_p(t.data_ptr())
 
 
 # ------------------------------------------------------------------------------------------ helpers
-def oracle_q(agent, obs, g, actions, target=False):
-    """The oracle's critic on rows prepared in numpy from the agent's CURRENT parameters (hp_agent_get_params) and normalizer
-    statistics (hp_norm_get): [n, T]"""
-    n, T = g.shape[:2]
-    co, cr = float(agent.args.clip_obs), float(agent.args.clip_range)
-    parts = []
-    for raw, nz in ((obs[:, :T], agent.o_norm), (g, agent.g_norm)):
-        v = np.clip(np.asarray(raw, dtype=np.float64), -co, co)
-        v = (v - nz.mean.astype(np.float64)) / nz.std.astype(np.float64)
-        parts.append(np.clip(v, -cr, cr).astype(np.float32))
-    x = np.concatenate(parts, axis=-1).reshape(n * T, -1)
-    a = np.asarray(actions, dtype=np.float64).astype(np.float32).reshape(n * T, -1)
-    net = agent.critic_target_network if target else agent.critic_network
-    params = {k: v.detach().clone() for k, v in net.state_dict().items()}
-    want = oupd.critic_forward(params, torch.from_numpy(x), torch.from_numpy(a), float(agent.env_params['action_max']))
-    return want.numpy().reshape(n, T), x, a
-
-
-def raw_q(agent, obs, g, actions, target=False):
-    """hp_episode_q on uploaded arrays, into a poisoned tensor, in torch's stream order"""
-    o, gg, a = (torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(DEV) for v in (obs, g, actions))
-    n, T = g.shape[:2]
-    q = torch.full((n, T), float("nan"), dtype=torch.float32, device=DEV)
-    with agent.ctx.torch_bridge():
-        _lib.check(agent.lib.hp_episode_q(agent.h, agent.o_norm.h, agent.g_norm.h, NET_CRITIC_TARGET if target else NET_CRITIC, p(o), p(gg),
-                                          p(a), n, T, float(agent.args.clip_obs), p(q)))
-    return q.cpu().numpy()
-
-
 def assert_q(got, want, what):
     err = np.abs(got.astype(np.float64) - want.astype(np.float64))
     print(f"{what}: max |Q - oracle| {err.max():.3e} on |Q| up to {np.abs(want).max():.3e}")
@@ -81,23 +48,6 @@ def assert_audit(agent, batch, stats, q, returns, thr, target=False, tail="persi
     want = episode_critic_stats(q, want_returns, gamma)
     assert stats.dtype == np.float64 and stats.shape == (q.shape[0], 6) and np.array_equal(bits(stats), bits(want)), (stats, want)
     return want
-
-
-def shaped_agent(obs_dim, goal_dim, act_dim, amax, batch=64, T=20, **kw):
-    """An agent of another shape with random statistics, an online critic moved away from its initialisation and a target made
-    different from it by one soft update"""
-    env = {"obs": obs_dim, "goal": goal_dim, "action": act_dim, "action_max": amax, "max_timesteps": T}
-    torch.manual_seed(0)
-    agent = ddpg_agent(Args(batch_size=batch, buffer_size=8 * T, **kw), None, env, rng=fresh_rng(5))
-    rs = np.random.RandomState(obs_dim)
-    agent.o_norm.set_stats(rs.normal(0.1, 0.3, obs_dim), rs.uniform(0.2, 1.5, obs_dim).astype(np.float32))
-    agent.g_norm.set_stats(rs.normal(0.2, 0.1, goal_dim), rs.uniform(0.2, 1.5, goal_dim).astype(np.float32))
-    flat = agent._get_flat(NET_CRITIC)
-    agent._set_flat(NET_CRITIC, flat * 1.5 + rs.normal(0, 0.01, flat.size).astype(np.float32))
-    agent._soft_update_target_network()
-    assert not np.array_equal(agent._get_flat(NET_CRITIC), agent._get_flat(NET_CRITIC_TARGET))
-    assert not np.array_equal(agent._get_flat(NET_CRITIC_TARGET), flat)
-    return agent
 
 
 SHAPES = [(1, 1), (5, 3), (3, 63), (2, 64), (3, 65), (7, 100)]     # rows no multiple of 4, slabs that straddle episodes, T / T + 1 strides
@@ -161,7 +111,7 @@ def test_q_after_training_cycles_reads_the_stepped_weights(batch):
 def test_sub_ranges_of_a_push_block_collection():
     """Nine episodes of T = 20 on eight environments.  first * T is a multiple of 4 for every `first`, so every sub-range starts
     on a slab boundary of the whole-block call; a block of T = 5 has sub-ranges that do not."""
-    a = push_agent_on(NativePushBlockVecEnv, 8, env_kw=CONTACT, random_eps=0.3)
+    a = agent_on(NativePushBlockVecEnv, 8, 20, env_seed=21, env_kw=CONTACT, random_eps=0.3)
     eps = a.collect_episodes_device(n_rollouts=9)
     batch = eps.numpy()
     whole = a.episode_q(eps).cpu().numpy()
@@ -259,7 +209,7 @@ def test_every_rollout_form_on_the_push_block_environment(form):
     """Seven evaluation episodes on four environments: stepped on the tensor twin, fused per wave on the native environment, all
     waves in one launch with the reset on the device; the online and the target critic."""
     cls = PushBlockVecEnv if form == "stepped" else NativePushBlockVecEnv
-    a = push_agent_on(cls, 4, env_kw=CONTACT, reset=(form == "waves"))
+    a = agent_on(cls, 4, 20, env_seed=21, env_kw=CONTACT, reset=(form == "waves"))
     eps = a.collect_episodes_device(n_rollouts=7, explore=False)
     assert a.rollout_form == ("stepped" if form == "stepped" else "fused") and (form != "waves" or a.rollout_launches == 1)
     batch, thr = eps.numpy(), a.vec_env.distance_threshold
@@ -399,12 +349,6 @@ def test_eval_critic_on_the_host_path():
 
 
 # ------------------------------------------------------------------------------------------ 7. refusals
-def refused(status, text, code=-1):
-    assert status == code, status
-    with pytest.raises(ValueError if code == -1 else _lib.HpError, match=text):
-        _lib.check(status)
-
-
 def test_refusals_carry_the_librarys_message(monkeypatch):
     torch.manual_seed(0)
     a = make(NativePointMassVecEnv(2, seed=1, device=DEV, max_timesteps=10), T=10)

@@ -8,7 +8,6 @@ on the ORACLE's action, the whole chain on the host) on inputs prepared in numpy
 episode_q.  The columns and their summary are compared bit for bit with the host twins (synthetic.episode_policy_stats /
 episode_policy_summary): their orders are fixed."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -16,7 +15,6 @@ import torch
 
 from conftest import bits
 from gpu_common import ctx, fresh_rng, make_shape_episodes
-from oracle import ddpg_update as oupd
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd import train_state as ts
 from rl_arm_under_sparse_reward_amd.arguments import Args
@@ -24,49 +22,16 @@ from rl_arm_under_sparse_reward_amd.ddpg_agent import NET_ACTOR, NET_ACTOR_TARGE
 from rl_arm_under_sparse_reward_amd.device_env import (NativePickPlaceVecEnv, NativePointMassVecEnv, NativePushBlockVecEnv, PushBlockVecEnv,
                                                        generate_demos)
 from rl_arm_under_sparse_reward_amd.synthetic import POLICY_STATS, episode_policy_stats, episode_policy_summary
-from test_gpu_device_rollout import make, primed
-from test_gpu_episode_critic import oracle_q, refused, shaped_agent
-from test_gpu_episode_stats import learner
-from test_gpu_pick_place import agent_on as pick_agent_on
-from test_gpu_push_block import CONTACT, agent_on as push_agent_on
+from episode_common import learner, move_actor, oracle_policy, raw_policy, refused, shaped_agent, tree_bytes
+from rollout_common import CONTACT, DEV, agent_on, dev_ptr as p, make, primed
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 RTOL, ATOL = 1e-5, 1e-6
 NAN = np.uint64(0x7FF8000000000000)
-p = lambda t: C.c_void_p(t.data_ptr())
 host = lambda *ts_: [v.cpu().numpy() for v in ts_]
 
 
 # ------------------------------------------------------------------------------------------ helpers
-def oracle_policy(agent, obs, g, target=False):
-    """The oracle's actor, and its critic on that action, on rows prepared in numpy from the agent's CURRENT parameters
-    (hp_agent_get_params) and normalizer statistics: (pi [n, T, act], q_pi [n, T])"""
-    n, T = g.shape[:2]
-    amax = float(agent.env_params['action_max'])
-    _, x, _ = oracle_q(agent, obs, g, np.zeros((n, T, int(agent.env_params['action']))), target)
-    actor = agent.actor_target_network if target else agent.actor_network
-    critic = agent.critic_target_network if target else agent.critic_network
-    pa = {k: v.detach().clone() for k, v in actor.state_dict().items()}
-    pc = {k: v.detach().clone() for k, v in critic.state_dict().items()}
-    xt = torch.from_numpy(x)
-    pi = oupd.actor_forward(pa, xt, amax)
-    q_pi = oupd.critic_forward(pc, xt, pi, amax)
-    return pi.numpy().reshape(n, T, -1), q_pi.numpy().reshape(n, T), x
-
-
-def raw_policy(agent, obs, g, target=False):
-    """hp_episode_policy on uploaded arrays, into poisoned tensors, in torch's stream order"""
-    o, gg = (torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(DEV) for v in (obs, g))
-    n, T = g.shape[:2]
-    pi = torch.full((n, T, int(agent.env_params['action'])), float("nan"), dtype=torch.float32, device=DEV)
-    q_pi = torch.full((n, T), float("nan"), dtype=torch.float32, device=DEV)
-    with agent.ctx.torch_bridge():
-        _lib.check(agent.lib.hp_episode_policy(agent.h, agent.o_norm.h, agent.g_norm.h, 1 if target else 0, p(o), p(gg), n, T,
-                                               float(agent.args.clip_obs), p(pi), p(q_pi)))
-    return pi.cpu().numpy(), q_pi.cpu().numpy()
-
-
 def assert_close(got, want, what):
     err = np.abs(got.astype(np.float64) - want.astype(np.float64))
     print(f"{what}: max |device - oracle| {err.max():.3e} on values up to {np.abs(want).max():.3e}")
@@ -78,18 +43,6 @@ def assert_close(got, want, what):
 def assert_policy(agent, obs, g, pi, q_pi, what, target=False):
     want_pi, want_q, x = oracle_policy(agent, obs, g, target)
     return assert_close(pi, want_pi, what + ": pi"), assert_close(q_pi, want_q, what + ": Q(s, pi(s))"), x
-
-
-def move_actor(agent, seed):
-    """An online actor moved away from its initialisation (far enough that some tanh saturate) and a target actor made different
-    from it by one soft update"""
-    rs = np.random.RandomState(seed)
-    flat = agent._get_flat(NET_ACTOR)
-    agent._set_flat(NET_ACTOR, flat * 1.5 + rs.normal(0, 0.01, flat.size).astype(np.float32))
-    agent._soft_update_target_network()
-    assert not np.array_equal(agent._get_flat(NET_ACTOR), agent._get_flat(NET_ACTOR_TARGET))
-    assert not np.array_equal(agent._get_flat(NET_CRITIC), agent._get_flat(NET_CRITIC_TARGET))
-    return agent
 
 
 def twin_of(agent, stats, pi, q_pi, q, actions, sat=0.99):
@@ -170,7 +123,7 @@ def test_noise_free_episodes_give_back_their_own_actions_and_q(form):
     slab and this launch's run the same device functions on the same bits -- native observations lie inside clip_obs -- so pi is
     the recorded action, Q(s, pi(s)) is episode_q's Q(s, a), and three columns are exactly 0."""
     cls = PushBlockVecEnv if form == "stepped" else NativePushBlockVecEnv
-    a = push_agent_on(cls, 4, env_kw=CONTACT, reset=(form == "waves"))
+    a = agent_on(cls, 4, 20, env_seed=21, env_kw=CONTACT, reset=(form == "waves"))
     eps = a.collect_episodes_device(n_rollouts=7, explore=False, epoch=0)
     assert a.rollout_form == ("stepped" if form == "stepped" else "fused") and (form != "waves" or a.rollout_launches == 1)
     obs, _, g, actions = eps.numpy()
@@ -205,7 +158,7 @@ def raw_stats(c, pi, q_pi, actions, q, amax, sat):
 def test_columns_of_exploring_pick_and_place_episodes_equal_the_twin(T):
     """Less than a chunk of steps, exactly one, one more, and a third chunk; five episodes on three environments with their
     exploration streams; with and without Q(s, a); the default bound of saturation, two that bite and both ends."""
-    a = move_actor(pick_agent_on(NativePickPlaceVecEnv, 3, T=T, random_eps=0.3), 7)
+    a = move_actor(agent_on(NativePickPlaceVecEnv, 3, T, env_seed=21, random_eps=0.3), 7)
     eps = a.collect_episodes_device(n_rollouts=5, epoch=0)
     actions = eps.numpy()[3]
     stats, pi, q_pi, q = a.episode_policy_stats(eps)
@@ -239,7 +192,7 @@ def block_policy(a, eps, first, n, rows):
 def test_sub_ranges_of_a_push_block_collection():
     """Nine episodes of T = 20 on eight environments.  first * T is a multiple of 4 for every `first`, so every sub-range starts
     on a slab boundary of the whole-block call; a block of T = 5 has sub-ranges that do not."""
-    a = push_agent_on(NativePushBlockVecEnv, 8, env_kw=CONTACT, random_eps=0.3)
+    a = agent_on(NativePushBlockVecEnv, 8, 20, env_seed=21, env_kw=CONTACT, random_eps=0.3)
     eps = a.collect_episodes_device(n_rollouts=9)
     batch = eps.numpy()
     whole = host(*a.episode_policy(eps))
@@ -292,7 +245,7 @@ def test_the_q_filter_rate_of_pick_and_place_demonstrations():
 
 def test_host_episodes_through_the_same_kernels():
     """Episodes collected on the device, read back and handed in as host arrays: the same bits as the block's own audit"""
-    a = move_actor(pick_agent_on(NativePickPlaceVecEnv, 3, T=30, random_eps=0.3), 7)
+    a = move_actor(agent_on(NativePickPlaceVecEnv, 3, 30, env_seed=21, random_eps=0.3), 7)
     eps = a.collect_episodes_device(n_rollouts=5, epoch=0)
     batch = eps.numpy()
     for target, sat in ((False, 0.99), (True, 0.5)):
@@ -311,14 +264,6 @@ def test_host_episodes_through_the_same_kernels():
 
 
 # ------------------------------------------------------------------------------------------ 7. learn()
-def tree_bytes(root):
-    out = {}
-    for d, _, files in os.walk(root):
-        for f in files:
-            out[os.path.relpath(os.path.join(d, f), root)] = open(os.path.join(d, f), "rb").read()
-    return out
-
-
 def test_audit_policy_is_the_twins_and_changes_nothing_else(tmp_path, capsys):
     """Two epochs of learn() on two native environments with the option on and off (eval_metrics and eval_critic on in both): the
     same rates, metrics, printed lines, checkpoint files, training state and streams to the byte, an empty list with it off; with it

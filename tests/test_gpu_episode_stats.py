@@ -2,7 +2,6 @@
 DeviceEpisodes.stats, DeviceDemos.stats, collect_episodes_device(stats_out=), ddpg_agent.episode_stats_host, args.eval_metrics)
 against the host twin synthetic.episode_stats / episode_stats_summary.  Every comparison is bit for bit: the kernel's reductions
 are order independent and the summary's order is fixed."""
-import ctypes as C
 import shutil
 
 import numpy as np
@@ -10,21 +9,18 @@ import pytest
 import torch
 
 from conftest import bits, load_golden
+from cpu_common import pairs_as_episodes
 from gpu_common import ctx, make_shape_episodes
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd import train_state as ts
 from rl_arm_under_sparse_reward_amd.ddpg_agent import NET_ACTOR, NET_CRITIC
-from rl_arm_under_sparse_reward_amd.device_env import NativePickPlaceVecEnv, NativePointMassVecEnv, NativePushBlockVecEnv, generate_demos
+from rl_arm_under_sparse_reward_amd.device_env import (NativePickPlaceVecEnv, NativePointMassVecEnv, NativePushBlockVecEnv, PointMassVecEnv,
+                                                       generate_demos)
 from rl_arm_under_sparse_reward_amd.synthetic import EPISODE_SUMMARY, episode_stats, episode_stats_summary
-from test_episode_stats_cpu import pairs_as_episodes
-from test_gpu_device_reset import agent_on as reset_agent_on
-from test_gpu_device_rollout import make, primed
-from test_gpu_fused_rollout import pair
-from test_gpu_push_block import CONTACT, agent_on as push_agent_on
+from episode_common import learner
+from rollout_common import CONTACT, DEV, agent_on, agent_pair, dev_ptr as p, make
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-p = lambda t: C.c_void_p(t.data_ptr())
 
 
 def device_stats(ag, g, thr, steps=True):
@@ -113,7 +109,7 @@ def test_pairs_within_a_few_ulp_of_the_threshold():
 def test_a_sub_range_of_a_push_block_collection():
     """Nine episodes on eight environments (two waves) with contact-frequent parameters; episodes [3, 7) into rows [3, 7) of a
     poisoned tensor."""
-    a = push_agent_on(NativePushBlockVecEnv, 8, env_kw=CONTACT, random_eps=0.3)
+    a = agent_on(NativePushBlockVecEnv, 8, 20, env_seed=21, env_kw=CONTACT, random_eps=0.3)
     eps = a.collect_episodes_device(n_rollouts=9)
     thr = a.vec_env.distance_threshold
     out = torch.full((9, 6), float("nan"), dtype=torch.float64, device=DEV)
@@ -142,8 +138,8 @@ def test_all_three_rollout_forms_hand_out_the_same_stats(explore):
     """Stepped on the tensor twin, fused per wave on the native environment, all waves in one launch with the reset on the
     device: seven episodes on four environments, identically built agents."""
     T = 20
-    plain, native = pair(4, T)
-    waves = reset_agent_on(4, T, reset=True)
+    plain, native = agent_pair((PointMassVecEnv, NativePointMassVecEnv), 4, T, env_seed=10)
+    waves = agent_on(NativePointMassVecEnv, 4, T, env_seed=10, reset=True)
     got = []
     for a, form in ((plain, "stepped"), (native, "fused"), (waves, "fused")):
         flags, stats = [], []
@@ -159,7 +155,7 @@ def test_all_three_rollout_forms_hand_out_the_same_stats(explore):
     assert np.array_equal(bits(got[0]), bits(got[1])) and np.array_equal(bits(got[1]), bits(got[2]))
     assert (got[0][:, 2] <= got[0][:, 1]).all() and (got[0][:, 1] > 0).all()
     # without stats_out nothing is handed out and the episodes are the same
-    again = pair(4, T)[1]
+    again = agent_on(NativePointMassVecEnv, 4, T, env_seed=10)
     same = again.collect_episodes_device(n_rollouts=7, explore=explore).numpy()
     for x, y in zip(same, native._rollouts[7].numpy()):
         assert np.array_equal(bits(x), bits(y))
@@ -197,17 +193,6 @@ def test_host_episodes_through_the_same_kernel():
 
 
 # ------------------------------------------------------------------------------------------ 7. evaluation metrics in learn()
-def learner(tmp_path, name, reset, state_path=None, **kw):
-    torch.manual_seed(0)
-    np.random.seed(11)
-    env = NativePointMassVecEnv(2, seed=10, device=DEV, max_timesteps=10, distance_threshold=0.15)
-    a = make(env, T=10, seed=5, n_epochs=2, n_cycles=2, n_batches=2, n_test_rollouts=5, buffer_episodes=40, noise_eps=0.05,
-             explore_streams=True, device_reset=reset, save_dir=str(tmp_path / name), env_name="pm", **kw)
-    a.args.state_path = state_path
-    primed(a)
-    return a
-
-
 def evaluation_episodes(a):
     """The calls of _eval_agent_device made by hand: (ag, g) of the evaluation episodes, in order"""
     ags, gs, remaining = [], [], int(a.args.n_test_rollouts)

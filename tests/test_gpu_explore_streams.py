@@ -2,29 +2,21 @@
 random.DeviceRandomStreams, ddpg_agent.enable_explore_streams): every stream against its own numpy RandomState to the last word,
 independence of the width, the same bits as the single-stream kernel for the same stream, the closed loop against n host workers,
 the training state, and the refusals.  Everything goes through the C ABI."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from conftest import bits
-from gpu_common import ctx, fresh_rng
+from gpu_common import ctx, fresh_rng, host_select_actions, ulp_distance
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd.device_env import DeviceEpisodes, PointMassVecEnv, binomial1_qn
 from rl_arm_under_sparse_reward_amd.random import DeviceRandomStreams
 from rl_arm_under_sparse_reward_amd.replay_buffer import DeviceEpisodeBuffer
 from rl_arm_under_sparse_reward_amd.synthetic import PointMassGoalEnv
-from test_gpu_device_rollout import host_select_actions, make, primed, ulp_distance
+from rollout_common import DEV, assert_states_bit_equal, dev_ptr as p, make, primed
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NET_ACTOR = 0
-p = lambda t: C.c_void_p(t.data_ptr())
-
-
-def assert_states_bit_equal(a, b, where):
-    assert np.array_equal(a[1], b[1]) and a[2:4] == b[2:4] and np.float64(a[4]).tobytes() == np.float64(b[4]).tobytes(), where
 
 
 # --------------------------------------------------------------------------------------------------------------- 1. seeding

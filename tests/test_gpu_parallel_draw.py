@@ -227,7 +227,7 @@ def test_the_fused_learner_never_takes_the_parallel_draw():
     """hp_agent_update_kernels names exactly the kernels the launch-log test pins for the parent (UPDATE_KLOG), whatever the mode;
     updates draw their plans with the learner's own kernels and count nothing."""
     import torch
-    from test_gpu_update import UPDATE_KLOG, make_agent
+    from update_common import UPDATE_KLOG, make_agent
 
     def run(mode):
         torch.manual_seed(0)

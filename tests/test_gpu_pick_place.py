@@ -5,6 +5,7 @@ against the per-step form on start states with open fingers inside the cube and 
 the reset on the device against the host reset, generated demonstrations against synthetic.scripted_demos, the refusals, and the
 training state.  Every comparison is bit for bit."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -14,34 +15,20 @@ from conftest import bits
 from gpu_common import ctx
 from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd.ddpg_agent import NET_ACTOR, NET_CRITIC
-from rl_arm_under_sparse_reward_amd.device_env import (DeviceEpisodes, NativePickPlaceVecEnv, NativePushBlockVecEnv, PickPlaceVecEnv, _NativeEnv,
-                                                       generate_demos, script_desc)
+from rl_arm_under_sparse_reward_amd.device_env import (DeviceEpisodes, NativePickPlaceVecEnv, PickPlaceVecEnv, _NativeEnv, generate_demos,
+                                                       script_desc)
 from rl_arm_under_sparse_reward_amd.replay_buffer import DeviceEpisodeBuffer
-from rl_arm_under_sparse_reward_amd.synthetic import (PICK_FINGER_MAX, PICK_TOOL, DemoScript, PickPlaceGoalEnv, PickScript, PushBlockGoalEnv,
+from rl_arm_under_sparse_reward_amd.synthetic import (PICK_FINGER_MAX, PICK_TOOL, DemoScript, PickPlaceGoalEnv, PickScript,
                                                       pick_scripted_action, scripted_demos, scripted_episode)
-from test_gpu_device_rollout import make, primed
-from test_gpu_explore_streams import assert_states_bit_equal
+from rollout_common import (DEV, NAMES, agent_on as any_agent_on, assert_forms, assert_reset_streams_follow_host, assert_rows_equal,
+                            assert_same_as_host, assert_states_bit_equal, assert_widened_states, collect_both, dev_ptr as p, twins)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 T = 12
-p = lambda t: C.c_void_p(t.data_ptr())
+agent_on = functools.partial(any_agent_on, T=T, env_seed=21)
 SHORT = PickScript(phase_end=(1, 4, 6, 9, 10), open=0.5)      # all six phases inside T = 12
 SHORT_PUSH = DemoScript(phase_end=(1, 2, 3, 4, 5))
 WIDTHS = (3, 3, 3, 8)
-NAMES = ("obs", "ag", "g", "actions", "info")
-
-
-def host_state(h):
-    if isinstance(h, PushBlockGoalEnv):
-        return {"grip": h.grip, "blk": h.blk, "goal": h.goal, "vel": np.concatenate([h.gvel, h.bvel])}
-    return {"grip": h.grip, "blk": h.blk, "goal": h.goal, "aux": np.concatenate([h.gvel, h.bvel, [h.finger, h.held]])}
-
-
-def assert_rows_equal(env, hosts, k, where):
-    for i, h in enumerate(hosts[:k]):
-        for name, v in host_state(h).items():
-            assert np.array_equal(bits(getattr(env, name)[i].cpu().numpy()), bits(v)), (where, i, name)
 
 
 # ----------------------------------------------------------------------------- 1., 2. the twins, per step: resets and steps
@@ -109,38 +96,6 @@ class NativeSeededPickPlaceVecEnv(_NativeEnv, SeededPickPlaceVecEnv):
     kind = _lib.ENV_PICK_PLACE
 
 
-def agent_on(cls, n_envs, T=T, streams=True, reset=False, env_seed=21, base=900, env_kw=None, net_seed=0, **kw):
-    torch.manual_seed(net_seed)
-    kw.setdefault("noise_eps", 0.05)
-    a = make(cls(n_envs, seed=env_seed, device=DEV, max_timesteps=T, **(env_kw or {})), T=T, **kw)
-    primed(a)
-    if streams:
-        a.enable_explore_streams(base_seed=base)
-    if reset:
-        a.vec_env.enable_device_reset(a.ctx)
-    return a
-
-
-def collect_both(X, Y, **kw):
-    """One collect_episodes_device call on both agents: (episodes of Y, flags), everything compared bit for bit"""
-    flags, got = ([], []), []
-    for a, f in zip((X, Y), flags):
-        got.append(a.collect_episodes_device(success_out=f, **kw).numpy())
-    for name, x, y in zip(NAMES, *got):
-        assert x.shape == y.shape and np.array_equal(bits(x), bits(y)), name
-    fx, fy = (torch.cat([f.reshape(-1) for f in fl]) for fl in flags)
-    assert fx.dtype == fy.dtype == torch.float32 and fx.shape == fy.shape and torch.equal(fx, fy)
-    k = Y.vec_env.active
-    assert k == X.vec_env.active
-    for name in X.vec_env.state_names:
-        x, y = getattr(X.vec_env, name), getattr(Y.vec_env, name)
-        assert np.array_equal(bits(x[:k].cpu().numpy()), bits(y[:k].cpu().numpy())), name
-    if X.explore_streams is not None:
-        for i, (x, y) in enumerate(zip(X.explore_streams.get_states(), Y.explore_streams.get_states())):
-            assert_states_bit_equal(x, y, ("exploration stream", i))
-    return got[1], fy
-
-
 @pytest.mark.parametrize("explore", [False, True])
 @pytest.mark.parametrize("n_envs,n_rollouts", [(1, 1), (3, 3), (5, 5), (5, 8)])
 def test_fused_wave_equals_the_per_step_path_on_seeded_grasps(n_envs, n_rollouts, explore):
@@ -152,7 +107,7 @@ def test_fused_wave_equals_the_per_step_path_on_seeded_grasps(n_envs, n_rollouts
     plain, native = (agent_on(cls, n_envs, env_kw=env_kw, random_eps=0.3) for cls in (SeededPickPlaceVecEnv, NativeSeededPickPlaceVecEnv))
     before = native.explore_streams.get_states()
     (obs, ag, g, actions), flags = collect_both(plain, native, n_rollouts=n_rollouts, explore=explore)
-    assert plain.rollout_form == "stepped" and native.rollout_form == "fused", (plain.rollout_form, native.rollout_form, native.rollout_reason)
+    assert_forms(plain, native, "stepped", "fused")
     assert native.rollout_launches == -(-n_rollouts // n_envs)
     assert np.array_equal(ag, obs[:, :, 12:15]) and np.array_equal(obs[:, :, 18:21], obs[:, :, 12:15] - obs[:, :, 0:3])
     assert not obs[:, :, 3:6].any() and not obs[:, :, 11].any() and not obs[:, :, 15:18].any() and not obs[:, :, 24:27].any()
@@ -185,10 +140,8 @@ def test_all_waves_in_one_launch_equal_one_launch_per_wave(min_separation, env_s
         got, flags = collect_both(A, B, n_rollouts=n_rollouts)
         assert A.rollout_form == B.rollout_form == "fused" and B.rollout_launches == 1 and A.rollout_launches == -(-n_rollouts // 3)
         assert B.vec_env.active == (n_rollouts - 1) % 3 + 1
-        for name, width in zip(B.vec_env.state_names, WIDTHS):
-            assert tuple(getattr(B.vec_env, name).shape) == (3, width)
-        for i, (r, y) in enumerate(zip(A.vec_env.rs, B.vec_env.reset_streams.get_states())):
-            assert_states_bit_equal(r.get_state(), y, ("reset stream", i))
+        assert_widened_states(B.vec_env, WIDTHS)
+        assert_reset_streams_follow_host(A, B)
         spent += A.vec_env.reset_attempts
     print("attempts of the last reset of each environment:", spent)
     if min_separation == 0.5:
@@ -198,36 +151,12 @@ def test_all_waves_in_one_launch_equal_one_launch_per_wave(min_separation, env_s
 
 
 # ------------------------------------------------------------------------------------------- 5. generated demonstrations
-def twins(kind, n_envs, seed, **kw):
-    """(host environments, the native device environment with its reset on the device), seeded alike"""
-    host_cls, dev_cls = {"pick": (PickPlaceGoalEnv, NativePickPlaceVecEnv), "push": (PushBlockGoalEnv, NativePushBlockVecEnv)}[kind]
-    hosts = [host_cls(seed=seed + i, max_timesteps=T, **kw) for i in range(n_envs)]
-    env = dev_cls(n_envs, seed=seed, device=DEV, max_timesteps=T, **kw)
-    env.enable_device_reset(ctx())
-    return hosts, env
-
-
-def assert_same_as_host(hosts, env, demos, want):
-    *arrays, attempted = want
-    assert demos.kept == arrays[0].shape[0] == len(demos) and demos.attempted == attempted
-    got = demos.numpy()
-    assert len(got) == 5
-    for name, x, y in zip(NAMES, got, arrays):
-        assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(bits(x), bits(y)), name
-    if demos.kept:
-        assert isinstance(demos.episodes, DeviceEpisodes) and len(demos.episodes) == demos.kept and np.all(got[4][:, -1] == 1.0)
-    states = env.reset_streams.get_states()
-    for i, h in enumerate(hosts):
-        assert_states_bit_equal(h.rs.get_state(), states[i], ("reset stream", i))
-    assert_rows_equal(env, hosts, len(hosts), "final state")
-
-
 @pytest.mark.parametrize("n_envs,launch_cap,launches", [(1, None, 1), (5, None, 1), (5, T, 2)])
 def test_pick_demos_equal_the_host_generator(n_envs, launch_cap, launches):
     """The short schedule at step_scale 0.6, T = 12, seeds from 0: rounds of two waves until four episodes are kept -- some are
     kept and some rejected on the way (the host says which) -- with the environment's own default script type; a launch cap of
     T timesteps makes two launches of every round."""
-    hosts, env = twins("pick", n_envs, 0, step_scale=0.6, min_separation=0.3)
+    hosts, env = twins("pick", n_envs, 0, T, step_scale=0.6, min_separation=0.3)
     assert isinstance(env.default_demo_script(), PickScript)
     want = scripted_demos(hosts, 4, 2, max_episodes=40, script=SHORT)
     demos = generate_demos(env, 4, round_waves=2, max_episodes=40, script=SHORT, launch_cap=launch_cap)
@@ -243,12 +172,12 @@ def test_pick_demos_equal_the_host_generator(n_envs, launch_cap, launches):
 def test_the_default_script_of_the_environment_is_the_pick_schedule():
     """script=None on the new kind runs PickScript() (at T = 12: lift, then approach; nothing is kept), on the push block the
     push schedule as before"""
-    hosts, env = twins("pick", 3, 5)
+    hosts, env = twins("pick", 3, 5, T)
     want = scripted_demos(hosts, 2, 1, max_episodes=3, script=PickScript())
     demos = generate_demos(env, 2, round_waves=1, max_episodes=3)
     assert demos.kept == 0 and demos.attempted == 3 and demos.launches == 1
     assert_same_as_host(hosts, env, demos, want)
-    hosts, env = twins("push", 3, 5)
+    hosts, env = twins("push", 3, 5, T)
     want = scripted_demos(hosts, 2, 1, max_episodes=3)
     demos = generate_demos(env, 2, round_waves=1, max_episodes=3)
     assert_same_as_host(hosts, env, demos, want)
@@ -259,7 +188,7 @@ def test_the_default_script_of_the_environment_is_the_pick_schedule():
 def test_either_controller_runs_on_either_kind(kind, script, kw):
     """The push schedule on the pick-and-place kind and the pick schedule on the push block, through the entry that matches the
     script's type: bit for bit the host's.  Kept or not, every attempted episode is compared: n_demos is out of reach."""
-    hosts, env = twins(kind, 5, 21, **kw)
+    hosts, env = twins(kind, 5, 21, T, **kw)
     c, n = ctx(), 8
     shape = DeviceEpisodeBuffer(1, T, 27, 3, 4, ctx=c)
     block = DeviceEpisodes(c, shape, n)
@@ -287,7 +216,7 @@ def test_either_controller_runs_on_either_kind(kind, script, kw):
 def test_refusals_carry_the_entrys_own_name():
     c, n = ctx(), 4
     lib = c.lib
-    _, env = twins("pick", n, 21)
+    _, env = twins("pick", n, 21, T)
     shape = DeviceEpisodeBuffer(1, T, 27, 3, 4, ctx=c)
     block = DeviceEpisodes(c, shape, 8)
     success = torch.zeros(8, dtype=torch.float32, device=DEV)

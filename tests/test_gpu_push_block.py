@@ -3,6 +3,7 @@ instantiated in csrc/env_push_block.hip, device_env.NativePushBlockVecEnv): the 
 one launch per wave against the per-step form on the torch twin, all waves in one launch with the reset on the device against one
 launch per wave with the host reset, the training state, and the refusals.  Every comparison is bit for bit."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -15,15 +16,12 @@ from rl_arm_under_sparse_reward_amd import train_state as ts
 from rl_arm_under_sparse_reward_amd.arguments import Args
 from rl_arm_under_sparse_reward_amd.ddpg_agent import NET_ACTOR, NET_CRITIC, ddpg_agent
 from rl_arm_under_sparse_reward_amd.device_env import DeviceEpisodes, NativePushBlockVecEnv, PushBlockVecEnv, binomial1_qn
-from test_gpu_device_rollout import make, primed
-from test_gpu_explore_streams import assert_states_bit_equal
+from rollout_common import (CONTACT, DEV, agent_on as any_agent_on, agent_pair, assert_forms, assert_reset_streams_follow_host,
+                            assert_states_bit_equal, assert_widened_states, collect_both, dev_ptr as p)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 T = 20
-p = lambda t: C.c_void_p(t.data_ptr())
-# parameters under which a random policy touches the block every few steps (a 4 cm block is rarely touched at all)
-CONTACT = dict(half_width=0.15, z_touch=0.6, step_scale=0.3)
+agent_on = functools.partial(any_agent_on, T=T, env_seed=21)
 PARAMS = {"default": {}, "contact": CONTACT}
 # Contact-heavy cases whose episodes miss a branch with the seeds of the others (environments from 21, networks from 0): what they
 # are built with instead.  Keys: ("wave", n_envs, n_rollouts, explore, epoch).
@@ -36,18 +34,6 @@ SEEDS = {
     ("wave", 4, 7, False, 0): dict(env_seed=32),
     ("wave", 4, 7, False, 100): dict(env_seed=32),
 }
-
-
-def agent_on(cls, n_envs, T=T, streams=True, reset=False, env_seed=21, base=900, env_kw=None, net_seed=0, **kw):
-    torch.manual_seed(net_seed)
-    kw.setdefault("noise_eps", 0.05)
-    a = make(cls(n_envs, seed=env_seed, device=DEV, max_timesteps=T, **(env_kw or {})), T=T, **kw)
-    primed(a)
-    if streams:
-        a.enable_explore_streams(base_seed=base)
-    if reset:
-        a.vec_env.enable_device_reset(a.ctx)
-    return a
 
 
 def setup(params, case):
@@ -64,29 +50,6 @@ def assert_contact_coverage(obs):
     print(f"contact coverage: {x} timesteps pushed along x, {y} along y, {still} without contact, of {bvel.shape[0] * bvel.shape[1]}")
     assert x > 0 and y > 0 and still > 0, (x, y, still)
     assert not bvel[..., 2].any()
-
-
-def collect_both(X, Y, **kw):
-    """One collect_episodes_device call on both agents: (episodes of X, of Y, flags of X, of Y), the learner's stream untouched"""
-    flags, got = ([], []), []
-    for a, f in zip((X, Y), flags):
-        learner = a.rng.get_state()
-        got.append(a.collect_episodes_device(success_out=f, **kw).numpy())
-        if a.explore_streams is not None or not kw.get("explore", True):
-            assert_states_bit_equal(a.rng.get_state(), learner, "learner stream")
-    for name, x, y in zip(("obs", "ag", "g", "actions"), *got):
-        assert x.shape == y.shape and np.array_equal(bits(x), bits(y)), name
-    fx, fy = (torch.cat([f.reshape(-1) for f in fl]) for fl in flags)
-    assert fx.dtype == fy.dtype == torch.float32 and fx.shape == fy.shape and torch.equal(fx, fy)
-    k = Y.vec_env.active
-    assert k == X.vec_env.active
-    for name in X.vec_env.state_names:
-        x, y = getattr(X.vec_env, name), getattr(Y.vec_env, name)
-        assert np.array_equal(bits(x[:k].cpu().numpy()), bits(y[:k].cpu().numpy())), name
-    if X.explore_streams is not None:
-        for i, (x, y) in enumerate(zip(X.explore_streams.get_states(), Y.explore_streams.get_states())):
-            assert_states_bit_equal(x, y, ("exploration stream", i))
-    return got[1], flags
 
 
 # --------------------------------------------------------------------------------------------------- 1. the stand-alone reset
@@ -163,7 +126,7 @@ def test_fused_wave_equals_the_per_step_path(n_envs, n_rollouts, explore, epoch,
     plain, native = (agent_on(cls, n_envs, env_kw=env_kw, **kw) for cls in (PushBlockVecEnv, NativePushBlockVecEnv))
     before = native.explore_streams.get_states()
     (obs, ag, g, actions), flags = collect_both(plain, native, n_rollouts=n_rollouts, explore=explore, epoch=epoch)
-    assert plain.rollout_form == "stepped" and native.rollout_form == "fused", (plain.rollout_form, native.rollout_form, native.rollout_reason)
+    assert_forms(plain, native, "stepped", "fused")
     assert len(flags[0]) == len(flags[1]) == -(-n_rollouts // n_envs)
     assert np.array_equal(ag, obs[:, :, 12:15]) and np.array_equal(obs[:, :, 18:21], obs[:, :, 12:15] - obs[:, :, 0:3])
     assert not obs[:, :, 3:6].any() and not obs[:, :, 9:12].any() and not obs[:, :, 15:18].any() and not obs[:, :, 24:27].any()
@@ -176,19 +139,16 @@ def test_fused_wave_equals_the_per_step_path(n_envs, n_rollouts, explore, epoch,
 
 
 # ------------------------------------------------------------------- 3. all waves in one launch, the reset on the device
-def both(n_envs, T=T, **kw):
-    """(A: host reset, one launch per wave; B: the same with enable_device_reset())"""
-    return (agent_on(NativePushBlockVecEnv, n_envs, T=T, reset=False, **kw), agent_on(NativePushBlockVecEnv, n_envs, T=T, reset=True, **kw))
+# (A: host reset, one launch per wave; B: the same with enable_device_reset())
+both = functools.partial(agent_pair, NativePushBlockVecEnv, T=T, env_seed=21)
 
 
 def assert_calls_equal(A, B, launches=1, **kw):
     got, flags = collect_both(A, B, **kw)
-    assert A.rollout_form == B.rollout_form == "fused", (A.rollout_form, B.rollout_form, B.rollout_reason)
+    assert_forms(A, B, "fused", "fused")
     assert B.rollout_launches == launches and len(flags[1]) == 1, B.rollout_launches
-    for name, width in zip(B.vec_env.state_names, (3, 3, 3, 6)):
-        assert tuple(getattr(B.vec_env, name).shape) == (B.vec_env.n_envs, width)
-    for i, (r, y) in enumerate(zip(A.vec_env.rs, B.vec_env.reset_streams.get_states())):
-        assert_states_bit_equal(r.get_state(), y, ("reset stream", i))
+    assert_widened_states(B.vec_env, (3, 3, 3, 6))
+    assert_reset_streams_follow_host(A, B)
     return got
 
 

@@ -11,21 +11,9 @@ from oracle.running_norm import RunningNorm
 from rl_arm_under_sparse_reward_amd.arguments import Args
 from rl_arm_under_sparse_reward_amd.ddpg_agent import ddpg_agent
 from rl_arm_under_sparse_reward_amd.synthetic import PointMassGoalEnv
+from rollout_common import make, primed
 
 pytestmark = pytest.mark.gpu
-
-
-def make(envs, T=50, seed=3, **kw):
-    args = Args(batch_size=256, buffer_size=200 * T, **kw)
-    env_params = envs[0].env_params if envs else PointMassGoalEnv(max_timesteps=T).env_params
-    return ddpg_agent(args, (envs if len(envs) > 1 else envs[0]) if envs else None, env_params, rng=fresh_rng(seed))
-
-
-def primed(agent, seed=0):
-    rs = np.random.RandomState(seed)
-    agent.o_norm.update(rs.normal(0.2, 0.3, size=(400, 27))); agent.o_norm.recompute_stats()
-    agent.g_norm.update(rs.normal(0.25, 0.1, size=(400, 3))); agent.g_norm.recompute_stats()
-    return rs
 
 
 @pytest.mark.parametrize("engine", ["", "RLARM_ENGINE=layers"])       # fused policy kernel | layer-per-launch fallback
@@ -36,7 +24,7 @@ def test_act_equals_preproc_plus_actor_and_tracks_oracle(rows, engine, monkeypat
     if engine:
         monkeypatch.setenv(*engine.split("="))
     torch.manual_seed(0)
-    agent = make([])
+    agent = make(None)
     rs = primed(agent)
     obs = rs.normal(0.2, 0.6, size=(rows, 27)); obs[0, :3] = [40.0, -40.0, 0.2]     # exercises the +-5 clip
     g = rs.normal(0.25, 0.2, size=(rows, 3))

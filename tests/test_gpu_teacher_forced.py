@@ -50,6 +50,7 @@ from rl_arm_under_sparse_reward_amd.arguments import Args
 from rl_arm_under_sparse_reward_amd.ddpg_agent import (NET_ACTOR, NET_ACTOR_TARGET, NET_CRITIC, NET_CRITIC_TARGET,
                                                         ddpg_agent)
 from rl_arm_under_sparse_reward_amd.synthetic import make_episodes
+from update_common import HP, HP_ENV, expect_engine, set_launch
 
 pytestmark = pytest.mark.gpu
 LOSS_RTOL = 1e-5
@@ -339,38 +340,9 @@ def test_every_update_meets_the_bar_through_the_data_parallel_optimizer(transpor
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# The same bars away from the reference's defaults.  Every hyperparameter the learner reads, as in
-# tests/golden/ddpg_update_hparams.npz (tools/gen_golden.py DDPG_HPARAMS): gamma 0.9 (clip_return 10), action_l2 0.5,
-# unequal learning rates (a swapped per-element rate selection in an optimizer kernel is invisible at 1e-3 / 1e-3),
-# polyak 0.9, and clips that bite -- clip_obs 0.8 clips ~16% of the raw values, clip_range 1.5 ~17% of the normalised ones;
-# action_max 0.7 is not a power of two, so a dropped or reordered division by it is not exact.
-HP = dict(gamma=0.9, action_l2=0.5, lr_actor=3e-4, lr_critic=2e-3, polyak=0.9, clip_range=1.5, clip_obs=0.8)
-HP_ENV = dict(ENV_PARAMS, action_max=0.7)
+# The same bars away from the reference's defaults (update_common.HP, HP_ENV), through the launch structures of
+# update_common.LAUNCH.
 CASE_STEPS = 12              # polyak every 4 steps: later steps see targets that differ from the online nets
-
-# launch structures of one update: switch name -> environment read by hp_agent_create
-LAUNCH = {"default": {}, "split": {"RLARM_SPLIT": "1"}, "slab8_rows8": {"RLARM_SLAB_ROWS": "8"},
-          "slab8_rows16": {"RLARM_SLAB_ROWS": "16"}, "slab32": {"RLARM_ENGINE": "slab32"}, "dw64": {"RLARM_DW64": "s3"},
-          "adam_unfused": {"RLARM_FUSE_ADAM": "0"}, "layers": {"RLARM_ENGINE": "layers"},
-          "slab32_dw64": {"RLARM_ENGINE": "slab32", "RLARM_DW64": "s3"}}
-
-
-def _launch(name, monkeypatch):
-    monkeypatch.setenv("RLARM_KEEP_GRADS", "1")
-    for kk, v in LAUNCH[name].items():
-        monkeypatch.setenv(kk, v)
-
-
-def _expect_engine(agent, launch, engine):
-    """The engine a case is about, asserted, so that a change of the default table cannot move the case elsewhere silently."""
-    e = agent.engine()
-    assert e["engine"] == engine, (launch, e)
-    first = agent.update_kernels(1)["updates"][0][0]
-    if launch == "split":
-        assert first.startswith("k_fb_split8"), (launch, first)
-    elif engine == "slab8":
-        assert first == "k_fb_slab8", (launch, first)
-    return e
 
 
 def _report(tag, worst, agent, n_steps, extra=""):
@@ -385,9 +357,9 @@ def _report(tag, worst, agent, n_steps, extra=""):
                                     "layers"])
 def test_every_update_meets_the_bar_at_other_hyperparameters(launch, monkeypatch):
     """Case A: HP at 27/3/4, batch 256, through every launch structure of the update."""
-    _launch(launch, monkeypatch)
+    set_launch(launch, monkeypatch)
     worst, agent, _ = _run(256, 4, n_steps=CASE_STEPS, hp=HP, env_params=HP_ENV, polyak_every=4)
-    _expect_engine(agent, launch, {"slab32": "slab32", "layers": "layers"}.get(launch, "slab8"))
+    expect_engine(agent, launch, {"slab32": "slab32", "layers": "layers"}.get(launch, "slab8"))
     _report(f"hparams {launch} batch 256", worst, agent, CASE_STEPS)
 
 
@@ -396,7 +368,7 @@ def test_every_update_meets_the_bar_at_other_hyperparameters(launch, monkeypatch
                                           (2080, 4, ("slab32", 32, "dw64 split 3"))])
 def test_every_update_meets_the_bar_at_other_hyperparameters_ragged(batch, k, want, monkeypatch):
     """Case A, ragged batches on the default table: padding rows, 1/B, the dw64 slices of a batch that is no multiple of 64."""
-    _launch("default", monkeypatch)
+    set_launch("default", monkeypatch)
     worst, agent, _ = _run(batch, k, n_steps=CASE_STEPS, hp=HP, env_params=HP_ENV, polyak_every=4)
     e = agent.engine()
     assert (e["engine"], e["slab_rows"], e["weight_grad"]) == want, e
@@ -443,11 +415,11 @@ def _clamp_branches(i, side, mb):
 def test_every_update_meets_the_bar_on_both_clamp_branches(launch, monkeypatch):
     """Case B: gamma 0.5 puts clip_return at 2; the target critic's head is spread so that every minibatch has rows clamped
     at -2 AND rows clamped at 0 (>= 5% each, asserted in float64 on the taught state, so the case cannot pass vacuously)."""
-    _launch(launch, monkeypatch)
+    set_launch(launch, monkeypatch)
     hp = dict(HP, gamma=0.5)
     worst, agent, side = _run(256, 4, n_steps=CASE_STEPS, hp=hp, env_params=HP_ENV, polyak_every=4,
                               before_step=_spread_target_q, on_minibatch=_clamp_branches)
-    _expect_engine(agent, launch, {"slab32": "slab32", "layers": "layers"}.get(launch, "slab8"))
+    expect_engine(agent, launch, {"slab32": "slab32", "layers": "layers"}.get(launch, "slab8"))
     _report(f"clamp branches {launch}", worst, agent, CASE_STEPS,
             f", rows clamped at -clip_return >= {side.branch_min[0]:.2f}, at 0 >= {side.branch_min[1]:.2f}")
 
@@ -467,10 +439,10 @@ SHAPE_CASES = [(s, "default") for s in SHAPES] + [(s, launch) for s in SHAPES if
 def test_every_update_meets_the_bar_at_other_env_shapes(shape, launch, monkeypatch):
     """Case C: GoalEnv shapes other than 27/3/4, default hyperparameters, 24 episodes of 50 steps."""
     o, g, a, amax, engine = shape
-    _launch(launch, monkeypatch)
+    set_launch(launch, monkeypatch)
     env = {"obs": o, "goal": g, "action": a, "action_max": amax, "max_timesteps": 50}
     worst, agent, _ = _run(256, 4, n_steps=CASE_STEPS, n_eps=24, env_params=env, polyak_every=4)
-    _expect_engine(agent, launch, "slab32" if launch == "slab32" else engine)
+    expect_engine(agent, launch, "slab32" if launch == "slab32" else engine)
     _report(f"shape {o}/{g}/{a} action_max {amax} {launch}", worst, agent, CASE_STEPS)
 
 
@@ -546,10 +518,10 @@ def test_every_update_meets_the_bar_at_other_hidden_widths(case, monkeypatch):
     the HER sampler refuses goals of 8 or more components (her.py: bit-exact rewards are only claimed below numpy's pairwise
     summation), so the goal has 7 and the observation the normalizers' 256; the padded widths are the same 272 and 288."""
     hidden, batch, env, n_eps, seed = WIDTH_CASES[case]
-    _launch("default", monkeypatch)
+    set_launch("default", monkeypatch)
     worst, agent, _ = _run(batch, 4, n_steps=CASE_STEPS, n_eps=n_eps, hp=HP, env_params=dict(env, hidden=hidden), polyak_every=4,
                            torch_seed=seed)
-    _expect_engine(agent, "default", "layers")
+    expect_engine(agent, "default", "layers")
     assert agent.actor_network.fc2.weight.shape == (hidden, hidden) and agent.critic_network.fc1.weight.shape[0] == hidden
     _report(f"width {case} hidden {hidden} batch {batch} input {env['obs']}/{env['goal']}/{env['action']}", worst, agent, CASE_STEPS)
 
@@ -582,9 +554,9 @@ def test_polyak_folded_into_the_last_update_at_other_polyak(launch, monkeypatch)
     expression of k_polyak_frag), p_new being the device's own post-step parameters; then, with the targets left as the
     cycle wrote them, one more update against the oracle loaded from the device's state meets the loss bar, which it
     cannot if the folded write reached the arena but not the forward-fragment copy the next update's target chains read."""
-    _launch(launch, monkeypatch)
+    set_launch(launch, monkeypatch)
     worst, agent, side = _run(256, 4, n_steps=4, hp=HP, env_params=HP_ENV, polyak_every=4, spare_eps=4)
-    _expect_engine(agent, launch, "slab32" if launch == "slab32_dw64" else "layers" if launch == "layers" else "slab8")
+    expect_engine(agent, launch, "slab32" if launch == "slab32_dw64" else "layers" if launch == "layers" else "slab8")
     learner, p = side.learner, np.float32(side.args.polyak)
     _teach(agent, learner)
     t_old = {s: agent._get_flat(s) for s in (NET_ACTOR_TARGET, NET_CRITIC_TARGET)}

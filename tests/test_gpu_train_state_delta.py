@@ -15,7 +15,7 @@ from rl_arm_under_sparse_reward_amd import train_state as ts
 from rl_arm_under_sparse_reward_amd.arguments import Args
 from rl_arm_under_sparse_reward_amd.ddpg_agent import ddpg_agent
 from rl_arm_under_sparse_reward_amd.synthetic import make_episodes
-from test_gpu_train_state import EPS_PER_CYCLE, N_BATCHES, assert_same, build, cycles, episodes, fingerprint
+from train_state_common import EPS_PER_CYCLE, N_BATCHES, assert_same, build, cycles, episodes, fingerprint
 
 pytestmark = pytest.mark.gpu
 

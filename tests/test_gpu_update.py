@@ -16,15 +16,10 @@ from rl_arm_under_sparse_reward_amd.arguments import Args
 from rl_arm_under_sparse_reward_amd.ddpg_agent import (NET_ACTOR, NET_ACTOR_TARGET, NET_CRITIC, NET_CRITIC_TARGET,
                                                         ddpg_agent)
 from rl_arm_under_sparse_reward_amd.synthetic import episode_checksum, make_episodes
+from update_common import UPDATE_KLOG, klog, make_agent
 
 pytestmark = pytest.mark.gpu
 LOSS_RTOL = 1e-5
-
-
-def make_agent(batch=256, n_eps=64, seed=125, replay_k=4, env_params=None, **kw):
-    args = Args(batch_size=batch, buffer_size=n_eps * 100, replay_k=replay_k, **kw)
-    rng = fresh_rng(seed)
-    return ddpg_agent(args, None, dict(env_params or ENV_PARAMS), rng=rng), rng
 
 
 def close(a, b, atol):
@@ -576,12 +571,6 @@ def _run_cycles(agent, n_cycles=3, n_batches=4, graph=False):
             agent.last_losses(n_cycles * n_batches), agent.o_norm.mean, agent.g_norm.std)
 
 
-def klog(open_, updates, close=(), prologue=()):
-    """The dict update_kernels returns, from runs of identical updates: updates = [(kernels, count), ...]."""
-    return {"open": list(open_), "prologue": list(prologue), "updates": [list(k) for k, c in updates for _ in range(c)],
-            "close": list(close)}
-
-
 # update_kernels(4) per transport and reduction, the whole log
 PEER_END = ["k_peer_seq_end"]
 WORLD1_KLOG = {
@@ -997,28 +986,6 @@ def test_a_failing_deferred_update_names_itself_and_stays_owed():
     empty.buffer.store_episode(make_episodes(2, seed=11, mode="walk"))
     empty._update_network(2)
     assert np.isfinite(empty.last_losses(2)).all()
-
-
-# The whole launch log of a sequence, per engine shape and switch.
-UPDATE_KLOG = {
-    ("", 256, 40): klog(["k_draw_plan"], [(["k_fb_split8<0>", "k_gemm_lds_adam"], 40)], prologue=["k_fb_split8<0>"]),
-    ("", 256, 4): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds_adam"], 4)]),
-    ("", 256, 1): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds_adam"], 1)]),
-    ("RLARM_SPLIT=0", 256, 40): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds_adam"], 40)]),
-    ("RLARM_SPLIT=1", 256, 4): klog(["k_draw_plan"], [(["k_fb_split8<0>", "k_gemm_lds_adam"], 4)], prologue=["k_fb_split8<0>"]),
-    ("RLARM_SPLIT=1", 256, 1): klog(["k_draw_plan"], [(["k_fb_split8<0>", "k_gemm_lds_adam"], 1)], prologue=["k_fb_split8<0>"]),
-    # the last update has nothing left to draw or gather: no riders
-    ("", 512, 40): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds_adam_ride_u"], 39), (["k_fb_slab8", "k_gemm_lds_adam_u"], 1)]),
-    ("", 1024, 40): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds_adam_ride"], 39), (["k_fb_slab8", "k_gemm_lds_adam"], 1)]),
-    ("", 2048, 40): klog(["k_draw_plan"], [(["k_fb_slab8", "k_dw64_adam"], 40)]),
-    ("", 4096, 40): klog(["k_draw_plan"], [(["k_gather_fused", "k_fb_slab32", "k_dw64_adam"], 1), (["k_fb_slab32", "k_dw64_adam"], 39)]),
-    ("RLARM_ENGINE=layers", 256, 4): klog(["k_draw_plan"], [(["k_gather_fused"] + ["k_gemm_lds"] * 16, 4)]),
-    ("RLARM_FUSE_ADAM=0", 256, 4): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds", "k_adam_frag4"], 4)]),
-    ("RLARM_FUSE_ADAM=0", 1024, 4): klog(["k_draw_plan"], [(["k_fb_slab8", "k_gemm_lds_ride", "k_adam_frag4"], 3),
-                                                           (["k_fb_slab8", "k_gemm_lds", "k_adam_frag4"], 1)]),
-    ("RLARM_FUSE_ADAM=0", 4096, 4): klog(["k_draw_plan"], [(["k_gather_fused", "k_fb_slab32", "k_dw64", "k_adam_frag4"], 1),
-                                                           (["k_fb_slab32", "k_dw64", "k_adam_frag4"], 3)]),
-}
 
 
 @pytest.mark.parametrize("switch,batch,n_updates", [

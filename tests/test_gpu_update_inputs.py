@@ -46,8 +46,7 @@ from rl_arm_under_sparse_reward_amd import _lib
 from rl_arm_under_sparse_reward_amd.arguments import Args
 from rl_arm_under_sparse_reward_amd.ddpg_agent import ddpg_agent
 from rl_arm_under_sparse_reward_amd.synthetic import make_episodes
-from test_gpu_her import _pairs_as_one_step_episodes, _threshold_pairs
-from test_gpu_teacher_forced import HP, HP_ENV, _expect_engine, _launch
+from update_common import HP, HP_ENV, expect_engine, pairs_as_one_step_episodes, set_launch, threshold_pairs
 
 pytestmark = pytest.mark.gpu
 SPLIT_MIN_UPDATES = 12      # agent.h: the shortest sequence that takes the split form by itself
@@ -182,9 +181,9 @@ def test_every_launch_form_gathers_the_oracles_minibatch(launch, monkeypatch):
     """27/3/4, batch 256, max_action 0.7, clip_obs 0.8, clip_range 1.5: sequences of 1 (in-chain gather into set 0), 2 (gather
     ahead into set 1) and 3 updates (gather ahead back into set 0, over the first update's rows) on one agent; the default table
     also runs the shortest sequence that takes the split form by itself."""
-    _launch(launch, monkeypatch)
+    set_launch(launch, monkeypatch)
     agent, side = _make(256, HP_ENV, 64, make_episodes(64, seed=3, mode="walk"))
-    _expect_engine(agent, launch, {"slab32": "slab32", "layers": "layers"}.get(launch, "slab8"))
+    expect_engine(agent, launch, {"slab32": "slab32", "layers": "layers"}.get(launch, "slab8"))
     fresh = agent.debug_inputs(1)
     assert not fresh["XA"].any() and not fresh["R"].any() and (fresh["Mp"], fresh["ldx"], fresh["act_off"]) == (256, 48, 32)
     for n in (1, 2, 3):
@@ -206,7 +205,7 @@ def test_ragged_batches_gather_every_live_row_and_leave_the_padding_zero(batch, 
     of s8_gather_ahead's per = ceil(B / ng) rows that is short and no multiple of its 4 rows in flight (ng = 4 beside the
     chains: per 2, 113, 129, 321; ng = 64 in k_dw64_adam at 2080: per 33).  Rows B .. Mp - 1 of XA, of the gathered columns of XP and
     XT and of R are +0 after every sequence (the expected arrays hold +0 there)."""
-    _launch("default", monkeypatch)
+    set_launch("default", monkeypatch)
     agent, side = _make(batch, HP_ENV, 64, make_episodes(64, seed=3, mode="walk"))
     e = agent.engine()
     assert (e["engine"], e["slab_rows"], e["weight_grad"]) == want, e
@@ -237,10 +236,10 @@ def test_other_env_shapes_gather_the_oracles_minibatch(shape, launch, monkeypatc
     """GoalEnv shapes at which a lane's role in the gathers changes (statistics hoisted per lane, the action block's offset,
     the reward's operand lanes), batch 136 (no multiple of 32: 24 padded rows; per = 34), 24 episodes of 50 steps."""
     od, gd, ad, engine = shape
-    _launch(launch, monkeypatch)
+    set_launch(launch, monkeypatch)
     env = _env(od, gd, ad, 50)
     agent, side = _make(136, env, 24, make_shape_episodes(24, od, gd, ad, 50, seed=3))
-    _expect_engine(agent, launch, "slab32" if launch == "slab32" else engine)
+    expect_engine(agent, launch, "slab32" if launch == "slab32" else engine)
     d = agent.debug_inputs(0)
     assert (d["xdim"], d["act_off"], d["Mp"]) == (od + gd, -(-(od + gd) // 16) * 16, 160)
     seen_r = set()
@@ -267,25 +266,25 @@ def test_one_step_episodes_and_a_single_stored_episode():
 @pytest.mark.parametrize("launch", ["default", "split", "slab32", "layers"])
 @pytest.mark.parametrize("pairs", ["golden_gd3", "radius_gd1", "radius_gd5"])
 def test_reward_bits_on_the_success_radius_through_the_in_launch_gathers(pairs, launch, monkeypatch):
-    """The pairs within a few ulps of the 0.05 radius (tests/golden/reward_adversarial.npz, gd 3; _threshold_pairs for gd 1 and
+    """The pairs within a few ulps of the 0.05 radius (tests/golden/reward_adversarial.npz, gd 3; threshold_pairs for gd 1 and
     5) as one-step episodes, future_p = 0: every R[m] an update launch leaves must be r_bits[e_m], e_m from the oracle's draw,
     for the gather of a sequence's first update AND for the gather ahead (sequences of 2 updates: set 0 = s8_gather /
     k_gather_fused, set 1 = s8_gather_ahead; layers: sequences of 1, k_gather_fused only).  Each of the two must meet at least
     99 % of the stored pairs: ceil(5.5 M / B) sequences give an expected 99.6 % (checked on the CPU for these seeds)."""
-    _launch(launch, monkeypatch)
+    set_launch(launch, monkeypatch)
     if pairs == "golden_gd3":
         gold = load_golden("reward_adversarial.npz")
         ag, g, r_bits, od, ad = gold["ag"], gold["g"], gold["r_bits"], 27, 4
         assert ag.shape == (4096, 3)
     else:
         gd = int(pairs[-1])
-        (ag, g, r_bits), od, ad = _threshold_pairs(gd), 12, 3
+        (ag, g, r_bits), od, ad = threshold_pairs(gd), 12, 3
     M, gd = ag.shape
     batch = 256 if launch == "split" else 1024
-    agent, side = _make(batch, _env(od, gd, ad, 1), M, _pairs_as_one_step_episodes(ag, g, od, ad), replay_k=0,
+    agent, side = _make(batch, _env(od, gd, ad, 1), M, pairs_as_one_step_episodes(ag, g, od, ad), replay_k=0,
                         prime=(0.1, 0.35, 0.15, 0.1))
     assert side.fp == 0.0
-    _expect_engine(agent, launch, {"slab32": "slab32", "layers": "layers"}.get(launch, "slab8"))
+    expect_engine(agent, launch, {"slab32": "slab32", "layers": "layers"}.get(launch, "slab8"))
     n = 1 if launch == "layers" else 2
     met = np.zeros((n, M), bool)
     for _ in range(-(-11 * M // (2 * batch))):
@@ -310,7 +309,7 @@ def test_a_cycles_updates_gather_the_oracles_minibatches(mode, monkeypatch):
     scatters, updates the normalizers and draws the first plans, as a cached hipGraph that later cycles replay -- the sets are
     what a replayed graph leaves.  eager_calls: the same cycle call by call on plain launches (RLARM_UPDATE_GRAPH=0), plans from
     k_draw_plan.  The oracle side is that of test_updates_track_oracle_over_a_cycle."""
-    _launch("default", monkeypatch)
+    set_launch("default", monkeypatch)
     graph = mode == "cycle_graph"
     monkeypatch.setenv("RLARM_UPDATE_GRAPH", "1" if graph else "0")
     agent, side = _make(256, HP_ENV, 16, make_episodes(16, seed=9, mode="walk"), seed=11)
