@@ -792,6 +792,8 @@ __device__ __forceinline__ void s8_l2_warm(const FbSlabArgs &P, int widx, float 
     s8_l2_warm_at(P, P.xcd_split ? (int)((blockIdx.x & 7) >> 2) : 2, P.n_pref >> 3, widx >> 3, sink);
 }
 
+#include "slab8_chain.h"   // segments that more than one chain body runs
+
 #ifndef S8_DEVICE_ONLY   // a translation unit that only borrows the device functions (rollout.hip) compiles no kernel of this file
 // OUT_WT: store policy of both chains' outputs ("store policy" at the top of this file): nothing in this launch loads them.
 // The body of k_fb_slab8 (write-through, the default) and k_fb_slab8_plain (RLARM_ENGINE=chain_plain) below.
@@ -943,22 +945,8 @@ __device__ __forceinline__ void fb_slab8_body(const FbSlabArgs &P) {
         }
         s8_sync();
         S8_TSTAMP(tl, 18);
-        // ---- critic loss (ddpg_agent.py:255-263)
         float keep_g = 0.f, keep_a = 0.f;
-        if (tid < S8_ROWS) {
-            const size_t m = row0 + tid;
-            float g = 0.f, sq = 0.f;
-            if ((int)m < Bk.B) {
-                float y = rows[2][tid] + Bk.gamma * rows[0][tid];
-                y = fminf(fmaxf(y, -Bk.clip_ret), 0.f);
-                const float d = y - rows[1][tid];
-                sq = d * d;
-                g = -2.f * d * invB;
-            }
-            sq = s8_rows_sum_to_lane0(sq);
-            keep_g = g;
-            keep_a = sq;
-        }
+        if (tid < S8_ROWS) s8_critic_loss(tid, rows, row0, Bk, invB, keep_g, keep_a);
         s8_head_bwd_inplace_td(rows, (int)row0, Bk.B, Bk.gamma, Bk.clip_ret, invB, w4c, bufA);   // bufA holds h3 of critic(x, a)
         s8_sync();
         S8_TSTAMP(tl, 19);

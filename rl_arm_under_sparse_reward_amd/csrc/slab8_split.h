@@ -309,22 +309,8 @@ __device__ __forceinline__ void fb_split8_body(unsigned long long r0, unsigned l
         }
         s8_sync();
         S8_TSTAMP(tl, 18);
-        // ---- critic loss (ddpg_agent.py:255-263)
         float keep_g = 0.f, keep_a = 0.f;
-        if (tid < S8_ROWS) {
-            const size_t m = row0 + tid;
-            float g = 0.f, sq = 0.f;
-            if ((int)m < Bk.B) {
-                float y = rows[2][tid] + Bk.gamma * rows[0][tid];
-                y = fminf(fmaxf(y, -Bk.clip_ret), 0.f);
-                const float d = y - rows[1][tid];
-                sq = d * d;
-                g = -2.f * d * invB;
-            }
-            sq = s8_rows_sum_to_lane0(sq);
-            keep_g = g;
-            keep_a = sq;
-        }
+        if (tid < S8_ROWS) s8_critic_loss(tid, rows, row0, Bk, invB, keep_g, keep_a);
         s8_head_bwd_inplace_td(rows, (int)row0, Bk.B, Bk.gamma, Bk.clip_ret, invB, w4c, bufA);   // bufA holds h3 of critic(x, a)
         s8_sync();
         S8_TSTAMP(tl, 19);
